@@ -2,7 +2,7 @@
 """
 bench.py -- training-points/sec of the VarNet variational-loss step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--no-cpu-baseline] [--dump-outputs DIR]
         (N > 1: starts its own N ranks, one per GPU, before anything touches the GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -17,6 +17,10 @@ training set.  With N > 1 ranks the SAME 100 000 test functions are sharded cont
 (strong scaling, BASELINE cfg 4) and the flat gradient is all-reduced over RCCL.
 
 Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed, as a caller of the step receives
+it, to DIR/<name>.npy (float32; see OUTPUT_NAMES).  The inputs are fixed by the arguments, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -31,6 +35,12 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 PEAK_FP32_MFMA_TFLOPS = 157.3      # MI355X_MICROARCH.md: Peak FP32 (matrix), dense
+
+# --dump-outputs: what a step (vn_train_epoch: gradient, SUM all-reduce, Adam) leaves for its caller
+OUTPUT_NAMES = {'params': 'flat network parameters after the last timed step\'s Adam update [P]',
+                'grad': 'd loss / d theta of the last timed step, at its pre-update parameters, summed over ranks [P]',
+                'loss_terms': 'loss, BC loss, IC loss, variational loss of the last timed step, pre-update [4]'}
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 # which files determine the code of a profiled kernel (the instantiation's name starts with the key): its translation unit, every
@@ -628,6 +638,22 @@ def mor_epoch_line(epochs, warmup, cal=None):
     return out
 
 
+def dump_outputs(dirname, arrays):
+    """Write every array of `arrays` ({name: array}, names from OUTPUT_NAMES) as dirname/<name>.npy in float32.  Refuses a
+    set above DUMP_LIMIT_BYTES rather than writing part of it."""
+    unknown = sorted(set(arrays) - set(OUTPUT_NAMES))
+    if unknown:
+        raise ValueError('no description in OUTPUT_NAMES for %s' % unknown)
+    out = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError('outputs of %d bytes exceed the %d-byte dump limit' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, k + '.npy'), a)
+    return sorted(out)
+
+
 def main():
     try:
         _main()
@@ -651,7 +677,10 @@ def _main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-dedup', action='store_true', help='skip the extra de-duplicated-formulation timing')
     ap.add_argument('--no-extra', action='store_true', help='skip the calibration launches, the 2-s sustained window and the extra small-step workloads (configs 1, 2, 5)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (float32)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         # `python bench.py --gpus N`: start the N ranks ourselves, as fresh children, BEFORE anything in this
@@ -704,6 +733,8 @@ def _main():
             dist.init_process_group(backend, rank=rank, world_size=world, timeout=pg_timeout)
 
     mark_stage('build_problem')
+    np.random.seed(0)                             # same arguments, same inputs (uniform sampling draws nothing today)
+    torch.manual_seed(0)
     vn, wname = build_problem(args.config)        # joins the engine's RCCL communicator when world > 1
     mark_stage('data')
     fd, eng = vn.fixData, vn.engine
@@ -752,6 +783,10 @@ def _main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     mark_stage('report')
+    if args.dump_outputs and rank == 0:
+        # before anything below moves the engine on (the sustained window, the dedup leg and the CPU baseline take more steps)
+        dump_outputs(args.dump_outputs, {'params': eng.get_params(), 'grad': gb[:P].cpu().numpy(),
+                                         'loss_terms': gb[P:P + 4].cpu().numpy()})
     comm_ms = None
     if world > 1:
         comm_ms = eng.profile_comm()[0] if in_engine else float(np.mean([a.elapsed_time(b) for a, b in ar_ev]))

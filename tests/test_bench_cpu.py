@@ -229,3 +229,28 @@ def test_kernel_hash_ignores_comments_and_layout_only():
     assert 'include/varnet_hip.h' in bench.KERNEL_SOURCES['vn_fused16_kernel'] and 'varnet_amd/csrc/vn_fused16_common.h' in bench.KERNEL_SOURCES['vn_fused16_kernel']
     assert '-fno-slp-vectorize' in bench.effective_cxxflags() and '--offload-arch=gfx950' in bench.effective_cxxflags()
     assert len({bench.kernel_source_hash(k) for k in ('vn_fused16_kernel', 'vn_pgrad16_kernel', 'vn_dedup_seed_kernel', 'vn_split16_pgrad_kernel')}) == 4
+
+
+def test_dump_outputs_writes_float32_npy_within_the_limit(tmp_path):
+    """--dump-outputs: every output of the timed step as <name>.npy in float32; a set above the size limit or an undescribed
+    name is refused before anything is written."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    out = str(tmp_path / 'dump')
+    arrays = {'params': np.arange(7, dtype=np.float64), 'grad': np.ones(7, dtype=np.float32), 'loss_terms': [1.5, 0.25, 0.5, 0.75]}
+    assert bench.dump_outputs(out, arrays) == sorted(bench.OUTPUT_NAMES)
+    for k, v in arrays.items():
+        a = np.load(os.path.join(out, k + '.npy'))
+        assert a.dtype == np.float32 and np.array_equal(a, np.asarray(v, dtype=np.float32))
+    big = str(tmp_path / 'big')
+    with pytest.raises(ValueError):
+        bench.dump_outputs(big, {'params': np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)})
+    with pytest.raises(ValueError):
+        bench.dump_outputs(big, {'u': np.zeros(3)})
+    assert not os.path.exists(big)
+
+
+def test_bench_refuses_zero_timed_steps():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and '--steps' in r.stderr
