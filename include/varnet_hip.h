@@ -165,7 +165,9 @@ int vn_set_dedup(vn_engine* h, int32_t batch, const float* Xu_dev, int64_t U, co
                  const int32_t* rowptr_dev, const int32_t* rowidx_dev);
 
 /* Feed of tower.biInput / biLabel / bDof / biDimVal (VarNetUtility.py:841-849).
- * biInput [nB, d_in], biLabel [nB]; rows [0,bDof) are boundary, [bDof,nB) initial condition. */
+ * biInput [nB, d_in], biLabel [nB]; rows [0,bDof) are boundary, [bDof,nB) initial condition.  A steady engine
+ * (time_dependent == 0) has no initial condition (TFModel.py:646-650: ICloss is the constant 0): it never evaluates the
+ * rows [bDof,nB), and they enter neither the loss nor the gradient. */
 int vn_set_bic(vn_engine* h, const float* biInput_dev, const float* biLabel_dev, int64_t nB,
                int64_t bDof, double biDimVal);
 /* Optional per-batch copy of the BC/IC rows: the reference's shuffleTrainData feeds every (mini-batch, tower) its own

@@ -233,7 +233,9 @@ def record(store, key, vn, RVU, batchNum, batchLen, pu):
     return tData
 
 
-def main():
+def load_reference():
+    """Import the reference's NumPy half behind the TF placeholders: returns its VarNet, VarNetUtility, Domain and ADPDE
+    modules (oracle/gen_golden_steady.py reuses this procedure)."""
     os.environ.setdefault('MPLBACKEND', 'Agg')
     sys.path.insert(0, REF)
     install_placeholders()
@@ -248,6 +250,11 @@ def main():
     import Domain as RD
     import ADPDE as RA
     RV.TFNN = TowerRecord
+    return RV, RVU, RD, RA
+
+
+def main():
+    RV, RVU, RD, RA = load_reference()
     os.makedirs(OUT, exist_ok=True)
     st = {}
 

@@ -19,7 +19,7 @@ for dt, name in ((torch.float64, 'fp64'), (torch.float32, 'fp32')):
         z['flat'].astype(np.float64 if dt == torch.float64 else np.float32), d_in, widths, dt, Input=c(g('Input')), gcoef=c(g('gcoef')),
         source=c(g('source')), N=c(g('N')), dNt=c(g('dNt')), integW=c(g('integW')), intShape=[n_k, q],
         detJ=(c(g('detJ')) if djv else float(g('detJ'))), detJvec=djv, biInput=c(g('biInput')), biLabel=c(g('biLabel')),
-        bDof=bDof, biDimVal=2.0, w=g('w'), dim=dim, time_dependent=True, is_source=src, integWflag=iw, activation=act)
+        bDof=bDof, biDimVal=2.0, w=g('w'), dim=dim, time_dependent=bool(z['td']) if 'td' in z.files else True, is_source=src, integWflag=iw, activation=act)
     res[name] = (ref['loss'], np.asarray(gref, dtype=np.float64))
 l64, g64 = res['fp64']
 print('case: %s L=%d widths=%s q=%d n_k=%d   |grad|_inf %.3e  loss %.6e' % (act, len(widths), widths, q, n_k, np.max(np.abs(g64)), l64))

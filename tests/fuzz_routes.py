@@ -53,19 +53,21 @@ def synth(seed, d_in, dim, widths, integNum, n_k, nB, bDof, source=False, integW
     return d
 
 
-def make_engine(d_in, dim, widths, integNum, source, integW, kernel=0, act='sigmoid'):
+def make_engine(d_in, dim, widths, integNum, source, integW, kernel=0, act='sigmoid', td=True):
     from varnet_amd.engine import VNEngine
     if kernel == 40:                            # the layer-by-layer route on its GEMMs (read when the engine is created)
         os.environ['VN_LAYERED_NOWIDE'] = '1'
         try:
-            return VNEngine(dim, d_in, widths, True, integNum, isSource=source, integWflag=integW, kernel=4, activationFun=act)
+            return VNEngine(dim, d_in, widths, td, integNum, isSource=source, integWflag=integW, kernel=4, activationFun=act)
         finally:
             del os.environ['VN_LAYERED_NOWIDE']
-    return VNEngine(dim, d_in, widths, True, integNum, isSource=source, integWflag=integW, kernel=kernel, activationFun=act)
+    return VNEngine(dim, d_in, widths, td, integNum, isSource=source, integWflag=integW, kernel=kernel, activationFun=act)
 
 
-def draw_case(rng, case):
-    """One random case; `rng` is advanced exactly as the round-2 tool advanced it (same seeds = same cases)."""
+def draw_case(rng, case, steady=False):
+    """One random case; `rng` is advanced exactly as the round-2 tool advanced it (same seeds = same cases).  steady: a
+    time-independent problem (same number of draws): d_in = dim or dim + 1, the extra column is NOT time; dNt and the rows
+    behind bDof are still fed, and a steady loss ignores both."""
     beyond = rng.random() < 0.2
     L = int(rng.integers(1, 10 if beyond else 7))
     act = 'tanh' if rng.random() < 0.3 else 'sigmoid'
@@ -74,7 +76,7 @@ def draw_case(rng, case):
     else:
         widths = [int(rng.integers(1, 301 if beyond else 65)) for _ in range(L)]
     dim = int(rng.integers(1, 4))
-    d_in = dim + 1 + int(rng.integers(0, 2))
+    d_in = dim + (0 if steady else 1) + int(rng.integers(0, 2))
     q = int(rng.choice([4, 8, 16, 27, 32, 36, 64, 128, 216, 256, 1296]))     # 256: 3D+t 2-point, 1296: 3D+t 3-point Gauss
     big = rng.random() < 0.25
     n_k = int(rng.integers(1, 40)) if not big else int(rng.integers(300, 2500) * 128 // q + 1)
@@ -83,7 +85,7 @@ def draw_case(rng, case):
     src, iw, djv = bool(rng.random() < 0.5), bool(rng.random() < 0.5), bool(rng.random() < 0.3)
     rows = bool(rng.random() < 0.2)
     return dict(case=case, L=L, act=act, widths=widths, dim=dim, d_in=d_in, q=q, big=big, n_k=n_k, nB=nB, bDof=bDof,
-                src=src, iw=iw, djv=djv, rows=rows)
+                src=src, iw=iw, djv=djv, rows=rows, td=not steady)
 
 
 def oracle(c, d, flat, dtype):
@@ -93,7 +95,7 @@ def oracle(c, d, flat, dtype):
         flat.astype(f), c['d_in'], c['widths'], dtype, Input=cv(d['Input']), gcoef=cv(d['gcoef']), source=cv(d['source']),
         N=cv(d['N']), dNt=cv(d['dNt']), integW=cv(d['integW']), intShape=[c['n_k'], c['q']],
         detJ=(cv(d['detJ']) if c['djv'] else float(d['detJ'])), detJvec=c['djv'], biInput=cv(d['biInput']),
-        biLabel=cv(d['biLabel']), bDof=c['bDof'], biDimVal=2.0, w=d['w'], dim=c['dim'], time_dependent=True,
+        biLabel=cv(d['biLabel']), bDof=c['bDof'], biDimVal=2.0, w=d['w'], dim=c['dim'], time_dependent=c.get('td', True),
         is_source=c['src'], integWflag=c['iw'], activation=c['act'])
     return float(ref['loss']), np.asarray(g, dtype=np.float64)
 
@@ -102,11 +104,12 @@ def run_case(c, with_oracle=True):
     """All routes that can run the case.  Returns a result dict; result['ok'] is the verdict, result['msg'] a line."""
     L, widths, d_in, dim, q = c['L'], c['widths'], c['d_in'], c['dim'], c['q']
     src, iw, djv, act, case = c['src'], c['iw'], c['djv'], c['act'], c['case']
+    td = c.get('td', True)
     in_range = L <= 6 and max(widths) <= 64 and d_in <= 8       # the generic kernels' range
     kernels = [40, 4, 0]
     if in_range:
         try:
-            make_engine(d_in, dim, widths, q, src, iw, 1, act).close()
+            make_engine(d_in, dim, widths, q, src, iw, 1, act, td).close()
             kernels.append(1)
         except Exception:                       # deep + wide: too big for the generic kernels' LDS
             pass
@@ -119,7 +122,7 @@ def run_case(c, with_oracle=True):
     # other reduction paths here.
     dd = None
     if not djv and not c['rows'] and dim <= 3:
-        probe = make_engine(d_in, dim, widths, q, src, iw, 0, act)
+        probe = make_engine(d_in, dim, widths, q, src, iw, 0, act, td)
         if probe.dedup_supported():
             r5 = np.random.default_rng(5000 + case)
             n = n_k * q
@@ -135,7 +138,7 @@ def run_case(c, with_oracle=True):
         probe.close()
     grads, routes, flat = [], [], None
     for kernel in kernels:
-        eng = make_engine(d_in, dim, widths, q, src, iw, kernel, act)
+        eng = make_engine(d_in, dim, widths, q, src, iw, kernel, act, td)
         eng.init_params(seed=case)
         flat = eng.get_params() + 0.05 * np.random.default_rng(case).standard_normal(eng.P).astype(np.float32)
         eng.set_params(flat)
@@ -184,8 +187,8 @@ def run_case(c, with_oracle=True):
     if with_oracle:
         ok = ok and res['gerr'] <= gbar and res['lerr'] <= LOSS_BAR
     res['ok'] = bool(ok)
-    res['msg'] = ('case %3d %s L=%d widths=%s d_in=%d dim=%d q=%d n_k=%d nB=%d src=%d iw=%d djv=%d rows=%d routes=%s: '
-                  'pair %.1e/%.1e' % (case, act, L, widths, d_in, dim, q, n_k, c['nB'], src, iw, djv, c['rows'], routes, pair, lpair))
+    res['msg'] = ('%scase %3d %s L=%d widths=%s d_in=%d dim=%d q=%d n_k=%d nB=%d src=%d iw=%d djv=%d rows=%d routes=%s: '
+                  'pair %.1e/%.1e' % ('' if td else 'steady ', case, act, L, widths, d_in, dim, q, n_k, c['nB'], src, iw, djv, c['rows'], routes, pair, lpair))
     if with_oracle:
         res['msg'] += '  oracle %.1e/%.1e' % (res['gerr'], res['lerr'])
     if res['cond'] is not None:
@@ -194,7 +197,7 @@ def run_case(c, with_oracle=True):
         res['msg'] += '   <<<<<<<< MISMATCH'
         os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
         np.savez(os.path.join(ROOT, 'gpurun_out', 'fuzz_mismatch.npz'), widths=np.array(widths), d_in=d_in, dim=dim, q=q,
-                 n_k=n_k, nB=c['nB'], bDof=c['bDof'], src=src, iw=iw, djv=djv, rows=c['rows'], act=act, flat=flat,
+                 n_k=n_k, nB=c['nB'], bDof=c['bDof'], td=td, src=src, iw=iw, djv=djv, rows=c['rows'], act=act, flat=flat,
                  routes=np.array(routes), grads=np.array(grads),
                  **{'d_' + k: (np.zeros(0) if v is None else np.asarray(v)) for k, v in d.items()})
     return res

@@ -18,6 +18,7 @@ from varnet_amd.varnet import VarNet
 from tests.oracle_engine import OracleEngine
 
 G = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'assembly.npz'))
+GS = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'assembly_steady.npz'))    # oracle/gen_golden_steady.py
 TOL = dict(rtol=1e-13, atol=1e-13)
 
 
@@ -54,7 +55,20 @@ def pde2(source=False):
     return ADPDE(PolygonDomain2D(verts), tInterval=[0, 1.5], BCs=BC, IC=0.0, **kw)
 
 
+def pde2_steady():
+    """Steady 2D problem of tests/golden/assembly_steady.npz (oracle/gen_golden_steady.py): variable coefficients, source."""
+    verts = np.array([[0.0, -0.5], [0.0, -0.2], [0.0, 0.2], [0.0, 0.5], [2.0, 0.5], [2.0, -0.5]])
+    return ADPDE(PolygonDomain2D(verts), BCs=[[], [0.0, 1.0, 1.0], [], [], [], []],
+                 diff=lambda x, t=0: 1e-2 * (1.0 + x[:, 1:2] ** 2),
+                 vel=lambda x, t=0: np.hstack([1.0 + 0.0 * x[:, 0:1], 0.1 * x[:, 0:1]]),
+                 source=lambda x, t=0: np.sin(x[:, 0:1]) * (1.0 + x[:, 1:2]),
+                 d_diff=lambda x, t=0: np.hstack([0.0 * x[:, 0:1], 2e-2 * x[:, 1:2]]),
+                 cEx=lambda x, t=0: np.sin(x[:, 0:1]) * (1.0 + x[:, 1:2]))
+
+
 def build(kind, ip):
+    if kind == '2d_steady':
+        return VarNet(pde2_steady(), layerWidth=[5], discNum=[4, 3], bDiscNum=3, tDiscNum=[], integPnum=ip)
     if kind == '1dt':
         return VarNet(pde1(), layerWidth=[5], discNum=5, bDiscNum=None, tDiscNum=6, integPnum=ip)
     if kind == '2dt':
@@ -68,7 +82,7 @@ def npy(t):
     return None if t is None else (t.numpy() if hasattr(t, 'numpy') else np.asarray(t))
 
 
-def check_case(key, vn, bn, bl, pu):
+def check_case(key, vn, bn, bl, pu, G=G):
     g = key + '_'
     fd = vn.fixData
     sc = G[g + 'scalars']
@@ -148,6 +162,14 @@ def test_variable_coefficients_and_source_match_reference():
 
 def test_steady_problem_matches_reference():
     check_case('1d_steady', build('1d_steady', 2), None, None, 1)
+
+
+@pytest.mark.parametrize('ip', [2, 3])
+def test_steady_2d_problem_matches_reference(ip):
+    """PolygonDomain2D, timeDependent=False, two- and three-point Gauss (integNum 16 and 36), variable diff / vel / source."""
+    vn = build('2d_steady', ip)
+    assert not vn.PDE.timeDependent and vn.fixData.integNum == ip ** 2 * 4 and vn.inpDim == vn.dim == 2
+    check_case('2d_steady_ip%d' % ip, vn, None, None, 1, G=GS)
 
 
 @pytest.mark.parametrize('name', ['td', 'steady'])

@@ -62,7 +62,7 @@ def make_engine(d_in, dim, widths, integNum, source, integW, kernel=0, optimizer
                     optimizer_name=optimizer_name)
 
 
-def oracle_eval(flat, d, d_in, dim, widths, integNum, n_k, bDof, source, integW, detJvec):
+def oracle_eval(flat, d, d_in, dim, widths, integNum, n_k, bDof, source, integW, detJvec, time_dependent=True):
     kw = dict(Input=d['Input'].astype(np.float64), gcoef=d['gcoef'].astype(np.float64),
               source=None if d['source'] is None else d['source'].astype(np.float64),
               N=d['N'].astype(np.float64), dNt=d['dNt'].astype(np.float64),
@@ -70,7 +70,7 @@ def oracle_eval(flat, d, d_in, dim, widths, integNum, n_k, bDof, source, integW,
               intShape=[n_k, integNum],
               detJ=(d['detJ'].astype(np.float64) if detJvec else float(d['detJ'])), detJvec=detJvec,
               biInput=d['biInput'].astype(np.float64), biLabel=d['biLabel'].astype(np.float64),
-              bDof=bDof, biDimVal=2.0, w=d['w'], dim=dim, time_dependent=True,
+              bDof=bDof, biDimVal=2.0, w=d['w'], dim=dim, time_dependent=time_dependent,
               is_source=source, integWflag=integW)
     return og.loss_and_grad(flat.astype(np.float64), d_in, widths, torch.float64, **kw)
 
@@ -296,50 +296,110 @@ def test_train_epoch_equals_single_steps():
 
 
 STEADY = [
-    # d_in dim widths        integNum n_k nB  (time-independent: no IC rows, no dNt term; TFModel.py:537,646-650)
-    (1, 1, [20, 20],         4,       37, 2),
-    (2, 2, [20, 20, 20],     16,      50, 60),
-    (2, 2, [50, 50, 50],     16,      129, 33),
-    (2, 2, [7, 9],           36,      11, 20),
+    # time-independent: no IC rows, no dNt term (TFModel.py:537,646-650); nonzero dNt tables and rows behind bDof are fed
+    # all the same (a route that read them would be caught: the oracle ignores both for a steady problem)
+    # d_in dim widths        integNum n_k nB  bDof act        integW detJvec
+    (1, 1, [20, 20],         4,       37, 2,  2,   'sigmoid', False, False),
+    (2, 2, [20, 20, 20],     16,      50, 60, 60,  'sigmoid', False, False),
+    (2, 2, [50, 50, 50],     16,      129, 33, 33, 'sigmoid', False, False),
+    (2, 2, [7, 9],           36,      11, 20, 20,  'sigmoid', True,  False),
+    (1, 1, [20],             6,       40, 2,  2,   'sigmoid', True,  False),   # 1D three-point Gauss: 21 test functions per 128-row tile
+    (1, 1, [50] * 5,         6,       77, 2,  2,   'tanh',    True,  True),
+    (2, 2, [64, 64, 64],     16,      60, 40, 25,  'sigmoid', False, True),    # rows behind bDof: ignored by a steady loss
+    (2, 2, [60, 64, 51],     36,      30, 30, 12,  'tanh',    True,  False),   # widths 51..64
+    (3, 2, [20, 20, 20],     16,      40, 30, 20,  'sigmoid', False, False),   # d_in = dim + 1: the extra column is NOT time
+    (3, 2, [60, 64, 51],     36,      17, 20, 20,  'sigmoid', True,  True),
+    (2, 1, [64, 64, 64],     4,       300, 2, 2,   'tanh',    False, True),    # d_in = dim + 1 in 1D
+    (2, 2, [50] * 5,         36,      400, 60, 60, 'sigmoid', True,  False),   # several hundred test functions
+    (2, 2, [128, 128],       16,      30, 40, 20,  'sigmoid', False, False),   # beyond the kernels: layer by layer
+    (1, 1, [300],            6,       25, 2,  2,   'tanh',    True,  True),
 ]
 
 
-@pytest.mark.parametrize('kernel', [1, 0], ids=['generic', 'auto'])
-@pytest.mark.parametrize('case', STEADY)
-def test_steady_problem_parity(case, kernel):
+def steady_routes(widths, d_in):
+    """Routes that serve a STEADY case: forced kernels only where the network is in their range."""
+    in_range = max(widths) <= 64 and len(widths) <= 6 and d_in <= 8
+    return ['generic', 'auto', 'fused16'] if in_range else ['auto']
+
+
+def steady_setup(case, kernel, seed=7):
     from varnet_amd.engine import VNEngine
-    d_in, dim, widths, q, n_k, nB = case
-    rng = np.random.default_rng(7)
+    d_in, dim, widths, q, n_k, nB, bDof, act, has_w, detJvec = case
+    rng = np.random.default_rng(seed)
     n = n_k * q
-    Input = rng.uniform(-1, 1, (n, d_in)).astype(np.float32)
-    gcoef = rng.standard_normal((n, dim)).astype(np.float32)
-    src = rng.standard_normal((n, 1)).astype(np.float32)
-    N1 = rng.uniform(0, 1, q).astype(np.float32)
-    integW = rng.uniform(0.5, 1, (1, q)).astype(np.float32) if q == 36 else None
-    biInput = rng.uniform(-1, 1, (nB, d_in)).astype(np.float32)
-    biLabel = rng.standard_normal((nB, 1)).astype(np.float32)
-    w = np.array([4.0, 0.0, 3.0])                                   # VarNet.py:1132: IC weight 0
-    eng = VNEngine(dim, d_in, widths, False, q, isSource=True, integWflag=integW is not None, kernel=kernel)
+    d = dict(Input=rng.uniform(-1, 1, (n, d_in)).astype(np.float32),
+             gcoef=rng.standard_normal((n, dim)).astype(np.float32),
+             source=rng.standard_normal((n, 1)).astype(np.float32),
+             N1=rng.uniform(0, 1, q).astype(np.float32))
+    d['integW'] = rng.uniform(0.5, 1, (1, q)).astype(np.float32) if has_w else None
+    d['biInput'] = rng.uniform(-1, 1, (nB, d_in)).astype(np.float32)
+    d['biLabel'] = rng.standard_normal((nB, 1)).astype(np.float32)
+    d['dNt1'] = rng.standard_normal(q).astype(np.float32)
+    d['detJ'] = rng.uniform(0.01, 0.03, (n_k, 1)).astype(np.float32) if detJvec else np.float32(0.02)
+    d['w'] = np.array([4.0, 0.0, 3.0])                              # VarNet.py:1132: IC weight 0
+    eng = VNEngine(dim, d_in, widths, False, q, isSource=True, integWflag=has_w, kernel=kernel, activationFun=act)
     eng.init_params(seed=2)
     flat = eng.get_params()
-    eng.set_fe_table(N1, np.zeros(q, np.float32), integW)
-    eng.set_interior(0, Input, gcoef, src, n_k=n_k, detJ=0.02)
-    eng.set_bic(biInput, biLabel, nB, 1.5)                          # every row is a boundary row
-    eng.set_weights(w)
-    ref, gref = og.loss_and_grad(
-        flat.astype(np.float64), d_in, widths, torch.float64, Input=Input.astype(np.float64),
-        gcoef=gcoef.astype(np.float64), source=src.astype(np.float64),
-        N=np.tile(N1, n_k).reshape(n, 1).astype(np.float64), dNt=np.zeros((n, 1)),
-        integW=None if integW is None else integW.astype(np.float64), intShape=[n_k, q], detJ=0.02,
-        detJvec=False, biInput=biInput.astype(np.float64), biLabel=biLabel.astype(np.float64), bDof=nB,
-        biDimVal=1.5, w=w, dim=dim, time_dependent=False, is_source=True, integWflag=integW is not None)
+    flat = flat + 0.05 * np.random.default_rng(5).standard_normal(flat.size).astype(np.float32)
+    eng.set_params(flat)
+    eng.set_fe_table(d['N1'], d['dNt1'], d['integW'])
+    eng.set_interior(0, d['Input'], d['gcoef'], d['source'], n_k=n_k, detJ=d['detJ'])
+    eng.set_bic(d['biInput'], d['biLabel'], bDof, 1.5)
+    eng.set_weights(d['w'])
+    return eng, d, flat
+
+
+def steady_oracle(flat, d, case):
+    d_in, dim, widths, q, n_k, nB, bDof, act, has_w, detJvec = case
+    n = n_k * q
+    f64 = lambda a: None if a is None else a.astype(np.float64)
+    return og.loss_and_grad(
+        flat.astype(np.float64), d_in, widths, torch.float64, Input=f64(d['Input']), gcoef=f64(d['gcoef']),
+        source=f64(d['source']), N=np.tile(d['N1'], n_k).reshape(n, 1).astype(np.float64),
+        dNt=np.tile(d['dNt1'], n_k).reshape(n, 1).astype(np.float64), integW=f64(d['integW']), intShape=[n_k, q],
+        detJ=f64(d['detJ']) if detJvec else float(d['detJ']), detJvec=detJvec, biInput=f64(d['biInput']),
+        biLabel=f64(d['biLabel']), bDof=bDof, biDimVal=1.5, w=d['w'], dim=dim, time_dependent=False, is_source=True,
+        integWflag=has_w, activation=act)
+
+
+def steady_check(eng, d, flat, case, tag):
+    """Loss components, lossVec and gradient of a steady engine against the fp64 oracle; ICloss is exactly 0."""
+    ref, gref = steady_oracle(flat, d, case)
+    assert ref['ICloss'] == 0.0
+    out, lv = eng.eval_loss(0, lossVec=True)
+    rec = {}
+    for got, key in zip(out, ['loss', 'BCloss', 'ICloss', 'varLoss']):
+        rec['eval_' + key] = abs(got - ref[key]) / max(abs(ref[key]), 1e-300)
+        assert abs(got - ref[key]) <= LOSS_RTOL * abs(ref[key]) + 1e-7, (key, got, ref[key])
+    assert out[2] == 0.0
+    lref = ref['lossVec'].reshape(-1)
+    rec['lossVec'] = float(np.max(np.abs(lv.cpu().numpy() - lref)) / np.max(np.abs(lref)))
     gb = eng.bind_grad_buffer()
     eng.grad(0)
     torch.cuda.synchronize()
     g = gb.cpu().numpy()
-    assert abs(g[eng.P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
-    assert abs(g[eng.P + 2]) == 0.0                                  # ICloss is the constant 0
-    assert np.max(np.abs(g[:eng.P] - gref)) <= GRAD_RTOL * np.max(np.abs(gref))
+    P = eng.P
+    rec['grad_loss'] = float(abs(g[P] - ref['loss']) / abs(ref['loss']))
+    rec['grad'] = float(np.max(np.abs(g[:P] - gref)) / np.max(np.abs(gref)))
+    ERRORS['steady ' + tag] = rec
+    assert rec['lossVec'] <= LVEC_RTOL, rec
+    assert abs(g[P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
+    assert abs(g[P + 2]) == 0.0                                      # ICloss is the constant 0
+    assert rec['grad'] <= GRAD_RTOL, rec
+
+
+_KERNEL = {'generic': 1, 'auto': 0, 'fused16': 3}
+
+
+@pytest.mark.parametrize('case,kernel', [pytest.param(c, r, id='case%d-%s' % (i, r))
+                                         for i, c in enumerate(STEADY) for r in steady_routes(c[2], c[0])])
+def test_steady_problem_parity(case, kernel):
+    eng, d, flat = steady_setup(case, _KERNEL[kernel])
+    if kernel == 'fused16':
+        assert eng.kernel_path()[0] == 3
+    elif kernel == 'generic':
+        assert eng.kernel_path()[0] == 1
+    steady_check(eng, d, flat, case, 'case%d %s %s %s q%d' % (STEADY.index(case), kernel, case[2], case[7], case[3]))
     eng.close()
 
 
@@ -441,6 +501,10 @@ def test_dedup_formulation_parity(case):
     """De-duplicated formulation (one network evaluation per unique quadrature point): same loss
     and gradient as the row-wise formulation -- against the fp64 oracle on the expanded rows and
     against the engine's own row-wise path."""
+    _dedup_parity(case, True)
+
+
+def _dedup_parity(case, td, tag=None):
     from varnet_amd.engine import VNEngine
     d_in, dim, widths, q, n_k, U, nB, bDof, source, integW = case
     rng = np.random.default_rng(21)
@@ -457,8 +521,10 @@ def test_dedup_formulation_parity(case):
     W = rng.uniform(0.5, 1, (1, q)).astype(np.float32) if integW else None
     biInput = rng.uniform(-1, 1, (nB, d_in)).astype(np.float32)
     biLabel = rng.standard_normal((nB, 1)).astype(np.float32)
-    w = np.array([3.0, 2.0, 5.0])
-    eng = VNEngine(dim, d_in, widths, True, q, isSource=source, integWflag=integW)
+    w = np.array([3.0, 2.0, 5.0]) if td else np.array([3.0, 0.0, 5.0])
+    eng = VNEngine(dim, d_in, widths, td, q, isSource=source, integWflag=integW)
+    if not td:
+        assert eng.dedup_supported()                                 # what train(dedup='auto') would pick for this problem
     eng.init_params(seed=4)
     flat = eng.get_params()
     eng.set_fe_table(N1, dNt1, W)
@@ -480,8 +546,15 @@ def test_dedup_formulation_parity(case):
         N=np.tile(N1, n_k).reshape(n, 1).astype(np.float64), dNt=np.tile(dNt1, n_k).reshape(n, 1).astype(np.float64),
         integW=None if W is None else W.astype(np.float64), intShape=[n_k, q], detJ=0.05, detJvec=False,
         biInput=biInput.astype(np.float64), biLabel=biLabel.astype(np.float64), bDof=bDof, biDimVal=2.0, w=w,
-        dim=dim, time_dependent=True, is_source=source, integWflag=integW)
+        dim=dim, time_dependent=td, is_source=source, integWflag=integW)
     P = eng.P
+    if tag is not None:
+        ERRORS[tag] = {k: float(np.max(np.abs(g[:P] - gref)) / np.max(np.abs(gref))) for k, g in
+                       (('grad_rowwise', g_rows), ('grad_dedup', g_dd))}
+        ERRORS[tag].update({'loss_' + k: float(abs(g[P] - ref['loss']) / abs(ref['loss'])) for k, g in
+                            (('rowwise', g_rows), ('dedup', g_dd))})
+    if not td:
+        assert ref['ICloss'] == 0.0 and g_rows[P + 2] == 0.0 and g_dd[P + 2] == 0.0
     for g in (g_rows, g_dd):
         assert abs(g[P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
         assert np.max(np.abs(g[:P] - gref)) <= GRAD_RTOL * np.max(np.abs(gref))
@@ -498,6 +571,7 @@ def test_dedup_formulation_parity(case):
     for out, lv in ((out_dd, lv_dd), (out_rw, lv_rw)):
         assert abs(out[0] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
         assert abs(out[1] - ref['BCloss']) <= LOSS_RTOL * abs(ref['BCloss']) and abs(out[2] - ref['ICloss']) <= LOSS_RTOL * abs(ref['ICloss'])
+        assert td or out[2] == 0.0
         assert abs(out[3] - ref['varLoss']) <= LOSS_RTOL * abs(ref['varLoss'])
         assert np.max(np.abs(lv.cpu().numpy().astype(np.float64) - lvref)) <= 1e-4 * np.max(np.abs(lvref))
     assert np.allclose(out_dd, [g_dd[P], g_dd[P + 1], g_dd[P + 2], g_dd[P + 3]], rtol=2e-6)
@@ -510,6 +584,26 @@ def test_dedup_formulation_parity(case):
     torch.cuda.synchronize()
     assert np.array_equal(gb.cpu().numpy(), g_rows)
     eng.close()
+
+
+DEDUP_STEADY = [
+    # d_in dim widths            q   n_k  U     nB  bDof source integW   (steady: bDof < nB feeds rows a steady loss ignores)
+    (1, 1, [20, 20],             4,   77,  90,   12, 5,   True,  False),      # integPnum 2 in 1D: one live input feature
+    (1, 1, [50, 50, 50],         6,   53,  200,  2,  2,   True,  True),       # integPnum 3 in 1D: ragged 128-row tiles
+    (2, 2, [32, 17],             16,  50,  230,  30, 18,  False, False),      # widths <= 32: vn_pgrad16
+    (2, 2, [33, 50, 41],         16,  40,  300,  20, 20,  True,  False),      # widths 33..64: vn_split16
+    (2, 2, [64, 64, 64],         36,  30,  400,  40, 22,  True,  True),
+    (3, 2, [20, 30],             36,  21,  333,  12, 6,   False, True),       # d_in = dim + 1: the extra column is not time
+    (3, 2, [60, 64, 51],         16,  45,  500,  9,  4,   True,  False),
+]
+
+
+@pytest.mark.parametrize('case', DEDUP_STEADY)
+def test_dedup_formulation_parity_steady(case):
+    """The de-duplicated formulation on a steady problem (no time seed in the reverse launch, vn_dedup.hip's steady branches):
+    the method of test_dedup_formulation_parity -- fp64 oracle, the row-wise path, the monitor's loss split, bitwise repeatable,
+    switching it off restores the row-wise path."""
+    _dedup_parity(case, False, 'steady dedup case%d %s q%d' % (DEDUP_STEADY.index(case), case[2], case[3]))
 
 
 @pytest.mark.parametrize('d_in,dim,widths,act,n', [
@@ -662,6 +756,101 @@ def test_taylor_residual_parity(d_in, dim, widths, act, n, with_src, with_ddx, m
     u2, r2 = eng.residual(X32, diff, vel, src, ddx, fp64=False)
     torch.cuda.synchronize()
     assert torch.equal(r, r2) and torch.equal(u, u2)
+    eng.close()
+
+
+STEADY_POINTS = [
+    # d_in dim widths                 act        route of vn_forward / vn_residual (f32) | fp64
+    (1, 1, [50, 50, 50],              'sigmoid'),  # bf16 pieces (vn_split16), one live input feature | vn_taylor16d
+    (2, 2, [64, 51, 64],              'tanh'),     # bf16 pieces | vn_taylor16d
+    (3, 2, [40, 52],                  'sigmoid'),  # bf16 pieces, d_in = dim + 1: the extra column is NOT time
+    (1, 1, [20, 20, 20],              'tanh'),     # vn_pgrad16 / vn_taylor16 | vn_taylor16d
+    (2, 2, [10, 20, 30],              'sigmoid'),
+    (3, 2, [32, 17],                  'sigmoid'),  # vn_taylor16, d_in = dim + 1
+    (2, 2, [64] * 6,                  'sigmoid'),  # fp64 images do not fit the LDS: the per-point fp64 kernel
+    (2, 2, [128, 128],                'sigmoid'),  # layer by layer (f32 and fp64)
+    (1, 1, [300],                     'tanh'),
+    (2, 1, [300],                     'sigmoid'),  # layer by layer, d_in = dim + 1
+]
+POINT_COUNTS = (1, 15, 16, 17, 4099)
+
+
+@pytest.mark.parametrize('d_in,dim,widths,act', STEADY_POINTS)
+def test_steady_point_kernels_parity(d_in, dim, widths, act):
+    """vn_forward, vn_forward_grad, vn_residual, vn_forward_f64 and vn_residual_f64 of a STEADY engine (the td = 0 branches:
+    no time pass, no -du/dt term) against og.model_grad / og.residual with time_dependent=False, on every route that serves
+    the network: the automatic one, the per-point kernels (route 1) and the f32-MFMA forms (route 2, cross-check library)."""
+    from varnet_amd.engine import VNEngine
+    eng = VNEngine(dim, d_in, widths, False, 16, activationFun=act)
+    layered = eng.kernel_path()[0] == 4
+    assert layered == (max(widths) > 64)
+    eng.init_params(seed=5)
+    flat = (eng.get_params() * 2.0).astype(np.float32)            # steeper than glorot: second derivatives that are not tiny
+    eng.set_params(flat)
+    engx = None
+    if not layered:
+        engx = VNEngine(dim, d_in, widths, False, 16, activationFun=act, xcheck=True)
+        engx.set_params(flat)
+        engx.debug_point_route(2)
+    params = og.unflatten(flat.astype(np.float64), d_in, widths, torch.float64)
+    rec = {}
+    rng = np.random.default_rng(23)
+    for n in POINT_COUNTS:
+        X = rng.uniform(-1.2, 1.2, (n, d_in))
+        diff = rng.uniform(0.1, 1, (n, 1)); vel = rng.standard_normal((n, dim))
+        src = rng.standard_normal((n, 1)); ddx = rng.standard_normal((n, dim))
+        uref, rref = og.residual(flat.astype(np.float64), d_in, widths, torch.float64, X, diff, vel, src, ddx, dim, False,
+                                 activation=act)
+        uref, rref = uref[:, 0], rref[:, 0]
+        uscale = max(1.0, float(np.max(np.abs(uref))))
+        scale = max(1.0, float(np.max(np.abs(rref))))
+        if d_in > dim:
+            # negative control: a kernel that took column `dim` for time would be off by |du/dx_dim|, far beyond the bar
+            _, rtd = og.residual(flat.astype(np.float64), d_in, widths, torch.float64, X, diff, vel, src, ddx, dim, True,
+                                 activation=act)
+            assert np.max(np.abs(rtd[:, 0] - rref)) > 100 * 5e-5 * scale
+        X32 = X.astype(np.float32)
+        e = {}
+        outs = [('', eng)] + ([('f32_mfma_', engx)] if engx is not None else [])
+        for pre, en in outs:
+            u = en.forward(X32)
+            ur, r = en.residual(X32, diff, vel, src, ddx, fp64=False)
+            torch.cuda.synchronize()
+            e[pre + 'u'] = float(np.max(np.abs(u.cpu().numpy() - uref))) / uscale
+            e[pre + 'res_u'] = float(np.max(np.abs(ur.cpu().numpy() - uref))) / uscale
+            e[pre + 'res'] = float(np.max(np.abs(r.cpu().numpy() - rref))) / scale
+            if not layered:
+                ug, g = en.forward_grad(X32)
+                torch.cuda.synchronize()
+                Xt = torch.tensor(X, requires_grad=True)
+                Val, dM_dx, dM_dt, _ = og.model_grad(params, Xt, dim, time_dependent=False, activation=act)
+                assert dM_dt is None
+                gref = dM_dx.detach().numpy()
+                e[pre + 'fg_u'] = float(np.max(np.abs(ug.cpu().numpy() - uref))) / uscale
+                e[pre + 'fg_grad'] = float(np.max(np.abs(g.cpu().numpy() - gref))) / max(1e-30, float(np.max(np.abs(gref))))
+        u64 = eng.forward_f64(X)
+        u64r, r64 = eng.residual(X, diff, vel, src, ddx, fp64=True)
+        torch.cuda.synchronize()
+        e['u_f64'] = float(np.max(np.abs(u64.cpu().numpy() - uref)))
+        e['res_u_f64'] = float(np.max(np.abs(u64r.cpu().numpy() - uref)))
+        e['res_f64'] = float(np.max(np.abs(r64.cpu().numpy() - rref))) / scale
+        if not layered:
+            eng.debug_point_route(1)                                  # the per-point kernels, same inputs
+            _, rp = eng.residual(X32, diff, vel, src, ddx, fp64=False)
+            _, rp64 = eng.residual(X, diff, vel, src, ddx, fp64=True)
+            torch.cuda.synchronize()
+            eng.debug_point_route(0)
+            e['pointwise_res'] = float(np.max(np.abs(rp.cpu().numpy() - rref))) / scale
+            e['pointwise_res_f64'] = float(np.max(np.abs(rp64.cpu().numpy() - rref))) / scale
+        rec['n%d' % n] = e
+        for k, v in e.items():
+            bar = (1e-13 if k in ('u_f64', 'res_u_f64') else 1e-11 if k.endswith('res_f64') else 5e-5 if k.endswith('res')
+                   else 4e-6 if k.startswith('f32_mfma_') and k.endswith('u')     # that kernel's bar in test_taylor_residual_parity
+                   else 2e-6 if k.endswith('u') else 1e-5)
+            assert v <= bar, (n, k, v, bar)
+    ERRORS['steady points %s %s d_in%d %s' % ('layered' if layered else 'kernels', widths, d_in, act)] = rec
+    if engx is not None:
+        engx.close()
     eng.close()
 
 
@@ -828,11 +1017,17 @@ def test_many_tiles_per_workgroup_fused_vs_generic(widths, q, n_k, src):
     ('1dt_ip2_bnNone_blNone_pu1', [50] * 4),
     ('1dt_ip3_bnNone_blNone_pu1', [20, 20, 20]),          # integNum 36, integW
     ('2dt_var', [32, 17]),                                # variable kappa / v, source term
+    ('1d_steady', [20, 20, 20]),                          # steady 1D with a source: d_in = dim = 1, integNum 4
+    ('2d_steady_ip2', [50] * 5),                          # steady 2D (assembly_steady.npz): integNum 16, variable data
+    ('2d_steady_ip3', [64, 51, 64]),                      # ... integNum 36, integW, bf16-piece widths
 ])
 def test_reference_assembled_inputs_through_engine(key, widths):
     import os
-    G = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'assembly.npz'))
+    from varnet_amd.engine import VNEngine
+    name = 'assembly_steady.npz' if key.startswith('2d_steady') else 'assembly.npz'
+    G = np.load(os.path.join(os.path.dirname(__file__), 'golden', name), allow_pickle=True)
     g = key + '_'
+    td = G[g + 'dNt'].dtype != object                    # the reference builds no dNt table for a steady problem (None)
     sc = G[g + 'scalars']
     nt, nT, q, detJ, bDof, biDimVal = int(sc[0]), int(sc[1]), int(sc[2]), float(sc[3]), int(sc[4]), float(sc[5])
     Input, gcoef = G[g + 'Input'], G[g + 'gcoef']
@@ -840,19 +1035,20 @@ def test_reference_assembled_inputs_through_engine(key, widths):
     source = bool(np.any(G[g + 'source']))
     integW = G[g + 'integW']
     has_w = integW.size > 0
-    eng = make_engine(d_in, dim, widths, q, source, has_w)
+    eng = VNEngine(dim, d_in, widths, td, q, isSource=source, integWflag=has_w)
     eng.init_params(seed=11)
     flat = eng.get_params()
-    eng.set_fe_table(G[g + 'N'][:q], G[g + 'dNt'][:q], integW.reshape(-1) if has_w else None)
+    dNt = G[g + 'dNt'] if td else np.zeros((nt * q, 1))
+    eng.set_fe_table(G[g + 'N'][:q], dNt[:q], integW.reshape(-1) if has_w else None)
     eng.set_interior(0, Input, gcoef, G[g + 'source'] if source else None, n_k=nt, detJ=detJ)
     eng.set_bic(G[g + 'biInput'], G[g + 'biLabel'], bDof, biDimVal)
-    w = np.array([3.0, 2.0, 5.0])
+    w = np.array([3.0, 2.0, 5.0]) if td else np.array([3.0, 0.0, 5.0])       # VarNet.py:1132: IC weight 0 when steady
     eng.set_weights(w)
     f32 = lambda a: a.astype(np.float32).astype(np.float64)       # what the device is fed (TFModel.py:531)
     kw = dict(Input=f32(Input), gcoef=f32(gcoef), source=f32(G[g + 'source']) if source else None,
-              N=f32(G[g + 'N']), dNt=f32(G[g + 'dNt']), integW=f32(integW.reshape(1, -1)) if has_w else None,
+              N=f32(G[g + 'N']), dNt=f32(dNt), integW=f32(integW.reshape(1, -1)) if has_w else None,
               intShape=[nt, q], detJ=float(np.float32(detJ)), detJvec=False, biInput=f32(G[g + 'biInput']),
-              biLabel=f32(G[g + 'biLabel']), bDof=bDof, biDimVal=biDimVal, w=w, dim=dim, time_dependent=True,
+              biLabel=f32(G[g + 'biLabel']), bDof=bDof, biDimVal=biDimVal, w=w, dim=dim, time_dependent=td,
               is_source=source, integWflag=has_w)
     ref, gref = og.loss_and_grad(flat.astype(np.float64), d_in, widths, torch.float64, **kw)
     out, lv = eng.eval_loss(0, lossVec=True)
@@ -867,7 +1063,7 @@ def test_reference_assembled_inputs_through_engine(key, widths):
     ref32, _ = og.loss_and_grad(flat, d_in, widths, torch.float32, **kw32)
     own = float(np.max(np.abs(ref32['lossVec'].reshape(-1).astype(np.float64) - lref)))
     dv = float(np.max(np.abs(lv.cpu().numpy() - lref)))
-    ERRORS['golden_' + key] = {'lossVec_abs': dv, 'lossVec_fp32_oracle_abs': own, 'lossVec_scale': float(np.max(np.abs(lref)))}
+    ERRORS[('golden_' if td else 'steady golden_') + key] = {'lossVec_abs': dv, 'lossVec_fp32_oracle_abs': own, 'lossVec_scale': float(np.max(np.abs(lref)))}
     assert dv <= max(LVEC_RTOL * np.max(np.abs(lref)), 4 * own), (dv, own)
     gb = eng.bind_grad_buffer()
     eng.grad(0)
@@ -875,6 +1071,7 @@ def test_reference_assembled_inputs_through_engine(key, widths):
     gg = gb.cpu().numpy()
     assert abs(gg[eng.P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
     assert np.max(np.abs(gg[:eng.P] - gref)) / np.max(np.abs(gref)) <= GRAD_RTOL
+    assert td or (out[2] == 0.0 and gg[eng.P + 2] == 0.0)             # a steady ICloss is the constant 0
     eng.close()
 
 

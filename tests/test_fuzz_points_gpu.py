@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 from oracle import tf1_graph as og  # noqa: E402
 
 
-def _draw(rng):
+def _draw(rng, steady=False):
     wide = rng.random() < 0.3
     L = int(rng.integers(1, 7 if wide else 9))
     hi = 65 if wide else 51
@@ -21,7 +21,7 @@ def _draw(rng):
     else:
         widths = [int(rng.integers(1, hi)) for _ in range(L)]
     dim = int(rng.integers(1, 4))
-    d_in = dim + 1 + int(rng.integers(0, 2))
+    d_in = dim + (0 if steady else 1) + int(rng.integers(0, 2))     # steady: the extra column is not time
     act = 'tanh' if rng.random() < 0.35 else 'sigmoid'
     n = int(rng.choice([1, 15, 16, 17, 127, 128, 1000, 4099]))
     return L, widths, dim, d_in, act, n
@@ -29,12 +29,22 @@ def _draw(rng):
 
 @pytest.mark.parametrize('seed', [0, 1, 2, 3])
 def test_point_kernels_against_the_oracle(seed, monkeypatch):
+    _point_kernels(seed, True)
+
+
+@pytest.mark.parametrize('seed', [4, 5])
+def test_point_kernels_against_the_oracle_steady(seed):
+    """The td = 0 branches of the same kernels: a steady engine against the oracle with time_dependent=False."""
+    _point_kernels(seed, False)
+
+
+def _point_kernels(seed, td):
     from varnet_amd.engine import VNEngine
     rng = np.random.default_rng(100 + seed)
     worst = {'u': 0.0, 'grad': 0.0, 'res': 0.0, 'res_vs_pointwise': 0.0}
     for case in range(12):
-        L, widths, dim, d_in, act, n = _draw(rng)
-        eng = VNEngine(dim, d_in, widths, True, 16, activationFun=act)
+        L, widths, dim, d_in, act, n = _draw(rng, not td)
+        eng = VNEngine(dim, d_in, widths, td, 16, activationFun=act)
         if not eng.dedup_supported():                 # not a network of the 8-wave family
             eng.close()
             continue
@@ -45,10 +55,11 @@ def test_point_kernels_against_the_oracle(seed, monkeypatch):
         diff = rng.uniform(0.05, 1, (n, 1)); vel = rng.standard_normal((n, dim))
         src = rng.standard_normal((n, 1)); ddx = rng.standard_normal((n, dim))
         f64 = flat.astype(np.float64)
-        uref, rref = og.residual(f64, d_in, widths, torch.float64, X, diff, vel, src, ddx, dim, True, activation=act)
+        uref, rref = og.residual(f64, d_in, widths, torch.float64, X, diff, vel, src, ddx, dim, td, activation=act)
         params = og.unflatten(f64, d_in, widths, torch.float64)
         Xt = torch.tensor(X, requires_grad=True)
-        _, gref, _, _ = og.model_grad(params, Xt, dim, activation=act)
+        _, gref, gt, _ = og.model_grad(params, Xt, dim, time_dependent=td, activation=act)
+        assert td or gt is None
         gref = gref.detach().numpy()
         X32 = X.astype(np.float32)
         u, g = eng.forward_grad(X32)
@@ -69,10 +80,10 @@ def test_point_kernels_against_the_oracle(seed, monkeypatch):
              'grad': np.abs(g.cpu().numpy() - gref).max() / sg,
              'res': np.abs(r.cpu().numpy() - rref[:, 0]).max() / sr,
              'res_vs_pointwise': np.abs(r.cpu().numpy() - rp.cpu().numpy()).max() / sr}
-        msg = 'seed %d case %d %s L=%d widths=%s d_in=%d dim=%d n=%d: %s' % (seed, case, act, L, widths, d_in, dim, n, e)
+        msg = ('' if td else 'steady ') + 'seed %d case %d %s L=%d widths=%s d_in=%d dim=%d n=%d: %s' % (seed, case, act, L, widths, d_in, dim, n, e)
         print(msg)
         assert e['u'] <= 2e-6 and e['grad'] <= 2e-5 and e['res'] <= 1e-4 and e['res_vs_pointwise'] <= 1e-4, msg
         for k in worst:
             worst[k] = max(worst[k], float(e[k]))
         eng.close()
-    print('worst over the cases of seed %d: %s' % (seed, worst))
+    print('worst over the cases of seed %d%s: %s' % (seed, '' if td else ' (steady)', worst))

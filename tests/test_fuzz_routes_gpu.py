@@ -22,6 +22,19 @@ def test_routes_agree_with_the_oracle_and_each_other(seed, ncases):
         assert r['ok'], r['msg']
 
 
+@pytest.mark.parametrize('seed,ncases', [(31, 10)])
+def test_routes_agree_with_the_oracle_and_each_other_steady(seed, ncases):
+    """Steady draws (no time column: d_in = dim or dim + 1 with a non-time extra column; dNt and IC rows fed, unused) on
+    every route, including the de-duplicated formulation, against the oracle with time_dependent=False."""
+    rng = np.random.default_rng(seed)
+    for case in range(ncases):
+        c = fz.draw_case(rng, case, steady=True)
+        assert not c['td'] and c['dim'] <= c['d_in'] <= c['dim'] + 1
+        r = fz.run_case(c, with_oracle=True)
+        print(r['msg'])
+        assert r['ok'], r['msg']
+
+
 def test_ill_conditioned_draw_is_whitelisted_by_its_condition_number_only():
     """Seed 11, case 15 (profiles/r2_fuzz_case15_diag.txt): the whitelist applies because the draw's condition estimate
     is beyond COND_WHITELIST, and the widened bar is 2 x the fp32 restatement's own deviation."""

@@ -10,6 +10,7 @@ import torch
 
 from oracle import tf1_graph as og
 from tests.test_engine_gpu import synth, make_engine, oracle_eval, LOSS_RTOL, GRAD_RTOL, LVEC_RTOL
+from tests.test_engine_gpu import STEADY, steady_setup, steady_check, _dump_errors  # noqa: F401 (autouse: the steady cases' errors)
 
 pytestmark = pytest.mark.gpu
 
@@ -91,6 +92,19 @@ def test_loss_and_grad_parity_layered(case, impl, monkeypatch):
     eng.grad(0)
     torch.cuda.synchronize()
     assert np.array_equal(gb.cpu().numpy(), g)
+    eng.close()
+
+
+@pytest.mark.parametrize('impl', ['tile-kernels', 'gemms'])
+@pytest.mark.parametrize('case', STEADY, ids=['case%d' % i for i in range(len(STEADY))])
+def test_steady_problem_parity_layered(case, impl, monkeypatch):
+    """The steady cases of tests/test_engine_gpu.py (no time column, dNt and the rows behind bDof fed but unused) on both
+    implementations of the layer-by-layer route, against the fp64 oracle at the same bars."""
+    if impl == 'gemms':
+        monkeypatch.setenv('VN_LAYERED_NOWIDE', '1')
+    eng, d, flat = steady_setup(case, LAYERED)
+    assert eng.kernel_path()[0] == LAYERED
+    steady_check(eng, d, flat, case, 'case%d layered-%s %s %s q%d' % (STEADY.index(case), impl, case[2], case[7], case[3]))
     eng.close()
 
 

@@ -5,6 +5,7 @@ autograd restatement of the reference graph and the hand-derived tangent formula
 kernels implement, TF-1 Adam known answer, glorot limits, shard rule.
 """
 import numpy as np
+import pytest
 import torch
 
 from oracle import tf1_graph as og
@@ -130,3 +131,112 @@ def test_tf1_rmsprop_known_answer():
     th2 = opt.step(th1, g)
     ms2 = ms1 + (g * g - ms1) * 0.1
     np.testing.assert_allclose(th2, th1 - 1e-2 * g / np.sqrt(ms2 + 1e-10), rtol=1e-15)
+
+
+# ---- the steady (time-independent) problem: ADPDE's default timeDependent=False (no time column, no dNt term, no IC rows) ----
+STEADY_SHAPES = [
+    # d_in dim  (d_in == dim + 1: a steady MOR-style input whose last column is a parameter, not time)
+    (1, 1),
+    (2, 2),
+    (2, 1),
+    (3, 2),
+]
+
+
+def _steady_case(seed, d_in, dim, widths=(7, 5, 6), q=8, n_k=5, nB=11, bDof=7):
+    flat, widths, d_in, dim, q, n_k, kw = _case(seed, d_in, dim, widths, q, n_k, nB, bDof)
+    kw['time_dependent'] = False
+    return flat, widths, d_in, dim, q, n_k, kw
+
+
+def _steady_field(d_in, dim, seed=1, n=6, widths=(6, 7)):
+    widths = list(widths)
+    rng = np.random.default_rng(seed)
+    flat = 2.0 * og.glorot_init(d_in, widths, 4).astype(np.float64)
+    X = rng.uniform(-1, 1, (n, d_in))
+    diff = rng.uniform(.1, 1, (n, 1)); vel = rng.standard_normal((n, dim))
+    src = rng.standard_normal((n, 1)); ddx = rng.standard_normal((n, dim))
+    return flat, widths, X, diff, vel, src, ddx
+
+
+@pytest.mark.parametrize('d_in,dim', STEADY_SHAPES)
+def test_steady_model_grad_has_no_time_derivative_and_matches_finite_differences(d_in, dim):
+    flat, widths, X, _, _, _, _ = _steady_field(d_in, dim)
+    params = og.unflatten(flat, d_in, widths, torch.float64)
+    Xt = torch.tensor(X, requires_grad=True)
+    Val, dM_dx, dM_dt, lap = og.model_grad(params, Xt, dim, time_dependent=False, need_hess=True)
+    assert dM_dt is None
+    assert dM_dx.shape == (X.shape[0], dim)
+    f = lambda Z: og.forward(flat, d_in, widths, torch.float64, Z)
+    h = 1e-4
+    grad = np.zeros((X.shape[0], dim)); lapfd = np.zeros((X.shape[0], 1))
+    for d in range(dim):
+        e = np.zeros(d_in); e[d] = h
+        grad[:, d:d + 1] = (f(X + e) - f(X - e)) / (2 * h)
+        lapfd += (f(X + e) - 2 * f(X) + f(X - e)) / h ** 2
+    np.testing.assert_allclose(Val.detach().numpy(), f(X), rtol=1e-14)
+    np.testing.assert_allclose(dM_dx.detach().numpy(), grad, rtol=1e-7, atol=1e-9)
+    np.testing.assert_allclose(lap.detach().numpy(), lapfd, rtol=1e-5, atol=1e-6)
+
+
+@pytest.mark.parametrize('d_in,dim', STEADY_SHAPES)
+def test_steady_residual_finite_difference_and_time_identity(d_in, dim):
+    """residual(time_dependent=False) = diff*Lap u - (vel - ddx).grad u + src by finite differences; where a column
+    behind the spatial ones exists, residual_td - residual_steady = -du/dx_dim on the same inputs (the steady
+    residual does not read that column as time)."""
+    flat, widths, X, diff, vel, src, ddx = _steady_field(d_in, dim, seed=2)
+    u, res = og.residual(flat, d_in, widths, torch.float64, X, diff, vel, src, ddx, dim, False)
+    f = lambda Z: og.forward(flat, d_in, widths, torch.float64, Z)
+    h = 1e-4
+    grad = np.zeros((X.shape[0], d_in)); lap = np.zeros((X.shape[0], 1))
+    for d in range(d_in):
+        e = np.zeros(d_in); e[d] = h
+        grad[:, d:d + 1] = (f(X + e) - f(X - e)) / (2 * h)
+        if d < dim:
+            lap += (f(X + e) - 2 * f(X) + f(X - e)) / h ** 2
+    ref = diff * lap - ((vel - ddx) * grad[:, :dim]).sum(1, keepdims=True) + src
+    np.testing.assert_allclose(u, f(X), rtol=1e-14)
+    np.testing.assert_allclose(res, ref, rtol=1e-5, atol=1e-6)
+    if d_in > dim:
+        _, res_td = og.residual(flat, d_in, widths, torch.float64, X, diff, vel, src, ddx, dim, True)
+        np.testing.assert_allclose(res_td - res, -grad[:, dim:dim + 1], rtol=1e-6, atol=1e-8)
+        assert np.max(np.abs(res_td - res)) > 1e-2 * np.max(np.abs(res))     # the identity is not vacuous here
+
+
+@pytest.mark.parametrize('d_in,dim', STEADY_SHAPES)
+def test_steady_autograd_graph_equals_tangent_formulation(d_in, dim):
+    flat, widths, d_in, dim, q, n_k, kw = _steady_case(11, d_in, dim)
+    res, g = og.loss_and_grad(flat, d_in, widths, torch.float64, **kw)
+    res2, g2 = tr.loss_and_grad(flat, d_in, widths, dim, kw['Input'], kw['gcoef'], kw['source'], kw['N'],
+                                kw['dNt'], kw['integW'], n_k, q, kw['detJ'], kw['biInput'], kw['biLabel'],
+                                kw['bDof'], kw['biDimVal'], kw['w'], time_dependent=False)
+    assert res['ICloss'] == 0.0 and res2['ICloss'] == 0.0
+    for k in ('loss', 'BCloss', 'varLoss'):
+        np.testing.assert_allclose(res2[k], res[k], rtol=1e-13)
+    np.testing.assert_allclose(res2['lossVec'], res['lossVec'].reshape(-1), rtol=1e-12)
+    np.testing.assert_allclose(g2, g, rtol=1e-10, atol=1e-12)
+    # neither dNt nor the rows behind bDof enter a steady loss: the same loss from scrambled dNt / IC rows
+    kw2 = dict(kw, dNt=-3.0 * kw['dNt'] + 1.0, biInput=kw['biInput'].copy(), biLabel=kw['biLabel'].copy())
+    kw2['biInput'][kw['bDof']:] += 0.5
+    kw2['biLabel'][kw['bDof']:] -= 1.0
+    res3, g3 = og.loss_and_grad(flat, d_in, widths, torch.float64, **kw2)
+    assert res3['loss'] == res['loss'] and np.array_equal(g3, g)
+    # ... while the time-dependent loss of the same inputs differs by far more than any device bar
+    rtd, gtd = og.loss_and_grad(flat, d_in, widths, torch.float64, **dict(kw, time_dependent=True))
+    assert abs(rtd['loss'] - res['loss']) > 1e-2 * abs(res['loss'])
+    assert np.max(np.abs(gtd - g)) > 1e-2 * np.max(np.abs(g))
+
+
+@pytest.mark.parametrize('d_in,dim', [(1, 1), (3, 2)])
+def test_steady_parameter_gradient_finite_difference(d_in, dim):
+    flat, widths, d_in, dim, q, n_k, kw = _steady_case(13, d_in, dim)
+    _, g = og.loss_and_grad(flat, d_in, widths, torch.float64, **kw)
+    rng = np.random.default_rng(0)
+    for i in rng.choice(flat.size, 12, replace=False):
+        e = 1e-6
+        fp, fm = flat.copy(), flat.copy()
+        fp[i] += e
+        fm[i] -= e
+        lp = og.loss_and_grad(fp, d_in, widths, torch.float64, **kw)[0]['loss']
+        lm = og.loss_and_grad(fm, d_in, widths, torch.float64, **kw)[0]['loss']
+        np.testing.assert_allclose((lp - lm) / (2 * e), g[i], rtol=2e-6, atol=1e-7)

@@ -11,6 +11,7 @@ import torch
 
 from oracle import tf1_graph as og
 from tests.test_varnet_host import cExact, pi
+from tests.test_engine_gpu import ERRORS, _dump_errors  # noqa: F401 (autouse: the steady runs' errors)
 from varnet_amd import ADPDE, Domain1D, PolygonDomain2D, MOR, VarNet
 
 pytestmark = pytest.mark.gpu
@@ -428,3 +429,63 @@ def test_shuffled_feeds_on_device(tmp_path):
     res = vn.train(str(tmp_path), weight=[10., 10., 1.], epochNum=12, saveFreq=100, verbose=False, batchNum=3, shuffleData=True)
     assert np.isfinite(res.lossAll).all() and vn.engine.step == 36
     vn.engine.close()
+
+
+def _steady(kind):
+    if kind == '1d':
+        pde = ADPDE(Domain1D(), diff=0.1 / pi, vel=1.0, source=lambda x, t=0: 1.0 + x ** 2,
+                    BCs=[[0., 1., 0.5], [0., 2., 1.0]], cEx=lambda x, t=0: 0.5 + 0.25 * (x + 1.0) ** 2)
+        return VarNet(pde, layerWidth=[20, 20, 20], discNum=15, bDiscNum=None, tDiscNum=[])
+    verts = np.array([[0.0, -0.5], [0.0, -0.2], [0.0, 0.2], [0.0, 0.5], [2.0, 0.5], [2.0, -0.5]])
+    pde = ADPDE(PolygonDomain2D(verts), BCs=[[], [0.0, 1.0, 1.0], [], [], [], []],
+                diff=lambda x, t=0: 1e-2 * (1.0 + x[:, 1:2] ** 2),
+                vel=lambda x, t=0: np.hstack([1.0 + 0.0 * x[:, 0:1], 0.1 * x[:, 0:1]]),
+                source=lambda x, t=0: np.sin(x[:, 0:1]) * (1.0 + x[:, 1:2]),
+                d_diff=lambda x, t=0: np.hstack([0.0 * x[:, 0:1], 2e-2 * x[:, 1:2]]))
+    return VarNet(pde, layerWidth=[20, 20, 20], discNum=[6, 4], bDiscNum=4, tDiscNum=[])
+
+
+@pytest.mark.parametrize('kind', ['1d', '2d'])
+def test_steady_training_on_device_matches_the_oracle_engine(kind, tmp_path, monkeypatch):
+    """A steady VarNet (timeDependent=False: no time column, IC weight 0) trained 300 epochs on the HIP engine with dedup='auto',
+    forced on and off, and on tests/oracle_engine.OracleEngine (CPU fp64, same glorot init): loss trajectories and final
+    parameters at the bars of the trajectory tests; residual() and evaluate() on the device against the oracle."""
+    from tests.oracle_engine import OracleEngine
+    epochs, runs, rec = 300, {}, {}
+    for mode in ('auto', True, False, 'oracle'):
+        if mode == 'oracle':
+            def make(self, processors):
+                fd = self.fixData
+                return OracleEngine(self.dim, self.inpDim, self.layerWidth, self.PDE.timeDependent, fd.integNum,
+                                    isSource=self.lossOpt['isSource'], integWflag=self.lossOpt['integWflag'],
+                                    learning_rate=self.learning_rate)
+            monkeypatch.setattr(VarNet, '_make_engine', make)
+        vn = _steady(kind)
+        assert not vn.PDE.timeDependent and vn.inpDim == vn.dim
+        res = vn.train(str(tmp_path / str(mode)), weight=[10., 1.], epochNum=epochs, saveFreq=epochs, verbose=False,
+                       dedup=False if mode == 'oracle' else mode)
+        runs[mode] = (np.array(res.lossAll), vn.engine.get_params().astype(np.float64))
+        if mode == 'oracle':
+            break
+        rec[str(mode)] = {'dedup_on': bool(vn.tData.dedup_on)}
+        # evaluate() / residual() on the device against the oracle at the device's own parameters
+        flat = runs[mode][1]
+        ui = vn.fixData.uniform_input
+        uref = og.forward(flat, vn.inpDim, vn.layerWidth, torch.float64, ui)
+        rec[str(mode)]['evaluate'] = float(np.max(np.abs(vn.evaluate() - uref)))
+        diff, vel, src = vn.fixData.uniform_inpData
+        _, rref = og.residual(flat, vn.inpDim, vn.layerWidth, torch.float64, ui, diff, vel, src, vn.fixData.d_diff, vn.dim,
+                              False)
+        rec[str(mode)]['residual'] = float(np.max(np.abs(vn.residual()[1] - rref))) / max(1.0, float(np.max(np.abs(rref))))
+        vn.engine.close()
+        assert rec[str(mode)]['evaluate'] < 5e-6 and rec[str(mode)]['residual'] < 2e-4, rec
+    assert not rec['False']['dedup_on'] and rec['True']['dedup_on']
+    l_or, flat_or = runs['oracle']
+    for mode in ('auto', True, False):
+        loss, flat = runs[mode]
+        assert loss.shape == l_or.shape and loss[-1] < loss[0]
+        rec[str(mode)]['loss'] = float(np.max(np.abs(loss - l_or) / np.abs(l_or)))
+        rec[str(mode)]['params'] = float(np.max(np.abs(flat - flat_or)) / np.max(np.abs(flat_or)))
+    ERRORS['steady training %s' % kind] = rec
+    for mode in ('auto', 'True', 'False'):
+        assert rec[mode]['loss'] <= 1e-2 and rec[mode]['params'] <= 2e-3, rec

@@ -931,6 +931,8 @@ int vn_set_bic(vn_engine* h, const float* biInput, const float* biLabel, int64_t
   if (nB < 0 || bDof < 0 || bDof > nB) return fail(VN_EINVAL, "need 0 <= bDof <= nB");
   if (nB > 0 && (!biInput || !biLabel)) return fail(VN_EINVAL, "null argument");
   HIPCHK(hipSetDevice(h->cfg.device));
+  // a steady problem has no initial condition (TFModel.py:646-650): rows behind bDof are never part of its loss
+  if (!h->cfg.time_dependent) nB = bDof;
   h->biInput = biInput; h->biLabel = biLabel; h->nB = nB; h->bDof = bDof; h->biDimVal = biDimVal;
   if (nB > h->work_b) {
     long c0 = h->work_b, c1 = h->work_b;
