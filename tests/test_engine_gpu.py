@@ -10,12 +10,12 @@ import pytest
 import torch
 
 from oracle import tf1_graph as og
+from tests.gradcheck import assert_columns_close, assert_grad_close, assert_pair_close, block_errors, column_errors
+from tests.parity_cases import (CASES, GRAD_RTOL, LOSS_RTOL, LVEC_RTOL, STEADY, oracle_eval,  # noqa: F401 (re-exported)
+                                steady_inputs, steady_oracle, synth)
 
 pytestmark = pytest.mark.gpu
 
-LOSS_RTOL = 1e-5
-GRAD_RTOL = 1e-4
-LVEC_RTOL = 1e-4
 
 # measured worst-case deviations per parity case, written to gpurun_out/parity_errors.json at the end of the
 # module (copied to profiles/ when a round's numbers are recorded)
@@ -36,81 +36,10 @@ def _dump_errors():
         pass
 
 
-def synth(seed, d_in, dim, widths, integNum, n_k, nB, bDof, source=False, integW=False, detJvec=False):
-    rng = np.random.default_rng(seed)
-    n = n_k * integNum
-    d = dict(
-        Input=rng.uniform(-1, 1, (n, d_in)).astype(np.float32),
-        gcoef=rng.standard_normal((n, dim)).astype(np.float32),
-        source=rng.standard_normal((n, 1)).astype(np.float32) if source else None,
-        N1=rng.uniform(0, 1, integNum).astype(np.float32),
-        dNt1=rng.standard_normal(integNum).astype(np.float32),
-        integW=rng.uniform(0.5, 1.0, (1, integNum)).astype(np.float32) if integW else None,
-        detJ=(rng.uniform(0.1, 0.2, (n_k, 1)).astype(np.float32) if detJvec else np.float32(0.137)),
-        biInput=rng.uniform(-1, 1, (nB, d_in)).astype(np.float32),
-        biLabel=rng.standard_normal((nB, 1)).astype(np.float32),
-        w=np.array([3.0, 2.0, 5.0]),
-    )
-    d['N'] = np.tile(d['N1'], n_k).reshape(n, 1)
-    d['dNt'] = np.tile(d['dNt1'], n_k).reshape(n, 1)
-    return d
-
-
 def make_engine(d_in, dim, widths, integNum, source, integW, kernel=0, optimizer_name='adam'):
     from varnet_amd.engine import VNEngine
     return VNEngine(dim, d_in, widths, True, integNum, isSource=source, integWflag=integW, kernel=kernel,
                     optimizer_name=optimizer_name)
-
-
-def oracle_eval(flat, d, d_in, dim, widths, integNum, n_k, bDof, source, integW, detJvec, time_dependent=True):
-    kw = dict(Input=d['Input'].astype(np.float64), gcoef=d['gcoef'].astype(np.float64),
-              source=None if d['source'] is None else d['source'].astype(np.float64),
-              N=d['N'].astype(np.float64), dNt=d['dNt'].astype(np.float64),
-              integW=None if d['integW'] is None else d['integW'].astype(np.float64),
-              intShape=[n_k, integNum],
-              detJ=(d['detJ'].astype(np.float64) if detJvec else float(d['detJ'])), detJvec=detJvec,
-              biInput=d['biInput'].astype(np.float64), biLabel=d['biLabel'].astype(np.float64),
-              bDof=bDof, biDimVal=2.0, w=d['w'], dim=dim, time_dependent=time_dependent,
-              is_source=source, integWflag=integW)
-    return og.loss_and_grad(flat.astype(np.float64), d_in, widths, torch.float64, **kw)
-
-
-CASES = [
-    # d_in dim widths            integNum n_k  nB  bDof source integW detJvec
-    (2, 1, [20, 20, 20],         16,      40,  50, 30,  False, False, False),
-    (3, 2, [50, 50, 50, 50, 50], 64,      9,   77, 40,  False, False, False),
-    (3, 2, [10, 20],             64,      5,   33, 20,  True,  False, False),
-    (3, 1, [10, 20, 30],         16,      21,  19, 7,   False, False, False),   # MOR-style extra input
-    (2, 1, [7],                  36,      11,  40, 13,  True,  True,  True),
-    (3, 2, [64, 64, 64],         216,     3,   5,  2,   False, True,  False),
-    (3, 2, [50, 50, 50, 50, 50], 64,      300, 1000, 600, False, False, False),
-    (2, 1, [50, 50, 50, 50],     16,      801, 450, 400, True,  False, True),     # config-2 shaped
-    (3, 2, [20, 20, 20],         64,      33,  70,  30,  True,  False, False),
-    (3, 2, [32, 17],             32,      50,  10,  4,   False, True,  True),
-    (2, 1, [20, 20, 20],         36,      41,  25,  9,   True,  True,  False),    # 3-point Gauss, 1D+t
-    (3, 2, [50, 50, 50],         36,      17,  12,  5,   False, True,  True),
-    (3, 2, [50, 50, 50],         216,     7,   40,  22,  True,  True,  False),   # 3-point Gauss, 2D+t: two-pass fused
-    (3, 2, [20, 20, 20, 20],     216,     5,   9,   4,   False, True,  True),
-    (3, 2, [60, 60, 60, 60],     64,      30,  50,  20,  False, False, False),   # widths 51..63: KS = 16 fused tiles
-    (3, 2, [51, 63, 57],         36,      17,  12,  5,   True,  True,  True),
-    (2, 1, [63, 63],             16,      90,  33,  11,  True,  False, False),
-    (3, 2, [60, 60, 60, 60, 60], 64,      9,   77,  40,  False, False, False),
-    (3, 2, [64, 64],             64,      6,   20,  8,   False, False, False),   # 64 wide: bias gradient by thin_bias
-    (2, 1, [20],                 16,      300, 40,  25,  False, False, False),   # one hidden layer (Operator_1Dt.py:156)
-    (3, 2, [50],                 64,      40,  30,  10,  True,  False, True),
-    (3, 2, [60],                 36,      21,  30,  10,  False, True,  False),
-    (3, 2, [50] * 6,             64,      12,  30,  10,  False, False, False),   # six hidden layers, 50 wide
-    (3, 2, [64, 64, 64, 64],     64,      40,  70,  30,  True,  False, True),    # 64 wide, several tiles
-    (2, 1, [64, 40, 64],         16,      77,  33,  11,  False, False, False),   # 64 wide next to narrower layers
-    (3, 2, [64],                 36,      21,  30,  10,  False, True,  False),   # one 64-wide layer: output bias per lane
-    (3, 2, [64] * 6,             64,      12,  30,  10,  True,  False, False),   # six 64-wide layers: flush image over the weight images
-    (3, 2, [60, 64, 51, 64, 56, 63], 36,  17,  12,  5,   False, True,  True),
-    # KS = 8 (widths 21..32): padding-only k-steps / row tiles are branched over on the layers' real widths, the bias row rides at the
-    # position of feature 31 unless the input side is exactly 32 wide (then thin_bias + the serial flush): ADVICE r3
-    (3, 2, [31, 32, 17],         64,      21,  30,  10,  False, False, False),
-    (2, 1, [17, 32, 32, 21],     16,      90,  33,  11,  True,  False, True),
-    (3, 1, [32, 32],             16,      40,  19,  7,   False, True,  False),
-]
 
 
 def _skip_unsupported(kernel, widths, integNum):
@@ -161,6 +90,9 @@ def test_loss_and_grad_parity(case, kernel):
     rec['grad'] = float(err)
     ERRORS['case%d_%s' % (CASES.index(case), ['auto', 'generic', 'fused32', 'fused16'][kernel])] = rec
     assert err <= GRAD_RTOL, err
+    assert_grad_close(g, gref, d_in, widths, GRAD_RTOL, dim=dim, rec=rec, what='case%d' % CASES.index(case),
+                      g32=lambda: oracle_eval(flat, d, d_in, dim, widths, integNum, n_k, bDof, source, integW, detJvec,
+                                              dtype=torch.float32)[1])
     eng.close()
 
 
@@ -255,6 +187,9 @@ def test_rmsprop_trajectory_parity():
     ref = np.array(ref)
     assert np.max(np.abs(got - ref) / np.abs(ref)) <= 1e-3
     assert np.max(np.abs(eng.get_params() - th)) <= 2e-3 * np.max(np.abs(th))
+    pe = block_errors(eng.get_params(), th, d_in, widths, dim)          # and every parameter tensor on its own scale
+    ERRORS['rmsprop_trajectory_params'] = pe
+    assert max(pe.values()) <= 2e-3, pe
     st = eng.export_state()
     p1 = eng.get_params()
     eng.init_params(seed=9)
@@ -295,27 +230,6 @@ def test_train_epoch_equals_single_steps():
         e.close()
 
 
-STEADY = [
-    # time-independent: no IC rows, no dNt term (TFModel.py:537,646-650); nonzero dNt tables and rows behind bDof are fed
-    # all the same (a route that read them would be caught: the oracle ignores both for a steady problem)
-    # d_in dim widths        integNum n_k nB  bDof act        integW detJvec
-    (1, 1, [20, 20],         4,       37, 2,  2,   'sigmoid', False, False),
-    (2, 2, [20, 20, 20],     16,      50, 60, 60,  'sigmoid', False, False),
-    (2, 2, [50, 50, 50],     16,      129, 33, 33, 'sigmoid', False, False),
-    (2, 2, [7, 9],           36,      11, 20, 20,  'sigmoid', True,  False),
-    (1, 1, [20],             6,       40, 2,  2,   'sigmoid', True,  False),   # 1D three-point Gauss: 21 test functions per 128-row tile
-    (1, 1, [50] * 5,         6,       77, 2,  2,   'tanh',    True,  True),
-    (2, 2, [64, 64, 64],     16,      60, 40, 25,  'sigmoid', False, True),    # rows behind bDof: ignored by a steady loss
-    (2, 2, [60, 64, 51],     36,      30, 30, 12,  'tanh',    True,  False),   # widths 51..64
-    (3, 2, [20, 20, 20],     16,      40, 30, 20,  'sigmoid', False, False),   # d_in = dim + 1: the extra column is NOT time
-    (3, 2, [60, 64, 51],     36,      17, 20, 20,  'sigmoid', True,  True),
-    (2, 1, [64, 64, 64],     4,       300, 2, 2,   'tanh',    False, True),    # d_in = dim + 1 in 1D
-    (2, 2, [50] * 5,         36,      400, 60, 60, 'sigmoid', True,  False),   # several hundred test functions
-    (2, 2, [128, 128],       16,      30, 40, 20,  'sigmoid', False, False),   # beyond the kernels: layer by layer
-    (1, 1, [300],            6,       25, 2,  2,   'tanh',    True,  True),
-]
-
-
 def steady_routes(widths, d_in):
     """Routes that serve a STEADY case: forced kernels only where the network is in their range."""
     in_range = max(widths) <= 64 and len(widths) <= 6 and d_in <= 8
@@ -325,41 +239,16 @@ def steady_routes(widths, d_in):
 def steady_setup(case, kernel, seed=7):
     from varnet_amd.engine import VNEngine
     d_in, dim, widths, q, n_k, nB, bDof, act, has_w, detJvec = case
-    rng = np.random.default_rng(seed)
-    n = n_k * q
-    d = dict(Input=rng.uniform(-1, 1, (n, d_in)).astype(np.float32),
-             gcoef=rng.standard_normal((n, dim)).astype(np.float32),
-             source=rng.standard_normal((n, 1)).astype(np.float32),
-             N1=rng.uniform(0, 1, q).astype(np.float32))
-    d['integW'] = rng.uniform(0.5, 1, (1, q)).astype(np.float32) if has_w else None
-    d['biInput'] = rng.uniform(-1, 1, (nB, d_in)).astype(np.float32)
-    d['biLabel'] = rng.standard_normal((nB, 1)).astype(np.float32)
-    d['dNt1'] = rng.standard_normal(q).astype(np.float32)
-    d['detJ'] = rng.uniform(0.01, 0.03, (n_k, 1)).astype(np.float32) if detJvec else np.float32(0.02)
-    d['w'] = np.array([4.0, 0.0, 3.0])                              # VarNet.py:1132: IC weight 0
+    d, flat = steady_inputs(case, seed)
     eng = VNEngine(dim, d_in, widths, False, q, isSource=True, integWflag=has_w, kernel=kernel, activationFun=act)
     eng.init_params(seed=2)
-    flat = eng.get_params()
-    flat = flat + 0.05 * np.random.default_rng(5).standard_normal(flat.size).astype(np.float32)
+    assert np.array_equal(eng.get_params(), og.glorot_init(d_in, widths, 2))
     eng.set_params(flat)
     eng.set_fe_table(d['N1'], d['dNt1'], d['integW'])
     eng.set_interior(0, d['Input'], d['gcoef'], d['source'], n_k=n_k, detJ=d['detJ'])
     eng.set_bic(d['biInput'], d['biLabel'], bDof, 1.5)
     eng.set_weights(d['w'])
     return eng, d, flat
-
-
-def steady_oracle(flat, d, case):
-    d_in, dim, widths, q, n_k, nB, bDof, act, has_w, detJvec = case
-    n = n_k * q
-    f64 = lambda a: None if a is None else a.astype(np.float64)
-    return og.loss_and_grad(
-        flat.astype(np.float64), d_in, widths, torch.float64, Input=f64(d['Input']), gcoef=f64(d['gcoef']),
-        source=f64(d['source']), N=np.tile(d['N1'], n_k).reshape(n, 1).astype(np.float64),
-        dNt=np.tile(d['dNt1'], n_k).reshape(n, 1).astype(np.float64), integW=f64(d['integW']), intShape=[n_k, q],
-        detJ=f64(d['detJ']) if detJvec else float(d['detJ']), detJvec=detJvec, biInput=f64(d['biInput']),
-        biLabel=f64(d['biLabel']), bDof=bDof, biDimVal=1.5, w=d['w'], dim=dim, time_dependent=False, is_source=True,
-        integWflag=has_w, activation=act)
 
 
 def steady_check(eng, d, flat, case, tag):
@@ -386,6 +275,8 @@ def steady_check(eng, d, flat, case, tag):
     assert abs(g[P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
     assert abs(g[P + 2]) == 0.0                                      # ICloss is the constant 0
     assert rec['grad'] <= GRAD_RTOL, rec
+    assert_grad_close(g, gref, case[0], case[2], GRAD_RTOL, dim=case[1], td=False, rec=rec, what='steady ' + tag,
+                      g32=lambda: steady_oracle(flat, d, case, torch.float32)[1])
 
 
 _KERNEL = {'generic': 1, 'auto': 0, 'fused16': 3}
@@ -400,6 +291,36 @@ def test_steady_problem_parity(case, kernel):
     elif kernel == 'generic':
         assert eng.kernel_path()[0] == 1
     steady_check(eng, d, flat, case, 'case%d %s %s %s q%d' % (STEADY.index(case), kernel, case[2], case[7], case[3]))
+    eng.close()
+
+
+def test_nine_inputs_run_layer_by_layer_and_the_fused_family_refuses_them():
+    """VN_KMAX_DIN = 8: at d_in = 9 AUTO takes the layer-by-layer route and matches the oracle; forcing the 8-wave fused kernel
+    (or the generic kernels) is refused with a sentence, not a fault."""
+    from varnet_amd.engine import VNEngine, VNError
+    d_in, dim, widths, q, n_k, nB, bDof = 9, 2, [50] * 5, 64, 20, 40, 20
+    for kernel in (3, 1):
+        with pytest.raises(VNError, match='outside the range of the requested kernel family'):
+            VNEngine(dim, d_in, widths, True, q, kernel=kernel)
+    d = synth(13, d_in, dim, widths, q, n_k, nB, bDof, True, True, False)
+    eng = make_engine(d_in, dim, widths, q, True, True, 0)
+    assert eng.kernel_path()[0] == 4
+    eng.init_params(seed=3)
+    flat = eng.get_params() + 0.05 * np.random.default_rng(5).standard_normal(eng.P).astype(np.float32)
+    eng.set_params(flat)
+    eng.set_fe_table(d['N1'], d['dNt1'], d['integW'])
+    eng.set_interior(0, d['Input'], d['gcoef'], d['source'], n_k=n_k, detJ=d['detJ'])
+    eng.set_bic(d['biInput'], d['biLabel'], bDof, 2.0)
+    eng.set_weights(d['w'])
+    ref, gref = oracle_eval(flat, d, d_in, dim, widths, q, n_k, bDof, True, True, False)
+    gb = eng.bind_grad_buffer()
+    eng.grad(0)
+    torch.cuda.synchronize()
+    g = gb.cpu().numpy()
+    assert abs(g[eng.P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
+    rec = ERRORS.setdefault('d_in9 auto (layer by layer)', {})
+    assert_grad_close(g, gref, d_in, widths, GRAD_RTOL, dim=dim, rec=rec,
+                      g32=lambda: oracle_eval(flat, d, d_in, dim, widths, q, n_k, bDof, True, True, False, dtype=torch.float32)[1])
     eng.close()
 
 
@@ -470,6 +391,7 @@ def test_per_row_tables_and_detjvec_parity(q, widths, kernel):
     g = gb.cpu().numpy()
     assert abs(g[eng.P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
     assert np.max(np.abs(g[:eng.P] - gref)) <= GRAD_RTOL * np.max(np.abs(gref))
+    ERRORS['per_row_tables q%d %s %s' % (q, widths, kernel)] = assert_grad_close(g, gref, d_in, widths, GRAD_RTOL, dim=dim)
     eng.close()
 
 
@@ -496,6 +418,11 @@ def _csr(uid, U):
     # beyond one 128-point tile (the two-pass route's networks): the formulation has no tiles of whole test functions
     (3, 2, [50, 50, 50, 50, 50], 216, 11,  410,  33, 17,  True,  True),       # integPnum 3 in 2D+t
     (4, 3, [20, 30],             256, 7,   600,  12, 6,   False, False),      # integPnum 2 in 3D+t
+    # 6 and 8 inputs (MOR parameters): the point kernels' second input k-step, in 2D and in 3D
+    (6, 2, [50, 50, 50],         64,  30,  500,  40, 22,  True,  False),      # 2D+t + 3 parameters
+    (8, 2, [32, 17],             216, 9,   500,  12, 6,   True,  True),       # 2D+t + 5 parameters, two-pass network
+    (6, 3, [64, 64, 64],         16,  40,  400,  20, 10,  False, True),       # 3D+t + 2 parameters
+    (8, 3, [50, 50, 50, 50],     64,  21,  333,  40, 22,  True,  False),      # 3D+t + 4 parameters
 ])
 def test_dedup_formulation_parity(case):
     """De-duplicated formulation (one network evaluation per unique quadrature point): same loss
@@ -558,6 +485,12 @@ def _dedup_parity(case, td, tag=None):
     for g in (g_rows, g_dd):
         assert abs(g[P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
         assert np.max(np.abs(g[:P] - gref)) <= GRAD_RTOL * np.max(np.abs(gref))
+    rec = ERRORS.setdefault(tag or 'dedup %s d_in%d q%d' % (widths, d_in, q), {})
+    for name, g in (('rowwise', g_rows), ('dedup', g_dd)):
+        r = assert_grad_close(g, gref, d_in, widths, GRAD_RTOL, dim=dim, td=td, what=name)
+        rec.update({'worst_block_' + name: r['worst_block'], 'worst_block_err_' + name: r['worst_block_err']})
+    r = assert_pair_close(g_dd, g_rows, d_in, widths, 2e-4, dim=dim, td=td, what='dedup vs row-wise')
+    rec.update(worst_block_dedup_vs_rowwise=r['worst_block'], worst_block_err_dedup_vs_rowwise=r['worst_block_err'])
     assert np.allclose(g_dd[P + 1:P + 4], g_rows[P + 1:P + 4], rtol=1e-5)
     # vn_eval_loss (splitLoss: every monitor, trainWeight) of a batch that carries the map: (u, grad u) once per unique point and the
     # loss-only form of the assembly kernel (round 6) -- loss components and loss field against the fp64 oracle at the suite's bars,
@@ -595,6 +528,8 @@ DEDUP_STEADY = [
     (2, 2, [64, 64, 64],         36,  30,  400,  40, 22,  True,  True),
     (3, 2, [20, 30],             36,  21,  333,  12, 6,   False, True),       # d_in = dim + 1: the extra column is not time
     (3, 2, [60, 64, 51],         16,  45,  500,  9,  4,   True,  False),
+    (6, 2, [33, 50, 41],         16,  40,  300,  20, 20,  True,  False),      # 2D + 4 parameters
+    (8, 3, [20, 30],             36,  21,  333,  12, 6,   False, True),       # 3D + 5 parameters
 ]
 
 
@@ -641,6 +576,7 @@ def test_forward_grad_parity(d_in, dim, widths, act, n):
     uref, gref = Val.detach().numpy().reshape(-1), dM_dx.detach().numpy()
     eu = np.max(np.abs(u.cpu().numpy() - uref)) / np.max(np.abs(uref))
     eg = np.max(np.abs(g.cpu().numpy() - gref)) / np.max(np.abs(gref))
+    egc = column_errors(g.cpu().numpy(), gref)                   # each spatial direction on its own scale
     # vn_forward: hidden widths 33..64 run the bf16-piece kernel (vn_split16.hip: six products of exact bf16 pieces per layer), the
     # others the value-only sweep of vn_pgrad16; route 2 forces the latter -- both against the oracle at the SAME bar, errors side by side
     # (the f32-MFMA forms of the networks vn_split16 serves live in the tests' cross-check library: an engine of that library)
@@ -656,12 +592,15 @@ def test_forward_grad_parity(d_in, dim, widths, act, n):
     euf = np.max(np.abs(uf32.cpu().numpy() - uref)) / np.max(np.abs(uref))
     egf = np.max(np.abs(gf32.cpu().numpy() - gref)) / np.max(np.abs(gref))
     assert euf <= 2e-6 and egf <= 1e-5, (euf, egf)          # vn_pgrad16 (f32 MFMA): round 5's kernel at round 5's bars
+    egfc = assert_columns_close(gf32.cpu().numpy(), gref, 1e-5, 'grad u, f32-MFMA kernel')
     ef = np.max(np.abs(u2.cpu().numpy() - uref)) / np.max(np.abs(uref))
     ef32 = np.max(np.abs(u2f.cpu().numpy() - uref)) / np.max(np.abs(uref))
     ERRORS['forward_grad %s %s' % (widths, act)] = {'u': float(eu), 'grad': float(eg), 'vn_forward': float(ef),
                                                     'vn_forward_f32_mfma_kernel': float(ef32), 'u_f32_mfma_kernel': float(euf),
-                                                    'grad_f32_mfma_kernel': float(egf)}
+                                                    'grad_f32_mfma_kernel': float(egf), 'grad_per_column': egc,
+                                                    'grad_f32_mfma_kernel_worst_column': egfc}
     assert eu <= 2e-6 and eg <= 1e-5, (eu, eg)
+    assert max(egc) <= 1e-5, egc
     assert ef <= 2e-6 and ef32 <= 2e-6, (ef, ef32)
     assert np.max(np.abs(u.cpu().numpy() - u2.cpu().numpy())) <= 2e-6 * np.max(np.abs(uref))      # vn_forward: the same values
     assert torch.equal(eng.forward(X), u2)                                                       # repeatable bit for bit
@@ -780,8 +719,29 @@ def test_steady_point_kernels_parity(d_in, dim, widths, act):
     """vn_forward, vn_forward_grad, vn_residual, vn_forward_f64 and vn_residual_f64 of a STEADY engine (the td = 0 branches:
     no time pass, no -du/dt term) against og.model_grad / og.residual with time_dependent=False, on every route that serves
     the network: the automatic one, the per-point kernels (route 1) and the f32-MFMA forms (route 2, cross-check library)."""
+    _point_kernels_parity(d_in, dim, widths, act, False, POINT_COUNTS)
+
+
+@pytest.mark.parametrize('d_in,dim,widths,act,td', [
+    # 5..8 inputs (MOR parameters): inputs 4..7 ride in the point kernels' second input k-step (KS0 = 2)
+    (5, 2, [50, 50, 50, 50, 50], 'sigmoid', True),   # bf16 pieces (vn_split16) | f32 MFMA (cross-check)
+    (6, 1, [20, 20, 20], 'tanh', True),              # vn_pgrad16 / vn_taylor16
+    (7, 3, [64, 51, 64], 'sigmoid', True),           # bf16 pieces, 3D+t + 3 parameters
+    (8, 3, [32, 17], 'sigmoid', True),               # vn_pgrad16 / vn_taylor16, 3D+t + 4 parameters
+    (8, 2, [40, 52, 64, 33], 'sigmoid', True),       # bf16 pieces, 2D+t + 5 parameters
+    (6, 3, [10, 20, 30], 'sigmoid', False),          # steady 3D + 3 parameters
+    (8, 2, [50, 50, 50], 'tanh', False),             # steady, bf16 pieces
+    (5, 1, [64] * 6, 'sigmoid', True),               # six 64-wide layers: the per-point fp64 kernel
+])
+def test_point_kernels_parity_five_to_eight_inputs(d_in, dim, widths, act, td):
+    """The method of test_steady_point_kernels_parity at 5..8 inputs, time-dependent and steady, on 1, 17 and 4099 points:
+    f32 and fp64 entry points against the fp64 oracle, the per-point kernels and the f32-MFMA forms; grad u per direction."""
+    _point_kernels_parity(d_in, dim, widths, act, td, (1, 17, 4099))
+
+
+def _point_kernels_parity(d_in, dim, widths, act, td, counts):
     from varnet_amd.engine import VNEngine
-    eng = VNEngine(dim, d_in, widths, False, 16, activationFun=act)
+    eng = VNEngine(dim, d_in, widths, td, 16, activationFun=act)
     layered = eng.kernel_path()[0] == 4
     assert layered == (max(widths) > 64)
     eng.init_params(seed=5)
@@ -789,22 +749,22 @@ def test_steady_point_kernels_parity(d_in, dim, widths, act):
     eng.set_params(flat)
     engx = None
     if not layered:
-        engx = VNEngine(dim, d_in, widths, False, 16, activationFun=act, xcheck=True)
+        engx = VNEngine(dim, d_in, widths, td, 16, activationFun=act, xcheck=True)
         engx.set_params(flat)
         engx.debug_point_route(2)
     params = og.unflatten(flat.astype(np.float64), d_in, widths, torch.float64)
     rec = {}
     rng = np.random.default_rng(23)
-    for n in POINT_COUNTS:
+    for n in counts:
         X = rng.uniform(-1.2, 1.2, (n, d_in))
         diff = rng.uniform(0.1, 1, (n, 1)); vel = rng.standard_normal((n, dim))
         src = rng.standard_normal((n, 1)); ddx = rng.standard_normal((n, dim))
-        uref, rref = og.residual(flat.astype(np.float64), d_in, widths, torch.float64, X, diff, vel, src, ddx, dim, False,
+        uref, rref = og.residual(flat.astype(np.float64), d_in, widths, torch.float64, X, diff, vel, src, ddx, dim, td,
                                  activation=act)
         uref, rref = uref[:, 0], rref[:, 0]
         uscale = max(1.0, float(np.max(np.abs(uref))))
         scale = max(1.0, float(np.max(np.abs(rref))))
-        if d_in > dim:
+        if d_in > dim and not td:
             # negative control: a kernel that took column `dim` for time would be off by |du/dx_dim|, far beyond the bar
             _, rtd = og.residual(flat.astype(np.float64), d_in, widths, torch.float64, X, diff, vel, src, ddx, dim, True,
                                  activation=act)
@@ -823,11 +783,12 @@ def test_steady_point_kernels_parity(d_in, dim, widths, act):
                 ug, g = en.forward_grad(X32)
                 torch.cuda.synchronize()
                 Xt = torch.tensor(X, requires_grad=True)
-                Val, dM_dx, dM_dt, _ = og.model_grad(params, Xt, dim, time_dependent=False, activation=act)
-                assert dM_dt is None
+                Val, dM_dx, dM_dt, _ = og.model_grad(params, Xt, dim, time_dependent=td, activation=act)
+                assert td or dM_dt is None
                 gref = dM_dx.detach().numpy()
                 e[pre + 'fg_u'] = float(np.max(np.abs(ug.cpu().numpy() - uref))) / uscale
                 e[pre + 'fg_grad'] = float(np.max(np.abs(g.cpu().numpy() - gref))) / max(1e-30, float(np.max(np.abs(gref))))
+                e[pre + 'fg_grad_worst_column'] = max(column_errors(g.cpu().numpy(), gref))   # asserted at the fg_grad bar
         u64 = eng.forward_f64(X)
         u64r, r64 = eng.residual(X, diff, vel, src, ddx, fp64=True)
         torch.cuda.synchronize()
@@ -848,7 +809,7 @@ def test_steady_point_kernels_parity(d_in, dim, widths, act):
                    else 4e-6 if k.startswith('f32_mfma_') and k.endswith('u')     # that kernel's bar in test_taylor_residual_parity
                    else 2e-6 if k.endswith('u') else 1e-5)
             assert v <= bar, (n, k, v, bar)
-    ERRORS['steady points %s %s d_in%d %s' % ('layered' if layered else 'kernels', widths, d_in, act)] = rec
+    ERRORS['%spoints %s %s d_in%d %s' % ('' if td else 'steady ', 'layered' if layered else 'kernels', widths, d_in, act)] = rec
     if engx is not None:
         engx.close()
     eng.close()
@@ -894,6 +855,7 @@ def test_dedup_periodic_gcoef_table_is_bitwise_the_csr_path(q, dim, d_in, widths
     torch.cuda.synchronize()
     g_rows = gb.cpu().numpy().copy()
     assert np.max(np.abs(g_tab[:eng.P] - g_rows[:eng.P])) <= 1e-4 * np.max(np.abs(g_rows[:eng.P]))
+    assert_pair_close(g_tab, g_rows, d_in, widths, 1e-4, dim=dim, what='periodic table vs row-wise')
     # one row off the period: the table must not be used (the general path then agrees with the row-wise launch on THAT data)
     g2 = gcoef.copy()
     g2[5 * q + 3, 0] += 0.75
@@ -903,6 +865,7 @@ def test_dedup_periodic_gcoef_table_is_bitwise_the_csr_path(q, dim, d_in, widths
     torch.cuda.synchronize()
     b = gb.cpu().numpy().copy()
     assert np.max(np.abs(a[:eng.P] - b[:eng.P])) <= 1e-4 * np.max(np.abs(b[:eng.P]))
+    assert_pair_close(a, b, d_in, widths, 1e-4, dim=dim, what='general path vs row-wise')
     assert not np.array_equal(a, g_tab)
     eng.close()
 
@@ -1007,6 +970,7 @@ def test_many_tiles_per_workgroup_fused_vs_generic(widths, q, n_k, src):
     P = g_gen.size - 4
     assert abs(g_a[P] - g_gen[P]) <= 2e-5 * abs(g_gen[P])
     assert np.max(np.abs(g_a[:P] - g_gen[:P])) <= 2e-4 * np.max(np.abs(g_gen[:P]))
+    ERRORS['many_tiles %s q%d fused vs generic' % (widths, q)] = assert_pair_close(g_a, g_gen, d_in, widths, 2e-4, dim=dim)
 
 
 # ---- reference-generated inputs (tests/golden/assembly.npz, written by oracle/gen_golden_assembly.py from the
@@ -1060,7 +1024,7 @@ def test_reference_assembled_inputs_through_engine(key, widths):
     # in fp32 (what TF-1 runs), deviates from fp64 by the same amount.  Bar: 1e-4 of the largest entry, or 4x the
     # fp32 restatement's own deviation from fp64, whichever is larger.
     kw32 = {k: (v.astype(np.float32) if isinstance(v, np.ndarray) and v.dtype == np.float64 else v) for k, v in kw.items()}
-    ref32, _ = og.loss_and_grad(flat, d_in, widths, torch.float32, **kw32)
+    ref32, gref32 = og.loss_and_grad(flat, d_in, widths, torch.float32, **kw32)
     own = float(np.max(np.abs(ref32['lossVec'].reshape(-1).astype(np.float64) - lref)))
     dv = float(np.max(np.abs(lv.cpu().numpy() - lref)))
     ERRORS[('golden_' if td else 'steady golden_') + key] = {'lossVec_abs': dv, 'lossVec_fp32_oracle_abs': own, 'lossVec_scale': float(np.max(np.abs(lref)))}
@@ -1071,6 +1035,8 @@ def test_reference_assembled_inputs_through_engine(key, widths):
     gg = gb.cpu().numpy()
     assert abs(gg[eng.P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
     assert np.max(np.abs(gg[:eng.P] - gref)) / np.max(np.abs(gref)) <= GRAD_RTOL
+    assert_grad_close(gg, gref, d_in, widths, GRAD_RTOL, g32=lambda: gref32, dim=dim, td=td, what=key,
+                      rec=ERRORS[('golden_' if td else 'steady golden_') + key])
     assert td or (out[2] == 0.0 and gg[eng.P + 2] == 0.0)             # a steady ICloss is the constant 0
     eng.close()
 
@@ -1103,6 +1069,7 @@ def test_empty_tower_feed(kernel):
     g = gb.cpu().numpy()
     assert abs(g[eng.P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
     assert np.max(np.abs(g[:eng.P] - gref)) <= GRAD_RTOL * np.max(np.abs(gref))
+    assert_grad_close(g, gref, 3, [50] * 3, GRAD_RTOL, dim=2, what='BC/IC rows only')
     eng.set_bic(None, None, 0, 2.0)                     # nothing at all
     out, _ = eng.eval_loss(0)
     eng.grad(0)
@@ -1134,6 +1101,9 @@ def test_six_wide_layers(kernel, path):
         g = gb.cpu().numpy()
         assert abs(g[eng.P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
         assert np.max(np.abs(g[:eng.P] - gref)) <= GRAD_RTOL * np.max(np.abs(gref))
+        ERRORS['six_wide %s %s' % (widths, kernel)] = assert_grad_close(
+            g, gref, 3, widths, GRAD_RTOL, dim=2, what=str(widths),
+            g32=lambda: oracle_eval(flat, d, 3, 2, widths, 16, 30, 15, False, False, False, dtype=torch.float32)[1])
         eng.close()
 
 

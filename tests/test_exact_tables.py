@@ -46,6 +46,7 @@ import pytest
 import torch
 
 from oracle import tf1_graph as og
+from tests.gradcheck import assert_grad_close, block_errors
 from varnet_amd import ADPDE, Domain1D, MOR, VarNet
 from varnet_amd.utility import UF
 
@@ -183,14 +184,17 @@ def test_cexact_restatements_match_reference_outputs():
     assert on_ic.sum() == 21 and np.allclose(g['c'][on_ic, 0], -np.sin(pi * g['x'][on_ic, 0]))
 
 
-def _grad_bar(theta, d_in, widths, kw64, gref, lref=None):
+def _grad_bar(theta, d_in, widths, kw64, gref, lref=None, g32_out=None):
     """Bar for the fp32 gradient at a CONVERGED theta.  Near a minimum the gradient is the small residual of large cancelling
     terms, so its relative fp32 error grows with the cancellation (here 4e-4 where a random theta gives 1e-6).  As in
     tests/fuzz_routes.py the bar follows the measured conditioning of the case, never a global loosening: the stated 1e-4,
-    or twice the deviation of the ORACLE's own fp32 run from its fp64 run on the same inputs, whichever is larger."""
+    or twice the deviation of the ORACLE's own fp32 run from its fp64 run on the same inputs, whichever is larger.  g32_out: a
+    list that receives the fp32 run's gradient (the per-block conditioning of tests/gradcheck.py reuses it)."""
     kw32 = {k: (v.astype(np.float32) if isinstance(v, np.ndarray) and v.dtype == np.float64 else v) for k, v in kw64.items()}
     r32, g32 = og.loss_and_grad(theta.astype(np.float32), d_in, widths, torch.float32, **kw32)
     cond = float(np.max(np.abs(np.asarray(g32, dtype=np.float64) - gref)) / np.max(np.abs(gref)))
+    if g32_out is not None:
+        g32_out.append(g32)
     if lref is not None:                    # the loss at a converged theta is a sum of squared small residuals R_k: same rule
         lcond = abs(float(r32['loss']) - lref) / abs(lref)
         assert cond <= GRAD_COND_CAP and lcond <= LOSS_COND_CAP, ('theta* is worse conditioned than any converged run so far', cond, lcond)
@@ -274,19 +278,23 @@ def test_config1_converged_run_against_cexact(tmp_path):
     gerr = float(np.max(np.abs(gh[:eng.P] - gref)) / np.max(np.abs(gref)))
     # (round 6: the loss at this theta* -- after the re-draw, a sum of 9 000 squared small residuals -- gets the same self-calibrated,
     # capped bar as the gradient and as the other converged runs' losses: 1.02e-5 measured where the oracle's own fp32 run deviates alike)
-    gbar, gcond, lbar, lcond = _grad_bar(theta, 2, [20, 20, 20], kw, gref, lref=float(ref['loss']))
+    g32s = []
+    gbar, gcond, lbar, lcond = _grad_bar(theta, 2, [20, 20, 20], kw, gref, lref=float(ref['loss']), g32_out=g32s)
+    blk = block_errors(gh, gref, 2, [20, 20, 20], dim=1)
     record('config1_converged', dict(epochs=len(res.lossAll), l2Err_cExact_hip=e_hip, l2Err_cExact_oracle_at_theta_star=e_orc,
                                      max_field_diff_hip_vs_oracle=fdiff, loss_rel_err_at_theta_star=float(lerr),
                                      grad_rel_err_at_theta_star=gerr, grad_rel_err_of_the_fp32_restatement_itself=gcond, grad_bar=gbar,
                                      loss_rel_err_of_the_fp32_restatement_itself=lcond, loss_bar=lbar,
                                      loss_first_last=[float(res.lossAll[0]), float(res.lossAll[-1])],
                                      training_sets_redrawn_at=[int(e) for e in res.inpIter], rows_after_the_redraw=144000,
+                                     grad_per_block=blk, grad_per_block_of_the_fp32_restatement=block_errors(g32s[0], gref, 2, [20, 20, 20], dim=1),
                                      train_weights_at_the_end=[float(x) for x in w_after], bar=CFG1_BAR))
     print('config 1, %d epochs: l2Err(cExact) hip %.5f oracle %.5f, field diff %.1e, loss/grad err at theta* %.1e / %.1e'
           % (len(res.lossAll), e_hip, e_orc, fdiff, lerr, gerr))
     assert e_hip <= CFG1_BAR and e_orc <= CFG1_BAR
     assert fdiff <= FWD_BAR
     assert lerr <= lbar and gerr <= gbar, (lerr, lbar, gerr, gbar)
+    assert_grad_close(gh, gref, 2, [20, 20, 20], 1e-4, g32=lambda: g32s[0], dim=1, global_bar=gbar, what='config 1 at theta*')
     eng.close()
 
 
@@ -411,7 +419,7 @@ def test_operator_1dtmor_converged_run_against_the_known_answers(tmp_path):
     w = np.array([3.0, 2.0, 5.0])
     eng.set_weights(w)
     gb = eng.bind_grad_buffer()
-    q, errs = fd.integNum, []
+    q, errs, blocks = fd.integNum, [], []
     f64 = lambda t: t.cpu().numpy().astype(np.float64)
     torch.set_num_threads(16)
     for mb, bi in ((0, 0), (2, 7), (5, 19)):
@@ -429,7 +437,11 @@ def test_operator_1dtmor_converged_run_against_the_known_answers(tmp_path):
                   biLabel=f64(d['biLabel']).reshape(-1, 1), bDof=fd.bDofsum, biDimVal=float(fd.biDimVal), w=w, dim=1,
                   time_dependent=True, is_source=False, integWflag=False)
         ref, gref = og.loss_and_grad(theta, 3, [10, 20, 30], torch.float64, **kw)
-        gbar, gcond, lbar, lcond = _grad_bar(theta, 3, [10, 20, 30], kw, gref, ref['loss'])
+        g32s = []
+        gbar, gcond, lbar, lcond = _grad_bar(theta, 3, [10, 20, 30], kw, gref, ref['loss'], g32_out=g32s)
+        out.setdefault('grad_per_block', []).append(block_errors(gh, gref, 3, [10, 20, 30], dim=1))
+        out.setdefault('grad_per_block_of_the_fp32_restatement', []).append(block_errors(g32s[0], gref, 3, [10, 20, 30], dim=1))
+        blocks.append((gh, gref, g32s[0], gbar, 'MOR batch %d/%d at theta*' % (mb, bi)))
         errs.append((abs(gh[eng.P] - ref['loss']) / abs(ref['loss']), float(np.max(np.abs(gh[:eng.P] - gref)) / np.max(np.abs(gref))), gbar, gcond,
                      lbar, lcond))
     out.update(epochs=len(res.lossAll), adam_steps=120 * len(res.lossAll), loss_first_last=[float(res.lossAll[0]), float(res.lossAll[-1])],
@@ -440,6 +452,8 @@ def test_operator_1dtmor_converged_run_against_the_known_answers(tmp_path):
                tables_relative_distance=float(uf.l2Err(d3, d4)),
                bars=dict(table=MOR_TABLE_BAR, inner=MOR_INNER_BAR, cexact=MOR_CEXACT_BAR, far_factor=MOR_FAR_FACTOR, inner_sensitivity=MOR_SENS_BAR))
     record('operator_1dtmor_converged', out)
+    for gh, gref, g32, gbar, what in blocks:
+        assert_grad_close(gh, gref, 3, [10, 20, 30], 1e-4, g32=lambda: g32, dim=1, global_bar=gbar, what=what)
     print('MOR converged run: %s' % json.dumps(out['hip']))
     for name in ('hip', 'oracle_at_theta_star'):
         o = out[name]

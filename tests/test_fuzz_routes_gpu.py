@@ -35,6 +35,18 @@ def test_routes_agree_with_the_oracle_and_each_other_steady(seed, ncases):
         assert r['ok'], r['msg']
 
 
+@pytest.mark.parametrize('seed,ncases,steady', [(5, 12, False), (37, 6, True)])
+def test_routes_agree_with_the_oracle_and_each_other_mor_inputs(seed, ncases, steady):
+    """MOR-shaped inputs (up to 8: dim + time + parameter columns) on every route, per block against the oracle and pairwise."""
+    rng = np.random.default_rng(seed)
+    for case in range(ncases):
+        c = fz.draw_case(rng, case, steady=steady, mor=True)
+        assert c['d_in'] <= 8
+        r = fz.run_case(c, with_oracle=True)
+        print(r['msg'])
+        assert r['ok'], r['msg']
+
+
 def test_ill_conditioned_draw_is_whitelisted_by_its_condition_number_only():
     """Seed 11, case 15 (profiles/r2_fuzz_case15_diag.txt): the whitelist applies because the draw's condition estimate
     is beyond COND_WHITELIST, and the widened bar is 2 x the fp32 restatement's own deviation."""

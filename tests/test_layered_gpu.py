@@ -9,7 +9,8 @@ import pytest
 import torch
 
 from oracle import tf1_graph as og
-from tests.test_engine_gpu import synth, make_engine, oracle_eval, LOSS_RTOL, GRAD_RTOL, LVEC_RTOL
+from tests.gradcheck import assert_grad_close, assert_pair_close
+from tests.test_engine_gpu import synth, make_engine, oracle_eval, LOSS_RTOL, GRAD_RTOL, LVEC_RTOL, ERRORS
 from tests.test_engine_gpu import STEADY, steady_setup, steady_check, _dump_errors  # noqa: F401 (autouse: the steady cases' errors)
 
 pytestmark = pytest.mark.gpu
@@ -34,6 +35,11 @@ CASES = [
     (3, 2, [2048, 700],               16,      5,   9,  4,   False, False, False),   # the widest a vn_config describes
     (2, 1, [12] * 16,                 16,      20,  30, 10,  True,  False, False),   # ... and the deepest
     (32, 3, [24, 24],                 64,      6,   20, 8,   False, True,  False),   # ... and the most inputs
+    # beyond 8 inputs on deep nets: W1's gradient is small there, judged per input row (tests/gradcheck.py)
+    (9, 3, [50] * 5,                  64,      12,  30, 10,  True,  True,  False),   # one past VN_KMAX_DIN
+    (17, 2, [40, 80, 40, 80, 40],     16,      20,  30, 10,  False, False, True),
+    (31, 3, [64] * 6,                 16,      9,   20, 8,   True,  False, False),
+    (32, 2, [24, 96, 24, 96, 24],     64,      6,   20, 8,   False, True,  False),
 ]
 
 
@@ -88,6 +94,9 @@ def test_loss_and_grad_parity_layered(case, impl, monkeypatch):
     assert abs(g[eng.P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
     err = np.max(np.abs(g[:eng.P] - gref)) / np.max(np.abs(gref))
     assert err <= GRAD_RTOL, err
+    assert_grad_close(g, gref, d_in, widths, GRAD_RTOL, dim=dim, rec=ERRORS.setdefault('layered case%d %s' % (CASES.index(case), impl), {}),
+                      g32=lambda: oracle_eval(flat, d, d_in, dim, widths, integNum, n_k, bDof, source, integW, detJvec,
+                                              dtype=torch.float32)[1])
     # run-to-run reproducible (no atomics in the weight-gradient GEMMs)
     eng.grad(0)
     torch.cuda.synchronize()
@@ -120,6 +129,7 @@ def test_layered_tanh_and_agreement_with_the_kernels():
         eng.close()
     a, b = grads
     assert np.max(np.abs(a[:-4] - b[:-4])) <= 3e-5 * np.max(np.abs(a[:-4]))
+    assert_pair_close(b, a, 3, [50, 50, 50], 1e-4, dim=2, what='layer by layer vs fused, tanh')
     assert abs(a[-4] - b[-4]) <= 1e-5 * abs(a[-4])
 
 
@@ -158,6 +168,7 @@ def test_layered_chunks_and_shard_additivity(widths, keep, monkeypatch):
         parts.append(gb.cpu().numpy().astype(np.float64))
     s = parts[0] + parts[1]
     assert np.max(np.abs(s[:eng.P] - g[:eng.P])) <= 2e-5 * np.max(np.abs(g[:eng.P]))
+    assert_pair_close(s, g, d_in, widths, 1e-4, dim=dim, global_bar=2e-5, what='sum of halves vs whole')
     assert abs(s[eng.P] - g[eng.P]) <= 1e-5 * abs(g[eng.P])
     eng.close()
     # the two forms of the reverse pass give the same bits (same chunks, same kernels, same order)
@@ -168,6 +179,7 @@ def test_layered_chunks_and_shard_additivity(widths, keep, monkeypatch):
             assert np.array_equal(prev, g)
         else:
             assert np.max(np.abs(prev[:-4] - g[:-4])) <= 3e-5 * np.max(np.abs(g[:-4]))
+            assert_pair_close(prev, g, d_in, widths, 1e-4, dim=dim, global_bar=3e-5, what='kept vs recomputed activations')
             assert abs(prev[-4] - g[-4]) <= 1e-5 * abs(g[-4])
     setattr(test_layered_chunks_and_shard_additivity, key, g)
 
@@ -299,6 +311,7 @@ def test_gemm_route_multi_chunk_multi_tile_against_the_oracle():
     assert abs(g[P] - loss) <= LOSS_RTOL * abs(loss), (g[P], loss)
     err = np.max(np.abs(g[:P] - grad)) / np.max(np.abs(grad))
     assert err <= GRAD_RTOL, err
+    ERRORS['layered gemm route multi-chunk %s' % widths] = assert_grad_close(g, grad, d_in, widths, GRAD_RTOL, dim=dim)
     u = eng.forward(d['Input'][:4099]).cpu().numpy()
     uref = og.forward(flat, d_in, widths, torch.float64, np.asarray(d['Input'][:4099], dtype=np.float64))
     assert np.max(np.abs(u - uref[:, 0])) <= 2e-6 * max(1.0, np.max(np.abs(uref)))
@@ -430,6 +443,7 @@ def test_per_layer_activation_lists(widths, acts):
     g = gb.cpu().numpy()
     assert abs(g[eng.P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
     assert np.max(np.abs(g[:eng.P] - gref)) / np.max(np.abs(gref)) <= GRAD_RTOL
+    ERRORS['layered per-layer activations %s %s' % (widths, acts)] = assert_grad_close(g, gref, d_in, widths, GRAD_RTOL, dim=dim)
     rng = np.random.default_rng(0)
     n = 500
     X = rng.uniform(-1, 1, (n, d_in))
@@ -469,13 +483,16 @@ def test_deep_narrow_nets_on_the_fused_kernel(case, act):
     d_in, dim, widths, integNum, n_k, nB, bDof, source, integW, detJvec = case
     eng, d, flat = _setup(case, 0, act=act)
     assert eng.kernel_path()[0] == 3                      # 8-wave fused kernel (two-pass for integNum 216)
-    f64 = lambda a: None if a is None else a.astype(np.float64)
-    ref, gref = og.loss_and_grad(
-        flat.astype(np.float64), d_in, widths, torch.float64, Input=f64(d['Input']), gcoef=f64(d['gcoef']),
-        source=f64(d['source']), N=f64(d['N']), dNt=f64(d['dNt']), integW=f64(d['integW']), intShape=[n_k, integNum],
-        detJ=(f64(d['detJ']) if detJvec else float(d['detJ'])), detJvec=detJvec, biInput=f64(d['biInput']),
-        biLabel=f64(d['biLabel']), bDof=bDof, biDimVal=2.0, w=d['w'], dim=dim, time_dependent=True,
-        is_source=source, integWflag=integW, activation=act)
+    def oracle(dtype):
+        f = np.float64 if dtype == torch.float64 else np.float32
+        f64 = lambda a: None if a is None else a.astype(f)
+        return og.loss_and_grad(
+            flat.astype(f), d_in, widths, dtype, Input=f64(d['Input']), gcoef=f64(d['gcoef']),
+            source=f64(d['source']), N=f64(d['N']), dNt=f64(d['dNt']), integW=f64(d['integW']), intShape=[n_k, integNum],
+            detJ=(f64(d['detJ']) if detJvec else float(d['detJ'])), detJvec=detJvec, biInput=f64(d['biInput']),
+            biLabel=f64(d['biLabel']), bDof=bDof, biDimVal=2.0, w=d['w'], dim=dim, time_dependent=True,
+            is_source=source, integWflag=integW, activation=act)
+    ref, gref = oracle(torch.float64)
     out, lv = eng.eval_loss(0, lossVec=True)
     for got, key in zip(out, ['loss', 'BCloss', 'ICloss', 'varLoss']):
         assert abs(got - ref[key]) <= LOSS_RTOL * abs(ref[key]) + 1e-7, (key, got, ref[key])
@@ -487,6 +504,8 @@ def test_deep_narrow_nets_on_the_fused_kernel(case, act):
     g = gb.cpu().numpy()
     assert abs(g[eng.P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
     assert np.max(np.abs(g[:eng.P] - gref)) / np.max(np.abs(gref)) <= GRAD_RTOL
+    assert_grad_close(g, gref, d_in, widths, GRAD_RTOL, dim=dim, g32=lambda: oracle(torch.float32)[1],
+                      rec=ERRORS.setdefault('deep fused case%d %s' % (DEEP.index(case), act), {}))
     # forward / residual entry points of such an engine (pointwise kernels, fused forward)
     rng = np.random.default_rng(0)
     X = rng.uniform(-1, 1, (300, d_in))

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from oracle import tf1_graph as og
+from tests.gradcheck import assert_grad_close, assert_pair_close, fp32_deviation
 from tests.test_varnet_host import cExact, pi
 from tests.test_varnet_gpu import op1dt, op2dt
 from varnet_amd import ADPDE, Domain1D, MOR, VarNet
@@ -153,6 +154,18 @@ def test_config2_fullsize(cfg2):
     assert np.max(np.abs(g1[:P] - gg[:P])) <= 2e-4 * np.max(np.abs(gg[:P]))
     assert abs(g1[P] - gg[P]) <= 1e-4 * abs(gg[P])
     gen.close()
+    th = eng.get_params()
+    dev32 = []
+
+    def full_dev32():
+        """Per-block conditioning of the whole problem (fp32 oracle against fp64; evaluated only if a block misses its bar)."""
+        if not dev32:
+            kw = oracle_kwargs(vn, td, [3.0, 2.0, 5.0])
+            k64 = {k: (v.astype(np.float64) if isinstance(v, np.ndarray) and v.dtype == np.float32 else v) for k, v in kw.items()}
+            g64 = og.loss_and_grad(th.astype(np.float64), 2, [50] * 4, torch.float64, **k64)[1]
+            dev32.append(fp32_deviation(og.loss_and_grad(th, 2, [50] * 4, torch.float32, **kw)[1], g64, 2, [50] * 4, 1))
+        return dev32[0]
+    assert_pair_close(g1, gg, 2, [50] * 4, 2e-4, dev32=full_dev32, dim=1, what='fused vs generic')
     # sampled oracle check: the first 300 test functions (fp64 oracle)
     q = fd.integNum
     eng.set_interior(1, d['Input'][:300 * q], d['gcoef'][:300 * q], None, n_k=300, detJ=fd.detJ)
@@ -162,6 +175,9 @@ def test_config2_fullsize(cfg2):
     ref, gref = og.loss_and_grad(eng.get_params().astype(np.float64), 2, [50] * 4, torch.float64, **kw)
     assert abs(gs[P] - ref['loss']) <= 1e-5 * abs(ref['loss'])
     assert np.max(np.abs(gs[:P] - gref)) <= 1e-4 * np.max(np.abs(gref))
+    kw32 = oracle_kwargs(vn, td, [3.0, 2.0, 5.0], rows=300)
+    assert_grad_close(gs, gref, 2, [50] * 4, 1e-4, dim=1, what='300 test functions',
+                      g32=lambda: og.loss_and_grad(th, 2, [50] * 4, torch.float32, **kw32)[1])
     # shard additivity (what the towers rely on)
     half = fd.nt // 2
     eng.set_interior(2, d['Input'][:half * q], d['gcoef'][:half * q], None, n_k=half, detJ=fd.detJ)
@@ -169,6 +185,7 @@ def test_config2_fullsize(cfg2):
     eng.set_weights([1.5, 1.0, 5.0])
     ga, gb_ = _grad(eng, 2), _grad(eng, 3)
     assert np.max(np.abs(ga[:P] + gb_[:P] - g1[:P])) <= 2e-5 * np.max(np.abs(g1[:P]))
+    assert_pair_close(ga + gb_, g1, 2, [50] * 4, 1e-4, dev32=full_dev32, dim=1, global_bar=2e-5, what='sum of shards vs whole')
     assert abs(ga[P] + gb_[P] - g1[P]) <= 2e-5 * abs(g1[P])
     eng.set_weights([3.0, 2.0, 5.0])
     # the de-duplicated formulation at config-2 size (bench.py extra.config2_small_step.dedup): 41 004 unique points for 160 000
@@ -180,6 +197,8 @@ def test_config2_fullsize(cfg2):
     assert np.array_equal(gd, gd2)
     assert np.max(np.abs(gd[:P] - g1[:P])) <= 1e-4 * np.max(np.abs(g1[:P]))
     assert np.max(np.abs(gd[:P] - gg[:P])) <= 2e-4 * np.max(np.abs(gg[:P]))
+    assert_pair_close(gd, g1, 2, [50] * 4, 1e-4, dev32=full_dev32, dim=1, what='dedup vs row-wise')
+    assert_pair_close(gd, gg, 2, [50] * 4, 2e-4, dev32=full_dev32, dim=1, what='dedup vs generic')
     assert np.allclose(gd[P:P + 4], g1[P:P + 4], rtol=1e-5)
     td.disable_dedup()
     assert np.array_equal(_grad(eng), g1)
@@ -240,16 +259,21 @@ def test_config5_fullsize_fp64_residual_and_mor_batch():
     q = fd.integNum
     n0, n1 = td.block(bi)
     n = (n1 - n0) * q
-    f64 = lambda t: t.cpu().numpy().astype(np.float64)
-    ref, gref = og.loss_and_grad(
-        eng.get_params().astype(np.float64), 3, [10, 20, 30], torch.float64,
-        Input=f64(d['Input'][n0 * q:n1 * q]), gcoef=f64(d['gcoef'][n0 * q:n1 * q]), source=None,
-        N=np.tile(fd.N, n1 - n0).reshape(n, 1).astype(np.float32).astype(np.float64),
-        dNt=np.tile(fd.dNt, n1 - n0).reshape(n, 1).astype(np.float32).astype(np.float64), integW=None,
-        intShape=[n1 - n0, q], detJ=float(np.float32(fd.detJ)), detJvec=False, biInput=f64(d['biInput']),
-        biLabel=f64(d['biLabel']).reshape(-1, 1), bDof=fd.bDofsum, biDimVal=float(fd.biDimVal), w=w_e, dim=1,
-        time_dependent=True, is_source=False, integWflag=False)
+
+    def oracle(dtype):
+        f = np.float64 if dtype == torch.float64 else np.float32
+        f64 = lambda t: t.cpu().numpy().astype(f)
+        return og.loss_and_grad(
+            eng.get_params().astype(f), 3, [10, 20, 30], dtype,
+            Input=f64(d['Input'][n0 * q:n1 * q]), gcoef=f64(d['gcoef'][n0 * q:n1 * q]), source=None,
+            N=np.tile(fd.N, n1 - n0).reshape(n, 1).astype(np.float32).astype(f),
+            dNt=np.tile(fd.dNt, n1 - n0).reshape(n, 1).astype(np.float32).astype(f), integW=None,
+            intShape=[n1 - n0, q], detJ=float(np.float32(fd.detJ)), detJvec=False, biInput=f64(d['biInput']),
+            biLabel=f64(d['biLabel']).reshape(-1, 1), bDof=fd.bDofsum, biDimVal=float(fd.biDimVal), w=w_e, dim=1,
+            time_dependent=True, is_source=False, integWflag=False)
+    ref, gref = oracle(torch.float64)
     P = eng.P
     assert abs(g[P] - ref['loss']) <= 1e-5 * abs(ref['loss'])
     assert np.max(np.abs(g[:P] - gref)) <= 1e-4 * np.max(np.abs(gref))
+    assert_grad_close(g, gref, 3, [10, 20, 30], 1e-4, dim=1, g32=lambda: oracle(torch.float32)[1], what='MOR mini-batch')
     eng.close()

@@ -7,7 +7,9 @@ import pytest
 import torch
 
 from oracle import tf1_graph as og
-from tests.test_engine_gpu import synth, LOSS_RTOL, GRAD_RTOL, LVEC_RTOL, CASES
+from tests.gradcheck import assert_grad_close
+from tests.test_engine_gpu import synth, LOSS_RTOL, GRAD_RTOL, LVEC_RTOL, CASES, ERRORS
+from tests.test_engine_gpu import _dump_errors  # noqa: F401  (this module's records go to parity_errors.json too)
 
 pytestmark = pytest.mark.gpu
 
@@ -36,13 +38,16 @@ def test_tanh_loss_and_grad_parity(case, kernel):
     eng.set_interior(0, d['Input'], d['gcoef'], d['source'], n_k=n_k, detJ=d['detJ'])
     eng.set_bic(d['biInput'], d['biLabel'], bDof, 2.0)
     eng.set_weights(d['w'])
-    f64 = lambda a: None if a is None else a.astype(np.float64)
-    ref, gref = og.loss_and_grad(
-        flat.astype(np.float64), d_in, widths, torch.float64, Input=f64(d['Input']), gcoef=f64(d['gcoef']),
-        source=f64(d['source']), N=f64(d['N']), dNt=f64(d['dNt']), integW=f64(d['integW']), intShape=[n_k, q],
-        detJ=(f64(d['detJ']) if detJvec else float(d['detJ'])), detJvec=detJvec, biInput=f64(d['biInput']),
-        biLabel=f64(d['biLabel']), bDof=bDof, biDimVal=2.0, w=d['w'], dim=dim, time_dependent=True,
-        is_source=source, integWflag=integW, activation='tanh')
+    def oracle(dtype):
+        f = np.float64 if dtype == torch.float64 else np.float32
+        f64 = lambda a: None if a is None else a.astype(f)
+        return og.loss_and_grad(
+            flat.astype(f), d_in, widths, dtype, Input=f64(d['Input']), gcoef=f64(d['gcoef']),
+            source=f64(d['source']), N=f64(d['N']), dNt=f64(d['dNt']), integW=f64(d['integW']), intShape=[n_k, q],
+            detJ=(f64(d['detJ']) if detJvec else float(d['detJ'])), detJvec=detJvec, biInput=f64(d['biInput']),
+            biLabel=f64(d['biLabel']), bDof=bDof, biDimVal=2.0, w=d['w'], dim=dim, time_dependent=True,
+            is_source=source, integWflag=integW, activation='tanh')
+    ref, gref = oracle(torch.float64)
     out, lv = eng.eval_loss(0, lossVec=True)
     for got, key in zip(out, ['loss', 'BCloss', 'ICloss', 'varLoss']):
         assert abs(got - ref[key]) <= LOSS_RTOL * abs(ref[key]) + 1e-7, (key, got, ref[key])
@@ -54,6 +59,8 @@ def test_tanh_loss_and_grad_parity(case, kernel):
     g = gb.cpu().numpy()
     assert abs(g[eng.P] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
     assert np.max(np.abs(g[:eng.P] - gref)) / np.max(np.abs(gref)) <= GRAD_RTOL
+    assert_grad_close(g, gref, d_in, widths, GRAD_RTOL, dim=dim, g32=lambda: oracle(torch.float32)[1],
+                      rec=ERRORS.setdefault('tanh case%d %s' % (CASES.index(case), ['auto', 'generic'][kernel]), {}))
     eng.close()
 
 

@@ -11,10 +11,18 @@ import torch
 
 from oracle import tf1_graph as og
 from tests.test_varnet_host import cExact, pi
+from tests.gradcheck import assert_grad_close, assert_pair_close
 from tests.test_engine_gpu import ERRORS, _dump_errors  # noqa: F401 (autouse: the steady runs' errors)
 from varnet_amd import ADPDE, Domain1D, PolygonDomain2D, MOR, VarNet
 
 pytestmark = pytest.mark.gpu
+
+
+def _oracle(flat, d_in, widths, dtype, **kw):
+    """og.loss_and_grad in fp64, plus a callable that redoes it in fp32 (the per-block conditioning of tests/gradcheck.py)."""
+    ref, gref = og.loss_and_grad(flat, d_in, widths, dtype, **kw)
+    k32 = {k: (v.astype(np.float32) if isinstance(v, np.ndarray) and v.dtype == np.float64 else v) for k, v in kw.items()}
+    return ref, gref, lambda: og.loss_and_grad(np.asarray(flat, dtype=np.float32), d_in, widths, torch.float32, **k32)[1]
 
 
 def op1dt(layerWidth, discNum, tDiscNum, cEx=None):
@@ -113,6 +121,7 @@ def test_fullsize_fused_vs_generic_and_determinism(cfg3):
     P = eng.P
     assert np.max(np.abs(g1[:P] - gg[:P])) <= 2e-4 * np.max(np.abs(gg[:P]))
     assert abs(g1[P] - gg[P]) <= 1e-4 * abs(gg[P])
+    ERRORS['cfg3 fused vs generic'] = assert_pair_close(g1, gg, 3, [50] * 5, 2e-4, dim=2)
     out, lv = gen.eval_loss(0, lossVec=True)
     assert abs(float(lv.double().sum()) - out[3]) <= 1e-4 * abs(out[3])
     assert abs(out[0] - g1[P]) <= 1e-4 * abs(out[0])
@@ -136,6 +145,7 @@ def test_fullsize_gradient_is_additive_over_shards(cfg3):
     P = eng.P
     s = ga + gb_
     assert np.max(np.abs(s[:P] - g_full[:P])) <= 5e-5 * np.max(np.abs(g_full[:P]))
+    ERRORS['cfg3 sum of shards vs whole'] = assert_pair_close(s, g_full, 3, [50] * 5, 1e-4, dim=2, global_bar=5e-5)
     assert abs(s[P] - g_full[P]) <= 2e-5 * abs(g_full[P])
 
 
@@ -149,7 +159,7 @@ def test_fullsize_sampled_oracle_check(cfg3):
     g = _grad(eng, 3)
     flat = eng.get_params().astype(np.float64)
     w = np.array([3.0, 2.0, 5.0])
-    ref, gref = og.loss_and_grad(
+    ref, gref, g32 = _oracle(
         flat, 3, [50] * 5, torch.float64, Input=d['Input'][:rows].cpu().numpy().astype(np.float64),
         gcoef=d['gcoef'][:rows].cpu().numpy().astype(np.float64), source=None,
         N=np.tile(fd.N, n_s).reshape(rows, 1).astype(np.float32).astype(np.float64),      # the fp32 feed (TFModel.py:606-607)
@@ -164,6 +174,7 @@ def test_fullsize_sampled_oracle_check(cfg3):
     # by the cancellation inside R_k, not of the arithmetic.
     assert abs(g[P] - ref['loss']) <= 1e-5 * abs(ref['loss'])
     assert np.max(np.abs(g[:P] - gref)) <= 1e-4 * np.max(np.abs(gref))
+    ERRORS['cfg3 sample of 300 test functions'] = assert_grad_close(g, gref, 3, [50] * 5, 1e-4, g32=g32, dim=2)
 
 
 def test_fullsize_dedup_formulation(cfg3):
@@ -185,6 +196,7 @@ def test_fullsize_dedup_formulation(cfg3):
     assert not np.array_equal(g1, g_row)                             # ... and it IS another formulation that ran
     gerr = np.max(np.abs(g1[:P] - g_row[:P])) / np.max(np.abs(g_row[:P]))
     assert gerr <= 1e-4, gerr
+    ERRORS['cfg3 dedup vs row-wise'] = assert_pair_close(g1, g_row, 3, [50] * 5, 1e-4, dim=2)
     # loss, BC, IC at the loss bar.  The variational term of this problem at glorot parameters (5.4e-6: 1e5 squared weak residuals,
     # each the small remainder of cancelling integrand terms) is measured against the fp64 oracle on the sample below, formulation
     # by formulation; across formulations it gets the bar of the per-test-function loss field it is the sum of (lossVec: 1e-4)
@@ -202,7 +214,7 @@ def test_fullsize_dedup_formulation(cfg3):
     eng.set_dedup(3, blk[first], uid, rowptr, rowidx)
     g3 = _grad(eng, 3)
     flat = eng.get_params().astype(np.float64)
-    ref, gref = og.loss_and_grad(
+    ref, gref, g32 = _oracle(
         flat, 3, [50] * 5, torch.float64, Input=d['Input'][:rows].cpu().numpy().astype(np.float64),
         gcoef=d['gcoef'][:rows].cpu().numpy().astype(np.float64), source=None,
         N=np.tile(fd.N, n_s).reshape(rows, 1).astype(np.float32).astype(np.float64),
@@ -215,6 +227,8 @@ def test_fullsize_dedup_formulation(cfg3):
     lerr = abs(g3[P] - ref['loss']) / abs(ref['loss'])
     gerr3 = np.max(np.abs(g3[:P] - gref)) / np.max(np.abs(gref))
     assert lerr <= 1e-5 and gerr3 <= 1e-4, (lerr, gerr3)
+    ERRORS['cfg3 sample dedup'] = assert_grad_close(g3, gref, 3, [50] * 5, 1e-4, g32=g32, dim=2, what='dedup')
+    ERRORS['cfg3 sample row-wise'] = assert_grad_close(g_row3, gref, 3, [50] * 5, 1e-4, g32=g32, dim=2, what='row-wise')
     # the variational term alone, both formulations against the fp64 oracle (same bar: neither formulation is the worse one)
     verr_dd = abs(g3[P + 3] - ref['varLoss']) / abs(ref['varLoss'])
     verr_row = abs(g_row3[P + 3] - ref['varLoss']) / abs(ref['varLoss'])
@@ -412,7 +426,7 @@ def test_shuffled_feeds_on_device(tmp_path):
     perm = td.biPerm[bi]
     f64 = lambda t: t.cpu().numpy().astype(np.float64)
     n = rows.size
-    ref, gref = og.loss_and_grad(
+    ref, gref, g32 = _oracle(
         eng.get_params().astype(np.float64), 2, [20, 20], torch.float64, Input=f64(d['Input'])[rows], gcoef=f64(d['gcoef'])[rows],
         source=None, N=np.tile(fd.N, n1 - n0).reshape(n, 1).astype(np.float32).astype(np.float64),
         dNt=np.tile(fd.dNt, n1 - n0).reshape(n, 1).astype(np.float32).astype(np.float64), integW=None, intShape=[n1 - n0, q],
@@ -421,6 +435,7 @@ def test_shuffled_feeds_on_device(tmp_path):
     P = eng.P
     assert abs(g[P] - ref['loss']) <= 1e-5 * abs(ref['loss'])
     assert np.max(np.abs(g[:P] - gref)) <= 1e-4 * np.max(np.abs(gref))
+    assert_grad_close(g, gref, 2, [20, 20], 1e-4, g32=g32, dim=1, what='shuffled mini-batch')
     # the permutation crosses the BC/IC split: the BC mean really differs from the unshuffled one
     eng.set_batch_bic(td.engine_batch(0, bi))
     eng.grad(td.engine_batch(0, bi))
@@ -489,3 +504,56 @@ def test_steady_training_on_device_matches_the_oracle_engine(kind, tmp_path, mon
     ERRORS['steady training %s' % kind] = rec
     for mode in ('auto', 'True', 'False'):
         assert rec[mode]['loss'] <= 1e-2 and rec[mode]['params'] <= 2e-3, rec
+
+
+def test_mor_varnet_with_six_inputs_matches_the_oracle():
+    """The public API at d_in > 3: a 1D+t VarNet whose MOR has four variables (two of diff, two of vel) has inpDim = 6 and runs
+    on the 8-wave fused kernel (VN_KMAX_DIN = 8).  After one pass of Adam steps over every MOR batch, one MOR mini-batch's loss
+    and gradient against the fp64 oracle -- per block: the four parameter rows of W1 carry the MOR dependence."""
+    def diffFun(x, t=0, D=0.01, E=0.5):
+        return D * (1.0 + E * x[:, 0:1] ** 2)
+
+    def velFun(x, t=0, a=1.0, b=0.0):
+        return a + b * np.sin(pi * x[:, 0:1])
+
+    mor = MOR([diffFun, velFun], [['D', 'E'], ['a', 'b']], [[[0.01, 0.05], [0.2, 0.8]], [[0.5, 1.5], [-0.3, 0.3]]])
+    pde = ADPDE(Domain1D(), diff=diffFun, vel=velFun, timeDependent=True, tInterval=[0, 1.0], IC=lambda x: -np.sin(pi * x),
+                MORvar=mor)
+    widths = [50] * 5
+    vn = VarNet(pde, layerWidth=widths, discNum=40, bDiscNum=10, tDiscNum=30, MORdiscScheme=[2, 2])
+    fd, eng = vn.fixData, vn.engine
+    assert vn.inpDim == 6 and fd.MORbatchNum == 16 and eng.kernel_path()[0] == 3
+    td = vn._build_tdata(batchNum=2)
+    eng.set_weights(td.towerWeights([1e3, 1e3, 1.0]))
+    acc = torch.zeros((), dtype=torch.float32, device=eng.device)
+    for mb in range(fd.MORbatchNum):
+        td.select_mor(mb)
+        vn.optimIter(td, mb, acc)
+    torch.cuda.synchronize()
+    assert eng.step == 16 * 2 and np.isfinite(float(acc.item()))
+    mb, bi = 11, 1
+    td.select_mor(mb)
+    w_e = td.towerWeights([1e3, 1e3, 1.0])
+    eng.set_weights(w_e)
+    gb = eng.bind_grad_buffer()
+    eng.grad(td.engine_batch(mb, bi))
+    torch.cuda.synchronize()
+    g = gb.cpu().numpy().astype(np.float64)
+    d = td.mor[mb]
+    q = fd.integNum
+    n0, n1 = td.block(bi)
+    n = (n1 - n0) * q
+    f64 = lambda t: t.cpu().numpy().astype(np.float64)
+    X = f64(d['Input'][n0 * q:n1 * q])
+    assert np.ptp(X[:, 2:], axis=0).max() == 0.0 and X.shape[1] == 6      # one MOR batch: constant parameter columns
+    ref, gref, g32 = _oracle(
+        eng.get_params().astype(np.float64), 6, widths, torch.float64, Input=X, gcoef=f64(d['gcoef'][n0 * q:n1 * q]),
+        source=None, N=np.tile(fd.N, n1 - n0).reshape(n, 1).astype(np.float32).astype(np.float64),
+        dNt=np.tile(fd.dNt, n1 - n0).reshape(n, 1).astype(np.float32).astype(np.float64), integW=None, intShape=[n1 - n0, q],
+        detJ=float(np.float32(fd.detJ)), detJvec=False, biInput=f64(d['biInput']), biLabel=f64(d['biLabel']).reshape(-1, 1),
+        bDof=fd.bDofsum, biDimVal=float(fd.biDimVal), w=w_e, dim=1, time_dependent=True, is_source=False, integWflag=False)
+    P = eng.P
+    assert abs(g[P] - ref['loss']) <= 1e-5 * abs(ref['loss'])
+    assert np.max(np.abs(g[:P] - gref)) <= 1e-4 * np.max(np.abs(gref))
+    ERRORS['varnet MOR inpDim 6 mini-batch'] = assert_grad_close(g, gref, 6, widths, 1e-4, g32=g32, dim=1, what='MOR d_in 6')
+    eng.close()
