@@ -66,13 +66,29 @@ struct Batch {
   const float* biLabel = nullptr;
   // de-duplicated formulation (vn_set_dedup)
   const float* Xu = nullptr;
-  const int* uid = nullptr;
+  const int* uid = nullptr;   // (Xu is only ever set on the 8-wave routes: vn_set_dedup refuses the others)
   const int* rowptr = nullptr;
   const int* rowidx = nullptr;
   long U = 0;
   float* gcsr = nullptr;      // owned: gcoef in CSR order, [n_k*integ_num, dim] (static per batch; built by vn_set_dedup)
   long gcsr_cap = 0;
   bool gper = false;          // gcoef repeats with period integ_num along the rows (constant coefficients): no CSR copy needed
+};
+
+// How an engine computes its gradient, decided once by pick_route (vn_create).
+enum class Route {
+  layered,    // layer by layer (vn_layered.hip): networks outside the kernels' range, or VN_KERNEL_LAYERED
+  generic,    // generic forward / backward kernels (vn_generic.hip)
+  fused4,     // 4-wave fused kernel (vn_fused.hip): the cross-check build only
+  fused8,     // 8-wave fused kernel (vn_fused16.hip)
+  twopass,    // 8-wave fused kernel twice around the row-wise seed kernel (integ_num > 128)
+};
+
+// vn_debug_point_route & 3: which kernels evaluate points (vn_forward*, vn_residual*, the de-duplicated unique points)
+enum class PointRoute {
+  automatic,  // 0 (and 3): the matrix-pipe kernels where the network has them
+  per_thread, // 1: vn_residual / vn_*_f64 on the per-thread kernels (the tests' cross-check)
+  f32_mfma,   // 2: the f32-MFMA point kernels where the bf16-piece kernels (vn_split16.hip) would run (cross-check build only)
 };
 
 constexpr int PROF_CAP = 4096;
@@ -129,27 +145,21 @@ struct vn_engine {
   long losspart_cap = 0;
 
   int64_t step = 0;
-  bool use_fused = false;
-  bool use_fused16 = false;
+  Route route = Route::generic;
   bool full_grid = false;            // VN_FULL_GRID=1 (diagnostic): #CU workgroups whatever the tile count (fixed-cost measurements)
   VnOptArgs fuse;                    // optimizer step to fold into the next gradient reduction (kind -1: none)
-  bool two_pass = false;             // fused kernel twice around the row-wise seed kernel (integ_num > 128)
-  bool fused_only = false;           // 7-8 hidden layers: no generic kernels for this net
-  VnLayered* layered = nullptr;      // layer-by-layer route (networks outside the kernels' range, or forced)
+  VnLayered* layered = nullptr;      // Route::layered
   float* tp_losspart = nullptr; long tp_losspart_cap = 0;
   float* fused_losspart = nullptr;   // [ncu*3]
   unsigned long long* stamps = nullptr;   // 8 counters, diagnostic builds
   // de-duplicated formulation work buffers
-  float *dd_uv = nullptr, *dd_ug = nullptr, *dd_su = nullptr, *dd_sg = nullptr, *dd_partial = nullptr,
-        *dd_losspart = nullptr;
-  long dd_capU = 0, dd_cap_lp = 0;
+  float *dd_uv = nullptr, *dd_su = nullptr, *dd_sg = nullptr, *dd_partial = nullptr, *dd_losspart = nullptr;
+  long dd_uv_cap = 0, dd_su_cap = 0, dd_sg_cap = 0, dd_partial_cap = 0, dd_cap_lp = 0;
   float* snap = nullptr;       // vn_state_snapshot: device copy of (theta | m | v), 3 P floats
   int64_t snap_step = -1;      // step counter at the snapshot (-1: none)
-  bool point_kernels = false;  // vn_debug_point_route(1): vn_residual / vn_*_f64 on the per-thread kernels (the tests' cross-check)
+  PointRoute point_route = PointRoute::automatic;   // vn_debug_point_route(route & 3)
   bool eval_rowwise = false;   // vn_debug_point_route(route | 8): vn_eval_loss on the row-wise forward although the batch carries a de-duplication map
   bool no_gtable = false;      // vn_debug_point_route(route | 4): vn_set_dedup keeps the CSR-ordered copy of gcoef although it is periodic
-  bool no_split = false;       // vn_debug_point_route(2): the f32-MFMA point kernels where the bf16-piece kernels (vn_split16.hip) would run
-  int pgrad_wgs = 0;           // workgroups per CU of vn_pgrad16: 0 = what fits, at most 2 (diagnostic override: $VN_PGRAD_WGS = 1..4)
 
   // tower gradient SUM over RCCL (vn_comm_init); nullptr = single process or host-side collective
   ncclComm_t comm = nullptr;
@@ -220,10 +230,52 @@ int build_net(const vn_config& c, VnNet& net) {
   return VN_OK;
 }
 
+// Networks outside the kernels' range (VN_KMAX_*), and nets whose generic-kernel tile does not fit LDS while no fused
+// instantiation exists, go layer by layer (vn_layered.hip); VN_KERNEL_LAYERED forces that route.  One extension of the range:
+// 7 and 8 hidden layers up to 50 wide are instantiated in the 8-wave fused kernel (deep, narrow nets); the generic kernels do
+// not cover them, so every path of such an engine runs on the fused kernel.
+int pick_route(const vn_config& c, const VnNet& net, Route* route) {
+  const int k = c.kernel, q = c.integ_num;
+  const bool generic_range = vn_net_in_kernel_range(net);
+  const bool deep_fused = !generic_range && net.L <= 8 && net.hmax <= VN_KMAX_WIDTH && net.d_in <= VN_KMAX_DIN &&
+                          net.act != VN_ACT_PER_LAYER && vn_fused16_net_supported(net) &&
+                          (k == VN_KERNEL_AUTO || k == VN_KERNEL_FUSED16);
+  const bool in_range = generic_range || deep_fused;
+  if (!in_range && k != VN_KERNEL_AUTO && k != VN_KERNEL_LAYERED)
+    return fail(VN_EUNSUPPORTED, "network (%d layers, widest %d, %d inputs%s) is outside the range of the requested kernel family "
+                "(<= %d layers, width <= %d, <= %d inputs, one activation): use VN_KERNEL_AUTO or VN_KERNEL_LAYERED",
+                net.L, net.hmax, net.d_in, net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "", VN_KMAX_LAYERS,
+                VN_KMAX_WIDTH, VN_KMAX_DIN);
+  *route = Route::layered;
+  if (k == VN_KERNEL_LAYERED || !in_range) return VN_OK;
+  const bool fused_ok = k != VN_KERNEL_GENERIC && k != VN_KERNEL_FUSED && vn_fused16_net_supported(net);
+  if (!fused_ok && vn_generic_bwd_lds_bytes(net) > 160 * 1024) {
+    if (k == VN_KERNEL_AUTO) return VN_OK;
+    return fail(VN_EUNSUPPORTED, "network needs %zu B of LDS per tile on the generic kernels (> 160 KiB): reduce depth/width",
+                vn_generic_bwd_lds_bytes(net));
+  }
+  if (k == VN_KERNEL_FUSED && !vn_fused_supported(net, q))
+    return fail(VN_EUNSUPPORTED, kWithFused32 ? "fused kernel unsupported for this network / integ_num"
+                                              : "VN_KERNEL_FUSED (the 4-wave geometry) is not part of the product library: it lives in the "
+                                                "tests' cross-check build, libvarnet_hip_xcheck.so (make -C varnet_amd/csrc xcheck)");
+  const bool tp_ok = q > 128 && vn_fused16_net_supported(net);
+  if (k == VN_KERNEL_FUSED16 && !vn_fused16_supported(net, q) && !tp_ok)
+    return fail(VN_EUNSUPPORTED, "fused16 kernel unsupported for this network / integ_num");
+  // AUTO: the 8-wave geometry where instantiated (faster: two waves per SIMD overlap VALU/LDS work with MFMA), else the 4-wave
+  // geometry, else two-pass, else the generic kernels
+  const bool eight = k == VN_KERNEL_FUSED16 || k == VN_KERNEL_AUTO;
+  if (eight && vn_fused16_supported(net, q)) *route = Route::fused8;
+  else if (k != VN_KERNEL_GENERIC && vn_fused_supported(net, q)) *route = Route::fused4;
+  else if (eight && tp_ok) *route = Route::twopass;
+  else *route = Route::generic;
+  return VN_OK;
+}
+
 int ensure(float** p, long* cap, long need) {
   if (need <= *cap) return VN_OK;
   if (*p) (void)hipFree(*p);
   *p = nullptr;
+  *cap = 0;
   HIPCHK(hipMalloc((void**)p, (size_t)need * sizeof(float)));
   *cap = need;
   return VN_OK;
@@ -259,19 +311,115 @@ int check_batch(vn_engine* h, int32_t batch) {
 
 inline const float* bi_x(const vn_engine* h, const Batch& b) { return b.biInput ? b.biInput : h->biInput; }
 inline const float* bi_y(const vn_engine* h, const Batch& b) { return b.biLabel ? b.biLabel : h->biLabel; }
+inline const float* batch_src(const vn_engine* h, const Batch& b) { return h->cfg.has_source ? b.source : nullptr; }
+inline const float* fe_w(const vn_engine* h) { return (h->cfg.has_integw && h->has_feW) ? h->feW : nullptr; }
+
+inline bool on_8wave(const vn_engine* h) { return h->route == Route::fused8 || h->route == Route::twopass; }
+
+// ---- point kernels of the 8-wave family (vn_debug_point_route) ----------------------------
+// hidden widths 33..64: the products as six bf16-piece MFMAs, fp32-class (vn_split16.hip), unless route 2 asks for f32-MFMA
+inline bool use_split16(const vn_engine* h) { return h->point_route != PointRoute::f32_mfma && vn_split16_supported(h->net); }
+
+// (u, grad u) at n points, the outputs of vn_pgrad16_launch; with neither g nor pack, the value-only sweep (F_pt per point)
+hipError_t point_pass(const vn_engine* h, const float* X, long n, float* u, float* g, float* pack) {
+  if (!use_split16(h)) return vn_pgrad16_launch(h->net, h->theta, X, n, u, g, pack, h->ncu, 0, h->stream);
+  if (!g && !pack) return vn_split16_forward(h->net, h->theta, X, n, u, h->ncu, h->stream);
+  return vn_split16_pgrad(h->net, h->theta, X, n, u, g, pack, h->ncu, h->stream);
+}
+
+// Strong residual in f32.  Networks of the 8-wave family: second-order forward mode on the matrix pipe (vn_split16.hip or
+// vn_taylor16.hip); the per-point kernel keeps the generic / 4-wave requests (and is what the new kernels are cross-checked against)
+hipError_t residual_f32(const vn_engine* h, const float* X, const float* diff, const float* vel, const float* src, const float* ddx,
+                        long n, float* u, float* res) {
+  const int td = h->cfg.time_dependent;
+  if (on_8wave(h) && h->point_route != PointRoute::per_thread && vn_taylor16_supported(h->net, td)) {
+    if (use_split16(h)) return vn_split16_residual(h->net, h->theta, X, diff, vel, src, ddx, td, n, u, res, h->ncu, h->stream);
+    return vn_taylor16_residual(h->net, h->theta, X, diff, vel, src, ddx, td, n, u, res, h->ncu, h->stream);
+  }
+  return vn_pointwise_residual_f32(h->net, h->theta, X, diff, vel, src, ddx, td, n, u, res, h->stream);
+}
+
+// fp64 points (vn_forward_f64, vn_residual_f64): networks of the 8-wave family whose fp64 images fit the LDS on the fp64 matrix
+// pipe (vn_taylor16d.hip), else per thread
+inline bool use_taylor16d(const vn_engine* h) {
+  return on_8wave(h) && h->point_route != PointRoute::per_thread && vn_taylor16d_supported(h->net);
+}
+
+// ---- vn_profile_*: HIP events around the region of a step that prof_name is charged with ---
+// (prof_n moves in prof_stop only, so both ends of a region see the same slot)
+int prof_start(vn_engine* h) {
+  if (!h->prof_on || h->prof_n >= PROF_CAP) return VN_OK;
+  if (!h->ev0[h->prof_n]) { HIPCHK(hipEventCreate(&h->ev0[h->prof_n])); HIPCHK(hipEventCreate(&h->ev1[h->prof_n])); }
+  HIPCHK(hipEventRecord(h->ev0[h->prof_n], h->stream));
+  return VN_OK;
+}
+
+int prof_stop(vn_engine* h) {
+  if (!h->prof_on || h->prof_n >= PROF_CAP) return VN_OK;
+  HIPCHK(hipEventRecord(h->ev1[h->prof_n], h->stream));
+  h->prof_n++;
+  return VN_OK;
+}
+
+// A checker kernel's count of violations in one device int, zeroed before and read back after it (synchronises: registration only)
+template <class Launch>
+int count_on_device(vn_engine* h, Launch launch, int* count) {
+  int* err_dev = nullptr;
+  HIPCHK(hipMalloc((void**)&err_dev, sizeof(int)));
+  hipError_t e = hipMemsetAsync(err_dev, 0, sizeof(int), h->stream);
+  if (e == hipSuccess) e = launch(err_dev);
+  *count = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(count, err_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  (void)hipFree(err_dev);
+  if (e != hipSuccess) return fail(VN_EHIP, "vn_set_dedup: %s", hipGetErrorString(e));
+  return VN_OK;
+}
+
+// ---- kernel arguments shared by every launch site; callers set rows, mode, outputs, seeds and partial buffers ----
+// Fused kernels: with a batch, also its BC/IC rows, bDof, biDimVal and the loss weights; without one (the forward-only mode on
+// arbitrary rows) those stay zero.
+VnFusedArgs fused_args(const vn_engine* h, const Batch* b) {
+  VnFusedArgs f{};
+  f.net = h->net; f.theta = h->theta; f.integ_num = h->cfg.integ_num;
+  f.feN = h->feN; f.fedNt = h->fedNt; f.time_dependent = h->cfg.time_dependent;
+  if (b) {
+    f.Xb = bi_x(h, *b); f.label = bi_y(h, *b); f.nB = h->nB; f.bDof = h->bDof; f.biDimVal = (float)h->biDimVal;
+    f.w0 = (float)h->w[0]; f.w1 = (float)h->w[1]; f.w2 = (float)h->w[2];
+  }
+  return f;
+}
+
+// Row-wise seed kernel: the batch's interior rows (values in h->u, h->ud) and the BC/IC rows (values in h->ub)
+VnSeedArgs seed_args(const vn_engine* h, const Batch& b) {
+  VnSeedArgs a{};
+  a.u = h->u; a.ud = h->ud; a.source = batch_src(h, b);
+  a.feN = h->feN; a.fedNt = h->fedNt; a.feW = fe_w(h);
+  a.Nrow = b.Nrow; a.dNtrow = b.dNtrow; a.detJv = b.detJv; a.detJ = (float)b.detJ;
+  a.n_k = b.n_k; a.integ_num = h->cfg.integ_num; a.time_dependent = h->cfg.time_dependent;
+  a.ub = h->ub; a.label = bi_y(h, b); a.nB = h->nB; a.bDof = h->bDof; a.biDimVal = (float)h->biDimVal;
+  a.w0 = (float)h->w[0]; a.w1 = (float)h->w[1]; a.w2 = (float)h->w[2];
+  return a;
+}
+
+// De-duplicated assembly (seed and gather kernels) of a batch with a de-duplication map, (u, grad u) of its points in h->dd_uv
+VnDedupArgs dedup_args(const vn_engine* h, const Batch& b) {
+  VnDedupArgs a{};
+  a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
+  a.gcoef = b.gcoef; a.gcoef_csr = b.gcsr; a.source = batch_src(h, b);
+  a.feN = h->feN; a.fedNt = h->fedNt; a.feW = fe_w(h);
+  a.detJv = b.detJv; a.detJ = (float)b.detJ; a.n_k = b.n_k; a.U = b.U; a.q = h->cfg.integ_num; a.dim = h->cfg.dim;
+  a.time_dependent = h->cfg.time_dependent; a.w2 = (float)h->w[2]; a.gper = b.gper ? 1 : 0;
+  return a;
+}
 
 // Model value (and directional derivative along G, if given) at n rows with the 8-wave fused kernel in its
 // forward-only mode: 2 F_pt per row at the fused kernel's efficiency instead of the generic forward kernel.
 int fused_forward(vn_engine* h, const float* X, const float* G, long n, float* out_u, float* out_ud) {
   if (n <= 0) return VN_OK;
-  VnFusedArgs f{};
-  f.net = h->net; f.theta = h->theta; f.X = X; f.G = G; f.src = nullptr;
-  f.nT = n; f.n_k = 0; f.integ_num = h->cfg.integ_num;
-  f.feN = h->feN; f.fedNt = h->fedNt; f.feW = nullptr; f.detJv = nullptr; f.detJ = 0.f;
-  f.time_dependent = h->cfg.time_dependent; f.lossVec = nullptr;
-  f.Xb = nullptr; f.label = nullptr; f.nB = 0; f.bDof = 0; f.biDimVal = 0.f;
-  f.w0 = f.w1 = f.w2 = 0.f;
-  f.partial = h->partial; f.losspart = h->fused_losspart ? h->fused_losspart : h->tp_losspart; f.stamps = nullptr;
+  VnFusedArgs f = fused_args(h, nullptr);
+  f.X = X; f.G = G; f.nT = n;
+  f.partial = h->partial; f.losspart = h->fused_losspart;
   f.mode = 1; f.dir = G ? -1 : 0; f.ostride = 1; f.out_u = out_u; f.out_ud = G ? out_ud : nullptr;
   if (!f.losspart || !f.partial) return fail(VN_ESTATE, "fused forward without its work buffers");   // the kernel stores to both
   const long tiles = (n + 127) / 128;
@@ -286,29 +434,17 @@ int fused_forward(vn_engine* h, const float* X, const float* G, long n, float* o
 // row-wise seed kernel with an empty interior set.  What every monitor of a run on the de-duplicated formulation calls (splitLoss,
 // VarNet.py:1365): 2.9 -> 0.45 ms on BASELINE config 3.
 int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst) {
-  const int q = h->cfg.integ_num, dim = h->cfg.dim;
   const int sblk = (int)((b.n_k + VN_DEDUP_TFB - 1) / VN_DEDUP_TFB);
   const int bgrid = (int)(((h->nB > 0 ? h->nB : 1) + 255) / 256);
   if (int rc = ensure(&h->losspart, &h->losspart_cap, (long)(sblk + bgrid) * 3)) return rc;
-  if (!h->no_split && vn_split16_supported(h->net)) HIPCHK(vn_split16_pgrad(h->net, h->theta, b.Xu, b.U, nullptr, nullptr, h->dd_uv, h->ncu, h->stream));
-  else HIPCHK(vn_pgrad16_launch(h->net, h->theta, b.Xu, b.U, nullptr, nullptr, h->dd_uv, h->ncu, h->pgrad_wgs, h->stream));
-  VnDedupArgs a{};
-  a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
-  a.gcoef = b.gcoef; a.gcoef_csr = b.gcsr; a.source = h->cfg.has_source ? b.source : nullptr;
-  a.feN = h->feN; a.fedNt = h->fedNt; a.feW = (h->cfg.has_integw && h->has_feW) ? h->feW : nullptr;
-  a.detJv = b.detJv; a.detJ = (float)b.detJ; a.n_k = b.n_k; a.U = b.U; a.q = q; a.dim = dim;
-  a.time_dependent = h->cfg.time_dependent; a.w2 = (float)h->w[2]; a.gper = b.gper ? 1 : 0;
-  a.stf = nullptr; a.lossVec = lossVec; a.part = h->losspart;          // loss only: no seeds
-  a.seed_u = nullptr; a.seed_g = nullptr;
+  HIPCHK(point_pass(h, b.Xu, b.U, nullptr, nullptr, h->dd_uv));
+  VnDedupArgs a = dedup_args(h, b);
+  a.lossVec = lossVec; a.part = h->losspart;          // loss only: no seeds
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
   if (int rc = fused_forward(h, bi_x(h, b), nullptr, h->nB, h->ub, nullptr)) return rc;
-  VnSeedArgs s{};
-  s.u = h->u; s.ud = h->ud; s.source = nullptr; s.feN = h->feN; s.fedNt = h->fedNt; s.feW = nullptr;
-  s.Nrow = nullptr; s.dNtrow = nullptr; s.detJv = nullptr; s.detJ = (float)b.detJ;
-  s.n_k = 0; s.integ_num = q; s.time_dependent = h->cfg.time_dependent;      // interior set empty: the BC/IC terms alone
-  s.ubar = nullptr; s.udbar = nullptr; s.lossVec = nullptr;
-  s.ub = h->ub; s.label = bi_y(h, b); s.nB = h->nB; s.bDof = h->bDof; s.biDimVal = (float)h->biDimVal; s.ubar_b = nullptr;
-  s.w0 = (float)h->w[0]; s.w1 = (float)h->w[1]; s.w2 = (float)h->w[2];
+  VnSeedArgs s = seed_args(h, b);
+  // interior set empty: the BC/IC terms alone (Nrow, dNtrow and detJv are nullptr on a batch with a de-duplication map)
+  s.n_k = 0; s.source = nullptr; s.feW = nullptr;
   s.part = h->losspart + (long)sblk * 3;
   HIPCHK(vn_seed_launch(s, bgrid, h->stream));
   if (lossdst)
@@ -318,45 +454,87 @@ int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst) {
 
 // forward + weak-form epilogue; with_seeds = also produce backward seeds.
 int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* lossVec, float* lossdst) {
-  const long nT = b.n_k * h->cfg.integ_num;
-  if (!with_seeds && b.Xu && !h->layered && (h->use_fused16 || h->two_pass) && h->has_fe && !h->eval_rowwise)
-    return eval_dedup(h, b, lossVec, lossdst);
-  if (h->layered) {
-    VnRows s0{}, s1{};
-    s0.X = b.Input; s0.G = b.gcoef; s0.u = h->u; s0.ud = h->ud; s0.n = nT;
-    s1.X = bi_x(h, b); s1.G = nullptr; s1.u = h->ub; s1.ud = nullptr; s1.n = h->nB;
+  if (!with_seeds && b.Xu && h->has_fe && !h->eval_rowwise) return eval_dedup(h, b, lossVec, lossdst);
+  VnRows s0{}, s1{};
+  s0.X = b.Input; s0.G = b.gcoef; s0.u = h->u; s0.ud = h->ud; s0.n = b.n_k * h->cfg.integ_num;
+  s1.X = bi_x(h, b); s1.G = nullptr; s1.u = h->ub; s1.ud = nullptr; s1.n = h->nB;
+  if (h->route == Route::layered) {
     LAYCHK(vn_layered_forward(h->layered, h->theta, s0, h->stream, lerr_, sizeof lerr_, with_seeds ? 0 : -1));
     LAYCHK(vn_layered_forward(h->layered, h->theta, s1, h->stream, lerr_, sizeof lerr_, with_seeds ? 1 : -1));
-  } else if (((h->use_fused16 || h->two_pass) && h->has_fe && !with_seeds) || h->fused_only) {
-    // splitLoss / trainWeight / the monitors: the fused kernel's forward-only mode for both row sets
-    if (int rc = fused_forward(h, b.Input, b.gcoef, nT, h->u, h->ud)) return rc;
-    if (int rc = fused_forward(h, bi_x(h, b), nullptr, h->nB, h->ub, nullptr)) return rc;
+  } else if ((on_8wave(h) && h->has_fe && !with_seeds) || !vn_net_in_kernel_range(h->net)) {
+    // splitLoss / trainWeight / the monitors: the fused kernel's forward-only mode for both row sets (and every forward of a
+    // 7-8 hidden layer net, which the generic kernels do not cover)
+    if (int rc = fused_forward(h, s0.X, s0.G, s0.n, s0.u, s0.ud)) return rc;
+    if (int rc = fused_forward(h, s1.X, nullptr, s1.n, s1.u, nullptr)) return rc;
   } else {
-    VnRows s0{}, s1{};
-    s0.X = b.Input; s0.G = b.gcoef; s0.u = h->u; s0.ud = h->ud; s0.n = nT;
-    s1.X = bi_x(h, b); s1.G = nullptr; s1.u = h->ub; s1.ud = nullptr; s1.n = h->nB;
     HIPCHK(vn_generic_forward(h->net, h->theta, s0, s1, h->fwd_grid, h->stream));
   }
 
   const long nthreads = b.n_k > h->nB ? b.n_k : h->nB;
   const int grid = (int)(((nthreads > 0 ? nthreads : 1) + 255) / 256);      // an empty set still zeroes its partials
   if (int rc = ensure(&h->losspart, &h->losspart_cap, (long)grid * 3)) return rc;
-  VnSeedArgs a{};
-  a.u = h->u; a.ud = h->ud; a.source = h->cfg.has_source ? b.source : nullptr;
-  a.feN = h->feN; a.fedNt = h->fedNt; a.feW = (h->cfg.has_integw && h->has_feW) ? h->feW : nullptr;
-  a.Nrow = b.Nrow; a.dNtrow = b.dNtrow;
-  a.detJv = b.detJv; a.detJ = (float)b.detJ;
-  a.n_k = b.n_k; a.integ_num = h->cfg.integ_num; a.time_dependent = h->cfg.time_dependent;
-  a.ubar = with_seeds ? h->ubar : nullptr; a.udbar = with_seeds ? h->udbar : nullptr;
-  a.lossVec = lossVec;
-  a.ub = h->ub; a.label = bi_y(h, b); a.nB = h->nB; a.bDof = h->bDof; a.biDimVal = (float)h->biDimVal;
-  a.ubar_b = with_seeds ? h->ubar_b : nullptr;
-  a.w0 = (float)h->w[0]; a.w1 = (float)h->w[1]; a.w2 = (float)h->w[2];
-  a.part = h->losspart;
+  VnSeedArgs a = seed_args(h, b);
+  if (with_seeds) { a.ubar = h->ubar; a.udbar = h->udbar; a.ubar_b = h->ubar_b; }
+  a.lossVec = lossVec; a.part = h->losspart;
   HIPCHK(vn_seed_launch(a, grid, h->stream));
   if (lossdst) {
     HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2, lossdst, h->stream));
   }
+  return VN_OK;
+}
+
+int run_layered(vn_engine* h, const Batch& b, float* gradbuf) {
+  if (int rc = run_forward_and_seed(h, b, true, nullptr, nullptr)) return rc;
+  VnRows s0{}, s1{};
+  s0.X = b.Input; s0.G = b.gcoef; s0.ubar = h->ubar; s0.udbar = h->udbar; s0.n = b.n_k * h->cfg.integ_num;
+  s1.X = bi_x(h, b); s1.G = nullptr; s1.ubar = h->ubar_b; s1.udbar = nullptr; s1.n = h->nB;
+  // one gradient vector (no per-workgroup partials): the GEMMs accumulate into it chunk by chunk
+  HIPCHK(hipMemsetAsync(h->partial, 0, (size_t)h->net.P * sizeof(float), h->stream));
+  if (int rc = prof_start(h)) return rc;
+  LAYCHK(vn_layered_backward(h->layered, h->theta, s0, h->partial, h->stream, lerr_, sizeof lerr_, 0));
+  LAYCHK(vn_layered_backward(h->layered, h->theta, s1, h->partial, h->stream, lerr_, sizeof lerr_, 1));
+  if (int rc = prof_stop(h)) return rc;
+  const long nth = b.n_k > h->nB ? b.n_k : h->nB;
+  const int lg = (int)(((nth > 0 ? nth : 1) + 255) / 256);
+  HIPCHK(vn_reduce_launch(h->partial, 1, h->net.P, h->losspart, lg, h->bDof, h->nB, (float)h->w[0], (float)h->w[1],
+                          (float)h->w[2], gradbuf, h->stream, h->fuse));
+  return VN_OK;
+}
+
+int run_generic(vn_engine* h, const Batch& b, float* gradbuf) {
+  if (int rc = run_forward_and_seed(h, b, true, nullptr, nullptr)) return rc;
+  VnRows s0{}, s1{};
+  s0.X = b.Input; s0.G = b.gcoef; s0.ubar = h->ubar; s0.udbar = h->udbar; s0.n = b.n_k * h->cfg.integ_num;
+  s1.X = bi_x(h, b); s1.G = nullptr; s1.ubar = h->ubar_b; s1.udbar = nullptr; s1.n = h->nB;
+  if (int rc = prof_start(h)) return rc;
+  HIPCHK(vn_generic_backward(h->net, h->theta, s0, s1, h->partial, h->bwd_grid, h->stream));
+  if (int rc = prof_stop(h)) return rc;
+  const long nthreads = b.n_k > h->nB ? b.n_k : h->nB;
+  const int lgrid = (int)((nthreads + 255) / 256);
+  HIPCHK(vn_reduce_launch(h->partial, h->bwd_grid, h->net.P, h->losspart, lgrid, h->bDof, h->nB, (float)h->w[0],
+                          (float)h->w[1], (float)h->w[2], gradbuf, h->stream, h->fuse));
+  return VN_OK;
+}
+
+// One launch of the fused kernel (8-wave, or 4-wave in the cross-check build) for the whole step: forward, weak-form epilogue
+// and reverse pass of every tile, BC/IC tiles included
+int run_fused(vn_engine* h, const Batch& b, float* gradbuf) {
+  VnFusedArgs a = fused_args(h, &b);
+  a.X = b.Input; a.G = b.gcoef; a.src = batch_src(h, b);
+  a.nT = b.n_k * h->cfg.integ_num; a.n_k = b.n_k; a.feW = fe_w(h);
+  a.Nrow = b.Nrow; a.dNtrow = b.dNtrow; a.detJv = b.detJv; a.detJ = (float)b.detJ;
+  a.partial = h->partial; a.losspart = h->fused_losspart; a.stamps = h->stamps;
+  // one persistent workgroup per CU, but never more workgroups than tiles (small mini-batches: idle workgroups would still
+  // image the weights, flush and store an all-zero partial that the reduction then has to read)
+  const long tt = 128 / a.integ_num > 0 ? 128 / a.integ_num : 1;
+  const long tiles = (a.n_k + tt - 1) / tt + (a.nB + 127) / 128;
+  const int grid = h->full_grid ? h->ncu : (int)(tiles < 1 ? 1 : tiles < h->ncu ? tiles : h->ncu);
+  if (int rc = prof_start(h)) return rc;
+  if (h->route == Route::fused8) HIPCHK(vn_fused16_launch(a, grid, h->stream));
+  else HIPCHK(vn_fused_launch(a, grid, h->stream));
+  if (int rc = prof_stop(h)) return rc;
+  HIPCHK(vn_reduce_launch(h->partial, grid, h->net.P, h->fused_losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2,
+                          gradbuf, h->stream, h->fuse));
   return VN_OK;
 }
 
@@ -367,43 +545,27 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
 //   3. reverse pass with those seeds (recomputes the forward); BC/IC tiles ride along   (6 F_pt)
 // 8 F_pt per point instead of 6, against 8 F_pt at 0.07 of peak on the generic kernels.
 int run_twopass(vn_engine* h, const Batch& b, float* gradbuf) {
-  const int grid = h->ncu, P = h->net.P, q = h->cfg.integ_num;
-  const long nT = b.n_k * q;
+  const int grid = h->ncu, P = h->net.P;
   const int sgrid = (int)((b.n_k + 255) / 256);
   if (int rc = ensure(&h->tp_losspart, &h->tp_losspart_cap, (long)(grid + sgrid) * 3)) return rc;
   float* lp = h->tp_losspart;
-  VnFusedArgs f{};
-  f.net = h->net; f.theta = h->theta; f.X = b.Input; f.G = b.gcoef; f.src = nullptr;
-  f.nT = nT; f.n_k = 0; f.integ_num = q;
-  f.feN = h->feN; f.fedNt = h->fedNt; f.feW = nullptr; f.detJv = nullptr; f.detJ = 0.f;
-  f.time_dependent = h->cfg.time_dependent; f.lossVec = nullptr;
-  f.Xb = bi_x(h, b); f.label = bi_y(h, b); f.nB = 0; f.bDof = h->bDof; f.biDimVal = (float)h->biDimVal;
-  f.w0 = (float)h->w[0]; f.w1 = (float)h->w[1]; f.w2 = (float)h->w[2];
-  f.partial = h->partial; f.losspart = lp; f.stamps = nullptr;
+  VnFusedArgs f = fused_args(h, &b);
+  f.X = b.Input; f.G = b.gcoef; f.nT = b.n_k * h->cfg.integ_num; f.nB = 0;     // BC/IC: step 3
+  f.partial = h->partial; f.losspart = lp;
   f.dir = -1; f.ostride = 1;
   f.mode = 1; f.out_u = h->u; f.out_ud = h->ud;
   HIPCHK(vn_fused16_launch(f, grid, h->stream));
 
-  VnSeedArgs a{};
-  a.u = h->u; a.ud = h->ud; a.source = h->cfg.has_source ? b.source : nullptr;
-  a.feN = h->feN; a.fedNt = h->fedNt; a.feW = (h->cfg.has_integw && h->has_feW) ? h->feW : nullptr;
-  a.Nrow = b.Nrow; a.dNtrow = b.dNtrow;
-  a.detJv = b.detJv; a.detJ = (float)b.detJ;
-  a.n_k = b.n_k; a.integ_num = q; a.time_dependent = h->cfg.time_dependent;
-  a.ubar = h->ubar; a.udbar = h->udbar; a.lossVec = nullptr;
-  a.ub = nullptr; a.label = nullptr; a.nB = 0; a.bDof = 0; a.biDimVal = 0.f; a.ubar_b = nullptr;   // BC/IC: step 3
-  a.w0 = f.w0; a.w1 = f.w1; a.w2 = f.w2;
+  VnSeedArgs a = seed_args(h, b);
+  a.ubar = h->ubar; a.udbar = h->udbar;
+  a.ub = nullptr; a.label = nullptr; a.nB = 0; a.bDof = 0; a.biDimVal = 0.f;   // BC/IC: step 3
   a.part = lp + (long)grid * 3;
   HIPCHK(vn_seed_launch(a, sgrid, h->stream));
 
   f.mode = 2; f.out_u = nullptr; f.out_ud = nullptr; f.seed_u = h->ubar; f.seed_ud = h->udbar; f.nB = h->nB;
-  const bool rec = h->prof_on && h->prof_n < PROF_CAP;
-  if (rec) {
-    if (!h->ev0[h->prof_n]) { HIPCHK(hipEventCreate(&h->ev0[h->prof_n])); HIPCHK(hipEventCreate(&h->ev1[h->prof_n])); }
-    HIPCHK(hipEventRecord(h->ev0[h->prof_n], h->stream));
-  }
+  if (int rc = prof_start(h)) return rc;
   HIPCHK(vn_fused16_launch(f, grid, h->stream));
-  if (rec) { HIPCHK(hipEventRecord(h->ev1[h->prof_n], h->stream)); h->prof_n++; }
+  if (int rc = prof_stop(h)) return rc;
   HIPCHK(vn_reduce_launch(h->partial, grid, P, lp, grid + sgrid, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream, h->fuse));
   return VN_OK;
 }
@@ -416,40 +578,25 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf) {
 //      direction, sum_d sg_d * d(u_{x_d})/d theta = d(sg . grad u)/d theta with sg held fixed, so the per-point direction
 //      G = sg with tangent seed 1 and value seed su gives the whole gradient; BC/IC tiles ride along       (6 F_pt)
 int run_dedup(vn_engine* h, const Batch& b, float* gradbuf) {
-  const int dim = h->cfg.dim, q = h->cfg.integ_num, grid = h->ncu, P = h->net.P;
+  const int grid = h->ncu, P = h->net.P;
   const int sblk = (int)((b.n_k + VN_DEDUP_TFB - 1) / VN_DEDUP_TFB);
   float* lp = h->dd_losspart;                       // [grid + sblk][3]
   // vn_profile_*: HIP events around the formulation's whole kernel sequence (steps 1-4; the reduction stays outside as
   // in the row-wise step)
-  const bool rec = h->prof_on && h->prof_n < PROF_CAP;
-  if (rec) {
-    if (!h->ev0[h->prof_n]) { HIPCHK(hipEventCreate(&h->ev0[h->prof_n])); HIPCHK(hipEventCreate(&h->ev1[h->prof_n])); }
-    HIPCHK(hipEventRecord(h->ev0[h->prof_n], h->stream));
-  }
-  if (!h->no_split && vn_split16_supported(h->net)) HIPCHK(vn_split16_pgrad(h->net, h->theta, b.Xu, b.U, nullptr, nullptr, h->dd_uv, grid, h->stream));
-  else HIPCHK(vn_pgrad16_launch(h->net, h->theta, b.Xu, b.U, nullptr, nullptr, h->dd_uv, grid, h->pgrad_wgs, h->stream));
-  VnDedupArgs a{};
-  a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
-  a.gcoef = b.gcoef; a.gcoef_csr = b.gcsr; a.source = h->cfg.has_source ? b.source : nullptr;
-  a.feN = h->feN; a.fedNt = h->fedNt; a.feW = (h->cfg.has_integw && h->has_feW) ? h->feW : nullptr;
-  a.detJv = b.detJv; a.detJ = (float)b.detJ; a.n_k = b.n_k; a.U = b.U; a.q = q; a.dim = dim;
-  a.time_dependent = h->cfg.time_dependent; a.w2 = (float)h->w[2]; a.gper = b.gper ? 1 : 0;
-  a.stf = h->u; a.lossVec = nullptr; a.part = lp + (long)grid * 3;
+  if (int rc = prof_start(h)) return rc;
+  HIPCHK(point_pass(h, b.Xu, b.U, nullptr, nullptr, h->dd_uv));
+  VnDedupArgs a = dedup_args(h, b);
+  a.stf = h->u; a.part = lp + (long)grid * 3;
   a.seed_u = h->dd_su; a.seed_g = h->dd_sg;
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
   HIPCHK(vn_dedup_gather_launch(a, h->stream));
-  VnFusedArgs f{};
-  f.net = h->net; f.theta = h->theta; f.X = b.Xu; f.G = h->dd_sg; f.src = nullptr;
-  f.nT = b.U; f.n_k = 0; f.integ_num = q;
-  f.feN = h->feN; f.fedNt = h->fedNt; f.feW = nullptr; f.detJv = nullptr; f.detJ = 0.f;
-  f.time_dependent = h->cfg.time_dependent; f.lossVec = nullptr;
-  f.Xb = bi_x(h, b); f.label = bi_y(h, b); f.nB = h->nB; f.bDof = h->bDof; f.biDimVal = (float)h->biDimVal;
-  f.w0 = (float)h->w[0]; f.w1 = (float)h->w[1]; f.w2 = (float)h->w[2];
-  f.partial = h->dd_partial; f.losspart = lp; f.stamps = nullptr;
-  f.mode = 2; f.dir = -1; f.ostride = 1; f.out_u = nullptr; f.out_ud = nullptr;
+  VnFusedArgs f = fused_args(h, &b);
+  f.X = b.Xu; f.G = h->dd_sg; f.nT = b.U;
+  f.partial = h->dd_partial; f.losspart = lp;
+  f.mode = 2; f.dir = -1; f.ostride = 1;
   f.seed_u = h->dd_su; f.seed_ud = nullptr;          // tangent seed 1
   HIPCHK(vn_fused16_launch(f, grid, h->stream));
-  if (rec) { HIPCHK(hipEventRecord(h->ev1[h->prof_n], h->stream)); h->prof_n++; }
+  if (int rc = prof_stop(h)) return rc;
   HIPCHK(vn_reduce_launch(h->dd_partial, grid, P, lp, grid + sblk, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream, h->fuse));
   return VN_OK;
 }
@@ -532,36 +679,16 @@ int vn_create(const vn_config* cfg, vn_engine** out) {
                 e == hipSuccess ? "device count 0" : hipGetErrorString(e));
   if (cfg->device < 0 || cfg->device >= ndev) return fail(VN_EINVAL, "requested processor %d is unavailable!", cfg->device);
   HIPCHK(hipSetDevice(cfg->device));
-  // Route.  Networks outside the kernels' range (VN_KMAX_*), and nets whose generic-kernel tile does not fit LDS while
-  // no fused instantiation exists, go layer by layer (vn_layered.hip); VN_KERNEL_LAYERED forces that route.  One
-  // extension of the range: 7 and 8 hidden layers up to 50 wide are instantiated in the 8-wave fused kernel (deep,
-  // narrow nets); the generic kernels do not cover them, so every path of such an engine runs on the fused kernel.
-  const bool generic_range = vn_net_in_kernel_range(net);
-  const bool deep_fused = !generic_range && net.L <= 8 && net.hmax <= VN_KMAX_WIDTH && net.d_in <= VN_KMAX_DIN &&
-                          net.act != VN_ACT_PER_LAYER && vn_fused16_net_supported(net) &&
-                          (cfg->kernel == VN_KERNEL_AUTO || cfg->kernel == VN_KERNEL_FUSED16);
-  const bool in_range = generic_range || deep_fused;
-  if (!in_range && cfg->kernel != VN_KERNEL_AUTO && cfg->kernel != VN_KERNEL_LAYERED)
-    return fail(VN_EUNSUPPORTED, "network (%d layers, widest %d, %d inputs%s) is outside the range of the requested kernel family "
-                "(<= %d layers, width <= %d, <= %d inputs, one activation): use VN_KERNEL_AUTO or VN_KERNEL_LAYERED",
-                net.L, net.hmax, net.d_in, net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "", VN_KMAX_LAYERS,
-                VN_KMAX_WIDTH, VN_KMAX_DIN);
-  const bool fused_ok = in_range && cfg->kernel != VN_KERNEL_GENERIC && cfg->kernel != VN_KERNEL_FUSED &&
-                        cfg->kernel != VN_KERNEL_LAYERED && vn_fused16_net_supported(net);
-  bool use_layered = cfg->kernel == VN_KERNEL_LAYERED || !in_range;
-  if (!use_layered && !fused_ok && vn_generic_bwd_lds_bytes(net) > 160 * 1024) {
-    if (cfg->kernel == VN_KERNEL_AUTO) use_layered = true;
-    else
-      return fail(VN_EUNSUPPORTED, "network needs %zu B of LDS per tile on the generic kernels (> 160 KiB): reduce depth/width",
-                  vn_generic_bwd_lds_bytes(net));
-  }
+  Route route;
+  if (int rc = pick_route(*cfg, net, &route)) return rc;
   vn_engine* h = new vn_engine();
   h->cfg = *cfg;              // taken literally (lr = 0 is a legal, if useless, TF learning rate: TFModel.py:130)
   h->net = net;
+  h->route = route;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess) h->ncu = prop.multiProcessorCount;
   const size_t P = net.P;
-  if (use_layered) {
+  if (route == Route::layered) {
     h->fwd_grid = h->bwd_grid = 1;            // one gradient vector, no per-workgroup partials
   } else {
     const size_t fwd_lds = vn_generic_fwd_lds_bytes(net), bwd_lds = vn_generic_bwd_lds_bytes(net);
@@ -570,6 +697,10 @@ int vn_create(const vn_config* cfg, vn_engine** out) {
     h->fwd_grid = h->ncu * fpc;
     h->bwd_grid = h->ncu * bpc;
   }
+  h->ev0.resize(PROF_CAP, nullptr);
+  h->ev1.resize(PROF_CAP, nullptr);
+  h->cev0.resize(PROF_CAP, nullptr);
+  h->cev1.resize(PROF_CAP, nullptr);
   hipError_t a = hipSuccess;
   if (a == hipSuccess) a = hipMalloc((void**)&h->theta, P * sizeof(float));
   if (a == hipSuccess) a = hipMalloc((void**)&h->m, P * sizeof(float));
@@ -589,50 +720,23 @@ int vn_create(const vn_config* cfg, vn_engine** out) {
     return fail(VN_ENOMEM, "device allocation failed: %s", hipGetErrorString(a));
   }
   h->gradbuf = h->gradbuf_int;
-  if (use_layered) {
+  { const char* fg = getenv("VN_FULL_GRID"); h->full_grid = fg && *fg && *fg != '0'; }
+  if (route == Route::layered) {
     char lerr[384] = "";
     if (vn_layered_create(&h->layered, net, lerr, sizeof lerr)) {
       vn_destroy(h);
       return fail(VN_EUNSUPPORTED, "layer-by-layer route unavailable: %s", lerr);
     }
     h->prof_name = "vn_layered_backward";
-    h->ev0.resize(PROF_CAP, nullptr);
-    h->ev1.resize(PROF_CAP, nullptr);
-    h->cev0.resize(PROF_CAP, nullptr);
-    h->cev1.resize(PROF_CAP, nullptr);
-    *out = h;
-    return VN_OK;
-  }
-  if (cfg->kernel == VN_KERNEL_FUSED && !vn_fused_supported(net, cfg->integ_num)) {
-    vn_destroy(h);
-    return fail(VN_EUNSUPPORTED, kWithFused32 ? "fused kernel unsupported for this network / integ_num"
-                                              : "VN_KERNEL_FUSED (the 4-wave geometry) is not part of the product library: it lives in the "
-                                                "tests' cross-check build, libvarnet_hip_xcheck.so (make -C varnet_amd/csrc xcheck)");
-  }
-  const bool tp_ok = cfg->integ_num > 128 && vn_fused16_net_supported(net);
-  if (cfg->kernel == VN_KERNEL_FUSED16 && !vn_fused16_supported(net, cfg->integ_num) && !tp_ok) {
-    vn_destroy(h);
-    return fail(VN_EUNSUPPORTED, "fused16 kernel unsupported for this network / integ_num");
-  }
-  // AUTO: the 8-wave geometry where instantiated (faster: two waves per SIMD overlap VALU/LDS work
-  // with MFMA), else the 4-wave geometry, else the generic kernels
-  h->use_fused16 = (cfg->kernel == VN_KERNEL_FUSED16 || cfg->kernel == VN_KERNEL_AUTO) &&
-                   vn_fused16_supported(net, cfg->integ_num);
-  h->use_fused = h->use_fused16 ||
-                 (cfg->kernel != VN_KERNEL_GENERIC && vn_fused_supported(net, cfg->integ_num));
-  h->two_pass = !h->use_fused && tp_ok && (cfg->kernel == VN_KERNEL_FUSED16 || cfg->kernel == VN_KERNEL_AUTO);
-  h->fused_only = deep_fused;
-  { const char* fg = getenv("VN_FULL_GRID"); h->full_grid = fg && *fg && *fg != '0'; }
-  { const char* pw = getenv("VN_PGRAD_WGS"); if (pw && *pw >= '1' && *pw <= '4') h->pgrad_wgs = *pw - '0'; }
-  if (h->use_fused || h->two_pass) {
+  } else if (route != Route::generic) {
     // (the forward-only mode of the 8-wave kernel writes its per-workgroup loss partials here too: vn_forward and
     // vn_eval_loss of a two-pass engine must not find it NULL)
     if (hipMalloc((void**)&h->fused_losspart, (size_t)h->ncu * 3 * sizeof(float)) != hipSuccess) {
       vn_destroy(h);
       return fail(VN_ENOMEM, "device allocation failed");
     }
-    h->prof_name = (h->use_fused16 || h->two_pass) ? "vn_fused16_kernel" : "vn_fused_kernel";
-    if (h->use_fused16 || h->two_pass) {       // the instantiation that runs, as rocprofv3 prints it (template arguments)
+    h->prof_name = "vn_fused_kernel";
+    if (on_8wave(h)) {       // the instantiation that runs, as rocprofv3 prints it (template arguments)
       char nm[96];
       snprintf(nm, sizeof nm, "vn_fused16_kernel<%d, %d, %s>", net.L, vn_fused16_ks(net), net.act == VN_ACT_TANH ? "true" : "false");
       h->prof_name = nm;
@@ -640,10 +744,6 @@ int vn_create(const vn_config* cfg, vn_engine** out) {
     if (hipMalloc((void**)&h->stamps, 8 * sizeof(unsigned long long)) == hipSuccess)
       (void)hipMemset(h->stamps, 0, 8 * sizeof(unsigned long long));
   }
-  h->ev0.resize(PROF_CAP, nullptr);
-  h->ev1.resize(PROF_CAP, nullptr);
-  h->cev0.resize(PROF_CAP, nullptr);
-  h->cev1.resize(PROF_CAP, nullptr);
   *out = h;
   return VN_OK;
 }
@@ -654,7 +754,7 @@ int vn_destroy(vn_engine* h) {
   if (h->layered) { (void)hipStreamSynchronize(h->stream); vn_layered_destroy(h->layered); h->layered = nullptr; }
   if (h->comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(h->stream); (void)g_rccl.CommDestroy(h->comm); h->comm = nullptr; }
   void* ptrs[] = {h->theta, h->m, h->v, h->snap, h->theta64, h->gradbuf_int, h->lossbuf, h->partial, h->feN, h->fedNt,
-                  h->feW, h->u, h->ud, h->ubar, h->udbar, h->ub, h->ubar_b, h->losspart, h->fused_losspart, h->stamps, h->dd_uv, h->dd_ug, h->dd_su, h->dd_sg, h->dd_partial,
+                  h->feW, h->u, h->ud, h->ubar, h->udbar, h->ub, h->ubar_b, h->losspart, h->fused_losspart, h->stamps, h->dd_uv, h->dd_su, h->dd_sg, h->dd_partial,
                   h->dd_losspart, h->tp_losspart};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -855,71 +955,35 @@ int vn_set_dedup(vn_engine* h, int32_t batch, const float* Xu, int64_t U, const 
   if (!uid || !rowptr || !rowidx || U <= 0) return fail(VN_EINVAL, "null argument");
   // the formulation has no tiles of whole test functions (its rows are unique points), so it also serves integ_num beyond one
   // 128-point tile -- the networks of the two-pass route (216: three-point Gauss in 2D+t) -- up to the seed kernel's 256-row chunk
-  if (!h->use_fused16 && !h->two_pass) return fail(VN_EUNSUPPORTED, "de-duplication needs the 8-wave fused kernel for this network");
+  if (!on_8wave(h)) return fail(VN_EUNSUPPORTED, "de-duplication needs the 8-wave fused kernel for this network");
   if (h->cfg.integ_num > 256) return fail(VN_EUNSUPPORTED, "de-duplication supports integ_num <= 256");
   if (b.Nrow || b.detJv) return fail(VN_EUNSUPPORTED, "de-duplication needs uniform supports (no per-row tables)");
   if (h->cfg.dim > 3) return fail(VN_EUNSUPPORTED, "de-duplication supports dim <= 3");
   HIPCHK(hipSetDevice(h->cfg.device));
   const int dim = h->cfg.dim;
-  if (U > h->dd_capU) {
-    float** bufs[] = {&h->dd_uv, &h->dd_su, &h->dd_sg};          // dd_uv: [U, 4] packed (u, grad u) records
-    const long sizes[] = {4 * U, U, U * dim};
-    for (int i = 0; i < 3; ++i) {
-      if (*bufs[i]) (void)hipFree(*bufs[i]);
-      *bufs[i] = nullptr;
-      HIPCHK(hipMalloc((void**)bufs[i], (size_t)sizes[i] * sizeof(float)));
-    }
-    h->dd_capU = U;
-  }
-  if (!h->dd_partial) HIPCHK(hipMalloc((void**)&h->dd_partial, (size_t)h->ncu * h->net.P * sizeof(float)));
-  const long need_lp = ((long)h->ncu + (b.n_k + VN_DEDUP_TFB - 1) / VN_DEDUP_TFB) * 3;
-  if (need_lp > h->dd_cap_lp) {
-    if (h->dd_losspart) (void)hipFree(h->dd_losspart);
-    h->dd_losspart = nullptr;
-    HIPCHK(hipMalloc((void**)&h->dd_losspart, (size_t)need_lp * sizeof(float)));
-    h->dd_cap_lp = need_lp;
-  }
+  const long nT = b.n_k * h->cfg.integ_num;
+  if (int rc = ensure(&h->dd_uv, &h->dd_uv_cap, 4 * U)) return rc;          // [U, 4] packed (u, grad u) records
+  if (int rc = ensure(&h->dd_su, &h->dd_su_cap, U)) return rc;
+  if (int rc = ensure(&h->dd_sg, &h->dd_sg_cap, U * dim)) return rc;
+  if (int rc = ensure(&h->dd_partial, &h->dd_partial_cap, (long)h->ncu * h->net.P)) return rc;
+  if (int rc = ensure(&h->dd_losspart, &h->dd_cap_lp, ((long)h->ncu + (b.n_k + VN_DEDUP_TFB - 1) / VN_DEDUP_TFB) * 3)) return rc;
   // The map indexes device memory in every later kernel: validate it once, here (a registration call may synchronise), so
   // that an inconsistent map is an error code and never a GPU fault.  The rowptr reads assume U + 1 entries, rowidx / uid nT.
-  {
-    const long nTc = b.n_k * h->cfg.integ_num;
-    int* err_dev = nullptr;
-    HIPCHK(hipMalloc((void**)&err_dev, sizeof(int)));
-    hipError_t e = hipMemsetAsync(err_dev, 0, sizeof(int), h->stream);
-    if (e == hipSuccess) e = vn_dedup_check_launch(uid, rowptr, rowidx, nTc, U, err_dev, h->stream);
-    int bad = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, err_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(err_dev);
-    if (e != hipSuccess) return fail(VN_EHIP, "vn_set_dedup: %s", hipGetErrorString(e));
-    if (bad) return fail(VN_EINVAL, "inconsistent de-duplication map: %d violation(s) (need 0 <= uid < U, rowptr[0] = 0 <= ... <= rowptr[U] = n_k*integ_num, "
-                                    "0 <= rowidx < n_k*integ_num, uid[rowidx[e]] = the point whose segment holds e, rows of a point in increasing order)", bad);
-  }
+  int bad = 0;
+  auto check = [&](int* err_dev) { return vn_dedup_check_launch(uid, rowptr, rowidx, nT, U, err_dev, h->stream); };
+  if (int rc = count_on_device(h, check, &bad)) return rc;
+  if (bad) return fail(VN_EINVAL, "inconsistent de-duplication map: %d violation(s) (need 0 <= uid < U, rowptr[0] = 0 <= ... <= rowptr[U] = n_k*integ_num, "
+                                  "0 <= rowidx < n_k*integ_num, uid[rowidx[e]] = the point whose segment holds e, rows of a point in increasing order)", bad);
   // With constant coefficients gcoef = kappa dN/dx + v N repeats with period integ_num along the rows (the reference tiles the
   // tables to nT rows, VarNet.py:837): detected here, bitwise, and both assembly kernels then read the rows of test function 0
   // as an integ_num-entry table instead of 8 bytes per row each.  Otherwise the gather kernel gets gcoef in CSR order (it then
   // reads it, like rowidx, as one contiguous stream: a per-row gather of 8-byte entries fetched 2.6 x the bytes it used,
   // profiles/r5_pmc_traffic_dedup.json).  gcoef is static per batch: examined / permuted once, here.
-  const long nT = b.n_k * h->cfg.integ_num;
-  {
-    int* err_dev = nullptr;
-    HIPCHK(hipMalloc((void**)&err_dev, sizeof(int)));
-    hipError_t e = hipMemsetAsync(err_dev, 0, sizeof(int), h->stream);
-    if (e == hipSuccess) e = vn_dedup_periodic_launch(b.gcoef, nT, h->cfg.integ_num, dim, err_dev, h->stream);
-    int bad = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, err_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(err_dev);
-    if (e != hipSuccess) return fail(VN_EHIP, "vn_set_dedup: %s", hipGetErrorString(e));
-    b.gper = bad == 0 && !h->no_gtable;
-  }
+  auto periodic = [&](int* err_dev) { return vn_dedup_periodic_launch(b.gcoef, nT, h->cfg.integ_num, dim, err_dev, h->stream); };
+  if (int rc = count_on_device(h, periodic, &bad)) return rc;
+  b.gper = bad == 0 && !h->no_gtable;
   if (!b.gper) {
-    if (nT * dim > b.gcsr_cap) {
-      if (b.gcsr) (void)hipFree(b.gcsr);
-      b.gcsr = nullptr; b.gcsr_cap = 0;
-      HIPCHK(hipMalloc((void**)&b.gcsr, (size_t)nT * dim * sizeof(float)));
-      b.gcsr_cap = nT * dim;
-    }
+    if (int rc = ensure(&b.gcsr, &b.gcsr_cap, nT * dim)) return rc;
     HIPCHK(vn_dedup_permute_launch(b.gcoef, rowidx, b.gcsr, nT, dim, h->stream));
   }
   b.Xu = Xu; b.U = U; b.uid = uid; b.rowptr = rowptr; b.rowidx = rowidx;
@@ -971,71 +1035,14 @@ int vn_grad(vn_engine* h, int32_t batch) {
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   const Batch& b = h->batches[batch];
-  if (b.Xu && (h->use_fused16 || h->two_pass)) return run_dedup(h, b, h->gradbuf);
-  if (h->two_pass) return run_twopass(h, b, h->gradbuf);
-  if (h->use_fused) {
-    VnFusedArgs a{};
-    a.net = h->net; a.theta = h->theta;
-    a.X = b.Input; a.G = b.gcoef; a.src = h->cfg.has_source ? b.source : nullptr;
-    a.nT = b.n_k * h->cfg.integ_num; a.n_k = b.n_k; a.integ_num = h->cfg.integ_num;
-    a.feN = h->feN; a.fedNt = h->fedNt; a.feW = (h->cfg.has_integw && h->has_feW) ? h->feW : nullptr;
-    a.Nrow = b.Nrow; a.dNtrow = b.dNtrow;
-    a.detJv = b.detJv; a.detJ = (float)b.detJ; a.time_dependent = h->cfg.time_dependent;
-    a.lossVec = nullptr;
-    a.Xb = bi_x(h, b); a.label = bi_y(h, b); a.nB = h->nB; a.bDof = h->bDof; a.biDimVal = (float)h->biDimVal;
-    a.w0 = (float)h->w[0]; a.w1 = (float)h->w[1]; a.w2 = (float)h->w[2];
-    a.partial = h->partial; a.losspart = h->fused_losspart; a.stamps = h->stamps;
-    // one persistent workgroup per CU, but never more workgroups than tiles (small mini-batches: idle workgroups would still
-    // image the weights, flush and store an all-zero partial that the reduction then has to read)
-    const long tt = 128 / a.integ_num > 0 ? 128 / a.integ_num : 1;
-    const long tiles = (a.n_k + tt - 1) / tt + (a.nB + 127) / 128;
-    const int grid = h->full_grid ? h->ncu : (int)(tiles < 1 ? 1 : tiles < h->ncu ? tiles : h->ncu);
-    const bool rec = h->prof_on && h->prof_n < PROF_CAP;
-    if (rec) {
-      if (!h->ev0[h->prof_n]) { HIPCHK(hipEventCreate(&h->ev0[h->prof_n])); HIPCHK(hipEventCreate(&h->ev1[h->prof_n])); }
-      HIPCHK(hipEventRecord(h->ev0[h->prof_n], h->stream));
-    }
-    if (h->use_fused16) HIPCHK(vn_fused16_launch(a, grid, h->stream));
-    else HIPCHK(vn_fused_launch(a, grid, h->stream));
-    if (rec) { HIPCHK(hipEventRecord(h->ev1[h->prof_n], h->stream)); h->prof_n++; }
-    HIPCHK(vn_reduce_launch(h->partial, grid, h->net.P, h->fused_losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2,
-                            h->gradbuf, h->stream, h->fuse));
-    return VN_OK;
+  if (b.Xu) return run_dedup(h, b, h->gradbuf);      // (a de-duplication map: 8-wave routes only)
+  switch (h->route) {
+    case Route::layered: return run_layered(h, b, h->gradbuf);
+    case Route::generic: return run_generic(h, b, h->gradbuf);
+    case Route::fused4:
+    case Route::fused8: return run_fused(h, b, h->gradbuf);
+    case Route::twopass: return run_twopass(h, b, h->gradbuf);
   }
-  if (int rc = run_forward_and_seed(h, b, true, nullptr, nullptr)) return rc;
-  const long nT = b.n_k * h->cfg.integ_num;
-  VnRows s0{}, s1{};
-  s0.X = b.Input; s0.G = b.gcoef; s0.ubar = h->ubar; s0.udbar = h->udbar; s0.n = nT;
-  s1.X = bi_x(h, b); s1.G = nullptr; s1.ubar = h->ubar_b; s1.udbar = nullptr; s1.n = h->nB;
-  if (h->layered) {
-    // one gradient vector (no per-workgroup partials): the GEMMs accumulate into it chunk by chunk
-    HIPCHK(hipMemsetAsync(h->partial, 0, (size_t)h->net.P * sizeof(float), h->stream));
-    const bool lrec = h->prof_on && h->prof_n < PROF_CAP;
-    if (lrec) {
-      if (!h->ev0[h->prof_n]) { HIPCHK(hipEventCreate(&h->ev0[h->prof_n])); HIPCHK(hipEventCreate(&h->ev1[h->prof_n])); }
-      HIPCHK(hipEventRecord(h->ev0[h->prof_n], h->stream));
-    }
-    LAYCHK(vn_layered_backward(h->layered, h->theta, s0, h->partial, h->stream, lerr_, sizeof lerr_, 0));
-    LAYCHK(vn_layered_backward(h->layered, h->theta, s1, h->partial, h->stream, lerr_, sizeof lerr_, 1));
-    if (lrec) { HIPCHK(hipEventRecord(h->ev1[h->prof_n], h->stream)); h->prof_n++; }
-    const long nth = b.n_k > h->nB ? b.n_k : h->nB;
-    const int lg = (int)(((nth > 0 ? nth : 1) + 255) / 256);
-    HIPCHK(vn_reduce_launch(h->partial, 1, h->net.P, h->losspart, lg, h->bDof, h->nB, (float)h->w[0], (float)h->w[1],
-                            (float)h->w[2], h->gradbuf, h->stream, h->fuse));
-    return VN_OK;
-  }
-  const bool rec = h->prof_on && h->prof_n < PROF_CAP;
-  if (rec) {
-    if (!h->ev0[h->prof_n]) { HIPCHK(hipEventCreate(&h->ev0[h->prof_n])); HIPCHK(hipEventCreate(&h->ev1[h->prof_n])); }
-    HIPCHK(hipEventRecord(h->ev0[h->prof_n], h->stream));
-  }
-  HIPCHK(vn_generic_backward(h->net, h->theta, s0, s1, h->partial, h->bwd_grid, h->stream));
-  if (rec) { HIPCHK(hipEventRecord(h->ev1[h->prof_n], h->stream)); h->prof_n++; }
-  const long nthreads = b.n_k > h->nB ? b.n_k : h->nB;
-  const int lgrid = (int)((nthreads + 255) / 256);
-  HIPCHK(vn_reduce_launch(h->partial, h->bwd_grid, h->net.P, h->losspart, lgrid, h->bDof, h->nB, (float)h->w[0],
-                          (float)h->w[1], (float)h->w[2], h->gradbuf, h->stream, h->fuse));
-  return VN_OK;
 }
 
 static int apply_impl(vn_engine* h, float* loss_acc) {
@@ -1122,21 +1129,18 @@ int vn_forward(vn_engine* h, const float* X, int64_t n, float* u) {
   if (!h || (n > 0 && (!X || !u))) return fail(VN_EINVAL, "null argument");
   (void)hipGetLastError();   // a stale last-error of another library on this thread is not ours to report
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (h->layered) {
+  if (h->route == Route::layered) {
     VnRows sl{};
     sl.X = X; sl.G = nullptr; sl.u = u; sl.ud = nullptr; sl.n = n;
     LAYCHK(vn_layered_forward(h->layered, h->theta, sl, h->stream, lerr_, sizeof lerr_));
     return VN_OK;
   }
-  // networks of the 8-wave family: the value-only sweep of vn_pgrad16 (F_pt per point; the fused kernel's forward-only mode
-  // would carry a tangent stream of zeros through every layer)
-  if (h->use_fused16 || h->two_pass) {
-    // hidden widths 33..64: the products as six bf16-piece MFMAs, fp32-class (vn_split16.hip)
-    if (!h->no_split && vn_split16_supported(h->net)) HIPCHK(vn_split16_forward(h->net, h->theta, X, n, u, h->ncu, h->stream));
-    else HIPCHK(vn_pgrad16_launch(h->net, h->theta, X, n, u, nullptr, nullptr, h->ncu, h->pgrad_wgs, h->stream));
+  // networks of the 8-wave family (7-8 hidden layers included): the value-only sweep of the point kernels (F_pt per point;
+  // the fused kernel's forward-only mode would carry a tangent stream of zeros through every layer)
+  if (on_8wave(h)) {
+    HIPCHK(point_pass(h, X, n, u, nullptr, nullptr));
     return VN_OK;
   }
-  if (h->fused_only) return fused_forward(h, X, nullptr, n, u, nullptr);
   VnRows s0{}, s1{};
   s0.X = X; s0.G = nullptr; s0.u = u; s0.ud = nullptr; s0.n = n;
   HIPCHK(vn_generic_forward(h->net, h->theta, s0, s1, h->fwd_grid, h->stream));
@@ -1146,11 +1150,10 @@ int vn_forward(vn_engine* h, const float* X, int64_t n, float* u) {
 int vn_forward_grad(vn_engine* h, const float* X, int64_t n, float* u, float* g) {
   if (!h || (n > 0 && (!X || !u || !g))) return fail(VN_EINVAL, "null argument");
   (void)hipGetLastError();   // a stale last-error of another library on this thread is not ours to report
-  if (!h->use_fused16 && !h->two_pass) return fail(VN_EUNSUPPORTED, "vn_forward_grad needs a network of the 8-wave fused kernel");
+  if (!on_8wave(h)) return fail(VN_EUNSUPPORTED, "vn_forward_grad needs a network of the 8-wave fused kernel");
   if (h->cfg.dim > 3) return fail(VN_EUNSUPPORTED, "vn_forward_grad supports dim <= 3");
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (!h->no_split && vn_split16_supported(h->net)) HIPCHK(vn_split16_pgrad(h->net, h->theta, X, n, u, g, nullptr, h->ncu, h->stream));
-  else HIPCHK(vn_pgrad16_launch(h->net, h->theta, X, n, u, g, nullptr, h->ncu, h->pgrad_wgs, h->stream));
+  HIPCHK(point_pass(h, X, n, u, g, nullptr));
   return VN_OK;
 }
 
@@ -1159,12 +1162,11 @@ int vn_forward_f64(vn_engine* h, const double* X, int64_t n, double* u) {
   (void)hipGetLastError();   // a stale last-error of another library on this thread is not ours to report
   HIPCHK(hipSetDevice(h->cfg.device));
   if (int rc = refresh_theta64(h)) return rc;
-  if (h->layered) {
+  if (h->route == Route::layered) {
     LAYCHK(vn_layered_forward_f64(h->layered, h->theta64, X, n, u, h->stream, lerr_, sizeof lerr_));
     return VN_OK;
   }
-  // networks of the 8-wave family whose fp64 images fit the LDS: the fp64 matrix pipe (vn_taylor16d.hip); else per thread
-  if ((h->use_fused16 || h->two_pass) && vn_taylor16d_supported(h->net) && !h->point_kernels) {
+  if (use_taylor16d(h)) {
     HIPCHK(vn_taylor16d_launch(h->net, h->theta64, X, nullptr, nullptr, nullptr, nullptr, h->cfg.time_dependent, n, u, nullptr, h->ncu, h->stream));
     return VN_OK;
   }
@@ -1177,22 +1179,12 @@ int vn_residual(vn_engine* h, const float* X, const float* diff, const float* ve
   if (!h || (n > 0 && (!X || !diff || !vel || !res))) return fail(VN_EINVAL, "null argument");
   if (h->cfg.dim > 3) return fail(VN_EUNSUPPORTED, "residual supports dim <= 3");
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (h->layered) {
+  if (h->route == Route::layered) {
     LAYCHK(vn_layered_residual_f32(h->layered, h->theta, X, diff, vel, src, ddx, h->cfg.time_dependent, n, u, res, h->stream,
                                    lerr_, sizeof lerr_));
     return VN_OK;
   }
-  // networks of the 8-wave family: second-order forward mode on the matrix pipe (vn_taylor16.hip); the per-point kernel keeps
-  // the generic / 4-wave requests (and is what the new kernel is cross-checked against)
-  if ((h->use_fused16 || h->two_pass) && vn_taylor16_supported(h->net, h->cfg.time_dependent) && !h->point_kernels) {
-    if (!h->no_split && vn_split16_supported(h->net))
-      HIPCHK(vn_split16_residual(h->net, h->theta, X, diff, vel, src, ddx, h->cfg.time_dependent, n, u, res, h->ncu, h->stream));
-    else
-      HIPCHK(vn_taylor16_residual(h->net, h->theta, X, diff, vel, src, ddx, h->cfg.time_dependent, n, u, res, h->ncu, h->stream));
-    return VN_OK;
-  }
-  HIPCHK(vn_pointwise_residual_f32(h->net, h->theta, X, diff, vel, src, ddx, h->cfg.time_dependent, n, u, res,
-                                   h->stream));
+  HIPCHK(residual_f32(h, X, diff, vel, src, ddx, n, u, res));
   return VN_OK;
 }
 
@@ -1202,12 +1194,12 @@ int vn_residual_f64(vn_engine* h, const double* X, const double* diff, const dou
   if (h->cfg.dim > 3) return fail(VN_EUNSUPPORTED, "residual supports dim <= 3");
   HIPCHK(hipSetDevice(h->cfg.device));
   if (int rc = refresh_theta64(h)) return rc;
-  if (h->layered) {
+  if (h->route == Route::layered) {
     LAYCHK(vn_layered_residual_f64(h->layered, h->theta64, X, diff, vel, src, ddx, h->cfg.time_dependent, n, u, res, h->stream,
                                    lerr_, sizeof lerr_));
     return VN_OK;
   }
-  if ((h->use_fused16 || h->two_pass) && vn_taylor16d_supported(h->net) && !h->point_kernels) {
+  if (use_taylor16d(h)) {
     HIPCHK(vn_taylor16d_launch(h->net, h->theta64, X, diff, vel, src, ddx, h->cfg.time_dependent, n, u, res, h->ncu, h->stream));
     return VN_OK;
   }
@@ -1331,8 +1323,14 @@ int vn_profile_comm(vn_engine* h, double* mean_ms, int64_t* calls) {
 
 int vn_kernel_path(const vn_engine* h, int32_t* kernel, int32_t* two_pass) {
   if (!h || !kernel) return fail(VN_EINVAL, "null argument");
-  *kernel = h->layered ? VN_KERNEL_LAYERED : h->use_fused16 ? VN_KERNEL_FUSED16 : h->use_fused ? VN_KERNEL_FUSED : h->two_pass ? VN_KERNEL_FUSED16 : VN_KERNEL_GENERIC;
-  if (two_pass) *two_pass = h->two_pass ? 1 : 0;
+  switch (h->route) {
+    case Route::layered: *kernel = VN_KERNEL_LAYERED; break;
+    case Route::generic: *kernel = VN_KERNEL_GENERIC; break;
+    case Route::fused4: *kernel = VN_KERNEL_FUSED; break;
+    case Route::fused8:
+    case Route::twopass: *kernel = VN_KERNEL_FUSED16; break;
+  }
+  if (two_pass) *two_pass = h->route == Route::twopass ? 1 : 0;
   return VN_OK;
 }
 
@@ -1360,8 +1358,7 @@ int vn_debug_point_route(vn_engine* h, int32_t per_thread) {
   if (per_thread == 2 && !kWithF32Point)
     return fail(VN_EUNSUPPORTED, "route 2 (f32-MFMA point kernels for the networks the bf16-piece kernels serve) exists in the tests' "
                                  "cross-check build only: libvarnet_hip_xcheck.so (make -C varnet_amd/csrc xcheck)");
-  h->point_kernels = per_thread == 1;
-  h->no_split = per_thread == 2;
+  h->point_route = per_thread == 1 ? PointRoute::per_thread : per_thread == 2 ? PointRoute::f32_mfma : PointRoute::automatic;
   return VN_OK;
 }
 
