@@ -151,6 +151,7 @@ struct vn_engine {
   VnLayered* layered = nullptr;      // Route::layered
   float* tp_losspart = nullptr; long tp_losspart_cap = 0;
   float* fused_losspart = nullptr;   // [ncu*3]
+  float* f16_stash = nullptr; long f16_stash_cap = 0;   // 8-wave kernel's weight-gradient stash (vn_fused16_stash_bytes per workgroup)
   unsigned long long* stamps = nullptr;   // 8 counters, diagnostic builds
   // de-duplicated formulation work buffers
   float *dd_uv = nullptr, *dd_su = nullptr, *dd_sg = nullptr, *dd_partial = nullptr, *dd_losspart = nullptr;
@@ -413,6 +414,17 @@ VnDedupArgs dedup_args(const vn_engine* h, const Batch& b) {
   return a;
 }
 
+// Every launch of the 8-wave fused kernel: its global-memory stash (per workgroup; none for most instantiations) is sized here
+int fused8_launch(vn_engine* h, VnFusedArgs& f, int grid) {
+  const long per = (long)(vn_fused16_stash_bytes(h->net) / sizeof(float));
+  if (per > 0) {
+    if (int rc = ensure(&h->f16_stash, &h->f16_stash_cap, per * grid)) return rc;
+    f.stash = h->f16_stash;
+  }
+  HIPCHK(vn_fused16_launch(f, grid, h->stream));
+  return VN_OK;
+}
+
 // Model value (and directional derivative along G, if given) at n rows with the 8-wave fused kernel in its
 // forward-only mode: 2 F_pt per row at the fused kernel's efficiency instead of the generic forward kernel.
 int fused_forward(vn_engine* h, const float* X, const float* G, long n, float* out_u, float* out_ud) {
@@ -424,7 +436,7 @@ int fused_forward(vn_engine* h, const float* X, const float* G, long n, float* o
   if (!f.losspart || !f.partial) return fail(VN_ESTATE, "fused forward without its work buffers");   // the kernel stores to both
   const long tiles = (n + 127) / 128;
   const int grid = (int)(tiles < h->ncu ? tiles : h->ncu);
-  HIPCHK(vn_fused16_launch(f, grid, h->stream));
+  if (int rc = fused8_launch(h, f, grid)) return rc;
   return VN_OK;
 }
 
@@ -530,8 +542,11 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf) {
   const long tiles = (a.n_k + tt - 1) / tt + (a.nB + 127) / 128;
   const int grid = h->full_grid ? h->ncu : (int)(tiles < 1 ? 1 : tiles < h->ncu ? tiles : h->ncu);
   if (int rc = prof_start(h)) return rc;
-  if (h->route == Route::fused8) HIPCHK(vn_fused16_launch(a, grid, h->stream));
-  else HIPCHK(vn_fused_launch(a, grid, h->stream));
+  if (h->route == Route::fused8) {
+    if (int rc = fused8_launch(h, a, grid)) return rc;
+  } else {
+    HIPCHK(vn_fused_launch(a, grid, h->stream));
+  }
   if (int rc = prof_stop(h)) return rc;
   HIPCHK(vn_reduce_launch(h->partial, grid, h->net.P, h->fused_losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2,
                           gradbuf, h->stream, h->fuse));
@@ -554,7 +569,7 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf) {
   f.partial = h->partial; f.losspart = lp;
   f.dir = -1; f.ostride = 1;
   f.mode = 1; f.out_u = h->u; f.out_ud = h->ud;
-  HIPCHK(vn_fused16_launch(f, grid, h->stream));
+  if (int rc = fused8_launch(h, f, grid)) return rc;
 
   VnSeedArgs a = seed_args(h, b);
   a.ubar = h->ubar; a.udbar = h->udbar;
@@ -564,7 +579,7 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf) {
 
   f.mode = 2; f.out_u = nullptr; f.out_ud = nullptr; f.seed_u = h->ubar; f.seed_ud = h->udbar; f.nB = h->nB;
   if (int rc = prof_start(h)) return rc;
-  HIPCHK(vn_fused16_launch(f, grid, h->stream));
+  if (int rc = fused8_launch(h, f, grid)) return rc;
   if (int rc = prof_stop(h)) return rc;
   HIPCHK(vn_reduce_launch(h->partial, grid, P, lp, grid + sgrid, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream, h->fuse));
   return VN_OK;
@@ -595,7 +610,7 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf) {
   f.partial = h->dd_partial; f.losspart = lp;
   f.mode = 2; f.dir = -1; f.ostride = 1;
   f.seed_u = h->dd_su; f.seed_ud = nullptr;          // tangent seed 1
-  HIPCHK(vn_fused16_launch(f, grid, h->stream));
+  if (int rc = fused8_launch(h, f, grid)) return rc;
   if (int rc = prof_stop(h)) return rc;
   HIPCHK(vn_reduce_launch(h->dd_partial, grid, P, lp, grid + sblk, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream, h->fuse));
   return VN_OK;
@@ -755,7 +770,7 @@ int vn_destroy(vn_engine* h) {
   if (h->comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(h->stream); (void)g_rccl.CommDestroy(h->comm); h->comm = nullptr; }
   void* ptrs[] = {h->theta, h->m, h->v, h->snap, h->theta64, h->gradbuf_int, h->lossbuf, h->partial, h->feN, h->fedNt,
                   h->feW, h->u, h->ud, h->ubar, h->udbar, h->ub, h->ubar_b, h->losspart, h->fused_losspart, h->stamps, h->dd_uv, h->dd_su, h->dd_sg, h->dd_partial,
-                  h->dd_losspart, h->tp_losspart};
+                  h->dd_losspart, h->tp_losspart, h->f16_stash};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (Batch& b : h->batches)

@@ -19,7 +19,10 @@
 //   * Accumulators persist across tiles in registers, those of up to three hidden layers in an LDS stash
 //     (registers are short while the forward pass stores 2*KS*L activation values; scratch spills would go
 //     through L2 to HBM).  Fixed summation order everywhere: results are bitwise reproducible.
-// Register budget: 256 VGPRs per wave (stored activations 2*KS*L = 130 at 5x50; 18 spilled at 5x50).
+//   * Hidden widths 33..50 with 2..5 hidden layers (bf_sweeps): forward and input-gradient sweeps as bf16-piece
+//     products on the bf16 matrix pipe (vn_fused16_common.h); their images need the LDS of the stash, which then
+//     holds one layer in global memory.
+// Register budget: 256 VGPRs per wave (stored activations 2*KS*L = 130 at 5x50; 49 spilled at 5x50).
 #include "vn_internal.h"
 #include "vn_fused16_common.h"
 
@@ -60,13 +63,19 @@ static_assert(vfeat(63) == 63 && vfeat(31) == 31 && vpos(7, 3) == 31, "position 
 #define VN_MERGED_ROUNDS 1
 #endif
 __host__ __device__ constexpr bool merged_rounds(int L, int KS) { return VN_MERGED_ROUNDS && KS <= 8 && L >= 2; }   // one publish/contract round per hidden layer
+// Hidden-layer sweeps (forward value + tangent, input-gradient z-bar + z-bar-dot) as bf16-piece products (vn_fused16_common.h):
+// hidden widths 33..50 with 2..5 hidden layers.  The f32 MFMA shares its datapath with the f32 vector unit on gfx950, the bf16
+// MFMA does not.  Each hidden layer's 24 KB piece image replaces its f32 image; the weight-gradient stash moves to global memory
+// to make room.  Six 24 KB images (L = 7) do not fit next to the transposition region; 64-wide layers keep the f32 sweeps.
+__host__ __device__ constexpr bool bf_sweeps(int L, int KS) { return KS == 13 && L >= 2 && L <= 5; }
 
 template <int L, int KS>
 struct Lay {
   static constexpr int HP = 4 * KS;
-  static constexpr int HPWS = al4(HP * WS);
+  static constexpr bool BF = bf_sweeps(L, KS);
+  static constexpr int HPWS = BF ? IMG / 4 : al4(HP * WS);  // floats per hidden layer image
   static constexpr int W1_OFF = 0;                          // [8][WS]
-  static constexpr int WH_OFF = al4(8 * WS);                // [L-1][HP][WS]
+  static constexpr int WH_OFF = al4(8 * WS);                // [L-1][HP][WS] | [L-1] bf16-piece images (BF)
   static constexpr int BI_OFF = WH_OFF + (L - 1) * HPWS;    // [L][64] biases in (tile, g, i) order
   static constexpr int WO_OFF = BI_OFF + L * 64;            // [4*KS]
   static constexpr int MISC_OFF = WO_OFF + al4(4 * KS);     // sInt[128] (+128 spare)
@@ -100,8 +109,16 @@ struct Lay {
   static constexpr int ST_OFF = T_OFF + T_SZ;
   static constexpr int ST_LAYER = NW * 2 * 64 * 4;
   static constexpr int ST_FIT = (160 * 256 - ST_OFF) / ST_LAYER;
-  static constexpr int NST = ((KS != 13 && KS != 16) || L < 3) ? 0 : (ST_FIT < L - 1 ? ST_FIT : L - 1);
+  static constexpr int NST = (BF || (KS != 13 && KS != 16) || L < 3) ? 0 : (ST_FIT < L - 1 ? ST_FIT : L - 1);
   static constexpr int TOTAL = ST_OFF + NST * ST_LAYER;
+  // BF: the stash moves to a per-workgroup buffer in global memory ([layer][wave][slot][lane] f32x4, ST_LAYER floats per layer;
+  // every lane re-reads only what it wrote one tile earlier, L2-resident) and holds ONE layer (layer 2, the last of the reverse
+  // sweep); the others stay in registers.  Measured at 5 x 50 (DESIGN_LOG G.1): 4 layers in the stash 7.45 ms, 3: 7.24, 2: 7.18,
+  // 1: 7.12-7.17, 0: 7.32 -- each stashed layer's load sits behind a publish round and a barrier, and costs more than the
+  // 8 VGPRs of spill traffic it saves, until the last one.
+  static constexpr int NSTG = (!BF || L < 3) ? 0 : 1;
+  static constexpr int NSTK = BF ? NSTG : NST;             // stashed layers, wherever the stash lives
+  static_assert(!BF || TOTAL <= 160 * 256, "bf16-piece images must fit the LDS");
 };
 
 
@@ -600,6 +617,7 @@ struct VnFusedArgsD {
   float w0, w1, w2;
   float* partial;
   float* losspart;
+  float* stash;             // [grid][Lay::NSTG][ST_LAYER] weight-gradient stash (bf16-piece instantiations), else unused
   unsigned long long* stamps;
   // de-duplicated formulation (rows = unique quadrature points, no test-function grouping):
   int mode;                 // 0 fused step; 1 forward only -> out_u/out_ud; 2 reverse pass with external seeds
@@ -682,7 +700,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
     float v1 = 0.f, vh[L > 1 ? L - 1 : 1][NSRC];
     if (tid < d_in * H1) v1 = A.theta[net.woff[1] + tid];
 #pragma unroll
-    for (int l = 2; l <= L; ++l) {
+    for (int l = 2; l <= (LY::BF ? 1 : L); ++l) {
       const int n = net.H[l - 1] * net.H[l];
       const float* src = A.theta + net.woff[l];
 #pragma unroll
@@ -703,15 +721,16 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
     if (tid < 4 * KS) vo = (tid < net.H[L]) ? A.theta[net.woff[L + 1] + tid] : 0.f;
     static_assert(LY::BI_OFF % 4 == 0 && LY::T_OFF % 4 == 0 && LY::T_SZ % 4 == 0, "16-byte zero fill");
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    for (int i = tid; i < LY::BI_OFF / 4; i += NTHREADS) reinterpret_cast<f32x4a*>(lds)[i] = z4;                    // W1 | WH
+    for (int i = tid; i < (LY::BF ? LY::WH_OFF : LY::BI_OFF) / 4; i += NTHREADS) reinterpret_cast<f32x4a*>(lds)[i] = z4;   // W1 | WH
     for (int i = tid; i < LY::T_SZ / 4; i += NTHREADS) reinterpret_cast<f32x4a*>(lds + LY::T_OFF)[i] = z4;
     __syncthreads();
     if (tid < d_in * H1) {
       const int k = tid / H1, f = tid - k * H1;
       W1[k * WS + vpos(f >> 2, f & 3)] = v1;
     }
+    if constexpr (LY::BF) stage_split_hidden<L>(net, A.theta, reinterpret_cast<char*>(WH), tid);
 #pragma unroll
-    for (int l = 2; l <= L; ++l) {
+    for (int l = 2; l <= (LY::BF ? 1 : L); ++l) {
       float* Wl = WH + (l - 2) * LY::HPWS;
       const int Hout = net.H[l], n = net.H[l - 1] * Hout;
       const int dq = NTHREADS / Hout, dr = NTHREADS - dq * Hout;      // j -> j + NTHREADS: k += dq, f += dr (one carry)
@@ -742,8 +761,12 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
   using WHG = WG<KS, KS>;
   constexpr bool HID13 = (KS == 13);                 // 50-wide hidden layers: 3x3 core tiles + 4x4x1 borders
   constexpr int NHACC = HID13 ? 2 : WHG::TPW;
-  f32x4a* stash = reinterpret_cast<f32x4a*>(lds + LY::ST_OFF) + wave * 2 * 64 + lane;   // [layer][wave][slot][lane]
   constexpr int ST_L = LY::ST_LAYER / 4;
+  f32x4a* stash = (LY::BF ? reinterpret_cast<f32x4a*>(A.stash) + (long)blockIdx.x * LY::NSTG * ST_L
+                          : reinterpret_cast<f32x4a*>(lds + LY::ST_OFF)) + wave * 2 * 64 + lane;   // [layer][wave][slot][lane]
+  // bf16-piece sweeps: lane bases of the row (forward) and transposed (sweep back) fragment reads
+  const char* wrd = reinterpret_cast<const char*>(WH) + split_row_base(lc.g, lc.c);
+  const char* wtr = reinterpret_cast<const char*>(WH) + split_tr_base(lc.g, lc.c);
   f32x4 wacc1[W1G::TPW], wacch[L > 1 ? L - 1 : 1][NHACC];
   float woacc = 0.f, boacc = 0.f;                    // output layer: lane (g, c) holds d w_o[4c + g]; d b_o in every lane
 #pragma unroll
@@ -753,7 +776,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
 #pragma unroll
     for (int t = 0; t < NHACC; ++t) {
       wacch[l][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (l < LY::NST) stash[l * ST_L + t * 64] = wacch[l][t];
+      if (l < LY::NSTK) stash[l * ST_L + t * 64] = wacch[l][t];
     }
 
   const bool thin_in = net.d_in <= 3;                // input-layer weight gradient without workgroup barriers
@@ -823,6 +846,53 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
     layer1_raw(xin, gin, pv, ptn);
 #pragma unroll
     for (int l = 2; l <= L; ++l) {
+      if constexpr (LY::BF) {
+        // bf16 pieces: all four row tiles on the matrix pipe (features 48, 49 land in row 48 + 4g as in the edge path), value
+        // and tangent share each weight fragment; the activation and the split are scalar f32 forms (no v_pk_* beside bf16 MFMAs)
+        const char* rl = wrd + (l - 2) * IMG;
+        f32x4 nv[MT], nt[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+          nv[m] = *reinterpret_cast<const f32x4a*>(&BI[(l - 1) * 64 + m * 16 + lc.g * 4]);
+          nt[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int qf = 0; qf < 2; ++qf) {             // K fragment: k-steps 8qf..8qf+7, cut per fragment (registers)
+          u32x4 Bv[3], Bt[3];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {              // pair e = k-steps 8qf+2e, 8qf+2e+1 (13..15: padding, zero weights)
+            const int k0 = 8 * qf + 2 * e;
+            if (k0 >= KS) {
+#pragma unroll
+              for (int p = 0; p < 3; ++p) { Bv[p][e] = 0u; Bt[p][e] = 0u; }
+              continue;
+            }
+            const int t = k0 >> 2, i = k0 & 3;
+            const bool full = k0 + 1 < KS;
+            const float a0 = act_fin<TANH>(act_exp<TANH>(pv[t][i]));
+            const float a1 = full ? act_fin<TANH>(act_exp<TANH>(pv[t][i + 1])) : 0.f;
+            const float z0 = ptn[t][i], z1 = full ? ptn[t][i + 1] : 0.f;
+            a[l - 2].p[k0 >> 1] = f32x2{a0, a1};
+            zd[l - 2].p[k0 >> 1] = f32x2{z0, z1};
+            u32 h, md, lo;
+            split2(a0, a1, h, md, lo);
+            Bv[0][e] = h; Bv[1][e] = md; Bv[2][e] = lo;
+            split2(act_d1<TANH>(a0) * z0, act_d1<TANH>(a1) * z1, h, md, lo);
+            Bt[0][e] = h; Bt[1][e] = md; Bt[2][e] = lo;
+          }
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            u32x4 Af[3];
+            split_frag_row(rl, qf, mt, Af);
+            const u32x4 (*const Bs[2])[3] = {&Bv, &Bt};
+            f32x4* const as[2] = {&nv[mt], &nt[mt]};
+            six<2>(Af, Bs, as);
+          }
+        }
+#pragma unroll
+        for (int m = 0; m < MT; ++m) { pv[m] = nv[m]; ptn[m] = nt[m]; }
+        continue;
+      }
       const float* Wl = WH + (l - 2) * LY::HPWS;
       int k_in = (net.H[l - 1] + 3) >> 2, m_out = (net.H[l] + 15) >> 4;      // KSKIP: live k-steps / row tiles of this layer (scalar)
       f32x4 nv[MT], nt[MT];
@@ -1063,7 +1133,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
         }
       }
       if constexpr (HID13) {
-        if (l - 2 < LY::NST) {
+        if (l - 2 < LY::NSTK) {
           f32x4 acc2[2] = {stash[(l - 2) * ST_L], stash[(l - 2) * ST_L + 64]};
           h13_wgrad_layer<TANH>(a[l - 2], zd[l - 2], zb, zdb, TA, lc, wave, lane, t_base_bytes, acc2);
           stash[(l - 2) * ST_L] = acc2[0];
@@ -1073,7 +1143,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
         }
       }
       else if constexpr (NHACC == 2) {
-        if (l - 2 < LY::NST) {               // accumulators of this layer live in the LDS stash between tiles
+        if (l - 2 < LY::NSTK) {               // accumulators of this layer live in the LDS stash between tiles
           f32x4 acc2[2] = {stash[(l - 2) * ST_L], stash[(l - 2) * ST_L + 64]};
           wgrad_layer<KS, KS, false, TANH, LY::MERGE>(a[l - 2], zd[l - 2], zb, zdb, TA, TB, lc, wave, acc2, ones_h[l - 2]);
           stash[(l - 2) * ST_L] = acc2[0];
@@ -1086,11 +1156,43 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       if constexpr (fullpos(KS)) {
         if (!ones_h[l - 2]) thin_bias<KS>(zb, TA, TB, lc, wave, lane, bsum_h[l - 2]);
       }
-      const float* Wl = WH + (l - 2) * LY::HPWS;
-      int k_out = (net.H[l] + 3) >> 2, m_in = (net.H[l - 1] + 15) >> 4;
       f32x4 accv[MT], acct[MT];
 #pragma unroll
       for (int m = 0; m < MT; ++m) { accv[m] = f32x4{0.f, 0.f, 0.f, 0.f}; acct[m] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+      if constexpr (LY::BF) {
+        // bf16 pieces through the transposed reads of the same images: K fragment over the OUT-features 4(8qf+j)+g of layer l,
+        // row tile over the IN-positions 16 mt + c (all four on the matrix pipe)
+        const char* tl = wtr + (l - 2) * IMG;
+#pragma unroll
+        for (int qf = 0; qf < 2; ++qf) {
+          u32x4 Bz[3], Bzd[3];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int k0 = 8 * qf + 2 * e;
+            if (k0 >= KS) {
+#pragma unroll
+              for (int p = 0; p < 3; ++p) { Bz[p][e] = 0u; Bzd[p][e] = 0u; }
+              continue;
+            }
+            const bool full = k0 + 1 < KS;
+            u32 h, md, lo;
+            split2(zb[k0], full ? zb[k0 + 1] : 0.f, h, md, lo);
+            Bz[0][e] = h; Bz[1][e] = md; Bz[2][e] = lo;
+            split2(zdb[k0], full ? zdb[k0 + 1] : 0.f, h, md, lo);
+            Bzd[0][e] = h; Bzd[1][e] = md; Bzd[2][e] = lo;
+          }
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            u32x4 At[3];
+            split_frag_tr(tl, qf, mt, At);
+            const u32x4 (*const Bs[2])[3] = {&Bz, &Bzd};
+            f32x4* const as[2] = {&accv[mt], &acct[mt]};
+            six<2>(At, Bs, as);
+          }
+        }
+      } else {
+      const float* Wl = WH + (l - 2) * LY::HPWS;
+      int k_out = (net.H[l] + 3) >> 2, m_in = (net.H[l - 1] + 15) >> 4;
       float wf[MTM], we[NVE], ev[NVE], et[NVE];
 #pragma unroll
       for (int m = 0; m < MTM; ++m) wf[m] = Wl[lc.offB0 + 16 * m * WS + vpos(0, 0)];
@@ -1130,6 +1232,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       if (EDGE) {
         accv[MT - 1][0] = edge_reduce_scatter<NVE>(ev, lc.g);
         acct[MT - 1][0] = edge_reduce_scatter<NVE>(et, lc.g);
+      }
       }
       // zbar of layer l-1, two k-steps per packed instruction (accumulator rows ks, ks+1 are a register pair)
 #pragma unroll
@@ -1176,7 +1279,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
 #pragma unroll
       for (int l = 2; l <= L; ++l) {
         f32x4 acc2[2];
-        if (l - 2 < LY::NST) { acc2[0] = stash[(l - 2) * ST_L]; acc2[1] = stash[(l - 2) * ST_L + 64]; }
+        if (l - 2 < LY::NSTK) { acc2[0] = stash[(l - 2) * ST_L]; acc2[1] = stash[(l - 2) * ST_L + 64]; }
         else { acc2[0] = wacch[l - 2][0]; acc2[1] = wacch[l - 2][1]; }
         h13_flush<LY::HP>(acc2, Gacc + LY::G1_SZ + (l - 2) * LY::GH_SZ, lc, wave, lane, slot_lo, slot_hi);
       }
@@ -1219,7 +1322,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
 #pragma unroll
         for (int l = 2; l <= L; ++l) {
           if constexpr (NHACC == 2) {
-            if (l - 2 < LY::NST) {
+            if (l - 2 < LY::NSTK) {
               const f32x4 acc2[2] = {stash[(l - 2) * ST_L], stash[(l - 2) * ST_L + 64]};
               wgrad_flush<KS, KS, LY::HP>(acc2, Gacc + LY::G1_SZ + (l - 2) * LY::GH_SZ, lc, wave, ones_h[l - 2]);
               continue;
@@ -1310,6 +1413,11 @@ size_t lds_one() {
   return (size_t)Lay<L, KS>::TOTAL * sizeof(float);
 }
 
+template <int L, int KS>
+size_t stash_one() {
+  return (size_t)Lay<L, KS>::NSTG * Lay<L, KS>::ST_LAYER * sizeof(float);
+}
+
 int pick_ks(int hmax) {
   if (hmax <= 20) return 5;
   if (hmax <= 32) return 8;
@@ -1337,6 +1445,14 @@ size_t vn_fused16_lds_bytes(const VnNet& net) {
   return 0;
 }
 
+size_t vn_fused16_stash_bytes(const VnNet& net) {
+  const int ks = pick_ks(net.hmax);
+#define X(LL, KK) if (net.L == LL && ks == KK) return stash_one<LL, KK>();
+  VN_FUSED16_CASES(X)
+#undef X
+  return 0;
+}
+
 bool vn_fused16_net_supported(const VnNet& net) {
   if (net.d_in > 4 * KS0) return false;
   const size_t b = vn_fused16_lds_bytes(net);
@@ -1354,10 +1470,11 @@ hipError_t vn_fused16_launch(const VnFusedArgs& h, int grid, hipStream_t s) {
   a.integ_num = h.integ_num; a.feN = h.feN; a.fedNt = h.fedNt; a.feW = h.feW; a.Nrow = h.Nrow; a.dNtrow = h.dNtrow; a.detJv = h.detJv;
   a.detJ = h.detJ; a.time_dependent = h.time_dependent; a.lossVec = h.lossVec; a.Xb = h.Xb;
   a.label = h.label; a.nB = h.nB; a.bDof = h.bDof; a.biDimVal = h.biDimVal; a.w0 = h.w0; a.w1 = h.w1;
-  a.w2 = h.w2; a.partial = h.partial; a.losspart = h.losspart; a.stamps = h.stamps;
+  a.w2 = h.w2; a.partial = h.partial; a.losspart = h.losspart; a.stash = h.stash; a.stamps = h.stamps;
   a.mode = h.mode; a.dir = h.mode ? h.dir : -1; a.ostride = h.ostride; a.out_u = h.out_u; a.out_ud = h.out_ud;
   a.seed_u = h.seed_u; a.seed_ud = h.seed_ud;
   const int ks = pick_ks(h.net.hmax);
+  if (!h.stash && vn_fused16_stash_bytes(h.net) > 0) return hipErrorInvalidValue;
 #define X(LL, KK)                                                                              \
   if (h.net.L == LL && ks == KK)                                                                \
     return h.net.act == VN_ACT_TANH ? launch_one<LL, KK, true>(a, grid, s) : launch_one<LL, KK, false>(a, grid, s);

@@ -1,6 +1,7 @@
 // Device helpers shared by the 8-wave kernels of the fused family (vn_fused16.hip: the training step;
-// vn_pgrad16.hip: value + input gradient at points): the feature <-> (k-step, lane group, accumulator row) layout,
-// activation arithmetic on register pairs, cross-lane sums.
+// vn_pgrad16.hip: value + input gradient at points; vn_split16.hip: point kernels on the bf16 pipe): the feature <->
+// (k-step, lane group, accumulator row) layout, activation arithmetic on register pairs, cross-lane sums, and the
+// bf16-piece machinery of the hidden-layer products (exact three-way split, 1 KB-block weight images, fragment reads).
 #pragma once
 #include "vn_internal.h"
 
@@ -147,6 +148,113 @@ __device__ __forceinline__ float edge_reduce_scatter(const float (&e)[NV], int g
     // step 2 (partner g^2): keep feature g
     const bool hi = (g & 2) != 0;
     return (hi ? b : a) + __shfl_xor(hi ? a : b, 32, 64);
+  }
+}
+
+// ---- bf16-piece hidden-layer products (hidden widths 33..64: two K fragments of 32) ----------------------------------
+// Every f32 operand is cut EXACTLY into three bf16 pieces x = h + m + l (3 x 8 significand bits, truncation), and a layer
+// product is the six terms hh, hm, mh, hl, lh, mm with f32 accumulation, small terms first; the dropped terms (ml, lm, ll)
+// are <= 3 * 2^-24 relative (profiles/r2_micro_split_bf16.md).
+// Weight image of a hidden layer: 24 blocks [piece 3][q 2][row tile 4] of 1 KB = [g 4][c ^ 12(g&1)][8 bf16]: lane (g, c)
+// reads the 8 in-features 4(8q+j)+g, j = 0..7, of out-position 16 mt + c with ONE conflict-free ds_read_b128.
+typedef short bf16x8 __attribute__((ext_vector_type(8)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32;
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 u32x4a __attribute__((may_alias));
+
+constexpr int BLK = 1024;                                  // bytes of one (piece, q, row tile) block
+constexpr int IMG = 24 * BLK;                              // bytes of one hidden layer's image
+
+__device__ __forceinline__ u32 fu(float x) { return __builtin_bit_cast(u32, x); }
+__device__ __forceinline__ float uf(u32 x) { return __builtin_bit_cast(float, x); }
+__device__ __forceinline__ u32 pack_hi(u32 u1, u32 u0) { return __builtin_amdgcn_perm(u1, u0, 0x07060302u); }   // (hi16(u1) << 16) | hi16(u0)
+
+// exact three-way split of two f32 values into packed bf16 pairs (truncation: h = the top 8 significand bits, m the next 8 of
+// the remainder, l the next 8).  Scalar subtracts: packed f32 instructions are expensive beside bf16 MFMAs (the study's raw table).
+__device__ __forceinline__ void split2(float x0, float x1, u32& h, u32& m, u32& l) {
+  const u32 u0 = fu(x0), u1 = fu(x1);
+  h = pack_hi(u1, u0);
+  const float r0 = x0 - uf(u0 & 0xffff0000u), r1 = x1 - uf(u1 & 0xffff0000u);
+  const u32 v0 = fu(r0), v1 = fu(r1);
+  m = pack_hi(v1, v0);
+  const float s0 = r0 - uf(v0 & 0xffff0000u), s1 = r1 - uf(v1 & 0xffff0000u);
+  l = pack_hi(fu(s1), fu(s0));
+}
+
+__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// the six products of one (row tile, K fragment), small terms first; the streams that share the weight fragment are interleaved
+// product by product (independent accumulators: no MFMA waits for its predecessor's result)
+template <int N>
+__device__ __forceinline__ void six(const u32x4 (&A)[3], const u32x4 (*const (&B)[N])[3], f32x4* const (&acc)[N]) {
+  constexpr int pa[6] = {1, 2, 0, 1, 0, 0}, pb[6] = {1, 0, 2, 0, 1, 0};
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+#pragma unroll
+    for (int s = 0; s < N; ++s) *acc[s] = mfma_bf16(A[pa[i]], (*B[s])[pb[i]], *acc[s]);
+  }
+}
+
+// The bf16-piece images of hidden layers 2..L at img (L - 1 consecutive IMG-byte images): one 16-byte entry (8 in-features of
+// one out-position) per thread and layer, cut into its three pieces here; padding exact zeros.  Ends with the images written
+// but not yet visible to other waves: the caller synchronises.
+template <int L>
+__device__ __forceinline__ void stage_split_hidden(const VnNet& net, const float* theta, char* img, int tid) {
+  static_assert(NTHREADS == 2 * 4 * 4 * 16, "one entry per thread and layer");
+  const int q = tid >> 8, mt = (tid >> 6) & 3, g = (tid >> 4) & 3, c = tid & 15;
+  const int pos = 16 * mt + c, fo = vfeat(pos);
+  const int ent = (g * 16 + (c ^ (12 * (g & 1)))) * 16;
+#pragma unroll
+  for (int l = 2; l <= L; ++l) {
+    const int Hin = net.H[l - 1], Hout = net.H[l];
+    const float* src = theta + net.woff[l];
+    float w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int fi = 4 * (8 * q + j) + g;
+      w[j] = (fi < Hin && fo < Hout) ? src[fi * Hout + fo] : 0.f;
+    }
+    u32x4 ph, pm, pl;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      u32 h, m, lo;
+      split2(w[2 * jj], w[2 * jj + 1], h, m, lo);
+      ph[jj] = h; pm[jj] = m; pl[jj] = lo;
+    }
+    char* il = img + (l - 2) * IMG;
+    *reinterpret_cast<u32x4a*>(il + ((0 * 2 + q) * 4 + mt) * BLK + ent) = ph;
+    *reinterpret_cast<u32x4a*>(il + ((1 * 2 + q) * 4 + mt) * BLK + ent) = pm;
+    *reinterpret_cast<u32x4a*>(il + ((2 * 2 + q) * 4 + mt) * BLK + ent) = pl;
+  }
+}
+
+// Lane bases into the images.  Row read (forward: contraction over a layer's IN-features): lane (g, c) reads its entry of a
+// block.  Transposed read (sweep back: contraction over the OUT-features 4(8q+j)+g, row tile over the IN-positions 16 mt + c):
+// lane 4r + p of its group supplies row r (c_out = 4g + r), columns 4p..4p+3 (entry g_in = p) of a ds_read_b64_tr_b16.
+__device__ __forceinline__ int split_row_base(int g, int c) { return (g * 16 + (c ^ (12 * (g & 1)))) * 16; }
+__device__ __forceinline__ int split_tr_base(int g, int c) {
+  const int tr_r = c >> 2, tr_p = c & 3;
+  return (tr_p * 16 + ((4 * g + tr_r) ^ (12 * (tr_p & 1)))) * 16;
+}
+// A fragment (three pieces) of row tile mt, K fragment q, from a layer's image at rl = image + split_row_base
+__device__ __forceinline__ void split_frag_row(const char* rl, int q, int mt, u32x4 (&Af)[3]) {
+#pragma unroll
+  for (int p = 0; p < 3; ++p) Af[p] = *reinterpret_cast<const u32x4a*>(rl + ((p * 2 + q) * 4 + mt) * BLK);
+}
+// Transposed A fragment of in-position row tile mt, out-feature K fragment q, from tl = image + split_tr_base: in the forward
+// image those are element 4(mt&1) + (c&3) of the entries (g_in = (c>>2)&3, c_out = 4g + (j&3)) of blocks (q_in = mt>>1,
+// mt_out = 2q + (j>>2)): two transposed reads per piece (EXEC must be all ones).
+__device__ __forceinline__ void split_frag_tr(const char* tl, int q, int mt, u32x4 (&At)[3]) {
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+    const char* b0 = tl + ((p * 2 + (mt >> 1)) * 4 + 2 * q) * BLK + 8 * (mt & 1);
+    const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b0));
+    const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b0 + BLK));
+    const unsigned long long l64 = __builtin_bit_cast(unsigned long long, lo4), h64 = __builtin_bit_cast(unsigned long long, hi4);
+    At[p] = u32x4{(u32)l64, (u32)(l64 >> 32), (u32)h64, (u32)(h64 >> 32)};
   }
 }
 

@@ -89,6 +89,7 @@ struct VnFusedArgs {
   float w0, w1, w2;
   float* partial;    // [grid, P] per-workgroup gradient partials
   float* losspart;   // [grid, 3] per-workgroup (var, bc, ic) partial sums
+  float* stash;      // 8-wave kernel: [grid, vn_fused16_stash_bytes / 4] weight-gradient stash, or nullptr where that is 0
   unsigned long long* stamps;   // diagnostic builds (-DVN_STAMPS) only: 8 phase cycle sums, else nullptr
   // de-duplicated formulation (8-wave kernel only; rows X = unique quadrature points):
   int mode;                     // 0 fused step | 1 forward only | 2 reverse pass with external seeds
@@ -105,6 +106,7 @@ bool vn_fused16_supported(const VnNet& net, int integ_num);
 bool vn_fused16_net_supported(const VnNet& net);   // network instantiated (any integ_num: two-pass route)
 size_t vn_fused16_lds_bytes(const VnNet& net);
 int vn_fused16_ks(const VnNet& net);               // k-steps per hidden layer of the instantiation that serves `net` (0: none)
+size_t vn_fused16_stash_bytes(const VnNet& net);   // global-memory stash per workgroup of that instantiation (0: none)
 hipError_t vn_fused16_launch(const VnFusedArgs& a, int grid, hipStream_t s);
 
 // ---- measurement aid (vn_calib.hip): sustained fp32 MFMA rate and fp32 vector issue cost of this GPU; out[5], see there

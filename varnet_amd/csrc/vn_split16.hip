@@ -25,14 +25,6 @@
 namespace {
 using namespace vn16;
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32;
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 u32x4a __attribute__((may_alias));
-
-constexpr int BLK = 1024;                                  // bytes of one (piece, q, row tile) block
-constexpr int IMG = 24 * BLK;                              // bytes of one hidden layer's image
-
 template <int L>
 struct SLay {                                              // byte offsets
   static constexpr int WH_OFF = 0;                         // [L-1] images
@@ -56,72 +48,15 @@ struct VnSplitArgsD {
   float* res;                // [n] (residual)
 };
 
-__device__ __forceinline__ u32 fu(float x) { return __builtin_bit_cast(u32, x); }
-__device__ __forceinline__ float uf(u32 x) { return __builtin_bit_cast(float, x); }
-__device__ __forceinline__ u32 pack_hi(u32 u1, u32 u0) { return __builtin_amdgcn_perm(u1, u0, 0x07060302u); }   // (hi16(u1) << 16) | hi16(u0)
-
-// exact three-way split of two f32 values into packed bf16 pairs (truncation: h = the top 8 significand bits, m the next 8 of
-// the remainder, l the next 8).  Scalar subtracts: packed f32 instructions are expensive beside bf16 MFMAs (the study's raw table).
-__device__ __forceinline__ void split2(float x0, float x1, u32& h, u32& m, u32& l) {
-  const u32 u0 = fu(x0), u1 = fu(x1);
-  h = pack_hi(u1, u0);
-  const float r0 = x0 - uf(u0 & 0xffff0000u), r1 = x1 - uf(u1 & 0xffff0000u);
-  const u32 v0 = fu(r0), v1 = fu(r1);
-  m = pack_hi(v1, v0);
-  const float s0 = r0 - uf(v0 & 0xffff0000u), s1 = r1 - uf(v1 & 0xffff0000u);
-  l = pack_hi(fu(s1), fu(s0));
-}
-
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// the six products of one (row tile, K fragment), small terms first; the streams that share the weight fragment are interleaved
-// product by product (independent accumulators: no MFMA waits for its predecessor's result)
-template <int N>
-__device__ __forceinline__ void six(const u32x4 (&A)[3], const u32x4 (*const (&B)[N])[3], f32x4* const (&acc)[N]) {
-  constexpr int pa[6] = {1, 2, 0, 1, 0, 0}, pb[6] = {1, 0, 2, 0, 1, 0};
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-#pragma unroll
-    for (int s = 0; s < N; ++s) *acc[s] = mfma_bf16(A[pa[i]], (*B[s])[pb[i]], *acc[s]);
-  }
-}
-
-// Prologue of both kernels: the bf16-piece images of the hidden layers -- one 16-byte entry (8 in-features of one out-position)
-// per thread and layer, cut into its three pieces here -- and the f32 input-layer image, biases and output weights; padding exact
-// zeros.  Ends with the images written but not yet visible to other waves: the caller synchronises.
+// Prologue of both kernels: the bf16-piece images of the hidden layers (stage_split_hidden, vn_fused16_common.h) and the f32
+// input-layer image, biases and output weights; padding exact zeros.  Ends with the images written but not yet visible to other waves: the caller synchronises.
 template <int L>
 __device__ __forceinline__ void stage_split_images(const VnNet& net, const float* theta, char* ldsb, int tid) {
   using LY = SLay<L>;
   float* W1 = reinterpret_cast<float*>(ldsb + LY::W1_OFF);
   float* BI = reinterpret_cast<float*>(ldsb + LY::BI_OFF);
   float* WO = reinterpret_cast<float*>(ldsb + LY::WO_OFF);
-  const int q = tid >> 8, mt = (tid >> 6) & 3, g = (tid >> 4) & 3, c = tid & 15;
-  const int pos = 16 * mt + c, fo = vfeat(pos);
-  const int ent = (g * 16 + (c ^ (12 * (g & 1)))) * 16;
-#pragma unroll
-  for (int l = 2; l <= L; ++l) {
-    const int Hin = net.H[l - 1], Hout = net.H[l];
-    const float* src = theta + net.woff[l];
-    float w[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int fi = 4 * (8 * q + j) + g;
-      w[j] = (fi < Hin && fo < Hout) ? src[fi * Hout + fo] : 0.f;
-    }
-    u32x4 ph, pm, pl;
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      u32 h, m, lo;
-      split2(w[2 * jj], w[2 * jj + 1], h, m, lo);
-      ph[jj] = h; pm[jj] = m; pl[jj] = lo;
-    }
-    char* img = ldsb + LY::WH_OFF + (l - 2) * IMG;
-    *reinterpret_cast<u32x4a*>(img + ((0 * 2 + q) * 4 + mt) * BLK + ent) = ph;
-    *reinterpret_cast<u32x4a*>(img + ((1 * 2 + q) * 4 + mt) * BLK + ent) = pm;
-    *reinterpret_cast<u32x4a*>(img + ((2 * 2 + q) * 4 + mt) * BLK + ent) = pl;
-  }
+  stage_split_hidden<L>(net, theta, ldsb + LY::WH_OFF, tid);
   for (int i = tid; i < al4(8 * WS); i += NTHREADS) W1[i] = 0.f;
   __syncthreads();
   const int H1 = net.H[1];
@@ -159,7 +94,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void vn_split16_kernel(VnSplitArgsD A)
 
   const int g = lane >> 4, c = lane & 15;
   const int offF = g * WS + c;                       // input layer A fragment: in-feature 4s+g, out-position 16m+c
-  const char* rd = ldsb + LY::WH_OFF + (g * 16 + (c ^ (12 * (g & 1)))) * 16;
+  const char* rd = ldsb + LY::WH_OFF + split_row_base(g, c);
   const int dim = net.dim, nd1 = (NS == 1) ? 1 : dim;
   // Streams of a pass (NS = 3): value, first and second derivative along e_d -- and, in pass 0 of a time-dependent problem, the
   // first derivative along t as a FOURTH stream (it needs no second derivative; a pass of its own would recompute the value
@@ -254,8 +189,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void vn_split16_kernel(VnSplitArgsD A)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
             u32x4 Af[3];
-#pragma unroll
-            for (int p = 0; p < 3; ++p) Af[p] = *reinterpret_cast<const u32x4a*>(rl + ((p * 2 + q) * 4 + mt) * BLK);
+            split_frag_row(rl, q, mt, Af);
             if (NS == 1) {
               const u32x4 (*const Bs[1])[3] = {&Bv};
               f32x4* const as[1] = {&nv[mt]};
@@ -334,8 +268,6 @@ struct VnSplitPgArgsD {
   float* out_pack;           // [n, 4] = (u, du/dx_0, du/dx_1, du/dx_2) or nullptr
 };
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 template <int L, int KS, bool TANH>
 __global__ __launch_bounds__(NTHREADS, 1) void vn_split16_pgrad_kernel(VnSplitPgArgsD A) {
   static_assert(KS == 13 || KS == 16, "two K fragments of 32: hidden widths 33..64");
@@ -353,10 +285,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void vn_split16_pgrad_kernel(VnSplitPg
 
   const int g = lane >> 4, c = lane & 15;
   const int offF = g * WS + c;
-  const char* rd = ldsb + LY::WH_OFF + (g * 16 + (c ^ (12 * (g & 1)))) * 16;                    // row read (forward)
-  // transposed read: lane 4r + p of its group supplies row r (c_out = 4g + r), columns 4p..4p+3 (entry g_in = p)
-  const int tr_r = c >> 2, tr_p = c & 3;
-  const char* rt = ldsb + LY::WH_OFF + (tr_p * 16 + ((4 * g + tr_r) ^ (12 * (tr_p & 1)))) * 16;
+  const char* rd = ldsb + LY::WH_OFF + split_row_base(g, c);                                    // row read (forward)
+  const char* rt = ldsb + LY::WH_OFF + split_tr_base(g, c);                                     // transposed read (sweep back)
 
   const long nchunks = (A.n + CW - 1) / CW;
   for (long chunk = (long)blockIdx.x * NW + wave; chunk < nchunks; chunk += (long)gridDim.x * NW) {
@@ -410,8 +340,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void vn_split16_pgrad_kernel(VnSplitPg
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
           u32x4 Af[3];
-#pragma unroll
-          for (int p = 0; p < 3; ++p) Af[p] = *reinterpret_cast<const u32x4a*>(rl + ((p * 2 + q) * 4 + mt) * BLK);
+          split_frag_row(rl, q, mt, Af);
           const u32x4 (*const Bs[1])[3] = {&Bv};
           f32x4* const as[1] = {&nv[mt]};
           six<1>(Af, Bs, as);
@@ -457,14 +386,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void vn_split16_pgrad_kernel(VnSplitPg
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {            // row tile over the IN-positions 16 mt + c
           u32x4 At[3];
-#pragma unroll
-          for (int p = 0; p < 3; ++p) {
-            const char* b0 = tl + ((p * 2 + (mt >> 1)) * 4 + 2 * q) * BLK + 8 * (mt & 1);
-            const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b0));
-            const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b0 + BLK));
-            const unsigned long long l64 = __builtin_bit_cast(unsigned long long, lo4), h64 = __builtin_bit_cast(unsigned long long, hi4);
-            At[p] = u32x4{(u32)l64, (u32)(l64 >> 32), (u32)h64, (u32)(h64 >> 32)};
-          }
+          split_frag_tr(tl, q, mt, At);
           const u32x4 (*const Bs[1])[3] = {&Bz};
           f32x4* const as[1] = {&acc[mt]};
           six<1>(At, Bs, as);
