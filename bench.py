@@ -2,7 +2,8 @@
 """
 bench.py -- training-points/sec of the VarNet variational-loss step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-dedup] [--no-extra]]
         (N > 1: starts its own N ranks, one per GPU, before anything touches the GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -17,6 +18,13 @@ training set.  With N > 1 ranks the SAME 100 000 test functions are sharded cont
 (strong scaling, BASELINE cfg 4) and the flat gradient is all-reduced over RCCL.
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and prints the result line:
+the headline, its roofline from the HIP events of the timed steps and the committed counter files, and (N > 1) the
+communication figures.  --full adds, at N = 1, what takes runs of its own: the calibration launches, the 2-s sustained
+window, the fp32 / fp64 inference kernels and, for --config 3, the small-step workloads of configs 1, 2 and 5 (--no-extra
+skips these); the de-duplicated formulation (--no-dedup); the CPU oracle on a sample and at full size (--no-cpu-baseline).
+Without --full the three --no-* options change nothing.
 
 --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed, as a caller of the step receives
 it, to DIR/<name>.npy (float32; see OUTPUT_NAMES).  The inputs are fixed by the arguments, so two builds run with the same
@@ -668,19 +676,31 @@ def main():
         sys.exit(1)
 
 
-def _main():
+def parse_args(argv=None):
+    """The options, plus which legs beyond the headline this run takes (`cpu_baseline`, `dedup`, `extra`): none without --full."""
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', type=int, default=3)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-dedup', action='store_true', help='skip the extra de-duplicated-formulation timing')
-    ap.add_argument('--no-extra', action='store_true', help='skip the calibration launches, the 2-s sustained window and the extra small-step workloads (configs 1, 2, 5)')
+    ap.add_argument('--full', action='store_true', help='after the headline, also run the calibration, sustained-window, '
+                    'de-duplicated-formulation, inference, CPU-oracle and small-step legs')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle')
+    ap.add_argument('--no-dedup', action='store_true', help='with --full: skip the extra de-duplicated-formulation timing')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: skip the calibration launches, the 2-s sustained window, '
+                    'the inference kernels and the extra small-step workloads (configs 1, 2, 5)')
     ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (float32)')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be >= 1 and --warmup >= 0')
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    args.dedup = args.full and not args.no_dedup
+    args.extra = args.full and not args.no_extra
+    return args
+
+
+def _main():
+    args = parse_args()
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         # `python bench.py --gpus N`: start the N ranks ourselves, as fresh children, BEFORE anything in this
@@ -805,7 +825,7 @@ def _main():
 
     F_pt = 2 * (vn.inpDim * vn.layerWidth[0] + sum(a * b for a, b in zip(vn.layerWidth[:-1], vn.layerWidth[1:])) + vn.layerWidth[-1])
     cal, sustained, dd = None, None, None
-    if world == 1 and not args.no_extra:
+    if world == 1 and args.extra:
         # what this GPU sustains on the two instruction streams the kernel is priced against (vn_calib.hip, ~30 ms)
         cal = eng.calibrate()
         # ---- the same workload for >= 2 s in ONE timed window: does the 20-step rate hold under seconds of load?
@@ -820,7 +840,7 @@ def _main():
                      "note": "one timed window, one host call (vn_train_epoch), synchronised at both ends"}
     # ---- extra, separately reported: de-duplicated formulation (one network evaluation per unique
     # quadrature point; SURVEY.md 8d "honest accounting").  Never mixed into `value`.
-    if not args.no_dedup and world == 1:          # the scaling runs time the headline formulation only
+    if args.dedup and world == 1:                 # the scaling runs time the headline formulation only
         dd = dedup_leg(vn, tdata, eng, step, args.steps, args.warmup, nT_total, nB, F_pt, lambda: float(gb[P].item()), args.config)
 
     if rank == 0:
@@ -882,14 +902,14 @@ def _main():
         if dd is not None:
             out["dedup"] = dd
         inference = None
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.extra:
             inference = inference_line(vn, tdata, eng, F_pt)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(vn, tdata)
-        if world == 1 and args.config == 3 and not args.no_extra:
+        if world == 1 and args.config == 3 and args.extra:
             eng.close()
             out["extra"] = {"sustained": sustained, "inference": inference,
-                            "config2_small_step": small_step_line(2, 400, 40, cal, with_dedup=not args.no_dedup),
+                            "config2_small_step": small_step_line(2, 400, 40, cal, with_dedup=args.dedup),
                             "config1_small_step": small_step_line(1, 1000, 100, cal),
                             "config5_mor_epoch": mor_epoch_line(5, 2, cal)}
         elif sustained is not None:

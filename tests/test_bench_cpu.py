@@ -251,6 +251,22 @@ def test_dump_outputs_writes_float32_npy_within_the_limit(tmp_path):
     assert not os.path.exists(big)
 
 
+def test_plain_run_takes_no_leg_beyond_the_headline():
+    """A plain run times the headline alone; --full adds the CPU oracle, the de-duplicated formulation and the extra legs, and
+    under --full each --no-* option still skips its own leg."""
+    sys.path.insert(0, ROOT)
+    import bench
+    legs = lambda *argv: [getattr(bench.parse_args(['--steps', '2'] + list(argv)), k) for k in ('cpu_baseline', 'dedup', 'extra')]
+    assert legs() == legs('--no-cpu-baseline', '--no-dedup', '--no-extra') == legs('--dump-outputs', 'd') == [False] * 3
+    assert legs('--full') == [True] * 3
+    assert legs('--full', '--no-cpu-baseline') == [False, True, True]
+    assert legs('--full', '--no-dedup') == [True, False, True]
+    assert legs('--full', '--no-extra') == [True, True, False]
+    assert legs('--full', '--no-cpu-baseline', '--no-dedup', '--no-extra') == [False] * 3
+    args = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert (args.gpus, args.steps, args.warmup, args.config, args.full, args.dump_outputs) == (1, 7, 2, 3, False, None)
+
+
 def test_bench_refuses_zero_timed_steps():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and '--steps' in r.stderr

@@ -128,7 +128,7 @@ if full:
     print(json.dumps(out, indent=1))
 # config 2 (1D+t, 160 000 points, 4x50): Input [nT,2] + gcoef [nT,1] + BC/IC rows, f32
 out2 = pmc_summary('c2pmc_', 2, 'bench.py --config 2 (160k points/step)', 160000 * 3 * 4 + 450 * 3 * 4,
-                   'tools/collect_profiles.sh (rocprofv3 --pmc <group> --kernel-trace, one pass per group) -- python bench.py --config 2 --steps 50 '
+                   'tools/collect_profiles.sh (rocprofv3 --pmc <group> --kernel-trace, one pass per group) -- python bench.py --full --config 2 --steps 50 '
                    '--warmup 5 --no-cpu-baseline --no-dedup', False)
 if out2:
     json.dump(out2, open('profiles/%s_pmc_traffic_cfg2.json' % pre, 'w'), indent=1)
@@ -169,7 +169,7 @@ def dedup_summary():
         ks.append(e)
     return {'config': 3, 'round': pre, 'kernels': ks, 'hbm_bytes_per_step': sum(k['hbm_bytes_per_launch'] for k in ks),
             'correction': 'gfx950: FETCH_SIZE counts 128-B requests at 64 B (MI355X_MICROARCH.md, HBM section) -> doubled; WRITE_SIZE taken as is',
-            'command': 'tools/collect_profiles.sh (rocprofv3 --pmc <group> --kernel-trace, one pass per group) -- python bench.py --steps 3 --warmup 1 '
+            'command': 'tools/collect_profiles.sh (rocprofv3 --pmc <group> --kernel-trace, one pass per group) -- python bench.py --full --steps 3 --warmup 1 '
                        '--no-cpu-baseline --no-extra',
             'note': 'one launch of each kernel per de-duplicated step; vn_fused16_kernel = its reverse-mode launches (dispatches behind the first '
                     '(u, grad u) dispatch)'}
