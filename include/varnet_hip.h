@@ -174,6 +174,20 @@ int vn_set_bic(vn_engine* h, const float* biInput_dev, const float* biLabel_dev,
  * permutation of biInput / biLabel (VarNetUtility.py:988-996).  Same nB, bDof, biDimVal as vn_set_bic; NULL, NULL (or a
  * new vn_set_interior for the batch) returns to the shared set. */
 int vn_set_batch_bic(vn_engine* h, int32_t batch, const float* biInput_dev, const float* biLabel_dev);
+/* OPTIONAL, no reference counterpart: boundary-flux rows (Neumann / Robin), shared by all batches.  Device pointers:
+ * X [nF, d_in], normal [nF, dim] (outward unit normals), coef [nF] (b/a), label [nF] (g/a).  nF == 0 or X == NULL clears.
+ * The reference enforces Dirichlet edges only (the BC rows of vn_set_bic); a boundary a grad(c).n + b c = g with a != 0 enters
+ * no term of its loss.  With flux rows registered, vn_grad / vn_train_step / vn_train_epoch / vn_eval_loss add per row the
+ * residual r = n . grad_x u + (b/a) u - g/a (grad_x: the dim space inputs) to the BC component:
+ *     BC = mean_D[biDimVal (u - g/beta)^2] + mean_F[biDimVal r^2]     (the first mean is 0 without Dirichlet rows)
+ * weighted by w[0] like the Dirichlet mean; the gradient, the update fused into the reduction and a communicator's all-reduce
+ * all see it.  The pass runs on the generic kernels (forward along the normals, residual seeds, reverse pass: three launches
+ * per step) whatever route the interior term takes; networks outside VN_KMAX_* (the layer-by-layer route, 7-8 hidden layers,
+ * mixed activations) get VN_EUNSUPPORTED.  Without flux rows no launch is added and every result is what it is without this
+ * call.  The arrays are READ on every step: they must stay valid while registered.  A call replaces the previous
+ * registration, also when it fails (after an error there is none). */
+int vn_set_flux_bc(vn_engine* h, const float* X_dev, const float* normal_dev, const float* coef_dev,
+                   const float* label_dev, int64_t nF, double biDimVal);
 /* updateDictFields('trainW') (VarNetUtility.py:921-922); the caller applies the
  * w[0:2] /= batchNum*puNum rule (VarNetUtility.py:900-901). */
 int vn_set_weights(vn_engine* h, const double w[3]);

@@ -2,6 +2,7 @@
 // reference call sites each entry point replaces).
 #include "vn_internal.h"
 #include "vn_dedup.h"
+#include "vn_flux.h"
 #include "vn_pgrad16.h"
 #include "vn_taylor16.h"
 #include "vn_split16.h"
@@ -156,6 +157,13 @@ struct vn_engine {
   // de-duplicated formulation work buffers
   float *dd_uv = nullptr, *dd_su = nullptr, *dd_sg = nullptr, *dd_partial = nullptr, *dd_losspart = nullptr;
   long dd_uv_cap = 0, dd_su_cap = 0, dd_sg_cap = 0, dd_partial_cap = 0, dd_cap_lp = 0;
+  // boundary-flux rows (vn_set_flux_bc): caller-owned inputs, engine-owned work buffers; nF == 0: none
+  const float *fX = nullptr, *fN = nullptr, *fcoef = nullptr, *flabel = nullptr;
+  long nF = 0;
+  double fbiDimVal = 1.0;
+  int fgrid = 0;                                  // workgroups of the flux rows' reverse pass
+  float *fu = nullptr, *fud = nullptr, *fubar = nullptr, *fudbar = nullptr, *floss = nullptr, *fpartial = nullptr;
+  long fu_cap = 0, fud_cap = 0, fubar_cap = 0, fudbar_cap = 0, floss_cap = 0, fpartial_cap = 0;
   float* snap = nullptr;       // vn_state_snapshot: device copy of (theta | m | v), 3 P floats
   int64_t snap_step = -1;      // step counter at the snapshot (-1: none)
   PointRoute point_route = PointRoute::automatic;   // vn_debug_point_route(route & 3)
@@ -440,12 +448,37 @@ int fused_forward(vn_engine* h, const float* X, const float* G, long n, float* o
   return VN_OK;
 }
 
+// Boundary-flux rows (vn_set_flux_bc), on every route: value and normal derivative n . grad_x u of each row (the generic forward
+// kernel with the outward normals as tangent directions), the residual r = n . grad_x u + c u - l with its loss partials and
+// seeds, and with_grad the generic reverse pass into the engine's own partials.  Everything reads theta before the step's
+// reduction (which may fold the update in); *fx is what that reduction adds.  Without flux rows nothing is enqueued.
+int flux_pass(vn_engine* h, bool with_grad, VnFluxSum* fx) {
+  *fx = VnFluxSum();
+  if (h->nF <= 0) return VN_OK;
+  VnRows r{}, none{};
+  r.X = h->fX; r.G = h->fN; r.u = h->fu; r.ud = h->fud; r.n = h->nF;
+  HIPCHK(vn_generic_forward(h->net, h->theta, r, none, h->fwd_grid, h->stream));
+  VnFluxSeedArgs a{};
+  a.u = h->fu; a.ud = h->fud; a.coef = h->fcoef; a.label = h->flabel; a.nF = h->nF;
+  a.biDimVal = (float)h->fbiDimVal; a.w0 = (float)h->w[0];
+  a.ubar = with_grad ? h->fubar : nullptr; a.udbar = with_grad ? h->fudbar : nullptr;
+  a.part = h->floss;
+  HIPCHK(vn_flux_seed_launch(a, h->stream));
+  if (with_grad) {
+    r.u = nullptr; r.ud = nullptr; r.ubar = h->fubar; r.udbar = h->fudbar;
+    HIPCHK(vn_generic_backward(h->net, h->theta, r, none, h->fpartial, h->fgrid, h->stream));
+    fx->partial = h->fpartial; fx->nparts = h->fgrid;
+  }
+  fx->loss = h->floss; fx->nlp = vn_flux_seed_blocks(h->nF); fx->nF = h->nF;
+  return VN_OK;
+}
+
 // Loss components and loss field of a batch that carries a de-duplication map (vn_set_dedup), without the row-wise forward: (u, grad u)
 // once per unique point (2 F_pt per POINT where the forward-only mode of the fused kernel costs 2 F_pt per ROW), the assembly kernel of
 // the training step in its loss-only form (R_k, lossVec, variational partials), the BC/IC rows through the forward-only mode and the
 // row-wise seed kernel with an empty interior set.  What every monitor of a run on the de-duplicated formulation calls (splitLoss,
 // VarNet.py:1365): 2.9 -> 0.45 ms on BASELINE config 3.
-int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst) {
+int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst, const VnFluxSum& fx) {
   const int sblk = (int)((b.n_k + VN_DEDUP_TFB - 1) / VN_DEDUP_TFB);
   const int bgrid = (int)(((h->nB > 0 ? h->nB : 1) + 255) / 256);
   if (int rc = ensure(&h->losspart, &h->losspart_cap, (long)(sblk + bgrid) * 3)) return rc;
@@ -460,13 +493,15 @@ int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst) {
   s.part = h->losspart + (long)sblk * 3;
   HIPCHK(vn_seed_launch(s, bgrid, h->stream));
   if (lossdst)
-    HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, sblk + bgrid, h->bDof, h->nB, s.w0, s.w1, s.w2, lossdst, h->stream));
+    HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, sblk + bgrid, h->bDof, h->nB, s.w0, s.w1, s.w2, lossdst, h->stream,
+                            VnOptArgs(), fx));
   return VN_OK;
 }
 
-// forward + weak-form epilogue; with_seeds = also produce backward seeds.
-int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* lossVec, float* lossdst) {
-  if (!with_seeds && b.Xu && h->has_fe && !h->eval_rowwise) return eval_dedup(h, b, lossVec, lossdst);
+// forward + weak-form epilogue; with_seeds = also produce backward seeds.  fx: the flux rows' loss, folded into lossdst.
+int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* lossVec, float* lossdst,
+                         const VnFluxSum& fx = VnFluxSum()) {
+  if (!with_seeds && b.Xu && h->has_fe && !h->eval_rowwise) return eval_dedup(h, b, lossVec, lossdst, fx);
   VnRows s0{}, s1{};
   s0.X = b.Input; s0.G = b.gcoef; s0.u = h->u; s0.ud = h->ud; s0.n = b.n_k * h->cfg.integ_num;
   s1.X = bi_x(h, b); s1.G = nullptr; s1.u = h->ub; s1.ud = nullptr; s1.n = h->nB;
@@ -490,12 +525,13 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
   a.lossVec = lossVec; a.part = h->losspart;
   HIPCHK(vn_seed_launch(a, grid, h->stream));
   if (lossdst) {
-    HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2, lossdst, h->stream));
+    HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2, lossdst, h->stream,
+                            VnOptArgs(), fx));
   }
   return VN_OK;
 }
 
-int run_layered(vn_engine* h, const Batch& b, float* gradbuf) {
+int run_layered(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
   if (int rc = run_forward_and_seed(h, b, true, nullptr, nullptr)) return rc;
   VnRows s0{}, s1{};
   s0.X = b.Input; s0.G = b.gcoef; s0.ubar = h->ubar; s0.udbar = h->udbar; s0.n = b.n_k * h->cfg.integ_num;
@@ -509,11 +545,11 @@ int run_layered(vn_engine* h, const Batch& b, float* gradbuf) {
   const long nth = b.n_k > h->nB ? b.n_k : h->nB;
   const int lg = (int)(((nth > 0 ? nth : 1) + 255) / 256);
   HIPCHK(vn_reduce_launch(h->partial, 1, h->net.P, h->losspart, lg, h->bDof, h->nB, (float)h->w[0], (float)h->w[1],
-                          (float)h->w[2], gradbuf, h->stream, h->fuse));
+                          (float)h->w[2], gradbuf, h->stream, h->fuse, fx));
   return VN_OK;
 }
 
-int run_generic(vn_engine* h, const Batch& b, float* gradbuf) {
+int run_generic(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
   if (int rc = run_forward_and_seed(h, b, true, nullptr, nullptr)) return rc;
   VnRows s0{}, s1{};
   s0.X = b.Input; s0.G = b.gcoef; s0.ubar = h->ubar; s0.udbar = h->udbar; s0.n = b.n_k * h->cfg.integ_num;
@@ -524,13 +560,13 @@ int run_generic(vn_engine* h, const Batch& b, float* gradbuf) {
   const long nthreads = b.n_k > h->nB ? b.n_k : h->nB;
   const int lgrid = (int)((nthreads + 255) / 256);
   HIPCHK(vn_reduce_launch(h->partial, h->bwd_grid, h->net.P, h->losspart, lgrid, h->bDof, h->nB, (float)h->w[0],
-                          (float)h->w[1], (float)h->w[2], gradbuf, h->stream, h->fuse));
+                          (float)h->w[1], (float)h->w[2], gradbuf, h->stream, h->fuse, fx));
   return VN_OK;
 }
 
 // One launch of the fused kernel (8-wave, or 4-wave in the cross-check build) for the whole step: forward, weak-form epilogue
 // and reverse pass of every tile, BC/IC tiles included
-int run_fused(vn_engine* h, const Batch& b, float* gradbuf) {
+int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
   VnFusedArgs a = fused_args(h, &b);
   a.X = b.Input; a.G = b.gcoef; a.src = batch_src(h, b);
   a.nT = b.n_k * h->cfg.integ_num; a.n_k = b.n_k; a.feW = fe_w(h);
@@ -549,7 +585,7 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf) {
   }
   if (int rc = prof_stop(h)) return rc;
   HIPCHK(vn_reduce_launch(h->partial, grid, h->net.P, h->fused_losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2,
-                          gradbuf, h->stream, h->fuse));
+                          gradbuf, h->stream, h->fuse, fx));
   return VN_OK;
 }
 
@@ -559,7 +595,7 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf) {
 //   2. vn_seed_kernel -> R_k, lossVec, variational loss partials, per-row seeds
 //   3. reverse pass with those seeds (recomputes the forward); BC/IC tiles ride along   (6 F_pt)
 // 8 F_pt per point instead of 6, against 8 F_pt at 0.07 of peak on the generic kernels.
-int run_twopass(vn_engine* h, const Batch& b, float* gradbuf) {
+int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
   const int grid = h->ncu, P = h->net.P;
   const int sgrid = (int)((b.n_k + 255) / 256);
   if (int rc = ensure(&h->tp_losspart, &h->tp_losspart_cap, (long)(grid + sgrid) * 3)) return rc;
@@ -581,7 +617,7 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf) {
   if (int rc = prof_start(h)) return rc;
   if (int rc = fused8_launch(h, f, grid)) return rc;
   if (int rc = prof_stop(h)) return rc;
-  HIPCHK(vn_reduce_launch(h->partial, grid, P, lp, grid + sgrid, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream, h->fuse));
+  HIPCHK(vn_reduce_launch(h->partial, grid, P, lp, grid + sgrid, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream, h->fuse, fx));
   return VN_OK;
 }
 
@@ -592,7 +628,7 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf) {
 //   4. ONE reverse launch of the fused kernel (recomputes the forward): the directional derivative is linear in its
 //      direction, sum_d sg_d * d(u_{x_d})/d theta = d(sg . grad u)/d theta with sg held fixed, so the per-point direction
 //      G = sg with tangent seed 1 and value seed su gives the whole gradient; BC/IC tiles ride along       (6 F_pt)
-int run_dedup(vn_engine* h, const Batch& b, float* gradbuf) {
+int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
   const int grid = h->ncu, P = h->net.P;
   const int sblk = (int)((b.n_k + VN_DEDUP_TFB - 1) / VN_DEDUP_TFB);
   float* lp = h->dd_losspart;                       // [grid + sblk][3]
@@ -612,7 +648,7 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf) {
   f.seed_u = h->dd_su; f.seed_ud = nullptr;          // tangent seed 1
   if (int rc = fused8_launch(h, f, grid)) return rc;
   if (int rc = prof_stop(h)) return rc;
-  HIPCHK(vn_reduce_launch(h->dd_partial, grid, P, lp, grid + sblk, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream, h->fuse));
+  HIPCHK(vn_reduce_launch(h->dd_partial, grid, P, lp, grid + sblk, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream, h->fuse, fx));
   return VN_OK;
 }
 
@@ -770,7 +806,7 @@ int vn_destroy(vn_engine* h) {
   if (h->comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(h->stream); (void)g_rccl.CommDestroy(h->comm); h->comm = nullptr; }
   void* ptrs[] = {h->theta, h->m, h->v, h->snap, h->theta64, h->gradbuf_int, h->lossbuf, h->partial, h->feN, h->fedNt,
                   h->feW, h->u, h->ud, h->ubar, h->udbar, h->ub, h->ubar_b, h->losspart, h->fused_losspart, h->stamps, h->dd_uv, h->dd_su, h->dd_sg, h->dd_partial,
-                  h->dd_losspart, h->tp_losspart, h->f16_stash};
+                  h->dd_losspart, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (Batch& b : h->batches)
@@ -1022,6 +1058,33 @@ int vn_set_bic(vn_engine* h, const float* biInput, const float* biLabel, int64_t
   return VN_OK;
 }
 
+int vn_set_flux_bc(vn_engine* h, const float* X, const float* normal, const float* coef, const float* label, int64_t nF,
+                   double biDimVal) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (nF < 0) return fail(VN_EINVAL, "negative number of flux rows");
+  h->fX = h->fN = h->fcoef = h->flabel = nullptr;   // a call replaces the previous registration, also when it fails
+  h->nF = 0;
+  if (nF == 0 || !X) return VN_OK;
+  if (!normal || !coef || !label) return fail(VN_EINVAL, "null argument");
+  // the flux pass runs on the generic kernels, whatever route the interior term takes
+  if (h->route == Route::layered || !vn_net_in_kernel_range(h->net))
+    return fail(VN_EUNSUPPORTED, "boundary-flux rows need a network of the hand-written kernels (<= %d hidden layers, width <= %d, "
+                "<= %d inputs, one activation); this one (%d layers, widest %d, %d inputs%s) runs on the layer-by-layer route "
+                "or the deep fused kernel only", VN_KMAX_LAYERS, VN_KMAX_WIDTH, VN_KMAX_DIN, h->net.L, h->net.hmax, h->net.d_in,
+                h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const long tiles = (nF + 31) / 32;
+  const int fgrid = (int)(tiles < h->ncu ? tiles : h->ncu);
+  if (int rc = ensure(&h->fu, &h->fu_cap, nF)) return rc;
+  if (int rc = ensure(&h->fud, &h->fud_cap, nF)) return rc;
+  if (int rc = ensure(&h->fubar, &h->fubar_cap, nF)) return rc;
+  if (int rc = ensure(&h->fudbar, &h->fudbar_cap, nF)) return rc;
+  if (int rc = ensure(&h->floss, &h->floss_cap, vn_flux_seed_blocks(nF))) return rc;
+  if (int rc = ensure(&h->fpartial, &h->fpartial_cap, (long)fgrid * h->net.P)) return rc;
+  h->fX = X; h->fN = normal; h->fcoef = coef; h->flabel = label; h->nF = nF; h->fbiDimVal = biDimVal; h->fgrid = fgrid;
+  return VN_OK;
+}
+
 int vn_set_batch_bic(vn_engine* h, int32_t batch, const float* biInput, const float* biLabel) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
@@ -1050,13 +1113,15 @@ int vn_grad(vn_engine* h, int32_t batch) {
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   const Batch& b = h->batches[batch];
-  if (b.Xu) return run_dedup(h, b, h->gradbuf);      // (a de-duplication map: 8-wave routes only)
+  VnFluxSum fx;
+  if (int rc = flux_pass(h, true, &fx)) return rc;   // (no flux rows: nothing enqueued, fx empty)
+  if (b.Xu) return run_dedup(h, b, h->gradbuf, fx);      // (a de-duplication map: 8-wave routes only)
   switch (h->route) {
-    case Route::layered: return run_layered(h, b, h->gradbuf);
-    case Route::generic: return run_generic(h, b, h->gradbuf);
+    case Route::layered: return run_layered(h, b, h->gradbuf, fx);
+    case Route::generic: return run_generic(h, b, h->gradbuf, fx);
     case Route::fused4:
-    case Route::fused8: return run_fused(h, b, h->gradbuf);
-    case Route::twopass: return run_twopass(h, b, h->gradbuf);
+    case Route::fused8: return run_fused(h, b, h->gradbuf, fx);
+    case Route::twopass: return run_twopass(h, b, h->gradbuf, fx);
   }
 }
 
@@ -1132,7 +1197,9 @@ int vn_eval_loss(vn_engine* h, int32_t batch, double out[4], float* lossVec_dev)
   (void)hipGetLastError();   // a stale last-error of another library on this thread is not ours to report
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (int rc = run_forward_and_seed(h, h->batches[batch], false, lossVec_dev, h->lossbuf)) return rc;
+  VnFluxSum fx;
+  if (int rc = flux_pass(h, false, &fx)) return rc;
+  if (int rc = run_forward_and_seed(h, h->batches[batch], false, lossVec_dev, h->lossbuf, fx)) return rc;
   float t[4];
   HIPCHK(hipMemcpyAsync(t, h->lossbuf, sizeof t, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));

@@ -7,6 +7,7 @@
 // form in oracle/tangent_ref.py and follows the reference graph TFModel.py:536 (input gradient),
 // :653-661 (weak-form integrand), :709 (parameter gradient).
 #include "vn_internal.h"
+#include "vn_flux.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -385,15 +386,50 @@ __global__ __launch_bounds__(NTHREADS) void vn_seed_kernel(VnSeedArgs a) {
   }
 }
 
+// Boundary-flux rows: one thread per row, one loss partial per block (folded by vn_reduce_kernel in a fixed order).
+constexpr int FLUX_TB = 256;
+__global__ __launch_bounds__(FLUX_TB) void vn_flux_seed_kernel(VnFluxSeedArgs a) {
+  __shared__ float red[4];
+  const long k = (long)blockIdx.x * FLUX_TB + threadIdx.x;
+  float e2 = 0.f;
+  if (k < a.nF) {
+    const float c = a.coef[k];
+    const float r = a.ud[k] + c * a.u[k] - a.label[k];
+    e2 = a.biDimVal * r * r;
+    if (a.ubar) {
+      const float s = 2.f * a.w0 * a.biDimVal / (float)a.nF;
+      a.udbar[k] = s * r;
+      a.ubar[k] = s * c * r;
+    }
+  }
+  const float t = block_sum(e2, red);
+  if (threadIdx.x == 0) a.part[blockIdx.x] = t;
+}
+
 // grad[p] = sum over workgroup partials in a fixed order; block 0 also folds the loss partials.
 // A block owns 64 consecutive parameters; its 16 waves each sum every 16th partial (coalesced 256-B
 // rows, 16 loads in flight per lane), then the 16 sub-sums are added in wave order -> bitwise
 // reproducible.
 constexpr int RED_GROUPS = 16;
+__device__ __forceinline__ void add_parts(const float* __restrict__ partial, int nparts, int P, int p, int grp, float& acc) {
+  for (int g0 = grp; g0 < nparts; g0 += RED_GROUPS * 16) {
+    float t[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int g = g0 + j * RED_GROUPS;
+      t[j] = g < nparts ? partial[(long)g * P + p] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (g0 + j * RED_GROUPS < nparts) acc += t[j];          // same order as a sequential walk g = grp, grp + 16, ...
+  }
+}
+
 __global__ __launch_bounds__(64 * RED_GROUPS) void vn_reduce_kernel(const float* __restrict__ partial, int nparts,
                                                                   int P, const float* __restrict__ losspart,
                                                                   int nlp, long bDof, long nB, float w0, float w1,
-                                                                  float w2, float* __restrict__ gradbuf, VnOptArgs opt) {
+                                                                  float w2, float* __restrict__ gradbuf, VnOptArgs opt,
+                                                                  VnFluxSum flux) {
   __shared__ float sub[RED_GROUPS][64];
   const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
   const int p = blockIdx.x * 64 + lane;
@@ -405,17 +441,8 @@ __global__ __launch_bounds__(64 * RED_GROUPS) void vn_reduce_kernel(const float*
   if (upd) { th = opt.theta[p]; mo = opt.m[p]; vo = opt.v[p]; }
   float acc = 0.f;
   if (p < P) {
-    for (int g0 = grp; g0 < nparts; g0 += RED_GROUPS * 16) {
-      float t[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int g = g0 + j * RED_GROUPS;
-        t[j] = g < nparts ? partial[(long)g * P + p] : 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        if (g0 + j * RED_GROUPS < nparts) acc += t[j];          // same order as a sequential walk g = grp, grp + 16, ...
-    }
+    add_parts(partial, nparts, P, p, grp, acc);
+    add_parts(flux.partial, flux.nparts, P, p, grp, acc);     // boundary-flux rows (none: nparts 0)
   }
   sub[grp][lane] = acc;
   __syncthreads();
@@ -474,9 +501,23 @@ __global__ __launch_bounds__(64 * RED_GROUPS) void vn_reduce_kernel(const float*
         for (int v = 1; v < RED_GROUPS; ++v) { t0 += lsub[v][0]; t1 += lsub[v][1]; t2 += lsub[v][2]; }
       }
     }
+    // boundary-flux rows: wave 2 folds their per-block partials (lane-strided, fixed shuffle tree) into the BC component's
+    // second mean (block-uniform: flux.nF is a kernel argument)
+    __shared__ double fmean;
+    if (flux.nF > 0) {
+      if (grp == 2) {
+        double tf = 0.0;
+        for (int g = lane; g < flux.nlp; g += 64) tf += (double)flux.loss[g];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) tf += __shfl_down(tf, o, 64);
+        if (lane == 0) fmean = tf / (double)flux.nF;
+      }
+      __syncthreads();
+    }
     if (grp == 1 && lane == 0) {
       const double var = t0;
-      const double bc = bDof > 0 ? t1 / (double)bDof : 0.0;               // reduce_mean, TFModel.py:645
+      double bc = bDof > 0 ? t1 / (double)bDof : 0.0;                     // reduce_mean, TFModel.py:645
+      if (flux.nF > 0) bc += fmean;                                       // + mean_F[biDimVal r^2] (vn_set_flux_bc)
       const double ic = (nB - bDof) > 0 ? t2 / (double)(nB - bDof) : 0.0; // TFModel.py:648
       const float loss = (float)(w0 * bc + w1 * ic + w2 * var);           // TFModel.py:666
       gradbuf[P + 0] = loss;
@@ -575,10 +616,25 @@ hipError_t vn_seed_launch(const VnSeedArgs& a, int grid, hipStream_t s) {
 
 hipError_t vn_reduce_launch(const float* partial, int nparts, int P, const float* losspart, int nlossparts,
                             long bDof, long nB, float w0, float w1, float w2, float* gradbuf, hipStream_t s,
-                            VnOptArgs opt) {
+                            VnOptArgs opt, const VnFluxSum& flux) {
   const int grid = (P + 63) / 64;
   hipLaunchKernelGGL(vn_reduce_kernel, dim3(grid > 0 ? grid : 1), dim3(64 * RED_GROUPS), 0, s, partial, nparts, P,
-                     losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, opt);
+                     losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, opt, flux);
+  return hipGetLastError();
+}
+
+hipError_t vn_reduce_launch(const float* partial, int nparts, int P, const float* losspart, int nlossparts,
+                            long bDof, long nB, float w0, float w1, float w2, float* gradbuf, hipStream_t s,
+                            VnOptArgs opt) {
+  return vn_reduce_launch(partial, nparts, P, losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, s, opt, VnFluxSum());
+}
+
+int vn_flux_seed_blocks(long nF) { return (int)((nF + FLUX_TB - 1) / FLUX_TB); }
+
+hipError_t vn_flux_seed_launch(const VnFluxSeedArgs& a, hipStream_t s) {
+  const int grid = vn_flux_seed_blocks(a.nF);
+  if (grid <= 0) return hipSuccess;
+  hipLaunchKernelGGL(vn_flux_seed_kernel, dim3(grid), dim3(FLUX_TB), 0, s, a);
   return hipGetLastError();
 }
 

@@ -95,6 +95,25 @@ class PolygonDomain2D(Domain):
         v = np.asarray(vertices, dtype=float)
         return np.stack([v, np.roll(v, -1, axis=0)], axis=1)
 
+    @staticmethod
+    def _edgeNormals(vertices, sign):
+        """Unit normals of the edges v_i -> v_{i+1}, turned -90 deg for a counter-clockwise list (+90 deg for a clockwise one,
+        by the sign of the signed area): the side away from the polygon's interior, times `sign`."""
+        v = np.asarray(vertices, dtype=float)
+        e = np.roll(v, -1, axis=0) - v
+        area2 = np.sum(v[:, 0] * np.roll(v[:, 1], -1) - np.roll(v[:, 0], -1) * v[:, 1])
+        n = np.stack([e[:, 1], -e[:, 0]], axis=1) * (1.0 if area2 > 0 else -1.0)
+        return sign * n / np.linalg.norm(e, axis=1, keepdims=True)
+
+    def boundaryNormals(self):
+        """[bIndNum, 2] outward unit normal of every boundary indicator (no reference counterpart: the flux rows of
+        `VarNet(fluxBC=True)`): the outer polygon's edges, then the obstacles' edges, whose normals point out of the
+        computational domain, i.e. into the obstacle.  Clockwise and counter-clockwise vertex lists give the same normals."""
+        out = [self._edgeNormals(self.vertices, 1.0)]
+        for obs in self.obsVertices:
+            out.append(self._edgeNormals(obs, -1.0))
+        return np.vstack(out)
+
     def isInside(self, x, tol=0.):
         """Point-in-polygon with matplotlib.path, as the reference does (Domain.py:354-384)."""
         from matplotlib.path import Path
@@ -174,6 +193,10 @@ class Domain1D(Domain):
         super().__init__(1, np.reshape(interval, [2, 1]))
         self.bIndNum = 2
         self.measure = interval[1] - interval[0]
+
+    def boundaryNormals(self):
+        """[2, 1] outward unit normals: -1 at indicator 0 (the left end), +1 at indicator 1."""
+        return np.array([[-1.0], [1.0]])
 
     def isInside(self, x, tol=0.):
         x = np.asarray(x)

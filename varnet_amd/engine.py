@@ -59,6 +59,7 @@ _SIGS = {
     'vn_set_dedup': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'vn_set_bic': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double]),
     'vn_set_batch_bic': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'vn_set_flux_bc': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
     'vn_set_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_bind_grad_buffer': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vn_grad': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -406,6 +407,26 @@ class VNEngine:
         biLabel = self.dev(np.reshape(biLabel, -1) if isinstance(biLabel, np.ndarray) else biLabel.reshape(-1))
         self._keep[('bbic', batch)] = (biInput, biLabel)
         self._ck(self.lib.vn_set_batch_bic(self.h, batch, _ptr(biInput), _ptr(biLabel)))
+
+    def set_flux_bc(self, X=None, normal=None, coef=None, label=None, biDimVal=1.0):
+        """Register (or, with X=None, clear) the boundary-flux rows of Neumann / Robin edges (vn_set_flux_bc): X [nF, inpDim],
+        outward unit normals [nF, dim], coef = b/a [nF], label = g/a [nF]."""
+        if X is None or len(X) == 0:
+            self._keep['flux'] = None
+            self._ck(self.lib.vn_set_flux_bc(self.h, None, None, None, None, 0, float(biDimVal)))
+            return
+        X, normal = self.dev(X), self.dev(normal)
+        coef, label = self.dev(np.reshape(coef, -1)), self.dev(np.reshape(label, -1))
+        nF = X.shape[0]
+        # the ABI carries pointers only: the lengths every kernel of the pass relies on are checked here
+        assert X.shape == (nF, self.inpDim) and normal.shape == (nF, self.dim), (tuple(X.shape), tuple(normal.shape))
+        assert coef.numel() == nF and label.numel() == nF
+        old = self._keep.pop('flux', None)
+        try:
+            self._ck(self.lib.vn_set_flux_bc(self.h, _ptr(X), _ptr(normal), _ptr(coef), _ptr(label), nF, float(biDimVal)))
+        finally:
+            del old           # the engine dropped the previous registration before checking this one
+        self._keep['flux'] = (X, normal, coef, label)
 
     def set_weights(self, w):
         arr = (C.c_double * 3)(*[float(x) for x in w])

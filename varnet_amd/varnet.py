@@ -291,6 +291,8 @@ class TrainResult:
             geom = PDE.domain.boundryGeom.tolist()
             for bi in range(PDE.domain.bIndNum):
                 L.append('\tBC%d: %s - vertices: %s\n' % (bi + 1, PDE.BCtype[bi], geom[bi]))
+        for bInd, kind, rows in (varNet.fluxRows or {}).get('edges', []):
+            L.append('\tBC%d: %s condition enforced as a boundary flux term on %d rows\n' % (bInd + 1, kind, rows))
         L.append('\n')
         L.append('Neural Network architecture:\n')
         L.append('\ttype: ' + str(varNet.modelId) + '\n')
@@ -765,7 +767,7 @@ class ManageTrainData:
 class VarNet:
     def __init__(self, PDE, layerWidth=[20], modelId='MLP', activationFun=None, discNum=20,
                  bDiscNum=[], tDiscNum=[], MORdiscScheme=None, processors=None, controller=None,
-                 integPnum=2, optimizer='adam', learning_rate=0.001):
+                 integPnum=2, optimizer='adam', learning_rate=0.001, fluxBC=False):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -795,6 +797,10 @@ class VarNet:
             optimizer = 'rmsprop'
         if optimizer.lower() not in ('adam', 'rmsprop'):
             raise ValueError('unknown optimizer requested!')
+        if fluxBC and MORvar is not None:
+            raise NotImplementedError('fluxBC=True with model-order reduction is not supported: the flux rows carry one label '
+                                      'g/a per boundary point, shared by all batches, while a MOR problem needs per-batch labels '
+                                      'and per-batch network inputs on them')
 
         inpDim = dim + (1 if timeDependent else 0)
         if MORvar is not None:
@@ -808,6 +814,7 @@ class VarNet:
         self.layerWidth, self.inpDim, self.lossOpt = list(layerWidth), inpDim, lossOpt
         self.activationFun, self.optimizer, self.learning_rate = activationFun, optimizer, learning_rate
         self.processors, self.controller = processors, controller
+        self.fluxBC, self.fluxRows = bool(fluxBC), None
 
         self.fixData = FIXData(self, integPnum)
         self.fixData.setInputData(self)
@@ -828,7 +835,8 @@ class VarNet:
             from .towers import TowerGroup
             kw = dict(layerWidth=layerWidth, modelId=modelId, activationFun=activationFun, discNum=discNum,
                       bDiscNum=bDiscNum, tDiscNum=tDiscNum, MORdiscScheme=MORdiscScheme, processors=list(processors),
-                      controller=controller, integPnum=integPnum, optimizer=optimizer, learning_rate=learning_rate)
+                      controller=controller, integPnum=integPnum, optimizer=optimizer, learning_rate=learning_rate,
+                      fluxBC=fluxBC)
             self._towers = TowerGroup(type(self), (PDE,), kw, list(processors))
             self.world = self._towers.world
             self.engine = self.tfData = None
@@ -863,6 +871,13 @@ class VarNet:
                 self.comm_why = 'not attempted: VN_COMM=%s on the %s backend' % (mode, self.dist.get_backend())
         fd = self.fixData
         self.engine.set_fe_table(fd.N, fd.dNt, None if fd.integW is None else fd.integW)
+        if self.fluxBC:
+            # fixed for the whole run (the uniform boundary set; optimal re-draws resample Dirichlet rows only): registered once.
+            # A network outside the kernels that run the flux pass is refused here, with the engine's sentence.
+            self.fluxRows = self.fluxTrainData()
+            r = self.fluxRows
+            if r['X'].shape[0] > 0:
+                self.engine.set_flux_bc(r['X'], r['normal'], r['coef'], r['label'], fd.biDimVal)
         self.tfData = self.engine       # name kept for scripts that poke at `VarNet.tfData`
         from .launch import mark_stage
         mark_stage('engine_ready')      # past the launcher's bootstrap deadline: a rank that trains for hours is healthy
@@ -1078,6 +1093,37 @@ class VarNet:
             iInput = np.concatenate([mesh.coordinates, np.zeros([mesh.dof, 1])], axis=1)
             biDof.append(mesh.dof)
         return uf.vstack([bInput, iInput]), biDof
+
+    def fluxTrainData(self):
+        """
+        (No reference counterpart: `fluxBC=True`.)  Flux rows of every Neumann / Robin boundary indicator, assembled once on the
+        host in fp64: the uniform boundary points `mesh.bCoordinates[bInd]` (paired with the time nodes like the Dirichlet rows),
+        the indicator's outward unit normal n, coef = b/a and label = g(x[,t])/a, so that the row's residual is
+        n . grad_x u + coef u - label (DESIGN.md "Boundary flux term").  Returns dict(X, normal, coef, label, edges) with
+        edges = [(bInd, BCtype, rows)] in indicator order.
+        """
+        PDE, dim = self.PDE, self.dim
+        td = PDE.timeDependent
+        domain = PDE.domain
+        t_coord = self.timeDisc()[1] if td else []
+        mesh = domain.getMesh(self.discNum, self.bDiscNum)
+        normals = np.asarray(domain.boundaryNormals(), dtype=float)
+        X, nrm, coef, label, edges = [], [], [], [], []
+        for bInd in range(domain.bIndNum):
+            if PDE.BCtype[bInd] == 'Dirichlet':
+                continue
+            a, b, g = PDE.BCs[bInd]
+            x = np.asarray(uf.pairMats(mesh.bCoordinates[bInd], t_coord), dtype=float)
+            targ = [x[:, dim:dim + 1]] if td else []
+            n = x.shape[0]
+            X.append(x)
+            nrm.append(np.tile(normals[bInd], (n, 1)))
+            coef.append(np.full(n, float(b) / float(a)))
+            label.append(np.reshape(g(x[:, :dim], *targ), -1).astype(float) / float(a))
+            edges.append((bInd, PDE.BCtype[bInd], n))
+        if not X:
+            return dict(X=np.zeros([0, self.inpDim]), normal=np.zeros([0, dim]), coef=np.zeros(0), label=np.zeros(0), edges=[])
+        return dict(X=np.vstack(X), normal=np.vstack(nrm), coef=np.concatenate(coef), label=np.concatenate(label), edges=edges)
 
     def biTrainData(self, biInput, biDof, biArg=[]):
         """Labels g/beta on Dirichlet edges, IC(x) on the initial slice (VarNet.py:649-722)."""
