@@ -3,10 +3,12 @@ The reference's 1D+t demo (/root/reference/Operator_1Dt.py:69-186) on the MI355X
 ([20]), same discretisation (discNum=20, tDiscNum=300 -> 96 000 training points), same call sequence -- the only
 edit a user of the reference makes is the import line (varnet_amd instead of the flat VarNet modules).
 
-    python examples/operator_1dt.py [out_folder] [epochs] [smpScheme] [lossLag]
+    python examples/operator_1dt.py [out_folder] [epochs] [smpScheme] [lossLag] [optimizer]
 
 The reference runs `train(..., smpScheme='optimal', adjustWeight=True)` until `loss < tol` or 500 000 epochs; pass an
 epoch count to bound the run.  Prints the script's own acceptance metric, "Normalized approximation error".
+optimizer: adam (default), rmsprop or lbfgs (an extension: one device-resident L-BFGS iteration per epoch, DESIGN.md section 12;
+e.g. `operator_1dt.py out 8000 uniform 0 lbfgs`).
 """
 import os
 import sys
@@ -50,9 +52,10 @@ def main():
     epochs = int(sys.argv[2]) if len(sys.argv) > 2 else 20000
     scheme = sys.argv[3] if len(sys.argv) > 3 else 'optimal'
     lag = int(sys.argv[4]) if len(sys.argv) > 4 else None              # lossLag: read-back schedule (None = train()'s default: 8, exact; 0 = one read-back per epoch)
+    optimizer = sys.argv[5] if len(sys.argv) > 5 else 'adam'
     domain = Domain1D()
     pde = ADPDE(domain, diff=D, vel=u, timeDependent=True, tInterval=[0, T], IC=IC, cEx=cExact)
-    vn = VarNet(pde, layerWidth=[20], discNum=20, bDiscNum=None, tDiscNum=300, processors='GPU:0')
+    vn = VarNet(pde, layerWidth=[20], discNum=20, bDiscNum=None, tDiscNum=300, processors='GPU:0', optimizer=optimizer)
     os.makedirs(folder, exist_ok=True)
     t0 = time.perf_counter()
     vn.train(folder, weight=[1.e1, 1.e1, 1.], smpScheme=scheme, adjustWeight=True, epochNum=epochs, saveFreq=1000,

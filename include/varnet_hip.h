@@ -53,7 +53,9 @@ enum {
  * per hidden layer (the reference accepts a list, TFModel.py:113-119); a list with different entries runs on the
  * layer-by-layer route, the kernels take one activation for all hidden layers. */
 enum { VN_ACT_SIGMOID = 0, VN_ACT_TANH = 1, VN_ACT_PER_LAYER = 2 };
-enum { VN_OPT_ADAM = 0, VN_OPT_RMSPROP = 1 };   /* tf.train.AdamOptimizer / RMSPropOptimizer (TFModel.py:183-186) */
+enum { VN_OPT_ADAM = 0, VN_OPT_RMSPROP = 1,     /* tf.train.AdamOptimizer / RMSPropOptimizer (TFModel.py:183-186) */
+       VN_OPT_LBFGS = 2 };                      /* no reference counterpart: device-resident L-BFGS, advanced by vn_lbfgs_step */
+#define VN_LBFGS_HISTORY 10                     /* (s, y) pairs the L-BFGS ring keeps */
 /* Kernel families.  AUTO picks the 8-wave fused kernel where it is instantiated: uniform or ragged hidden widths
  * <= 50 with 1..8 layers, <= 64 with 1..6 layers, d_in <= 8, sigmoid or tanh; integ_num <= 128 in one launch, larger
  * through the two-pass route.  The generic kernels serve VN_KERNEL_GENERIC requests (the independent cross-check of the
@@ -83,13 +85,14 @@ typedef struct vn_config {
   int32_t has_source;               /* lossOpt['isSource']  (TFModel.py:656)               */
   int32_t has_integw;               /* lossOpt['integWflag'] (TFModel.py:660)              */
   int32_t device;                   /* HIP device ordinal                                  */
-  int32_t optimizer;                /* VN_OPT_ADAM | VN_OPT_RMSPROP (TFModel.py:183-186)   */
+  int32_t optimizer;                /* VN_OPT_ADAM | VN_OPT_RMSPROP (TFModel.py:183-186) | VN_OPT_LBFGS */
   int32_t kernel;                   /* VN_KERNEL_*                                         */
   double  lr, beta1, beta2, eps;    /* taken literally, NO defaulting (TF-1's own defaults are 1e-3, .9, .999, 1e-8).  lr >= 0
                                      * (lr = 0 is legal TF: TFModel.py:130).  With VN_OPT_ADAM: 0 <= beta1, beta2 < 1 and
                                      * eps > 0, else vn_create returns VN_EINVAL -- a zero-initialised struct (eps = 0 turns a
                                      * zero gradient into 0/0 = NaN in the update) is rejected, not trained.  RMSProp ignores
-                                     * beta1, beta2, eps (TF-1 constants: decay 0.9, momentum 0, epsilon 1e-10).           */
+                                     * beta1, beta2, eps (TF-1 constants: decay 0.9, momentum 0, epsilon 1e-10); L-BFGS ignores
+                                     * all four.                                                                          */
   int32_t layer_act[VN_MAX_LAYERS]; /* with VN_ACT_PER_LAYER: VN_ACT_SIGMOID | VN_ACT_TANH of hidden layer i */
 } vn_config;
 
@@ -210,6 +213,36 @@ int vn_train_step(vn_engine* h, int32_t batch, float* loss_out_dev);
  * (vn_grad + vn_apply) over batches[0..n), the pre-update loss of each step ADDED to the device scalar
  * *loss_acc_dev (may be NULL).  One host call per epoch instead of four per mini-batch; no sync. */
 int vn_train_epoch(vn_engine* h, const int32_t* batches, int32_t n, float* loss_acc_dev);
+
+/* OPTIONAL, no reference counterpart: one L-BFGS iteration on the objective "vn_grad of `batch`" (whatever route, de-duplication
+ * map and flux rows that batch has), for engines created with optimizer = VN_OPT_LBFGS; VN_ESTATE on Adam / RMSProp engines,
+ * VN_EUNSUPPORTED on a handle with a communicator.  On such an engine vn_apply, vn_train_step, vn_train_epoch, vn_state_snapshot
+ * and vn_state_rollback return VN_ESTATE.  Full-batch, deterministic objectives only: consecutive calls must see the same one.
+ *   State (device, fp32 vectors of length P, allocated at the first call -- VN_ENOMEM if they do not fit): theta_k, the
+ *   optimizer's own copy of g_k and of the loss scalars f_k (a caller's vn_grad between two calls does not disturb them), the
+ *   direction, and a ring of up to m = VN_LBFGS_HISTORY pairs (s_i, y_i) in m + 1 slots per family (the spare slot takes the pair
+ *   of an accepted step before its curvature test): (2 m + 5) P floats in all.
+ *   1. (f_k, g_k) not valid: vn_grad(batch) at theta_k first (an evaluation, not a trial).
+ *   2. Direction: the two-loop recursion over the stored pairs, newest first, gamma = s.y / y.y of the newest pair (1 without
+ *      pairs), d = -H g_k; run in its Gram form on the coefficients of d in the basis [s_i, y_i, g_k], every inner product
+ *      accumulated in fp64 in a fixed order (bitwise repeatable).  g_k.d >= 0: the ring is dropped and d = -g_k.
+ *   3. Backtracking Armijo search: t0 = min(1, 1/|g_k|_1) with an empty ring, else 1; trial j runs vn_grad at
+ *      fl32(theta_k + t d), t = t0 2^-j, j < max_trials; the first trial whose loss is finite and <= f_k + 1e-4 t g_k.d is
+ *      accepted.  One 16-byte copy and one synchronisation per trial; the decision is the host's, in double.
+ *   4. Accepted: theta_{k+1} is the trial point, s = fl32(theta_{k+1} - theta_k), y = fl32(g_{k+1} - g_k); the pair enters the
+ *      ring (evicting the oldest) iff s.y > 1e-10 |s|_2 |y|_2 (decided on the device when the next direction is formed); the step
+ *      counter moves by one; the gradient buffer holds g_{k+1} and the loss scalars of theta_{k+1}.
+ *   5. No trial accepted: theta is restored to theta_k bit for bit, the step counter does not move; status 1 with pairs in the
+ *      ring (they are dropped: the next call is a steepest-descent iteration), status 2 ("stalled") with an empty ring.  Both
+ *      return VN_OK.
+ * info = {status, f_k, f_{k+1}, BC, IC, var at theta_{k+1}, accepted t, trials used, g_k.d, pairs the direction was formed from}
+ * (after a status != 0: f_{k+1} = f_k, the components of theta_k, t = 0).
+ * vn_params_init, vn_params_set, vn_state_import, vn_set_bic, vn_set_flux_bc, vn_set_interior / vn_set_dedup /
+ * vn_set_batch_bic of that batch, a call with another `batch` than the previous one and vn_set_weights invalidate (f_k, g_k) and
+ * drop the ring -- vn_set_weights when the call finds other weights than (f_k, g_k) were evaluated with (weights changed and put
+ * back between two calls, as the monitors of VarNet.train do, leave the objective and therefore the optimizer alone).
+ * vn_state_export writes the two slots as zeros and vn_state_import ignores them; the ring is not part of a checkpoint. */
+int vn_lbfgs_step(vn_engine* h, int32_t batch, int32_t max_trials, double info[10]);
 
 /* ManageTrainData.splitLoss (VarNetUtility.py:1080-1088): out = {loss, BCloss, ICloss,
  * varLoss} (host doubles), lossVec_dev [n_k] or NULL.  Synchronises. */

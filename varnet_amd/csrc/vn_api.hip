@@ -3,6 +3,7 @@
 #include "vn_internal.h"
 #include "vn_dedup.h"
 #include "vn_flux.h"
+#include "vn_lbfgs.h"
 #include "vn_pgrad16.h"
 #include "vn_taylor16.h"
 #include "vn_split16.h"
@@ -170,6 +171,16 @@ struct vn_engine {
   bool eval_rowwise = false;   // vn_debug_point_route(route | 8): vn_eval_loss on the row-wise forward although the batch carries a de-duplication map
   bool no_gtable = false;      // vn_debug_point_route(route | 4): vn_set_dedup keeps the CSR-ordered copy of gcoef although it is periodic
 
+  // VN_OPT_LBFGS (vn_lbfgs_step): device buffers allocated at the first call; what the host knows of the optimizer's state
+  VnLbfgsBufs lb{};
+  bool lb_alloc = false;
+  bool lb_valid = false;       // (f_k, g_k) in lb.g_k belong to theta and to the objective as registered
+  bool lb_reset = true;        // the ring is dropped before the next direction
+  int32_t lb_batch = -1;
+  double lb_f[4] = {0, 0, 0, 0};   // loss, BC, IC, var at theta_k
+  double lb_w[3] = {0, 0, 0};      // loss weights (f_k, g_k) were evaluated with
+  float* lb_lossh = nullptr;   // [4] pinned host floats: a trial's loss scalars
+
   // tower gradient SUM over RCCL (vn_comm_init); nullptr = single process or host-side collective
   ncclComm_t comm = nullptr;
   int comm_world = 1, comm_rank = 0;
@@ -198,8 +209,9 @@ int build_net(const vn_config& c, VnNet& net) {
   if (c.integ_num < 1) return fail(VN_EINVAL, "integ_num must be positive");
   if (c.activation != VN_ACT_SIGMOID && c.activation != VN_ACT_TANH && c.activation != VN_ACT_PER_LAYER)
     return fail(VN_EUNSUPPORTED, "activation must be sigmoid or tanh (VarNet.py:97)");
-  if (c.optimizer != VN_OPT_ADAM && c.optimizer != VN_OPT_RMSPROP) return fail(VN_EINVAL, "unknown optimizer requested!");
-  if (c.lr < 0.0) return fail(VN_EINVAL, "learning rate must be positive!");  // TFModel.py:130
+  if (c.optimizer != VN_OPT_ADAM && c.optimizer != VN_OPT_RMSPROP && c.optimizer != VN_OPT_LBFGS)
+    return fail(VN_EINVAL, "unknown optimizer requested!");
+  if (c.optimizer != VN_OPT_LBFGS && c.lr < 0.0) return fail(VN_EINVAL, "learning rate must be positive!");  // TFModel.py:130
   if (c.optimizer == VN_OPT_ADAM) {
     // taken literally, never defaulted: a zero-initialised config (eps = 0: 0/0 in the update of a zero-gradient
     // parameter) is an error, not a NaN three steps later
@@ -324,6 +336,13 @@ inline const float* batch_src(const vn_engine* h, const Batch& b) { return h->cf
 inline const float* fe_w(const vn_engine* h) { return (h->cfg.has_integw && h->has_feW) ? h->feW : nullptr; }
 
 inline bool on_8wave(const vn_engine* h) { return h->route == Route::fused8 || h->route == Route::twopass; }
+
+// VN_OPT_LBFGS: the objective or the iterate changed behind the optimizer's back -- (f_k, g_k) are stale, the ring is dropped
+inline void lbfgs_invalidate(vn_engine* h) { h->lb_valid = false; h->lb_reset = true; }
+inline void lbfgs_invalidate(vn_engine* h, int32_t batch) { if (batch == h->lb_batch) lbfgs_invalidate(h); }
+inline bool is_lbfgs(const vn_engine* h) { return h->cfg.optimizer == VN_OPT_LBFGS; }
+#define NOT_LBFGS(name)                                                                                              \
+  if (is_lbfgs(h)) return fail(VN_ESTATE, name " is a first-order optimizer step: an L-BFGS engine (VN_OPT_LBFGS) advances by vn_lbfgs_step only")
 
 // ---- point kernels of the 8-wave family (vn_debug_point_route) ----------------------------
 // hidden widths 33..64: the products as six bf16-piece MFMAs, fp32-class (vn_split16.hip), unless route 2 asks for f32-MFMA
@@ -806,9 +825,11 @@ int vn_destroy(vn_engine* h) {
   if (h->comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(h->stream); (void)g_rccl.CommDestroy(h->comm); h->comm = nullptr; }
   void* ptrs[] = {h->theta, h->m, h->v, h->snap, h->theta64, h->gradbuf_int, h->lossbuf, h->partial, h->feN, h->fedNt,
                   h->feW, h->u, h->ud, h->ubar, h->udbar, h->ub, h->ubar_b, h->losspart, h->fused_losspart, h->stamps, h->dd_uv, h->dd_su, h->dd_sg, h->dd_partial,
-                  h->dd_losspart, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial};
+                  h->dd_losspart, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial,
+                  h->lb.ring, h->lb.theta_k, h->lb.g_k, h->lb.d, h->lb.part, h->lb.G, h->lb.coef, h->lb.meta};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  if (h->lb.out) (void)hipHostFree(h->lb.out);
   for (Batch& b : h->batches)
     if (b.gcsr) (void)hipFree(b.gcsr);
   for (auto e : h->ev0) if (e) (void)hipEventDestroy(e);
@@ -856,6 +877,7 @@ int vn_params_init(vn_engine* h, uint64_t seed) {
   }
   HIPCHK(hipStreamSynchronize(h->stream));
   h->step = 0;
+  lbfgs_invalidate(h);
   return VN_OK;
 }
 
@@ -874,6 +896,7 @@ int vn_params_set(vn_engine* h, const float* host, int64_t n) {
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipMemcpyAsync(h->theta, host, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  lbfgs_invalidate(h);
   return VN_OK;
 }
 
@@ -907,6 +930,7 @@ int vn_state_export(vn_engine* h, void* host, int64_t bytes) {
 // run ends in exactly the state the reference's one-read-back-per-epoch loop ends in (VarNet.py:1346-1383).
 int vn_state_snapshot(vn_engine* h) {
   if (!h) return fail(VN_EINVAL, "null handle");
+  NOT_LBFGS("vn_state_snapshot (the block read-back of Adam / RMSProp epochs)");
   HIPCHK(hipSetDevice(h->cfg.device));
   const size_t nb = (size_t)h->net.P * sizeof(float);
   if (!h->snap) HIPCHK(hipMalloc((void**)&h->snap, 3 * nb));
@@ -919,6 +943,7 @@ int vn_state_snapshot(vn_engine* h) {
 
 int vn_state_rollback(vn_engine* h) {
   if (!h) return fail(VN_EINVAL, "null handle");
+  NOT_LBFGS("vn_state_rollback (the block read-back of Adam / RMSProp epochs)");
   if (!h->snap || h->snap_step < 0) return fail(VN_ESTATE, "no snapshot to roll back to (call vn_state_snapshot first)");
   HIPCHK(hipSetDevice(h->cfg.device));
   const size_t nb = (size_t)h->net.P * sizeof(float);
@@ -940,9 +965,12 @@ int vn_state_import(vn_engine* h, const void* host, int64_t bytes) {
   p += sizeof(int64_t);
   const size_t nb = (size_t)h->net.P * sizeof(float);
   HIPCHK(hipMemcpyAsync(h->theta, p, nb, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->m, p + nb, nb, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->v, p + 2 * nb, nb, hipMemcpyHostToDevice, h->stream));
+  if (!is_lbfgs(h)) {          // L-BFGS has no slots: a checkpoint's are ignored (and exported as the zeros vn_create left)
+    HIPCHK(hipMemcpyAsync(h->m, p + nb, nb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->v, p + 2 * nb, nb, hipMemcpyHostToDevice, h->stream));
+  }
   HIPCHK(hipStreamSynchronize(h->stream));
+  lbfgs_invalidate(h);
   return VN_OK;
 }
 
@@ -972,6 +1000,7 @@ int vn_set_interior(vn_engine* h, int32_t batch, const float* Input, const float
   if ((N_rows == nullptr) != (dNt_rows == nullptr)) return fail(VN_EINVAL, "N_rows and dNt_rows must be given together");
   HIPCHK(hipSetDevice(h->cfg.device));
   if ((int)h->batches.size() <= batch) h->batches.resize(batch + 1);
+  lbfgs_invalidate(h, batch);
   Batch& b = h->batches[batch];
   b.Input = Input; b.gcoef = gcoef; b.source = source; b.detJv = detJ_dev; b.detJ = detJ;
   b.Nrow = N_rows; b.dNtrow = dNt_rows; b.n_k = n_k; b.set = true;
@@ -994,6 +1023,7 @@ int vn_set_dedup(vn_engine* h, int32_t batch, const float* Xu, int64_t U, const 
   if (!h) return fail(VN_EINVAL, "null handle");
   if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
     return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
+  lbfgs_invalidate(h, batch);
   Batch& b = h->batches[batch];
   if (!Xu) {                                   // switch the formulation off for this batch
     b.Xu = nullptr; b.uid = nullptr; b.rowptr = nullptr; b.rowidx = nullptr; b.U = 0;
@@ -1049,6 +1079,7 @@ int vn_set_bic(vn_engine* h, const float* biInput, const float* biLabel, int64_t
   // a steady problem has no initial condition (TFModel.py:646-650): rows behind bDof are never part of its loss
   if (!h->cfg.time_dependent) nB = bDof;
   h->biInput = biInput; h->biLabel = biLabel; h->nB = nB; h->bDof = bDof; h->biDimVal = biDimVal;
+  lbfgs_invalidate(h);
   if (nB > h->work_b) {
     long c0 = h->work_b, c1 = h->work_b;
     if (int rc = ensure(&h->ub, &c0, nB)) return rc;
@@ -1063,6 +1094,7 @@ int vn_set_flux_bc(vn_engine* h, const float* X, const float* normal, const floa
   if (!h) return fail(VN_EINVAL, "null handle");
   if (nF < 0) return fail(VN_EINVAL, "negative number of flux rows");
   h->fX = h->fN = h->fcoef = h->flabel = nullptr;   // a call replaces the previous registration, also when it fails
+  lbfgs_invalidate(h);
   h->nF = 0;
   if (nF == 0 || !X) return VN_OK;
   if (!normal || !coef || !label) return fail(VN_EINVAL, "null argument");
@@ -1092,12 +1124,13 @@ int vn_set_batch_bic(vn_engine* h, int32_t batch, const float* biInput, const fl
   if ((biInput == nullptr) != (biLabel == nullptr)) return fail(VN_EINVAL, "biInput and biLabel must be given together");
   h->batches[batch].biInput = biInput;
   h->batches[batch].biLabel = biLabel;
+  lbfgs_invalidate(h, batch);
   return VN_OK;
 }
 
 int vn_set_weights(vn_engine* h, const double w[3]) {
   if (!h || !w) return fail(VN_EINVAL, "null argument");
-  h->w[0] = w[0]; h->w[1] = w[1]; h->w[2] = w[2];
+  h->w[0] = w[0]; h->w[1] = w[1]; h->w[2] = w[2];   // (VN_OPT_LBFGS: vn_lbfgs_step compares them with those of its (f_k, g_k))
   return VN_OK;
 }
 
@@ -1145,6 +1178,7 @@ static int apply_impl(vn_engine* h, float* loss_acc) {
 
 int vn_apply(vn_engine* h) {
   if (!h) return fail(VN_EINVAL, "null handle");
+  NOT_LBFGS("vn_apply");
   return apply_impl(h, nullptr);
 }
 
@@ -1179,6 +1213,7 @@ static int step_fused(vn_engine* h, int32_t batch, float* loss_acc) {
 
 int vn_train_epoch(vn_engine* h, const int32_t* batches, int32_t n, float* loss_acc_dev) {
   if (!h || (n > 0 && !batches)) return fail(VN_EINVAL, "null argument");
+  NOT_LBFGS("vn_train_epoch");
   for (int32_t i = 0; i < n; ++i)
     if (int rc = step_fused(h, batches[i], loss_acc_dev)) return rc;
   return VN_OK;
@@ -1186,9 +1221,115 @@ int vn_train_epoch(vn_engine* h, const int32_t* batches, int32_t n, float* loss_
 
 int vn_train_step(vn_engine* h, int32_t batch, float* loss_out_dev) {
   if (!h) return fail(VN_EINVAL, "null handle");
+  NOT_LBFGS("vn_train_step");
   if (int rc = step_fused(h, batch, nullptr)) return rc;
   if (loss_out_dev)
     HIPCHK(hipMemcpyAsync(loss_out_dev, h->gradbuf + h->net.P, sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  return VN_OK;
+}
+
+// ---- L-BFGS (VN_OPT_LBFGS): one iteration above vn_grad -------------------------------------
+static int lbfgs_alloc(vn_engine* h) {
+  if (h->lb_alloc) return VN_OK;
+  const size_t P = (size_t)h->net.P;
+  VnLbfgsBufs& b = h->lb;
+  hipError_t a = hipMalloc((void**)&b.ring, 2 * (size_t)VN_LBFGS_SLOTS * P * sizeof(float));
+  if (a == hipSuccess) a = hipMalloc((void**)&b.theta_k, P * sizeof(float));
+  if (a == hipSuccess) a = hipMalloc((void**)&b.g_k, (P + 4) * sizeof(float));
+  if (a == hipSuccess) a = hipMalloc((void**)&b.d, P * sizeof(float));
+  if (a == hipSuccess) a = hipMalloc((void**)&b.part, (size_t)VN_LBFGS_MAXBLK * VN_LBFGS_NACC * sizeof(double));
+  if (a == hipSuccess) a = hipMalloc((void**)&b.G, (size_t)VN_LBFGS_NB * VN_LBFGS_NB * sizeof(double));
+  if (a == hipSuccess) a = hipMalloc((void**)&b.coef, (VN_LBFGS_NB + 1) * sizeof(double));
+  if (a == hipSuccess) a = hipMalloc((void**)&b.meta, sizeof(VnLbfgsMeta));
+  // host memory the one-wave kernel stores its scalars to, and the landing place of a trial's loss scalars
+  if (a == hipSuccess) a = hipHostMalloc((void**)&b.out, sizeof(VnLbfgsOut) + 4 * sizeof(float), hipHostMallocDefault);
+  if (a == hipSuccess) a = hipMemsetAsync(b.G, 0, (size_t)VN_LBFGS_NB * VN_LBFGS_NB * sizeof(double), h->stream);
+  if (a == hipSuccess) a = hipMemsetAsync(b.meta, 0, sizeof(VnLbfgsMeta), h->stream);
+  if (a != hipSuccess) {
+    (void)hipGetLastError();
+    void* ptrs[] = {b.ring, b.theta_k, b.g_k, b.d, b.part, b.G, b.coef, b.meta};
+    for (void* p : ptrs)
+      if (p) (void)hipFree(p);
+    if (b.out) (void)hipHostFree(b.out);
+    b = VnLbfgsBufs{};
+    return fail(VN_ENOMEM, "L-BFGS state (%d vectors of %zu parameters) does not fit: %s", 2 * VN_LBFGS_SLOTS + 3, P,
+                hipGetErrorString(a));
+  }
+  memset(b.out, 0, sizeof(VnLbfgsOut) + 4 * sizeof(float));
+  h->lb_lossh = (float*)(b.out + 1);
+  h->lb_alloc = true;
+  return VN_OK;
+}
+
+int vn_lbfgs_step(vn_engine* h, int32_t batch, int32_t max_trials, double info[10]) {
+  if (!h || !info) return fail(VN_EINVAL, "null argument");
+  if (!is_lbfgs(h))
+    return fail(VN_ESTATE, "vn_lbfgs_step needs an engine created with optimizer = VN_OPT_LBFGS (this one runs %s)",
+                h->cfg.optimizer == VN_OPT_RMSPROP ? "RMSProp" : "Adam");
+  if (h->comm)
+    return fail(VN_EUNSUPPORTED, "vn_lbfgs_step under a communicator: every rank would have to take the same accept decision "
+                                 "from an all-reduced loss, which is not built");
+  if (max_trials < 1) return fail(VN_EINVAL, "max_trials must be at least 1");
+  (void)hipGetLastError();
+  if (int rc = check_batch(h, batch)) return rc;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (int rc = lbfgs_alloc(h)) return rc;
+  const long P = h->net.P;
+  const VnLbfgsBufs& b = h->lb;
+  const size_t nb4 = 4 * sizeof(float);
+  if (batch != h->lb_batch) { lbfgs_invalidate(h); h->lb_batch = batch; }
+  // weights: what counts is the objective this call sees (train()'s monitors set unit weights and put the run's back)
+  if (h->w[0] != h->lb_w[0] || h->w[1] != h->lb_w[1] || h->w[2] != h->lb_w[2]) lbfgs_invalidate(h);
+  if (!h->lb_valid) {                       // an evaluation, not a trial
+    if (int rc = vn_grad(h, batch)) return rc;
+    HIPCHK(vn_lbfgs_commit_launch(b, h->theta, h->gradbuf, P, 1, h->stream));
+    HIPCHK(hipMemcpyAsync(h->lb_lossh, h->gradbuf + P, nb4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 4; ++i) h->lb_f[i] = (double)h->lb_lossh[i];
+    for (int i = 0; i < 3; ++i) h->lb_w[i] = h->w[i];
+    h->lb_valid = true;
+    h->lb_reset = true;
+  }
+  const int reset = h->lb_reset ? 1 : 0;
+  HIPCHK(vn_lbfgs_gram_launch(b, P, reset, h->stream));
+  HIPCHK(vn_lbfgs_twoloop_launch(b, P, reset, h->stream));
+  h->lb_reset = false;
+  const double fk = h->lb_f[0];
+  double scale = 1.0, t = 0.0, f[4] = {0, 0, 0, 0};
+  int used = 0;
+  bool accepted = false;
+  for (int j = 0; j < max_trials && !accepted; ++j, scale *= 0.5) {
+    HIPCHK(vn_lbfgs_trial_launch(b, h->theta, P, scale, j == 0, h->stream));
+    int rc = vn_grad(h, batch);
+    if (rc == VN_OK) {
+      hipError_t e = hipMemcpyAsync(h->lb_lossh, h->gradbuf + P, nb4, hipMemcpyDeviceToHost, h->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+      if (e != hipSuccess) rc = fail(VN_EHIP, "vn_lbfgs_step: %s", hipGetErrorString(e));
+    }
+    if (rc != VN_OK) {                      // theta goes back to theta_k; the message is the failed call's
+      (void)hipMemcpyAsync(h->theta, b.theta_k, (size_t)P * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
+      (void)hipStreamSynchronize(h->stream);
+      return rc;
+    }
+    used = j + 1;
+    t = b.out->t0 * scale;
+    for (int i = 0; i < 4; ++i) f[i] = (double)h->lb_lossh[i];
+    accepted = std::isfinite(f[0]) && f[0] <= fk + 1e-4 * t * b.out->gd;
+  }
+  const double pairs = b.out->pairs;
+  info[1] = fk; info[7] = (double)used; info[8] = b.out->gd; info[9] = pairs;
+  if (accepted) {
+    HIPCHK(vn_lbfgs_commit_launch(b, h->theta, h->gradbuf, P, 0, h->stream));
+    h->step += 1;
+    for (int i = 0; i < 4; ++i) h->lb_f[i] = f[i];
+    info[0] = 0.0; info[2] = f[0]; info[3] = f[1]; info[4] = f[2]; info[5] = f[3]; info[6] = t;
+    return VN_OK;
+  }
+  // no trial accepted: theta_k back bit for bit; with pairs the next call is a steepest-descent iteration, without: stalled
+  HIPCHK(hipMemcpyAsync(h->theta, b.theta_k, (size_t)P * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  if (pairs > 0.0) h->lb_reset = true;
+  info[0] = pairs > 0.0 ? 1.0 : 2.0;
+  info[2] = fk; info[3] = h->lb_f[1]; info[4] = h->lb_f[2]; info[5] = h->lb_f[3]; info[6] = 0.0;
   return VN_OK;
 }
 

@@ -24,6 +24,9 @@ VN_MAX_WIDTH = 2048         # (6 layers x 64 wide, 8 inputs) the engine runs lay
 VN_MAX_DIN = 32
 VN_KMAX_LAYERS, VN_KMAX_WIDTH, VN_KMAX_DIN = 6, 64, 8
 VN_KERNEL_AUTO, VN_KERNEL_GENERIC, VN_KERNEL_FUSED, VN_KERNEL_FUSED16, VN_KERNEL_LAYERED = 0, 1, 2, 3, 4
+VN_OPT_ADAM, VN_OPT_RMSPROP, VN_OPT_LBFGS = 0, 1, 2
+VN_LBFGS_HISTORY = 10
+LBFGS_INFO = ('status', 'f_k', 'f_next', 'BCloss', 'ICloss', 'varLoss', 't', 'trials', 'gd', 'pairs')
 VN_COMM_ID_BYTES = 128
 VN_ABI_VERSION = 7          # include/varnet_hip.h: load_library refuses a library that reports another number
 
@@ -66,6 +69,7 @@ _SIGS = {
     'vn_apply': (C.c_int, [C.c_void_p]),
     'vn_train_step': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     'vn_train_epoch': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
+    'vn_lbfgs_step': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     'vn_eval_loss': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_void_p]),
     'vn_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'vn_forward_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -211,7 +215,7 @@ class VNEngine:
         acts = [str(a).lower() for a in acts]
         if any(a not in ('sigmoid', 'tanh') for a in acts):
             raise ValueError('activation function must be \'sigmoid\' or \'tanh\' (VarNet.py:97)')
-        if optimizer_name.lower() not in ('adam', 'rmsprop'):
+        if optimizer_name.lower() not in ('adam', 'rmsprop', 'lbfgs'):
             raise ValueError('unknown optimizer requested!')           # TFModel.py:133-134
         if learning_rate < 0.0:
             raise ValueError('learning rate must be positive!')        # TFModel.py:130
@@ -233,7 +237,8 @@ class VNEngine:
         cfg.has_source = int(bool(isSource))
         cfg.has_integw = int(bool(integWflag))
         cfg.device = int(device)
-        cfg.optimizer = 1 if optimizer_name.lower() == 'rmsprop' else 0
+        cfg.optimizer = {'adam': VN_OPT_ADAM, 'rmsprop': VN_OPT_RMSPROP, 'lbfgs': VN_OPT_LBFGS}[optimizer_name.lower()]
+        self.optimizer_name = optimizer_name.lower()
         cfg.kernel = kernel
         cfg.lr, cfg.beta1, cfg.beta2, cfg.eps = learning_rate, 0.9, 0.999, 1e-8
         self.cfg = cfg
@@ -458,6 +463,17 @@ class VNEngine:
             if isinstance(batches, tuple) and len(self._epoch_arrays) < 4096:
                 self._epoch_arrays[batches] = arr
         self._ck(self.lib.vn_train_epoch(self.h, arr, len(batches), _ptr(loss_acc)))
+
+    def lbfgs_step(self, batch=0, max_trials=20):
+        """One L-BFGS iteration on the objective `grad(batch)` (vn_lbfgs_step; engines made with optimizer_name='lbfgs').
+        Returns the `info` fields by name (LBFGS_INFO): status 0 accepted, 1 no trial accepted and the ring dropped, 2 stalled;
+        f_k, f_next and the components at the new parameters, the accepted step t, trials used, g.d, pairs in the ring."""
+        out = (C.c_double * 10)()
+        self._ck(self.lib.vn_lbfgs_step(self.h, int(batch), int(max_trials), out))
+        info = dict(zip(LBFGS_INFO, out))
+        for k in ('status', 'trials', 'pairs'):
+            info[k] = int(info[k])
+        return info
 
     def eval_loss(self, batch=0, lossVec=False):
         out = (C.c_double * 4)()

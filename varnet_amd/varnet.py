@@ -309,9 +309,12 @@ class TrainResult:
         else:
             L.append('\tutilized processor: GPU:0\n\n')
         L.append('Optimizer information:\n')
-        L.append('\ttype: %s stochastic gradient descent algorithm\n'
-                 % ('RMSProp' if str(varNet.optimizer).lower() == 'rmsprop' else 'Adam'))
-        L.append('\tlearning rate: ' + str(varNet.learning_rate) + '\n\n')
+        if str(varNet.optimizer).lower() == 'lbfgs':
+            L.append('\ttype: L-BFGS quasi-Newton algorithm (history 10, backtracking Armijo line search)\n\n')
+        else:
+            L.append('\ttype: %s stochastic gradient descent algorithm\n'
+                     % ('RMSProp' if str(varNet.optimizer).lower() == 'rmsprop' else 'Adam'))
+            L.append('\tlearning rate: ' + str(varNet.learning_rate) + '\n\n')
         L.append('Space-time discretization information:\n')
         L.append('\tspatial domain interior discretization number: ' + str(varNet.discNum) + '\n')
         L.append('\tspatial domain boundary discretization density: ' + str(varNet.bDiscNum) + '\n')
@@ -795,7 +798,7 @@ class VarNet:
             raise ValueError('learning rate must be positive!')
         if optimizer.lower() == 'rms':
             optimizer = 'rmsprop'
-        if optimizer.lower() not in ('adam', 'rmsprop'):
+        if optimizer.lower() not in ('adam', 'rmsprop', 'lbfgs'):
             raise ValueError('unknown optimizer requested!')
         if fluxBC and MORvar is not None:
             raise NotImplementedError('fluxBC=True with model-order reduction is not supported: the flux rows carry one label '
@@ -1330,6 +1333,13 @@ class VarNet:
         device scalar `loss_acc`."""
         eng = self.engine
         P = eng.P
+        if self._is_lbfgs():
+            # one L-BFGS iteration (train() has refused everything but one full batch); the epoch's loss is f_k, the loss at
+            # the parameters the epoch started from, as an Adam epoch records its pre-update loss
+            info = eng.lbfgs_step(tData.engine_batch(mb, 0))
+            self._lbfgs_info = info
+            loss_acc += float(info['f_k'])
+            return
         if (self.world == 1 or self.comm == 'rccl') and hasattr(eng, 'train_epoch'):
             # the whole pass in one host call (no per-mini-batch Python / launch-queue gaps); with towers the
             # engine's own RCCL communicator sums the gradient between the two kernels
@@ -1346,6 +1356,26 @@ class VarNet:
             self._allreduce(gb)
             eng.apply()
             loss_acc += gb[P]
+
+    def _is_lbfgs(self):
+        return str(self.optimizer).lower() == 'lbfgs'
+
+    def _lbfgs_refusals(self, batchNum, batchLen, shuffleData):
+        """optimizer='lbfgs' builds its curvature pairs from consecutive gradients of ONE objective: whatever makes consecutive
+        iterations see different ones is refused, with its reason."""
+        fd = self.fixData
+        if self.world > 1 or self._towers is not None:
+            raise ValueError('optimizer=\'lbfgs\' runs on one rank: with towers every rank would have to take the same '
+                             'line-search decision from an all-reduced loss, which is not built')
+        many = (batchNum is not None and int(batchNum) > 1) or (batchLen is not None and int(batchLen) < fd.nt)
+        if many:
+            raise ValueError('optimizer=\'lbfgs\' needs the full batch (batchNum / batchLen give more than one mini-batch): '
+                             'consecutive iterations would see different objectives')
+        if shuffleData:
+            raise ValueError('optimizer=\'lbfgs\' with shuffleData=True: a shuffle changes the objective between iterations')
+        if fd.MORbatchNum > 1:
+            raise ValueError('optimizer=\'lbfgs\' with %d MOR batches: consecutive iterations would see different objectives'
+                             % fd.MORbatchNum)
 
     def _choose_formulation(self, tData, dedup, shuffleData=False):
         """Apply `train(dedup=...)` to a training set; returns {'requested', 'on', 'unique_points', 'reason'} and records the
@@ -1387,6 +1417,8 @@ class VarNet:
               dedup='auto', lossLag=None):
         """Training loop of /root/reference/VarNet.py:1197-1421 (uniform, random and residual-driven
         "optimal" sampling with re-initialisation and re-weighting)."""
+        if self._is_lbfgs():
+            self._lbfgs_refusals(batchNum, batchLen, shuffleData)
         if self._towers is not None:                  # controller of forked towers: every tower runs the loop
             kw = {k: v for k, v in locals().items() if k not in ('self', 'folderpath')}
             self.folderpath = folderpath
@@ -1460,7 +1492,9 @@ class VarNet:
         # steps are bitwise reproducible): same losses, same checkpoints, same final parameters and step count as k = 0
         # (tests/test_varnet_host.py::test_loss_lag_is_only_a_readback_schedule).  Default (None): 8 with an engine that can
         # snapshot, else 0.
-        can_snap = hasattr(eng, 'state_snapshot')
+        can_snap = hasattr(eng, 'state_snapshot') and not self._is_lbfgs()
+        if self._is_lbfgs():
+            lossLag = 0                                           # every L-BFGS iteration ends in a read-back anyway
         if lossLag is None:
             lossLag = 8 if can_snap else 0
         # Non-uniform sampling: the re-draw test of VarNet.py:1385-1421 runs after every epoch, but what it looks at -- the losses
@@ -1548,6 +1582,18 @@ class VarNet:
                         print('Training completed!')
                     done = True
                     break
+                if self._is_lbfgs() and self._lbfgs_info['status'] != 0:
+                    if self._lbfgs_info['status'] == 1:
+                        trainRes.writeCase('epoch %d: L-BFGS line search found no acceptable step, history dropped '
+                                           '(the next iteration is a steepest-descent one).' % epoch)
+                    else:
+                        msg = ('epoch %d: L-BFGS stalled (no acceptable step along the steepest-descent direction), '
+                               'training ended.' % epoch)
+                        trainRes.writeCase(msg)
+                        if verbose and self.rank == 0:
+                            print(msg)
+                        done = True
+                        break
 
                 # regenerate the training set (VarNet.py:1385-1421)
                 if smpScheme != 'uniform' and (multiTrainUpd or tp_updates == 0) and (epoch - tp_epoch) >= (trainUpdelay - 1):
