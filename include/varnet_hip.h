@@ -243,10 +243,36 @@ int vn_train_epoch(vn_engine* h, const int32_t* batches, int32_t n, float* loss_
  * back between two calls, as the monitors of VarNet.train do, leave the objective and therefore the optimizer alone).
  * vn_state_export writes the two slots as zeros and vn_state_import ignores them; the ring is not part of a checkpoint. */
 int vn_lbfgs_step(vn_engine* h, int32_t batch, int32_t max_trials, double info[10]);
+/* OPTIONAL, default off: with `on` != 0 vn_lbfgs_step takes f_k and each trial's loss (and the BC, IC, var it reports) from the
+ * loss-only form of vn_objective_f64 at the trial point -- a 32-byte read-back of doubles instead of 16 bytes of floats -- so the
+ * Armijo test is not limited by the resolution of an fp32 loss.  The gradient, the direction, the ring and every other rule above
+ * are unchanged; with it off vn_lbfgs_step is bitwise what it is without this call.  A change of the flag invalidates (f_k, g_k).
+ * VN_ESTATE on Adam / RMSProp engines; VN_EUNSUPPORTED where vn_objective_f64 is. */
+int vn_lbfgs_loss64(vn_engine* h, int on);
 
 /* ManageTrainData.splitLoss (VarNetUtility.py:1080-1088): out = {loss, BCloss, ICloss,
  * varLoss} (host doubles), lossVec_dev [n_k] or NULL.  Synchronises. */
 int vn_eval_loss(vn_engine* h, int32_t batch, double out[4], float* lossVec_dev);
+
+/* OPTIONAL, no reference counterpart: the objective of vn_grad(batch) in double precision.
+ * Exactly the objective vn_grad / vn_eval_loss define for the batch as registered -- interior rows (per-row N_rows / dNt_rows,
+ * per-test-function detJ_dev, n_k == 0 included), FE table, integW, source term, the BC/IC rows of vn_set_bic or the batch's own
+ * vn_set_batch_bic copy, the flux rows of vn_set_flux_bc, the weights of vn_set_weights, steady or time-dependent -- with the
+ * registered fp32 arrays widened exactly and everything after that in fp64: layer products (fp64 matrix pipe), exp / tanh and
+ * the division, quadrature sums, squares and means, the reverse pass, and every reduction in a fixed order without
+ * floating-point atomics (two calls return the same bits).  A de-duplication map on the batch is ignored: the row-wise sum is
+ * evaluated (the two formulations are the same mathematics).
+ *   theta_dev    P doubles on the device, or NULL: the engine's own fp32 parameters, widened
+ *   grad_dev     P doubles, d loss / d theta, or NULL: loss only (no reverse launch is enqueued)
+ *   lossVec_dev  n_k doubles, or NULL
+ *   out          {loss, BC, IC, var} as host doubles
+ * Synchronises, like vn_eval_loss.  Changes no engine state (parameters, optimizer slots, step counter, gradient buffer, the
+ * L-BFGS validity flags, the communicator) and issues no collective.
+ * Range: 1..6 hidden layers of width <= 64 (ragged widths included), d_in <= 8, dim <= 3, one activation (sigmoid or tanh), any
+ * integ_num; networks outside VN_KMAX_* (the layer-by-layer route, 7-8 hidden layers, mixed activations): VN_EUNSUPPORTED.
+ * An unregistered batch: VN_ESTATE; out == NULL: VN_EINVAL. */
+int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev,
+                     double* grad_dev, double* lossVec_dev, double out[4]);
 
 /* runSession(['model']) (VarNetUtility.py:1123-1128,1142; VarNet.py:1930): u = model(X). */
 int vn_forward(vn_engine* h, const float* X_dev, int64_t n, float* u_dev);

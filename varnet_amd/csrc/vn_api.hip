@@ -4,6 +4,7 @@
 #include "vn_dedup.h"
 #include "vn_flux.h"
 #include "vn_lbfgs.h"
+#include "vn_obj64.h"
 #include "vn_pgrad16.h"
 #include "vn_taylor16.h"
 #include "vn_split16.h"
@@ -180,6 +181,9 @@ struct vn_engine {
   double lb_f[4] = {0, 0, 0, 0};   // loss, BC, IC, var at theta_k
   double lb_w[3] = {0, 0, 0};      // loss weights (f_k, g_k) were evaluated with
   float* lb_lossh = nullptr;   // [4] pinned host floats: a trial's loss scalars
+  bool lb_loss64 = false;      // vn_lbfgs_loss64: f_k and every trial's loss from the loss-only form of vn_objective_f64
+
+  VnObj64Work o64{};           // vn_objective_f64: work buffers, allocated at the first call
 
   // tower gradient SUM over RCCL (vn_comm_init); nullptr = single process or host-side collective
   ncclComm_t comm = nullptr;
@@ -830,6 +834,7 @@ int vn_destroy(vn_engine* h) {
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->lb.out) (void)hipHostFree(h->lb.out);
+  vn_obj64_free(h->o64);
   for (Batch& b : h->batches)
     if (b.gcsr) (void)hipFree(b.gcsr);
   for (auto e : h->ev0) if (e) (void)hipEventDestroy(e);
@@ -1286,6 +1291,8 @@ int vn_lbfgs_step(vn_engine* h, int32_t batch, int32_t max_trials, double info[1
     HIPCHK(hipMemcpyAsync(h->lb_lossh, h->gradbuf + P, nb4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int i = 0; i < 4; ++i) h->lb_f[i] = (double)h->lb_lossh[i];
+    if (h->lb_loss64)
+      if (int rc = vn_objective_f64(h, batch, nullptr, nullptr, nullptr, h->lb_f)) return rc;
     for (int i = 0; i < 3; ++i) h->lb_w[i] = h->w[i];
     h->lb_valid = true;
     h->lb_reset = true;
@@ -1306,6 +1313,8 @@ int vn_lbfgs_step(vn_engine* h, int32_t batch, int32_t max_trials, double info[1
       if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
       if (e != hipSuccess) rc = fail(VN_EHIP, "vn_lbfgs_step: %s", hipGetErrorString(e));
     }
+    double f64[4] = {0, 0, 0, 0};
+    if (rc == VN_OK && h->lb_loss64) rc = vn_objective_f64(h, batch, nullptr, nullptr, nullptr, f64);   // at the trial point
     if (rc != VN_OK) {                      // theta goes back to theta_k; the message is the failed call's
       (void)hipMemcpyAsync(h->theta, b.theta_k, (size_t)P * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
       (void)hipStreamSynchronize(h->stream);
@@ -1313,7 +1322,7 @@ int vn_lbfgs_step(vn_engine* h, int32_t batch, int32_t max_trials, double info[1
     }
     used = j + 1;
     t = b.out->t0 * scale;
-    for (int i = 0; i < 4; ++i) f[i] = (double)h->lb_lossh[i];
+    for (int i = 0; i < 4; ++i) f[i] = h->lb_loss64 ? f64[i] : (double)h->lb_lossh[i];
     accepted = std::isfinite(f[0]) && f[0] <= fk + 1e-4 * t * b.out->gd;
   }
   const double pairs = b.out->pairs;
@@ -1333,6 +1342,21 @@ int vn_lbfgs_step(vn_engine* h, int32_t batch, int32_t max_trials, double info[1
   return VN_OK;
 }
 
+int vn_lbfgs_loss64(vn_engine* h, int on) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (!is_lbfgs(h))
+    return fail(VN_ESTATE, "vn_lbfgs_loss64 needs an engine created with optimizer = VN_OPT_LBFGS (this one runs %s)",
+                h->cfg.optimizer == VN_OPT_RMSPROP ? "RMSProp" : "Adam");
+  if (on && !vn_obj64_supported(h->net))
+    return fail(VN_EUNSUPPORTED, "vn_lbfgs_loss64: the fp64 objective (vn_objective_f64) does not serve this network (%d layers, "
+                "widest %d, %d inputs, dim %d%s): it is outside the range of the hand-written kernels", h->net.L, h->net.hmax,
+                h->net.d_in, h->net.dim, h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+  const bool want = on != 0;
+  if (want != h->lb_loss64) lbfgs_invalidate(h);     // f_k was measured in the other precision
+  h->lb_loss64 = want;
+  return VN_OK;
+}
+
 int vn_eval_loss(vn_engine* h, int32_t batch, double out[4], float* lossVec_dev) {
   if (!h || !out) return fail(VN_EINVAL, "null argument");
   (void)hipGetLastError();   // a stale last-error of another library on this thread is not ours to report
@@ -1345,6 +1369,38 @@ int vn_eval_loss(vn_engine* h, int32_t batch, double out[4], float* lossVec_dev)
   HIPCHK(hipMemcpyAsync(t, h->lossbuf, sizeof t, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   for (int i = 0; i < 4; ++i) out[i] = (double)t[i];
+  return VN_OK;
+}
+
+int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, double* grad_dev, double* lossVec_dev, double out[4]) {
+  if (!h || !out) return fail(VN_EINVAL, "null argument");
+  (void)hipGetLastError();   // a stale last-error of another library on this thread is not ours to report
+  if (int rc = check_batch(h, batch)) return rc;
+  if (!vn_obj64_supported(h->net))
+    return fail(VN_EUNSUPPORTED, "vn_objective_f64 serves networks of the hand-written kernels (<= %d hidden layers, width <= %d, <= %d "
+                "inputs, dim <= 3, one activation); this one (%d layers, widest %d, %d inputs, dim %d%s) is outside that range",
+                VN_KMAX_LAYERS, VN_KMAX_WIDTH, VN_KMAX_DIN, h->net.L, h->net.hmax, h->net.d_in, h->net.dim,
+                h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (!theta_dev) {
+    if (int rc = refresh_theta64(h)) return rc;
+    theta_dev = h->theta64;
+  }
+  const Batch& b = h->batches[batch];
+  VnObj64Problem p{};
+  p.net = h->net; p.theta = theta_dev;
+  p.X = b.Input; p.G = b.gcoef; p.src = batch_src(h, b);
+  p.feN = h->feN; p.fedNt = h->fedNt; p.feW = fe_w(h);
+  p.Nrow = b.Nrow; p.dNtrow = b.dNtrow; p.detJv = b.detJv; p.detJ = b.detJ;
+  p.n_k = b.n_k; p.q = h->cfg.integ_num; p.td = h->cfg.time_dependent;
+  p.Xb = bi_x(h, b); p.label = bi_y(h, b); p.nB = h->nB; p.bDof = h->bDof; p.biDimVal = h->biDimVal;
+  p.Xf = h->fX; p.Nf = h->fN; p.fcoef = h->fcoef; p.flabel = h->flabel; p.nF = h->nF; p.fbiDimVal = h->fbiDimVal;
+  p.w[0] = h->w[0]; p.w[1] = h->w[1]; p.w[2] = h->w[2];
+  hipError_t e = vn_obj64_run(h->o64, p, grad_dev, lossVec_dev, out, h->ncu, h->stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(h->stream);
+    return fail(e == hipErrorOutOfMemory ? VN_ENOMEM : VN_EHIP, "vn_objective_f64: %s", hipGetErrorString(e));
+  }
   return VN_OK;
 }
 

@@ -1,0 +1,37 @@
+// The training objective of a batch and its gradient in double precision (vn_objective_f64): vn_obj64.hip.  Kept out of
+// vn_internal.h, which every kernel's source hash covers.
+#pragma once
+#include "vn_internal.h"
+
+// Engine-owned work buffers of the evaluation, sized at the call that first needs them and released by vn_obj64_free.
+struct VnObj64Work {
+  double* img = nullptr;   long img_cap = 0;     // zero-padded weight images of theta
+  double* u = nullptr;     long u_cap = 0;       // [rows]: forward values, then the value seeds in place
+  double* ud = nullptr;    long ud_cap = 0;      // [rows]: directional derivatives, then the tangent seeds in place
+  double* act = nullptr;   long act_cap = 0;     // [waves][L][2][16][64]: a wave's activations of its current chunk
+  double* part = nullptr;  long part_cap = 0;    // [waves][gradient image]
+  double* lpart = nullptr; long lpart_cap = 0;   // [seed blocks][4]: var, bc, ic, flux partial sums
+  double* out = nullptr;                         // [4] loss, BC, IC, var
+};
+
+// What the evaluation reads: the batch as registered (fp32 device arrays, widened exactly by the kernels).
+struct VnObj64Problem {
+  VnNet net;
+  const double* theta;                                   // [P] device
+  // interior rows
+  const float* X; const float* G; const float* src;      // [n_k*q, d_in], [n_k*q, dim], [n_k*q] or nullptr
+  const float* feN; const float* fedNt; const float* feW;
+  const float* Nrow; const float* dNtrow; const float* detJv;
+  double detJ; long n_k; int q; int td;
+  // BC / IC rows
+  const float* Xb; const float* label; long nB, bDof; double biDimVal;
+  // boundary-flux rows
+  const float* Xf; const float* Nf; const float* fcoef; const float* flabel; long nF; double fbiDimVal;
+  double w[3];
+};
+
+bool vn_obj64_supported(const VnNet& net);
+// loss components into out_host[4]; grad_dev [P] and lossVec_dev [n_k] optional.  Synchronises the stream.
+hipError_t vn_obj64_run(VnObj64Work& w, const VnObj64Problem& p, double* grad_dev, double* lossVec_dev, double out_host[4],
+                        int ncu, hipStream_t s);
+void vn_obj64_free(VnObj64Work& w);

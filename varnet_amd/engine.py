@@ -70,7 +70,9 @@ _SIGS = {
     'vn_train_step': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     'vn_train_epoch': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
     'vn_lbfgs_step': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
+    'vn_lbfgs_loss64': (C.c_int, [C.c_void_p, C.c_int]),
     'vn_eval_loss': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_void_p]),
+    'vn_objective_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'vn_forward_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'vn_debug_calibrate': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
@@ -475,7 +477,33 @@ class VNEngine:
             info[k] = int(info[k])
         return info
 
-    def eval_loss(self, batch=0, lossVec=False):
+    def lbfgs_loss64(self, on=True):
+        """L-BFGS engines: take f_k and every trial's loss of lbfgs_step from the fp64 objective (vn_lbfgs_loss64); default off."""
+        self._ck(self.lib.vn_lbfgs_loss64(self.h, 1 if on else 0))
+
+    def objective64(self, batch=0, theta=None, grad=True, lossVec=False):
+        """The objective of `grad(batch)` and its gradient in double precision on the device (vn_objective_f64).
+        theta: float64 tensor of P entries, or None for the engine's own parameters widened.  Returns
+        ([loss, BC, IC, var], gradient [P] float64 or None, lossVec [n_k] float64 or None).  Changes no engine state."""
+        t = self.torch
+        out = (C.c_double * 4)()
+        th = None
+        if theta is not None:
+            th = self.dev(theta, t.float64).reshape(-1)
+            if th.numel() != self.P:
+                raise ValueError('theta must hold P = %d entries, got %d' % (self.P, th.numel()))
+        g = t.empty(self.P, dtype=t.float64, device=self.device) if grad else None
+        lv = None
+        if lossVec:
+            n_k = self._keep[('int', batch)][0].shape[0] // self.integNum
+            lv = t.empty(n_k, dtype=t.float64, device=self.device)
+        self._ck(self.lib.vn_objective_f64(self.h, int(batch), _ptr(th), _ptr(g), _ptr(lv), out))
+        return list(out), g, lv
+
+    def eval_loss(self, batch=0, lossVec=False, fp64=False):
+        if fp64:
+            out, _, lv = self.objective64(batch, grad=False, lossVec=lossVec)
+            return out, lv
         out = (C.c_double * 4)()
         lv = None
         if lossVec:

@@ -770,7 +770,7 @@ class ManageTrainData:
 class VarNet:
     def __init__(self, PDE, layerWidth=[20], modelId='MLP', activationFun=None, discNum=20,
                  bDiscNum=[], tDiscNum=[], MORdiscScheme=None, processors=None, controller=None,
-                 integPnum=2, optimizer='adam', learning_rate=0.001, fluxBC=False):
+                 integPnum=2, optimizer='adam', learning_rate=0.001, fluxBC=False, lbfgsLoss64=False):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -800,6 +800,8 @@ class VarNet:
             optimizer = 'rmsprop'
         if optimizer.lower() not in ('adam', 'rmsprop', 'lbfgs'):
             raise ValueError('unknown optimizer requested!')
+        if lbfgsLoss64 and optimizer.lower() != 'lbfgs':
+            raise ValueError('lbfgsLoss64=True is an option of optimizer=\'lbfgs\' (the line search on the fp64 loss)')
         if fluxBC and MORvar is not None:
             raise NotImplementedError('fluxBC=True with model-order reduction is not supported: the flux rows carry one label '
                                       'g/a per boundary point, shared by all batches, while a MOR problem needs per-batch labels '
@@ -818,6 +820,7 @@ class VarNet:
         self.activationFun, self.optimizer, self.learning_rate = activationFun, optimizer, learning_rate
         self.processors, self.controller = processors, controller
         self.fluxBC, self.fluxRows = bool(fluxBC), None
+        self.lbfgsLoss64 = bool(lbfgsLoss64)
 
         self.fixData = FIXData(self, integPnum)
         self.fixData.setInputData(self)
@@ -839,7 +842,7 @@ class VarNet:
             kw = dict(layerWidth=layerWidth, modelId=modelId, activationFun=activationFun, discNum=discNum,
                       bDiscNum=bDiscNum, tDiscNum=tDiscNum, MORdiscScheme=MORdiscScheme, processors=list(processors),
                       controller=controller, integPnum=integPnum, optimizer=optimizer, learning_rate=learning_rate,
-                      fluxBC=fluxBC)
+                      fluxBC=fluxBC, lbfgsLoss64=lbfgsLoss64)
             self._towers = TowerGroup(type(self), (PDE,), kw, list(processors))
             self.world = self._towers.world
             self.engine = self.tfData = None
@@ -847,6 +850,8 @@ class VarNet:
         self._rng = np.random.default_rng(12345)
         self.engine = self._make_engine(processors)
         self.engine.init_params(seed=0)
+        if self.lbfgsLoss64:
+            self.engine.lbfgs_loss64(True)      # refused (VNError) where the fp64 objective is
         # tower gradient SUM (TFModel.py:342-377): by default an RCCL communicator inside the engine, so a
         # step is gradient -> all-reduce -> optimizer on one stream with one host call; VN_COMM=torch keeps the
         # collective in torch.distributed (three host calls per step)
@@ -1272,8 +1277,19 @@ class VarNet:
             cols.append(parts[pu][:n1 - n0])
         return torch.cat(cols).cpu().numpy().reshape(-1, 1)
 
-    def splitLoss(self, tData, W=None):
-        """BC, IC and variational loss summed over MOR batches (VarNet.py:1053-1090)."""
+    def _refuse_fp64_on_towers(self, what):
+        if self._towers is not None:
+            raise NotImplementedError(
+                '%s: the fp64 objective is evaluated by the process that owns the engine and the training set; this instance is '
+                'the controller of forked towers and holds neither.  Build the instance with one processor (or call it on a '
+                'rank of a launched job) to evaluate in double precision -- an fp32 result is never returned in its place' % what)
+
+    def splitLoss(self, tData, W=None, fp64=False):
+        """BC, IC and variational loss summed over MOR batches (VarNet.py:1053-1090).  fp64=True: the components (and the loss
+        field) from the device's double-precision evaluation of the same objective (VNEngine.objective64)."""
+        if fp64:
+            self._refuse_fp64_on_towers('splitLoss(fp64=True)')
+        ekw = {'fp64': True} if fp64 else {}
         if W is None:
             W = np.eye(3)
         eng, fd = self.engine, self.fixData
@@ -1285,7 +1301,7 @@ class VarNet:
             var = 0.0
             lv_b = []
             for bi in range(tData.batchNum):
-                out, lv = eng.eval_loss(tData.engine_batch(mb, bi), lossVec=fd.lossVecflag)
+                out, lv = eng.eval_loss(tData.engine_batch(mb, bi), lossVec=fd.lossVecflag, **ekw)
                 bc, ic = out[1], out[2]
                 var += out[3]
                 if lv is not None:
@@ -1298,6 +1314,60 @@ class VarNet:
             if lossVec is not None and lv_b:
                 lossVec.append(np.vstack(lv_b))
         return np.matmul(W, comp), tData, lossVec
+
+    def precisionReport(self, tData=None):
+        """How far the fp32 training step is from a double-precision evaluation of the same objective, at the current
+        parameters and on the training set `tData` (default: the set of the last train() call, else a freshly built full-batch set).
+        Per mini-batch the fp32 gradient call (VNEngine.grad: the step train() runs, on the route and formulation recorded
+        below) is compared with VNEngine.objective64; the sums over the mini-batches are judged:
+            'loss'        {loss, BCloss, ICloss, varLoss: |f32 - f64| / |f64|}
+            'grad_global' ||g32 - g64||_inf / ||g64||_inf
+            'grad_blocks' {parameter tensor: max|g32 - g64| over the tensor / max(||g64 tensor||_inf, 1e-7 ||g64||_inf)}
+            'route'       kernel family of the fp32 side (vn_kernel_path), 'two_pass', 'dedup' (the formulation: dedup_on)
+            'fp32', 'fp64' the summed components themselves, 'batches' the number of mini-batches.
+        Diagnostic only: nothing in train() calls it, and it leaves parameters and optimizer state as they are."""
+        self._refuse_fp64_on_towers('precisionReport')
+        if self.world > 1:
+            raise NotImplementedError('precisionReport compares one rank\'s step with its fp64 evaluation: run it on one rank')
+        if tData is None:
+            tData = getattr(self, 'tData', None) or self._build_tdata()
+        eng, fd = self.engine, self.fixData
+        P = eng.P
+        gb = eng.bind_grad_buffer()
+        f32, f64 = np.zeros(4), np.zeros(4)
+        g32, g64 = np.zeros(P), np.zeros(P)
+        nb = 0
+        for mb in range(fd.MORbatchNum):
+            tData.select_mor(mb)
+            for bi in range(tData.batchNum):
+                b = tData.engine_batch(mb, bi)
+                eng.grad(b)
+                a = gb.detach().cpu().numpy().astype(np.float64)
+                out, g, _ = eng.objective64(b, grad=True)
+                g32 += a[:P]
+                f32 += a[P:P + 4]
+                g64 += g.detach().cpu().numpy().astype(np.float64)
+                f64 += np.asarray(out, dtype=np.float64)
+                nb += 1
+        rel = lambda x, y: abs(x - y) / max(abs(y), 1e-300)
+        names = ['loss', 'BCloss', 'ICloss', 'varLoss']
+        scale = max(float(np.max(np.abs(g64))), 1e-300)
+        blocks, off, fan = {}, 0, self.inpDim
+        for l, h in enumerate(list(self.layerWidth) + [1]):
+            tag = 'o' if l == len(self.layerWidth) else str(l + 1)
+            for name, n in (('W' + tag, fan * h), ('b' + tag, h)):
+                s = slice(off, off + n)
+                blocks[name] = float(np.max(np.abs(g32[s] - g64[s]))) / max(float(np.max(np.abs(g64[s]))), 1e-7 * scale)
+                off += n
+            fan = h
+        kp = eng.kernel_path() if hasattr(eng, 'kernel_path') else (None, None)
+        fam = {0: 'auto', 1: 'generic', 2: 'fused (4-wave)', 3: 'fused16 (8-wave)', 4: 'layered'}
+        return {'loss': {k: rel(f32[i], f64[i]) for i, k in enumerate(names)},
+                'grad_global': float(np.max(np.abs(g32 - g64))) / scale,
+                'grad_blocks': blocks,
+                'route': fam.get(kp[0], kp[0]), 'kernel': kp[0], 'two_pass': bool(kp[1]) if kp[1] is not None else None,
+                'dedup': bool(getattr(tData, 'dedup_on', False)),
+                'fp32': dict(zip(names, f32.tolist())), 'fp64': dict(zip(names, f64.tolist())), 'batches': nb}
 
     def trainWeight(self, weight, tData, normalizeW=False, useOriginalW=False, lossTot=1.e6):
         """Initial penalty weights (VarNet.py:1094-1146): default branch scales `weight` so the
