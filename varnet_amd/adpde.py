@@ -1,9 +1,12 @@
 """
-Advection-diffusion PDE container: `ADPDE(domain, diff, vel, source, timeDependent, tInterval,
-BCs, IC, cEx, MORvar, d_diff)` -- /root/reference/ADPDE.py:56-246 restated (plot helpers are
+Advection-diffusion(-reaction) PDE container: `ADPDE(domain, diff, vel, source, timeDependent, tInterval,
+BCs, IC, cEx, MORvar, d_diff, reaction)` -- /root/reference/ADPDE.py:56-246 restated (plot helpers are
 out of scope).
 
-    c_t = div(diff grad c) - vel . grad c + source,    a * dc/dn + b * c = g  on each edge.
+    c_t = div(diff grad c) - vel . grad c + source + rate * p(c),    a * dc/dn + b * c = g  on each edge,
+
+with the optional polynomial reaction p(c) = c1 c + c2 c^2 + c3 c^3 (`reaction=(rate, [c1, c2, c3])`, no reference
+counterpart; absent by default).
 
 Constants are wrapped into callables f(x[, t]) returning column arrays; every BC is normalised
 to [a, b, g(x,t)] and classified Dirichlet / Neumann / Robin; with a `MOR` instance a lookup
@@ -17,8 +20,16 @@ uf = UF()
 
 
 class ADPDE:
+    """
+    c_t = div(diff grad c) - vel . grad c + source + rate * (c1 c + c2 c^2 + c3 c^3),    a * dc/dn + b * c = g  on each edge.
+
+    reaction=(rate, [c1, c2, c3]) adds the polynomial reaction term on the source side (first-order decay: (lam, [-1]);
+    Fisher-KPP: (r, [1, -1]); Allen-Cahn: (1 / eps^2, [1, 0, -1])).  `rate` is a number or a callable f(x[, t]) returning a
+    column, like `source`; a shorter coefficient list is zero-padded.  None (the default): no reaction term.
+    """
+
     def __init__(self, domain, diff, vel, source=0.0, timeDependent=False, tInterval=None,
-                 BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None):
+                 BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None):
         # the reference ignores the `timeDependent` argument (ADPDE.py:108-109)
         timeDependent = tInterval is not None
 
@@ -38,6 +49,25 @@ class ADPDE:
             raise ValueError('exact solution must be a callable function!')
         if d_diff is not None and not uf.isnumber(d_diff) and not callable(d_diff):
             raise ValueError('diffusivity gradient must be constant or callable!')
+
+        if reaction is not None:
+            if not isinstance(reaction, (tuple, list)) or len(reaction) != 2:
+                raise ValueError('reaction must be given as (rate, [c1, c2, c3])!')
+            rate, coef = reaction
+            if not uf.isnumber(rate) and not callable(rate):
+                raise ValueError('reaction rate must be constant or callable!')
+            try:
+                coef = [float(c) for c in np.reshape(np.asarray(coef, dtype=float), -1)]
+            except (TypeError, ValueError):
+                raise ValueError('reaction coefficients must be a list of up to three numbers [c1, c2, c3]!')
+            if not 1 <= len(coef) <= 3 or not np.all(np.isfinite(coef)):
+                raise ValueError('reaction coefficients must be a list of up to three finite numbers [c1, c2, c3]!')
+            if uf.isnumber(rate) and not np.isfinite(float(rate)):
+                raise ValueError('reaction rate must be finite!')
+            if MORvar is not None:
+                raise NotImplementedError('a reaction term with model-order reduction is not supported: parametric reaction '
+                                          'rates are out of scope (the rate stream is assembled once, for all parameter batches)')
+            coef = coef + [0.0] * (3 - len(coef))
 
         dim = domain.dim
 
@@ -65,6 +95,18 @@ class ADPDE:
             d_diff = 0.0 if d_diff is None else d_diff
             self.d_diff = d_diff
             self.d_diffFun = const_field(np.asarray(d_diff, dtype=float), dim)
+
+        # reaction term: rate as a callable like the source, the three coefficients; None without one
+        self.reaction = None
+        if reaction is not None:
+            if callable(rate):
+                self.reactionRate = None
+                self.reactionRateFun = rate
+            else:
+                self.reactionRate = float(rate)
+                self.reactionRateFun = const_field(float(rate), 1)
+            self.reactionCoef = coef
+            self.reaction = (rate, coef)
 
         # boundary conditions -> [a, b, g]
         bIndNum = domain.bIndNum

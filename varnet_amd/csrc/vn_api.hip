@@ -6,6 +6,7 @@
 #include "vn_lbfgs.h"
 #include "vn_obj64.h"
 #include "vn_pgrad16.h"
+#include "vn_react.h"
 #include "vn_taylor16.h"
 #include "vn_split16.h"
 
@@ -76,6 +77,10 @@ struct Batch {
   float* gcsr = nullptr;      // owned: gcoef in CSR order, [n_k*integ_num, dim] (static per batch; built by vn_set_dedup)
   long gcsr_cap = 0;
   bool gper = false;          // gcoef repeats with period integ_num along the rows (constant coefficients): no CSR copy needed
+  // polynomial reaction term rate * (c1 u + c2 u^2 + c3 u^3) on the source side (vn_set_reaction)
+  bool react = false;
+  const float* rate = nullptr;   // [n_k*integ_num] or nullptr: rate == 1
+  double rc[3] = {0.0, 0.0, 0.0};
 };
 
 // How an engine computes its gradient, decided once by pick_route (vn_create).
@@ -159,6 +164,7 @@ struct vn_engine {
   // de-duplicated formulation work buffers
   float *dd_uv = nullptr, *dd_su = nullptr, *dd_sg = nullptr, *dd_partial = nullptr, *dd_losspart = nullptr;
   long dd_uv_cap = 0, dd_su_cap = 0, dd_sg_cap = 0, dd_partial_cap = 0, dd_cap_lp = 0;
+  float* rx_seff = nullptr; long rx_seff_cap = 0;   // reaction in the de-duplicated step: source + rate p(u) per row (vn_react.hip)
   // boundary-flux rows (vn_set_flux_bc): caller-owned inputs, engine-owned work buffers; nF == 0: none
   const float *fX = nullptr, *fN = nullptr, *fcoef = nullptr, *flabel = nullptr;
   long nF = 0;
@@ -431,6 +437,19 @@ VnSeedArgs seed_args(const vn_engine* h, const Batch& b) {
   a.n_k = b.n_k; a.integ_num = h->cfg.integ_num; a.time_dependent = h->cfg.time_dependent;
   a.ub = h->ub; a.label = bi_y(h, b); a.nB = h->nB; a.bDof = h->bDof; a.biDimVal = (float)h->biDimVal;
   a.w0 = (float)h->w[0]; a.w1 = (float)h->w[1]; a.w2 = (float)h->w[2];
+  if (b.react) { a.react = 1; a.rate = b.rate; a.c1 = (float)b.rc[0]; a.c2 = (float)b.rc[1]; a.c3 = (float)b.rc[2]; }
+  return a;
+}
+
+// Reaction term of a batch with a de-duplication map (vn_react.hip): the values of its points in h->dd_uv
+VnReactArgs react_args(const vn_engine* h, const Batch& b) {
+  VnReactArgs a{};
+  a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
+  a.source = batch_src(h, b); a.rate = b.rate;
+  a.c1 = (float)b.rc[0]; a.c2 = (float)b.rc[1]; a.c3 = (float)b.rc[2];
+  a.feN = h->feN; a.feW = fe_w(h);
+  a.nT = b.n_k * h->cfg.integ_num; a.U = b.U; a.q = h->cfg.integ_num;
+  a.s_eff = h->rx_seff;
   return a;
 }
 
@@ -508,6 +527,11 @@ int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst, con
   HIPCHK(point_pass(h, b.Xu, b.U, nullptr, nullptr, h->dd_uv));
   VnDedupArgs a = dedup_args(h, b);
   a.lossVec = lossVec; a.part = h->losspart;          // loss only: no seeds
+  if (b.react) {                                      // source + rate p(u) per row takes the place of the source
+    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
+    HIPCHK(vn_react_source_launch(react_args(h, b), h->stream));
+    a.source = h->rx_seff;
+  }
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
   if (int rc = fused_forward(h, bi_x(h, b), nullptr, h->nB, h->ub, nullptr)) return rc;
   VnSeedArgs s = seed_args(h, b);
@@ -618,6 +642,8 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx)
 //   2. vn_seed_kernel -> R_k, lossVec, variational loss partials, per-row seeds
 //   3. reverse pass with those seeds (recomputes the forward); BC/IC tiles ride along   (6 F_pt)
 // 8 F_pt per point instead of 6, against 8 F_pt at 0.07 of peak on the generic kernels.
+// Also the step of a batch with a reaction term on the single-launch route, at any integ_num (vn_set_reaction): the term lives
+// in the seed kernel; neither mode of the fused kernel looks at integ_num.
 int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
   const int grid = h->ncu, P = h->net.P;
   const int sgrid = (int)((b.n_k + 255) / 256);
@@ -662,8 +688,17 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx)
   VnDedupArgs a = dedup_args(h, b);
   a.stf = h->u; a.part = lp + (long)grid * 3;
   a.seed_u = h->dd_su; a.seed_g = h->dd_sg;
+  VnReactArgs ra{};
+  if (b.react) {                                      // source + rate p(u) per row takes the place of the source
+    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
+    ra = react_args(h, b);
+    ra.stf = a.stf; ra.seed_u = a.seed_u;
+    HIPCHK(vn_react_source_launch(ra, h->stream));
+    a.source = h->rx_seff;
+  }
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
   HIPCHK(vn_dedup_gather_launch(a, h->stream));
+  if (b.react) HIPCHK(vn_react_gather_launch(ra, h->stream));   // the term's value seed, added to the gathered one
   VnFusedArgs f = fused_args(h, &b);
   f.X = b.Xu; f.G = h->dd_sg; f.nT = b.U;
   f.partial = h->dd_partial; f.losspart = lp;
@@ -829,7 +864,7 @@ int vn_destroy(vn_engine* h) {
   if (h->comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(h->stream); (void)g_rccl.CommDestroy(h->comm); h->comm = nullptr; }
   void* ptrs[] = {h->theta, h->m, h->v, h->snap, h->theta64, h->gradbuf_int, h->lossbuf, h->partial, h->feN, h->fedNt,
                   h->feW, h->u, h->ud, h->ubar, h->udbar, h->ub, h->ubar_b, h->losspart, h->fused_losspart, h->stamps, h->dd_uv, h->dd_su, h->dd_sg, h->dd_partial,
-                  h->dd_losspart, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial,
+                  h->dd_losspart, h->rx_seff, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial,
                   h->lb.ring, h->lb.theta_k, h->lb.g_k, h->lb.d, h->lb.part, h->lb.G, h->lb.coef, h->lb.meta};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -1011,6 +1046,7 @@ int vn_set_interior(vn_engine* h, int32_t batch, const float* Input, const float
   b.Nrow = N_rows; b.dNtrow = dNt_rows; b.n_k = n_k; b.set = true;
   b.Xu = nullptr; b.uid = nullptr; b.rowptr = nullptr; b.rowidx = nullptr; b.U = 0;   // re-register with vn_set_dedup
   b.biInput = nullptr; b.biLabel = nullptr;                                            // ... and vn_set_batch_bic
+  b.react = false; b.rate = nullptr; b.rc[0] = b.rc[1] = b.rc[2] = 0.0;                // ... and vn_set_reaction
   const long nT = n_k * h->cfg.integ_num;
   if (nT > h->work_rows) {
     long c0 = h->work_rows, c1 = h->work_rows, c2 = h->work_rows, c3 = h->work_rows;
@@ -1072,7 +1108,33 @@ int vn_set_dedup(vn_engine* h, int32_t batch, const float* Xu, int64_t U, const 
     if (int rc = ensure(&b.gcsr, &b.gcsr_cap, nT * dim)) return rc;
     HIPCHK(vn_dedup_permute_launch(b.gcoef, rowidx, b.gcsr, nT, dim, h->stream));
   }
+  if (b.react)
+    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, nT)) return rc;
   b.Xu = Xu; b.U = U; b.uid = uid; b.rowptr = rowptr; b.rowidx = rowidx;
+  return VN_OK;
+}
+
+int vn_set_reaction(vn_engine* h, int32_t batch, const float* rate, const double coef[3]) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
+    return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
+  if (coef && !(std::isfinite(coef[0]) && std::isfinite(coef[1]) && std::isfinite(coef[2])))
+    return fail(VN_EINVAL, "reaction coefficients (%g, %g, %g) must be finite", coef[0], coef[1], coef[2]);
+  Batch& b = h->batches[batch];
+  if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no reaction term to integrate", batch);
+  lbfgs_invalidate(h, batch);
+  if (!coef || (coef[0] == 0.0 && coef[1] == 0.0 && coef[2] == 0.0)) {      // clears; a de-duplication map stays
+    b.react = false; b.rate = nullptr; b.rc[0] = b.rc[1] = b.rc[2] = 0.0;
+    return VN_OK;
+  }
+  if (h->route == Route::fused4)
+    return fail(VN_EUNSUPPORTED, "the reaction term is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its single "
+                                 "launch has no place for the term; every other kernel family carries it");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // (the row-wise work buffers u / ud / ubar / udbar of the two-pass sequence exist since vn_set_interior, on every route)
+  if (b.Xu)
+    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
+  b.react = true; b.rate = rate; b.rc[0] = coef[0]; b.rc[1] = coef[1]; b.rc[2] = coef[2];
   return VN_OK;
 }
 
@@ -1157,8 +1219,9 @@ int vn_grad(vn_engine* h, int32_t batch) {
   switch (h->route) {
     case Route::layered: return run_layered(h, b, h->gradbuf, fx);
     case Route::generic: return run_generic(h, b, h->gradbuf, fx);
-    case Route::fused4:
-    case Route::fused8: return run_fused(h, b, h->gradbuf, fx);
+    case Route::fused4: return run_fused(h, b, h->gradbuf, fx);
+    // a reaction term lives in the row-wise seed kernel: the single-launch route runs the two-pass sequence for such a batch
+    case Route::fused8: return b.react ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
     case Route::twopass: return run_twopass(h, b, h->gradbuf, fx);
   }
 }
@@ -1396,6 +1459,7 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   p.Xb = bi_x(h, b); p.label = bi_y(h, b); p.nB = h->nB; p.bDof = h->bDof; p.biDimVal = h->biDimVal;
   p.Xf = h->fX; p.Nf = h->fN; p.fcoef = h->fcoef; p.flabel = h->flabel; p.nF = h->nF; p.fbiDimVal = h->fbiDimVal;
   p.w[0] = h->w[0]; p.w[1] = h->w[1]; p.w[2] = h->w[2];
+  p.react = b.react ? 1 : 0; p.rate = b.rate; p.coef[0] = b.rc[0]; p.coef[1] = b.rc[1]; p.coef[2] = b.rc[2];
   hipError_t e = vn_obj64_run(h->o64, p, grad_dev, lossVec_dev, out, h->ncu, h->stream);
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(h->stream);

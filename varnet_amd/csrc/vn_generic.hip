@@ -346,7 +346,13 @@ __global__ __launch_bounds__(NTHREADS) void vn_seed_kernel(VnSeedArgs a) {
       const long r = base + p;
       float t = a.ud[r];
       if (a.time_dependent) t -= a.u[r] * (a.dNtrow ? a.dNtrow[r] : a.fedNt[p]);
-      if (a.source) t -= a.source[r] * (a.Nrow ? a.Nrow[r] : a.feN[p]);
+      if (a.react) {
+        // reaction on the source side: t -= (s + rate p(u)) N, p(u) = c1 u + c2 u^2 + c3 u^3
+        const float uu = a.u[r];
+        const float pu = uu * (a.c1 + uu * (a.c2 + uu * a.c3));
+        const float se = (a.source ? a.source[r] : 0.f) + (a.rate ? a.rate[r] * pu : pu);
+        t -= se * (a.Nrow ? a.Nrow[r] : a.feN[p]);
+      } else if (a.source) t -= a.source[r] * (a.Nrow ? a.Nrow[r] : a.feN[p]);
       if (a.feW) t *= a.feW[p];
       R += t;
     }
@@ -359,7 +365,13 @@ __global__ __launch_bounds__(NTHREADS) void vn_seed_kernel(VnSeedArgs a) {
         const long r = base + p;
         const float s = a.feW ? s0 * a.feW[p] : s0;
         a.udbar[r] = s;
-        a.ubar[r] = a.time_dependent ? -(a.dNtrow ? a.dNtrow[r] : a.fedNt[p]) * s : 0.f;
+        float ub = a.time_dependent ? -(a.dNtrow ? a.dNtrow[r] : a.fedNt[p]) * s : 0.f;
+        if (a.react) {                               // d t / d u of the reaction: -N rate p'(u)
+          const float uu = a.u[r];
+          const float dp = a.c1 + uu * (2.f * a.c2 + 3.f * a.c3 * uu);
+          ub -= (a.Nrow ? a.Nrow[r] : a.feN[p]) * (a.rate ? a.rate[r] * dp : dp) * s;
+        }
+        a.ubar[r] = ub;
       }
     }
   }

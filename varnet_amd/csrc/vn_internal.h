@@ -44,6 +44,10 @@ struct VnSeedArgs {
   float* ubar_b;                            // [nB] out (may be nullptr)
   float w0, w1, w2;
   float* part;                              // [gridDim.x * 3] block partials (var, bc, ic)
+  // polynomial reaction term rate * (c1 u + c2 u^2 + c3 u^3) on the source side (vn_set_reaction); react == 0: none
+  int react;
+  const float* rate;                        // [nT] or nullptr (rate == 1)
+  float c1, c2, c3;
 };
 
 inline bool vn_net_in_kernel_range(const VnNet& net) {

@@ -28,6 +28,8 @@ struct VnObj64Problem {
   // boundary-flux rows
   const float* Xf; const float* Nf; const float* fcoef; const float* flabel; long nF; double fbiDimVal;
   double w[3];
+  // reaction term of the batch (vn_set_reaction): rate [n_k*q] or nullptr (1), coef c1..c3; react == 0: none
+  int react; const float* rate; double coef[3];
 };
 
 bool vn_obj64_supported(const VnNet& net);

@@ -343,6 +343,7 @@ struct SeedArgs {
   const float* fcoef; const float* flabel; long nF; double fbiDimVal;
   double w0, w1, w2;
   int seeds;                                  // write the adjoint seeds in place of (u, ud)
+  int react; const float* rate; double c1, c2, c3;   // reaction rate p(u), p = c1 u + c2 u^2 + c3 u^3 (react == 0: none)
   double* lossVec; double* lpart;             // [n_k] or nullptr; [gridDim.x][4]
 };
 
@@ -367,7 +368,12 @@ __global__ __launch_bounds__(256) void vn_obj64_seed_kernel(SeedArgs a) {
       const long r = base + p;
       double t = a.ud[r];
       if (a.td) t -= a.u[r] * (double)(a.dNtrow ? a.dNtrow[r] : a.fedNt[p]);
-      if (a.source) t -= (double)a.source[r] * (double)(a.Nrow ? a.Nrow[r] : a.feN[p]);
+      if (a.react) {
+        const double uu = a.u[r];
+        const double pu = uu * (a.c1 + uu * (a.c2 + uu * a.c3));
+        const double se = (a.source ? (double)a.source[r] : 0.0) + (a.rate ? (double)a.rate[r] * pu : pu);
+        t -= se * (double)(a.Nrow ? a.Nrow[r] : a.feN[p]);
+      } else if (a.source) t -= (double)a.source[r] * (double)(a.Nrow ? a.Nrow[r] : a.feN[p]);
       if (a.feW) t *= (double)a.feW[p];
       R += t;
     }
@@ -380,7 +386,13 @@ __global__ __launch_bounds__(256) void vn_obj64_seed_kernel(SeedArgs a) {
         const long r = base + p;
         const double s = a.feW ? s0 * (double)a.feW[p] : s0;
         a.ud[r] = s;
-        a.u[r] = a.td ? -(double)(a.dNtrow ? a.dNtrow[r] : a.fedNt[p]) * s : 0.0;
+        double ub = a.td ? -(double)(a.dNtrow ? a.dNtrow[r] : a.fedNt[p]) * s : 0.0;
+        if (a.react) {                              // u[r] still holds the forward value here
+          const double uu = a.u[r];
+          const double dp = a.c1 + uu * (2.0 * a.c2 + 3.0 * a.c3 * uu);
+          ub -= (double)(a.Nrow ? a.Nrow[r] : a.feN[p]) * (a.rate ? (double)a.rate[r] * dp : dp) * s;
+        }
+        a.u[r] = ub;
       }
     }
   }
@@ -540,6 +552,7 @@ hipError_t vn_obj64_run(VnObj64Work& w, const VnObj64Problem& p, double* grad_de
   sa.fcoef = p.fcoef; sa.flabel = p.flabel; sa.nF = nF; sa.fbiDimVal = p.fbiDimVal;
   sa.w0 = p.w[0]; sa.w1 = p.w[1]; sa.w2 = p.w[2];
   sa.seeds = grad_dev ? 1 : 0;
+  sa.react = p.react; sa.rate = p.rate; sa.c1 = p.coef[0]; sa.c2 = p.coef[1]; sa.c3 = p.coef[2];
   sa.lossVec = lossVec_dev; sa.lpart = w.lpart;
   hipLaunchKernelGGL(vn_obj64_seed_kernel, dim3(sblk), dim3(256), 0, s, sa);
   OCHK(hipGetLastError());

@@ -63,6 +63,7 @@ _SIGS = {
     'vn_set_bic': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double]),
     'vn_set_batch_bic': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'vn_set_flux_bc': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
+    'vn_set_reaction': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_bind_grad_buffer': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vn_grad': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -368,6 +369,7 @@ class VNEngine:
         self._keep[('int', batch)] = (Input, gcoef, source, detJv, Nr, dNr)
         self._ck(self.lib.vn_set_interior(self.h, batch, _ptr(Input), _ptr(gcoef), _ptr(source), n_k,
                                           _ptr(detJv), detJ_s, _ptr(Nr), _ptr(dNr)))
+        self._keep.pop(('react', batch), None)       # vn_set_interior cleared the batch's reaction term
 
     def set_dedup(self, batch, Xu=None, uid=None, rowptr=None, rowidx=None):
         """Register (or, with Xu=None, clear) the de-duplicated formulation of `batch`."""
@@ -434,6 +436,28 @@ class VNEngine:
         finally:
             del old           # the engine dropped the previous registration before checking this one
         self._keep['flux'] = (X, normal, coef, label)
+
+    def set_reaction(self, batch, rate=None, coef=None):
+        """Register (or, with coef=None or all zero, clear) the reaction term rate * (c1 u + c2 u^2 + c3 u^3) of `batch`
+        (vn_set_reaction), after set_interior of that batch: rate one value per interior row or None (rate = 1), coef up to
+        three numbers (a shorter list is zero-padded)."""
+        c = [] if coef is None else [float(x) for x in np.reshape(np.asarray(coef, dtype=np.float64), -1)]
+        if len(c) > 3:
+            raise ValueError('a reaction takes at most three coefficients (c1, c2, c3), got %d' % len(c))
+        c = c + [0.0] * (3 - len(c))
+        if coef is None or not any(c):
+            self._keep.pop(('react', batch), None)
+            self._ck(self.lib.vn_set_reaction(self.h, int(batch), None, None))
+            return
+        if rate is not None:
+            t = self.torch
+            rate = self.dev(rate.reshape(-1) if isinstance(rate, t.Tensor) else np.reshape(rate, -1))
+            # the ABI carries a pointer only: the length the kernels rely on is checked here
+            kept = self._keep.get(('int', batch))
+            assert kept is None or rate.numel() == kept[0].shape[0], \
+                'rate must have one entry per interior row (%s != %s)' % (rate.numel(), kept[0].shape[0])
+        self._ck(self.lib.vn_set_reaction(self.h, int(batch), _ptr(rate), (C.c_double * 3)(*c)))
+        self._keep[('react', batch)] = rate
 
     def set_weights(self, w):
         arr = (C.c_double * 3)(*[float(x) for x in w])
@@ -533,7 +557,9 @@ class VNEngine:
         self._ck(self.lib.vn_forward_f64(self.h, _ptr(X), X.shape[0], _ptr(u)))
         return u
 
-    def residual(self, X, diff, vel, source=None, diff_dx=None, fp64=False):
+    def residual(self, X, diff, vel, source=None, diff_dx=None, fp64=False, reaction=None):
+        """(u, strong residual) at X.  reaction=(rate, coef): the residual gains rate * (c1 u + c2 u^2 + c3 u^3), rate a number,
+        one value per point or None (1)."""
         t = self.torch
         dt = t.float64 if fp64 else t.float32
         X = self.dev(X, dt)
@@ -546,6 +572,15 @@ class VNEngine:
         r = t.empty(n, dtype=dt, device=self.device)
         fn = self.lib.vn_residual_f64 if fp64 else self.lib.vn_residual
         self._ck(fn(self.h, _ptr(X), _ptr(diff), _ptr(vel), _ptr(source), _ptr(diff_dx), n, _ptr(u), _ptr(r)))
+        if reaction is not None:
+            rate, coef = reaction
+            c = [float(x) for x in np.reshape(np.asarray(coef, dtype=np.float64), -1)]
+            c = c + [0.0] * (3 - len(c))
+            pu = u * (c[0] + u * (c[1] + u * c[2]))
+            if rate is not None:
+                pu = pu * (float(rate) if np.ndim(rate) == 0 and not isinstance(rate, t.Tensor) else self.dev(
+                    rate.reshape(-1) if isinstance(rate, t.Tensor) else np.reshape(rate, -1), dt))
+            r = r + pu
         return u, r
 
     # -- towers: RCCL communicator inside the engine (TFModel.py:253-289, 342-377) ---------------

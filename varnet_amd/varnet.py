@@ -294,6 +294,8 @@ class TrainResult:
         for bInd, kind, rows in (varNet.fluxRows or {}).get('edges', []):
             L.append('\tBC%d: %s condition enforced as a boundary flux term on %d rows\n' % (bInd + 1, kind, rows))
         L.append('\n')
+        if getattr(PDE, 'reaction', None) is not None:
+            L.append('Reaction term: rate*(c1 c + c2 c^2 + c3 c^3), coefficients %s\n\n' % str(list(PDE.reactionCoef)))
         L.append('Neural Network architecture:\n')
         L.append('\ttype: ' + str(varNet.modelId) + '\n')
         L.append('\tnumber of inputs: ' + str(varNet.inpDim) + '\n')
@@ -581,7 +583,7 @@ class ManageTrainData:
         for mb, d in enumerate(self.mor):
             if self.shuffled:                     # one gather per array and parameter batch; the blocks are views of it
                 d = dict(d)
-                for key in ('Input', 'gcoef', 'source', 'N_rows', 'dNt_rows'):
+                for key in ('Input', 'gcoef', 'source', 'N_rows', 'dNt_rows', 'rate'):
                     if d.get(key) is not None:
                         d[key] = d[key].index_select(0, rows_all)
                 if d.get('detJ') is not None:
@@ -594,6 +596,8 @@ class ManageTrainData:
                 eng.set_interior(self.engine_batch(mb, bi), pick(d['Input']), pick(d['gcoef']), pick(d['source']),
                                  n_k=n1 - n0, detJ=self.detJ if detJ is None else detJ,
                                  N_rows=pick(d.get('N_rows')), dNt_rows=pick(d.get('dNt_rows')))
+                if d.get('reactCoef') is not None and n1 > n0:      # the reaction term of these rows (vn_set_reaction)
+                    eng.set_reaction(self.engine_batch(mb, bi), pick(d.get('rate')), d['reactCoef'])
                 perm = getattr(self, 'biPerm', {}).get(bi)
                 if perm is not None and hasattr(eng, 'set_batch_bic'):
                     ix = torch.as_tensor(perm, device=eng.device, dtype=torch.long)
@@ -1170,6 +1174,16 @@ class VarNet:
         return (PDE.diffFun(X, *targ, **diffArg), PDE.velFun(X, *targ, **velArg),
                 PDE.sourceFun(X, *targ, **sourceArg))
 
+    def _reaction_rate(self, Input):
+        """Reaction rate at the rows of Input (a column), evaluated like the source (PDEinpData)."""
+        dim, PDE = self.dim, self.PDE
+        targ = [Input[:, dim][np.newaxis].T] if PDE.timeDependent else []
+        rate = np.asarray(PDE.reactionRateFun(Input[:, 0:dim], *targ), dtype=np.float64)
+        if rate.size != Input.shape[0]:
+            raise ValueError('the reaction rate must return one value per point (a column), got shape %s for %d points'
+                             % (rate.shape, Input.shape[0]))
+        return rate.reshape(-1, 1)
+
     def MORargExtract(self, batch, MORdiscArg):
         """Keyword arguments of every parametric callable for MOR batch `batch`, and the extra
         network inputs, in the reference's order (VarNet.py:901-1049): BC functions, IC, diff,
@@ -1224,7 +1238,15 @@ class VarNet:
         if MORinp is not None:
             Input = np.hstack([Input, np.tile(MORinp, [Input.shape[0], 1])])
             biInput = np.hstack([biInput, np.tile(MORinp, [biInput.shape[0], 1])])
-        return dict(Input=eng.dev(Input), Input_host=Input, gcoef=eng.dev(gcoef),
+        rate = reactCoef = None
+        if getattr(self.PDE, 'reaction', None) is not None:
+            # rate at the rows of Input in fp64, uploaded as fp32 (a constant rate is folded into the coefficients: no stream)
+            reactCoef = list(self.PDE.reactionCoef)
+            if self.PDE.reactionRate is not None:
+                reactCoef = [self.PDE.reactionRate * c for c in reactCoef]
+            else:
+                rate = eng.dev(np.asarray(self._reaction_rate(Input), dtype=np.float64).reshape(-1))
+        return dict(Input=eng.dev(Input), Input_host=Input, gcoef=eng.dev(gcoef), rate=rate, reactCoef=reactCoef,
                     source=eng.dev(src.reshape(-1)) if self.lossOpt['isSource'] else None,
                     biInput=eng.dev(biInput), biLabel=eng.dev(biLabel.reshape(-1)),
                     N_rows=N_rows, dNt_rows=dNt_rows,
@@ -2067,7 +2089,10 @@ class VarNet:
                 cols, _, inpArg = self._mor_columns(b, Input.shape[0])
                 diff, vel, src = self.PDEinpData(Input, inpArg)
                 Inp = np.hstack([Input, cols])
-            u, r = self.engine.residual(Inp, diff, vel, src, diff_dx, fp64=fp64)
+            rkw = {}
+            if getattr(PDE, 'reaction', None) is not None:           # res += rate p(u)
+                rkw['reaction'] = (self._reaction_rate(Input).reshape(-1), PDE.reactionCoef)
+            u, r = self.engine.residual(Inp, diff, vel, src, diff_dx, fp64=fp64, **rkw)
             cApp = u.cpu().numpy().astype(np.float64).reshape(-1, 1)
             resVec = r.cpu().numpy().astype(np.float64).reshape(-1, 1)
             if PDE.cEx is not None:
