@@ -209,6 +209,28 @@ int vn_set_flux_bc(vn_engine* h, const float* X_dev, const float* normal_dev, co
  * (vn_react.hip); the 4-wave cross-check geometry (VN_KERNEL_FUSED) returns VN_EUNSUPPORTED.  Without a registration nothing is
  * launched, nothing is allocated and every result is bit for bit what it is without this call. */
 int vn_set_reaction(vn_engine* h, int32_t batch, const float* rate_dev, const double coef[3]);
+/* OPTIONAL, no reference counterpart: a polynomial flux term (Burgers-type advection, scalar conservation laws) for `batch`,
+ *     c_t = div(kappa grad c) - v.grad c - div( w(x,t) F(c) ) + s + rate p(c),     F(c) = f1 c + f2 c^2 + f3 c^3
+ * (Burgers: w = 1, F = c^2 / 2; LWR traffic: F = c - c^2).  The flux is conservative, so the weak form integrates it by parts onto
+ * the test function and only the network value enters: with  phi_r = sum_d w_d(x_r, t_r) dN_r/dx_d  the row integrand
+ * (TFModel.py:653-657) becomes  sum_d u_{x_d} gcoef_d - u dNt - (s + rate p(u)) N - F(u) phi,  everything after it is unchanged, and
+ * the value seed of a row gains  -phi F'(u)  times the row's tangent seed.  The test functions vanish on the edge of their supports
+ * (as the diffusion and time terms assume): there is no boundary term.
+ *   phi_dev   [n_k*integ_num] device floats, one per interior row.  READ on every step (it must stay valid while registered),
+ *             like the flux rows.  NULL with non-zero coefficients: VN_EINVAL.
+ *   coef      {f1, f2, f3}; NULL or all zero clears the registration.  Non-finite: VN_EINVAL.
+ * Per batch, called after vn_set_interior of that batch: a new vn_set_interior clears it (as it clears the de-duplication map),
+ * vn_set_dedup and vn_set_reaction keep it, and this call keeps a registered map and a registered reaction.  An unregistered
+ * batch: VN_ESTATE; a batch without interior rows (n_k == 0): VN_EINVAL.  A change invalidates the L-BFGS (f_k, g_k) and ring of
+ * that batch, like vn_set_flux_bc.
+ * With a flux term on the batch vn_grad / vn_train_step / vn_train_epoch (under a communicator as well), vn_eval_loss (lossVec
+ * included), vn_lbfgs_step and vn_objective_f64 all see the term, together with a reaction of the same batch.  Routes: the generic,
+ * layer-by-layer and two-pass routes run two elementwise kernels around their row-wise seed kernel (vn_nlflux.hip); a batch of the
+ * single-launch 8-wave route runs the two-pass sequence instead, at any integ_num; the de-duplicated step adds two small kernels
+ * (they divide by the table entries N_p of vn_set_fe_table: a table with a zero entry is VN_EUNSUPPORTED for a batch that has both
+ * a map and a flux term); the 4-wave cross-check geometry (VN_KERNEL_FUSED) returns VN_EUNSUPPORTED.  Without a registration
+ * nothing is launched, nothing is allocated and every result is bit for bit what it is without this call. */
+int vn_set_nlflux(vn_engine* h, int32_t batch, const float* phi_dev, const double coef[3]);
 /* updateDictFields('trainW') (VarNetUtility.py:921-922); the caller applies the
  * w[0:2] /= batchNum*puNum rule (VarNetUtility.py:900-901). */
 int vn_set_weights(vn_engine* h, const double w[3]);
@@ -256,7 +278,7 @@ int vn_train_epoch(vn_engine* h, const int32_t* batches, int32_t n, float* loss_
  * info = {status, f_k, f_{k+1}, BC, IC, var at theta_{k+1}, accepted t, trials used, g_k.d, pairs the direction was formed from}
  * (after a status != 0: f_{k+1} = f_k, the components of theta_k, t = 0).
  * vn_params_init, vn_params_set, vn_state_import, vn_set_bic, vn_set_flux_bc, vn_set_interior / vn_set_dedup /
- * vn_set_batch_bic / vn_set_reaction of that batch, a call with another `batch` than the previous one and vn_set_weights invalidate (f_k, g_k) and
+ * vn_set_batch_bic / vn_set_reaction / vn_set_nlflux of that batch, a call with another `batch` than the previous one and vn_set_weights invalidate (f_k, g_k) and
  * drop the ring -- vn_set_weights when the call finds other weights than (f_k, g_k) were evaluated with (weights changed and put
  * back between two calls, as the monitors of VarNet.train do, leave the objective and therefore the optimizer alone).
  * vn_state_export writes the two slots as zeros and vn_state_import ignores them; the ring is not part of a checkpoint. */

@@ -1,12 +1,13 @@
 """
 Advection-diffusion(-reaction) PDE container: `ADPDE(domain, diff, vel, source, timeDependent, tInterval,
-BCs, IC, cEx, MORvar, d_diff, reaction)` -- /root/reference/ADPDE.py:56-246 restated (plot helpers are
+BCs, IC, cEx, MORvar, d_diff, reaction, nlflux)` -- /root/reference/ADPDE.py:56-246 restated (plot helpers are
 out of scope).
 
-    c_t = div(diff grad c) - vel . grad c + source + rate * p(c),    a * dc/dn + b * c = g  on each edge,
+    c_t = div(diff grad c) - vel . grad c - div(w F(c)) + source + rate * p(c),    a * dc/dn + b * c = g  on each edge,
 
-with the optional polynomial reaction p(c) = c1 c + c2 c^2 + c3 c^3 (`reaction=(rate, [c1, c2, c3])`, no reference
-counterpart; absent by default).
+with the optional polynomial reaction p(c) = c1 c + c2 c^2 + c3 c^3 (`reaction=(rate, [c1, c2, c3])`) and the optional
+polynomial flux F(c) = f1 c + f2 c^2 + f3 c^3 (`nlflux=(w, [f1, f2, f3])`); neither has a reference counterpart, both are
+absent by default.
 
 Constants are wrapped into callables f(x[, t]) returning column arrays; every BC is normalised
 to [a, b, g(x,t)] and classified Dirichlet / Neumann / Robin; with a `MOR` instance a lookup
@@ -26,10 +27,16 @@ class ADPDE:
     reaction=(rate, [c1, c2, c3]) adds the polynomial reaction term on the source side (first-order decay: (lam, [-1]);
     Fisher-KPP: (r, [1, -1]); Allen-Cahn: (1 / eps^2, [1, 0, -1])).  `rate` is a number or a callable f(x[, t]) returning a
     column, like `source`; a shorter coefficient list is zero-padded.  None (the default): no reaction term.
+
+    nlflux=(w, [f1, f2, f3]) or (w, [f1, f2, f3], div_w) adds the conservative flux term -div(w F(c)), F(c) = f1 c + f2 c^2 +
+    f3 c^3 (Burgers' equation: vel=0, nlflux=(1.0, [0, 0.5]); LWR traffic: (1.0, [1, -1])).  `w` is a number (1D), a list of
+    `dim` numbers or a callable f(x[, t]) returning [n, dim], like `vel`.  `div_w` is an optional callable f(x[, t]) returning
+    the divergence of w as a column; only the strong residual uses it, and without it the divergence is taken as zero: `w`
+    must then be constant or divergence-free.  Inviscid problems (shocks) are the user's responsibility.  None: no flux term.
     """
 
     def __init__(self, domain, diff, vel, source=0.0, timeDependent=False, tInterval=None,
-                 BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None):
+                 BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None, nlflux=None):
         # the reference ignores the `timeDependent` argument (ADPDE.py:108-109)
         timeDependent = tInterval is not None
 
@@ -69,6 +76,33 @@ class ADPDE:
                                           'rates are out of scope (the rate stream is assembled once, for all parameter batches)')
             coef = coef + [0.0] * (3 - len(coef))
 
+        if nlflux is not None:
+            if not isinstance(nlflux, (tuple, list)) or len(nlflux) not in (2, 3):
+                raise ValueError('nlflux must be given as (w, [f1, f2, f3]) or (w, [f1, f2, f3], div_w)!')
+            fw, fcoef = nlflux[0], nlflux[1]
+            fdiv = nlflux[2] if len(nlflux) == 3 else None
+            if not callable(fw):
+                try:
+                    fw = np.reshape(np.asarray(fw, dtype=float), -1)
+                except (TypeError, ValueError):
+                    raise ValueError('nlflux field w must be a number, a list of `dim` numbers or callable!')
+                if fw.size != domain.dim:
+                    raise ValueError('nlflux field w must have one entry per space dimension (%d), got %d!' % (domain.dim, fw.size))
+                if not np.all(np.isfinite(fw)):
+                    raise ValueError('nlflux field w must be finite!')
+            try:
+                fcoef = [float(c) for c in np.reshape(np.asarray(fcoef, dtype=float), -1)]
+            except (TypeError, ValueError):
+                raise ValueError('nlflux coefficients must be a list of up to three numbers [f1, f2, f3]!')
+            if not 1 <= len(fcoef) <= 3 or not np.all(np.isfinite(fcoef)):
+                raise ValueError('nlflux coefficients must be a list of up to three finite numbers [f1, f2, f3]!')
+            if fdiv is not None and not callable(fdiv):
+                raise ValueError('nlflux divergence div_w must be callable (or left out: w constant or divergence-free)!')
+            if MORvar is not None:
+                raise NotImplementedError('a flux term with model-order reduction is not supported: a parametric field w is out of '
+                                          'scope (the phi stream is assembled once, for all parameter batches)')
+            fcoef = fcoef + [0.0] * (3 - len(fcoef))
+
         dim = domain.dim
 
         def const_field(val, ncol):
@@ -107,6 +141,19 @@ class ADPDE:
                 self.reactionRateFun = const_field(float(rate), 1)
             self.reactionCoef = coef
             self.reaction = (rate, coef)
+
+        # flux term -div(w F(c)): w as a callable like the velocity, the three coefficients, the optional divergence; None without one
+        self.nlflux = None
+        if nlflux is not None:
+            if callable(fw):
+                self.nlfluxW = None
+                self.nlfluxWFun = fw
+            else:
+                self.nlfluxW = fw
+                self.nlfluxWFun = const_field(fw, dim)
+            self.nlfluxCoef = fcoef
+            self.nlfluxDivFun = fdiv
+            self.nlflux = (nlflux[0], fcoef) if fdiv is None else (nlflux[0], fcoef, fdiv)
 
         # boundary conditions -> [a, b, g]
         bIndNum = domain.bIndNum

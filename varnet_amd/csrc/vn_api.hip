@@ -4,6 +4,7 @@
 #include "vn_dedup.h"
 #include "vn_flux.h"
 #include "vn_lbfgs.h"
+#include "vn_nlflux.h"
 #include "vn_obj64.h"
 #include "vn_pgrad16.h"
 #include "vn_react.h"
@@ -81,6 +82,10 @@ struct Batch {
   bool react = false;
   const float* rate = nullptr;   // [n_k*integ_num] or nullptr: rate == 1
   double rc[3] = {0.0, 0.0, 0.0};
+  // polynomial flux term -div(w F(u)), F(u) = f1 u + f2 u^2 + f3 u^3, integrated by parts onto the test function (vn_set_nlflux)
+  bool nlflux = false;
+  const float* phi = nullptr;    // [n_k*integ_num]: sum_d w_d dN/dx_d per row
+  double fc[3] = {0.0, 0.0, 0.0};
 };
 
 // How an engine computes its gradient, decided once by pick_route (vn_create).
@@ -164,6 +169,7 @@ struct vn_engine {
   // de-duplicated formulation work buffers
   float *dd_uv = nullptr, *dd_su = nullptr, *dd_sg = nullptr, *dd_partial = nullptr, *dd_losspart = nullptr;
   long dd_uv_cap = 0, dd_su_cap = 0, dd_sg_cap = 0, dd_partial_cap = 0, dd_cap_lp = 0;
+  bool feN_zero = false;      // the table of vn_set_fe_table has an entry N_p == 0 (the flux term's fold divides by N_p)
   float* rx_seff = nullptr; long rx_seff_cap = 0;   // reaction in the de-duplicated step: source + rate p(u) per row (vn_react.hip)
   // boundary-flux rows (vn_set_flux_bc): caller-owned inputs, engine-owned work buffers; nF == 0: none
   const float *fX = nullptr, *fN = nullptr, *fcoef = nullptr, *flabel = nullptr;
@@ -453,6 +459,35 @@ VnReactArgs react_args(const vn_engine* h, const Batch& b) {
   return a;
 }
 
+// Flux term of a batch on the row-wise routes (vn_nlflux.hip): values in h->u, integrand / seeds in h->ud, h->ubar, h->udbar
+VnNlfluxRowArgs nlflux_row_args(const vn_engine* h, const Batch& b) {
+  VnNlfluxRowArgs a{};
+  a.u = h->u; a.phi = b.phi; a.f1 = (float)b.fc[0]; a.f2 = (float)b.fc[1]; a.f3 = (float)b.fc[2];
+  a.nT = b.n_k * h->cfg.integ_num;
+  a.ud = h->ud; a.udbar = h->udbar; a.ubar = h->ubar;
+  return a;
+}
+
+// ... and of a batch with a de-duplication map: on top of the reaction's source + rate p(u) when both are registered
+VnNlfluxDedupArgs nlflux_dedup_args(const vn_engine* h, const Batch& b) {
+  VnNlfluxDedupArgs a{};
+  a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
+  a.base = b.react ? h->rx_seff : batch_src(h, b); a.phi = b.phi;
+  a.f1 = (float)b.fc[0]; a.f2 = (float)b.fc[1]; a.f3 = (float)b.fc[2];
+  a.feN = h->feN; a.feW = fe_w(h);
+  a.nT = b.n_k * h->cfg.integ_num; a.U = b.U; a.q = h->cfg.integ_num;
+  a.s_eff = h->rx_seff;
+  return a;
+}
+
+// The fold of the flux term into the de-duplicated assembly's source divides by N_p: a table with a zero entry is an error code
+int nlflux_dedup_check(const vn_engine* h, const Batch& b) {
+  if (b.nlflux && b.Xu && h->feN_zero)
+    return fail(VN_EUNSUPPORTED, "the flux term of a de-duplicated batch needs test-function values N_p != 0 at every quadrature "
+                                 "point (vn_set_fe_table has a zero entry); clear the map (vn_set_dedup with Xu = NULL) to run row-wise");
+  return VN_OK;
+}
+
 // De-duplicated assembly (seed and gather kernels) of a batch with a de-duplication map, (u, grad u) of its points in h->dd_uv
 VnDedupArgs dedup_args(const vn_engine* h, const Batch& b) {
   VnDedupArgs a{};
@@ -532,6 +567,12 @@ int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst, con
     HIPCHK(vn_react_source_launch(react_args(h, b), h->stream));
     a.source = h->rx_seff;
   }
+  if (b.nlflux) {                                     // ... and F(u) phi / N_p on top of it
+    if (int rc = nlflux_dedup_check(h, b)) return rc;
+    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
+    HIPCHK(vn_nlflux_source_launch(nlflux_dedup_args(h, b), h->stream));
+    a.source = h->rx_seff;
+  }
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
   if (int rc = fused_forward(h, bi_x(h, b), nullptr, h->nB, h->ub, nullptr)) return rc;
   VnSeedArgs s = seed_args(h, b);
@@ -570,7 +611,10 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
   VnSeedArgs a = seed_args(h, b);
   if (with_seeds) { a.ubar = h->ubar; a.udbar = h->udbar; a.ubar_b = h->ubar_b; }
   a.lossVec = lossVec; a.part = h->losspart;
+  // flux term: -F(u) phi joins the row integrand before the seed kernel reads it, its value seed is added after (vn_nlflux.hip)
+  if (b.nlflux) HIPCHK(vn_nlflux_fold_launch(nlflux_row_args(h, b), h->stream));
   HIPCHK(vn_seed_launch(a, grid, h->stream));
+  if (b.nlflux && with_seeds) HIPCHK(vn_nlflux_seed_launch(nlflux_row_args(h, b), h->stream));
   if (lossdst) {
     HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2, lossdst, h->stream,
                             VnOptArgs(), fx));
@@ -643,7 +687,8 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx)
 //   3. reverse pass with those seeds (recomputes the forward); BC/IC tiles ride along   (6 F_pt)
 // 8 F_pt per point instead of 6, against 8 F_pt at 0.07 of peak on the generic kernels.
 // Also the step of a batch with a reaction term on the single-launch route, at any integ_num (vn_set_reaction): the term lives
-// in the seed kernel; neither mode of the fused kernel looks at integ_num.
+// in the seed kernel; neither mode of the fused kernel looks at integ_num.  A flux term (vn_set_nlflux) takes the same sequence,
+// with its two elementwise kernels around the seed kernel.
 int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
   const int grid = h->ncu, P = h->net.P;
   const int sgrid = (int)((b.n_k + 255) / 256);
@@ -660,7 +705,9 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& f
   a.ubar = h->ubar; a.udbar = h->udbar;
   a.ub = nullptr; a.label = nullptr; a.nB = 0; a.bDof = 0; a.biDimVal = 0.f;   // BC/IC: step 3
   a.part = lp + (long)grid * 3;
+  if (b.nlflux) HIPCHK(vn_nlflux_fold_launch(nlflux_row_args(h, b), h->stream));      // flux term, as in run_forward_and_seed
   HIPCHK(vn_seed_launch(a, sgrid, h->stream));
+  if (b.nlflux) HIPCHK(vn_nlflux_seed_launch(nlflux_row_args(h, b), h->stream));
 
   f.mode = 2; f.out_u = nullptr; f.out_ud = nullptr; f.seed_u = h->ubar; f.seed_ud = h->udbar; f.nB = h->nB;
   if (int rc = prof_start(h)) return rc;
@@ -696,9 +743,19 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx)
     HIPCHK(vn_react_source_launch(ra, h->stream));
     a.source = h->rx_seff;
   }
+  VnNlfluxDedupArgs na{};
+  if (b.nlflux) {                                     // ... and F(u) phi / N_p on top of it
+    if (int rc = nlflux_dedup_check(h, b)) return rc;
+    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
+    na = nlflux_dedup_args(h, b);
+    na.stf = a.stf; na.seed_u = a.seed_u;
+    HIPCHK(vn_nlflux_source_launch(na, h->stream));
+    a.source = h->rx_seff;
+  }
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
   HIPCHK(vn_dedup_gather_launch(a, h->stream));
   if (b.react) HIPCHK(vn_react_gather_launch(ra, h->stream));   // the term's value seed, added to the gathered one
+  if (b.nlflux) HIPCHK(vn_nlflux_gather_launch(na, h->stream));
   VnFusedArgs f = fused_args(h, &b);
   f.X = b.Xu; f.G = h->dd_sg; f.nT = b.U;
   f.partial = h->dd_partial; f.losspart = lp;
@@ -1025,6 +1082,8 @@ int vn_set_fe_table(vn_engine* h, const float* N, const float* dNt, const float*
   HIPCHK(hipStreamSynchronize(h->stream));   // host buffers may be released on return
   h->has_fe = true;
   h->has_feW = integW != nullptr;
+  h->feN_zero = false;
+  for (int p = 0; p < h->cfg.integ_num; ++p) h->feN_zero = h->feN_zero || N[p] == 0.f;
   return VN_OK;
 }
 
@@ -1047,6 +1106,7 @@ int vn_set_interior(vn_engine* h, int32_t batch, const float* Input, const float
   b.Xu = nullptr; b.uid = nullptr; b.rowptr = nullptr; b.rowidx = nullptr; b.U = 0;   // re-register with vn_set_dedup
   b.biInput = nullptr; b.biLabel = nullptr;                                            // ... and vn_set_batch_bic
   b.react = false; b.rate = nullptr; b.rc[0] = b.rc[1] = b.rc[2] = 0.0;                // ... and vn_set_reaction
+  b.nlflux = false; b.phi = nullptr; b.fc[0] = b.fc[1] = b.fc[2] = 0.0;                // ... and vn_set_nlflux
   const long nT = n_k * h->cfg.integ_num;
   if (nT > h->work_rows) {
     long c0 = h->work_rows, c1 = h->work_rows, c2 = h->work_rows, c3 = h->work_rows;
@@ -1108,8 +1168,10 @@ int vn_set_dedup(vn_engine* h, int32_t batch, const float* Xu, int64_t U, const 
     if (int rc = ensure(&b.gcsr, &b.gcsr_cap, nT * dim)) return rc;
     HIPCHK(vn_dedup_permute_launch(b.gcoef, rowidx, b.gcsr, nT, dim, h->stream));
   }
-  if (b.react)
+  if (b.react || b.nlflux)
     if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, nT)) return rc;
+  if (b.nlflux && h->feN_zero)
+    return fail(VN_EUNSUPPORTED, "the flux term of batch %d cannot be de-duplicated: vn_set_fe_table has an entry N_p == 0", batch);
   b.Xu = Xu; b.U = U; b.uid = uid; b.rowptr = rowptr; b.rowidx = rowidx;
   return VN_OK;
 }
@@ -1135,6 +1197,33 @@ int vn_set_reaction(vn_engine* h, int32_t batch, const float* rate, const double
   if (b.Xu)
     if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
   b.react = true; b.rate = rate; b.rc[0] = coef[0]; b.rc[1] = coef[1]; b.rc[2] = coef[2];
+  return VN_OK;
+}
+
+int vn_set_nlflux(vn_engine* h, int32_t batch, const float* phi, const double coef[3]) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
+    return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
+  if (coef && !(std::isfinite(coef[0]) && std::isfinite(coef[1]) && std::isfinite(coef[2])))
+    return fail(VN_EINVAL, "flux coefficients (%g, %g, %g) must be finite", coef[0], coef[1], coef[2]);
+  Batch& b = h->batches[batch];
+  if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no flux term to integrate", batch);
+  lbfgs_invalidate(h, batch);
+  if (!coef || (coef[0] == 0.0 && coef[1] == 0.0 && coef[2] == 0.0)) {      // clears; a map and a reaction stay
+    b.nlflux = false; b.phi = nullptr; b.fc[0] = b.fc[1] = b.fc[2] = 0.0;
+    return VN_OK;
+  }
+  if (!phi) return fail(VN_EINVAL, "the flux term needs phi = sum_d w_d dN/dx_d per interior row (phi_dev is NULL)");
+  if (h->route == Route::fused4)
+    return fail(VN_EUNSUPPORTED, "the flux term is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its single "
+                                 "launch has no place for the term; every other kernel family carries it");
+  if (b.Xu && h->feN_zero)
+    return fail(VN_EUNSUPPORTED, "the flux term of batch %d cannot join its de-duplication map: vn_set_fe_table has an entry N_p == 0", batch);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // (the row-wise work buffers u / ud / ubar / udbar of the two-pass sequence exist since vn_set_interior, on every route)
+  if (b.Xu)
+    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
+  b.nlflux = true; b.phi = phi; b.fc[0] = coef[0]; b.fc[1] = coef[1]; b.fc[2] = coef[2];
   return VN_OK;
 }
 
@@ -1220,8 +1309,9 @@ int vn_grad(vn_engine* h, int32_t batch) {
     case Route::layered: return run_layered(h, b, h->gradbuf, fx);
     case Route::generic: return run_generic(h, b, h->gradbuf, fx);
     case Route::fused4: return run_fused(h, b, h->gradbuf, fx);
-    // a reaction term lives in the row-wise seed kernel: the single-launch route runs the two-pass sequence for such a batch
-    case Route::fused8: return b.react ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
+    // a reaction term lives in the row-wise seed kernel, a flux term around it: the single-launch route runs the two-pass
+    // sequence for such a batch
+    case Route::fused8: return (b.react || b.nlflux) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
     case Route::twopass: return run_twopass(h, b, h->gradbuf, fx);
   }
 }
@@ -1460,6 +1550,7 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   p.Xf = h->fX; p.Nf = h->fN; p.fcoef = h->fcoef; p.flabel = h->flabel; p.nF = h->nF; p.fbiDimVal = h->fbiDimVal;
   p.w[0] = h->w[0]; p.w[1] = h->w[1]; p.w[2] = h->w[2];
   p.react = b.react ? 1 : 0; p.rate = b.rate; p.coef[0] = b.rc[0]; p.coef[1] = b.rc[1]; p.coef[2] = b.rc[2];
+  p.nlflux = b.nlflux ? 1 : 0; p.phi = b.phi; p.fcoef3[0] = b.fc[0]; p.fcoef3[1] = b.fc[1]; p.fcoef3[2] = b.fc[2];
   hipError_t e = vn_obj64_run(h->o64, p, grad_dev, lossVec_dev, out, h->ncu, h->stream);
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(h->stream);

@@ -30,6 +30,8 @@ struct VnObj64Problem {
   double w[3];
   // reaction term of the batch (vn_set_reaction): rate [n_k*q] or nullptr (1), coef c1..c3; react == 0: none
   int react; const float* rate; double coef[3];
+  // flux term of the batch (vn_set_nlflux): phi [n_k*q], coefficients f1..f3; nlflux == 0: none
+  int nlflux; const float* phi; double fcoef3[3];
 };
 
 bool vn_obj64_supported(const VnNet& net);

@@ -344,6 +344,7 @@ struct SeedArgs {
   double w0, w1, w2;
   int seeds;                                  // write the adjoint seeds in place of (u, ud)
   int react; const float* rate; double c1, c2, c3;   // reaction rate p(u), p = c1 u + c2 u^2 + c3 u^3 (react == 0: none)
+  int nlflux; const float* phi; double f1, f2, f3;   // flux term -F(u) phi, F = f1 u + f2 u^2 + f3 u^3 (nlflux == 0: none)
   double* lossVec; double* lpart;             // [n_k] or nullptr; [gridDim.x][4]
 };
 
@@ -374,6 +375,10 @@ __global__ __launch_bounds__(256) void vn_obj64_seed_kernel(SeedArgs a) {
         const double se = (a.source ? (double)a.source[r] : 0.0) + (a.rate ? (double)a.rate[r] * pu : pu);
         t -= se * (double)(a.Nrow ? a.Nrow[r] : a.feN[p]);
       } else if (a.source) t -= (double)a.source[r] * (double)(a.Nrow ? a.Nrow[r] : a.feN[p]);
+      if (a.nlflux) {
+        const double uu = a.u[r];
+        t -= uu * (a.f1 + uu * (a.f2 + uu * a.f3)) * (double)a.phi[r];
+      }
       if (a.feW) t *= (double)a.feW[p];
       R += t;
     }
@@ -391,6 +396,10 @@ __global__ __launch_bounds__(256) void vn_obj64_seed_kernel(SeedArgs a) {
           const double uu = a.u[r];
           const double dp = a.c1 + uu * (2.0 * a.c2 + 3.0 * a.c3 * uu);
           ub -= (double)(a.Nrow ? a.Nrow[r] : a.feN[p]) * (a.rate ? (double)a.rate[r] * dp : dp) * s;
+        }
+        if (a.nlflux) {                             // d t / d u of the flux term: -phi F'(u)
+          const double uu = a.u[r];
+          ub -= (double)a.phi[r] * (a.f1 + uu * (2.0 * a.f2 + 3.0 * a.f3 * uu)) * s;
         }
         a.u[r] = ub;
       }
@@ -553,6 +562,7 @@ hipError_t vn_obj64_run(VnObj64Work& w, const VnObj64Problem& p, double* grad_de
   sa.w0 = p.w[0]; sa.w1 = p.w[1]; sa.w2 = p.w[2];
   sa.seeds = grad_dev ? 1 : 0;
   sa.react = p.react; sa.rate = p.rate; sa.c1 = p.coef[0]; sa.c2 = p.coef[1]; sa.c3 = p.coef[2];
+  sa.nlflux = p.nlflux; sa.phi = p.phi; sa.f1 = p.fcoef3[0]; sa.f2 = p.fcoef3[1]; sa.f3 = p.fcoef3[2];
   sa.lossVec = lossVec_dev; sa.lpart = w.lpart;
   hipLaunchKernelGGL(vn_obj64_seed_kernel, dim3(sblk), dim3(256), 0, s, sa);
   OCHK(hipGetLastError());

@@ -64,6 +64,7 @@ _SIGS = {
     'vn_set_batch_bic': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'vn_set_flux_bc': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
     'vn_set_reaction': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
+    'vn_set_nlflux': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_bind_grad_buffer': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vn_grad': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -370,6 +371,7 @@ class VNEngine:
         self._ck(self.lib.vn_set_interior(self.h, batch, _ptr(Input), _ptr(gcoef), _ptr(source), n_k,
                                           _ptr(detJv), detJ_s, _ptr(Nr), _ptr(dNr)))
         self._keep.pop(('react', batch), None)       # vn_set_interior cleared the batch's reaction term
+        self._keep.pop(('nlflux', batch), None)      # ... and its flux term
 
     def set_dedup(self, batch, Xu=None, uid=None, rowptr=None, rowidx=None):
         """Register (or, with Xu=None, clear) the de-duplicated formulation of `batch`."""
@@ -458,6 +460,28 @@ class VNEngine:
                 'rate must have one entry per interior row (%s != %s)' % (rate.numel(), kept[0].shape[0])
         self._ck(self.lib.vn_set_reaction(self.h, int(batch), _ptr(rate), (C.c_double * 3)(*c)))
         self._keep[('react', batch)] = rate
+
+    def set_nlflux(self, batch, phi=None, coef=None):
+        """Register (or, with coef=None or all zero, clear) the flux term -div(w F(u)), F(u) = f1 u + f2 u^2 + f3 u^3, of `batch`
+        (vn_set_nlflux), after set_interior of that batch: phi = sum_d w_d dN/dx_d, one value per interior row, coef up to three
+        numbers (a shorter list is zero-padded)."""
+        c = [] if coef is None else [float(x) for x in np.reshape(np.asarray(coef, dtype=np.float64), -1)]
+        if len(c) > 3:
+            raise ValueError('a flux term takes at most three coefficients (f1, f2, f3), got %d' % len(c))
+        c = c + [0.0] * (3 - len(c))
+        if coef is None or not any(c):
+            self._keep.pop(('nlflux', batch), None)
+            self._ck(self.lib.vn_set_nlflux(self.h, int(batch), None, None))
+            return
+        if phi is not None:
+            t = self.torch
+            phi = self.dev(phi.reshape(-1) if isinstance(phi, t.Tensor) else np.reshape(phi, -1))
+            # the ABI carries a pointer only: the length the kernels rely on is checked here
+            kept = self._keep.get(('int', batch))
+            assert kept is None or phi.numel() == kept[0].shape[0], \
+                'phi must have one entry per interior row (%s != %s)' % (phi.numel(), kept[0].shape[0])
+        self._ck(self.lib.vn_set_nlflux(self.h, int(batch), _ptr(phi), (C.c_double * 3)(*c)))
+        self._keep[('nlflux', batch)] = phi
 
     def set_weights(self, w):
         arr = (C.c_double * 3)(*[float(x) for x in w])
@@ -557,9 +581,10 @@ class VNEngine:
         self._ck(self.lib.vn_forward_f64(self.h, _ptr(X), X.shape[0], _ptr(u)))
         return u
 
-    def residual(self, X, diff, vel, source=None, diff_dx=None, fp64=False, reaction=None):
+    def residual(self, X, diff, vel, source=None, diff_dx=None, fp64=False, reaction=None, nlflux=None):
         """(u, strong residual) at X.  reaction=(rate, coef): the residual gains rate * (c1 u + c2 u^2 + c3 u^3), rate a number,
-        one value per point or None (1)."""
+        one value per point or None (1).  nlflux=(w, coef, div_w): the residual gains -(F'(u) w . grad u + F(u) div w),
+        F(u) = f1 u + f2 u^2 + f3 u^3, w [n, dim] (or `dim` numbers), div_w one value per point, a number or None (0)."""
         t = self.torch
         dt = t.float64 if fp64 else t.float32
         X = self.dev(X, dt)
@@ -570,6 +595,20 @@ class VNEngine:
         diff_dx = None if diff_dx is None else self.dev(np.reshape(diff_dx, (n, self.dim)), dt)
         u = t.empty(n, dtype=dt, device=self.device)
         r = t.empty(n, dtype=dt, device=self.device)
+        fu = None
+        if nlflux is not None:
+            # the residual is affine in vel: the flux term's F'(u) w . grad u rides as an extra velocity, with u from the forward
+            w, fcoef, div_w = nlflux
+            f = [float(x) for x in np.reshape(np.asarray(fcoef, dtype=np.float64), -1)]
+            f = f + [0.0] * (3 - len(f))
+            w = w if isinstance(w, t.Tensor) else np.asarray(w, dtype=np.float64)
+            w = self.dev(w.reshape(-1, self.dim), dt)                # [n, dim] or [1, dim]
+            u0 = self.forward_f64(X) if fp64 else self.forward(X)
+            vel = vel + (f[0] + u0 * (2.0 * f[1] + 3.0 * f[2] * u0)).unsqueeze(1) * w
+            if div_w is not None:
+                fu = u0 * (f[0] + u0 * (f[1] + u0 * f[2]))
+                fu = fu * (float(div_w) if np.ndim(div_w) == 0 and not isinstance(div_w, t.Tensor) else self.dev(
+                    div_w.reshape(-1) if isinstance(div_w, t.Tensor) else np.reshape(div_w, -1), dt))
         fn = self.lib.vn_residual_f64 if fp64 else self.lib.vn_residual
         self._ck(fn(self.h, _ptr(X), _ptr(diff), _ptr(vel), _ptr(source), _ptr(diff_dx), n, _ptr(u), _ptr(r)))
         if reaction is not None:
@@ -581,6 +620,8 @@ class VNEngine:
                 pu = pu * (float(rate) if np.ndim(rate) == 0 and not isinstance(rate, t.Tensor) else self.dev(
                     rate.reshape(-1) if isinstance(rate, t.Tensor) else np.reshape(rate, -1), dt))
             r = r + pu
+        if fu is not None:
+            r = r - fu
         return u, r
 
     # -- towers: RCCL communicator inside the engine (TFModel.py:253-289, 342-377) ---------------

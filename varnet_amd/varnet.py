@@ -296,6 +296,8 @@ class TrainResult:
         L.append('\n')
         if getattr(PDE, 'reaction', None) is not None:
             L.append('Reaction term: rate*(c1 c + c2 c^2 + c3 c^3), coefficients %s\n\n' % str(list(PDE.reactionCoef)))
+        if getattr(PDE, 'nlflux', None) is not None:
+            L.append('Flux term: -div(w*(f1 c + f2 c^2 + f3 c^3)), coefficients %s\n\n' % str(list(PDE.nlfluxCoef)))
         L.append('Neural Network architecture:\n')
         L.append('\ttype: ' + str(varNet.modelId) + '\n')
         L.append('\tnumber of inputs: ' + str(varNet.inpDim) + '\n')
@@ -583,7 +585,7 @@ class ManageTrainData:
         for mb, d in enumerate(self.mor):
             if self.shuffled:                     # one gather per array and parameter batch; the blocks are views of it
                 d = dict(d)
-                for key in ('Input', 'gcoef', 'source', 'N_rows', 'dNt_rows', 'rate'):
+                for key in ('Input', 'gcoef', 'source', 'N_rows', 'dNt_rows', 'rate', 'phi'):
                     if d.get(key) is not None:
                         d[key] = d[key].index_select(0, rows_all)
                 if d.get('detJ') is not None:
@@ -598,6 +600,8 @@ class ManageTrainData:
                                  N_rows=pick(d.get('N_rows')), dNt_rows=pick(d.get('dNt_rows')))
                 if d.get('reactCoef') is not None and n1 > n0:      # the reaction term of these rows (vn_set_reaction)
                     eng.set_reaction(self.engine_batch(mb, bi), pick(d.get('rate')), d['reactCoef'])
+                if d.get('phi') is not None and n1 > n0:            # the flux term of these rows (vn_set_nlflux)
+                    eng.set_nlflux(self.engine_batch(mb, bi), pick(d['phi']), d['nlfluxCoef'])
                 perm = getattr(self, 'biPerm', {}).get(bi)
                 if perm is not None and hasattr(eng, 'set_batch_bic'):
                     ix = torch.as_tensor(perm, device=eng.device, dtype=torch.long)
@@ -1184,6 +1188,23 @@ class VarNet:
                              % (rate.shape, Input.shape[0]))
         return rate.reshape(-1, 1)
 
+    def _nlflux_field(self, Input):
+        """(w [n, dim], div w [n, 1] or None) of the flux term at the rows of Input, evaluated like the velocity (PDEinpData)."""
+        dim, PDE = self.dim, self.PDE
+        targ = [Input[:, dim][np.newaxis].T] if PDE.timeDependent else []
+        n = Input.shape[0]
+        w = np.asarray(PDE.nlfluxWFun(Input[:, 0:dim], *targ), dtype=np.float64)
+        if w.size != n * dim:
+            raise ValueError('the flux field w must return [n, dim] values, got shape %s for %d points in %d dimension(s)'
+                             % (w.shape, n, dim))
+        div = None
+        if PDE.nlfluxDivFun is not None:
+            div = np.asarray(PDE.nlfluxDivFun(Input[:, 0:dim], *targ), dtype=np.float64)
+            if div.size != n:
+                raise ValueError('div_w must return one value per point (a column), got shape %s for %d points' % (div.shape, n))
+            div = div.reshape(-1, 1)
+        return w.reshape(n, dim), div
+
     def MORargExtract(self, batch, MORdiscArg):
         """Keyword arguments of every parametric callable for MOR batch `batch`, and the extra
         network inputs, in the reference's order (VarNet.py:901-1049): BC functions, IC, diff,
@@ -1246,7 +1267,18 @@ class VarNet:
                 reactCoef = [self.PDE.reactionRate * c for c in reactCoef]
             else:
                 rate = eng.dev(np.asarray(self._reaction_rate(Input), dtype=np.float64).reshape(-1))
+        phi = nlfluxCoef = None
+        if getattr(self.PDE, 'nlflux', None) is not None:
+            # phi = sum_d w_d dN/dx_d at the rows of Input in fp64, beside gcoef; uploaded as fp32
+            w = self._nlflux_field(Input)[0]
+            if fd.detJvec:
+                phi = (w * dNxr).sum(1)
+            else:
+                phi = (w.reshape(nt, q, dim) * fd.dNx[None]).sum(-1)
+            phi = eng.dev(np.asarray(phi, dtype=np.float64).reshape(-1))
+            nlfluxCoef = list(self.PDE.nlfluxCoef)
         return dict(Input=eng.dev(Input), Input_host=Input, gcoef=eng.dev(gcoef), rate=rate, reactCoef=reactCoef,
+                    phi=phi, nlfluxCoef=nlfluxCoef,
                     source=eng.dev(src.reshape(-1)) if self.lossOpt['isSource'] else None,
                     biInput=eng.dev(biInput), biLabel=eng.dev(biLabel.reshape(-1)),
                     N_rows=N_rows, dNt_rows=dNt_rows,
@@ -2092,6 +2124,9 @@ class VarNet:
             rkw = {}
             if getattr(PDE, 'reaction', None) is not None:           # res += rate p(u)
                 rkw['reaction'] = (self._reaction_rate(Input).reshape(-1), PDE.reactionCoef)
+            if getattr(PDE, 'nlflux', None) is not None:             # res -= F'(u) w . grad u + F(u) div w
+                w_rows, divw_rows = self._nlflux_field(Input)
+                rkw['nlflux'] = (w_rows, PDE.nlfluxCoef, divw_rows)
             u, r = self.engine.residual(Inp, diff, vel, src, diff_dx, fp64=fp64, **rkw)
             cApp = u.cpu().numpy().astype(np.float64).reshape(-1, 1)
             resVec = r.cpu().numpy().astype(np.float64).reshape(-1, 1)
