@@ -231,6 +231,30 @@ int vn_set_reaction(vn_engine* h, int32_t batch, const float* rate_dev, const do
  * a map and a flux term); the 4-wave cross-check geometry (VN_KERNEL_FUSED) returns VN_EUNSUPPORTED.  Without a registration
  * nothing is launched, nothing is allocated and every result is bit for bit what it is without this call. */
 int vn_set_nlflux(vn_engine* h, int32_t batch, const float* phi_dev, const double coef[3]);
+/* OPTIONAL, no reference counterpart: a solution-dependent diffusivity (quasilinear diffusion) for `batch`,
+ *     c_t = div( kappa(x,t) D(c) grad c ) - v.grad c - div( w F(c) ) + s + rate p(c),     D(c) = d0 + d1 c + d2 c^2
+ * (porous medium c_t = Lap(c^m): D = m c^(m-1); temperature-dependent conductivity; Richards-type moisture transport).
+ * THE CALLER'S SIDE: the engine carries one tangent per row, along gcoef, and D(u) must scale the diffusion part only.  On a batch
+ * with this term gcoef (vn_set_interior) is  kappa dN/dx  ALONE -- without the v N part -- and the advection comes on the value
+ * side: int v.grad u N = -int u (v.grad N + N div v), the test functions vanishing on the edge of their supports, so with
+ *     psi_r = sum_d v_d(x_r, t_r) dN_r/dx_d + N_r div v(x_r, t_r)        and       A_r = sum_d u_{x_d} gcoef_d
+ * the row integrand (TFModel.py:653-657) becomes  D(u) A - u psi - u dNt - (s + rate p(u)) N - F(u) phi,  everything after it is
+ * unchanged, the value seed of a row gains  (D'(u) A - psi)  times the row's tangent seed and the tangent seed is scaled by D(u).
+ * Nothing divides by D(u): D(0) = 0 (the porous-medium case) is a regular point.
+ *   psi_dev   [n_k*integ_num] device floats, one per interior row, or NULL when v is identically zero.  READ on every step (it
+ *             must stay valid while registered), like phi_dev.
+ *   coef      {d0, d1, d2}; NULL, or {1, 0, 0} together with psi_dev == NULL, clears the registration.  Non-finite: VN_EINVAL.
+ * Per batch, called after vn_set_interior of that batch: a new vn_set_interior clears it, vn_set_dedup, vn_set_reaction and
+ * vn_set_nlflux keep it, and this call keeps a registered map, reaction and flux term.  An unregistered batch: VN_ESTATE; a batch
+ * without interior rows (n_k == 0): VN_EINVAL.  A change invalidates the L-BFGS (f_k, g_k) and ring of that batch.
+ * vn_grad / vn_train_step / vn_train_epoch, vn_eval_loss (lossVec included), vn_lbfgs_step and vn_objective_f64 all see the term.
+ * Routes: the generic, layer-by-layer and two-pass routes run two elementwise kernels (vn_nldiff.hip) around their row-wise seed
+ * kernel and the flux term's pair, with A_r saved in an engine-owned [n_k*integ_num] buffer that the first registration allocates;
+ * a batch of the single-launch 8-wave route runs the two-pass sequence instead; the de-duplicated step adds two small kernels (the
+ * first divides by the table entries N_p of vn_set_fe_table: a zero entry is VN_EUNSUPPORTED for a batch that has both a map and
+ * this term); the 4-wave cross-check geometry (VN_KERNEL_FUSED) returns VN_EUNSUPPORTED.  Without a registration nothing is
+ * launched, nothing is allocated and every result is bit for bit what it is without this call. */
+int vn_set_nldiff(vn_engine* h, int32_t batch, const float* psi_dev, const double coef[3]);
 /* updateDictFields('trainW') (VarNetUtility.py:921-922); the caller applies the
  * w[0:2] /= batchNum*puNum rule (VarNetUtility.py:900-901). */
 int vn_set_weights(vn_engine* h, const double w[3]);
@@ -278,7 +302,7 @@ int vn_train_epoch(vn_engine* h, const int32_t* batches, int32_t n, float* loss_
  * info = {status, f_k, f_{k+1}, BC, IC, var at theta_{k+1}, accepted t, trials used, g_k.d, pairs the direction was formed from}
  * (after a status != 0: f_{k+1} = f_k, the components of theta_k, t = 0).
  * vn_params_init, vn_params_set, vn_state_import, vn_set_bic, vn_set_flux_bc, vn_set_interior / vn_set_dedup /
- * vn_set_batch_bic / vn_set_reaction / vn_set_nlflux of that batch, a call with another `batch` than the previous one and vn_set_weights invalidate (f_k, g_k) and
+ * vn_set_batch_bic / vn_set_reaction / vn_set_nlflux / vn_set_nldiff of that batch, a call with another `batch` than the previous one and vn_set_weights invalidate (f_k, g_k) and
  * drop the ring -- vn_set_weights when the call finds other weights than (f_k, g_k) were evaluated with (weights changed and put
  * back between two calls, as the monitors of VarNet.train do, leave the objective and therefore the optimizer alone).
  * vn_state_export writes the two slots as zeros and vn_state_import ignores them; the ring is not part of a checkpoint. */

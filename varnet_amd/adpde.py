@@ -1,13 +1,13 @@
 """
 Advection-diffusion(-reaction) PDE container: `ADPDE(domain, diff, vel, source, timeDependent, tInterval,
-BCs, IC, cEx, MORvar, d_diff, reaction, nlflux)` -- /root/reference/ADPDE.py:56-246 restated (plot helpers are
+BCs, IC, cEx, MORvar, d_diff, reaction, nlflux, nldiff)` -- /root/reference/ADPDE.py:56-246 restated (plot helpers are
 out of scope).
 
-    c_t = div(diff grad c) - vel . grad c - div(w F(c)) + source + rate * p(c),    a * dc/dn + b * c = g  on each edge,
+    c_t = div(diff D(c) grad c) - vel . grad c - div(w F(c)) + source + rate * p(c),    a * dc/dn + b * c = g  on each edge,
 
-with the optional polynomial reaction p(c) = c1 c + c2 c^2 + c3 c^3 (`reaction=(rate, [c1, c2, c3])`) and the optional
-polynomial flux F(c) = f1 c + f2 c^2 + f3 c^3 (`nlflux=(w, [f1, f2, f3])`); neither has a reference counterpart, both are
-absent by default.
+with the optional polynomial reaction p(c) = c1 c + c2 c^2 + c3 c^3 (`reaction=(rate, [c1, c2, c3])`), the optional
+polynomial flux F(c) = f1 c + f2 c^2 + f3 c^3 (`nlflux=(w, [f1, f2, f3])`) and the optional solution-dependent diffusivity
+D(c) = d0 + d1 c + d2 c^2 (`nldiff=[d0, d1, d2]`; D = 1 without it); none has a reference counterpart, all are absent by default.
 
 Constants are wrapped into callables f(x[, t]) returning column arrays; every BC is normalised
 to [a, b, g(x,t)] and classified Dirichlet / Neumann / Robin; with a `MOR` instance a lookup
@@ -33,10 +33,18 @@ class ADPDE:
     `dim` numbers or a callable f(x[, t]) returning [n, dim], like `vel`.  `div_w` is an optional callable f(x[, t]) returning
     the divergence of w as a column; only the strong residual uses it, and without it the divergence is taken as zero: `w`
     must then be constant or divergence-free.  Inviscid problems (shocks) are the user's responsibility.  None: no flux term.
+
+    nldiff=[d0, d1, d2] or ([d0, d1, d2], div_vel) makes the diffusion quasilinear: div(diff D(c) grad c) with D(c) = d0 + d1 c +
+    d2 c^2 (porous medium c_t = Lap(c^2): diff=1, nldiff=[0, 2]; conductivity k0 (1 + b c): diff=k0, nldiff=[1, b]).  `diff`
+    keeps its meaning as kappa(x, t); a shorter list is zero-padded, every entry is finite.  With the term the advection is
+    integrated by parts onto the test function, -int c (vel . grad N + N div vel): `div_vel` is an optional callable f(x[, t])
+    returning the divergence of vel as a column, and without it the divergence is taken as zero: `vel` must then be constant
+    or divergence-free.  D(c) = 0 somewhere (degenerate diffusion) is allowed; D(c) < 0 is the user's responsibility.
+    None (the default): no term, D = 1.
     """
 
     def __init__(self, domain, diff, vel, source=0.0, timeDependent=False, tInterval=None,
-                 BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None, nlflux=None):
+                 BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None, nlflux=None, nldiff=None):
         # the reference ignores the `timeDependent` argument (ADPDE.py:108-109)
         timeDependent = tInterval is not None
 
@@ -103,6 +111,25 @@ class ADPDE:
                                           'scope (the phi stream is assembled once, for all parameter batches)')
             fcoef = fcoef + [0.0] * (3 - len(fcoef))
 
+        if nldiff is not None:
+            if not isinstance(nldiff, (tuple, list, np.ndarray)) or len(nldiff) == 0:
+                raise ValueError('nldiff must be given as [d0, d1, d2] or ([d0, d1, d2], div_vel)!')
+            dcoef, ddiv = nldiff, None
+            if isinstance(nldiff, (tuple, list)) and len(nldiff) == 2 and isinstance(nldiff[0], (tuple, list, np.ndarray)):
+                dcoef, ddiv = nldiff
+            try:
+                dcoef = [float(c) for c in np.reshape(np.asarray(dcoef, dtype=float), -1)]
+            except (TypeError, ValueError):
+                raise ValueError('nldiff coefficients must be a list of up to three numbers [d0, d1, d2]!')
+            if not 1 <= len(dcoef) <= 3 or not np.all(np.isfinite(dcoef)):
+                raise ValueError('nldiff coefficients must be a list of up to three finite numbers [d0, d1, d2]!')
+            if ddiv is not None and not callable(ddiv):
+                raise ValueError('nldiff divergence div_vel must be callable (or left out: vel constant or divergence-free)!')
+            if MORvar is not None:
+                raise NotImplementedError('a solution-dependent diffusivity with model-order reduction is not supported: the psi '
+                                          'stream of the advection is assembled once, for all parameter batches')
+            dcoef = dcoef + [0.0] * (3 - len(dcoef))
+
         dim = domain.dim
 
         def const_field(val, ncol):
@@ -154,6 +181,13 @@ class ADPDE:
             self.nlfluxCoef = fcoef
             self.nlfluxDivFun = fdiv
             self.nlflux = (nlflux[0], fcoef) if fdiv is None else (nlflux[0], fcoef, fdiv)
+
+        # solution-dependent diffusivity D(c) = d0 + d1 c + d2 c^2: the three coefficients, the optional divergence of vel; None without
+        self.nldiff = None
+        if nldiff is not None:
+            self.nldiffCoef = dcoef
+            self.nldiffDivFun = ddiv
+            self.nldiff = dcoef if ddiv is None else (dcoef, ddiv)
 
         # boundary conditions -> [a, b, g]
         bIndNum = domain.bIndNum

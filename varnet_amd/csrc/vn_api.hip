@@ -4,6 +4,7 @@
 #include "vn_dedup.h"
 #include "vn_flux.h"
 #include "vn_lbfgs.h"
+#include "vn_nldiff.h"
 #include "vn_nlflux.h"
 #include "vn_obj64.h"
 #include "vn_pgrad16.h"
@@ -86,6 +87,10 @@ struct Batch {
   bool nlflux = false;
   const float* phi = nullptr;    // [n_k*integ_num]: sum_d w_d dN/dx_d per row
   double fc[3] = {0.0, 0.0, 0.0};
+  // solution-dependent diffusivity D(u) = d0 + d1 u + d2 u^2 of div(kappa D(u) grad u) (vn_set_nldiff); gcoef is then kappa dN/dx alone
+  bool nldiff = false;
+  const float* psi = nullptr;    // [n_k*integ_num]: sum_d v_d dN/dx_d + N div v per row, or nullptr (no advection)
+  double dc[3] = {1.0, 0.0, 0.0};
 };
 
 // How an engine computes its gradient, decided once by pick_route (vn_create).
@@ -171,6 +176,7 @@ struct vn_engine {
   long dd_uv_cap = 0, dd_su_cap = 0, dd_sg_cap = 0, dd_partial_cap = 0, dd_cap_lp = 0;
   bool feN_zero = false;      // the table of vn_set_fe_table has an entry N_p == 0 (the flux term's fold divides by N_p)
   float* rx_seff = nullptr; long rx_seff_cap = 0;   // reaction in the de-duplicated step: source + rate p(u) per row (vn_react.hip)
+  float* nd_A = nullptr; long nd_A_cap = 0;         // quasilinear diffusion on the row-wise routes: sum_d u_{x_d} gcoef_d per row (vn_nldiff.hip)
   // boundary-flux rows (vn_set_flux_bc): caller-owned inputs, engine-owned work buffers; nF == 0: none
   const float *fX = nullptr, *fN = nullptr, *fcoef = nullptr, *flabel = nullptr;
   long nF = 0;
@@ -488,6 +494,35 @@ int nlflux_dedup_check(const vn_engine* h, const Batch& b) {
   return VN_OK;
 }
 
+// Quasilinear diffusion of a batch on the row-wise routes (vn_nldiff.hip): values in h->u, A_r saved in h->nd_A
+VnNldiffRowArgs nldiff_row_args(const vn_engine* h, const Batch& b) {
+  VnNldiffRowArgs a{};
+  a.u = h->u; a.psi = b.psi; a.d0 = (float)b.dc[0]; a.d1 = (float)b.dc[1]; a.d2 = (float)b.dc[2];
+  a.nT = b.n_k * h->cfg.integ_num;
+  a.ud = h->ud; a.A = h->nd_A; a.udbar = h->udbar; a.ubar = h->ubar;
+  return a;
+}
+
+// ... and of a batch with a de-duplication map: on top of what the reaction and the flux term made of the source
+VnNldiffDedupArgs nldiff_dedup_args(const vn_engine* h, const Batch& b) {
+  VnNldiffDedupArgs a{};
+  a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
+  a.base = (b.react || b.nlflux) ? h->rx_seff : batch_src(h, b); a.gcoef = b.gcoef; a.psi = b.psi;
+  a.d0 = (float)b.dc[0]; a.d1 = (float)b.dc[1]; a.d2 = (float)b.dc[2];
+  a.feN = h->feN; a.feW = fe_w(h);
+  a.nT = b.n_k * h->cfg.integ_num; a.U = b.U; a.q = h->cfg.integ_num; a.dim = h->cfg.dim; a.gper = b.gper ? 1 : 0;
+  a.s_eff = h->rx_seff;
+  return a;
+}
+
+// Its fold into the de-duplicated assembly's source divides by N_p, like the flux term's: a zero table entry is an error code
+int nldiff_dedup_check(const vn_engine* h, const Batch& b) {
+  if (b.nldiff && b.Xu && h->feN_zero)
+    return fail(VN_EUNSUPPORTED, "the diffusivity D(u) of a de-duplicated batch needs test-function values N_p != 0 at every quadrature "
+                                 "point (vn_set_fe_table has a zero entry); clear the map (vn_set_dedup with Xu = NULL) to run row-wise");
+  return VN_OK;
+}
+
 // De-duplicated assembly (seed and gather kernels) of a batch with a de-duplication map, (u, grad u) of its points in h->dd_uv
 VnDedupArgs dedup_args(const vn_engine* h, const Batch& b) {
   VnDedupArgs a{};
@@ -573,6 +608,12 @@ int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst, con
     HIPCHK(vn_nlflux_source_launch(nlflux_dedup_args(h, b), h->stream));
     a.source = h->rx_seff;
   }
+  if (b.nldiff) {                                     // ... and ((1 - D(u)) A + u psi) / N_p on top of both
+    if (int rc = nldiff_dedup_check(h, b)) return rc;
+    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
+    HIPCHK(vn_nldiff_source_launch(nldiff_dedup_args(h, b), h->stream));
+    a.source = h->rx_seff;
+  }
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
   if (int rc = fused_forward(h, bi_x(h, b), nullptr, h->nB, h->ub, nullptr)) return rc;
   VnSeedArgs s = seed_args(h, b);
@@ -611,10 +652,17 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
   VnSeedArgs a = seed_args(h, b);
   if (with_seeds) { a.ubar = h->ubar; a.udbar = h->udbar; a.ubar_b = h->ubar_b; }
   a.lossVec = lossVec; a.part = h->losspart;
+  // quasilinear diffusion: ud = A becomes D(u) A - u psi before anything else edits it, and the seeds are rescaled after
+  // everything else has read the unscaled tangent seed (vn_nldiff.hip)
+  if (b.nldiff) {
+    if (int rc = ensure(&h->nd_A, &h->nd_A_cap, b.n_k * h->cfg.integ_num)) return rc;
+    HIPCHK(vn_nldiff_fold_launch(nldiff_row_args(h, b), h->stream));
+  }
   // flux term: -F(u) phi joins the row integrand before the seed kernel reads it, its value seed is added after (vn_nlflux.hip)
   if (b.nlflux) HIPCHK(vn_nlflux_fold_launch(nlflux_row_args(h, b), h->stream));
   HIPCHK(vn_seed_launch(a, grid, h->stream));
   if (b.nlflux && with_seeds) HIPCHK(vn_nlflux_seed_launch(nlflux_row_args(h, b), h->stream));
+  if (b.nldiff && with_seeds) HIPCHK(vn_nldiff_seed_launch(nldiff_row_args(h, b), h->stream));
   if (lossdst) {
     HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2, lossdst, h->stream,
                             VnOptArgs(), fx));
@@ -688,7 +736,7 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx)
 // 8 F_pt per point instead of 6, against 8 F_pt at 0.07 of peak on the generic kernels.
 // Also the step of a batch with a reaction term on the single-launch route, at any integ_num (vn_set_reaction): the term lives
 // in the seed kernel; neither mode of the fused kernel looks at integ_num.  A flux term (vn_set_nlflux) takes the same sequence,
-// with its two elementwise kernels around the seed kernel.
+// with its two elementwise kernels around the seed kernel, and so does a diffusivity D(u) (vn_set_nldiff), with its pair around those.
 int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
   const int grid = h->ncu, P = h->net.P;
   const int sgrid = (int)((b.n_k + 255) / 256);
@@ -705,9 +753,14 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& f
   a.ubar = h->ubar; a.udbar = h->udbar;
   a.ub = nullptr; a.label = nullptr; a.nB = 0; a.bDof = 0; a.biDimVal = 0.f;   // BC/IC: step 3
   a.part = lp + (long)grid * 3;
+  if (b.nldiff) {                                                                      // D(u), as in run_forward_and_seed
+    if (int rc = ensure(&h->nd_A, &h->nd_A_cap, b.n_k * h->cfg.integ_num)) return rc;
+    HIPCHK(vn_nldiff_fold_launch(nldiff_row_args(h, b), h->stream));
+  }
   if (b.nlflux) HIPCHK(vn_nlflux_fold_launch(nlflux_row_args(h, b), h->stream));      // flux term, as in run_forward_and_seed
   HIPCHK(vn_seed_launch(a, sgrid, h->stream));
   if (b.nlflux) HIPCHK(vn_nlflux_seed_launch(nlflux_row_args(h, b), h->stream));
+  if (b.nldiff) HIPCHK(vn_nldiff_seed_launch(nldiff_row_args(h, b), h->stream));
 
   f.mode = 2; f.out_u = nullptr; f.out_ud = nullptr; f.seed_u = h->ubar; f.seed_ud = h->udbar; f.nB = h->nB;
   if (int rc = prof_start(h)) return rc;
@@ -752,10 +805,20 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx)
     HIPCHK(vn_nlflux_source_launch(na, h->stream));
     a.source = h->rx_seff;
   }
+  VnNldiffDedupArgs da{};
+  if (b.nldiff) {                                     // ... and ((1 - D(u)) A + u psi) / N_p on top of both
+    if (int rc = nldiff_dedup_check(h, b)) return rc;
+    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
+    da = nldiff_dedup_args(h, b);
+    da.stf = a.stf; da.seed_u = a.seed_u; da.seed_g = a.seed_g;
+    HIPCHK(vn_nldiff_source_launch(da, h->stream));
+    a.source = h->rx_seff;
+  }
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
   HIPCHK(vn_dedup_gather_launch(a, h->stream));
   if (b.react) HIPCHK(vn_react_gather_launch(ra, h->stream));   // the term's value seed, added to the gathered one
   if (b.nlflux) HIPCHK(vn_nlflux_gather_launch(na, h->stream));
+  if (b.nldiff) HIPCHK(vn_nldiff_point_launch(da, h->stream));  // last: D'(u) grad u . seed_g needs the unscaled seed_g
   VnFusedArgs f = fused_args(h, &b);
   f.X = b.Xu; f.G = h->dd_sg; f.nT = b.U;
   f.partial = h->dd_partial; f.losspart = lp;
@@ -921,7 +984,7 @@ int vn_destroy(vn_engine* h) {
   if (h->comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(h->stream); (void)g_rccl.CommDestroy(h->comm); h->comm = nullptr; }
   void* ptrs[] = {h->theta, h->m, h->v, h->snap, h->theta64, h->gradbuf_int, h->lossbuf, h->partial, h->feN, h->fedNt,
                   h->feW, h->u, h->ud, h->ubar, h->udbar, h->ub, h->ubar_b, h->losspart, h->fused_losspart, h->stamps, h->dd_uv, h->dd_su, h->dd_sg, h->dd_partial,
-                  h->dd_losspart, h->rx_seff, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial,
+                  h->dd_losspart, h->rx_seff, h->nd_A, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial,
                   h->lb.ring, h->lb.theta_k, h->lb.g_k, h->lb.d, h->lb.part, h->lb.G, h->lb.coef, h->lb.meta};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -1107,6 +1170,7 @@ int vn_set_interior(vn_engine* h, int32_t batch, const float* Input, const float
   b.biInput = nullptr; b.biLabel = nullptr;                                            // ... and vn_set_batch_bic
   b.react = false; b.rate = nullptr; b.rc[0] = b.rc[1] = b.rc[2] = 0.0;                // ... and vn_set_reaction
   b.nlflux = false; b.phi = nullptr; b.fc[0] = b.fc[1] = b.fc[2] = 0.0;                // ... and vn_set_nlflux
+  b.nldiff = false; b.psi = nullptr; b.dc[0] = 1.0; b.dc[1] = b.dc[2] = 0.0;            // ... and vn_set_nldiff
   const long nT = n_k * h->cfg.integ_num;
   if (nT > h->work_rows) {
     long c0 = h->work_rows, c1 = h->work_rows, c2 = h->work_rows, c3 = h->work_rows;
@@ -1168,10 +1232,12 @@ int vn_set_dedup(vn_engine* h, int32_t batch, const float* Xu, int64_t U, const 
     if (int rc = ensure(&b.gcsr, &b.gcsr_cap, nT * dim)) return rc;
     HIPCHK(vn_dedup_permute_launch(b.gcoef, rowidx, b.gcsr, nT, dim, h->stream));
   }
-  if (b.react || b.nlflux)
+  if (b.react || b.nlflux || b.nldiff)
     if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, nT)) return rc;
   if (b.nlflux && h->feN_zero)
     return fail(VN_EUNSUPPORTED, "the flux term of batch %d cannot be de-duplicated: vn_set_fe_table has an entry N_p == 0", batch);
+  if (b.nldiff && h->feN_zero)
+    return fail(VN_EUNSUPPORTED, "the diffusivity D(u) of batch %d cannot be de-duplicated: vn_set_fe_table has an entry N_p == 0", batch);
   b.Xu = Xu; b.U = U; b.uid = uid; b.rowptr = rowptr; b.rowidx = rowidx;
   return VN_OK;
 }
@@ -1224,6 +1290,33 @@ int vn_set_nlflux(vn_engine* h, int32_t batch, const float* phi, const double co
   if (b.Xu)
     if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
   b.nlflux = true; b.phi = phi; b.fc[0] = coef[0]; b.fc[1] = coef[1]; b.fc[2] = coef[2];
+  return VN_OK;
+}
+
+int vn_set_nldiff(vn_engine* h, int32_t batch, const float* psi, const double coef[3]) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
+    return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
+  if (coef && !(std::isfinite(coef[0]) && std::isfinite(coef[1]) && std::isfinite(coef[2])))
+    return fail(VN_EINVAL, "diffusivity coefficients (%g, %g, %g) must be finite", coef[0], coef[1], coef[2]);
+  Batch& b = h->batches[batch];
+  if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no diffusion term to integrate", batch);
+  lbfgs_invalidate(h, batch);
+  if (!coef || (coef[0] == 1.0 && coef[1] == 0.0 && coef[2] == 0.0 && !psi)) {   // D = 1, no psi: clears; a map and the other terms stay
+    b.nldiff = false; b.psi = nullptr; b.dc[0] = 1.0; b.dc[1] = b.dc[2] = 0.0;
+    return VN_OK;
+  }
+  if (h->route == Route::fused4)
+    return fail(VN_EUNSUPPORTED, "the diffusivity D(u) is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its single "
+                                 "launch has no place for the term; every other kernel family carries it");
+  if (b.Xu && h->feN_zero)
+    return fail(VN_EUNSUPPORTED, "the diffusivity D(u) of batch %d cannot join its de-duplication map: vn_set_fe_table has an entry N_p == 0", batch);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // A_r of the row-wise routes: engine-owned, allocated when a batch first carries the term (the steps grow it if a larger batch follows)
+  if (int rc = ensure(&h->nd_A, &h->nd_A_cap, b.n_k * h->cfg.integ_num)) return rc;
+  if (b.Xu)
+    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
+  b.nldiff = true; b.psi = psi; b.dc[0] = coef[0]; b.dc[1] = coef[1]; b.dc[2] = coef[2];
   return VN_OK;
 }
 
@@ -1309,9 +1402,9 @@ int vn_grad(vn_engine* h, int32_t batch) {
     case Route::layered: return run_layered(h, b, h->gradbuf, fx);
     case Route::generic: return run_generic(h, b, h->gradbuf, fx);
     case Route::fused4: return run_fused(h, b, h->gradbuf, fx);
-    // a reaction term lives in the row-wise seed kernel, a flux term around it: the single-launch route runs the two-pass
-    // sequence for such a batch
-    case Route::fused8: return (b.react || b.nlflux) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
+    // a reaction term lives in the row-wise seed kernel, a flux term and a diffusivity D(u) around it: the single-launch route
+    // runs the two-pass sequence for such a batch
+    case Route::fused8: return (b.react || b.nlflux || b.nldiff) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
     case Route::twopass: return run_twopass(h, b, h->gradbuf, fx);
   }
 }
@@ -1551,6 +1644,7 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   p.w[0] = h->w[0]; p.w[1] = h->w[1]; p.w[2] = h->w[2];
   p.react = b.react ? 1 : 0; p.rate = b.rate; p.coef[0] = b.rc[0]; p.coef[1] = b.rc[1]; p.coef[2] = b.rc[2];
   p.nlflux = b.nlflux ? 1 : 0; p.phi = b.phi; p.fcoef3[0] = b.fc[0]; p.fcoef3[1] = b.fc[1]; p.fcoef3[2] = b.fc[2];
+  p.nldiff = b.nldiff ? 1 : 0; p.psi = b.psi; p.dcoef3[0] = b.dc[0]; p.dcoef3[1] = b.dc[1]; p.dcoef3[2] = b.dc[2];
   hipError_t e = vn_obj64_run(h->o64, p, grad_dev, lossVec_dev, out, h->ncu, h->stream);
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(h->stream);

@@ -32,6 +32,8 @@ struct VnObj64Problem {
   int react; const float* rate; double coef[3];
   // flux term of the batch (vn_set_nlflux): phi [n_k*q], coefficients f1..f3; nlflux == 0: none
   int nlflux; const float* phi; double fcoef3[3];
+  // diffusivity D(u) of the batch (vn_set_nldiff): psi [n_k*q] or nullptr, coefficients d0..d2; nldiff == 0: none
+  int nldiff; const float* psi; double dcoef3[3];
 };
 
 bool vn_obj64_supported(const VnNet& net);

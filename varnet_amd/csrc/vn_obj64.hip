@@ -345,6 +345,7 @@ struct SeedArgs {
   int seeds;                                  // write the adjoint seeds in place of (u, ud)
   int react; const float* rate; double c1, c2, c3;   // reaction rate p(u), p = c1 u + c2 u^2 + c3 u^3 (react == 0: none)
   int nlflux; const float* phi; double f1, f2, f3;   // flux term -F(u) phi, F = f1 u + f2 u^2 + f3 u^3 (nlflux == 0: none)
+  int nldiff; const float* psi; double d0, d1, d2;   // D(u) ud - u psi for ud, D = d0 + d1 u + d2 u^2 (nldiff == 0: none; psi may be nullptr)
   double* lossVec; double* lpart;             // [n_k] or nullptr; [gridDim.x][4]
 };
 
@@ -368,6 +369,11 @@ __global__ __launch_bounds__(256) void vn_obj64_seed_kernel(SeedArgs a) {
     for (int p = 0; p < q; ++p) {
       const long r = base + p;
       double t = a.ud[r];
+      if (a.nldiff) {                               // quasilinear diffusion: the tangent part scaled by D(u), advection as -u psi
+        const double uu = a.u[r];
+        t *= a.d0 + uu * (a.d1 + uu * a.d2);
+        if (a.psi) t -= uu * (double)a.psi[r];
+      }
       if (a.td) t -= a.u[r] * (double)(a.dNtrow ? a.dNtrow[r] : a.fedNt[p]);
       if (a.react) {
         const double uu = a.u[r];
@@ -390,6 +396,7 @@ __global__ __launch_bounds__(256) void vn_obj64_seed_kernel(SeedArgs a) {
       for (int p = 0; p < q; ++p) {
         const long r = base + p;
         const double s = a.feW ? s0 * (double)a.feW[p] : s0;
+        const double A = a.ud[r];                   // the forward's directional derivative, before the seed takes its place
         a.ud[r] = s;
         double ub = a.td ? -(double)(a.dNtrow ? a.dNtrow[r] : a.fedNt[p]) * s : 0.0;
         if (a.react) {                              // u[r] still holds the forward value here
@@ -400,6 +407,11 @@ __global__ __launch_bounds__(256) void vn_obj64_seed_kernel(SeedArgs a) {
         if (a.nlflux) {                             // d t / d u of the flux term: -phi F'(u)
           const double uu = a.u[r];
           ub -= (double)a.phi[r] * (a.f1 + uu * (2.0 * a.f2 + 3.0 * a.f3 * uu)) * s;
+        }
+        if (a.nldiff) {                             // d t / d u = D'(u) A - psi; the tangent seed scaled by D(u)
+          const double uu = a.u[r];
+          ub += ((a.d1 + 2.0 * a.d2 * uu) * A - (a.psi ? (double)a.psi[r] : 0.0)) * s;
+          a.ud[r] = (a.d0 + uu * (a.d1 + uu * a.d2)) * s;
         }
         a.u[r] = ub;
       }
@@ -563,6 +575,7 @@ hipError_t vn_obj64_run(VnObj64Work& w, const VnObj64Problem& p, double* grad_de
   sa.seeds = grad_dev ? 1 : 0;
   sa.react = p.react; sa.rate = p.rate; sa.c1 = p.coef[0]; sa.c2 = p.coef[1]; sa.c3 = p.coef[2];
   sa.nlflux = p.nlflux; sa.phi = p.phi; sa.f1 = p.fcoef3[0]; sa.f2 = p.fcoef3[1]; sa.f3 = p.fcoef3[2];
+  sa.nldiff = p.nldiff; sa.psi = p.psi; sa.d0 = p.dcoef3[0]; sa.d1 = p.dcoef3[1]; sa.d2 = p.dcoef3[2];
   sa.lossVec = lossVec_dev; sa.lpart = w.lpart;
   hipLaunchKernelGGL(vn_obj64_seed_kernel, dim3(sblk), dim3(256), 0, s, sa);
   OCHK(hipGetLastError());

@@ -65,6 +65,7 @@ _SIGS = {
     'vn_set_flux_bc': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
     'vn_set_reaction': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_nlflux': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
+    'vn_set_nldiff': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_bind_grad_buffer': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vn_grad': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -372,6 +373,7 @@ class VNEngine:
                                           _ptr(detJv), detJ_s, _ptr(Nr), _ptr(dNr)))
         self._keep.pop(('react', batch), None)       # vn_set_interior cleared the batch's reaction term
         self._keep.pop(('nlflux', batch), None)      # ... and its flux term
+        self._keep.pop(('nldiff', batch), None)      # ... and its diffusivity D(u)
 
     def set_dedup(self, batch, Xu=None, uid=None, rowptr=None, rowidx=None):
         """Register (or, with Xu=None, clear) the de-duplicated formulation of `batch`."""
@@ -483,6 +485,29 @@ class VNEngine:
         self._ck(self.lib.vn_set_nlflux(self.h, int(batch), _ptr(phi), (C.c_double * 3)(*c)))
         self._keep[('nlflux', batch)] = phi
 
+    def set_nldiff(self, batch, psi=None, coef=None):
+        """Register (or, with coef=None, or coef (1, 0, 0) and psi=None, clear) the diffusivity D(u) = d0 + d1 u + d2 u^2 of the
+        quasilinear diffusion div(kappa D(u) grad u) of `batch` (vn_set_nldiff), after set_interior of that batch.  The batch's
+        gcoef must then be kappa dN/dx alone; psi = sum_d v_d dN/dx_d + N div v, one value per interior row, carries the
+        advection (None: no advection).  coef: up to three numbers (a shorter list is zero-padded)."""
+        c = [] if coef is None else [float(x) for x in np.reshape(np.asarray(coef, dtype=np.float64), -1)]
+        if len(c) > 3:
+            raise ValueError('a diffusivity takes at most three coefficients (d0, d1, d2), got %d' % len(c))
+        c = c + [0.0] * (3 - len(c))
+        if coef is None or (c == [1.0, 0.0, 0.0] and psi is None):
+            self._keep.pop(('nldiff', batch), None)
+            self._ck(self.lib.vn_set_nldiff(self.h, int(batch), None, None))
+            return
+        if psi is not None:
+            t = self.torch
+            psi = self.dev(psi.reshape(-1) if isinstance(psi, t.Tensor) else np.reshape(psi, -1))
+            # the ABI carries a pointer only: the length the kernels rely on is checked here
+            kept = self._keep.get(('int', batch))
+            assert kept is None or psi.numel() == kept[0].shape[0], \
+                'psi must have one entry per interior row (%s != %s)' % (psi.numel(), kept[0].shape[0])
+        self._ck(self.lib.vn_set_nldiff(self.h, int(batch), _ptr(psi), (C.c_double * 3)(*c)))
+        self._keep[('nldiff', batch)] = psi
+
     def set_weights(self, w):
         arr = (C.c_double * 3)(*[float(x) for x in w])
         self._ck(self.lib.vn_set_weights(self.h, arr))
@@ -581,10 +606,34 @@ class VNEngine:
         self._ck(self.lib.vn_forward_f64(self.h, _ptr(X), X.shape[0], _ptr(u)))
         return u
 
-    def residual(self, X, diff, vel, source=None, diff_dx=None, fp64=False, reaction=None, nlflux=None):
+    def _grad_u(self, X, fp64):
+        """(u [n], du/dx [n, dim]) at X for the residual's nonlinear terms.  fp32: forward_grad.  fp64: vn_residual_f64 is affine in
+        vel with slope -du/dx_d, so `dim` calls with unit velocities against one call with vel = 0 give the gradient."""
+        t = self.torch
+        if not fp64:
+            return self.forward_grad(X)
+        n = X.shape[0]
+        one = t.ones(n, dtype=t.float64, device=self.device)
+        vel = t.zeros((n, self.dim), dtype=t.float64, device=self.device)
+        u = t.empty(n, dtype=t.float64, device=self.device)
+        r0 = t.empty(n, dtype=t.float64, device=self.device)
+        self._ck(self.lib.vn_residual_f64(self.h, _ptr(X), _ptr(one), _ptr(vel), None, None, n, _ptr(u), _ptr(r0)))
+        g = t.empty((n, self.dim), dtype=t.float64, device=self.device)
+        rd = t.empty(n, dtype=t.float64, device=self.device)
+        for d in range(self.dim):
+            vel.zero_()
+            vel[:, d] = 1.0
+            self._ck(self.lib.vn_residual_f64(self.h, _ptr(X), _ptr(one), _ptr(vel), None, None, n, _ptr(u), _ptr(rd)))
+            g[:, d] = r0 - rd
+        return u, g
+
+    def residual(self, X, diff, vel, source=None, diff_dx=None, fp64=False, reaction=None, nlflux=None, nldiff=None):
         """(u, strong residual) at X.  reaction=(rate, coef): the residual gains rate * (c1 u + c2 u^2 + c3 u^3), rate a number,
         one value per point or None (1).  nlflux=(w, coef, div_w): the residual gains -(F'(u) w . grad u + F(u) div w),
-        F(u) = f1 u + f2 u^2 + f3 u^3, w [n, dim] (or `dim` numbers), div_w one value per point, a number or None (0)."""
+        F(u) = f1 u + f2 u^2 + f3 u^3, w [n, dim] (or `dim` numbers), div_w one value per point, a number or None (0).
+        nldiff=coef (d0, d1, d2): the diffusion term becomes div(diff D(u) grad u), D(u) = d0 + d1 u + d2 u^2, with no new kernel:
+        the residual entry point runs with diff -> diff D(u) and diff_dx -> D(u) diff_dx, and D'(u) diff |grad u|^2 is added;
+        u and grad u come from forward_grad (fp32) or from `dim` + 1 calls of vn_residual_f64 with unit velocities (fp64)."""
         t = self.torch
         dt = t.float64 if fp64 else t.float32
         X = self.dev(X, dt)
@@ -595,7 +644,17 @@ class VNEngine:
         diff_dx = None if diff_dx is None else self.dev(np.reshape(diff_dx, (n, self.dim)), dt)
         u = t.empty(n, dtype=dt, device=self.device)
         r = t.empty(n, dtype=dt, device=self.device)
-        fu = None
+        fu = dterm = None
+        if nldiff is not None:
+            dc = [float(x) for x in np.reshape(np.asarray(nldiff, dtype=np.float64), -1)]
+            dc = dc + [0.0] * (3 - len(dc))
+            u0, gu = self._grad_u(X, fp64)
+            Du = dc[0] + u0 * (dc[1] + u0 * dc[2])
+            # div(kappa D(u) grad u) = D kappa Lap u + D grad kappa . grad u + D'(u) kappa |grad u|^2
+            dterm = (dc[1] + 2.0 * dc[2] * u0) * diff * (gu * gu).sum(1)
+            diff = diff * Du
+            if diff_dx is not None:
+                diff_dx = diff_dx * Du.unsqueeze(1)
         if nlflux is not None:
             # the residual is affine in vel: the flux term's F'(u) w . grad u rides as an extra velocity, with u from the forward
             w, fcoef, div_w = nlflux
@@ -622,6 +681,8 @@ class VNEngine:
             r = r + pu
         if fu is not None:
             r = r - fu
+        if dterm is not None:
+            r = r + dterm
         return u, r
 
     # -- towers: RCCL communicator inside the engine (TFModel.py:253-289, 342-377) ---------------

@@ -298,6 +298,9 @@ class TrainResult:
             L.append('Reaction term: rate*(c1 c + c2 c^2 + c3 c^3), coefficients %s\n\n' % str(list(PDE.reactionCoef)))
         if getattr(PDE, 'nlflux', None) is not None:
             L.append('Flux term: -div(w*(f1 c + f2 c^2 + f3 c^3)), coefficients %s\n\n' % str(list(PDE.nlfluxCoef)))
+        if getattr(PDE, 'nldiff', None) is not None:
+            L.append('Solution-dependent diffusivity: div(diff*(d0 + d1 c + d2 c^2) grad c), coefficients %s\n\n'
+                     % str(list(PDE.nldiffCoef)))
         L.append('Neural Network architecture:\n')
         L.append('\ttype: ' + str(varNet.modelId) + '\n')
         L.append('\tnumber of inputs: ' + str(varNet.inpDim) + '\n')
@@ -585,7 +588,7 @@ class ManageTrainData:
         for mb, d in enumerate(self.mor):
             if self.shuffled:                     # one gather per array and parameter batch; the blocks are views of it
                 d = dict(d)
-                for key in ('Input', 'gcoef', 'source', 'N_rows', 'dNt_rows', 'rate', 'phi'):
+                for key in ('Input', 'gcoef', 'source', 'N_rows', 'dNt_rows', 'rate', 'phi', 'psi'):
                     if d.get(key) is not None:
                         d[key] = d[key].index_select(0, rows_all)
                 if d.get('detJ') is not None:
@@ -602,6 +605,8 @@ class ManageTrainData:
                     eng.set_reaction(self.engine_batch(mb, bi), pick(d.get('rate')), d['reactCoef'])
                 if d.get('phi') is not None and n1 > n0:            # the flux term of these rows (vn_set_nlflux)
                     eng.set_nlflux(self.engine_batch(mb, bi), pick(d['phi']), d['nlfluxCoef'])
+                if d.get('nldiffCoef') is not None and n1 > n0:     # the diffusivity D(u) of these rows (vn_set_nldiff)
+                    eng.set_nldiff(self.engine_batch(mb, bi), pick(d.get('psi')), d['nldiffCoef'])
                 perm = getattr(self, 'biPerm', {}).get(bi)
                 if perm is not None and hasattr(eng, 'set_batch_bic'):
                     ix = torch.as_tensor(perm, device=eng.device, dtype=torch.long)
@@ -1205,6 +1210,18 @@ class VarNet:
             div = div.reshape(-1, 1)
         return w.reshape(n, dim), div
 
+    def _vel_div(self, Input):
+        """div vel [n, 1] at the rows of Input, or None (taken as zero): the `div_vel` callable of `ADPDE(nldiff=...)`."""
+        dim, PDE = self.dim, self.PDE
+        if getattr(PDE, 'nldiffDivFun', None) is None:
+            return None
+        targ = [Input[:, dim][np.newaxis].T] if PDE.timeDependent else []
+        div = np.asarray(PDE.nldiffDivFun(Input[:, 0:dim], *targ), dtype=np.float64)
+        if div.size != Input.shape[0]:
+            raise ValueError('div_vel must return one value per point (a column), got shape %s for %d points'
+                             % (div.shape, Input.shape[0]))
+        return div.reshape(-1, 1)
+
     def MORargExtract(self, batch, MORdiscArg):
         """Keyword arguments of every parametric callable for MOR batch `batch`, and the extra
         network inputs, in the reference's order (VarNet.py:901-1049): BC functions, IC, diff,
@@ -1247,6 +1264,22 @@ class VarNet:
         diff, vel, src = self.PDEinpData(Input, inpArg)
         nt, q, dim = fd.nt, fd.integNum, self.dim
         N_rows = dNt_rows = None
+        psi = nldiffCoef = None
+        if getattr(self.PDE, 'nldiff', None) is not None:
+            # D(u) scales the diffusion part of the one tangent the engine carries: gcoef = kappa dN/dx alone, and the advection
+            # goes to the value side as -u psi, psi = sum_d v_d dN/dx_d + N div v (fp64 here, uploaded as fp32; None: vel == 0)
+            nldiffCoef = list(self.PDE.nldiffCoef)
+            div = self._vel_div(Input)
+            vel = np.asarray(vel, dtype=np.float64).reshape(-1, dim)
+            if fd.detJvec:
+                Nr, dNxr, dNtr = fd.rows()
+                psi = (vel * dNxr).sum(1, keepdims=True) + (0.0 if div is None else div * Nr.reshape(-1, 1))
+            else:
+                psi = (vel.reshape(nt, q, dim) * fd.dNx[None]).sum(-1)
+                if div is not None:
+                    psi = psi + div.reshape(nt, q) * np.reshape(fd.N, -1)[None, :]
+            psi = eng.dev(np.asarray(psi, dtype=np.float64).reshape(-1)) if np.any(psi) else None
+            vel = np.zeros_like(vel)
         if fd.detJvec:
             # non-uniform supports: per-row tables (VarNetUtility.py:506-523)
             Nr, dNxr, dNtr = fd.rows()
@@ -1278,7 +1311,7 @@ class VarNet:
             phi = eng.dev(np.asarray(phi, dtype=np.float64).reshape(-1))
             nlfluxCoef = list(self.PDE.nlfluxCoef)
         return dict(Input=eng.dev(Input), Input_host=Input, gcoef=eng.dev(gcoef), rate=rate, reactCoef=reactCoef,
-                    phi=phi, nlfluxCoef=nlfluxCoef,
+                    phi=phi, nlfluxCoef=nlfluxCoef, psi=psi, nldiffCoef=nldiffCoef,
                     source=eng.dev(src.reshape(-1)) if self.lossOpt['isSource'] else None,
                     biInput=eng.dev(biInput), biLabel=eng.dev(biLabel.reshape(-1)),
                     N_rows=N_rows, dNt_rows=dNt_rows,
@@ -2127,6 +2160,8 @@ class VarNet:
             if getattr(PDE, 'nlflux', None) is not None:             # res -= F'(u) w . grad u + F(u) div w
                 w_rows, divw_rows = self._nlflux_field(Input)
                 rkw['nlflux'] = (w_rows, PDE.nlfluxCoef, divw_rows)
+            if getattr(PDE, 'nldiff', None) is not None:             # div(kappa D(u) grad u); the advection stays v . grad u
+                rkw['nldiff'] = PDE.nldiffCoef
             u, r = self.engine.residual(Inp, diff, vel, src, diff_dx, fp64=fp64, **rkw)
             cApp = u.cpu().numpy().astype(np.float64).reshape(-1, 1)
             resVec = r.cpu().numpy().astype(np.float64).reshape(-1, 1)
