@@ -25,6 +25,8 @@ Bars:
   last hidden bias b5 deviates by 5.4e-4 (worst route) where the fp32 oracle deviates by 2.4e-4 (case bar 1.0e-3).
 
     python -m tests.fuzz_routes [cases] [seed] [oracle_every]      (soak; on the GPU box)
+
+The nonlinear PDE terms and the boundary-flux rows have a fuzz of their own on the same draws: tests/fuzz_terms.py.
 """
 import os
 import sys
