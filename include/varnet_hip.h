@@ -206,7 +206,7 @@ int vn_set_flux_bc(vn_engine* h, const float* X_dev, const float* normal_dev, co
  * included), vn_lbfgs_step and vn_objective_f64 all see the term.  Routes: the generic, layer-by-layer and two-pass routes carry it
  * in their row-wise seed kernel; a batch of the single-launch 8-wave route runs the two-pass sequence instead (forward-only launch,
  * seed kernel, seeded reverse launch: 8 F_pt per row instead of 6) at any integ_num; the de-duplicated step adds two small kernels
- * (vn_react.hip); the 4-wave cross-check geometry (VN_KERNEL_FUSED) returns VN_EUNSUPPORTED.  Without a registration nothing is
+ * (vn_terms.hip); the 4-wave cross-check geometry (VN_KERNEL_FUSED) returns VN_EUNSUPPORTED.  Without a registration nothing is
  * launched, nothing is allocated and every result is bit for bit what it is without this call. */
 int vn_set_reaction(vn_engine* h, int32_t batch, const float* rate_dev, const double coef[3]);
 /* OPTIONAL, no reference counterpart: a polynomial flux term (Burgers-type advection, scalar conservation laws) for `batch`,
@@ -225,7 +225,7 @@ int vn_set_reaction(vn_engine* h, int32_t batch, const float* rate_dev, const do
  * that batch, like vn_set_flux_bc.
  * With a flux term on the batch vn_grad / vn_train_step / vn_train_epoch (under a communicator as well), vn_eval_loss (lossVec
  * included), vn_lbfgs_step and vn_objective_f64 all see the term, together with a reaction of the same batch.  Routes: the generic,
- * layer-by-layer and two-pass routes run two elementwise kernels around their row-wise seed kernel (vn_nlflux.hip); a batch of the
+ * layer-by-layer and two-pass routes run two elementwise kernels around their row-wise seed kernel (vn_terms.hip); a batch of the
  * single-launch 8-wave route runs the two-pass sequence instead, at any integ_num; the de-duplicated step adds two small kernels
  * (they divide by the table entries N_p of vn_set_fe_table: a table with a zero entry is VN_EUNSUPPORTED for a batch that has both
  * a map and a flux term); the 4-wave cross-check geometry (VN_KERNEL_FUSED) returns VN_EUNSUPPORTED.  Without a registration
@@ -248,7 +248,7 @@ int vn_set_nlflux(vn_engine* h, int32_t batch, const float* phi_dev, const doubl
  * vn_set_nlflux keep it, and this call keeps a registered map, reaction and flux term.  An unregistered batch: VN_ESTATE; a batch
  * without interior rows (n_k == 0): VN_EINVAL.  A change invalidates the L-BFGS (f_k, g_k) and ring of that batch.
  * vn_grad / vn_train_step / vn_train_epoch, vn_eval_loss (lossVec included), vn_lbfgs_step and vn_objective_f64 all see the term.
- * Routes: the generic, layer-by-layer and two-pass routes run two elementwise kernels (vn_nldiff.hip) around their row-wise seed
+ * Routes: the generic, layer-by-layer and two-pass routes run two elementwise kernels (vn_terms.hip) around their row-wise seed
  * kernel and the flux term's pair, with A_r saved in an engine-owned [n_k*integ_num] buffer that the first registration allocates;
  * a batch of the single-launch 8-wave route runs the two-pass sequence instead; the de-duplicated step adds two small kernels (the
  * first divides by the table entries N_p of vn_set_fe_table: a zero entry is VN_EUNSUPPORTED for a batch that has both a map and

@@ -4,7 +4,7 @@ de-duplication maps: the cases, their seeded inputs and maps, the CSR builder an
 tests/nldiff_ref.py on the expanded rows Input = Xu[uid].  Plain module (no GPU, no pytest marks), shared by
 tests/test_dedup_terms_host.py and tests/test_dedup_terms_gpu.py.
 
-What each case is there for (the branches of vn_react.hip, vn_nlflux.hip, vn_nldiff.hip and of run_dedup / eval_dedup it reaches):
+What each case is there for (the branches of vn_terms.hip and of run_dedup / eval_dedup it reaches):
 
   bench_rand      the bench network on a random map: segments of 1..9 rows (the four-in-flight CSR loop beyond one pass and
                   its tails 1, 2, 3), a plain source below the terms (`base` non-null with each term alone)

@@ -5,7 +5,7 @@ extra launches show), ms per gradient step (vn_grad: every kernel of the step an
 variants see the same parameters) of five variants of the SAME engine and batch:
     row-wise                         the single-launch 8-wave step
     row-wise + D                     the two-pass sequence (forward-only launch, seed kernel, seeded reverse launch) with the two
-                                     elementwise kernels of vn_nldiff.hip around the seed kernel
+                                     elementwise kernels of vn_terms.hip around the seed kernel
     row-wise + reaction + flux + D   ... the flux term's pair inside those and the reaction inside the seed kernel
     dedup                            the de-duplicated step
     dedup + D                        ... plus vn_nldiff_source_kernel and vn_nldiff_point_kernel

@@ -4,12 +4,10 @@
 #include "vn_dedup.h"
 #include "vn_flux.h"
 #include "vn_lbfgs.h"
-#include "vn_nldiff.h"
-#include "vn_nlflux.h"
 #include "vn_obj64.h"
 #include "vn_pgrad16.h"
-#include "vn_react.h"
 #include "vn_taylor16.h"
+#include "vn_terms.h"
 #include "vn_split16.h"
 
 hipError_t vn_calibrate_f64(int ncu, hipStream_t s, double ghz, double out[3]);      // vn_calib.hip (fp64 MFMA loop)
@@ -17,6 +15,7 @@ hipError_t vn_calibrate_f64(int ncu, hipStream_t s, double ghz, double out[3]); 
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types and prototypes only: librccl is dlopen'ed by vn_comm_*, never linked
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -57,6 +56,13 @@ int fail(int code, const char* fmt, ...) {
     }                                                                         \
   } while (0)
 
+// One polynomial term of a batch's PDE
+struct Term {
+  bool on = false;
+  const float* stream = nullptr;   // [n_k*integ_num] per-row coefficient of the term, caller-owned
+  double c[3] = {0.0, 0.0, 0.0};
+};
+
 struct Batch {
   const float* Input = nullptr;
   const float* gcoef = nullptr;
@@ -79,19 +85,18 @@ struct Batch {
   float* gcsr = nullptr;      // owned: gcoef in CSR order, [n_k*integ_num, dim] (static per batch; built by vn_set_dedup)
   long gcsr_cap = 0;
   bool gper = false;          // gcoef repeats with period integ_num along the rows (constant coefficients): no CSR copy needed
-  // polynomial reaction term rate * (c1 u + c2 u^2 + c3 u^3) on the source side (vn_set_reaction)
-  bool react = false;
-  const float* rate = nullptr;   // [n_k*integ_num] or nullptr: rate == 1
-  double rc[3] = {0.0, 0.0, 0.0};
-  // polynomial flux term -div(w F(u)), F(u) = f1 u + f2 u^2 + f3 u^3, integrated by parts onto the test function (vn_set_nlflux)
-  bool nlflux = false;
-  const float* phi = nullptr;    // [n_k*integ_num]: sum_d w_d dN/dx_d per row
-  double fc[3] = {0.0, 0.0, 0.0};
-  // solution-dependent diffusivity D(u) = d0 + d1 u + d2 u^2 of div(kappa D(u) grad u) (vn_set_nldiff); gcoef is then kappa dN/dx alone
-  bool nldiff = false;
-  const float* psi = nullptr;    // [n_k*integ_num]: sum_d v_d dN/dx_d + N div v per row, or nullptr (no advection)
-  double dc[3] = {1.0, 0.0, 0.0};
+  // the polynomial terms (vn_terms.hip); as initialised here: not registered
+  // reaction rate * (c1 u + c2 u^2 + c3 u^3) on the source side (vn_set_reaction); stream = rate, or nullptr: rate == 1
+  Term react;
+  // flux -div(w F(u)), F(u) = f1 u + f2 u^2 + f3 u^3, integrated by parts onto the test function (vn_set_nlflux);
+  // stream = phi = sum_d w_d dN/dx_d per row
+  Term nlflux;
+  // diffusivity D(u) = d0 + d1 u + d2 u^2 of div(kappa D(u) grad u) (vn_set_nldiff); gcoef is then kappa dN/dx alone;
+  // stream = psi = sum_d v_d dN/dx_d + N div v per row, or nullptr: no advection
+  Term nldiff = {false, nullptr, {1.0, 0.0, 0.0}};
 };
+
+inline bool has_terms(const Batch& b) { return b.react.on || b.nlflux.on || b.nldiff.on; }
 
 // How an engine computes its gradient, decided once by pick_route (vn_create).
 enum class Route {
@@ -175,8 +180,8 @@ struct vn_engine {
   float *dd_uv = nullptr, *dd_su = nullptr, *dd_sg = nullptr, *dd_partial = nullptr, *dd_losspart = nullptr;
   long dd_uv_cap = 0, dd_su_cap = 0, dd_sg_cap = 0, dd_partial_cap = 0, dd_cap_lp = 0;
   bool feN_zero = false;      // the table of vn_set_fe_table has an entry N_p == 0 (the flux term's fold divides by N_p)
-  float* rx_seff = nullptr; long rx_seff_cap = 0;   // reaction in the de-duplicated step: source + rate p(u) per row (vn_react.hip)
-  float* nd_A = nullptr; long nd_A_cap = 0;         // quasilinear diffusion on the row-wise routes: sum_d u_{x_d} gcoef_d per row (vn_nldiff.hip)
+  float* rx_seff = nullptr; long rx_seff_cap = 0;   // the terms in the de-duplicated step: source + their shares per row (vn_terms.hip)
+  float* nd_A = nullptr; long nd_A_cap = 0;         // quasilinear diffusion on the row-wise routes: sum_d u_{x_d} gcoef_d per row (vn_terms.hip)
   // boundary-flux rows (vn_set_flux_bc): caller-owned inputs, engine-owned work buffers; nF == 0: none
   const float *fX = nullptr, *fN = nullptr, *fcoef = nullptr, *flabel = nullptr;
   long nF = 0;
@@ -449,78 +454,8 @@ VnSeedArgs seed_args(const vn_engine* h, const Batch& b) {
   a.n_k = b.n_k; a.integ_num = h->cfg.integ_num; a.time_dependent = h->cfg.time_dependent;
   a.ub = h->ub; a.label = bi_y(h, b); a.nB = h->nB; a.bDof = h->bDof; a.biDimVal = (float)h->biDimVal;
   a.w0 = (float)h->w[0]; a.w1 = (float)h->w[1]; a.w2 = (float)h->w[2];
-  if (b.react) { a.react = 1; a.rate = b.rate; a.c1 = (float)b.rc[0]; a.c2 = (float)b.rc[1]; a.c3 = (float)b.rc[2]; }
+  if (b.react.on) { a.react = 1; a.rate = b.react.stream; a.c1 = (float)b.react.c[0]; a.c2 = (float)b.react.c[1]; a.c3 = (float)b.react.c[2]; }
   return a;
-}
-
-// Reaction term of a batch with a de-duplication map (vn_react.hip): the values of its points in h->dd_uv
-VnReactArgs react_args(const vn_engine* h, const Batch& b) {
-  VnReactArgs a{};
-  a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
-  a.source = batch_src(h, b); a.rate = b.rate;
-  a.c1 = (float)b.rc[0]; a.c2 = (float)b.rc[1]; a.c3 = (float)b.rc[2];
-  a.feN = h->feN; a.feW = fe_w(h);
-  a.nT = b.n_k * h->cfg.integ_num; a.U = b.U; a.q = h->cfg.integ_num;
-  a.s_eff = h->rx_seff;
-  return a;
-}
-
-// Flux term of a batch on the row-wise routes (vn_nlflux.hip): values in h->u, integrand / seeds in h->ud, h->ubar, h->udbar
-VnNlfluxRowArgs nlflux_row_args(const vn_engine* h, const Batch& b) {
-  VnNlfluxRowArgs a{};
-  a.u = h->u; a.phi = b.phi; a.f1 = (float)b.fc[0]; a.f2 = (float)b.fc[1]; a.f3 = (float)b.fc[2];
-  a.nT = b.n_k * h->cfg.integ_num;
-  a.ud = h->ud; a.udbar = h->udbar; a.ubar = h->ubar;
-  return a;
-}
-
-// ... and of a batch with a de-duplication map: on top of the reaction's source + rate p(u) when both are registered
-VnNlfluxDedupArgs nlflux_dedup_args(const vn_engine* h, const Batch& b) {
-  VnNlfluxDedupArgs a{};
-  a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
-  a.base = b.react ? h->rx_seff : batch_src(h, b); a.phi = b.phi;
-  a.f1 = (float)b.fc[0]; a.f2 = (float)b.fc[1]; a.f3 = (float)b.fc[2];
-  a.feN = h->feN; a.feW = fe_w(h);
-  a.nT = b.n_k * h->cfg.integ_num; a.U = b.U; a.q = h->cfg.integ_num;
-  a.s_eff = h->rx_seff;
-  return a;
-}
-
-// The fold of the flux term into the de-duplicated assembly's source divides by N_p: a table with a zero entry is an error code
-int nlflux_dedup_check(const vn_engine* h, const Batch& b) {
-  if (b.nlflux && b.Xu && h->feN_zero)
-    return fail(VN_EUNSUPPORTED, "the flux term of a de-duplicated batch needs test-function values N_p != 0 at every quadrature "
-                                 "point (vn_set_fe_table has a zero entry); clear the map (vn_set_dedup with Xu = NULL) to run row-wise");
-  return VN_OK;
-}
-
-// Quasilinear diffusion of a batch on the row-wise routes (vn_nldiff.hip): values in h->u, A_r saved in h->nd_A
-VnNldiffRowArgs nldiff_row_args(const vn_engine* h, const Batch& b) {
-  VnNldiffRowArgs a{};
-  a.u = h->u; a.psi = b.psi; a.d0 = (float)b.dc[0]; a.d1 = (float)b.dc[1]; a.d2 = (float)b.dc[2];
-  a.nT = b.n_k * h->cfg.integ_num;
-  a.ud = h->ud; a.A = h->nd_A; a.udbar = h->udbar; a.ubar = h->ubar;
-  return a;
-}
-
-// ... and of a batch with a de-duplication map: on top of what the reaction and the flux term made of the source
-VnNldiffDedupArgs nldiff_dedup_args(const vn_engine* h, const Batch& b) {
-  VnNldiffDedupArgs a{};
-  a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
-  a.base = (b.react || b.nlflux) ? h->rx_seff : batch_src(h, b); a.gcoef = b.gcoef; a.psi = b.psi;
-  a.d0 = (float)b.dc[0]; a.d1 = (float)b.dc[1]; a.d2 = (float)b.dc[2];
-  a.feN = h->feN; a.feW = fe_w(h);
-  a.nT = b.n_k * h->cfg.integ_num; a.U = b.U; a.q = h->cfg.integ_num; a.dim = h->cfg.dim; a.gper = b.gper ? 1 : 0;
-  a.s_eff = h->rx_seff;
-  return a;
-}
-
-// Its fold into the de-duplicated assembly's source divides by N_p, like the flux term's: a zero table entry is an error code
-int nldiff_dedup_check(const vn_engine* h, const Batch& b) {
-  if (b.nldiff && b.Xu && h->feN_zero)
-    return fail(VN_EUNSUPPORTED, "the diffusivity D(u) of a de-duplicated batch needs test-function values N_p != 0 at every quadrature "
-                                 "point (vn_set_fe_table has a zero entry); clear the map (vn_set_dedup with Xu = NULL) to run row-wise");
-  return VN_OK;
 }
 
 // De-duplicated assembly (seed and gather kernels) of a batch with a de-duplication map, (u, grad u) of its points in h->dd_uv
@@ -532,6 +467,97 @@ VnDedupArgs dedup_args(const vn_engine* h, const Batch& b) {
   a.detJv = b.detJv; a.detJ = (float)b.detJ; a.n_k = b.n_k; a.U = b.U; a.q = h->cfg.integ_num; a.dim = h->cfg.dim;
   a.time_dependent = h->cfg.time_dependent; a.w2 = (float)h->w[2]; a.gper = b.gper ? 1 : 0;
   return a;
+}
+
+// ---- the polynomial terms of a batch (vn_terms.hip): what the messages call each, and the four stages that know their order ----
+struct TermKind {
+  Term Batch::*slot;
+  const char* name;         // "the <name> is not built for ..."
+  const char* coefs;        // "<coefs> coefficients"
+  const char* integrand;    // "no <integrand> to integrate"
+  bool by_Np;               // its share of the de-duplicated source divides by N_p
+};
+const TermKind kReact{&Batch::react, "reaction term", "reaction", "reaction term", false};
+const TermKind kNlflux{&Batch::nlflux, "flux term", "flux", "flux term", true};
+const TermKind kNldiff{&Batch::nldiff, "diffusivity D(u)", "diffusivity", "diffusion term", true};
+const TermKind* const kTerms[] = {&kReact, &kNlflux, &kNldiff};
+
+// A term that divides by N_p cannot join a de-duplication map while the table of vn_set_fe_table has a zero entry: an error code at
+// registration (`how`: what the call cannot do for batch `batch`) and, since the table may change afterwards, in the steps
+int check_Np(const vn_engine* h, const TermKind& k, int batch = -1, const char* how = nullptr) {
+  if (!k.by_Np || !h->feN_zero) return VN_OK;
+  if (how) return fail(VN_EUNSUPPORTED, "the %s of batch %d %s: vn_set_fe_table has an entry N_p == 0", k.name, batch, how);
+  return fail(VN_EUNSUPPORTED, "the %s of a de-duplicated batch needs test-function values N_p != 0 at every quadrature "
+                               "point (vn_set_fe_table has a zero entry); clear the map (vn_set_dedup with Xu = NULL) to run row-wise", k.name);
+}
+
+// Row-wise routes: values in h->u, integrand / seeds in h->ud, h->ubar, h->udbar, A_r of the D(u) pair saved in h->nd_A
+VnTermRowArgs term_row_args(const vn_engine* h, const Batch& b, const Term& t) {
+  VnTermRowArgs a{};
+  a.u = h->u; a.stream = t.stream;
+  for (int i = 0; i < 3; ++i) a.c[i] = (float)t.c[i];
+  a.nT = b.n_k * h->cfg.integ_num;
+  a.ud = h->ud; a.A = h->nd_A; a.udbar = h->udbar; a.ubar = h->ubar;
+  return a;
+}
+
+// Before vn_seed_launch: D(u) turns ud = A into D(u) A - u psi before anything else edits it, then -F(u) phi joins it
+int terms_fold_rows(vn_engine* h, const Batch& b) {
+  if (b.nldiff.on) {
+    if (int rc = ensure(&h->nd_A, &h->nd_A_cap, b.n_k * h->cfg.integ_num)) return rc;
+    HIPCHK(vn_nldiff_fold_launch(term_row_args(h, b, b.nldiff), h->stream));
+  }
+  if (b.nlflux.on) HIPCHK(vn_nlflux_fold_launch(term_row_args(h, b, b.nlflux), h->stream));
+  return VN_OK;
+}
+
+// After a vn_seed_launch that produced seeds: D(u) rescales the tangent seed last, the flux term's value seed reads it unscaled
+int terms_seed_rows(vn_engine* h, const Batch& b) {
+  if (b.nlflux.on) HIPCHK(vn_nlflux_seed_launch(term_row_args(h, b, b.nlflux), h->stream));
+  if (b.nldiff.on) HIPCHK(vn_nldiff_seed_launch(term_row_args(h, b, b.nldiff), h->stream));
+  return VN_OK;
+}
+
+// De-duplicated step: the values of the batch's points in h->dd_uv; source so far, test-function seeds and point seeds as in d
+VnTermDedupArgs term_dedup_args(const vn_engine* h, const Batch& b, const Term& t, const VnDedupArgs& d) {
+  VnTermDedupArgs a{};
+  a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
+  a.base = d.source; a.stream = t.stream;
+  for (int i = 0; i < 3; ++i) a.c[i] = (float)t.c[i];
+  a.feN = h->feN; a.feW = fe_w(h); a.stf = d.stf;
+  a.nT = b.n_k * h->cfg.integ_num; a.U = b.U; a.q = h->cfg.integ_num;
+  a.s_eff = h->rx_seff; a.seed_u = d.seed_u;
+  return a;
+}
+
+// ... of D(u), which alone reads gcoef and the points' tangent seeds
+VnTermDedupArgs nldiff_dedup_args(const vn_engine* h, const Batch& b, const VnDedupArgs& d) {
+  VnTermDedupArgs a = term_dedup_args(h, b, b.nldiff, d);
+  a.gcoef = b.gcoef; a.dim = h->cfg.dim; a.gper = b.gper ? 1 : 0; a.seed_g = d.seed_g;
+  return a;
+}
+
+// Before vn_dedup_seed_launch, which takes d.source: source + rate p(u) per row takes the place of the source, F(u) phi / N_p comes
+// on top of it, ((1 - D(u)) A + u psi) / N_p on top of both -- each in h->rx_seff, on what the previous one left there
+int terms_source_dedup(vn_engine* h, const Batch& b, VnDedupArgs& d) {
+  if (!has_terms(b)) return VN_OK;
+  for (const TermKind* k : kTerms)
+    if ((b.*(k->slot)).on)
+      if (int rc = check_Np(h, *k)) return rc;
+  if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
+  if (b.react.on) { HIPCHK(vn_react_source_launch(term_dedup_args(h, b, b.react, d), h->stream)); d.source = h->rx_seff; }
+  if (b.nlflux.on) { HIPCHK(vn_nlflux_source_launch(term_dedup_args(h, b, b.nlflux, d), h->stream)); d.source = h->rx_seff; }
+  if (b.nldiff.on) { HIPCHK(vn_nldiff_source_launch(nldiff_dedup_args(h, b, d), h->stream)); d.source = h->rx_seff; }
+  return VN_OK;
+}
+
+// After vn_dedup_gather_launch: each term's value seed, added to the gathered one; D(u) last (D'(u) grad u . seed_g needs the
+// unscaled seed_g)
+int terms_gather_dedup(vn_engine* h, const Batch& b, const VnDedupArgs& d) {
+  if (b.react.on) HIPCHK(vn_react_gather_launch(term_dedup_args(h, b, b.react, d), h->stream));
+  if (b.nlflux.on) HIPCHK(vn_nlflux_gather_launch(term_dedup_args(h, b, b.nlflux, d), h->stream));
+  if (b.nldiff.on) HIPCHK(vn_nldiff_point_launch(nldiff_dedup_args(h, b, d), h->stream));
+  return VN_OK;
 }
 
 // Every launch of the 8-wave fused kernel: its global-memory stash (per workgroup; none for most instantiations) is sized here
@@ -597,23 +623,7 @@ int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst, con
   HIPCHK(point_pass(h, b.Xu, b.U, nullptr, nullptr, h->dd_uv));
   VnDedupArgs a = dedup_args(h, b);
   a.lossVec = lossVec; a.part = h->losspart;          // loss only: no seeds
-  if (b.react) {                                      // source + rate p(u) per row takes the place of the source
-    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
-    HIPCHK(vn_react_source_launch(react_args(h, b), h->stream));
-    a.source = h->rx_seff;
-  }
-  if (b.nlflux) {                                     // ... and F(u) phi / N_p on top of it
-    if (int rc = nlflux_dedup_check(h, b)) return rc;
-    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
-    HIPCHK(vn_nlflux_source_launch(nlflux_dedup_args(h, b), h->stream));
-    a.source = h->rx_seff;
-  }
-  if (b.nldiff) {                                     // ... and ((1 - D(u)) A + u psi) / N_p on top of both
-    if (int rc = nldiff_dedup_check(h, b)) return rc;
-    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
-    HIPCHK(vn_nldiff_source_launch(nldiff_dedup_args(h, b), h->stream));
-    a.source = h->rx_seff;
-  }
+  if (int rc = terms_source_dedup(h, b, a)) return rc;
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
   if (int rc = fused_forward(h, bi_x(h, b), nullptr, h->nB, h->ub, nullptr)) return rc;
   VnSeedArgs s = seed_args(h, b);
@@ -652,17 +662,10 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
   VnSeedArgs a = seed_args(h, b);
   if (with_seeds) { a.ubar = h->ubar; a.udbar = h->udbar; a.ubar_b = h->ubar_b; }
   a.lossVec = lossVec; a.part = h->losspart;
-  // quasilinear diffusion: ud = A becomes D(u) A - u psi before anything else edits it, and the seeds are rescaled after
-  // everything else has read the unscaled tangent seed (vn_nldiff.hip)
-  if (b.nldiff) {
-    if (int rc = ensure(&h->nd_A, &h->nd_A_cap, b.n_k * h->cfg.integ_num)) return rc;
-    HIPCHK(vn_nldiff_fold_launch(nldiff_row_args(h, b), h->stream));
-  }
-  // flux term: -F(u) phi joins the row integrand before the seed kernel reads it, its value seed is added after (vn_nlflux.hip)
-  if (b.nlflux) HIPCHK(vn_nlflux_fold_launch(nlflux_row_args(h, b), h->stream));
+  if (int rc = terms_fold_rows(h, b)) return rc;
   HIPCHK(vn_seed_launch(a, grid, h->stream));
-  if (b.nlflux && with_seeds) HIPCHK(vn_nlflux_seed_launch(nlflux_row_args(h, b), h->stream));
-  if (b.nldiff && with_seeds) HIPCHK(vn_nldiff_seed_launch(nldiff_row_args(h, b), h->stream));
+  if (with_seeds)
+    if (int rc = terms_seed_rows(h, b)) return rc;
   if (lossdst) {
     HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2, lossdst, h->stream,
                             VnOptArgs(), fx));
@@ -735,8 +738,8 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx)
 //   3. reverse pass with those seeds (recomputes the forward); BC/IC tiles ride along   (6 F_pt)
 // 8 F_pt per point instead of 6, against 8 F_pt at 0.07 of peak on the generic kernels.
 // Also the step of a batch with a reaction term on the single-launch route, at any integ_num (vn_set_reaction): the term lives
-// in the seed kernel; neither mode of the fused kernel looks at integ_num.  A flux term (vn_set_nlflux) takes the same sequence,
-// with its two elementwise kernels around the seed kernel, and so does a diffusivity D(u) (vn_set_nldiff), with its pair around those.
+// in the seed kernel; neither mode of the fused kernel looks at integ_num.  A flux term (vn_set_nlflux) and a diffusivity D(u)
+// (vn_set_nldiff) take the same sequence, with their elementwise kernels around the seed kernel (terms_fold_rows, terms_seed_rows).
 int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
   const int grid = h->ncu, P = h->net.P;
   const int sgrid = (int)((b.n_k + 255) / 256);
@@ -753,14 +756,9 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& f
   a.ubar = h->ubar; a.udbar = h->udbar;
   a.ub = nullptr; a.label = nullptr; a.nB = 0; a.bDof = 0; a.biDimVal = 0.f;   // BC/IC: step 3
   a.part = lp + (long)grid * 3;
-  if (b.nldiff) {                                                                      // D(u), as in run_forward_and_seed
-    if (int rc = ensure(&h->nd_A, &h->nd_A_cap, b.n_k * h->cfg.integ_num)) return rc;
-    HIPCHK(vn_nldiff_fold_launch(nldiff_row_args(h, b), h->stream));
-  }
-  if (b.nlflux) HIPCHK(vn_nlflux_fold_launch(nlflux_row_args(h, b), h->stream));      // flux term, as in run_forward_and_seed
+  if (int rc = terms_fold_rows(h, b)) return rc;
   HIPCHK(vn_seed_launch(a, sgrid, h->stream));
-  if (b.nlflux) HIPCHK(vn_nlflux_seed_launch(nlflux_row_args(h, b), h->stream));
-  if (b.nldiff) HIPCHK(vn_nldiff_seed_launch(nldiff_row_args(h, b), h->stream));
+  if (int rc = terms_seed_rows(h, b)) return rc;
 
   f.mode = 2; f.out_u = nullptr; f.out_ud = nullptr; f.seed_u = h->ubar; f.seed_ud = h->udbar; f.nB = h->nB;
   if (int rc = prof_start(h)) return rc;
@@ -788,37 +786,10 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx)
   VnDedupArgs a = dedup_args(h, b);
   a.stf = h->u; a.part = lp + (long)grid * 3;
   a.seed_u = h->dd_su; a.seed_g = h->dd_sg;
-  VnReactArgs ra{};
-  if (b.react) {                                      // source + rate p(u) per row takes the place of the source
-    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
-    ra = react_args(h, b);
-    ra.stf = a.stf; ra.seed_u = a.seed_u;
-    HIPCHK(vn_react_source_launch(ra, h->stream));
-    a.source = h->rx_seff;
-  }
-  VnNlfluxDedupArgs na{};
-  if (b.nlflux) {                                     // ... and F(u) phi / N_p on top of it
-    if (int rc = nlflux_dedup_check(h, b)) return rc;
-    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
-    na = nlflux_dedup_args(h, b);
-    na.stf = a.stf; na.seed_u = a.seed_u;
-    HIPCHK(vn_nlflux_source_launch(na, h->stream));
-    a.source = h->rx_seff;
-  }
-  VnNldiffDedupArgs da{};
-  if (b.nldiff) {                                     // ... and ((1 - D(u)) A + u psi) / N_p on top of both
-    if (int rc = nldiff_dedup_check(h, b)) return rc;
-    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
-    da = nldiff_dedup_args(h, b);
-    da.stf = a.stf; da.seed_u = a.seed_u; da.seed_g = a.seed_g;
-    HIPCHK(vn_nldiff_source_launch(da, h->stream));
-    a.source = h->rx_seff;
-  }
+  if (int rc = terms_source_dedup(h, b, a)) return rc;
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
   HIPCHK(vn_dedup_gather_launch(a, h->stream));
-  if (b.react) HIPCHK(vn_react_gather_launch(ra, h->stream));   // the term's value seed, added to the gathered one
-  if (b.nlflux) HIPCHK(vn_nlflux_gather_launch(na, h->stream));
-  if (b.nldiff) HIPCHK(vn_nldiff_point_launch(da, h->stream));  // last: D'(u) grad u . seed_g needs the unscaled seed_g
+  if (int rc = terms_gather_dedup(h, b, a)) return rc;
   VnFusedArgs f = fused_args(h, &b);
   f.X = b.Xu; f.G = h->dd_sg; f.nT = b.U;
   f.partial = h->dd_partial; f.losspart = lp;
@@ -1168,9 +1139,8 @@ int vn_set_interior(vn_engine* h, int32_t batch, const float* Input, const float
   b.Nrow = N_rows; b.dNtrow = dNt_rows; b.n_k = n_k; b.set = true;
   b.Xu = nullptr; b.uid = nullptr; b.rowptr = nullptr; b.rowidx = nullptr; b.U = 0;   // re-register with vn_set_dedup
   b.biInput = nullptr; b.biLabel = nullptr;                                            // ... and vn_set_batch_bic
-  b.react = false; b.rate = nullptr; b.rc[0] = b.rc[1] = b.rc[2] = 0.0;                // ... and vn_set_reaction
-  b.nlflux = false; b.phi = nullptr; b.fc[0] = b.fc[1] = b.fc[2] = 0.0;                // ... and vn_set_nlflux
-  b.nldiff = false; b.psi = nullptr; b.dc[0] = 1.0; b.dc[1] = b.dc[2] = 0.0;            // ... and vn_set_nldiff
+  const Batch fresh;
+  b.react = fresh.react; b.nlflux = fresh.nlflux; b.nldiff = fresh.nldiff;             // ... and the three term setters
   const long nT = n_k * h->cfg.integ_num;
   if (nT > h->work_rows) {
     long c0 = h->work_rows, c1 = h->work_rows, c2 = h->work_rows, c3 = h->work_rows;
@@ -1232,93 +1202,53 @@ int vn_set_dedup(vn_engine* h, int32_t batch, const float* Xu, int64_t U, const 
     if (int rc = ensure(&b.gcsr, &b.gcsr_cap, nT * dim)) return rc;
     HIPCHK(vn_dedup_permute_launch(b.gcoef, rowidx, b.gcsr, nT, dim, h->stream));
   }
-  if (b.react || b.nlflux || b.nldiff)
+  if (has_terms(b))
     if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, nT)) return rc;
-  if (b.nlflux && h->feN_zero)
-    return fail(VN_EUNSUPPORTED, "the flux term of batch %d cannot be de-duplicated: vn_set_fe_table has an entry N_p == 0", batch);
-  if (b.nldiff && h->feN_zero)
-    return fail(VN_EUNSUPPORTED, "the diffusivity D(u) of batch %d cannot be de-duplicated: vn_set_fe_table has an entry N_p == 0", batch);
+  for (const TermKind* k : kTerms)
+    if ((b.*(k->slot)).on)
+      if (int rc = check_Np(h, *k, batch, "cannot be de-duplicated")) return rc;
   b.Xu = Xu; b.U = U; b.uid = uid; b.rowptr = rowptr; b.rowidx = rowidx;
   return VN_OK;
 }
 
-int vn_set_reaction(vn_engine* h, int32_t batch, const float* rate, const double coef[3]) {
+// vn_set_reaction, vn_set_nlflux, vn_set_nldiff: coef == NULL, or the coefficients of an unregistered term (for D(u): D = 1 and
+// no psi, which is advection on the value side), clear the term; a de-duplication map and the other terms stay
+static int set_term(vn_engine* h, int32_t batch, const TermKind& k, const float* stream, const double coef[3]) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
     return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
   if (coef && !(std::isfinite(coef[0]) && std::isfinite(coef[1]) && std::isfinite(coef[2])))
-    return fail(VN_EINVAL, "reaction coefficients (%g, %g, %g) must be finite", coef[0], coef[1], coef[2]);
+    return fail(VN_EINVAL, "%s coefficients (%g, %g, %g) must be finite", k.coefs, coef[0], coef[1], coef[2]);
   Batch& b = h->batches[batch];
-  if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no reaction term to integrate", batch);
+  if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no %s to integrate", batch, k.integrand);
   lbfgs_invalidate(h, batch);
-  if (!coef || (coef[0] == 0.0 && coef[1] == 0.0 && coef[2] == 0.0)) {      // clears; a de-duplication map stays
-    b.react = false; b.rate = nullptr; b.rc[0] = b.rc[1] = b.rc[2] = 0.0;
+  const Term off = Batch().*(k.slot);
+  if (!coef || (std::equal(coef, coef + 3, off.c) && !(&k == &kNldiff && stream))) {
+    b.*(k.slot) = off;
     return VN_OK;
   }
+  if (&k == &kNlflux && !stream)
+    return fail(VN_EINVAL, "the flux term needs phi = sum_d w_d dN/dx_d per interior row (phi_dev is NULL)");
   if (h->route == Route::fused4)
-    return fail(VN_EUNSUPPORTED, "the reaction term is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its single "
-                                 "launch has no place for the term; every other kernel family carries it");
+    return fail(VN_EUNSUPPORTED, "the %s is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its single "
+                                 "launch has no place for the term; every other kernel family carries it", k.name);
+  if (b.Xu)
+    if (int rc = check_Np(h, k, batch, "cannot join its de-duplication map")) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
-  // (the row-wise work buffers u / ud / ubar / udbar of the two-pass sequence exist since vn_set_interior, on every route)
+  // (the row-wise work buffers u / ud / ubar / udbar of the two-pass sequence exist since vn_set_interior, on every route;
+  // A_r of the D(u) pair is allocated when a batch first carries the term, and the steps grow it if a larger batch follows)
+  if (&k == &kNldiff)
+    if (int rc = ensure(&h->nd_A, &h->nd_A_cap, b.n_k * h->cfg.integ_num)) return rc;
   if (b.Xu)
     if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
-  b.react = true; b.rate = rate; b.rc[0] = coef[0]; b.rc[1] = coef[1]; b.rc[2] = coef[2];
+  Term& t = b.*(k.slot);
+  t.on = true; t.stream = stream; std::copy(coef, coef + 3, t.c);
   return VN_OK;
 }
 
-int vn_set_nlflux(vn_engine* h, int32_t batch, const float* phi, const double coef[3]) {
-  if (!h) return fail(VN_EINVAL, "null handle");
-  if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
-    return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
-  if (coef && !(std::isfinite(coef[0]) && std::isfinite(coef[1]) && std::isfinite(coef[2])))
-    return fail(VN_EINVAL, "flux coefficients (%g, %g, %g) must be finite", coef[0], coef[1], coef[2]);
-  Batch& b = h->batches[batch];
-  if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no flux term to integrate", batch);
-  lbfgs_invalidate(h, batch);
-  if (!coef || (coef[0] == 0.0 && coef[1] == 0.0 && coef[2] == 0.0)) {      // clears; a map and a reaction stay
-    b.nlflux = false; b.phi = nullptr; b.fc[0] = b.fc[1] = b.fc[2] = 0.0;
-    return VN_OK;
-  }
-  if (!phi) return fail(VN_EINVAL, "the flux term needs phi = sum_d w_d dN/dx_d per interior row (phi_dev is NULL)");
-  if (h->route == Route::fused4)
-    return fail(VN_EUNSUPPORTED, "the flux term is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its single "
-                                 "launch has no place for the term; every other kernel family carries it");
-  if (b.Xu && h->feN_zero)
-    return fail(VN_EUNSUPPORTED, "the flux term of batch %d cannot join its de-duplication map: vn_set_fe_table has an entry N_p == 0", batch);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  // (the row-wise work buffers u / ud / ubar / udbar of the two-pass sequence exist since vn_set_interior, on every route)
-  if (b.Xu)
-    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
-  b.nlflux = true; b.phi = phi; b.fc[0] = coef[0]; b.fc[1] = coef[1]; b.fc[2] = coef[2];
-  return VN_OK;
-}
-
-int vn_set_nldiff(vn_engine* h, int32_t batch, const float* psi, const double coef[3]) {
-  if (!h) return fail(VN_EINVAL, "null handle");
-  if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
-    return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
-  if (coef && !(std::isfinite(coef[0]) && std::isfinite(coef[1]) && std::isfinite(coef[2])))
-    return fail(VN_EINVAL, "diffusivity coefficients (%g, %g, %g) must be finite", coef[0], coef[1], coef[2]);
-  Batch& b = h->batches[batch];
-  if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no diffusion term to integrate", batch);
-  lbfgs_invalidate(h, batch);
-  if (!coef || (coef[0] == 1.0 && coef[1] == 0.0 && coef[2] == 0.0 && !psi)) {   // D = 1, no psi: clears; a map and the other terms stay
-    b.nldiff = false; b.psi = nullptr; b.dc[0] = 1.0; b.dc[1] = b.dc[2] = 0.0;
-    return VN_OK;
-  }
-  if (h->route == Route::fused4)
-    return fail(VN_EUNSUPPORTED, "the diffusivity D(u) is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its single "
-                                 "launch has no place for the term; every other kernel family carries it");
-  if (b.Xu && h->feN_zero)
-    return fail(VN_EUNSUPPORTED, "the diffusivity D(u) of batch %d cannot join its de-duplication map: vn_set_fe_table has an entry N_p == 0", batch);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  // A_r of the row-wise routes: engine-owned, allocated when a batch first carries the term (the steps grow it if a larger batch follows)
-  if (int rc = ensure(&h->nd_A, &h->nd_A_cap, b.n_k * h->cfg.integ_num)) return rc;
-  if (b.Xu)
-    if (int rc = ensure(&h->rx_seff, &h->rx_seff_cap, b.n_k * h->cfg.integ_num)) return rc;
-  b.nldiff = true; b.psi = psi; b.dc[0] = coef[0]; b.dc[1] = coef[1]; b.dc[2] = coef[2];
-  return VN_OK;
-}
+int vn_set_reaction(vn_engine* h, int32_t batch, const float* rate, const double coef[3]) { return set_term(h, batch, kReact, rate, coef); }
+int vn_set_nlflux(vn_engine* h, int32_t batch, const float* phi, const double coef[3]) { return set_term(h, batch, kNlflux, phi, coef); }
+int vn_set_nldiff(vn_engine* h, int32_t batch, const float* psi, const double coef[3]) { return set_term(h, batch, kNldiff, psi, coef); }
 
 int vn_set_bic(vn_engine* h, const float* biInput, const float* biLabel, int64_t nB, int64_t bDof, double biDimVal) {
   if (!h) return fail(VN_EINVAL, "null handle");
@@ -1404,7 +1334,7 @@ int vn_grad(vn_engine* h, int32_t batch) {
     case Route::fused4: return run_fused(h, b, h->gradbuf, fx);
     // a reaction term lives in the row-wise seed kernel, a flux term and a diffusivity D(u) around it: the single-launch route
     // runs the two-pass sequence for such a batch
-    case Route::fused8: return (b.react || b.nlflux || b.nldiff) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
+    case Route::fused8: return has_terms(b) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
     case Route::twopass: return run_twopass(h, b, h->gradbuf, fx);
   }
 }
@@ -1642,9 +1572,9 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   p.Xb = bi_x(h, b); p.label = bi_y(h, b); p.nB = h->nB; p.bDof = h->bDof; p.biDimVal = h->biDimVal;
   p.Xf = h->fX; p.Nf = h->fN; p.fcoef = h->fcoef; p.flabel = h->flabel; p.nF = h->nF; p.fbiDimVal = h->fbiDimVal;
   p.w[0] = h->w[0]; p.w[1] = h->w[1]; p.w[2] = h->w[2];
-  p.react = b.react ? 1 : 0; p.rate = b.rate; p.coef[0] = b.rc[0]; p.coef[1] = b.rc[1]; p.coef[2] = b.rc[2];
-  p.nlflux = b.nlflux ? 1 : 0; p.phi = b.phi; p.fcoef3[0] = b.fc[0]; p.fcoef3[1] = b.fc[1]; p.fcoef3[2] = b.fc[2];
-  p.nldiff = b.nldiff ? 1 : 0; p.psi = b.psi; p.dcoef3[0] = b.dc[0]; p.dcoef3[1] = b.dc[1]; p.dcoef3[2] = b.dc[2];
+  p.react = b.react.on ? 1 : 0; p.rate = b.react.stream; std::copy(b.react.c, b.react.c + 3, p.coef);
+  p.nlflux = b.nlflux.on ? 1 : 0; p.phi = b.nlflux.stream; std::copy(b.nlflux.c, b.nlflux.c + 3, p.fcoef3);
+  p.nldiff = b.nldiff.on ? 1 : 0; p.psi = b.nldiff.stream; std::copy(b.nldiff.c, b.nldiff.c + 3, p.dcoef3);
   hipError_t e = vn_obj64_run(h->o64, p, grad_dev, lossVec_dev, out, h->ncu, h->stream);
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(h->stream);

@@ -371,9 +371,8 @@ class VNEngine:
         self._keep[('int', batch)] = (Input, gcoef, source, detJv, Nr, dNr)
         self._ck(self.lib.vn_set_interior(self.h, batch, _ptr(Input), _ptr(gcoef), _ptr(source), n_k,
                                           _ptr(detJv), detJ_s, _ptr(Nr), _ptr(dNr)))
-        self._keep.pop(('react', batch), None)       # vn_set_interior cleared the batch's reaction term
-        self._keep.pop(('nlflux', batch), None)      # ... and its flux term
-        self._keep.pop(('nldiff', batch), None)      # ... and its diffusivity D(u)
+        for key in ('react', 'nlflux', 'nldiff'):    # vn_set_interior cleared the batch's three polynomial terms
+            self._keep.pop((key, batch), None)
 
     def set_dedup(self, batch, Xu=None, uid=None, rowptr=None, rowidx=None):
         """Register (or, with Xu=None, clear) the de-duplicated formulation of `batch`."""
@@ -441,72 +440,48 @@ class VNEngine:
             del old           # the engine dropped the previous registration before checking this one
         self._keep['flux'] = (X, normal, coef, label)
 
+    def _set_term(self, key, fn, takes, stream_name, batch, stream, coef, clears):
+        """One of the three polynomial terms of `batch` (vn_terms.hip): coef normalised to three doubles; clears(c, stream) tells
+        whether the call unregisters the term; else `stream` (one value per interior row, or None) is uploaded and kept alive."""
+        c = [] if coef is None else [float(x) for x in np.reshape(np.asarray(coef, dtype=np.float64), -1)]
+        if len(c) > 3:
+            raise ValueError('%s, got %d' % (takes, len(c)))
+        c = c + [0.0] * (3 - len(c))
+        if coef is None or clears(c, stream):
+            self._keep.pop((key, batch), None)
+            self._ck(fn(self.h, int(batch), None, None))
+            return
+        if stream is not None:
+            t = self.torch
+            stream = self.dev(stream.reshape(-1) if isinstance(stream, t.Tensor) else np.reshape(stream, -1))
+            # the ABI carries a pointer only: the length the kernels rely on is checked here
+            kept = self._keep.get(('int', batch))
+            assert kept is None or stream.numel() == kept[0].shape[0], \
+                '%s must have one entry per interior row (%s != %s)' % (stream_name, stream.numel(), kept[0].shape[0])
+        self._ck(fn(self.h, int(batch), _ptr(stream), (C.c_double * 3)(*c)))
+        self._keep[(key, batch)] = stream
+
     def set_reaction(self, batch, rate=None, coef=None):
         """Register (or, with coef=None or all zero, clear) the reaction term rate * (c1 u + c2 u^2 + c3 u^3) of `batch`
         (vn_set_reaction), after set_interior of that batch: rate one value per interior row or None (rate = 1), coef up to
         three numbers (a shorter list is zero-padded)."""
-        c = [] if coef is None else [float(x) for x in np.reshape(np.asarray(coef, dtype=np.float64), -1)]
-        if len(c) > 3:
-            raise ValueError('a reaction takes at most three coefficients (c1, c2, c3), got %d' % len(c))
-        c = c + [0.0] * (3 - len(c))
-        if coef is None or not any(c):
-            self._keep.pop(('react', batch), None)
-            self._ck(self.lib.vn_set_reaction(self.h, int(batch), None, None))
-            return
-        if rate is not None:
-            t = self.torch
-            rate = self.dev(rate.reshape(-1) if isinstance(rate, t.Tensor) else np.reshape(rate, -1))
-            # the ABI carries a pointer only: the length the kernels rely on is checked here
-            kept = self._keep.get(('int', batch))
-            assert kept is None or rate.numel() == kept[0].shape[0], \
-                'rate must have one entry per interior row (%s != %s)' % (rate.numel(), kept[0].shape[0])
-        self._ck(self.lib.vn_set_reaction(self.h, int(batch), _ptr(rate), (C.c_double * 3)(*c)))
-        self._keep[('react', batch)] = rate
+        self._set_term('react', self.lib.vn_set_reaction, 'a reaction takes at most three coefficients (c1, c2, c3)', 'rate',
+                       batch, rate, coef, lambda c, s: not any(c))
 
     def set_nlflux(self, batch, phi=None, coef=None):
         """Register (or, with coef=None or all zero, clear) the flux term -div(w F(u)), F(u) = f1 u + f2 u^2 + f3 u^3, of `batch`
         (vn_set_nlflux), after set_interior of that batch: phi = sum_d w_d dN/dx_d, one value per interior row, coef up to three
         numbers (a shorter list is zero-padded)."""
-        c = [] if coef is None else [float(x) for x in np.reshape(np.asarray(coef, dtype=np.float64), -1)]
-        if len(c) > 3:
-            raise ValueError('a flux term takes at most three coefficients (f1, f2, f3), got %d' % len(c))
-        c = c + [0.0] * (3 - len(c))
-        if coef is None or not any(c):
-            self._keep.pop(('nlflux', batch), None)
-            self._ck(self.lib.vn_set_nlflux(self.h, int(batch), None, None))
-            return
-        if phi is not None:
-            t = self.torch
-            phi = self.dev(phi.reshape(-1) if isinstance(phi, t.Tensor) else np.reshape(phi, -1))
-            # the ABI carries a pointer only: the length the kernels rely on is checked here
-            kept = self._keep.get(('int', batch))
-            assert kept is None or phi.numel() == kept[0].shape[0], \
-                'phi must have one entry per interior row (%s != %s)' % (phi.numel(), kept[0].shape[0])
-        self._ck(self.lib.vn_set_nlflux(self.h, int(batch), _ptr(phi), (C.c_double * 3)(*c)))
-        self._keep[('nlflux', batch)] = phi
+        self._set_term('nlflux', self.lib.vn_set_nlflux, 'a flux term takes at most three coefficients (f1, f2, f3)', 'phi',
+                       batch, phi, coef, lambda c, s: not any(c))
 
     def set_nldiff(self, batch, psi=None, coef=None):
         """Register (or, with coef=None, or coef (1, 0, 0) and psi=None, clear) the diffusivity D(u) = d0 + d1 u + d2 u^2 of the
         quasilinear diffusion div(kappa D(u) grad u) of `batch` (vn_set_nldiff), after set_interior of that batch.  The batch's
         gcoef must then be kappa dN/dx alone; psi = sum_d v_d dN/dx_d + N div v, one value per interior row, carries the
         advection (None: no advection).  coef: up to three numbers (a shorter list is zero-padded)."""
-        c = [] if coef is None else [float(x) for x in np.reshape(np.asarray(coef, dtype=np.float64), -1)]
-        if len(c) > 3:
-            raise ValueError('a diffusivity takes at most three coefficients (d0, d1, d2), got %d' % len(c))
-        c = c + [0.0] * (3 - len(c))
-        if coef is None or (c == [1.0, 0.0, 0.0] and psi is None):
-            self._keep.pop(('nldiff', batch), None)
-            self._ck(self.lib.vn_set_nldiff(self.h, int(batch), None, None))
-            return
-        if psi is not None:
-            t = self.torch
-            psi = self.dev(psi.reshape(-1) if isinstance(psi, t.Tensor) else np.reshape(psi, -1))
-            # the ABI carries a pointer only: the length the kernels rely on is checked here
-            kept = self._keep.get(('int', batch))
-            assert kept is None or psi.numel() == kept[0].shape[0], \
-                'psi must have one entry per interior row (%s != %s)' % (psi.numel(), kept[0].shape[0])
-        self._ck(self.lib.vn_set_nldiff(self.h, int(batch), _ptr(psi), (C.c_double * 3)(*c)))
-        self._keep[('nldiff', batch)] = psi
+        self._set_term('nldiff', self.lib.vn_set_nldiff, 'a diffusivity takes at most three coefficients (d0, d1, d2)', 'psi',
+                       batch, psi, coef, lambda c, s: c == [1.0, 0.0, 0.0] and s is None)
 
     def set_weights(self, w):
         arr = (C.c_double * 3)(*[float(x) for x in w])
