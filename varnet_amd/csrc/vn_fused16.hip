@@ -22,7 +22,7 @@
 //   * Hidden widths 33..50 with 2..5 hidden layers (bf_sweeps): forward and input-gradient sweeps as bf16-piece
 //     products on the bf16 matrix pipe (vn_fused16_common.h); their images need the LDS of the stash, which then
 //     holds one layer in global memory.
-// Register budget: 256 VGPRs per wave (stored activations 2*KS*L = 130 at 5x50; 49 spilled at 5x50).
+// Register budget: 256 VGPRs per wave (stored activations 2*KS*L = 130 at 5x50; 36 spilled at 5x50).
 #include "vn_internal.h"
 #include "vn_fused16_common.h"
 
@@ -430,18 +430,22 @@ __device__ __forceinline__ void h13_contract(const float* TA, const float* TB, c
     const int oA = (role == 1) ? H13::off(H13::edge_row(sel)) : lane_off;
     const int oB = (role == 1) ? TBO + lane_off
                                : (sel == 0 ? TBO + H13::off(H13::P48) : sel == 1 ? TBO + H13::off(H13::P49) : H13::off(H13::ZERO));
-    const float* pA = TA + oA;
-    const float* pB = TA + oB;
+    // TA lies past the first 64 KB of the LDS, out of reach of a DS immediate from a zero base: the lane bases carry TA's own
+    // address (formed here, once per round, and pinned), and a stage's eight reads differ by immediates only
+    typedef const __attribute__((address_space(3))) f32x4a* lds4;
+    unsigned aA = (unsigned)(unsigned long)(const __attribute__((address_space(3))) float*)TA + 4u * oA;
+    unsigned aB = (unsigned)(unsigned long)(const __attribute__((address_space(3))) float*)TA + 4u * oB;
+    asm volatile("" : "+v"(aA), "+v"(aB));
     // 8 points per stage (wave w's columns 0..7 or 8..15), two register buffers used alternately (no
     // rotation copies: a stage's loads are waited for one stage later, behind 16 MFMAs)
     constexpr int NSTG = TILE / 8;
     f32x4 a0[2], b0[2], a1[2], b1[2];
     auto load = [&](f32x4 (&a4)[2], f32x4 (&b4)[2], int stage) {
-      const int o = (stage >> 1) * 64 + (stage & 1) * 8;
+      const unsigned o = 4u * ((stage >> 1) * 64 + (stage & 1) * 8);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        a4[h] = *reinterpret_cast<const f32x4a*>(&pA[o + 4 * h]);
-        b4[h] = *reinterpret_cast<const f32x4a*>(&pB[o + 4 * h]);
+        a4[h] = *(lds4)(unsigned long)(aA + o + 16u * h);
+        b4[h] = *(lds4)(unsigned long)(aB + o + 16u * h);
       }
     };
     auto compute = [&](const f32x4 (&a4)[2], const f32x4 (&b4)[2]) {
@@ -508,25 +512,28 @@ __device__ __forceinline__ void h13_contract(const float* TA, const float* TB, c
   }
 }
 
-template <int KS_, int I, bool TANH>
+// OPQ: sigma'(a) is formed from an opaque copy of a (the f32-sweep instantiations: left plain, the compiler keeps the packed
+// sigma' of the forward sweep alive across the tile and spills for it; the bf16-piece sweeps have no such value to reuse, and
+// there the copy is seven register-pair moves per round for nothing)
+template <int KS_, int I, bool TANH, bool OPQ>
 struct H13Pub {      // unrolled stores with compile-time offsets (inline-asm immediates)
   static __device__ __forceinline__ void run(int half, const PA<13>& av, const PA<13>& azd, const PA<13>& bv,
                                              const PA<13>& bt) {
     // I even: this step publishes k-steps I and I+1 (one packed sigma'(a)*zdot for both)
     f32x2 v2 = av.p[I >> 1];
-    if (half == 1) v2 = act_d1_2<TANH>(opaque2(av.p[I >> 1])) * azd.p[I >> 1];
+    if (half == 1) v2 = act_d1_2<TANH>(OPQ ? opaque2(av.p[I >> 1]) : av.p[I >> 1]) * azd.p[I >> 1];
     addtid_store<I * H13::RS * 4>(v2[0]);
     addtid_store<(H13::TA_ROWS + I) * H13::RS * 4>(half == 0 ? bv[I] : bt[I]);
     if constexpr (I + 1 < KS_) {
       addtid_store<(I + 1) * H13::RS * 4>(v2[1]);
       addtid_store<(H13::TA_ROWS + I + 1) * H13::RS * 4>(half == 0 ? bv[I + 1] : bt[I + 1]);
     }
-    if constexpr (I + 2 < KS_) H13Pub<KS_, I + 2, TANH>::run(half, av, azd, bv, bt);
+    if constexpr (I + 2 < KS_) H13Pub<KS_, I + 2, TANH, OPQ>::run(half, av, azd, bv, bt);
   }
 };
 
 // both rounds of a 50-wide hidden layer; t_base_bytes = byte address of this wave's 64 columns of TA
-template <bool TANH>
+template <bool TANH, bool OPQ>
 __device__ __forceinline__ void h13_wgrad_layer(const PA<13>& av, const PA<13>& azd, const PA<13>& bv,
                                                 const PA<13>& bt, float* TA, const LaneC& lc, int wave, int lane,
                                                 unsigned t_base_bytes, f32x4 (&acc)[2]) {
@@ -534,7 +541,7 @@ __device__ __forceinline__ void h13_wgrad_layer(const PA<13>& av, const PA<13>& 
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
     addtid_base(t_base_bytes);
-    H13Pub<13, 0, TANH>::run(half, av, azd, bv, bt);
+    H13Pub<13, 0, TANH, OPQ>::run(half, av, azd, bv, bt);
     addtid_store<13 * H13::RS * 4>((half == 0 && lc.g == 0) ? 1.f : 0.f);      // bias row | zeros
     addtid_drain();
     __syncthreads();
@@ -764,9 +771,20 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
   constexpr int ST_L = LY::ST_LAYER / 4;
   f32x4a* stash = (LY::BF ? reinterpret_cast<f32x4a*>(A.stash) + (long)blockIdx.x * LY::NSTG * ST_L
                           : reinterpret_cast<f32x4a*>(lds + LY::ST_OFF)) + wave * 2 * 64 + lane;   // [layer][wave][slot][lane]
-  // bf16-piece sweeps: lane bases of the row (forward) and transposed (sweep back) fragment reads
-  const char* wrd = reinterpret_cast<const char*>(WH) + split_row_base(lc.g, lc.c);
-  const char* wtr = reinterpret_cast<const char*>(WH) + split_tr_base(lc.g, lc.c);
+  // bf16-piece sweeps: lane bases of the row (forward) and transposed (sweep back) fragment reads.
+  // The images of layers 2..5 span 96 KB and a DS instruction's immediate offset reaches 64 KB.  Layers 2-3 are read from the lane
+  // bases below; a layer of the second 48 KB window (layers 4-5) forms its own base ONCE per sweep (win_base: one vector add,
+  // pinned where it stands), so that every (piece, q, row tile) block offset is an immediate of its read instead of a vector
+  // add in front of it.  A second pair of loop-invariant bases would cost two registers for the whole tile (+7 spilled).
+  constexpr int WIN = 2 * IMG;
+  const int rowb = split_row_base(lc.g, lc.c), trb = split_tr_base(lc.g, lc.c);
+  auto win_base = [&](int lane_base, int l) {          // image of layer l (2..L) + lane_base
+    const char* wh = reinterpret_cast<const char*>(WH);
+    if (l - 2 < 2) return wh + lane_base + (l - 2) * IMG;
+    int b = lane_base + WIN;
+    asm volatile("" : "+v"(b));
+    return wh + b + (l - 4) * IMG;
+  };
   f32x4 wacc1[W1G::TPW], wacch[L > 1 ? L - 1 : 1][NHACC];
   float woacc = 0.f, boacc = 0.f;                    // output layer: lane (g, c) holds d w_o[4c + g]; d b_o in every lane
 #pragma unroll
@@ -797,15 +815,41 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
   const long nI = A.nB - A.bDof;
   const float cb = A.bDof > 0 ? 2.f * A.w0 * A.biDimVal / (float)A.bDof : 0.f;
   const float ci = nI > 0 ? 2.f * A.w1 * A.biDimVal / (float)nI : 0.f;
+  // Launch-uniform predicates of the tile loop, one bit each of ONE scalar register.  Left as plain conditions the compiler
+  // hoists every one of them out of the loop as a 64-bit lane mask -- a pair of scalar registers each, spilled through
+  // v_writelane / v_readlane on the vector path -- and branches on it through VCC; fl() tests a bit of an opaque copy where the
+  // condition is used (scalar compare, branch on SCC).  The scalars compared against lane values (d_in, dim, dir, q) are made
+  // opaque at their use for the same reason (sc()).
+  enum : unsigned {
+    FL_MODE1 = 1u << 0, FL_MODE2 = 1u << 1, FL_DIR = 1u << 2, FL_TD = 1u << 3, FL_DNTROW = 1u << 4, FL_SRC = 1u << 5,
+    FL_NROW = 1u << 6, FL_QTREE = 1u << 7, FL_DETJV = 1u << 8, FL_LOSSVEC = 1u << 9, FL_SEEDU = 1u << 10, FL_SEEDUD = 1u << 11,
+    FL_OUTU = 1u << 12, FL_OUTUD = 1u << 13, FL_THIN_IN = 1u << 14
+  };
+  const unsigned flags = (A.mode == 1 ? FL_MODE1 : 0u) | (A.mode == 2 ? FL_MODE2 : 0u) | (A.dir >= 0 ? FL_DIR : 0u) |
+                         (A.time_dependent ? FL_TD : 0u) | (A.dNtrow ? FL_DNTROW : 0u) | (A.src ? FL_SRC : 0u) |
+                         (A.Nrow ? FL_NROW : 0u) | (qtree ? FL_QTREE : 0u) | (A.detJv ? FL_DETJV : 0u) |
+                         (A.lossVec ? FL_LOSSVEC : 0u) | (A.seed_u ? FL_SEEDU : 0u) | (A.seed_ud ? FL_SEEDUD : 0u) |
+                         (A.out_u ? FL_OUTU : 0u) | (A.out_ud ? FL_OUTUD : 0u) | (thin_in ? FL_THIN_IN : 0u);
+  auto fl = [flags](unsigned bits) {
+    unsigned f = flags;
+    asm volatile("" : "+s"(f));
+    return (f & bits) != 0u;
+  };
+  auto sc = [](int v) {
+    asm volatile("" : "+s"(v));
+    return v;
+  };
+  const int d_in_s = net.d_in, dim_s = net.dim, dir_s = A.dir;
 
   for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     asm volatile("" ::: "memory");                 // keep LDS fragment loads inside the loop
     const bool interior = tile < ntiles_i;
-    const long r0 = (interior && !A.mode) ? tile * TPTS : (interior ? tile : tile - ntiles_i) * TILE;
+    const bool moded = fl(FL_MODE1 | FL_MODE2);    // mode != 0
+    const long r0 = (interior && !moded) ? tile * TPTS : (interior ? tile : tile - ntiles_i) * TILE;
     const long nrows = interior ? A.nT : A.nB;
     const int pt = wave * CW + lc.c;
     const long row = r0 + pt;
-    const bool valid = row < nrows && (!interior || A.mode || pt < TPTS);
+    const bool valid = row < nrows && (!interior || moded || pt < TPTS);
 
     float xin[KS0], gin[KS0];
     {
@@ -813,9 +857,9 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
 #pragma unroll
       for (int s = 0; s < KS0; ++s) {
         const int f = 4 * s + lc.g;
-        xin[s] = (valid && f < net.d_in) ? Xp[row * net.d_in + f] : 0.f;
-        if (A.dir >= 0) gin[s] = (valid && interior && f == A.dir) ? 1.f : 0.f;
-        else gin[s] = (valid && interior && f < net.dim) ? A.G[row * net.dim + f] : 0.f;
+        xin[s] = (valid && f < sc(d_in_s)) ? Xp[row * net.d_in + f] : 0.f;
+        if (fl(FL_DIR)) gin[s] = (valid && interior && f == sc(dir_s)) ? 1.f : 0.f;
+        else gin[s] = (valid && interior && f < sc(dim_s)) ? A.G[row * net.dim + f] : 0.f;
       }
     }
 
@@ -830,7 +874,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       }
 #pragma unroll
       for (int s = 0; s < KS0; ++s) {
-        if (4 * s < net.d_in) {
+        if (4 * s < sc(d_in_s)) {
 #pragma unroll
           for (int m = 0; m < MT; ++m) {
             const float wf = W1[4 * s * WS + lc.offF + 16 * m];
@@ -849,7 +893,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       if constexpr (LY::BF) {
         // bf16 pieces: all four row tiles on the matrix pipe (features 48, 49 land in row 48 + 4g as in the edge path), value
         // and tangent share each weight fragment; the activation and the split are scalar f32 forms (no v_pk_* beside bf16 MFMAs)
-        const char* rl = wrd + (l - 2) * IMG;
+        const char* rl = win_base(rowb, l);
         f32x4 nv[MT], nt[MT];
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
@@ -1007,33 +1051,35 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
     u += bo;
 
     // ---------------------------------------------------------------- weak-form epilogue
-    if (A.mode == 1) {                                       // forward only: model value and directional derivative
+    if (fl(FL_MODE1)) {                                      // forward only: model value and directional derivative
       if (valid && lc.g == 0) {
-        if (A.out_u) A.out_u[row] = u;
-        if (A.out_ud) A.out_ud[row * A.ostride] = ud;
+        if (fl(FL_OUTU)) A.out_u[row] = u;
+        if (fl(FL_OUTUD)) A.out_ud[row * A.ostride] = ud;
       }
       continue;
     }
     float ubar = 0.f, udbar = 0.f;
     bool epi_barrier = false;                                // this tile's epilogue ran a workgroup barrier (uniform)
-    if (interior && A.mode == 2) {                           // seeds were assembled per unique point
+    if (interior && fl(FL_MODE2)) {                          // seeds were assembled per unique point
       if (valid) {
-        ubar = A.seed_u ? A.seed_u[row] : 0.f;
-        udbar = A.seed_ud ? A.seed_ud[row * A.ostride] : 1.f;   // no array: tangent seed 1 (the direction G carries the seeds)
+        ubar = fl(FL_SEEDU) ? A.seed_u[row] : 0.f;
+        udbar = fl(FL_SEEDUD) ? A.seed_ud[row * A.ostride] : 1.f;   // no array: tangent seed 1 (the direction G carries the seeds)
       }
     } else if (interior) {
       // per-row tables (non-uniform supports, VarNetUtility.py:506-523) override the periodic ones
-      const float dnt = !A.time_dependent ? 0.f : (A.dNtrow ? (valid ? A.dNtrow[row] : 0.f) : tab_dnt);
+      const float dnt = !fl(FL_TD) ? 0.f : (fl(FL_DNTROW) ? (valid ? A.dNtrow[row] : 0.f) : tab_dnt);
       const float wq = tab_w;
       float t = ud - dnt * u;
-      if (A.src) t -= (valid ? A.src[row] : 0.f) * (A.Nrow ? (valid ? A.Nrow[row] : 0.f) : tab_N);
+      if (fl(FL_SRC)) t -= (valid ? A.src[row] : 0.f) * (fl(FL_NROW) ? (valid ? A.Nrow[row] : 0.f) : tab_N);
       t *= wq;
       if (!valid) t = 0.f;
-      const int seg = q < CW ? q : CW;
+      const int qs = sc(q);
+      const int seg = qs < CW ? qs : CW;
       // A test function of up to 16 points (1D+t, two-point Gauss: q = 16) lies inside one wave: the butterfly below leaves
       // its sum R_k in every lane of the group (a + b == b + a bit for bit, so all lanes agree) -- no LDS, no workgroup barrier.
-      const bool rk_in_wave = qtree && q <= CW;
-      if (qtree) {
+      const bool qtree_t = fl(FL_QTREE);
+      const bool rk_in_wave = qtree_t && qs <= CW;
+      if (qtree_t) {
         // butterfly over the seg <= 16 lanes of a test function's points, inside a 16-lane row: DPP moves (no LDS round
         // trip on the critical path of the epilogue).  After the two quad steps all lanes of a quad hold the same value, so
         // mirroring within 8 and within 16 lanes pairs the same sums as xor 4 / xor 8 would (bit-identical results).
@@ -1041,7 +1087,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
         if (seg > 2) t += dpp_f32<0x4E>(t);        // quad_perm [2,3,0,1]
         if (seg > 4) t += dpp_f32<0x141>(t);       // row_half_mirror
         if (seg > 8) t += dpp_f32<0x140>(t);       // row_mirror
-        if (!rk_in_wave && lc.g == 0 && (lc.c % seg) == 0) sInt[pt / seg] = t;
+        if (!rk_in_wave && lc.g == 0 && lc.c == 0) sInt[pt >> 4] = t;       // seg == CW here: q > CW
       } else if (lc.g == 0) {
         sInt[pt] = t;                                                 // q does not divide the tile: serial sum
       }
@@ -1051,8 +1097,8 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       float R = 0.f;
       if (rk_in_wave) {
         R = t;
-      } else if (qtree) {
-        const int per = q / seg;                                      // partials per test function (a power of two <= 8)
+      } else if (qtree_t) {
+        const int per = qs >> 4;                                      // partials per test function, q / seg: seg == CW here (q > CW)
         if (per == 4) {
           // integNum 64 (2D+t, two-point Gauss): the four partials with one 16-byte read instead of four dependent round
           // trips right behind the barrier, where every wave of the workgroup waits for them; same order of additions
@@ -1062,16 +1108,16 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
           for (int j = 0; j < per; ++j) R += sInt[tf_l * per + j];    // :661
         }
       } else {
-        for (int p = 0; p < q; ++p) R += sInt[tf_l * q + p];
+        for (int p = 0; p < qs; ++p) R += sInt[tf_l * qs + p];
       }
       const long k = tile * TT + tf_l;                                // = r0 / q + tf_l
       float s = 0.f;
       if (pt < TPTS && k < A.n_k) {
-        const float dj = A.detJv ? A.detJv[k] : A.detJ;
+        const float dj = fl(FL_DETJV) ? A.detJv[k] : A.detJ;
         if (lc.g == 0 && pq_l == 0) {                                 // one lane per test function
           const float lv = dj * R * R;
           loss_var += lv;
-          if (A.lossVec) A.lossVec[k] = lv;
+          if (fl(FL_LOSSVEC)) A.lossVec[k] = lv;
         }
         s = 2.f * A.w2 * dj * R * wq;
       }
@@ -1135,11 +1181,11 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       if constexpr (HID13) {
         if (l - 2 < LY::NSTK) {
           f32x4 acc2[2] = {stash[(l - 2) * ST_L], stash[(l - 2) * ST_L + 64]};
-          h13_wgrad_layer<TANH>(a[l - 2], zd[l - 2], zb, zdb, TA, lc, wave, lane, t_base_bytes, acc2);
+          h13_wgrad_layer<TANH, !LY::BF>(a[l - 2], zd[l - 2], zb, zdb, TA, lc, wave, lane, t_base_bytes, acc2);
           stash[(l - 2) * ST_L] = acc2[0];
           stash[(l - 2) * ST_L + 64] = acc2[1];
         } else {
-          h13_wgrad_layer<TANH>(a[l - 2], zd[l - 2], zb, zdb, TA, lc, wave, lane, t_base_bytes, wacch[l - 2]);
+          h13_wgrad_layer<TANH, !LY::BF>(a[l - 2], zd[l - 2], zb, zdb, TA, lc, wave, lane, t_base_bytes, wacch[l - 2]);
         }
       }
       else if constexpr (NHACC == 2) {
@@ -1162,7 +1208,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       if constexpr (LY::BF) {
         // bf16 pieces through the transposed reads of the same images: K fragment over the OUT-features 4(8qf+j)+g of layer l,
         // row tile over the IN-positions 16 mt + c (all four on the matrix pipe)
-        const char* tl = wtr + (l - 2) * IMG;
+        const char* tl = win_base(trb, l);
 #pragma unroll
         for (int qf = 0; qf < 2; ++qf) {
           u32x4 Bz[3], Bzd[3];
@@ -1255,7 +1301,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
         }
       }
     }
-    if (thin_in) thin_wgrad_in<KS>(xin, gin, zb, zdb, TA, TB, lc, wave, lane, wacc1[0]);
+    if (fl(FL_THIN_IN)) thin_wgrad_in<KS>(xin, gin, zb, zdb, TA, TB, lc, wave, lane, wacc1[0]);
     else wgrad_layer<KS0, KS, true, TANH, LY::MERGE>(xin, gin, zb, zdb, TA, TB, lc, wave, wacc1, true);
   }
 
