@@ -107,10 +107,11 @@ def _rel(got, want):
     return abs(got - want) / max(abs(want), 1e-300) if want != 0.0 else abs(got)
 
 
-def check_parity(i, eng, tag, ref, g32, batch=0, rowwise_eval=False):
+def check_parity(i, eng, tag, ref, g32, batch=0, rowwise_eval=False, net=None, record=None):
     """eval_loss (with lossVec) and grad of a batch against the reference (ref, gref); with rowwise_eval also the row-wise
-    evaluation of a batch that carries a map (debug_point_route(8)).  Prints and records every figure, then asserts."""
-    d_in, dim, widths, td = CASES[i][0], CASES[i][1], CASES[i][2], CASES[i][10]
+    evaluation of a batch that carries a map (debug_point_route(8)).  Prints and records every figure, then asserts.  net, record:
+    (d_in, dim, widths, td) and the record of a caller whose case is not one of CASES (tests/test_dedup_maps_gpu.py)."""
+    d_in, dim, widths, td = (CASES[i][0], CASES[i][1], CASES[i][2], CASES[i][10]) if net is None else net
     ref, gref = ref
     evals = {'eval': eng.eval_loss(batch, lossVec=True)}
     if rowwise_eval:
@@ -131,7 +132,7 @@ def check_parity(i, eng, tag, ref, g32, batch=0, rowwise_eval=False):
     rec['worst_block'] = max(errs, key=errs.get)
     rec['worst_block_err'] = errs[rec['worst_block']]
     rec['kernel_path'] = list(eng.kernel_path())
-    RECORD[tag] = rec
+    (RECORD if record is None else record)[tag] = rec
     print('dedup terms %s: %s' % (tag, json.dumps(rec, sort_keys=True)))
     assert np.all(np.isfinite(g))
     for name, (out, lv) in evals.items():

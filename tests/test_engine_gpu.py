@@ -402,7 +402,7 @@ def _csr(uid, U):
     return rowptr, order
 
 
-@pytest.mark.parametrize('case', [
+DEDUP_CASES = [
     # d_in dim widths            q   n_k  U     nB  bDof source integW
     (2, 1, [20, 20, 20],         16, 50,  230,  30, 18,  False, False),
     (3, 2, [50, 50, 50, 50, 50], 64, 40,  500,  77, 40,  True,  False),
@@ -423,7 +423,10 @@ def _csr(uid, U):
     (8, 2, [32, 17],             216, 9,   500,  12, 6,   True,  True),       # 2D+t + 5 parameters, two-pass network
     (6, 3, [64, 64, 64],         16,  40,  400,  20, 10,  False, True),       # 3D+t + 2 parameters
     (8, 3, [50, 50, 50, 50],     64,  21,  333,  40, 22,  True,  False),      # 3D+t + 4 parameters
-])
+]
+
+
+@pytest.mark.parametrize('case', DEDUP_CASES)
 def test_dedup_formulation_parity(case):
     """De-duplicated formulation (one network evaluation per unique quadrature point): same loss
     and gradient as the row-wise formulation -- against the fp64 oracle on the expanded rows and
@@ -440,40 +443,60 @@ def _dedup_parity(case, td, tag=None):
     uid = rng.integers(0, U, n).astype(np.int32)
     uid[:U] = np.arange(U)                                           # every unique point is used
     rng.shuffle(uid)
-    Input = Xu[uid]
-    gcoef = rng.standard_normal((n, dim)).astype(np.float32)
-    src = rng.standard_normal((n, 1)).astype(np.float32) if source else None
-    N1 = rng.uniform(0, 1, q).astype(np.float32)
-    dNt1 = rng.standard_normal(q).astype(np.float32)
-    W = rng.uniform(0.5, 1, (1, q)).astype(np.float32) if integW else None
-    biInput = rng.uniform(-1, 1, (nB, d_in)).astype(np.float32)
-    biLabel = rng.standard_normal((nB, 1)).astype(np.float32)
-    w = np.array([3.0, 2.0, 5.0]) if td else np.array([3.0, 0.0, 5.0])
+    d = dict(Xu=Xu, uid=uid, Input=Xu[uid], gcoef=rng.standard_normal((n, dim)).astype(np.float32),
+             source=rng.standard_normal((n, 1)).astype(np.float32) if source else None,
+             N1=rng.uniform(0, 1, q).astype(np.float32), dNt1=rng.standard_normal(q).astype(np.float32),
+             integW=rng.uniform(0.5, 1, (1, q)).astype(np.float32) if integW else None,
+             biInput=rng.uniform(-1, 1, (nB, d_in)).astype(np.float32), biLabel=rng.standard_normal((nB, 1)).astype(np.float32),
+             bDof=bDof, n_k=n_k, w=np.array([3.0, 2.0, 5.0]) if td else np.array([3.0, 0.0, 5.0]))
+    d['rowptr'], d['rowidx'] = _csr(uid, U)
     eng = VNEngine(dim, d_in, widths, td, q, isSource=source, integWflag=integW)
     if not td:
         assert eng.dedup_supported()                                 # what train(dedup='auto') would pick for this problem
     eng.init_params(seed=4)
-    flat = eng.get_params()
-    eng.set_fe_table(N1, dNt1, W)
-    eng.set_interior(0, Input, gcoef, src, n_k=n_k, detJ=0.05)
-    eng.set_bic(biInput, biLabel, bDof, 2.0)
-    eng.set_weights(w)
+    dedup_checks(eng, d, td, tag)
+    eng.close()
+
+
+def dedup_oracle(eng, d, td, act='sigmoid', dtype=torch.float64):
+    """The oracle on the expanded rows of a ready-made map (the dict of dedup_checks) at the engine's parameters."""
+    f = np.float64 if dtype == torch.float64 else np.float32
+    cv = lambda a: None if a is None else a.astype(f)
+    n_k, q = d['n_k'], eng.integNum
+    n = n_k * q
+    return og.loss_and_grad(
+        eng.get_params().astype(f), eng.inpDim, eng.layerWidth, dtype,
+        Input=cv(d['Input']), gcoef=cv(d['gcoef']), source=cv(d['source']),
+        N=np.tile(d['N1'], n_k).reshape(n, 1).astype(f), dNt=np.tile(d['dNt1'], n_k).reshape(n, 1).astype(f),
+        integW=cv(d['integW']), intShape=[n_k, q], detJ=0.05, detJvec=False,
+        biInput=cv(d['biInput']), biLabel=cv(d['biLabel']), bDof=d['bDof'], biDimVal=2.0, w=d['w'],
+        dim=eng.dim, time_dependent=td, is_source=d['source'] is not None, integWflag=d['integW'] is not None, activation=act)
+
+
+def dedup_checks(eng, d, td, tag=None, act='sigmoid', oracle=None, errors=None):
+    """The checks of the de-duplicated formulation on an engine that has its parameters and a ready-made map in d (Xu, uid,
+    rowptr, rowidx, Input = Xu[uid], gcoef, source, N1, dNt1, integW, biInput, biLabel, bDof, n_k, w): the row-wise and the
+    de-duplicated step against the fp64 oracle (globally and per block), against each other, eval_loss with lossVec on the map and
+    row-wise, a second grad the same bits, and set_dedup(batch) off restoring the row-wise bits.  oracle: a callable dtype ->
+    (ref, gref) for a caller that has the reference already; its fp32 form then serves the per-block rule as g32.  errors: the
+    record the figures go to (default: this module's).  Returns (row-wise, de-duplicated) gradients."""
+    ERRORS = globals()['ERRORS'] if errors is None else errors
+    d_in, dim, widths, q, n_k = eng.inpDim, eng.dim, eng.layerWidth, eng.integNum, d['n_k']
+    Xu, uid, rowptr, rowidx = d['Xu'], d['uid'], d['rowptr'], d['rowidx']
+    eng.set_fe_table(d['N1'], d['dNt1'], d['integW'])
+    eng.set_interior(0, d['Input'], d['gcoef'], d['source'], n_k=n_k, detJ=0.05)
+    eng.set_bic(d['biInput'], d['biLabel'], d['bDof'], 2.0)
+    eng.set_weights(d['w'])
     gb = eng.bind_grad_buffer()
     eng.grad(0)
     torch.cuda.synchronize()
     g_rows = gb.cpu().numpy().copy()
-    rowptr, rowidx = _csr(uid, U)
     eng.set_dedup(0, Xu, uid, rowptr, rowidx)
     eng.grad(0)
     torch.cuda.synchronize()
     g_dd = gb.cpu().numpy().copy()
-    ref, gref = og.loss_and_grad(
-        flat.astype(np.float64), d_in, widths, torch.float64, Input=Input.astype(np.float64),
-        gcoef=gcoef.astype(np.float64), source=None if src is None else src.astype(np.float64),
-        N=np.tile(N1, n_k).reshape(n, 1).astype(np.float64), dNt=np.tile(dNt1, n_k).reshape(n, 1).astype(np.float64),
-        integW=None if W is None else W.astype(np.float64), intShape=[n_k, q], detJ=0.05, detJvec=False,
-        biInput=biInput.astype(np.float64), biLabel=biLabel.astype(np.float64), bDof=bDof, biDimVal=2.0, w=w,
-        dim=dim, time_dependent=td, is_source=source, integWflag=integW)
+    ref, gref = dedup_oracle(eng, d, td, act) if oracle is None else oracle(torch.float64)
+    g32 = None if oracle is None else (lambda: oracle(torch.float32)[1])
     P = eng.P
     if tag is not None:
         ERRORS[tag] = {k: float(np.max(np.abs(g[:P] - gref)) / np.max(np.abs(gref))) for k, g in
@@ -487,10 +510,16 @@ def _dedup_parity(case, td, tag=None):
         assert np.max(np.abs(g[:P] - gref)) <= GRAD_RTOL * np.max(np.abs(gref))
     rec = ERRORS.setdefault(tag or 'dedup %s d_in%d q%d' % (widths, d_in, q), {})
     for name, g in (('rowwise', g_rows), ('dedup', g_dd)):
-        r = assert_grad_close(g, gref, d_in, widths, GRAD_RTOL, dim=dim, td=td, what=name)
-        rec.update({'worst_block_' + name: r['worst_block'], 'worst_block_err_' + name: r['worst_block_err']})
-    r = assert_pair_close(g_dd, g_rows, d_in, widths, 2e-4, dim=dim, td=td, what='dedup vs row-wise')
-    rec.update(worst_block_dedup_vs_rowwise=r['worst_block'], worst_block_err_dedup_vs_rowwise=r['worst_block_err'])
+        r = {}                                                       # (filled before any assertion: a miss leaves its figures)
+        try:
+            assert_grad_close(g, gref, d_in, widths, GRAD_RTOL, dim=dim, td=td, what=name, g32=g32, rec=r)
+        finally:
+            rec.update({'worst_block_' + name: r.get('worst_block'), 'worst_block_err_' + name: r.get('worst_block_err')})
+    r = {}
+    try:
+        assert_pair_close(g_dd, g_rows, d_in, widths, 2e-4, dim=dim, td=td, what='dedup vs row-wise', rec=r)
+    finally:
+        rec.update(worst_block_dedup_vs_rowwise=r.get('worst_block'), worst_block_err_dedup_vs_rowwise=r.get('worst_block_err'))
     assert np.allclose(g_dd[P + 1:P + 4], g_rows[P + 1:P + 4], rtol=1e-5)
     # vn_eval_loss (splitLoss: every monitor, trainWeight) of a batch that carries the map: (u, grad u) once per unique point and the
     # loss-only form of the assembly kernel (round 6) -- loss components and loss field against the fp64 oracle at the suite's bars,
@@ -501,6 +530,9 @@ def _dedup_parity(case, td, tag=None):
     eng.debug_point_route(0)
     torch.cuda.synchronize()
     lvref = np.asarray(ref['lossVec'], dtype=np.float64).reshape(-1)
+    for name, out, lv in (('dedup', out_dd, lv_dd), ('rowwise', out_rw, lv_rw)):
+        rec['eval_loss_' + name] = float(abs(out[0] - ref['loss']) / abs(ref['loss']))
+        rec['eval_lossVec_' + name] = float(np.max(np.abs(lv.cpu().numpy().astype(np.float64) - lvref)) / np.max(np.abs(lvref)))
     for out, lv in ((out_dd, lv_dd), (out_rw, lv_rw)):
         assert abs(out[0] - ref['loss']) <= LOSS_RTOL * abs(ref['loss'])
         assert abs(out[1] - ref['BCloss']) <= LOSS_RTOL * abs(ref['BCloss']) and abs(out[2] - ref['ICloss']) <= LOSS_RTOL * abs(ref['ICloss'])
@@ -516,7 +548,7 @@ def _dedup_parity(case, td, tag=None):
     eng.grad(0)
     torch.cuda.synchronize()
     assert np.array_equal(gb.cpu().numpy(), g_rows)
-    eng.close()
+    return g_rows, g_dd
 
 
 DEDUP_STEADY = [

@@ -125,7 +125,11 @@ __global__ __launch_bounds__(256) void vn_dedup_seed_kernel(VnDedupArgs a) {
 // gcoef by row, which fetched 2.6 x the bytes it used; per-row seeds written by the seed kernel and gathered here: 8 bytes of
 // HBM traffic per row for what n_k floats hold.)
 constexpr int VN_GATHER_PB = 256;           // unique points per block
-constexpr int VN_GATHER_CH = 2304;          // CSR entries per LDS chunk (256 points x 8 rows + slack: normally one chunk)
+// CSR entries per LDS chunk: 256 points x 8 rows + slack, i.e. one chunk per block on a uniform 2D+t grid.  A block that owns more
+// walks the loop below again: a 3D+t grid (interior points own 16 rows, blocks of up to 2768 entries), a caller-built map with a
+// hot point or with few unique points (a segment may be cut by a chunk boundary or span several chunks: the lo / hi clipping).
+// tests/dedup_map_cases.py reads both constants out of this file and builds its maps around them.
+constexpr int VN_GATHER_CH = 2304;
 __global__ __launch_bounds__(256) void vn_dedup_gather_kernel(VnDedupArgs a) {
   __shared__ float sp[VN_GATHER_CH][4];     // (-dNt s, g0 s, g1 s, g2 s) per entry
   __shared__ int sptr[VN_GATHER_PB + 1];

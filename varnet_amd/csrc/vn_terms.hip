@@ -178,8 +178,9 @@ __global__ __launch_bounds__(256) void vn_nldiff_source_kernel(VnTermDedupArgs a
 }
 
 // sum over the rows r of unique point j, in CSR order, of term(r, k, p): k = r / q the row's test function, p = r % q its
-// quadrature point.  A point has 2^feDim rows on a uniform grid (<= 8): four entries in flight per thread -- all row indices,
-// then all dependent loads, then the additions in CSR order.
+// quadrature point.  A point has up to 2^feDim rows on a uniform grid (8 in 2D+t, 16 in 3D+t) and any number on a caller-built
+// map (one thread then walks them all): four entries in flight per thread and pass -- all row indices, then all dependent loads,
+// then the additions in CSR order.
 template <class Term>
 __device__ __forceinline__ float csr_walk(const VnTermDedupArgs& a, long j, Term term) {
   const int q = a.q;
