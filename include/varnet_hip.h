@@ -255,6 +255,45 @@ int vn_set_nlflux(vn_engine* h, int32_t batch, const float* phi_dev, const doubl
  * this term); the 4-wave cross-check geometry (VN_KERNEL_FUSED) returns VN_EUNSUPPORTED.  Without a registration nothing is
  * launched, nothing is allocated and every result is bit for bit what it is without this call. */
 int vn_set_nldiff(vn_engine* h, int32_t batch, const float* psi_dev, const double coef[3]);
+/* Per-test-function loss weights.  The variational loss of a batch is var = sum_k l_k, l_k = detJ_k R_k^2 (lossVec[k]); with
+ * weights omega_k >= 0 it becomes  var = sum_k omega_k l_k,  loss = w0 BC + w1 IC + w2 var.  THE GRADIENT TREATS omega AS
+ * CONSTANT: the seed of test function k becomes 2 w2 omega_k detJ_k R_k, and every per-row seed derived from it (time term,
+ * reaction, flux and D(u) value seeds, the D(u) rescale) is linear in it.  lossVec stays UNWEIGHTED everywhere, in fp32 and
+ * fp64: the causal weights are derived from it, and residual-driven sampling and the monitors read it.  BC / IC terms are not
+ * weighted.
+ *   omega_dev  [n_k] device floats.  READ on every step (it must stay valid while registered), like rate_dev.  NULL clears
+ *              the registration.
+ * Per batch, called after vn_set_interior of that batch: a new vn_set_interior clears it, vn_set_dedup, vn_set_reaction,
+ * vn_set_nlflux and vn_set_nldiff keep it, and this call keeps theirs; it replaces a causal registration (vn_set_causal) of the
+ * batch.  An unregistered batch: VN_ESTATE; a batch without interior rows (n_k == 0): VN_EINVAL; the 4-wave cross-check geometry
+ * (VN_KERNEL_FUSED): VN_EUNSUPPORTED; clearing is always accepted.  A change invalidates the L-BFGS (f_k, g_k) and ring of that
+ * batch.  vn_grad / vn_train_step / vn_train_epoch, vn_eval_loss (weighted var and loss, unweighted lossVec), vn_lbfgs_step and
+ * vn_objective_f64 (weights widened exactly) all see the weights.  They work under a communicator.
+ * Routes: the weights are applied in kernels of their own (vn_weights.hip) after the seed kernel and the terms' seed kernels:
+ * the row-wise routes scale the rows' seeds in one elementwise pass, the de-duplicated step scales the n_k test-function seeds
+ * before its gather; both replace the var loss partials by block sums of omega_k l_k in a fixed order.  A batch of the
+ * single-launch 8-wave route runs the two-pass sequence instead.  When the caller passes no lossVec the engine uses an [n_k]
+ * buffer of its own, allocated at the first registration.  Without a registration nothing is launched, nothing is allocated
+ * and every result is bit for bit what it is without this call. */
+int vn_set_tf_weights(vn_engine* h, int32_t batch, const float* omega_dev);
+/* Causal time-slab weights (Wang, Sankaran, Perdikaris 2022), recomputed on the device at every step from that step's own loss
+ * field.  Every test function has a slab id s_k in [0, n_slabs).  With L_s the mean of l_k over the batch's test functions of
+ * slab s (an empty slab: 0) and C_s = sum_{s' < s} L_s':  omega_k = exp(-eps C_{s_k}), so omega = 1 on slab 0 and a late slab
+ * counts only once the earlier ones have converged.  Accumulated in fp64 in a fixed order, no floating-point atomics: two calls
+ * give the same bits (vn_state_rollback + replay relies on it).  Everything else as for vn_set_tf_weights, whose registration
+ * on the same batch this call replaces, and vice versa.
+ *   slab_dev   [n_k] device ints, VALIDATED on the device and COPIED at this call, which therefore synchronises (like
+ *              vn_set_dedup); the caller's array need not outlive the call.  The engine keeps a CSR slab -> test functions in
+ *              increasing k, so the slab sums have a fixed order.  NULL clears the registration.
+ *   n_slabs    1 <= n_slabs <= 4096;   eps  >= 0 and finite;   ids in range.  Otherwise VN_EINVAL.
+ * Refused: vn_lbfgs_step on a batch with a causal registration (VN_EUNSUPPORTED: with constant-for-the-gradient weights that
+ * move with theta the search direction is not the gradient of the reported loss, so an Armijo test on it means nothing);
+ * this call on a handle that has a communicator, and vn_comm_init on a handle that has a causal batch (VN_EUNSUPPORTED: a
+ * rank's slab means would cover only its shard, so W ranks would train another objective than one rank). */
+int vn_set_causal(vn_engine* h, int32_t batch, const int32_t* slab_dev, int32_t n_slabs, double eps);
+/* omega_s of the batch's causal registration at the current parameters into omega_slab_host[n_slabs] (n_slabs as registered):
+ * runs the batch's loss-only evaluation.  Synchronises; changes no engine state.  Without a causal registration: VN_ESTATE. */
+int vn_causal_weights(vn_engine* h, int32_t batch, double* omega_slab_host, int32_t n_slabs);
 /* updateDictFields('trainW') (VarNetUtility.py:921-922); the caller applies the
  * w[0:2] /= batchNum*puNum rule (VarNetUtility.py:900-901). */
 int vn_set_weights(vn_engine* h, const double w[3]);

@@ -8,6 +8,7 @@
 #include "vn_pgrad16.h"
 #include "vn_taylor16.h"
 #include "vn_terms.h"
+#include "vn_weights.h"
 #include "vn_split16.h"
 
 hipError_t vn_calibrate_f64(int ncu, hipStream_t s, double ghz, double out[3]);      // vn_calib.hip (fp64 MFMA loop)
@@ -94,9 +95,13 @@ struct Batch {
   // diffusivity D(u) = d0 + d1 u + d2 u^2 of div(kappa D(u) grad u) (vn_set_nldiff); gcoef is then kappa dN/dx alone;
   // stream = psi = sum_d v_d dN/dx_d + N div v per row, or nullptr: no advection
   Term nldiff = {false, nullptr, {1.0, 0.0, 0.0}};
+  // per-test-function loss weights (vn_weights.hip): static (vn_set_tf_weights) or causal (vn_set_causal); as initialised: none
+  VnWeightsReg wt;
+  int* wt_own = nullptr;      // owned: the causal registration's slab ids and CSR, one allocation (wt.slab / wt.sptr / wt.sidx)
 };
 
 inline bool has_terms(const Batch& b) { return b.react.on || b.nlflux.on || b.nldiff.on; }
+inline bool has_weights(const Batch& b) { return vn_weights_on(b.wt); }
 
 // How an engine computes its gradient, decided once by pick_route (vn_create).
 enum class Route {
@@ -182,6 +187,11 @@ struct vn_engine {
   bool feN_zero = false;      // the table of vn_set_fe_table has an entry N_p == 0 (the flux term's fold divides by N_p)
   float* rx_seff = nullptr; long rx_seff_cap = 0;   // the terms in the de-duplicated step: source + their shares per row (vn_terms.hip)
   float* nd_A = nullptr; long nd_A_cap = 0;         // quasilinear diffusion on the row-wise routes: sum_d u_{x_d} gcoef_d per row (vn_terms.hip)
+  // loss weights (vn_weights.hip), allocated at the first registration: the loss field of a step whose caller passes none, omega_k
+  // of the causal mode, and its slab statistics (doubles, sized in floats: lsum [S * chunks], then oslab [S])
+  float* wt_lvec = nullptr; long wt_lvec_cap = 0;
+  float* wt_omega = nullptr; long wt_omega_cap = 0;
+  float* wt_stat = nullptr; long wt_stat_cap = 0;
   // boundary-flux rows (vn_set_flux_bc): caller-owned inputs, engine-owned work buffers; nF == 0: none
   const float *fX = nullptr, *fN = nullptr, *fcoef = nullptr, *flabel = nullptr;
   long nF = 0;
@@ -560,6 +570,38 @@ int terms_gather_dedup(vn_engine* h, const Batch& b, const VnDedupArgs& d) {
   return VN_OK;
 }
 
+// ---- per-test-function loss weights (vn_weights.hip) ----
+constexpr long kWtStat = 2L * VN_WEIGHTS_MAX_SLABS * (VN_WEIGHTS_MAX_CHUNKS + 1);   // floats that hold lsum and oslab at their largest
+
+inline VnWeightsWork weights_work(const vn_engine* h) {
+  VnWeightsWork wk;
+  wk.lsum = reinterpret_cast<double*>(h->wt_stat);
+  wk.oslab = wk.lsum + (long)VN_WEIGHTS_MAX_SLABS * VN_WEIGHTS_MAX_CHUNKS;
+  return wk;
+}
+
+// Where a seed kernel writes the batch's loss field: the caller's array, else the engine's own when the weights need one
+inline float* weights_lossvec(const vn_engine* h, const Batch& b, float* lossVec) {
+  return lossVec || !has_weights(b) ? lossVec : h->wt_lvec;
+}
+
+// After the seed kernel and every term's seed kernel: [causal: the weights from lossVec], stf scaled (de-duplicated step),
+// the var loss partials of the seed kernel's blocks (tfb test functions each) replaced, the rows' seeds scaled (row-wise routes)
+int weights_stage(vn_engine* h, const Batch& b, const float* lossVec, int tfb, float* stf, float* part, bool rows) {
+  if (!has_weights(b)) return VN_OK;
+  const bool causal = b.wt.S > 0;
+  HIPCHK(vn_weights_apply_f32(b.wt, weights_work(h), lossVec, b.n_k, tfb, causal ? h->wt_omega : nullptr, stf, part, h->stream));
+  if (rows)
+    HIPCHK(vn_weights_rows_f32(causal ? h->wt_omega : b.wt.omega, b.n_k, h->cfg.integ_num, h->ubar, h->udbar, h->stream));
+  return VN_OK;
+}
+
+void clear_weights(Batch& b) {
+  if (b.wt_own) (void)hipFree(b.wt_own);
+  b.wt_own = nullptr;
+  b.wt = VnWeightsReg();
+}
+
 // Every launch of the 8-wave fused kernel: its global-memory stash (per workgroup; none for most instantiations) is sized here
 int fused8_launch(vn_engine* h, VnFusedArgs& f, int grid) {
   const long per = (long)(vn_fused16_stash_bytes(h->net) / sizeof(float));
@@ -622,9 +664,10 @@ int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst, con
   if (int rc = ensure(&h->losspart, &h->losspart_cap, (long)(sblk + bgrid) * 3)) return rc;
   HIPCHK(point_pass(h, b.Xu, b.U, nullptr, nullptr, h->dd_uv));
   VnDedupArgs a = dedup_args(h, b);
-  a.lossVec = lossVec; a.part = h->losspart;          // loss only: no seeds
+  a.lossVec = weights_lossvec(h, b, lossVec); a.part = h->losspart;          // loss only: no seeds
   if (int rc = terms_source_dedup(h, b, a)) return rc;
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
+  if (int rc = weights_stage(h, b, a.lossVec, VN_DEDUP_TFB, nullptr, a.part, false)) return rc;
   if (int rc = fused_forward(h, bi_x(h, b), nullptr, h->nB, h->ub, nullptr)) return rc;
   VnSeedArgs s = seed_args(h, b);
   // interior set empty: the BC/IC terms alone (Nrow, dNtrow and detJv are nullptr on a batch with a de-duplication map)
@@ -661,11 +704,12 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
   if (int rc = ensure(&h->losspart, &h->losspart_cap, (long)grid * 3)) return rc;
   VnSeedArgs a = seed_args(h, b);
   if (with_seeds) { a.ubar = h->ubar; a.udbar = h->udbar; a.ubar_b = h->ubar_b; }
-  a.lossVec = lossVec; a.part = h->losspart;
+  a.lossVec = weights_lossvec(h, b, lossVec); a.part = h->losspart;
   if (int rc = terms_fold_rows(h, b)) return rc;
   HIPCHK(vn_seed_launch(a, grid, h->stream));
   if (with_seeds)
     if (int rc = terms_seed_rows(h, b)) return rc;
+  if (int rc = weights_stage(h, b, a.lossVec, 256, nullptr, a.part, with_seeds)) return rc;
   if (lossdst) {
     HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2, lossdst, h->stream,
                             VnOptArgs(), fx));
@@ -740,6 +784,7 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx)
 // Also the step of a batch with a reaction term on the single-launch route, at any integ_num (vn_set_reaction): the term lives
 // in the seed kernel; neither mode of the fused kernel looks at integ_num.  A flux term (vn_set_nlflux) and a diffusivity D(u)
 // (vn_set_nldiff) take the same sequence, with their elementwise kernels around the seed kernel (terms_fold_rows, terms_seed_rows).
+// So does a batch with per-test-function loss weights (vn_set_tf_weights, vn_set_causal): they are applied after the seed kernel.
 int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
   const int grid = h->ncu, P = h->net.P;
   const int sgrid = (int)((b.n_k + 255) / 256);
@@ -756,9 +801,11 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& f
   a.ubar = h->ubar; a.udbar = h->udbar;
   a.ub = nullptr; a.label = nullptr; a.nB = 0; a.bDof = 0; a.biDimVal = 0.f;   // BC/IC: step 3
   a.part = lp + (long)grid * 3;
+  a.lossVec = weights_lossvec(h, b, nullptr);
   if (int rc = terms_fold_rows(h, b)) return rc;
   HIPCHK(vn_seed_launch(a, sgrid, h->stream));
   if (int rc = terms_seed_rows(h, b)) return rc;
+  if (int rc = weights_stage(h, b, a.lossVec, 256, nullptr, a.part, true)) return rc;
 
   f.mode = 2; f.out_u = nullptr; f.out_ud = nullptr; f.seed_u = h->ubar; f.seed_ud = h->udbar; f.nB = h->nB;
   if (int rc = prof_start(h)) return rc;
@@ -786,8 +833,10 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx)
   VnDedupArgs a = dedup_args(h, b);
   a.stf = h->u; a.part = lp + (long)grid * 3;
   a.seed_u = h->dd_su; a.seed_g = h->dd_sg;
+  a.lossVec = weights_lossvec(h, b, nullptr);
   if (int rc = terms_source_dedup(h, b, a)) return rc;
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
+  if (int rc = weights_stage(h, b, a.lossVec, VN_DEDUP_TFB, a.stf, a.part, false)) return rc;   // stf[k] *= omega_k before the gather
   HIPCHK(vn_dedup_gather_launch(a, h->stream));
   if (int rc = terms_gather_dedup(h, b, a)) return rc;
   VnFusedArgs f = fused_args(h, &b);
@@ -955,14 +1004,16 @@ int vn_destroy(vn_engine* h) {
   if (h->comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(h->stream); (void)g_rccl.CommDestroy(h->comm); h->comm = nullptr; }
   void* ptrs[] = {h->theta, h->m, h->v, h->snap, h->theta64, h->gradbuf_int, h->lossbuf, h->partial, h->feN, h->fedNt,
                   h->feW, h->u, h->ud, h->ubar, h->udbar, h->ub, h->ubar_b, h->losspart, h->fused_losspart, h->stamps, h->dd_uv, h->dd_su, h->dd_sg, h->dd_partial,
-                  h->dd_losspart, h->rx_seff, h->nd_A, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial,
+                  h->dd_losspart, h->rx_seff, h->nd_A, h->wt_lvec, h->wt_omega, h->wt_stat, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial,
                   h->lb.ring, h->lb.theta_k, h->lb.g_k, h->lb.d, h->lb.part, h->lb.G, h->lb.coef, h->lb.meta};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->lb.out) (void)hipHostFree(h->lb.out);
   vn_obj64_free(h->o64);
-  for (Batch& b : h->batches)
+  for (Batch& b : h->batches) {
     if (b.gcsr) (void)hipFree(b.gcsr);
+    clear_weights(b);
+  }
   for (auto e : h->ev0) if (e) (void)hipEventDestroy(e);
   for (auto e : h->ev1) if (e) (void)hipEventDestroy(e);
   for (auto e : h->cev0) if (e) (void)hipEventDestroy(e);
@@ -1141,6 +1192,7 @@ int vn_set_interior(vn_engine* h, int32_t batch, const float* Input, const float
   b.biInput = nullptr; b.biLabel = nullptr;                                            // ... and vn_set_batch_bic
   const Batch fresh;
   b.react = fresh.react; b.nlflux = fresh.nlflux; b.nldiff = fresh.nldiff;             // ... and the three term setters
+  clear_weights(b);                                                                    // ... and vn_set_tf_weights / vn_set_causal
   const long nT = n_k * h->cfg.integ_num;
   if (nT > h->work_rows) {
     long c0 = h->work_rows, c1 = h->work_rows, c2 = h->work_rows, c3 = h->work_rows;
@@ -1250,6 +1302,100 @@ int vn_set_reaction(vn_engine* h, int32_t batch, const float* rate, const double
 int vn_set_nlflux(vn_engine* h, int32_t batch, const float* phi, const double coef[3]) { return set_term(h, batch, kNlflux, phi, coef); }
 int vn_set_nldiff(vn_engine* h, int32_t batch, const float* psi, const double coef[3]) { return set_term(h, batch, kNldiff, psi, coef); }
 
+// vn_set_tf_weights / vn_set_causal: what both check before they touch the batch; *clear: the call unregisters
+static int weights_common(vn_engine* h, int32_t batch, bool clear, const char* who) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
+    return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
+  Batch& b = h->batches[batch];
+  if (clear) {
+    HIPCHK(hipSetDevice(h->cfg.device));
+    lbfgs_invalidate(h, batch);
+    clear_weights(b);
+    return VN_OK;
+  }
+  if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no test function to weight", batch);
+  if (h->route == Route::fused4)
+    return fail(VN_EUNSUPPORTED, "%s is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its single launch has no "
+                                 "place for the weights; every other kernel family carries them", who);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (int rc = ensure(&h->wt_lvec, &h->wt_lvec_cap, b.n_k)) return rc;
+  return VN_OK;
+}
+
+int vn_set_tf_weights(vn_engine* h, int32_t batch, const float* omega_dev) {
+  if (int rc = weights_common(h, batch, omega_dev == nullptr, "vn_set_tf_weights")) return rc;
+  if (!omega_dev) return VN_OK;
+  lbfgs_invalidate(h, batch);
+  Batch& b = h->batches[batch];
+  clear_weights(b);                                  // replaces a causal registration
+  b.wt.omega = omega_dev;
+  return VN_OK;
+}
+
+int vn_set_causal(vn_engine* h, int32_t batch, const int32_t* slab_dev, int32_t n_slabs, double eps) {
+  if (slab_dev) {
+    if (!(std::isfinite(eps) && eps >= 0.0)) return fail(VN_EINVAL, "causal eps = %g must be finite and >= 0", eps);
+    if (n_slabs < 1 || n_slabs > VN_WEIGHTS_MAX_SLABS)
+      return fail(VN_EINVAL, "n_slabs = %d outside [1, %d]", n_slabs, VN_WEIGHTS_MAX_SLABS);
+    if (h && h->comm)
+      return fail(VN_EUNSUPPORTED, "vn_set_causal under a communicator: a rank's slab means would cover only its shard, so the "
+                                   "ranks together would train another objective than one rank");
+  }
+  if (int rc = weights_common(h, batch, slab_dev == nullptr, "vn_set_causal")) return rc;
+  if (!slab_dev) return VN_OK;
+  Batch& b = h->batches[batch];
+  const long n_k = b.n_k;
+  const int S = n_slabs;
+  // the ids index LDS and the CSR in every later step: validated here, on the device, so that a bad id is an error code
+  int bad = 0;
+  auto check = [&](int* err_dev) { return vn_weights_check_launch(slab_dev, n_k, S, err_dev, h->stream); };
+  if (int rc = count_on_device(h, check, &bad)) return rc;
+  if (bad) return fail(VN_EINVAL, "%d slab id(s) outside [0, %d)", bad, S);
+  if (int rc = ensure(&h->wt_omega, &h->wt_omega_cap, n_k)) return rc;
+  if (int rc = ensure(&h->wt_stat, &h->wt_stat_cap, kWtStat)) return rc;
+  // copied at this call (the caller's array need not outlive it); CSR slab -> test functions in increasing k, by counting sort
+  std::vector<int> own((size_t)n_k + (size_t)S + 1 + (size_t)n_k);
+  int* slab = own.data();
+  int* sptr = slab + n_k;
+  int* sidx = sptr + S + 1;
+  HIPCHK(hipMemcpyAsync(slab, slab_dev, (size_t)n_k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  std::fill(sptr, sptr + S + 1, 0);
+  for (long k = 0; k < n_k; ++k) sptr[slab[k] + 1] += 1;
+  long most = 0;
+  for (int s = 0; s < S; ++s) { most = std::max<long>(most, sptr[s + 1]); sptr[s + 1] += sptr[s]; }
+  std::vector<int> fill(sptr, sptr + S);
+  for (long k = 0; k < n_k; ++k) sidx[fill[slab[k]]++] = (int)k;
+  int* dev = nullptr;
+  HIPCHK(hipMalloc((void**)&dev, own.size() * sizeof(int)));
+  hipError_t e = hipMemcpyAsync(dev, own.data(), own.size() * sizeof(int), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) { (void)hipFree(dev); return fail(VN_EHIP, "vn_set_causal: %s", hipGetErrorString(e)); }
+  lbfgs_invalidate(h, batch);
+  clear_weights(b);                                  // replaces a static (or an earlier causal) registration
+  b.wt_own = dev;
+  b.wt.slab = dev; b.wt.sptr = dev + n_k; b.wt.sidx = dev + n_k + S + 1;
+  b.wt.S = S; b.wt.eps = eps;
+  // workgroups per slab: one per 1024 test functions of the fullest slab (four loads in flight per thread)
+  b.wt.chunks = (int)std::min<long>(VN_WEIGHTS_MAX_CHUNKS, std::max<long>(1, (most + 1023) / 1024));
+  return VN_OK;
+}
+
+int vn_causal_weights(vn_engine* h, int32_t batch, double* omega_slab_host, int32_t n_slabs) {
+  if (!h || !omega_slab_host) return fail(VN_EINVAL, "null argument");
+  (void)hipGetLastError();
+  if (int rc = check_batch(h, batch)) return rc;
+  const Batch& b = h->batches[batch];
+  if (b.wt.S <= 0) return fail(VN_ESTATE, "batch %d has no causal registration (call vn_set_causal first)", batch);
+  if (n_slabs != b.wt.S) return fail(VN_EINVAL, "n_slabs = %d, batch %d was registered with %d", n_slabs, batch, b.wt.S);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (int rc = run_forward_and_seed(h, b, false, nullptr, nullptr)) return rc;      // loss only: the interior loss field and its weights
+  HIPCHK(hipMemcpyAsync(omega_slab_host, weights_work(h).oslab, (size_t)b.wt.S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return VN_OK;
+}
+
 int vn_set_bic(vn_engine* h, const float* biInput, const float* biLabel, int64_t nB, int64_t bDof, double biDimVal) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (nB < 0 || bDof < 0 || bDof > nB) return fail(VN_EINVAL, "need 0 <= bDof <= nB");
@@ -1334,7 +1480,8 @@ int vn_grad(vn_engine* h, int32_t batch) {
     case Route::fused4: return run_fused(h, b, h->gradbuf, fx);
     // a reaction term lives in the row-wise seed kernel, a flux term and a diffusivity D(u) around it: the single-launch route
     // runs the two-pass sequence for such a batch
-    case Route::fused8: return has_terms(b) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
+    // ... and so do per-test-function loss weights, applied after it
+    case Route::fused8: return has_terms(b) || has_weights(b) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
     case Route::twopass: return run_twopass(h, b, h->gradbuf, fx);
   }
 }
@@ -1453,6 +1600,11 @@ int vn_lbfgs_step(vn_engine* h, int32_t batch, int32_t max_trials, double info[1
   if (max_trials < 1) return fail(VN_EINVAL, "max_trials must be at least 1");
   (void)hipGetLastError();
   if (int rc = check_batch(h, batch)) return rc;
+  if (h->batches[batch].wt.S > 0)
+    return fail(VN_EUNSUPPORTED, "vn_lbfgs_step on batch %d, which has a causal registration (vn_set_causal): its weights move with "
+                                 "the parameters but are held constant for the gradient, so the search direction is not the gradient "
+                                 "of the reported loss and an Armijo test on it means nothing; static weights (vn_set_tf_weights) work",
+                batch);
   HIPCHK(hipSetDevice(h->cfg.device));
   if (int rc = lbfgs_alloc(h)) return rc;
   const long P = h->net.P;
@@ -1575,6 +1727,7 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   p.react = b.react.on ? 1 : 0; p.rate = b.react.stream; std::copy(b.react.c, b.react.c + 3, p.coef);
   p.nlflux = b.nlflux.on ? 1 : 0; p.phi = b.nlflux.stream; std::copy(b.nlflux.c, b.nlflux.c + 3, p.fcoef3);
   p.nldiff = b.nldiff.on ? 1 : 0; p.psi = b.nldiff.stream; std::copy(b.nldiff.c, b.nldiff.c + 3, p.dcoef3);
+  p.wt = b.wt;
   hipError_t e = vn_obj64_run(h->o64, p, grad_dev, lossVec_dev, out, h->ncu, h->stream);
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(h->stream);
@@ -1697,6 +1850,10 @@ int vn_comm_init(vn_engine* h, int32_t rank, int32_t world, const void* unique_i
     if (h->comm_abandoned) return fail(VN_ESTATE, "this engine's communicator was abandoned (vn_comm_abandon): it takes no other");
     if (h->comm) return fail(VN_ESTATE, "communicator already initialised (call vn_comm_destroy first)");
   }
+  for (size_t i = 0; i < h->batches.size(); ++i)
+    if (h->batches[i].wt.S > 0)
+      return fail(VN_EUNSUPPORTED, "vn_comm_init: batch %d has a causal registration (vn_set_causal); a rank's slab means would cover "
+                                   "only its shard, so the ranks together would train another objective than one rank", (int)i);
   if (int rc = load_rccl()) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   ncclUniqueId id;

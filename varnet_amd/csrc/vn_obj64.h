@@ -2,6 +2,7 @@
 // vn_internal.h, which every kernel's source hash covers.
 #pragma once
 #include "vn_internal.h"
+#include "vn_weights.h"
 
 // Engine-owned work buffers of the evaluation, sized at the call that first needs them and released by vn_obj64_free.
 struct VnObj64Work {
@@ -12,6 +13,10 @@ struct VnObj64Work {
   double* part = nullptr;  long part_cap = 0;    // [waves][gradient image]
   double* lpart = nullptr; long lpart_cap = 0;   // [seed blocks][4]: var, bc, ic, flux partial sums
   double* out = nullptr;                         // [4] loss, BC, IC, var
+  // per-test-function loss weights (vn_weights.hip), allocated by the first evaluation of a batch that has them
+  double* lvec = nullptr;  long lvec_cap = 0;    // [n_k] the loss field when the caller passes none
+  double* omega = nullptr; long omega_cap = 0;   // [n_k] omega_k in double
+  double* wstat = nullptr; long wstat_cap = 0;   // causal: lsum [S * chunks], then omega_s [S]
 };
 
 // What the evaluation reads: the batch as registered (fp32 device arrays, widened exactly by the kernels).
@@ -34,6 +39,8 @@ struct VnObj64Problem {
   int nlflux; const float* phi; double fcoef3[3];
   // diffusivity D(u) of the batch (vn_set_nldiff): psi [n_k*q] or nullptr, coefficients d0..d2; nldiff == 0: none
   int nldiff; const float* psi; double dcoef3[3];
+  // per-test-function loss weights of the batch (vn_set_tf_weights / vn_set_causal); default: none
+  VnWeightsReg wt;
 };
 
 bool vn_obj64_supported(const VnNet& net);

@@ -524,12 +524,12 @@ hipError_t ensure_d(double** p, long* cap, long need) {
 bool vn_obj64_supported(const VnNet& net) { return vn_net_in_kernel_range(net) && net.dim <= 3; }
 
 void vn_obj64_free(VnObj64Work& w) {
-  double** ps[] = {&w.img, &w.u, &w.ud, &w.act, &w.part, &w.lpart, &w.out};
+  double** ps[] = {&w.img, &w.u, &w.ud, &w.act, &w.part, &w.lpart, &w.out, &w.lvec, &w.omega, &w.wstat};
   for (double** p : ps) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
-  w.img_cap = w.u_cap = w.ud_cap = w.act_cap = w.part_cap = w.lpart_cap = 0;
+  w.img_cap = w.u_cap = w.ud_cap = w.act_cap = w.part_cap = w.lpart_cap = w.lvec_cap = w.omega_cap = w.wstat_cap = 0;
 }
 
 hipError_t vn_obj64_run(VnObj64Work& w, const VnObj64Problem& p, double* grad_dev, double* lossVec_dev, double out_host[4],
@@ -577,8 +577,21 @@ hipError_t vn_obj64_run(VnObj64Work& w, const VnObj64Problem& p, double* grad_de
   sa.nlflux = p.nlflux; sa.phi = p.phi; sa.f1 = p.fcoef3[0]; sa.f2 = p.fcoef3[1]; sa.f3 = p.fcoef3[2];
   sa.nldiff = p.nldiff; sa.psi = p.psi; sa.d0 = p.dcoef3[0]; sa.d1 = p.dcoef3[1]; sa.d2 = p.dcoef3[2];
   sa.lossVec = lossVec_dev; sa.lpart = w.lpart;
+  const bool weighted = vn_weights_on(p.wt) && p.n_k > 0;
+  if (weighted) {
+    // the same objective as the fp32 steps (vn_weights.hip): the weights in double from this evaluation's own loss field
+    if (!sa.lossVec) { OCHK(ensure_d(&w.lvec, &w.lvec_cap, p.n_k)); sa.lossVec = w.lvec; }
+    OCHK(ensure_d(&w.omega, &w.omega_cap, p.n_k));
+    if (p.wt.S > 0) OCHK(ensure_d(&w.wstat, &w.wstat_cap, (long)p.wt.S * (p.wt.chunks + 1)));
+  }
   hipLaunchKernelGGL(vn_obj64_seed_kernel, dim3(sblk), dim3(256), 0, s, sa);
   OCHK(hipGetLastError());
+  if (weighted) {
+    VnWeightsWork wk;
+    wk.lsum = w.wstat; wk.oslab = w.wstat ? w.wstat + (long)p.wt.S * p.wt.chunks : nullptr;
+    OCHK(vn_weights_apply_f64(p.wt, wk, sa.lossVec, p.n_k, w.omega, w.lpart, s));    // var partials weighted, lossVec as it is
+    if (grad_dev) OCHK(vn_weights_rows_f64(w.omega, p.n_k, p.q, w.u, w.ud, s));       // the interior seeds in u / ud scaled
+  }
   hipLaunchKernelGGL(vn_obj64_loss_kernel, dim3(1), dim3(64), 0, s, w.lpart, sblk, p.bDof, nB, nF, p.w[0], p.w[1], p.w[2], w.out);
   OCHK(hipGetLastError());
 

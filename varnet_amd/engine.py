@@ -66,6 +66,9 @@ _SIGS = {
     'vn_set_reaction': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_nlflux': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_nldiff': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
+    'vn_set_tf_weights': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    'vn_set_causal': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double]),
+    'vn_causal_weights': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int32]),
     'vn_set_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_bind_grad_buffer': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vn_grad': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -371,8 +374,8 @@ class VNEngine:
         self._keep[('int', batch)] = (Input, gcoef, source, detJv, Nr, dNr)
         self._ck(self.lib.vn_set_interior(self.h, batch, _ptr(Input), _ptr(gcoef), _ptr(source), n_k,
                                           _ptr(detJv), detJ_s, _ptr(Nr), _ptr(dNr)))
-        for key in ('react', 'nlflux', 'nldiff'):    # vn_set_interior cleared the batch's three polynomial terms
-            self._keep.pop((key, batch), None)
+        for key in ('react', 'nlflux', 'nldiff', 'tfw', 'causal'):    # vn_set_interior cleared the batch's three polynomial terms
+            self._keep.pop((key, batch), None)                        # and its per-test-function loss weights
 
     def set_dedup(self, batch, Xu=None, uid=None, rowptr=None, rowidx=None):
         """Register (or, with Xu=None, clear) the de-duplicated formulation of `batch`."""
@@ -482,6 +485,60 @@ class VNEngine:
         advection (None: no advection).  coef: up to three numbers (a shorter list is zero-padded)."""
         self._set_term('nldiff', self.lib.vn_set_nldiff, 'a diffusivity takes at most three coefficients (d0, d1, d2)', 'psi',
                        batch, psi, coef, lambda c, s: c == [1.0, 0.0, 0.0] and s is None)
+
+    def _n_k(self, batch):
+        kept = self._keep.get(('int', batch))
+        return None if kept is None else int(kept[0].shape[0]) // self.integNum
+
+    def set_tf_weights(self, batch, omega=None):
+        """Register (or, with omega=None, clear) per-test-function loss weights of `batch` (vn_set_tf_weights), after set_interior
+        of that batch: var = sum_k omega_k lossVec[k], omega held constant for the gradient, lossVec itself stays unweighted.
+        omega: one value >= 0 per test function; a device tensor is registered as it is (also a view that is not 16-byte
+        aligned), anything else is uploaded.  Replaces a causal registration of the batch."""
+        if omega is None:
+            self._ck(self.lib.vn_set_tf_weights(self.h, int(batch), None))
+            self._keep.pop(('tfw', batch), None)
+            return
+        t = self.torch
+        if isinstance(omega, t.Tensor) and omega.device == self.device and omega.dtype == t.float32 and omega.is_contiguous():
+            omega = omega.reshape(-1)
+        else:
+            omega = self.dev(omega.reshape(-1) if isinstance(omega, t.Tensor) else np.reshape(omega, -1))
+        # the ABI carries a pointer only: the length the kernels rely on is checked here
+        n_k = self._n_k(batch)
+        assert n_k is None or omega.numel() == n_k, 'omega must have one entry per test function (%s != %s)' % (omega.numel(), n_k)
+        self._ck(self.lib.vn_set_tf_weights(self.h, int(batch), _ptr(omega)))
+        self._keep[('tfw', batch)] = omega
+        self._keep.pop(('causal', batch), None)
+
+    def set_causal(self, batch, slab=None, n_slabs=None, eps=0.0):
+        """Register (or, with slab=None, clear) the causal time-slab weights of `batch` (vn_set_causal), after set_interior of
+        that batch: slab one id in [0, n_slabs) per test function (n_slabs None: max id + 1), omega_k = exp(-eps * sum of the
+        mean losses of the earlier slabs), recomputed on the device at every step.  The ids are validated and copied by the
+        call.  Replaces a static registration of the batch."""
+        if slab is None:
+            self._ck(self.lib.vn_set_causal(self.h, int(batch), None, 0, 0.0))
+            self._keep.pop(('causal', batch), None)
+            return
+        t = self.torch
+        slab = (slab if isinstance(slab, t.Tensor) else t.as_tensor(np.ascontiguousarray(slab))).to(
+            device=self.device, dtype=t.int32).reshape(-1).contiguous()
+        n_k = self._n_k(batch)
+        assert n_k is None or slab.numel() == n_k, 'slab must have one entry per test function (%s != %s)' % (slab.numel(), n_k)
+        if n_slabs is None:
+            n_slabs = int(slab.max().item()) + 1 if slab.numel() else 1
+        self._ck(self.lib.vn_set_causal(self.h, int(batch), _ptr(slab), int(n_slabs), float(eps)))
+        self._keep[('causal', batch)] = (int(n_slabs), float(eps))      # (the engine copied the ids)
+        self._keep.pop(('tfw', batch), None)
+
+    def causal_weights(self, batch=0):
+        """omega_s [n_slabs] float64 of the batch's causal registration at the current parameters (vn_causal_weights): one
+        loss-only evaluation.  Changes no engine state."""
+        kept = self._keep.get(('causal', batch))
+        n = kept[0] if kept is not None else 1                          # (no registration: the engine says so)
+        out = (C.c_double * n)()
+        self._ck(self.lib.vn_causal_weights(self.h, int(batch), out, n))
+        return np.array(out, dtype=np.float64)
 
     def set_weights(self, w):
         arr = (C.c_double * 3)(*[float(x) for x in w])

@@ -301,6 +301,8 @@ class TrainResult:
         if getattr(PDE, 'nldiff', None) is not None:
             L.append('Solution-dependent diffusivity: div(diff*(d0 + d1 c + d2 c^2) grad c), coefficients %s\n\n'
                      % str(list(PDE.nldiffCoef)))
+        if getattr(varNet, 'causal', None) is not None:
+            L.append('Causal time-slab loss weights: eps = %s, %d slabs\n\n' % (repr(float(varNet.causal)), varNet.causalSlabNum()))
         L.append('Neural Network architecture:\n')
         L.append('\ttype: ' + str(varNet.modelId) + '\n')
         L.append('\tnumber of inputs: ' + str(varNet.inpDim) + '\n')
@@ -591,8 +593,9 @@ class ManageTrainData:
                 for key in ('Input', 'gcoef', 'source', 'N_rows', 'dNt_rows', 'rate', 'phi', 'psi'):
                     if d.get(key) is not None:
                         d[key] = d[key].index_select(0, rows_all)
-                if d.get('detJ') is not None:
-                    d['detJ'] = d['detJ'].index_select(0, perm_dev)
+                for key in ('detJ', 'slab'):      # one entry per test function
+                    if d.get(key) is not None:
+                        d[key] = d[key].index_select(0, perm_dev)
             for bi in range(self.batchNum):
                 n0, n1 = self.block(bi)
                 pick = lambda t: None if t is None else t[n0 * q:n1 * q]
@@ -607,6 +610,8 @@ class ManageTrainData:
                     eng.set_nlflux(self.engine_batch(mb, bi), pick(d['phi']), d['nlfluxCoef'])
                 if d.get('nldiffCoef') is not None and n1 > n0:     # the diffusivity D(u) of these rows (vn_set_nldiff)
                     eng.set_nldiff(self.engine_batch(mb, bi), pick(d.get('psi')), d['nldiffCoef'])
+                if d.get('slab') is not None and n1 > n0 and self.vn.causal is not None:      # causal weights (vn_set_causal)
+                    eng.set_causal(self.engine_batch(mb, bi), pick_k(d['slab']), self.vn.causalSlabNum(), float(self.vn.causal))
                 perm = getattr(self, 'biPerm', {}).get(bi)
                 if perm is not None and hasattr(eng, 'set_batch_bic'):
                     ix = torch.as_tensor(perm, device=eng.device, dtype=torch.long)
@@ -783,7 +788,8 @@ class ManageTrainData:
 class VarNet:
     def __init__(self, PDE, layerWidth=[20], modelId='MLP', activationFun=None, discNum=20,
                  bDiscNum=[], tDiscNum=[], MORdiscScheme=None, processors=None, controller=None,
-                 integPnum=2, optimizer='adam', learning_rate=0.001, fluxBC=False, lbfgsLoss64=False):
+                 integPnum=2, optimizer='adam', learning_rate=0.001, fluxBC=False, lbfgsLoss64=False,
+                 causal=None, causalSlabs=None):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -815,6 +821,21 @@ class VarNet:
             raise ValueError('unknown optimizer requested!')
         if lbfgsLoss64 and optimizer.lower() != 'lbfgs':
             raise ValueError('lbfgsLoss64=True is an option of optimizer=\'lbfgs\' (the line search on the fp64 loss)')
+        # causal=eps (extension; no reference counterpart): the variational loss of every test function is weighted by
+        # exp(-eps * accumulated mean loss of the earlier time slabs), recomputed at every step and held constant for the
+        # gradient (causal training, Wang, Sankaran, Perdikaris 2022); causalSlabs: number of slabs (default tDiscNum)
+        if causal is not None:
+            self._check_causal_eps(causal)
+            if not timeDependent:
+                raise ValueError('causal=%r needs a time-dependent PDE: a steady problem has no time slabs' % (causal,))
+            if optimizer.lower() == 'lbfgs':
+                raise ValueError('causal=%r with optimizer=\'lbfgs\': the causal weights move with the parameters but are held '
+                                 'constant for the gradient, so the search direction is not the gradient of the reported loss and '
+                                 'an Armijo test on it means nothing' % (causal,))
+            if causalSlabs is not None and not (isinstance(causalSlabs, (int, np.integer)) and 1 <= int(causalSlabs) <= 4096):
+                raise ValueError('causalSlabs must be an integer in [1, 4096]')
+        elif causalSlabs is not None:
+            raise ValueError('causalSlabs is an option of causal=eps')
         if fluxBC and MORvar is not None:
             raise NotImplementedError('fluxBC=True with model-order reduction is not supported: the flux rows carry one label '
                                       'g/a per boundary point, shared by all batches, while a MOR problem needs per-batch labels '
@@ -834,6 +855,8 @@ class VarNet:
         self.processors, self.controller = processors, controller
         self.fluxBC, self.fluxRows = bool(fluxBC), None
         self.lbfgsLoss64 = bool(lbfgsLoss64)
+        self.causal = None if causal is None else float(causal)
+        self.causalSlabs = None if causalSlabs is None else int(causalSlabs)
 
         self.fixData = FIXData(self, integPnum)
         self.fixData.setInputData(self)
@@ -848,6 +871,10 @@ class VarNet:
                 self.dist, self.rank, self.world = dist, dist.get_rank(), dist.get_world_size()
         except ImportError:
             pass
+        if self.causal is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
+            raise NotImplementedError('causal=%r with towers: a rank\'s slab means would cover only its shard of the test '
+                                      'functions, so the ranks together would train another objective than one rank'
+                                      % (causal,))
         if isinstance(processors, (list, tuple)) and len(processors) > 1 and self.world == 1:
             # the reference's single-process multi-GPU call (TFModel.py:120-165): this process becomes the
             # controller of one forked child per GPU (varnet_amd/towers.py); it never touches the GPU itself
@@ -855,7 +882,7 @@ class VarNet:
             kw = dict(layerWidth=layerWidth, modelId=modelId, activationFun=activationFun, discNum=discNum,
                       bDiscNum=bDiscNum, tDiscNum=tDiscNum, MORdiscScheme=MORdiscScheme, processors=list(processors),
                       controller=controller, integPnum=integPnum, optimizer=optimizer, learning_rate=learning_rate,
-                      fluxBC=fluxBC, lbfgsLoss64=lbfgsLoss64)
+                      fluxBC=fluxBC, lbfgsLoss64=lbfgsLoss64, causal=causal, causalSlabs=causalSlabs)
             self._towers = TowerGroup(type(self), (PDE,), kw, list(processors))
             self.world = self._towers.world
             self.engine = self.tfData = None
@@ -931,6 +958,62 @@ class VarNet:
                         isSource=self.lossOpt['isSource'], integWflag=self.lossOpt['integWflag'],
                         learning_rate=self.learning_rate, device=device, activationFun=self.activationFun,
                         optimizer_name=self.optimizer)
+
+    # -- causal time-slab weights (extension) ------------------------------------------------------
+    @staticmethod
+    def _check_causal_eps(eps):
+        if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not np.isfinite(eps) or eps < 0:
+            raise ValueError('causal must be a finite float >= 0 (the eps of exp(-eps * accumulated loss)), got %r' % (eps,))
+
+    def causalSlabNum(self):
+        """S: the number of time slabs of the causal mode (causalSlabs, default tDiscNum)."""
+        return int(self.causalSlabs or self.tDiscNum)
+
+    def causalSlabIds(self, Input):
+        """Slab id of every test function of the rows `Input` [nt*integNum, >= dim+1]: a test function centred at t_k (the mean
+        time of its quadrature points) lies in slab clip(floor((t_k - t0 - h/2) / h), 0, S-1), h = (T - t0) / S.  On the uniform
+        set with S = tDiscNum that is k % tDiscNum; it also serves residual-driven sets and `frac`-thinned grids."""
+        q, S = self.fixData.integNum, self.causalSlabNum()
+        t0, T = [float(x) for x in self.PDE.tInterval]
+        h = (T - t0) / S
+        tk = np.asarray(Input, dtype=np.float64)[:, self.dim].reshape(-1, q).mean(axis=1)
+        # (half a slab below the node, and a relative 1e-9 above the rounding of t_k: nodes sit at slab ends)
+        return np.clip(np.floor((tk - t0 - 0.5 * h) / h + 1e-9), 0, S - 1).astype(np.int32)
+
+    def setCausal(self, eps):
+        """A new eps for the causal mode (None switches it off), re-registered on the training set of the last train() call:
+        eps can be annealed between train() calls."""
+        if eps is not None:
+            self._check_causal_eps(eps)
+            if not self.PDE.timeDependent:
+                raise ValueError('causal=%r needs a time-dependent PDE: a steady problem has no time slabs' % (eps,))
+            if self._is_lbfgs():
+                raise ValueError('causal=%r with optimizer=\'lbfgs\': the search direction would not be the gradient of the '
+                                 'reported loss' % (eps,))
+            if self.world > 1 or self._towers is not None:
+                raise NotImplementedError('causal=%r with towers: a rank\'s slab means would cover only its shard' % (eps,))
+        self.causal = None if eps is None else float(eps)
+        tData = getattr(self, 'tData', None)
+        if tData is not None:
+            if self.causal is not None:
+                for d in tData.mor:                   # a set assembled while the mode was off has no ids yet
+                    if d.get('slab') is None:
+                        d['slab'] = self._slab_tensor(d['Input_host'])
+            tData.activate()
+
+    def _slab_tensor(self, Input):
+        torch = self.engine.torch
+        return torch.as_tensor(self.causalSlabIds(Input), dtype=torch.int32, device=self.engine.device)
+
+    def causalWeights(self, tData=None):
+        """omega_s [S] of block 0 of `tData` (default: the set of the last train() call, else a freshly built full-batch set) at
+        the current parameters: min omega -> 1 as the early slabs converge and release the late ones."""
+        if self.causal is None:
+            raise ValueError('causalWeights: the causal mode is off (VarNet(causal=eps) or setCausal(eps))')
+        if tData is None:
+            tData = getattr(self, 'tData', None) or self._build_tdata()
+        tData.select_mor(0)
+        return self.engine.causal_weights(tData.engine_batch(0, 0))
 
     # -- discretisation ----------------------------------------------------------------------
     def timeDisc(self, tdof=None, rfrac=0, sortflg=True, discTol=None):
@@ -1310,7 +1393,8 @@ class VarNet:
                 phi = (w.reshape(nt, q, dim) * fd.dNx[None]).sum(-1)
             phi = eng.dev(np.asarray(phi, dtype=np.float64).reshape(-1))
             nlfluxCoef = list(self.PDE.nlfluxCoef)
-        return dict(Input=eng.dev(Input), Input_host=Input, gcoef=eng.dev(gcoef), rate=rate, reactCoef=reactCoef,
+        slab = self._slab_tensor(Input) if self.causal is not None else None   # (time column dim: the same ids for every MOR batch)
+        return dict(Input=eng.dev(Input), Input_host=Input, gcoef=eng.dev(gcoef), rate=rate, reactCoef=reactCoef, slab=slab,
                     phi=phi, nlfluxCoef=nlfluxCoef, psi=psi, nldiffCoef=nldiffCoef,
                     source=eng.dev(src.reshape(-1)) if self.lossOpt['isSource'] else None,
                     biInput=eng.dev(biInput), biLabel=eng.dev(biLabel.reshape(-1)),
