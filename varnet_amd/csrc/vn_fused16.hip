@@ -26,9 +26,6 @@
 #include "vn_internal.h"
 #include "vn_fused16_common.h"
 
-#include <atomic>
-
-
 namespace {
 using namespace vn16;
 
@@ -635,42 +632,9 @@ struct VnFusedArgsD {
 };
 
 template <int L, int KS, bool TANH>
-// The machine-level load/store optimizer pairs LDS reads into ds_read2_b32, whose 8-bit offsets force a
-// VALU address add per pair; vector instructions share the datapath with the f32 MFMAs here, LDS issue
-// does not, so pairing is switched off for this kernel (device pass only; -0.8 % kernel time).
-#if defined(__HIP_DEVICE_COMPILE__)
-#define VN_NO_LDS_PAIRING __attribute__((target("no-load-store-opt")))
-#else
-#define VN_NO_LDS_PAIRING
-#endif
 __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kernel(VnFusedArgsD A) {
   using LY = Lay<L, KS>;
-  constexpr int MT = mtiles(KS);
-  // EDGE: the last 16-row tile holds a single k-step (features 4(KS-1) .. 4(KS-1)+3, e.g. 48,49 of a
-  // 50-wide layer).  Producing those few rows with an MFMA tile costs a quarter of the matrix work of
-  // the layer; instead every lane accumulates its share of their dot products on the VALU (which runs
-  // under the partner wave's MFMAs) and the four lane groups are summed with two shuffles.
-  constexpr bool EDGE = (KS % 4) == 1 && KS > 1;
-  constexpr int MTM = EDGE ? MT - 1 : MT;            // row tiles produced by MFMA in hidden layers
-  constexpr int NVE = (KS == 13) ? 2 : 4;            // edge features that can be non-padding
-  constexpr int EPOS = 16 * (MT - 1);                // accumulator row of edge feature 0
-  // KSKIP: nets up to 32 wide are padded to 4*KS features in EVERY layer; a small net's tile is bound by the matrix pipe like
-  // any other (removing MFMAs scales the step: profiles/r3_small_sensitivity.txt), so the k-steps and row tiles that hold
-  // only padding (zero weights: they add +0) are branched over, wave-uniformly, on the layer's real widths -- the [10,20,30]
-  // net of Operator_1DtMOR.py:189 needs 3 and 5 of its 8 forward k-steps, and one of two row tiles in its last input gradient.
-  constexpr bool KSKIP = KS <= 8;
-  // (the bound is made opaque at every use: left to itself the compiler hoists the loop-invariant compares out of the tile
-  // loop as 64-bit lane masks, a pair of scalar registers per guard, and spills them through v_writelane)
-  auto live_k = [](int ks, int& kn) {
-    if (!KSKIP || ks == 0) return true;
-    asm volatile("" : "+s"(kn));
-    return ks < kn;
-  };
-  auto live_m = [](int m, int& mn) {
-    if (!KSKIP || m == 0) return true;
-    asm volatile("" : "+s"(mn));
-    return m < mn;
-  };
+  using GE = Geo<KS>;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const VnNet& net = A.net;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -758,7 +722,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
   lc.g = lane >> 4;
   lc.c = lane & 15;
   lc.offF = lc.g * WS + lc.c;
-  static_assert(16 * MTM <= LY::HP, "backward fragment rows stay inside the weight image");
+  static_assert(16 * GE::MTM <= LY::HP, "backward fragment rows stay inside the weight image");
   static_assert(vfeat(16 + 5) == 16 + vfeat(5), "row tile m holds features fin(c) + 16m");
   lc.offB0 = vfeat(lc.c) * WS + 4 * lc.g;
   lc.twr = 4 * lc.g * TSW + wave * CW + lc.c;
@@ -866,9 +830,9 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
     PA<KS> a[L], zd[L];
 
     // ---------------------------------------------------------------- layer 1 (also recomputed late)
-    auto layer1_raw = [&](const float (&xi)[KS0], const float (&gi)[KS0], f32x4 (&ov)[MT], f32x4 (&ot)[MT]) {
+    auto layer1_raw = [&](const float (&xi)[KS0], const float (&gi)[KS0], f32x4 (&ov)[GE::MT], f32x4 (&ot)[GE::MT]) {
 #pragma unroll
-      for (int m = 0; m < MT; ++m) {
+      for (int m = 0; m < GE::MT; ++m) {
         ov[m] = *reinterpret_cast<const f32x4a*>(&BI[m * 16 + lc.g * 4]);
         ot[m] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
@@ -876,7 +840,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       for (int s = 0; s < KS0; ++s) {
         if (4 * s < sc(d_in_s)) {
 #pragma unroll
-          for (int m = 0; m < MT; ++m) {
+          for (int m = 0; m < GE::MT; ++m) {
             const float wf = W1[4 * s * WS + lc.offF + 16 * m];
             ov[m] = mfma16(wf, xi[s], ov[m]);
             ot[m] = mfma16(wf, gi[s], ot[m]);
@@ -886,7 +850,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
     };
 
     // ---------------------------------------------------------------- forward
-    f32x4 pv[MT], ptn[MT];
+    f32x4 pv[GE::MT], ptn[GE::MT];
     layer1_raw(xin, gin, pv, ptn);
 #pragma unroll
     for (int l = 2; l <= L; ++l) {
@@ -894,9 +858,9 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
         // bf16 pieces: all four row tiles on the matrix pipe (features 48, 49 land in row 48 + 4g as in the edge path), value
         // and tangent share each weight fragment; the activation and the split are scalar f32 forms (no v_pk_* beside bf16 MFMAs)
         const char* rl = win_base(rowb, l);
-        f32x4 nv[MT], nt[MT];
+        f32x4 nv[GE::MT], nt[GE::MT];
 #pragma unroll
-        for (int m = 0; m < MT; ++m) {
+        for (int m = 0; m < GE::MT; ++m) {
           nv[m] = *reinterpret_cast<const f32x4a*>(&BI[(l - 1) * 64 + m * 16 + lc.g * 4]);
           nt[m] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -925,7 +889,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
             Bt[0][e] = h; Bt[1][e] = md; Bt[2][e] = lo;
           }
 #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) {
+          for (int mt = 0; mt < GE::MT; ++mt) {
             u32x4 Af[3];
             split_frag_row(rl, qf, mt, Af);
             const u32x4 (*const Bs[2])[3] = {&Bv, &Bt};
@@ -934,14 +898,14 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
           }
         }
 #pragma unroll
-        for (int m = 0; m < MT; ++m) { pv[m] = nv[m]; ptn[m] = nt[m]; }
+        for (int m = 0; m < GE::MT; ++m) { pv[m] = nv[m]; ptn[m] = nt[m]; }
         continue;
       }
       const float* Wl = WH + (l - 2) * LY::HPWS;
-      int k_in = (net.H[l - 1] + 3) >> 2, m_out = (net.H[l] + 15) >> 4;      // KSKIP: live k-steps / row tiles of this layer (scalar)
-      f32x4 nv[MT], nt[MT];
+      int k_in = (net.H[l - 1] + 3) >> 2, m_out = (net.H[l] + 15) >> 4;      // GE::KSKIP: live k-steps / row tiles of this layer (scalar)
+      f32x4 nv[GE::MT], nt[GE::MT];
 #pragma unroll
-      for (int m = 0; m < MT; ++m) {
+      for (int m = 0; m < GE::MT; ++m) {
         nv[m] = *reinterpret_cast<const f32x4a*>(&BI[(l - 1) * 64 + m * 16 + lc.g * 4]);
         nt[m] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
@@ -954,12 +918,12 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       constexpr int NP = PA<KS>::NP;
       auto zin2 = [&](int j) { return f32x2{pv[(2 * j) >> 2][(2 * j) & 3], pv[(2 * j) >> 2][((2 * j) & 3) + 1]}; };
       auto zdin2 = [&](int j) { return f32x2{ptn[(2 * j) >> 2][(2 * j) & 3], ptn[(2 * j) >> 2][((2 * j) & 3) + 1]}; };
-      float wf[MTM], we[NVE], ev[NVE], et[NVE];
+      float wf[GE::MTM], we[GE::NVE], ev[GE::NVE], et[GE::NVE];
 #pragma unroll
-      for (int m = 0; m < MTM; ++m) wf[m] = Wl[lc.offF + 16 * m];
+      for (int m = 0; m < GE::MTM; ++m) wf[m] = Wl[lc.offF + 16 * m];
 #pragma unroll
-      for (int v = 0; v < NVE; ++v) {
-        we[v] = EDGE ? Wl[lc.offF - lc.c + EPOS + 4 * v] : 0.f;
+      for (int v = 0; v < GE::NVE; ++v) {
+        we[v] = GE::EDGE ? Wl[lc.offF - lc.c + GE::EPOS + 4 * v] : 0.f;
         ev[v] = 0.f;
         et[v] = 0.f;
       }
@@ -973,25 +937,25 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const int j = ks >> 1;
-        float wn[MTM], wen[NVE];
+        float wn[GE::MTM], wen[GE::NVE];
 #pragma unroll
-        for (int m = 0; m < MTM; ++m) wn[m] = (ks + 1 < KS) ? Wl[4 * (ks + 1) * WS + lc.offF + 16 * m] : 0.f;
+        for (int m = 0; m < GE::MTM; ++m) wn[m] = (ks + 1 < KS) ? Wl[4 * (ks + 1) * WS + lc.offF + 16 * m] : 0.f;
 #pragma unroll
-        for (int v = 0; v < NVE; ++v)
-          wen[v] = (EDGE && ks + 1 < KS) ? Wl[4 * (ks + 1) * WS + lc.offF - lc.c + EPOS + 4 * v] : 0.f;
+        for (int v = 0; v < GE::NVE; ++v)
+          wen[v] = (GE::EDGE && ks + 1 < KS) ? Wl[4 * (ks + 1) * WS + lc.offF - lc.c + GE::EPOS + 4 * v] : 0.f;
         const float cs = cs2[ks & 1], cq = cq2[ks & 1];
         __builtin_amdgcn_sched_barrier(0);
-        if (live_k(ks, k_in)) {
+        if (GE::live_k(ks, k_in)) {
 #pragma unroll
-          for (int m = 0; m < MTM; ++m) {
-            if (!live_m(m, m_out)) continue;
+          for (int m = 0; m < GE::MTM; ++m) {
+            if (!GE::live_m(m, m_out)) continue;
             nv[m] = mfma16(wf[m], cs, nv[m]);
             nt[m] = mfma16(wf[m], cq, nt[m]);
           }
         }
-        if (EDGE) {
+        if (GE::EDGE) {
 #pragma unroll
-          for (int v = 0; v < NVE; ++v) { ev[v] += we[v] * cs; et[v] += we[v] * cq; }
+          for (int v = 0; v < GE::NVE; ++v) { ev[v] += we[v] * cs; et[v] += we[v] * cq; }
         }
         if ((ks & 1) == 0) {
           if (j + 3 < NP) e3 = act_exp2<TANH>(zin2(j + 3));                  // stage A of pair j+3
@@ -1009,21 +973,21 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
           cs2 = s1; cq2 = q1; s1 = s2; e2 = e3;
         }
 #pragma unroll
-        for (int m = 0; m < MTM; ++m) wf[m] = wn[m];
+        for (int m = 0; m < GE::MTM; ++m) wf[m] = wn[m];
 #pragma unroll
-        for (int v = 0; v < NVE; ++v) we[v] = wen[v];
+        for (int v = 0; v < GE::NVE; ++v) we[v] = wen[v];
       }
-      if (EDGE) {
+      if (GE::EDGE) {
         // sum the four lane groups' shares; group g keeps edge feature g
-        nv[MT - 1][0] += edge_reduce_scatter<NVE>(ev, lc.g);         // bias was loaded above
-        nt[MT - 1][0] = edge_reduce_scatter<NVE>(et, lc.g);
+        nv[GE::MT - 1][0] += edge_reduce_scatter<GE::NVE>(ev, lc.g);         // bias was loaded above
+        nt[GE::MT - 1][0] = edge_reduce_scatter<GE::NVE>(et, lc.g);
       }
 #pragma unroll
-      for (int m = 0; m < MT; ++m) { pv[m] = nv[m]; ptn[m] = nt[m]; }
+      for (int m = 0; m < GE::MT; ++m) { pv[m] = nv[m]; ptn[m] = nt[m]; }
     }
     // rows (2j, 2j+1) of an accumulator tile are a register pair: pairs of k-steps per packed instruction (the
     // second half of a last, odd pair is a padding row: computed, never used)
-    auto pairOf = [](const f32x4 (&t)[MT], int j) { return f32x2{t[(2 * j) >> 2][(2 * j) & 3], t[(2 * j) >> 2][((2 * j) & 3) + 1]}; };
+    auto pairOf = [](const f32x4 (&t)[GE::MT], int j) { return f32x2{t[(2 * j) >> 2][(2 * j) & 3], t[(2 * j) >> 2][((2 * j) & 3) + 1]}; };
 #pragma unroll
     for (int j = 0; j < PA<KS>::NP; ++j) {
       a[L - 1].p[j] = act_fin2<TANH>(act_exp2<TANH>(pairOf(pv, j)));
@@ -1170,7 +1134,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
         float xr[KS0], gr[KS0];
 #pragma unroll
         for (int s = 0; s < KS0; ++s) { xr[s] = opaque(xin[s]); gr[s] = opaque(gin[s]); }
-        f32x4 rv[MT], rt[MT];
+        f32x4 rv[GE::MT], rt[GE::MT];
         layer1_raw(xr, gr, rv, rt);
 #pragma unroll
         for (int j = 0; j < PA<KS>::NP; ++j) {
@@ -1202,9 +1166,9 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       if constexpr (fullpos(KS)) {
         if (!ones_h[l - 2]) thin_bias<KS>(zb, TA, TB, lc, wave, lane, bsum_h[l - 2]);
       }
-      f32x4 accv[MT], acct[MT];
+      f32x4 accv[GE::MT], acct[GE::MT];
 #pragma unroll
-      for (int m = 0; m < MT; ++m) { accv[m] = f32x4{0.f, 0.f, 0.f, 0.f}; acct[m] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+      for (int m = 0; m < GE::MT; ++m) { accv[m] = f32x4{0.f, 0.f, 0.f, 0.f}; acct[m] = f32x4{0.f, 0.f, 0.f, 0.f}; }
       if constexpr (LY::BF) {
         // bf16 pieces through the transposed reads of the same images: K fragment over the OUT-features 4(8qf+j)+g of layer l,
         // row tile over the IN-positions 16 mt + c (all four on the matrix pipe)
@@ -1228,7 +1192,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
             Bzd[0][e] = h; Bzd[1][e] = md; Bzd[2][e] = lo;
           }
 #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) {
+          for (int mt = 0; mt < GE::MT; ++mt) {
             u32x4 At[3];
             split_frag_tr(tl, qf, mt, At);
             const u32x4 (*const Bs[2])[3] = {&Bz, &Bzd};
@@ -1239,45 +1203,45 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       } else {
       const float* Wl = WH + (l - 2) * LY::HPWS;
       int k_out = (net.H[l] + 3) >> 2, m_in = (net.H[l - 1] + 15) >> 4;
-      float wf[MTM], we[NVE], ev[NVE], et[NVE];
+      float wf[GE::MTM], we[GE::NVE], ev[GE::NVE], et[GE::NVE];
 #pragma unroll
-      for (int m = 0; m < MTM; ++m) wf[m] = Wl[lc.offB0 + 16 * m * WS + vpos(0, 0)];
+      for (int m = 0; m < GE::MTM; ++m) wf[m] = Wl[lc.offB0 + 16 * m * WS + vpos(0, 0)];
 #pragma unroll
-      for (int v = 0; v < NVE; ++v) {
-        we[v] = EDGE ? Wl[(4 * (KS - 1) + v) * WS + 4 * lc.g + vpos(0, 0)] : 0.f;
+      for (int v = 0; v < GE::NVE; ++v) {
+        we[v] = GE::EDGE ? Wl[(4 * (KS - 1) + v) * WS + 4 * lc.g + vpos(0, 0)] : 0.f;
         ev[v] = 0.f;
         et[v] = 0.f;
       }
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        float wn[MTM], wen[NVE];
+        float wn[GE::MTM], wen[GE::NVE];
 #pragma unroll
-        for (int m = 0; m < MTM; ++m) wn[m] = (ks + 1 < KS) ? Wl[lc.offB0 + 16 * m * WS + vpos(ks + 1, 0)] : 0.f;
+        for (int m = 0; m < GE::MTM; ++m) wn[m] = (ks + 1 < KS) ? Wl[lc.offB0 + 16 * m * WS + vpos(ks + 1, 0)] : 0.f;
 #pragma unroll
-        for (int v = 0; v < NVE; ++v)
-          wen[v] = (EDGE && ks + 1 < KS) ? Wl[(4 * (KS - 1) + v) * WS + 4 * lc.g + vpos(ks + 1, 0)] : 0.f;
+        for (int v = 0; v < GE::NVE; ++v)
+          wen[v] = (GE::EDGE && ks + 1 < KS) ? Wl[(4 * (KS - 1) + v) * WS + 4 * lc.g + vpos(ks + 1, 0)] : 0.f;
         __builtin_amdgcn_sched_barrier(0);
-        if (live_k(ks, k_out)) {
+        if (GE::live_k(ks, k_out)) {
 #pragma unroll
-          for (int m = 0; m < MTM; ++m) {
-            if (!live_m(m, m_in)) continue;
+          for (int m = 0; m < GE::MTM; ++m) {
+            if (!GE::live_m(m, m_in)) continue;
             accv[m] = mfma16(wf[m], zb[ks], accv[m]);
             acct[m] = mfma16(wf[m], zdb[ks], acct[m]);
           }
         }
-        if (EDGE) {
+        if (GE::EDGE) {
 #pragma unroll
-          for (int v = 0; v < NVE; ++v) { ev[v] += we[v] * zb[ks]; et[v] += we[v] * zdb[ks]; }
+          for (int v = 0; v < GE::NVE; ++v) { ev[v] += we[v] * zb[ks]; et[v] += we[v] * zdb[ks]; }
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int m = 0; m < MTM; ++m) wf[m] = wn[m];
+        for (int m = 0; m < GE::MTM; ++m) wf[m] = wn[m];
 #pragma unroll
-        for (int v = 0; v < NVE; ++v) we[v] = wen[v];
+        for (int v = 0; v < GE::NVE; ++v) we[v] = wen[v];
       }
-      if (EDGE) {
-        accv[MT - 1][0] = edge_reduce_scatter<NVE>(ev, lc.g);
-        acct[MT - 1][0] = edge_reduce_scatter<NVE>(et, lc.g);
+      if (GE::EDGE) {
+        accv[GE::MT - 1][0] = edge_reduce_scatter<GE::NVE>(ev, lc.g);
+        acct[GE::MT - 1][0] = edge_reduce_scatter<GE::NVE>(et, lc.g);
       }
       }
       // zbar of layer l-1, two k-steps per packed instruction (accumulator rows ks, ks+1 are a register pair)
@@ -1434,36 +1398,6 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
   }
 }
 
-template <int L, int KS, bool TANH>
-hipError_t launch_one(const VnFusedArgsD& a, int grid, hipStream_t s) {
-  using LY = Lay<L, KS>;
-  const size_t bytes = (size_t)LY::TOTAL * sizeof(float);
-  // the attribute is per device and sticky: set it once per device (bit mask; engines on different devices may
-  // be driven from different threads)
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)vn_fused16_kernel<L, KS, TANH>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return e;
-    attr_done.fetch_or(bit, std::memory_order_release);
-  }
-  hipLaunchKernelGGL((vn_fused16_kernel<L, KS, TANH>), dim3(grid), dim3(NTHREADS), bytes, s, a);
-  return hipGetLastError();
-}
-
-template <int L, int KS>
-size_t lds_one() {
-  return (size_t)Lay<L, KS>::TOTAL * sizeof(float);
-}
-
-template <int L, int KS>
-size_t stash_one() {
-  return (size_t)Lay<L, KS>::NSTG * Lay<L, KS>::ST_LAYER * sizeof(float);
-}
-
 int pick_ks(int hmax) {
   if (hmax <= 20) return 5;
   if (hmax <= 32) return 8;
@@ -1475,28 +1409,17 @@ int pick_ks(int hmax) {
 
 }  // namespace
 
-#define VN_FUSED16_CASES(X) \
-  X(1, 5) X(2, 5) X(3, 5) X(4, 5) X(5, 5) X(6, 5) X(7, 5) X(8, 5)  \
-  X(1, 8) X(2, 8) X(3, 8) X(4, 8) X(5, 8) X(6, 8) X(7, 8) X(8, 8)  \
-  X(1, 13) X(2, 13) X(3, 13) X(4, 13) X(5, 13) X(6, 13) X(7, 13) X(8, 13)  \
-  X(1, 16) X(2, 16) X(3, 16) X(4, 16) X(5, 16) X(6, 16)
-
 int vn_fused16_ks(const VnNet& net) { return pick_ks(net.hmax); }
 
 size_t vn_fused16_lds_bytes(const VnNet& net) {
-  const int ks = pick_ks(net.hmax);
-#define X(LL, KK) if (net.L == LL && ks == KK) return lds_one<LL, KK>();
-  VN_FUSED16_CASES(X)
-#undef X
-  return 0;
+  return visit_all(net, (size_t)0, [](auto I) { return (size_t)Lay<decltype(I)::L, decltype(I)::KS>::TOTAL * sizeof(float); });
 }
 
 size_t vn_fused16_stash_bytes(const VnNet& net) {
-  const int ks = pick_ks(net.hmax);
-#define X(LL, KK) if (net.L == LL && ks == KK) return stash_one<LL, KK>();
-  VN_FUSED16_CASES(X)
-#undef X
-  return 0;
+  return visit_all(net, (size_t)0, [](auto I) {
+    using LY = Lay<decltype(I)::L, decltype(I)::KS>;
+    return (size_t)LY::NSTG * LY::ST_LAYER * sizeof(float);
+  });
 }
 
 bool vn_fused16_net_supported(const VnNet& net) {
@@ -1519,12 +1442,14 @@ hipError_t vn_fused16_launch(const VnFusedArgs& h, int grid, hipStream_t s) {
   a.w2 = h.w2; a.partial = h.partial; a.losspart = h.losspart; a.stash = h.stash; a.stamps = h.stamps;
   a.mode = h.mode; a.dir = h.mode ? h.dir : -1; a.ostride = h.ostride; a.out_u = h.out_u; a.out_ud = h.out_ud;
   a.seed_u = h.seed_u; a.seed_ud = h.seed_ud;
-  const int ks = pick_ks(h.net.hmax);
   if (!h.stash && vn_fused16_stash_bytes(h.net) > 0) return hipErrorInvalidValue;
-#define X(LL, KK)                                                                              \
-  if (h.net.L == LL && ks == KK)                                                                \
-    return h.net.act == VN_ACT_TANH ? launch_one<LL, KK, true>(a, grid, s) : launch_one<LL, KK, false>(a, grid, s);
-  VN_FUSED16_CASES(X)
-#undef X
-  return hipErrorInvalidValue;
+  return visit_all(h.net, hipErrorInvalidValue, [&](auto I) {
+    using T = decltype(I);
+    constexpr auto kernel = vn_fused16_kernel<T::L, T::KS, T::TANH>;
+    constexpr size_t bytes = (size_t)Lay<T::L, T::KS>::TOTAL * sizeof(float);
+    const hipError_t e = allow_lds_once<kernel>(bytes);            // the grid is the caller's
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTHREADS), bytes, s, a);
+    return hipGetLastError();
+  });
 }

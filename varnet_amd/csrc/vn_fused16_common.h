@@ -2,8 +2,12 @@
 // vn_pgrad16.hip: value + input gradient at points; vn_split16.hip: point kernels on the bf16 pipe): the feature <->
 // (k-step, lane group, accumulator row) layout, activation arithmetic on register pairs, cross-lane sums, and the
 // bf16-piece machinery of the hidden-layer products (exact three-way split, 1 KB-block weight images, fragment reads).
+// Also what the five translation units of the family share beyond device helpers: the table of instantiations, the tile
+// geometry of an instantiation (Geo), and -- host side, at the end -- the one dispatch walk and the one launcher.
 #pragma once
 #include "vn_internal.h"
+
+#include <atomic>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef f32x4 f32x4a __attribute__((may_alias));
@@ -35,6 +39,72 @@ __host__ __device__ constexpr bool layout_ties_ksteps_and_tiles_to_features() {
 }
 static_assert(layout_ties_ksteps_and_tiles_to_features(), "KSKIP: k-step = feature >> 2, row tile = feature >> 4");
 __host__ __device__ constexpr int mtiles(int KS) { return (KS + 3) / 4; }
+
+// ---- the instantiations of the family: (hidden layers L, k-steps per hidden layer KS) ---------------------------------------
+// KS = 5 | 8 | 13 | 16 serves hidden widths up to 20 | 32 | 50 | 64 (vn_fused16_ks).  Every pair is written ONCE, under the list
+// it belongs to, so the two lists are disjoint by construction and adding an instantiation is a one-line change here:
+//   S  the bf16-piece networks -- hidden widths 33..64 (KS = 13, 16) with 2..7 hidden layers, 6 beyond 50 wide (L = 1 has no
+//      hidden product; 8 x 24 KB of images do not fit): their point kernels are those of vn_split16.hip; the f32-MFMA forms
+//      (vn_pgrad16 / vn_taylor16) are what the tests compare them with and are instantiated in the tests' cross-check library
+//      only (-DVN_XCHECK_F32_POINT, Makefile target xcheck);
+//   F  the rest: vn_pgrad16 / vn_taylor16 serve them in the product library.
+// The fused step kernel (vn_fused16.hip) is instantiated for the union, and vn_fused16_net_supported -- hence the engine's
+// route -- accepts exactly the union; vn_taylor16d.hip walks the union and keeps the pairs whose double images fit the LDS.
+// The two lists share one table, KS-major, because the compiler emits kernels into a code object in the order of the walk.
+#define VN16_TABLE(F, S) \
+  F(1, 5)  F(2, 5)  F(3, 5)  F(4, 5)  F(5, 5)  F(6, 5)  F(7, 5)  F(8, 5)   \
+  F(1, 8)  F(2, 8)  F(3, 8)  F(4, 8)  F(5, 8)  F(6, 8)  F(7, 8)  F(8, 8)   \
+  F(1, 13) S(2, 13) S(3, 13) S(4, 13) S(5, 13) S(6, 13) S(7, 13) F(8, 13)  \
+  F(1, 16) S(2, 16) S(3, 16) S(4, 16) S(5, 16) S(6, 16)
+#define VN16_NOT_LISTED(L, KS)
+#define VN16_SPLIT_CASES(X) VN16_TABLE(VN16_NOT_LISTED, X)
+#define VN16_F32_ONLY_CASES(X) VN16_TABLE(X, VN16_NOT_LISTED)
+#define VN16_CASES(X) VN16_TABLE(X, X)
+#ifdef VN_XCHECK_F32_POINT
+#define VN16_F32_POINT_CASES(X) VN16_F32_ONLY_CASES(X) VN16_SPLIT_CASES(X)
+#else
+#define VN16_F32_POINT_CASES(X) VN16_F32_ONLY_CASES(X)
+#endif
+
+// The machine-level load/store optimizer pairs LDS reads into ds_read2_b32, whose 8-bit offsets force a
+// VALU address add per pair; vector instructions share the datapath with the f32 MFMAs here, LDS issue
+// does not, so pairing is switched off for the f32-MFMA kernels (device pass only; -0.8 % kernel time).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VN_NO_LDS_PAIRING __attribute__((target("no-load-store-opt")))
+#else
+#define VN_NO_LDS_PAIRING
+#endif
+
+// Tile geometry of the f32-MFMA kernels (vn_fused16, vn_pgrad16, vn_taylor16) at KS k-steps per hidden layer.
+template <int KS>
+struct Geo {
+  static constexpr int MT = mtiles(KS);
+  // EDGE: the last 16-row tile holds a single k-step (features 4(KS-1) .. 4(KS-1)+3, e.g. 48,49 of a
+  // 50-wide layer).  Producing those few rows with an MFMA tile costs a quarter of the matrix work of
+  // the layer; instead every lane accumulates its share of their dot products on the VALU (which runs
+  // under the partner wave's MFMAs) and the four lane groups are summed with two shuffles.
+  static constexpr bool EDGE = (KS % 4) == 1 && KS > 1;
+  static constexpr int MTM = EDGE ? MT - 1 : MT;            // row tiles produced by MFMA in hidden layers
+  static constexpr int NVE = (KS == 13) ? 2 : 4;            // edge features that can be non-padding
+  static constexpr int EPOS = 16 * (MT - 1);                // accumulator row of edge feature 0
+  // KSKIP: nets up to 32 wide are padded to 4*KS features in EVERY layer; a small net's tile is bound by the matrix pipe like
+  // any other (removing MFMAs scales the step: profiles/r3_small_sensitivity.txt), so the k-steps and row tiles that hold
+  // only padding (zero weights: they add +0) are branched over, wave-uniformly, on the layer's real widths -- the [10,20,30]
+  // net of Operator_1DtMOR.py:189 needs 3 and 5 of its 8 forward k-steps, and one of two row tiles in its last input gradient.
+  static constexpr bool KSKIP = KS <= 8;
+  // (the bound is made opaque at every use: left to itself the compiler hoists the loop-invariant compares out of the tile
+  // loop as 64-bit lane masks, a pair of scalar registers per guard, and spills them through v_writelane)
+  static __device__ __forceinline__ bool live_k(int ks, int& kn) {
+    if (!KSKIP || ks == 0) return true;
+    asm volatile("" : "+s"(kn));
+    return ks < kn;
+  }
+  static __device__ __forceinline__ bool live_m(int m, int& mn) {
+    if (!KSKIP || m == 0) return true;
+    asm volatile("" : "+s"(mn));
+    return m < mn;
+  }
+};
 
 __device__ __forceinline__ float opaque(float x) {
   asm("" : "+v"(x));
@@ -256,6 +326,75 @@ __device__ __forceinline__ void split_frag_tr(const char* tl, int q, int mt, u32
     const unsigned long long l64 = __builtin_bit_cast(unsigned long long, lo4), h64 = __builtin_bit_cast(unsigned long long, hi4);
     At[p] = u32x4{(u32)l64, (u32)(l64 >> 32), (u32)h64, (u32)(h64 >> 32)};
   }
+}
+
+// ---- host side: one dispatch walk, one launcher ----------------------------------------------------------------------------
+template <int L_, int KS_, bool TANH_>
+struct Inst {
+  static constexpr int L = L_, KS = KS_;
+  static constexpr bool TANH = TANH_;
+};
+
+// visit_*(net, none, f): f(Inst<L, KS, TANH>{}) for the pair of the list that serves `net`, `none` where the list has no such
+// pair.  f is a generic lambda; what it does not instantiate (if constexpr) does not exist.
+#define VN16_VISIT(LL, KK) \
+  if (net.L == LL && ks == KK) return net.act == VN_ACT_TANH ? f(Inst<LL, KK, true>{}) : f(Inst<LL, KK, false>{});
+#define VN16_DEFINE_VISIT(NAME, CASES)            \
+  template <class R, class F>                     \
+  R NAME(const VnNet& net, R none, F f) {         \
+    const int ks = vn_fused16_ks(net);            \
+    CASES(VN16_VISIT)                             \
+    return none;                                  \
+  }
+VN16_DEFINE_VISIT(visit_all, VN16_CASES)
+VN16_DEFINE_VISIT(visit_f32_point, VN16_F32_POINT_CASES)
+VN16_DEFINE_VISIT(visit_split, VN16_SPLIT_CASES)
+#undef VN16_DEFINE_VISIT
+#undef VN16_VISIT
+
+// The attribute that allows KERNEL (one instantiation: the state lives here) lds_bytes of dynamic LDS is per device and sticky:
+// it is set once per device (bit mask; engines on different devices may be driven from different threads).  OCC: the workgroups
+// of this instantiation a CU holds (registers, LDS) are asked for at the same time and cached; *occ receives them (else 1).
+template <auto KERNEL, bool OCC = false>
+hipError_t allow_lds_once(size_t lds_bytes, int* occ = nullptr) {
+  static std::atomic<unsigned long long> attr_done{0};
+  static std::atomic<int> occ_cached{1};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (!(attr_done.load(std::memory_order_acquire) & bit)) {
+    hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    if (OCC) {
+      int nb = 1;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)KERNEL, NTHREADS, lds_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        nb = 1;
+      }
+      occ_cached.store(nb < 1 ? 1 : nb, std::memory_order_relaxed);
+    }
+    attr_done.fetch_or(bit, std::memory_order_release);
+  }
+  if (occ) *occ = occ_cached.load(std::memory_order_relaxed);
+  return hipSuccess;
+}
+
+// Launch of a point kernel: every wave walks 16-point chunks with a grid stride, so the grid is the workgroups the n points fill,
+// capped at per_cu workgroups per CU.  per_cu <= 0: two where the cached occupancy allows it (OCC), else one.  Waves are
+// independent in these kernels (no workgroup barrier in the chunk loop), so a second resident workgroup per CU -- where the
+// instantiation's registers (<= 128) and weight images (<= 80 KB) allow it -- hides more of the LDS / transcendental latencies
+// under the partner's MFMAs: 395 -> 382 us on the bench network with vn_pgrad16 (profiles/r5_dedup_ab.txt).
+template <auto KERNEL, bool OCC, class ARGS>
+hipError_t launch_chunks(const ARGS& a, long n, size_t lds_bytes, int ncu, int per_cu, hipStream_t s) {
+  int occ = 1;
+  const hipError_t e = allow_lds_once<KERNEL, OCC>(lds_bytes, &occ);
+  if (e != hipSuccess) return e;
+  if (per_cu <= 0) per_cu = occ >= 2 ? 2 : 1;
+  const long wgs = ((n + CW - 1) / CW + NW - 1) / NW;
+  const long cap = (long)ncu * per_cu;
+  const int grid = (int)(wgs < cap ? wgs : cap);
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(NTHREADS), lds_bytes, s, a);
+  return hipGetLastError();
 }
 
 }  // namespace vn16

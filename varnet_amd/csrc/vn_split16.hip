@@ -20,8 +20,6 @@
 #include "vn_points16.h"
 #include "vn_split16.h"
 
-#include <atomic>
-
 namespace {
 using namespace vn16;
 
@@ -240,12 +238,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void vn_split16_kernel(VnSplitArgsD A)
       if (NS == 1) {
         A.u[row] = uval;
       } else {
-        float out = A.td ? -ut : 0.f;
-        out += A.diff[row] * lap;
-        out -= adv;
-        if (A.src) out += A.src[row];
-        if (A.u) A.u[row] = uval;
-        A.res[row] = out;
+        store_residual(A, row, uval, ut, lap, adv);
       }
     }
   }
@@ -416,58 +409,19 @@ __global__ __launch_bounds__(NTHREADS, 1) void vn_split16_pgrad_kernel(VnSplitPg
   }
 }
 
-template <int L, int KS, bool TANH, int NS>
-hipError_t launch_one(const VnSplitArgsD& a, int ncu, hipStream_t s) {
-  constexpr size_t bytes = (size_t)SLay<L>::TOTAL;
-  static_assert(bytes <= 160 * 1024, "images of L - 1 hidden layers must fit the LDS");
-  static std::atomic<unsigned long long> attr_done{0};   // per device and sticky: set once per device (vn_pgrad16.hip)
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)vn_split16_kernel<L, KS, TANH, NS>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return e;
-    attr_done.fetch_or(bit, std::memory_order_release);
-  }
-  const long wgs = ((a.n + CW - 1) / CW + NW - 1) / NW;
-  const int grid = (int)(wgs < ncu ? wgs : ncu);
-  hipLaunchKernelGGL((vn_split16_kernel<L, KS, TANH, NS>), dim3(grid), dim3(NTHREADS), bytes, s, a);
-  return hipGetLastError();
-}
-
-template <int L, int KS, bool TANH>
-hipError_t launch_pg(const VnSplitPgArgsD& a, int ncu, hipStream_t s) {
-  constexpr size_t bytes = (size_t)SLay<L>::TOTAL;
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)vn_split16_pgrad_kernel<L, KS, TANH>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return e;
-    attr_done.fetch_or(bit, std::memory_order_release);
-  }
-  const long wgs = ((a.n + CW - 1) / CW + NW - 1) / NW;
-  const int grid = (int)(wgs < ncu ? wgs : ncu);
-  hipLaunchKernelGGL((vn_split16_pgrad_kernel<L, KS, TANH>), dim3(grid), dim3(NTHREADS), bytes, s, a);
-  return hipGetLastError();
+template <int L>
+constexpr size_t lds_bytes() {
+  static_assert(SLay<L>::TOTAL <= 160 * 1024, "images of L - 1 hidden layers must fit the LDS");
+  return (size_t)SLay<L>::TOTAL;
 }
 
 }  // namespace
 
-// hidden widths 33..64 of the 8-wave family, 2..7 hidden layers (L = 1 has no hidden product; 8 x 24 KB of images do not fit)
-#define VN_SPLIT16_CASES(X) VN_POINT16_SPLIT_CASES(X)
-
+// The entry points: the networks of VN16_SPLIT_CASES (vn_fused16_common.h), one workgroup per CU (two waves per SIMD, 256 registers per lane)
 bool vn_split16_supported(const VnNet& net) {
   if (net.d_in > 4 * KS0) return false;
   if (net.act != VN_ACT_SIGMOID && net.act != VN_ACT_TANH) return false;
-  const int ks = vn_fused16_ks(net);
-#define X(LL, KK) if (net.L == LL && ks == KK) return true;
-  VN_SPLIT16_CASES(X)
-#undef X
-  return false;
+  return visit_split(net, false, [](auto) { return true; });
 }
 
 hipError_t vn_split16_forward(const VnNet& net, const float* theta, const float* X, long n, float* u, int ncu, hipStream_t s) {
@@ -475,13 +429,10 @@ hipError_t vn_split16_forward(const VnNet& net, const float* theta, const float*
   if (!vn_split16_supported(net) || !u) return hipErrorInvalidValue;
   VnSplitArgsD a{};
   a.net = net; a.theta = theta; a.X = X; a.n = n; a.u = u;
-  const int ks = vn_fused16_ks(net);
-#define X(LL, KK)                                                                              \
-  if (net.L == LL && ks == KK)                                                                  \
-    return net.act == VN_ACT_TANH ? launch_one<LL, KK, true, 1>(a, ncu, s) : launch_one<LL, KK, false, 1>(a, ncu, s);
-  VN_SPLIT16_CASES(X)
-#undef X
-  return hipErrorInvalidValue;
+  return visit_split(net, hipErrorInvalidValue, [&](auto I) {
+    using T = decltype(I);
+    return launch_chunks<vn_split16_kernel<T::L, T::KS, T::TANH, 1>, false>(a, n, lds_bytes<T::L>(), ncu, 1, s);
+  });
 }
 
 hipError_t vn_split16_residual(const VnNet& net, const float* theta, const float* X, const float* diff, const float* vel,
@@ -490,13 +441,10 @@ hipError_t vn_split16_residual(const VnNet& net, const float* theta, const float
   if (!vn_split16_supported(net) || net.dim > 3 || net.dim + (td ? 1 : 0) > net.d_in) return hipErrorInvalidValue;
   VnSplitArgsD a{};
   a.net = net; a.theta = theta; a.X = X; a.diff = diff; a.vel = vel; a.src = src; a.ddx = ddx; a.td = td; a.n = n; a.u = u; a.res = res;
-  const int ks = vn_fused16_ks(net);
-#define X(LL, KK)                                                                              \
-  if (net.L == LL && ks == KK)                                                                  \
-    return net.act == VN_ACT_TANH ? launch_one<LL, KK, true, 3>(a, ncu, s) : launch_one<LL, KK, false, 3>(a, ncu, s);
-  VN_SPLIT16_CASES(X)
-#undef X
-  return hipErrorInvalidValue;
+  return visit_split(net, hipErrorInvalidValue, [&](auto I) {
+    using T = decltype(I);
+    return launch_chunks<vn_split16_kernel<T::L, T::KS, T::TANH, 3>, false>(a, n, lds_bytes<T::L>(), ncu, 1, s);
+  });
 }
 
 hipError_t vn_split16_pgrad(const VnNet& net, const float* theta, const float* X, long n, float* out_u, float* out_g, float* out_pack,
@@ -505,11 +453,8 @@ hipError_t vn_split16_pgrad(const VnNet& net, const float* theta, const float* X
   if (!vn_split16_supported(net) || net.dim > 3) return hipErrorInvalidValue;
   VnSplitPgArgsD a{};
   a.net = net; a.theta = theta; a.X = X; a.n = n; a.out_u = out_u; a.out_g = out_g; a.out_pack = out_pack;
-  const int ks = vn_fused16_ks(net);
-#define X(LL, KK)                                                                              \
-  if (net.L == LL && ks == KK)                                                                  \
-    return net.act == VN_ACT_TANH ? launch_pg<LL, KK, true>(a, ncu, s) : launch_pg<LL, KK, false>(a, ncu, s);
-  VN_SPLIT16_CASES(X)
-#undef X
-  return hipErrorInvalidValue;
+  return visit_split(net, hipErrorInvalidValue, [&](auto I) {
+    using T = decltype(I);
+    return launch_chunks<vn_split16_pgrad_kernel<T::L, T::KS, T::TANH>, false>(a, n, lds_bytes<T::L>(), ncu, 1, s);
+  });
 }

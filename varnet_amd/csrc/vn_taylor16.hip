@@ -15,8 +15,6 @@
 #include "vn_points16.h"
 #include "vn_taylor16.h"
 
-#include <atomic>
-
 namespace {
 using namespace vn16;
 
@@ -35,29 +33,9 @@ struct VnTaylorArgsD {
 };
 
 template <int L, int KS, bool TANH>
-#if defined(__HIP_DEVICE_COMPILE__)
-#define VN_NO_LDS_PAIRING __attribute__((target("no-load-store-opt")))      // see vn_fused16.hip
-#else
-#define VN_NO_LDS_PAIRING
-#endif
 __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_taylor16_kernel(VnTaylorArgsD A) {
   using LY = PLay<L, KS>;
-  constexpr int MT = mtiles(KS);
-  constexpr bool EDGE = (KS % 4) == 1 && KS > 1;     // the last row tile holds one k-step: its rows run on the VALU (vn_fused16.hip)
-  constexpr int MTM = EDGE ? MT - 1 : MT;
-  constexpr int NVE = (KS == 13) ? 2 : 4;
-  constexpr int EPOS = 16 * (MT - 1);
-  constexpr bool KSKIP = KS <= 8;                    // k-steps / row tiles that hold only padding are branched over
-  auto live_k = [](int ks, int& kn) {
-    if (!KSKIP || ks == 0) return true;
-    asm volatile("" : "+s"(kn));
-    return ks < kn;
-  };
-  auto live_m = [](int m, int& mn) {
-    if (!KSKIP || m == 0) return true;
-    asm volatile("" : "+s"(mn));
-    return m < mn;
-  };
+  using GE = Geo<KS>;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const VnNet& net = A.net;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -92,9 +70,9 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_taylor16_ker
 #pragma unroll
       for (int s = 0; s < KS0; ++s) gin[s] = (4 * s + g == d) ? 1.f : 0.f;
       // ---------------------------------------------------------------- layer 1: z.. = 0 (an affine map has no curvature)
-      f32x4 pv[MT], pt[MT], p2[MT];
+      f32x4 pv[GE::MT], pt[GE::MT], p2[GE::MT];
 #pragma unroll
-      for (int m = 0; m < MT; ++m) {
+      for (int m = 0; m < GE::MT; ++m) {
         pv[m] = *reinterpret_cast<const f32x4a*>(&BI[m * 16 + g * 4]);
         pt[m] = f32x4{0.f, 0.f, 0.f, 0.f};
         p2[m] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -103,7 +81,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_taylor16_ker
       for (int s = 0; s < KS0; ++s) {
         if (4 * s < net.d_in) {
 #pragma unroll
-          for (int m = 0; m < MT; ++m) {
+          for (int m = 0; m < GE::MT; ++m) {
             const float wf = W1[4 * s * WS + offF + 16 * m];
             pv[m] = mfma16(wf, xin[s], pv[m]);
             pt[m] = mfma16(wf, gin[s], pt[m]);
@@ -115,9 +93,9 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_taylor16_ker
       for (int l = 2; l <= L; ++l) {
         const float* Wl = WH + (l - 2) * LY::HPWS;
         int k_in = (net.H[l - 1] + 3) >> 2, m_out = (net.H[l] + 15) >> 4;
-        f32x4 nv[MT], nt[MT], n2[MT];
+        f32x4 nv[GE::MT], nt[GE::MT], n2[GE::MT];
 #pragma unroll
-        for (int m = 0; m < MT; ++m) {
+        for (int m = 0; m < GE::MT; ++m) {
           nv[m] = *reinterpret_cast<const f32x4a*>(&BI[(l - 1) * 64 + m * 16 + g * 4]);
           nt[m] = f32x4{0.f, 0.f, 0.f, 0.f};
           n2[m] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -126,16 +104,16 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_taylor16_ker
         // (packed scale + 2 v_exp) of pair j+3 after the first k-step of pair j, stage B (packed 1+e + 2 v_rcp) of pair j+2 and
         // stage C (the two derivative streams of pair j+1) after the second
         constexpr int NP = PA<KS>::NP;
-        auto pr = [](const f32x4 (&t)[MT], int j) { return f32x2{t[(2 * j) >> 2][(2 * j) & 3], t[(2 * j) >> 2][((2 * j) & 3) + 1]}; };
+        auto pr = [](const f32x4 (&t)[GE::MT], int j) { return f32x2{t[(2 * j) >> 2][(2 * j) & 3], t[(2 * j) >> 2][((2 * j) & 3) + 1]}; };
         auto second_of = [&](f32x2 s, f32x2 zd, f32x2 z2) {          // a..' = sigma'(z) ((sigma''/sigma')(z) z.^2 + z..)
           return act_d1_2<TANH>(s) * (act_d2r_2<TANH>(s) * zd * zd + z2);
         };
-        float wf[MTM > 0 ? MTM : 1], we[NVE], ev[NVE], et[NVE], e2v[NVE];
+        float wf[GE::MTM > 0 ? GE::MTM : 1], we[GE::NVE], ev[GE::NVE], et[GE::NVE], e2v[GE::NVE];
 #pragma unroll
-        for (int m = 0; m < MTM; ++m) wf[m] = Wl[offF + 16 * m];
+        for (int m = 0; m < GE::MTM; ++m) wf[m] = Wl[offF + 16 * m];
 #pragma unroll
-        for (int v = 0; v < NVE; ++v) {
-          we[v] = EDGE ? Wl[offF - c + EPOS + 4 * v] : 0.f;
+        for (int v = 0; v < GE::NVE; ++v) {
+          we[v] = GE::EDGE ? Wl[offF - c + GE::EPOS + 4 * v] : 0.f;
           ev[v] = 0.f; et[v] = 0.f; e2v[v] = 0.f;
         }
         f32x2 cs2 = act_fin2<TANH>(act_exp2<TANH>(pr(pv, 0)));
@@ -147,25 +125,25 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_taylor16_ker
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           const int j = ks >> 1;
-          float wn[MTM > 0 ? MTM : 1], wen[NVE];
+          float wn[GE::MTM > 0 ? GE::MTM : 1], wen[GE::NVE];
 #pragma unroll
-          for (int m = 0; m < MTM; ++m) wn[m] = (ks + 1 < KS) ? Wl[4 * (ks + 1) * WS + offF + 16 * m] : 0.f;
+          for (int m = 0; m < GE::MTM; ++m) wn[m] = (ks + 1 < KS) ? Wl[4 * (ks + 1) * WS + offF + 16 * m] : 0.f;
 #pragma unroll
-          for (int v = 0; v < NVE; ++v) wen[v] = (EDGE && ks + 1 < KS) ? Wl[4 * (ks + 1) * WS + offF - c + EPOS + 4 * v] : 0.f;
+          for (int v = 0; v < GE::NVE; ++v) wen[v] = (GE::EDGE && ks + 1 < KS) ? Wl[4 * (ks + 1) * WS + offF - c + GE::EPOS + 4 * v] : 0.f;
           const float cs = cs2[ks & 1], cq = cq2[ks & 1], cw = cw2[ks & 1];
           __builtin_amdgcn_sched_barrier(0);
-          if (live_k(ks, k_in)) {
+          if (GE::live_k(ks, k_in)) {
 #pragma unroll
-            for (int m = 0; m < MTM; ++m) {
-              if (!live_m(m, m_out)) continue;
+            for (int m = 0; m < GE::MTM; ++m) {
+              if (!GE::live_m(m, m_out)) continue;
               nv[m] = mfma16(wf[m], cs, nv[m]);
               nt[m] = mfma16(wf[m], cq, nt[m]);
               if (second) n2[m] = mfma16(wf[m], cw, n2[m]);
             }
           }
-          if (EDGE) {
+          if (GE::EDGE) {
 #pragma unroll
-            for (int v = 0; v < NVE; ++v) { ev[v] += we[v] * cs; et[v] += we[v] * cq; e2v[v] += we[v] * cw; }
+            for (int v = 0; v < GE::NVE; ++v) { ev[v] += we[v] * cs; et[v] += we[v] * cq; e2v[v] += we[v] * cw; }
           }
           if ((ks & 1) == 0) {
             if (j + 3 < NP) e3 = act_exp2<TANH>(pr(pv, j + 3));
@@ -182,20 +160,20 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_taylor16_ker
             cs2 = s1; cq2 = q1; cw2 = w1; s1 = s2; e2 = e3;
           }
 #pragma unroll
-          for (int m = 0; m < MTM; ++m) wf[m] = wn[m];
+          for (int m = 0; m < GE::MTM; ++m) wf[m] = wn[m];
 #pragma unroll
-          for (int v = 0; v < NVE; ++v) we[v] = wen[v];
+          for (int v = 0; v < GE::NVE; ++v) we[v] = wen[v];
         }
-        if (EDGE) {                                   // sum the four lane groups' shares; group g keeps edge feature g
-          nv[MT - 1][0] += edge_reduce_scatter<NVE>(ev, g);          // bias was loaded above
-          nt[MT - 1][0] = edge_reduce_scatter<NVE>(et, g);
-          n2[MT - 1][0] = edge_reduce_scatter<NVE>(e2v, g);
+        if (GE::EDGE) {                                   // sum the four lane groups' shares; group g keeps edge feature g
+          nv[GE::MT - 1][0] += edge_reduce_scatter<GE::NVE>(ev, g);          // bias was loaded above
+          nt[GE::MT - 1][0] = edge_reduce_scatter<GE::NVE>(et, g);
+          n2[GE::MT - 1][0] = edge_reduce_scatter<GE::NVE>(e2v, g);
         }
 #pragma unroll
-        for (int m = 0; m < MT; ++m) { pv[m] = nv[m]; pt[m] = nt[m]; p2[m] = n2[m]; }
+        for (int m = 0; m < GE::MT; ++m) { pv[m] = nv[m]; pt[m] = nt[m]; p2[m] = n2[m]; }
       }
       // ---------------------------------------------------------------- last activation + output layer (VALU)
-      auto pairOf = [](const f32x4 (&t)[MT], int j) { return f32x2{t[(2 * j) >> 2][(2 * j) & 3], t[(2 * j) >> 2][((2 * j) & 3) + 1]}; };
+      auto pairOf = [](const f32x4 (&t)[GE::MT], int j) { return f32x2{t[(2 * j) >> 2][(2 * j) & 3], t[(2 * j) >> 2][((2 * j) & 3) + 1]}; };
       f32x2 u2 = {0.f, 0.f}, ud2 = {0.f, 0.f}, uw2 = {0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < PA<KS>::NP; ++j) {
@@ -224,51 +202,11 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_taylor16_ker
         ut = ud;
       }
     }
-    if (valid && g == 0) {
-      float out = A.td ? -ut : 0.f;
-      out += A.diff[row] * lap;
-      out -= adv;
-      if (A.src) out += A.src[row];
-      if (A.u) A.u[row] = uval;
-      A.res[row] = out;
-    }
+    if (valid && g == 0) store_residual(A, row, uval, ut, lap, adv);
   }
-}
-
-template <int L, int KS, bool TANH>
-hipError_t launch_one(const VnTaylorArgsD& a, int ncu, hipStream_t s) {
-  const size_t bytes = (size_t)PLay<L, KS>::TOTAL * sizeof(float);
-  // the attribute is per device and sticky: set it once per device (bit mask; engines on different devices may be
-  // driven from different threads)
-  static std::atomic<unsigned long long> attr_done{0};
-  static std::atomic<int> occ{0};                    // workgroups of this instantiation a CU holds (registers, LDS)
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)vn_taylor16_kernel<L, KS, TANH>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return e;
-    int nb = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)vn_taylor16_kernel<L, KS, TANH>, NTHREADS, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      nb = 1;
-    }
-    occ.store(nb < 1 ? 1 : nb, std::memory_order_relaxed);
-    attr_done.fetch_or(bit, std::memory_order_release);
-  }
-  const int per_cu = occ.load(std::memory_order_relaxed) >= 2 ? 2 : 1;       // waves are independent: see vn_pgrad16.hip
-  const long wgs = ((a.n + CW - 1) / CW + NW - 1) / NW;
-  const long cap = (long)ncu * per_cu;
-  const int grid = (int)(wgs < cap ? wgs : cap);
-  hipLaunchKernelGGL((vn_taylor16_kernel<L, KS, TANH>), dim3(grid), dim3(NTHREADS), bytes, s, a);
-  return hipGetLastError();
 }
 
 }  // namespace
-
-// the instantiations (vn_points16.h): in the product library the networks the bf16-piece kernels do NOT serve
-#define VN_TAYLOR16_CASES(X) VN_POINT16_F32_CASES(X)
 
 hipError_t vn_taylor16_residual(const VnNet& net, const float* theta, const float* X, const float* diff, const float* vel,
                                 const float* src, const float* ddx, int td, long n, float* u, float* res, int ncu, hipStream_t s) {
@@ -277,11 +215,9 @@ hipError_t vn_taylor16_residual(const VnNet& net, const float* theta, const floa
   if (!vn_taylor16_supported(net, td)) return hipErrorInvalidValue;
   VnTaylorArgsD a;
   a.net = net; a.theta = theta; a.X = X; a.diff = diff; a.vel = vel; a.src = src; a.ddx = ddx; a.td = td; a.n = n; a.u = u; a.res = res;
-  const int ks = vn_fused16_ks(net);
-#define X(LL, KK)                                                                              \
-  if (net.L == LL && ks == KK)                                                                  \
-    return net.act == VN_ACT_TANH ? launch_one<LL, KK, true>(a, ncu, s) : launch_one<LL, KK, false>(a, ncu, s);
-  VN_TAYLOR16_CASES(X)
-#undef X
-  return hipErrorInvalidValue;
+  // in the product library the networks the bf16-piece kernels do NOT serve (VN16_F32_POINT_CASES); two workgroups per CU where they fit
+  return visit_f32_point(net, hipErrorInvalidValue, [&](auto I) {
+    using T = decltype(I);
+    return launch_chunks<vn_taylor16_kernel<T::L, T::KS, T::TANH>, true>(a, n, (size_t)PLay<T::L, T::KS>::TOTAL * sizeof(float), ncu, 0, s);
+  });
 }

@@ -13,8 +13,6 @@
 #include "vn_points16.h"
 #include "vn_taylor16.h"
 
-#include <atomic>
-
 namespace {
 using namespace vn16;
 
@@ -212,45 +210,20 @@ __global__ __launch_bounds__(NTHREADS, 2) void vn_taylor16d_kernel(VnTaylorDArgs
   }
 }
 
-template <int L, int KS, bool TANH>
-hipError_t launch_one(const VnTaylorDArgs& a, int ncu, hipStream_t s) {
-  constexpr size_t bytes = DLay<L, KS>::BYTES;
-  if (bytes > 160 * 1024) return hipErrorInvalidValue;       // images beyond the LDS: the caller falls back to the per-thread kernels
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)vn_taylor16d_kernel<L, KS, TANH>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return e;
-    attr_done.fetch_or(bit, std::memory_order_release);
-  }
-  const long wgs = ((a.n + CW - 1) / CW + NW - 1) / NW;
-  const int grid = (int)(wgs < ncu ? wgs : ncu);
-  hipLaunchKernelGGL((vn_taylor16d_kernel<L, KS, TANH>), dim3(grid), dim3(NTHREADS), bytes, s, a);
-  return hipGetLastError();
+// every network of the 8-wave family whose double-precision images fit the LDS: f(Inst) for it, else `none` (and no kernel)
+template <class R, class F>
+R visit_fitting(const VnNet& net, R none, F f) {
+  return visit_all(net, none, [&](auto I) {
+    if constexpr (DLay<decltype(I)::L, decltype(I)::KS>::BYTES <= 160 * 1024) return f(I);
+    else return none;
+  });
 }
-
-template <int L, int KS>
-constexpr bool fits() { return DLay<L, KS>::BYTES <= 160 * 1024; }
 
 }  // namespace
 
-// every network of the 8-wave family whose double-precision images fit the LDS
-#define VN_TAYLOR16D_CASES(X) \
-  X(1, 5) X(2, 5) X(3, 5) X(4, 5) X(5, 5) X(6, 5) X(7, 5) X(8, 5)  \
-  X(1, 8) X(2, 8) X(3, 8) X(4, 8) X(5, 8) X(6, 8) X(7, 8) X(8, 8)  \
-  X(1, 13) X(2, 13) X(3, 13) X(4, 13) X(5, 13) X(6, 13)  \
-  X(1, 16) X(2, 16) X(3, 16) X(4, 16) X(5, 16)
-
 bool vn_taylor16d_supported(const VnNet& net) {
   if (!vn_fused16_net_supported(net) || net.dim > 3 || net.d_in > 4 * KS0) return false;
-  const int ks = vn_fused16_ks(net);
-#define X(LL, KK) if (net.L == LL && ks == KK) return fits<LL, KK>();
-  VN_TAYLOR16D_CASES(X)
-#undef X
-  return false;
+  return visit_fitting(net, false, [](auto) { return true; });
 }
 
 hipError_t vn_taylor16d_launch(const VnNet& net, const double* theta, const double* X, const double* diff, const double* vel,
@@ -259,11 +232,8 @@ hipError_t vn_taylor16d_launch(const VnNet& net, const double* theta, const doub
   if (!vn_taylor16d_supported(net) || (res && net.dim + (td ? 1 : 0) > net.d_in)) return hipErrorInvalidValue;
   VnTaylorDArgs a;
   a.net = net; a.theta = theta; a.X = X; a.diff = diff; a.vel = vel; a.src = src; a.ddx = ddx; a.td = td; a.n = n; a.u = u; a.res = res;
-  const int ks = vn_fused16_ks(net);
-#define X(LL, KK)                                                                              \
-  if (net.L == LL && ks == KK)                                                                  \
-    return net.act == VN_ACT_TANH ? launch_one<LL, KK, true>(a, ncu, s) : launch_one<LL, KK, false>(a, ncu, s);
-  VN_TAYLOR16D_CASES(X)
-#undef X
-  return hipErrorInvalidValue;
+  return visit_fitting(net, hipErrorInvalidValue, [&](auto I) {
+    using T = decltype(I);
+    return launch_chunks<vn_taylor16d_kernel<T::L, T::KS, T::TANH>, false>(a, n, DLay<T::L, T::KS>::BYTES, ncu, 1, s);
+  });
 }
