@@ -21,8 +21,9 @@
 //     through L2 to HBM).  Fixed summation order everywhere: results are bitwise reproducible.
 //   * Hidden widths 33..50 with 2..5 hidden layers (bf_sweeps): forward and input-gradient sweeps as bf16-piece
 //     products on the bf16 matrix pipe (vn_fused16_common.h); their images need the LDS of the stash, which then
-//     holds one layer in global memory.
-// Register budget: 256 VGPRs per wave (stored activations 2*KS*L = 130 at 5x50; 36 spilled at 5x50).
+//     holds one layer in global memory.  The fourth row tile of either sweep (features 48, 49) is folded: its idle rows
+//     carry the m- and l-pieces, three MFMAs per K fragment and stream instead of six (stage_split_hidden, FOLD13).
+// Register budget: 256 VGPRs per wave (stored activations 2*KS*L = 130 at 5x50; 18 spilled at 5x50).
 #include "vn_internal.h"
 #include "vn_fused16_common.h"
 
@@ -699,7 +700,7 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       const int k = tid / H1, f = tid - k * H1;
       W1[k * WS + vpos(f >> 2, f & 3)] = v1;
     }
-    if constexpr (LY::BF) stage_split_hidden<L>(net, A.theta, reinterpret_cast<char*>(WH), tid);
+    if constexpr (LY::BF) stage_split_hidden<L, true>(net, A.theta, reinterpret_cast<char*>(WH), tid);
 #pragma unroll
     for (int l = 2; l <= (LY::BF ? 1 : L); ++l) {
       float* Wl = WH + (l - 2) * LY::HPWS;
@@ -856,7 +857,10 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
     for (int l = 2; l <= L; ++l) {
       if constexpr (LY::BF) {
         // bf16 pieces: all four row tiles on the matrix pipe (features 48, 49 land in row 48 + 4g as in the edge path), value
-        // and tangent share each weight fragment; the activation and the split are scalar f32 forms (no v_pk_* beside bf16 MFMAs)
+        // and tangent share each weight fragment; the activation and the split are scalar f32 forms (no v_pk_* beside bf16 MFMAs).
+        // Invariants of the folded fourth tile: the B operands below are exact zeros at k-steps 13..15 (0u, `full ? .. : 0.f`), the
+        // bias image is zero there, and registers 1..3 of tile 3 (finite partial sums after fold_rows, not 0) are read only
+        // under ks < KS guards (B operands, H13Pub, the z-bar step) or against the zero padding weights of the output layer.
         const char* rl = win_base(rowb, l);
         f32x4 nv[GE::MT], nt[GE::MT];
 #pragma unroll
@@ -890,13 +894,19 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
           }
 #pragma unroll
           for (int mt = 0; mt < GE::MT; ++mt) {
-            u32x4 Af[3];
-            split_frag_row(rl, qf, mt, Af);
             const u32x4 (*const Bs[2])[3] = {&Bv, &Bt};
             f32x4* const as[2] = {&nv[mt], &nt[mt]};
+            if (mt == 3) {                           // features 48, 49: folded edge tile (the bias image is zero in rows 1..3)
+              three_folded<2>(split_frag_row1(rl, 0, qf, mt), Bs, as);
+              continue;
+            }
+            u32x4 Af[3];
+            split_frag_row(rl, qf, mt, Af);
             six<2>(Af, Bs, as);
           }
         }
+        fold_rows(nv[3]);
+        fold_rows(nt[3]);
 #pragma unroll
         for (int m = 0; m < GE::MT; ++m) { pv[m] = nv[m]; ptn[m] = nt[m]; }
         continue;
@@ -1193,13 +1203,19 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
           }
 #pragma unroll
           for (int mt = 0; mt < GE::MT; ++mt) {
-            u32x4 At[3];
-            split_frag_tr(tl, qf, mt, At);
             const u32x4 (*const Bs[2])[3] = {&Bz, &Bzd};
             f32x4* const as[2] = {&accv[mt], &acct[mt]};
+            if (mt == 3) {                           // in-features 48, 49: the mirror fold (in-slots 5, 6 of piece 0)
+              three_folded<2>(split_frag_tr1(tl, 0, qf, mt), Bs, as);
+              continue;
+            }
+            u32x4 At[3];
+            split_frag_tr(tl, qf, mt, At);
             six<2>(At, Bs, as);
           }
         }
+        fold_rows(accv[3]);
+        fold_rows(acct[3]);
       } else {
       const float* Wl = WH + (l - 2) * LY::HPWS;
       int k_out = (net.H[l] + 3) >> 2, m_in = (net.H[l - 1] + 15) >> 4;

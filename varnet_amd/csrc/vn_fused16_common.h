@@ -271,11 +271,26 @@ __device__ __forceinline__ void six(const u32x4 (&A)[3], const u32x4 (*const (&B
 // The bf16-piece images of hidden layers 2..L at img (L - 1 consecutive IMG-byte images): one 16-byte entry (8 in-features of
 // one out-position) per thread and layer, cut into its three pieces here; padding exact zeros.  Ends with the images written
 // but not yet visible to other waves: the caller synchronises.
-template <int L>
+//
+// FOLD13 (the fused step kernel at KS == 13, widths 33..50): the edge k-step 12 holds features 48, 49 only, so the fourth row
+// tile of the forward sweep has two real rows (4g' + 0, g' = 0, 1) and the fourth row tile of the sweep back likewise.  Their
+// idle neighbours carry the other two pieces of the same weights, in the PIECE-0 blocks:
+//   out-fold: rows 4g' + 1 and 4g' + 2 of row tile 3 hold the m- and the l-pieces of out-feature 48 + g' -- one MFMA per B
+//             piece leaves Ah.B, Am.B, Al.B in accumulator registers 0, 1, 2 (three MFMAs and one fragment instead of six
+//             and three; all nine piece products instead of six);
+//   in-fold:  slots j = 5, 6 of the q == 1 entries (k-steps 13, 14) hold the m- and the l-piece of slot 4 (in-feature 48 + g):
+//             the transposed read of piece 0 hands the sweep back the same three rows.
+// What makes this safe: k-steps 13..15 never hold a feature at KS == 13 (features >= 52), every sweep's B operand is an exact
+// zero there (the constant 0u and the `full ? .. : 0.f` halves), and so is the bias image.  Where both folds meet (rows
+// 4g' + 1, 2 x slots 5, 6) the image stays zero.
+template <int L, bool FOLD13 = false>
 __device__ __forceinline__ void stage_split_hidden(const VnNet& net, const float* theta, char* img, int tid) {
   static_assert(NTHREADS == 2 * 4 * 4 * 16, "one entry per thread and layer");
   const int q = tid >> 8, mt = (tid >> 6) & 3, g = (tid >> 4) & 3, c = tid & 15;
-  const int pos = 16 * mt + c, fo = vfeat(pos);
+  const int pos = 16 * mt + c;
+  const int fold_r = (FOLD13 && mt == 3) ? (c & 3) : 0;                      // 1 | 2: an out-fold row (m- | l-pieces)
+  const bool ofold = fold_r == 1 || fold_r == 2;
+  const int fo = ofold ? 48 + (c >> 2) : vfeat(pos);
   const int ent = (g * 16 + (c ^ (12 * (g & 1)))) * 16;
 #pragma unroll
   for (int l = 2; l <= L; ++l) {
@@ -294,6 +309,16 @@ __device__ __forceinline__ void stage_split_hidden(const VnNet& net, const float
       split2(w[2 * jj], w[2 * jj + 1], h, m, lo);
       ph[jj] = h; pm[jj] = m; pl[jj] = lo;
     }
+    if constexpr (FOLD13) {
+      if (ofold) {             // slots 5..7 of q == 1 are in-features >= 52: zero in every piece, so the corners stay zero
+        ph = fold_r == 1 ? pm : pl;
+        pm = u32x4{0u, 0u, 0u, 0u};
+        pl = u32x4{0u, 0u, 0u, 0u};
+      } else if (q == 1) {     // slot 4 = low half of word 2; slot 5 = its high half, slot 6 = low half of word 3 (both zero so far)
+        ph[2] = (ph[2] & 0xffffu) | (pm[2] << 16);
+        ph[3] = (ph[3] & 0xffff0000u) | (pl[2] & 0xffffu);
+      }
+    }
     char* il = img + (l - 2) * IMG;
     *reinterpret_cast<u32x4a*>(il + ((0 * 2 + q) * 4 + mt) * BLK + ent) = ph;
     *reinterpret_cast<u32x4a*>(il + ((1 * 2 + q) * 4 + mt) * BLK + ent) = pm;
@@ -310,23 +335,46 @@ __device__ __forceinline__ int split_tr_base(int g, int c) {
   return (tr_p * 16 + ((4 * g + tr_r) ^ (12 * (tr_p & 1)))) * 16;
 }
 // A fragment (three pieces) of row tile mt, K fragment q, from a layer's image at rl = image + split_row_base
+__device__ __forceinline__ u32x4 split_frag_row1(const char* rl, int p, int q, int mt) {
+  return *reinterpret_cast<const u32x4a*>(rl + ((p * 2 + q) * 4 + mt) * BLK);
+}
 __device__ __forceinline__ void split_frag_row(const char* rl, int q, int mt, u32x4 (&Af)[3]) {
 #pragma unroll
-  for (int p = 0; p < 3; ++p) Af[p] = *reinterpret_cast<const u32x4a*>(rl + ((p * 2 + q) * 4 + mt) * BLK);
+  for (int p = 0; p < 3; ++p) Af[p] = split_frag_row1(rl, p, q, mt);
 }
 // Transposed A fragment of in-position row tile mt, out-feature K fragment q, from tl = image + split_tr_base: in the forward
 // image those are element 4(mt&1) + (c&3) of the entries (g_in = (c>>2)&3, c_out = 4g + (j&3)) of blocks (q_in = mt>>1,
 // mt_out = 2q + (j>>2)): two transposed reads per piece (EXEC must be all ones).
+__device__ __forceinline__ u32x4 split_frag_tr1(const char* tl, int p, int q, int mt) {
+  const char* b0 = tl + ((p * 2 + (mt >> 1)) * 4 + 2 * q) * BLK + 8 * (mt & 1);
+  const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b0));
+  const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b0 + BLK));
+  const unsigned long long l64 = __builtin_bit_cast(unsigned long long, lo4), h64 = __builtin_bit_cast(unsigned long long, hi4);
+  return u32x4{(u32)l64, (u32)(l64 >> 32), (u32)h64, (u32)(h64 >> 32)};
+}
 __device__ __forceinline__ void split_frag_tr(const char* tl, int q, int mt, u32x4 (&At)[3]) {
 #pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    const char* b0 = tl + ((p * 2 + (mt >> 1)) * 4 + 2 * q) * BLK + 8 * (mt & 1);
-    const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b0));
-    const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b0 + BLK));
-    const unsigned long long l64 = __builtin_bit_cast(unsigned long long, lo4), h64 = __builtin_bit_cast(unsigned long long, hi4);
-    At[p] = u32x4{(u32)l64, (u32)(l64 >> 32), (u32)h64, (u32)(h64 >> 32)};
+  for (int p = 0; p < 3; ++p) At[p] = split_frag_tr1(tl, p, q, mt);
+}
+
+// The folded edge tile (stage_split_hidden, FOLD13): ONE fragment -- piece 0, whose rows / slots 0, 1, 2 of every group of four
+// hold the h-, m- and l-pieces of the same weights -- against the B pieces l, m, h (small terms first), one MFMA each and stream.
+// Registers 0, 1, 2 of the accumulators then hold Ah.B, Am.B, Al.B: fold_rows adds them up once the K fragments are through.
+template <int N>
+__device__ __forceinline__ void three_folded(const u32x4& A0, const u32x4 (*const (&B)[N])[3], f32x4* const (&acc)[N]) {
+#pragma unroll
+  for (int p = 2; p >= 0; --p) {
+#pragma unroll
+    for (int s = 0; s < N; ++s) *acc[s] = mfma_bf16(A0, (*B[s])[p], *acc[s]);
   }
 }
+// registers 1, 2 keep their partial sums (finite, never NaN: sums of products of finite pieces).  Nothing reads them unguarded:
+// at KS == 13 they are k-steps 13, 14, which every consumer of an accumulator tile either skips (ks < KS) or multiplies by a
+// zero weight (the output layer's padding weights).
+// The order of the two adds is free as far as accuracy goes (they differ by an ulp of the m- and l-rows, 2^-8 and 2^-16 of the
+// result); h + m first, then l, is the order the whole suite was verified with: an L-BFGS trajectory test that hangs on
+// the last bit of a loss of 10.5 stalls with l + m first (DESIGN_LOG G.3).
+__device__ __forceinline__ void fold_rows(f32x4& t) { t[0] = (t[0] + t[1]) + t[2]; }
 
 // ---- host side: one dispatch walk, one launcher ----------------------------------------------------------------------------
 template <int L_, int KS_, bool TANH_>
