@@ -191,6 +191,23 @@ int vn_set_batch_bic(vn_engine* h, int32_t batch, const float* biInput_dev, cons
  * registration, also when it fails (after an error there is none). */
 int vn_set_flux_bc(vn_engine* h, const float* X_dev, const float* normal_dev, const float* coef_dev,
                    const float* label_dev, int64_t nF, double biDimVal);
+/* OPTIONAL, no reference counterpart: periodic boundary pairs, shared by all batches.  Device pointers: X [2 nP, d_in],
+ * dir [2 nP, dim]; rows i and i + nP are the two images of one point (x_B = x_A + s, same time), and both carry the same unit
+ * direction d (the outward normal of side A).  nP == 0 or X == NULL clears.  With pairs registered, vn_grad / vn_train_step /
+ * vn_train_epoch / vn_eval_loss / vn_lbfgs_step / vn_objective_f64 add the jumps of value and derivative across each pair,
+ *     r0 = u_i - u_{i+nP},     r1 = d . grad_x u_i - d . grad_x u_{i+nP}     (grad_x: the dim space inputs)
+ * to the BC component:
+ *     BC = mean_D[biDimVal (u - g/beta)^2] + mean_F[biDimVal r^2] + mean_P[biDimVal (r0^2 + gamma r1^2)]
+ * weighted by w[0] like the other two means (each is 0 without its rows); the gradient, the update fused into the reduction and
+ * a communicator's all-reduce all see it.  gamma >= 0 weights the derivative match; gamma == 0 matches values only (no tangent
+ * stream is computed and no derivative seed produced); negative or non-finite: VN_EINVAL.  The pass runs on the generic kernels
+ * (forward along the directions, pair seeds, reverse pass: three launches per step, beside the flux rows' three when both are
+ * registered) whatever route the interior term takes; networks outside VN_KMAX_* (the layer-by-layer route, 7-8 hidden layers,
+ * mixed activations) get VN_EUNSUPPORTED.  Without a registration nothing is launched, nothing is allocated and every result is
+ * bit for bit what it is without this call.  The arrays are READ on every step: they must stay valid while registered.  A call
+ * replaces the previous registration, also when it fails (after an error there is none), and invalidates the L-BFGS (f_k, g_k)
+ * and ring, like vn_set_flux_bc. */
+int vn_set_periodic(vn_engine* h, const float* X_dev, const float* dir_dev, int64_t nP, double gamma, double biDimVal);
 /* OPTIONAL, no reference counterpart: a polynomial reaction term for `batch`,
  *     c_t = div(kappa grad c) - v.grad c + s + rate(x,t) p(c),     p(c) = c1 c + c2 c^2 + c3 c^3
  * (first-order decay, Fisher-KPP, Allen-Cahn-type reactions).  The term sits on the source side: the row integrand of the weak

@@ -1,6 +1,6 @@
 """
 Advection-diffusion(-reaction) PDE container: `ADPDE(domain, diff, vel, source, timeDependent, tInterval,
-BCs, IC, cEx, MORvar, d_diff, reaction, nlflux, nldiff)` -- /root/reference/ADPDE.py:56-246 restated (plot helpers are
+BCs, IC, cEx, MORvar, d_diff, reaction, nlflux, nldiff, periodic)` -- /root/reference/ADPDE.py:56-246 restated (plot helpers are
 out of scope).
 
     c_t = div(diff D(c) grad c) - vel . grad c - div(w F(c)) + source + rate * p(c),    a * dc/dn + b * c = g  on each edge,
@@ -8,6 +8,8 @@ out of scope).
 with the optional polynomial reaction p(c) = c1 c + c2 c^2 + c3 c^3 (`reaction=(rate, [c1, c2, c3])`), the optional
 polynomial flux F(c) = f1 c + f2 c^2 + f3 c^3 (`nlflux=(w, [f1, f2, f3])`) and the optional solution-dependent diffusivity
 D(c) = d0 + d1 c + d2 c^2 (`nldiff=[d0, d1, d2]`; D = 1 without it); none has a reference counterpart, all are absent by default.
+`periodic=[(bIndA, bIndB), ...]` ties boundary indicators in pairs (c and its normal derivative agree across each pair) instead
+of giving them an [a, b, g]; it has no reference counterpart either.
 
 Constants are wrapped into callables f(x[, t]) returning column arrays; every BC is normalised
 to [a, b, g(x,t)] and classified Dirichlet / Neumann / Robin; with a `MOR` instance a lookup
@@ -41,10 +43,15 @@ class ADPDE:
     returning the divergence of vel as a column, and without it the divergence is taken as zero: `vel` must then be constant
     or divergence-free.  D(c) = 0 somewhere (degenerate diffusion) is allowed; D(c) < 0 is the user's responsibility.
     None (the default): no term, D = 1.
+
+    periodic=[(bIndA, bIndB), ...] makes boundary indicator B the periodic image of indicator A: c(x_A) = c(x_A + s) and
+    dc/dn(x_A) = dc/dn(x_A + s) with s the translation that maps edge A onto edge B.  `Domain1D`: the pair is (0, 1), in either
+    order.  `PolygonDomain2D`: the two edges have equal length and opposite outward normals.  A paired indicator has no [a, b, g]:
+    its `BCs` entry stays empty, and `BCtype` reports 'Periodic' for it.  None (the default): no pairs.
     """
 
     def __init__(self, domain, diff, vel, source=0.0, timeDependent=False, tInterval=None,
-                 BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None, nlflux=None, nldiff=None):
+                 BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None, nlflux=None, nldiff=None, periodic=None):
         # the reference ignores the `timeDependent` argument (ADPDE.py:108-109)
         timeDependent = tInterval is not None
 
@@ -130,6 +137,12 @@ class ADPDE:
                                           'stream of the advection is assembled once, for all parameter batches')
             dcoef = dcoef + [0.0] * (3 - len(dcoef))
 
+        if periodic is not None:
+            periodic = self._check_periodic(periodic, domain, BCs)
+            if MORvar is not None:
+                raise NotImplementedError('periodic boundaries with model-order reduction are not supported: the paired rows are '
+                                          'assembled once, for all parameter batches, and carry no parameter inputs')
+
         dim = domain.dim
 
         def const_field(val, ncol):
@@ -207,9 +220,12 @@ class ADPDE:
             elif not callable(bc[2]):
                 last_const['g'] = bc[2]
                 BCs[bInd] = [bc[0], bc[1], lambda x, t=0: last_const['g'] * np.ones([len(x), 1])]
+        paired = set() if periodic is None else {b for pair in periodic for b in pair}
         BCtype = []
         for bInd in range(bIndNum):
-            if BCs[bInd][0] == 0:
+            if bInd in paired:
+                BCtype.append('Periodic')
+            elif BCs[bInd][0] == 0:
                 BCtype.append('Dirichlet')
             elif BCs[bInd][1] == 0:
                 BCtype.append('Neumann')
@@ -260,3 +276,48 @@ class ADPDE:
         self.IC = IC
         self.cEx = cEx
         self.MORvar = MORvar
+        self.periodic = periodic
+
+    @staticmethod
+    def _check_periodic(periodic, domain, BCs):
+        """The pairs as a list of (A, B) integer tuples, or ValueError: indices in range and distinct, every indicator in at most
+        one pair, no [a, b, g] on a paired indicator, and edges that are translates of each other."""
+        if not isinstance(periodic, (list, tuple)) or len(periodic) == 0:
+            raise ValueError('periodic must be a non-empty list of boundary indicator pairs [(bIndA, bIndB), ...]!')
+        nb = domain.bIndNum
+        pairs, seen = [], set()
+        for pair in periodic:
+            if not isinstance(pair, (list, tuple)) or len(pair) != 2 or \
+                    not all(isinstance(b, (int, np.integer)) and not isinstance(b, bool) for b in pair):
+                raise ValueError('periodic must be a non-empty list of boundary indicator pairs [(bIndA, bIndB), ...]!')
+            A, B = int(pair[0]), int(pair[1])
+            for b in (A, B):
+                if not 0 <= b < nb:
+                    raise ValueError('periodic pair (%d, %d): boundary indicator %d outside [0, %d)!' % (A, B, b, nb))
+            if A == B:
+                raise ValueError('periodic pair (%d, %d): the two boundary indicators must be distinct!' % (A, B))
+            for b in (A, B):
+                if b in seen:
+                    raise ValueError('periodic pair (%d, %d): boundary indicator %d appears in more than one pair!' % (A, B, b))
+                seen.add(b)
+            if BCs is not None:
+                for b in (A, B):
+                    if not uf.isempty(BCs[b]):
+                        raise ValueError('periodic pair (%d, %d): BCs[%d] must be empty, a periodic edge has no [a, b, g]!' % (A, B, b))
+            if domain.dim == 1:
+                if {A, B} != {0, 1}:                # (unreachable while Domain1D has two indicators; kept for the message)
+                    raise ValueError('periodic pair (%d, %d): a 1D domain pairs its two ends, (0, 1)!' % (A, B))
+            else:
+                if A >= domain.vertexNum or B >= domain.vertexNum:
+                    raise ValueError('periodic pair (%d, %d): obstacle edges cannot be paired!' % (A, B))
+                g = np.asarray(domain.boundryGeom, dtype=float)
+                lA, lB = np.linalg.norm(g[A, 1] - g[A, 0]), np.linalg.norm(g[B, 1] - g[B, 0])
+                if abs(lA - lB) > 1e-12 * max(lA, lB):
+                    raise ValueError('periodic pair (%d, %d): edges %d and %d have unequal lengths (%.17g and %.17g), they are '
+                                     'not translates of each other!' % (A, B, A, B, lA, lB))
+                n = np.asarray(domain.boundaryNormals(), dtype=float)
+                if np.max(np.abs(n[A] + n[B])) > 1e-12:
+                    raise ValueError('periodic pair (%d, %d): the outward normals of edges %d and %d are not opposite (%s and %s), '
+                                     'they are not translates of each other!' % (A, B, A, B, n[A], n[B]))
+            pairs.append((A, B))
+        return pairs

@@ -3,6 +3,7 @@
 #include "vn_internal.h"
 #include "vn_dedup.h"
 #include "vn_flux.h"
+#include "vn_periodic.h"
 #include "vn_lbfgs.h"
 #include "vn_obj64.h"
 #include "vn_pgrad16.h"
@@ -199,6 +200,13 @@ struct vn_engine {
   int fgrid = 0;                                  // workgroups of the flux rows' reverse pass
   float *fu = nullptr, *fud = nullptr, *fubar = nullptr, *fudbar = nullptr, *floss = nullptr, *fpartial = nullptr;
   long fu_cap = 0, fud_cap = 0, fubar_cap = 0, fudbar_cap = 0, floss_cap = 0, fpartial_cap = 0;
+  // periodic pairs (vn_set_periodic): caller-owned inputs (rows i and i + nP pair), engine-owned work buffers; nP == 0: none
+  const float *pX = nullptr, *pD = nullptr;
+  long nP = 0;
+  double pgamma = 1.0, pbiDimVal = 1.0;
+  int pgrid = 0;                                  // workgroups of the paired rows' reverse pass
+  float *pu = nullptr, *pud = nullptr, *pubar = nullptr, *pudbar = nullptr, *ploss = nullptr, *ppartial = nullptr;
+  long pu_cap = 0, pud_cap = 0, pubar_cap = 0, pudbar_cap = 0, ploss_cap = 0, ppartial_cap = 0;
   float* snap = nullptr;       // vn_state_snapshot: device copy of (theta | m | v), 3 P floats
   int64_t snap_step = -1;      // step counter at the snapshot (-1: none)
   PointRoute point_route = PointRoute::automatic;   // vn_debug_point_route(route & 3)
@@ -653,12 +661,43 @@ int flux_pass(vn_engine* h, bool with_grad, VnFluxSum* fx) {
   return VN_OK;
 }
 
+// Periodic pairs (vn_set_periodic), on every route, the two-point version of flux_pass: value and derivative d . grad_x u of the
+// 2 nP paired rows, the jumps r0, r1 of each pair with their loss partials and seeds, and with_grad the generic reverse pass into
+// partials of their own -- launches of their own, so a step with flux rows only is untouched.  gamma == 0: value stream only.
+int periodic_pass(vn_engine* h, bool with_grad, VnFluxSum* px) {
+  *px = VnFluxSum();
+  if (h->nP <= 0) return VN_OK;
+  const bool deriv = h->pgamma > 0.0;
+  VnRows r{}, none{};
+  r.X = h->pX; r.G = deriv ? h->pD : nullptr; r.u = h->pu; r.ud = deriv ? h->pud : nullptr; r.n = 2 * h->nP;
+  HIPCHK(vn_generic_forward(h->net, h->theta, r, none, h->fwd_grid, h->stream));
+  VnPeriodicSeedArgs a{};
+  a.u = h->pu; a.ud = r.ud; a.nP = h->nP; a.gamma = (float)h->pgamma;
+  a.biDimVal = (float)h->pbiDimVal; a.w0 = (float)h->w[0];
+  a.ubar = with_grad ? h->pubar : nullptr; a.udbar = with_grad && deriv ? h->pudbar : nullptr;
+  a.part = h->ploss;
+  HIPCHK(vn_periodic_seed_launch(a, h->stream));
+  if (with_grad) {
+    r.u = nullptr; r.ud = nullptr; r.ubar = h->pubar; r.udbar = a.udbar;
+    HIPCHK(vn_generic_backward(h->net, h->theta, r, none, h->ppartial, h->pgrid, h->stream));
+    px->partial = h->ppartial; px->nparts = h->pgrid;
+  }
+  px->loss = h->ploss; px->nlp = vn_periodic_seed_blocks(h->nP); px->nF = h->nP;
+  return VN_OK;
+}
+
+// Both boundary passes of a step, flux rows first: what its reduction adds.
+int edge_passes(vn_engine* h, bool with_grad, VnEdgeSums* fx) {
+  if (int rc = flux_pass(h, with_grad, &fx->flux)) return rc;
+  return periodic_pass(h, with_grad, &fx->per);
+}
+
 // Loss components and loss field of a batch that carries a de-duplication map (vn_set_dedup), without the row-wise forward: (u, grad u)
 // once per unique point (2 F_pt per POINT where the forward-only mode of the fused kernel costs 2 F_pt per ROW), the assembly kernel of
 // the training step in its loss-only form (R_k, lossVec, variational partials), the BC/IC rows through the forward-only mode and the
 // row-wise seed kernel with an empty interior set.  What every monitor of a run on the de-duplicated formulation calls (splitLoss,
 // VarNet.py:1365): 2.9 -> 0.45 ms on BASELINE config 3.
-int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst, const VnFluxSum& fx) {
+int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst, const VnEdgeSums& fx) {
   const int sblk = (int)((b.n_k + VN_DEDUP_TFB - 1) / VN_DEDUP_TFB);
   const int bgrid = (int)(((h->nB > 0 ? h->nB : 1) + 255) / 256);
   if (int rc = ensure(&h->losspart, &h->losspart_cap, (long)(sblk + bgrid) * 3)) return rc;
@@ -680,9 +719,10 @@ int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst, con
   return VN_OK;
 }
 
-// forward + weak-form epilogue; with_seeds = also produce backward seeds.  fx: the flux rows' loss, folded into lossdst.
+// forward + weak-form epilogue; with_seeds = also produce backward seeds.  fx: the flux rows' and the periodic pairs' loss, folded
+// into lossdst.
 int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* lossVec, float* lossdst,
-                         const VnFluxSum& fx = VnFluxSum()) {
+                         const VnEdgeSums& fx = VnEdgeSums()) {
   if (!with_seeds && b.Xu && h->has_fe && !h->eval_rowwise) return eval_dedup(h, b, lossVec, lossdst, fx);
   VnRows s0{}, s1{};
   s0.X = b.Input; s0.G = b.gcoef; s0.u = h->u; s0.ud = h->ud; s0.n = b.n_k * h->cfg.integ_num;
@@ -717,7 +757,7 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
   return VN_OK;
 }
 
-int run_layered(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
+int run_layered(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx) {
   if (int rc = run_forward_and_seed(h, b, true, nullptr, nullptr)) return rc;
   VnRows s0{}, s1{};
   s0.X = b.Input; s0.G = b.gcoef; s0.ubar = h->ubar; s0.udbar = h->udbar; s0.n = b.n_k * h->cfg.integ_num;
@@ -735,7 +775,7 @@ int run_layered(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& f
   return VN_OK;
 }
 
-int run_generic(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
+int run_generic(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx) {
   if (int rc = run_forward_and_seed(h, b, true, nullptr, nullptr)) return rc;
   VnRows s0{}, s1{};
   s0.X = b.Input; s0.G = b.gcoef; s0.ubar = h->ubar; s0.udbar = h->udbar; s0.n = b.n_k * h->cfg.integ_num;
@@ -752,7 +792,7 @@ int run_generic(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& f
 
 // One launch of the fused kernel (8-wave, or 4-wave in the cross-check build) for the whole step: forward, weak-form epilogue
 // and reverse pass of every tile, BC/IC tiles included
-int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
+int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx) {
   VnFusedArgs a = fused_args(h, &b);
   a.X = b.Input; a.G = b.gcoef; a.src = batch_src(h, b);
   a.nT = b.n_k * h->cfg.integ_num; a.n_k = b.n_k; a.feW = fe_w(h);
@@ -785,7 +825,7 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx)
 // in the seed kernel; neither mode of the fused kernel looks at integ_num.  A flux term (vn_set_nlflux) and a diffusivity D(u)
 // (vn_set_nldiff) take the same sequence, with their elementwise kernels around the seed kernel (terms_fold_rows, terms_seed_rows).
 // So does a batch with per-test-function loss weights (vn_set_tf_weights, vn_set_causal): they are applied after the seed kernel.
-int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
+int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx) {
   const int grid = h->ncu, P = h->net.P;
   const int sgrid = (int)((b.n_k + 255) / 256);
   if (int rc = ensure(&h->tp_losspart, &h->tp_losspart_cap, (long)(grid + sgrid) * 3)) return rc;
@@ -822,7 +862,7 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& f
 //   4. ONE reverse launch of the fused kernel (recomputes the forward): the directional derivative is linear in its
 //      direction, sum_d sg_d * d(u_{x_d})/d theta = d(sg . grad u)/d theta with sg held fixed, so the per-point direction
 //      G = sg with tangent seed 1 and value seed su gives the whole gradient; BC/IC tiles ride along       (6 F_pt)
-int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnFluxSum& fx) {
+int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx) {
   const int grid = h->ncu, P = h->net.P;
   const int sblk = (int)((b.n_k + VN_DEDUP_TFB - 1) / VN_DEDUP_TFB);
   float* lp = h->dd_losspart;                       // [grid + sblk][3]
@@ -1004,7 +1044,7 @@ int vn_destroy(vn_engine* h) {
   if (h->comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(h->stream); (void)g_rccl.CommDestroy(h->comm); h->comm = nullptr; }
   void* ptrs[] = {h->theta, h->m, h->v, h->snap, h->theta64, h->gradbuf_int, h->lossbuf, h->partial, h->feN, h->fedNt,
                   h->feW, h->u, h->ud, h->ubar, h->udbar, h->ub, h->ubar_b, h->losspart, h->fused_losspart, h->stamps, h->dd_uv, h->dd_su, h->dd_sg, h->dd_partial,
-                  h->dd_losspart, h->rx_seff, h->nd_A, h->wt_lvec, h->wt_omega, h->wt_stat, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial,
+                  h->dd_losspart, h->rx_seff, h->nd_A, h->wt_lvec, h->wt_omega, h->wt_stat, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial, h->pu, h->pud, h->pubar, h->pudbar, h->ploss, h->ppartial,
                   h->lb.ring, h->lb.theta_k, h->lb.g_k, h->lb.d, h->lb.part, h->lb.G, h->lb.coef, h->lb.meta};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -1442,6 +1482,37 @@ int vn_set_flux_bc(vn_engine* h, const float* X, const float* normal, const floa
   return VN_OK;
 }
 
+int vn_set_periodic(vn_engine* h, const float* X, const float* dir, int64_t nP, double gamma, double biDimVal) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (nP < 0) return fail(VN_EINVAL, "negative number of periodic pairs");
+  h->pX = h->pD = nullptr;   // a call replaces the previous registration, also when it fails
+  lbfgs_invalidate(h);
+  h->nP = 0;
+  if (nP == 0 || !X) return VN_OK;
+  if (!dir) return fail(VN_EINVAL, "null argument");
+  if (!(gamma >= 0.0) || !std::isfinite(gamma))
+    return fail(VN_EINVAL, "periodic pairs: the derivative weight gamma = %g must be finite and >= 0", gamma);
+  // the periodic pass runs on the generic kernels, whatever route the interior term takes
+  if (h->route == Route::layered || !vn_net_in_kernel_range(h->net))
+    return fail(VN_EUNSUPPORTED, "periodic boundary pairs need a network of the hand-written kernels (<= %d hidden layers, width <= %d, "
+                "<= %d inputs, one activation); this one (%d layers, widest %d, %d inputs%s) runs on the layer-by-layer route "
+                "or the deep fused kernel only", VN_KMAX_LAYERS, VN_KMAX_WIDTH, VN_KMAX_DIN, h->net.L, h->net.hmax, h->net.d_in,
+                h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const long rows = 2 * nP, tiles = (rows + 31) / 32;
+  const int pgrid = (int)(tiles < h->ncu ? tiles : h->ncu);
+  if (int rc = ensure(&h->pu, &h->pu_cap, rows)) return rc;
+  if (int rc = ensure(&h->pubar, &h->pubar_cap, rows)) return rc;
+  if (gamma > 0.0) {                                  // gamma == 0: no tangent stream, no derivative seed
+    if (int rc = ensure(&h->pud, &h->pud_cap, rows)) return rc;
+    if (int rc = ensure(&h->pudbar, &h->pudbar_cap, rows)) return rc;
+  }
+  if (int rc = ensure(&h->ploss, &h->ploss_cap, vn_periodic_seed_blocks(nP))) return rc;
+  if (int rc = ensure(&h->ppartial, &h->ppartial_cap, (long)pgrid * h->net.P)) return rc;
+  h->pX = X; h->pD = dir; h->nP = nP; h->pgamma = gamma; h->pbiDimVal = biDimVal; h->pgrid = pgrid;
+  return VN_OK;
+}
+
 int vn_set_batch_bic(vn_engine* h, int32_t batch, const float* biInput, const float* biLabel) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
@@ -1471,8 +1542,8 @@ int vn_grad(vn_engine* h, int32_t batch) {
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   const Batch& b = h->batches[batch];
-  VnFluxSum fx;
-  if (int rc = flux_pass(h, true, &fx)) return rc;   // (no flux rows: nothing enqueued, fx empty)
+  VnEdgeSums fx;
+  if (int rc = edge_passes(h, true, &fx)) return rc;   // (no flux rows, no periodic pairs: nothing enqueued, fx empty)
   if (b.Xu) return run_dedup(h, b, h->gradbuf, fx);      // (a de-duplication map: 8-wave routes only)
   switch (h->route) {
     case Route::layered: return run_layered(h, b, h->gradbuf, fx);
@@ -1690,8 +1761,8 @@ int vn_eval_loss(vn_engine* h, int32_t batch, double out[4], float* lossVec_dev)
   (void)hipGetLastError();   // a stale last-error of another library on this thread is not ours to report
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
-  VnFluxSum fx;
-  if (int rc = flux_pass(h, false, &fx)) return rc;
+  VnEdgeSums fx;
+  if (int rc = edge_passes(h, false, &fx)) return rc;
   if (int rc = run_forward_and_seed(h, h->batches[batch], false, lossVec_dev, h->lossbuf, fx)) return rc;
   float t[4];
   HIPCHK(hipMemcpyAsync(t, h->lossbuf, sizeof t, hipMemcpyDeviceToHost, h->stream));
@@ -1723,6 +1794,7 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   p.n_k = b.n_k; p.q = h->cfg.integ_num; p.td = h->cfg.time_dependent;
   p.Xb = bi_x(h, b); p.label = bi_y(h, b); p.nB = h->nB; p.bDof = h->bDof; p.biDimVal = h->biDimVal;
   p.Xf = h->fX; p.Nf = h->fN; p.fcoef = h->fcoef; p.flabel = h->flabel; p.nF = h->nF; p.fbiDimVal = h->fbiDimVal;
+  p.Xp = h->pX; p.Dp = h->pD; p.nP = h->nP; p.pgamma = h->pgamma; p.pbiDimVal = h->pbiDimVal;
   p.w[0] = h->w[0]; p.w[1] = h->w[1]; p.w[2] = h->w[2];
   p.react = b.react.on ? 1 : 0; p.rate = b.react.stream; std::copy(b.react.c, b.react.c + 3, p.coef);
   p.nlflux = b.nlflux.on ? 1 : 0; p.phi = b.nlflux.stream; std::copy(b.nlflux.c, b.nlflux.c + 3, p.fcoef3);

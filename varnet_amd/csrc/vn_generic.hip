@@ -8,6 +8,7 @@
 // :653-661 (weak-form integrand), :709 (parameter gradient).
 #include "vn_internal.h"
 #include "vn_flux.h"
+#include "vn_periodic.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -441,7 +442,7 @@ __global__ __launch_bounds__(64 * RED_GROUPS) void vn_reduce_kernel(const float*
                                                                   int P, const float* __restrict__ losspart,
                                                                   int nlp, long bDof, long nB, float w0, float w1,
                                                                   float w2, float* __restrict__ gradbuf, VnOptArgs opt,
-                                                                  VnFluxSum flux) {
+                                                                  VnFluxSum flux, VnFluxSum per) {
   __shared__ float sub[RED_GROUPS][64];
   const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
   const int p = blockIdx.x * 64 + lane;
@@ -455,6 +456,7 @@ __global__ __launch_bounds__(64 * RED_GROUPS) void vn_reduce_kernel(const float*
   if (p < P) {
     add_parts(partial, nparts, P, p, grp, acc);
     add_parts(flux.partial, flux.nparts, P, p, grp, acc);     // boundary-flux rows (none: nparts 0)
+    add_parts(per.partial, per.nparts, P, p, grp, acc);       // periodic pairs (none: nparts 0)
   }
   sub[grp][lane] = acc;
   __syncthreads();
@@ -526,10 +528,23 @@ __global__ __launch_bounds__(64 * RED_GROUPS) void vn_reduce_kernel(const float*
       }
       __syncthreads();
     }
+    // periodic pairs: wave 3, the same fold, the mean over their own count of pairs (block-uniform: per.nF is a kernel argument)
+    __shared__ double pmean;
+    if (per.nF > 0) {
+      if (grp == 3) {
+        double tp = 0.0;
+        for (int g = lane; g < per.nlp; g += 64) tp += (double)per.loss[g];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) tp += __shfl_down(tp, o, 64);
+        if (lane == 0) pmean = tp / (double)per.nF;
+      }
+      __syncthreads();
+    }
     if (grp == 1 && lane == 0) {
       const double var = t0;
       double bc = bDof > 0 ? t1 / (double)bDof : 0.0;                     // reduce_mean, TFModel.py:645
       if (flux.nF > 0) bc += fmean;                                       // + mean_F[biDimVal r^2] (vn_set_flux_bc)
+      if (per.nF > 0) bc += pmean;                                        // + mean_P[biDimVal (r0^2 + gamma r1^2)] (vn_set_periodic)
       const double ic = (nB - bDof) > 0 ? t2 / (double)(nB - bDof) : 0.0; // TFModel.py:648
       const float loss = (float)(w0 * bc + w1 * ic + w2 * var);           // TFModel.py:666
       gradbuf[P + 0] = loss;
@@ -628,11 +643,19 @@ hipError_t vn_seed_launch(const VnSeedArgs& a, int grid, hipStream_t s) {
 
 hipError_t vn_reduce_launch(const float* partial, int nparts, int P, const float* losspart, int nlossparts,
                             long bDof, long nB, float w0, float w1, float w2, float* gradbuf, hipStream_t s,
-                            VnOptArgs opt, const VnFluxSum& flux) {
+                            VnOptArgs opt, const VnEdgeSums& sums) {
   const int grid = (P + 63) / 64;
   hipLaunchKernelGGL(vn_reduce_kernel, dim3(grid > 0 ? grid : 1), dim3(64 * RED_GROUPS), 0, s, partial, nparts, P,
-                     losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, opt, flux);
+                     losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, opt, sums.flux, sums.per);
   return hipGetLastError();
+}
+
+hipError_t vn_reduce_launch(const float* partial, int nparts, int P, const float* losspart, int nlossparts,
+                            long bDof, long nB, float w0, float w1, float w2, float* gradbuf, hipStream_t s,
+                            VnOptArgs opt, const VnFluxSum& flux) {
+  VnEdgeSums sums;
+  sums.flux = flux;
+  return vn_reduce_launch(partial, nparts, P, losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, s, opt, sums);
 }
 
 hipError_t vn_reduce_launch(const float* partial, int nparts, int P, const float* losspart, int nlossparts,

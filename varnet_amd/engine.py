@@ -63,6 +63,7 @@ _SIGS = {
     'vn_set_bic': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double]),
     'vn_set_batch_bic': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'vn_set_flux_bc': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
+    'vn_set_periodic': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double]),
     'vn_set_reaction': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_nlflux': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_nldiff': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
@@ -442,6 +443,26 @@ class VNEngine:
         finally:
             del old           # the engine dropped the previous registration before checking this one
         self._keep['flux'] = (X, normal, coef, label)
+
+    def set_periodic(self, X=None, dir=None, gamma=1.0, biDimVal=1.0):
+        """Register (or, with X=None, clear) the periodic boundary pairs (vn_set_periodic): X [2 nP, inpDim] and unit directions
+        dir [2 nP, dim], rows i and i + nP being the two images of one point with the same direction; gamma >= 0 weights the
+        derivative match (0: values only)."""
+        if X is None or len(X) == 0:
+            self._keep['periodic'] = None
+            self._ck(self.lib.vn_set_periodic(self.h, None, None, 0, float(gamma), float(biDimVal)))
+            return
+        X, dir = self.dev(X), self.dev(dir)
+        rows = X.shape[0]
+        # the ABI carries pointers only: the lengths every kernel of the pass relies on are checked here
+        assert rows % 2 == 0, rows
+        assert X.shape == (rows, self.inpDim) and dir.shape == (rows, self.dim), (tuple(X.shape), tuple(dir.shape))
+        old = self._keep.pop('periodic', None)
+        try:
+            self._ck(self.lib.vn_set_periodic(self.h, _ptr(X), _ptr(dir), rows // 2, float(gamma), float(biDimVal)))
+        finally:
+            del old           # the engine dropped the previous registration before checking this one
+        self._keep['periodic'] = (X, dir)
 
     def _set_term(self, key, fn, takes, stream_name, batch, stream, coef, clears):
         """One of the three polynomial terms of `batch` (vn_terms.hip): coef normalised to three doubles; clears(c, stream) tells

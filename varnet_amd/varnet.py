@@ -293,6 +293,9 @@ class TrainResult:
                 L.append('\tBC%d: %s - vertices: %s\n' % (bi + 1, PDE.BCtype[bi], geom[bi]))
         for bInd, kind, rows in (varNet.fluxRows or {}).get('edges', []):
             L.append('\tBC%d: %s condition enforced as a boundary flux term on %d rows\n' % (bInd + 1, kind, rows))
+        for A, B, rows in (getattr(varNet, 'periodicRows', None) or {}).get('pairs', []):
+            L.append('\tBC%d and BC%d: periodic pair enforced on %d rows each, derivative weight %s\n'
+                     % (A + 1, B + 1, rows, repr(float(varNet.periodicDeriv))))
         L.append('\n')
         if getattr(PDE, 'reaction', None) is not None:
             L.append('Reaction term: rate*(c1 c + c2 c^2 + c3 c^3), coefficients %s\n\n' % str(list(PDE.reactionCoef)))
@@ -789,7 +792,7 @@ class VarNet:
     def __init__(self, PDE, layerWidth=[20], modelId='MLP', activationFun=None, discNum=20,
                  bDiscNum=[], tDiscNum=[], MORdiscScheme=None, processors=None, controller=None,
                  integPnum=2, optimizer='adam', learning_rate=0.001, fluxBC=False, lbfgsLoss64=False,
-                 causal=None, causalSlabs=None):
+                 causal=None, causalSlabs=None, periodicDeriv=None):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -841,6 +844,16 @@ class VarNet:
                                       'g/a per boundary point, shared by all batches, while a MOR problem needs per-batch labels '
                                       'and per-batch network inputs on them')
 
+        # periodicDeriv=gamma (extension; no reference counterpart): weight of the normal-derivative match of the periodic pairs
+        # of `PDE.periodic` against their value match; default 1, 0 matches values only
+        if periodicDeriv is not None:
+            if getattr(PDE, 'periodic', None) is None:
+                raise ValueError('periodicDeriv=%r is an option of a PDE with periodic boundaries (ADPDE(..., periodic=[(A, B)]))'
+                                 % (periodicDeriv,))
+            if not isinstance(periodicDeriv, (int, float, np.integer, np.floating)) or isinstance(periodicDeriv, bool) \
+                    or not np.isfinite(float(periodicDeriv)) or float(periodicDeriv) < 0.0:
+                raise ValueError('periodicDeriv=%r must be a finite number >= 0' % (periodicDeriv,))
+
         inpDim = dim + (1 if timeDependent else 0)
         if MORvar is not None:
             inpDim += int(np.sum(MORvar.varNum))
@@ -854,6 +867,9 @@ class VarNet:
         self.activationFun, self.optimizer, self.learning_rate = activationFun, optimizer, learning_rate
         self.processors, self.controller = processors, controller
         self.fluxBC, self.fluxRows = bool(fluxBC), None
+        self.periodicDeriv = (1.0 if periodicDeriv is None else float(periodicDeriv)) \
+            if getattr(PDE, 'periodic', None) is not None else None
+        self.periodicRows = None
         self.lbfgsLoss64 = bool(lbfgsLoss64)
         self.causal = None if causal is None else float(causal)
         self.causalSlabs = None if causalSlabs is None else int(causalSlabs)
@@ -883,6 +899,8 @@ class VarNet:
                       bDiscNum=bDiscNum, tDiscNum=tDiscNum, MORdiscScheme=MORdiscScheme, processors=list(processors),
                       controller=controller, integPnum=integPnum, optimizer=optimizer, learning_rate=learning_rate,
                       fluxBC=fluxBC, lbfgsLoss64=lbfgsLoss64, causal=causal, causalSlabs=causalSlabs)
+            if periodicDeriv is not None:
+                kw['periodicDeriv'] = periodicDeriv
             self._towers = TowerGroup(type(self), (PDE,), kw, list(processors))
             self.world = self._towers.world
             self.engine = self.tfData = None
@@ -926,6 +944,12 @@ class VarNet:
             r = self.fluxRows
             if r['X'].shape[0] > 0:
                 self.engine.set_flux_bc(r['X'], r['normal'], r['coef'], r['label'], fd.biDimVal)
+        if getattr(self.PDE, 'periodic', None) is not None:
+            # fixed for the whole run like the flux rows (optimal re-draws leave them on the uniform set): registered once; a
+            # network outside the kernels that run the periodic pass is refused here, with the engine's sentence
+            self.periodicRows = self.periodicTrainData()
+            r = self.periodicRows
+            self.engine.set_periodic(r['X'], r['dir'], self.periodicDeriv, fd.biDimVal)
         self.tfData = self.engine       # name kept for scripts that poke at `VarNet.tfData`
         from .launch import mark_stage
         mark_stage('engine_ready')      # past the launcher's bootstrap deadline: a rank that trains for hours is healthy
@@ -1214,7 +1238,7 @@ class VarNet:
         normals = np.asarray(domain.boundaryNormals(), dtype=float)
         X, nrm, coef, label, edges = [], [], [], [], []
         for bInd in range(domain.bIndNum):
-            if PDE.BCtype[bInd] == 'Dirichlet':
+            if PDE.BCtype[bInd] in ('Dirichlet', 'Periodic'):
                 continue
             a, b, g = PDE.BCs[bInd]
             x = np.asarray(uf.pairMats(mesh.bCoordinates[bInd], t_coord), dtype=float)
@@ -1228,6 +1252,40 @@ class VarNet:
         if not X:
             return dict(X=np.zeros([0, self.inpDim]), normal=np.zeros([0, dim]), coef=np.zeros(0), label=np.zeros(0), edges=[])
         return dict(X=np.vstack(X), normal=np.vstack(nrm), coef=np.concatenate(coef), label=np.concatenate(label), edges=edges)
+
+    def periodicTrainData(self):
+        """
+        (No reference counterpart: `ADPDE(..., periodic=[(A, B), ...])`.)  The paired rows of every periodic pair, assembled once
+        on the host in fp64.  Side A: the uniform boundary points `mesh.bCoordinates[A]` paired with the time nodes like the
+        Dirichlet rows.  Side B: the same rows with the space columns shifted by the translation s that maps edge A onto edge B,
+        taken from the vertices (polygon edges of a pair run in opposite senses: s = v_{B,next} - v_A; 1D: the other end minus
+        this one), not from the ordering of `mesh.bCoordinates[B]`.  Both sides carry A's outward unit normal as direction.
+        Returns dict(X, dir, pairs): X [2 nP, inpDim] with every pair's side-A rows first, then every pair's side-B rows in the
+        same order (row i pairs with row i + nP), dir [2 nP, dim], pairs = [(A, B, rows)].
+        """
+        PDE, dim = self.PDE, self.dim
+        td = PDE.timeDependent
+        domain = PDE.domain
+        t_coord = self.timeDisc()[1] if td else []
+        mesh = domain.getMesh(self.discNum, self.bDiscNum)
+        normals = np.asarray(domain.boundaryNormals(), dtype=float)
+        XA, XB, dirs, pairs = [], [], [], []
+        for A, B in PDE.periodic:
+            if dim == 1:
+                lim = np.reshape(np.asarray(domain.lim, dtype=float), -1)
+                s = np.array([lim[B] - lim[A]])
+            else:
+                g = np.asarray(domain.boundryGeom, dtype=float)
+                s = g[B, 1] - g[A, 0]
+            xa = np.array(uf.pairMats(mesh.bCoordinates[A], t_coord), dtype=float)
+            xb = xa.copy()
+            xb[:, :dim] += s
+            XA.append(xa)
+            XB.append(xb)
+            dirs.append(np.tile(normals[A], (xa.shape[0], 1)))
+            pairs.append((A, B, xa.shape[0]))
+        d = np.vstack(dirs)
+        return dict(X=np.vstack(XA + XB), dir=np.vstack([d, d]), pairs=pairs)
 
     def biTrainData(self, biInput, biDof, biArg=[]):
         """Labels g/beta on Dirichlet edges, IC(x) on the initial slice (VarNet.py:649-722)."""
