@@ -208,6 +208,33 @@ int vn_set_flux_bc(vn_engine* h, const float* X_dev, const float* normal_dev, co
  * replaces the previous registration, also when it fails (after an error there is none), and invalidates the L-BFGS (f_k, g_k)
  * and ring, like vn_set_flux_bc. */
 int vn_set_periodic(vn_engine* h, const float* X_dev, const float* dir_dev, int64_t nP, double gamma, double biDimVal);
+/* OPTIONAL, no reference counterpart: observations (sensor data), shared by all batches.  Observation i is a linear functional of
+ * the network over a segment of registered points, its measured value c_i and a weight wgt_i (1 / sigma_i^2):
+ *     l_i(u) = sum_{j in seg i} [ q_j u(x_j) + dir_j . grad_x u(x_j) ]      (grad_x: the dim space inputs)
+ *     r_i = l_i(u) - c_i,     O = (1/nO) sum_i wgt_i r_i^2,     loss = w0 BC + w1 IC + w2 var + lambda O
+ * Device pointers: X [n, d_in]; q [n] or NULL (all 1); dir [n, dim] or NULL (no derivative part: no tangent stream is computed and
+ * no derivative seed produced); rowptr [nO + 1] int32 or NULL (point sensors: segment i is the point i, n == nO); value [nO];
+ * wgt [nO] or NULL (all 1).  A point sensor is a segment of one point with q = 1; an averaged sensor carries quadrature weights q_j;
+ * a flux gauge has q = 0 and dir_j = the gauge direction times its coefficient.  nO == 0 clears.  BC, IC, var, lossVec and the
+ * gradient buffer's slots P+1..P+3 are untouched by the term; slot P+0 (the loss) gains lambda O, the gradient its derivative, and
+ * the unweighted O of the last evaluation (vn_grad, vn_train_step, vn_train_epoch, vn_eval_loss, vn_lbfgs_step, vn_objective_f64)
+ * is read with vn_get_obs_misfit.  The update fused into the reduction and a communicator's all-reduce see the term: ranks that
+ * register the same observations divide lambda by their number.  The pass runs on the generic kernels (forward along dir, the
+ * observations' seed kernel, reverse pass: three launches per step, beside the flux rows' and the periodic pairs') whatever route
+ * the interior term takes; networks outside VN_KMAX_* (the layer-by-layer route, 7-8 hidden layers, mixed activations) get
+ * VN_EUNSUPPORTED.  The registration is validated on the device (the call may synchronise): rowptr[0] == 0, rowptr strictly
+ * increasing (no empty segment), rowptr[nO] == n; value finite; wgt finite and >= 0; q and dir finite; else VN_EINVAL.  lambda
+ * negative or non-finite: VN_EINVAL.  Without a registration nothing is launched, nothing is allocated and every result is bit
+ * for bit what it is without this call.  The arrays are READ on every step: they must stay valid while registered.  A call
+ * replaces the previous registration, also when it fails (after an error there is none), and invalidates the L-BFGS (f_k, g_k)
+ * and ring, like vn_set_periodic. */
+int vn_set_observations(vn_engine* h, const float* X_dev, const float* q_dev, const float* dir_dev, const int32_t* rowptr_dev,
+                        const float* value_dev, const float* wgt_dev, int64_t n, int64_t nO, double lambda);
+/* The weight lambda of the observation term, without re-registering (negative or non-finite: VN_EINVAL).  A change invalidates
+ * the L-BFGS (f_k, g_k) and ring. */
+int vn_set_obs_weight(vn_engine* h, double lambda);
+/* The unweighted misfit O of the last evaluation (synchronises the engine's stream).  VN_ESTATE without a registration. */
+int vn_get_obs_misfit(vn_engine* h, double* misfit);
 /* OPTIONAL, no reference counterpart: a polynomial reaction term for `batch`,
  *     c_t = div(kappa grad c) - v.grad c + s + rate(x,t) p(c),     p(c) = c1 c + c2 c^2 + c3 c^3
  * (first-order decay, Fisher-KPP, Allen-Cahn-type reactions).  The term sits on the source side: the row integrand of the weak

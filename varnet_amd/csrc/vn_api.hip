@@ -4,6 +4,7 @@
 #include "vn_dedup.h"
 #include "vn_flux.h"
 #include "vn_periodic.h"
+#include "vn_obs.h"
 #include "vn_lbfgs.h"
 #include "vn_obj64.h"
 #include "vn_pgrad16.h"
@@ -207,6 +208,15 @@ struct vn_engine {
   int pgrid = 0;                                  // workgroups of the paired rows' reverse pass
   float *pu = nullptr, *pud = nullptr, *pubar = nullptr, *pudbar = nullptr, *ploss = nullptr, *ppartial = nullptr;
   long pu_cap = 0, pud_cap = 0, pubar_cap = 0, pudbar_cap = 0, ploss_cap = 0, ppartial_cap = 0;
+  // observations (vn_set_observations): caller-owned inputs (n points in nO segments), engine-owned work buffers; nO == 0: none
+  const float *oX = nullptr, *oQ = nullptr, *oD = nullptr, *oval = nullptr, *owgt = nullptr;
+  const int* orowptr = nullptr;
+  long on = 0, nO = 0;
+  double olambda = 0.0;
+  int ogrid = 0;                                  // workgroups of the observed points' reverse pass
+  float *ou = nullptr, *oud = nullptr, *oubar = nullptr, *oudbar = nullptr, *oloss = nullptr, *opartial = nullptr;
+  long ou_cap = 0, oud_cap = 0, oubar_cap = 0, oudbar_cap = 0, oloss_cap = 0, opartial_cap = 0;
+  double* omisfit = nullptr;                      // device slot: the unweighted misfit O of the last evaluation
   float* snap = nullptr;       // vn_state_snapshot: device copy of (theta | m | v), 3 P floats
   int64_t snap_step = -1;      // step counter at the snapshot (-1: none)
   PointRoute point_route = PointRoute::automatic;   // vn_debug_point_route(route & 3)
@@ -686,10 +696,38 @@ int periodic_pass(vn_engine* h, bool with_grad, VnFluxSum* px) {
   return VN_OK;
 }
 
-// Both boundary passes of a step, flux rows first: what its reduction adds.
+// Observations (vn_set_observations), on every route, the third pass of this kind: value and derivative g . grad_x u of the n
+// registered points, the residual of each observation's functional with its loss partial and the seeds of its points, and
+// with_grad the generic reverse pass into partials of their own -- launches of their own, so a step with flux rows or periodic
+// pairs only is untouched.  No directions registered: value stream only.
+int obs_pass(vn_engine* h, bool with_grad, VnObsSum* ox) {
+  *ox = VnObsSum();
+  if (h->nO <= 0) return VN_OK;
+  const bool deriv = h->oD != nullptr;
+  VnRows r{}, none{};
+  r.X = h->oX; r.G = h->oD; r.u = h->ou; r.ud = deriv ? h->oud : nullptr; r.n = h->on;
+  HIPCHK(vn_generic_forward(h->net, h->theta, r, none, h->fwd_grid, h->stream));
+  VnObsSeedArgs a{};
+  a.u = h->ou; a.ud = r.ud; a.q = h->oQ; a.rowptr = h->orowptr; a.value = h->oval; a.wgt = h->owgt;
+  a.nO = h->nO; a.lambda = (float)h->olambda;
+  a.ubar = with_grad ? h->oubar : nullptr; a.udbar = with_grad && deriv ? h->oudbar : nullptr;
+  a.part = h->oloss;
+  HIPCHK(vn_obs_seed_launch(a, h->stream));
+  if (with_grad) {
+    r.u = nullptr; r.ud = nullptr; r.ubar = h->oubar; r.udbar = a.udbar;
+    HIPCHK(vn_generic_backward(h->net, h->theta, r, none, h->opartial, h->ogrid, h->stream));
+    ox->sum.partial = h->opartial; ox->sum.nparts = h->ogrid;
+  }
+  ox->sum.loss = h->oloss; ox->sum.nlp = vn_obs_seed_blocks(h->nO); ox->sum.nF = h->nO;
+  ox->lambda = (float)h->olambda; ox->misfit = h->omisfit;
+  return VN_OK;
+}
+
+// The boundary passes of a step, flux rows first, and the observations' pass: what its reduction adds.
 int edge_passes(vn_engine* h, bool with_grad, VnEdgeSums* fx) {
   if (int rc = flux_pass(h, with_grad, &fx->flux)) return rc;
-  return periodic_pass(h, with_grad, &fx->per);
+  if (int rc = periodic_pass(h, with_grad, &fx->per)) return rc;
+  return obs_pass(h, with_grad, &fx->obs);
 }
 
 // Loss components and loss field of a batch that carries a de-duplication map (vn_set_dedup), without the row-wise forward: (u, grad u)
@@ -1045,6 +1083,7 @@ int vn_destroy(vn_engine* h) {
   void* ptrs[] = {h->theta, h->m, h->v, h->snap, h->theta64, h->gradbuf_int, h->lossbuf, h->partial, h->feN, h->fedNt,
                   h->feW, h->u, h->ud, h->ubar, h->udbar, h->ub, h->ubar_b, h->losspart, h->fused_losspart, h->stamps, h->dd_uv, h->dd_su, h->dd_sg, h->dd_partial,
                   h->dd_losspart, h->rx_seff, h->nd_A, h->wt_lvec, h->wt_omega, h->wt_stat, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial, h->pu, h->pud, h->pubar, h->pudbar, h->ploss, h->ppartial,
+                  h->ou, h->oud, h->oubar, h->oudbar, h->oloss, h->opartial, h->omisfit,
                   h->lb.ring, h->lb.theta_k, h->lb.g_k, h->lb.d, h->lb.part, h->lb.G, h->lb.coef, h->lb.meta};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -1513,6 +1552,75 @@ int vn_set_periodic(vn_engine* h, const float* X, const float* dir, int64_t nP, 
   return VN_OK;
 }
 
+int vn_set_observations(vn_engine* h, const float* X, const float* q, const float* dir, const int32_t* rowptr, const float* value,
+                        const float* wgt, int64_t n, int64_t nO, double lambda) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (n < 0 || nO < 0) return fail(VN_EINVAL, "negative number of observations or of observed points");
+  h->oX = h->oQ = h->oD = h->oval = h->owgt = nullptr;   // a call replaces the previous registration, also when it fails
+  h->orowptr = nullptr;
+  lbfgs_invalidate(h);
+  h->nO = h->on = 0;
+  if (nO == 0) return VN_OK;
+  if (!X || !value) return fail(VN_EINVAL, "null argument");
+  if (!(lambda >= 0.0) || !std::isfinite(lambda))
+    return fail(VN_EINVAL, "observations: the weight lambda = %g must be finite and >= 0", lambda);
+  if (n > 0x7fffffffL) return fail(VN_EINVAL, "observations: %lld points exceed the 32-bit row pointers", (long long)n);
+  if (!rowptr && n != nO)
+    return fail(VN_EINVAL, "observations: point sensors (rowptr == NULL) have one point each, but n = %lld and nO = %lld",
+                (long long)n, (long long)nO);
+  if (n < nO) return fail(VN_EINVAL, "observations: %lld points cannot fill %lld non-empty segments", (long long)n, (long long)nO);
+  // the observations' pass runs on the generic kernels, whatever route the interior term takes
+  if (h->route == Route::layered || !vn_net_in_kernel_range(h->net))
+    return fail(VN_EUNSUPPORTED, "observations need a network of the hand-written kernels (<= %d hidden layers, width <= %d, "
+                "<= %d inputs, one activation); this one (%d layers, widest %d, %d inputs%s) runs on the layer-by-layer route "
+                "or the deep fused kernel only", VN_KMAX_LAYERS, VN_KMAX_WIDTH, VN_KMAX_DIN, h->net.L, h->net.hmax, h->net.d_in,
+                h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // rowptr indexes device memory in the seed kernel: validated once, here (a registration call may synchronise), so that an
+  // inconsistent registration is an error code and never a GPU fault.  The reads assume nO + 1 entries of rowptr.
+  int bad = 0;
+  auto check = [&](int* err_dev) { return vn_obs_check_launch(q, dir, rowptr, value, wgt, n, nO, h->cfg.dim, err_dev, h->stream); };
+  if (int rc = count_on_device(h, check, &bad)) return rc;
+  if (bad)
+    return fail(VN_EINVAL, "inconsistent observations: %d violation(s) (need rowptr[0] = 0 < rowptr[1] < ... < rowptr[nO] = n, no empty "
+                           "segment; value finite; wgt finite and >= 0; q and dir finite)", bad);
+  const long tiles = (n + 31) / 32;
+  const int ogrid = (int)(tiles < h->ncu ? tiles : h->ncu);
+  if (int rc = ensure(&h->ou, &h->ou_cap, n)) return rc;
+  if (int rc = ensure(&h->oubar, &h->oubar_cap, n)) return rc;
+  if (dir) {                                          // no directions: no tangent stream, no derivative seed
+    if (int rc = ensure(&h->oud, &h->oud_cap, n)) return rc;
+    if (int rc = ensure(&h->oudbar, &h->oudbar_cap, n)) return rc;
+  }
+  if (int rc = ensure(&h->oloss, &h->oloss_cap, vn_obs_seed_blocks(nO))) return rc;
+  if (int rc = ensure(&h->opartial, &h->opartial_cap, (long)ogrid * h->net.P)) return rc;
+  if (!h->omisfit) {
+    HIPCHK(hipMalloc((void**)&h->omisfit, sizeof(double)));
+    HIPCHK(hipMemsetAsync(h->omisfit, 0, sizeof(double), h->stream));
+  }
+  h->oX = X; h->oQ = q; h->oD = dir; h->orowptr = rowptr; h->oval = value; h->owgt = wgt;
+  h->on = n; h->nO = nO; h->olambda = lambda; h->ogrid = ogrid;
+  return VN_OK;
+}
+
+int vn_set_obs_weight(vn_engine* h, double lambda) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (!(lambda >= 0.0) || !std::isfinite(lambda))
+    return fail(VN_EINVAL, "observations: the weight lambda = %g must be finite and >= 0", lambda);
+  if (lambda != h->olambda) lbfgs_invalidate(h);     // another objective: (f_k, g_k) and the ring are stale
+  h->olambda = lambda;
+  return VN_OK;
+}
+
+int vn_get_obs_misfit(vn_engine* h, double* misfit) {
+  if (!h || !misfit) return fail(VN_EINVAL, "null argument");
+  if (h->nO <= 0) return fail(VN_ESTATE, "vn_get_obs_misfit: no observations are registered (vn_set_observations)");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipMemcpyAsync(misfit, h->omisfit, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return VN_OK;
+}
+
 int vn_set_batch_bic(vn_engine* h, int32_t batch, const float* biInput, const float* biLabel) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
@@ -1795,6 +1903,8 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   p.Xb = bi_x(h, b); p.label = bi_y(h, b); p.nB = h->nB; p.bDof = h->bDof; p.biDimVal = h->biDimVal;
   p.Xf = h->fX; p.Nf = h->fN; p.fcoef = h->fcoef; p.flabel = h->flabel; p.nF = h->nF; p.fbiDimVal = h->fbiDimVal;
   p.Xp = h->pX; p.Dp = h->pD; p.nP = h->nP; p.pgamma = h->pgamma; p.pbiDimVal = h->pbiDimVal;
+  p.Xo = h->oX; p.Qo = h->oQ; p.Do = h->oD; p.orowptr = h->orowptr; p.ovalue = h->oval; p.owgt = h->owgt;
+  p.on = h->on; p.nO = h->nO; p.olambda = h->olambda; p.omisfit = h->omisfit;
   p.w[0] = h->w[0]; p.w[1] = h->w[1]; p.w[2] = h->w[2];
   p.react = b.react.on ? 1 : 0; p.rate = b.react.stream; std::copy(b.react.c, b.react.c + 3, p.coef);
   p.nlflux = b.nlflux.on ? 1 : 0; p.phi = b.nlflux.stream; std::copy(b.nlflux.c, b.nlflux.c + 3, p.fcoef3);

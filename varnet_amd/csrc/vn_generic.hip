@@ -442,7 +442,8 @@ __global__ __launch_bounds__(64 * RED_GROUPS) void vn_reduce_kernel(const float*
                                                                   int P, const float* __restrict__ losspart,
                                                                   int nlp, long bDof, long nB, float w0, float w1,
                                                                   float w2, float* __restrict__ gradbuf, VnOptArgs opt,
-                                                                  VnFluxSum flux, VnFluxSum per) {
+                                                                  VnFluxSum flux, VnFluxSum per, VnFluxSum obs,
+                                                                  float olambda, double* __restrict__ omisfit) {
   __shared__ float sub[RED_GROUPS][64];
   const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
   const int p = blockIdx.x * 64 + lane;
@@ -457,6 +458,7 @@ __global__ __launch_bounds__(64 * RED_GROUPS) void vn_reduce_kernel(const float*
     add_parts(partial, nparts, P, p, grp, acc);
     add_parts(flux.partial, flux.nparts, P, p, grp, acc);     // boundary-flux rows (none: nparts 0)
     add_parts(per.partial, per.nparts, P, p, grp, acc);       // periodic pairs (none: nparts 0)
+    add_parts(obs.partial, obs.nparts, P, p, grp, acc);       // observations (none: nparts 0)
   }
   sub[grp][lane] = acc;
   __syncthreads();
@@ -540,13 +542,30 @@ __global__ __launch_bounds__(64 * RED_GROUPS) void vn_reduce_kernel(const float*
       }
       __syncthreads();
     }
+    // observations: wave 4, the same fold, the unweighted misfit O = sum / nO (block-uniform: obs.nF is a kernel argument)
+    __shared__ double omean;
+    if (obs.nF > 0) {
+      if (grp == 4) {
+        double to = 0.0;
+        for (int g = lane; g < obs.nlp; g += 64) to += (double)obs.loss[g];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) to += __shfl_down(to, o, 64);
+        if (lane == 0) omean = to / (double)obs.nF;
+      }
+      __syncthreads();
+    }
     if (grp == 1 && lane == 0) {
       const double var = t0;
       double bc = bDof > 0 ? t1 / (double)bDof : 0.0;                     // reduce_mean, TFModel.py:645
       if (flux.nF > 0) bc += fmean;                                       // + mean_F[biDimVal r^2] (vn_set_flux_bc)
       if (per.nF > 0) bc += pmean;                                        // + mean_P[biDimVal (r0^2 + gamma r1^2)] (vn_set_periodic)
       const double ic = (nB - bDof) > 0 ? t2 / (double)(nB - bDof) : 0.0; // TFModel.py:648
-      const float loss = (float)(w0 * bc + w1 * ic + w2 * var);           // TFModel.py:666
+      double l64 = w0 * bc + w1 * ic + w2 * var;                          // TFModel.py:666
+      if (obs.nF > 0) {                                                   // + lambda O (vn_set_observations)
+        l64 += (double)olambda * omean;
+        *omisfit = omean;
+      }
+      const float loss = (float)l64;
       gradbuf[P + 0] = loss;
       if (opt.loss_acc) opt.loss_acc[0] += loss;
       gradbuf[P + 1] = (float)bc;
@@ -646,7 +665,8 @@ hipError_t vn_reduce_launch(const float* partial, int nparts, int P, const float
                             VnOptArgs opt, const VnEdgeSums& sums) {
   const int grid = (P + 63) / 64;
   hipLaunchKernelGGL(vn_reduce_kernel, dim3(grid > 0 ? grid : 1), dim3(64 * RED_GROUPS), 0, s, partial, nparts, P,
-                     losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, opt, sums.flux, sums.per);
+                     losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, opt, sums.flux, sums.per, sums.obs.sum,
+                     sums.obs.lambda, sums.obs.misfit);
   return hipGetLastError();
 }
 

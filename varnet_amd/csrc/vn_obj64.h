@@ -11,7 +11,7 @@ struct VnObj64Work {
   double* ud = nullptr;    long ud_cap = 0;      // [rows]: directional derivatives, then the tangent seeds in place
   double* act = nullptr;   long act_cap = 0;     // [waves][L][2][16][64]: a wave's activations of its current chunk
   double* part = nullptr;  long part_cap = 0;    // [waves][gradient image]
-  double* lpart = nullptr; long lpart_cap = 0;   // [seed blocks][4]: var, bc, ic, flux partial sums; then [seed blocks]: periodic pairs
+  double* lpart = nullptr; long lpart_cap = 0;   // [seed blocks][4]: var, bc, ic, flux partial sums; then [seed blocks]: periodic pairs; then [seed blocks]: observations
   double* out = nullptr;                         // [4] loss, BC, IC, var
   // per-test-function loss weights (vn_weights.hip), allocated by the first evaluation of a batch that has them
   double* lvec = nullptr;  long lvec_cap = 0;    // [n_k] the loss field when the caller passes none
@@ -34,6 +34,10 @@ struct VnObj64Problem {
   const float* Xf; const float* Nf; const float* fcoef; const float* flabel; long nF; double fbiDimVal;
   // periodic pairs (vn_set_periodic): rows i and i + nP pair, Dp the common direction (nullptr with pgamma == 0); nP == 0: none
   const float* Xp; const float* Dp; long nP; double pgamma, pbiDimVal;
+  // observations (vn_set_observations): on points in nO segments (orowptr nullptr: one point each); Qo, Do, owgt may be nullptr;
+  // omisfit: device slot of the unweighted misfit; nO == 0: none
+  const float* Xo; const float* Qo; const float* Do; const int* orowptr; const float* ovalue; const float* owgt;
+  long on, nO; double olambda; double* omisfit;
   double w[3];
   // reaction term of the batch (vn_set_reaction): rate [n_k*q] or nullptr (1), coef c1..c3; react == 0: none
   int react; const float* rate; double coef[3];

@@ -1,4 +1,4 @@
-// vn_objective_f64: the weak-form training objective of a batch -- interior rows, BC/IC rows, boundary-flux rows, periodic pairs, exactly what
+// vn_objective_f64: the weak-form training objective of a batch -- interior rows, BC/IC rows, boundary-flux rows, periodic pairs, observed points, exactly what
 // vn_grad / vn_eval_loss define -- and its gradient, with every operation after the exact widening of the registered fp32 arrays
 // in double precision and every product of a layer on the fp64 matrix pipe (v_mfma_f64_16x16x4_f64).  A checking path in the
 // plain style of vn_taylor16d.hip (see its header for the instruction's row interleave: register i of lane group g holds row
@@ -57,7 +57,7 @@ struct Seg {
 struct ObjArgs {
   VnNet net;
   const double* img;
-  Seg seg[4];          // interior, BC/IC, flux, periodic pairs (side A rows, then side B rows)
+  Seg seg[5];          // interior, BC/IC, flux, periodic pairs (side A rows, then side B rows), observed points
   double* u; double* ud;
   double* act; double* part;
 };
@@ -118,16 +118,16 @@ __global__ __launch_bounds__(OT) void vn_obj64_kernel(ObjArgs A) {
   double* part = REV ? A.part + wg * (long)GImg::total(L) : nullptr;
   double* zs = zs_all + (REV ? wave * LAYER : 0);
   const long c0 = (A.seg[0].n + CW - 1) / CW, c1 = c0 + (A.seg[1].n + CW - 1) / CW, c2 = c1 + (A.seg[2].n + CW - 1) / CW;
-  const long c3 = c2 + (A.seg[3].n + CW - 1) / CW;
+  const long c3 = c2 + (A.seg[3].n + CW - 1) / CW, c4 = c3 + (A.seg[4].n + CW - 1) / CW;
   const int d_in = net.d_in, dim = net.dim;
 
-  for (long chunk = wg; chunk < c3; chunk += nwaves) {
-    const int si = chunk < c0 ? 0 : chunk < c1 ? 1 : chunk < c2 ? 2 : 3;
-    const float* X = si == 0 ? A.seg[0].X : si == 1 ? A.seg[1].X : si == 2 ? A.seg[2].X : A.seg[3].X;
-    const float* G = si == 0 ? A.seg[0].G : si == 1 ? A.seg[1].G : si == 2 ? A.seg[2].G : A.seg[3].G;
-    const long n = si == 0 ? A.seg[0].n : si == 1 ? A.seg[1].n : si == 2 ? A.seg[2].n : A.seg[3].n;
-    const long off = si == 0 ? A.seg[0].off : si == 1 ? A.seg[1].off : si == 2 ? A.seg[2].off : A.seg[3].off;
-    const long base = (chunk - (si == 0 ? 0 : si == 1 ? c0 : si == 2 ? c1 : c2)) * CW;
+  for (long chunk = wg; chunk < c4; chunk += nwaves) {
+    const int si = chunk < c0 ? 0 : chunk < c1 ? 1 : chunk < c2 ? 2 : chunk < c3 ? 3 : 4;
+    const float* X = si == 0 ? A.seg[0].X : si == 1 ? A.seg[1].X : si == 2 ? A.seg[2].X : si == 3 ? A.seg[3].X : A.seg[4].X;
+    const float* G = si == 0 ? A.seg[0].G : si == 1 ? A.seg[1].G : si == 2 ? A.seg[2].G : si == 3 ? A.seg[3].G : A.seg[4].G;
+    const long n = si == 0 ? A.seg[0].n : si == 1 ? A.seg[1].n : si == 2 ? A.seg[2].n : si == 3 ? A.seg[3].n : A.seg[4].n;
+    const long off = si == 0 ? A.seg[0].off : si == 1 ? A.seg[1].off : si == 2 ? A.seg[2].off : si == 3 ? A.seg[3].off : A.seg[4].off;
+    const long base = (chunk - (si == 0 ? 0 : si == 1 ? c0 : si == 2 ? c1 : si == 3 ? c2 : c3)) * CW;
     const long row = base + c;
     const bool valid = row < n;
     const bool tangent = G != nullptr;                     // wave-uniform
@@ -335,14 +335,16 @@ __global__ __launch_bounds__(OT) void vn_obj64_kernel(ObjArgs A) {
 
 // ---- weak-form epilogue in double: the arithmetic of vn_seed_kernel / vn_flux_seed_kernel (vn_generic.hip) ----------------
 struct SeedArgs {
-  double* u; double* ud;                      // interior rows at 0, BC/IC rows at offB, flux rows at offF, periodic rows at offP
-  long offB, offF, offP;
+  double* u; double* ud;                      // interior rows at 0, BC/IC rows at offB, flux rows at offF, periodic rows at offP, observed points at offO
+  long offB, offF, offP, offO;
   const float* source; const float* feN; const float* fedNt; const float* feW;
   const float* Nrow; const float* dNtrow; const float* detJv; double detJ;
   long n_k; int q; int td;
   const float* label; long nB, bDof; double biDimVal;
   const float* fcoef; const float* flabel; long nF; double fbiDimVal;
   long nP; double pgamma, pbiDimVal; double* ppart;   // periodic pairs (i, i + nP); ppart [gridDim.x]
+  // observations: segment k = points [orowptr[k], orowptr[k+1]) (nullptr: point k); oq, owgt nullptr: 1; odir: ud is live
+  const float* oq; const int* orowptr; const float* ovalue; const float* owgt; long nO; int odir; double olambda; double* opart;
   double w0, w1, w2;
   int seeds;                                  // write the adjoint seeds in place of (u, ud)
   int react; const float* rate; double c1, c2, c3;   // reaction rate p(u), p = c1 u + c2 u^2 + c3 u^3 (react == 0: none)
@@ -363,7 +365,7 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {
 __global__ __launch_bounds__(256) void vn_obj64_seed_kernel(SeedArgs a) {
   __shared__ double red[4];
   const long k = (long)blockIdx.x * 256 + threadIdx.x;
-  double lv = 0.0, bc = 0.0, ic = 0.0, fl = 0.0, pe = 0.0;
+  double lv = 0.0, bc = 0.0, ic = 0.0, fl = 0.0, pe = 0.0, oe = 0.0;
   if (k < a.n_k) {
     const int q = a.q;
     const long base = k * q;
@@ -452,6 +454,25 @@ __global__ __launch_bounds__(256) void vn_obj64_seed_kernel(SeedArgs a) {
       a.ud[i] = s * a.pgamma * r1; a.ud[j] = -s * a.pgamma * r1;
     }
   }
+  if (k < a.nO) {                                 // the arithmetic of vn_obs_seed_kernel (vn_obs.hip), additions in CSR order
+    const long e0 = a.orowptr ? (long)a.orowptr[k] : k, e1 = a.orowptr ? (long)a.orowptr[k + 1] : k + 1;
+    double acc = 0.0;
+    for (long e = e0; e < e1; ++e) {
+      double t = a.oq ? (double)a.oq[e] * a.u[a.offO + e] : a.u[a.offO + e];
+      if (a.odir) t += a.ud[a.offO + e];
+      acc += t;
+    }
+    const double wk = a.owgt ? (double)a.owgt[k] : 1.0;
+    const double r = acc - (double)a.ovalue[k];
+    oe = wk * r * r;
+    if (a.seeds) {
+      const double s = 2.0 * a.olambda * wk * r / (double)a.nO;
+      for (long e = e0; e < e1; ++e) {
+        a.u[a.offO + e] = a.oq ? s * (double)a.oq[e] : s;
+        if (a.odir) a.ud[a.offO + e] = s;
+      }
+    }
+  }
   const double s0 = block_sum_d(lv, red);
   const double s1 = block_sum_d(bc, red);
   const double s2 = block_sum_d(ic, red);
@@ -464,11 +485,17 @@ __global__ __launch_bounds__(256) void vn_obj64_seed_kernel(SeedArgs a) {
     const double s4 = block_sum_d(pe, red);
     if (threadIdx.x == 0) a.ppart[blockIdx.x] = s4;
   }
+  if (a.nO > 0) {                                 // (block-uniform)
+    const double s5 = block_sum_d(oe, red);
+    if (threadIdx.x == 0) a.opart[blockIdx.x] = s5;
+  }
 }
 
 // loss scalars: one wave, lane-strided over the seed blocks, then a fixed shuffle tree
 __global__ __launch_bounds__(64) void vn_obj64_loss_kernel(const double* __restrict__ lpart, int nblk, long bDof, long nB, long nF,
-                                                          const double* __restrict__ ppart, long nP, double w0, double w1, double w2, double* __restrict__ out) {
+                                                          const double* __restrict__ ppart, long nP, const double* __restrict__ opart, long nO,
+                                                          double olambda, double* __restrict__ omisfit, double w0, double w1, double w2,
+                                                          double* __restrict__ out) {
   const int lane = threadIdx.x;
   double t[4] = {0.0, 0.0, 0.0, 0.0};
   for (int b = lane; b < nblk; b += 64)
@@ -480,13 +507,24 @@ __global__ __launch_bounds__(64) void vn_obj64_loss_kernel(const double* __restr
     for (int b = lane; b < nblk; b += 64) tp += ppart[b];
     for (int o = 32; o > 0; o >>= 1) tp += __shfl_down(tp, o, 64);
   }
+  double to = 0.0;                                // observations: the same fold over their own partials
+  if (nO > 0) {
+    for (int b = lane; b < nblk; b += 64) to += opart[b];
+    for (int o = 32; o > 0; o >>= 1) to += __shfl_down(to, o, 64);
+  }
   if (lane == 0) {
     const double var = t[0];
     double bc = bDof > 0 ? t[1] / (double)bDof : 0.0;
     if (nF > 0) bc += t[3] / (double)nF;
     if (nP > 0) bc += tp / (double)nP;
     const double ic = (nB - bDof) > 0 ? t[2] / (double)(nB - bDof) : 0.0;
-    out[0] = w0 * bc + w1 * ic + w2 * var;
+    double loss = w0 * bc + w1 * ic + w2 * var;
+    if (nO > 0) {
+      const double O = to / (double)nO;
+      loss += olambda * O;
+      *omisfit = O;
+    }
+    out[0] = loss;
     out[1] = bc; out[2] = ic; out[3] = var;
   }
 }
@@ -560,17 +598,18 @@ hipError_t vn_obj64_run(VnObj64Work& w, const VnObj64Problem& p, double* grad_de
   if (!vn_obj64_supported(p.net)) return hipErrorInvalidValue;
   const VnNet& net = p.net;
   const int L = net.L;
-  const long n0 = p.n_k * p.q, nB = p.nB, nF = p.nF, nP = p.nP, nP2 = 2 * p.nP;
-  const long rows = n0 + nB + nF + nP2;
-  const long chunks = (n0 + CW - 1) / CW + (nB + CW - 1) / CW + (nF + CW - 1) / CW + (nP2 + CW - 1) / CW;
+  const long n0 = p.n_k * p.q, nB = p.nB, nF = p.nF, nP = p.nP, nP2 = 2 * p.nP, nO = p.nO, on = nO > 0 ? p.on : 0;
+  const long rows = n0 + nB + nF + nP2 + on;
+  const long chunks = (n0 + CW - 1) / CW + (nB + CW - 1) / CW + (nF + CW - 1) / CW + (nP2 + CW - 1) / CW + (on + CW - 1) / CW;
   OCHK(ensure_d(&w.img, &w.img_cap, WImg::total(L)));
   OCHK(ensure_d(&w.u, &w.u_cap, rows > 0 ? rows : 1));
   OCHK(ensure_d(&w.ud, &w.ud_cap, rows > 0 ? rows : 1));
   if (!w.out) OCHK(hipMalloc((void**)&w.out, 4 * sizeof(double)));
   long most = p.n_k > nB ? (p.n_k > nF ? p.n_k : nF) : (nB > nF ? nB : nF);
   if (nP > most) most = nP;
+  if (nO > most) most = nO;
   const int sblk = (int)(((most > 0 ? most : 1) + 255) / 256);
-  OCHK(ensure_d(&w.lpart, &w.lpart_cap, (long)sblk * (nP > 0 ? 5 : 4)));
+  OCHK(ensure_d(&w.lpart, &w.lpart_cap, (long)sblk * (4 + (nP > 0 ? 1 : 0) + (nO > 0 ? 1 : 0))));
 
   hipLaunchKernelGGL(vn_obj64_pack_kernel, dim3((WImg::total(L) + 255) / 256), dim3(256), 0, s, net, p.theta, w.img);
   OCHK(hipGetLastError());
@@ -581,6 +620,7 @@ hipError_t vn_obj64_run(VnObj64Work& w, const VnObj64Problem& p, double* grad_de
   a.seg[1] = Seg{p.Xb, nullptr, nB, n0};
   a.seg[2] = Seg{p.Xf, p.Nf, nF, n0 + nB};
   a.seg[3] = Seg{p.Xp, p.pgamma > 0.0 ? p.Dp : nullptr, nP2, n0 + nB + nF};
+  a.seg[4] = Seg{p.Xo, p.Do, on, n0 + nB + nF + nP2};
   const bool tanh_ = net.act == VN_ACT_TANH;
   const long wgs = (chunks + OW - 1) / OW;
   if (chunks > 0) {
@@ -597,6 +637,8 @@ hipError_t vn_obj64_run(VnObj64Work& w, const VnObj64Problem& p, double* grad_de
   sa.label = p.label; sa.nB = nB; sa.bDof = p.bDof; sa.biDimVal = p.biDimVal;
   sa.fcoef = p.fcoef; sa.flabel = p.flabel; sa.nF = nF; sa.fbiDimVal = p.fbiDimVal;
   sa.offP = n0 + nB + nF; sa.nP = nP; sa.pgamma = p.pgamma; sa.pbiDimVal = p.pbiDimVal; sa.ppart = w.lpart + (long)sblk * 4;
+  sa.offO = n0 + nB + nF + nP2; sa.nO = nO; sa.oq = p.Qo; sa.orowptr = p.orowptr; sa.ovalue = p.ovalue; sa.owgt = p.owgt;
+  sa.odir = p.Do ? 1 : 0; sa.olambda = p.olambda; sa.opart = w.lpart + (long)sblk * (nP > 0 ? 5 : 4);
   sa.w0 = p.w[0]; sa.w1 = p.w[1]; sa.w2 = p.w[2];
   sa.seeds = grad_dev ? 1 : 0;
   sa.react = p.react; sa.rate = p.rate; sa.c1 = p.coef[0]; sa.c2 = p.coef[1]; sa.c3 = p.coef[2];
@@ -618,7 +660,8 @@ hipError_t vn_obj64_run(VnObj64Work& w, const VnObj64Problem& p, double* grad_de
     OCHK(vn_weights_apply_f64(p.wt, wk, sa.lossVec, p.n_k, w.omega, w.lpart, s));    // var partials weighted, lossVec as it is
     if (grad_dev) OCHK(vn_weights_rows_f64(w.omega, p.n_k, p.q, w.u, w.ud, s));       // the interior seeds in u / ud scaled
   }
-  hipLaunchKernelGGL(vn_obj64_loss_kernel, dim3(1), dim3(64), 0, s, w.lpart, sblk, p.bDof, nB, nF, sa.ppart, nP, p.w[0], p.w[1], p.w[2], w.out);
+  hipLaunchKernelGGL(vn_obj64_loss_kernel, dim3(1), dim3(64), 0, s, w.lpart, sblk, p.bDof, nB, nF, sa.ppart, nP, sa.opart, nO, p.olambda, p.omisfit,
+                     p.w[0], p.w[1], p.w[2], w.out);
   OCHK(hipGetLastError());
 
   if (grad_dev) {

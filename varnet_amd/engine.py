@@ -64,6 +64,10 @@ _SIGS = {
     'vn_set_batch_bic': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'vn_set_flux_bc': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
     'vn_set_periodic': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double]),
+    'vn_set_observations': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.c_int64, C.c_double]),
+    'vn_set_obs_weight': (C.c_int, [C.c_void_p, C.c_double]),
+    'vn_get_obs_misfit': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_reaction': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_nlflux': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_nldiff': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
@@ -463,6 +467,48 @@ class VNEngine:
         finally:
             del old           # the engine dropped the previous registration before checking this one
         self._keep['periodic'] = (X, dir)
+
+    def set_observations(self, X=None, value=None, q=None, dir=None, rowptr=None, wgt=None, weight=1.0):
+        """Register (or, with X=None, clear) the observations (vn_set_observations): points X [n, inpDim] in nO segments
+        rowptr [nO + 1] (None: point sensors, one point each), measured values value [nO], optional quadrature weights q [n]
+        (None: 1), directions dir [n, dim] of a derivative part (None: values only) and weights wgt [nO] = 1 / sigma^2 (None: 1);
+        weight = lambda, the factor of the misfit O = mean_i[wgt_i r_i^2] in the loss."""
+        t = self.torch
+        if X is None or len(X) == 0:
+            self._keep['obs'] = None
+            self._ck(self.lib.vn_set_observations(self.h, None, None, None, None, None, None, 0, 0, float(weight)))
+            return
+        X, value = self.dev(X), self.dev(value).reshape(-1)
+        n, nO = X.shape[0], value.shape[0]
+        q = None if q is None else self.dev(q).reshape(-1)
+        dir = None if dir is None else self.dev(dir)
+        wgt = None if wgt is None else self.dev(wgt).reshape(-1)
+        if rowptr is not None:
+            rowptr = (rowptr if isinstance(rowptr, t.Tensor) else t.as_tensor(np.ascontiguousarray(rowptr))).to(
+                device=self.device, dtype=t.int32).contiguous()
+        # the ABI carries pointers only: the lengths the validator and every kernel of the pass rely on are checked here
+        assert X.shape == (n, self.inpDim), tuple(X.shape)
+        assert q is None or q.shape[0] == n, (tuple(q.shape), n)
+        assert dir is None or dir.shape == (n, self.dim), (tuple(dir.shape), n)
+        assert wgt is None or wgt.shape[0] == nO, (tuple(wgt.shape), nO)
+        assert (rowptr.numel() == nO + 1) if rowptr is not None else (n == nO), (n, nO)
+        old = self._keep.pop('obs', None)
+        try:
+            self._ck(self.lib.vn_set_observations(self.h, _ptr(X), _ptr(q), _ptr(dir), _ptr(rowptr), _ptr(value), _ptr(wgt), n, nO,
+                                                  float(weight)))
+        finally:
+            del old           # the engine dropped the previous registration before checking this one
+        self._keep['obs'] = (X, q, dir, rowptr, value, wgt)
+
+    def set_obs_weight(self, weight):
+        """lambda of the observation term, without re-registering (vn_set_obs_weight)."""
+        self._ck(self.lib.vn_set_obs_weight(self.h, float(weight)))
+
+    def obs_misfit(self):
+        """The unweighted misfit O = mean_i[wgt_i r_i^2] of the last evaluation (grad, train_step, eval_loss, objective64, ...)."""
+        out = C.c_double(0.0)
+        self._ck(self.lib.vn_get_obs_misfit(self.h, C.byref(out)))
+        return float(out.value)
 
     def _set_term(self, key, fn, takes, stream_name, batch, stream, coef, clears):
         """One of the three polynomial terms of `batch` (vn_terms.hip): coef normalised to three doubles; clears(c, stream) tells

@@ -293,6 +293,10 @@ class TrainResult:
                 L.append('\tBC%d: %s - vertices: %s\n' % (bi + 1, PDE.BCtype[bi], geom[bi]))
         for bInd, kind, rows in (varNet.fluxRows or {}).get('edges', []):
             L.append('\tBC%d: %s condition enforced as a boundary flux term on %d rows\n' % (bInd + 1, kind, rows))
+        if getattr(varNet, 'obsRows', None) is not None:
+            r = varNet.obsRows
+            L.append('\tObservations: %d (%d points%s), weight %s\n'
+                     % (len(r['value']), len(r['X']), '' if r['dir'] is None else ', with a derivative part', repr(float(varNet.obsWeight))))
         for A, B, rows in (getattr(varNet, 'periodicRows', None) or {}).get('pairs', []):
             L.append('\tBC%d and BC%d: periodic pair enforced on %d rows each, derivative weight %s\n'
                      % (A + 1, B + 1, rows, repr(float(varNet.periodicDeriv))))
@@ -792,7 +796,7 @@ class VarNet:
     def __init__(self, PDE, layerWidth=[20], modelId='MLP', activationFun=None, discNum=20,
                  bDiscNum=[], tDiscNum=[], MORdiscScheme=None, processors=None, controller=None,
                  integPnum=2, optimizer='adam', learning_rate=0.001, fluxBC=False, lbfgsLoss64=False,
-                 causal=None, causalSlabs=None, periodicDeriv=None):
+                 causal=None, causalSlabs=None, periodicDeriv=None, observations=None, obsWeight=None):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -854,6 +858,17 @@ class VarNet:
                     or not np.isfinite(float(periodicDeriv)) or float(periodicDeriv) < 0.0:
                 raise ValueError('periodicDeriv=%r must be a finite number >= 0' % (periodicDeriv,))
 
+        # observations=... (extension; no reference counterpart): sensor data as linear functionals of the solution, fitted by a
+        # misfit term obsWeight * O next to the PDE's loss (`obsData`)
+        if observations is None:
+            if obsWeight is not None:
+                raise ValueError('obsWeight=%r is an option of observations=...' % (obsWeight,))
+        else:
+            if MORvar is not None:
+                raise NotImplementedError('observations with model-order reduction are not supported: the observed points are '
+                                          'assembled once, for all parameter batches, and carry no parameter inputs')
+            self._check_obs_weight(1.0 if obsWeight is None else obsWeight)
+
         inpDim = dim + (1 if timeDependent else 0)
         if MORvar is not None:
             inpDim += int(np.sum(MORvar.varNum))
@@ -870,6 +885,9 @@ class VarNet:
         self.periodicDeriv = (1.0 if periodicDeriv is None else float(periodicDeriv)) \
             if getattr(PDE, 'periodic', None) is not None else None
         self.periodicRows = None
+        self.obsRows = None if observations is None else self.obsData(observations, dim, inpDim)
+        self.obsWeight = None if observations is None else (1.0 if obsWeight is None else float(obsWeight))
+        self._obs_scale = 1.0            # factor of the last train() on the variational weight (trainWeight), applied to obsWeight
         self.lbfgsLoss64 = bool(lbfgsLoss64)
         self.causal = None if causal is None else float(causal)
         self.causalSlabs = None if causalSlabs is None else int(causalSlabs)
@@ -901,6 +919,8 @@ class VarNet:
                       fluxBC=fluxBC, lbfgsLoss64=lbfgsLoss64, causal=causal, causalSlabs=causalSlabs)
             if periodicDeriv is not None:
                 kw['periodicDeriv'] = periodicDeriv
+            if observations is not None:
+                kw['observations'], kw['obsWeight'] = observations, obsWeight
             self._towers = TowerGroup(type(self), (PDE,), kw, list(processors))
             self.world = self._towers.world
             self.engine = self.tfData = None
@@ -950,6 +970,12 @@ class VarNet:
             self.periodicRows = self.periodicTrainData()
             r = self.periodicRows
             self.engine.set_periodic(r['X'], r['dir'], self.periodicDeriv, fd.biDimVal)
+        if self.obsRows is not None:
+            # fixed for the whole run and replicated in every feed and on every rank like the Dirichlet rows (optimal re-draws leave
+            # them alone): registered once; a network outside the kernels that run the pass is refused here, with the engine's sentence
+            r = self.obsRows
+            self.engine.set_observations(r['X'], r['value'], q=r['q'], dir=r['dir'], rowptr=r['rowptr'], wgt=r['wgt'],
+                                         weight=self.obsWeight / self.world)
         self.tfData = self.engine       # name kept for scripts that poke at `VarNet.tfData`
         from .launch import mark_stage
         mark_stage('engine_ready')      # past the launcher's bootstrap deadline: a rank that trains for hours is healthy
@@ -1252,6 +1278,113 @@ class VarNet:
         if not X:
             return dict(X=np.zeros([0, self.inpDim]), normal=np.zeros([0, dim]), coef=np.zeros(0), label=np.zeros(0), edges=[])
         return dict(X=np.vstack(X), normal=np.vstack(nrm), coef=np.concatenate(coef), label=np.concatenate(label), edges=edges)
+
+    @staticmethod
+    def _check_obs_weight(lam):
+        if not isinstance(lam, (int, float, np.integer, np.floating)) or isinstance(lam, bool) \
+                or not np.isfinite(float(lam)) or float(lam) < 0.0:
+            raise ValueError('obsWeight=%r must be a finite number >= 0' % (lam,))
+
+    @staticmethod
+    def obsData(observations, dim, inpDim):
+        """
+        (No reference counterpart: `VarNet(..., observations=...)`.)  The observations in the engine's layout, assembled in fp64
+        (the engine rounds every array once, to fp32).  `observations` is (X, c) or (X, c, sigma) for point sensors -- X [nO, inpDim]
+        with rows [x..., t] as `biInput` has them, c the measured values, sigma their standard deviations (scalar or [nO]) -- or,
+        for linear functionals, a dict with X [n, inpDim], value [nO], rowptr [nO + 1] (observation i owns the points
+        rowptr[i] .. rowptr[i+1]-1) and optionally q [n] (quadrature weights, default 1), dir [n, dim] (a derivative part
+        dir_j . grad_x u(x_j), default none) and sigma.  The functional is l_i = sum_j (q_j u(x_j) + dir_j . grad_x u(x_j)), the
+        misfit O = mean_i[(l_i - value_i)^2 / sigma_i^2].  ValueError names the field that is malformed.
+        Returns dict(X, value, q, dir, rowptr, wgt) with wgt = 1 / sigma^2 formed in fp64 (None: all 1); q, dir, rowptr None if absent.
+        """
+        def arr(name, a, shape=None):
+            try:
+                a = np.array(a, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError('observations: %s must be a numeric array' % name)
+            if shape is not None:
+                if a.size != int(np.prod(shape)):
+                    raise ValueError('observations: %s has %d entries, expected shape %s' % (name, a.size, list(shape)))
+                a = a.reshape(shape)
+            if not np.all(np.isfinite(a)):
+                raise ValueError('observations: %s has non-finite entries' % name)
+            return a
+
+        if isinstance(observations, dict):
+            unknown = set(observations) - {'X', 'value', 'rowptr', 'q', 'dir', 'sigma'}
+            if unknown:
+                raise ValueError('observations: unknown field(s) %s' % sorted(unknown))
+            for k in ('X', 'value', 'rowptr'):
+                if observations.get(k) is None:
+                    raise ValueError('observations: the field %s is required (X, value, rowptr; optional q, dir, sigma)' % k)
+            X, value, sigma = observations['X'], observations['value'], observations.get('sigma')
+            rowptr, q, dirs = observations['rowptr'], observations.get('q'), observations.get('dir')
+        elif isinstance(observations, (tuple, list)) and len(observations) in (2, 3):
+            X, value = observations[0], observations[1]
+            sigma = observations[2] if len(observations) == 3 else None
+            rowptr = q = dirs = None
+        else:
+            raise ValueError('observations must be (X, c), (X, c, sigma) or a dict with X, value, rowptr and optional q, dir, sigma')
+        X = arr('X', X)
+        if X.ndim == 1 and inpDim == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2 or X.shape[1] != inpDim or X.shape[0] == 0:
+            raise ValueError('observations: X has shape %s, expected [n, %d] with rows [x..., t] and n >= 1' % (list(X.shape), inpDim))
+        n = X.shape[0]
+        value = arr('value', value).reshape(-1)
+        nO = value.shape[0]
+        if rowptr is None:
+            if nO != n:
+                raise ValueError('observations: value has %d entries for %d point sensors' % (nO, n))
+        else:
+            rp = np.asarray(rowptr)
+            if rp.ndim != 1 or rp.shape[0] != nO + 1 or not np.issubdtype(rp.dtype, np.integer):
+                raise ValueError('observations: rowptr must hold %d integers (one more than value)' % (nO + 1))
+            if nO == 0 or rp[0] != 0 or rp[-1] != n or np.any(np.diff(rp) <= 0):
+                raise ValueError('observations: rowptr must increase strictly from 0 to %d (no empty segment)' % n)
+            rowptr = rp.astype(np.int32)
+        if nO == 0:
+            raise ValueError('observations: value is empty')
+        if q is not None:
+            q = arr('q', q, (n,))
+        if dirs is not None:
+            dirs = arr('dir', dirs, (n, dim))
+        wgt = None
+        if sigma is not None:
+            sigma = arr('sigma', sigma)
+            if sigma.size not in (1, nO):
+                raise ValueError('observations: sigma has %d entries, expected 1 or %d' % (sigma.size, nO))
+            sigma = np.broadcast_to(sigma.reshape(-1), (nO,)) if sigma.size == 1 else sigma.reshape(nO)
+            if np.any(sigma <= 0.0):
+                raise ValueError('observations: sigma must be positive')
+            with np.errstate(divide='ignore', over='ignore'):
+                wgt = 1.0 / (sigma * sigma)
+            if not np.all(np.isfinite(wgt)):
+                raise ValueError('observations: sigma is too small, 1/sigma^2 overflows')
+        return dict(X=X, value=value, q=q, dir=dirs, rowptr=rowptr, wgt=wgt)
+
+    def setObsWeight(self, obsWeight):
+        """The weight of the observation misfit, between train() calls: on the scale of `train(weight=[...])`, rescaled by the
+        next train() like the value given to the constructor."""
+        if self.obsRows is None:
+            raise ValueError('setObsWeight: this instance has no observations')
+        self._check_obs_weight(obsWeight)
+        self.obsWeight = float(obsWeight)
+        if self._towers is not None:
+            self._towers.call('setObsWeight', obsWeight)
+            return
+        self.engine.set_obs_weight(self.obsWeight * self._obs_scale / self.world)
+
+    def obsMisfit(self):
+        """The unweighted misfit O = mean_i[(l_i(u) - value_i)^2 / sigma_i^2] at the current parameters."""
+        if self.obsRows is None:
+            raise ValueError('obsMisfit: this instance has no observations')
+        if self._towers is not None:                  # every tower holds all observations: rank 0 answers
+            return self._towers.call('obsMisfit')
+        tData = getattr(self, 'tData', None) or self._build_tdata()
+        tData.select_mor(0)
+        self.engine.eval_loss(tData.engine_batch(0, 0))
+        return self.engine.obs_misfit()
 
     def periodicTrainData(self):
         """
@@ -1715,7 +1848,11 @@ class VarNet:
               useOriginalW=False, batchNum=None, batchLen=None, shuffleData=False, shuffleFreq=1,
               dedup='auto', lossLag=None):
         """Training loop of /root/reference/VarNet.py:1197-1421 (uniform, random and residual-driven
-        "optimal" sampling with re-initialisation and re-weighting)."""
+        "optimal" sampling with re-initialisation and re-weighting).
+
+        With `observations` the misfit joins the loss as obsWeight * O: obsWeight is on the scale of `weight`, multiplied by
+        the factor trainWeight applies to the variational weight (`useOriginalW` leaves it unscaled); `adjustWeight` (which
+        raises the BC/IC weights at a re-draw) leaves it alone, and re-draws leave the observed points alone."""
         if self._is_lbfgs():
             self._lbfgs_refusals(batchNum, batchLen, shuffleData)
         if self._towers is not None:                  # controller of forked towers: every tower runs the loop
@@ -1735,6 +1872,9 @@ class VarNet:
             raise ValueError('weight dimension does not match!')
         if smpScheme not in ('uniform', 'random', 'optimal'):
             raise ValueError('sampling scheme is not valid!')
+        if self.obsRows is not None and float(weight[-1]) == 0.0:
+            raise ValueError('observations with a zero variational weight: obsWeight is scaled by the factor train() puts on the '
+                             'variational weight, which a zero weight leaves undefined')
         if updateWeights:
             raise NotImplementedError('updateWeights=True is broken in the reference (VarNet.py:1373)')
         self.smpScheme = smpScheme
@@ -1767,6 +1907,11 @@ class VarNet:
             tW, tD, lv = self.trainWeight(wts, tD, normalizeW, useOriginalW)
             w_e = tD.towerWeights(tW)                                 # VarNetUtility.py:900-901
             eng.set_weights(w_e)
+            if self.obsRows is not None:
+                # obsWeight is on the scale of `weight`: it takes the factor trainWeight put on the variational weight (1 with
+                # useOriginalW), and, the observed points being replicated in every feed like the BC/IC rows, their division
+                self._obs_scale = 1.0 if useOriginalW else float(tW[-1]) / float(wts[-1])
+                eng.set_obs_weight(self.obsWeight * self._obs_scale / tD.batchNum / tD.puNum)
             return tW, w_e, lv
 
         trainW, w_eff, lossVal = set_train_weights(tData, weight)
