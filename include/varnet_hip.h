@@ -338,6 +338,34 @@ int vn_set_causal(vn_engine* h, int32_t batch, const int32_t* slab_dev, int32_t 
 /* omega_s of the batch's causal registration at the current parameters into omega_slab_host[n_slabs] (n_slabs as registered):
  * runs the batch's loss-only evaluation.  Synchronises; changes no engine state.  Without a causal registration: VN_ESTATE. */
 int vn_causal_weights(vn_engine* h, int32_t batch, double* omega_slab_host, int32_t n_slabs);
+/* Inverse mode: learn the nine polynomial coefficients next to the parameters.  Index 0..2 = (c1, c2, c3) of the reaction,
+ * 3..5 = (f1, f2, f3) of the flux, 6..8 = (d0, d1, d2) of the diffusivity.  While learning is on the engine owns ONE device
+ * vector of nine fp32 coefficients (`init`, rounded once), shared by every batch; every registered term of every batch reads its
+ * three coefficients from it, and the `coef` a batch passes to vn_set_reaction / vn_set_nlflux / vn_set_nldiff only says that the
+ * term is registered (values equal to an unregistered term's no longer clear a term that has a mask entry; NULL still does).
+ * The vector outlives a re-registration of the batches.
+ *   d loss / d c_m = - sum_r s_r N_p rate_r u_r^m,  d loss / d f_m = - sum_r s_r phi_r u_r^m,  d loss / d d_m = + sum_r s_r A_r u_r^m
+ * (s_r: the tangent seed of row r before D(u) rescales it) is formed inside vn_grad / vn_train_step / vn_train_epoch for the
+ * masked entries, in a fixed order without atomics (two evaluations: the same bits), per unique point on the de-duplicated step.
+ * vn_apply and the fused train steps update the masked entries with the arithmetic of the parameters' Adam update (the engine's
+ * beta1, beta2, eps, the shared step counter, the rate `lr`), then clamp them to [lo, hi] (+-inf: unbounded).  Unmasked entries
+ * never change a bit.  A masked coefficient of a term no batch carries has gradient 0 and does not move.
+ * vn_state_snapshot / vn_state_rollback carry coefficients and slots; vn_state_size / _export / _import keep their layout.
+ *   mask   nine ints (non-zero: learnt), or NULL: learning off, everything freed, the batches' own coefficients count again and
+ *          every result is bit for bit what it was before learning was switched on.
+ *   init, lo, hi   nine doubles each.  Non-finite init, NaN bounds, lo > hi, lr not finite or <= 0: VN_EINVAL.
+ * Refused with VN_EUNSUPPORTED: an RMSProp or L-BFGS engine (also vn_lbfgs_step while learning is on); a handle that has a
+ * communicator (and vn_comm_init while learning is on): the nine gradients are not in the all-reduced buffer; a batch with
+ * vn_set_tf_weights / vn_set_causal (here, in those calls and in the steps): the weights are applied after the seeds the
+ * reduction reads.  The call invalidates the snapshot of vn_state_snapshot.
+ * vn_objective_f64 evaluates at the current coefficients (widened exactly); a coefficient gradient in double is not built. */
+int vn_set_coef_learn(vn_engine* h, const int32_t mask[9], const double init[9], const double lo[9], const double hi[9], double lr);
+/* The nine coefficients now (synchronises) and, when grad is not NULL, the coefficient gradient of the last gradient evaluation
+ * (zeros for unmasked entries and before the first one).  Learning off: VN_ESTATE. */
+int vn_get_coefs(vn_engine* h, double coef[9], double grad[9]);
+/* Overwrites all nine coefficients (rounded to fp32, NOT clamped); the Adam slots stay.  Non-finite: VN_EINVAL; learning off:
+ * VN_ESTATE.  Invalidates the snapshot of vn_state_snapshot. */
+int vn_set_coefs(vn_engine* h, const double coef[9]);
 /* updateDictFields('trainW') (VarNetUtility.py:921-922); the caller applies the
  * w[0:2] /= batchNum*puNum rule (VarNetUtility.py:900-901). */
 int vn_set_weights(vn_engine* h, const double w[3]);

@@ -10,6 +10,7 @@
 #include "vn_pgrad16.h"
 #include "vn_taylor16.h"
 #include "vn_terms.h"
+#include "vn_coef.h"
 #include "vn_weights.h"
 #include "vn_split16.h"
 
@@ -217,6 +218,15 @@ struct vn_engine {
   float *ou = nullptr, *oud = nullptr, *oubar = nullptr, *oudbar = nullptr, *oloss = nullptr, *opartial = nullptr;
   long ou_cap = 0, oud_cap = 0, oubar_cap = 0, oudbar_cap = 0, oloss_cap = 0, opartial_cap = 0;
   double* omisfit = nullptr;                      // device slot: the unweighted misfit O of the last evaluation
+  // inverse mode (vn_set_coef_learn, vn_coef.hip): the nine coefficients live on the device while they are learnt
+  bool cl_on = false;
+  unsigned cl_mask = 0;                           // bit i: entry i is learnt
+  double cl_lo[VN_COEF_N] = {}, cl_hi[VN_COEF_N] = {}, cl_lr = 0.0;
+  float* cl_state = nullptr;                      // [54] (coef | m | v), then their copy of vn_state_snapshot
+  double* cl_grad = nullptr;                      // [9] coefficient gradient of the last gradient evaluation
+  float* cl_part = nullptr;                       // [VN_COEF_MAXBLK, 9] partials of the reduction
+  int cl_blocks = 0;                              // partials the current gradient evaluation wrote (0: the batch carries no term)
+  float* cl_acc = nullptr; long cl_acc_cap = 0;   // [3, U] accR_j, accF_j, gs_j of the de-duplicated step
   float* snap = nullptr;       // vn_state_snapshot: device copy of (theta | m | v), 3 P floats
   int64_t snap_step = -1;      // step counter at the snapshot (-1: none)
   PointRoute point_route = PointRoute::automatic;   // vn_debug_point_route(route & 3)
@@ -483,6 +493,7 @@ VnSeedArgs seed_args(const vn_engine* h, const Batch& b) {
   a.ub = h->ub; a.label = bi_y(h, b); a.nB = h->nB; a.bDof = h->bDof; a.biDimVal = (float)h->biDimVal;
   a.w0 = (float)h->w[0]; a.w1 = (float)h->w[1]; a.w2 = (float)h->w[2];
   if (b.react.on) { a.react = 1; a.rate = b.react.stream; a.c1 = (float)b.react.c[0]; a.c2 = (float)b.react.c[1]; a.c3 = (float)b.react.c[2]; }
+  if (b.react.on && h->cl_on) a.coef = h->cl_state;
   return a;
 }
 
@@ -519,11 +530,18 @@ int check_Np(const vn_engine* h, const TermKind& k, int batch = -1, const char* 
                                "point (vn_set_fe_table has a zero entry); clear the map (vn_set_dedup with Xu = NULL) to run row-wise", k.name);
 }
 
+// Inverse mode: where a registered term of b reads its three coefficients (nullptr: learning off, the batch's own by value)
+const float* term_cp(const vn_engine* h, const Batch& b, const Term& t) {
+  if (!h->cl_on) return nullptr;
+  return h->cl_state + 3 * (&t == &b.react ? 0 : &t == &b.nlflux ? 1 : 2);
+}
+
 // Row-wise routes: values in h->u, integrand / seeds in h->ud, h->ubar, h->udbar, A_r of the D(u) pair saved in h->nd_A
 VnTermRowArgs term_row_args(const vn_engine* h, const Batch& b, const Term& t) {
   VnTermRowArgs a{};
   a.u = h->u; a.stream = t.stream;
   for (int i = 0; i < 3; ++i) a.c[i] = (float)t.c[i];
+  a.cp = term_cp(h, b, t);
   a.nT = b.n_k * h->cfg.integ_num;
   a.ud = h->ud; a.A = h->nd_A; a.udbar = h->udbar; a.ubar = h->ubar;
   return a;
@@ -541,6 +559,14 @@ int terms_fold_rows(vn_engine* h, const Batch& b) {
 
 // After a vn_seed_launch that produced seeds: D(u) rescales the tangent seed last, the flux term's value seed reads it unscaled
 int terms_seed_rows(vn_engine* h, const Batch& b) {
+  if (h->cl_on && has_terms(b)) {                  // inverse mode: the coefficient sums read udbar before D(u) rescales it
+    VnCoefRowsArgs c{};
+    c.u = h->u; c.udbar = h->udbar; c.nT = b.n_k * h->cfg.integ_num; c.q = h->cfg.integ_num;
+    c.react = b.react.on ? 1 : 0; c.rate = b.react.stream; c.Nrow = b.Nrow; c.feN = h->feN;
+    c.phi = b.nlflux.on ? b.nlflux.stream : nullptr; c.A = b.nldiff.on ? h->nd_A : nullptr;
+    c.mask = h->cl_mask; c.part = h->cl_part;
+    HIPCHK(vn_coefgrad_rows_launch(c, &h->cl_blocks, h->stream));
+  }
   if (b.nlflux.on) HIPCHK(vn_nlflux_seed_launch(term_row_args(h, b, b.nlflux), h->stream));
   if (b.nldiff.on) HIPCHK(vn_nldiff_seed_launch(term_row_args(h, b, b.nldiff), h->stream));
   return VN_OK;
@@ -552,6 +578,7 @@ VnTermDedupArgs term_dedup_args(const vn_engine* h, const Batch& b, const Term& 
   a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
   a.base = d.source; a.stream = t.stream;
   for (int i = 0; i < 3; ++i) a.c[i] = (float)t.c[i];
+  a.cp = term_cp(h, b, t);
   a.feN = h->feN; a.feW = fe_w(h); a.stf = d.stf;
   a.nT = b.n_k * h->cfg.integ_num; a.U = b.U; a.q = h->cfg.integ_num;
   a.s_eff = h->rx_seff; a.seed_u = d.seed_u;
@@ -582,6 +609,19 @@ int terms_source_dedup(vn_engine* h, const Batch& b, VnDedupArgs& d) {
 // After vn_dedup_gather_launch: each term's value seed, added to the gathered one; D(u) last (D'(u) grad u . seed_g needs the
 // unscaled seed_g)
 int terms_gather_dedup(vn_engine* h, const Batch& b, const VnDedupArgs& d) {
+  if (h->cl_on && has_terms(b)) {                  // inverse mode: each kernel also stores its per-point sum for vn_coefgrad_points_kernel
+    if (int rc = ensure(&h->cl_acc, &h->cl_acc_cap, 3 * b.U)) return rc;
+    VnTermDedupArgs r = term_dedup_args(h, b, b.react, d), f = term_dedup_args(h, b, b.nlflux, d), n = nldiff_dedup_args(h, b, d);
+    r.acc_out = h->cl_acc; f.acc_out = h->cl_acc + b.U; n.acc_out = h->cl_acc + 2 * b.U;
+    if (b.react.on) HIPCHK(vn_react_gather_launch(r, h->stream));
+    if (b.nlflux.on) HIPCHK(vn_nlflux_gather_launch(f, h->stream));
+    if (b.nldiff.on) HIPCHK(vn_nldiff_point_launch(n, h->stream));
+    VnCoefPointsArgs c{};
+    c.upack = h->dd_uv; c.U = b.U; c.mask = h->cl_mask; c.part = h->cl_part;
+    c.accR = b.react.on ? r.acc_out : nullptr; c.accF = b.nlflux.on ? f.acc_out : nullptr; c.gs = b.nldiff.on ? n.acc_out : nullptr;
+    HIPCHK(vn_coefgrad_points_launch(c, &h->cl_blocks, h->stream));
+    return VN_OK;
+  }
   if (b.react.on) HIPCHK(vn_react_gather_launch(term_dedup_args(h, b, b.react, d), h->stream));
   if (b.nlflux.on) HIPCHK(vn_nlflux_gather_launch(term_dedup_args(h, b, b.nlflux, d), h->stream));
   if (b.nldiff.on) HIPCHK(vn_nldiff_point_launch(nldiff_dedup_args(h, b, d), h->stream));
@@ -928,6 +968,39 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
   return VN_OK;
 }
 
+// Inverse mode, after the last kernel of a gradient evaluation that reads the coefficients: the partials folded into cl_grad
+// (zeros when the batch carries no term), and with `update` the Adam step of the masked entries at step counter t
+int coef_finish(vn_engine* h, bool fold, bool update, double t) {
+  VnCoefApplyArgs a{};
+  if (fold) {
+    if (h->cl_blocks <= 0) {
+      HIPCHK(hipMemsetAsync(h->cl_part, 0, VN_COEF_N * sizeof(float), h->stream));
+      h->cl_blocks = 1;
+    }
+    a.part = h->cl_part; a.blocks = h->cl_blocks;
+  }
+  a.grad = h->cl_grad; a.coef = h->cl_state; a.m = h->cl_state + VN_COEF_N; a.v = h->cl_state + 2 * VN_COEF_N;
+  a.mask = h->cl_mask;
+  for (int i = 0; i < VN_COEF_N; ++i) { a.lo[i] = (float)h->cl_lo[i]; a.hi[i] = (float)h->cl_hi[i]; }
+  a.update = update ? 1 : 0;
+  if (update) {
+    a.lr_t = (float)(h->cl_lr * std::sqrt(1.0 - std::pow(h->cfg.beta2, t)) / (1.0 - std::pow(h->cfg.beta1, t)));
+    a.b1 = (float)h->cfg.beta1; a.b2 = (float)h->cfg.beta2; a.eps = (float)h->cfg.eps;
+  }
+  HIPCHK(vn_coef_apply_launch(a, h->stream));
+  return VN_OK;
+}
+
+void coef_free(vn_engine* h) {
+  for (void* p : {(void*)h->cl_state, (void*)h->cl_grad, (void*)h->cl_part, (void*)h->cl_acc})
+    if (p) (void)hipFree(p);
+  h->cl_state = nullptr; h->cl_grad = nullptr; h->cl_part = nullptr; h->cl_acc = nullptr; h->cl_acc_cap = 0;
+  h->cl_on = false; h->cl_mask = 0; h->cl_blocks = 0;
+}
+
+constexpr const char* kCoefWeights = "learnt coefficients (vn_set_coef_learn) next to per-test-function loss weights (vn_set_tf_weights / "
+                                     "vn_set_causal, batch %d): the weights are applied after the seeds the coefficient reduction reads";
+
 // ---- RCCL, loaded at run time -------------------------------------------------------------
 // librccl.so.1 is resolved by SONAME, so a process that already carries RCCL (PyTorch-ROCm does) shares that
 // copy; VN_RCCL_LIB names another file.  Nothing here is touched unless vn_comm_* is called, so the library
@@ -1089,6 +1162,7 @@ int vn_destroy(vn_engine* h) {
     if (p) (void)hipFree(p);
   if (h->lb.out) (void)hipHostFree(h->lb.out);
   vn_obj64_free(h->o64);
+  coef_free(h);
   for (Batch& b : h->batches) {
     if (b.gcsr) (void)hipFree(b.gcsr);
     clear_weights(b);
@@ -1198,6 +1272,8 @@ int vn_state_snapshot(vn_engine* h) {
   HIPCHK(hipMemcpyAsync(h->snap, h->theta, nb, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->snap + h->net.P, h->m, nb, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->snap + 2 * (size_t)h->net.P, h->v, nb, hipMemcpyDeviceToDevice, h->stream));
+  if (h->cl_on)
+    HIPCHK(hipMemcpyAsync(h->cl_state + 3 * VN_COEF_N, h->cl_state, 3 * VN_COEF_N * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   h->snap_step = h->step;
   return VN_OK;
 }
@@ -1211,6 +1287,8 @@ int vn_state_rollback(vn_engine* h) {
   HIPCHK(hipMemcpyAsync(h->theta, h->snap, nb, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->m, h->snap + h->net.P, nb, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->v, h->snap + 2 * (size_t)h->net.P, nb, hipMemcpyDeviceToDevice, h->stream));
+  if (h->cl_on)
+    HIPCHK(hipMemcpyAsync(h->cl_state, h->cl_state + 3 * VN_COEF_N, 3 * VN_COEF_N * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   h->step = h->snap_step;
   return VN_OK;
 }
@@ -1354,7 +1432,9 @@ static int set_term(vn_engine* h, int32_t batch, const TermKind& k, const float*
   if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no %s to integrate", batch, k.integrand);
   lbfgs_invalidate(h, batch);
   const Term off = Batch().*(k.slot);
-  if (!coef || (std::equal(coef, coef + 3, off.c) && !(&k == &kNldiff && stream))) {
+  // (a term with a learnt entry stays registered whatever `coef` says: its coefficients are the engine's, vn_set_coef_learn)
+  const bool learnt = h->cl_on && (h->cl_mask >> (3 * (&k == &kReact ? 0 : &k == &kNlflux ? 1 : 2)) & 7u);
+  if (!coef || (!learnt && std::equal(coef, coef + 3, off.c) && !(&k == &kNldiff && stream))) {
     b.*(k.slot) = off;
     return VN_OK;
   }
@@ -1381,6 +1461,83 @@ int vn_set_reaction(vn_engine* h, int32_t batch, const float* rate, const double
 int vn_set_nlflux(vn_engine* h, int32_t batch, const float* phi, const double coef[3]) { return set_term(h, batch, kNlflux, phi, coef); }
 int vn_set_nldiff(vn_engine* h, int32_t batch, const float* psi, const double coef[3]) { return set_term(h, batch, kNldiff, psi, coef); }
 
+// ---- inverse mode: the nine coefficients on the device, learnt next to the parameters (vn_coef.hip) ----
+int vn_set_coef_learn(vn_engine* h, const int32_t mask[9], const double init[9], const double lo[9], const double hi[9], double lr) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  (void)hipGetLastError();
+  HIPCHK(hipSetDevice(h->cfg.device));
+  h->snap_step = -1;
+  lbfgs_invalidate(h);
+  if (!mask) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    coef_free(h);
+    return VN_OK;
+  }
+  if (!init || !lo || !hi) return fail(VN_EINVAL, "null argument");
+  if (h->cfg.optimizer != VN_OPT_ADAM)
+    return fail(VN_EUNSUPPORTED, "vn_set_coef_learn on %s engine: the coefficients are updated with the arithmetic of the Adam step only%s",
+                is_lbfgs(h) ? "an L-BFGS" : "an RMSProp", is_lbfgs(h) ? " (vn_lbfgs_step searches over the parameters alone)" : "");
+  if (h->comm)
+    return fail(VN_EUNSUPPORTED, "vn_set_coef_learn under a communicator: the nine coefficient gradients are not in the all-reduced "
+                                 "buffer, so every rank would follow its own shard's");
+  for (size_t i = 0; i < h->batches.size(); ++i)
+    if (has_weights(h->batches[i])) return fail(VN_EUNSUPPORTED, kCoefWeights, (int)i);
+  if (!(std::isfinite(lr) && lr > 0.0)) return fail(VN_EINVAL, "coefficient learning rate %g must be finite and > 0", lr);
+  for (int i = 0; i < VN_COEF_N; ++i) {
+    if (!std::isfinite(init[i])) return fail(VN_EINVAL, "initial coefficient %d = %g must be finite", i, init[i]);
+    if (std::isnan(lo[i]) || std::isnan(hi[i]) || lo[i] > hi[i])
+      return fail(VN_EINVAL, "bounds of coefficient %d: [%g, %g] is no interval", i, lo[i], hi[i]);
+  }
+  if (!h->cl_state) {
+    hipError_t e = hipMalloc((void**)&h->cl_state, 6 * VN_COEF_N * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->cl_grad, VN_COEF_N * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->cl_part, (size_t)VN_COEF_MAXBLK * VN_COEF_N * sizeof(float));
+    if (e != hipSuccess) { (void)hipGetLastError(); coef_free(h); return fail(VN_ENOMEM, "vn_set_coef_learn: %s", hipGetErrorString(e)); }
+  }
+  float st[6 * VN_COEF_N] = {};
+  h->cl_mask = 0;
+  for (int i = 0; i < VN_COEF_N; ++i) {
+    st[i] = (float)init[i];
+    h->cl_lo[i] = lo[i]; h->cl_hi[i] = hi[i];
+    if (mask[i]) h->cl_mask |= 1u << i;
+  }
+  h->cl_lr = lr;
+  HIPCHK(hipMemcpyAsync(h->cl_state, st, sizeof st, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(h->cl_grad, 0, VN_COEF_N * sizeof(double), h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));      // (st leaves scope)
+  h->cl_on = true;
+  h->cl_blocks = 0;
+  return VN_OK;
+}
+
+int vn_get_coefs(vn_engine* h, double coef[9], double grad[9]) {
+  if (!h || !coef) return fail(VN_EINVAL, "null argument");
+  if (!h->cl_on) return fail(VN_ESTATE, "no learnt coefficients (call vn_set_coef_learn first)");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  float c[VN_COEF_N];
+  HIPCHK(hipMemcpyAsync(c, h->cl_state, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  if (grad) HIPCHK(hipMemcpyAsync(grad, h->cl_grad, VN_COEF_N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < VN_COEF_N; ++i) coef[i] = (double)c[i];
+  return VN_OK;
+}
+
+int vn_set_coefs(vn_engine* h, const double coef[9]) {
+  if (!h || !coef) return fail(VN_EINVAL, "null argument");
+  if (!h->cl_on) return fail(VN_ESTATE, "no learnt coefficients (call vn_set_coef_learn first)");
+  float c[VN_COEF_N];
+  for (int i = 0; i < VN_COEF_N; ++i) {
+    if (!std::isfinite(coef[i])) return fail(VN_EINVAL, "coefficient %d = %g must be finite", i, coef[i]);
+    c[i] = (float)coef[i];
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipMemcpyAsync(h->cl_state, c, sizeof c, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->snap_step = -1;
+  lbfgs_invalidate(h);
+  return VN_OK;
+}
+
 // vn_set_tf_weights / vn_set_causal: what both check before they touch the batch; *clear: the call unregisters
 static int weights_common(vn_engine* h, int32_t batch, bool clear, const char* who) {
   if (!h) return fail(VN_EINVAL, "null handle");
@@ -1394,6 +1551,7 @@ static int weights_common(vn_engine* h, int32_t batch, bool clear, const char* w
     return VN_OK;
   }
   if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no test function to weight", batch);
+  if (h->cl_on) return fail(VN_EUNSUPPORTED, kCoefWeights, batch);
   if (h->route == Route::fused4)
     return fail(VN_EUNSUPPORTED, "%s is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its single launch has no "
                                  "place for the weights; every other kernel family carries them", who);
@@ -1644,12 +1802,23 @@ int vn_bind_grad_buffer(vn_engine* h, float* dev) {
   return VN_OK;
 }
 
+static int grad_route(vn_engine* h, const Batch& b);
+
 int vn_grad(vn_engine* h, int32_t batch) {
   if (!h) return fail(VN_EINVAL, "null handle");
   (void)hipGetLastError();   // a stale last-error of another library on this thread is not ours to report
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   const Batch& b = h->batches[batch];
+  if (!h->cl_on) return grad_route(h, b);
+  if (has_weights(b)) return fail(VN_EUNSUPPORTED, kCoefWeights, batch);
+  h->cl_blocks = 0;
+  if (int rc = grad_route(h, b)) return rc;
+  // inverse mode: after every kernel that reads the coefficients (the parameters' update rides in the reduction above)
+  return coef_finish(h, true, h->fuse.kind == VN_OPT_ADAM, (double)h->step);
+}
+
+static int grad_route(vn_engine* h, const Batch& b) {
   VnEdgeSums fx;
   if (int rc = edge_passes(h, true, &fx)) return rc;   // (no flux rows, no periodic pairs: nothing enqueued, fx empty)
   if (b.Xu) return run_dedup(h, b, h->gradbuf, fx);      // (a de-duplication map: 8-wave routes only)
@@ -1679,6 +1848,8 @@ static int apply_impl(vn_engine* h, float* loss_acc) {
   const double lr_t = h->cfg.lr * std::sqrt(1.0 - std::pow(h->cfg.beta2, t)) / (1.0 - std::pow(h->cfg.beta1, t));
   HIPCHK(vn_adam_launch(h->theta, h->m, h->v, h->gradbuf, h->net.P, (float)lr_t, (float)h->cfg.beta1,
                         (float)h->cfg.beta2, (float)h->cfg.eps, loss_acc, h->stream));
+  if (h->cl_on)
+    if (int rc = coef_finish(h, false, true, t)) return rc;
   h->step += 1;
   return VN_OK;
 }
@@ -1909,6 +2080,12 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   p.react = b.react.on ? 1 : 0; p.rate = b.react.stream; std::copy(b.react.c, b.react.c + 3, p.coef);
   p.nlflux = b.nlflux.on ? 1 : 0; p.phi = b.nlflux.stream; std::copy(b.nlflux.c, b.nlflux.c + 3, p.fcoef3);
   p.nldiff = b.nldiff.on ? 1 : 0; p.psi = b.nldiff.stream; std::copy(b.nldiff.c, b.nldiff.c + 3, p.dcoef3);
+  if (h->cl_on) {                            // inverse mode: at the current device coefficients, widened exactly
+    float c[VN_COEF_N];
+    HIPCHK(hipMemcpyAsync(c, h->cl_state, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 3; ++i) { p.coef[i] = c[i]; p.fcoef3[i] = c[3 + i]; p.dcoef3[i] = c[6 + i]; }
+  }
   p.wt = b.wt;
   hipError_t e = vn_obj64_run(h->o64, p, grad_dev, lossVec_dev, out, h->ncu, h->stream);
   if (e != hipSuccess) {
@@ -2036,6 +2213,9 @@ int vn_comm_init(vn_engine* h, int32_t rank, int32_t world, const void* unique_i
     if (h->batches[i].wt.S > 0)
       return fail(VN_EUNSUPPORTED, "vn_comm_init: batch %d has a causal registration (vn_set_causal); a rank's slab means would cover "
                                    "only its shard, so the ranks together would train another objective than one rank", (int)i);
+  if (h->cl_on)
+    return fail(VN_EUNSUPPORTED, "vn_comm_init while coefficients are learnt (vn_set_coef_learn): the nine coefficient gradients are "
+                                 "not in the all-reduced buffer, so every rank would follow its own shard's");
   if (int rc = load_rccl()) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   ncclUniqueId id;

@@ -339,6 +339,7 @@ __global__ __launch_bounds__(NTHREADS) void vn_seed_kernel(VnSeedArgs a) {
   __shared__ float red[4];
   const long k = (long)blockIdx.x * NTHREADS + threadIdx.x;
   float lv = 0.f;
+  if (a.coef) { a.c1 = a.coef[0]; a.c2 = a.coef[1]; a.c3 = a.coef[2]; }   // learnt coefficients: the engine's device vector
   if (k < a.n_k) {
     const int q = a.integ_num;
     const long base = k * q;

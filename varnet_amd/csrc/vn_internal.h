@@ -48,6 +48,7 @@ struct VnSeedArgs {
   int react;
   const float* rate;                        // [nT] or nullptr (rate == 1)
   float c1, c2, c3;
+  const float* coef;                        // [3] device, or nullptr: (c1, c2, c3) while they are learnt (vn_set_coef_learn)
 };
 
 inline bool vn_net_in_kernel_range(const VnNet& net) {

@@ -11,6 +11,7 @@ struct VnTermRowArgs {
   const float* stream;                       // [nT] flux: phi_r = sum_d w_d dN_r/dx_d;  D(u): psi_r = sum_d v_d dN_r/dx_d + N_r div v,
                                              //      or nullptr (no advection)
   float c[3];                                // flux: (f1, f2, f3);  D(u): (d0, d1, d2)
+  const float* cp;                           // [3] device, or nullptr: the same three while they are learnt (vn_set_coef_learn); c is then unused
   long nT;
   float* ud;                                 // [nT] in/out: the row integrand's tangent part A_r = sum_d u_{x_d} gcoef_d
   float* A;                                  // [nT] D(u) only, engine-owned: A_r saved by the fold kernel, read by the seed kernel
@@ -35,6 +36,9 @@ struct VnTermDedupArgs {
                                              // it (may be s_eff itself)
   const float* stream;                       // [nT] reaction: rate, or nullptr (rate == 1);  flux: phi;  D(u): psi, or nullptr
   float c[3];                                // reaction: (c1, c2, c3);  flux: (f1, f2, f3);  D(u): (d0, d1, d2)
+  const float* cp;                           // [3] device, or nullptr: the same three while they are learnt (vn_set_coef_learn); c is then unused
+  float* acc_out;                            // [U] or nullptr: the gather kernels store their CSR sum (accR_j, accF_j), the point
+                                             // kernel its dot product gs_j = grad u_j . seed_g[j,:] -- read by vn_coef.hip
   const float* feN; const float* feW;        // [q] tables (feW may be nullptr)
   const float* stf;                          // [n_k] seed of every test function (vn_dedup_seed_kernel's output)
   long nT, U; int q;

@@ -33,6 +33,11 @@
 //     vn_nldiff_point_kernel  last: seed_g[j,:] = sum_r W_p gcoef_r stf[k_r] is what the rows' tangent seeds add up to, so
 //       d loss / d u_j += D'(u_j) (grad u_j . seed_g[j,:]) needs the unscaled seed_g and no gather, then seed_g[j,:] *= D(u_j);
 //       only -sum_r W_p psi_r stf[k_r] walks the rows of the point.
+//
+// Inverse mode (vn_set_coef_learn): every kernel takes its three coefficients from the argument `cp` when it is given -- the engine's
+// device vector, which the optimizer step updates -- and from the by-value `c` otherwise; the gather and point kernels store their
+// per-point sum (accR_j, accF_j, gs_j) to `acc_out` when it is given, for the coefficient reduction of vn_coef.hip.  With both null
+// code path and arithmetic are unchanged.
 #include <cstdint>
 #include <initializer_list>
 
@@ -49,6 +54,17 @@ __device__ __forceinline__ float dquad(float u, const float* c) { return c[1] + 
 __device__ __forceinline__ float cubic(float u, const float* c) { return u * quad(u, c); }
 __device__ __forceinline__ float dcubic(float u, const float* c) { return c[0] + u * (2.f * c[1] + 3.f * c[2] * u); }
 
+// The three coefficients of a term: the engine's device vector while the coefficients are learnt (vn_set_coef_learn: cp), else
+// the by-value ones.  Either way three floats in registers before the first use: the arithmetic after it is the same.
+struct Coef3 { float c[3]; };
+template <class Args>
+__device__ __forceinline__ Coef3 coef3(const Args& a) {
+  Coef3 k;
+  if (a.cp) { k.c[0] = a.cp[0]; k.c[1] = a.cp[1]; k.c[2] = a.cp[2]; }
+  else { k.c[0] = a.c[0]; k.c[1] = a.c[1]; k.c[2] = a.c[2]; }
+  return k;
+}
+
 // ---- row-wise routes ----
 __device__ __forceinline__ f32x4t load4(const float* p, long i) { return reinterpret_cast<const f32x4t*>(p)[i]; }
 __device__ __forceinline__ void store4(float* p, long i, f32x4t v) { reinterpret_cast<f32x4t*>(p)[i] = v; }
@@ -56,41 +72,46 @@ __device__ __forceinline__ void store4(float* p, long i, f32x4t v) { reinterpret
 __global__ __launch_bounds__(256) void vn_nlflux_fold_kernel(VnTermRowArgs a) {
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= a.nT) return;
-  a.ud[r] -= cubic(a.u[r], a.c) * a.stream[r];
+  const Coef3 k = coef3(a);
+  a.ud[r] -= cubic(a.u[r], k.c) * a.stream[r];
 }
 
 __global__ __launch_bounds__(256) void vn_nlflux_fold4_kernel(VnTermRowArgs a) {      // nT % 4 == 0, 16-byte aligned pointers
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.nT / 4) return;
+  const Coef3 k = coef3(a);
   const f32x4t u = load4(a.u, i), ph = load4(a.stream, i);
   f32x4t ud = load4(a.ud, i);
 #pragma unroll
-  for (int c = 0; c < 4; ++c) ud[c] -= cubic(u[c], a.c) * ph[c];
+  for (int c = 0; c < 4; ++c) ud[c] -= cubic(u[c], k.c) * ph[c];
   store4(a.ud, i, ud);
 }
 
 __global__ __launch_bounds__(256) void vn_nlflux_seed_kernel(VnTermRowArgs a) {
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= a.nT) return;
-  a.ubar[r] -= a.stream[r] * dcubic(a.u[r], a.c) * a.udbar[r];
+  const Coef3 k = coef3(a);
+  a.ubar[r] -= a.stream[r] * dcubic(a.u[r], k.c) * a.udbar[r];
 }
 
 __global__ __launch_bounds__(256) void vn_nlflux_seed4_kernel(VnTermRowArgs a) {      // nT % 4 == 0, 16-byte aligned pointers
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.nT / 4) return;
+  const Coef3 k = coef3(a);
   const f32x4t u = load4(a.u, i), ph = load4(a.stream, i), sd = load4(a.udbar, i);
   f32x4t ub = load4(a.ubar, i);
 #pragma unroll
-  for (int c = 0; c < 4; ++c) ub[c] -= ph[c] * dcubic(u[c], a.c) * sd[c];
+  for (int c = 0; c < 4; ++c) ub[c] -= ph[c] * dcubic(u[c], k.c) * sd[c];
   store4(a.ubar, i, ub);
 }
 
 __global__ __launch_bounds__(256) void vn_nldiff_fold_kernel(VnTermRowArgs a) {
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= a.nT) return;
+  const Coef3 k = coef3(a);
   const float u = a.u[r], A = a.ud[r];
   a.A[r] = A;
-  float t = quad(u, a.c) * A;
+  float t = quad(u, k.c) * A;
   if (a.stream) t -= u * a.stream[r];
   a.ud[r] = t;
 }
@@ -98,13 +119,14 @@ __global__ __launch_bounds__(256) void vn_nldiff_fold_kernel(VnTermRowArgs a) {
 __global__ __launch_bounds__(256) void vn_nldiff_fold4_kernel(VnTermRowArgs a) {      // nT % 4 == 0, 16-byte aligned pointers
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.nT / 4) return;
+  const Coef3 k = coef3(a);
   const f32x4t u = load4(a.u, i), A = load4(a.ud, i);
   f32x4t ps = {0.f, 0.f, 0.f, 0.f};
   if (a.stream) ps = load4(a.stream, i);
   f32x4t t;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    t[c] = quad(u[c], a.c) * A[c];
+    t[c] = quad(u[c], k.c) * A[c];
     if (a.stream) t[c] -= u[c] * ps[c];
   }
   store4(a.A, i, A);
@@ -114,26 +136,28 @@ __global__ __launch_bounds__(256) void vn_nldiff_fold4_kernel(VnTermRowArgs a) {
 __global__ __launch_bounds__(256) void vn_nldiff_seed_kernel(VnTermRowArgs a) {
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= a.nT) return;
+  const Coef3 k = coef3(a);
   const float u = a.u[r], sd = a.udbar[r];
-  float g = dquad(u, a.c) * a.A[r];
+  float g = dquad(u, k.c) * a.A[r];
   if (a.stream) g -= a.stream[r];
   a.ubar[r] += g * sd;
-  a.udbar[r] = quad(u, a.c) * sd;
+  a.udbar[r] = quad(u, k.c) * sd;
 }
 
 __global__ __launch_bounds__(256) void vn_nldiff_seed4_kernel(VnTermRowArgs a) {      // nT % 4 == 0, 16-byte aligned pointers
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.nT / 4) return;
+  const Coef3 k = coef3(a);
   const f32x4t u = load4(a.u, i), A = load4(a.A, i);
   f32x4t sd = load4(a.udbar, i), ub = load4(a.ubar, i);
   f32x4t ps = {0.f, 0.f, 0.f, 0.f};
   if (a.stream) ps = load4(a.stream, i);
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    float g = dquad(u[c], a.c) * A[c];
+    float g = dquad(u[c], k.c) * A[c];
     if (a.stream) g -= ps[c];
     ub[c] += g * sd[c];
-    sd[c] = quad(u[c], a.c) * sd[c];
+    sd[c] = quad(u[c], k.c) * sd[c];
   }
   store4(a.ubar, i, ub);
   store4(a.udbar, i, sd);
@@ -143,27 +167,30 @@ __global__ __launch_bounds__(256) void vn_nldiff_seed4_kernel(VnTermRowArgs a) {
 __global__ __launch_bounds__(256) void vn_react_source_kernel(VnTermDedupArgs a) {
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= a.nT) return;
+  const Coef3 k = coef3(a);
   const long j = a.uid[r];                                     // (validated against U by vn_set_dedup)
   const float base = a.base ? a.base[r] : 0.f;
   const float rho = a.stream ? a.stream[r] : 1.f;
-  const float pu = cubic(a.upack[j * 4], a.c);
+  const float pu = cubic(a.upack[j * 4], k.c);
   a.s_eff[r] = base + (a.stream ? rho * pu : pu);
 }
 
 __global__ __launch_bounds__(256) void vn_nlflux_source_kernel(VnTermDedupArgs a) {
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= a.nT) return;
+  const Coef3 k = coef3(a);
   const long j = a.uid[r];                                     // (validated against U by vn_set_dedup)
   const int p = (int)(r % a.q);
   const float base = a.base ? a.base[r] : 0.f;
   const float u = a.upack[j * 4];
   // vn_dedup_seed_kernel multiplies its source by N_p (non-zero: checked on the host against the table of vn_set_fe_table)
-  a.s_eff[r] = base + cubic(u, a.c) * a.stream[r] / a.feN[p];
+  a.s_eff[r] = base + cubic(u, k.c) * a.stream[r] / a.feN[p];
 }
 
 __global__ __launch_bounds__(256) void vn_nldiff_source_kernel(VnTermDedupArgs a) {
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= a.nT) return;
+  const Coef3 k = coef3(a);
   const long j = a.uid[r];                                     // (validated against U by vn_set_dedup)
   const int p = (int)(r % a.q);
   const long gr = a.gper ? p : r;                              // periodic gcoef: the table = the rows of test function 0
@@ -171,7 +198,7 @@ __global__ __launch_bounds__(256) void vn_nldiff_source_kernel(VnTermDedupArgs a
   const f32x4t pd = *reinterpret_cast<const f32x4t*>(a.upack + j * 4);
   float A = 0.f;
   for (int d = 0; d < a.dim; ++d) A += pd[1 + d] * a.gcoef[gr * a.dim + d];
-  float t = (1.f - quad(pd[0], a.c)) * A;
+  float t = (1.f - quad(pd[0], k.c)) * A;
   if (a.stream) t += pd[0] * a.stream[r];
   // N_p non-zero, as for the flux term
   a.s_eff[r] = base + t / a.feN[p];
@@ -219,6 +246,7 @@ __device__ __forceinline__ float stream_term(const VnTermDedupArgs& a, unsigned 
 __global__ __launch_bounds__(256) void vn_react_gather_kernel(VnTermDedupArgs a) {
   const long j = (long)blockIdx.x * 256 + threadIdx.x;
   if (j >= a.U) return;
+  const Coef3 k = coef3(a);
   const float u = a.upack[j * 4];
   const float su = a.seed_u[j];
   const float acc = csr_walk(a, j, [&a](unsigned ru, unsigned k, unsigned p) {
@@ -227,33 +255,38 @@ __global__ __launch_bounds__(256) void vn_react_gather_kernel(VnTermDedupArgs a)
     if (a.stream) t *= a.stream[ru];
     return t;
   });
-  a.seed_u[j] = su - dcubic(u, a.c) * acc;
+  if (a.acc_out) a.acc_out[j] = acc;                          // vn_coefgrad_points_kernel reads it (vn_set_coef_learn)
+  a.seed_u[j] = su - dcubic(u, k.c) * acc;
 }
 
 __global__ __launch_bounds__(256) void vn_nlflux_gather_kernel(VnTermDedupArgs a) {
   const long j = (long)blockIdx.x * 256 + threadIdx.x;
   if (j >= a.U) return;
+  const Coef3 k = coef3(a);
   const float u = a.upack[j * 4];
   const float su = a.seed_u[j];
   const float acc = csr_walk(a, j, [&a](unsigned ru, unsigned k, unsigned p) { return stream_term(a, ru, k, p); });
-  a.seed_u[j] = su - dcubic(u, a.c) * acc;
+  if (a.acc_out) a.acc_out[j] = acc;                          // vn_coefgrad_points_kernel reads it (vn_set_coef_learn)
+  a.seed_u[j] = su - dcubic(u, k.c) * acc;
 }
 
 __global__ __launch_bounds__(256) void vn_nldiff_point_kernel(VnTermDedupArgs a) {
   const long j = (long)blockIdx.x * 256 + threadIdx.x;
   if (j >= a.U) return;
+  const Coef3 k = coef3(a);
   const int dim = a.dim;
   const f32x4t pd = *reinterpret_cast<const f32x4t*>(a.upack + j * 4);
   float acc = 0.f;
   if (a.stream) acc = csr_walk(a, j, [&a](unsigned ru, unsigned k, unsigned p) { return stream_term(a, ru, k, p); });
-  const float D = quad(pd[0], a.c);
+  const float D = quad(pd[0], k.c);
   float gs = 0.f;
   for (int d = 0; d < dim; ++d) {
     const float sg = a.seed_g[j * dim + d];
     gs += pd[1 + d] * sg;
     a.seed_g[j * dim + d] = D * sg;
   }
-  a.seed_u[j] = a.seed_u[j] + dquad(pd[0], a.c) * gs - acc;
+  if (a.acc_out) a.acc_out[j] = gs;                           // ... the dot product with the unscaled seed_g
+  a.seed_u[j] = a.seed_u[j] + dquad(pd[0], k.c) * gs - acc;
 }
 
 // ---- launches ----

@@ -74,6 +74,10 @@ _SIGS = {
     'vn_set_tf_weights': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     'vn_set_causal': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double]),
     'vn_causal_weights': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int32]),
+    'vn_set_coef_learn': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), C.c_double]),
+    'vn_get_coefs': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    'vn_set_coefs': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_bind_grad_buffer': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vn_grad': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -112,6 +116,9 @@ _SIGS = {
 }
 
 ABI_SYMBOLS = tuple(_SIGS.keys())
+
+# the _keep keys of the three polynomial terms, in the order of the coefficient index (vn_set_coef_learn)
+COEF_TERMS = ('react', 'nlflux', 'nldiff')
 
 
 class VNError(RuntimeError):
@@ -517,7 +524,10 @@ class VNEngine:
         if len(c) > 3:
             raise ValueError('%s, got %d' % (takes, len(c)))
         c = c + [0.0] * (3 - len(c))
-        if coef is None or clears(c, stream):
+        # (a term with a learnt coefficient stays registered whatever its values: set_coef_learn)
+        mask = getattr(self, '_coef_mask', None)
+        learnt = mask is not None and any(mask[3 * COEF_TERMS.index(key):3 * COEF_TERMS.index(key) + 3])
+        if coef is None or (clears(c, stream) and not learnt):
             self._keep.pop((key, batch), None)
             self._ck(fn(self.h, int(batch), None, None))
             return
@@ -552,6 +562,45 @@ class VNEngine:
         advection (None: no advection).  coef: up to three numbers (a shorter list is zero-padded)."""
         self._set_term('nldiff', self.lib.vn_set_nldiff, 'a diffusivity takes at most three coefficients (d0, d1, d2)', 'psi',
                        batch, psi, coef, lambda c, s: c == [1.0, 0.0, 0.0] and s is None)
+
+    def set_coef_learn(self, mask=None, init=None, lo=None, hi=None, lr=None):
+        """Inverse mode (vn_set_coef_learn): learn the masked entries of the nine polynomial coefficients -- index 0..2 reaction
+        (c1, c2, c3), 3..5 flux (f1, f2, f3), 6..8 diffusivity (d0, d1, d2) -- next to the parameters.  init: the nine starting
+        values, which every registered term of every batch then reads from the engine's device vector; lo / hi: the clamp (None:
+        unbounded; entries may be +-inf); lr: their Adam rate.  mask=None switches learning off and frees everything."""
+        if mask is None:
+            self._ck(self.lib.vn_set_coef_learn(self.h, None, None, None, None, 0.0))
+            self._coef_mask = None
+            return
+        def nine(a, fill, name):
+            v = np.full(9, fill, dtype=np.float64) if a is None else np.asarray(a, dtype=np.float64).reshape(-1)
+            if v.size != 9:
+                raise ValueError('%s must have nine entries (reaction, flux, diffusivity: three each), got %d' % (name, v.size))
+            return v
+        m = np.asarray(mask).reshape(-1)
+        if m.size != 9:
+            raise ValueError('mask must have nine entries (reaction, flux, diffusivity: three each), got %d' % m.size)
+        m = [1 if x else 0 for x in m]
+        if init is None or lr is None:
+            raise ValueError('set_coef_learn needs init (nine values) and lr')
+        v0, l, u = nine(init, 0.0, 'init'), nine(lo, -np.inf, 'lo'), nine(hi, np.inf, 'hi')
+        self._ck(self.lib.vn_set_coef_learn(self.h, (C.c_int32 * 9)(*m), (C.c_double * 9)(*v0), (C.c_double * 9)(*l),
+                                            (C.c_double * 9)(*u), float(lr)))
+        self._coef_mask = m
+
+    def get_coefs(self, grad=False):
+        """The nine coefficients at the current state (vn_get_coefs); grad=True: (coef, gradient of the last gradient evaluation)."""
+        c, g = (C.c_double * 9)(), (C.c_double * 9)()
+        self._ck(self.lib.vn_get_coefs(self.h, c, g if grad else None))
+        c = np.array(list(c), dtype=np.float64)
+        return (c, np.array(list(g), dtype=np.float64)) if grad else c
+
+    def set_coefs(self, coef):
+        """Overwrite the nine coefficients (vn_set_coefs): rounded to fp32, not clamped; the Adam slots stay."""
+        v = np.asarray(coef, dtype=np.float64).reshape(-1)
+        if v.size != 9:
+            raise ValueError('coef must have nine entries (reaction, flux, diffusivity: three each), got %d' % v.size)
+        self._ck(self.lib.vn_set_coefs(self.h, (C.c_double * 9)(*v)))
 
     def _n_k(self, batch):
         kept = self._keep.get(('int', batch))

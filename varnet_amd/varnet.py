@@ -796,7 +796,8 @@ class VarNet:
     def __init__(self, PDE, layerWidth=[20], modelId='MLP', activationFun=None, discNum=20,
                  bDiscNum=[], tDiscNum=[], MORdiscScheme=None, processors=None, controller=None,
                  integPnum=2, optimizer='adam', learning_rate=0.001, fluxBC=False, lbfgsLoss64=False,
-                 causal=None, causalSlabs=None, periodicDeriv=None, observations=None, obsWeight=None):
+                 causal=None, causalSlabs=None, periodicDeriv=None, observations=None, obsWeight=None,
+                 learnCoef=None, coefLr=None, coefBounds=None):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -858,6 +859,9 @@ class VarNet:
                     or not np.isfinite(float(periodicDeriv)) or float(periodicDeriv) < 0.0:
                 raise ValueError('periodicDeriv=%r must be a finite number >= 0' % (periodicDeriv,))
 
+        if learnCoef is not None and MORvar is not None:
+            raise NotImplementedError('learnCoef with model-order reduction is not supported: neither the three polynomial terms nor '
+                                      'the observations it needs are')
         # observations=... (extension; no reference counterpart): sensor data as linear functionals of the solution, fitted by a
         # misfit term obsWeight * O next to the PDE's loss (`obsData`)
         if observations is None:
@@ -868,6 +872,20 @@ class VarNet:
                 raise NotImplementedError('observations with model-order reduction are not supported: the observed points are '
                                           'assembled once, for all parameter batches, and carry no parameter inputs')
             self._check_obs_weight(1.0 if obsWeight is None else obsWeight)
+
+        # learnCoef=... (extension; no reference counterpart): inverse mode, the masked polynomial coefficients of the PDE's
+        # reaction / flux / diffusivity are learnt next to the network from the observations (`coefLearnData`)
+        self.coefLearn = self.coefLearnData(PDE, learnCoef, coefLr, coefBounds, learning_rate)
+        if self.coefLearn is not None:
+            if observations is None:
+                raise ValueError('learnCoef needs observations=...: without interior data every coefficient admits a solution of '
+                                 'the boundary value problem, so the loss cannot tell one value from another')
+            if optimizer.lower() != 'adam':
+                raise NotImplementedError('learnCoef with optimizer=%r: the coefficients are updated by the Adam step only (an L-BFGS '
+                                          'search over (parameters, coefficients) and an RMSProp update are not built)' % (optimizer,))
+            if causal is not None:
+                raise NotImplementedError('learnCoef with causal=%r: the causal weights are applied after the seeds the coefficient '
+                                          'gradient is reduced from' % (causal,))
 
         inpDim = dim + (1 if timeDependent else 0)
         if MORvar is not None:
@@ -909,6 +927,9 @@ class VarNet:
             raise NotImplementedError('causal=%r with towers: a rank\'s slab means would cover only its shard of the test '
                                       'functions, so the ranks together would train another objective than one rank'
                                       % (causal,))
+        if self.coefLearn is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
+            raise NotImplementedError('learnCoef with towers: the nine coefficient gradients are not part of the all-reduced '
+                                      'buffer, so every rank would follow its own shard')
         if isinstance(processors, (list, tuple)) and len(processors) > 1 and self.world == 1:
             # the reference's single-process multi-GPU call (TFModel.py:120-165): this process becomes the
             # controller of one forked child per GPU (varnet_amd/towers.py); it never touches the GPU itself
@@ -976,6 +997,10 @@ class VarNet:
             r = self.obsRows
             self.engine.set_observations(r['X'], r['value'], q=r['q'], dir=r['dir'], rowptr=r['rowptr'], wgt=r['wgt'],
                                          weight=self.obsWeight / self.world)
+        if self.coefLearn is not None:
+            # the engine owns the nine coefficients from here on: every batch registered later reads them from its device vector
+            cl = self.coefLearn
+            self.engine.set_coef_learn(cl['mask'], cl['init'], cl['lo'], cl['hi'], cl['lr'])
         self.tfData = self.engine       # name kept for scripts that poke at `VarNet.tfData`
         from .launch import mark_stage
         mark_stage('engine_ready')      # past the launcher's bootstrap deadline: a rank that trains for hours is healthy
@@ -1008,6 +1033,128 @@ class VarNet:
                         isSource=self.lossOpt['isSource'], integWflag=self.lossOpt['integWflag'],
                         learning_rate=self.learning_rate, device=device, activationFun=self.activationFun,
                         optimizer_name=self.optimizer)
+
+    # -- inverse mode: learnt PDE coefficients (extension) ------------------------------------------
+    COEF_KEYS = ('reaction', 'nlflux', 'nldiff')
+
+    @staticmethod
+    def _pde_coefs(PDE):
+        """(user-scale coefficients [9], engine scale [9]) of PDE: index 0..2 reaction, 3..5 flux, 6..8 diffusivity.  The engine
+        carries rate * c for a reaction with a scalar rate (`_assemble` folds it in), c itself with a rate field."""
+        c, scale = np.zeros(9), np.ones(9)
+        c[6] = 1.0
+        for g, (key, attr) in enumerate((('reaction', 'reactionCoef'), ('nlflux', 'nlfluxCoef'), ('nldiff', 'nldiffCoef'))):
+            if getattr(PDE, key, None) is not None:
+                v = [float(x) for x in getattr(PDE, attr)]
+                c[3 * g:3 * g + 3] = (v + [0.0] * 3)[:3]
+        if getattr(PDE, 'reaction', None) is not None and PDE.reactionRate is not None:
+            scale[0:3] = float(PDE.reactionRate)
+        return c, scale
+
+    @staticmethod
+    def coefLearnData(PDE, learnCoef, coefLr=None, coefBounds=None, learning_rate=0.001):
+        """(No reference counterpart: `VarNet(..., learnCoef=...)`.)  The registration of `vn_set_coef_learn` in the engine's
+        scale, or None without learnCoef: mask, init, lo, hi (nine entries each), lr, and `scale`, by which `coefficients()`
+        divides (the rate of a reaction with a scalar rate, 1 elsewhere).  learnCoef = {'reaction' | 'nlflux' | 'nldiff': True or
+        a 3-mask}; the PDE's own coefficients are the initial guess; coefLr defaults to the network's learning rate;
+        coefBounds = {key: [None | (lo, hi) x 3]} with None for an open side."""
+        keys = VarNet.COEF_KEYS
+        if learnCoef is None:
+            if coefLr is not None:
+                raise ValueError('coefLr=%r is an option of learnCoef=...' % (coefLr,))
+            if coefBounds is not None:
+                raise ValueError('coefBounds is an option of learnCoef=...')
+            return None
+        if not isinstance(learnCoef, dict) or not learnCoef:
+            raise ValueError('learnCoef must be a dict with keys among %s' % (keys,))
+        mask = np.zeros(9, dtype=bool)
+        for key, val in learnCoef.items():
+            if key not in keys:
+                raise ValueError('learnCoef: unknown key %r (the keys are %s)' % (key, keys))
+            if getattr(PDE, key, None) is None:
+                raise ValueError('learnCoef: the PDE has no %s term (ADPDE(..., %s=...))' % (key, key))
+            g = keys.index(key)
+            if val is True:
+                mask[3 * g:3 * g + 3] = True
+                continue
+            ok = isinstance(val, (list, tuple, np.ndarray)) and len(val) == 3 and \
+                all(isinstance(x, (bool, np.bool_)) or (isinstance(x, (int, np.integer)) and x in (0, 1)) for x in val)
+            if not ok:
+                raise ValueError('learnCoef[%r] must be True or a mask of three booleans, got %r' % (key, val))
+            mask[3 * g:3 * g + 3] = [bool(x) for x in val]
+        if not mask.any():
+            raise ValueError('learnCoef selects no coefficient')
+        lr = learning_rate if coefLr is None else coefLr
+        if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not np.isfinite(lr) or lr <= 0:
+            raise ValueError('coefLr=%r must be a finite number > 0' % (lr,))
+        c, scale = VarNet._pde_coefs(PDE)
+        if mask[0:3].any() and scale[0] == 0.0:
+            raise ValueError('learnCoef[\'reaction\'] with a reaction rate of 0: the engine learns rate * c and coefficients() '
+                             'divides by the rate')
+        lo, hi = np.full(9, -np.inf), np.full(9, np.inf)
+        if coefBounds is not None:
+            if not isinstance(coefBounds, dict):
+                raise ValueError('coefBounds must be a dict with keys among %s' % (keys,))
+            for key, val in coefBounds.items():
+                if key not in keys:
+                    raise ValueError('coefBounds: unknown key %r (the keys are %s)' % (key, keys))
+                if not isinstance(val, (list, tuple)) or len(val) != 3:
+                    raise ValueError('coefBounds[%r] must list three entries, each None or (lo, hi)' % (key,))
+                g = keys.index(key)
+                for m, bd in enumerate(val):
+                    if bd is None:
+                        continue
+                    i = 3 * g + m
+                    if not mask[i]:
+                        raise ValueError('coefBounds[%r][%d] bounds a coefficient that learnCoef does not select' % (key, m))
+                    if not isinstance(bd, (list, tuple)) or len(bd) != 2:
+                        raise ValueError('coefBounds[%r][%d] must be None or (lo, hi), got %r' % (key, m, bd))
+                    a = -np.inf if bd[0] is None else bd[0]
+                    b = np.inf if bd[1] is None else bd[1]
+                    for x in (a, b):
+                        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or np.isnan(x):
+                            raise ValueError('coefBounds[%r][%d] must hold numbers or None, got %r' % (key, m, bd))
+                    if a > b:
+                        raise ValueError('coefBounds[%r][%d]: lower bound %r above upper bound %r' % (key, m, a, b))
+                    if not a <= c[i] <= b:
+                        raise ValueError('coefBounds[%r][%d] = %r excludes the initial guess %r' % (key, m, bd, float(c[i])))
+                    ea, eb = float(a) * scale[i], float(b) * scale[i]
+                    lo[i], hi[i] = min(ea, eb), max(ea, eb)
+        return dict(mask=[int(x) for x in mask], init=c * scale, lo=lo, hi=hi, lr=float(lr), scale=scale)
+
+    def _coef_dict(self, v):
+        return {k: [float(x) for x in v[3 * g:3 * g + 3]] for g, k in enumerate(self.COEF_KEYS)}
+
+    def coefficients(self):
+        """{'reaction': [c1, c2, c3], 'nlflux': [f1, f2, f3], 'nldiff': [d0, d1, d2]} at the current state: the learnt values
+        with learnCoef (a reaction with a scalar rate is divided by it: the engine learns rate * c), else the PDE's own."""
+        if self.coefLearn is None:
+            return self._coef_dict(self._pde_coefs(self.PDE)[0])
+        return self._coef_dict(self.engine.get_coefs() / self.coefLearn['scale'])
+
+    def coefGrad(self):
+        """d loss / d coefficient of the last gradient evaluation, in the layout of `coefficients()` (zeros where not learnt)."""
+        if self.coefLearn is None:
+            raise ValueError('coefGrad: this instance learns no coefficients (learnCoef=...)')
+        return self._coef_dict(self.engine.get_coefs(grad=True)[1] * self.coefLearn['scale'])
+
+    def setCoefficients(self, coef):
+        """Overwrite coefficients between train() calls: {'reaction' | 'nlflux' | 'nldiff': three numbers}; keys left out keep
+        their values.  Not clamped to coefBounds (the next update is)."""
+        if self.coefLearn is None:
+            raise ValueError('setCoefficients: this instance learns no coefficients (learnCoef=...)')
+        if not isinstance(coef, dict):
+            raise ValueError('setCoefficients takes a dict with keys among %s' % (self.COEF_KEYS,))
+        v = self.engine.get_coefs() / self.coefLearn['scale']
+        for key, val in coef.items():
+            if key not in self.COEF_KEYS:
+                raise ValueError('setCoefficients: unknown key %r (the keys are %s)' % (key, self.COEF_KEYS))
+            a = np.asarray(val, dtype=np.float64).reshape(-1)
+            if a.size != 3 or not np.all(np.isfinite(a)):
+                raise ValueError('setCoefficients[%r] must hold three finite numbers, got %r' % (key, val))
+            g = self.COEF_KEYS.index(key)
+            v[3 * g:3 * g + 3] = a
+        self.engine.set_coefs(v * self.coefLearn['scale'])
 
     # -- causal time-slab weights (extension) ------------------------------------------------------
     @staticmethod
@@ -2063,6 +2210,11 @@ class VarNet:
                         trainW, w_eff, _ = set_train_weights(tData, weight)
             epoch = first + nblk
         trainRes.flushPlots()
+        if self.coefLearn is not None and self.rank == 0:
+            cl, cur = self.coefLearn, self.coefficients()
+            trainRes.writeCase('Learnt coefficients: mask %s, initial %s, final %s\n'
+                               % (cl['mask'], [float(x) for x in cl['init'] / cl['scale']],
+                                  [x for k in self.COEF_KEYS for x in cur[k]]))
         return trainRes
 
     # -- checkpoints ----------------------------------------------------------------------------------
@@ -2098,6 +2250,9 @@ class VarNet:
         if slot[0] == 'Adam':
             out['beta1_power'] = np.float32(0.9 ** (step + 1))       # TF keeps beta^(t+1) for the next update
             out['beta2_power'] = np.float32(0.999 ** (step + 1))
+        if getattr(self, 'coefLearn', None) is not None:
+            # the nine values in the engine's scale (vn_get_coefs); their Adam slots have no entry point and restart from zero
+            out['pde_coefficients'] = np.asarray(self.engine.get_coefs(), dtype=np.float64)
         return out
 
     def restore_arrays(self, arrays):
@@ -2121,6 +2276,8 @@ class VarNet:
         step = np.array([int(arrays['global_step']) if 'global_step' in arrays else 0], dtype=np.int64)
         blob = np.concatenate([step.view(np.uint8), np.concatenate(th + m + v).astype(np.float32).view(np.uint8)])
         self.engine.import_state(blob)
+        if getattr(self, 'coefLearn', None) is not None and 'pde_coefficients' in arrays:
+            self.engine.set_coefs(np.asarray(arrays['pde_coefficients'], dtype=np.float64).reshape(-1))
 
     def saveModel(self, epoch):
         """`saver.save(sess, 'best_model', global_step=epoch)` with max_to_keep=2 (TFModel.py:307,
@@ -2442,13 +2599,14 @@ class VarNet:
                 diff, vel, src = self.PDEinpData(Input, inpArg)
                 Inp = np.hstack([Input, cols])
             rkw = {}
+            cur = self.coefficients() if getattr(self, 'coefLearn', None) is not None else None      # learnt: the current values
             if getattr(PDE, 'reaction', None) is not None:           # res += rate p(u)
-                rkw['reaction'] = (self._reaction_rate(Input).reshape(-1), PDE.reactionCoef)
+                rkw['reaction'] = (self._reaction_rate(Input).reshape(-1), cur['reaction'] if cur else PDE.reactionCoef)
             if getattr(PDE, 'nlflux', None) is not None:             # res -= F'(u) w . grad u + F(u) div w
                 w_rows, divw_rows = self._nlflux_field(Input)
-                rkw['nlflux'] = (w_rows, PDE.nlfluxCoef, divw_rows)
+                rkw['nlflux'] = (w_rows, cur['nlflux'] if cur else PDE.nlfluxCoef, divw_rows)
             if getattr(PDE, 'nldiff', None) is not None:             # div(kappa D(u) grad u); the advection stays v . grad u
-                rkw['nldiff'] = PDE.nldiffCoef
+                rkw['nldiff'] = cur['nldiff'] if cur else PDE.nldiffCoef
             u, r = self.engine.residual(Inp, diff, vel, src, diff_dx, fp64=fp64, **rkw)
             cApp = u.cpu().numpy().astype(np.float64).reshape(-1, 1)
             resVec = r.cpu().numpy().astype(np.float64).reshape(-1, 1)
