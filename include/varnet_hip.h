@@ -366,6 +366,39 @@ int vn_get_coefs(vn_engine* h, double coef[9], double grad[9]);
 /* Overwrites all nine coefficients (rounded to fp32, NOT clamped); the Adam slots stay.  Non-finite: VN_EINVAL; learning off:
  * VN_ESTATE.  Invalidates the snapshot of vn_state_snapshot. */
 int vn_set_coefs(vn_engine* h, const double coef[9]);
+/* Source identification: the source of a batch is s0 + sum_j a_j phi_j over a basis of J per-row streams, and the amplitudes a_j
+ * are learnt next to the parameters from the observations.
+ * vn_set_source_basis registers the basis of one batch: phi_dev is [J, n_k * integ_num] fp32 on the device, stream-major (every
+ * stream contiguous); the streams are read on every step and must stay valid while registered.  phi_dev == NULL or J == 0 clears
+ * the registration, and so does vn_set_interior of that batch.  A call replaces the previous registration, also when it fails.
+ * Needs cfg.has_source (VN_ESTATE otherwise; pass a zero source stream when the PDE has no source); J > VN_SRC_MAX: VN_EINVAL.
+ * Without vn_set_source_learn a registered basis changes nothing: the batch's source is the stream of vn_set_interior. */
+#define VN_SRC_MAX 64
+int vn_set_source_basis(vn_engine* h, int32_t batch, const float* phi_dev, int32_t J);
+/* The amplitudes are engine-wide, like the nine coefficients of vn_set_coef_learn: while learning is on the engine owns ONE device
+ * vector of J fp32 amplitudes (`init`, rounded once), their two Adam slots and a snapshot copy of the three; it outlives a
+ * re-registration of the batches.  Every evaluation of a batch with a basis (vn_grad, vn_train_step / _epoch, vn_eval_loss,
+ * vn_objective_f64) first forms s_mix[r] = s0[r] + sum_j a_j phi_j[r] (fp32, j ascending, one fused multiply-add per stream) and
+ * reads it in place of the batch's source; a batch whose basis has another J makes the step return VN_EINVAL.
+ *   d loss / d a_j = - sum_r s_r N_p phi_j[r]   (s_r: the tangent seed of row r before D(u) rescales it)
+ * is formed inside vn_grad / vn_train_step / vn_train_epoch for the masked entries, in a fixed order without atomics (two
+ * evaluations: the same bits); the single-launch 8-wave route runs its two-pass sequence for such a batch.  vn_apply and the
+ * fused train steps update the masked entries with the arithmetic of the parameters' Adam update (the engine's beta1, beta2, eps,
+ * the shared step counter -- shared with vn_set_coef_learn too --, the rate `lr`), then clamp them to [lo, hi] (+-inf: unbounded).
+ * Unmasked entries take part in the source at their init value and never change a bit.
+ * vn_state_snapshot / vn_state_rollback carry amplitudes and slots; vn_state_size / _export / _import keep their layout.
+ *   mask   J ints (non-zero: learnt), or NULL: learning off, everything freed, every result bit for bit what it was before.
+ *   init, lo, hi   J doubles each.  Non-finite init, NaN bounds, lo > hi, lr not finite or <= 0, J outside 1..VN_SRC_MAX: VN_EINVAL.
+ * Refused with VN_EUNSUPPORTED for the reasons of vn_set_coef_learn: an RMSProp or L-BFGS engine; a handle that has a communicator
+ * (and vn_comm_init while learning is on); a batch with vn_set_tf_weights / vn_set_causal (here, in those calls and in the steps).
+ * The call invalidates the snapshot of vn_state_snapshot and the L-BFGS (f_k, g_k). */
+int vn_set_source_learn(vn_engine* h, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi, double lr);
+/* The J amplitudes now (synchronises) and, when grad is not NULL, the amplitude gradient of the last gradient evaluation (zeros for
+ * unmasked entries and before the first one).  Learning off: VN_ESTATE; J not the engine's: VN_EINVAL. */
+int vn_get_source_amps(vn_engine* h, double* amp, double* grad, int32_t J);
+/* Overwrites all J amplitudes (rounded to fp32, NOT clamped); the Adam slots stay.  Non-finite: VN_EINVAL; learning off: VN_ESTATE.
+ * Invalidates the snapshot of vn_state_snapshot. */
+int vn_set_source_amps(vn_engine* h, const double* amp, int32_t J);
 /* updateDictFields('trainW') (VarNetUtility.py:921-922); the caller applies the
  * w[0:2] /= batchNum*puNum rule (VarNetUtility.py:900-901). */
 int vn_set_weights(vn_engine* h, const double w[3]);

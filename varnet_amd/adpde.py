@@ -1,7 +1,7 @@
 """
 Advection-diffusion(-reaction) PDE container: `ADPDE(domain, diff, vel, source, timeDependent, tInterval,
-BCs, IC, cEx, MORvar, d_diff, reaction, nlflux, nldiff, periodic)` -- /root/reference/ADPDE.py:56-246 restated (plot helpers are
-out of scope).
+BCs, IC, cEx, MORvar, d_diff, reaction, nlflux, nldiff, periodic, sourceBasis, sourceAmp)` -- /root/reference/ADPDE.py:56-246
+restated (plot helpers are out of scope).
 
     c_t = div(diff D(c) grad c) - vel . grad c - div(w F(c)) + source + rate * p(c),    a * dc/dn + b * c = g  on each edge,
 
@@ -48,10 +48,16 @@ class ADPDE:
     dc/dn(x_A) = dc/dn(x_A + s) with s the translation that maps edge A onto edge B.  `Domain1D`: the pair is (0, 1), in either
     order.  `PolygonDomain2D`: the two edges have equal length and opposite outward normals.  A paired indicator has no [a, b, g]:
     its `BCs` entry stays empty, and `BCtype` reports 'Periodic' for it.  None (the default): no pairs.
+
+    sourceBasis=[phi_1, ..., phi_J] with sourceAmp=[a_1, ..., a_J] (default: zeros) makes the source `source + sum_j a_j phi_j`:
+    every phi_j is a callable f(x[, t]) returning a column, evaluated like `source`; 1 <= J <= 64.  The amplitudes can be learnt
+    from observations (`VarNet(..., learnSource=...)`: source identification); without that the sum is part of the source.
     """
+    SRC_MAX = 64
 
     def __init__(self, domain, diff, vel, source=0.0, timeDependent=False, tInterval=None,
-                 BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None, nlflux=None, nldiff=None, periodic=None):
+                 BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None, nlflux=None, nldiff=None, periodic=None,
+                 sourceBasis=None, sourceAmp=None):
         # the reference ignores the `timeDependent` argument (ADPDE.py:108-109)
         timeDependent = tInterval is not None
 
@@ -142,6 +148,32 @@ class ADPDE:
             if MORvar is not None:
                 raise NotImplementedError('periodic boundaries with model-order reduction are not supported: the paired rows are '
                                           'assembled once, for all parameter batches, and carry no parameter inputs')
+
+        if sourceBasis is None:
+            if sourceAmp is not None:
+                raise ValueError('sourceAmp is an option of sourceBasis=[phi_1, ..., phi_J]!')
+        else:
+            if not isinstance(sourceBasis, (list, tuple)) or len(sourceBasis) == 0:
+                raise ValueError('sourceBasis must be a non-empty list of callables [phi_1, ..., phi_J]!')
+            if len(sourceBasis) > self.SRC_MAX:
+                raise ValueError('sourceBasis holds %d functions, at most %d are supported!' % (len(sourceBasis), self.SRC_MAX))
+            for j, f in enumerate(sourceBasis):
+                if not callable(f):
+                    raise ValueError('sourceBasis[%d] must be callable, like a source function!' % j)
+            if sourceAmp is None:
+                sourceAmp = np.zeros(len(sourceBasis))
+            try:
+                sourceAmp = np.array(np.reshape(np.asarray(sourceAmp, dtype=float), -1))
+            except (TypeError, ValueError):
+                raise ValueError('sourceAmp must be a list of %d numbers, one per function of sourceBasis!' % len(sourceBasis))
+            if sourceAmp.size != len(sourceBasis):
+                raise ValueError('sourceAmp holds %d values for the %d functions of sourceBasis!' % (sourceAmp.size, len(sourceBasis)))
+            if not np.all(np.isfinite(sourceAmp)):
+                raise ValueError('sourceAmp must be finite!')
+            if MORvar is not None:
+                raise NotImplementedError('a source basis with model-order reduction is not supported: parametric basis functions '
+                                          'are out of scope (the basis streams are assembled once, for all parameter batches)')
+            sourceBasis = list(sourceBasis)
 
         dim = domain.dim
 
@@ -277,6 +309,10 @@ class ADPDE:
         self.cEx = cEx
         self.MORvar = MORvar
         self.periodic = periodic
+        # source basis: the J callables and their amplitudes (the initial guess when they are learnt); no attributes without one
+        if sourceBasis is not None:
+            self.sourceBasis = sourceBasis
+            self.sourceAmp = sourceAmp
 
     @staticmethod
     def _check_periodic(periodic, domain, BCs):

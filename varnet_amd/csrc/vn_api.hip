@@ -11,6 +11,7 @@
 #include "vn_taylor16.h"
 #include "vn_terms.h"
 #include "vn_coef.h"
+#include "vn_source.h"
 #include "vn_weights.h"
 #include "vn_split16.h"
 
@@ -71,6 +72,8 @@ struct Batch {
   const float* Input = nullptr;
   const float* gcoef = nullptr;
   const float* source = nullptr;
+  const float* sb_phi = nullptr;   // [sb_J, n_k*integ_num] basis streams of the source (vn_set_source_basis), caller-owned; nullptr: none
+  int sb_J = 0;
   const float* detJv = nullptr;
   const float* Nrow = nullptr;
   const float* dNtrow = nullptr;
@@ -227,6 +230,17 @@ struct vn_engine {
   float* cl_part = nullptr;                       // [VN_COEF_MAXBLK, 9] partials of the reduction
   int cl_blocks = 0;                              // partials the current gradient evaluation wrote (0: the batch carries no term)
   float* cl_acc = nullptr; long cl_acc_cap = 0;   // [3, U] accR_j, accF_j, gs_j of the de-duplicated step
+  // source identification (vn_set_source_learn, vn_source.hip): the amplitudes of the batches' source bases, engine-wide
+  bool sl_on = false;
+  int sl_J = 0;
+  unsigned long long sl_mask = 0;                 // bit j: amplitude j is learnt
+  double sl_lr = 0.0;
+  float* sl_state = nullptr;                      // [6 * 64] (amp | m | v) at stride 64, then their copy of vn_state_snapshot
+  float* sl_bounds = nullptr;                     // [2 * 64] (lo | hi)
+  double* sl_grad = nullptr;                      // [64] amplitude gradient of the last gradient evaluation
+  float* sl_part = nullptr;                       // [VN_SRC_MAXBLK, J] partials of the reduction
+  int sl_blocks = 0;                              // partials the current gradient evaluation wrote (0: the batch has no basis)
+  float* sl_mix = nullptr; long sl_mix_cap = 0;   // [nT] s0 + sum_j a_j phi_j of the batch being evaluated
   float* snap = nullptr;       // vn_state_snapshot: device copy of (theta | m | v), 3 P floats
   int64_t snap_step = -1;      // step counter at the snapshot (-1: none)
   PointRoute point_route = PointRoute::automatic;   // vn_debug_point_route(route & 3)
@@ -397,7 +411,11 @@ int check_batch(vn_engine* h, int32_t batch) {
 
 inline const float* bi_x(const vn_engine* h, const Batch& b) { return b.biInput ? b.biInput : h->biInput; }
 inline const float* bi_y(const vn_engine* h, const Batch& b) { return b.biLabel ? b.biLabel : h->biLabel; }
-inline const float* batch_src(const vn_engine* h, const Batch& b) { return h->cfg.has_source ? b.source : nullptr; }
+// (while amplitudes are learnt, a batch with a basis reads the mixed stream source_mix formed at the start of the evaluation)
+inline bool src_learnt(const vn_engine* h, const Batch& b) { return h->sl_on && b.sb_phi; }
+inline const float* batch_src(const vn_engine* h, const Batch& b) {
+  return !h->cfg.has_source ? nullptr : src_learnt(h, b) ? h->sl_mix : b.source;
+}
 inline const float* fe_w(const vn_engine* h) { return (h->cfg.has_integw && h->has_feW) ? h->feW : nullptr; }
 
 inline bool on_8wave(const vn_engine* h) { return h->route == Route::fused8 || h->route == Route::twopass; }
@@ -559,6 +577,12 @@ int terms_fold_rows(vn_engine* h, const Batch& b) {
 
 // After a vn_seed_launch that produced seeds: D(u) rescales the tangent seed last, the flux term's value seed reads it unscaled
 int terms_seed_rows(vn_engine* h, const Batch& b) {
+  if (src_learnt(h, b)) {                          // source identification: the amplitude sums read udbar before D(u) rescales it
+    VnSrcGradArgs g{};
+    g.udbar = h->udbar; g.Nrow = b.Nrow; g.feN = h->feN; g.phi = b.sb_phi; g.J = b.sb_J;
+    g.nT = b.n_k * h->cfg.integ_num; g.q = h->cfg.integ_num; g.mask = h->sl_mask; g.part = h->sl_part;
+    HIPCHK(vn_srcgrad_rows_launch(g, &h->sl_blocks, h->stream));
+  }
   if (h->cl_on && has_terms(b)) {                  // inverse mode: the coefficient sums read udbar before D(u) rescales it
     VnCoefRowsArgs c{};
     c.u = h->u; c.udbar = h->udbar; c.nT = b.n_k * h->cfg.integ_num; c.q = h->cfg.integ_num;
@@ -957,6 +981,12 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
   if (int rc = weights_stage(h, b, a.lossVec, VN_DEDUP_TFB, a.stf, a.part, false)) return rc;   // stf[k] *= omega_k before the gather
   HIPCHK(vn_dedup_gather_launch(a, h->stream));
   if (int rc = terms_gather_dedup(h, b, a)) return rc;
+  if (src_learnt(h, b)) {                          // source identification: a row's seed is stf[k] x its quadrature weight
+    VnSrcGradArgs g{};
+    g.stf = a.stf; g.feW = fe_w(h); g.feN = h->feN; g.phi = b.sb_phi; g.J = b.sb_J;
+    g.nT = b.n_k * h->cfg.integ_num; g.q = h->cfg.integ_num; g.mask = h->sl_mask; g.part = h->sl_part;
+    HIPCHK(vn_srcgrad_rows_launch(g, &h->sl_blocks, h->stream));
+  }
   VnFusedArgs f = fused_args(h, &b);
   f.X = b.Xu; f.G = h->dd_sg; f.nT = b.U;
   f.partial = h->dd_partial; f.losspart = lp;
@@ -997,6 +1027,57 @@ void coef_free(vn_engine* h) {
   h->cl_state = nullptr; h->cl_grad = nullptr; h->cl_part = nullptr; h->cl_acc = nullptr; h->cl_acc_cap = 0;
   h->cl_on = false; h->cl_mask = 0; h->cl_blocks = 0;
 }
+
+// Source identification, first thing in an evaluation of batch b: the batch's basis must be the engine's, then s_mix is formed
+int source_mix(vn_engine* h, const Batch& b, int batch) {
+  if (!src_learnt(h, b)) return VN_OK;
+  if (b.sb_J != h->sl_J)
+    return fail(VN_EINVAL, "batch %d has a source basis of %d streams, the learnt amplitudes (vn_set_source_learn) are %d", batch, b.sb_J, h->sl_J);
+  if (h->route == Route::fused4 && !b.Xu)
+    return fail(VN_EUNSUPPORTED, "learnt source amplitudes are not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its "
+                                 "single launch leaves no row seeds to reduce; every other kernel family carries them");
+  const long nT = b.n_k * h->cfg.integ_num;
+  if (nT <= 0) return VN_OK;
+  if (int rc = ensure(&h->sl_mix, &h->sl_mix_cap, nT)) return rc;
+  VnSrcMixArgs a{};
+  a.s0 = b.source; a.phi = b.sb_phi; a.amp = h->sl_state; a.J = b.sb_J; a.nT = nT; a.out = h->sl_mix;
+  HIPCHK(vn_source_mix_launch(a, h->stream));
+  return VN_OK;
+}
+
+// After the last kernel of a gradient evaluation that reads s_mix: the partials folded into sl_grad (zeros when the batch has no
+// basis), and with `update` the Adam step of the masked amplitudes at step counter t -- coef_finish's sibling
+int source_finish(vn_engine* h, bool fold, bool update, double t) {
+  VnSrcApplyArgs a{};
+  a.J = h->sl_J;
+  if (fold) {
+    if (h->sl_blocks <= 0) {
+      HIPCHK(hipMemsetAsync(h->sl_part, 0, (size_t)h->sl_J * sizeof(float), h->stream));
+      h->sl_blocks = 1;
+    }
+    a.part = h->sl_part; a.blocks = h->sl_blocks;
+  }
+  a.grad = h->sl_grad; a.amp = h->sl_state; a.m = h->sl_state + VN_SRC_JMAX; a.v = h->sl_state + 2 * VN_SRC_JMAX;
+  a.lo = h->sl_bounds; a.hi = h->sl_bounds + VN_SRC_JMAX;
+  a.mask = h->sl_mask;
+  a.update = update ? 1 : 0;
+  if (update) {
+    a.lr_t = (float)(h->sl_lr * std::sqrt(1.0 - std::pow(h->cfg.beta2, t)) / (1.0 - std::pow(h->cfg.beta1, t)));
+    a.b1 = (float)h->cfg.beta1; a.b2 = (float)h->cfg.beta2; a.eps = (float)h->cfg.eps;
+  }
+  HIPCHK(vn_source_apply_launch(a, h->stream));
+  return VN_OK;
+}
+
+void source_free(vn_engine* h) {
+  for (void* p : {(void*)h->sl_state, (void*)h->sl_bounds, (void*)h->sl_grad, (void*)h->sl_part, (void*)h->sl_mix})
+    if (p) (void)hipFree(p);
+  h->sl_state = nullptr; h->sl_bounds = nullptr; h->sl_grad = nullptr; h->sl_part = nullptr; h->sl_mix = nullptr; h->sl_mix_cap = 0;
+  h->sl_on = false; h->sl_J = 0; h->sl_mask = 0; h->sl_blocks = 0;
+}
+
+constexpr const char* kSrcWeights = "learnt source amplitudes (vn_set_source_learn) next to per-test-function loss weights (vn_set_tf_weights / "
+                                    "vn_set_causal, batch %d): the weights are applied after the seeds the amplitude reduction reads";
 
 constexpr const char* kCoefWeights = "learnt coefficients (vn_set_coef_learn) next to per-test-function loss weights (vn_set_tf_weights / "
                                      "vn_set_causal, batch %d): the weights are applied after the seeds the coefficient reduction reads";
@@ -1163,6 +1244,7 @@ int vn_destroy(vn_engine* h) {
   if (h->lb.out) (void)hipHostFree(h->lb.out);
   vn_obj64_free(h->o64);
   coef_free(h);
+  source_free(h);
   for (Batch& b : h->batches) {
     if (b.gcsr) (void)hipFree(b.gcsr);
     clear_weights(b);
@@ -1274,6 +1356,8 @@ int vn_state_snapshot(vn_engine* h) {
   HIPCHK(hipMemcpyAsync(h->snap + 2 * (size_t)h->net.P, h->v, nb, hipMemcpyDeviceToDevice, h->stream));
   if (h->cl_on)
     HIPCHK(hipMemcpyAsync(h->cl_state + 3 * VN_COEF_N, h->cl_state, 3 * VN_COEF_N * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  if (h->sl_on)
+    HIPCHK(hipMemcpyAsync(h->sl_state + 3 * VN_SRC_JMAX, h->sl_state, 3 * VN_SRC_JMAX * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   h->snap_step = h->step;
   return VN_OK;
 }
@@ -1289,6 +1373,8 @@ int vn_state_rollback(vn_engine* h) {
   HIPCHK(hipMemcpyAsync(h->v, h->snap + 2 * (size_t)h->net.P, nb, hipMemcpyDeviceToDevice, h->stream));
   if (h->cl_on)
     HIPCHK(hipMemcpyAsync(h->cl_state, h->cl_state + 3 * VN_COEF_N, 3 * VN_COEF_N * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  if (h->sl_on)
+    HIPCHK(hipMemcpyAsync(h->sl_state, h->sl_state + 3 * VN_SRC_JMAX, 3 * VN_SRC_JMAX * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   h->step = h->snap_step;
   return VN_OK;
 }
@@ -1347,6 +1433,7 @@ int vn_set_interior(vn_engine* h, int32_t batch, const float* Input, const float
   b.Nrow = N_rows; b.dNtrow = dNt_rows; b.n_k = n_k; b.set = true;
   b.Xu = nullptr; b.uid = nullptr; b.rowptr = nullptr; b.rowidx = nullptr; b.U = 0;   // re-register with vn_set_dedup
   b.biInput = nullptr; b.biLabel = nullptr;                                            // ... and vn_set_batch_bic
+  b.sb_phi = nullptr; b.sb_J = 0;                                                      // ... and vn_set_source_basis
   const Batch fresh;
   b.react = fresh.react; b.nlflux = fresh.nlflux; b.nldiff = fresh.nldiff;             // ... and the three term setters
   clear_weights(b);                                                                    // ... and vn_set_tf_weights / vn_set_causal
@@ -1538,6 +1625,106 @@ int vn_set_coefs(vn_engine* h, const double coef[9]) {
   return VN_OK;
 }
 
+// ---- source identification: basis streams per batch, amplitudes on the device, learnt next to the parameters (vn_source.hip) ----
+int vn_set_source_basis(vn_engine* h, int32_t batch, const float* phi_dev, int32_t J) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
+    return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
+  Batch& b = h->batches[batch];
+  lbfgs_invalidate(h, batch);
+  b.sb_phi = nullptr; b.sb_J = 0;                  // a call replaces the previous registration, also when it fails
+  if (!phi_dev || J == 0) return VN_OK;
+  if (J < 0 || J > VN_SRC_MAX) return fail(VN_EINVAL, "a source basis has 1 to %d streams, got %d", VN_SRC_MAX, J);
+  if (!h->cfg.has_source)
+    return fail(VN_ESTATE, "vn_set_source_basis needs an engine created with has_source = 1 (pass a zero source stream to "
+                           "vn_set_interior when the PDE has none)");
+  if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no source to integrate", batch);
+  b.sb_phi = phi_dev; b.sb_J = J;
+  return VN_OK;
+}
+
+int vn_set_source_learn(vn_engine* h, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi, double lr) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  (void)hipGetLastError();
+  HIPCHK(hipSetDevice(h->cfg.device));
+  h->snap_step = -1;
+  lbfgs_invalidate(h);
+  if (!mask) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    source_free(h);
+    return VN_OK;
+  }
+  if (!init || !lo || !hi) return fail(VN_EINVAL, "null argument");
+  if (J < 1 || J > VN_SRC_MAX) return fail(VN_EINVAL, "1 to %d source amplitudes can be learnt, got %d", VN_SRC_MAX, J);
+  if (h->cfg.optimizer != VN_OPT_ADAM)
+    return fail(VN_EUNSUPPORTED, "vn_set_source_learn on %s engine: the amplitudes are updated with the arithmetic of the Adam step only%s",
+                is_lbfgs(h) ? "an L-BFGS" : "an RMSProp", is_lbfgs(h) ? " (vn_lbfgs_step searches over the parameters alone)" : "");
+  if (h->comm)
+    return fail(VN_EUNSUPPORTED, "vn_set_source_learn under a communicator: the amplitude gradients are not in the all-reduced "
+                                 "buffer, so every rank would follow its own shard's");
+  for (size_t i = 0; i < h->batches.size(); ++i)
+    if (has_weights(h->batches[i])) return fail(VN_EUNSUPPORTED, kSrcWeights, (int)i);
+  if (!(std::isfinite(lr) && lr > 0.0)) return fail(VN_EINVAL, "amplitude learning rate %g must be finite and > 0", lr);
+  for (int i = 0; i < J; ++i) {
+    if (!std::isfinite(init[i])) return fail(VN_EINVAL, "initial amplitude %d = %g must be finite", i, init[i]);
+    if (std::isnan(lo[i]) || std::isnan(hi[i]) || lo[i] > hi[i])
+      return fail(VN_EINVAL, "bounds of amplitude %d: [%g, %g] is no interval", i, lo[i], hi[i]);
+  }
+  if (!h->sl_state) {
+    hipError_t e = hipMalloc((void**)&h->sl_state, 6 * VN_SRC_JMAX * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->sl_bounds, 2 * VN_SRC_JMAX * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->sl_grad, VN_SRC_JMAX * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->sl_part, (size_t)VN_SRC_MAXBLK * VN_SRC_JMAX * sizeof(float));
+    if (e != hipSuccess) { (void)hipGetLastError(); source_free(h); return fail(VN_ENOMEM, "vn_set_source_learn: %s", hipGetErrorString(e)); }
+  }
+  float st[6 * VN_SRC_JMAX] = {}, bd[2 * VN_SRC_JMAX] = {};
+  h->sl_mask = 0;
+  for (int i = 0; i < J; ++i) {
+    st[i] = (float)init[i];
+    bd[i] = (float)lo[i]; bd[VN_SRC_JMAX + i] = (float)hi[i];
+    if (mask[i]) h->sl_mask |= 1ull << i;
+  }
+  h->sl_lr = lr;
+  h->sl_J = J;
+  HIPCHK(hipMemcpyAsync(h->sl_state, st, sizeof st, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->sl_bounds, bd, sizeof bd, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(h->sl_grad, 0, VN_SRC_JMAX * sizeof(double), h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));      // (st, bd leave scope)
+  h->sl_on = true;
+  h->sl_blocks = 0;
+  return VN_OK;
+}
+
+int vn_get_source_amps(vn_engine* h, double* amp, double* grad, int32_t J) {
+  if (!h || !amp) return fail(VN_EINVAL, "null argument");
+  if (!h->sl_on) return fail(VN_ESTATE, "no learnt source amplitudes (call vn_set_source_learn first)");
+  if (J != h->sl_J) return fail(VN_EINVAL, "the engine holds %d source amplitudes, the caller asks for %d", h->sl_J, J);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  float c[VN_SRC_JMAX];
+  HIPCHK(hipMemcpyAsync(c, h->sl_state, (size_t)J * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (grad) HIPCHK(hipMemcpyAsync(grad, h->sl_grad, (size_t)J * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < J; ++i) amp[i] = (double)c[i];
+  return VN_OK;
+}
+
+int vn_set_source_amps(vn_engine* h, const double* amp, int32_t J) {
+  if (!h || !amp) return fail(VN_EINVAL, "null argument");
+  if (!h->sl_on) return fail(VN_ESTATE, "no learnt source amplitudes (call vn_set_source_learn first)");
+  if (J != h->sl_J) return fail(VN_EINVAL, "the engine holds %d source amplitudes, the caller passes %d", h->sl_J, J);
+  float c[VN_SRC_JMAX];
+  for (int i = 0; i < J; ++i) {
+    if (!std::isfinite(amp[i])) return fail(VN_EINVAL, "amplitude %d = %g must be finite", i, amp[i]);
+    c[i] = (float)amp[i];
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipMemcpyAsync(h->sl_state, c, (size_t)J * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->snap_step = -1;
+  lbfgs_invalidate(h);
+  return VN_OK;
+}
+
 // vn_set_tf_weights / vn_set_causal: what both check before they touch the batch; *clear: the call unregisters
 static int weights_common(vn_engine* h, int32_t batch, bool clear, const char* who) {
   if (!h) return fail(VN_EINVAL, "null handle");
@@ -1552,6 +1739,7 @@ static int weights_common(vn_engine* h, int32_t batch, bool clear, const char* w
   }
   if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no test function to weight", batch);
   if (h->cl_on) return fail(VN_EUNSUPPORTED, kCoefWeights, batch);
+  if (h->sl_on) return fail(VN_EUNSUPPORTED, kSrcWeights, batch);
   if (h->route == Route::fused4)
     return fail(VN_EUNSUPPORTED, "%s is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its single launch has no "
                                  "place for the weights; every other kernel family carries them", who);
@@ -1810,12 +1998,19 @@ int vn_grad(vn_engine* h, int32_t batch) {
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   const Batch& b = h->batches[batch];
-  if (!h->cl_on) return grad_route(h, b);
-  if (has_weights(b)) return fail(VN_EUNSUPPORTED, kCoefWeights, batch);
+  if (!h->cl_on && !h->sl_on) return grad_route(h, b);
+  if (has_weights(b)) return fail(VN_EUNSUPPORTED, h->cl_on ? kCoefWeights : kSrcWeights, batch);
+  if (int rc = source_mix(h, b, batch)) return rc;
   h->cl_blocks = 0;
+  h->sl_blocks = 0;
   if (int rc = grad_route(h, b)) return rc;
-  // inverse mode: after every kernel that reads the coefficients (the parameters' update rides in the reduction above)
-  return coef_finish(h, true, h->fuse.kind == VN_OPT_ADAM, (double)h->step);
+  // inverse mode: after every kernel that reads the coefficients or s_mix (the parameters' update rides in the reduction above);
+  // both vectors step on the same counter
+  if (h->cl_on)
+    if (int rc = coef_finish(h, true, h->fuse.kind == VN_OPT_ADAM, (double)h->step)) return rc;
+  if (h->sl_on)
+    if (int rc = source_finish(h, true, h->fuse.kind == VN_OPT_ADAM, (double)h->step)) return rc;
+  return VN_OK;
 }
 
 static int grad_route(vn_engine* h, const Batch& b) {
@@ -1828,8 +2023,8 @@ static int grad_route(vn_engine* h, const Batch& b) {
     case Route::fused4: return run_fused(h, b, h->gradbuf, fx);
     // a reaction term lives in the row-wise seed kernel, a flux term and a diffusivity D(u) around it: the single-launch route
     // runs the two-pass sequence for such a batch
-    // ... and so do per-test-function loss weights, applied after it
-    case Route::fused8: return has_terms(b) || has_weights(b) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
+    // ... and so do per-test-function loss weights, applied after it, and learnt source amplitudes, whose sums read udbar
+    case Route::fused8: return has_terms(b) || has_weights(b) || src_learnt(h, b) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
     case Route::twopass: return run_twopass(h, b, h->gradbuf, fx);
   }
 }
@@ -1850,6 +2045,8 @@ static int apply_impl(vn_engine* h, float* loss_acc) {
                         (float)h->cfg.beta2, (float)h->cfg.eps, loss_acc, h->stream));
   if (h->cl_on)
     if (int rc = coef_finish(h, false, true, t)) return rc;
+  if (h->sl_on)
+    if (int rc = source_finish(h, false, true, t)) return rc;
   h->step += 1;
   return VN_OK;
 }
@@ -2040,6 +2237,7 @@ int vn_eval_loss(vn_engine* h, int32_t batch, double out[4], float* lossVec_dev)
   (void)hipGetLastError();   // a stale last-error of another library on this thread is not ours to report
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
+  if (int rc = source_mix(h, h->batches[batch], batch)) return rc;
   VnEdgeSums fx;
   if (int rc = edge_passes(h, false, &fx)) return rc;
   if (int rc = run_forward_and_seed(h, h->batches[batch], false, lossVec_dev, h->lossbuf, fx)) return rc;
@@ -2065,6 +2263,7 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
     theta_dev = h->theta64;
   }
   const Batch& b = h->batches[batch];
+  if (int rc = source_mix(h, b, batch)) return rc;     // source identification: the mixed fp32 stream, widened exactly
   VnObj64Problem p{};
   p.net = h->net; p.theta = theta_dev;
   p.X = b.Input; p.G = b.gcoef; p.src = batch_src(h, b);
@@ -2213,6 +2412,9 @@ int vn_comm_init(vn_engine* h, int32_t rank, int32_t world, const void* unique_i
     if (h->batches[i].wt.S > 0)
       return fail(VN_EUNSUPPORTED, "vn_comm_init: batch %d has a causal registration (vn_set_causal); a rank's slab means would cover "
                                    "only its shard, so the ranks together would train another objective than one rank", (int)i);
+  if (h->sl_on)
+    return fail(VN_EUNSUPPORTED, "vn_comm_init while source amplitudes are learnt (vn_set_source_learn): the amplitude gradients are "
+                                 "not in the all-reduced buffer, so every rank would follow its own shard's");
   if (h->cl_on)
     return fail(VN_EUNSUPPORTED, "vn_comm_init while coefficients are learnt (vn_set_coef_learn): the nine coefficient gradients are "
                                  "not in the all-reduced buffer, so every rank would follow its own shard's");

@@ -600,6 +600,8 @@ class ManageTrainData:
                 for key in ('Input', 'gcoef', 'source', 'N_rows', 'dNt_rows', 'rate', 'phi', 'psi'):
                     if d.get(key) is not None:
                         d[key] = d[key].index_select(0, rows_all)
+                if d.get('srcphi') is not None:   # [J, nT]: the rows are the second axis
+                    d['srcphi'] = d['srcphi'].index_select(1, rows_all)
                 for key in ('detJ', 'slab'):      # one entry per test function
                     if d.get(key) is not None:
                         d[key] = d[key].index_select(0, perm_dev)
@@ -617,6 +619,8 @@ class ManageTrainData:
                     eng.set_nlflux(self.engine_batch(mb, bi), pick(d['phi']), d['nlfluxCoef'])
                 if d.get('nldiffCoef') is not None and n1 > n0:     # the diffusivity D(u) of these rows (vn_set_nldiff)
                     eng.set_nldiff(self.engine_batch(mb, bi), pick(d.get('psi')), d['nldiffCoef'])
+                if d.get('srcphi') is not None and n1 > n0:         # the source basis of these rows (vn_set_source_basis)
+                    eng.set_source_basis(self.engine_batch(mb, bi), d['srcphi'][:, n0 * q:n1 * q].contiguous())
                 if d.get('slab') is not None and n1 > n0 and self.vn.causal is not None:      # causal weights (vn_set_causal)
                     eng.set_causal(self.engine_batch(mb, bi), pick_k(d['slab']), self.vn.causalSlabNum(), float(self.vn.causal))
                 perm = getattr(self, 'biPerm', {}).get(bi)
@@ -797,7 +801,7 @@ class VarNet:
                  bDiscNum=[], tDiscNum=[], MORdiscScheme=None, processors=None, controller=None,
                  integPnum=2, optimizer='adam', learning_rate=0.001, fluxBC=False, lbfgsLoss64=False,
                  causal=None, causalSlabs=None, periodicDeriv=None, observations=None, obsWeight=None,
-                 learnCoef=None, coefLr=None, coefBounds=None):
+                 learnCoef=None, coefLr=None, coefBounds=None, learnSource=None, sourceLr=None, sourceBounds=None):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -862,6 +866,9 @@ class VarNet:
         if learnCoef is not None and MORvar is not None:
             raise NotImplementedError('learnCoef with model-order reduction is not supported: neither the three polynomial terms nor '
                                       'the observations it needs are')
+        if learnSource is not None and MORvar is not None:
+            raise NotImplementedError('learnSource with model-order reduction is not supported: neither the source basis nor '
+                                      'the observations it needs are')
         # observations=... (extension; no reference counterpart): sensor data as linear functionals of the solution, fitted by a
         # misfit term obsWeight * O next to the PDE's loss (`obsData`)
         if observations is None:
@@ -887,11 +894,27 @@ class VarNet:
                 raise NotImplementedError('learnCoef with causal=%r: the causal weights are applied after the seeds the coefficient '
                                           'gradient is reduced from' % (causal,))
 
+        # learnSource=... (extension; no reference counterpart): source identification, the masked amplitudes of the PDE's source
+        # basis are learnt next to the network from the observations (`sourceLearnData`)
+        self.srcLearn = self.sourceLearnData(PDE, learnSource, sourceLr, sourceBounds, learning_rate)
+        if self.srcLearn is not None:
+            if observations is None:
+                raise ValueError('learnSource needs observations=...: without interior data every amplitude admits a solution of '
+                                 'the boundary value problem, so the loss cannot tell one value from another')
+            if optimizer.lower() != 'adam':
+                raise NotImplementedError('learnSource with optimizer=%r: the amplitudes are updated by the Adam step only (an L-BFGS '
+                                          'search over (parameters, amplitudes) and an RMSProp update are not built)' % (optimizer,))
+            if causal is not None:
+                raise NotImplementedError('learnSource with causal=%r: the causal weights are applied after the seeds the amplitude '
+                                          'gradient is reduced from' % (causal,))
+
         inpDim = dim + (1 if timeDependent else 0)
         if MORvar is not None:
             inpDim += int(np.sum(MORvar.varNum))
         lossOpt = {'integWflag': integPnum != 2}
         lossOpt['isSource'] = not (hasattr(PDE, 'source') and PDE.source == 0.0)   # VarNet.py:184
+        if getattr(PDE, 'sourceBasis', None) is not None:
+            lossOpt['isSource'] = True          # a basis is a source also when `source` itself is 0
 
         self.dim, self.discNum, self.bDiscNum, self.tDiscNum = dim, discNum, bDiscNum, tDiscNum
         self.MORdiscScheme = MORdiscScheme
@@ -929,6 +952,9 @@ class VarNet:
                                       % (causal,))
         if self.coefLearn is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
             raise NotImplementedError('learnCoef with towers: the nine coefficient gradients are not part of the all-reduced '
+                                      'buffer, so every rank would follow its own shard')
+        if self.srcLearn is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
+            raise NotImplementedError('learnSource with towers: the amplitude gradients are not part of the all-reduced '
                                       'buffer, so every rank would follow its own shard')
         if isinstance(processors, (list, tuple)) and len(processors) > 1 and self.world == 1:
             # the reference's single-process multi-GPU call (TFModel.py:120-165): this process becomes the
@@ -1001,6 +1027,10 @@ class VarNet:
             # the engine owns the nine coefficients from here on: every batch registered later reads them from its device vector
             cl = self.coefLearn
             self.engine.set_coef_learn(cl['mask'], cl['init'], cl['lo'], cl['hi'], cl['lr'])
+        if self.srcLearn is not None:
+            # the engine owns the amplitudes from here on: every batch registered later carries its basis streams
+            sl = self.srcLearn
+            self.engine.set_source_learn(sl['mask'], sl['init'], sl['lo'], sl['hi'], sl['lr'])
         self.tfData = self.engine       # name kept for scripts that poke at `VarNet.tfData`
         from .launch import mark_stage
         mark_stage('engine_ready')      # past the launcher's bootstrap deadline: a rank that trains for hours is healthy
@@ -1155,6 +1185,107 @@ class VarNet:
             g = self.COEF_KEYS.index(key)
             v[3 * g:3 * g + 3] = a
         self.engine.set_coefs(v * self.coefLearn['scale'])
+
+    # -- source identification: learnt amplitudes of a source basis (extension) ------------------------
+    @staticmethod
+    def sourceLearnData(PDE, learnSource, sourceLr=None, sourceBounds=None, learning_rate=0.001):
+        """(No reference counterpart: `VarNet(..., learnSource=...)`.)  The registration of `vn_set_source_learn`, or None without
+        learnSource: mask, init, lo, hi (J entries each) and lr.  learnSource = True or a mask of J booleans; the PDE's sourceAmp
+        is the initial guess; sourceLr defaults to the network's learning rate; sourceBounds = (lo, hi) for every learnt
+        amplitude or a list of J entries, each None or (lo, hi), with None for an open side."""
+        if learnSource is None or learnSource is False:
+            if sourceLr is not None:
+                raise ValueError('sourceLr=%r is an option of learnSource=...' % (sourceLr,))
+            if sourceBounds is not None:
+                raise ValueError('sourceBounds is an option of learnSource=...')
+            return None
+        basis = getattr(PDE, 'sourceBasis', None)
+        if basis is None:
+            raise ValueError('learnSource: the PDE has no source basis (ADPDE(..., sourceBasis=[phi_1, ..., phi_J]))')
+        J = len(basis)
+        isbool = lambda x: isinstance(x, (bool, np.bool_)) or (isinstance(x, (int, np.integer)) and x in (0, 1))
+        if learnSource is True:
+            mask = np.ones(J, dtype=bool)
+        else:
+            if not isinstance(learnSource, (list, tuple, np.ndarray)) or len(learnSource) != J or not all(isbool(x) for x in learnSource):
+                raise ValueError('learnSource must be True or a mask of %d booleans (one per function of sourceBasis), got %r'
+                                 % (J, learnSource))
+            mask = np.array([bool(x) for x in learnSource])
+        if not mask.any():
+            raise ValueError('learnSource selects no amplitude')
+        lr = learning_rate if sourceLr is None else sourceLr
+        if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not np.isfinite(lr) or lr <= 0:
+            raise ValueError('sourceLr=%r must be a finite number > 0' % (lr,))
+        a0 = np.asarray(PDE.sourceAmp, dtype=np.float64)
+        lo, hi = np.full(J, -np.inf), np.full(J, np.inf)
+        if sourceBounds is not None:
+            free = lambda x: x is None or (isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool))
+            if isinstance(sourceBounds, (list, tuple)) and len(sourceBounds) == 2 and all(free(x) for x in sourceBounds):
+                entries = [tuple(sourceBounds) if mask[j] else None for j in range(J)]      # one pair: every learnt amplitude
+            elif isinstance(sourceBounds, (list, tuple)) and len(sourceBounds) == J:
+                entries = list(sourceBounds)
+            else:
+                raise ValueError('sourceBounds must be (lo, hi) or a list of %d entries, each None or (lo, hi), got %r'
+                                 % (J, sourceBounds))
+            for j, bd in enumerate(entries):
+                if bd is None:
+                    continue
+                if not mask[j]:
+                    raise ValueError('sourceBounds[%d] bounds an amplitude that learnSource does not select' % j)
+                if not isinstance(bd, (list, tuple)) or len(bd) != 2:
+                    raise ValueError('sourceBounds[%d] must be None or (lo, hi), got %r' % (j, bd))
+                a = -np.inf if bd[0] is None else bd[0]
+                b = np.inf if bd[1] is None else bd[1]
+                for x in (a, b):
+                    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or np.isnan(x):
+                        raise ValueError('sourceBounds[%d] must hold numbers or None, got %r' % (j, bd))
+                if a > b:
+                    raise ValueError('sourceBounds[%d]: lower bound %r above upper bound %r' % (j, a, b))
+                if not a <= a0[j] <= b:
+                    raise ValueError('sourceBounds[%d] = %r excludes the initial guess %r' % (j, bd, float(a0[j])))
+                lo[j], hi[j] = float(a), float(b)
+        return dict(mask=[int(x) for x in mask], init=a0.copy(), lo=lo, hi=hi, lr=float(lr))
+
+    def _source_basis(self, Input):
+        """The basis functions of the PDE's source at the rows of Input, [n, J] in fp64, evaluated like the source (PDEinpData)."""
+        dim, PDE = self.dim, self.PDE
+        targ = [Input[:, dim][np.newaxis].T] if PDE.timeDependent else []
+        n = Input.shape[0]
+        cols = []
+        for j, f in enumerate(PDE.sourceBasis):
+            v = np.asarray(f(Input[:, 0:dim], *targ), dtype=np.float64)
+            if v.size != n:
+                raise ValueError('sourceBasis[%d] must return one value per point (a column), got shape %s for %d points'
+                                 % (j, v.shape, n))
+            cols.append(v.reshape(n))
+        return np.stack(cols, axis=1)
+
+    def sourceAmplitudes(self):
+        """The J amplitudes of the PDE's source basis at the current state: the learnt values with learnSource, else the PDE's."""
+        if getattr(self.PDE, 'sourceBasis', None) is None:
+            raise ValueError('sourceAmplitudes: the PDE has no source basis (ADPDE(..., sourceBasis=[...]))')
+        if getattr(self, 'srcLearn', None) is None or getattr(self, 'engine', None) is None:
+            return np.array(self.PDE.sourceAmp, dtype=np.float64)
+        return np.asarray(self.engine.get_source_amps(J=len(self.PDE.sourceBasis)), dtype=np.float64)
+
+    def sourceGrad(self):
+        """d loss / d amplitude of the last gradient evaluation, J values (zeros where not learnt)."""
+        if self.srcLearn is None:
+            raise ValueError('sourceGrad: this instance learns no source amplitudes (learnSource=...)')
+        return np.asarray(self.engine.get_source_amps(grad=True, J=len(self.PDE.sourceBasis))[1], dtype=np.float64)
+
+    def setSourceAmplitudes(self, a):
+        """Overwrite the J amplitudes between train() calls.  Not clamped to sourceBounds (the next update is)."""
+        if self.srcLearn is None:
+            raise ValueError('setSourceAmplitudes: this instance learns no source amplitudes (learnSource=...)')
+        J = len(self.PDE.sourceBasis)
+        try:
+            v = np.asarray(a, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            v = np.empty(0)
+        if v.size != J or not np.all(np.isfinite(v)):
+            raise ValueError('setSourceAmplitudes takes %d finite numbers, got %r' % (J, a))
+        self.engine.set_source_amps(v)
 
     # -- causal time-slab weights (extension) ------------------------------------------------------
     @staticmethod
@@ -1592,8 +1723,9 @@ class VarNet:
             out = uf.vstack([out, PDE.IC(biInput[ind:, :dim], **arg)])
         return out
 
-    def PDEinpData(self, Input, inpArg=[]):
-        """kappa, v, s at the rows of Input (VarNet.py:726-774)."""
+    def PDEinpData(self, Input, inpArg=[], basis=True):
+        """kappa, v, s at the rows of Input (VarNet.py:726-774).  With a source basis s = source + sum_j a_j phi_j at the current
+        amplitudes (`sourceAmplitudes`); basis=False: `source` alone."""
         dim, PDE = self.dim, self.PDE
         if uf.isempty(inpArg):
             diffArg, velArg, sourceArg = {}, {}, {}
@@ -1601,8 +1733,10 @@ class VarNet:
             diffArg, velArg, sourceArg = [a if a is not None else {} for a in inpArg]
         targ = [Input[:, dim][np.newaxis].T] if PDE.timeDependent else []
         X = Input[:, 0:dim]
-        return (PDE.diffFun(X, *targ, **diffArg), PDE.velFun(X, *targ, **velArg),
-                PDE.sourceFun(X, *targ, **sourceArg))
+        src = PDE.sourceFun(X, *targ, **sourceArg)
+        if basis and getattr(PDE, 'sourceBasis', None) is not None:
+            src = np.asarray(src, dtype=np.float64).reshape(-1, 1) + self._source_basis(Input) @ self.sourceAmplitudes().reshape(-1, 1)
+        return PDE.diffFun(X, *targ, **diffArg), PDE.velFun(X, *targ, **velArg), src
 
     def _reaction_rate(self, Input):
         """Reaction rate at the rows of Input (a column), evaluated like the source (PDEinpData)."""
@@ -1682,7 +1816,11 @@ class VarNet:
         else:
             biArg, inpArg, MORinp = self.MORargExtract(batch, MORdiscArg)
         biLabel = self.biTrainData(biInput, biDof, biArg)
-        diff, vel, src = self.PDEinpData(Input, inpArg)
+        # learnt amplitudes: the engine mixes s0 and the basis streams itself; else the sum is folded into the source here
+        srcphi = None
+        diff, vel, src = self.PDEinpData(Input, inpArg, basis=self.srcLearn is None)
+        if self.srcLearn is not None:
+            srcphi = eng.dev(np.ascontiguousarray(self._source_basis(Input).T))         # [J, nT], stream-major, fp32
         nt, q, dim = fd.nt, fd.integNum, self.dim
         N_rows = dNt_rows = None
         psi = nldiffCoef = None
@@ -1733,7 +1871,7 @@ class VarNet:
             nlfluxCoef = list(self.PDE.nlfluxCoef)
         slab = self._slab_tensor(Input) if self.causal is not None else None   # (time column dim: the same ids for every MOR batch)
         return dict(Input=eng.dev(Input), Input_host=Input, gcoef=eng.dev(gcoef), rate=rate, reactCoef=reactCoef, slab=slab,
-                    phi=phi, nlfluxCoef=nlfluxCoef, psi=psi, nldiffCoef=nldiffCoef,
+                    phi=phi, nlfluxCoef=nlfluxCoef, psi=psi, nldiffCoef=nldiffCoef, srcphi=srcphi,
                     source=eng.dev(src.reshape(-1)) if self.lossOpt['isSource'] else None,
                     biInput=eng.dev(biInput), biLabel=eng.dev(biLabel.reshape(-1)),
                     N_rows=N_rows, dNt_rows=dNt_rows,
@@ -2215,6 +2353,10 @@ class VarNet:
             trainRes.writeCase('Learnt coefficients: mask %s, initial %s, final %s\n'
                                % (cl['mask'], [float(x) for x in cl['init'] / cl['scale']],
                                   [x for k in self.COEF_KEYS for x in cur[k]]))
+        if self.srcLearn is not None and self.rank == 0:
+            sl = self.srcLearn
+            trainRes.writeCase('Learnt source amplitudes: mask %s, initial %s, final %s\n'
+                               % (sl['mask'], [float(x) for x in sl['init']], [float(x) for x in self.sourceAmplitudes()]))
         return trainRes
 
     # -- checkpoints ----------------------------------------------------------------------------------
@@ -2253,6 +2395,9 @@ class VarNet:
         if getattr(self, 'coefLearn', None) is not None:
             # the nine values in the engine's scale (vn_get_coefs); their Adam slots have no entry point and restart from zero
             out['pde_coefficients'] = np.asarray(self.engine.get_coefs(), dtype=np.float64)
+        if getattr(self, 'srcLearn', None) is not None:
+            # the J amplitudes (vn_get_source_amps); their Adam slots restart from zero, as for pde_coefficients
+            out['source_amplitudes'] = self.sourceAmplitudes()
         return out
 
     def restore_arrays(self, arrays):
@@ -2278,6 +2423,8 @@ class VarNet:
         self.engine.import_state(blob)
         if getattr(self, 'coefLearn', None) is not None and 'pde_coefficients' in arrays:
             self.engine.set_coefs(np.asarray(arrays['pde_coefficients'], dtype=np.float64).reshape(-1))
+        if getattr(self, 'srcLearn', None) is not None and 'source_amplitudes' in arrays:
+            self.engine.set_source_amps(np.asarray(arrays['source_amplitudes'], dtype=np.float64).reshape(-1))
 
     def saveModel(self, epoch):
         """`saver.save(sess, 'best_model', global_step=epoch)` with max_to_keep=2 (TFModel.py:307,
@@ -2589,7 +2736,7 @@ class VarNet:
         resVec = cApp = None
         for b in batchRange:
             if PDE.MORvar is None:
-                if noInput and fd.uniform_inpData[0] is not None:
+                if noInput and fd.uniform_inpData[0] is not None and getattr(self, 'srcLearn', None) is None:
                     diff, vel, src = fd.uniform_inpData
                 else:
                     diff, vel, src = self.PDEinpData(Input)
