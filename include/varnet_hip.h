@@ -399,6 +399,46 @@ int vn_get_source_amps(vn_engine* h, double* amp, double* grad, int32_t J);
 /* Overwrites all J amplitudes (rounded to fp32, NOT clamped); the Adam slots stay.  Non-finite: VN_EINVAL; learning off: VN_ESTATE.
  * Invalidates the snapshot of vn_state_snapshot. */
 int vn_set_source_amps(vn_engine* h, const double* amp, int32_t J);
+/* Field identification: the tangent direction of a batch is gcoef = g0 + sum_j b_j G_j over a basis of J per-row streams of dim
+ * floats per row (G_j[r, d] = chi_j dN_r/dx_d for a diffusivity basis function chi_j, omega_{j,d} N_r for a velocity basis function
+ * omega_j; the engine does not know which stream is which), and the amplitudes b_j are learnt next to the parameters from the
+ * observations.
+ * vn_set_field_basis registers the basis of one batch: G_dev is [J, n_k * integ_num, dim] fp32 on the device, stream-major (every
+ * stream contiguous, rows as in gcoef); the streams are read on every step and must stay valid while registered.  G_dev == NULL or
+ * J == 0 clears the registration, and so does vn_set_interior of that batch.  A call replaces the previous registration, also
+ * when it fails.  J > VN_FLD_MAX: VN_EINVAL.  vn_set_dedup and vn_set_field_basis may come in either order.
+ * Without vn_set_field_learn a registered basis is not read: the batch's direction is the gcoef of vn_set_interior. */
+#define VN_FLD_MAX 32
+int vn_set_field_basis(vn_engine* h, int32_t batch, const float* G_dev, int32_t J);
+/* The amplitudes are engine-wide, like those of vn_set_source_learn: while learning is on the engine owns ONE device vector of J
+ * fp32 amplitudes (`init`, rounded once), their two Adam slots and a snapshot copy of the three; it outlives a re-registration of
+ * the batches.  Every evaluation of a batch with a basis (vn_grad, vn_train_step / _epoch, vn_eval_loss, vn_objective_f64) first
+ * forms gmix[e] = g0[e] + sum_j b_j G_j[e] over the n_k * integ_num * dim entries (fp32, j ascending, one fused multiply-add per
+ * stream) and reads it in place of the batch's gcoef; the de-duplicated step rebuilds its CSR-ordered copy from it and does not use
+ * the periodic-table shortcut for such a batch.  A batch whose basis has another J makes the step return VN_EINVAL.
+ *   d loss / d b_j = + sum_r s_r (grad u_r . G_j[r, :])   (s_r: the tangent seed of row r AFTER D(u) rescaled it, vn_set_nldiff)
+ * is formed inside vn_grad / vn_train_step / vn_train_epoch for the masked entries, in a fixed order without atomics (two
+ * evaluations: the same bits); grad u_r comes from one extra point pass over the batch's rows (row-wise routes; the de-duplicated
+ * step has it per point), and the single-launch 8-wave route runs its two-pass sequence for such a batch.  vn_apply and the fused
+ * train steps update the masked entries with the arithmetic of the parameters' Adam update (the engine's beta1, beta2, eps, the
+ * shared step counter -- shared with vn_set_coef_learn and vn_set_source_learn too --, the rate `lr`), then clamp them to [lo, hi]
+ * (+-inf: unbounded).  Unmasked entries take part in gcoef at their init value and never change a bit.  The loss-only forms and
+ * vn_objective_f64 run the mix only: no amplitude gradient is built in fp64.
+ * vn_state_snapshot / vn_state_rollback carry amplitudes and slots; vn_state_size / _export / _import keep their layout.
+ *   mask   J ints (non-zero: learnt), or NULL: learning off, everything freed, every result bit for bit what it was before.
+ *   init, lo, hi   J doubles each.  Non-finite init, NaN bounds, lo > hi, lr not finite or <= 0, J outside 1..VN_FLD_MAX: VN_EINVAL.
+ * Refused with VN_EUNSUPPORTED for the reasons of vn_set_source_learn: an RMSProp or L-BFGS engine; a handle that has a communicator
+ * (and vn_comm_init while learning is on); a batch with vn_set_tf_weights / vn_set_causal (here, in those calls and in the steps).
+ * Also with VN_EUNSUPPORTED: cfg.dim > 3 (the point pass carries three gradient components), the layer-by-layer route, the 4-wave
+ * cross-check geometry (VN_KERNEL_FUSED), and a network of the generic kernels that the 8-wave point pass does not serve.
+ * The call invalidates the snapshot of vn_state_snapshot and the L-BFGS (f_k, g_k). */
+int vn_set_field_learn(vn_engine* h, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi, double lr);
+/* The J amplitudes now (synchronises) and, when grad is not NULL, the amplitude gradient of the last gradient evaluation (zeros for
+ * unmasked entries and before the first one).  Learning off: VN_ESTATE; J not the engine's: VN_EINVAL. */
+int vn_get_field_amps(vn_engine* h, double* amp, double* grad, int32_t J);
+/* Overwrites all J amplitudes (rounded to fp32, NOT clamped); the Adam slots stay.  Non-finite: VN_EINVAL; learning off: VN_ESTATE.
+ * Invalidates the snapshot of vn_state_snapshot. */
+int vn_set_field_amps(vn_engine* h, const double* amp, int32_t J);
 /* updateDictFields('trainW') (VarNetUtility.py:921-922); the caller applies the
  * w[0:2] /= batchNum*puNum rule (VarNetUtility.py:900-901). */
 int vn_set_weights(vn_engine* h, const double w[3]);

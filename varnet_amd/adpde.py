@@ -1,7 +1,7 @@
 """
 Advection-diffusion(-reaction) PDE container: `ADPDE(domain, diff, vel, source, timeDependent, tInterval,
-BCs, IC, cEx, MORvar, d_diff, reaction, nlflux, nldiff, periodic, sourceBasis, sourceAmp)` -- /root/reference/ADPDE.py:56-246
-restated (plot helpers are out of scope).
+BCs, IC, cEx, MORvar, d_diff, reaction, nlflux, nldiff, periodic, sourceBasis, sourceAmp, diffBasis, diffAmp, d_diffBasis, velBasis,
+velAmp)` -- the reference's ADPDE.py:56-246 restated (plot helpers are out of scope).
 
     c_t = div(diff D(c) grad c) - vel . grad c - div(w F(c)) + source + rate * p(c),    a * dc/dn + b * c = g  on each edge,
 
@@ -52,12 +52,21 @@ class ADPDE:
     sourceBasis=[phi_1, ..., phi_J] with sourceAmp=[a_1, ..., a_J] (default: zeros) makes the source `source + sum_j a_j phi_j`:
     every phi_j is a callable f(x[, t]) returning a column, evaluated like `source`; 1 <= J <= 64.  The amplitudes can be learnt
     from observations (`VarNet(..., learnSource=...)`: source identification); without that the sum is part of the source.
+
+    diffBasis=[chi_1, ..., chi_Jk] with diffAmp=[...] (default: zeros) makes the diffusivity `diff + sum_j diffAmp_j chi_j`, and
+    velBasis=[omega_1, ..., omega_Jv] with velAmp=[...] the velocity `vel + sum_j velAmp_j omega_j`.  A chi_j is a number or a
+    callable f(x[, t]) returning a column, like `diff`; an omega_j is a number, a list of `dim` numbers or a callable returning
+    [n, dim], like `vel`; Jk + Jv <= 32.  d_diffBasis=[grad chi_1, ...] follows the `d_diff` convention (numbers or callables
+    returning [n, dim], default zero): only the strong residual uses it, so without it the chi_j must be constant for the residual
+    to be right.  The amplitudes can be learnt from observations (`VarNet(..., learnField=...)`: field identification); without
+    that the sums are part of `diffFun`, `velFun` and `d_diffFun`.  velBasis with nldiff is not supported.
     """
     SRC_MAX = 64
+    FLD_MAX = 32
 
     def __init__(self, domain, diff, vel, source=0.0, timeDependent=False, tInterval=None,
                  BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None, nlflux=None, nldiff=None, periodic=None,
-                 sourceBasis=None, sourceAmp=None):
+                 sourceBasis=None, sourceAmp=None, diffBasis=None, diffAmp=None, d_diffBasis=None, velBasis=None, velAmp=None):
         # the reference ignores the `timeDependent` argument (ADPDE.py:108-109)
         timeDependent = tInterval is not None
 
@@ -180,6 +189,24 @@ class ADPDE:
         def const_field(val, ncol):
             return lambda x, t=0: val * np.ones([np.shape(x)[0], ncol])
 
+        diffBasis, diffAmp = self._check_field_basis('diffBasis', 'diffAmp', diffBasis, diffAmp, MORvar, 1, dim, const_field)
+        velBasis, velAmp = self._check_field_basis('velBasis', 'velAmp', velBasis, velAmp, MORvar, dim, dim, const_field)
+        if d_diffBasis is not None and diffBasis is None:
+            raise ValueError('d_diffBasis is an option of diffBasis=[chi_1, ..., chi_J]!')
+        if diffBasis is not None:
+            if d_diffBasis is None:
+                d_diffBasis = [None] * len(diffBasis)
+            if not isinstance(d_diffBasis, (list, tuple)) or len(d_diffBasis) != len(diffBasis):
+                raise ValueError('d_diffBasis must be a list of %d entries, one gradient per function of diffBasis!' % len(diffBasis))
+            d_diffBasis, _ = self._check_field_basis('d_diffBasis', 'diffAmp', [0.0 if f is None else f for f in d_diffBasis], None,
+                                                     MORvar, dim, dim, const_field)
+        if (0 if diffBasis is None else len(diffBasis)) + (0 if velBasis is None else len(velBasis)) > self.FLD_MAX:
+            raise ValueError('diffBasis and velBasis hold %d functions together, at most %d are supported!'
+                             % (len(diffBasis or []) + len(velBasis or []), self.FLD_MAX))
+        if velBasis is not None and nldiff is not None:
+            raise NotImplementedError('velBasis with nldiff is not supported: with a solution-dependent diffusivity the advection lives '
+                                      'in the psi stream on the value side, which carries no basis; diffBasis with nldiff works')
+
         if callable(diff):
             self.diffFun = diff
         else:
@@ -201,6 +228,18 @@ class ADPDE:
             d_diff = 0.0 if d_diff is None else d_diff
             self.d_diff = d_diff
             self.d_diffFun = const_field(np.asarray(d_diff, dtype=float), dim)
+
+        # field bases: the callables and their amplitudes (the initial guess when they are learnt); no attributes without one.
+        # diffFun, velFun and d_diffFun become the sums at the PDE's amplitudes, the plain fields stay in diffFun0, velFun0, d_diffFun0
+        if diffBasis is not None:
+            self.diffBasis, self.diffAmp, self.d_diffBasis = diffBasis, diffAmp, d_diffBasis
+            self.diffFun0, self.d_diffFun0 = self.diffFun, self.d_diffFun
+            self.diffFun = lambda x, *t: self._field_sum(self.diffFun0, self.diffBasis, self.diffAmp, 'diffBasis', 1, x, t)
+            self.d_diffFun = lambda x, *t: self._field_sum(self.d_diffFun0, self.d_diffBasis, self.diffAmp, 'd_diffBasis', dim, x, t)
+        if velBasis is not None:
+            self.velBasis, self.velAmp = velBasis, velAmp
+            self.velFun0 = self.velFun
+            self.velFun = lambda x, *t: self._field_sum(self.velFun0, self.velBasis, self.velAmp, 'velBasis', dim, x, t)
 
         # reaction term: rate as a callable like the source, the three coefficients; None without one
         self.reaction = None
@@ -313,6 +352,63 @@ class ADPDE:
         if sourceBasis is not None:
             self.sourceBasis = sourceBasis
             self.sourceAmp = sourceAmp
+
+    def _check_field_basis(self, name, ampName, basis, amp, MORvar, ncol, dim, const_field):
+        """(list of callables, amplitudes) of diffBasis / velBasis / d_diffBasis, or (None, None) without one; ValueError names
+        the field.  An entry is a number, a list of `ncol` numbers (ncol > 1) or a callable."""
+        if basis is None:
+            if amp is not None:
+                raise ValueError('%s is an option of %s=[f_1, ..., f_J]!' % (ampName, name))
+            return None, None
+        if not isinstance(basis, (list, tuple)) or len(basis) == 0:
+            raise ValueError('%s must be a non-empty list of numbers or callables [f_1, ..., f_J]!' % name)
+        if len(basis) > self.FLD_MAX:
+            raise ValueError('%s holds %d functions, at most %d are supported!' % (name, len(basis), self.FLD_MAX))
+        out = []
+        for j, f in enumerate(basis):
+            if callable(f):
+                out.append(f)
+                continue
+            try:
+                v = np.reshape(np.asarray(f, dtype=float), -1)
+            except (TypeError, ValueError):
+                v = np.empty(0)
+            if isinstance(f, bool) or v.size not in (1, ncol) or not np.all(np.isfinite(v)):
+                raise ValueError('%s[%d] must be callable, a finite number%s!'
+                                 % (name, j, '' if ncol == 1 else ' or a list of %d finite numbers' % ncol))
+            out.append(const_field(v if v.size == ncol else float(v[0]), ncol))
+        if amp is None:
+            amp = np.zeros(len(out))
+        try:
+            amp = np.array(np.reshape(np.asarray(amp, dtype=float), -1))
+        except (TypeError, ValueError):
+            raise ValueError('%s must be a list of %d numbers, one per function of %s!' % (ampName, len(out), name))
+        if amp.size != len(out):
+            raise ValueError('%s holds %d values for the %d functions of %s!' % (ampName, amp.size, len(out), name))
+        if not np.all(np.isfinite(amp)):
+            raise ValueError('%s must be finite!' % ampName)
+        if MORvar is not None:
+            raise NotImplementedError('%s with model-order reduction is not supported: parametric basis functions are out of scope '
+                                      '(the basis streams are assembled once, for all parameter batches)' % name)
+        return out, amp
+
+    @staticmethod
+    def field_basis_values(basis, name, ncol, x, t=()):
+        """The functions of one field basis at the points x (and times t): [J, n, ncol] in fp64; a wrong shape names the entry."""
+        n = np.shape(x)[0]
+        out = np.empty((len(basis), n, ncol), dtype=np.float64)
+        for j, f in enumerate(basis):
+            v = np.asarray(f(x, *t), dtype=np.float64)
+            if v.size != n * ncol:
+                raise ValueError('%s[%d] must return %s per point, got shape %s for %d points'
+                                 % (name, j, 'one value (a column)' if ncol == 1 else '%d values ([n, %d])' % (ncol, ncol), v.shape, n))
+            out[j] = v.reshape(n, ncol)
+        return out
+
+    def _field_sum(self, base, basis, amp, name, ncol, x, t):
+        """base + sum_j amp_j f_j at the points x: what diffFun, velFun and d_diffFun return when the PDE has a basis."""
+        v = np.asarray(base(x, *t), dtype=np.float64).reshape(-1, ncol)
+        return v + np.tensordot(np.asarray(amp, dtype=np.float64), self.field_basis_values(basis, name, ncol, x, t), axes=1)
 
     @staticmethod
     def _check_periodic(periodic, domain, BCs):

@@ -12,6 +12,7 @@
 #include "vn_terms.h"
 #include "vn_coef.h"
 #include "vn_source.h"
+#include "vn_field.h"
 #include "vn_weights.h"
 #include "vn_split16.h"
 
@@ -74,6 +75,8 @@ struct Batch {
   const float* source = nullptr;
   const float* sb_phi = nullptr;   // [sb_J, n_k*integ_num] basis streams of the source (vn_set_source_basis), caller-owned; nullptr: none
   int sb_J = 0;
+  const float* fb_G = nullptr;     // [fb_J, n_k*integ_num, dim] basis streams of gcoef (vn_set_field_basis), caller-owned; nullptr: none
+  int fb_J = 0;
   const float* detJv = nullptr;
   const float* Nrow = nullptr;
   const float* dNtrow = nullptr;
@@ -241,6 +244,19 @@ struct vn_engine {
   float* sl_part = nullptr;                       // [VN_SRC_MAXBLK, J] partials of the reduction
   int sl_blocks = 0;                              // partials the current gradient evaluation wrote (0: the batch has no basis)
   float* sl_mix = nullptr; long sl_mix_cap = 0;   // [nT] s0 + sum_j a_j phi_j of the batch being evaluated
+  // field identification (vn_set_field_learn, vn_field.hip): the amplitudes of the batches' gcoef bases, engine-wide
+  bool fl_on = false;
+  int fl_J = 0;
+  unsigned fl_mask = 0;                           // bit j: amplitude j is learnt
+  double fl_lr = 0.0;
+  float* fl_state = nullptr;                      // [6 * 32] (amp | m | v) at stride 32, then their copy of vn_state_snapshot
+  float* fl_bounds = nullptr;                     // [2 * 32] (lo | hi)
+  double* fl_grad = nullptr;                      // [32] amplitude gradient of the last gradient evaluation
+  float* fl_part = nullptr;                       // [VN_FLD_MAXBLK, J] partials of the reduction
+  int fl_blocks = 0;                              // partials the current gradient evaluation wrote (0: the batch has no basis)
+  float* fl_mix = nullptr; long fl_mix_cap = 0;   // [nT, dim] g0 + sum_j b_j G_j of the batch being evaluated
+  float* fl_csr = nullptr; long fl_csr_cap = 0;   // [nT, dim] fl_mix in CSR order (de-duplicated step), rebuilt every evaluation
+  float* fl_pack = nullptr; long fl_pack_cap = 0; // [nT, 4] (u, grad u) of the batch's own rows (row-wise gradient evaluation)
   float* snap = nullptr;       // vn_state_snapshot: device copy of (theta | m | v), 3 P floats
   int64_t snap_step = -1;      // step counter at the snapshot (-1: none)
   PointRoute point_route = PointRoute::automatic;   // vn_debug_point_route(route & 3)
@@ -416,6 +432,9 @@ inline bool src_learnt(const vn_engine* h, const Batch& b) { return h->sl_on && 
 inline const float* batch_src(const vn_engine* h, const Batch& b) {
   return !h->cfg.has_source ? nullptr : src_learnt(h, b) ? h->sl_mix : b.source;
 }
+// (... and the mixed direction field_mix formed there in place of the batch's gcoef)
+inline bool fld_learnt(const vn_engine* h, const Batch& b) { return h->fl_on && b.fb_G; }
+inline const float* batch_gcoef(const vn_engine* h, const Batch& b) { return fld_learnt(h, b) ? h->fl_mix : b.gcoef; }
 inline const float* fe_w(const vn_engine* h) { return (h->cfg.has_integw && h->has_feW) ? h->feW : nullptr; }
 
 inline bool on_8wave(const vn_engine* h) { return h->route == Route::fused8 || h->route == Route::twopass; }
@@ -519,10 +538,12 @@ VnSeedArgs seed_args(const vn_engine* h, const Batch& b) {
 VnDedupArgs dedup_args(const vn_engine* h, const Batch& b) {
   VnDedupArgs a{};
   a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
-  a.gcoef = b.gcoef; a.gcoef_csr = b.gcsr; a.source = batch_src(h, b);
+  // (learnt field amplitudes: gcoef moves every step, so no periodic table, and the CSR copy is the one field_mix rebuilt)
+  const bool fld = fld_learnt(h, b);
+  a.gcoef = batch_gcoef(h, b); a.gcoef_csr = fld ? h->fl_csr : b.gcsr; a.source = batch_src(h, b);
   a.feN = h->feN; a.fedNt = h->fedNt; a.feW = fe_w(h);
   a.detJv = b.detJv; a.detJ = (float)b.detJ; a.n_k = b.n_k; a.U = b.U; a.q = h->cfg.integ_num; a.dim = h->cfg.dim;
-  a.time_dependent = h->cfg.time_dependent; a.w2 = (float)h->w[2]; a.gper = b.gper ? 1 : 0;
+  a.time_dependent = h->cfg.time_dependent; a.w2 = (float)h->w[2]; a.gper = b.gper && !fld ? 1 : 0;
   return a;
 }
 
@@ -593,6 +614,15 @@ int terms_seed_rows(vn_engine* h, const Batch& b) {
   }
   if (b.nlflux.on) HIPCHK(vn_nlflux_seed_launch(term_row_args(h, b, b.nlflux), h->stream));
   if (b.nldiff.on) HIPCHK(vn_nldiff_seed_launch(term_row_args(h, b, b.nldiff), h->stream));
+  if (fld_learnt(h, b)) {                          // field identification: the amplitude sums read udbar as D(u) left it, and the
+    const long nT = b.n_k * h->cfg.integ_num;      // second tangent grad u_r of a point pass over the batch's own rows
+    if (int rc = ensure(&h->fl_pack, &h->fl_pack_cap, 4 * nT)) return rc;
+    HIPCHK(point_pass(h, b.Input, nT, nullptr, nullptr, h->fl_pack));
+    VnFldGradArgs g{};
+    g.udbar = h->udbar; g.pack = h->fl_pack; g.G = b.fb_G; g.J = b.fb_J; g.dim = h->cfg.dim;
+    g.nT = nT; g.q = h->cfg.integ_num; g.mask = h->fl_mask; g.part = h->fl_part;
+    HIPCHK(vn_fldgrad_rows_launch(g, &h->fl_blocks, h->stream));
+  }
   return VN_OK;
 }
 
@@ -612,7 +642,7 @@ VnTermDedupArgs term_dedup_args(const vn_engine* h, const Batch& b, const Term& 
 // ... of D(u), which alone reads gcoef and the points' tangent seeds
 VnTermDedupArgs nldiff_dedup_args(const vn_engine* h, const Batch& b, const VnDedupArgs& d) {
   VnTermDedupArgs a = term_dedup_args(h, b, b.nldiff, d);
-  a.gcoef = b.gcoef; a.dim = h->cfg.dim; a.gper = b.gper ? 1 : 0; a.seed_g = d.seed_g;
+  a.gcoef = batch_gcoef(h, b); a.dim = h->cfg.dim; a.gper = b.gper && !fld_learnt(h, b) ? 1 : 0; a.seed_g = d.seed_g;
   return a;
 }
 
@@ -827,7 +857,7 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
                          const VnEdgeSums& fx = VnEdgeSums()) {
   if (!with_seeds && b.Xu && h->has_fe && !h->eval_rowwise) return eval_dedup(h, b, lossVec, lossdst, fx);
   VnRows s0{}, s1{};
-  s0.X = b.Input; s0.G = b.gcoef; s0.u = h->u; s0.ud = h->ud; s0.n = b.n_k * h->cfg.integ_num;
+  s0.X = b.Input; s0.G = batch_gcoef(h, b); s0.u = h->u; s0.ud = h->ud; s0.n = b.n_k * h->cfg.integ_num;
   s1.X = bi_x(h, b); s1.G = nullptr; s1.u = h->ub; s1.ud = nullptr; s1.n = h->nB;
   if (h->route == Route::layered) {
     LAYCHK(vn_layered_forward(h->layered, h->theta, s0, h->stream, lerr_, sizeof lerr_, with_seeds ? 0 : -1));
@@ -862,7 +892,7 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
 int run_layered(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx) {
   if (int rc = run_forward_and_seed(h, b, true, nullptr, nullptr)) return rc;
   VnRows s0{}, s1{};
-  s0.X = b.Input; s0.G = b.gcoef; s0.ubar = h->ubar; s0.udbar = h->udbar; s0.n = b.n_k * h->cfg.integ_num;
+  s0.X = b.Input; s0.G = batch_gcoef(h, b); s0.ubar = h->ubar; s0.udbar = h->udbar; s0.n = b.n_k * h->cfg.integ_num;
   s1.X = bi_x(h, b); s1.G = nullptr; s1.ubar = h->ubar_b; s1.udbar = nullptr; s1.n = h->nB;
   // one gradient vector (no per-workgroup partials): the GEMMs accumulate into it chunk by chunk
   HIPCHK(hipMemsetAsync(h->partial, 0, (size_t)h->net.P * sizeof(float), h->stream));
@@ -880,7 +910,7 @@ int run_layered(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& 
 int run_generic(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx) {
   if (int rc = run_forward_and_seed(h, b, true, nullptr, nullptr)) return rc;
   VnRows s0{}, s1{};
-  s0.X = b.Input; s0.G = b.gcoef; s0.ubar = h->ubar; s0.udbar = h->udbar; s0.n = b.n_k * h->cfg.integ_num;
+  s0.X = b.Input; s0.G = batch_gcoef(h, b); s0.ubar = h->ubar; s0.udbar = h->udbar; s0.n = b.n_k * h->cfg.integ_num;
   s1.X = bi_x(h, b); s1.G = nullptr; s1.ubar = h->ubar_b; s1.udbar = nullptr; s1.n = h->nB;
   if (int rc = prof_start(h)) return rc;
   HIPCHK(vn_generic_backward(h->net, h->theta, s0, s1, h->partial, h->bwd_grid, h->stream));
@@ -896,7 +926,7 @@ int run_generic(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& 
 // and reverse pass of every tile, BC/IC tiles included
 int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx) {
   VnFusedArgs a = fused_args(h, &b);
-  a.X = b.Input; a.G = b.gcoef; a.src = batch_src(h, b);
+  a.X = b.Input; a.G = batch_gcoef(h, b); a.src = batch_src(h, b);
   a.nT = b.n_k * h->cfg.integ_num; a.n_k = b.n_k; a.feW = fe_w(h);
   a.Nrow = b.Nrow; a.dNtrow = b.dNtrow; a.detJv = b.detJv; a.detJ = (float)b.detJ;
   a.partial = h->partial; a.losspart = h->fused_losspart; a.stamps = h->stamps;
@@ -933,7 +963,7 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& 
   if (int rc = ensure(&h->tp_losspart, &h->tp_losspart_cap, (long)(grid + sgrid) * 3)) return rc;
   float* lp = h->tp_losspart;
   VnFusedArgs f = fused_args(h, &b);
-  f.X = b.Input; f.G = b.gcoef; f.nT = b.n_k * h->cfg.integ_num; f.nB = 0;     // BC/IC: step 3
+  f.X = b.Input; f.G = batch_gcoef(h, b); f.nT = b.n_k * h->cfg.integ_num; f.nB = 0;     // BC/IC: step 3
   f.partial = h->partial; f.losspart = lp;
   f.dir = -1; f.ostride = 1;
   f.mode = 1; f.out_u = h->u; f.out_ud = h->ud;
@@ -986,6 +1016,14 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
     g.stf = a.stf; g.feW = fe_w(h); g.feN = h->feN; g.phi = b.sb_phi; g.J = b.sb_J;
     g.nT = b.n_k * h->cfg.integ_num; g.q = h->cfg.integ_num; g.mask = h->sl_mask; g.part = h->sl_part;
     HIPCHK(vn_srcgrad_rows_launch(g, &h->sl_blocks, h->stream));
+  }
+  if (fld_learnt(h, b)) {                          // field identification: ... times D(u_j), with grad u of the row's point
+    VnFldGradArgs g{};
+    g.stf = a.stf; g.feW = fe_w(h); g.pack = h->dd_uv; g.uid = b.uid; g.G = b.fb_G; g.J = b.fb_J; g.dim = h->cfg.dim;
+    g.nldiff = b.nldiff.on ? 1 : 0; g.cp = b.nldiff.on ? term_cp(h, b, b.nldiff) : nullptr;
+    for (int i = 0; i < 3; ++i) g.c[i] = (float)b.nldiff.c[i];
+    g.nT = b.n_k * h->cfg.integ_num; g.q = h->cfg.integ_num; g.mask = h->fl_mask; g.part = h->fl_part;
+    HIPCHK(vn_fldgrad_rows_launch(g, &h->fl_blocks, h->stream));
   }
   VnFusedArgs f = fused_args(h, &b);
   f.X = b.Xu; f.G = h->dd_sg; f.nT = b.U;
@@ -1075,6 +1113,61 @@ void source_free(vn_engine* h) {
   h->sl_state = nullptr; h->sl_bounds = nullptr; h->sl_grad = nullptr; h->sl_part = nullptr; h->sl_mix = nullptr; h->sl_mix_cap = 0;
   h->sl_on = false; h->sl_J = 0; h->sl_mask = 0; h->sl_blocks = 0;
 }
+
+// Field identification, first thing in an evaluation of batch b (the routes without a point pass for the rows' grad u were refused by
+// vn_set_field_learn): the batch's basis must be the engine's, then gcoef is formed --
+// vn_source_mix_kernel's arithmetic over the nT * dim entries of a stream -- and, on a de-duplication map, its CSR-ordered copy
+int field_mix(vn_engine* h, const Batch& b, int batch) {
+  if (!fld_learnt(h, b)) return VN_OK;
+  if (b.fb_J != h->fl_J)
+    return fail(VN_EINVAL, "batch %d has a field basis of %d streams, the learnt amplitudes (vn_set_field_learn) are %d", batch, b.fb_J, h->fl_J);
+  const long n = b.n_k * h->cfg.integ_num * h->cfg.dim;
+  if (n <= 0) return VN_OK;
+  if (int rc = ensure(&h->fl_mix, &h->fl_mix_cap, n)) return rc;
+  VnSrcMixArgs a{};
+  a.s0 = b.gcoef; a.phi = b.fb_G; a.amp = h->fl_state; a.J = b.fb_J; a.nT = n; a.out = h->fl_mix;
+  HIPCHK(vn_source_mix_launch(a, h->stream));
+  if (b.Xu) {
+    if (int rc = ensure(&h->fl_csr, &h->fl_csr_cap, n)) return rc;
+    HIPCHK(vn_dedup_permute_launch(h->fl_mix, b.rowidx, h->fl_csr, b.n_k * h->cfg.integ_num, h->cfg.dim, h->stream));
+  }
+  return VN_OK;
+}
+
+// source_finish's sibling, through vn_source_apply_kernel (nothing in it is the source's): fold, Adam step at counter t, clamp
+int field_finish(vn_engine* h, bool fold, bool update, double t) {
+  VnSrcApplyArgs a{};
+  a.J = h->fl_J;
+  if (fold) {
+    if (h->fl_blocks <= 0) {
+      HIPCHK(hipMemsetAsync(h->fl_part, 0, (size_t)h->fl_J * sizeof(float), h->stream));
+      h->fl_blocks = 1;
+    }
+    a.part = h->fl_part; a.blocks = h->fl_blocks;
+  }
+  a.grad = h->fl_grad; a.amp = h->fl_state; a.m = h->fl_state + VN_FLD_JMAX; a.v = h->fl_state + 2 * VN_FLD_JMAX;
+  a.lo = h->fl_bounds; a.hi = h->fl_bounds + VN_FLD_JMAX;
+  a.mask = h->fl_mask;
+  a.update = update ? 1 : 0;
+  if (update) {
+    a.lr_t = (float)(h->fl_lr * std::sqrt(1.0 - std::pow(h->cfg.beta2, t)) / (1.0 - std::pow(h->cfg.beta1, t)));
+    a.b1 = (float)h->cfg.beta1; a.b2 = (float)h->cfg.beta2; a.eps = (float)h->cfg.eps;
+  }
+  HIPCHK(vn_source_apply_launch(a, h->stream));
+  return VN_OK;
+}
+
+void field_free(vn_engine* h) {
+  for (void* p : {(void*)h->fl_state, (void*)h->fl_bounds, (void*)h->fl_grad, (void*)h->fl_part, (void*)h->fl_mix, (void*)h->fl_csr,
+                  (void*)h->fl_pack})
+    if (p) (void)hipFree(p);
+  h->fl_state = nullptr; h->fl_bounds = nullptr; h->fl_grad = nullptr; h->fl_part = nullptr;
+  h->fl_mix = nullptr; h->fl_mix_cap = 0; h->fl_csr = nullptr; h->fl_csr_cap = 0; h->fl_pack = nullptr; h->fl_pack_cap = 0;
+  h->fl_on = false; h->fl_J = 0; h->fl_mask = 0; h->fl_blocks = 0;
+}
+
+constexpr const char* kFldWeights = "learnt field amplitudes (vn_set_field_learn) next to per-test-function loss weights (vn_set_tf_weights / "
+                                    "vn_set_causal, batch %d): the weights are applied after the seeds the amplitude reduction reads";
 
 constexpr const char* kSrcWeights = "learnt source amplitudes (vn_set_source_learn) next to per-test-function loss weights (vn_set_tf_weights / "
                                     "vn_set_causal, batch %d): the weights are applied after the seeds the amplitude reduction reads";
@@ -1245,6 +1338,7 @@ int vn_destroy(vn_engine* h) {
   vn_obj64_free(h->o64);
   coef_free(h);
   source_free(h);
+  field_free(h);
   for (Batch& b : h->batches) {
     if (b.gcsr) (void)hipFree(b.gcsr);
     clear_weights(b);
@@ -1358,6 +1452,8 @@ int vn_state_snapshot(vn_engine* h) {
     HIPCHK(hipMemcpyAsync(h->cl_state + 3 * VN_COEF_N, h->cl_state, 3 * VN_COEF_N * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   if (h->sl_on)
     HIPCHK(hipMemcpyAsync(h->sl_state + 3 * VN_SRC_JMAX, h->sl_state, 3 * VN_SRC_JMAX * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  if (h->fl_on)
+    HIPCHK(hipMemcpyAsync(h->fl_state + 3 * VN_FLD_JMAX, h->fl_state, 3 * VN_FLD_JMAX * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   h->snap_step = h->step;
   return VN_OK;
 }
@@ -1375,6 +1471,8 @@ int vn_state_rollback(vn_engine* h) {
     HIPCHK(hipMemcpyAsync(h->cl_state, h->cl_state + 3 * VN_COEF_N, 3 * VN_COEF_N * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   if (h->sl_on)
     HIPCHK(hipMemcpyAsync(h->sl_state, h->sl_state + 3 * VN_SRC_JMAX, 3 * VN_SRC_JMAX * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  if (h->fl_on)
+    HIPCHK(hipMemcpyAsync(h->fl_state, h->fl_state + 3 * VN_FLD_JMAX, 3 * VN_FLD_JMAX * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   h->step = h->snap_step;
   return VN_OK;
 }
@@ -1434,6 +1532,7 @@ int vn_set_interior(vn_engine* h, int32_t batch, const float* Input, const float
   b.Xu = nullptr; b.uid = nullptr; b.rowptr = nullptr; b.rowidx = nullptr; b.U = 0;   // re-register with vn_set_dedup
   b.biInput = nullptr; b.biLabel = nullptr;                                            // ... and vn_set_batch_bic
   b.sb_phi = nullptr; b.sb_J = 0;                                                      // ... and vn_set_source_basis
+  b.fb_G = nullptr; b.fb_J = 0;                                                        // ... and vn_set_field_basis
   const Batch fresh;
   b.react = fresh.react; b.nlflux = fresh.nlflux; b.nldiff = fresh.nldiff;             // ... and the three term setters
   clear_weights(b);                                                                    // ... and vn_set_tf_weights / vn_set_causal
@@ -1725,6 +1824,116 @@ int vn_set_source_amps(vn_engine* h, const double* amp, int32_t J) {
   return VN_OK;
 }
 
+// ---- field identification: basis streams of gcoef per batch, amplitudes on the device, learnt next to the parameters (vn_field.hip) ----
+int vn_set_field_basis(vn_engine* h, int32_t batch, const float* G_dev, int32_t J) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
+    return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
+  Batch& b = h->batches[batch];
+  lbfgs_invalidate(h, batch);
+  b.fb_G = nullptr; b.fb_J = 0;                  // a call replaces the previous registration, also when it fails
+  if (!G_dev || J == 0) return VN_OK;
+  if (J < 0 || J > VN_FLD_MAX) return fail(VN_EINVAL, "a field basis has 1 to %d streams, got %d", VN_FLD_MAX, J);
+  if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no direction to mix", batch);
+  b.fb_G = G_dev; b.fb_J = J;
+  return VN_OK;
+}
+
+int vn_set_field_learn(vn_engine* h, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi, double lr) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  (void)hipGetLastError();
+  HIPCHK(hipSetDevice(h->cfg.device));
+  h->snap_step = -1;
+  lbfgs_invalidate(h);
+  if (!mask) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    field_free(h);
+    return VN_OK;
+  }
+  if (!init || !lo || !hi) return fail(VN_EINVAL, "null argument");
+  if (J < 1 || J > VN_FLD_MAX) return fail(VN_EINVAL, "1 to %d field amplitudes can be learnt, got %d", VN_FLD_MAX, J);
+  if (h->cfg.optimizer != VN_OPT_ADAM)
+    return fail(VN_EUNSUPPORTED, "vn_set_field_learn on %s engine: the amplitudes are updated with the arithmetic of the Adam step only%s",
+                is_lbfgs(h) ? "an L-BFGS" : "an RMSProp", is_lbfgs(h) ? " (vn_lbfgs_step searches over the parameters alone)" : "");
+  if (h->comm)
+    return fail(VN_EUNSUPPORTED, "vn_set_field_learn under a communicator: the amplitude gradients are not in the all-reduced "
+                                 "buffer, so every rank would follow its own shard's");
+  if (h->cfg.dim > 3)
+    return fail(VN_EUNSUPPORTED, "learnt field amplitudes need dim <= 3, got %d: the point pass that gives the rows' grad u carries "
+                                 "three gradient components", h->cfg.dim);
+  if (h->route == Route::layered)
+    return fail(VN_EUNSUPPORTED, "learnt field amplitudes are not built for the layer-by-layer route: it has no point pass for the "
+                                 "rows' grad u; networks of the hand-written kernels carry one");
+  if (h->route == Route::fused4)
+    return fail(VN_EUNSUPPORTED, "learnt field amplitudes are not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its "
+                                 "single launch leaves no row seeds to reduce; every other kernel family carries them");
+  if (!on_8wave(h) && !(vn_fused16_net_supported(h->net) && h->net.act != VN_ACT_PER_LAYER))
+    return fail(VN_EUNSUPPORTED, "learnt field amplitudes on the generic kernels need a network of the 8-wave point pass for the rows' "
+                                 "grad u; this one (%d layers, widest %d, %d inputs%s) has none", h->net.L, h->net.hmax, h->net.d_in,
+                h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+  for (size_t i = 0; i < h->batches.size(); ++i)
+    if (has_weights(h->batches[i])) return fail(VN_EUNSUPPORTED, kFldWeights, (int)i);
+  if (!(std::isfinite(lr) && lr > 0.0)) return fail(VN_EINVAL, "amplitude learning rate %g must be finite and > 0", lr);
+  for (int i = 0; i < J; ++i) {
+    if (!std::isfinite(init[i])) return fail(VN_EINVAL, "initial amplitude %d = %g must be finite", i, init[i]);
+    if (std::isnan(lo[i]) || std::isnan(hi[i]) || lo[i] > hi[i])
+      return fail(VN_EINVAL, "bounds of amplitude %d: [%g, %g] is no interval", i, lo[i], hi[i]);
+  }
+  if (!h->fl_state) {
+    hipError_t e = hipMalloc((void**)&h->fl_state, 6 * VN_FLD_JMAX * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->fl_bounds, 2 * VN_FLD_JMAX * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->fl_grad, VN_FLD_JMAX * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->fl_part, (size_t)VN_FLD_MAXBLK * VN_FLD_JMAX * sizeof(float));
+    if (e != hipSuccess) { (void)hipGetLastError(); field_free(h); return fail(VN_ENOMEM, "vn_set_field_learn: %s", hipGetErrorString(e)); }
+  }
+  float st[6 * VN_FLD_JMAX] = {}, bd[2 * VN_FLD_JMAX] = {};
+  h->fl_mask = 0;
+  for (int i = 0; i < J; ++i) {
+    st[i] = (float)init[i];
+    bd[i] = (float)lo[i]; bd[VN_FLD_JMAX + i] = (float)hi[i];
+    if (mask[i]) h->fl_mask |= 1u << i;
+  }
+  h->fl_lr = lr;
+  h->fl_J = J;
+  HIPCHK(hipMemcpyAsync(h->fl_state, st, sizeof st, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->fl_bounds, bd, sizeof bd, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(h->fl_grad, 0, VN_FLD_JMAX * sizeof(double), h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));      // (st, bd leave scope)
+  h->fl_on = true;
+  h->fl_blocks = 0;
+  return VN_OK;
+}
+
+int vn_get_field_amps(vn_engine* h, double* amp, double* grad, int32_t J) {
+  if (!h || !amp) return fail(VN_EINVAL, "null argument");
+  if (!h->fl_on) return fail(VN_ESTATE, "no learnt field amplitudes (call vn_set_field_learn first)");
+  if (J != h->fl_J) return fail(VN_EINVAL, "the engine holds %d field amplitudes, the caller asks for %d", h->fl_J, J);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  float c[VN_FLD_JMAX];
+  HIPCHK(hipMemcpyAsync(c, h->fl_state, (size_t)J * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (grad) HIPCHK(hipMemcpyAsync(grad, h->fl_grad, (size_t)J * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < J; ++i) amp[i] = (double)c[i];
+  return VN_OK;
+}
+
+int vn_set_field_amps(vn_engine* h, const double* amp, int32_t J) {
+  if (!h || !amp) return fail(VN_EINVAL, "null argument");
+  if (!h->fl_on) return fail(VN_ESTATE, "no learnt field amplitudes (call vn_set_field_learn first)");
+  if (J != h->fl_J) return fail(VN_EINVAL, "the engine holds %d field amplitudes, the caller passes %d", h->fl_J, J);
+  float c[VN_FLD_JMAX];
+  for (int i = 0; i < J; ++i) {
+    if (!std::isfinite(amp[i])) return fail(VN_EINVAL, "amplitude %d = %g must be finite", i, amp[i]);
+    c[i] = (float)amp[i];
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipMemcpyAsync(h->fl_state, c, (size_t)J * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->snap_step = -1;
+  lbfgs_invalidate(h);
+  return VN_OK;
+}
+
 // vn_set_tf_weights / vn_set_causal: what both check before they touch the batch; *clear: the call unregisters
 static int weights_common(vn_engine* h, int32_t batch, bool clear, const char* who) {
   if (!h) return fail(VN_EINVAL, "null handle");
@@ -1740,6 +1949,7 @@ static int weights_common(vn_engine* h, int32_t batch, bool clear, const char* w
   if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no test function to weight", batch);
   if (h->cl_on) return fail(VN_EUNSUPPORTED, kCoefWeights, batch);
   if (h->sl_on) return fail(VN_EUNSUPPORTED, kSrcWeights, batch);
+  if (h->fl_on) return fail(VN_EUNSUPPORTED, kFldWeights, batch);
   if (h->route == Route::fused4)
     return fail(VN_EUNSUPPORTED, "%s is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its single launch has no "
                                  "place for the weights; every other kernel family carries them", who);
@@ -1998,11 +2208,13 @@ int vn_grad(vn_engine* h, int32_t batch) {
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   const Batch& b = h->batches[batch];
-  if (!h->cl_on && !h->sl_on) return grad_route(h, b);
-  if (has_weights(b)) return fail(VN_EUNSUPPORTED, h->cl_on ? kCoefWeights : kSrcWeights, batch);
+  if (!h->cl_on && !h->sl_on && !h->fl_on) return grad_route(h, b);
+  if (has_weights(b)) return fail(VN_EUNSUPPORTED, h->cl_on ? kCoefWeights : h->sl_on ? kSrcWeights : kFldWeights, batch);
   if (int rc = source_mix(h, b, batch)) return rc;
+  if (int rc = field_mix(h, b, batch)) return rc;
   h->cl_blocks = 0;
   h->sl_blocks = 0;
+  h->fl_blocks = 0;
   if (int rc = grad_route(h, b)) return rc;
   // inverse mode: after every kernel that reads the coefficients or s_mix (the parameters' update rides in the reduction above);
   // both vectors step on the same counter
@@ -2010,6 +2222,8 @@ int vn_grad(vn_engine* h, int32_t batch) {
     if (int rc = coef_finish(h, true, h->fuse.kind == VN_OPT_ADAM, (double)h->step)) return rc;
   if (h->sl_on)
     if (int rc = source_finish(h, true, h->fuse.kind == VN_OPT_ADAM, (double)h->step)) return rc;
+  if (h->fl_on)
+    if (int rc = field_finish(h, true, h->fuse.kind == VN_OPT_ADAM, (double)h->step)) return rc;
   return VN_OK;
 }
 
@@ -2024,7 +2238,7 @@ static int grad_route(vn_engine* h, const Batch& b) {
     // a reaction term lives in the row-wise seed kernel, a flux term and a diffusivity D(u) around it: the single-launch route
     // runs the two-pass sequence for such a batch
     // ... and so do per-test-function loss weights, applied after it, and learnt source amplitudes, whose sums read udbar
-    case Route::fused8: return has_terms(b) || has_weights(b) || src_learnt(h, b) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
+    case Route::fused8: return has_terms(b) || has_weights(b) || src_learnt(h, b) || fld_learnt(h, b) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
     case Route::twopass: return run_twopass(h, b, h->gradbuf, fx);
   }
 }
@@ -2047,6 +2261,8 @@ static int apply_impl(vn_engine* h, float* loss_acc) {
     if (int rc = coef_finish(h, false, true, t)) return rc;
   if (h->sl_on)
     if (int rc = source_finish(h, false, true, t)) return rc;
+  if (h->fl_on)
+    if (int rc = field_finish(h, false, true, t)) return rc;
   h->step += 1;
   return VN_OK;
 }
@@ -2238,6 +2454,7 @@ int vn_eval_loss(vn_engine* h, int32_t batch, double out[4], float* lossVec_dev)
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   if (int rc = source_mix(h, h->batches[batch], batch)) return rc;
+  if (int rc = field_mix(h, h->batches[batch], batch)) return rc;
   VnEdgeSums fx;
   if (int rc = edge_passes(h, false, &fx)) return rc;
   if (int rc = run_forward_and_seed(h, h->batches[batch], false, lossVec_dev, h->lossbuf, fx)) return rc;
@@ -2264,9 +2481,10 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   }
   const Batch& b = h->batches[batch];
   if (int rc = source_mix(h, b, batch)) return rc;     // source identification: the mixed fp32 stream, widened exactly
+  if (int rc = field_mix(h, b, batch)) return rc;      // field identification: likewise the mixed direction
   VnObj64Problem p{};
   p.net = h->net; p.theta = theta_dev;
-  p.X = b.Input; p.G = b.gcoef; p.src = batch_src(h, b);
+  p.X = b.Input; p.G = batch_gcoef(h, b); p.src = batch_src(h, b);
   p.feN = h->feN; p.fedNt = h->fedNt; p.feW = fe_w(h);
   p.Nrow = b.Nrow; p.dNtrow = b.dNtrow; p.detJv = b.detJv; p.detJ = b.detJ;
   p.n_k = b.n_k; p.q = h->cfg.integ_num; p.td = h->cfg.time_dependent;
@@ -2412,6 +2630,9 @@ int vn_comm_init(vn_engine* h, int32_t rank, int32_t world, const void* unique_i
     if (h->batches[i].wt.S > 0)
       return fail(VN_EUNSUPPORTED, "vn_comm_init: batch %d has a causal registration (vn_set_causal); a rank's slab means would cover "
                                    "only its shard, so the ranks together would train another objective than one rank", (int)i);
+  if (h->fl_on)
+    return fail(VN_EUNSUPPORTED, "vn_comm_init while field amplitudes are learnt (vn_set_field_learn): the amplitude gradients are "
+                                 "not in the all-reduced buffer, so every rank would follow its own shard's");
   if (h->sl_on)
     return fail(VN_EUNSUPPORTED, "vn_comm_init while source amplitudes are learnt (vn_set_source_learn): the amplitude gradients are "
                                  "not in the all-reduced buffer, so every rank would follow its own shard's");

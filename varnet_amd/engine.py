@@ -83,6 +83,11 @@ _SIGS = {
                                       C.POINTER(C.c_double), C.c_double]),
     'vn_get_source_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32]),
     'vn_set_source_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
+    'vn_set_field_basis': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    'vn_set_field_learn': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.c_double]),
+    'vn_get_field_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32]),
+    'vn_set_field_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
     'vn_set_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_bind_grad_buffer': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vn_grad': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -391,8 +396,8 @@ class VNEngine:
         self._keep[('int', batch)] = (Input, gcoef, source, detJv, Nr, dNr)
         self._ck(self.lib.vn_set_interior(self.h, batch, _ptr(Input), _ptr(gcoef), _ptr(source), n_k,
                                           _ptr(detJv), detJ_s, _ptr(Nr), _ptr(dNr)))
-        for key in ('react', 'nlflux', 'nldiff', 'tfw', 'causal', 'srcbasis'):   # vn_set_interior cleared the batch's three polynomial
-            self._keep.pop((key, batch), None)                        # terms, its per-test-function loss weights and its source basis
+        for key in ('react', 'nlflux', 'nldiff', 'tfw', 'causal', 'srcbasis', 'fldbasis'):   # vn_set_interior cleared the batch's three
+            self._keep.pop((key, batch), None)      # polynomial terms, its per-test-function loss weights, its source and field bases
 
     def set_dedup(self, batch, Xu=None, uid=None, rowptr=None, rowidx=None):
         """Register (or, with Xu=None, clear) the de-duplicated formulation of `batch`."""
@@ -662,6 +667,62 @@ class VNEngine:
         """Overwrite the amplitudes (vn_set_source_amps): rounded to fp32, not clamped; the Adam slots stay."""
         v = np.asarray(amp, dtype=np.float64).reshape(-1)
         self._ck(self.lib.vn_set_source_amps(self.h, (C.c_double * max(v.size, 1))(*v), int(v.size)))
+
+    def set_field_basis(self, batch, G=None):
+        """Register (G=None: clear) the field basis of `batch` (vn_set_field_basis), after set_interior of that batch: G is
+        [J, rows, dim] (J streams laid out like gcoef), J <= 32."""
+        if G is None:
+            self._keep.pop(('fldbasis', batch), None)
+            self._ck(self.lib.vn_set_field_basis(self.h, int(batch), None, 0))
+            return
+        t = self.torch
+        if not isinstance(G, t.Tensor):
+            G = np.asarray(G, dtype=np.float32)
+        kept = self._keep.get(('int', batch))
+        J = int(G.shape[0])
+        G = self.dev(G.reshape(J, -1, self.dim))
+        # the ABI carries a pointer only: the length the kernels rely on is checked here
+        assert kept is None or G.shape[1] == kept[0].shape[0], \
+            'every basis stream must have one entry per interior row (%s != %s)' % (G.shape[1], kept[0].shape[0])
+        self._keep.pop(('fldbasis', batch), None)         # (a failed call leaves the batch without a basis)
+        self._ck(self.lib.vn_set_field_basis(self.h, int(batch), _ptr(G), J))
+        self._keep[('fldbasis', batch)] = G
+
+    def set_field_learn(self, mask=None, init=None, lo=None, hi=None, lr=None):
+        """Field identification (vn_set_field_learn): learn the masked amplitudes b_j of the batches' field bases next to the
+        parameters.  mask: J booleans; init: the J starting values (unmasked entries keep theirs); lo / hi: the clamp (None:
+        unbounded; entries may be +-inf); lr: their Adam rate.  mask=None switches learning off and frees everything."""
+        if mask is None:
+            self._ck(self.lib.vn_set_field_learn(self.h, 0, None, None, None, None, 0.0))
+            self._fld_J = None
+            return
+        m = [1 if x else 0 for x in np.asarray(mask).reshape(-1)]
+        J = len(m)
+        if init is None or lr is None:
+            raise ValueError('set_field_learn needs init (one value per amplitude) and lr')
+
+        def vec(a, fill, name):
+            v = np.full(J, fill, dtype=np.float64) if a is None else np.asarray(a, dtype=np.float64).reshape(-1)
+            if v.size != J:
+                raise ValueError('%s must have one entry per amplitude (%d), got %d' % (name, J, v.size))
+            return v
+        v0, l, u = vec(init, 0.0, 'init'), vec(lo, -np.inf, 'lo'), vec(hi, np.inf, 'hi')
+        self._ck(self.lib.vn_set_field_learn(self.h, J, (C.c_int32 * max(J, 1))(*m), (C.c_double * max(J, 1))(*v0),
+                                             (C.c_double * max(J, 1))(*l), (C.c_double * max(J, 1))(*u), float(lr)))
+        self._fld_J = J
+
+    def get_field_amps(self, grad=False, J=None):
+        """The amplitudes at the current state (vn_get_field_amps); grad=True: (amp, gradient of the last gradient evaluation)."""
+        J = int(J if J is not None else (getattr(self, '_fld_J', None) or 1))
+        a, g = (C.c_double * J)(), (C.c_double * J)()
+        self._ck(self.lib.vn_get_field_amps(self.h, a, g if grad else None, J))
+        a = np.array(list(a), dtype=np.float64)
+        return (a, np.array(list(g), dtype=np.float64)) if grad else a
+
+    def set_field_amps(self, amp):
+        """Overwrite the amplitudes (vn_set_field_amps): rounded to fp32, not clamped; the Adam slots stay."""
+        v = np.asarray(amp, dtype=np.float64).reshape(-1)
+        self._ck(self.lib.vn_set_field_amps(self.h, (C.c_double * max(v.size, 1))(*v), int(v.size)))
 
     def _n_k(self, batch):
         kept = self._keep.get(('int', batch))

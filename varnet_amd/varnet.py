@@ -600,8 +600,9 @@ class ManageTrainData:
                 for key in ('Input', 'gcoef', 'source', 'N_rows', 'dNt_rows', 'rate', 'phi', 'psi'):
                     if d.get(key) is not None:
                         d[key] = d[key].index_select(0, rows_all)
-                if d.get('srcphi') is not None:   # [J, nT]: the rows are the second axis
-                    d['srcphi'] = d['srcphi'].index_select(1, rows_all)
+                for key in ('srcphi', 'fldG'):    # [J, nT] and [J, nT, dim]: the rows are the second axis
+                    if d.get(key) is not None:
+                        d[key] = d[key].index_select(1, rows_all)
                 for key in ('detJ', 'slab'):      # one entry per test function
                     if d.get(key) is not None:
                         d[key] = d[key].index_select(0, perm_dev)
@@ -621,6 +622,8 @@ class ManageTrainData:
                     eng.set_nldiff(self.engine_batch(mb, bi), pick(d.get('psi')), d['nldiffCoef'])
                 if d.get('srcphi') is not None and n1 > n0:         # the source basis of these rows (vn_set_source_basis)
                     eng.set_source_basis(self.engine_batch(mb, bi), d['srcphi'][:, n0 * q:n1 * q].contiguous())
+                if d.get('fldG') is not None and n1 > n0:           # the field basis of these rows (vn_set_field_basis)
+                    eng.set_field_basis(self.engine_batch(mb, bi), d['fldG'][:, n0 * q:n1 * q].contiguous())
                 if d.get('slab') is not None and n1 > n0 and self.vn.causal is not None:      # causal weights (vn_set_causal)
                     eng.set_causal(self.engine_batch(mb, bi), pick_k(d['slab']), self.vn.causalSlabNum(), float(self.vn.causal))
                 perm = getattr(self, 'biPerm', {}).get(bi)
@@ -801,7 +804,8 @@ class VarNet:
                  bDiscNum=[], tDiscNum=[], MORdiscScheme=None, processors=None, controller=None,
                  integPnum=2, optimizer='adam', learning_rate=0.001, fluxBC=False, lbfgsLoss64=False,
                  causal=None, causalSlabs=None, periodicDeriv=None, observations=None, obsWeight=None,
-                 learnCoef=None, coefLr=None, coefBounds=None, learnSource=None, sourceLr=None, sourceBounds=None):
+                 learnCoef=None, coefLr=None, coefBounds=None, learnSource=None, sourceLr=None, sourceBounds=None,
+                 learnField=None, fieldLr=None, fieldBounds=None):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -869,6 +873,9 @@ class VarNet:
         if learnSource is not None and MORvar is not None:
             raise NotImplementedError('learnSource with model-order reduction is not supported: neither the source basis nor '
                                       'the observations it needs are')
+        if learnField is not None and MORvar is not None:
+            raise NotImplementedError('learnField with model-order reduction is not supported: neither the field bases nor '
+                                      'the observations it needs are')
         # observations=... (extension; no reference counterpart): sensor data as linear functionals of the solution, fitted by a
         # misfit term obsWeight * O next to the PDE's loss (`obsData`)
         if observations is None:
@@ -906,6 +913,20 @@ class VarNet:
                                           'search over (parameters, amplitudes) and an RMSProp update are not built)' % (optimizer,))
             if causal is not None:
                 raise NotImplementedError('learnSource with causal=%r: the causal weights are applied after the seeds the amplitude '
+                                          'gradient is reduced from' % (causal,))
+
+        # learnField=... (extension; no reference counterpart): field identification, the masked amplitudes of the PDE's diffusivity
+        # and velocity bases are learnt next to the network from the observations (`fieldLearnData`)
+        self.fldLearn = self.fieldLearnData(PDE, learnField, fieldLr, fieldBounds, learning_rate)
+        if self.fldLearn is not None:
+            if observations is None:
+                raise ValueError('learnField needs observations=...: without interior data every amplitude admits a solution of '
+                                 'the boundary value problem, so the loss cannot tell one value from another')
+            if optimizer.lower() != 'adam':
+                raise NotImplementedError('learnField with optimizer=%r: the amplitudes are updated by the Adam step only (an L-BFGS '
+                                          'search over (parameters, amplitudes) and an RMSProp update are not built)' % (optimizer,))
+            if causal is not None:
+                raise NotImplementedError('learnField with causal=%r: the causal weights are applied after the seeds the amplitude '
                                           'gradient is reduced from' % (causal,))
 
         inpDim = dim + (1 if timeDependent else 0)
@@ -955,6 +976,9 @@ class VarNet:
                                       'buffer, so every rank would follow its own shard')
         if self.srcLearn is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
             raise NotImplementedError('learnSource with towers: the amplitude gradients are not part of the all-reduced '
+                                      'buffer, so every rank would follow its own shard')
+        if self.fldLearn is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
+            raise NotImplementedError('learnField with towers: the amplitude gradients are not part of the all-reduced '
                                       'buffer, so every rank would follow its own shard')
         if isinstance(processors, (list, tuple)) and len(processors) > 1 and self.world == 1:
             # the reference's single-process multi-GPU call (TFModel.py:120-165): this process becomes the
@@ -1031,6 +1055,10 @@ class VarNet:
             # the engine owns the amplitudes from here on: every batch registered later carries its basis streams
             sl = self.srcLearn
             self.engine.set_source_learn(sl['mask'], sl['init'], sl['lo'], sl['hi'], sl['lr'])
+        if self.fldLearn is not None:
+            # likewise the field amplitudes: every batch registered later carries its [J, nT, dim] basis streams
+            fl = self.fldLearn
+            self.engine.set_field_learn(fl['mask'], fl['init'], fl['lo'], fl['hi'], fl['lr'])
         self.tfData = self.engine       # name kept for scripts that poke at `VarNet.tfData`
         from .launch import mark_stage
         mark_stage('engine_ready')      # past the launcher's bootstrap deadline: a rank that trains for hours is healthy
@@ -1286,6 +1314,148 @@ class VarNet:
         if v.size != J or not np.all(np.isfinite(v)):
             raise ValueError('setSourceAmplitudes takes %d finite numbers, got %r' % (J, a))
         self.engine.set_source_amps(v)
+
+    # -- field identification: learnt amplitudes of a diffusivity and a velocity basis (extension) -----
+    FIELD_KEYS = ('diff', 'vel')
+
+    @staticmethod
+    def _field_sizes(PDE):
+        """(J_kappa, J_v): the number of functions of the PDE's diffusivity and velocity bases (0 without one)."""
+        return len(getattr(PDE, 'diffBasis', None) or []), len(getattr(PDE, 'velBasis', None) or [])
+
+    @staticmethod
+    def fieldLearnData(PDE, learnField, fieldLr=None, fieldBounds=None, learning_rate=0.001):
+        """(No reference counterpart: `VarNet(..., learnField=...)`.)  The registration of `vn_set_field_learn`, or None without
+        learnField: mask, init, lo, hi (J = J_kappa + J_v entries each, the diffusivity streams first) and lr.  learnField =
+        {'diff': True | mask, 'vel': True | mask} (a key left out: none of that basis is learnt); the PDE's diffAmp / velAmp are the
+        initial guess; fieldLr defaults to the network's learning rate; fieldBounds = {'diff': ..., 'vel': ...}, each (lo, hi) for
+        every learnt amplitude of that basis or a list with one entry per function, each None or (lo, hi), None for an open side."""
+        if learnField is None or learnField is False:
+            if fieldLr is not None:
+                raise ValueError('fieldLr=%r is an option of learnField=...' % (fieldLr,))
+            if fieldBounds is not None:
+                raise ValueError('fieldBounds is an option of learnField=...')
+            return None
+        keys = VarNet.FIELD_KEYS
+        if not isinstance(learnField, dict) or not learnField or any(k not in keys for k in learnField):
+            raise ValueError('learnField must be a dict {\'diff\': True | mask, \'vel\': True | mask}, got %r' % (learnField,))
+        if fieldBounds is not None and (not isinstance(fieldBounds, dict) or any(k not in keys for k in fieldBounds)):
+            raise ValueError('fieldBounds must be a dict {\'diff\': ..., \'vel\': ...}, got %r' % (fieldBounds,))
+        Jk, Jv = VarNet._field_sizes(PDE)
+        isbool = lambda x: isinstance(x, (bool, np.bool_)) or (isinstance(x, (int, np.integer)) and x in (0, 1))
+        free = lambda x: x is None or (isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool))
+        masks, a0s, los, his = [], [], [], []
+        for key, J, amp in (('diff', Jk, 'diffAmp'), ('vel', Jv, 'velAmp')):
+            sel = learnField.get(key)
+            if sel is not None and sel is not False and J == 0:
+                raise ValueError('learnField[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (key, key, key))
+            if J == 0:
+                if fieldBounds is not None and fieldBounds.get(key) is not None:
+                    raise ValueError('fieldBounds[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (key, key, key))
+                continue
+            if sel is None or sel is False:
+                mask = np.zeros(J, dtype=bool)
+            elif sel is True:
+                mask = np.ones(J, dtype=bool)
+            else:
+                if not isinstance(sel, (list, tuple, np.ndarray)) or len(sel) != J or not all(isbool(x) for x in sel):
+                    raise ValueError('learnField[%r] must be True or a mask of %d booleans (one per function of %sBasis), got %r'
+                                     % (key, J, key, sel))
+                mask = np.array([bool(x) for x in sel])
+            a0 = np.asarray(getattr(PDE, amp), dtype=np.float64)
+            lo, hi = np.full(J, -np.inf), np.full(J, np.inf)
+            bounds = None if fieldBounds is None else fieldBounds.get(key)
+            if bounds is not None:
+                if isinstance(bounds, (list, tuple)) and len(bounds) == 2 and all(free(x) for x in bounds):
+                    entries = [tuple(bounds) if mask[j] else None for j in range(J)]      # one pair: every learnt amplitude
+                elif isinstance(bounds, (list, tuple)) and len(bounds) == J:
+                    entries = list(bounds)
+                else:
+                    raise ValueError('fieldBounds[%r] must be (lo, hi) or a list of %d entries, each None or (lo, hi), got %r'
+                                     % (key, J, bounds))
+                for j, bd in enumerate(entries):
+                    if bd is None:
+                        continue
+                    if not mask[j]:
+                        raise ValueError('fieldBounds[%r][%d] bounds an amplitude that learnField does not select' % (key, j))
+                    if not isinstance(bd, (list, tuple)) or len(bd) != 2:
+                        raise ValueError('fieldBounds[%r][%d] must be None or (lo, hi), got %r' % (key, j, bd))
+                    a = -np.inf if bd[0] is None else bd[0]
+                    b = np.inf if bd[1] is None else bd[1]
+                    for x in (a, b):
+                        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or np.isnan(x):
+                            raise ValueError('fieldBounds[%r][%d] must hold numbers or None, got %r' % (key, j, bd))
+                    if a > b:
+                        raise ValueError('fieldBounds[%r][%d]: lower bound %r above upper bound %r' % (key, j, a, b))
+                    if not a <= a0[j] <= b:
+                        raise ValueError('fieldBounds[%r][%d] = %r excludes the initial guess %r' % (key, j, bd, float(a0[j])))
+                    lo[j], hi[j] = float(a), float(b)
+            masks.append(mask); a0s.append(a0); los.append(lo); his.append(hi)
+        mask = np.concatenate(masks)
+        if not mask.any():
+            raise ValueError('learnField selects no amplitude')
+        lr = learning_rate if fieldLr is None else fieldLr
+        if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not np.isfinite(lr) or lr <= 0:
+            raise ValueError('fieldLr=%r must be a finite number > 0' % (lr,))
+        return dict(mask=[int(x) for x in mask], init=np.concatenate(a0s), lo=np.concatenate(los), hi=np.concatenate(his),
+                    lr=float(lr), Jk=Jk, Jv=Jv)
+
+    def _field_basis(self, Input, grad=False):
+        """(chi [Jk, n, 1], grad chi [Jk, n, dim] or None without `grad`, omega [Jv, n, dim]) of the PDE's field bases at the rows
+        of Input, fp64."""
+        dim, PDE = self.dim, self.PDE
+        targ = [Input[:, dim][np.newaxis].T] if PDE.timeDependent else []
+        X = Input[:, 0:dim]
+        val = PDE.field_basis_values
+        return (val(getattr(PDE, 'diffBasis', None) or [], 'diffBasis', 1, X, targ),
+                val(getattr(PDE, 'd_diffBasis', None) or [], 'd_diffBasis', dim, X, targ) if grad else None,
+                val(getattr(PDE, 'velBasis', None) or [], 'velBasis', dim, X, targ))
+
+    def _field_vector(self):
+        """The J = J_kappa + J_v amplitudes as one vector: the engine's with learnField, else the PDE's."""
+        Jk, Jv = self._field_sizes(self.PDE)
+        if getattr(self, 'fldLearn', None) is not None and getattr(self, 'engine', None) is not None:
+            return np.asarray(self.engine.get_field_amps(J=Jk + Jv), dtype=np.float64)
+        return np.concatenate([np.asarray(getattr(self.PDE, 'diffAmp', []), dtype=np.float64),
+                               np.asarray(getattr(self.PDE, 'velAmp', []), dtype=np.float64)])
+
+    def fieldAmplitudes(self):
+        """{'diff': J_kappa amplitudes, 'vel': J_v amplitudes} of the PDE's field bases at the current state: the learnt values
+        with learnField, else the PDE's."""
+        Jk, Jv = self._field_sizes(self.PDE)
+        if Jk + Jv == 0:
+            raise ValueError('fieldAmplitudes: the PDE has no field basis (ADPDE(..., diffBasis=[...], velBasis=[...]))')
+        v = self._field_vector()
+        return {'diff': v[:Jk].copy(), 'vel': v[Jk:].copy()}
+
+    def fieldGrad(self):
+        """d loss / d amplitude of the last gradient evaluation as {'diff': ..., 'vel': ...} (zeros where not learnt)."""
+        if self.fldLearn is None:
+            raise ValueError('fieldGrad: this instance learns no field amplitudes (learnField=...)')
+        Jk, Jv = self._field_sizes(self.PDE)
+        g = np.asarray(self.engine.get_field_amps(grad=True, J=Jk + Jv)[1], dtype=np.float64)
+        return {'diff': g[:Jk].copy(), 'vel': g[Jk:].copy()}
+
+    def setFieldAmplitudes(self, amps):
+        """Overwrite amplitudes between train() calls: {'diff': [...], 'vel': [...]} (a key left out keeps its values).  Not
+        clamped to fieldBounds (the next update is)."""
+        if self.fldLearn is None:
+            raise ValueError('setFieldAmplitudes: this instance learns no field amplitudes (learnField=...)')
+        if not isinstance(amps, dict) or not amps or any(k not in self.FIELD_KEYS for k in amps):
+            raise ValueError('setFieldAmplitudes takes a dict {\'diff\': [...], \'vel\': [...]}, got %r' % (amps,))
+        Jk, Jv = self._field_sizes(self.PDE)
+        cur = self._field_vector()
+        for key, sl, J in (('diff', slice(0, Jk), Jk), ('vel', slice(Jk, Jk + Jv), Jv)):
+            if key not in amps:
+                continue
+            try:
+                v = np.asarray(amps[key], dtype=np.float64).reshape(-1)
+            except (TypeError, ValueError):
+                v = np.empty(0)
+            if J == 0 or v.size != J or not np.all(np.isfinite(v)):
+                raise ValueError('setFieldAmplitudes[%r] takes %d finite numbers, got %r' % (key, J, amps[key]))
+            cur[sl] = v
+        self.engine.set_field_amps(cur)
 
     # -- causal time-slab weights (extension) ------------------------------------------------------
     @staticmethod
@@ -1723,9 +1893,10 @@ class VarNet:
             out = uf.vstack([out, PDE.IC(biInput[ind:, :dim], **arg)])
         return out
 
-    def PDEinpData(self, Input, inpArg=[], basis=True):
+    def PDEinpData(self, Input, inpArg=[], basis=True, field=True):
         """kappa, v, s at the rows of Input (VarNet.py:726-774).  With a source basis s = source + sum_j a_j phi_j at the current
-        amplitudes (`sourceAmplitudes`); basis=False: `source` alone."""
+        amplitudes (`sourceAmplitudes`); basis=False: `source` alone.  With field bases kappa and v are the sums at the current
+        amplitudes (`fieldAmplitudes`); field=False: `diff` and `vel` alone."""
         dim, PDE = self.dim, self.PDE
         if uf.isempty(inpArg):
             diffArg, velArg, sourceArg = {}, {}, {}
@@ -1736,7 +1907,29 @@ class VarNet:
         src = PDE.sourceFun(X, *targ, **sourceArg)
         if basis and getattr(PDE, 'sourceBasis', None) is not None:
             src = np.asarray(src, dtype=np.float64).reshape(-1, 1) + self._source_basis(Input) @ self.sourceAmplitudes().reshape(-1, 1)
-        return PDE.diffFun(X, *targ, **diffArg), PDE.velFun(X, *targ, **velArg), src
+        Jk, Jv = self._field_sizes(PDE)
+        if Jk + Jv == 0:
+            return PDE.diffFun(X, *targ, **diffArg), PDE.velFun(X, *targ, **velArg), src
+        # (a basis excludes MOR: no extra arguments) the plain fields, plus the sums at the current amplitudes
+        diff = np.asarray((PDE.diffFun0 if Jk else PDE.diffFun)(X, *targ), dtype=np.float64).reshape(-1, 1)
+        vel = np.asarray((PDE.velFun0 if Jv else PDE.velFun)(X, *targ), dtype=np.float64).reshape(-1, dim)
+        if field:
+            b = self._field_vector()
+            chi, _, omega = self._field_basis(Input)
+            diff = diff + np.tensordot(b[:Jk], chi, axes=1)
+            vel = vel + np.tensordot(b[Jk:], omega, axes=1)
+        return diff, vel, src
+
+    def diffGradData(self, Input):
+        """grad kappa at the rows of Input, [n, dim]: with a diffusivity basis at the current amplitudes (`fieldAmplitudes`)."""
+        dim, PDE = self.dim, self.PDE
+        targ = [Input[:, dim][np.newaxis].T] if PDE.timeDependent else []
+        X = Input[:, 0:dim]
+        Jk = self._field_sizes(PDE)[0]
+        if Jk == 0:
+            return PDE.d_diffFun(X, *targ)
+        g = np.asarray(PDE.d_diffFun0(X, *targ), dtype=np.float64).reshape(-1, dim)
+        return g + np.tensordot(self._field_vector()[:Jk], self._field_basis(Input, grad=True)[1], axes=1)
 
     def _reaction_rate(self, Input):
         """Reaction rate at the rows of Input (a column), evaluated like the source (PDEinpData)."""
@@ -1818,7 +2011,8 @@ class VarNet:
         biLabel = self.biTrainData(biInput, biDof, biArg)
         # learnt amplitudes: the engine mixes s0 and the basis streams itself; else the sum is folded into the source here
         srcphi = None
-        diff, vel, src = self.PDEinpData(Input, inpArg, basis=self.srcLearn is None)
+        # ... and likewise g0 and the basis streams of gcoef
+        diff, vel, src = self.PDEinpData(Input, inpArg, basis=self.srcLearn is None, field=self.fldLearn is None)
         if self.srcLearn is not None:
             srcphi = eng.dev(np.ascontiguousarray(self._source_basis(Input).T))         # [J, nT], stream-major, fp32
         nt, q, dim = fd.nt, fd.integNum, self.dim
@@ -1848,6 +2042,17 @@ class VarNet:
             # gcoef = kappa*dNx + v*N  (VarNet.py:837) with the period tables broadcast over test functions
             gcoef = (diff.reshape(nt, q, 1) * fd.dNx[None, :, :] +
                      vel.reshape(nt, q, dim) * fd.N[None, :, None]).reshape(nt * q, dim)
+        fldG = None
+        if self.fldLearn is not None:
+            # G_j = chi_j dN/dx (diffusivity streams, first) or omega_j N (velocity streams): [J, nT, dim], stream-major, evaluated
+            # in fp64 like gcoef and rounded once on upload
+            chi, _, omega = self._field_basis(Input)
+            if fd.detJvec:
+                G = np.concatenate([chi * dNxr[None], omega * Nr.reshape(1, -1, 1)])
+            else:
+                G = np.concatenate([(chi.reshape(-1, nt, q, 1) * fd.dNx[None, None]).reshape(-1, nt * q, dim),
+                                    (omega.reshape(-1, nt, q, dim) * np.reshape(fd.N, -1)[None, None, :, None]).reshape(-1, nt * q, dim)])
+            fldG = eng.dev(np.ascontiguousarray(G))
         if MORinp is not None:
             Input = np.hstack([Input, np.tile(MORinp, [Input.shape[0], 1])])
             biInput = np.hstack([biInput, np.tile(MORinp, [biInput.shape[0], 1])])
@@ -1871,7 +2076,7 @@ class VarNet:
             nlfluxCoef = list(self.PDE.nlfluxCoef)
         slab = self._slab_tensor(Input) if self.causal is not None else None   # (time column dim: the same ids for every MOR batch)
         return dict(Input=eng.dev(Input), Input_host=Input, gcoef=eng.dev(gcoef), rate=rate, reactCoef=reactCoef, slab=slab,
-                    phi=phi, nlfluxCoef=nlfluxCoef, psi=psi, nldiffCoef=nldiffCoef, srcphi=srcphi,
+                    phi=phi, nlfluxCoef=nlfluxCoef, psi=psi, nldiffCoef=nldiffCoef, srcphi=srcphi, fldG=fldG,
                     source=eng.dev(src.reshape(-1)) if self.lossOpt['isSource'] else None,
                     biInput=eng.dev(biInput), biLabel=eng.dev(biLabel.reshape(-1)),
                     N_rows=N_rows, dNt_rows=dNt_rows,
@@ -2357,6 +2562,10 @@ class VarNet:
             sl = self.srcLearn
             trainRes.writeCase('Learnt source amplitudes: mask %s, initial %s, final %s\n'
                                % (sl['mask'], [float(x) for x in sl['init']], [float(x) for x in self.sourceAmplitudes()]))
+        if self.fldLearn is not None and self.rank == 0:
+            fl = self.fldLearn
+            trainRes.writeCase('Learnt field amplitudes (diff, then vel): mask %s, initial %s, final %s\n'
+                               % (fl['mask'], [float(x) for x in fl['init']], [float(x) for x in self._field_vector()]))
         return trainRes
 
     # -- checkpoints ----------------------------------------------------------------------------------
@@ -2398,6 +2607,9 @@ class VarNet:
         if getattr(self, 'srcLearn', None) is not None:
             # the J amplitudes (vn_get_source_amps); their Adam slots restart from zero, as for pde_coefficients
             out['source_amplitudes'] = self.sourceAmplitudes()
+        if getattr(self, 'fldLearn', None) is not None:
+            # the J amplitudes, diffusivity streams first (vn_get_field_amps); their Adam slots restart from zero likewise
+            out['field_amplitudes'] = self._field_vector()
         return out
 
     def restore_arrays(self, arrays):
@@ -2425,6 +2637,8 @@ class VarNet:
             self.engine.set_coefs(np.asarray(arrays['pde_coefficients'], dtype=np.float64).reshape(-1))
         if getattr(self, 'srcLearn', None) is not None and 'source_amplitudes' in arrays:
             self.engine.set_source_amps(np.asarray(arrays['source_amplitudes'], dtype=np.float64).reshape(-1))
+        if getattr(self, 'fldLearn', None) is not None and 'field_amplitudes' in arrays:
+            self.engine.set_field_amps(np.asarray(arrays['field_amplitudes'], dtype=np.float64).reshape(-1))
 
     def saveModel(self, epoch):
         """`saver.save(sess, 'best_model', global_step=epoch)` with max_to_keep=2 (TFModel.py:307,
@@ -2731,12 +2945,13 @@ class VarNet:
         elif PDE.cEx is not None:
             cEx = PDE.cEx(Input[:, :dim], Input[:, dim:dim + 1]) if td else PDE.cEx(Input[:, :dim])
         targ = [Input[:, dim:dim + 1]] if td else []
-        diff_dx = fd.d_diff if noInput else PDE.d_diffFun(Input[:, :dim], *targ)
+        learnt_field = getattr(self, 'fldLearn', None) is not None       # kappa, v and grad kappa move with the amplitudes
+        diff_dx = fd.d_diff if noInput and not learnt_field else self.diffGradData(Input)
         res, err = 0., (0. if PDE.cEx is not None else None)
         resVec = cApp = None
         for b in batchRange:
             if PDE.MORvar is None:
-                if noInput and fd.uniform_inpData[0] is not None and getattr(self, 'srcLearn', None) is None:
+                if noInput and fd.uniform_inpData[0] is not None and getattr(self, 'srcLearn', None) is None and not learnt_field:
                     diff, vel, src = fd.uniform_inpData
                 else:
                     diff, vel, src = self.PDEinpData(Input)
