@@ -141,6 +141,77 @@ constexpr bool kWithF32Point = true;     // cross-check build: vn_pgrad16 / vn_t
 constexpr bool kWithF32Point = false;
 #endif
 
+// ---- learnt vectors: small vectors the Adam step moves next to the parameters ----------------
+// One record per vector; what differs between the vectors is a row of kLearnt.  Everything that handles them (learnt_* below
+// vn_engine) runs over the records in LearntId order.
+enum LearntId { LV_COEF, LV_SRC, LV_FLD, LV_N };
+constexpr int LV_CAP = VN_SRC_JMAX;              // the largest capacity of any kind (host staging arrays)
+
+struct Learnt {
+  bool on = false;
+  int J = 0;                                      // entries in use (<= the kind's cap)
+  unsigned long long mask = 0;                    // bit j: entry j is learnt
+  double lr = 0.0;
+  float* state = nullptr;                         // [6 * cap] (value | m | v) at stride cap, then their copy of vn_state_snapshot
+  float* bounds = nullptr;                        // [2 * cap] (lo | hi) on the device, for the kinds that keep them there
+  float hbounds[2 * VN_COEF_N] = {};              // (lo | hi) of the kind whose bounds travel by value in the launch arguments
+  double* grad = nullptr;                         // [cap] gradient of the last gradient evaluation
+  float* part = nullptr;                          // [maxblk, J] partials of the reduction
+  int blocks = 0;                                 // partials the current gradient evaluation wrote (0: the batch has nothing to reduce)
+};
+
+// fold + Adam step + clamp of one vector: the arguments both apply kernels share (`fold`: the partials are folded into grad first)
+template <class Args>
+void learnt_apply_args(Args& a, const Learnt& v, int cap, bool fold, bool update, double t, const vn_config& c) {
+  if (fold) { a.part = v.part; a.blocks = v.blocks; }
+  a.grad = v.grad; a.m = v.state + cap; a.v = v.state + 2 * cap;
+  a.mask = (decltype(a.mask))v.mask;
+  a.update = update ? 1 : 0;
+  if (update) {
+    a.lr_t = (float)(v.lr * std::sqrt(1.0 - std::pow(c.beta2, t)) / (1.0 - std::pow(c.beta1, t)));
+    a.b1 = (float)c.beta1; a.b2 = (float)c.beta2; a.eps = (float)c.eps;
+  }
+}
+
+hipError_t learnt_apply_coef(const Learnt& v, int cap, bool fold, bool update, double t, const vn_config& c, hipStream_t s) {
+  VnCoefApplyArgs a{};
+  learnt_apply_args(a, v, cap, fold, update, t, c);
+  a.coef = v.state;
+  std::copy(v.hbounds, v.hbounds + VN_COEF_N, a.lo);
+  std::copy(v.hbounds + VN_COEF_N, v.hbounds + 2 * VN_COEF_N, a.hi);
+  return vn_coef_apply_launch(a, s);
+}
+
+// (vn_source_apply_kernel: nothing in it is the source's, so the field amplitudes go through it at their own stride)
+hipError_t learnt_apply_amps(const Learnt& v, int cap, bool fold, bool update, double t, const vn_config& c, hipStream_t s) {
+  VnSrcApplyArgs a{};
+  learnt_apply_args(a, v, cap, fold, update, t, c);
+  a.J = v.J; a.amp = v.state;
+  a.lo = v.bounds; a.hi = v.bounds + cap;
+  return vn_source_apply_launch(a, s);
+}
+
+struct LearntKind {
+  int cap;                    // capacity, and the stride of (value | m | v)
+  int maxblk;                 // cap of the reduction grid
+  bool dev_bounds;            // bounds in Learnt::bounds (else by value: Learnt::hbounds)
+  hipError_t (*apply)(const Learnt&, int cap, bool fold, bool update, double t, const vn_config&, hipStream_t);
+  const char* setter;         // the messages' nouns
+  const char* noun;
+  const char* what;
+  const char* grads;
+};
+constexpr LearntKind kLearnt[LV_N] = {
+  {VN_COEF_N, VN_COEF_MAXBLK, false, learnt_apply_coef, "vn_set_coef_learn", "coefficient", "coefficients", "the nine coefficient gradients"},
+  {VN_SRC_JMAX, VN_SRC_MAXBLK, true, learnt_apply_amps, "vn_set_source_learn", "amplitude", "source amplitudes", "the amplitude gradients"},
+  {VN_FLD_JMAX, VN_FLD_MAXBLK, true, learnt_apply_amps, "vn_set_field_learn", "amplitude", "field amplitudes", "the amplitude gradients"},
+};
+
+int learnt_weights_refusal(const LearntKind& k, int batch) {
+  return fail(VN_EUNSUPPORTED, "learnt %s (%s) next to per-test-function loss weights (vn_set_tf_weights / vn_set_causal, batch %d): "
+                               "the weights are applied after the seeds the %s reduction reads", k.what, k.setter, batch, k.noun);
+}
+
 }  // namespace
 
 #ifndef VN_WITH_FUSED32
@@ -224,36 +295,12 @@ struct vn_engine {
   float *ou = nullptr, *oud = nullptr, *oubar = nullptr, *oudbar = nullptr, *oloss = nullptr, *opartial = nullptr;
   long ou_cap = 0, oud_cap = 0, oubar_cap = 0, oudbar_cap = 0, oloss_cap = 0, opartial_cap = 0;
   double* omisfit = nullptr;                      // device slot: the unweighted misfit O of the last evaluation
-  // inverse mode (vn_set_coef_learn, vn_coef.hip): the nine coefficients live on the device while they are learnt
-  bool cl_on = false;
-  unsigned cl_mask = 0;                           // bit i: entry i is learnt
-  double cl_lo[VN_COEF_N] = {}, cl_hi[VN_COEF_N] = {}, cl_lr = 0.0;
-  float* cl_state = nullptr;                      // [54] (coef | m | v), then their copy of vn_state_snapshot
-  double* cl_grad = nullptr;                      // [9] coefficient gradient of the last gradient evaluation
-  float* cl_part = nullptr;                       // [VN_COEF_MAXBLK, 9] partials of the reduction
-  int cl_blocks = 0;                              // partials the current gradient evaluation wrote (0: the batch carries no term)
+  // the vectors learnt next to the parameters, by LearntId: the nine coefficients of inverse mode (vn_set_coef_learn, vn_coef.hip),
+  // which live on the device while they are learnt, and the engine-wide amplitudes of the batches' source bases
+  // (vn_set_source_learn, vn_source.hip) and gcoef bases (vn_set_field_learn, vn_field.hip); then each feature's own work buffers
+  Learnt lv[LV_N];
   float* cl_acc = nullptr; long cl_acc_cap = 0;   // [3, U] accR_j, accF_j, gs_j of the de-duplicated step
-  // source identification (vn_set_source_learn, vn_source.hip): the amplitudes of the batches' source bases, engine-wide
-  bool sl_on = false;
-  int sl_J = 0;
-  unsigned long long sl_mask = 0;                 // bit j: amplitude j is learnt
-  double sl_lr = 0.0;
-  float* sl_state = nullptr;                      // [6 * 64] (amp | m | v) at stride 64, then their copy of vn_state_snapshot
-  float* sl_bounds = nullptr;                     // [2 * 64] (lo | hi)
-  double* sl_grad = nullptr;                      // [64] amplitude gradient of the last gradient evaluation
-  float* sl_part = nullptr;                       // [VN_SRC_MAXBLK, J] partials of the reduction
-  int sl_blocks = 0;                              // partials the current gradient evaluation wrote (0: the batch has no basis)
   float* sl_mix = nullptr; long sl_mix_cap = 0;   // [nT] s0 + sum_j a_j phi_j of the batch being evaluated
-  // field identification (vn_set_field_learn, vn_field.hip): the amplitudes of the batches' gcoef bases, engine-wide
-  bool fl_on = false;
-  int fl_J = 0;
-  unsigned fl_mask = 0;                           // bit j: amplitude j is learnt
-  double fl_lr = 0.0;
-  float* fl_state = nullptr;                      // [6 * 32] (amp | m | v) at stride 32, then their copy of vn_state_snapshot
-  float* fl_bounds = nullptr;                     // [2 * 32] (lo | hi)
-  double* fl_grad = nullptr;                      // [32] amplitude gradient of the last gradient evaluation
-  float* fl_part = nullptr;                       // [VN_FLD_MAXBLK, J] partials of the reduction
-  int fl_blocks = 0;                              // partials the current gradient evaluation wrote (0: the batch has no basis)
   float* fl_mix = nullptr; long fl_mix_cap = 0;   // [nT, dim] g0 + sum_j b_j G_j of the batch being evaluated
   float* fl_csr = nullptr; long fl_csr_cap = 0;   // [nT, dim] fl_mix in CSR order (de-duplicated step), rebuilt every evaluation
   float* fl_pack = nullptr; long fl_pack_cap = 0; // [nT, 4] (u, grad u) of the batch's own rows (row-wise gradient evaluation)
@@ -428,12 +475,12 @@ int check_batch(vn_engine* h, int32_t batch) {
 inline const float* bi_x(const vn_engine* h, const Batch& b) { return b.biInput ? b.biInput : h->biInput; }
 inline const float* bi_y(const vn_engine* h, const Batch& b) { return b.biLabel ? b.biLabel : h->biLabel; }
 // (while amplitudes are learnt, a batch with a basis reads the mixed stream source_mix formed at the start of the evaluation)
-inline bool src_learnt(const vn_engine* h, const Batch& b) { return h->sl_on && b.sb_phi; }
+inline bool src_learnt(const vn_engine* h, const Batch& b) { return h->lv[LV_SRC].on && b.sb_phi; }
 inline const float* batch_src(const vn_engine* h, const Batch& b) {
   return !h->cfg.has_source ? nullptr : src_learnt(h, b) ? h->sl_mix : b.source;
 }
 // (... and the mixed direction field_mix formed there in place of the batch's gcoef)
-inline bool fld_learnt(const vn_engine* h, const Batch& b) { return h->fl_on && b.fb_G; }
+inline bool fld_learnt(const vn_engine* h, const Batch& b) { return h->lv[LV_FLD].on && b.fb_G; }
 inline const float* batch_gcoef(const vn_engine* h, const Batch& b) { return fld_learnt(h, b) ? h->fl_mix : b.gcoef; }
 inline const float* fe_w(const vn_engine* h) { return (h->cfg.has_integw && h->has_feW) ? h->feW : nullptr; }
 
@@ -530,7 +577,7 @@ VnSeedArgs seed_args(const vn_engine* h, const Batch& b) {
   a.ub = h->ub; a.label = bi_y(h, b); a.nB = h->nB; a.bDof = h->bDof; a.biDimVal = (float)h->biDimVal;
   a.w0 = (float)h->w[0]; a.w1 = (float)h->w[1]; a.w2 = (float)h->w[2];
   if (b.react.on) { a.react = 1; a.rate = b.react.stream; a.c1 = (float)b.react.c[0]; a.c2 = (float)b.react.c[1]; a.c3 = (float)b.react.c[2]; }
-  if (b.react.on && h->cl_on) a.coef = h->cl_state;
+  if (b.react.on && h->lv[LV_COEF].on) a.coef = h->lv[LV_COEF].state;
   return a;
 }
 
@@ -571,8 +618,8 @@ int check_Np(const vn_engine* h, const TermKind& k, int batch = -1, const char* 
 
 // Inverse mode: where a registered term of b reads its three coefficients (nullptr: learning off, the batch's own by value)
 const float* term_cp(const vn_engine* h, const Batch& b, const Term& t) {
-  if (!h->cl_on) return nullptr;
-  return h->cl_state + 3 * (&t == &b.react ? 0 : &t == &b.nlflux ? 1 : 2);
+  if (!h->lv[LV_COEF].on) return nullptr;
+  return h->lv[LV_COEF].state + 3 * (&t == &b.react ? 0 : &t == &b.nlflux ? 1 : 2);
 }
 
 // Row-wise routes: values in h->u, integrand / seeds in h->ud, h->ubar, h->udbar, A_r of the D(u) pair saved in h->nd_A
@@ -601,16 +648,16 @@ int terms_seed_rows(vn_engine* h, const Batch& b) {
   if (src_learnt(h, b)) {                          // source identification: the amplitude sums read udbar before D(u) rescales it
     VnSrcGradArgs g{};
     g.udbar = h->udbar; g.Nrow = b.Nrow; g.feN = h->feN; g.phi = b.sb_phi; g.J = b.sb_J;
-    g.nT = b.n_k * h->cfg.integ_num; g.q = h->cfg.integ_num; g.mask = h->sl_mask; g.part = h->sl_part;
-    HIPCHK(vn_srcgrad_rows_launch(g, &h->sl_blocks, h->stream));
+    g.nT = b.n_k * h->cfg.integ_num; g.q = h->cfg.integ_num; g.mask = h->lv[LV_SRC].mask; g.part = h->lv[LV_SRC].part;
+    HIPCHK(vn_srcgrad_rows_launch(g, &h->lv[LV_SRC].blocks, h->stream));
   }
-  if (h->cl_on && has_terms(b)) {                  // inverse mode: the coefficient sums read udbar before D(u) rescales it
+  if (h->lv[LV_COEF].on && has_terms(b)) {   // inverse mode: the coefficient sums read udbar before D(u) rescales it
     VnCoefRowsArgs c{};
     c.u = h->u; c.udbar = h->udbar; c.nT = b.n_k * h->cfg.integ_num; c.q = h->cfg.integ_num;
     c.react = b.react.on ? 1 : 0; c.rate = b.react.stream; c.Nrow = b.Nrow; c.feN = h->feN;
     c.phi = b.nlflux.on ? b.nlflux.stream : nullptr; c.A = b.nldiff.on ? h->nd_A : nullptr;
-    c.mask = h->cl_mask; c.part = h->cl_part;
-    HIPCHK(vn_coefgrad_rows_launch(c, &h->cl_blocks, h->stream));
+    c.mask = h->lv[LV_COEF].mask; c.part = h->lv[LV_COEF].part;
+    HIPCHK(vn_coefgrad_rows_launch(c, &h->lv[LV_COEF].blocks, h->stream));
   }
   if (b.nlflux.on) HIPCHK(vn_nlflux_seed_launch(term_row_args(h, b, b.nlflux), h->stream));
   if (b.nldiff.on) HIPCHK(vn_nldiff_seed_launch(term_row_args(h, b, b.nldiff), h->stream));
@@ -620,8 +667,8 @@ int terms_seed_rows(vn_engine* h, const Batch& b) {
     HIPCHK(point_pass(h, b.Input, nT, nullptr, nullptr, h->fl_pack));
     VnFldGradArgs g{};
     g.udbar = h->udbar; g.pack = h->fl_pack; g.G = b.fb_G; g.J = b.fb_J; g.dim = h->cfg.dim;
-    g.nT = nT; g.q = h->cfg.integ_num; g.mask = h->fl_mask; g.part = h->fl_part;
-    HIPCHK(vn_fldgrad_rows_launch(g, &h->fl_blocks, h->stream));
+    g.nT = nT; g.q = h->cfg.integ_num; g.mask = h->lv[LV_FLD].mask; g.part = h->lv[LV_FLD].part;
+    HIPCHK(vn_fldgrad_rows_launch(g, &h->lv[LV_FLD].blocks, h->stream));
   }
   return VN_OK;
 }
@@ -663,7 +710,7 @@ int terms_source_dedup(vn_engine* h, const Batch& b, VnDedupArgs& d) {
 // After vn_dedup_gather_launch: each term's value seed, added to the gathered one; D(u) last (D'(u) grad u . seed_g needs the
 // unscaled seed_g)
 int terms_gather_dedup(vn_engine* h, const Batch& b, const VnDedupArgs& d) {
-  if (h->cl_on && has_terms(b)) {                  // inverse mode: each kernel also stores its per-point sum for vn_coefgrad_points_kernel
+  if (h->lv[LV_COEF].on && has_terms(b)) {   // inverse mode: each kernel also stores its per-point sum for vn_coefgrad_points_kernel
     if (int rc = ensure(&h->cl_acc, &h->cl_acc_cap, 3 * b.U)) return rc;
     VnTermDedupArgs r = term_dedup_args(h, b, b.react, d), f = term_dedup_args(h, b, b.nlflux, d), n = nldiff_dedup_args(h, b, d);
     r.acc_out = h->cl_acc; f.acc_out = h->cl_acc + b.U; n.acc_out = h->cl_acc + 2 * b.U;
@@ -671,9 +718,9 @@ int terms_gather_dedup(vn_engine* h, const Batch& b, const VnDedupArgs& d) {
     if (b.nlflux.on) HIPCHK(vn_nlflux_gather_launch(f, h->stream));
     if (b.nldiff.on) HIPCHK(vn_nldiff_point_launch(n, h->stream));
     VnCoefPointsArgs c{};
-    c.upack = h->dd_uv; c.U = b.U; c.mask = h->cl_mask; c.part = h->cl_part;
+    c.upack = h->dd_uv; c.U = b.U; c.mask = h->lv[LV_COEF].mask; c.part = h->lv[LV_COEF].part;
     c.accR = b.react.on ? r.acc_out : nullptr; c.accF = b.nlflux.on ? f.acc_out : nullptr; c.gs = b.nldiff.on ? n.acc_out : nullptr;
-    HIPCHK(vn_coefgrad_points_launch(c, &h->cl_blocks, h->stream));
+    HIPCHK(vn_coefgrad_points_launch(c, &h->lv[LV_COEF].blocks, h->stream));
     return VN_OK;
   }
   if (b.react.on) HIPCHK(vn_react_gather_launch(term_dedup_args(h, b, b.react, d), h->stream));
@@ -1014,16 +1061,16 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
   if (src_learnt(h, b)) {                          // source identification: a row's seed is stf[k] x its quadrature weight
     VnSrcGradArgs g{};
     g.stf = a.stf; g.feW = fe_w(h); g.feN = h->feN; g.phi = b.sb_phi; g.J = b.sb_J;
-    g.nT = b.n_k * h->cfg.integ_num; g.q = h->cfg.integ_num; g.mask = h->sl_mask; g.part = h->sl_part;
-    HIPCHK(vn_srcgrad_rows_launch(g, &h->sl_blocks, h->stream));
+    g.nT = b.n_k * h->cfg.integ_num; g.q = h->cfg.integ_num; g.mask = h->lv[LV_SRC].mask; g.part = h->lv[LV_SRC].part;
+    HIPCHK(vn_srcgrad_rows_launch(g, &h->lv[LV_SRC].blocks, h->stream));
   }
   if (fld_learnt(h, b)) {                          // field identification: ... times D(u_j), with grad u of the row's point
     VnFldGradArgs g{};
     g.stf = a.stf; g.feW = fe_w(h); g.pack = h->dd_uv; g.uid = b.uid; g.G = b.fb_G; g.J = b.fb_J; g.dim = h->cfg.dim;
     g.nldiff = b.nldiff.on ? 1 : 0; g.cp = b.nldiff.on ? term_cp(h, b, b.nldiff) : nullptr;
     for (int i = 0; i < 3; ++i) g.c[i] = (float)b.nldiff.c[i];
-    g.nT = b.n_k * h->cfg.integ_num; g.q = h->cfg.integ_num; g.mask = h->fl_mask; g.part = h->fl_part;
-    HIPCHK(vn_fldgrad_rows_launch(g, &h->fl_blocks, h->stream));
+    g.nT = b.n_k * h->cfg.integ_num; g.q = h->cfg.integ_num; g.mask = h->lv[LV_FLD].mask; g.part = h->lv[LV_FLD].part;
+    HIPCHK(vn_fldgrad_rows_launch(g, &h->lv[LV_FLD].blocks, h->stream));
   }
   VnFusedArgs f = fused_args(h, &b);
   f.X = b.Xu; f.G = h->dd_sg; f.nT = b.U;
@@ -1036,41 +1083,55 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
   return VN_OK;
 }
 
-// Inverse mode, after the last kernel of a gradient evaluation that reads the coefficients: the partials folded into cl_grad
-// (zeros when the batch carries no term), and with `update` the Adam step of the masked entries at step counter t
-int coef_finish(vn_engine* h, bool fold, bool update, double t) {
-  VnCoefApplyArgs a{};
-  if (fold) {
-    if (h->cl_blocks <= 0) {
-      HIPCHK(hipMemsetAsync(h->cl_part, 0, VN_COEF_N * sizeof(float), h->stream));
-      h->cl_blocks = 1;
-    }
-    a.part = h->cl_part; a.blocks = h->cl_blocks;
+// After the last kernel of a gradient evaluation that reads vector `id` (or what was mixed from it): with `fold` the partials are
+// folded into its gradient (zeros when the batch wrote none: one zeroed partial row stands in), and with `update` the masked
+// entries take their Adam step at step counter t and are clamped
+int learnt_finish(vn_engine* h, int id, bool fold, bool update, double t) {
+  const LearntKind& k = kLearnt[id];
+  Learnt& v = h->lv[id];
+  if (fold && v.blocks <= 0) {
+    HIPCHK(hipMemsetAsync(v.part, 0, (size_t)v.J * sizeof(float), h->stream));
+    v.blocks = 1;
   }
-  a.grad = h->cl_grad; a.coef = h->cl_state; a.m = h->cl_state + VN_COEF_N; a.v = h->cl_state + 2 * VN_COEF_N;
-  a.mask = h->cl_mask;
-  for (int i = 0; i < VN_COEF_N; ++i) { a.lo[i] = (float)h->cl_lo[i]; a.hi[i] = (float)h->cl_hi[i]; }
-  a.update = update ? 1 : 0;
-  if (update) {
-    a.lr_t = (float)(h->cl_lr * std::sqrt(1.0 - std::pow(h->cfg.beta2, t)) / (1.0 - std::pow(h->cfg.beta1, t)));
-    a.b1 = (float)h->cfg.beta1; a.b2 = (float)h->cfg.beta2; a.eps = (float)h->cfg.eps;
-  }
-  HIPCHK(vn_coef_apply_launch(a, h->stream));
+  HIPCHK(k.apply(v, k.cap, fold, update, t, h->cfg, h->stream));
   return VN_OK;
 }
 
-void coef_free(vn_engine* h) {
-  for (void* p : {(void*)h->cl_state, (void*)h->cl_grad, (void*)h->cl_part, (void*)h->cl_acc})
+// (the feature's own work buffers go with its vector)
+void learnt_free(vn_engine* h, int id) {
+  Learnt& v = h->lv[id];
+  for (void* p : {(void*)v.state, (void*)v.bounds, (void*)v.grad, (void*)v.part})
     if (p) (void)hipFree(p);
-  h->cl_state = nullptr; h->cl_grad = nullptr; h->cl_part = nullptr; h->cl_acc = nullptr; h->cl_acc_cap = 0;
-  h->cl_on = false; h->cl_mask = 0; h->cl_blocks = 0;
+  auto drop = [](float*& p, long& cap) { if (p) (void)hipFree(p); p = nullptr; cap = 0; };
+  if (id == LV_COEF) drop(h->cl_acc, h->cl_acc_cap);
+  if (id == LV_SRC) drop(h->sl_mix, h->sl_mix_cap);
+  if (id == LV_FLD) { drop(h->fl_mix, h->fl_mix_cap); drop(h->fl_csr, h->fl_csr_cap); drop(h->fl_pack, h->fl_pack_cap); }
+  v = Learnt{};
+}
+
+// vn_state_snapshot (`back`: vn_state_rollback): (value | m | v) of every learnt vector to (from) the copy behind them
+int learnt_copy(vn_engine* h, bool back) {
+  for (int id = 0; id < LV_N; ++id) {
+    const Learnt& v = h->lv[id];
+    if (!v.on) continue;
+    const size_t n = 3 * (size_t)kLearnt[id].cap;
+    HIPCHK(hipMemcpyAsync(v.state + (back ? 0 : n), v.state + (back ? n : 0), n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  }
+  return VN_OK;
+}
+
+// the first vector that is learnt, in LearntId order (the one whose refusal of weighted batches is reported), or nullptr
+const LearntKind* learnt_any(const vn_engine* h) {
+  for (int id = 0; id < LV_N; ++id)
+    if (h->lv[id].on) return &kLearnt[id];
+  return nullptr;
 }
 
 // Source identification, first thing in an evaluation of batch b: the batch's basis must be the engine's, then s_mix is formed
 int source_mix(vn_engine* h, const Batch& b, int batch) {
   if (!src_learnt(h, b)) return VN_OK;
-  if (b.sb_J != h->sl_J)
-    return fail(VN_EINVAL, "batch %d has a source basis of %d streams, the learnt amplitudes (vn_set_source_learn) are %d", batch, b.sb_J, h->sl_J);
+  if (b.sb_J != h->lv[LV_SRC].J)
+    return fail(VN_EINVAL, "batch %d has a source basis of %d streams, the learnt amplitudes (vn_set_source_learn) are %d", batch, b.sb_J, h->lv[LV_SRC].J);
   if (h->route == Route::fused4 && !b.Xu)
     return fail(VN_EUNSUPPORTED, "learnt source amplitudes are not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its "
                                  "single launch leaves no row seeds to reduce; every other kernel family carries them");
@@ -1078,40 +1139,9 @@ int source_mix(vn_engine* h, const Batch& b, int batch) {
   if (nT <= 0) return VN_OK;
   if (int rc = ensure(&h->sl_mix, &h->sl_mix_cap, nT)) return rc;
   VnSrcMixArgs a{};
-  a.s0 = b.source; a.phi = b.sb_phi; a.amp = h->sl_state; a.J = b.sb_J; a.nT = nT; a.out = h->sl_mix;
+  a.s0 = b.source; a.phi = b.sb_phi; a.amp = h->lv[LV_SRC].state; a.J = b.sb_J; a.nT = nT; a.out = h->sl_mix;
   HIPCHK(vn_source_mix_launch(a, h->stream));
   return VN_OK;
-}
-
-// After the last kernel of a gradient evaluation that reads s_mix: the partials folded into sl_grad (zeros when the batch has no
-// basis), and with `update` the Adam step of the masked amplitudes at step counter t -- coef_finish's sibling
-int source_finish(vn_engine* h, bool fold, bool update, double t) {
-  VnSrcApplyArgs a{};
-  a.J = h->sl_J;
-  if (fold) {
-    if (h->sl_blocks <= 0) {
-      HIPCHK(hipMemsetAsync(h->sl_part, 0, (size_t)h->sl_J * sizeof(float), h->stream));
-      h->sl_blocks = 1;
-    }
-    a.part = h->sl_part; a.blocks = h->sl_blocks;
-  }
-  a.grad = h->sl_grad; a.amp = h->sl_state; a.m = h->sl_state + VN_SRC_JMAX; a.v = h->sl_state + 2 * VN_SRC_JMAX;
-  a.lo = h->sl_bounds; a.hi = h->sl_bounds + VN_SRC_JMAX;
-  a.mask = h->sl_mask;
-  a.update = update ? 1 : 0;
-  if (update) {
-    a.lr_t = (float)(h->sl_lr * std::sqrt(1.0 - std::pow(h->cfg.beta2, t)) / (1.0 - std::pow(h->cfg.beta1, t)));
-    a.b1 = (float)h->cfg.beta1; a.b2 = (float)h->cfg.beta2; a.eps = (float)h->cfg.eps;
-  }
-  HIPCHK(vn_source_apply_launch(a, h->stream));
-  return VN_OK;
-}
-
-void source_free(vn_engine* h) {
-  for (void* p : {(void*)h->sl_state, (void*)h->sl_bounds, (void*)h->sl_grad, (void*)h->sl_part, (void*)h->sl_mix})
-    if (p) (void)hipFree(p);
-  h->sl_state = nullptr; h->sl_bounds = nullptr; h->sl_grad = nullptr; h->sl_part = nullptr; h->sl_mix = nullptr; h->sl_mix_cap = 0;
-  h->sl_on = false; h->sl_J = 0; h->sl_mask = 0; h->sl_blocks = 0;
 }
 
 // Field identification, first thing in an evaluation of batch b (the routes without a point pass for the rows' grad u were refused by
@@ -1119,13 +1149,13 @@ void source_free(vn_engine* h) {
 // vn_source_mix_kernel's arithmetic over the nT * dim entries of a stream -- and, on a de-duplication map, its CSR-ordered copy
 int field_mix(vn_engine* h, const Batch& b, int batch) {
   if (!fld_learnt(h, b)) return VN_OK;
-  if (b.fb_J != h->fl_J)
-    return fail(VN_EINVAL, "batch %d has a field basis of %d streams, the learnt amplitudes (vn_set_field_learn) are %d", batch, b.fb_J, h->fl_J);
+  if (b.fb_J != h->lv[LV_FLD].J)
+    return fail(VN_EINVAL, "batch %d has a field basis of %d streams, the learnt amplitudes (vn_set_field_learn) are %d", batch, b.fb_J, h->lv[LV_FLD].J);
   const long n = b.n_k * h->cfg.integ_num * h->cfg.dim;
   if (n <= 0) return VN_OK;
   if (int rc = ensure(&h->fl_mix, &h->fl_mix_cap, n)) return rc;
   VnSrcMixArgs a{};
-  a.s0 = b.gcoef; a.phi = b.fb_G; a.amp = h->fl_state; a.J = b.fb_J; a.nT = n; a.out = h->fl_mix;
+  a.s0 = b.gcoef; a.phi = b.fb_G; a.amp = h->lv[LV_FLD].state; a.J = b.fb_J; a.nT = n; a.out = h->fl_mix;
   HIPCHK(vn_source_mix_launch(a, h->stream));
   if (b.Xu) {
     if (int rc = ensure(&h->fl_csr, &h->fl_csr_cap, n)) return rc;
@@ -1133,47 +1163,6 @@ int field_mix(vn_engine* h, const Batch& b, int batch) {
   }
   return VN_OK;
 }
-
-// source_finish's sibling, through vn_source_apply_kernel (nothing in it is the source's): fold, Adam step at counter t, clamp
-int field_finish(vn_engine* h, bool fold, bool update, double t) {
-  VnSrcApplyArgs a{};
-  a.J = h->fl_J;
-  if (fold) {
-    if (h->fl_blocks <= 0) {
-      HIPCHK(hipMemsetAsync(h->fl_part, 0, (size_t)h->fl_J * sizeof(float), h->stream));
-      h->fl_blocks = 1;
-    }
-    a.part = h->fl_part; a.blocks = h->fl_blocks;
-  }
-  a.grad = h->fl_grad; a.amp = h->fl_state; a.m = h->fl_state + VN_FLD_JMAX; a.v = h->fl_state + 2 * VN_FLD_JMAX;
-  a.lo = h->fl_bounds; a.hi = h->fl_bounds + VN_FLD_JMAX;
-  a.mask = h->fl_mask;
-  a.update = update ? 1 : 0;
-  if (update) {
-    a.lr_t = (float)(h->fl_lr * std::sqrt(1.0 - std::pow(h->cfg.beta2, t)) / (1.0 - std::pow(h->cfg.beta1, t)));
-    a.b1 = (float)h->cfg.beta1; a.b2 = (float)h->cfg.beta2; a.eps = (float)h->cfg.eps;
-  }
-  HIPCHK(vn_source_apply_launch(a, h->stream));
-  return VN_OK;
-}
-
-void field_free(vn_engine* h) {
-  for (void* p : {(void*)h->fl_state, (void*)h->fl_bounds, (void*)h->fl_grad, (void*)h->fl_part, (void*)h->fl_mix, (void*)h->fl_csr,
-                  (void*)h->fl_pack})
-    if (p) (void)hipFree(p);
-  h->fl_state = nullptr; h->fl_bounds = nullptr; h->fl_grad = nullptr; h->fl_part = nullptr;
-  h->fl_mix = nullptr; h->fl_mix_cap = 0; h->fl_csr = nullptr; h->fl_csr_cap = 0; h->fl_pack = nullptr; h->fl_pack_cap = 0;
-  h->fl_on = false; h->fl_J = 0; h->fl_mask = 0; h->fl_blocks = 0;
-}
-
-constexpr const char* kFldWeights = "learnt field amplitudes (vn_set_field_learn) next to per-test-function loss weights (vn_set_tf_weights / "
-                                    "vn_set_causal, batch %d): the weights are applied after the seeds the amplitude reduction reads";
-
-constexpr const char* kSrcWeights = "learnt source amplitudes (vn_set_source_learn) next to per-test-function loss weights (vn_set_tf_weights / "
-                                    "vn_set_causal, batch %d): the weights are applied after the seeds the amplitude reduction reads";
-
-constexpr const char* kCoefWeights = "learnt coefficients (vn_set_coef_learn) next to per-test-function loss weights (vn_set_tf_weights / "
-                                     "vn_set_causal, batch %d): the weights are applied after the seeds the coefficient reduction reads";
 
 // ---- RCCL, loaded at run time -------------------------------------------------------------
 // librccl.so.1 is resolved by SONAME, so a process that already carries RCCL (PyTorch-ROCm does) shares that
@@ -1336,9 +1325,7 @@ int vn_destroy(vn_engine* h) {
     if (p) (void)hipFree(p);
   if (h->lb.out) (void)hipHostFree(h->lb.out);
   vn_obj64_free(h->o64);
-  coef_free(h);
-  source_free(h);
-  field_free(h);
+  for (int id = 0; id < LV_N; ++id) learnt_free(h, id);
   for (Batch& b : h->batches) {
     if (b.gcsr) (void)hipFree(b.gcsr);
     clear_weights(b);
@@ -1448,12 +1435,7 @@ int vn_state_snapshot(vn_engine* h) {
   HIPCHK(hipMemcpyAsync(h->snap, h->theta, nb, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->snap + h->net.P, h->m, nb, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->snap + 2 * (size_t)h->net.P, h->v, nb, hipMemcpyDeviceToDevice, h->stream));
-  if (h->cl_on)
-    HIPCHK(hipMemcpyAsync(h->cl_state + 3 * VN_COEF_N, h->cl_state, 3 * VN_COEF_N * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  if (h->sl_on)
-    HIPCHK(hipMemcpyAsync(h->sl_state + 3 * VN_SRC_JMAX, h->sl_state, 3 * VN_SRC_JMAX * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  if (h->fl_on)
-    HIPCHK(hipMemcpyAsync(h->fl_state + 3 * VN_FLD_JMAX, h->fl_state, 3 * VN_FLD_JMAX * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  if (int rc = learnt_copy(h, false)) return rc;
   h->snap_step = h->step;
   return VN_OK;
 }
@@ -1467,12 +1449,7 @@ int vn_state_rollback(vn_engine* h) {
   HIPCHK(hipMemcpyAsync(h->theta, h->snap, nb, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->m, h->snap + h->net.P, nb, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->v, h->snap + 2 * (size_t)h->net.P, nb, hipMemcpyDeviceToDevice, h->stream));
-  if (h->cl_on)
-    HIPCHK(hipMemcpyAsync(h->cl_state, h->cl_state + 3 * VN_COEF_N, 3 * VN_COEF_N * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  if (h->sl_on)
-    HIPCHK(hipMemcpyAsync(h->sl_state, h->sl_state + 3 * VN_SRC_JMAX, 3 * VN_SRC_JMAX * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  if (h->fl_on)
-    HIPCHK(hipMemcpyAsync(h->fl_state, h->fl_state + 3 * VN_FLD_JMAX, 3 * VN_FLD_JMAX * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  if (int rc = learnt_copy(h, true)) return rc;
   h->step = h->snap_step;
   return VN_OK;
 }
@@ -1619,7 +1596,7 @@ static int set_term(vn_engine* h, int32_t batch, const TermKind& k, const float*
   lbfgs_invalidate(h, batch);
   const Term off = Batch().*(k.slot);
   // (a term with a learnt entry stays registered whatever `coef` says: its coefficients are the engine's, vn_set_coef_learn)
-  const bool learnt = h->cl_on && (h->cl_mask >> (3 * (&k == &kReact ? 0 : &k == &kNlflux ? 1 : 2)) & 7u);
+  const bool learnt = h->lv[LV_COEF].on && (h->lv[LV_COEF].mask >> (3 * (&k == &kReact ? 0 : &k == &kNlflux ? 1 : 2)) & 7u);
   if (!coef || (!learnt && std::equal(coef, coef + 3, off.c) && !(&k == &kNldiff && stream))) {
     b.*(k.slot) = off;
     return VN_OK;
@@ -1647,8 +1624,12 @@ int vn_set_reaction(vn_engine* h, int32_t batch, const float* rate, const double
 int vn_set_nlflux(vn_engine* h, int32_t batch, const float* phi, const double coef[3]) { return set_term(h, batch, kNlflux, phi, coef); }
 int vn_set_nldiff(vn_engine* h, int32_t batch, const float* psi, const double coef[3]) { return set_term(h, batch, kNldiff, psi, coef); }
 
-// ---- inverse mode: the nine coefficients on the device, learnt next to the parameters (vn_coef.hip) ----
-int vn_set_coef_learn(vn_engine* h, const int32_t mask[9], const double init[9], const double lo[9], const double hi[9], double lr) {
+// ---- learnt vectors: what vn_set_*_learn, vn_get_* and vn_set_* of the three share ----
+// vn_set_*_learn: mask == NULL switches the vector off and frees it; `extra` holds the refusals that are the feature's own.
+// Every call, also a failing one, invalidates the snapshot and the L-BFGS state.
+static int learnt_set_learn(vn_engine* h, int id, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi,
+                            double lr, int (*extra)(vn_engine*) = nullptr) {
+  const LearntKind& k = kLearnt[id];
   if (!h) return fail(VN_EINVAL, "null handle");
   (void)hipGetLastError();
   HIPCHK(hipSetDevice(h->cfg.device));
@@ -1656,73 +1637,96 @@ int vn_set_coef_learn(vn_engine* h, const int32_t mask[9], const double init[9],
   lbfgs_invalidate(h);
   if (!mask) {
     HIPCHK(hipStreamSynchronize(h->stream));
-    coef_free(h);
+    learnt_free(h, id);
     return VN_OK;
   }
   if (!init || !lo || !hi) return fail(VN_EINVAL, "null argument");
+  if (J < 1 || J > k.cap) return fail(VN_EINVAL, "1 to %d %s can be learnt, got %d", k.cap, k.what, J);
   if (h->cfg.optimizer != VN_OPT_ADAM)
-    return fail(VN_EUNSUPPORTED, "vn_set_coef_learn on %s engine: the coefficients are updated with the arithmetic of the Adam step only%s",
-                is_lbfgs(h) ? "an L-BFGS" : "an RMSProp", is_lbfgs(h) ? " (vn_lbfgs_step searches over the parameters alone)" : "");
+    return fail(VN_EUNSUPPORTED, "%s on %s engine: the %ss are updated with the arithmetic of the Adam step only%s", k.setter,
+                is_lbfgs(h) ? "an L-BFGS" : "an RMSProp", k.noun, is_lbfgs(h) ? " (vn_lbfgs_step searches over the parameters alone)" : "");
   if (h->comm)
-    return fail(VN_EUNSUPPORTED, "vn_set_coef_learn under a communicator: the nine coefficient gradients are not in the all-reduced "
-                                 "buffer, so every rank would follow its own shard's");
+    return fail(VN_EUNSUPPORTED, "%s under a communicator: %s are not in the all-reduced buffer, so every rank would follow its own "
+                                 "shard's", k.setter, k.grads);
+  if (extra)
+    if (int rc = extra(h)) return rc;
   for (size_t i = 0; i < h->batches.size(); ++i)
-    if (has_weights(h->batches[i])) return fail(VN_EUNSUPPORTED, kCoefWeights, (int)i);
-  if (!(std::isfinite(lr) && lr > 0.0)) return fail(VN_EINVAL, "coefficient learning rate %g must be finite and > 0", lr);
-  for (int i = 0; i < VN_COEF_N; ++i) {
-    if (!std::isfinite(init[i])) return fail(VN_EINVAL, "initial coefficient %d = %g must be finite", i, init[i]);
+    if (has_weights(h->batches[i])) return learnt_weights_refusal(k, (int)i);
+  if (!(std::isfinite(lr) && lr > 0.0)) return fail(VN_EINVAL, "%s learning rate %g must be finite and > 0", k.noun, lr);
+  for (int i = 0; i < J; ++i) {
+    if (!std::isfinite(init[i])) return fail(VN_EINVAL, "initial %s %d = %g must be finite", k.noun, i, init[i]);
     if (std::isnan(lo[i]) || std::isnan(hi[i]) || lo[i] > hi[i])
-      return fail(VN_EINVAL, "bounds of coefficient %d: [%g, %g] is no interval", i, lo[i], hi[i]);
+      return fail(VN_EINVAL, "bounds of %s %d: [%g, %g] is no interval", k.noun, i, lo[i], hi[i]);
   }
-  if (!h->cl_state) {
-    hipError_t e = hipMalloc((void**)&h->cl_state, 6 * VN_COEF_N * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->cl_grad, VN_COEF_N * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->cl_part, (size_t)VN_COEF_MAXBLK * VN_COEF_N * sizeof(float));
-    if (e != hipSuccess) { (void)hipGetLastError(); coef_free(h); return fail(VN_ENOMEM, "vn_set_coef_learn: %s", hipGetErrorString(e)); }
+  Learnt& v = h->lv[id];
+  if (!v.state) {
+    hipError_t e = hipMalloc((void**)&v.state, 6 * (size_t)k.cap * sizeof(float));
+    if (e == hipSuccess && k.dev_bounds) e = hipMalloc((void**)&v.bounds, 2 * (size_t)k.cap * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&v.grad, (size_t)k.cap * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&v.part, (size_t)k.maxblk * k.cap * sizeof(float));
+    if (e != hipSuccess) { (void)hipGetLastError(); learnt_free(h, id); return fail(VN_ENOMEM, "%s: %s", k.setter, hipGetErrorString(e)); }
   }
-  float st[6 * VN_COEF_N] = {};
-  h->cl_mask = 0;
-  for (int i = 0; i < VN_COEF_N; ++i) {
+  float st[6 * LV_CAP] = {}, bd[2 * LV_CAP] = {};    // (m, v and the snapshot copy start at zero)
+  v.mask = 0;
+  for (int i = 0; i < J; ++i) {
     st[i] = (float)init[i];
-    h->cl_lo[i] = lo[i]; h->cl_hi[i] = hi[i];
-    if (mask[i]) h->cl_mask |= 1u << i;
+    bd[i] = (float)lo[i]; bd[k.cap + i] = (float)hi[i];
+    if (mask[i]) v.mask |= 1ull << i;
   }
-  h->cl_lr = lr;
-  HIPCHK(hipMemcpyAsync(h->cl_state, st, sizeof st, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemsetAsync(h->cl_grad, 0, VN_COEF_N * sizeof(double), h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));      // (st leaves scope)
-  h->cl_on = true;
-  h->cl_blocks = 0;
+  v.lr = lr;
+  v.J = J;
+  HIPCHK(hipMemcpyAsync(v.state, st, 6 * (size_t)k.cap * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (k.dev_bounds) HIPCHK(hipMemcpyAsync(v.bounds, bd, 2 * (size_t)k.cap * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  else std::copy(bd, bd + 2 * k.cap, v.hbounds);
+  HIPCHK(hipMemsetAsync(v.grad, 0, (size_t)k.cap * sizeof(double), h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));      // (st, bd leave scope)
+  v.on = true;
+  v.blocks = 0;
   return VN_OK;
 }
 
-int vn_get_coefs(vn_engine* h, double coef[9], double grad[9]) {
-  if (!h || !coef) return fail(VN_EINVAL, "null argument");
-  if (!h->cl_on) return fail(VN_ESTATE, "no learnt coefficients (call vn_set_coef_learn first)");
+// vn_get_*: the values at the current state, widened, and with `grad` the gradient of the last gradient evaluation
+static int learnt_get(vn_engine* h, int id, double* val, double* grad, int32_t J) {
+  const LearntKind& k = kLearnt[id];
+  if (!h || !val) return fail(VN_EINVAL, "null argument");
+  const Learnt& v = h->lv[id];
+  if (!v.on) return fail(VN_ESTATE, "no learnt %s (call %s first)", k.what, k.setter);
+  if (J != v.J) return fail(VN_EINVAL, "the engine holds %d %s, the caller asks for %d", v.J, k.what, J);
   HIPCHK(hipSetDevice(h->cfg.device));
-  float c[VN_COEF_N];
-  HIPCHK(hipMemcpyAsync(c, h->cl_state, sizeof c, hipMemcpyDeviceToHost, h->stream));
-  if (grad) HIPCHK(hipMemcpyAsync(grad, h->cl_grad, VN_COEF_N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  float c[LV_CAP];
+  HIPCHK(hipMemcpyAsync(c, v.state, (size_t)J * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (grad) HIPCHK(hipMemcpyAsync(grad, v.grad, (size_t)J * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  for (int i = 0; i < VN_COEF_N; ++i) coef[i] = (double)c[i];
+  for (int i = 0; i < J; ++i) val[i] = (double)c[i];
   return VN_OK;
 }
 
-int vn_set_coefs(vn_engine* h, const double coef[9]) {
-  if (!h || !coef) return fail(VN_EINVAL, "null argument");
-  if (!h->cl_on) return fail(VN_ESTATE, "no learnt coefficients (call vn_set_coef_learn first)");
-  float c[VN_COEF_N];
-  for (int i = 0; i < VN_COEF_N; ++i) {
-    if (!std::isfinite(coef[i])) return fail(VN_EINVAL, "coefficient %d = %g must be finite", i, coef[i]);
-    c[i] = (float)coef[i];
+// vn_set_*: the values overwritten (rounded to fp32, not clamped; the Adam slots stay); the snapshot and the L-BFGS state go
+static int learnt_put(vn_engine* h, int id, const double* val, int32_t J) {
+  const LearntKind& k = kLearnt[id];
+  if (!h || !val) return fail(VN_EINVAL, "null argument");
+  const Learnt& v = h->lv[id];
+  if (!v.on) return fail(VN_ESTATE, "no learnt %s (call %s first)", k.what, k.setter);
+  if (J != v.J) return fail(VN_EINVAL, "the engine holds %d %s, the caller passes %d", v.J, k.what, J);
+  float c[LV_CAP];
+  for (int i = 0; i < J; ++i) {
+    if (!std::isfinite(val[i])) return fail(VN_EINVAL, "%s %d = %g must be finite", k.noun, i, val[i]);
+    c[i] = (float)val[i];
   }
   HIPCHK(hipSetDevice(h->cfg.device));
-  HIPCHK(hipMemcpyAsync(h->cl_state, c, sizeof c, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(v.state, c, (size_t)J * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->snap_step = -1;
   lbfgs_invalidate(h);
   return VN_OK;
 }
+
+// ---- inverse mode: the nine coefficients on the device, learnt next to the parameters (vn_coef.hip) ----
+int vn_set_coef_learn(vn_engine* h, const int32_t mask[9], const double init[9], const double lo[9], const double hi[9], double lr) {
+  return learnt_set_learn(h, LV_COEF, VN_COEF_N, mask, init, lo, hi, lr);
+}
+int vn_get_coefs(vn_engine* h, double coef[9], double grad[9]) { return learnt_get(h, LV_COEF, coef, grad, VN_COEF_N); }
+int vn_set_coefs(vn_engine* h, const double coef[9]) { return learnt_put(h, LV_COEF, coef, VN_COEF_N); }
 
 // ---- source identification: basis streams per batch, amplitudes on the device, learnt next to the parameters (vn_source.hip) ----
 int vn_set_source_basis(vn_engine* h, int32_t batch, const float* phi_dev, int32_t J) {
@@ -1743,86 +1747,10 @@ int vn_set_source_basis(vn_engine* h, int32_t batch, const float* phi_dev, int32
 }
 
 int vn_set_source_learn(vn_engine* h, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi, double lr) {
-  if (!h) return fail(VN_EINVAL, "null handle");
-  (void)hipGetLastError();
-  HIPCHK(hipSetDevice(h->cfg.device));
-  h->snap_step = -1;
-  lbfgs_invalidate(h);
-  if (!mask) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    source_free(h);
-    return VN_OK;
-  }
-  if (!init || !lo || !hi) return fail(VN_EINVAL, "null argument");
-  if (J < 1 || J > VN_SRC_MAX) return fail(VN_EINVAL, "1 to %d source amplitudes can be learnt, got %d", VN_SRC_MAX, J);
-  if (h->cfg.optimizer != VN_OPT_ADAM)
-    return fail(VN_EUNSUPPORTED, "vn_set_source_learn on %s engine: the amplitudes are updated with the arithmetic of the Adam step only%s",
-                is_lbfgs(h) ? "an L-BFGS" : "an RMSProp", is_lbfgs(h) ? " (vn_lbfgs_step searches over the parameters alone)" : "");
-  if (h->comm)
-    return fail(VN_EUNSUPPORTED, "vn_set_source_learn under a communicator: the amplitude gradients are not in the all-reduced "
-                                 "buffer, so every rank would follow its own shard's");
-  for (size_t i = 0; i < h->batches.size(); ++i)
-    if (has_weights(h->batches[i])) return fail(VN_EUNSUPPORTED, kSrcWeights, (int)i);
-  if (!(std::isfinite(lr) && lr > 0.0)) return fail(VN_EINVAL, "amplitude learning rate %g must be finite and > 0", lr);
-  for (int i = 0; i < J; ++i) {
-    if (!std::isfinite(init[i])) return fail(VN_EINVAL, "initial amplitude %d = %g must be finite", i, init[i]);
-    if (std::isnan(lo[i]) || std::isnan(hi[i]) || lo[i] > hi[i])
-      return fail(VN_EINVAL, "bounds of amplitude %d: [%g, %g] is no interval", i, lo[i], hi[i]);
-  }
-  if (!h->sl_state) {
-    hipError_t e = hipMalloc((void**)&h->sl_state, 6 * VN_SRC_JMAX * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->sl_bounds, 2 * VN_SRC_JMAX * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->sl_grad, VN_SRC_JMAX * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->sl_part, (size_t)VN_SRC_MAXBLK * VN_SRC_JMAX * sizeof(float));
-    if (e != hipSuccess) { (void)hipGetLastError(); source_free(h); return fail(VN_ENOMEM, "vn_set_source_learn: %s", hipGetErrorString(e)); }
-  }
-  float st[6 * VN_SRC_JMAX] = {}, bd[2 * VN_SRC_JMAX] = {};
-  h->sl_mask = 0;
-  for (int i = 0; i < J; ++i) {
-    st[i] = (float)init[i];
-    bd[i] = (float)lo[i]; bd[VN_SRC_JMAX + i] = (float)hi[i];
-    if (mask[i]) h->sl_mask |= 1ull << i;
-  }
-  h->sl_lr = lr;
-  h->sl_J = J;
-  HIPCHK(hipMemcpyAsync(h->sl_state, st, sizeof st, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->sl_bounds, bd, sizeof bd, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemsetAsync(h->sl_grad, 0, VN_SRC_JMAX * sizeof(double), h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));      // (st, bd leave scope)
-  h->sl_on = true;
-  h->sl_blocks = 0;
-  return VN_OK;
+  return learnt_set_learn(h, LV_SRC, J, mask, init, lo, hi, lr);
 }
-
-int vn_get_source_amps(vn_engine* h, double* amp, double* grad, int32_t J) {
-  if (!h || !amp) return fail(VN_EINVAL, "null argument");
-  if (!h->sl_on) return fail(VN_ESTATE, "no learnt source amplitudes (call vn_set_source_learn first)");
-  if (J != h->sl_J) return fail(VN_EINVAL, "the engine holds %d source amplitudes, the caller asks for %d", h->sl_J, J);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  float c[VN_SRC_JMAX];
-  HIPCHK(hipMemcpyAsync(c, h->sl_state, (size_t)J * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (grad) HIPCHK(hipMemcpyAsync(grad, h->sl_grad, (size_t)J * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  for (int i = 0; i < J; ++i) amp[i] = (double)c[i];
-  return VN_OK;
-}
-
-int vn_set_source_amps(vn_engine* h, const double* amp, int32_t J) {
-  if (!h || !amp) return fail(VN_EINVAL, "null argument");
-  if (!h->sl_on) return fail(VN_ESTATE, "no learnt source amplitudes (call vn_set_source_learn first)");
-  if (J != h->sl_J) return fail(VN_EINVAL, "the engine holds %d source amplitudes, the caller passes %d", h->sl_J, J);
-  float c[VN_SRC_JMAX];
-  for (int i = 0; i < J; ++i) {
-    if (!std::isfinite(amp[i])) return fail(VN_EINVAL, "amplitude %d = %g must be finite", i, amp[i]);
-    c[i] = (float)amp[i];
-  }
-  HIPCHK(hipSetDevice(h->cfg.device));
-  HIPCHK(hipMemcpyAsync(h->sl_state, c, (size_t)J * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  h->snap_step = -1;
-  lbfgs_invalidate(h);
-  return VN_OK;
-}
+int vn_get_source_amps(vn_engine* h, double* amp, double* grad, int32_t J) { return learnt_get(h, LV_SRC, amp, grad, J); }
+int vn_set_source_amps(vn_engine* h, const double* amp, int32_t J) { return learnt_put(h, LV_SRC, amp, J); }
 
 // ---- field identification: basis streams of gcoef per batch, amplitudes on the device, learnt next to the parameters (vn_field.hip) ----
 int vn_set_field_basis(vn_engine* h, int32_t batch, const float* G_dev, int32_t J) {
@@ -1839,25 +1767,8 @@ int vn_set_field_basis(vn_engine* h, int32_t batch, const float* G_dev, int32_t 
   return VN_OK;
 }
 
-int vn_set_field_learn(vn_engine* h, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi, double lr) {
-  if (!h) return fail(VN_EINVAL, "null handle");
-  (void)hipGetLastError();
-  HIPCHK(hipSetDevice(h->cfg.device));
-  h->snap_step = -1;
-  lbfgs_invalidate(h);
-  if (!mask) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    field_free(h);
-    return VN_OK;
-  }
-  if (!init || !lo || !hi) return fail(VN_EINVAL, "null argument");
-  if (J < 1 || J > VN_FLD_MAX) return fail(VN_EINVAL, "1 to %d field amplitudes can be learnt, got %d", VN_FLD_MAX, J);
-  if (h->cfg.optimizer != VN_OPT_ADAM)
-    return fail(VN_EUNSUPPORTED, "vn_set_field_learn on %s engine: the amplitudes are updated with the arithmetic of the Adam step only%s",
-                is_lbfgs(h) ? "an L-BFGS" : "an RMSProp", is_lbfgs(h) ? " (vn_lbfgs_step searches over the parameters alone)" : "");
-  if (h->comm)
-    return fail(VN_EUNSUPPORTED, "vn_set_field_learn under a communicator: the amplitude gradients are not in the all-reduced "
-                                 "buffer, so every rank would follow its own shard's");
+// what vn_set_field_learn refuses on its own: the amplitude reduction reads the rows' grad u from an 8-wave point pass
+static int field_learn_checks(vn_engine* h) {
   if (h->cfg.dim > 3)
     return fail(VN_EUNSUPPORTED, "learnt field amplitudes need dim <= 3, got %d: the point pass that gives the rows' grad u carries "
                                  "three gradient components", h->cfg.dim);
@@ -1871,68 +1782,14 @@ int vn_set_field_learn(vn_engine* h, int32_t J, const int32_t* mask, const doubl
     return fail(VN_EUNSUPPORTED, "learnt field amplitudes on the generic kernels need a network of the 8-wave point pass for the rows' "
                                  "grad u; this one (%d layers, widest %d, %d inputs%s) has none", h->net.L, h->net.hmax, h->net.d_in,
                 h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
-  for (size_t i = 0; i < h->batches.size(); ++i)
-    if (has_weights(h->batches[i])) return fail(VN_EUNSUPPORTED, kFldWeights, (int)i);
-  if (!(std::isfinite(lr) && lr > 0.0)) return fail(VN_EINVAL, "amplitude learning rate %g must be finite and > 0", lr);
-  for (int i = 0; i < J; ++i) {
-    if (!std::isfinite(init[i])) return fail(VN_EINVAL, "initial amplitude %d = %g must be finite", i, init[i]);
-    if (std::isnan(lo[i]) || std::isnan(hi[i]) || lo[i] > hi[i])
-      return fail(VN_EINVAL, "bounds of amplitude %d: [%g, %g] is no interval", i, lo[i], hi[i]);
-  }
-  if (!h->fl_state) {
-    hipError_t e = hipMalloc((void**)&h->fl_state, 6 * VN_FLD_JMAX * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->fl_bounds, 2 * VN_FLD_JMAX * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->fl_grad, VN_FLD_JMAX * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->fl_part, (size_t)VN_FLD_MAXBLK * VN_FLD_JMAX * sizeof(float));
-    if (e != hipSuccess) { (void)hipGetLastError(); field_free(h); return fail(VN_ENOMEM, "vn_set_field_learn: %s", hipGetErrorString(e)); }
-  }
-  float st[6 * VN_FLD_JMAX] = {}, bd[2 * VN_FLD_JMAX] = {};
-  h->fl_mask = 0;
-  for (int i = 0; i < J; ++i) {
-    st[i] = (float)init[i];
-    bd[i] = (float)lo[i]; bd[VN_FLD_JMAX + i] = (float)hi[i];
-    if (mask[i]) h->fl_mask |= 1u << i;
-  }
-  h->fl_lr = lr;
-  h->fl_J = J;
-  HIPCHK(hipMemcpyAsync(h->fl_state, st, sizeof st, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->fl_bounds, bd, sizeof bd, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemsetAsync(h->fl_grad, 0, VN_FLD_JMAX * sizeof(double), h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));      // (st, bd leave scope)
-  h->fl_on = true;
-  h->fl_blocks = 0;
   return VN_OK;
 }
 
-int vn_get_field_amps(vn_engine* h, double* amp, double* grad, int32_t J) {
-  if (!h || !amp) return fail(VN_EINVAL, "null argument");
-  if (!h->fl_on) return fail(VN_ESTATE, "no learnt field amplitudes (call vn_set_field_learn first)");
-  if (J != h->fl_J) return fail(VN_EINVAL, "the engine holds %d field amplitudes, the caller asks for %d", h->fl_J, J);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  float c[VN_FLD_JMAX];
-  HIPCHK(hipMemcpyAsync(c, h->fl_state, (size_t)J * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (grad) HIPCHK(hipMemcpyAsync(grad, h->fl_grad, (size_t)J * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  for (int i = 0; i < J; ++i) amp[i] = (double)c[i];
-  return VN_OK;
+int vn_set_field_learn(vn_engine* h, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi, double lr) {
+  return learnt_set_learn(h, LV_FLD, J, mask, init, lo, hi, lr, field_learn_checks);
 }
-
-int vn_set_field_amps(vn_engine* h, const double* amp, int32_t J) {
-  if (!h || !amp) return fail(VN_EINVAL, "null argument");
-  if (!h->fl_on) return fail(VN_ESTATE, "no learnt field amplitudes (call vn_set_field_learn first)");
-  if (J != h->fl_J) return fail(VN_EINVAL, "the engine holds %d field amplitudes, the caller passes %d", h->fl_J, J);
-  float c[VN_FLD_JMAX];
-  for (int i = 0; i < J; ++i) {
-    if (!std::isfinite(amp[i])) return fail(VN_EINVAL, "amplitude %d = %g must be finite", i, amp[i]);
-    c[i] = (float)amp[i];
-  }
-  HIPCHK(hipSetDevice(h->cfg.device));
-  HIPCHK(hipMemcpyAsync(h->fl_state, c, (size_t)J * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  h->snap_step = -1;
-  lbfgs_invalidate(h);
-  return VN_OK;
-}
+int vn_get_field_amps(vn_engine* h, double* amp, double* grad, int32_t J) { return learnt_get(h, LV_FLD, amp, grad, J); }
+int vn_set_field_amps(vn_engine* h, const double* amp, int32_t J) { return learnt_put(h, LV_FLD, amp, J); }
 
 // vn_set_tf_weights / vn_set_causal: what both check before they touch the batch; *clear: the call unregisters
 static int weights_common(vn_engine* h, int32_t batch, bool clear, const char* who) {
@@ -1947,9 +1804,7 @@ static int weights_common(vn_engine* h, int32_t batch, bool clear, const char* w
     return VN_OK;
   }
   if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no test function to weight", batch);
-  if (h->cl_on) return fail(VN_EUNSUPPORTED, kCoefWeights, batch);
-  if (h->sl_on) return fail(VN_EUNSUPPORTED, kSrcWeights, batch);
-  if (h->fl_on) return fail(VN_EUNSUPPORTED, kFldWeights, batch);
+  if (const LearntKind* k = learnt_any(h)) return learnt_weights_refusal(*k, batch);
   if (h->route == Route::fused4)
     return fail(VN_EUNSUPPORTED, "%s is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its single launch has no "
                                  "place for the weights; every other kernel family carries them", who);
@@ -2208,22 +2063,18 @@ int vn_grad(vn_engine* h, int32_t batch) {
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   const Batch& b = h->batches[batch];
-  if (!h->cl_on && !h->sl_on && !h->fl_on) return grad_route(h, b);
-  if (has_weights(b)) return fail(VN_EUNSUPPORTED, h->cl_on ? kCoefWeights : h->sl_on ? kSrcWeights : kFldWeights, batch);
+  const LearntKind* learnt = learnt_any(h);
+  if (!learnt) return grad_route(h, b);
+  if (has_weights(b)) return learnt_weights_refusal(*learnt, batch);
   if (int rc = source_mix(h, b, batch)) return rc;
   if (int rc = field_mix(h, b, batch)) return rc;
-  h->cl_blocks = 0;
-  h->sl_blocks = 0;
-  h->fl_blocks = 0;
+  for (Learnt& v : h->lv) v.blocks = 0;
   if (int rc = grad_route(h, b)) return rc;
-  // inverse mode: after every kernel that reads the coefficients or s_mix (the parameters' update rides in the reduction above);
-  // both vectors step on the same counter
-  if (h->cl_on)
-    if (int rc = coef_finish(h, true, h->fuse.kind == VN_OPT_ADAM, (double)h->step)) return rc;
-  if (h->sl_on)
-    if (int rc = source_finish(h, true, h->fuse.kind == VN_OPT_ADAM, (double)h->step)) return rc;
-  if (h->fl_on)
-    if (int rc = field_finish(h, true, h->fuse.kind == VN_OPT_ADAM, (double)h->step)) return rc;
+  // after every kernel that reads the coefficients, s_mix or the mixed gcoef (the parameters' update rides in the reduction above);
+  // every vector steps on the same counter
+  for (int id = 0; id < LV_N; ++id)
+    if (h->lv[id].on)
+      if (int rc = learnt_finish(h, id, true, h->fuse.kind == VN_OPT_ADAM, (double)h->step)) return rc;
   return VN_OK;
 }
 
@@ -2257,12 +2108,9 @@ static int apply_impl(vn_engine* h, float* loss_acc) {
   const double lr_t = h->cfg.lr * std::sqrt(1.0 - std::pow(h->cfg.beta2, t)) / (1.0 - std::pow(h->cfg.beta1, t));
   HIPCHK(vn_adam_launch(h->theta, h->m, h->v, h->gradbuf, h->net.P, (float)lr_t, (float)h->cfg.beta1,
                         (float)h->cfg.beta2, (float)h->cfg.eps, loss_acc, h->stream));
-  if (h->cl_on)
-    if (int rc = coef_finish(h, false, true, t)) return rc;
-  if (h->sl_on)
-    if (int rc = source_finish(h, false, true, t)) return rc;
-  if (h->fl_on)
-    if (int rc = field_finish(h, false, true, t)) return rc;
+  for (int id = 0; id < LV_N; ++id)
+    if (h->lv[id].on)
+      if (int rc = learnt_finish(h, id, false, true, t)) return rc;
   h->step += 1;
   return VN_OK;
 }
@@ -2497,9 +2345,9 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   p.react = b.react.on ? 1 : 0; p.rate = b.react.stream; std::copy(b.react.c, b.react.c + 3, p.coef);
   p.nlflux = b.nlflux.on ? 1 : 0; p.phi = b.nlflux.stream; std::copy(b.nlflux.c, b.nlflux.c + 3, p.fcoef3);
   p.nldiff = b.nldiff.on ? 1 : 0; p.psi = b.nldiff.stream; std::copy(b.nldiff.c, b.nldiff.c + 3, p.dcoef3);
-  if (h->cl_on) {                            // inverse mode: at the current device coefficients, widened exactly
+  if (h->lv[LV_COEF].on) {   // inverse mode: at the current device coefficients, widened exactly
     float c[VN_COEF_N];
-    HIPCHK(hipMemcpyAsync(c, h->cl_state, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(c, h->lv[LV_COEF].state, sizeof c, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int i = 0; i < 3; ++i) { p.coef[i] = c[i]; p.fcoef3[i] = c[3 + i]; p.dcoef3[i] = c[6 + i]; }
   }
@@ -2630,15 +2478,10 @@ int vn_comm_init(vn_engine* h, int32_t rank, int32_t world, const void* unique_i
     if (h->batches[i].wt.S > 0)
       return fail(VN_EUNSUPPORTED, "vn_comm_init: batch %d has a causal registration (vn_set_causal); a rank's slab means would cover "
                                    "only its shard, so the ranks together would train another objective than one rank", (int)i);
-  if (h->fl_on)
-    return fail(VN_EUNSUPPORTED, "vn_comm_init while field amplitudes are learnt (vn_set_field_learn): the amplitude gradients are "
-                                 "not in the all-reduced buffer, so every rank would follow its own shard's");
-  if (h->sl_on)
-    return fail(VN_EUNSUPPORTED, "vn_comm_init while source amplitudes are learnt (vn_set_source_learn): the amplitude gradients are "
-                                 "not in the all-reduced buffer, so every rank would follow its own shard's");
-  if (h->cl_on)
-    return fail(VN_EUNSUPPORTED, "vn_comm_init while coefficients are learnt (vn_set_coef_learn): the nine coefficient gradients are "
-                                 "not in the all-reduced buffer, so every rank would follow its own shard's");
+  for (int id = LV_N - 1; id >= 0; --id)       // (the field amplitudes are reported first)
+    if (h->lv[id].on)
+      return fail(VN_EUNSUPPORTED, "vn_comm_init while %s are learnt (%s): %s are not in the all-reduced buffer, so every rank would "
+                                   "follow its own shard's", kLearnt[id].what, kLearnt[id].setter, kLearnt[id].grads);
   if (int rc = load_rccl()) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   ncclUniqueId id;

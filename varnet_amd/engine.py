@@ -129,6 +129,8 @@ ABI_SYMBOLS = tuple(_SIGS.keys())
 
 # the _keep keys of the three polynomial terms, in the order of the coefficient index (vn_set_coef_learn)
 COEF_TERMS = ('react', 'nlflux', 'nldiff')
+# the learnt vectors: the name vn_get_* / vn_set_* carry, and the fixed length (None: the ABI takes the length J)
+LEARNT = {'coef': ('coefs', 9), 'source': ('source_amps', None), 'field': ('field_amps', None)}
 
 
 class VNError(RuntimeError):
@@ -535,7 +537,7 @@ class VNEngine:
             raise ValueError('%s, got %d' % (takes, len(c)))
         c = c + [0.0] * (3 - len(c))
         # (a term with a learnt coefficient stays registered whatever its values: set_coef_learn)
-        mask = getattr(self, '_coef_mask', None)
+        mask = getattr(self, '_learnt_coef', None)
         learnt = mask is not None and any(mask[3 * COEF_TERMS.index(key):3 * COEF_TERMS.index(key) + 3])
         if coef is None or (clears(c, stream) and not learnt):
             self._keep.pop((key, batch), None)
@@ -573,156 +575,120 @@ class VNEngine:
         self._set_term('nldiff', self.lib.vn_set_nldiff, 'a diffusivity takes at most three coefficients (d0, d1, d2)', 'psi',
                        batch, psi, coef, lambda c, s: c == [1.0, 0.0, 0.0] and s is None)
 
+    def _set_learn(self, kind, mask, init, lo, hi, lr):
+        """Register one learnt vector (vn_set_<kind>_learn): mask, init, lo and hi as vectors of its length n -- nine for the
+        coefficients, else the length of `mask` -- with lo / hi defaulting to unbounded; mask=None switches it off."""
+        fn, fixed = getattr(self.lib, 'vn_set_%s_learn' % kind), LEARNT[kind][1]
+        lead = () if fixed else (0,)
+        if mask is None:
+            self._ck(fn(self.h, *lead, None, None, None, None, 0.0))
+            setattr(self, '_learnt_' + kind, None)
+            return
+        m = [1 if x else 0 for x in np.asarray(mask).reshape(-1)]
+        n = fixed or len(m)
+        entries = 'nine entries (reaction, flux, diffusivity: three each)' if fixed else 'one entry per amplitude (%d)' % n
+
+        def vec(a, fill, name):
+            v = np.full(n, fill, dtype=np.float64) if a is None else np.asarray(a, dtype=np.float64).reshape(-1)
+            if v.size != n:
+                raise ValueError('%s must have %s, got %d' % (name, entries, v.size))
+            return v
+        vec(m, 0, 'mask')
+        if init is None or lr is None:
+            raise ValueError('set_%s_learn needs init (%s) and lr' % (kind, 'nine values' if fixed else 'one value per amplitude'))
+        v0, l, u = vec(init, 0.0, 'init'), vec(lo, -np.inf, 'lo'), vec(hi, np.inf, 'hi')
+        dbl = C.c_double * max(n, 1)
+        self._ck(fn(self.h, *(() if fixed else (n,)), (C.c_int32 * max(n, 1))(*m), dbl(*v0), dbl(*l), dbl(*u), float(lr)))
+        setattr(self, '_learnt_' + kind, m)            # (the mask of a vector that is on)
+
+    def _get_learnt(self, kind, grad, J=None):
+        """The values of one learnt vector at the current state (vn_get_*); grad=True: (values, gradient of the last gradient
+        evaluation).  J: the length the caller expects (default: the registered one)."""
+        name, fixed = LEARNT[kind]
+        n = fixed or int(J if J is not None else (len(getattr(self, '_learnt_' + kind, None) or ()) or 1))
+        a, g = (C.c_double * n)(), (C.c_double * n)()
+        self._ck(getattr(self.lib, 'vn_get_' + name)(self.h, a, g if grad else None, *(() if fixed else (n,))))
+        a = np.array(list(a), dtype=np.float64)
+        return (a, np.array(list(g), dtype=np.float64)) if grad else a
+
+    def _set_learnt(self, kind, values):
+        """Overwrite the values of one learnt vector (vn_set_*)."""
+        name, fixed = LEARNT[kind]
+        v = np.asarray(values, dtype=np.float64).reshape(-1)
+        if fixed and v.size != fixed:
+            raise ValueError('coef must have nine entries (reaction, flux, diffusivity: three each), got %d' % v.size)
+        self._ck(getattr(self.lib, 'vn_set_' + name)(self.h, (C.c_double * max(v.size, 1))(*v), *(() if fixed else (int(v.size),))))
+
+    def _set_basis(self, key, fn, batch, streams, trailing):
+        """Register (streams=None: clear) the J basis streams of `batch`, uploaded as [J, rows, *trailing] and kept alive."""
+        if streams is None:
+            self._keep.pop((key, batch), None)
+            self._ck(fn(self.h, int(batch), None, 0))
+            return
+        if not isinstance(streams, self.torch.Tensor):
+            streams = np.asarray(streams, dtype=np.float32)
+        kept = self._keep.get(('int', batch))
+        J = int(streams.shape[0])
+        streams = self.dev(streams.reshape(J, -1, *trailing))
+        # the ABI carries a pointer only: the length the kernels rely on is checked here
+        assert kept is None or streams.shape[1] == kept[0].shape[0], \
+            'every basis stream must have one entry per interior row (%s != %s)' % (streams.shape[1], kept[0].shape[0])
+        self._keep.pop((key, batch), None)         # (a failed call leaves the batch without a basis)
+        self._ck(fn(self.h, int(batch), _ptr(streams), J))
+        self._keep[(key, batch)] = streams
+
     def set_coef_learn(self, mask=None, init=None, lo=None, hi=None, lr=None):
         """Inverse mode (vn_set_coef_learn): learn the masked entries of the nine polynomial coefficients -- index 0..2 reaction
         (c1, c2, c3), 3..5 flux (f1, f2, f3), 6..8 diffusivity (d0, d1, d2) -- next to the parameters.  init: the nine starting
         values, which every registered term of every batch then reads from the engine's device vector; lo / hi: the clamp (None:
         unbounded; entries may be +-inf); lr: their Adam rate.  mask=None switches learning off and frees everything."""
-        if mask is None:
-            self._ck(self.lib.vn_set_coef_learn(self.h, None, None, None, None, 0.0))
-            self._coef_mask = None
-            return
-        def nine(a, fill, name):
-            v = np.full(9, fill, dtype=np.float64) if a is None else np.asarray(a, dtype=np.float64).reshape(-1)
-            if v.size != 9:
-                raise ValueError('%s must have nine entries (reaction, flux, diffusivity: three each), got %d' % (name, v.size))
-            return v
-        m = np.asarray(mask).reshape(-1)
-        if m.size != 9:
-            raise ValueError('mask must have nine entries (reaction, flux, diffusivity: three each), got %d' % m.size)
-        m = [1 if x else 0 for x in m]
-        if init is None or lr is None:
-            raise ValueError('set_coef_learn needs init (nine values) and lr')
-        v0, l, u = nine(init, 0.0, 'init'), nine(lo, -np.inf, 'lo'), nine(hi, np.inf, 'hi')
-        self._ck(self.lib.vn_set_coef_learn(self.h, (C.c_int32 * 9)(*m), (C.c_double * 9)(*v0), (C.c_double * 9)(*l),
-                                            (C.c_double * 9)(*u), float(lr)))
-        self._coef_mask = m
+        self._set_learn('coef', mask, init, lo, hi, lr)
 
     def get_coefs(self, grad=False):
         """The nine coefficients at the current state (vn_get_coefs); grad=True: (coef, gradient of the last gradient evaluation)."""
-        c, g = (C.c_double * 9)(), (C.c_double * 9)()
-        self._ck(self.lib.vn_get_coefs(self.h, c, g if grad else None))
-        c = np.array(list(c), dtype=np.float64)
-        return (c, np.array(list(g), dtype=np.float64)) if grad else c
+        return self._get_learnt('coef', grad)
 
     def set_coefs(self, coef):
         """Overwrite the nine coefficients (vn_set_coefs): rounded to fp32, not clamped; the Adam slots stay."""
-        v = np.asarray(coef, dtype=np.float64).reshape(-1)
-        if v.size != 9:
-            raise ValueError('coef must have nine entries (reaction, flux, diffusivity: three each), got %d' % v.size)
-        self._ck(self.lib.vn_set_coefs(self.h, (C.c_double * 9)(*v)))
+        self._set_learnt('coef', coef)
 
     def set_source_basis(self, batch, phi=None):
         """Register (phi=None: clear) the source basis of `batch` (vn_set_source_basis), after set_interior of that batch: phi is
         [J, rows] (or J arrays of one value per interior row), J <= 64.  The engine must have been created with isSource=True."""
-        if phi is None:
-            self._keep.pop(('srcbasis', batch), None)
-            self._ck(self.lib.vn_set_source_basis(self.h, int(batch), None, 0))
-            return
-        t = self.torch
-        if not isinstance(phi, t.Tensor):
-            phi = np.asarray(phi, dtype=np.float32)
-        kept = self._keep.get(('int', batch))
-        J = int(phi.shape[0])
-        phi = self.dev(phi.reshape(J, -1))
-        # the ABI carries a pointer only: the length the kernels rely on is checked here
-        assert kept is None or phi.shape[1] == kept[0].shape[0], \
-            'every basis stream must have one entry per interior row (%s != %s)' % (phi.shape[1], kept[0].shape[0])
-        self._keep.pop(('srcbasis', batch), None)         # (a failed call leaves the batch without a basis)
-        self._ck(self.lib.vn_set_source_basis(self.h, int(batch), _ptr(phi), J))
-        self._keep[('srcbasis', batch)] = phi
+        self._set_basis('srcbasis', self.lib.vn_set_source_basis, batch, phi, ())
 
     def set_source_learn(self, mask=None, init=None, lo=None, hi=None, lr=None):
         """Source identification (vn_set_source_learn): learn the masked amplitudes a_j of the batches' source bases next to the
         parameters.  mask: J booleans; init: the J starting values (unmasked entries keep theirs); lo / hi: the clamp (None:
         unbounded; entries may be +-inf); lr: their Adam rate.  mask=None switches learning off and frees everything."""
-        if mask is None:
-            self._ck(self.lib.vn_set_source_learn(self.h, 0, None, None, None, None, 0.0))
-            self._src_J = None
-            return
-        m = [1 if x else 0 for x in np.asarray(mask).reshape(-1)]
-        J = len(m)
-        if init is None or lr is None:
-            raise ValueError('set_source_learn needs init (one value per amplitude) and lr')
-
-        def vec(a, fill, name):
-            v = np.full(J, fill, dtype=np.float64) if a is None else np.asarray(a, dtype=np.float64).reshape(-1)
-            if v.size != J:
-                raise ValueError('%s must have one entry per amplitude (%d), got %d' % (name, J, v.size))
-            return v
-        v0, l, u = vec(init, 0.0, 'init'), vec(lo, -np.inf, 'lo'), vec(hi, np.inf, 'hi')
-        self._ck(self.lib.vn_set_source_learn(self.h, J, (C.c_int32 * max(J, 1))(*m), (C.c_double * max(J, 1))(*v0),
-                                              (C.c_double * max(J, 1))(*l), (C.c_double * max(J, 1))(*u), float(lr)))
-        self._src_J = J
+        self._set_learn('source', mask, init, lo, hi, lr)
 
     def get_source_amps(self, grad=False, J=None):
         """The amplitudes at the current state (vn_get_source_amps); grad=True: (amp, gradient of the last gradient evaluation)."""
-        J = int(J if J is not None else (getattr(self, '_src_J', None) or 1))
-        a, g = (C.c_double * J)(), (C.c_double * J)()
-        self._ck(self.lib.vn_get_source_amps(self.h, a, g if grad else None, J))
-        a = np.array(list(a), dtype=np.float64)
-        return (a, np.array(list(g), dtype=np.float64)) if grad else a
+        return self._get_learnt('source', grad, J)
 
     def set_source_amps(self, amp):
         """Overwrite the amplitudes (vn_set_source_amps): rounded to fp32, not clamped; the Adam slots stay."""
-        v = np.asarray(amp, dtype=np.float64).reshape(-1)
-        self._ck(self.lib.vn_set_source_amps(self.h, (C.c_double * max(v.size, 1))(*v), int(v.size)))
+        self._set_learnt('source', amp)
 
     def set_field_basis(self, batch, G=None):
         """Register (G=None: clear) the field basis of `batch` (vn_set_field_basis), after set_interior of that batch: G is
         [J, rows, dim] (J streams laid out like gcoef), J <= 32."""
-        if G is None:
-            self._keep.pop(('fldbasis', batch), None)
-            self._ck(self.lib.vn_set_field_basis(self.h, int(batch), None, 0))
-            return
-        t = self.torch
-        if not isinstance(G, t.Tensor):
-            G = np.asarray(G, dtype=np.float32)
-        kept = self._keep.get(('int', batch))
-        J = int(G.shape[0])
-        G = self.dev(G.reshape(J, -1, self.dim))
-        # the ABI carries a pointer only: the length the kernels rely on is checked here
-        assert kept is None or G.shape[1] == kept[0].shape[0], \
-            'every basis stream must have one entry per interior row (%s != %s)' % (G.shape[1], kept[0].shape[0])
-        self._keep.pop(('fldbasis', batch), None)         # (a failed call leaves the batch without a basis)
-        self._ck(self.lib.vn_set_field_basis(self.h, int(batch), _ptr(G), J))
-        self._keep[('fldbasis', batch)] = G
+        self._set_basis('fldbasis', self.lib.vn_set_field_basis, batch, G, (self.dim,))
 
     def set_field_learn(self, mask=None, init=None, lo=None, hi=None, lr=None):
         """Field identification (vn_set_field_learn): learn the masked amplitudes b_j of the batches' field bases next to the
         parameters.  mask: J booleans; init: the J starting values (unmasked entries keep theirs); lo / hi: the clamp (None:
         unbounded; entries may be +-inf); lr: their Adam rate.  mask=None switches learning off and frees everything."""
-        if mask is None:
-            self._ck(self.lib.vn_set_field_learn(self.h, 0, None, None, None, None, 0.0))
-            self._fld_J = None
-            return
-        m = [1 if x else 0 for x in np.asarray(mask).reshape(-1)]
-        J = len(m)
-        if init is None or lr is None:
-            raise ValueError('set_field_learn needs init (one value per amplitude) and lr')
-
-        def vec(a, fill, name):
-            v = np.full(J, fill, dtype=np.float64) if a is None else np.asarray(a, dtype=np.float64).reshape(-1)
-            if v.size != J:
-                raise ValueError('%s must have one entry per amplitude (%d), got %d' % (name, J, v.size))
-            return v
-        v0, l, u = vec(init, 0.0, 'init'), vec(lo, -np.inf, 'lo'), vec(hi, np.inf, 'hi')
-        self._ck(self.lib.vn_set_field_learn(self.h, J, (C.c_int32 * max(J, 1))(*m), (C.c_double * max(J, 1))(*v0),
-                                             (C.c_double * max(J, 1))(*l), (C.c_double * max(J, 1))(*u), float(lr)))
-        self._fld_J = J
+        self._set_learn('field', mask, init, lo, hi, lr)
 
     def get_field_amps(self, grad=False, J=None):
         """The amplitudes at the current state (vn_get_field_amps); grad=True: (amp, gradient of the last gradient evaluation)."""
-        J = int(J if J is not None else (getattr(self, '_fld_J', None) or 1))
-        a, g = (C.c_double * J)(), (C.c_double * J)()
-        self._ck(self.lib.vn_get_field_amps(self.h, a, g if grad else None, J))
-        a = np.array(list(a), dtype=np.float64)
-        return (a, np.array(list(g), dtype=np.float64)) if grad else a
+        return self._get_learnt('field', grad, J)
 
     def set_field_amps(self, amp):
         """Overwrite the amplitudes (vn_set_field_amps): rounded to fp32, not clamped; the Adam slots stay."""
-        v = np.asarray(amp, dtype=np.float64).reshape(-1)
-        self._ck(self.lib.vn_set_field_amps(self.h, (C.c_double * max(v.size, 1))(*v), int(v.size)))
+        self._set_learnt('field', amp)
 
     def _n_k(self, batch):
         kept = self._keep.get(('int', batch))

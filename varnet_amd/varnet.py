@@ -16,6 +16,7 @@ constructor and `train / evaluate / residual / loadModel` surface
 
 Out of scope here: modelId='RNN', updateWeights, plots.
 """
+import collections
 import math
 import os
 import pickle
@@ -867,15 +868,12 @@ class VarNet:
                     or not np.isfinite(float(periodicDeriv)) or float(periodicDeriv) < 0.0:
                 raise ValueError('periodicDeriv=%r must be a finite number >= 0' % (periodicDeriv,))
 
-        if learnCoef is not None and MORvar is not None:
-            raise NotImplementedError('learnCoef with model-order reduction is not supported: neither the three polynomial terms nor '
-                                      'the observations it needs are')
-        if learnSource is not None and MORvar is not None:
-            raise NotImplementedError('learnSource with model-order reduction is not supported: neither the source basis nor '
-                                      'the observations it needs are')
-        if learnField is not None and MORvar is not None:
-            raise NotImplementedError('learnField with model-order reduction is not supported: neither the field bases nor '
-                                      'the observations it needs are')
+        learnt = {'learnCoef': (learnCoef, coefLr, coefBounds), 'learnSource': (learnSource, sourceLr, sourceBounds),
+                  'learnField': (learnField, fieldLr, fieldBounds)}
+        for lv in self.LEARNT:
+            if learnt[lv.option][0] is not None and MORvar is not None:
+                raise NotImplementedError('%s with model-order reduction is not supported: neither %s nor the observations it needs '
+                                          'are' % (lv.option, lv.mor_lacks))
         # observations=... (extension; no reference counterpart): sensor data as linear functionals of the solution, fitted by a
         # misfit term obsWeight * O next to the PDE's loss (`obsData`)
         if observations is None:
@@ -887,47 +885,25 @@ class VarNet:
                                           'assembled once, for all parameter batches, and carry no parameter inputs')
             self._check_obs_weight(1.0 if obsWeight is None else obsWeight)
 
-        # learnCoef=... (extension; no reference counterpart): inverse mode, the masked polynomial coefficients of the PDE's
-        # reaction / flux / diffusivity are learnt next to the network from the observations (`coefLearnData`)
-        self.coefLearn = self.coefLearnData(PDE, learnCoef, coefLr, coefBounds, learning_rate)
-        if self.coefLearn is not None:
+        # learnCoef=..., learnSource=..., learnField=... (extensions; no reference counterpart): inverse mode, source and field
+        # identification -- the masked polynomial coefficients of the PDE's reaction / flux / diffusivity, the masked amplitudes of
+        # its source basis, and those of its diffusivity and velocity bases are learnt next to the network from the observations
+        # (`coefLearnData`, `sourceLearnData`, `fieldLearnData`)
+        for lv in self.LEARNT:
+            data = getattr(self, lv.parser)(PDE, *learnt[lv.option], learning_rate)
+            setattr(self, lv.attr, data)
+            if data is None:
+                continue
             if observations is None:
-                raise ValueError('learnCoef needs observations=...: without interior data every coefficient admits a solution of '
-                                 'the boundary value problem, so the loss cannot tell one value from another')
+                raise ValueError('%s needs observations=...: without interior data every %s admits a solution of the boundary value '
+                                 'problem, so the loss cannot tell one value from another' % (lv.option, lv.noun))
             if optimizer.lower() != 'adam':
-                raise NotImplementedError('learnCoef with optimizer=%r: the coefficients are updated by the Adam step only (an L-BFGS '
-                                          'search over (parameters, coefficients) and an RMSProp update are not built)' % (optimizer,))
+                raise NotImplementedError('%s with optimizer=%r: the %ss are updated by the Adam step only (an L-BFGS search over '
+                                          '(parameters, %ss) and an RMSProp update are not built)'
+                                          % (lv.option, optimizer, lv.noun, lv.noun))
             if causal is not None:
-                raise NotImplementedError('learnCoef with causal=%r: the causal weights are applied after the seeds the coefficient '
-                                          'gradient is reduced from' % (causal,))
-
-        # learnSource=... (extension; no reference counterpart): source identification, the masked amplitudes of the PDE's source
-        # basis are learnt next to the network from the observations (`sourceLearnData`)
-        self.srcLearn = self.sourceLearnData(PDE, learnSource, sourceLr, sourceBounds, learning_rate)
-        if self.srcLearn is not None:
-            if observations is None:
-                raise ValueError('learnSource needs observations=...: without interior data every amplitude admits a solution of '
-                                 'the boundary value problem, so the loss cannot tell one value from another')
-            if optimizer.lower() != 'adam':
-                raise NotImplementedError('learnSource with optimizer=%r: the amplitudes are updated by the Adam step only (an L-BFGS '
-                                          'search over (parameters, amplitudes) and an RMSProp update are not built)' % (optimizer,))
-            if causal is not None:
-                raise NotImplementedError('learnSource with causal=%r: the causal weights are applied after the seeds the amplitude '
-                                          'gradient is reduced from' % (causal,))
-
-        # learnField=... (extension; no reference counterpart): field identification, the masked amplitudes of the PDE's diffusivity
-        # and velocity bases are learnt next to the network from the observations (`fieldLearnData`)
-        self.fldLearn = self.fieldLearnData(PDE, learnField, fieldLr, fieldBounds, learning_rate)
-        if self.fldLearn is not None:
-            if observations is None:
-                raise ValueError('learnField needs observations=...: without interior data every amplitude admits a solution of '
-                                 'the boundary value problem, so the loss cannot tell one value from another')
-            if optimizer.lower() != 'adam':
-                raise NotImplementedError('learnField with optimizer=%r: the amplitudes are updated by the Adam step only (an L-BFGS '
-                                          'search over (parameters, amplitudes) and an RMSProp update are not built)' % (optimizer,))
-            if causal is not None:
-                raise NotImplementedError('learnField with causal=%r: the causal weights are applied after the seeds the amplitude '
-                                          'gradient is reduced from' % (causal,))
+                raise NotImplementedError('%s with causal=%r: the causal weights are applied after the seeds the %s gradient is '
+                                          'reduced from' % (lv.option, causal, lv.noun))
 
         inpDim = dim + (1 if timeDependent else 0)
         if MORvar is not None:
@@ -971,15 +947,10 @@ class VarNet:
             raise NotImplementedError('causal=%r with towers: a rank\'s slab means would cover only its shard of the test '
                                       'functions, so the ranks together would train another objective than one rank'
                                       % (causal,))
-        if self.coefLearn is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
-            raise NotImplementedError('learnCoef with towers: the nine coefficient gradients are not part of the all-reduced '
-                                      'buffer, so every rank would follow its own shard')
-        if self.srcLearn is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
-            raise NotImplementedError('learnSource with towers: the amplitude gradients are not part of the all-reduced '
-                                      'buffer, so every rank would follow its own shard')
-        if self.fldLearn is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
-            raise NotImplementedError('learnField with towers: the amplitude gradients are not part of the all-reduced '
-                                      'buffer, so every rank would follow its own shard')
+        for lv in self.LEARNT:
+            if getattr(self, lv.attr) is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
+                raise NotImplementedError('%s with towers: %s are not part of the all-reduced buffer, so every rank would follow its '
+                                          'own shard' % (lv.option, lv.grads))
         if isinstance(processors, (list, tuple)) and len(processors) > 1 and self.world == 1:
             # the reference's single-process multi-GPU call (TFModel.py:120-165): this process becomes the
             # controller of one forked child per GPU (varnet_amd/towers.py); it never touches the GPU itself
@@ -1109,6 +1080,74 @@ class VarNet:
             scale[0:3] = float(PDE.reactionRate)
         return c, scale
 
+    # -- the vectors learnt next to the network, in the engine's order: the option, its parser, the attribute that keeps the parsed
+    # registration, the noun of an entry, what model-order reduction lacks for it, what towers lack, the checkpoint key, the stem
+    # of the engine's get_* / set_* methods, and the title of train()'s closing line
+    LearntVector = collections.namedtuple('LearntVector', 'option parser attr noun mor_lacks grads key engine title')
+    LEARNT = (
+        LearntVector('learnCoef', 'coefLearnData', 'coefLearn', 'coefficient', 'the three polynomial terms',
+                     'the nine coefficient gradients', 'pde_coefficients', 'coefs', 'Learnt coefficients'),
+        LearntVector('learnSource', 'sourceLearnData', 'srcLearn', 'amplitude', 'the source basis',
+                     'the amplitude gradients', 'source_amplitudes', 'source_amps', 'Learnt source amplitudes'),
+        LearntVector('learnField', 'fieldLearnData', 'fldLearn', 'amplitude', 'the field bases',
+                     'the amplitude gradients', 'field_amplitudes', 'field_amps', 'Learnt field amplitudes (diff, then vel)'))
+
+    # -- what the three learnt vectors' options share (coefLearnData, sourceLearnData, fieldLearnData) --
+    @staticmethod
+    def _learn_mask(sel, n, err):
+        """A mask selection: True (all n entries) or a list of n 0/1/bool values; anything else raises ValueError(err)."""
+        if sel is True:
+            return np.ones(n, dtype=bool)
+        isbool = lambda x: isinstance(x, (bool, np.bool_)) or (isinstance(x, (int, np.integer)) and x in (0, 1))
+        if not isinstance(sel, (list, tuple, np.ndarray)) or len(sel) != n or not all(isbool(x) for x in sel):
+            raise ValueError(err)
+        return np.array([bool(x) for x in sel])
+
+    @staticmethod
+    def _learn_bounds(bounds, label, mask, init, noun, option, err, pair=True, scale=None):
+        """A bounds selection over the entries of `mask` as (lo, hi) arrays: with `pair` one (lo, hi) for every learnt entry, or a
+        list of one entry per mask entry, each None or (lo, hi) with None for an open side; any other shape raises
+        ValueError(err).  `label` prefixes the messages about entry j (label[j]), `noun` and `option` name what it bounds; `scale`
+        takes the bounds (checked against `init` as given) to the engine's scale."""
+        n = len(mask)
+        lo, hi = np.full(n, -np.inf), np.full(n, np.inf)
+        if bounds is None:
+            return lo, hi
+        free = lambda x: x is None or (isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool))
+        if pair and isinstance(bounds, (list, tuple)) and len(bounds) == 2 and all(free(x) for x in bounds):
+            entries = [tuple(bounds) if mask[j] else None for j in range(n)]      # one pair: every learnt entry
+        elif isinstance(bounds, (list, tuple)) and len(bounds) == n:
+            entries = list(bounds)
+        else:
+            raise ValueError(err)
+        for j, bd in enumerate(entries):
+            if bd is None:
+                continue
+            if not mask[j]:
+                raise ValueError('%s[%d] bounds %s that %s does not select' % (label, j, noun, option))
+            if not isinstance(bd, (list, tuple)) or len(bd) != 2:
+                raise ValueError('%s[%d] must be None or (lo, hi), got %r' % (label, j, bd))
+            a = -np.inf if bd[0] is None else bd[0]
+            b = np.inf if bd[1] is None else bd[1]
+            for x in (a, b):
+                if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or np.isnan(x):
+                    raise ValueError('%s[%d] must hold numbers or None, got %r' % (label, j, bd))
+            if a > b:
+                raise ValueError('%s[%d]: lower bound %r above upper bound %r' % (label, j, a, b))
+            if not a <= init[j] <= b:
+                raise ValueError('%s[%d] = %r excludes the initial guess %r' % (label, j, bd, float(init[j])))
+            ea, eb = float(a) * (1.0 if scale is None else scale[j]), float(b) * (1.0 if scale is None else scale[j])
+            lo[j], hi[j] = min(ea, eb), max(ea, eb)
+        return lo, hi
+
+    @staticmethod
+    def _learn_rate(lr, name, learning_rate):
+        """The Adam rate of a learnt vector: option `name`, by default the network's learning rate."""
+        lr = learning_rate if lr is None else lr
+        if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not np.isfinite(lr) or lr <= 0:
+            raise ValueError('%s=%r must be a finite number > 0' % (name, lr))
+        return float(lr)
+
     @staticmethod
     def coefLearnData(PDE, learnCoef, coefLr=None, coefBounds=None, learning_rate=0.001):
         """(No reference counterpart: `VarNet(..., learnCoef=...)`.)  The registration of `vn_set_coef_learn` in the engine's
@@ -1132,19 +1171,10 @@ class VarNet:
             if getattr(PDE, key, None) is None:
                 raise ValueError('learnCoef: the PDE has no %s term (ADPDE(..., %s=...))' % (key, key))
             g = keys.index(key)
-            if val is True:
-                mask[3 * g:3 * g + 3] = True
-                continue
-            ok = isinstance(val, (list, tuple, np.ndarray)) and len(val) == 3 and \
-                all(isinstance(x, (bool, np.bool_)) or (isinstance(x, (int, np.integer)) and x in (0, 1)) for x in val)
-            if not ok:
-                raise ValueError('learnCoef[%r] must be True or a mask of three booleans, got %r' % (key, val))
-            mask[3 * g:3 * g + 3] = [bool(x) for x in val]
+            mask[3 * g:3 * g + 3] = VarNet._learn_mask(val, 3, 'learnCoef[%r] must be True or a mask of three booleans, got %r' % (key, val))
         if not mask.any():
             raise ValueError('learnCoef selects no coefficient')
-        lr = learning_rate if coefLr is None else coefLr
-        if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not np.isfinite(lr) or lr <= 0:
-            raise ValueError('coefLr=%r must be a finite number > 0' % (lr,))
+        lr = VarNet._learn_rate(coefLr, 'coefLr', learning_rate)
         c, scale = VarNet._pde_coefs(PDE)
         if mask[0:3].any() and scale[0] == 0.0:
             raise ValueError('learnCoef[\'reaction\'] with a reaction rate of 0: the engine learns rate * c and coefficients() '
@@ -1156,29 +1186,11 @@ class VarNet:
             for key, val in coefBounds.items():
                 if key not in keys:
                     raise ValueError('coefBounds: unknown key %r (the keys are %s)' % (key, keys))
-                if not isinstance(val, (list, tuple)) or len(val) != 3:
-                    raise ValueError('coefBounds[%r] must list three entries, each None or (lo, hi)' % (key,))
-                g = keys.index(key)
-                for m, bd in enumerate(val):
-                    if bd is None:
-                        continue
-                    i = 3 * g + m
-                    if not mask[i]:
-                        raise ValueError('coefBounds[%r][%d] bounds a coefficient that learnCoef does not select' % (key, m))
-                    if not isinstance(bd, (list, tuple)) or len(bd) != 2:
-                        raise ValueError('coefBounds[%r][%d] must be None or (lo, hi), got %r' % (key, m, bd))
-                    a = -np.inf if bd[0] is None else bd[0]
-                    b = np.inf if bd[1] is None else bd[1]
-                    for x in (a, b):
-                        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or np.isnan(x):
-                            raise ValueError('coefBounds[%r][%d] must hold numbers or None, got %r' % (key, m, bd))
-                    if a > b:
-                        raise ValueError('coefBounds[%r][%d]: lower bound %r above upper bound %r' % (key, m, a, b))
-                    if not a <= c[i] <= b:
-                        raise ValueError('coefBounds[%r][%d] = %r excludes the initial guess %r' % (key, m, bd, float(c[i])))
-                    ea, eb = float(a) * scale[i], float(b) * scale[i]
-                    lo[i], hi[i] = min(ea, eb), max(ea, eb)
-        return dict(mask=[int(x) for x in mask], init=c * scale, lo=lo, hi=hi, lr=float(lr), scale=scale)
+                t = slice(3 * keys.index(key), 3 * keys.index(key) + 3)
+                lo[t], hi[t] = VarNet._learn_bounds(val, 'coefBounds[%r]' % (key,), mask[t], c[t], 'a coefficient', 'learnCoef',
+                                                    'coefBounds[%r] must list three entries, each None or (lo, hi)' % (key,),
+                                                    pair=False, scale=scale[t])
+        return dict(mask=[int(x) for x in mask], init=c * scale, lo=lo, hi=hi, lr=lr, scale=scale)
 
     def _coef_dict(self, v):
         return {k: [float(x) for x in v[3 * g:3 * g + 3]] for g, k in enumerate(self.COEF_KEYS)}
@@ -1231,48 +1243,16 @@ class VarNet:
         if basis is None:
             raise ValueError('learnSource: the PDE has no source basis (ADPDE(..., sourceBasis=[phi_1, ..., phi_J]))')
         J = len(basis)
-        isbool = lambda x: isinstance(x, (bool, np.bool_)) or (isinstance(x, (int, np.integer)) and x in (0, 1))
-        if learnSource is True:
-            mask = np.ones(J, dtype=bool)
-        else:
-            if not isinstance(learnSource, (list, tuple, np.ndarray)) or len(learnSource) != J or not all(isbool(x) for x in learnSource):
-                raise ValueError('learnSource must be True or a mask of %d booleans (one per function of sourceBasis), got %r'
-                                 % (J, learnSource))
-            mask = np.array([bool(x) for x in learnSource])
+        mask = VarNet._learn_mask(learnSource, J, 'learnSource must be True or a mask of %d booleans (one per function of sourceBasis), '
+                                  'got %r' % (J, learnSource))
         if not mask.any():
             raise ValueError('learnSource selects no amplitude')
-        lr = learning_rate if sourceLr is None else sourceLr
-        if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not np.isfinite(lr) or lr <= 0:
-            raise ValueError('sourceLr=%r must be a finite number > 0' % (lr,))
+        lr = VarNet._learn_rate(sourceLr, 'sourceLr', learning_rate)
         a0 = np.asarray(PDE.sourceAmp, dtype=np.float64)
-        lo, hi = np.full(J, -np.inf), np.full(J, np.inf)
-        if sourceBounds is not None:
-            free = lambda x: x is None or (isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool))
-            if isinstance(sourceBounds, (list, tuple)) and len(sourceBounds) == 2 and all(free(x) for x in sourceBounds):
-                entries = [tuple(sourceBounds) if mask[j] else None for j in range(J)]      # one pair: every learnt amplitude
-            elif isinstance(sourceBounds, (list, tuple)) and len(sourceBounds) == J:
-                entries = list(sourceBounds)
-            else:
-                raise ValueError('sourceBounds must be (lo, hi) or a list of %d entries, each None or (lo, hi), got %r'
-                                 % (J, sourceBounds))
-            for j, bd in enumerate(entries):
-                if bd is None:
-                    continue
-                if not mask[j]:
-                    raise ValueError('sourceBounds[%d] bounds an amplitude that learnSource does not select' % j)
-                if not isinstance(bd, (list, tuple)) or len(bd) != 2:
-                    raise ValueError('sourceBounds[%d] must be None or (lo, hi), got %r' % (j, bd))
-                a = -np.inf if bd[0] is None else bd[0]
-                b = np.inf if bd[1] is None else bd[1]
-                for x in (a, b):
-                    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or np.isnan(x):
-                        raise ValueError('sourceBounds[%d] must hold numbers or None, got %r' % (j, bd))
-                if a > b:
-                    raise ValueError('sourceBounds[%d]: lower bound %r above upper bound %r' % (j, a, b))
-                if not a <= a0[j] <= b:
-                    raise ValueError('sourceBounds[%d] = %r excludes the initial guess %r' % (j, bd, float(a0[j])))
-                lo[j], hi[j] = float(a), float(b)
-        return dict(mask=[int(x) for x in mask], init=a0.copy(), lo=lo, hi=hi, lr=float(lr))
+        lo, hi = VarNet._learn_bounds(sourceBounds, 'sourceBounds', mask, a0, 'an amplitude', 'learnSource',
+                                      'sourceBounds must be (lo, hi) or a list of %d entries, each None or (lo, hi), got %r'
+                                      % (J, sourceBounds))
+        return dict(mask=[int(x) for x in mask], init=a0.copy(), lo=lo, hi=hi, lr=lr)
 
     def _source_basis(self, Input):
         """The basis functions of the PDE's source at the rows of Input, [n, J] in fp64, evaluated like the source (PDEinpData)."""
@@ -1342,8 +1322,6 @@ class VarNet:
         if fieldBounds is not None and (not isinstance(fieldBounds, dict) or any(k not in keys for k in fieldBounds)):
             raise ValueError('fieldBounds must be a dict {\'diff\': ..., \'vel\': ...}, got %r' % (fieldBounds,))
         Jk, Jv = VarNet._field_sizes(PDE)
-        isbool = lambda x: isinstance(x, (bool, np.bool_)) or (isinstance(x, (int, np.integer)) and x in (0, 1))
-        free = lambda x: x is None or (isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool))
         masks, a0s, los, his = [], [], [], []
         for key, J, amp in (('diff', Jk, 'diffAmp'), ('vel', Jv, 'velAmp')):
             sel = learnField.get(key)
@@ -1355,50 +1333,21 @@ class VarNet:
                 continue
             if sel is None or sel is False:
                 mask = np.zeros(J, dtype=bool)
-            elif sel is True:
-                mask = np.ones(J, dtype=bool)
             else:
-                if not isinstance(sel, (list, tuple, np.ndarray)) or len(sel) != J or not all(isbool(x) for x in sel):
-                    raise ValueError('learnField[%r] must be True or a mask of %d booleans (one per function of %sBasis), got %r'
-                                     % (key, J, key, sel))
-                mask = np.array([bool(x) for x in sel])
+                mask = VarNet._learn_mask(sel, J, 'learnField[%r] must be True or a mask of %d booleans (one per function of %sBasis), '
+                                          'got %r' % (key, J, key, sel))
             a0 = np.asarray(getattr(PDE, amp), dtype=np.float64)
-            lo, hi = np.full(J, -np.inf), np.full(J, np.inf)
             bounds = None if fieldBounds is None else fieldBounds.get(key)
-            if bounds is not None:
-                if isinstance(bounds, (list, tuple)) and len(bounds) == 2 and all(free(x) for x in bounds):
-                    entries = [tuple(bounds) if mask[j] else None for j in range(J)]      # one pair: every learnt amplitude
-                elif isinstance(bounds, (list, tuple)) and len(bounds) == J:
-                    entries = list(bounds)
-                else:
-                    raise ValueError('fieldBounds[%r] must be (lo, hi) or a list of %d entries, each None or (lo, hi), got %r'
-                                     % (key, J, bounds))
-                for j, bd in enumerate(entries):
-                    if bd is None:
-                        continue
-                    if not mask[j]:
-                        raise ValueError('fieldBounds[%r][%d] bounds an amplitude that learnField does not select' % (key, j))
-                    if not isinstance(bd, (list, tuple)) or len(bd) != 2:
-                        raise ValueError('fieldBounds[%r][%d] must be None or (lo, hi), got %r' % (key, j, bd))
-                    a = -np.inf if bd[0] is None else bd[0]
-                    b = np.inf if bd[1] is None else bd[1]
-                    for x in (a, b):
-                        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or np.isnan(x):
-                            raise ValueError('fieldBounds[%r][%d] must hold numbers or None, got %r' % (key, j, bd))
-                    if a > b:
-                        raise ValueError('fieldBounds[%r][%d]: lower bound %r above upper bound %r' % (key, j, a, b))
-                    if not a <= a0[j] <= b:
-                        raise ValueError('fieldBounds[%r][%d] = %r excludes the initial guess %r' % (key, j, bd, float(a0[j])))
-                    lo[j], hi[j] = float(a), float(b)
+            lo, hi = VarNet._learn_bounds(bounds, 'fieldBounds[%r]' % (key,), mask, a0, 'an amplitude', 'learnField',
+                                          'fieldBounds[%r] must be (lo, hi) or a list of %d entries, each None or (lo, hi), got %r'
+                                          % (key, J, bounds))
             masks.append(mask); a0s.append(a0); los.append(lo); his.append(hi)
         mask = np.concatenate(masks)
         if not mask.any():
             raise ValueError('learnField selects no amplitude')
-        lr = learning_rate if fieldLr is None else fieldLr
-        if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not np.isfinite(lr) or lr <= 0:
-            raise ValueError('fieldLr=%r must be a finite number > 0' % (lr,))
+        lr = VarNet._learn_rate(fieldLr, 'fieldLr', learning_rate)
         return dict(mask=[int(x) for x in mask], init=np.concatenate(a0s), lo=np.concatenate(los), hi=np.concatenate(his),
-                    lr=float(lr), Jk=Jk, Jv=Jv)
+                    lr=lr, Jk=Jk, Jv=Jv)
 
     def _field_basis(self, Input, grad=False):
         """(chi [Jk, n, 1], grad chi [Jk, n, dim] or None without `grad`, omega [Jv, n, dim]) of the PDE's field bases at the rows
@@ -2553,19 +2502,13 @@ class VarNet:
                         trainW, w_eff, _ = set_train_weights(tData, weight)
             epoch = first + nblk
         trainRes.flushPlots()
-        if self.coefLearn is not None and self.rank == 0:
-            cl, cur = self.coefLearn, self.coefficients()
-            trainRes.writeCase('Learnt coefficients: mask %s, initial %s, final %s\n'
-                               % (cl['mask'], [float(x) for x in cl['init'] / cl['scale']],
-                                  [x for k in self.COEF_KEYS for x in cur[k]]))
-        if self.srcLearn is not None and self.rank == 0:
-            sl = self.srcLearn
-            trainRes.writeCase('Learnt source amplitudes: mask %s, initial %s, final %s\n'
-                               % (sl['mask'], [float(x) for x in sl['init']], [float(x) for x in self.sourceAmplitudes()]))
-        if self.fldLearn is not None and self.rank == 0:
-            fl = self.fldLearn
-            trainRes.writeCase('Learnt field amplitudes (diff, then vel): mask %s, initial %s, final %s\n'
-                               % (fl['mask'], [float(x) for x in fl['init']], [float(x) for x in self._field_vector()]))
+        for lv in self.LEARNT:
+            data = getattr(self, lv.attr)
+            if data is not None and self.rank == 0:
+                scale = data.get('scale', 1.0)           # (coefficients are reported in the user's scale: `coefficients()`)
+                trainRes.writeCase('%s: mask %s, initial %s, final %s\n'
+                                   % (lv.title, data['mask'], [float(x) for x in data['init'] / scale],
+                                      [float(x) for x in getattr(self.engine, 'get_' + lv.engine)() / scale]))
         return trainRes
 
     # -- checkpoints ----------------------------------------------------------------------------------
@@ -2601,15 +2544,11 @@ class VarNet:
         if slot[0] == 'Adam':
             out['beta1_power'] = np.float32(0.9 ** (step + 1))       # TF keeps beta^(t+1) for the next update
             out['beta2_power'] = np.float32(0.999 ** (step + 1))
-        if getattr(self, 'coefLearn', None) is not None:
-            # the nine values in the engine's scale (vn_get_coefs); their Adam slots have no entry point and restart from zero
-            out['pde_coefficients'] = np.asarray(self.engine.get_coefs(), dtype=np.float64)
-        if getattr(self, 'srcLearn', None) is not None:
-            # the J amplitudes (vn_get_source_amps); their Adam slots restart from zero, as for pde_coefficients
-            out['source_amplitudes'] = self.sourceAmplitudes()
-        if getattr(self, 'fldLearn', None) is not None:
-            # the J amplitudes, diffusivity streams first (vn_get_field_amps); their Adam slots restart from zero likewise
-            out['field_amplitudes'] = self._field_vector()
+        for lv in self.LEARNT:
+            if getattr(self, lv.attr, None) is not None:
+                # the values in the engine's scale (vn_get_*: the nine coefficients, the J source amplitudes, the J field amplitudes
+                # with the diffusivity streams first); their Adam slots have no entry point and restart from zero
+                out[lv.key] = np.asarray(getattr(self.engine, 'get_' + lv.engine)(), dtype=np.float64)
         return out
 
     def restore_arrays(self, arrays):
@@ -2633,12 +2572,9 @@ class VarNet:
         step = np.array([int(arrays['global_step']) if 'global_step' in arrays else 0], dtype=np.int64)
         blob = np.concatenate([step.view(np.uint8), np.concatenate(th + m + v).astype(np.float32).view(np.uint8)])
         self.engine.import_state(blob)
-        if getattr(self, 'coefLearn', None) is not None and 'pde_coefficients' in arrays:
-            self.engine.set_coefs(np.asarray(arrays['pde_coefficients'], dtype=np.float64).reshape(-1))
-        if getattr(self, 'srcLearn', None) is not None and 'source_amplitudes' in arrays:
-            self.engine.set_source_amps(np.asarray(arrays['source_amplitudes'], dtype=np.float64).reshape(-1))
-        if getattr(self, 'fldLearn', None) is not None and 'field_amplitudes' in arrays:
-            self.engine.set_field_amps(np.asarray(arrays['field_amplitudes'], dtype=np.float64).reshape(-1))
+        for lv in self.LEARNT:
+            if getattr(self, lv.attr, None) is not None and lv.key in arrays:
+                getattr(self.engine, 'set_' + lv.engine)(np.asarray(arrays[lv.key], dtype=np.float64).reshape(-1))
 
     def saveModel(self, epoch):
         """`saver.save(sess, 'best_model', global_step=epoch)` with max_to_keep=2 (TFModel.py:307,
