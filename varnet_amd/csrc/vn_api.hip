@@ -2,9 +2,7 @@
 // reference call sites each entry point replaces).
 #include "vn_internal.h"
 #include "vn_dedup.h"
-#include "vn_flux.h"
-#include "vn_periodic.h"
-#include "vn_obs.h"
+#include "vn_edge.h"
 #include "vn_lbfgs.h"
 #include "vn_obj64.h"
 #include "vn_pgrad16.h"
@@ -212,6 +210,21 @@ int learnt_weights_refusal(const LearntKind& k, int batch) {
                                "the weights are applied after the seeds the %s reduction reads", k.what, k.setter, batch, k.noun);
 }
 
+// ---- edge row sets: rows the network is evaluated on beside a batch (vn_edge.h) ---------------
+// One record per set, by VnEdgeId; what differs between the sets is a row of kEdge (below vn_engine) and the few fields the
+// engine keeps beside the records.  Everything that handles them (edge_* below) runs over the records in VnEdgeId order.
+enum EdgeBuf { EB_U, EB_UD, EB_UBAR, EB_UDBAR, EB_LOSS, EB_PARTIAL, EB_N };
+
+struct EdgeSet {
+  const float* X = nullptr;                       // caller-owned rows [rows, d_in]
+  const float* G = nullptr;                       // caller-owned tangent directions [rows, dim]; nullptr: values only
+  long rows = 0;                                  // rows the network sees
+  long count = 0;                                 // rows, pairs or observations the mean divides by; 0: none registered
+  int grid = 0;                                   // workgroups of the rows' reverse pass
+  float* buf[EB_N] = {};                          // engine-owned: u, ud, ubar, udbar [rows], loss [seed blocks], partial [grid, P]
+  long cap[EB_N] = {};
+};
+
 }  // namespace
 
 #ifndef VN_WITH_FUSED32
@@ -272,28 +285,17 @@ struct vn_engine {
   float* wt_lvec = nullptr; long wt_lvec_cap = 0;
   float* wt_omega = nullptr; long wt_omega_cap = 0;
   float* wt_stat = nullptr; long wt_stat_cap = 0;
-  // boundary-flux rows (vn_set_flux_bc): caller-owned inputs, engine-owned work buffers; nF == 0: none
-  const float *fX = nullptr, *fN = nullptr, *fcoef = nullptr, *flabel = nullptr;
-  long nF = 0;
+  // the edge row sets by VnEdgeId (es[id].count == 0: none registered), then what each kind keeps beside its record, caller-owned:
+  // boundary-flux rows (vn_set_flux_bc), nF = count rows with their normals in G
+  EdgeSet es[VN_EDGE_N];
+  const float *fcoef = nullptr, *flabel = nullptr;
   double fbiDimVal = 1.0;
-  int fgrid = 0;                                  // workgroups of the flux rows' reverse pass
-  float *fu = nullptr, *fud = nullptr, *fubar = nullptr, *fudbar = nullptr, *floss = nullptr, *fpartial = nullptr;
-  long fu_cap = 0, fud_cap = 0, fubar_cap = 0, fudbar_cap = 0, floss_cap = 0, fpartial_cap = 0;
-  // periodic pairs (vn_set_periodic): caller-owned inputs (rows i and i + nP pair), engine-owned work buffers; nP == 0: none
-  const float *pX = nullptr, *pD = nullptr;
-  long nP = 0;
+  // periodic pairs (vn_set_periodic): rows i and i + nP pair, nP = count, 2 nP rows; the directions in G while pgamma > 0
   double pgamma = 1.0, pbiDimVal = 1.0;
-  int pgrid = 0;                                  // workgroups of the paired rows' reverse pass
-  float *pu = nullptr, *pud = nullptr, *pubar = nullptr, *pudbar = nullptr, *ploss = nullptr, *ppartial = nullptr;
-  long pu_cap = 0, pud_cap = 0, pubar_cap = 0, pudbar_cap = 0, ploss_cap = 0, ppartial_cap = 0;
-  // observations (vn_set_observations): caller-owned inputs (n points in nO segments), engine-owned work buffers; nO == 0: none
-  const float *oX = nullptr, *oQ = nullptr, *oD = nullptr, *oval = nullptr, *owgt = nullptr;
+  // observations (vn_set_observations): n = rows points in nO = count segments
+  const float *oQ = nullptr, *oval = nullptr, *owgt = nullptr;
   const int* orowptr = nullptr;
-  long on = 0, nO = 0;
   double olambda = 0.0;
-  int ogrid = 0;                                  // workgroups of the observed points' reverse pass
-  float *ou = nullptr, *oud = nullptr, *oubar = nullptr, *oudbar = nullptr, *oloss = nullptr, *opartial = nullptr;
-  long ou_cap = 0, oud_cap = 0, oubar_cap = 0, oudbar_cap = 0, oloss_cap = 0, opartial_cap = 0;
   double* omisfit = nullptr;                      // device slot: the unweighted misfit O of the last evaluation
   // the vectors learnt next to the parameters, by LearntId: the nine coefficients of inverse mode (vn_set_coef_learn, vn_coef.hip),
   // which live on the device while they are learnt, and the engine-wide amplitudes of the batches' source bases
@@ -787,88 +789,104 @@ int fused_forward(vn_engine* h, const float* X, const float* G, long n, float* o
   return VN_OK;
 }
 
-// Boundary-flux rows (vn_set_flux_bc), on every route: value and normal derivative n . grad_x u of each row (the generic forward
-// kernel with the outward normals as tangent directions), the residual r = n . grad_x u + c u - l with its loss partials and
-// seeds, and with_grad the generic reverse pass into the engine's own partials.  Everything reads theta before the step's
-// reduction (which may fold the update in); *fx is what that reduction adds.  Without flux rows nothing is enqueued.
-int flux_pass(vn_engine* h, bool with_grad, VnFluxSum* fx) {
-  *fx = VnFluxSum();
-  if (h->nF <= 0) return VN_OK;
-  VnRows r{}, none{};
-  r.X = h->fX; r.G = h->fN; r.u = h->fu; r.ud = h->fud; r.n = h->nF;
-  HIPCHK(vn_generic_forward(h->net, h->theta, r, none, h->fwd_grid, h->stream));
+// ---- edge row sets (vn_edge.h) ------------------------------------------------------------------
+// The seed kernel of each kind: from the values in e.buf[EB_U] and the tangent stream ud (nullptr: values only) the loss
+// partials in e.buf[EB_LOSS] and, where asked for, the seeds ubar and udbar (nullptr: loss only / values only).
+hipError_t flux_seed(const vn_engine* h, const EdgeSet& e, const float* ud, float* ubar, float* udbar) {
   VnFluxSeedArgs a{};
-  a.u = h->fu; a.ud = h->fud; a.coef = h->fcoef; a.label = h->flabel; a.nF = h->nF;
+  a.u = e.buf[EB_U]; a.ud = ud; a.coef = h->fcoef; a.label = h->flabel; a.nF = e.count;
   a.biDimVal = (float)h->fbiDimVal; a.w0 = (float)h->w[0];
-  a.ubar = with_grad ? h->fubar : nullptr; a.udbar = with_grad ? h->fudbar : nullptr;
-  a.part = h->floss;
-  HIPCHK(vn_flux_seed_launch(a, h->stream));
-  if (with_grad) {
-    r.u = nullptr; r.ud = nullptr; r.ubar = h->fubar; r.udbar = h->fudbar;
-    HIPCHK(vn_generic_backward(h->net, h->theta, r, none, h->fpartial, h->fgrid, h->stream));
-    fx->partial = h->fpartial; fx->nparts = h->fgrid;
-  }
-  fx->loss = h->floss; fx->nlp = vn_flux_seed_blocks(h->nF); fx->nF = h->nF;
-  return VN_OK;
+  a.ubar = ubar; a.udbar = udbar; a.part = e.buf[EB_LOSS];
+  return vn_flux_seed_launch(a, h->stream);
 }
 
-// Periodic pairs (vn_set_periodic), on every route, the two-point version of flux_pass: value and derivative d . grad_x u of the
-// 2 nP paired rows, the jumps r0, r1 of each pair with their loss partials and seeds, and with_grad the generic reverse pass into
-// partials of their own -- launches of their own, so a step with flux rows only is untouched.  gamma == 0: value stream only.
-int periodic_pass(vn_engine* h, bool with_grad, VnFluxSum* px) {
-  *px = VnFluxSum();
-  if (h->nP <= 0) return VN_OK;
-  const bool deriv = h->pgamma > 0.0;
-  VnRows r{}, none{};
-  r.X = h->pX; r.G = deriv ? h->pD : nullptr; r.u = h->pu; r.ud = deriv ? h->pud : nullptr; r.n = 2 * h->nP;
-  HIPCHK(vn_generic_forward(h->net, h->theta, r, none, h->fwd_grid, h->stream));
+hipError_t periodic_seed(const vn_engine* h, const EdgeSet& e, const float* ud, float* ubar, float* udbar) {
   VnPeriodicSeedArgs a{};
-  a.u = h->pu; a.ud = r.ud; a.nP = h->nP; a.gamma = (float)h->pgamma;
+  a.u = e.buf[EB_U]; a.ud = ud; a.nP = e.count; a.gamma = (float)h->pgamma;
   a.biDimVal = (float)h->pbiDimVal; a.w0 = (float)h->w[0];
-  a.ubar = with_grad ? h->pubar : nullptr; a.udbar = with_grad && deriv ? h->pudbar : nullptr;
-  a.part = h->ploss;
-  HIPCHK(vn_periodic_seed_launch(a, h->stream));
-  if (with_grad) {
-    r.u = nullptr; r.ud = nullptr; r.ubar = h->pubar; r.udbar = a.udbar;
-    HIPCHK(vn_generic_backward(h->net, h->theta, r, none, h->ppartial, h->pgrid, h->stream));
-    px->partial = h->ppartial; px->nparts = h->pgrid;
-  }
-  px->loss = h->ploss; px->nlp = vn_periodic_seed_blocks(h->nP); px->nF = h->nP;
-  return VN_OK;
+  a.ubar = ubar; a.udbar = udbar; a.part = e.buf[EB_LOSS];
+  return vn_periodic_seed_launch(a, h->stream);
 }
 
-// Observations (vn_set_observations), on every route, the third pass of this kind: value and derivative g . grad_x u of the n
-// registered points, the residual of each observation's functional with its loss partial and the seeds of its points, and
-// with_grad the generic reverse pass into partials of their own -- launches of their own, so a step with flux rows or periodic
-// pairs only is untouched.  No directions registered: value stream only.
-int obs_pass(vn_engine* h, bool with_grad, VnObsSum* ox) {
-  *ox = VnObsSum();
-  if (h->nO <= 0) return VN_OK;
-  const bool deriv = h->oD != nullptr;
-  VnRows r{}, none{};
-  r.X = h->oX; r.G = h->oD; r.u = h->ou; r.ud = deriv ? h->oud : nullptr; r.n = h->on;
-  HIPCHK(vn_generic_forward(h->net, h->theta, r, none, h->fwd_grid, h->stream));
+hipError_t obs_seed(const vn_engine* h, const EdgeSet& e, const float* ud, float* ubar, float* udbar) {
   VnObsSeedArgs a{};
-  a.u = h->ou; a.ud = r.ud; a.q = h->oQ; a.rowptr = h->orowptr; a.value = h->oval; a.wgt = h->owgt;
-  a.nO = h->nO; a.lambda = (float)h->olambda;
-  a.ubar = with_grad ? h->oubar : nullptr; a.udbar = with_grad && deriv ? h->oudbar : nullptr;
-  a.part = h->oloss;
-  HIPCHK(vn_obs_seed_launch(a, h->stream));
+  a.u = e.buf[EB_U]; a.ud = ud; a.q = h->oQ; a.rowptr = h->orowptr; a.value = h->oval; a.wgt = h->owgt;
+  a.nO = e.count; a.lambda = (float)h->olambda;
+  a.ubar = ubar; a.udbar = udbar; a.part = e.buf[EB_LOSS];
+  return vn_obs_seed_launch(a, h->stream);
+}
+
+struct EdgeKind {
+  const char* noun;           // the subject of the refusal message
+  hipError_t (*seed)(const vn_engine*, const EdgeSet&, const float* ud, float* ubar, float* udbar);
+};
+constexpr EdgeKind kEdge[VN_EDGE_N] = {
+  {"boundary-flux rows", flux_seed},
+  {"periodic boundary pairs", periodic_seed},
+  {"observations", obs_seed},
+};
+
+// One set, on every route: value and derivative G . grad_x u of each of its rows (the generic forward kernel with the set's
+// directions as tangents; none registered: the value stream only), the kind's residuals with their loss partials and seeds,
+// and with_grad the generic reverse pass into the set's own partials -- launches of the set's own, so a step without it is
+// untouched.  Everything reads theta before the step's reduction (which may fold the update in); *sum is what that reduction
+// adds.  Nothing registered: nothing is enqueued.
+int edge_pass(vn_engine* h, int id, bool with_grad, VnEdgeSum* sum) {
+  *sum = VnEdgeSum();
+  const EdgeSet& e = h->es[id];
+  if (e.count <= 0) return VN_OK;
+  const bool deriv = e.G != nullptr;
+  VnRows r{}, none{};
+  r.X = e.X; r.G = e.G; r.u = e.buf[EB_U]; r.ud = deriv ? e.buf[EB_UD] : nullptr; r.n = e.rows;
+  HIPCHK(vn_generic_forward(h->net, h->theta, r, none, h->fwd_grid, h->stream));
+  float* ubar = with_grad ? e.buf[EB_UBAR] : nullptr;
+  float* udbar = with_grad && deriv ? e.buf[EB_UDBAR] : nullptr;
+  HIPCHK(kEdge[id].seed(h, e, r.ud, ubar, udbar));
   if (with_grad) {
-    r.u = nullptr; r.ud = nullptr; r.ubar = h->oubar; r.udbar = a.udbar;
-    HIPCHK(vn_generic_backward(h->net, h->theta, r, none, h->opartial, h->ogrid, h->stream));
-    ox->sum.partial = h->opartial; ox->sum.nparts = h->ogrid;
+    r.u = nullptr; r.ud = nullptr; r.ubar = ubar; r.udbar = udbar;
+    HIPCHK(vn_generic_backward(h->net, h->theta, r, none, e.buf[EB_PARTIAL], e.grid, h->stream));
+    sum->partial = e.buf[EB_PARTIAL]; sum->nparts = e.grid;
   }
-  ox->sum.loss = h->oloss; ox->sum.nlp = vn_obs_seed_blocks(h->nO); ox->sum.nF = h->nO;
-  ox->lambda = (float)h->olambda; ox->misfit = h->omisfit;
+  sum->loss = e.buf[EB_LOSS]; sum->nlp = vn_edge_seed_blocks(e.count); sum->count = e.count;
   return VN_OK;
 }
 
-// The boundary passes of a step, flux rows first, and the observations' pass: what its reduction adds.
+// The edge passes of a step in VnEdgeId order: what its reduction adds.
 int edge_passes(vn_engine* h, bool with_grad, VnEdgeSums* fx) {
-  if (int rc = flux_pass(h, with_grad, &fx->flux)) return rc;
-  if (int rc = periodic_pass(h, with_grad, &fx->per)) return rc;
-  return obs_pass(h, with_grad, &fx->obs);
+  for (int id = 0; id < VN_EDGE_N; ++id)
+    if (int rc = edge_pass(h, id, with_grad, &fx->set[id])) return rc;
+  if (h->es[VN_EDGE_OBS].count > 0) { fx->lambda = (float)h->olambda; fx->misfit = h->omisfit; }
+  return VN_OK;
+}
+
+// Registration, step 1: a call replaces the previous registration, also when it fails.
+void edge_drop(vn_engine* h, int id) {
+  EdgeSet& e = h->es[id];
+  e.X = e.G = nullptr;
+  lbfgs_invalidate(h);
+  e.count = e.rows = 0;
+}
+
+// Step 2, after the call's own argument checks: the edge passes run on the generic kernels, whatever route the interior term takes.
+int edge_check_route(const vn_engine* h, int id) {
+  if (h->route != Route::layered && vn_net_in_kernel_range(h->net)) return VN_OK;
+  return fail(VN_EUNSUPPORTED, "%s need a network of the hand-written kernels (<= %d hidden layers, width <= %d, "
+              "<= %d inputs, one activation); this one (%d layers, widest %d, %d inputs%s) runs on the layer-by-layer route "
+              "or the deep fused kernel only", kEdge[id].noun, VN_KMAX_LAYERS, VN_KMAX_WIDTH, VN_KMAX_DIN, h->net.L, h->net.hmax,
+              h->net.d_in, h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+}
+
+// Step 3: the reverse grid and the work buffers of `rows` rows and `count` seed threads (deriv: a direction is in play -- else no
+// tangent stream, no derivative seed).  The set stays unregistered until the caller sets X, G and count.
+int edge_alloc(vn_engine* h, int id, long rows, long count, bool deriv) {
+  EdgeSet& e = h->es[id];
+  const long tiles = (rows + 31) / 32;
+  e.rows = rows;
+  e.grid = (int)(tiles < h->ncu ? tiles : h->ncu);
+  const long need[EB_N] = {rows, deriv ? rows : 0, rows, deriv ? rows : 0, vn_edge_seed_blocks(count), (long)e.grid * h->net.P};
+  for (int b : {EB_U, EB_UBAR, EB_UD, EB_UDBAR, EB_LOSS, EB_PARTIAL})
+    if (int rc = ensure(&e.buf[b], &e.cap[b], need[b])) return rc;
+  return VN_OK;
 }
 
 // Loss components and loss field of a batch that carries a de-duplication map (vn_set_dedup), without the row-wise forward: (u, grad u)
@@ -1318,11 +1336,13 @@ int vn_destroy(vn_engine* h) {
   if (h->comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(h->stream); (void)g_rccl.CommDestroy(h->comm); h->comm = nullptr; }
   void* ptrs[] = {h->theta, h->m, h->v, h->snap, h->theta64, h->gradbuf_int, h->lossbuf, h->partial, h->feN, h->fedNt,
                   h->feW, h->u, h->ud, h->ubar, h->udbar, h->ub, h->ubar_b, h->losspart, h->fused_losspart, h->stamps, h->dd_uv, h->dd_su, h->dd_sg, h->dd_partial,
-                  h->dd_losspart, h->rx_seff, h->nd_A, h->wt_lvec, h->wt_omega, h->wt_stat, h->tp_losspart, h->f16_stash, h->fu, h->fud, h->fubar, h->fudbar, h->floss, h->fpartial, h->pu, h->pud, h->pubar, h->pudbar, h->ploss, h->ppartial,
-                  h->ou, h->oud, h->oubar, h->oudbar, h->oloss, h->opartial, h->omisfit,
+                  h->dd_losspart, h->rx_seff, h->nd_A, h->wt_lvec, h->wt_omega, h->wt_stat, h->tp_losspart, h->f16_stash, h->omisfit,
                   h->lb.ring, h->lb.theta_k, h->lb.g_k, h->lb.d, h->lb.part, h->lb.G, h->lb.coef, h->lb.meta};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  for (EdgeSet& e : h->es)
+    for (float* p : e.buf)
+      if (p) (void)hipFree(p);
   if (h->lb.out) (void)hipHostFree(h->lb.out);
   vn_obj64_free(h->o64);
   for (int id = 0; id < LV_N; ++id) learnt_free(h, id);
@@ -1908,58 +1928,34 @@ int vn_set_flux_bc(vn_engine* h, const float* X, const float* normal, const floa
                    double biDimVal) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (nF < 0) return fail(VN_EINVAL, "negative number of flux rows");
-  h->fX = h->fN = h->fcoef = h->flabel = nullptr;   // a call replaces the previous registration, also when it fails
-  lbfgs_invalidate(h);
-  h->nF = 0;
+  edge_drop(h, VN_EDGE_FLUX);
+  h->fcoef = h->flabel = nullptr;
   if (nF == 0 || !X) return VN_OK;
   if (!normal || !coef || !label) return fail(VN_EINVAL, "null argument");
-  // the flux pass runs on the generic kernels, whatever route the interior term takes
-  if (h->route == Route::layered || !vn_net_in_kernel_range(h->net))
-    return fail(VN_EUNSUPPORTED, "boundary-flux rows need a network of the hand-written kernels (<= %d hidden layers, width <= %d, "
-                "<= %d inputs, one activation); this one (%d layers, widest %d, %d inputs%s) runs on the layer-by-layer route "
-                "or the deep fused kernel only", VN_KMAX_LAYERS, VN_KMAX_WIDTH, VN_KMAX_DIN, h->net.L, h->net.hmax, h->net.d_in,
-                h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+  if (int rc = edge_check_route(h, VN_EDGE_FLUX)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
-  const long tiles = (nF + 31) / 32;
-  const int fgrid = (int)(tiles < h->ncu ? tiles : h->ncu);
-  if (int rc = ensure(&h->fu, &h->fu_cap, nF)) return rc;
-  if (int rc = ensure(&h->fud, &h->fud_cap, nF)) return rc;
-  if (int rc = ensure(&h->fubar, &h->fubar_cap, nF)) return rc;
-  if (int rc = ensure(&h->fudbar, &h->fudbar_cap, nF)) return rc;
-  if (int rc = ensure(&h->floss, &h->floss_cap, vn_flux_seed_blocks(nF))) return rc;
-  if (int rc = ensure(&h->fpartial, &h->fpartial_cap, (long)fgrid * h->net.P)) return rc;
-  h->fX = X; h->fN = normal; h->fcoef = coef; h->flabel = label; h->nF = nF; h->fbiDimVal = biDimVal; h->fgrid = fgrid;
+  if (int rc = edge_alloc(h, VN_EDGE_FLUX, nF, nF, true)) return rc;
+  EdgeSet& e = h->es[VN_EDGE_FLUX];
+  e.X = X; e.G = normal; e.count = nF;
+  h->fcoef = coef; h->flabel = label; h->fbiDimVal = biDimVal;
   return VN_OK;
 }
 
 int vn_set_periodic(vn_engine* h, const float* X, const float* dir, int64_t nP, double gamma, double biDimVal) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (nP < 0) return fail(VN_EINVAL, "negative number of periodic pairs");
-  h->pX = h->pD = nullptr;   // a call replaces the previous registration, also when it fails
-  lbfgs_invalidate(h);
-  h->nP = 0;
+  edge_drop(h, VN_EDGE_PERIODIC);
   if (nP == 0 || !X) return VN_OK;
   if (!dir) return fail(VN_EINVAL, "null argument");
   if (!(gamma >= 0.0) || !std::isfinite(gamma))
     return fail(VN_EINVAL, "periodic pairs: the derivative weight gamma = %g must be finite and >= 0", gamma);
-  // the periodic pass runs on the generic kernels, whatever route the interior term takes
-  if (h->route == Route::layered || !vn_net_in_kernel_range(h->net))
-    return fail(VN_EUNSUPPORTED, "periodic boundary pairs need a network of the hand-written kernels (<= %d hidden layers, width <= %d, "
-                "<= %d inputs, one activation); this one (%d layers, widest %d, %d inputs%s) runs on the layer-by-layer route "
-                "or the deep fused kernel only", VN_KMAX_LAYERS, VN_KMAX_WIDTH, VN_KMAX_DIN, h->net.L, h->net.hmax, h->net.d_in,
-                h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+  if (int rc = edge_check_route(h, VN_EDGE_PERIODIC)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
-  const long rows = 2 * nP, tiles = (rows + 31) / 32;
-  const int pgrid = (int)(tiles < h->ncu ? tiles : h->ncu);
-  if (int rc = ensure(&h->pu, &h->pu_cap, rows)) return rc;
-  if (int rc = ensure(&h->pubar, &h->pubar_cap, rows)) return rc;
-  if (gamma > 0.0) {                                  // gamma == 0: no tangent stream, no derivative seed
-    if (int rc = ensure(&h->pud, &h->pud_cap, rows)) return rc;
-    if (int rc = ensure(&h->pudbar, &h->pudbar_cap, rows)) return rc;
-  }
-  if (int rc = ensure(&h->ploss, &h->ploss_cap, vn_periodic_seed_blocks(nP))) return rc;
-  if (int rc = ensure(&h->ppartial, &h->ppartial_cap, (long)pgrid * h->net.P)) return rc;
-  h->pX = X; h->pD = dir; h->nP = nP; h->pgamma = gamma; h->pbiDimVal = biDimVal; h->pgrid = pgrid;
+  const bool deriv = gamma > 0.0;                     // gamma == 0: no tangent stream, no derivative seed
+  if (int rc = edge_alloc(h, VN_EDGE_PERIODIC, 2 * nP, nP, deriv)) return rc;
+  EdgeSet& e = h->es[VN_EDGE_PERIODIC];
+  e.X = X; e.G = deriv ? dir : nullptr; e.count = nP;
+  h->pgamma = gamma; h->pbiDimVal = biDimVal;
   return VN_OK;
 }
 
@@ -1967,10 +1963,9 @@ int vn_set_observations(vn_engine* h, const float* X, const float* q, const floa
                         const float* wgt, int64_t n, int64_t nO, double lambda) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (n < 0 || nO < 0) return fail(VN_EINVAL, "negative number of observations or of observed points");
-  h->oX = h->oQ = h->oD = h->oval = h->owgt = nullptr;   // a call replaces the previous registration, also when it fails
+  edge_drop(h, VN_EDGE_OBS);
+  h->oQ = h->oval = h->owgt = nullptr;
   h->orowptr = nullptr;
-  lbfgs_invalidate(h);
-  h->nO = h->on = 0;
   if (nO == 0) return VN_OK;
   if (!X || !value) return fail(VN_EINVAL, "null argument");
   if (!(lambda >= 0.0) || !std::isfinite(lambda))
@@ -1980,12 +1975,7 @@ int vn_set_observations(vn_engine* h, const float* X, const float* q, const floa
     return fail(VN_EINVAL, "observations: point sensors (rowptr == NULL) have one point each, but n = %lld and nO = %lld",
                 (long long)n, (long long)nO);
   if (n < nO) return fail(VN_EINVAL, "observations: %lld points cannot fill %lld non-empty segments", (long long)n, (long long)nO);
-  // the observations' pass runs on the generic kernels, whatever route the interior term takes
-  if (h->route == Route::layered || !vn_net_in_kernel_range(h->net))
-    return fail(VN_EUNSUPPORTED, "observations need a network of the hand-written kernels (<= %d hidden layers, width <= %d, "
-                "<= %d inputs, one activation); this one (%d layers, widest %d, %d inputs%s) runs on the layer-by-layer route "
-                "or the deep fused kernel only", VN_KMAX_LAYERS, VN_KMAX_WIDTH, VN_KMAX_DIN, h->net.L, h->net.hmax, h->net.d_in,
-                h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+  if (int rc = edge_check_route(h, VN_EDGE_OBS)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   // rowptr indexes device memory in the seed kernel: validated once, here (a registration call may synchronise), so that an
   // inconsistent registration is an error code and never a GPU fault.  The reads assume nO + 1 entries of rowptr.
@@ -1995,22 +1985,14 @@ int vn_set_observations(vn_engine* h, const float* X, const float* q, const floa
   if (bad)
     return fail(VN_EINVAL, "inconsistent observations: %d violation(s) (need rowptr[0] = 0 < rowptr[1] < ... < rowptr[nO] = n, no empty "
                            "segment; value finite; wgt finite and >= 0; q and dir finite)", bad);
-  const long tiles = (n + 31) / 32;
-  const int ogrid = (int)(tiles < h->ncu ? tiles : h->ncu);
-  if (int rc = ensure(&h->ou, &h->ou_cap, n)) return rc;
-  if (int rc = ensure(&h->oubar, &h->oubar_cap, n)) return rc;
-  if (dir) {                                          // no directions: no tangent stream, no derivative seed
-    if (int rc = ensure(&h->oud, &h->oud_cap, n)) return rc;
-    if (int rc = ensure(&h->oudbar, &h->oudbar_cap, n)) return rc;
-  }
-  if (int rc = ensure(&h->oloss, &h->oloss_cap, vn_obs_seed_blocks(nO))) return rc;
-  if (int rc = ensure(&h->opartial, &h->opartial_cap, (long)ogrid * h->net.P)) return rc;
+  if (int rc = edge_alloc(h, VN_EDGE_OBS, n, nO, dir != nullptr)) return rc;   // no directions: no tangent stream, no derivative seed
   if (!h->omisfit) {
     HIPCHK(hipMalloc((void**)&h->omisfit, sizeof(double)));
     HIPCHK(hipMemsetAsync(h->omisfit, 0, sizeof(double), h->stream));
   }
-  h->oX = X; h->oQ = q; h->oD = dir; h->orowptr = rowptr; h->oval = value; h->owgt = wgt;
-  h->on = n; h->nO = nO; h->olambda = lambda; h->ogrid = ogrid;
+  EdgeSet& e = h->es[VN_EDGE_OBS];
+  e.X = X; e.G = dir; e.count = nO;
+  h->oQ = q; h->orowptr = rowptr; h->oval = value; h->owgt = wgt; h->olambda = lambda;
   return VN_OK;
 }
 
@@ -2025,7 +2007,7 @@ int vn_set_obs_weight(vn_engine* h, double lambda) {
 
 int vn_get_obs_misfit(vn_engine* h, double* misfit) {
   if (!h || !misfit) return fail(VN_EINVAL, "null argument");
-  if (h->nO <= 0) return fail(VN_ESTATE, "vn_get_obs_misfit: no observations are registered (vn_set_observations)");
+  if (h->es[VN_EDGE_OBS].count <= 0) return fail(VN_ESTATE, "vn_get_obs_misfit: no observations are registered (vn_set_observations)");
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipMemcpyAsync(misfit, h->omisfit, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -2337,10 +2319,11 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   p.Nrow = b.Nrow; p.dNtrow = b.dNtrow; p.detJv = b.detJv; p.detJ = b.detJ;
   p.n_k = b.n_k; p.q = h->cfg.integ_num; p.td = h->cfg.time_dependent;
   p.Xb = bi_x(h, b); p.label = bi_y(h, b); p.nB = h->nB; p.bDof = h->bDof; p.biDimVal = h->biDimVal;
-  p.Xf = h->fX; p.Nf = h->fN; p.fcoef = h->fcoef; p.flabel = h->flabel; p.nF = h->nF; p.fbiDimVal = h->fbiDimVal;
-  p.Xp = h->pX; p.Dp = h->pD; p.nP = h->nP; p.pgamma = h->pgamma; p.pbiDimVal = h->pbiDimVal;
-  p.Xo = h->oX; p.Qo = h->oQ; p.Do = h->oD; p.orowptr = h->orowptr; p.ovalue = h->oval; p.owgt = h->owgt;
-  p.on = h->on; p.nO = h->nO; p.olambda = h->olambda; p.omisfit = h->omisfit;
+  const EdgeSet &ef = h->es[VN_EDGE_FLUX], &ep = h->es[VN_EDGE_PERIODIC], &eo = h->es[VN_EDGE_OBS];
+  p.Xf = ef.X; p.Nf = ef.G; p.fcoef = h->fcoef; p.flabel = h->flabel; p.nF = ef.count; p.fbiDimVal = h->fbiDimVal;
+  p.Xp = ep.X; p.Dp = ep.G; p.nP = ep.count; p.pgamma = h->pgamma; p.pbiDimVal = h->pbiDimVal;
+  p.Xo = eo.X; p.Qo = h->oQ; p.Do = eo.G; p.orowptr = h->orowptr; p.ovalue = h->oval; p.owgt = h->owgt;
+  p.on = eo.rows; p.nO = eo.count; p.olambda = h->olambda; p.omisfit = h->omisfit;
   p.w[0] = h->w[0]; p.w[1] = h->w[1]; p.w[2] = h->w[2];
   p.react = b.react.on ? 1 : 0; p.rate = b.react.stream; std::copy(b.react.c, b.react.c + 3, p.coef);
   p.nlflux = b.nlflux.on ? 1 : 0; p.phi = b.nlflux.stream; std::copy(b.nlflux.c, b.nlflux.c + 3, p.fcoef3);

@@ -9,12 +9,13 @@
 //                       with accR_j, accF_j the CSR sums of vn_react_gather_kernel / vn_nlflux_gather_kernel and gs_j the dot product
 //                       grad u_j . seed_g[j,:] of vn_nldiff_point_kernel (unscaled seed_g), which those kernels store: no second walk.
 // Both reductions are grid-stride loops over a capped grid, so every partial covers a fixed set of rows; fp32 accumulators per
-// thread, for the masked entries only; per block the order of block_sum (vn_generic.hip); one [blocks, 9] partial array, folded
+// thread, for the masked entries only; per block the order of block_sum (vn_blocksum.h); one [blocks, 9] partial array, folded
 // in fp64 in index order by the single block of vn_coef_apply_kernel.  No atomics, plain vector stores: two evaluations give the
 // same bits.  HBM-bound: at most five 4-byte streams per row (u, s, rate, phi, A).
 #include <cstdint>
 #include <initializer_list>
 
+#include "vn_blocksum.h"
 #include "vn_coef.h"
 
 namespace {
@@ -23,16 +24,6 @@ typedef float f32x4t __attribute__((ext_vector_type(4)));
 constexpr int TB = 256;
 
 __device__ __forceinline__ f32x4t load4(const float* p, long i) { return reinterpret_cast<const f32x4t*>(p)[i]; }
-
-// the order of block_sum in vn_generic.hip: a shuffle tree per wave, then the four wave sums in wave order
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
 
 // acc[3 g + m] += w x^(m + first) for the masked entries of group g
 __device__ __forceinline__ void add_powers(float* acc, unsigned mask, int g, float w, float x, bool from_one) {

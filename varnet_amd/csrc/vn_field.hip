@@ -11,10 +11,11 @@
 //   vn_fldgrad_rows_kernel<DIM>   the J sums.  Grid (row blocks <= 256, ceil(J / 8)): a workgroup carries eight streams in eight
 //                                 accumulators per thread (compile-time indices: no scratch at any J), a grid-stride loop over a
 //                                 capped grid so every partial covers a fixed set of rows, per block the order of block_sum
-//                                 (vn_generic.hip).  Per row: the seed, one 16-byte (u, grad u) record, DIM floats per stream.
+//                                 (vn_blocksum.h).  Per row: the seed, one 16-byte (u, grad u) record, DIM floats per stream.
 // One [blocks, J] partial array.  No atomics, plain vector stores: two evaluations give the same bits.
 #include <cstdint>
 
+#include "vn_blocksum.h"
 #include "vn_field.h"
 
 namespace {
@@ -22,16 +23,6 @@ namespace {
 typedef float f32x4t __attribute__((ext_vector_type(4)));
 constexpr int TB = 256;
 constexpr int JG = VN_FLD_JG;
-
-// the order of block_sum in vn_generic.hip: a shuffle tree per wave, then the four wave sums in wave order
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
 
 // the learnt streams of this workgroup's group of eight, as bits 0..7
 __device__ __forceinline__ unsigned group_mask(const VnFldGradArgs& a, int j0) {

@@ -7,8 +7,8 @@
 // form in oracle/tangent_ref.py and follows the reference graph TFModel.py:536 (input gradient),
 // :653-661 (weak-form integrand), :709 (parameter gradient).
 #include "vn_internal.h"
-#include "vn_flux.h"
-#include "vn_periodic.h"
+#include "vn_blocksum.h"
+#include "vn_edge.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -326,15 +326,6 @@ __global__ __launch_bounds__(NTHREADS) void vn_generic_bwd_kernel(VnNet net, con
 // --------------------------------------------------------------------------------------
 // weak-form epilogue: (u, udot) -> R_k, lossVec, loss partials, backward seeds
 // --------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
 __global__ __launch_bounds__(NTHREADS) void vn_seed_kernel(VnSeedArgs a) {
   __shared__ float red[4];
   const long k = (long)blockIdx.x * NTHREADS + threadIdx.x;
@@ -400,26 +391,6 @@ __global__ __launch_bounds__(NTHREADS) void vn_seed_kernel(VnSeedArgs a) {
   }
 }
 
-// Boundary-flux rows: one thread per row, one loss partial per block (folded by vn_reduce_kernel in a fixed order).
-constexpr int FLUX_TB = 256;
-__global__ __launch_bounds__(FLUX_TB) void vn_flux_seed_kernel(VnFluxSeedArgs a) {
-  __shared__ float red[4];
-  const long k = (long)blockIdx.x * FLUX_TB + threadIdx.x;
-  float e2 = 0.f;
-  if (k < a.nF) {
-    const float c = a.coef[k];
-    const float r = a.ud[k] + c * a.u[k] - a.label[k];
-    e2 = a.biDimVal * r * r;
-    if (a.ubar) {
-      const float s = 2.f * a.w0 * a.biDimVal / (float)a.nF;
-      a.udbar[k] = s * r;
-      a.ubar[k] = s * c * r;
-    }
-  }
-  const float t = block_sum(e2, red);
-  if (threadIdx.x == 0) a.part[blockIdx.x] = t;
-}
-
 // grad[p] = sum over workgroup partials in a fixed order; block 0 also folds the loss partials.
 // A block owns 64 consecutive parameters; its 16 waves each sum every 16th partial (coalesced 256-B
 // rows, 16 loads in flight per lane), then the 16 sub-sums are added in wave order -> bitwise
@@ -443,8 +414,7 @@ __global__ __launch_bounds__(64 * RED_GROUPS) void vn_reduce_kernel(const float*
                                                                   int P, const float* __restrict__ losspart,
                                                                   int nlp, long bDof, long nB, float w0, float w1,
                                                                   float w2, float* __restrict__ gradbuf, VnOptArgs opt,
-                                                                  VnFluxSum flux, VnFluxSum per, VnFluxSum obs,
-                                                                  float olambda, double* __restrict__ omisfit) {
+                                                                  VnEdgeSums edge) {
   __shared__ float sub[RED_GROUPS][64];
   const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
   const int p = blockIdx.x * 64 + lane;
@@ -452,14 +422,20 @@ __global__ __launch_bounds__(64 * RED_GROUPS) void vn_reduce_kernel(const float*
   // [10,20,30] net is 50 us), so every global load is issued before anything waits: the optimizer state of this block's
   // parameters does not depend on the sums and is fetched first, the partials of a lane 16 at a time.
   const bool upd = grp == 0 && p < P && opt.kind >= 0;
+  // (likewise the edge sets' operands: copied here they are fetched with the other arguments, in one batch, instead of one
+  // dependent scalar load in front of each set's loop -- 0.3 us per registered set on a 37 us step)
+  VnEdgeSum es[VN_EDGE_N];
+#pragma unroll
+  for (int e = 0; e < VN_EDGE_N; ++e) es[e] = edge.set[e];
+  double* const omisfit = edge.misfit;
   float th = 0.f, mo = 0.f, vo = 0.f;
   if (upd) { th = opt.theta[p]; mo = opt.m[p]; vo = opt.v[p]; }
   float acc = 0.f;
   if (p < P) {
     add_parts(partial, nparts, P, p, grp, acc);
-    add_parts(flux.partial, flux.nparts, P, p, grp, acc);     // boundary-flux rows (none: nparts 0)
-    add_parts(per.partial, per.nparts, P, p, grp, acc);       // periodic pairs (none: nparts 0)
-    add_parts(obs.partial, obs.nparts, P, p, grp, acc);       // observations (none: nparts 0)
+#pragma unroll
+    for (int e = 0; e < VN_EDGE_N; ++e)                       // the edge row sets in VnEdgeId order (none: nparts 0)
+      add_parts(es[e].partial, es[e].nparts, P, p, grp, acc);
   }
   sub[grp][lane] = acc;
   __syncthreads();
@@ -518,53 +494,32 @@ __global__ __launch_bounds__(64 * RED_GROUPS) void vn_reduce_kernel(const float*
         for (int v = 1; v < RED_GROUPS; ++v) { t0 += lsub[v][0]; t1 += lsub[v][1]; t2 += lsub[v][2]; }
       }
     }
-    // boundary-flux rows: wave 2 folds their per-block partials (lane-strided, fixed shuffle tree) into the BC component's
-    // second mean (block-uniform: flux.nF is a kernel argument)
-    __shared__ double fmean;
-    if (flux.nF > 0) {
-      if (grp == 2) {
-        double tf = 0.0;
-        for (int g = lane; g < flux.nlp; g += 64) tf += (double)flux.loss[g];
+    // edge row sets: wave 2 + e folds the per-block partials of set e (lane-strided, fixed shuffle tree) into its mean over the
+    // set's own count (block-uniform: the counts are kernel arguments)
+    __shared__ double emean[VN_EDGE_N];
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) tf += __shfl_down(tf, o, 64);
-        if (lane == 0) fmean = tf / (double)flux.nF;
-      }
-      __syncthreads();
-    }
-    // periodic pairs: wave 3, the same fold, the mean over their own count of pairs (block-uniform: per.nF is a kernel argument)
-    __shared__ double pmean;
-    if (per.nF > 0) {
-      if (grp == 3) {
-        double tp = 0.0;
-        for (int g = lane; g < per.nlp; g += 64) tp += (double)per.loss[g];
+    for (int e = 0; e < VN_EDGE_N; ++e) {
+      if (es[e].count > 0) {
+        if (grp == 2 + e) {
+          double t = 0.0;
+          for (int g = lane; g < es[e].nlp; g += 64) t += (double)es[e].loss[g];
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) tp += __shfl_down(tp, o, 64);
-        if (lane == 0) pmean = tp / (double)per.nF;
+          for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
+          if (lane == 0) emean[e] = t / (double)es[e].count;
+        }
+        __syncthreads();
       }
-      __syncthreads();
-    }
-    // observations: wave 4, the same fold, the unweighted misfit O = sum / nO (block-uniform: obs.nF is a kernel argument)
-    __shared__ double omean;
-    if (obs.nF > 0) {
-      if (grp == 4) {
-        double to = 0.0;
-        for (int g = lane; g < obs.nlp; g += 64) to += (double)obs.loss[g];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) to += __shfl_down(to, o, 64);
-        if (lane == 0) omean = to / (double)obs.nF;
-      }
-      __syncthreads();
     }
     if (grp == 1 && lane == 0) {
       const double var = t0;
       double bc = bDof > 0 ? t1 / (double)bDof : 0.0;                     // reduce_mean, TFModel.py:645
-      if (flux.nF > 0) bc += fmean;                                       // + mean_F[biDimVal r^2] (vn_set_flux_bc)
-      if (per.nF > 0) bc += pmean;                                        // + mean_P[biDimVal (r0^2 + gamma r1^2)] (vn_set_periodic)
+      if (es[VN_EDGE_FLUX].count > 0) bc += emean[VN_EDGE_FLUX];          // + mean_F[biDimVal r^2] (vn_set_flux_bc)
+      if (es[VN_EDGE_PERIODIC].count > 0) bc += emean[VN_EDGE_PERIODIC];  // + mean_P[biDimVal (r0^2 + gamma r1^2)] (vn_set_periodic)
       const double ic = (nB - bDof) > 0 ? t2 / (double)(nB - bDof) : 0.0; // TFModel.py:648
       double l64 = w0 * bc + w1 * ic + w2 * var;                          // TFModel.py:666
-      if (obs.nF > 0) {                                                   // + lambda O (vn_set_observations)
-        l64 += (double)olambda * omean;
-        *omisfit = omean;
+      if (es[VN_EDGE_OBS].count > 0) {                              // + lambda O (vn_set_observations)
+        l64 += (double)edge.lambda * emean[VN_EDGE_OBS];
+        *omisfit = emean[VN_EDGE_OBS];
       }
       const float loss = (float)l64;
       gradbuf[P + 0] = loss;
@@ -666,32 +621,14 @@ hipError_t vn_reduce_launch(const float* partial, int nparts, int P, const float
                             VnOptArgs opt, const VnEdgeSums& sums) {
   const int grid = (P + 63) / 64;
   hipLaunchKernelGGL(vn_reduce_kernel, dim3(grid > 0 ? grid : 1), dim3(64 * RED_GROUPS), 0, s, partial, nparts, P,
-                     losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, opt, sums.flux, sums.per, sums.obs.sum,
-                     sums.obs.lambda, sums.obs.misfit);
+                     losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, opt, sums);
   return hipGetLastError();
-}
-
-hipError_t vn_reduce_launch(const float* partial, int nparts, int P, const float* losspart, int nlossparts,
-                            long bDof, long nB, float w0, float w1, float w2, float* gradbuf, hipStream_t s,
-                            VnOptArgs opt, const VnFluxSum& flux) {
-  VnEdgeSums sums;
-  sums.flux = flux;
-  return vn_reduce_launch(partial, nparts, P, losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, s, opt, sums);
 }
 
 hipError_t vn_reduce_launch(const float* partial, int nparts, int P, const float* losspart, int nlossparts,
                             long bDof, long nB, float w0, float w1, float w2, float* gradbuf, hipStream_t s,
                             VnOptArgs opt) {
-  return vn_reduce_launch(partial, nparts, P, losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, s, opt, VnFluxSum());
-}
-
-int vn_flux_seed_blocks(long nF) { return (int)((nF + FLUX_TB - 1) / FLUX_TB); }
-
-hipError_t vn_flux_seed_launch(const VnFluxSeedArgs& a, hipStream_t s) {
-  const int grid = vn_flux_seed_blocks(a.nF);
-  if (grid <= 0) return hipSuccess;
-  hipLaunchKernelGGL(vn_flux_seed_kernel, dim3(grid), dim3(FLUX_TB), 0, s, a);
-  return hipGetLastError();
+  return vn_reduce_launch(partial, nparts, P, losspart, nlossparts, bDof, nB, w0, w1, w2, gradbuf, s, opt, VnEdgeSums());
 }
 
 hipError_t vn_adam_launch(float* theta, float* m, float* v, const float* grad, int P, float lr_t, float b1,

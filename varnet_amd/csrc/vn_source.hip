@@ -8,13 +8,14 @@
 //   vn_source_mix_kernel     s_mix = s0 + Phi^T a, which every kernel of the step then reads in place of the batch's source;
 //   vn_srcgrad_rows_kernel   the J sums.  Grid (row blocks <= 256, ceil(J / 8)): a workgroup carries eight streams in eight
 //                            accumulators per thread (compile-time indices: no scratch at any J), a grid-stride loop over a capped
-//                            grid so every partial covers a fixed set of rows, per block the order of block_sum (vn_generic.hip).
+//                            grid so every partial covers a fixed set of rows, per block the order of block_sum (vn_blocksum.h).
 //                            The seed stream is re-read once per group of eight: (J + 2 ceil(J / 8)) nT floats at most.
 // One [blocks, J] partial array, folded in fp64 in index order by the single block of vn_source_apply_kernel, which also takes
 // the Adam step and clamps.  No atomics, plain vector stores: two evaluations give the same bits.
 #include <cstdint>
 #include <initializer_list>
 
+#include "vn_blocksum.h"
 #include "vn_source.h"
 
 namespace {
@@ -24,16 +25,6 @@ constexpr int TB = 256;
 constexpr int JG = VN_SRC_JG;
 
 __device__ __forceinline__ f32x4t load4(const float* p, long i) { return reinterpret_cast<const f32x4t*>(p)[i]; }
-
-// the order of block_sum in vn_generic.hip: a shuffle tree per wave, then the four wave sums in wave order
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
 
 __global__ __launch_bounds__(TB) void vn_source_mix_kernel(VnSrcMixArgs a) {
   const long r = (long)blockIdx.x * TB + threadIdx.x;

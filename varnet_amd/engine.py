@@ -447,45 +447,45 @@ class VNEngine:
         self._keep[('bbic', batch)] = (biInput, biLabel)
         self._ck(self.lib.vn_set_batch_bic(self.h, batch, _ptr(biInput), _ptr(biLabel)))
 
+    def _set_edge(self, key, fn, tensors, *scalars):
+        """One registration call of an edge row set (vn_edge.h): fn(h, pointers of `tensors`, *scalars).  tensors None clears the
+        set; else the device tensors are kept alive under `key` in place of the previous registration's."""
+        if tensors is None:
+            self._keep[key] = None
+            self._ck(fn(self.h, *[None] * (len(fn.argtypes) - 1 - len(scalars)), *scalars))
+            return
+        old = self._keep.pop(key, None)
+        try:
+            self._ck(fn(self.h, *[_ptr(x) for x in tensors], *scalars))
+        finally:
+            del old           # the engine dropped the previous registration before checking this one
+        self._keep[key] = tensors
+
     def set_flux_bc(self, X=None, normal=None, coef=None, label=None, biDimVal=1.0):
         """Register (or, with X=None, clear) the boundary-flux rows of Neumann / Robin edges (vn_set_flux_bc): X [nF, inpDim],
         outward unit normals [nF, dim], coef = b/a [nF], label = g/a [nF]."""
         if X is None or len(X) == 0:
-            self._keep['flux'] = None
-            self._ck(self.lib.vn_set_flux_bc(self.h, None, None, None, None, 0, float(biDimVal)))
-            return
+            return self._set_edge('flux', self.lib.vn_set_flux_bc, None, 0, float(biDimVal))
         X, normal = self.dev(X), self.dev(normal)
         coef, label = self.dev(np.reshape(coef, -1)), self.dev(np.reshape(label, -1))
         nF = X.shape[0]
         # the ABI carries pointers only: the lengths every kernel of the pass relies on are checked here
         assert X.shape == (nF, self.inpDim) and normal.shape == (nF, self.dim), (tuple(X.shape), tuple(normal.shape))
         assert coef.numel() == nF and label.numel() == nF
-        old = self._keep.pop('flux', None)
-        try:
-            self._ck(self.lib.vn_set_flux_bc(self.h, _ptr(X), _ptr(normal), _ptr(coef), _ptr(label), nF, float(biDimVal)))
-        finally:
-            del old           # the engine dropped the previous registration before checking this one
-        self._keep['flux'] = (X, normal, coef, label)
+        self._set_edge('flux', self.lib.vn_set_flux_bc, (X, normal, coef, label), nF, float(biDimVal))
 
     def set_periodic(self, X=None, dir=None, gamma=1.0, biDimVal=1.0):
         """Register (or, with X=None, clear) the periodic boundary pairs (vn_set_periodic): X [2 nP, inpDim] and unit directions
         dir [2 nP, dim], rows i and i + nP being the two images of one point with the same direction; gamma >= 0 weights the
         derivative match (0: values only)."""
         if X is None or len(X) == 0:
-            self._keep['periodic'] = None
-            self._ck(self.lib.vn_set_periodic(self.h, None, None, 0, float(gamma), float(biDimVal)))
-            return
+            return self._set_edge('periodic', self.lib.vn_set_periodic, None, 0, float(gamma), float(biDimVal))
         X, dir = self.dev(X), self.dev(dir)
         rows = X.shape[0]
         # the ABI carries pointers only: the lengths every kernel of the pass relies on are checked here
         assert rows % 2 == 0, rows
         assert X.shape == (rows, self.inpDim) and dir.shape == (rows, self.dim), (tuple(X.shape), tuple(dir.shape))
-        old = self._keep.pop('periodic', None)
-        try:
-            self._ck(self.lib.vn_set_periodic(self.h, _ptr(X), _ptr(dir), rows // 2, float(gamma), float(biDimVal)))
-        finally:
-            del old           # the engine dropped the previous registration before checking this one
-        self._keep['periodic'] = (X, dir)
+        self._set_edge('periodic', self.lib.vn_set_periodic, (X, dir), rows // 2, float(gamma), float(biDimVal))
 
     def set_observations(self, X=None, value=None, q=None, dir=None, rowptr=None, wgt=None, weight=1.0):
         """Register (or, with X=None, clear) the observations (vn_set_observations): points X [n, inpDim] in nO segments
@@ -494,9 +494,7 @@ class VNEngine:
         weight = lambda, the factor of the misfit O = mean_i[wgt_i r_i^2] in the loss."""
         t = self.torch
         if X is None or len(X) == 0:
-            self._keep['obs'] = None
-            self._ck(self.lib.vn_set_observations(self.h, None, None, None, None, None, None, 0, 0, float(weight)))
-            return
+            return self._set_edge('obs', self.lib.vn_set_observations, None, 0, 0, float(weight))
         X, value = self.dev(X), self.dev(value).reshape(-1)
         n, nO = X.shape[0], value.shape[0]
         q = None if q is None else self.dev(q).reshape(-1)
@@ -511,13 +509,7 @@ class VNEngine:
         assert dir is None or dir.shape == (n, self.dim), (tuple(dir.shape), n)
         assert wgt is None or wgt.shape[0] == nO, (tuple(wgt.shape), nO)
         assert (rowptr.numel() == nO + 1) if rowptr is not None else (n == nO), (n, nO)
-        old = self._keep.pop('obs', None)
-        try:
-            self._ck(self.lib.vn_set_observations(self.h, _ptr(X), _ptr(q), _ptr(dir), _ptr(rowptr), _ptr(value), _ptr(wgt), n, nO,
-                                                  float(weight)))
-        finally:
-            del old           # the engine dropped the previous registration before checking this one
-        self._keep['obs'] = (X, q, dir, rowptr, value, wgt)
+        self._set_edge('obs', self.lib.vn_set_observations, (X, q, dir, rowptr, value, wgt), n, nO, float(weight))
 
     def set_obs_weight(self, weight):
         """lambda of the observation term, without re-registering (vn_set_obs_weight)."""
