@@ -349,7 +349,9 @@ int vn_causal_weights(vn_engine* h, int32_t batch, double* omega_slab_host, int3
  * masked entries, in a fixed order without atomics (two evaluations: the same bits), per unique point on the de-duplicated step.
  * vn_apply and the fused train steps update the masked entries with the arithmetic of the parameters' Adam update (the engine's
  * beta1, beta2, eps, the shared step counter, the rate `lr`), then clamp them to [lo, hi] (+-inf: unbounded).  Unmasked entries
- * never change a bit.  A masked coefficient of a term no batch carries has gradient 0 and does not move.
+ * never change a bit.  On a batch that does not carry its term a masked coefficient's gradient reads 0, and the coefficient
+ * follows the momentum in its slots from the batches before that did (Adam with g = 0); it stays where it is only while
+ * its slots are zero, that is while no batch has carried the term since the registration.
  * vn_state_snapshot / vn_state_rollback carry coefficients and slots; vn_state_size / _export / _import keep their layout.
  *   mask   nine ints (non-zero: learnt), or NULL: learning off, everything freed, the batches' own coefficients count again and
  *          every result is bit for bit what it was before learning was switched on.
@@ -385,7 +387,8 @@ int vn_set_source_basis(vn_engine* h, int32_t batch, const float* phi_dev, int32
  * evaluations: the same bits); the single-launch 8-wave route runs its two-pass sequence for such a batch.  vn_apply and the
  * fused train steps update the masked entries with the arithmetic of the parameters' Adam update (the engine's beta1, beta2, eps,
  * the shared step counter -- shared with vn_set_coef_learn too --, the rate `lr`), then clamp them to [lo, hi] (+-inf: unbounded).
- * Unmasked entries take part in the source at their init value and never change a bit.
+ * Unmasked entries take part in the source at their init value and never change a bit.  On a batch without a basis the
+ * amplitude gradient reads 0, and the masked amplitudes follow the momentum in their slots, as a coefficient without its term does.
  * vn_state_snapshot / vn_state_rollback carry amplitudes and slots; vn_state_size / _export / _import keep their layout.
  *   mask   J ints (non-zero: learnt), or NULL: learning off, everything freed, every result bit for bit what it was before.
  *   init, lo, hi   J doubles each.  Non-finite init, NaN bounds, lo > hi, lr not finite or <= 0, J outside 1..VN_SRC_MAX: VN_EINVAL.
@@ -422,7 +425,8 @@ int vn_set_field_basis(vn_engine* h, int32_t batch, const float* G_dev, int32_t 
  * step has it per point), and the single-launch 8-wave route runs its two-pass sequence for such a batch.  vn_apply and the fused
  * train steps update the masked entries with the arithmetic of the parameters' Adam update (the engine's beta1, beta2, eps, the
  * shared step counter -- shared with vn_set_coef_learn and vn_set_source_learn too --, the rate `lr`), then clamp them to [lo, hi]
- * (+-inf: unbounded).  Unmasked entries take part in gcoef at their init value and never change a bit.  The loss-only forms and
+ * (+-inf: unbounded).  Unmasked entries take part in gcoef at their init value and never change a bit.  On a batch without a
+ * basis the amplitude gradient reads 0, and the masked amplitudes follow the momentum in their slots.  The loss-only forms and
  * vn_objective_f64 run the mix only: no amplitude gradient is built in fp64.
  * vn_state_snapshot / vn_state_rollback carry amplitudes and slots; vn_state_size / _export / _import keep their layout.
  *   mask   J ints (non-zero: learnt), or NULL: learning off, everything freed, every result bit for bit what it was before.
