@@ -92,9 +92,11 @@ def csr(uid, U):
 
 
 @functools.lru_cache(maxsize=None)
-def inputs(i):
-    """The seeded inputs of CASES[i] as a dict of fp32 arrays: computed once, shared, never modified."""
-    d_in, dim, widths, q, n_k, U, nB, bDof, source, integW, td, act, periodic, gscale, tscale, pscale = CASES[i]
+def inputs(i, n_k=None, q=None):
+    """The seeded inputs of CASES[i] as a dict of fp32 arrays: computed once, shared, never modified.  (n_k, q: another number of
+    test functions and of quadrature points on the case's network, unique points and BC/IC rows -- tests/source_cases.BIG.)"""
+    d_in, dim, widths, q0, n_k0, U, nB, bDof, source, integW, td, act, periodic, gscale, tscale, pscale = CASES[i]
+    n_k, q = n_k or n_k0, q or q0
     rng = np.random.default_rng(21)
     n = n_k * q
     Xu = rng.uniform(-1, 1, (U, d_in)).astype(np.float32)
@@ -143,10 +145,10 @@ def theta(i):
 def ref_kw(i, dtype=torch.float64, gcoef=None, d=None):
     """Keyword arguments of tests/nldiff_ref.loss_and_grad for CASES[i] on the expanded rows (gcoef: another [nT, dim] array; d:
     another interior data set on the same network, tables and BC/IC rows -- `big_batch`)."""
-    d_in, dim, widths, q, n_k, U, nB, bDof, source, integW, td, act = CASES[i][:12]
+    d_in, dim, widths, _, n_k, U, nB, bDof, source, integW, td, act = CASES[i][:12]
     d = inputs(i) if d is None else d
     f = np.float64 if dtype == torch.float64 else np.float32
-    n = d['Input'].shape[0]
+    n, q = d['Input'].shape[0], d['N1'].size
     n_k = n // q
     nb = nB if td else bDof
     return dict(Input=d['Input'].astype(f), gcoef=(d['gcoef'] if gcoef is None else gcoef).astype(f),

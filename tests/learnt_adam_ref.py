@@ -1,6 +1,6 @@
 """
-fp64 restatement of the step the three learnt vectors take (vn_coef_apply_kernel, vn_source_apply_kernel; driven by learnt_finish /
-learnt_apply_args in vn_api.hip), its fp32 twin, named wrong variants of it, and the bar between the device and the restatement.
+fp64 restatement of the step the three learnt vectors take (vn_learnt_apply_kernel of vn_learnt.hip; driven by learnt_finish in
+vn_api.hip), its fp32 twin, named wrong variants of it, and the bar between the device and the restatement.
 Plain module (no GPU, no pytest marks), shared by tests/test_learnt_adam_host.py and tests/test_learnt_adam_gpu.py.
 
 The step of entry i at step counter t (masked entries only; the others and their slots are not touched):

@@ -18,6 +18,15 @@ Basis (default_rng(41 + 97 i + J), in the case's own coordinates x = Input[:, :d
 
 J = 3 runs on every case; J of 1, 64 and 5 (mask [1, 0, 1, 0, 0]) on cases 0 and 6 only.
 
+Large-row cases (indices N_CASES + k, tests/test_learnt_gpu.py only; not in PAIRS): the network, unique points, BC/IC rows and
+scales of case 8 -- 1D + t, widths [24, 31], the smallest network of the cases -- at the (n_k, q) of BIG, J = 9 with entries 0, 7
+and 8 learnt (both sides of the boundary between the stream groups of eight).  nT = 65 538 is just above the 256 x 256 rows a capped
+reduction grid takes one row per thread of, and nT % 4 == 2: the one-row kernels, a thread taking up to two rows of a partial.
+nT = 262 152 is just above four times that and a multiple of 4: the four-row kernels wrap too.  Their basis seeds are the formula's
+own (source 41 + 97 i + 9 = 1117 and 1214, field 83 + 97 i + 9 = 1159 and 1256): with them the fp64 reference leaves no learnt
+component on the conditioning floor (least |g64_j| / S_j of the learnt ones: source 0.14 and 0.053, field 0.21 and 0.13, against
+COND_FLOOR = 0.01; tests/test_learnt_gpu.py asserts it from the reference before it looks at the device).
+
 The bar, per component j:   |g_j - g64_j| <= GRAD_RTOL * max(|g64_j|, COND_FLOOR * S_j)
 with S_j = sum_r |row contribution| (tests/source_ref.py).  The floor may be the binding branch for at most BINDING_FRAC of all
 components over all (case, J); tests/test_source_host.py asserts that, and that the reference evaluated in fp32 on the CPU stays
@@ -42,17 +51,23 @@ MASK5 = [1, 0, 1, 0, 0]
 CUT = 76
 # (case, J) of every gradient check
 PAIRS = [(i, 3) for i in range(N_CASES)] + [(i, J) for i in WIDE for J in (1, 64, 5)]
+BIG_BASE = 8
+BIG = [(10923, 6), (43692, 6)]                 # (n_k, q) of the large-row cases N_CASES, N_CASES + 1
+BIG_IDS = ['1dt_rows65538', '1dt_rows262152']
+BIG_J, BIG_MASK = 9, [1, 0, 0, 0, 0, 0, 0, 1, 1]
 
 
 def base(i):
     """The case of tests/dedup_term_cases.CASES that case i takes its network, tables and BC/IC rows from."""
-    return 6 if i == N_CASES - 1 else i
+    return BIG_BASE if i >= N_CASES else 6 if i == N_CASES - 1 else i
 
 
 def case(i):
-    """The row of tests/dedup_term_cases.CASES, with the case's own n_k."""
+    """The row of tests/dedup_term_cases.CASES, with the case's own n_k (a large-row case: and q)."""
     c = list(dt.CASES[base(i)])
-    if i != base(i):
+    if i >= N_CASES:
+        c[4], c[3] = BIG[i - N_CASES]
+    elif i != base(i):
         c[4] = CUT
     return tuple(c)
 
@@ -60,6 +75,8 @@ def case(i):
 @functools.lru_cache(maxsize=None)
 def inputs(i):
     """The seeded inputs of case i (tests/dedup_term_cases.inputs; case 10: the first CUT test functions of case 6)."""
+    if i >= N_CASES:
+        return dt.inputs(BIG_BASE, *BIG[i - N_CASES])
     d = dt.inputs(base(i))
     if i == base(i):
         return d

@@ -1,6 +1,6 @@
 """
 GPU tier of field identification (vn_set_field_basis, vn_set_field_learn, vn_get_field_amps, vn_set_field_amps;
-`VarNet(learnField=...)`): the amplitude gradient of vn_field.hip against the fp64 restatement tests/field_ref.py on the cases of
+`VarNet(learnField=...)`): the amplitude gradient of vn_learnt.hip against the fp64 restatement tests/field_ref.py on the cases of
 tests/field_cases.py -- row-wise on the automatic route (the two-pass sequence; for integ_num > 128 the two-pass route itself) and
 on the generic kernels, de-duplicated on the case's shared-point map (for the EMPTY cases also the map with row-less points) --
 loss pieces, lossVec and the theta-gradient at the mixed gcoef, that b = 0 and learning off give back the bits of an engine without

@@ -1,6 +1,6 @@
 """
 GPU tier of the inverse mode (vn_set_coef_learn, vn_get_coefs, vn_set_coefs; `VarNet(learnCoef=...)`): the coefficient gradient of
-vn_coef.hip against the fp64 restatement tests/inverse_ref.py on the ten cases of tests/dedup_term_cases.py -- row-wise on the
+vn_learnt.hip against the fp64 restatement tests/inverse_ref.py on the ten cases of tests/dedup_term_cases.py -- row-wise on the
 automatic route (the two-pass sequence; for integ_num > 128 the two-pass route itself) and on the generic kernels, de-duplicated on
 the case's shared-point map (for the EMPTY cases also the map with row-less points) -- that nothing else moves, the Adam step of
 the coefficients, snapshot / rollback, the fp64 objective at the device coefficients, every refusal, and two recoveries end to end.

@@ -1,7 +1,7 @@
 """
 GPU tier of the step the three learnt vectors take -- the nine polynomial coefficients (vn_set_coef_learn), the source amplitudes
-(vn_set_source_learn) and the field amplitudes (vn_set_field_learn); vn_coef_apply_kernel and vn_source_apply_kernel, driven by
-learnt_finish / learnt_apply_args -- against the fp64 restatement tests/learnt_adam_ref.Adam64 over eight steps, on the cases of
+(vn_set_source_learn) and the field amplitudes (vn_set_field_learn); vn_learnt_apply_kernel of vn_learnt.hip, driven by
+learnt_finish -- against the fp64 restatement tests/learnt_adam_ref.Adam64 over eight steps, on the cases of
 tests/learnt_cases.py, on the automatic route and on the case's shared-point map:
   a  one batch, vn_train_step and vn_grad + vn_apply in turn;
   b  one bound per vector that is reached at step 2 and held, then every vector overwritten by its value setter after step 5;

@@ -4,6 +4,11 @@ amplitudes (vn_set_source_learn) and the field amplitudes (vn_set_field_learn) -
 single steps, snapshot / rollback / replay, one vector switched off next to the other two, one vector registered again at another
 length, and every setter invalidating the snapshot.  Case 0 of tests/field_cases.py and tests/source_cases.py, J = 3, on the
 automatic route and on the case's shared-point map.  Every comparison is bitwise.
+
+And the paths of the reductions that no case of a few hundred rows reaches (the large-row cases of tests/source_cases.py): a capped
+grid, where a thread takes more than one row of a partial, on the one-row and on the four-row kernels, with learnt entries on both
+sides of the boundary between two stream groups -- the amplitude gradients of the source and of the field against their fp64
+restatements, within the bars of their case modules.
 """
 import numpy as np
 import pytest
@@ -11,6 +16,8 @@ import torch
 
 from tests import field_cases as fc
 from tests import source_cases as sc
+from tests import test_source_gpu as tsg
+from tests.test_field_gpu import check_amp_grad as check_field_grad
 from tests.test_field_gpu import grad_of, make_engine
 from varnet_amd.engine import VNError
 
@@ -113,3 +120,29 @@ def test_shared_lifecycle_of_the_three_vectors(route):
         b.close()
         if twin is not None:
             twin.close()
+
+
+@pytest.mark.parametrize('vector', ['source', 'field'])
+@pytest.mark.parametrize('k', range(len(sc.BIG)), ids=sc.BIG_IDS)
+def test_amplitude_gradient_on_a_capped_grid(k, vector):
+    """nT > 256 x 256 (one-row kernels) and nT > 4 x 256 x 256 (four-row kernels), J = 9, entries 0, 7 and 8 learnt, automatic
+    row-wise route."""
+    i, n, mask = sc.N_CASES + k, sc.BIG_J, sc.BIG_MASK
+    q, n_k = sc.case(i)[3:5]
+    assert n_k * q > (1 if k == 0 else 4) * 256 * 256 and (n_k * q) % 4 == (2 if k == 0 else 0)
+    cases = sc if vector == 'source' else fc
+    _, _, g64, S = cases.reference64(i, n)
+    on = np.array(mask, dtype=bool)
+    assert np.all(np.abs(g64[on]) > cases.COND_FLOOR * S[on]), (g64, S)    # the bar of a learnt component is relative to itself
+    eng = tsg.make_engine(i, 'auto', n) if vector == 'source' else make_engine(i, 'auto', n)
+    try:
+        if vector == 'source':
+            eng.set_source_learn(mask, sc.basis(i, n)[1], lr=0.01)
+            grad_of(eng)
+            tsg.check_amp_grad('%s/J%d/auto/amp' % (sc.BIG_IDS[k], n), eng.get_source_amps(grad=True)[1], i, n, mask)
+        else:
+            eng.set_field_learn(mask, fc.basis(i, n)[1], lr=0.01)
+            grad_of(eng)
+            check_field_grad('%s/J%d/auto/amp' % (sc.BIG_IDS[k], n), eng.get_field_amps(grad=True)[1], g64, S, mask)
+    finally:
+        eng.close()

@@ -1,6 +1,6 @@
 """
 GPU tier of source identification (vn_set_source_basis, vn_set_source_learn, vn_get_source_amps, vn_set_source_amps;
-`VarNet(learnSource=...)`): the amplitude gradient of vn_source.hip against the fp64 restatement tests/source_ref.py on the cases of
+`VarNet(learnSource=...)`): the amplitude gradient of vn_learnt.hip against the fp64 restatement tests/source_ref.py on the cases of
 tests/source_cases.py -- row-wise on the automatic route (the two-pass sequence; for integ_num > 128 the two-pass route itself), on
 the generic kernels and on one layer-by-layer engine, de-duplicated on the case's shared-point map (for the EMPTY cases also the
 map with row-less points) -- loss pieces, lossVec and the theta-gradient at the mixed source, that a = 0 and learning off give back
@@ -391,7 +391,7 @@ def test_train_epoch_snapshot_and_rollback(route):
 
 # ---- 3. evaluations at the device amplitudes ----------------------------------------------------------------------------
 def fma_mix(i, J, amp):
-    """The stream vn_source_mix_kernel forms, restated: fp32, from s0, j ascending, one fused multiply-add per stream (the product
+    """The stream vn_learnt_mix_kernel forms, restated: fp32, from s0, j ascending, one fused multiply-add per stream (the product
     of two fp32 numbers is exact in fp64, so each step is one fp64 addition rounded to fp32)."""
     Phi = sc.basis(i, J)[0]
     s = sc.s0_of(i).astype(np.float32)

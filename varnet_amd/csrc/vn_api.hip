@@ -8,9 +8,7 @@
 #include "vn_pgrad16.h"
 #include "vn_taylor16.h"
 #include "vn_terms.h"
-#include "vn_coef.h"
-#include "vn_source.h"
-#include "vn_field.h"
+#include "vn_learnt.h"
 #include "vn_weights.h"
 #include "vn_split16.h"
 
@@ -151,58 +149,24 @@ struct Learnt {
   unsigned long long mask = 0;                    // bit j: entry j is learnt
   double lr = 0.0;
   float* state = nullptr;                         // [6 * cap] (value | m | v) at stride cap, then their copy of vn_state_snapshot
-  float* bounds = nullptr;                        // [2 * cap] (lo | hi) on the device, for the kinds that keep them there
-  float hbounds[2 * VN_COEF_N] = {};              // (lo | hi) of the kind whose bounds travel by value in the launch arguments
+  float* bounds = nullptr;                        // [2 * cap] (lo | hi) at stride cap
   double* grad = nullptr;                         // [cap] gradient of the last gradient evaluation
   float* part = nullptr;                          // [maxblk, J] partials of the reduction
   int blocks = 0;                                 // partials the current gradient evaluation wrote (0: the batch has nothing to reduce)
 };
 
-// fold + Adam step + clamp of one vector: the arguments both apply kernels share (`fold`: the partials are folded into grad first)
-template <class Args>
-void learnt_apply_args(Args& a, const Learnt& v, int cap, bool fold, bool update, double t, const vn_config& c) {
-  if (fold) { a.part = v.part; a.blocks = v.blocks; }
-  a.grad = v.grad; a.m = v.state + cap; a.v = v.state + 2 * cap;
-  a.mask = (decltype(a.mask))v.mask;
-  a.update = update ? 1 : 0;
-  if (update) {
-    a.lr_t = (float)(v.lr * std::sqrt(1.0 - std::pow(c.beta2, t)) / (1.0 - std::pow(c.beta1, t)));
-    a.b1 = (float)c.beta1; a.b2 = (float)c.beta2; a.eps = (float)c.eps;
-  }
-}
-
-hipError_t learnt_apply_coef(const Learnt& v, int cap, bool fold, bool update, double t, const vn_config& c, hipStream_t s) {
-  VnCoefApplyArgs a{};
-  learnt_apply_args(a, v, cap, fold, update, t, c);
-  a.coef = v.state;
-  std::copy(v.hbounds, v.hbounds + VN_COEF_N, a.lo);
-  std::copy(v.hbounds + VN_COEF_N, v.hbounds + 2 * VN_COEF_N, a.hi);
-  return vn_coef_apply_launch(a, s);
-}
-
-// (vn_source_apply_kernel: nothing in it is the source's, so the field amplitudes go through it at their own stride)
-hipError_t learnt_apply_amps(const Learnt& v, int cap, bool fold, bool update, double t, const vn_config& c, hipStream_t s) {
-  VnSrcApplyArgs a{};
-  learnt_apply_args(a, v, cap, fold, update, t, c);
-  a.J = v.J; a.amp = v.state;
-  a.lo = v.bounds; a.hi = v.bounds + cap;
-  return vn_source_apply_launch(a, s);
-}
-
 struct LearntKind {
   int cap;                    // capacity, and the stride of (value | m | v)
-  int maxblk;                 // cap of the reduction grid
-  bool dev_bounds;            // bounds in Learnt::bounds (else by value: Learnt::hbounds)
-  hipError_t (*apply)(const Learnt&, int cap, bool fold, bool update, double t, const vn_config&, hipStream_t);
+  int lanes;                  // lane-group width of the fp64 fold (VnLearntApplyArgs)
   const char* setter;         // the messages' nouns
   const char* noun;
   const char* what;
   const char* grads;
 };
 constexpr LearntKind kLearnt[LV_N] = {
-  {VN_COEF_N, VN_COEF_MAXBLK, false, learnt_apply_coef, "vn_set_coef_learn", "coefficient", "coefficients", "the nine coefficient gradients"},
-  {VN_SRC_JMAX, VN_SRC_MAXBLK, true, learnt_apply_amps, "vn_set_source_learn", "amplitude", "source amplitudes", "the amplitude gradients"},
-  {VN_FLD_JMAX, VN_FLD_MAXBLK, true, learnt_apply_amps, "vn_set_field_learn", "amplitude", "field amplitudes", "the amplitude gradients"},
+  {VN_COEF_N, 16, "vn_set_coef_learn", "coefficient", "coefficients", "the nine coefficient gradients"},
+  {VN_SRC_JMAX, 64, "vn_set_source_learn", "amplitude", "source amplitudes", "the amplitude gradients"},
+  {VN_FLD_JMAX, 64, "vn_set_field_learn", "amplitude", "field amplitudes", "the amplitude gradients"},
 };
 
 int learnt_weights_refusal(const LearntKind& k, int batch) {
@@ -297,9 +261,9 @@ struct vn_engine {
   const int* orowptr = nullptr;
   double olambda = 0.0;
   double* omisfit = nullptr;                      // device slot: the unweighted misfit O of the last evaluation
-  // the vectors learnt next to the parameters, by LearntId: the nine coefficients of inverse mode (vn_set_coef_learn, vn_coef.hip),
+  // the vectors learnt next to the parameters, by LearntId: the nine coefficients of inverse mode (vn_set_coef_learn),
   // which live on the device while they are learnt, and the engine-wide amplitudes of the batches' source bases
-  // (vn_set_source_learn, vn_source.hip) and gcoef bases (vn_set_field_learn, vn_field.hip); then each feature's own work buffers
+  // (vn_set_source_learn) and gcoef bases (vn_set_field_learn), all of vn_learnt.hip; then each feature's own work buffers
   Learnt lv[LV_N];
   float* cl_acc = nullptr; long cl_acc_cap = 0;   // [3, U] accR_j, accF_j, gs_j of the de-duplicated step
   float* sl_mix = nullptr; long sl_mix_cap = 0;   // [nT] s0 + sum_j a_j phi_j of the batch being evaluated
@@ -1111,7 +1075,19 @@ int learnt_finish(vn_engine* h, int id, bool fold, bool update, double t) {
     HIPCHK(hipMemsetAsync(v.part, 0, (size_t)v.J * sizeof(float), h->stream));
     v.blocks = 1;
   }
-  HIPCHK(k.apply(v, k.cap, fold, update, t, h->cfg, h->stream));
+  VnLearntApplyArgs a{};
+  if (fold) { a.part = v.part; a.blocks = v.blocks; }
+  a.J = v.J; a.lanes = k.lanes; a.grad = v.grad;
+  a.val = v.state; a.m = v.state + k.cap; a.v = v.state + 2 * k.cap;
+  a.lo = v.bounds; a.hi = v.bounds + k.cap;
+  a.mask = v.mask;
+  a.update = update ? 1 : 0;
+  if (update) {
+    const vn_config& c = h->cfg;
+    a.lr_t = (float)(v.lr * std::sqrt(1.0 - std::pow(c.beta2, t)) / (1.0 - std::pow(c.beta1, t)));
+    a.b1 = (float)c.beta1; a.b2 = (float)c.beta2; a.eps = (float)c.eps;
+  }
+  HIPCHK(vn_learnt_apply_launch(a, h->stream));
   return VN_OK;
 }
 
@@ -1156,15 +1132,15 @@ int source_mix(vn_engine* h, const Batch& b, int batch) {
   const long nT = b.n_k * h->cfg.integ_num;
   if (nT <= 0) return VN_OK;
   if (int rc = ensure(&h->sl_mix, &h->sl_mix_cap, nT)) return rc;
-  VnSrcMixArgs a{};
-  a.s0 = b.source; a.phi = b.sb_phi; a.amp = h->lv[LV_SRC].state; a.J = b.sb_J; a.nT = nT; a.out = h->sl_mix;
-  HIPCHK(vn_source_mix_launch(a, h->stream));
+  VnMixArgs a{};
+  a.base = b.source; a.stream = b.sb_phi; a.amp = h->lv[LV_SRC].state; a.J = b.sb_J; a.n = nT; a.out = h->sl_mix;
+  HIPCHK(vn_learnt_mix_launch(a, h->stream));
   return VN_OK;
 }
 
 // Field identification, first thing in an evaluation of batch b (the routes without a point pass for the rows' grad u were refused by
-// vn_set_field_learn): the batch's basis must be the engine's, then gcoef is formed --
-// vn_source_mix_kernel's arithmetic over the nT * dim entries of a stream -- and, on a de-duplication map, its CSR-ordered copy
+// vn_set_field_learn): the batch's basis must be the engine's, then gcoef is formed -- the mix over the nT * dim entries of a
+// stream -- and, on a de-duplication map, its CSR-ordered copy
 int field_mix(vn_engine* h, const Batch& b, int batch) {
   if (!fld_learnt(h, b)) return VN_OK;
   if (b.fb_J != h->lv[LV_FLD].J)
@@ -1172,9 +1148,9 @@ int field_mix(vn_engine* h, const Batch& b, int batch) {
   const long n = b.n_k * h->cfg.integ_num * h->cfg.dim;
   if (n <= 0) return VN_OK;
   if (int rc = ensure(&h->fl_mix, &h->fl_mix_cap, n)) return rc;
-  VnSrcMixArgs a{};
-  a.s0 = b.gcoef; a.phi = b.fb_G; a.amp = h->lv[LV_FLD].state; a.J = b.fb_J; a.nT = n; a.out = h->fl_mix;
-  HIPCHK(vn_source_mix_launch(a, h->stream));
+  VnMixArgs a{};
+  a.base = b.gcoef; a.stream = b.fb_G; a.amp = h->lv[LV_FLD].state; a.J = b.fb_J; a.n = n; a.out = h->fl_mix;
+  HIPCHK(vn_learnt_mix_launch(a, h->stream));
   if (b.Xu) {
     if (int rc = ensure(&h->fl_csr, &h->fl_csr_cap, n)) return rc;
     HIPCHK(vn_dedup_permute_launch(h->fl_mix, b.rowidx, h->fl_csr, b.n_k * h->cfg.integ_num, h->cfg.dim, h->stream));
@@ -1681,9 +1657,9 @@ static int learnt_set_learn(vn_engine* h, int id, int32_t J, const int32_t* mask
   Learnt& v = h->lv[id];
   if (!v.state) {
     hipError_t e = hipMalloc((void**)&v.state, 6 * (size_t)k.cap * sizeof(float));
-    if (e == hipSuccess && k.dev_bounds) e = hipMalloc((void**)&v.bounds, 2 * (size_t)k.cap * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&v.bounds, 2 * (size_t)k.cap * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&v.grad, (size_t)k.cap * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&v.part, (size_t)k.maxblk * k.cap * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&v.part, (size_t)VN_LEARNT_MAXBLK * k.cap * sizeof(float));
     if (e != hipSuccess) { (void)hipGetLastError(); learnt_free(h, id); return fail(VN_ENOMEM, "%s: %s", k.setter, hipGetErrorString(e)); }
   }
   float st[6 * LV_CAP] = {}, bd[2 * LV_CAP] = {};    // (m, v and the snapshot copy start at zero)
@@ -1696,8 +1672,7 @@ static int learnt_set_learn(vn_engine* h, int id, int32_t J, const int32_t* mask
   v.lr = lr;
   v.J = J;
   HIPCHK(hipMemcpyAsync(v.state, st, 6 * (size_t)k.cap * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (k.dev_bounds) HIPCHK(hipMemcpyAsync(v.bounds, bd, 2 * (size_t)k.cap * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  else std::copy(bd, bd + 2 * k.cap, v.hbounds);
+  HIPCHK(hipMemcpyAsync(v.bounds, bd, 2 * (size_t)k.cap * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemsetAsync(v.grad, 0, (size_t)k.cap * sizeof(double), h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));      // (st, bd leave scope)
   v.on = true;
@@ -1741,14 +1716,14 @@ static int learnt_put(vn_engine* h, int id, const double* val, int32_t J) {
   return VN_OK;
 }
 
-// ---- inverse mode: the nine coefficients on the device, learnt next to the parameters (vn_coef.hip) ----
+// ---- inverse mode: the nine coefficients on the device, learnt next to the parameters (vn_learnt.hip) ----
 int vn_set_coef_learn(vn_engine* h, const int32_t mask[9], const double init[9], const double lo[9], const double hi[9], double lr) {
   return learnt_set_learn(h, LV_COEF, VN_COEF_N, mask, init, lo, hi, lr);
 }
 int vn_get_coefs(vn_engine* h, double coef[9], double grad[9]) { return learnt_get(h, LV_COEF, coef, grad, VN_COEF_N); }
 int vn_set_coefs(vn_engine* h, const double coef[9]) { return learnt_put(h, LV_COEF, coef, VN_COEF_N); }
 
-// ---- source identification: basis streams per batch, amplitudes on the device, learnt next to the parameters (vn_source.hip) ----
+// ---- source identification: basis streams per batch, amplitudes on the device, learnt next to the parameters (vn_learnt.hip) ----
 int vn_set_source_basis(vn_engine* h, int32_t batch, const float* phi_dev, int32_t J) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
@@ -1772,7 +1747,7 @@ int vn_set_source_learn(vn_engine* h, int32_t J, const int32_t* mask, const doub
 int vn_get_source_amps(vn_engine* h, double* amp, double* grad, int32_t J) { return learnt_get(h, LV_SRC, amp, grad, J); }
 int vn_set_source_amps(vn_engine* h, const double* amp, int32_t J) { return learnt_put(h, LV_SRC, amp, J); }
 
-// ---- field identification: basis streams of gcoef per batch, amplitudes on the device, learnt next to the parameters (vn_field.hip) ----
+// ---- field identification: basis streams of gcoef per batch, amplitudes on the device, learnt next to the parameters (vn_learnt.hip) ----
 int vn_set_field_basis(vn_engine* h, int32_t batch, const float* G_dev, int32_t J) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)

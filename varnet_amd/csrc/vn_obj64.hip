@@ -443,7 +443,7 @@ __global__ __launch_bounds__(256) void vn_obj64_seed_kernel(SeedArgs a) {
       a.u[a.offF + k] = s * cf * r;
     }
   }
-  if (k < a.nP) {                                 // the arithmetic of vn_periodic_seed_kernel (vn_periodic.hip)
+  if (k < a.nP) {                                 // the arithmetic of vn_periodic_seed_kernel (vn_edge.hip)
     const long i = a.offP + k, j = i + a.nP;
     const double r0 = a.u[i] - a.u[j];
     const double r1 = a.pgamma > 0.0 ? a.ud[i] - a.ud[j] : 0.0;
@@ -454,7 +454,7 @@ __global__ __launch_bounds__(256) void vn_obj64_seed_kernel(SeedArgs a) {
       a.ud[i] = s * a.pgamma * r1; a.ud[j] = -s * a.pgamma * r1;
     }
   }
-  if (k < a.nO) {                                 // the arithmetic of vn_obs_seed_kernel (vn_obs.hip), additions in CSR order
+  if (k < a.nO) {                                 // the arithmetic of vn_obs_seed_kernel (vn_edge.hip), additions in CSR order
     const long e0 = a.orowptr ? (long)a.orowptr[k] : k, e1 = a.orowptr ? (long)a.orowptr[k + 1] : k + 1;
     double acc = 0.0;
     for (long e = e0; e < e1; ++e) {

@@ -38,7 +38,7 @@ struct VnTermDedupArgs {
   float c[3];                                // reaction: (c1, c2, c3);  flux: (f1, f2, f3);  D(u): (d0, d1, d2)
   const float* cp;                           // [3] device, or nullptr: the same three while they are learnt (vn_set_coef_learn); c is then unused
   float* acc_out;                            // [U] or nullptr: the gather kernels store their CSR sum (accR_j, accF_j), the point
-                                             // kernel its dot product gs_j = grad u_j . seed_g[j,:] -- read by vn_coef.hip
+                                             // kernel its dot product gs_j = grad u_j . seed_g[j,:] -- read by vn_learnt.hip
   const float* feN; const float* feW;        // [q] tables (feW may be nullptr)
   const float* stf;                          // [n_k] seed of every test function (vn_dedup_seed_kernel's output)
   long nT, U; int q;

@@ -36,17 +36,13 @@
 //
 // Inverse mode (vn_set_coef_learn): every kernel takes its three coefficients from the argument `cp` when it is given -- the engine's
 // device vector, which the optimizer step updates -- and from the by-value `c` otherwise; the gather and point kernels store their
-// per-point sum (accR_j, accF_j, gs_j) to `acc_out` when it is given, for the coefficient reduction of vn_coef.hip.  With both null
+// per-point sum (accR_j, accF_j, gs_j) to `acc_out` when it is given, for the coefficient reduction of vn_learnt.hip.  With both null
 // code path and arithmetic are unchanged.
-#include <cstdint>
-#include <initializer_list>
-
 #include "vn_internal.h"
+#include "vn_rows4.h"
 #include "vn_terms.h"
 
 namespace {
-
-typedef float f32x4t __attribute__((ext_vector_type(4)));
 
 // c[0] + c[1] u + c[2] u^2 is D(u); u times it is p(u) and F(u)
 __device__ __forceinline__ float quad(float u, const float* c) { return c[0] + u * (c[1] + u * c[2]); }
@@ -66,9 +62,6 @@ __device__ __forceinline__ Coef3 coef3(const Args& a) {
 }
 
 // ---- row-wise routes ----
-__device__ __forceinline__ f32x4t load4(const float* p, long i) { return reinterpret_cast<const f32x4t*>(p)[i]; }
-__device__ __forceinline__ void store4(float* p, long i, f32x4t v) { reinterpret_cast<f32x4t*>(p)[i] = v; }
-
 __global__ __launch_bounds__(256) void vn_nlflux_fold_kernel(VnTermRowArgs a) {
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= a.nT) return;
@@ -290,14 +283,11 @@ __global__ __launch_bounds__(256) void vn_nldiff_point_kernel(VnTermDedupArgs a)
 }
 
 // ---- launches ----
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// The 4-row kernel when nT % 4 == 0 and every pointer it touches is 16-byte aligned (nullptr counts), else the 1-row kernel
+// The 4-row kernel by the rule of vn_rows4.h, else the 1-row kernel
 hipError_t launch_rows(void (*k4)(VnTermRowArgs), void (*k1)(VnTermRowArgs), const VnTermRowArgs& a,
                        std::initializer_list<const void*> ptrs, hipStream_t s) {
   if (a.nT <= 0) return hipSuccess;
-  bool four = a.nT % 4 == 0;
-  for (const void* p : ptrs) four = four && aligned16(p);
+  const bool four = rows4_ok(a.nT, ptrs);
   const long n = four ? a.nT / 4 : a.nT;
   hipLaunchKernelGGL(four ? k4 : k1, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
   return hipGetLastError();

@@ -24,11 +24,10 @@
 #include <cstdint>
 
 #include "vn_internal.h"
+#include "vn_rows4.h"
 #include "vn_weights.h"
 
 namespace {
-
-typedef float f32x4w __attribute__((ext_vector_type(4)));
 
 template <class T>
 __device__ __forceinline__ T block_sum_w(T v, T* red) {
@@ -143,14 +142,12 @@ __global__ __launch_bounds__(256) void vn_weights_rows4_kernel(const float* __re
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= nT / 4) return;
   const float om = omega[(i * 4) / q];
-  f32x4w a = reinterpret_cast<const f32x4w*>(ubar)[i], b = reinterpret_cast<const f32x4w*>(udbar)[i];
+  f32x4t a = load4(ubar, i), b = load4(udbar, i);
 #pragma unroll
   for (int c = 0; c < 4; ++c) { a[c] *= om; b[c] *= om; }
-  reinterpret_cast<f32x4w*>(ubar)[i] = a;
-  reinterpret_cast<f32x4w*>(udbar)[i] = b;
+  store4(ubar, i, a);
+  store4(udbar, i, b);
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <class T>
 hipError_t apply(const VnWeightsReg& w, const VnWeightsWork& wk, const T* lossVec, long n_k, int tfb, int stride, T* omega_out,
@@ -190,7 +187,7 @@ hipError_t vn_weights_apply_f64(const VnWeightsReg& w, const VnWeightsWork& wk, 
 hipError_t vn_weights_rows_f32(const float* omega, long n_k, int q, float* ubar, float* udbar, hipStream_t s) {
   const long nT = n_k * q;
   if (nT <= 0) return hipSuccess;
-  const bool four = q % 4 == 0 && aligned16(omega) && aligned16(ubar) && aligned16(udbar);
+  const bool four = rows4_ok(q, {omega, ubar, udbar});
   const long n = four ? nT / 4 : nT;
   if (four) hipLaunchKernelGGL(vn_weights_rows4_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, omega, nT, q, ubar, udbar);
   else hipLaunchKernelGGL(vn_weights_rows_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, omega, nT, q, ubar, udbar);
