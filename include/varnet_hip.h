@@ -443,6 +443,46 @@ int vn_get_field_amps(vn_engine* h, double* amp, double* grad, int32_t J);
 /* Overwrites all J amplitudes (rounded to fp32, NOT clamped); the Adam slots stay.  Non-finite: VN_EINVAL; learning off: VN_ESTATE.
  * Invalidates the snapshot of vn_state_snapshot. */
 int vn_set_field_amps(vn_engine* h, const double* amp, int32_t J);
+/* Boundary data identification: the labels of a BC/IC row set are label0 + sum_j a_j B_j over a basis of J per-row streams (a
+ * Dirichlet basis function on its edge's rows and zero elsewhere, an initial-condition basis function on the initial rows; the
+ * engine does not know which stream is which), and the amplitudes a_j are learnt next to the parameters from the observations.
+ * vn_set_bic_basis registers the basis of one row set: B_dev is [J, nB] fp32 on the device, stream-major (every stream contiguous,
+ * nB as passed to vn_set_bic, also on a steady engine, which reads the first bDof entries of a stream); the streams are read on
+ * every step and must stay valid while registered.  batch = -1: the rows of vn_set_bic; batch >= 0: that batch's own copy, which
+ * needs a vn_set_batch_bic on that batch (VN_ESTATE without one).  B_dev == NULL or J == 0 clears the registration; vn_set_bic clears
+ * the shared one, vn_set_batch_bic and vn_set_interior the batch's.  A call replaces the previous registration, also when it fails.
+ * J > VN_BIC_MAX: VN_EINVAL.  The call invalidates the snapshot of vn_state_snapshot and the L-BFGS (f_k, g_k).
+ * Without vn_set_bic_learn a registered basis is not read: the labels are those of vn_set_bic / vn_set_batch_bic. */
+#define VN_BIC_MAX 64
+int vn_set_bic_basis(vn_engine* h, int32_t batch, const float* B_dev, int32_t J);
+/* The amplitudes are engine-wide, like those of vn_set_source_learn: while learning is on the engine owns ONE device vector of J
+ * fp32 amplitudes (`init`, rounded once), their two Adam slots and a snapshot copy of the three.  Every evaluation of a batch whose
+ * BC/IC set has a basis (vn_grad, vn_train_step / _epoch, vn_eval_loss, vn_objective_f64) first forms label[k] = label0[k] +
+ * sum_j a_j B_j[k] (fp32, j ascending, one fused multiply-add per stream) and every kernel reads it in place of the set's labels; a
+ * set whose basis has another J makes the step and the evaluations return VN_EINVAL.
+ *   d loss / d a_j = - sum_k ubar_b[k] B_j[k],  ubar_b[k] = (k < bDof ? 2 w0 biDimVal / bDof : 2 w1 biDimVal / (nB - bDof)) (u_b[k] - label[k])
+ * (k < bDof only on a steady engine) is formed inside vn_grad / vn_train_step / vn_train_epoch for the masked entries, in a fixed
+ * order without atomics (two evaluations: the same bits).  Every step keeps its route: the generic and the layer-by-layer route
+ * have u_b from their forward; the single launch, the two-pass sequence and the de-duplicated step run one forward of the BC/IC
+ * rows ahead of their own launches.  vn_apply and the fused train steps update the masked entries with the arithmetic of the
+ * parameters' Adam update (the engine's beta1, beta2, eps, the shared step counter, the rate `lr`), then clamp them to [lo, hi]
+ * (+-inf: unbounded).  Unmasked entries take part in the labels at their init value and never change a bit.  On a batch whose set
+ * has no basis the amplitude gradient reads 0, and the masked amplitudes follow the momentum in their slots.  The loss-only forms
+ * and vn_objective_f64 run the mix only: no amplitude gradient is built in fp64.
+ * vn_state_snapshot / vn_state_rollback carry amplitudes and slots; vn_state_size / _export / _import keep their layout.
+ *   mask   J ints (non-zero: learnt), or NULL: learning off, everything freed, every result bit for bit what it was before.
+ *   init, lo, hi   J doubles each.  Non-finite init, NaN bounds, lo > hi, lr not finite or <= 0, J outside 1..VN_BIC_MAX: VN_EINVAL.
+ * Refused with VN_EUNSUPPORTED for the reasons of vn_set_source_learn: an RMSProp or L-BFGS engine; a handle that has a communicator
+ * (and vn_comm_init while learning is on); a batch with vn_set_tf_weights / vn_set_causal (here, in those calls and in the steps);
+ * and the 4-wave cross-check geometry (VN_KERNEL_FUSED).
+ * The call invalidates the snapshot of vn_state_snapshot and the L-BFGS (f_k, g_k). */
+int vn_set_bic_learn(vn_engine* h, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi, double lr);
+/* The J amplitudes now (synchronises) and, when grad is not NULL, the amplitude gradient of the last gradient evaluation (zeros for
+ * unmasked entries and before the first one).  Learning off: VN_ESTATE; J not the engine's: VN_EINVAL. */
+int vn_get_bic_amps(vn_engine* h, double* amp, double* grad, int32_t J);
+/* Overwrites all J amplitudes (rounded to fp32, NOT clamped); the Adam slots stay.  Non-finite: VN_EINVAL; learning off: VN_ESTATE.
+ * Invalidates the snapshot of vn_state_snapshot. */
+int vn_set_bic_amps(vn_engine* h, const double* amp, int32_t J);
 /* updateDictFields('trainW') (VarNetUtility.py:921-922); the caller applies the
  * w[0:2] /= batchNum*puNum rule (VarNetUtility.py:900-901). */
 int vn_set_weights(vn_engine* h, const double w[3]);

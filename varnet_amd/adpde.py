@@ -1,7 +1,7 @@
 """
 Advection-diffusion(-reaction) PDE container: `ADPDE(domain, diff, vel, source, timeDependent, tInterval,
 BCs, IC, cEx, MORvar, d_diff, reaction, nlflux, nldiff, periodic, sourceBasis, sourceAmp, diffBasis, diffAmp, d_diffBasis, velBasis,
-velAmp)` -- the reference's ADPDE.py:56-246 restated (plot helpers are out of scope).
+velAmp, bcBasis, bcAmp, icBasis, icAmp)` -- the reference's ADPDE.py:56-246 restated (plot helpers are out of scope).
 
     c_t = div(diff D(c) grad c) - vel . grad c - div(w F(c)) + source + rate * p(c),    a * dc/dn + b * c = g  on each edge,
 
@@ -60,13 +60,22 @@ class ADPDE:
     returning [n, dim], default zero): only the strong residual uses it, so without it the chi_j must be constant for the residual
     to be right.  The amplitudes can be learnt from observations (`VarNet(..., learnField=...)`: field identification); without
     that the sums are part of `diffFun`, `velFun` and `d_diffFun`.  velBasis with nldiff is not supported.
+
+    bcBasis=[(bInd, gamma_1), ..., (bInd, gamma_Jb)] with bcAmp=[...] (default: zeros) makes the Dirichlet value on boundary
+    indicator bInd `g/beta + sum_j bcAmp_j gamma_j` over the entries of that indicator: every gamma_j is a callable f(x[, t])
+    returning a column, evaluated like `g`, and counts on the rows of its own indicator only.  icBasis=[iota_1, ..., iota_Ji] with
+    icAmp=[...] makes the initial condition `IC + sum_j icAmp_j iota_j`, every iota_j a callable f(x) evaluated like `IC`
+    (time-dependent problems only).  Jb + Ji <= 64.  The amplitudes can be learnt from observations (`VarNet(..., learnBic=...)`:
+    boundary data identification); without that the sums are part of the boundary and initial labels.
     """
     SRC_MAX = 64
     FLD_MAX = 32
+    BIC_MAX = 64
 
     def __init__(self, domain, diff, vel, source=0.0, timeDependent=False, tInterval=None,
                  BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None, nlflux=None, nldiff=None, periodic=None,
-                 sourceBasis=None, sourceAmp=None, diffBasis=None, diffAmp=None, d_diffBasis=None, velBasis=None, velAmp=None):
+                 sourceBasis=None, sourceAmp=None, diffBasis=None, diffAmp=None, d_diffBasis=None, velBasis=None, velAmp=None,
+                 bcBasis=None, bcAmp=None, icBasis=None, icAmp=None):
         # the reference ignores the `timeDependent` argument (ADPDE.py:108-109)
         timeDependent = tInterval is not None
 
@@ -352,6 +361,65 @@ class ADPDE:
         if sourceBasis is not None:
             self.sourceBasis = sourceBasis
             self.sourceAmp = sourceAmp
+        # boundary and initial bases: likewise ((bInd, callable) pairs for the Dirichlet data)
+        bcBasis, bcAmp = self._check_bic_basis('bcBasis', 'bcAmp', bcBasis, bcAmp, MORvar, True)
+        icBasis, icAmp = self._check_bic_basis('icBasis', 'icAmp', icBasis, icAmp, MORvar, False)
+        if len(bcBasis or []) + len(icBasis or []) > self.BIC_MAX:
+            raise ValueError('bcBasis and icBasis hold %d functions together, at most %d are supported!'
+                             % (len(bcBasis or []) + len(icBasis or []), self.BIC_MAX))
+        if bcBasis is not None:
+            self.bcBasis, self.bcAmp = bcBasis, bcAmp
+        if icBasis is not None:
+            self.icBasis, self.icAmp = icBasis, icAmp
+
+    def _check_bic_basis(self, name, ampName, basis, amp, MORvar, edges):
+        """(list of entries, amplitudes) of bcBasis (`edges`: (bInd, callable) pairs) / icBasis (callables), or (None, None) without
+        one; ValueError names the field.  Called at the end of __init__: BCtype, periodic and timeDependent are set."""
+        if basis is None:
+            if amp is not None:
+                raise ValueError('%s is an option of %s=[...]!' % (ampName, name))
+            return None, None
+        shape = '[(bInd, gamma_1), ..., (bInd, gamma_J)]' if edges else '[iota_1, ..., iota_J]'
+        if not isinstance(basis, (list, tuple)) or len(basis) == 0:
+            raise ValueError('%s must be a non-empty list %s!' % (name, shape))
+        if len(basis) > self.BIC_MAX:
+            raise ValueError('%s holds %d functions, at most %d are supported!' % (name, len(basis), self.BIC_MAX))
+        if not edges and not self.timeDependent:
+            raise ValueError('icBasis needs a time-dependent problem: a steady problem has no initial condition!')
+        out = []
+        for j, e in enumerate(basis):
+            if not edges:
+                if not callable(e):
+                    raise ValueError('icBasis[%d] must be callable, like an initial condition!' % j)
+                out.append(e)
+                continue
+            if not isinstance(e, (list, tuple)) or len(e) != 2 or isinstance(e[0], bool) or not isinstance(e[0], (int, np.integer)):
+                raise ValueError('bcBasis[%d] must be a pair (bInd, gamma) of a boundary indicator and a callable!' % j)
+            bInd, f = int(e[0]), e[1]
+            if not callable(f):
+                raise ValueError('bcBasis[%d]: gamma must be callable, like the g of a boundary condition!' % j)
+            if not 0 <= bInd < self.domain.bIndNum:
+                raise ValueError('bcBasis[%d]: boundary indicator %d outside [0, %d)!' % (j, bInd, self.domain.bIndNum))
+            if self.BCtype[bInd] == 'Periodic':
+                raise ValueError('bcBasis[%d]: boundary indicator %d is paired by `periodic`, it carries no boundary data!' % (j, bInd))
+            if self.BCtype[bInd] != 'Dirichlet':
+                raise ValueError('bcBasis[%d]: boundary indicator %d carries a %s condition, only Dirichlet data has a basis!'
+                                 % (j, bInd, self.BCtype[bInd]))
+            out.append((bInd, f))
+        if amp is None:
+            amp = np.zeros(len(out))
+        try:
+            amp = np.array(np.reshape(np.asarray(amp, dtype=float), -1))
+        except (TypeError, ValueError):
+            raise ValueError('%s must be a list of %d numbers, one per function of %s!' % (ampName, len(out), name))
+        if amp.size != len(out):
+            raise ValueError('%s holds %d values for the %d functions of %s!' % (ampName, amp.size, len(out), name))
+        if not np.all(np.isfinite(amp)):
+            raise ValueError('%s must be finite!' % ampName)
+        if MORvar is not None:
+            raise NotImplementedError('%s with model-order reduction is not supported: parametric basis functions are out of scope '
+                                      '(the basis streams are assembled once, for all parameter batches)' % name)
+        return out, amp
 
     def _check_field_basis(self, name, ampName, basis, amp, MORvar, ncol, dim, const_field):
         """(list of callables, amplitudes) of diffBasis / velBasis / d_diffBasis, or (None, None) without one; ValueError names

@@ -82,6 +82,8 @@ struct Batch {
   // optional per-batch copy of the BC/IC rows (the reference's shuffle permutes them per feed: vn_set_batch_bic)
   const float* biInput = nullptr;
   const float* biLabel = nullptr;
+  const float* bb_B = nullptr;     // [bb_J, nB] basis streams of that copy's labels (vn_set_bic_basis), caller-owned; nullptr: none
+  int bb_J = 0;
   // de-duplicated formulation (vn_set_dedup)
   const float* Xu = nullptr;
   const int* uid = nullptr;   // (Xu is only ever set on the 8-wave routes: vn_set_dedup refuses the others)
@@ -140,7 +142,7 @@ constexpr bool kWithF32Point = false;
 // ---- learnt vectors: small vectors the Adam step moves next to the parameters ----------------
 // One record per vector; what differs between the vectors is a row of kLearnt.  Everything that handles them (learnt_* below
 // vn_engine) runs over the records in LearntId order.
-enum LearntId { LV_COEF, LV_SRC, LV_FLD, LV_N };
+enum LearntId { LV_COEF, LV_SRC, LV_FLD, LV_BIC, LV_N };
 constexpr int LV_CAP = VN_SRC_JMAX;              // the largest capacity of any kind (host staging arrays)
 
 struct Learnt {
@@ -167,6 +169,7 @@ constexpr LearntKind kLearnt[LV_N] = {
   {VN_COEF_N, 16, "vn_set_coef_learn", "coefficient", "coefficients", "the nine coefficient gradients"},
   {VN_SRC_JMAX, 64, "vn_set_source_learn", "amplitude", "source amplitudes", "the amplitude gradients"},
   {VN_FLD_JMAX, 64, "vn_set_field_learn", "amplitude", "field amplitudes", "the amplitude gradients"},
+  {VN_BIC_JMAX, 64, "vn_set_bic_learn", "amplitude", "boundary and initial amplitudes", "the amplitude gradients"},
 };
 
 int learnt_weights_refusal(const LearntKind& k, int batch) {
@@ -219,6 +222,10 @@ struct vn_engine {
   std::vector<Batch> batches;
   const float *biInput = nullptr, *biLabel = nullptr;
   long nB = 0, bDof = 0;
+  long nBreg = 0;                    // rows of vn_set_bic as the caller counts them (a steady engine keeps nB = bDof of them): the
+                                     // length of a label stream and of every basis stream of vn_set_bic_basis
+  const float* bicB = nullptr;       // [bicJ, nBreg] basis streams of the shared set's labels (vn_set_bic_basis), caller-owned
+  int bicJ = 0;
   double biDimVal = 1.0;
   double w[3] = {1.0, 1.0, 1.0};
 
@@ -263,13 +270,15 @@ struct vn_engine {
   double* omisfit = nullptr;                      // device slot: the unweighted misfit O of the last evaluation
   // the vectors learnt next to the parameters, by LearntId: the nine coefficients of inverse mode (vn_set_coef_learn),
   // which live on the device while they are learnt, and the engine-wide amplitudes of the batches' source bases
-  // (vn_set_source_learn) and gcoef bases (vn_set_field_learn), all of vn_learnt.hip; then each feature's own work buffers
+  // (vn_set_source_learn) and gcoef bases (vn_set_field_learn) and of the BC/IC label bases (vn_set_bic_learn), all of
+  // vn_learnt.hip; then each feature's own work buffers
   Learnt lv[LV_N];
   float* cl_acc = nullptr; long cl_acc_cap = 0;   // [3, U] accR_j, accF_j, gs_j of the de-duplicated step
   float* sl_mix = nullptr; long sl_mix_cap = 0;   // [nT] s0 + sum_j a_j phi_j of the batch being evaluated
   float* fl_mix = nullptr; long fl_mix_cap = 0;   // [nT, dim] g0 + sum_j b_j G_j of the batch being evaluated
   float* fl_csr = nullptr; long fl_csr_cap = 0;   // [nT, dim] fl_mix in CSR order (de-duplicated step), rebuilt every evaluation
   float* fl_pack = nullptr; long fl_pack_cap = 0; // [nT, 4] (u, grad u) of the batch's own rows (row-wise gradient evaluation)
+  float* bl_mix = nullptr; long bl_mix_cap = 0;   // [nBreg] label0 + sum_j a_j B_j of the BC/IC set the batch being evaluated reads
   float* snap = nullptr;       // vn_state_snapshot: device copy of (theta | m | v), 3 P floats
   int64_t snap_step = -1;      // step counter at the snapshot (-1: none)
   PointRoute point_route = PointRoute::automatic;   // vn_debug_point_route(route & 3)
@@ -439,7 +448,14 @@ int check_batch(vn_engine* h, int32_t batch) {
 }
 
 inline const float* bi_x(const vn_engine* h, const Batch& b) { return b.biInput ? b.biInput : h->biInput; }
-inline const float* bi_y(const vn_engine* h, const Batch& b) { return b.biLabel ? b.biLabel : h->biLabel; }
+// the labels as registered, and the basis streams of the same set (the batch's own copy, else the shared one)
+inline const float* bi_y0(const vn_engine* h, const Batch& b) { return b.biLabel ? b.biLabel : h->biLabel; }
+inline const float* bic_basis(const vn_engine* h, const Batch& b) { return b.biLabel ? b.bb_B : h->bicB; }
+inline int bic_basis_J(const vn_engine* h, const Batch& b) { return b.biLabel ? b.bb_J : h->bicJ; }
+// (while boundary / initial amplitudes are learnt, a batch whose set has a basis reads the mixed labels bic_mix formed at the start
+// of the evaluation: every launch site takes its labels from here)
+inline bool bic_learnt(const vn_engine* h, const Batch& b) { return h->lv[LV_BIC].on && bic_basis(h, b); }
+inline const float* bi_y(const vn_engine* h, const Batch& b) { return bic_learnt(h, b) ? h->bl_mix : bi_y0(h, b); }
 // (while amplitudes are learnt, a batch with a basis reads the mixed stream source_mix formed at the start of the evaluation)
 inline bool src_learnt(const vn_engine* h, const Batch& b) { return h->lv[LV_SRC].on && b.sb_phi; }
 inline const float* batch_src(const vn_engine* h, const Batch& b) {
@@ -753,6 +769,27 @@ int fused_forward(vn_engine* h, const float* X, const float* G, long n, float* o
   return VN_OK;
 }
 
+// Boundary / initial amplitudes: the amplitude sums over the BC/IC rows, whose values are in h->ub (vn_learnt.hip)
+int bic_reduce(vn_engine* h, const Batch& b) {
+  if (!bic_learnt(h, b) || h->nB <= 0) return VN_OK;
+  VnBicGradArgs g{};
+  g.ub = h->ub; g.label = bi_y(h, b); g.B = bic_basis(h, b); g.J = bic_basis_J(h, b);
+  g.nB = h->nBreg; g.bDof = h->bDof; g.steady = h->cfg.time_dependent ? 0 : 1;
+  g.biDimVal = (float)h->biDimVal; g.w0 = (float)h->w[0]; g.w1 = (float)h->w[1];
+  g.mask = h->lv[LV_BIC].mask; g.part = h->lv[LV_BIC].part;
+  HIPCHK(vn_bicgrad_launch(g, &h->lv[LV_BIC].blocks, h->stream));
+  return VN_OK;
+}
+
+// ... on the routes whose reverse pass carries the BC/IC tiles and leaves no values of those rows behind (the single launch, the
+// two-pass sequence, the de-duplicated step): one forward of the rows first.  Enqueued ahead of the step's own launches: it
+// borrows the work buffers the step's reduction reads, and that reduction may fold the parameters' update in.
+int bic_forward_reduce(vn_engine* h, const Batch& b) {
+  if (!bic_learnt(h, b) || h->nB <= 0) return VN_OK;
+  if (int rc = fused_forward(h, bi_x(h, b), nullptr, h->nB, h->ub, nullptr)) return rc;
+  return bic_reduce(h, b);
+}
+
 // ---- edge row sets (vn_edge.h) ------------------------------------------------------------------
 // The seed kernel of each kind: from the values in e.buf[EB_U] and the tangent stream ud (nullptr: values only) the loss
 // partials in e.buf[EB_LOSS] and, where asked for, the seeds ubar and udbar (nullptr: loss only / values only).
@@ -908,8 +945,10 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
   a.lossVec = weights_lossvec(h, b, lossVec); a.part = h->losspart;
   if (int rc = terms_fold_rows(h, b)) return rc;
   HIPCHK(vn_seed_launch(a, grid, h->stream));
-  if (with_seeds)
+  if (with_seeds) {
+    if (int rc = bic_reduce(h, b)) return rc;      // boundary / initial amplitudes: u_b is in h->ub
     if (int rc = terms_seed_rows(h, b)) return rc;
+  }
   if (int rc = weights_stage(h, b, a.lossVec, 256, nullptr, a.part, with_seeds)) return rc;
   if (lossdst) {
     HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2, lossdst, h->stream,
@@ -964,6 +1003,7 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
   const long tt = 128 / a.integ_num > 0 ? 128 / a.integ_num : 1;
   const long tiles = (a.n_k + tt - 1) / tt + (a.nB + 127) / 128;
   const int grid = h->full_grid ? h->ncu : (int)(tiles < 1 ? 1 : tiles < h->ncu ? tiles : h->ncu);
+  if (int rc = bic_forward_reduce(h, b)) return rc;
   if (int rc = prof_start(h)) return rc;
   if (h->route == Route::fused8) {
     if (int rc = fused8_launch(h, a, grid)) return rc;
@@ -990,6 +1030,7 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& 
   const int grid = h->ncu, P = h->net.P;
   const int sgrid = (int)((b.n_k + 255) / 256);
   if (int rc = ensure(&h->tp_losspart, &h->tp_losspart_cap, (long)(grid + sgrid) * 3)) return rc;
+  if (int rc = bic_forward_reduce(h, b)) return rc;
   float* lp = h->tp_losspart;
   VnFusedArgs f = fused_args(h, &b);
   f.X = b.Input; f.G = batch_gcoef(h, b); f.nT = b.n_k * h->cfg.integ_num; f.nB = 0;     // BC/IC: step 3
@@ -1027,6 +1068,7 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
   const int grid = h->ncu, P = h->net.P;
   const int sblk = (int)((b.n_k + VN_DEDUP_TFB - 1) / VN_DEDUP_TFB);
   float* lp = h->dd_losspart;                       // [grid + sblk][3]
+  if (int rc = bic_forward_reduce(h, b)) return rc;
   // vn_profile_*: HIP events around the formulation's whole kernel sequence (steps 1-4; the reduction stays outside as
   // in the row-wise step)
   if (int rc = prof_start(h)) return rc;
@@ -1100,6 +1142,7 @@ void learnt_free(vn_engine* h, int id) {
   if (id == LV_COEF) drop(h->cl_acc, h->cl_acc_cap);
   if (id == LV_SRC) drop(h->sl_mix, h->sl_mix_cap);
   if (id == LV_FLD) { drop(h->fl_mix, h->fl_mix_cap); drop(h->fl_csr, h->fl_csr_cap); drop(h->fl_pack, h->fl_pack_cap); }
+  if (id == LV_BIC) drop(h->bl_mix, h->bl_mix_cap);
   v = Learnt{};
 }
 
@@ -1155,6 +1198,21 @@ int field_mix(vn_engine* h, const Batch& b, int batch) {
     if (int rc = ensure(&h->fl_csr, &h->fl_csr_cap, n)) return rc;
     HIPCHK(vn_dedup_permute_launch(h->fl_mix, b.rowidx, h->fl_csr, b.n_k * h->cfg.integ_num, h->cfg.dim, h->stream));
   }
+  return VN_OK;
+}
+
+// Boundary / initial amplitudes, first thing in an evaluation of batch b: the basis of the BC/IC set the batch reads must be the
+// engine's, then the labels are formed -- all nBreg of them, so a stream keeps its stride; a steady engine reads the first bDof
+int bic_mix(vn_engine* h, const Batch& b, int batch) {
+  if (!bic_learnt(h, b)) return VN_OK;
+  if (bic_basis_J(h, b) != h->lv[LV_BIC].J)
+    return fail(VN_EINVAL, "the BC/IC rows of batch %d have a basis of %d streams, the learnt amplitudes (vn_set_bic_learn) are %d", batch,
+                bic_basis_J(h, b), h->lv[LV_BIC].J);
+  if (h->nBreg <= 0) return VN_OK;
+  if (int rc = ensure(&h->bl_mix, &h->bl_mix_cap, h->nBreg)) return rc;
+  VnMixArgs a{};
+  a.base = bi_y0(h, b); a.stream = bic_basis(h, b); a.amp = h->lv[LV_BIC].state; a.J = h->lv[LV_BIC].J; a.n = h->nBreg; a.out = h->bl_mix;
+  HIPCHK(vn_learnt_mix_launch(a, h->stream));
   return VN_OK;
 }
 
@@ -1506,6 +1564,7 @@ int vn_set_interior(vn_engine* h, int32_t batch, const float* Input, const float
   b.biInput = nullptr; b.biLabel = nullptr;                                            // ... and vn_set_batch_bic
   b.sb_phi = nullptr; b.sb_J = 0;                                                      // ... and vn_set_source_basis
   b.fb_G = nullptr; b.fb_J = 0;                                                        // ... and vn_set_field_basis
+  b.bb_B = nullptr; b.bb_J = 0;                                                        // ... and vn_set_bic_basis of its own copy
   const Batch fresh;
   b.react = fresh.react; b.nlflux = fresh.nlflux; b.nldiff = fresh.nldiff;             // ... and the three term setters
   clear_weights(b);                                                                    // ... and vn_set_tf_weights / vn_set_causal
@@ -1786,6 +1845,40 @@ int vn_set_field_learn(vn_engine* h, int32_t J, const int32_t* mask, const doubl
 int vn_get_field_amps(vn_engine* h, double* amp, double* grad, int32_t J) { return learnt_get(h, LV_FLD, amp, grad, J); }
 int vn_set_field_amps(vn_engine* h, const double* amp, int32_t J) { return learnt_put(h, LV_FLD, amp, J); }
 
+// ---- boundary data identification: basis streams of the BC/IC labels per row set, amplitudes on the device (vn_learnt.hip) ----
+int vn_set_bic_basis(vn_engine* h, int32_t batch, const float* B_dev, int32_t J) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (batch < -1) return fail(VN_EINVAL, "batch index %d out of range (-1: the rows of vn_set_bic)", batch);
+  if (batch >= 0 && (batch >= (int)h->batches.size() || !h->batches[batch].set))
+    return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
+  const float** B = batch < 0 ? &h->bicB : &h->batches[batch].bb_B;
+  int* Jreg = batch < 0 ? &h->bicJ : &h->batches[batch].bb_J;
+  h->snap_step = -1;
+  if (batch < 0) lbfgs_invalidate(h); else lbfgs_invalidate(h, batch);
+  *B = nullptr; *Jreg = 0;                         // a call replaces the previous registration, also when it fails
+  if (!B_dev || J == 0) return VN_OK;
+  if (J < 0 || J > VN_BIC_MAX) return fail(VN_EINVAL, "a BC/IC basis has 1 to %d streams, got %d", VN_BIC_MAX, J);
+  if (batch >= 0 && !h->batches[batch].biLabel)
+    return fail(VN_ESTATE, "batch %d has no BC/IC rows of its own (call vn_set_batch_bic first, or pass batch = -1 for the rows of vn_set_bic)", batch);
+  if (h->nBreg <= 0) return fail(VN_EINVAL, "no BC/IC rows are registered (vn_set_bic): no label to mix");
+  *B = B_dev; *Jreg = J;
+  return VN_OK;
+}
+
+// what vn_set_bic_learn refuses on its own
+static int bic_learn_checks(vn_engine* h) {
+  if (h->route == Route::fused4)
+    return fail(VN_EUNSUPPORTED, "learnt boundary and initial amplitudes are not built for VN_KERNEL_FUSED (the 4-wave cross-check "
+                                 "geometry): its single launch leaves no values of the BC/IC rows to reduce; every other kernel family carries them");
+  return VN_OK;
+}
+
+int vn_set_bic_learn(vn_engine* h, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi, double lr) {
+  return learnt_set_learn(h, LV_BIC, J, mask, init, lo, hi, lr, bic_learn_checks);
+}
+int vn_get_bic_amps(vn_engine* h, double* amp, double* grad, int32_t J) { return learnt_get(h, LV_BIC, amp, grad, J); }
+int vn_set_bic_amps(vn_engine* h, const double* amp, int32_t J) { return learnt_put(h, LV_BIC, amp, J); }
+
 // vn_set_tf_weights / vn_set_causal: what both check before they touch the batch; *clear: the call unregisters
 static int weights_common(vn_engine* h, int32_t batch, bool clear, const char* who) {
   if (!h) return fail(VN_EINVAL, "null handle");
@@ -1887,6 +1980,8 @@ int vn_set_bic(vn_engine* h, const float* biInput, const float* biLabel, int64_t
   if (nB > 0 && (!biInput || !biLabel)) return fail(VN_EINVAL, "null argument");
   HIPCHK(hipSetDevice(h->cfg.device));
   // a steady problem has no initial condition (TFModel.py:646-650): rows behind bDof are never part of its loss
+  h->nBreg = nB;
+  h->bicB = nullptr; h->bicJ = 0;                    // the shared set's basis goes with it (vn_set_bic_basis)
   if (!h->cfg.time_dependent) nB = bDof;
   h->biInput = biInput; h->biLabel = biLabel; h->nB = nB; h->bDof = bDof; h->biDimVal = biDimVal;
   lbfgs_invalidate(h);
@@ -1996,6 +2091,7 @@ int vn_set_batch_bic(vn_engine* h, int32_t batch, const float* biInput, const fl
   if ((biInput == nullptr) != (biLabel == nullptr)) return fail(VN_EINVAL, "biInput and biLabel must be given together");
   h->batches[batch].biInput = biInput;
   h->batches[batch].biLabel = biLabel;
+  h->batches[batch].bb_B = nullptr; h->batches[batch].bb_J = 0;     // the copy's basis goes with it (vn_set_bic_basis)
   lbfgs_invalidate(h, batch);
   return VN_OK;
 }
@@ -2025,6 +2121,7 @@ int vn_grad(vn_engine* h, int32_t batch) {
   if (has_weights(b)) return learnt_weights_refusal(*learnt, batch);
   if (int rc = source_mix(h, b, batch)) return rc;
   if (int rc = field_mix(h, b, batch)) return rc;
+  if (int rc = bic_mix(h, b, batch)) return rc;
   for (Learnt& v : h->lv) v.blocks = 0;
   if (int rc = grad_route(h, b)) return rc;
   // after every kernel that reads the coefficients, s_mix or the mixed gcoef (the parameters' update rides in the reduction above);
@@ -2260,6 +2357,7 @@ int vn_eval_loss(vn_engine* h, int32_t batch, double out[4], float* lossVec_dev)
   HIPCHK(hipSetDevice(h->cfg.device));
   if (int rc = source_mix(h, h->batches[batch], batch)) return rc;
   if (int rc = field_mix(h, h->batches[batch], batch)) return rc;
+  if (int rc = bic_mix(h, h->batches[batch], batch)) return rc;
   VnEdgeSums fx;
   if (int rc = edge_passes(h, false, &fx)) return rc;
   if (int rc = run_forward_and_seed(h, h->batches[batch], false, lossVec_dev, h->lossbuf, fx)) return rc;
@@ -2287,6 +2385,7 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   const Batch& b = h->batches[batch];
   if (int rc = source_mix(h, b, batch)) return rc;     // source identification: the mixed fp32 stream, widened exactly
   if (int rc = field_mix(h, b, batch)) return rc;      // field identification: likewise the mixed direction
+  if (int rc = bic_mix(h, b, batch)) return rc;        // boundary data identification: likewise the mixed labels
   VnObj64Problem p{};
   p.net = h->net; p.theta = theta_dev;
   p.X = b.Input; p.G = batch_gcoef(h, b); p.src = batch_src(h, b);

@@ -7,6 +7,7 @@
 // form in oracle/tangent_ref.py and follows the reference graph TFModel.py:536 (input gradient),
 // :653-661 (weak-form integrand), :709 (parameter gradient).
 #include "vn_internal.h"
+#include "vn_bicseed.h"
 #include "vn_blocksum.h"
 #include "vn_edge.h"
 
@@ -374,12 +375,7 @@ __global__ __launch_bounds__(NTHREADS) void vn_seed_kernel(VnSeedArgs a) {
     const float e2 = a.biDimVal * e * e;             // TFModel.py:643
     const bool isbc = k < a.bDof;
     if (isbc) bc = e2; else ic = e2;
-    if (a.ubar_b) {
-      const long nI = a.nB - a.bDof;
-      const float cb = 2.f * a.w0 * a.biDimVal / (float)a.bDof;
-      const float ci = nI > 0 ? 2.f * a.w1 * a.biDimVal / (float)nI : 0.f;
-      a.ubar_b[k] = (isbc ? cb : ci) * e;
-    }
+    if (a.ubar_b) a.ubar_b[k] = vn_bic_value_seed(k, e, a.nB, a.bDof, a.biDimVal, a.w0, a.w1);
   }
   const float s0 = block_sum(lv, red);
   const float s1 = block_sum(bc, red);

@@ -1,18 +1,19 @@
 // Host-side declarations of vn_learnt.hip: the vectors learnt next to the parameters -- the nine polynomial coefficients of
 // vn_terms.hip (vn_set_coef_learn; index 0..2 reaction, 3..5 flux, 6..8 diffusivity), the source amplitudes (vn_set_source_learn)
-// and the field amplitudes (vn_set_field_learn) -- their mix, their gradient reductions and their Adam step.  Kept out of
-// vn_internal.h, which every kernel's source hash covers.
+// the field amplitudes (vn_set_field_learn) and the boundary / initial amplitudes (vn_set_bic_learn) -- their mix, their gradient
+// reductions and their Adam step.  Kept out of vn_internal.h, which every kernel's source hash covers.
 #pragma once
 #include "vn_internal.h"
 
 constexpr int VN_COEF_N = 9;
 constexpr int VN_SRC_JMAX = 64;              // == VN_SRC_MAX of the public header
 constexpr int VN_FLD_JMAX = 32;              // == VN_FLD_MAX of the public header
+constexpr int VN_BIC_JMAX = 64;              // == VN_BIC_MAX of the public header
 constexpr int VN_LEARNT_JG = 8;              // streams one workgroup of an amplitude reduction carries
 constexpr int VN_LEARNT_MAXBLK = 256;        // cap of every reduction grid along the rows: a partial sums a fixed set of rows
 
 // out[r] = base[r] + sum_j amp[j] stream[j, r]: fp32, from base[r], j ascending, one fused multiply-add per stream.  The source of
-// a batch (n = nT) and its tangent direction gcoef (n = nT dim) are both formed by it.
+// a batch (n = nT), its tangent direction gcoef (n = nT dim) and the labels of a BC/IC row set (n = nB) are all formed by it.
 struct VnMixArgs {
   const float* base;                         // [n]
   const float* stream;                       // [J, n] stream-major
@@ -78,6 +79,21 @@ struct VnFldGradArgs {
   float* part;                               // [blocks, J] out
 };
 hipError_t vn_fldgrad_rows_launch(const VnFldGradArgs& a, int* blocks, hipStream_t s);
+
+// ---- boundary / initial amplitudes.  part[b, j] = - sum_{k in block b's rows} ubar_b[k] B[j, k] for the masked j (0 for the
+// others), over the rows k < (steady ? bDof : nB); ubar_b[k] = vn_bic_value_seed(k, ub[k] - label[k], ...) of vn_bicseed.h, the
+// value vn_seed_kernel stores for the row.  After the forward of the BC/IC rows, on every route; reads no seed buffer.
+struct VnBicGradArgs {
+  const float* ub;                           // [rows] network value per BC/IC row
+  const float* label;                        // [nB] the mixed label the step reads
+  const float* B;                            // [J, nB] stream-major
+  int J; long nB, bDof;                      // nB: rows of a stream (and the stride between two)
+  int steady;                                // the problem has no initial rows: [bDof, nB) are never evaluated
+  float biDimVal, w0, w1;
+  unsigned long long mask;                   // bit j: amplitude j is learnt
+  float* part;                               // [blocks, J] out
+};
+hipError_t vn_bicgrad_launch(const VnBicGradArgs& a, int* blocks, hipStream_t s);
 
 // ---- every vector.  One block: grad[j] = sum over the [blocks, J] partials in fp64 (blocks > 0; else grad as it stands), then
 // with `update` the Adam step of the masked entries and the clamp.  `lanes` (16 or 64) is the fold's lane-group width: 256 / lanes

@@ -6,8 +6,11 @@
 //   field amplitudes (vn_set_field_*)    the tangent direction of a batch is gcoef_r = g0_r + sum_j b_j G_j[r, :] over J <= 32
 //                                        streams of dim floats per row (G_j = chi_j dN/dx for a diffusivity stream, omega_j N for a
 //                                        velocity stream; the engine does not know which is which).
+//   boundary / initial amplitudes        the labels of a BC/IC row set are label0[k] + sum_j a_j B_j[k] over J <= 64 per-row streams
+//   (vn_set_bic_*)                       (a Dirichlet basis stream is zero on the initial rows and on other edges, an initial one on
+//                                        the boundary rows; the engine does not know which is which).
 // Mix (vn_learnt_mix_kernel and its 4-row form): base + Sum_j amp[j] stream[j], which every kernel of the step then reads in
-// place of the batch's source (n = nT) or gcoef (n = nT dim).
+// place of the batch's source (n = nT), gcoef (n = nT dim) or BC/IC labels (n = nB).
 //
 // Gradients.  With u_r, A_r = grad u_r . gcoef_r, N_p, rate_r, phi_r as in vn_terms.hip's header, the row integrand is
 // t_r = D(u_r) A_r - (source + reaction) N_p - flux (D = 1 without vn_set_nldiff), and seed_r is the tangent seed of row r:
@@ -16,6 +19,8 @@
 //   d loss / d d_m = + sum_r seed_r A_r u_r^m            m = 0, 1, 2
 //   d loss / d a_j = - sum_r seed_r N_p phi_j[r]
 //   d loss / d b_j = + sum_r seed_r (grad u_r . G_j[r, :])
+// and over the BC/IC rows k, with ubar_b[k] the value seed of row k (vn_bicseed.h; the label enters through u_b[k] - label[k] only),
+//   d loss / d a_j = - sum_k ubar_b[k] B_j[k]       k < bDof on a steady problem, whose initial rows are never evaluated
 // Where each reads its seed.  The coefficients and the source read udbar[r] as vn_seed_kernel writes it (2 w2 detJ R_k W_p), BEFORE
 // vn_nldiff_seed_kernel rescales it by D(u); the field reads it AFTER that rescale (its integrand carries D(u)).  On the
 // de-duplicated step the source takes seed_r = stf[r / q] W_p with stf the per-test-function seed of vn_dedup_seed_kernel, the
@@ -31,6 +36,7 @@
 // give the same bits.  The amplitude reductions run on a grid (row blocks, ceil(J / 8)): a workgroup carries eight streams and
 // re-reads the seed once per group.  All HBM-bound.  The source and the field reduction stay two kernels over the shared helpers:
 // the source has a 4-row form with its own weight paths, the field a record load and DIM products per stream.
+#include "vn_bicseed.h"
 #include "vn_blocksum.h"
 #include "vn_learnt.h"
 #include "vn_rows4.h"
@@ -240,6 +246,23 @@ __global__ __launch_bounds__(TB) void vn_fldgrad_rows_kernel(VnFldGradArgs a) {
   write_group(acc, m, false, j0, a.J, a.part);
 }
 
+// ---- boundary / initial amplitudes ----
+// (one row per thread: nB is small against nT and the launch, not the bytes, is what the step pays -- DESIGN.md section 27)
+__global__ __launch_bounds__(TB) void vn_bicgrad_kernel(VnBicGradArgs a) {
+  const int j0 = blockIdx.y * JG;
+  const unsigned m = group_mask(a, j0);
+  const long rows = a.steady ? a.bDof : a.nB;
+  float acc[JG] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (m)
+    for (long k = (long)blockIdx.x * TB + threadIdx.x; k < rows; k += (long)gridDim.x * TB) {
+      const float w = vn_bic_value_seed(k, a.ub[k] - a.label[k], rows, a.bDof, a.biDimVal, a.w0, a.w1);
+#pragma unroll
+      for (int c = 0; c < JG; ++c)
+        if (m >> c & 1u) acc[c] += w * a.B[(long)(j0 + c) * a.nB + k];
+    }
+  write_group(acc, m, true, j0, a.J, a.part);
+}
+
 // ---- fold, Adam step, clamp ----
 // TB / LANES groups of LANES lanes: lane j < J of group g adds the partials of the blocks [g chunk, (g + 1) chunk) in index order,
 // then thread j adds the group sums in group order.  (16 lanes for the nine coefficients, 64 for the amplitudes: the order each
@@ -323,6 +346,14 @@ hipError_t vn_fldgrad_rows_launch(const VnFldGradArgs& a, int* blocks, hipStream
     case 2: hipLaunchKernelGGL(vn_fldgrad_rows_kernel<2>, grid, dim3(TB), 0, s, a); break;
     default: hipLaunchKernelGGL(vn_fldgrad_rows_kernel<3>, grid, dim3(TB), 0, s, a); break;
   }
+  return hipGetLastError();
+}
+
+hipError_t vn_bicgrad_launch(const VnBicGradArgs& a, int* blocks, hipStream_t s) {
+  if (a.J < 1 || a.J > VN_BIC_JMAX || a.bDof < 0 || a.bDof > a.nB) return hipErrorInvalidValue;
+  *blocks = learnt_blocks(a.steady ? a.bDof : a.nB);
+  const dim3 grid((unsigned)*blocks, (unsigned)((a.J + JG - 1) / JG));
+  hipLaunchKernelGGL(vn_bicgrad_kernel, grid, dim3(TB), 0, s, a);
   return hipGetLastError();
 }
 

@@ -88,6 +88,11 @@ _SIGS = {
                                      C.POINTER(C.c_double), C.c_double]),
     'vn_get_field_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32]),
     'vn_set_field_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
+    'vn_set_bic_basis': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    'vn_set_bic_learn': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double), C.c_double]),
+    'vn_get_bic_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32]),
+    'vn_set_bic_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
     'vn_set_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_bind_grad_buffer': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vn_grad': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -130,7 +135,7 @@ ABI_SYMBOLS = tuple(_SIGS.keys())
 # the _keep keys of the three polynomial terms, in the order of the coefficient index (vn_set_coef_learn)
 COEF_TERMS = ('react', 'nlflux', 'nldiff')
 # the learnt vectors: the name vn_get_* / vn_set_* carry, and the fixed length (None: the ABI takes the length J)
-LEARNT = {'coef': ('coefs', 9), 'source': ('source_amps', None), 'field': ('field_amps', None)}
+LEARNT = {'coef': ('coefs', 9), 'source': ('source_amps', None), 'field': ('field_amps', None), 'bic': ('bic_amps', None)}
 
 
 class VNError(RuntimeError):
@@ -398,8 +403,9 @@ class VNEngine:
         self._keep[('int', batch)] = (Input, gcoef, source, detJv, Nr, dNr)
         self._ck(self.lib.vn_set_interior(self.h, batch, _ptr(Input), _ptr(gcoef), _ptr(source), n_k,
                                           _ptr(detJv), detJ_s, _ptr(Nr), _ptr(dNr)))
-        for key in ('react', 'nlflux', 'nldiff', 'tfw', 'causal', 'srcbasis', 'fldbasis'):   # vn_set_interior cleared the batch's three
-            self._keep.pop((key, batch), None)      # polynomial terms, its per-test-function loss weights, its source and field bases
+        for key in ('react', 'nlflux', 'nldiff', 'tfw', 'causal', 'srcbasis', 'fldbasis', 'bicbasis'):   # vn_set_interior cleared the
+            self._keep.pop((key, batch), None)      # batch's three polynomial terms, its per-test-function loss weights, its source
+                                                    # and field bases and the basis of its own BC/IC copy
 
     def set_dedup(self, batch, Xu=None, uid=None, rowptr=None, rowidx=None):
         """Register (or, with Xu=None, clear) the de-duplicated formulation of `batch`."""
@@ -426,6 +432,7 @@ class VNEngine:
 
     def set_bic(self, biInput, biLabel, bDof, biDimVal):
         self._bic_key = None
+        self._keep.pop(('bicbasis', -1), None)     # vn_set_bic clears the shared set's basis
         if biInput is None or len(biInput) == 0:
             self._keep['bic'] = None
             self._ck(self.lib.vn_set_bic(self.h, None, None, 0, 0, float(biDimVal)))
@@ -438,6 +445,7 @@ class VNEngine:
 
     def set_batch_bic(self, batch, biInput=None, biLabel=None):
         """Per-batch copy of the BC/IC rows (the reference's shuffle permutes them per feed); None returns to the shared set."""
+        self._keep.pop(('bicbasis', batch), None)  # vn_set_batch_bic clears the copy's basis
         if biInput is None:
             self._keep.pop(('bbic', batch), None)
             self._ck(self.lib.vn_set_batch_bic(self.h, batch, None, None))
@@ -619,12 +627,15 @@ class VNEngine:
             return
         if not isinstance(streams, self.torch.Tensor):
             streams = np.asarray(streams, dtype=np.float32)
-        kept = self._keep.get(('int', batch))
+        # the rows a stream runs over: the batch's interior rows, or for the BC/IC labels the rows of the set they belong to
+        kept = (self._keep.get('bic') if batch < 0 else self._keep.get(('bbic', batch))) if key == 'bicbasis' \
+            else self._keep.get(('int', batch))
         J = int(streams.shape[0])
         streams = self.dev(streams.reshape(J, -1, *trailing))
         # the ABI carries a pointer only: the length the kernels rely on is checked here
         assert kept is None or streams.shape[1] == kept[0].shape[0], \
-            'every basis stream must have one entry per interior row (%s != %s)' % (streams.shape[1], kept[0].shape[0])
+            'every basis stream must have one entry per %s row (%s != %s)' % ('BC/IC' if key == 'bicbasis' else 'interior',
+                                                                             streams.shape[1], kept[0].shape[0])
         self._keep.pop((key, batch), None)         # (a failed call leaves the batch without a basis)
         self._ck(fn(self.h, int(batch), _ptr(streams), J))
         self._keep[(key, batch)] = streams
@@ -681,6 +692,25 @@ class VNEngine:
     def set_field_amps(self, amp):
         """Overwrite the amplitudes (vn_set_field_amps): rounded to fp32, not clamped; the Adam slots stay."""
         self._set_learnt('field', amp)
+
+    def set_bic_basis(self, batch, B=None):
+        """Register (B=None: clear) the basis of the BC/IC labels (vn_set_bic_basis): batch=-1 for the rows of set_bic, else the
+        batch's own copy (after set_batch_bic of that batch).  B is [J, nB] (or J arrays of one value per BC/IC row), J <= 64."""
+        self._set_basis('bicbasis', self.lib.vn_set_bic_basis, batch, B, ())
+
+    def set_bic_learn(self, mask=None, init=None, lo=None, hi=None, lr=None):
+        """Boundary data identification (vn_set_bic_learn): learn the masked amplitudes a_j of the BC/IC label bases next to the
+        parameters.  mask: J booleans; init: the J starting values (unmasked entries keep theirs); lo / hi: the clamp (None:
+        unbounded; entries may be +-inf); lr: their Adam rate.  mask=None switches learning off and frees everything."""
+        self._set_learn('bic', mask, init, lo, hi, lr)
+
+    def get_bic_amps(self, grad=False, J=None):
+        """The amplitudes at the current state (vn_get_bic_amps); grad=True: (amp, gradient of the last gradient evaluation)."""
+        return self._get_learnt('bic', grad, J)
+
+    def set_bic_amps(self, amp):
+        """Overwrite the amplitudes (vn_set_bic_amps): rounded to fp32, not clamped; the Adam slots stay."""
+        self._set_learnt('bic', amp)
 
     def _n_k(self, batch):
         kept = self._keep.get(('int', batch))

@@ -632,6 +632,8 @@ class ManageTrainData:
                     ix = torch.as_tensor(perm, device=eng.device, dtype=torch.long)
                     eng.set_batch_bic(self.engine_batch(mb, bi), d['biInput'].index_select(0, ix),
                                       d['biLabel'].index_select(0, ix))
+                    if d.get('bicB') is not None:         # the copy's basis: the same permutation of the columns
+                        eng.set_bic_basis(self.engine_batch(mb, bi), d['bicB'].index_select(1, ix).contiguous())
 
     def _upload_perm(self, torch, device):
         """Test-function permutation -> device.  On the GPU through one of two persistent pinned buffers and an
@@ -796,6 +798,8 @@ class ManageTrainData:
             return
         d = self.mor[mb]
         eng.set_bic(d['biInput'], d['biLabel'], self.bDofsum, self.biDimVal)
+        if d.get('bicB') is not None:             # the basis of these labels (vn_set_bic_basis, the shared set)
+            eng.set_bic_basis(-1, d['bicB'])
         eng._bic_key = (key, mb)
 
 
@@ -806,7 +810,7 @@ class VarNet:
                  integPnum=2, optimizer='adam', learning_rate=0.001, fluxBC=False, lbfgsLoss64=False,
                  causal=None, causalSlabs=None, periodicDeriv=None, observations=None, obsWeight=None,
                  learnCoef=None, coefLr=None, coefBounds=None, learnSource=None, sourceLr=None, sourceBounds=None,
-                 learnField=None, fieldLr=None, fieldBounds=None):
+                 learnField=None, fieldLr=None, fieldBounds=None, learnBic=None, bicLr=None, bicBounds=None):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -869,7 +873,7 @@ class VarNet:
                 raise ValueError('periodicDeriv=%r must be a finite number >= 0' % (periodicDeriv,))
 
         learnt = {'learnCoef': (learnCoef, coefLr, coefBounds), 'learnSource': (learnSource, sourceLr, sourceBounds),
-                  'learnField': (learnField, fieldLr, fieldBounds)}
+                  'learnField': (learnField, fieldLr, fieldBounds), 'learnBic': (learnBic, bicLr, bicBounds)}
         for lv in self.LEARNT:
             if learnt[lv.option][0] is not None and MORvar is not None:
                 raise NotImplementedError('%s with model-order reduction is not supported: neither %s nor the observations it needs '
@@ -885,10 +889,11 @@ class VarNet:
                                           'assembled once, for all parameter batches, and carry no parameter inputs')
             self._check_obs_weight(1.0 if obsWeight is None else obsWeight)
 
-        # learnCoef=..., learnSource=..., learnField=... (extensions; no reference counterpart): inverse mode, source and field
-        # identification -- the masked polynomial coefficients of the PDE's reaction / flux / diffusivity, the masked amplitudes of
-        # its source basis, and those of its diffusivity and velocity bases are learnt next to the network from the observations
-        # (`coefLearnData`, `sourceLearnData`, `fieldLearnData`)
+        # learnCoef=..., learnSource=..., learnField=..., learnBic=... (extensions; no reference counterpart): inverse mode, source,
+        # field and boundary data identification -- the masked polynomial coefficients of the PDE's reaction / flux / diffusivity,
+        # the masked amplitudes of its source basis, those of its diffusivity and velocity bases and those of its Dirichlet and
+        # initial bases are learnt next to the network from the observations (`coefLearnData`, `sourceLearnData`, `fieldLearnData`,
+        # `bicLearnData`)
         for lv in self.LEARNT:
             data = getattr(self, lv.parser)(PDE, *learnt[lv.option], learning_rate)
             setattr(self, lv.attr, data)
@@ -1030,6 +1035,10 @@ class VarNet:
             # likewise the field amplitudes: every batch registered later carries its [J, nT, dim] basis streams
             fl = self.fldLearn
             self.engine.set_field_learn(fl['mask'], fl['init'], fl['lo'], fl['hi'], fl['lr'])
+        if self.bicLearn is not None:
+            # likewise the boundary and initial amplitudes: every BC/IC row set registered later carries its [J, nB] basis streams
+            bl = self.bicLearn
+            self.engine.set_bic_learn(bl['mask'], bl['init'], bl['lo'], bl['hi'], bl['lr'])
         self.tfData = self.engine       # name kept for scripts that poke at `VarNet.tfData`
         from .launch import mark_stage
         mark_stage('engine_ready')      # past the launcher's bootstrap deadline: a rank that trains for hours is healthy
@@ -1090,7 +1099,9 @@ class VarNet:
         LearntVector('learnSource', 'sourceLearnData', 'srcLearn', 'amplitude', 'the source basis',
                      'the amplitude gradients', 'source_amplitudes', 'source_amps', 'Learnt source amplitudes'),
         LearntVector('learnField', 'fieldLearnData', 'fldLearn', 'amplitude', 'the field bases',
-                     'the amplitude gradients', 'field_amplitudes', 'field_amps', 'Learnt field amplitudes (diff, then vel)'))
+                     'the amplitude gradients', 'field_amplitudes', 'field_amps', 'Learnt field amplitudes (diff, then vel)'),
+        LearntVector('learnBic', 'bicLearnData', 'bicLearn', 'amplitude', 'the boundary and initial bases',
+                     'the amplitude gradients', 'bic_amplitudes', 'bic_amps', 'Learnt boundary and initial amplitudes (bc, then ic)'))
 
     # -- what the three learnt vectors' options share (coefLearnData, sourceLearnData, fieldLearnData) --
     @staticmethod
@@ -1405,6 +1416,138 @@ class VarNet:
                 raise ValueError('setFieldAmplitudes[%r] takes %d finite numbers, got %r' % (key, J, amps[key]))
             cur[sl] = v
         self.engine.set_field_amps(cur)
+
+    # -- boundary data identification: learnt amplitudes of a Dirichlet and an initial basis (extension) -----
+    BIC_KEYS = ('bc', 'ic')
+
+    @staticmethod
+    def _bic_sizes(PDE):
+        """(J_bc, J_ic): the number of functions of the PDE's Dirichlet and initial bases (0 without one)."""
+        return len(getattr(PDE, 'bcBasis', None) or []), len(getattr(PDE, 'icBasis', None) or [])
+
+    @staticmethod
+    def bicLearnData(PDE, learnBic, bicLr=None, bicBounds=None, learning_rate=0.001):
+        """(No reference counterpart: `VarNet(..., learnBic=...)`.)  The registration of `vn_set_bic_learn`, or None without
+        learnBic: mask, init, lo, hi (J = J_bc + J_ic entries each, the Dirichlet streams first) and lr.  learnBic =
+        {'bc': True | mask, 'ic': True | mask} (a key left out: none of that basis is learnt); the PDE's bcAmp / icAmp are the
+        initial guess; bicLr defaults to the network's learning rate; bicBounds = {'bc': ..., 'ic': ...}, each (lo, hi) for
+        every learnt amplitude of that basis or a list with one entry per function, each None or (lo, hi), None for an open side."""
+        if learnBic is None or learnBic is False:
+            if bicLr is not None:
+                raise ValueError('bicLr=%r is an option of learnBic=...' % (bicLr,))
+            if bicBounds is not None:
+                raise ValueError('bicBounds is an option of learnBic=...')
+            return None
+        keys = VarNet.BIC_KEYS
+        if not isinstance(learnBic, dict) or not learnBic or any(k not in keys for k in learnBic):
+            raise ValueError('learnBic must be a dict {\'bc\': True | mask, \'ic\': True | mask}, got %r' % (learnBic,))
+        if bicBounds is not None and (not isinstance(bicBounds, dict) or any(k not in keys for k in bicBounds)):
+            raise ValueError('bicBounds must be a dict {\'bc\': ..., \'ic\': ...}, got %r' % (bicBounds,))
+        Jb, Ji = VarNet._bic_sizes(PDE)
+        masks, a0s, los, his = [], [], [], []
+        for key, J, amp in (('bc', Jb, 'bcAmp'), ('ic', Ji, 'icAmp')):
+            sel = learnBic.get(key)
+            if sel is not None and sel is not False and J == 0:
+                raise ValueError('learnBic[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (key, key, key))
+            if J == 0:
+                if bicBounds is not None and bicBounds.get(key) is not None:
+                    raise ValueError('bicBounds[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (key, key, key))
+                continue
+            if sel is None or sel is False:
+                mask = np.zeros(J, dtype=bool)
+            else:
+                mask = VarNet._learn_mask(sel, J, 'learnBic[%r] must be True or a mask of %d booleans (one per function of %sBasis), '
+                                          'got %r' % (key, J, key, sel))
+            a0 = np.asarray(getattr(PDE, amp), dtype=np.float64)
+            bounds = None if bicBounds is None else bicBounds.get(key)
+            lo, hi = VarNet._learn_bounds(bounds, 'bicBounds[%r]' % (key,), mask, a0, 'an amplitude', 'learnBic',
+                                          'bicBounds[%r] must be (lo, hi) or a list of %d entries, each None or (lo, hi), got %r'
+                                          % (key, J, bounds))
+            masks.append(mask); a0s.append(a0); los.append(lo); his.append(hi)
+        mask = np.concatenate(masks) if masks else np.zeros(0, dtype=bool)
+        if not mask.any():
+            raise ValueError('learnBic selects no amplitude')
+        lr = VarNet._learn_rate(bicLr, 'bicLr', learning_rate)
+        return dict(mask=[int(x) for x in mask], init=np.concatenate(a0s), lo=np.concatenate(los), hi=np.concatenate(his),
+                    lr=lr, Jb=Jb, Ji=Ji)
+
+    def _bic_basis(self, biInput, biDof):
+        """The PDE's Dirichlet and initial basis functions at the BC/IC rows, [J_bc + J_ic, nB] in fp64 (the Dirichlet streams
+        first): a gamma_j evaluated like `g` on the rows of its own indicator and zero elsewhere, an iota_j evaluated like `IC`
+        on the initial rows and zero on the boundary rows."""
+        dim, PDE = self.dim, self.PDE
+        td = PDE.timeDependent
+        nB = biInput.shape[0]
+        Jb, Ji = self._bic_sizes(PDE)
+        B = np.zeros((Jb + Ji, nB), dtype=np.float64)
+        span, indp, j = {}, 0, 0
+        for bInd in range(PDE.domain.bIndNum):            # the rows of each Dirichlet indicator, as biTrainData walks them
+            if PDE.BCtype[bInd] != 'Dirichlet':
+                continue
+            span[bInd] = (indp, indp + biDof[j])
+            indp += biDof[j]
+            j += 1
+        for j, (bInd, f) in enumerate(getattr(PDE, 'bcBasis', None) or []):
+            i0, i1 = span[bInd]
+            targ = [biInput[i0:i1, dim][np.newaxis].T] if td else []
+            v = np.asarray(f(biInput[i0:i1, :dim], *targ), dtype=np.float64)
+            if v.size != i1 - i0:
+                raise ValueError('bcBasis[%d] must return one value per point (a column), got shape %s for %d points'
+                                 % (j, v.shape, i1 - i0))
+            B[j, i0:i1] = v.reshape(-1)
+        for j, f in enumerate(getattr(PDE, 'icBasis', None) or []):
+            v = np.asarray(f(biInput[indp:, :dim]), dtype=np.float64)
+            if v.size != nB - indp:
+                raise ValueError('icBasis[%d] must return one value per point (a column), got shape %s for %d points'
+                                 % (j, v.shape, nB - indp))
+            B[Jb + j, indp:] = v.reshape(-1)
+        return B
+
+    def _bic_vector(self):
+        """The J = J_bc + J_ic amplitudes as one vector: the engine's with learnBic, else the PDE's."""
+        Jb, Ji = self._bic_sizes(self.PDE)
+        if getattr(self, 'bicLearn', None) is not None and getattr(self, 'engine', None) is not None:
+            return np.asarray(self.engine.get_bic_amps(J=Jb + Ji), dtype=np.float64)
+        return np.concatenate([np.asarray(getattr(self.PDE, 'bcAmp', []), dtype=np.float64),
+                               np.asarray(getattr(self.PDE, 'icAmp', []), dtype=np.float64)])
+
+    def bicAmplitudes(self):
+        """{'bc': J_bc amplitudes, 'ic': J_ic amplitudes} of the PDE's Dirichlet and initial bases at the current state: the
+        learnt values with learnBic, else the PDE's."""
+        Jb, Ji = self._bic_sizes(self.PDE)
+        if Jb + Ji == 0:
+            raise ValueError('bicAmplitudes: the PDE has no Dirichlet or initial basis (ADPDE(..., bcBasis=[...], icBasis=[...]))')
+        v = self._bic_vector()
+        return {'bc': v[:Jb].copy(), 'ic': v[Jb:].copy()}
+
+    def bicGrad(self):
+        """d loss / d amplitude of the last gradient evaluation as {'bc': ..., 'ic': ...} (zeros where not learnt)."""
+        if self.bicLearn is None:
+            raise ValueError('bicGrad: this instance learns no boundary or initial amplitudes (learnBic=...)')
+        Jb, Ji = self._bic_sizes(self.PDE)
+        g = np.asarray(self.engine.get_bic_amps(grad=True, J=Jb + Ji)[1], dtype=np.float64)
+        return {'bc': g[:Jb].copy(), 'ic': g[Jb:].copy()}
+
+    def setBicAmplitudes(self, amps):
+        """Overwrite amplitudes between train() calls: {'bc': [...], 'ic': [...]} (a key left out keeps its values).  Not
+        clamped to bicBounds (the next update is)."""
+        if self.bicLearn is None:
+            raise ValueError('setBicAmplitudes: this instance learns no boundary or initial amplitudes (learnBic=...)')
+        if not isinstance(amps, dict) or not amps or any(k not in self.BIC_KEYS for k in amps):
+            raise ValueError('setBicAmplitudes takes a dict {\'bc\': [...], \'ic\': [...]}, got %r' % (amps,))
+        Jb, Ji = self._bic_sizes(self.PDE)
+        cur = self._bic_vector()
+        for key, sl, J in (('bc', slice(0, Jb), Jb), ('ic', slice(Jb, Jb + Ji), Ji)):
+            if key not in amps:
+                continue
+            try:
+                v = np.asarray(amps[key], dtype=np.float64).reshape(-1)
+            except (TypeError, ValueError):
+                v = np.empty(0)
+            if J == 0 or v.size != J or not np.all(np.isfinite(v)):
+                raise ValueError('setBicAmplitudes[%r] takes %d finite numbers, got %r' % (key, J, amps[key]))
+            cur[sl] = v
+        self.engine.set_bic_amps(cur)
 
     # -- causal time-slab weights (extension) ------------------------------------------------------
     @staticmethod
@@ -1817,8 +1960,9 @@ class VarNet:
         d = np.vstack(dirs)
         return dict(X=np.vstack(XA + XB), dir=np.vstack([d, d]), pairs=pairs)
 
-    def biTrainData(self, biInput, biDof, biArg=[]):
-        """Labels g/beta on Dirichlet edges, IC(x) on the initial slice (VarNet.py:649-722)."""
+    def biTrainData(self, biInput, biDof, biArg=[], basis=True):
+        """Labels g/beta on Dirichlet edges, IC(x) on the initial slice (VarNet.py:649-722).  With a Dirichlet or an initial basis
+        the sums at the current amplitudes (`bicAmplitudes`) are part of the labels; basis=False: `g/beta` and `IC` alone."""
         dim, PDE = self.dim, self.PDE
         td = PDE.timeDependent
         nb = PDE.domain.bIndNum
@@ -1840,6 +1984,8 @@ class VarNet:
         if td:
             arg = biArg[-1] if biArg[-1] is not None else {}
             out = uf.vstack([out, PDE.IC(biInput[ind:, :dim], **arg)])
+        if basis and sum(self._bic_sizes(PDE)) > 0:
+            out = np.asarray(out, dtype=np.float64).reshape(-1, 1) + (self._bic_vector() @ self._bic_basis(biInput, biDof)).reshape(-1, 1)
         return out
 
     def PDEinpData(self, Input, inpArg=[], basis=True, field=True):
@@ -1957,7 +2103,12 @@ class VarNet:
             biArg, inpArg, MORinp = [], [], None
         else:
             biArg, inpArg, MORinp = self.MORargExtract(batch, MORdiscArg)
-        biLabel = self.biTrainData(biInput, biDof, biArg)
+        # learnt boundary and initial amplitudes: the engine mixes label0 and the basis streams itself; else the sums are folded
+        # into the labels here
+        biLabel = self.biTrainData(biInput, biDof, biArg, basis=self.bicLearn is None)
+        bicB = None
+        if self.bicLearn is not None:
+            bicB = eng.dev(np.ascontiguousarray(self._bic_basis(biInput, biDof)))       # [J, nB], stream-major, fp64 then fp32
         # learnt amplitudes: the engine mixes s0 and the basis streams itself; else the sum is folded into the source here
         srcphi = None
         # ... and likewise g0 and the basis streams of gcoef
@@ -2025,7 +2176,7 @@ class VarNet:
             nlfluxCoef = list(self.PDE.nlfluxCoef)
         slab = self._slab_tensor(Input) if self.causal is not None else None   # (time column dim: the same ids for every MOR batch)
         return dict(Input=eng.dev(Input), Input_host=Input, gcoef=eng.dev(gcoef), rate=rate, reactCoef=reactCoef, slab=slab,
-                    phi=phi, nlfluxCoef=nlfluxCoef, psi=psi, nldiffCoef=nldiffCoef, srcphi=srcphi, fldG=fldG,
+                    phi=phi, nlfluxCoef=nlfluxCoef, psi=psi, nldiffCoef=nldiffCoef, srcphi=srcphi, fldG=fldG, bicB=bicB,
                     source=eng.dev(src.reshape(-1)) if self.lossOpt['isSource'] else None,
                     biInput=eng.dev(biInput), biLabel=eng.dev(biLabel.reshape(-1)),
                     N_rows=N_rows, dNt_rows=dNt_rows,
