@@ -483,6 +483,42 @@ int vn_get_bic_amps(vn_engine* h, double* amp, double* grad, int32_t J);
 /* Overwrites all J amplitudes (rounded to fp32, NOT clamped); the Adam slots stay.  Non-finite: VN_EINVAL; learning off: VN_ESTATE.
  * Invalidates the snapshot of vn_state_snapshot. */
 int vn_set_bic_amps(vn_engine* h, const double* amp, int32_t J);
+/* Flux boundary identification: the flux rows of vn_set_flux_bc evaluate r_k = n . grad_x u + coef[k] u - label[k] with
+ *   label[k] = label0[k] + sum_{j < J_flux} a_j S_j[k],    coef[k] = coef0[k] + sum_{j >= J_flux} a_j S_j[k]
+ * over a basis of J = J_flux + J_robin per-row streams (a stream is its basis function on the rows of its own edge and zero
+ * elsewhere), and the amplitudes a_j -- a wall flux, a transfer coefficient -- are learnt next to the parameters from the
+ * observations.  vn_set_fluxbc_basis registers the basis: S_dev is [J_flux + J_robin, nF] fp32 on the device, stream-major (every
+ * stream contiguous, nF as passed to vn_set_flux_bc), the J_flux streams of the flux datum first; the streams are read on every step
+ * and must stay valid while registered.  S_dev == NULL or J_flux + J_robin == 0 clears the registration, and so does vn_set_flux_bc.
+ * A call replaces the previous registration, also when it fails.  J_flux + J_robin > VN_FBC_MAX or a negative count: VN_EINVAL; no
+ * flux rows registered: VN_ESTATE.  The call invalidates the snapshot of vn_state_snapshot and the L-BFGS (f_k, g_k).
+ * Without vn_set_fluxbc_learn a registered basis is not read: coef and label are those of vn_set_flux_bc. */
+#define VN_FBC_MAX 64
+int vn_set_fluxbc_basis(vn_engine* h, const float* S_dev, int32_t J_flux, int32_t J_robin);
+/* While learning is on the engine owns ONE device vector of J fp32 amplitudes (`init`, rounded once), their two Adam slots and a
+ * snapshot copy of the three, like vn_set_bic_learn.  Every evaluation (vn_grad, vn_train_step / _epoch, vn_eval_loss,
+ * vn_objective_f64) first forms label and coef as above (fp32, from label0 / coef0, j ascending, one fused multiply-add per stream;
+ * a part without streams is the caller's array) and the flux rows read them in place of the arrays of vn_set_flux_bc; a basis with
+ * another J_flux + J_robin makes the step and the evaluations return VN_EINVAL.  With udbar[k] = 2 w0 biDimVal r_k / nF,
+ *   d loss / d a_j = - sum_k udbar[k] S_j[k]  (j < J_flux),    d loss / d a_j = + sum_k udbar[k] u[k] S_j[k]  (j >= J_flux)
+ * is formed inside vn_grad / vn_train_step / vn_train_epoch for the masked entries right after the flux rows' own pass, whose
+ * buffers it reads, on every route, in a fixed order without atomics (two evaluations: the same bits).  The update, the clamp, the
+ * unmasked entries, snapshot / rollback and the state layout are those of vn_set_bic_learn.  Without a registered basis the
+ * amplitude gradient reads 0 and the masked amplitudes follow the momentum in their slots.  The loss-only forms and
+ * vn_objective_f64 run the mix only: no amplitude gradient is built in fp64.
+ *   mask   J ints (non-zero: learnt), or NULL: learning off, everything freed, every result bit for bit what it was before.
+ *   init, lo, hi   J doubles each.  Non-finite init, NaN bounds, lo > hi, lr not finite or <= 0, J outside 1..VN_FBC_MAX: VN_EINVAL.
+ * Refused with VN_EUNSUPPORTED for the reasons of vn_set_source_learn: an RMSProp or L-BFGS engine; a handle that has a communicator
+ * (and vn_comm_init while learning is on); a batch with vn_set_tf_weights / vn_set_causal (here, in those calls and in the steps).
+ * No kernel family is refused: the flux rows run their own pass on every route that registers them.
+ * The call invalidates the snapshot of vn_state_snapshot and the L-BFGS (f_k, g_k). */
+int vn_set_fluxbc_learn(vn_engine* h, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi, double lr);
+/* The J amplitudes now (synchronises) and, when grad is not NULL, the amplitude gradient of the last gradient evaluation (zeros for
+ * unmasked entries and before the first one).  Learning off: VN_ESTATE; J not the engine's: VN_EINVAL. */
+int vn_get_fluxbc_amps(vn_engine* h, double* amp, double* grad, int32_t J);
+/* Overwrites all J amplitudes (rounded to fp32, NOT clamped); the Adam slots stay.  Non-finite: VN_EINVAL; learning off: VN_ESTATE.
+ * Invalidates the snapshot of vn_state_snapshot. */
+int vn_set_fluxbc_amps(vn_engine* h, const double* amp, int32_t J);
 /* updateDictFields('trainW') (VarNetUtility.py:921-922); the caller applies the
  * w[0:2] /= batchNum*puNum rule (VarNetUtility.py:900-901). */
 int vn_set_weights(vn_engine* h, const double w[3]);

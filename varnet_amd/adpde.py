@@ -1,7 +1,7 @@
 """
 Advection-diffusion(-reaction) PDE container: `ADPDE(domain, diff, vel, source, timeDependent, tInterval,
 BCs, IC, cEx, MORvar, d_diff, reaction, nlflux, nldiff, periodic, sourceBasis, sourceAmp, diffBasis, diffAmp, d_diffBasis, velBasis,
-velAmp, bcBasis, bcAmp, icBasis, icAmp)` -- the reference's ADPDE.py:56-246 restated (plot helpers are out of scope).
+velAmp, bcBasis, bcAmp, icBasis, icAmp, fluxBasis, fluxAmp, robinBasis, robinAmp)` -- the reference's ADPDE.py:56-246 restated (plot helpers are out of scope).
 
     c_t = div(diff D(c) grad c) - vel . grad c - div(w F(c)) + source + rate * p(c),    a * dc/dn + b * c = g  on each edge,
 
@@ -67,15 +67,24 @@ class ADPDE:
     icAmp=[...] makes the initial condition `IC + sum_j icAmp_j iota_j`, every iota_j a callable f(x) evaluated like `IC`
     (time-dependent problems only).  Jb + Ji <= 64.  The amplitudes can be learnt from observations (`VarNet(..., learnBic=...)`:
     boundary data identification); without that the sums are part of the boundary and initial labels.
+
+    fluxBasis=[(bInd, gamma_1), ..., (bInd, gamma_Jl)] with fluxAmp=[...] (default: zeros) makes the flux datum of the Neumann /
+    Robin condition `a dc/dn + b c = g` on boundary indicator bInd `g/a + sum_j fluxAmp_j gamma_j`, and robinBasis=[(bInd, eta_1),
+    ..., (bInd, eta_Jc)] with robinAmp=[...] makes its transfer coefficient `b/a + sum_j robinAmp_j eta_j`: every function is a
+    callable f(x[, t]) returning a column, evaluated like `g`, and counts on the rows of its own indicator only (a robinBasis on a
+    Neumann indicator, b = 0, is allowed).  Jl + Jc <= 64.  Both are data of the boundary-flux rows (`VarNet(..., fluxBC=True)`);
+    the amplitudes can be learnt from observations (`VarNet(..., learnFluxBC=...)`: flux boundary identification), without that
+    the sums are part of the rows' label and coefficient.
     """
     SRC_MAX = 64
     FLD_MAX = 32
     BIC_MAX = 64
+    FBC_MAX = 64
 
     def __init__(self, domain, diff, vel, source=0.0, timeDependent=False, tInterval=None,
                  BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None, nlflux=None, nldiff=None, periodic=None,
                  sourceBasis=None, sourceAmp=None, diffBasis=None, diffAmp=None, d_diffBasis=None, velBasis=None, velAmp=None,
-                 bcBasis=None, bcAmp=None, icBasis=None, icAmp=None):
+                 bcBasis=None, bcAmp=None, icBasis=None, icAmp=None, fluxBasis=None, fluxAmp=None, robinBasis=None, robinAmp=None):
         # the reference ignores the `timeDependent` argument (ADPDE.py:108-109)
         timeDependent = tInterval is not None
 
@@ -371,6 +380,57 @@ class ADPDE:
             self.bcBasis, self.bcAmp = bcBasis, bcAmp
         if icBasis is not None:
             self.icBasis, self.icAmp = icBasis, icAmp
+        # flux-datum and Robin-coefficient bases: likewise, on the Neumann / Robin indicators
+        fluxBasis, fluxAmp = self._check_fbc_basis('fluxBasis', 'fluxAmp', fluxBasis, fluxAmp, MORvar)
+        robinBasis, robinAmp = self._check_fbc_basis('robinBasis', 'robinAmp', robinBasis, robinAmp, MORvar)
+        if len(fluxBasis or []) + len(robinBasis or []) > self.FBC_MAX:
+            raise ValueError('fluxBasis and robinBasis hold %d functions together, at most %d are supported!'
+                             % (len(fluxBasis or []) + len(robinBasis or []), self.FBC_MAX))
+        if fluxBasis is not None:
+            self.fluxBasis, self.fluxAmp = fluxBasis, fluxAmp
+        if robinBasis is not None:
+            self.robinBasis, self.robinAmp = robinBasis, robinAmp
+
+    def _check_fbc_basis(self, name, ampName, basis, amp, MORvar):
+        """(list of (bInd, callable) pairs, amplitudes) of fluxBasis / robinBasis, or (None, None) without one; ValueError names
+        the field.  Called at the end of __init__: BCtype and periodic are set."""
+        if basis is None:
+            if amp is not None:
+                raise ValueError('%s is an option of %s=[...]!' % (ampName, name))
+            return None, None
+        if not isinstance(basis, (list, tuple)) or len(basis) == 0:
+            raise ValueError('%s must be a non-empty list [(bInd, f_1), ..., (bInd, f_J)]!' % name)
+        if len(basis) > self.FBC_MAX:
+            raise ValueError('%s holds %d functions, at most %d are supported!' % (name, len(basis), self.FBC_MAX))
+        out = []
+        for j, e in enumerate(basis):
+            if not isinstance(e, (list, tuple)) or len(e) != 2 or isinstance(e[0], bool) or not isinstance(e[0], (int, np.integer)):
+                raise ValueError('%s[%d] must be a pair (bInd, f) of a boundary indicator and a callable!' % (name, j))
+            bInd, f = int(e[0]), e[1]
+            if not callable(f):
+                raise ValueError('%s[%d]: the function must be callable, like the g of a boundary condition!' % (name, j))
+            if not 0 <= bInd < self.domain.bIndNum:
+                raise ValueError('%s[%d]: boundary indicator %d outside [0, %d)!' % (name, j, bInd, self.domain.bIndNum))
+            if self.BCtype[bInd] == 'Periodic':
+                raise ValueError('%s[%d]: boundary indicator %d is paired by `periodic`, it carries no boundary data!' % (name, j, bInd))
+            if self.BCtype[bInd] == 'Dirichlet':
+                raise ValueError('%s[%d]: boundary indicator %d carries a Dirichlet condition, only Neumann and Robin data has a '
+                                 'flux basis (bcBasis is the Dirichlet one)!' % (name, j, bInd))
+            out.append((bInd, f))
+        if amp is None:
+            amp = np.zeros(len(out))
+        try:
+            amp = np.array(np.reshape(np.asarray(amp, dtype=float), -1))
+        except (TypeError, ValueError):
+            raise ValueError('%s must be a list of %d numbers, one per function of %s!' % (ampName, len(out), name))
+        if amp.size != len(out):
+            raise ValueError('%s holds %d values for the %d functions of %s!' % (ampName, amp.size, len(out), name))
+        if not np.all(np.isfinite(amp)):
+            raise ValueError('%s must be finite!' % ampName)
+        if MORvar is not None:
+            raise NotImplementedError('%s with model-order reduction is not supported: parametric basis functions are out of scope '
+                                      '(the basis streams are assembled once, for all parameter batches)' % name)
+        return out, amp
 
     def _check_bic_basis(self, name, ampName, basis, amp, MORvar, edges):
         """(list of entries, amplitudes) of bcBasis (`edges`: (bInd, callable) pairs) / icBasis (callables), or (None, None) without

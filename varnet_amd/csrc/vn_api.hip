@@ -142,7 +142,7 @@ constexpr bool kWithF32Point = false;
 // ---- learnt vectors: small vectors the Adam step moves next to the parameters ----------------
 // One record per vector; what differs between the vectors is a row of kLearnt.  Everything that handles them (learnt_* below
 // vn_engine) runs over the records in LearntId order.
-enum LearntId { LV_COEF, LV_SRC, LV_FLD, LV_BIC, LV_N };
+enum LearntId { LV_COEF, LV_SRC, LV_FLD, LV_BIC, LV_FBC, LV_N };
 constexpr int LV_CAP = VN_SRC_JMAX;              // the largest capacity of any kind (host staging arrays)
 
 struct Learnt {
@@ -170,6 +170,7 @@ constexpr LearntKind kLearnt[LV_N] = {
   {VN_SRC_JMAX, 64, "vn_set_source_learn", "amplitude", "source amplitudes", "the amplitude gradients"},
   {VN_FLD_JMAX, 64, "vn_set_field_learn", "amplitude", "field amplitudes", "the amplitude gradients"},
   {VN_BIC_JMAX, 64, "vn_set_bic_learn", "amplitude", "boundary and initial amplitudes", "the amplitude gradients"},
+  {VN_FBC_JMAX, 64, "vn_set_fluxbc_learn", "amplitude", "flux and Robin amplitudes", "the amplitude gradients"},
 };
 
 int learnt_weights_refusal(const LearntKind& k, int batch) {
@@ -261,6 +262,8 @@ struct vn_engine {
   EdgeSet es[VN_EDGE_N];
   const float *fcoef = nullptr, *flabel = nullptr;
   double fbiDimVal = 1.0;
+  const float* fbcS = nullptr;       // [fbcJl + fbcJc, nF] basis streams of the flux rows (vn_set_fluxbc_basis), caller-owned: fbcJl of
+  int fbcJl = 0, fbcJc = 0;          // the flux datum (label), then fbcJc of the Robin coefficient (coef)
   // periodic pairs (vn_set_periodic): rows i and i + nP pair, nP = count, 2 nP rows; the directions in G while pgamma > 0
   double pgamma = 1.0, pbiDimVal = 1.0;
   // observations (vn_set_observations): n = rows points in nO = count segments
@@ -270,8 +273,8 @@ struct vn_engine {
   double* omisfit = nullptr;                      // device slot: the unweighted misfit O of the last evaluation
   // the vectors learnt next to the parameters, by LearntId: the nine coefficients of inverse mode (vn_set_coef_learn),
   // which live on the device while they are learnt, and the engine-wide amplitudes of the batches' source bases
-  // (vn_set_source_learn) and gcoef bases (vn_set_field_learn) and of the BC/IC label bases (vn_set_bic_learn), all of
-  // vn_learnt.hip; then each feature's own work buffers
+  // (vn_set_source_learn) and gcoef bases (vn_set_field_learn), of the BC/IC label bases (vn_set_bic_learn) and of the flux rows'
+  // bases (vn_set_fluxbc_learn), all of vn_learnt.hip; then each feature's own work buffers
   Learnt lv[LV_N];
   float* cl_acc = nullptr; long cl_acc_cap = 0;   // [3, U] accR_j, accF_j, gs_j of the de-duplicated step
   float* sl_mix = nullptr; long sl_mix_cap = 0;   // [nT] s0 + sum_j a_j phi_j of the batch being evaluated
@@ -279,6 +282,8 @@ struct vn_engine {
   float* fl_csr = nullptr; long fl_csr_cap = 0;   // [nT, dim] fl_mix in CSR order (de-duplicated step), rebuilt every evaluation
   float* fl_pack = nullptr; long fl_pack_cap = 0; // [nT, 4] (u, grad u) of the batch's own rows (row-wise gradient evaluation)
   float* bl_mix = nullptr; long bl_mix_cap = 0;   // [nBreg] label0 + sum_j a_j B_j of the BC/IC set the batch being evaluated reads
+  float* fb_label = nullptr; long fb_label_cap = 0;   // [nF] label0 + sum_{j < Jl} a_j S_j of the flux rows
+  float* fb_coef = nullptr; long fb_coef_cap = 0;     // [nF] coef0 + sum_{j >= Jl} a_j S_j of the flux rows
   float* snap = nullptr;       // vn_state_snapshot: device copy of (theta | m | v), 3 P floats
   int64_t snap_step = -1;      // step counter at the snapshot (-1: none)
   PointRoute point_route = PointRoute::automatic;   // vn_debug_point_route(route & 3)
@@ -790,12 +795,54 @@ int bic_forward_reduce(vn_engine* h, const Batch& b) {
   return bic_reduce(h, b);
 }
 
+// Flux and Robin amplitudes: while they are learnt and the flux rows have a basis, the part that has streams reads the values
+// fluxbc_mix formed at the start of the evaluation; else the caller's arrays.  The two read sites (flux_seed, vn_objective_f64)
+// take their coefficient and label from here.
+inline bool fbc_learnt(const vn_engine* h) { return h->lv[LV_FBC].on && h->fbcS; }
+inline const float* flux_coef(const vn_engine* h) { return fbc_learnt(h) && h->fbcJc > 0 ? h->fb_coef : h->fcoef; }
+inline const float* flux_label(const vn_engine* h) { return fbc_learnt(h) && h->fbcJl > 0 ? h->fb_label : h->flabel; }
+
+// ... first thing in an evaluation: the basis must be the engine's, then the label and the coefficient are formed, one mix per
+// part that has streams (vn_learnt.hip)
+int fluxbc_mix(vn_engine* h) {
+  if (!fbc_learnt(h)) return VN_OK;
+  const Learnt& v = h->lv[LV_FBC];
+  const long nF = h->es[VN_EDGE_FLUX].count;
+  if (h->fbcJl + h->fbcJc != v.J)
+    return fail(VN_EINVAL, "the flux rows have a basis of %d + %d streams, the learnt amplitudes (vn_set_fluxbc_learn) are %d", h->fbcJl,
+                h->fbcJc, v.J);
+  VnMixArgs a{};
+  a.n = nF;
+  if (h->fbcJl > 0) {
+    if (int rc = ensure(&h->fb_label, &h->fb_label_cap, nF)) return rc;
+    a.base = h->flabel; a.stream = h->fbcS; a.amp = v.state; a.J = h->fbcJl; a.out = h->fb_label;
+    HIPCHK(vn_learnt_mix_launch(a, h->stream));
+  }
+  if (h->fbcJc > 0) {
+    if (int rc = ensure(&h->fb_coef, &h->fb_coef_cap, nF)) return rc;
+    a.base = h->fcoef; a.stream = h->fbcS + (long)h->fbcJl * nF; a.amp = v.state + h->fbcJl; a.J = h->fbcJc; a.out = h->fb_coef;
+    HIPCHK(vn_learnt_mix_launch(a, h->stream));
+  }
+  return VN_OK;
+}
+
+// ... and after the flux set's edge pass of a gradient evaluation: the amplitude sums over its values and seeds
+int fluxbc_reduce(vn_engine* h) {
+  if (!fbc_learnt(h)) return VN_OK;
+  const EdgeSet& e = h->es[VN_EDGE_FLUX];
+  VnFbcGradArgs g{};
+  g.u = e.buf[EB_U]; g.udbar = e.buf[EB_UDBAR]; g.S = h->fbcS; g.J = h->fbcJl + h->fbcJc; g.Jl = h->fbcJl; g.nF = e.count;
+  g.mask = h->lv[LV_FBC].mask; g.part = h->lv[LV_FBC].part;
+  HIPCHK(vn_fbcgrad_launch(g, &h->lv[LV_FBC].blocks, h->stream));
+  return VN_OK;
+}
+
 // ---- edge row sets (vn_edge.h) ------------------------------------------------------------------
 // The seed kernel of each kind: from the values in e.buf[EB_U] and the tangent stream ud (nullptr: values only) the loss
 // partials in e.buf[EB_LOSS] and, where asked for, the seeds ubar and udbar (nullptr: loss only / values only).
 hipError_t flux_seed(const vn_engine* h, const EdgeSet& e, const float* ud, float* ubar, float* udbar) {
   VnFluxSeedArgs a{};
-  a.u = e.buf[EB_U]; a.ud = ud; a.coef = h->fcoef; a.label = h->flabel; a.nF = e.count;
+  a.u = e.buf[EB_U]; a.ud = ud; a.coef = flux_coef(h); a.label = flux_label(h); a.nF = e.count;
   a.biDimVal = (float)h->fbiDimVal; a.w0 = (float)h->w[0];
   a.ubar = ubar; a.udbar = udbar; a.part = e.buf[EB_LOSS];
   return vn_flux_seed_launch(a, h->stream);
@@ -854,8 +901,11 @@ int edge_pass(vn_engine* h, int id, bool with_grad, VnEdgeSum* sum) {
 
 // The edge passes of a step in VnEdgeId order: what its reduction adds.
 int edge_passes(vn_engine* h, bool with_grad, VnEdgeSums* fx) {
-  for (int id = 0; id < VN_EDGE_N; ++id)
+  for (int id = 0; id < VN_EDGE_N; ++id) {
     if (int rc = edge_pass(h, id, with_grad, &fx->set[id])) return rc;
+    if (id == VN_EDGE_FLUX && with_grad)
+      if (int rc = fluxbc_reduce(h)) return rc;      // flux and Robin amplitudes: u and udbar of the flux rows are in the set's buffers
+  }
   if (h->es[VN_EDGE_OBS].count > 0) { fx->lambda = (float)h->olambda; fx->misfit = h->omisfit; }
   return VN_OK;
 }
@@ -1143,6 +1193,7 @@ void learnt_free(vn_engine* h, int id) {
   if (id == LV_SRC) drop(h->sl_mix, h->sl_mix_cap);
   if (id == LV_FLD) { drop(h->fl_mix, h->fl_mix_cap); drop(h->fl_csr, h->fl_csr_cap); drop(h->fl_pack, h->fl_pack_cap); }
   if (id == LV_BIC) drop(h->bl_mix, h->bl_mix_cap);
+  if (id == LV_FBC) { drop(h->fb_label, h->fb_label_cap); drop(h->fb_coef, h->fb_coef_cap); }
   v = Learnt{};
 }
 
@@ -1879,6 +1930,28 @@ int vn_set_bic_learn(vn_engine* h, int32_t J, const int32_t* mask, const double*
 int vn_get_bic_amps(vn_engine* h, double* amp, double* grad, int32_t J) { return learnt_get(h, LV_BIC, amp, grad, J); }
 int vn_set_bic_amps(vn_engine* h, const double* amp, int32_t J) { return learnt_put(h, LV_BIC, amp, J); }
 
+// ---- flux boundary identification: basis streams of the flux rows' datum and coefficient, amplitudes on the device (vn_learnt.hip) ----
+int vn_set_fluxbc_basis(vn_engine* h, const float* S_dev, int32_t J_flux, int32_t J_robin) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  h->snap_step = -1;
+  lbfgs_invalidate(h);
+  h->fbcS = nullptr; h->fbcJl = h->fbcJc = 0;      // a call replaces the previous registration, also when it fails
+  if (!S_dev || (J_flux == 0 && J_robin == 0)) return VN_OK;
+  if (J_flux < 0 || J_robin < 0 || (long)J_flux + J_robin > VN_FBC_MAX)
+    return fail(VN_EINVAL, "a flux-row basis has 1 to %d streams (flux datum and Robin coefficient together), got %d + %d", VN_FBC_MAX,
+                J_flux, J_robin);
+  if (h->es[VN_EDGE_FLUX].count <= 0)
+    return fail(VN_ESTATE, "no boundary-flux rows are registered (call vn_set_flux_bc first): no datum or coefficient to mix");
+  h->fbcS = S_dev; h->fbcJl = J_flux; h->fbcJc = J_robin;
+  return VN_OK;
+}
+
+int vn_set_fluxbc_learn(vn_engine* h, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi, double lr) {
+  return learnt_set_learn(h, LV_FBC, J, mask, init, lo, hi, lr);
+}
+int vn_get_fluxbc_amps(vn_engine* h, double* amp, double* grad, int32_t J) { return learnt_get(h, LV_FBC, amp, grad, J); }
+int vn_set_fluxbc_amps(vn_engine* h, const double* amp, int32_t J) { return learnt_put(h, LV_FBC, amp, J); }
+
 // vn_set_tf_weights / vn_set_causal: what both check before they touch the batch; *clear: the call unregisters
 static int weights_common(vn_engine* h, int32_t batch, bool clear, const char* who) {
   if (!h) return fail(VN_EINVAL, "null handle");
@@ -2000,6 +2073,7 @@ int vn_set_flux_bc(vn_engine* h, const float* X, const float* normal, const floa
   if (nF < 0) return fail(VN_EINVAL, "negative number of flux rows");
   edge_drop(h, VN_EDGE_FLUX);
   h->fcoef = h->flabel = nullptr;
+  h->fbcS = nullptr; h->fbcJl = h->fbcJc = 0;        // the rows' basis goes with them (vn_set_fluxbc_basis)
   if (nF == 0 || !X) return VN_OK;
   if (!normal || !coef || !label) return fail(VN_EINVAL, "null argument");
   if (int rc = edge_check_route(h, VN_EDGE_FLUX)) return rc;
@@ -2122,6 +2196,7 @@ int vn_grad(vn_engine* h, int32_t batch) {
   if (int rc = source_mix(h, b, batch)) return rc;
   if (int rc = field_mix(h, b, batch)) return rc;
   if (int rc = bic_mix(h, b, batch)) return rc;
+  if (int rc = fluxbc_mix(h)) return rc;
   for (Learnt& v : h->lv) v.blocks = 0;
   if (int rc = grad_route(h, b)) return rc;
   // after every kernel that reads the coefficients, s_mix or the mixed gcoef (the parameters' update rides in the reduction above);
@@ -2358,6 +2433,7 @@ int vn_eval_loss(vn_engine* h, int32_t batch, double out[4], float* lossVec_dev)
   if (int rc = source_mix(h, h->batches[batch], batch)) return rc;
   if (int rc = field_mix(h, h->batches[batch], batch)) return rc;
   if (int rc = bic_mix(h, h->batches[batch], batch)) return rc;
+  if (int rc = fluxbc_mix(h)) return rc;
   VnEdgeSums fx;
   if (int rc = edge_passes(h, false, &fx)) return rc;
   if (int rc = run_forward_and_seed(h, h->batches[batch], false, lossVec_dev, h->lossbuf, fx)) return rc;
@@ -2386,6 +2462,7 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   if (int rc = source_mix(h, b, batch)) return rc;     // source identification: the mixed fp32 stream, widened exactly
   if (int rc = field_mix(h, b, batch)) return rc;      // field identification: likewise the mixed direction
   if (int rc = bic_mix(h, b, batch)) return rc;        // boundary data identification: likewise the mixed labels
+  if (int rc = fluxbc_mix(h)) return rc;               // flux boundary identification: likewise the flux rows' datum and coefficient
   VnObj64Problem p{};
   p.net = h->net; p.theta = theta_dev;
   p.X = b.Input; p.G = batch_gcoef(h, b); p.src = batch_src(h, b);
@@ -2394,7 +2471,7 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   p.n_k = b.n_k; p.q = h->cfg.integ_num; p.td = h->cfg.time_dependent;
   p.Xb = bi_x(h, b); p.label = bi_y(h, b); p.nB = h->nB; p.bDof = h->bDof; p.biDimVal = h->biDimVal;
   const EdgeSet &ef = h->es[VN_EDGE_FLUX], &ep = h->es[VN_EDGE_PERIODIC], &eo = h->es[VN_EDGE_OBS];
-  p.Xf = ef.X; p.Nf = ef.G; p.fcoef = h->fcoef; p.flabel = h->flabel; p.nF = ef.count; p.fbiDimVal = h->fbiDimVal;
+  p.Xf = ef.X; p.Nf = ef.G; p.fcoef = flux_coef(h); p.flabel = flux_label(h); p.nF = ef.count; p.fbiDimVal = h->fbiDimVal;
   p.Xp = ep.X; p.Dp = ep.G; p.nP = ep.count; p.pgamma = h->pgamma; p.pbiDimVal = h->pbiDimVal;
   p.Xo = eo.X; p.Qo = h->oQ; p.Do = eo.G; p.orowptr = h->orowptr; p.ovalue = h->oval; p.owgt = h->owgt;
   p.on = eo.rows; p.nO = eo.count; p.olambda = h->olambda; p.omisfit = h->omisfit;

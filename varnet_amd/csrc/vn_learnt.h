@@ -1,7 +1,7 @@
 // Host-side declarations of vn_learnt.hip: the vectors learnt next to the parameters -- the nine polynomial coefficients of
 // vn_terms.hip (vn_set_coef_learn; index 0..2 reaction, 3..5 flux, 6..8 diffusivity), the source amplitudes (vn_set_source_learn)
-// the field amplitudes (vn_set_field_learn) and the boundary / initial amplitudes (vn_set_bic_learn) -- their mix, their gradient
-// reductions and their Adam step.  Kept out of vn_internal.h, which every kernel's source hash covers.
+// the field amplitudes (vn_set_field_learn), the boundary / initial amplitudes (vn_set_bic_learn) and the flux-row amplitudes
+// (vn_set_fluxbc_learn) -- their mix, their gradient reductions and their Adam step.  Kept out of vn_internal.h, which every kernel's source hash covers.
 #pragma once
 #include "vn_internal.h"
 
@@ -9,11 +9,13 @@ constexpr int VN_COEF_N = 9;
 constexpr int VN_SRC_JMAX = 64;              // == VN_SRC_MAX of the public header
 constexpr int VN_FLD_JMAX = 32;              // == VN_FLD_MAX of the public header
 constexpr int VN_BIC_JMAX = 64;              // == VN_BIC_MAX of the public header
+constexpr int VN_FBC_JMAX = 64;              // == VN_FBC_MAX of the public header
 constexpr int VN_LEARNT_JG = 8;              // streams one workgroup of an amplitude reduction carries
 constexpr int VN_LEARNT_MAXBLK = 256;        // cap of every reduction grid along the rows: a partial sums a fixed set of rows
 
 // out[r] = base[r] + sum_j amp[j] stream[j, r]: fp32, from base[r], j ascending, one fused multiply-add per stream.  The source of
-// a batch (n = nT), its tangent direction gcoef (n = nT dim) and the labels of a BC/IC row set (n = nB) are all formed by it.
+// a batch (n = nT), its tangent direction gcoef (n = nT dim), the labels of a BC/IC row set (n = nB) and the flux datum and Robin
+// coefficient of the flux rows (n = nF, one launch each) are all formed by it.
 struct VnMixArgs {
   const float* base;                         // [n]
   const float* stream;                       // [J, n] stream-major
@@ -94,6 +96,21 @@ struct VnBicGradArgs {
   float* part;                               // [blocks, J] out
 };
 hipError_t vn_bicgrad_launch(const VnBicGradArgs& a, int* blocks, hipStream_t s);
+
+// ---- flux-row amplitudes.  The flux rows' residual is r_k = ud_k + coef[k] u_k - label[k] with label = label0 + sum_{j < Jl} a_j
+// S[j, :] and coef = coef0 + sum_{j >= Jl} a_j S[j, :].  part[b, j] = sum_{k in block b's rows} w_j[k] S[j, k] for the masked j (0 for
+// the others) with the row weight w_j[k] = - udbar[k] for j < Jl (the flux datum) and + udbar[k] u[k] for j >= Jl (the Robin
+// coefficient); udbar[k] = d loss / d r_k as vn_flux_seed_kernel stores it.  After the flux set's edge pass of a gradient
+// evaluation, whose value and seed buffers it reads.
+struct VnFbcGradArgs {
+  const float* u;                            // [nF] network value per flux row
+  const float* udbar;                        // [nF] the tangent seed of the row
+  const float* S;                            // [J, nF] stream-major: Jl streams of the flux datum, then J - Jl of the coefficient
+  int J, Jl; long nF;
+  unsigned long long mask;                   // bit j: amplitude j is learnt
+  float* part;                               // [blocks, J] out
+};
+hipError_t vn_fbcgrad_launch(const VnFbcGradArgs& a, int* blocks, hipStream_t s);
 
 // ---- every vector.  One block: grad[j] = sum over the [blocks, J] partials in fp64 (blocks > 0; else grad as it stands), then
 // with `update` the Adam step of the masked entries and the clamp.  `lanes` (16 or 64) is the fold's lane-group width: 256 / lanes

@@ -9,8 +9,11 @@
 //   boundary / initial amplitudes        the labels of a BC/IC row set are label0[k] + sum_j a_j B_j[k] over J <= 64 per-row streams
 //   (vn_set_bic_*)                       (a Dirichlet basis stream is zero on the initial rows and on other edges, an initial one on
 //                                        the boundary rows; the engine does not know which is which).
+//   flux-row amplitudes (vn_set_fluxbc_*) the flux rows' residual ud_k + coef[k] u_k - label[k] reads label = label0 + sum_{j < Jl} a_j S_j
+//                                        and coef = coef0 + sum_{j >= Jl} a_j S_j over J <= 64 per-row streams, the Jl of the flux datum
+//                                        first: one vector, two mixes.
 // Mix (vn_learnt_mix_kernel and its 4-row form): base + Sum_j amp[j] stream[j], which every kernel of the step then reads in
-// place of the batch's source (n = nT), gcoef (n = nT dim) or BC/IC labels (n = nB).
+// place of the batch's source (n = nT), gcoef (n = nT dim), BC/IC labels (n = nB) or the flux rows' label and coefficient (n = nF).
 //
 // Gradients.  With u_r, A_r = grad u_r . gcoef_r, N_p, rate_r, phi_r as in vn_terms.hip's header, the row integrand is
 // t_r = D(u_r) A_r - (source + reaction) N_p - flux (D = 1 without vn_set_nldiff), and seed_r is the tangent seed of row r:
@@ -21,6 +24,8 @@
 //   d loss / d b_j = + sum_r seed_r (grad u_r . G_j[r, :])
 // and over the BC/IC rows k, with ubar_b[k] the value seed of row k (vn_bicseed.h; the label enters through u_b[k] - label[k] only),
 //   d loss / d a_j = - sum_k ubar_b[k] B_j[k]       k < bDof on a steady problem, whose initial rows are never evaluated
+// and over the flux rows k, with udbar[k] = d loss / d r_k the tangent seed vn_flux_seed_kernel stores,
+//   d loss / d a_j = - sum_k udbar[k] S_j[k]  (j < Jl),    d loss / d a_j = + sum_k udbar[k] u[k] S_j[k]  (j >= Jl)
 // Where each reads its seed.  The coefficients and the source read udbar[r] as vn_seed_kernel writes it (2 w2 detJ R_k W_p), BEFORE
 // vn_nldiff_seed_kernel rescales it by D(u); the field reads it AFTER that rescale (its integrand carries D(u)).  On the
 // de-duplicated step the source takes seed_r = stf[r / q] W_p with stf the per-test-function seed of vn_dedup_seed_kernel, the
@@ -263,6 +268,25 @@ __global__ __launch_bounds__(TB) void vn_bicgrad_kernel(VnBicGradArgs a) {
   write_group(acc, m, true, j0, a.J, a.part);
 }
 
+// ---- flux-row amplitudes ----
+// (one row per thread, as above: nF is small against nT.)  The part of stream j0 + c decides its row weight; a group of eight may
+// carry streams of both parts, so both weights are formed per row and the choice is a uniform select per stream.
+__global__ __launch_bounds__(TB) void vn_fbcgrad_kernel(VnFbcGradArgs a) {
+  const int j0 = blockIdx.y * JG;
+  const unsigned m = group_mask(a, j0);
+  const int nl = a.Jl - j0;                                      // streams of this group that belong to the flux datum (may be <= 0, >= 8)
+  float acc[JG] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (m)
+    for (long k = (long)blockIdx.x * TB + threadIdx.x; k < a.nF; k += (long)gridDim.x * TB) {
+      const float s = a.udbar[k];
+      const float wl = -s, wc = s * a.u[k];
+#pragma unroll
+      for (int c = 0; c < JG; ++c)
+        if (m >> c & 1u) acc[c] += (c < nl ? wl : wc) * a.S[(long)(j0 + c) * a.nF + k];
+    }
+  write_group(acc, m, false, j0, a.J, a.part);
+}
+
 // ---- fold, Adam step, clamp ----
 // TB / LANES groups of LANES lanes: lane j < J of group g adds the partials of the blocks [g chunk, (g + 1) chunk) in index order,
 // then thread j adds the group sums in group order.  (16 lanes for the nine coefficients, 64 for the amplitudes: the order each
@@ -354,6 +378,14 @@ hipError_t vn_bicgrad_launch(const VnBicGradArgs& a, int* blocks, hipStream_t s)
   *blocks = learnt_blocks(a.steady ? a.bDof : a.nB);
   const dim3 grid((unsigned)*blocks, (unsigned)((a.J + JG - 1) / JG));
   hipLaunchKernelGGL(vn_bicgrad_kernel, grid, dim3(TB), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t vn_fbcgrad_launch(const VnFbcGradArgs& a, int* blocks, hipStream_t s) {
+  if (a.J < 1 || a.J > VN_FBC_JMAX || a.Jl < 0 || a.Jl > a.J || a.nF < 1) return hipErrorInvalidValue;
+  *blocks = learnt_blocks(a.nF);
+  const dim3 grid((unsigned)*blocks, (unsigned)((a.J + JG - 1) / JG));
+  hipLaunchKernelGGL(vn_fbcgrad_kernel, grid, dim3(TB), 0, s, a);
   return hipGetLastError();
 }
 

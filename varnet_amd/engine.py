@@ -93,6 +93,11 @@ _SIGS = {
                                    C.POINTER(C.c_double), C.c_double]),
     'vn_get_bic_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32]),
     'vn_set_bic_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
+    'vn_set_fluxbc_basis': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    'vn_set_fluxbc_learn': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.c_double]),
+    'vn_get_fluxbc_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32]),
+    'vn_set_fluxbc_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
     'vn_set_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_bind_grad_buffer': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vn_grad': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -135,7 +140,8 @@ ABI_SYMBOLS = tuple(_SIGS.keys())
 # the _keep keys of the three polynomial terms, in the order of the coefficient index (vn_set_coef_learn)
 COEF_TERMS = ('react', 'nlflux', 'nldiff')
 # the learnt vectors: the name vn_get_* / vn_set_* carry, and the fixed length (None: the ABI takes the length J)
-LEARNT = {'coef': ('coefs', 9), 'source': ('source_amps', None), 'field': ('field_amps', None), 'bic': ('bic_amps', None)}
+LEARNT = {'coef': ('coefs', 9), 'source': ('source_amps', None), 'field': ('field_amps', None), 'bic': ('bic_amps', None),
+          'fluxbc': ('fluxbc_amps', None)}
 
 
 class VNError(RuntimeError):
@@ -472,6 +478,7 @@ class VNEngine:
     def set_flux_bc(self, X=None, normal=None, coef=None, label=None, biDimVal=1.0):
         """Register (or, with X=None, clear) the boundary-flux rows of Neumann / Robin edges (vn_set_flux_bc): X [nF, inpDim],
         outward unit normals [nF, dim], coef = b/a [nF], label = g/a [nF]."""
+        self._keep.pop(('fbcbasis', -1), None)     # vn_set_flux_bc clears the rows' basis
         if X is None or len(X) == 0:
             return self._set_edge('flux', self.lib.vn_set_flux_bc, None, 0, float(biDimVal))
         X, normal = self.dev(X), self.dev(normal)
@@ -627,15 +634,16 @@ class VNEngine:
             return
         if not isinstance(streams, self.torch.Tensor):
             streams = np.asarray(streams, dtype=np.float32)
-        # the rows a stream runs over: the batch's interior rows, or for the BC/IC labels the rows of the set they belong to
+        # the rows a stream runs over: the batch's interior rows, for the BC/IC labels the rows of the set they belong to, for the
+        # flux datum and Robin coefficient the flux rows
         kept = (self._keep.get('bic') if batch < 0 else self._keep.get(('bbic', batch))) if key == 'bicbasis' \
-            else self._keep.get(('int', batch))
+            else self._keep.get('flux') if key == 'fbcbasis' else self._keep.get(('int', batch))
         J = int(streams.shape[0])
         streams = self.dev(streams.reshape(J, -1, *trailing))
         # the ABI carries a pointer only: the length the kernels rely on is checked here
         assert kept is None or streams.shape[1] == kept[0].shape[0], \
-            'every basis stream must have one entry per %s row (%s != %s)' % ('BC/IC' if key == 'bicbasis' else 'interior',
-                                                                             streams.shape[1], kept[0].shape[0])
+            'every basis stream must have one entry per %s row (%s != %s)' % (
+                {'bicbasis': 'BC/IC', 'fbcbasis': 'flux'}.get(key, 'interior'), streams.shape[1], kept[0].shape[0])
         self._keep.pop((key, batch), None)         # (a failed call leaves the batch without a basis)
         self._ck(fn(self.h, int(batch), _ptr(streams), J))
         self._keep[(key, batch)] = streams
@@ -711,6 +719,33 @@ class VNEngine:
     def set_bic_amps(self, amp):
         """Overwrite the amplitudes (vn_set_bic_amps): rounded to fp32, not clamped; the Adam slots stay."""
         self._set_learnt('bic', amp)
+
+    def set_fluxbc_basis(self, S=None, J_flux=0):
+        """Register (S=None: clear) the basis of the flux rows' datum and Robin coefficient (vn_set_fluxbc_basis), after
+        set_flux_bc: S is [J, nF] (or J arrays of one value per flux row), J <= 64 -- the first J_flux streams belong to the flux
+        datum g/a, the other J - J_flux to the coefficient b/a."""
+        J_flux = int(J_flux)
+
+        def fn(h, batch, ptr, J):      # (the flux rows are engine-wide: no batch index in the ABI)
+            return self.lib.vn_set_fluxbc_basis(h, ptr, J_flux if J else 0, J - J_flux if J else 0)
+        if S is not None and not 0 <= J_flux <= len(S):
+            raise ValueError('J_flux = %d must lie in [0, %d], the number of streams' % (J_flux, len(S)))
+        self._set_basis('fbcbasis', fn, -1, S, ())
+
+    def set_fluxbc_learn(self, mask=None, init=None, lo=None, hi=None, lr=None):
+        """Flux boundary identification (vn_set_fluxbc_learn): learn the masked amplitudes a_j of the flux rows' bases (flux datum
+        first, then Robin coefficient) next to the parameters.  mask: J booleans; init: the J starting values (unmasked entries
+        keep theirs); lo / hi: the clamp (None: unbounded; entries may be +-inf); lr: their Adam rate.  mask=None switches learning
+        off and frees everything."""
+        self._set_learn('fluxbc', mask, init, lo, hi, lr)
+
+    def get_fluxbc_amps(self, grad=False, J=None):
+        """The amplitudes at the current state (vn_get_fluxbc_amps); grad=True: (amp, gradient of the last gradient evaluation)."""
+        return self._get_learnt('fluxbc', grad, J)
+
+    def set_fluxbc_amps(self, amp):
+        """Overwrite the amplitudes (vn_set_fluxbc_amps): rounded to fp32, not clamped; the Adam slots stay."""
+        self._set_learnt('fluxbc', amp)
 
     def _n_k(self, batch):
         kept = self._keep.get(('int', batch))

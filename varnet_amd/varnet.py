@@ -810,7 +810,8 @@ class VarNet:
                  integPnum=2, optimizer='adam', learning_rate=0.001, fluxBC=False, lbfgsLoss64=False,
                  causal=None, causalSlabs=None, periodicDeriv=None, observations=None, obsWeight=None,
                  learnCoef=None, coefLr=None, coefBounds=None, learnSource=None, sourceLr=None, sourceBounds=None,
-                 learnField=None, fieldLr=None, fieldBounds=None, learnBic=None, bicLr=None, bicBounds=None):
+                 learnField=None, fieldLr=None, fieldBounds=None, learnBic=None, bicLr=None, bicBounds=None,
+                 learnFluxBC=None, fluxBCLr=None, fluxBCBounds=None):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -873,8 +874,12 @@ class VarNet:
                 raise ValueError('periodicDeriv=%r must be a finite number >= 0' % (periodicDeriv,))
 
         learnt = {'learnCoef': (learnCoef, coefLr, coefBounds), 'learnSource': (learnSource, sourceLr, sourceBounds),
-                  'learnField': (learnField, fieldLr, fieldBounds), 'learnBic': (learnBic, bicLr, bicBounds)}
-        for lv in self.LEARNT:
+                  'learnField': (learnField, fieldLr, fieldBounds), 'learnBic': (learnBic, bicLr, bicBounds),
+                  'learnFluxBC': (learnFluxBC, fluxBCLr, fluxBCBounds)}
+        # fluxBasis / robinBasis (ADPDE) live on the flux rows: without fluxBC=True nothing would ever evaluate them
+        if sum(self._fbc_sizes(PDE)) > 0 and not fluxBC:
+            raise ValueError('the PDE carries a fluxBasis / robinBasis, which is data of the boundary-flux rows: it needs fluxBC=True')
+        for lv in self.LEARNT_ALL:
             if learnt[lv.option][0] is not None and MORvar is not None:
                 raise NotImplementedError('%s with model-order reduction is not supported: neither %s nor the observations it needs '
                                           'are' % (lv.option, lv.mor_lacks))
@@ -893,8 +898,9 @@ class VarNet:
         # field and boundary data identification -- the masked polynomial coefficients of the PDE's reaction / flux / diffusivity,
         # the masked amplitudes of its source basis, those of its diffusivity and velocity bases and those of its Dirichlet and
         # initial bases are learnt next to the network from the observations (`coefLearnData`, `sourceLearnData`, `fieldLearnData`,
-        # `bicLearnData`)
-        for lv in self.LEARNT:
+        # `bicLearnData`); learnFluxBC=...: flux boundary identification, likewise the masked amplitudes of its flux-datum and
+        # Robin-coefficient bases (`fluxBCLearnData`)
+        for lv in self.LEARNT_ALL:
             data = getattr(self, lv.parser)(PDE, *learnt[lv.option], learning_rate)
             setattr(self, lv.attr, data)
             if data is None:
@@ -952,7 +958,7 @@ class VarNet:
             raise NotImplementedError('causal=%r with towers: a rank\'s slab means would cover only its shard of the test '
                                       'functions, so the ranks together would train another objective than one rank'
                                       % (causal,))
-        for lv in self.LEARNT:
+        for lv in self.LEARNT_ALL:
             if getattr(self, lv.attr) is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
                 raise NotImplementedError('%s with towers: %s are not part of the all-reduced buffer, so every rank would follow its '
                                           'own shard' % (lv.option, lv.grads))
@@ -1011,6 +1017,8 @@ class VarNet:
             r = self.fluxRows
             if r['X'].shape[0] > 0:
                 self.engine.set_flux_bc(r['X'], r['normal'], r['coef'], r['label'], fd.biDimVal)
+                if r.get('basis') is not None:        # learnt flux and Robin amplitudes: the engine mixes coef and label itself
+                    self.engine.set_fluxbc_basis(r['basis'], r['J_flux'])
         if getattr(self.PDE, 'periodic', None) is not None:
             # fixed for the whole run like the flux rows (optimal re-draws leave them on the uniform set): registered once; a
             # network outside the kernels that run the periodic pass is refused here, with the engine's sentence
@@ -1039,6 +1047,10 @@ class VarNet:
             # likewise the boundary and initial amplitudes: every BC/IC row set registered later carries its [J, nB] basis streams
             bl = self.bicLearn
             self.engine.set_bic_learn(bl['mask'], bl['init'], bl['lo'], bl['hi'], bl['lr'])
+        if self.fbcLearn is not None:
+            # likewise the flux and Robin amplitudes, whose [J, nF] basis streams were registered with the flux rows above
+            fb = self.fbcLearn
+            self.engine.set_fluxbc_learn(fb['mask'], fb['init'], fb['lo'], fb['hi'], fb['lr'])
         self.tfData = self.engine       # name kept for scripts that poke at `VarNet.tfData`
         from .launch import mark_stage
         mark_stage('engine_ready')      # past the launcher's bootstrap deadline: a rank that trains for hours is healthy
@@ -1102,6 +1114,12 @@ class VarNet:
                      'the amplitude gradients', 'field_amplitudes', 'field_amps', 'Learnt field amplitudes (diff, then vel)'),
         LearntVector('learnBic', 'bicLearnData', 'bicLearn', 'amplitude', 'the boundary and initial bases',
                      'the amplitude gradients', 'bic_amplitudes', 'bic_amps', 'Learnt boundary and initial amplitudes (bc, then ic)'))
+    # ... and the vectors whose rows are an edge row set's, not a batch's or the BC/IC set's: same record, same handling.  LEARNT keeps
+    # its four rows (tests/test_bic_host.py reads it as the list of those four); every loop runs over LEARNT_ALL.
+    LEARNT_EDGE = (
+        LearntVector('learnFluxBC', 'fluxBCLearnData', 'fbcLearn', 'amplitude', 'the boundary-flux rows',
+                     'the amplitude gradients', 'fluxbc_amplitudes', 'fluxbc_amps', 'Learnt flux and Robin amplitudes (flux, then robin)'),)
+    LEARNT_ALL = LEARNT + LEARNT_EDGE
 
     # -- what the three learnt vectors' options share (coefLearnData, sourceLearnData, fieldLearnData) --
     @staticmethod
@@ -1549,6 +1567,107 @@ class VarNet:
             cur[sl] = v
         self.engine.set_bic_amps(cur)
 
+    # -- flux boundary identification: learnt amplitudes of a flux-datum and a Robin-coefficient basis (extension) -----
+    FBC_KEYS = ('flux', 'robin')
+
+    @staticmethod
+    def _fbc_sizes(PDE):
+        """(J_flux, J_robin): the number of functions of the PDE's flux-datum and Robin-coefficient bases (0 without one)."""
+        return len(getattr(PDE, 'fluxBasis', None) or []), len(getattr(PDE, 'robinBasis', None) or [])
+
+    @staticmethod
+    def fluxBCLearnData(PDE, learnFluxBC, fluxBCLr=None, fluxBCBounds=None, learning_rate=0.001):
+        """(No reference counterpart: `VarNet(..., learnFluxBC=...)`.)  The registration of `vn_set_fluxbc_learn`, or None without
+        learnFluxBC: mask, init, lo, hi (J = J_flux + J_robin entries each, the flux-datum streams first) and lr.  learnFluxBC =
+        {'flux': True | mask, 'robin': True | mask} (a key left out: none of that basis is learnt); the PDE's fluxAmp / robinAmp
+        are the initial guess; fluxBCLr defaults to the network's learning rate; fluxBCBounds = {'flux': ..., 'robin': ...}, each
+        (lo, hi) for every learnt amplitude of that basis or a list with one entry per function, each None or (lo, hi), None for
+        an open side."""
+        if learnFluxBC is None or learnFluxBC is False:
+            if fluxBCLr is not None:
+                raise ValueError('fluxBCLr=%r is an option of learnFluxBC=...' % (fluxBCLr,))
+            if fluxBCBounds is not None:
+                raise ValueError('fluxBCBounds is an option of learnFluxBC=...')
+            return None
+        keys = VarNet.FBC_KEYS
+        if not isinstance(learnFluxBC, dict) or not learnFluxBC or any(k not in keys for k in learnFluxBC):
+            raise ValueError('learnFluxBC must be a dict {\'flux\': True | mask, \'robin\': True | mask}, got %r' % (learnFluxBC,))
+        if fluxBCBounds is not None and (not isinstance(fluxBCBounds, dict) or any(k not in keys for k in fluxBCBounds)):
+            raise ValueError('fluxBCBounds must be a dict {\'flux\': ..., \'robin\': ...}, got %r' % (fluxBCBounds,))
+        Jl, Jc = VarNet._fbc_sizes(PDE)
+        masks, a0s, los, his = [], [], [], []
+        for key, J, amp in (('flux', Jl, 'fluxAmp'), ('robin', Jc, 'robinAmp')):
+            sel = learnFluxBC.get(key)
+            if sel is not None and sel is not False and J == 0:
+                raise ValueError('learnFluxBC[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (key, key, key))
+            if J == 0:
+                if fluxBCBounds is not None and fluxBCBounds.get(key) is not None:
+                    raise ValueError('fluxBCBounds[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (key, key, key))
+                continue
+            if sel is None or sel is False:
+                mask = np.zeros(J, dtype=bool)
+            else:
+                mask = VarNet._learn_mask(sel, J, 'learnFluxBC[%r] must be True or a mask of %d booleans (one per function of %sBasis), '
+                                          'got %r' % (key, J, key, sel))
+            a0 = np.asarray(getattr(PDE, amp), dtype=np.float64)
+            bounds = None if fluxBCBounds is None else fluxBCBounds.get(key)
+            lo, hi = VarNet._learn_bounds(bounds, 'fluxBCBounds[%r]' % (key,), mask, a0, 'an amplitude', 'learnFluxBC',
+                                          'fluxBCBounds[%r] must be (lo, hi) or a list of %d entries, each None or (lo, hi), got %r'
+                                          % (key, J, bounds))
+            masks.append(mask); a0s.append(a0); los.append(lo); his.append(hi)
+        mask = np.concatenate(masks) if masks else np.zeros(0, dtype=bool)
+        if not mask.any():
+            raise ValueError('learnFluxBC selects no amplitude')
+        lr = VarNet._learn_rate(fluxBCLr, 'fluxBCLr', learning_rate)
+        return dict(mask=[int(x) for x in mask], init=np.concatenate(a0s), lo=np.concatenate(los), hi=np.concatenate(his),
+                    lr=lr, Jl=Jl, Jc=Jc)
+
+    def _fbc_vector(self):
+        """The J = J_flux + J_robin amplitudes as one vector: the engine's with learnFluxBC, else the PDE's."""
+        Jl, Jc = self._fbc_sizes(self.PDE)
+        if getattr(self, 'fbcLearn', None) is not None and getattr(self, 'engine', None) is not None:
+            return np.asarray(self.engine.get_fluxbc_amps(J=Jl + Jc), dtype=np.float64)
+        return np.concatenate([np.asarray(getattr(self.PDE, 'fluxAmp', []), dtype=np.float64),
+                               np.asarray(getattr(self.PDE, 'robinAmp', []), dtype=np.float64)])
+
+    def fluxBCAmplitudes(self):
+        """{'flux': J_flux amplitudes, 'robin': J_robin amplitudes} of the PDE's flux-datum and Robin-coefficient bases at the
+        current state: the learnt values with learnFluxBC, else the PDE's."""
+        Jl, Jc = self._fbc_sizes(self.PDE)
+        if Jl + Jc == 0:
+            raise ValueError('fluxBCAmplitudes: the PDE has no flux or Robin basis (ADPDE(..., fluxBasis=[...], robinBasis=[...]))')
+        v = self._fbc_vector()
+        return {'flux': v[:Jl].copy(), 'robin': v[Jl:].copy()}
+
+    def fluxBCGrad(self):
+        """d loss / d amplitude of the last gradient evaluation as {'flux': ..., 'robin': ...} (zeros where not learnt)."""
+        if self.fbcLearn is None:
+            raise ValueError('fluxBCGrad: this instance learns no flux or Robin amplitudes (learnFluxBC=...)')
+        Jl, Jc = self._fbc_sizes(self.PDE)
+        g = np.asarray(self.engine.get_fluxbc_amps(grad=True, J=Jl + Jc)[1], dtype=np.float64)
+        return {'flux': g[:Jl].copy(), 'robin': g[Jl:].copy()}
+
+    def setFluxBCAmplitudes(self, amps):
+        """Overwrite amplitudes between train() calls: {'flux': [...], 'robin': [...]} (a key left out keeps its values).  Not
+        clamped to fluxBCBounds (the next update is)."""
+        if self.fbcLearn is None:
+            raise ValueError('setFluxBCAmplitudes: this instance learns no flux or Robin amplitudes (learnFluxBC=...)')
+        if not isinstance(amps, dict) or not amps or any(k not in self.FBC_KEYS for k in amps):
+            raise ValueError('setFluxBCAmplitudes takes a dict {\'flux\': [...], \'robin\': [...]}, got %r' % (amps,))
+        Jl, Jc = self._fbc_sizes(self.PDE)
+        cur = self._fbc_vector()
+        for key, sl, J in (('flux', slice(0, Jl), Jl), ('robin', slice(Jl, Jl + Jc), Jc)):
+            if key not in amps:
+                continue
+            try:
+                v = np.asarray(amps[key], dtype=np.float64).reshape(-1)
+            except (TypeError, ValueError):
+                v = np.empty(0)
+            if J == 0 or v.size != J or not np.all(np.isfinite(v)):
+                raise ValueError('setFluxBCAmplitudes[%r] takes %d finite numbers, got %r' % (key, J, amps[key]))
+            cur[sl] = v
+        self.engine.set_fluxbc_amps(cur)
+
     # -- causal time-slab weights (extension) ------------------------------------------------------
     @staticmethod
     def _check_causal_eps(eps):
@@ -1794,7 +1913,10 @@ class VarNet:
         host in fp64: the uniform boundary points `mesh.bCoordinates[bInd]` (paired with the time nodes like the Dirichlet rows),
         the indicator's outward unit normal n, coef = b/a and label = g(x[,t])/a, so that the row's residual is
         n . grad_x u + coef u - label (DESIGN.md "Boundary flux term").  Returns dict(X, normal, coef, label, edges) with
-        edges = [(bInd, BCtype, rows)] in indicator order.
+        edges = [(bInd, BCtype, rows)] in indicator order.  With a fluxBasis / robinBasis (ADPDE) also basis = [J_flux + J_robin, nF]
+        in fp64, "flux, then robin" -- every function on the rows of its own indicator, zero elsewhere -- and J_flux; the sums at
+        the PDE's amplitudes are folded into label and coef here unless the amplitudes are learnt (`learnFluxBC`: the engine mixes
+        them, and coef / label stay b/a and g/a).
         """
         PDE, dim = self.PDE, self.dim
         td = PDE.timeDependent
@@ -1817,7 +1939,33 @@ class VarNet:
             edges.append((bInd, PDE.BCtype[bInd], n))
         if not X:
             return dict(X=np.zeros([0, self.inpDim]), normal=np.zeros([0, dim]), coef=np.zeros(0), label=np.zeros(0), edges=[])
-        return dict(X=np.vstack(X), normal=np.vstack(nrm), coef=np.concatenate(coef), label=np.concatenate(label), edges=edges)
+        out = dict(X=np.vstack(X), normal=np.vstack(nrm), coef=np.concatenate(coef), label=np.concatenate(label), edges=edges)
+        Jl, Jc = self._fbc_sizes(PDE)
+        if Jl + Jc > 0:
+            nF = out['X'].shape[0]
+            span, i0 = {}, 0
+            for bInd, _, n in edges:
+                span[bInd] = (i0, i0 + n)
+                i0 += n
+            S = np.zeros((Jl + Jc, nF), dtype=np.float64)
+            entries = [('fluxBasis', j, e) for j, e in enumerate(getattr(PDE, 'fluxBasis', None) or [])] \
+                + [('robinBasis', j, e) for j, e in enumerate(getattr(PDE, 'robinBasis', None) or [])]
+            for row, (name, j, (bInd, f)) in enumerate(entries):
+                r0, r1 = span[bInd]
+                x = out['X'][r0:r1]
+                targ = [x[:, dim:dim + 1]] if td else []
+                v = np.asarray(f(x[:, :dim], *targ), dtype=np.float64)
+                if v.size != r1 - r0:
+                    raise ValueError('%s[%d] must return one value per point (a column), got shape %s for %d points'
+                                     % (name, j, v.shape, r1 - r0))
+                S[row, r0:r1] = v.reshape(-1)
+            out['basis'], out['J_flux'] = S, Jl
+            if getattr(self, 'fbcLearn', None) is None:
+                a = self._fbc_vector()
+                out['label'] = out['label'] + a[:Jl] @ S[:Jl]
+                out['coef'] = out['coef'] + a[Jl:] @ S[Jl:]
+                out['basis'] = None
+        return out
 
     @staticmethod
     def _check_obs_weight(lam):
@@ -2653,7 +2801,7 @@ class VarNet:
                         trainW, w_eff, _ = set_train_weights(tData, weight)
             epoch = first + nblk
         trainRes.flushPlots()
-        for lv in self.LEARNT:
+        for lv in self.LEARNT_ALL:
             data = getattr(self, lv.attr)
             if data is not None and self.rank == 0:
                 scale = data.get('scale', 1.0)           # (coefficients are reported in the user's scale: `coefficients()`)
@@ -2695,7 +2843,7 @@ class VarNet:
         if slot[0] == 'Adam':
             out['beta1_power'] = np.float32(0.9 ** (step + 1))       # TF keeps beta^(t+1) for the next update
             out['beta2_power'] = np.float32(0.999 ** (step + 1))
-        for lv in self.LEARNT:
+        for lv in self.LEARNT_ALL:
             if getattr(self, lv.attr, None) is not None:
                 # the values in the engine's scale (vn_get_*: the nine coefficients, the J source amplitudes, the J field amplitudes
                 # with the diffusivity streams first); their Adam slots have no entry point and restart from zero
@@ -2723,7 +2871,7 @@ class VarNet:
         step = np.array([int(arrays['global_step']) if 'global_step' in arrays else 0], dtype=np.int64)
         blob = np.concatenate([step.view(np.uint8), np.concatenate(th + m + v).astype(np.float32).view(np.uint8)])
         self.engine.import_state(blob)
-        for lv in self.LEARNT:
+        for lv in self.LEARNT_ALL:
             if getattr(self, lv.attr, None) is not None and lv.key in arrays:
                 getattr(self.engine, 'set_' + lv.engine)(np.asarray(arrays[lv.key], dtype=np.float64).reshape(-1))
 
