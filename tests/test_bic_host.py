@@ -370,7 +370,7 @@ def test_learning_next_to_the_other_vectors():
               learnField={'diff': True}, learnCoef={'reaction': [1, 0, 0]})
     assert vn.bicLearn is not None and vn.srcLearn is not None and vn.fldLearn is not None and vn.coefLearn is not None
     assert vn.engine.bic_reg['mask'] == [0, 0, 0, 1, 1]
-    assert [lv.option for lv in VarNet.LEARNT] == ['learnCoef', 'learnSource', 'learnField', 'learnBic']
+    assert [lv.option for lv in VarNet.LEARNT] == ['learnCoef', 'learnSource', 'learnField', 'learnBic', 'learnFluxBC']
 
 
 def test_checkpoint_round_trip_of_the_amplitudes():

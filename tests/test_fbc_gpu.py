@@ -5,8 +5,8 @@ tests/fbc_ref.py on the cases of tests/fbc_cases.py -- on the automatic route (c
 kernels and de-duplicated on an identity point map -- loss pieces and the theta-gradient at the mixed data, that a = 0 and
 learning off give back the bits of an engine without a basis, the J variants and the mask, the capped grid, the evaluations at
 the device amplitudes, the Adam step of the amplitudes over eight steps against tests/learnt_adam_ref.Adam64 with a bound on a
-Robin amplitude that is reached and held, vn_train_epoch, snapshot / rollback, all five learnt vectors on one engine, every
-refusal, and two recoveries end to end.
+Robin amplitude that is reached and held, vn_train_epoch, snapshot / rollback, all five learnt vectors on one engine (and each
+keyed one switched off and on again there), every refusal, and two recoveries end to end.
 
 Bar per component (tests/fbc_cases.py): |g - g64| <= GRAD_RTOL * max(|g64|, 0.01 S_j).  The worst errors are written to
 fbc_parity.json in the directory VN_RECORD_DIR names (default: profile_out/ beside tests/; committed copy: profiles/fbc_parity.json).
@@ -259,37 +259,43 @@ def _flux_rows_for(i):
     return fx, S, amp
 
 
+def _build_five(i, route, flux_mixed, learn_flux, others=True):
+    """The engine of tests/test_learnt_adam_gpu.build (coefficients, source and field amplitudes learnt) with the BC/IC basis learnt
+    too -- without `others` none of the four -- and the seeded flux rows: `flux_mixed` at the pre-mixed coef and label, else with
+    their (2, 1) basis, whose amplitudes `learn_flux` learns."""
+    J = 3
+    B, bamp = bc.basis(i, J)
+    fx, S, famp = _flux_rows_for(i)
+    coef1, label1 = fc.fma_mix(fx['coef'], S[2:], famp[2:]), fc.fma_mix(fx['label'], S[:2], famp[:2])
+    eng = build_three(i, route, [lc.whole(i)])
+    try:
+        if others:
+            eng.set_bic_basis(-1, B)
+            eng.set_bic_learn([1] * J, bamp, lr=0.01)
+        else:
+            eng.set_coef_learn(None)
+            eng.set_source_learn(None)
+            eng.set_field_learn(None)
+        if flux_mixed:
+            eng.set_flux_bc(fx['X'], fx['normal'], coef1, label1, BIDIMVAL)
+        else:
+            eng.set_flux_bc(fx['X'], fx['normal'], fx['coef'], fx['label'], BIDIMVAL)
+            eng.set_fluxbc_basis(S, 2)
+        if learn_flux:
+            eng.set_fluxbc_learn([1] * 3, famp, lr=0.01)
+    except Exception:
+        eng.close()
+        raise
+    return eng
+
+
 @pytest.mark.parametrize('route', ['auto', 'dedup'])
 @pytest.mark.parametrize('i', lc.CASES[:2], ids=lc.IDS[:2])
 def test_all_five_vectors_on_one_engine(i, route):
     """Each gradient is bitwise what it is alone: the four others' with the flux rows registered at the pre-mixed coef and label,
     the flux amplitudes' on an engine that learns nothing else; one step moves all five on one counter."""
-    J = 3
-    B, bamp = bc.basis(i, J)
-    fx, S, famp = _flux_rows_for(i)
-    coef1, label1 = fc.fma_mix(fx['coef'], S[2:], famp[2:]), fc.fma_mix(fx['label'], S[:2], famp[:2])
-
-    def build(flux_mixed, learn_flux, others=True):
-        eng = build_three(i, route, [lc.whole(i)])
-        try:
-            if others:
-                eng.set_bic_basis(-1, B)
-                eng.set_bic_learn([1] * J, bamp, lr=0.01)
-            else:
-                eng.set_coef_learn(None)
-                eng.set_source_learn(None)
-                eng.set_field_learn(None)
-            if flux_mixed:
-                eng.set_flux_bc(fx['X'], fx['normal'], coef1, label1, BIDIMVAL)
-            else:
-                eng.set_flux_bc(fx['X'], fx['normal'], fx['coef'], fx['label'], BIDIMVAL)
-                eng.set_fluxbc_basis(S, 2)
-            if learn_flux:
-                eng.set_fluxbc_learn([1] * 3, famp, lr=0.01)
-        except Exception:
-            eng.close()
-            raise
-        return eng
+    def build(*a, **kw):
+        return _build_five(i, route, *a, **kw)
 
     four = build(True, False)
     try:
@@ -314,6 +320,40 @@ def test_all_five_vectors_on_one_engine(i, route):
         assert eng.step == 1
         for k, n in NAMES:
             assert np.all(getattr(eng, 'get_' + n)() != got[k][0]), k
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize('route', ['auto', 'dedup'])
+def test_a_vector_switched_off_and_on_again_changes_nothing(route):
+    """With all five vectors on, each of field, bic and fluxbc is switched off -- which frees its state and its work buffers -- and
+    registered again at the same values: the next evaluation allocates and mixes anew, and the network gradient and all five
+    (values, gradient) are bitwise those of a twin engine that never switched anything off."""
+    i = lc.CASES[0]
+    bamp, famp = bc.basis(i, 3)[1], _flux_rows_for(i)[2]
+    again = {'field': ([1] * lc.J, lc.initial(i)['field'], None, None, lc.LR), 'bic': ([1] * 3, bamp, None, None, 0.01),
+             'fluxbc': ([1] * 3, famp, None, None, 0.01)}
+
+    def evaluate(eng):
+        g = grad_of(eng)
+        return g, {k: getattr(eng, 'get_' + n)(grad=True) for k, n in NAMES}
+
+    twin = _build_five(i, route, False, True)
+    try:
+        g0, v0 = evaluate(twin)
+    finally:
+        twin.close()
+    assert all(np.all(v0[k][1] != 0.0) for k, _ in NAMES)
+    eng = _build_five(i, route, False, True)
+    try:
+        evaluate(eng)                                 # (the work buffers exist before the first switch)
+        for kind, reg in again.items():
+            getattr(eng, 'set_%s_learn' % kind)(None)
+            getattr(eng, 'set_%s_learn' % kind)(*reg)
+            g, v = evaluate(eng)
+            assert np.array_equal(g, g0), kind
+            for k, _ in NAMES:
+                assert np.array_equal(v[k][0], v0[k][0]) and np.array_equal(v[k][1], v0[k][1]), (kind, k, v[k], v0[k])
     finally:
         eng.close()
 

@@ -381,8 +381,8 @@ def test_learning_next_to_the_other_vectors():
               learnSource=True, learnField={'diff': True}, learnCoef={'reaction': [1, 0, 0]}, learnBic={'ic': True})
     assert all(getattr(vn, a) is not None for a in ('fbcLearn', 'srcLearn', 'fldLearn', 'coefLearn', 'bicLearn'))
     assert vn.engine.fbc_reg['mask'] == [0, 0, 1, 1]
-    assert [lv.option for lv in VarNet.LEARNT_ALL] == ['learnCoef', 'learnSource', 'learnField', 'learnBic', 'learnFluxBC']
-    assert VarNet.LEARNT_ALL[4].key == 'fluxbc_amplitudes' and VarNet.LEARNT_ALL[:4] == VarNet.LEARNT
+    assert [lv.option for lv in VarNet.LEARNT] == ['learnCoef', 'learnSource', 'learnField', 'learnBic', 'learnFluxBC']
+    assert VarNet.LEARNT[4].key == 'fluxbc_amplitudes'
 
 
 def test_checkpoint_round_trip_of_the_amplitudes():

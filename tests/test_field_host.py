@@ -383,6 +383,8 @@ def test_refusals():
         make(pde(velBasis=OMEGA), learnField={'diff': True})
     with pytest.raises(ValueError, match=r"fieldBounds\['vel'\]: the PDE has no vel basis"):
         make(pde(diffBasis=CHI), learnField={'diff': True}, fieldBounds={'vel': (0, 1)})
+    with pytest.raises(ValueError, match='^learnField selects no amplitude$'):      # (a PDE without bases: nothing to select from)
+        VarNet.fieldLearnData(pde(), {'diff': False})
     with pytest.raises(ValueError, match='learnField needs observations=.*every amplitude admits a solution'):
         make(obs=None, learnField={'diff': True})
     for opt in ('lbfgs', 'rmsprop', 'rms'):

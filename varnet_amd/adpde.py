@@ -207,8 +207,8 @@ class ADPDE:
         def const_field(val, ncol):
             return lambda x, t=0: val * np.ones([np.shape(x)[0], ncol])
 
-        diffBasis, diffAmp = self._check_field_basis('diffBasis', 'diffAmp', diffBasis, diffAmp, MORvar, 1, dim, const_field)
-        velBasis, velAmp = self._check_field_basis('velBasis', 'velAmp', velBasis, velAmp, MORvar, dim, dim, const_field)
+        diffBasis, diffAmp = self._check_field_basis('diffBasis', 'diffAmp', diffBasis, diffAmp, MORvar, 1, const_field)
+        velBasis, velAmp = self._check_field_basis('velBasis', 'velAmp', velBasis, velAmp, MORvar, dim, const_field)
         if d_diffBasis is not None and diffBasis is None:
             raise ValueError('d_diffBasis is an option of diffBasis=[chi_1, ..., chi_J]!')
         if diffBasis is not None:
@@ -217,7 +217,7 @@ class ADPDE:
             if not isinstance(d_diffBasis, (list, tuple)) or len(d_diffBasis) != len(diffBasis):
                 raise ValueError('d_diffBasis must be a list of %d entries, one gradient per function of diffBasis!' % len(diffBasis))
             d_diffBasis, _ = self._check_field_basis('d_diffBasis', 'diffAmp', [0.0 if f is None else f for f in d_diffBasis], None,
-                                                     MORvar, dim, dim, const_field)
+                                                     MORvar, dim, const_field)
         if (0 if diffBasis is None else len(diffBasis)) + (0 if velBasis is None else len(velBasis)) > self.FLD_MAX:
             raise ValueError('diffBasis and velBasis hold %d functions together, at most %d are supported!'
                              % (len(diffBasis or []) + len(velBasis or []), self.FLD_MAX))
@@ -391,112 +391,79 @@ class ADPDE:
         if robinBasis is not None:
             self.robinBasis, self.robinAmp = robinBasis, robinAmp
 
-    def _check_fbc_basis(self, name, ampName, basis, amp, MORvar):
-        """(list of (bInd, callable) pairs, amplitudes) of fluxBasis / robinBasis, or (None, None) without one; ValueError names
-        the field.  Called at the end of __init__: BCtype and periodic are set."""
+    def _check_basis(self, name, ampName, basis, amp, MORvar, cap, shape_text, entry, hint='[...]'):
+        """(checked entries, amplitudes) of one basis option, or (None, None) without one; ValueError names the option.  The basis is
+        a non-empty list (`shape_text` says of what) of at most `cap` entries; `entry(j, e)` checks entry j and returns what is kept
+        of it; the amplitudes default to zeros."""
         if basis is None:
             if amp is not None:
-                raise ValueError('%s is an option of %s=[...]!' % (ampName, name))
+                raise ValueError('%s is an option of %s=%s!' % (ampName, name, hint))
             return None, None
         if not isinstance(basis, (list, tuple)) or len(basis) == 0:
-            raise ValueError('%s must be a non-empty list [(bInd, f_1), ..., (bInd, f_J)]!' % name)
-        if len(basis) > self.FBC_MAX:
-            raise ValueError('%s holds %d functions, at most %d are supported!' % (name, len(basis), self.FBC_MAX))
-        out = []
-        for j, e in enumerate(basis):
+            raise ValueError('%s must be a non-empty list %s!' % (name, shape_text))
+        if len(basis) > cap:
+            raise ValueError('%s holds %d functions, at most %d are supported!' % (name, len(basis), cap))
+        out = [entry(j, e) for j, e in enumerate(basis)]
+        if amp is None:
+            amp = np.zeros(len(out))
+        try:
+            amp = np.array(np.reshape(np.asarray(amp, dtype=float), -1))
+        except (TypeError, ValueError):
+            raise ValueError('%s must be a list of %d numbers, one per function of %s!' % (ampName, len(out), name))
+        if amp.size != len(out):
+            raise ValueError('%s holds %d values for the %d functions of %s!' % (ampName, amp.size, len(out), name))
+        if not np.all(np.isfinite(amp)):
+            raise ValueError('%s must be finite!' % ampName)
+        if MORvar is not None:
+            raise NotImplementedError('%s with model-order reduction is not supported: parametric basis functions are out of scope '
+                                      '(the basis streams are assembled once, for all parameter batches)' % name)
+        return out, amp
+
+    def _edge_entry(self, name, sym, fun, refused, only):
+        """The entry check of a basis on boundary indicators (bcBasis, fluxBasis, robinBasis): a pair (bInd, callable) whose
+        indicator is not periodic and carries no condition among `refused`.  `sym` and `fun` name the callable, `only` says which
+        data has such a basis.  Used at the end of __init__: BCtype and periodic are set."""
+        def entry(j, e):
             if not isinstance(e, (list, tuple)) or len(e) != 2 or isinstance(e[0], bool) or not isinstance(e[0], (int, np.integer)):
-                raise ValueError('%s[%d] must be a pair (bInd, f) of a boundary indicator and a callable!' % (name, j))
+                raise ValueError('%s[%d] must be a pair (bInd, %s) of a boundary indicator and a callable!' % (name, j, sym))
             bInd, f = int(e[0]), e[1]
             if not callable(f):
-                raise ValueError('%s[%d]: the function must be callable, like the g of a boundary condition!' % (name, j))
+                raise ValueError('%s[%d]: %s must be callable, like the g of a boundary condition!' % (name, j, fun))
             if not 0 <= bInd < self.domain.bIndNum:
                 raise ValueError('%s[%d]: boundary indicator %d outside [0, %d)!' % (name, j, bInd, self.domain.bIndNum))
             if self.BCtype[bInd] == 'Periodic':
                 raise ValueError('%s[%d]: boundary indicator %d is paired by `periodic`, it carries no boundary data!' % (name, j, bInd))
-            if self.BCtype[bInd] == 'Dirichlet':
-                raise ValueError('%s[%d]: boundary indicator %d carries a Dirichlet condition, only Neumann and Robin data has a '
-                                 'flux basis (bcBasis is the Dirichlet one)!' % (name, j, bInd))
-            out.append((bInd, f))
-        if amp is None:
-            amp = np.zeros(len(out))
-        try:
-            amp = np.array(np.reshape(np.asarray(amp, dtype=float), -1))
-        except (TypeError, ValueError):
-            raise ValueError('%s must be a list of %d numbers, one per function of %s!' % (ampName, len(out), name))
-        if amp.size != len(out):
-            raise ValueError('%s holds %d values for the %d functions of %s!' % (ampName, amp.size, len(out), name))
-        if not np.all(np.isfinite(amp)):
-            raise ValueError('%s must be finite!' % ampName)
-        if MORvar is not None:
-            raise NotImplementedError('%s with model-order reduction is not supported: parametric basis functions are out of scope '
-                                      '(the basis streams are assembled once, for all parameter batches)' % name)
-        return out, amp
+            if self.BCtype[bInd] in refused:
+                raise ValueError('%s[%d]: boundary indicator %d carries a %s condition, %s!' % (name, j, bInd, self.BCtype[bInd], only))
+            return bInd, f
+        return entry
+
+    def _check_fbc_basis(self, name, ampName, basis, amp, MORvar):
+        """fluxBasis / robinBasis: (bInd, callable) pairs on the Neumann and Robin indicators."""
+        return self._check_basis(name, ampName, basis, amp, MORvar, self.FBC_MAX, '[(bInd, f_1), ..., (bInd, f_J)]',
+                                 self._edge_entry(name, 'f', 'the function', ('Dirichlet',),
+                                                  'only Neumann and Robin data has a flux basis (bcBasis is the Dirichlet one)'))
 
     def _check_bic_basis(self, name, ampName, basis, amp, MORvar, edges):
-        """(list of entries, amplitudes) of bcBasis (`edges`: (bInd, callable) pairs) / icBasis (callables), or (None, None) without
-        one; ValueError names the field.  Called at the end of __init__: BCtype, periodic and timeDependent are set."""
-        if basis is None:
-            if amp is not None:
-                raise ValueError('%s is an option of %s=[...]!' % (ampName, name))
-            return None, None
-        shape = '[(bInd, gamma_1), ..., (bInd, gamma_J)]' if edges else '[iota_1, ..., iota_J]'
-        if not isinstance(basis, (list, tuple)) or len(basis) == 0:
-            raise ValueError('%s must be a non-empty list %s!' % (name, shape))
-        if len(basis) > self.BIC_MAX:
-            raise ValueError('%s holds %d functions, at most %d are supported!' % (name, len(basis), self.BIC_MAX))
-        if not edges and not self.timeDependent:
-            raise ValueError('icBasis needs a time-dependent problem: a steady problem has no initial condition!')
-        out = []
-        for j, e in enumerate(basis):
-            if not edges:
-                if not callable(e):
-                    raise ValueError('icBasis[%d] must be callable, like an initial condition!' % j)
-                out.append(e)
-                continue
-            if not isinstance(e, (list, tuple)) or len(e) != 2 or isinstance(e[0], bool) or not isinstance(e[0], (int, np.integer)):
-                raise ValueError('bcBasis[%d] must be a pair (bInd, gamma) of a boundary indicator and a callable!' % j)
-            bInd, f = int(e[0]), e[1]
-            if not callable(f):
-                raise ValueError('bcBasis[%d]: gamma must be callable, like the g of a boundary condition!' % j)
-            if not 0 <= bInd < self.domain.bIndNum:
-                raise ValueError('bcBasis[%d]: boundary indicator %d outside [0, %d)!' % (j, bInd, self.domain.bIndNum))
-            if self.BCtype[bInd] == 'Periodic':
-                raise ValueError('bcBasis[%d]: boundary indicator %d is paired by `periodic`, it carries no boundary data!' % (j, bInd))
-            if self.BCtype[bInd] != 'Dirichlet':
-                raise ValueError('bcBasis[%d]: boundary indicator %d carries a %s condition, only Dirichlet data has a basis!'
-                                 % (j, bInd, self.BCtype[bInd]))
-            out.append((bInd, f))
-        if amp is None:
-            amp = np.zeros(len(out))
-        try:
-            amp = np.array(np.reshape(np.asarray(amp, dtype=float), -1))
-        except (TypeError, ValueError):
-            raise ValueError('%s must be a list of %d numbers, one per function of %s!' % (ampName, len(out), name))
-        if amp.size != len(out):
-            raise ValueError('%s holds %d values for the %d functions of %s!' % (ampName, amp.size, len(out), name))
-        if not np.all(np.isfinite(amp)):
-            raise ValueError('%s must be finite!' % ampName)
-        if MORvar is not None:
-            raise NotImplementedError('%s with model-order reduction is not supported: parametric basis functions are out of scope '
-                                      '(the basis streams are assembled once, for all parameter batches)' % name)
-        return out, amp
+        """bcBasis (`edges`: (bInd, callable) pairs on the Dirichlet indicators) / icBasis (callables, of a time-dependent problem)."""
+        if edges:
+            return self._check_basis(name, ampName, basis, amp, MORvar, self.BIC_MAX, '[(bInd, gamma_1), ..., (bInd, gamma_J)]',
+                                     self._edge_entry(name, 'gamma', 'gamma', ('Neumann', 'Robin'), 'only Dirichlet data has a basis'))
 
-    def _check_field_basis(self, name, ampName, basis, amp, MORvar, ncol, dim, const_field):
-        """(list of callables, amplitudes) of diffBasis / velBasis / d_diffBasis, or (None, None) without one; ValueError names
-        the field.  An entry is a number, a list of `ncol` numbers (ncol > 1) or a callable."""
-        if basis is None:
-            if amp is not None:
-                raise ValueError('%s is an option of %s=[f_1, ..., f_J]!' % (ampName, name))
-            return None, None
-        if not isinstance(basis, (list, tuple)) or len(basis) == 0:
-            raise ValueError('%s must be a non-empty list of numbers or callables [f_1, ..., f_J]!' % name)
-        if len(basis) > self.FLD_MAX:
-            raise ValueError('%s holds %d functions, at most %d are supported!' % (name, len(basis), self.FLD_MAX))
-        out = []
-        for j, f in enumerate(basis):
+        def entry(j, e):
+            if not self.timeDependent:
+                raise ValueError('icBasis needs a time-dependent problem: a steady problem has no initial condition!')
+            if not callable(e):
+                raise ValueError('icBasis[%d] must be callable, like an initial condition!' % j)
+            return e
+        return self._check_basis(name, ampName, basis, amp, MORvar, self.BIC_MAX, '[iota_1, ..., iota_J]', entry)
+
+    def _check_field_basis(self, name, ampName, basis, amp, MORvar, ncol, const_field):
+        """diffBasis / velBasis / d_diffBasis: an entry is a number, a list of `ncol` numbers (ncol > 1) or a callable, and is kept
+        as a callable."""
+        def entry(j, f):
             if callable(f):
-                out.append(f)
-                continue
+                return f
             try:
                 v = np.reshape(np.asarray(f, dtype=float), -1)
             except (TypeError, ValueError):
@@ -504,21 +471,9 @@ class ADPDE:
             if isinstance(f, bool) or v.size not in (1, ncol) or not np.all(np.isfinite(v)):
                 raise ValueError('%s[%d] must be callable, a finite number%s!'
                                  % (name, j, '' if ncol == 1 else ' or a list of %d finite numbers' % ncol))
-            out.append(const_field(v if v.size == ncol else float(v[0]), ncol))
-        if amp is None:
-            amp = np.zeros(len(out))
-        try:
-            amp = np.array(np.reshape(np.asarray(amp, dtype=float), -1))
-        except (TypeError, ValueError):
-            raise ValueError('%s must be a list of %d numbers, one per function of %s!' % (ampName, len(out), name))
-        if amp.size != len(out):
-            raise ValueError('%s holds %d values for the %d functions of %s!' % (ampName, amp.size, len(out), name))
-        if not np.all(np.isfinite(amp)):
-            raise ValueError('%s must be finite!' % ampName)
-        if MORvar is not None:
-            raise NotImplementedError('%s with model-order reduction is not supported: parametric basis functions are out of scope '
-                                      '(the basis streams are assembled once, for all parameter batches)' % name)
-        return out, amp
+            return const_field(v if v.size == ncol else float(v[0]), ncol)
+        return self._check_basis(name, ampName, basis, amp, MORvar, self.FLD_MAX, 'of numbers or callables [f_1, ..., f_J]', entry,
+                                 hint='[f_1, ..., f_J]')
 
     @staticmethod
     def field_basis_values(basis, name, ncol, x, t=()):

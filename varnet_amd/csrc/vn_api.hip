@@ -155,7 +155,14 @@ struct Learnt {
   double* grad = nullptr;                         // [cap] gradient of the last gradient evaluation
   float* part = nullptr;                          // [maxblk, J] partials of the reduction
   int blocks = 0;                                 // partials the current gradient evaluation wrote (0: the batch has nothing to reduce)
-};
+  struct Work { float* p = nullptr; long cap = 0; } work[3];   // the feature's own work buffers, by its *Work slot: allocated on
+};                                                             // first use (lv_ensure), freed with the vector (learnt_free)
+enum CoefWork { CW_ACC };                   // [3, U] accR_j, accF_j, gs_j of the de-duplicated step
+enum SrcWork { SW_MIX };                    // [nT] s0 + sum_j a_j phi_j of the batch being evaluated
+enum FldWork { FW_MIX, FW_CSR, FW_PACK };   // [nT, dim] g0 + sum_j b_j G_j of the batch being evaluated; the same in CSR order (de-duplicated
+                                            // step), rebuilt every evaluation; [nT, 4] (u, grad u) of the batch's own rows (row-wise gradient)
+enum BicWork { BW_MIX };                    // [nBreg] label0 + sum_j a_j B_j of the BC/IC set the batch being evaluated reads
+enum FbcWork { XW_LABEL, XW_COEF };         // [nF] label0 + sum_{j < Jl} a_j S_j and [nF] coef0 + sum_{j >= Jl} a_j S_j of the flux rows
 
 struct LearntKind {
   int cap;                    // capacity, and the stride of (value | m | v)
@@ -274,16 +281,8 @@ struct vn_engine {
   // the vectors learnt next to the parameters, by LearntId: the nine coefficients of inverse mode (vn_set_coef_learn),
   // which live on the device while they are learnt, and the engine-wide amplitudes of the batches' source bases
   // (vn_set_source_learn) and gcoef bases (vn_set_field_learn), of the BC/IC label bases (vn_set_bic_learn) and of the flux rows'
-  // bases (vn_set_fluxbc_learn), all of vn_learnt.hip; then each feature's own work buffers
+  // bases (vn_set_fluxbc_learn), all of vn_learnt.hip; each carries its feature's own work buffers
   Learnt lv[LV_N];
-  float* cl_acc = nullptr; long cl_acc_cap = 0;   // [3, U] accR_j, accF_j, gs_j of the de-duplicated step
-  float* sl_mix = nullptr; long sl_mix_cap = 0;   // [nT] s0 + sum_j a_j phi_j of the batch being evaluated
-  float* fl_mix = nullptr; long fl_mix_cap = 0;   // [nT, dim] g0 + sum_j b_j G_j of the batch being evaluated
-  float* fl_csr = nullptr; long fl_csr_cap = 0;   // [nT, dim] fl_mix in CSR order (de-duplicated step), rebuilt every evaluation
-  float* fl_pack = nullptr; long fl_pack_cap = 0; // [nT, 4] (u, grad u) of the batch's own rows (row-wise gradient evaluation)
-  float* bl_mix = nullptr; long bl_mix_cap = 0;   // [nBreg] label0 + sum_j a_j B_j of the BC/IC set the batch being evaluated reads
-  float* fb_label = nullptr; long fb_label_cap = 0;   // [nF] label0 + sum_{j < Jl} a_j S_j of the flux rows
-  float* fb_coef = nullptr; long fb_coef_cap = 0;     // [nF] coef0 + sum_{j >= Jl} a_j S_j of the flux rows
   float* snap = nullptr;       // vn_state_snapshot: device copy of (theta | m | v), 3 P floats
   int64_t snap_step = -1;      // step counter at the snapshot (-1: none)
   PointRoute point_route = PointRoute::automatic;   // vn_debug_point_route(route & 3)
@@ -424,6 +423,21 @@ int ensure(float** p, long* cap, long need) {
   return VN_OK;
 }
 
+// work buffer `slot` of learnt vector `id`: the pointer, and room for `need` floats
+inline float* lv_work(const vn_engine* h, int id, int slot) { return h->lv[id].work[slot].p; }
+int lv_ensure(vn_engine* h, int id, int slot, long need) { return ensure(&h->lv[id].work[slot].p, &h->lv[id].work[slot].cap, need); }
+
+// What the mixes at the start of an evaluation end in, once the caller has found the rows' basis to be the engine's: work buffer `slot`
+// of vector `id` = base + sum_{j < J} amp[first + j] stream_j over n entries (vn_learnt.hip)
+int learnt_mix(vn_engine* h, int id, int slot, const float* base, const float* stream, int first, int J, long n) {
+  if (n <= 0) return VN_OK;
+  if (int rc = lv_ensure(h, id, slot, n)) return rc;
+  VnMixArgs a{};
+  a.base = base; a.stream = stream; a.amp = h->lv[id].state + first; a.J = J; a.n = n; a.out = lv_work(h, id, slot);
+  HIPCHK(vn_learnt_mix_launch(a, h->stream));
+  return VN_OK;
+}
+
 uint64_t splitmix64(uint64_t& s) {
   s += 0x9E3779B97F4A7C15ull;
   uint64_t z = s;
@@ -460,15 +474,15 @@ inline int bic_basis_J(const vn_engine* h, const Batch& b) { return b.biLabel ? 
 // (while boundary / initial amplitudes are learnt, a batch whose set has a basis reads the mixed labels bic_mix formed at the start
 // of the evaluation: every launch site takes its labels from here)
 inline bool bic_learnt(const vn_engine* h, const Batch& b) { return h->lv[LV_BIC].on && bic_basis(h, b); }
-inline const float* bi_y(const vn_engine* h, const Batch& b) { return bic_learnt(h, b) ? h->bl_mix : bi_y0(h, b); }
+inline const float* bi_y(const vn_engine* h, const Batch& b) { return bic_learnt(h, b) ? lv_work(h, LV_BIC, BW_MIX) : bi_y0(h, b); }
 // (while amplitudes are learnt, a batch with a basis reads the mixed stream source_mix formed at the start of the evaluation)
 inline bool src_learnt(const vn_engine* h, const Batch& b) { return h->lv[LV_SRC].on && b.sb_phi; }
 inline const float* batch_src(const vn_engine* h, const Batch& b) {
-  return !h->cfg.has_source ? nullptr : src_learnt(h, b) ? h->sl_mix : b.source;
+  return !h->cfg.has_source ? nullptr : src_learnt(h, b) ? lv_work(h, LV_SRC, SW_MIX) : b.source;
 }
 // (... and the mixed direction field_mix formed there in place of the batch's gcoef)
 inline bool fld_learnt(const vn_engine* h, const Batch& b) { return h->lv[LV_FLD].on && b.fb_G; }
-inline const float* batch_gcoef(const vn_engine* h, const Batch& b) { return fld_learnt(h, b) ? h->fl_mix : b.gcoef; }
+inline const float* batch_gcoef(const vn_engine* h, const Batch& b) { return fld_learnt(h, b) ? lv_work(h, LV_FLD, FW_MIX) : b.gcoef; }
 inline const float* fe_w(const vn_engine* h) { return (h->cfg.has_integw && h->has_feW) ? h->feW : nullptr; }
 
 inline bool on_8wave(const vn_engine* h) { return h->route == Route::fused8 || h->route == Route::twopass; }
@@ -574,7 +588,7 @@ VnDedupArgs dedup_args(const vn_engine* h, const Batch& b) {
   a.upack = h->dd_uv; a.uid = b.uid; a.rowptr = b.rowptr; a.rowidx = b.rowidx;
   // (learnt field amplitudes: gcoef moves every step, so no periodic table, and the CSR copy is the one field_mix rebuilt)
   const bool fld = fld_learnt(h, b);
-  a.gcoef = batch_gcoef(h, b); a.gcoef_csr = fld ? h->fl_csr : b.gcsr; a.source = batch_src(h, b);
+  a.gcoef = batch_gcoef(h, b); a.gcoef_csr = fld ? lv_work(h, LV_FLD, FW_CSR) : b.gcsr; a.source = batch_src(h, b);
   a.feN = h->feN; a.fedNt = h->fedNt; a.feW = fe_w(h);
   a.detJv = b.detJv; a.detJ = (float)b.detJ; a.n_k = b.n_k; a.U = b.U; a.q = h->cfg.integ_num; a.dim = h->cfg.dim;
   a.time_dependent = h->cfg.time_dependent; a.w2 = (float)h->w[2]; a.gper = b.gper && !fld ? 1 : 0;
@@ -650,10 +664,11 @@ int terms_seed_rows(vn_engine* h, const Batch& b) {
   if (b.nldiff.on) HIPCHK(vn_nldiff_seed_launch(term_row_args(h, b, b.nldiff), h->stream));
   if (fld_learnt(h, b)) {                          // field identification: the amplitude sums read udbar as D(u) left it, and the
     const long nT = b.n_k * h->cfg.integ_num;      // second tangent grad u_r of a point pass over the batch's own rows
-    if (int rc = ensure(&h->fl_pack, &h->fl_pack_cap, 4 * nT)) return rc;
-    HIPCHK(point_pass(h, b.Input, nT, nullptr, nullptr, h->fl_pack));
+    if (int rc = lv_ensure(h, LV_FLD, FW_PACK, 4 * nT)) return rc;
+    float* pack = lv_work(h, LV_FLD, FW_PACK);
+    HIPCHK(point_pass(h, b.Input, nT, nullptr, nullptr, pack));
     VnFldGradArgs g{};
-    g.udbar = h->udbar; g.pack = h->fl_pack; g.G = b.fb_G; g.J = b.fb_J; g.dim = h->cfg.dim;
+    g.udbar = h->udbar; g.pack = pack; g.G = b.fb_G; g.J = b.fb_J; g.dim = h->cfg.dim;
     g.nT = nT; g.q = h->cfg.integ_num; g.mask = h->lv[LV_FLD].mask; g.part = h->lv[LV_FLD].part;
     HIPCHK(vn_fldgrad_rows_launch(g, &h->lv[LV_FLD].blocks, h->stream));
   }
@@ -698,9 +713,10 @@ int terms_source_dedup(vn_engine* h, const Batch& b, VnDedupArgs& d) {
 // unscaled seed_g)
 int terms_gather_dedup(vn_engine* h, const Batch& b, const VnDedupArgs& d) {
   if (h->lv[LV_COEF].on && has_terms(b)) {   // inverse mode: each kernel also stores its per-point sum for vn_coefgrad_points_kernel
-    if (int rc = ensure(&h->cl_acc, &h->cl_acc_cap, 3 * b.U)) return rc;
+    if (int rc = lv_ensure(h, LV_COEF, CW_ACC, 3 * b.U)) return rc;
+    float* acc = lv_work(h, LV_COEF, CW_ACC);
     VnTermDedupArgs r = term_dedup_args(h, b, b.react, d), f = term_dedup_args(h, b, b.nlflux, d), n = nldiff_dedup_args(h, b, d);
-    r.acc_out = h->cl_acc; f.acc_out = h->cl_acc + b.U; n.acc_out = h->cl_acc + 2 * b.U;
+    r.acc_out = acc; f.acc_out = acc + b.U; n.acc_out = acc + 2 * b.U;
     if (b.react.on) HIPCHK(vn_react_gather_launch(r, h->stream));
     if (b.nlflux.on) HIPCHK(vn_nlflux_gather_launch(f, h->stream));
     if (b.nldiff.on) HIPCHK(vn_nldiff_point_launch(n, h->stream));
@@ -799,8 +815,8 @@ int bic_forward_reduce(vn_engine* h, const Batch& b) {
 // fluxbc_mix formed at the start of the evaluation; else the caller's arrays.  The two read sites (flux_seed, vn_objective_f64)
 // take their coefficient and label from here.
 inline bool fbc_learnt(const vn_engine* h) { return h->lv[LV_FBC].on && h->fbcS; }
-inline const float* flux_coef(const vn_engine* h) { return fbc_learnt(h) && h->fbcJc > 0 ? h->fb_coef : h->fcoef; }
-inline const float* flux_label(const vn_engine* h) { return fbc_learnt(h) && h->fbcJl > 0 ? h->fb_label : h->flabel; }
+inline const float* flux_coef(const vn_engine* h) { return fbc_learnt(h) && h->fbcJc > 0 ? lv_work(h, LV_FBC, XW_COEF) : h->fcoef; }
+inline const float* flux_label(const vn_engine* h) { return fbc_learnt(h) && h->fbcJl > 0 ? lv_work(h, LV_FBC, XW_LABEL) : h->flabel; }
 
 // ... first thing in an evaluation: the basis must be the engine's, then the label and the coefficient are formed, one mix per
 // part that has streams (vn_learnt.hip)
@@ -811,18 +827,10 @@ int fluxbc_mix(vn_engine* h) {
   if (h->fbcJl + h->fbcJc != v.J)
     return fail(VN_EINVAL, "the flux rows have a basis of %d + %d streams, the learnt amplitudes (vn_set_fluxbc_learn) are %d", h->fbcJl,
                 h->fbcJc, v.J);
-  VnMixArgs a{};
-  a.n = nF;
-  if (h->fbcJl > 0) {
-    if (int rc = ensure(&h->fb_label, &h->fb_label_cap, nF)) return rc;
-    a.base = h->flabel; a.stream = h->fbcS; a.amp = v.state; a.J = h->fbcJl; a.out = h->fb_label;
-    HIPCHK(vn_learnt_mix_launch(a, h->stream));
-  }
-  if (h->fbcJc > 0) {
-    if (int rc = ensure(&h->fb_coef, &h->fb_coef_cap, nF)) return rc;
-    a.base = h->fcoef; a.stream = h->fbcS + (long)h->fbcJl * nF; a.amp = v.state + h->fbcJl; a.J = h->fbcJc; a.out = h->fb_coef;
-    HIPCHK(vn_learnt_mix_launch(a, h->stream));
-  }
+  if (h->fbcJl > 0)
+    if (int rc = learnt_mix(h, LV_FBC, XW_LABEL, h->flabel, h->fbcS, 0, h->fbcJl, nF)) return rc;
+  if (h->fbcJc > 0)
+    if (int rc = learnt_mix(h, LV_FBC, XW_COEF, h->fcoef, h->fbcS + (long)h->fbcJl * nF, h->fbcJl, h->fbcJc, nF)) return rc;
   return VN_OK;
 }
 
@@ -1188,12 +1196,8 @@ void learnt_free(vn_engine* h, int id) {
   Learnt& v = h->lv[id];
   for (void* p : {(void*)v.state, (void*)v.bounds, (void*)v.grad, (void*)v.part})
     if (p) (void)hipFree(p);
-  auto drop = [](float*& p, long& cap) { if (p) (void)hipFree(p); p = nullptr; cap = 0; };
-  if (id == LV_COEF) drop(h->cl_acc, h->cl_acc_cap);
-  if (id == LV_SRC) drop(h->sl_mix, h->sl_mix_cap);
-  if (id == LV_FLD) { drop(h->fl_mix, h->fl_mix_cap); drop(h->fl_csr, h->fl_csr_cap); drop(h->fl_pack, h->fl_pack_cap); }
-  if (id == LV_BIC) drop(h->bl_mix, h->bl_mix_cap);
-  if (id == LV_FBC) { drop(h->fb_label, h->fb_label_cap); drop(h->fb_coef, h->fb_coef_cap); }
+  for (const Learnt::Work& w : v.work)
+    if (w.p) (void)hipFree(w.p);
   v = Learnt{};
 }
 
@@ -1223,13 +1227,7 @@ int source_mix(vn_engine* h, const Batch& b, int batch) {
   if (h->route == Route::fused4 && !b.Xu)
     return fail(VN_EUNSUPPORTED, "learnt source amplitudes are not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its "
                                  "single launch leaves no row seeds to reduce; every other kernel family carries them");
-  const long nT = b.n_k * h->cfg.integ_num;
-  if (nT <= 0) return VN_OK;
-  if (int rc = ensure(&h->sl_mix, &h->sl_mix_cap, nT)) return rc;
-  VnMixArgs a{};
-  a.base = b.source; a.stream = b.sb_phi; a.amp = h->lv[LV_SRC].state; a.J = b.sb_J; a.n = nT; a.out = h->sl_mix;
-  HIPCHK(vn_learnt_mix_launch(a, h->stream));
-  return VN_OK;
+  return learnt_mix(h, LV_SRC, SW_MIX, b.source, b.sb_phi, 0, b.sb_J, b.n_k * h->cfg.integ_num);
 }
 
 // Field identification, first thing in an evaluation of batch b (the routes without a point pass for the rows' grad u were refused by
@@ -1240,14 +1238,11 @@ int field_mix(vn_engine* h, const Batch& b, int batch) {
   if (b.fb_J != h->lv[LV_FLD].J)
     return fail(VN_EINVAL, "batch %d has a field basis of %d streams, the learnt amplitudes (vn_set_field_learn) are %d", batch, b.fb_J, h->lv[LV_FLD].J);
   const long n = b.n_k * h->cfg.integ_num * h->cfg.dim;
-  if (n <= 0) return VN_OK;
-  if (int rc = ensure(&h->fl_mix, &h->fl_mix_cap, n)) return rc;
-  VnMixArgs a{};
-  a.base = b.gcoef; a.stream = b.fb_G; a.amp = h->lv[LV_FLD].state; a.J = b.fb_J; a.n = n; a.out = h->fl_mix;
-  HIPCHK(vn_learnt_mix_launch(a, h->stream));
-  if (b.Xu) {
-    if (int rc = ensure(&h->fl_csr, &h->fl_csr_cap, n)) return rc;
-    HIPCHK(vn_dedup_permute_launch(h->fl_mix, b.rowidx, h->fl_csr, b.n_k * h->cfg.integ_num, h->cfg.dim, h->stream));
+  if (int rc = learnt_mix(h, LV_FLD, FW_MIX, b.gcoef, b.fb_G, 0, b.fb_J, n)) return rc;
+  if (n > 0 && b.Xu) {
+    if (int rc = lv_ensure(h, LV_FLD, FW_CSR, n)) return rc;
+    HIPCHK(vn_dedup_permute_launch(lv_work(h, LV_FLD, FW_MIX), b.rowidx, lv_work(h, LV_FLD, FW_CSR), b.n_k * h->cfg.integ_num, h->cfg.dim,
+                                   h->stream));
   }
   return VN_OK;
 }
@@ -1259,12 +1254,7 @@ int bic_mix(vn_engine* h, const Batch& b, int batch) {
   if (bic_basis_J(h, b) != h->lv[LV_BIC].J)
     return fail(VN_EINVAL, "the BC/IC rows of batch %d have a basis of %d streams, the learnt amplitudes (vn_set_bic_learn) are %d", batch,
                 bic_basis_J(h, b), h->lv[LV_BIC].J);
-  if (h->nBreg <= 0) return VN_OK;
-  if (int rc = ensure(&h->bl_mix, &h->bl_mix_cap, h->nBreg)) return rc;
-  VnMixArgs a{};
-  a.base = bi_y0(h, b); a.stream = bic_basis(h, b); a.amp = h->lv[LV_BIC].state; a.J = h->lv[LV_BIC].J; a.n = h->nBreg; a.out = h->bl_mix;
-  HIPCHK(vn_learnt_mix_launch(a, h->stream));
-  return VN_OK;
+  return learnt_mix(h, LV_BIC, BW_MIX, bi_y0(h, b), bic_basis(h, b), 0, h->lv[LV_BIC].J, h->nBreg);
 }
 
 // ---- RCCL, loaded at run time -------------------------------------------------------------

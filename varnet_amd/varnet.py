@@ -877,9 +877,9 @@ class VarNet:
                   'learnField': (learnField, fieldLr, fieldBounds), 'learnBic': (learnBic, bicLr, bicBounds),
                   'learnFluxBC': (learnFluxBC, fluxBCLr, fluxBCBounds)}
         # fluxBasis / robinBasis (ADPDE) live on the flux rows: without fluxBC=True nothing would ever evaluate them
-        if sum(self._fbc_sizes(PDE)) > 0 and not fluxBC:
+        if sum(self._keyed_sizes(self._FBC, PDE)) > 0 and not fluxBC:
             raise ValueError('the PDE carries a fluxBasis / robinBasis, which is data of the boundary-flux rows: it needs fluxBC=True')
-        for lv in self.LEARNT_ALL:
+        for lv in self.LEARNT:
             if learnt[lv.option][0] is not None and MORvar is not None:
                 raise NotImplementedError('%s with model-order reduction is not supported: neither %s nor the observations it needs '
                                           'are' % (lv.option, lv.mor_lacks))
@@ -900,7 +900,7 @@ class VarNet:
         # initial bases are learnt next to the network from the observations (`coefLearnData`, `sourceLearnData`, `fieldLearnData`,
         # `bicLearnData`); learnFluxBC=...: flux boundary identification, likewise the masked amplitudes of its flux-datum and
         # Robin-coefficient bases (`fluxBCLearnData`)
-        for lv in self.LEARNT_ALL:
+        for lv in self.LEARNT:
             data = getattr(self, lv.parser)(PDE, *learnt[lv.option], learning_rate)
             setattr(self, lv.attr, data)
             if data is None:
@@ -958,7 +958,7 @@ class VarNet:
             raise NotImplementedError('causal=%r with towers: a rank\'s slab means would cover only its shard of the test '
                                       'functions, so the ranks together would train another objective than one rank'
                                       % (causal,))
-        for lv in self.LEARNT_ALL:
+        for lv in self.LEARNT:
             if getattr(self, lv.attr) is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
                 raise NotImplementedError('%s with towers: %s are not part of the all-reduced buffer, so every rank would follow its '
                                           'own shard' % (lv.option, lv.grads))
@@ -1031,26 +1031,13 @@ class VarNet:
             r = self.obsRows
             self.engine.set_observations(r['X'], r['value'], q=r['q'], dir=r['dir'], rowptr=r['rowptr'], wgt=r['wgt'],
                                          weight=self.obsWeight / self.world)
-        if self.coefLearn is not None:
-            # the engine owns the nine coefficients from here on: every batch registered later reads them from its device vector
-            cl = self.coefLearn
-            self.engine.set_coef_learn(cl['mask'], cl['init'], cl['lo'], cl['hi'], cl['lr'])
-        if self.srcLearn is not None:
-            # the engine owns the amplitudes from here on: every batch registered later carries its basis streams
-            sl = self.srcLearn
-            self.engine.set_source_learn(sl['mask'], sl['init'], sl['lo'], sl['hi'], sl['lr'])
-        if self.fldLearn is not None:
-            # likewise the field amplitudes: every batch registered later carries its [J, nT, dim] basis streams
-            fl = self.fldLearn
-            self.engine.set_field_learn(fl['mask'], fl['init'], fl['lo'], fl['hi'], fl['lr'])
-        if self.bicLearn is not None:
-            # likewise the boundary and initial amplitudes: every BC/IC row set registered later carries its [J, nB] basis streams
-            bl = self.bicLearn
-            self.engine.set_bic_learn(bl['mask'], bl['init'], bl['lo'], bl['hi'], bl['lr'])
-        if self.fbcLearn is not None:
-            # likewise the flux and Robin amplitudes, whose [J, nF] basis streams were registered with the flux rows above
-            fb = self.fbcLearn
-            self.engine.set_fluxbc_learn(fb['mask'], fb['init'], fb['lo'], fb['hi'], fb['lr'])
+        for lv in self.LEARNT:
+            # the engine owns a learnt vector from here on: every batch registered later reads the nine coefficients from its device
+            # vector, and carries the basis streams of the source [J, nT], the field [J, nT, dim] and the BC/IC rows [J, nB]; those of
+            # the flux and Robin amplitudes [J, nF] were registered with the flux rows above
+            d = getattr(self, lv.attr)
+            if d is not None:
+                getattr(self.engine, 'set_%s_learn' % lv.kind)(d['mask'], d['init'], d['lo'], d['hi'], d['lr'])
         self.tfData = self.engine       # name kept for scripts that poke at `VarNet.tfData`
         from .launch import mark_stage
         mark_stage('engine_ready')      # past the launcher's bootstrap deadline: a rank that trains for hours is healthy
@@ -1103,25 +1090,31 @@ class VarNet:
 
     # -- the vectors learnt next to the network, in the engine's order: the option, its parser, the attribute that keeps the parsed
     # registration, the noun of an entry, what model-order reduction lacks for it, what towers lack, the checkpoint key, the stem
-    # of the engine's get_* / set_* methods, and the title of train()'s closing line
-    LearntVector = collections.namedtuple('LearntVector', 'option parser attr noun mor_lacks grads key engine title')
+    # of the engine's get_* / set_* methods, the title of train()'s closing line, the kind in the engine's set_<kind>_learn, and for
+    # a vector made of two keyed parts its KeyedVector (else None)
+    LearntVector = collections.namedtuple('LearntVector', 'option parser attr noun mor_lacks grads key engine title kind keyed')
+    # a vector of two parts, each the amplitudes of one basis of the PDE, which keeps part `key` as <key>Basis / <key>Amp: the stem
+    # of its options (<stem>Lr, <stem>Bounds) and methods (<stem>Amplitudes, <stem>Grad, set<Stem>Amplitudes), the two keys in the
+    # vector's order, the names of the two sizes in the parsed registration, and how messages call its bases and its amplitudes
+    KeyedVector = collections.namedtuple('KeyedVector', 'stem keys sizes bases amps')
     LEARNT = (
         LearntVector('learnCoef', 'coefLearnData', 'coefLearn', 'coefficient', 'the three polynomial terms',
-                     'the nine coefficient gradients', 'pde_coefficients', 'coefs', 'Learnt coefficients'),
+                     'the nine coefficient gradients', 'pde_coefficients', 'coefs', 'Learnt coefficients', 'coef', None),
         LearntVector('learnSource', 'sourceLearnData', 'srcLearn', 'amplitude', 'the source basis',
-                     'the amplitude gradients', 'source_amplitudes', 'source_amps', 'Learnt source amplitudes'),
+                     'the amplitude gradients', 'source_amplitudes', 'source_amps', 'Learnt source amplitudes', 'source', None),
         LearntVector('learnField', 'fieldLearnData', 'fldLearn', 'amplitude', 'the field bases',
-                     'the amplitude gradients', 'field_amplitudes', 'field_amps', 'Learnt field amplitudes (diff, then vel)'),
+                     'the amplitude gradients', 'field_amplitudes', 'field_amps', 'Learnt field amplitudes (diff, then vel)', 'field',
+                     KeyedVector('field', ('diff', 'vel'), ('Jk', 'Jv'), 'field', 'field amplitudes')),
         LearntVector('learnBic', 'bicLearnData', 'bicLearn', 'amplitude', 'the boundary and initial bases',
-                     'the amplitude gradients', 'bic_amplitudes', 'bic_amps', 'Learnt boundary and initial amplitudes (bc, then ic)'))
-    # ... and the vectors whose rows are an edge row set's, not a batch's or the BC/IC set's: same record, same handling.  LEARNT keeps
-    # its four rows (tests/test_bic_host.py reads it as the list of those four); every loop runs over LEARNT_ALL.
-    LEARNT_EDGE = (
+                     'the amplitude gradients', 'bic_amplitudes', 'bic_amps', 'Learnt boundary and initial amplitudes (bc, then ic)', 'bic',
+                     KeyedVector('bic', ('bc', 'ic'), ('Jb', 'Ji'), 'Dirichlet or initial', 'boundary or initial amplitudes')),
+        # (its rows are an edge row set's, not a batch's or the BC/IC set's)
         LearntVector('learnFluxBC', 'fluxBCLearnData', 'fbcLearn', 'amplitude', 'the boundary-flux rows',
-                     'the amplitude gradients', 'fluxbc_amplitudes', 'fluxbc_amps', 'Learnt flux and Robin amplitudes (flux, then robin)'),)
-    LEARNT_ALL = LEARNT + LEARNT_EDGE
+                     'the amplitude gradients', 'fluxbc_amplitudes', 'fluxbc_amps', 'Learnt flux and Robin amplitudes (flux, then robin)',
+                     'fluxbc', KeyedVector('fluxBC', ('flux', 'robin'), ('Jl', 'Jc'), 'flux or Robin', 'flux or Robin amplitudes')))
+    _FIELD, _BIC, _FBC = LEARNT[2:]
 
-    # -- what the three learnt vectors' options share (coefLearnData, sourceLearnData, fieldLearnData) --
+    # -- what the learnt vectors' options share (coefLearnData, sourceLearnData and the keyed vectors') --
     @staticmethod
     def _learn_mask(sel, n, err):
         """A mask selection: True (all n entries) or a list of n 0/1/bool values; anything else raises ValueError(err)."""
@@ -1324,59 +1317,128 @@ class VarNet:
             raise ValueError('setSourceAmplitudes takes %d finite numbers, got %r' % (J, a))
         self.engine.set_source_amps(v)
 
-    # -- field identification: learnt amplitudes of a diffusivity and a velocity basis (extension) -----
-    FIELD_KEYS = ('diff', 'vel')
+    # -- the vectors of two keyed parts (field, boundary data and flux boundary identification): one path, taking the LEARNT row --
+    @staticmethod
+    def _keyed_sizes(lv, PDE):
+        """The number of functions of the PDE's two bases of the keyed vector `lv` (0 without one)."""
+        return tuple(len(getattr(PDE, key + 'Basis', None) or []) for key in lv.keyed.keys)
 
     @staticmethod
-    def _field_sizes(PDE):
-        """(J_kappa, J_v): the number of functions of the PDE's diffusivity and velocity bases (0 without one)."""
-        return len(getattr(PDE, 'diffBasis', None) or []), len(getattr(PDE, 'velBasis', None) or [])
-
-    @staticmethod
-    def fieldLearnData(PDE, learnField, fieldLr=None, fieldBounds=None, learning_rate=0.001):
-        """(No reference counterpart: `VarNet(..., learnField=...)`.)  The registration of `vn_set_field_learn`, or None without
-        learnField: mask, init, lo, hi (J = J_kappa + J_v entries each, the diffusivity streams first) and lr.  learnField =
-        {'diff': True | mask, 'vel': True | mask} (a key left out: none of that basis is learnt); the PDE's diffAmp / velAmp are the
-        initial guess; fieldLr defaults to the network's learning rate; fieldBounds = {'diff': ..., 'vel': ...}, each (lo, hi) for
-        every learnt amplitude of that basis or a list with one entry per function, each None or (lo, hi), None for an open side."""
-        if learnField is None or learnField is False:
-            if fieldLr is not None:
-                raise ValueError('fieldLr=%r is an option of learnField=...' % (fieldLr,))
-            if fieldBounds is not None:
-                raise ValueError('fieldBounds is an option of learnField=...')
+    def _keyed_learn_data(lv, PDE, learn, lr, bounds, learning_rate):
+        """The registration of the keyed vector `lv`, or None without its option: what fieldLearnData, bicLearnData and
+        fluxBCLearnData return."""
+        kv, option = lv.keyed, lv.option
+        lrName, bName = kv.stem + 'Lr', kv.stem + 'Bounds'
+        if learn is None or learn is False:
+            if lr is not None:
+                raise ValueError('%s=%r is an option of %s=...' % (lrName, lr, option))
+            if bounds is not None:
+                raise ValueError('%s is an option of %s=...' % (bName, option))
             return None
-        keys = VarNet.FIELD_KEYS
-        if not isinstance(learnField, dict) or not learnField or any(k not in keys for k in learnField):
-            raise ValueError('learnField must be a dict {\'diff\': True | mask, \'vel\': True | mask}, got %r' % (learnField,))
-        if fieldBounds is not None and (not isinstance(fieldBounds, dict) or any(k not in keys for k in fieldBounds)):
-            raise ValueError('fieldBounds must be a dict {\'diff\': ..., \'vel\': ...}, got %r' % (fieldBounds,))
-        Jk, Jv = VarNet._field_sizes(PDE)
+        keys = kv.keys
+        if not isinstance(learn, dict) or not learn or any(k not in keys for k in learn):
+            raise ValueError('%s must be a dict {%r: True | mask, %r: True | mask}, got %r' % (option, keys[0], keys[1], learn))
+        if bounds is not None and (not isinstance(bounds, dict) or any(k not in keys for k in bounds)):
+            raise ValueError('%s must be a dict {%r: ..., %r: ...}, got %r' % (bName, keys[0], keys[1], bounds))
+        Js = VarNet._keyed_sizes(lv, PDE)
         masks, a0s, los, his = [], [], [], []
-        for key, J, amp in (('diff', Jk, 'diffAmp'), ('vel', Jv, 'velAmp')):
-            sel = learnField.get(key)
+        for key, J in zip(keys, Js):
+            sel = learn.get(key)
             if sel is not None and sel is not False and J == 0:
-                raise ValueError('learnField[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (key, key, key))
+                raise ValueError('%s[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (option, key, key, key))
             if J == 0:
-                if fieldBounds is not None and fieldBounds.get(key) is not None:
-                    raise ValueError('fieldBounds[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (key, key, key))
+                if bounds is not None and bounds.get(key) is not None:
+                    raise ValueError('%s[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (bName, key, key, key))
                 continue
             if sel is None or sel is False:
                 mask = np.zeros(J, dtype=bool)
             else:
-                mask = VarNet._learn_mask(sel, J, 'learnField[%r] must be True or a mask of %d booleans (one per function of %sBasis), '
-                                          'got %r' % (key, J, key, sel))
-            a0 = np.asarray(getattr(PDE, amp), dtype=np.float64)
-            bounds = None if fieldBounds is None else fieldBounds.get(key)
-            lo, hi = VarNet._learn_bounds(bounds, 'fieldBounds[%r]' % (key,), mask, a0, 'an amplitude', 'learnField',
-                                          'fieldBounds[%r] must be (lo, hi) or a list of %d entries, each None or (lo, hi), got %r'
-                                          % (key, J, bounds))
+                mask = VarNet._learn_mask(sel, J, '%s[%r] must be True or a mask of %d booleans (one per function of %sBasis), '
+                                          'got %r' % (option, key, J, key, sel))
+            a0 = np.asarray(getattr(PDE, key + 'Amp'), dtype=np.float64)
+            bd = None if bounds is None else bounds.get(key)
+            lo, hi = VarNet._learn_bounds(bd, '%s[%r]' % (bName, key), mask, a0, 'an amplitude', option,
+                                          '%s[%r] must be (lo, hi) or a list of %d entries, each None or (lo, hi), got %r'
+                                          % (bName, key, J, bd))
             masks.append(mask); a0s.append(a0); los.append(lo); his.append(hi)
-        mask = np.concatenate(masks)
-        if not mask.any():
-            raise ValueError('learnField selects no amplitude')
-        lr = VarNet._learn_rate(fieldLr, 'fieldLr', learning_rate)
-        return dict(mask=[int(x) for x in mask], init=np.concatenate(a0s), lo=np.concatenate(los), hi=np.concatenate(his),
-                    lr=lr, Jk=Jk, Jv=Jv)
+        if not any(m.any() for m in masks):
+            raise ValueError('%s selects no amplitude' % option)
+        lr = VarNet._learn_rate(lr, lrName, learning_rate)
+        return dict(mask=[int(x) for x in np.concatenate(masks)], init=np.concatenate(a0s), lo=np.concatenate(los),
+                    hi=np.concatenate(his), lr=lr, **dict(zip(kv.sizes, Js)))
+
+    def _keyed_vector(self, lv):
+        """The amplitudes of the keyed vector `lv` as one vector, first key first: the engine's if learnt, else the PDE's."""
+        if getattr(self, lv.attr, None) is not None and getattr(self, 'engine', None) is not None:
+            return np.asarray(getattr(self.engine, 'get_' + lv.engine)(J=sum(self._keyed_sizes(lv, self.PDE))), dtype=np.float64)
+        return np.concatenate([np.asarray(getattr(self.PDE, key + 'Amp', []), dtype=np.float64) for key in lv.keyed.keys])
+
+    def _keyed_dict(self, lv, v):
+        """The vector v of `lv` as {key: its part}."""
+        (k0, k1), J0 = lv.keyed.keys, self._keyed_sizes(lv, self.PDE)[0]
+        return {k0: v[:J0].copy(), k1: v[J0:].copy()}
+
+    def _keyed_amplitudes(self, lv):
+        kv = lv.keyed
+        if sum(self._keyed_sizes(lv, self.PDE)) == 0:
+            raise ValueError('%sAmplitudes: the PDE has no %s basis (ADPDE(..., %sBasis=[...], %sBasis=[...]))'
+                             % (kv.stem, kv.bases, *kv.keys))
+        return self._keyed_dict(lv, self._keyed_vector(lv))
+
+    def _keyed_grad(self, lv):
+        if getattr(self, lv.attr) is None:
+            raise ValueError('%sGrad: this instance learns no %s (%s=...)' % (lv.keyed.stem, lv.keyed.amps, lv.option))
+        J = sum(self._keyed_sizes(lv, self.PDE))
+        return self._keyed_dict(lv, np.asarray(getattr(self.engine, 'get_' + lv.engine)(grad=True, J=J)[1], dtype=np.float64))
+
+    def _keyed_set(self, lv, amps):
+        kv = lv.keyed
+        name = 'set%s%sAmplitudes' % (kv.stem[0].upper(), kv.stem[1:])
+        if getattr(self, lv.attr) is None:
+            raise ValueError('%s: this instance learns no %s (%s=...)' % (name, kv.amps, lv.option))
+        if not isinstance(amps, dict) or not amps or any(k not in kv.keys for k in amps):
+            raise ValueError('%s takes a dict {%r: [...], %r: [...]}, got %r' % (name, *kv.keys, amps))
+        cur, i0 = self._keyed_vector(lv), 0
+        for key, J in zip(kv.keys, self._keyed_sizes(lv, self.PDE)):
+            i0 += J
+            if key not in amps:
+                continue
+            try:
+                v = np.asarray(amps[key], dtype=np.float64).reshape(-1)
+            except (TypeError, ValueError):
+                v = np.empty(0)
+            if J == 0 or v.size != J or not np.all(np.isfinite(v)):
+                raise ValueError('%s[%r] takes %d finite numbers, got %r' % (name, key, J, amps[key]))
+            cur[i0 - J:i0] = v
+        getattr(self.engine, 'set_' + lv.engine)(cur)
+
+    def _edge_basis(self, X, span, names):
+        """The (bInd, f) entries of the PDE's bases `names`, in that order, at the rows X: [J, n] in fp64, every function
+        evaluated like the `g` of a boundary condition on the rows span[bInd] = (first, end) of its own indicator and zero
+        elsewhere; a wrong shape names the entry."""
+        dim, PDE = self.dim, self.PDE
+        entries = [(name, j, e) for name in names for j, e in enumerate(getattr(PDE, name, None) or [])]
+        S = np.zeros((len(entries), X.shape[0]), dtype=np.float64)
+        for row, (name, j, (bInd, f)) in enumerate(entries):
+            r0, r1 = span[bInd]
+            x = X[r0:r1]
+            targ = [x[:, dim:dim + 1]] if PDE.timeDependent else []
+            v = np.asarray(f(x[:, :dim], *targ), dtype=np.float64)
+            if v.size != r1 - r0:
+                raise ValueError('%s[%d] must return one value per point (a column), got shape %s for %d points'
+                                 % (name, j, v.shape, r1 - r0))
+            S[row, r0:r1] = v.reshape(-1)
+        return S
+
+    # -- field identification: learnt amplitudes of a diffusivity and a velocity basis (extension) -----
+    @staticmethod
+    def fieldLearnData(PDE, learnField, fieldLr=None, fieldBounds=None, learning_rate=0.001):
+        """(No reference counterpart: `VarNet(..., learnField=...)`.)  The registration of `vn_set_field_learn`, or None without
+        learnField: mask, init, lo, hi (J = J_kappa + J_v entries each, the diffusivity streams first), lr, Jk and Jv.  learnField =
+        {'diff': True | mask, 'vel': True | mask} (a key left out: none of that basis is learnt); the PDE's diffAmp / velAmp are the
+        initial guess; fieldLr defaults to the network's learning rate; fieldBounds = {'diff': ..., 'vel': ...}, each (lo, hi) for
+        every learnt amplitude of that basis or a list with one entry per function, each None or (lo, hi), None for an open side."""
+        return VarNet._keyed_learn_data(VarNet._FIELD, PDE, learnField, fieldLr, fieldBounds, learning_rate)
 
     def _field_basis(self, Input, grad=False):
         """(chi [Jk, n, 1], grad chi [Jk, n, dim] or None without `grad`, omega [Jv, n, dim]) of the PDE's field bases at the rows
@@ -1389,130 +1451,44 @@ class VarNet:
                 val(getattr(PDE, 'd_diffBasis', None) or [], 'd_diffBasis', dim, X, targ) if grad else None,
                 val(getattr(PDE, 'velBasis', None) or [], 'velBasis', dim, X, targ))
 
-    def _field_vector(self):
-        """The J = J_kappa + J_v amplitudes as one vector: the engine's with learnField, else the PDE's."""
-        Jk, Jv = self._field_sizes(self.PDE)
-        if getattr(self, 'fldLearn', None) is not None and getattr(self, 'engine', None) is not None:
-            return np.asarray(self.engine.get_field_amps(J=Jk + Jv), dtype=np.float64)
-        return np.concatenate([np.asarray(getattr(self.PDE, 'diffAmp', []), dtype=np.float64),
-                               np.asarray(getattr(self.PDE, 'velAmp', []), dtype=np.float64)])
-
     def fieldAmplitudes(self):
         """{'diff': J_kappa amplitudes, 'vel': J_v amplitudes} of the PDE's field bases at the current state: the learnt values
         with learnField, else the PDE's."""
-        Jk, Jv = self._field_sizes(self.PDE)
-        if Jk + Jv == 0:
-            raise ValueError('fieldAmplitudes: the PDE has no field basis (ADPDE(..., diffBasis=[...], velBasis=[...]))')
-        v = self._field_vector()
-        return {'diff': v[:Jk].copy(), 'vel': v[Jk:].copy()}
+        return self._keyed_amplitudes(self._FIELD)
 
     def fieldGrad(self):
         """d loss / d amplitude of the last gradient evaluation as {'diff': ..., 'vel': ...} (zeros where not learnt)."""
-        if self.fldLearn is None:
-            raise ValueError('fieldGrad: this instance learns no field amplitudes (learnField=...)')
-        Jk, Jv = self._field_sizes(self.PDE)
-        g = np.asarray(self.engine.get_field_amps(grad=True, J=Jk + Jv)[1], dtype=np.float64)
-        return {'diff': g[:Jk].copy(), 'vel': g[Jk:].copy()}
+        return self._keyed_grad(self._FIELD)
 
     def setFieldAmplitudes(self, amps):
         """Overwrite amplitudes between train() calls: {'diff': [...], 'vel': [...]} (a key left out keeps its values).  Not
         clamped to fieldBounds (the next update is)."""
-        if self.fldLearn is None:
-            raise ValueError('setFieldAmplitudes: this instance learns no field amplitudes (learnField=...)')
-        if not isinstance(amps, dict) or not amps or any(k not in self.FIELD_KEYS for k in amps):
-            raise ValueError('setFieldAmplitudes takes a dict {\'diff\': [...], \'vel\': [...]}, got %r' % (amps,))
-        Jk, Jv = self._field_sizes(self.PDE)
-        cur = self._field_vector()
-        for key, sl, J in (('diff', slice(0, Jk), Jk), ('vel', slice(Jk, Jk + Jv), Jv)):
-            if key not in amps:
-                continue
-            try:
-                v = np.asarray(amps[key], dtype=np.float64).reshape(-1)
-            except (TypeError, ValueError):
-                v = np.empty(0)
-            if J == 0 or v.size != J or not np.all(np.isfinite(v)):
-                raise ValueError('setFieldAmplitudes[%r] takes %d finite numbers, got %r' % (key, J, amps[key]))
-            cur[sl] = v
-        self.engine.set_field_amps(cur)
+        self._keyed_set(self._FIELD, amps)
 
     # -- boundary data identification: learnt amplitudes of a Dirichlet and an initial basis (extension) -----
-    BIC_KEYS = ('bc', 'ic')
-
-    @staticmethod
-    def _bic_sizes(PDE):
-        """(J_bc, J_ic): the number of functions of the PDE's Dirichlet and initial bases (0 without one)."""
-        return len(getattr(PDE, 'bcBasis', None) or []), len(getattr(PDE, 'icBasis', None) or [])
-
     @staticmethod
     def bicLearnData(PDE, learnBic, bicLr=None, bicBounds=None, learning_rate=0.001):
         """(No reference counterpart: `VarNet(..., learnBic=...)`.)  The registration of `vn_set_bic_learn`, or None without
-        learnBic: mask, init, lo, hi (J = J_bc + J_ic entries each, the Dirichlet streams first) and lr.  learnBic =
+        learnBic: mask, init, lo, hi (J = J_bc + J_ic entries each, the Dirichlet streams first), lr, Jb and Ji.  learnBic =
         {'bc': True | mask, 'ic': True | mask} (a key left out: none of that basis is learnt); the PDE's bcAmp / icAmp are the
         initial guess; bicLr defaults to the network's learning rate; bicBounds = {'bc': ..., 'ic': ...}, each (lo, hi) for
         every learnt amplitude of that basis or a list with one entry per function, each None or (lo, hi), None for an open side."""
-        if learnBic is None or learnBic is False:
-            if bicLr is not None:
-                raise ValueError('bicLr=%r is an option of learnBic=...' % (bicLr,))
-            if bicBounds is not None:
-                raise ValueError('bicBounds is an option of learnBic=...')
-            return None
-        keys = VarNet.BIC_KEYS
-        if not isinstance(learnBic, dict) or not learnBic or any(k not in keys for k in learnBic):
-            raise ValueError('learnBic must be a dict {\'bc\': True | mask, \'ic\': True | mask}, got %r' % (learnBic,))
-        if bicBounds is not None and (not isinstance(bicBounds, dict) or any(k not in keys for k in bicBounds)):
-            raise ValueError('bicBounds must be a dict {\'bc\': ..., \'ic\': ...}, got %r' % (bicBounds,))
-        Jb, Ji = VarNet._bic_sizes(PDE)
-        masks, a0s, los, his = [], [], [], []
-        for key, J, amp in (('bc', Jb, 'bcAmp'), ('ic', Ji, 'icAmp')):
-            sel = learnBic.get(key)
-            if sel is not None and sel is not False and J == 0:
-                raise ValueError('learnBic[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (key, key, key))
-            if J == 0:
-                if bicBounds is not None and bicBounds.get(key) is not None:
-                    raise ValueError('bicBounds[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (key, key, key))
-                continue
-            if sel is None or sel is False:
-                mask = np.zeros(J, dtype=bool)
-            else:
-                mask = VarNet._learn_mask(sel, J, 'learnBic[%r] must be True or a mask of %d booleans (one per function of %sBasis), '
-                                          'got %r' % (key, J, key, sel))
-            a0 = np.asarray(getattr(PDE, amp), dtype=np.float64)
-            bounds = None if bicBounds is None else bicBounds.get(key)
-            lo, hi = VarNet._learn_bounds(bounds, 'bicBounds[%r]' % (key,), mask, a0, 'an amplitude', 'learnBic',
-                                          'bicBounds[%r] must be (lo, hi) or a list of %d entries, each None or (lo, hi), got %r'
-                                          % (key, J, bounds))
-            masks.append(mask); a0s.append(a0); los.append(lo); his.append(hi)
-        mask = np.concatenate(masks) if masks else np.zeros(0, dtype=bool)
-        if not mask.any():
-            raise ValueError('learnBic selects no amplitude')
-        lr = VarNet._learn_rate(bicLr, 'bicLr', learning_rate)
-        return dict(mask=[int(x) for x in mask], init=np.concatenate(a0s), lo=np.concatenate(los), hi=np.concatenate(his),
-                    lr=lr, Jb=Jb, Ji=Ji)
+        return VarNet._keyed_learn_data(VarNet._BIC, PDE, learnBic, bicLr, bicBounds, learning_rate)
 
     def _bic_basis(self, biInput, biDof):
         """The PDE's Dirichlet and initial basis functions at the BC/IC rows, [J_bc + J_ic, nB] in fp64 (the Dirichlet streams
         first): a gamma_j evaluated like `g` on the rows of its own indicator and zero elsewhere, an iota_j evaluated like `IC`
         on the initial rows and zero on the boundary rows."""
         dim, PDE = self.dim, self.PDE
-        td = PDE.timeDependent
         nB = biInput.shape[0]
-        Jb, Ji = self._bic_sizes(PDE)
+        span, indp = {}, 0
+        # the rows of each Dirichlet indicator, as biTrainData walks them (with time, biDof ends in the initial rows' count)
+        for bInd, n in zip([b for b in range(PDE.domain.bIndNum) if PDE.BCtype[b] == 'Dirichlet'], biDof):
+            span[bInd] = (indp, indp + n)
+            indp += n
+        Jb, Ji = self._keyed_sizes(self._BIC, PDE)
         B = np.zeros((Jb + Ji, nB), dtype=np.float64)
-        span, indp, j = {}, 0, 0
-        for bInd in range(PDE.domain.bIndNum):            # the rows of each Dirichlet indicator, as biTrainData walks them
-            if PDE.BCtype[bInd] != 'Dirichlet':
-                continue
-            span[bInd] = (indp, indp + biDof[j])
-            indp += biDof[j]
-            j += 1
-        for j, (bInd, f) in enumerate(getattr(PDE, 'bcBasis', None) or []):
-            i0, i1 = span[bInd]
-            targ = [biInput[i0:i1, dim][np.newaxis].T] if td else []
-            v = np.asarray(f(biInput[i0:i1, :dim], *targ), dtype=np.float64)
-            if v.size != i1 - i0:
-                raise ValueError('bcBasis[%d] must return one value per point (a column), got shape %s for %d points'
-                                 % (j, v.shape, i1 - i0))
-            B[j, i0:i1] = v.reshape(-1)
+        B[:Jb] = self._edge_basis(biInput, span, ('bcBasis',))
         for j, f in enumerate(getattr(PDE, 'icBasis', None) or []):
             v = np.asarray(f(biInput[indp:, :dim]), dtype=np.float64)
             if v.size != nB - indp:
@@ -1521,152 +1497,44 @@ class VarNet:
             B[Jb + j, indp:] = v.reshape(-1)
         return B
 
-    def _bic_vector(self):
-        """The J = J_bc + J_ic amplitudes as one vector: the engine's with learnBic, else the PDE's."""
-        Jb, Ji = self._bic_sizes(self.PDE)
-        if getattr(self, 'bicLearn', None) is not None and getattr(self, 'engine', None) is not None:
-            return np.asarray(self.engine.get_bic_amps(J=Jb + Ji), dtype=np.float64)
-        return np.concatenate([np.asarray(getattr(self.PDE, 'bcAmp', []), dtype=np.float64),
-                               np.asarray(getattr(self.PDE, 'icAmp', []), dtype=np.float64)])
-
     def bicAmplitudes(self):
         """{'bc': J_bc amplitudes, 'ic': J_ic amplitudes} of the PDE's Dirichlet and initial bases at the current state: the
         learnt values with learnBic, else the PDE's."""
-        Jb, Ji = self._bic_sizes(self.PDE)
-        if Jb + Ji == 0:
-            raise ValueError('bicAmplitudes: the PDE has no Dirichlet or initial basis (ADPDE(..., bcBasis=[...], icBasis=[...]))')
-        v = self._bic_vector()
-        return {'bc': v[:Jb].copy(), 'ic': v[Jb:].copy()}
+        return self._keyed_amplitudes(self._BIC)
 
     def bicGrad(self):
         """d loss / d amplitude of the last gradient evaluation as {'bc': ..., 'ic': ...} (zeros where not learnt)."""
-        if self.bicLearn is None:
-            raise ValueError('bicGrad: this instance learns no boundary or initial amplitudes (learnBic=...)')
-        Jb, Ji = self._bic_sizes(self.PDE)
-        g = np.asarray(self.engine.get_bic_amps(grad=True, J=Jb + Ji)[1], dtype=np.float64)
-        return {'bc': g[:Jb].copy(), 'ic': g[Jb:].copy()}
+        return self._keyed_grad(self._BIC)
 
     def setBicAmplitudes(self, amps):
         """Overwrite amplitudes between train() calls: {'bc': [...], 'ic': [...]} (a key left out keeps its values).  Not
         clamped to bicBounds (the next update is)."""
-        if self.bicLearn is None:
-            raise ValueError('setBicAmplitudes: this instance learns no boundary or initial amplitudes (learnBic=...)')
-        if not isinstance(amps, dict) or not amps or any(k not in self.BIC_KEYS for k in amps):
-            raise ValueError('setBicAmplitudes takes a dict {\'bc\': [...], \'ic\': [...]}, got %r' % (amps,))
-        Jb, Ji = self._bic_sizes(self.PDE)
-        cur = self._bic_vector()
-        for key, sl, J in (('bc', slice(0, Jb), Jb), ('ic', slice(Jb, Jb + Ji), Ji)):
-            if key not in amps:
-                continue
-            try:
-                v = np.asarray(amps[key], dtype=np.float64).reshape(-1)
-            except (TypeError, ValueError):
-                v = np.empty(0)
-            if J == 0 or v.size != J or not np.all(np.isfinite(v)):
-                raise ValueError('setBicAmplitudes[%r] takes %d finite numbers, got %r' % (key, J, amps[key]))
-            cur[sl] = v
-        self.engine.set_bic_amps(cur)
+        self._keyed_set(self._BIC, amps)
 
     # -- flux boundary identification: learnt amplitudes of a flux-datum and a Robin-coefficient basis (extension) -----
-    FBC_KEYS = ('flux', 'robin')
-
-    @staticmethod
-    def _fbc_sizes(PDE):
-        """(J_flux, J_robin): the number of functions of the PDE's flux-datum and Robin-coefficient bases (0 without one)."""
-        return len(getattr(PDE, 'fluxBasis', None) or []), len(getattr(PDE, 'robinBasis', None) or [])
-
     @staticmethod
     def fluxBCLearnData(PDE, learnFluxBC, fluxBCLr=None, fluxBCBounds=None, learning_rate=0.001):
         """(No reference counterpart: `VarNet(..., learnFluxBC=...)`.)  The registration of `vn_set_fluxbc_learn`, or None without
-        learnFluxBC: mask, init, lo, hi (J = J_flux + J_robin entries each, the flux-datum streams first) and lr.  learnFluxBC =
-        {'flux': True | mask, 'robin': True | mask} (a key left out: none of that basis is learnt); the PDE's fluxAmp / robinAmp
-        are the initial guess; fluxBCLr defaults to the network's learning rate; fluxBCBounds = {'flux': ..., 'robin': ...}, each
-        (lo, hi) for every learnt amplitude of that basis or a list with one entry per function, each None or (lo, hi), None for
-        an open side."""
-        if learnFluxBC is None or learnFluxBC is False:
-            if fluxBCLr is not None:
-                raise ValueError('fluxBCLr=%r is an option of learnFluxBC=...' % (fluxBCLr,))
-            if fluxBCBounds is not None:
-                raise ValueError('fluxBCBounds is an option of learnFluxBC=...')
-            return None
-        keys = VarNet.FBC_KEYS
-        if not isinstance(learnFluxBC, dict) or not learnFluxBC or any(k not in keys for k in learnFluxBC):
-            raise ValueError('learnFluxBC must be a dict {\'flux\': True | mask, \'robin\': True | mask}, got %r' % (learnFluxBC,))
-        if fluxBCBounds is not None and (not isinstance(fluxBCBounds, dict) or any(k not in keys for k in fluxBCBounds)):
-            raise ValueError('fluxBCBounds must be a dict {\'flux\': ..., \'robin\': ...}, got %r' % (fluxBCBounds,))
-        Jl, Jc = VarNet._fbc_sizes(PDE)
-        masks, a0s, los, his = [], [], [], []
-        for key, J, amp in (('flux', Jl, 'fluxAmp'), ('robin', Jc, 'robinAmp')):
-            sel = learnFluxBC.get(key)
-            if sel is not None and sel is not False and J == 0:
-                raise ValueError('learnFluxBC[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (key, key, key))
-            if J == 0:
-                if fluxBCBounds is not None and fluxBCBounds.get(key) is not None:
-                    raise ValueError('fluxBCBounds[%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (key, key, key))
-                continue
-            if sel is None or sel is False:
-                mask = np.zeros(J, dtype=bool)
-            else:
-                mask = VarNet._learn_mask(sel, J, 'learnFluxBC[%r] must be True or a mask of %d booleans (one per function of %sBasis), '
-                                          'got %r' % (key, J, key, sel))
-            a0 = np.asarray(getattr(PDE, amp), dtype=np.float64)
-            bounds = None if fluxBCBounds is None else fluxBCBounds.get(key)
-            lo, hi = VarNet._learn_bounds(bounds, 'fluxBCBounds[%r]' % (key,), mask, a0, 'an amplitude', 'learnFluxBC',
-                                          'fluxBCBounds[%r] must be (lo, hi) or a list of %d entries, each None or (lo, hi), got %r'
-                                          % (key, J, bounds))
-            masks.append(mask); a0s.append(a0); los.append(lo); his.append(hi)
-        mask = np.concatenate(masks) if masks else np.zeros(0, dtype=bool)
-        if not mask.any():
-            raise ValueError('learnFluxBC selects no amplitude')
-        lr = VarNet._learn_rate(fluxBCLr, 'fluxBCLr', learning_rate)
-        return dict(mask=[int(x) for x in mask], init=np.concatenate(a0s), lo=np.concatenate(los), hi=np.concatenate(his),
-                    lr=lr, Jl=Jl, Jc=Jc)
-
-    def _fbc_vector(self):
-        """The J = J_flux + J_robin amplitudes as one vector: the engine's with learnFluxBC, else the PDE's."""
-        Jl, Jc = self._fbc_sizes(self.PDE)
-        if getattr(self, 'fbcLearn', None) is not None and getattr(self, 'engine', None) is not None:
-            return np.asarray(self.engine.get_fluxbc_amps(J=Jl + Jc), dtype=np.float64)
-        return np.concatenate([np.asarray(getattr(self.PDE, 'fluxAmp', []), dtype=np.float64),
-                               np.asarray(getattr(self.PDE, 'robinAmp', []), dtype=np.float64)])
+        learnFluxBC: mask, init, lo, hi (J = J_flux + J_robin entries each, the flux-datum streams first), lr, Jl and Jc.
+        learnFluxBC = {'flux': True | mask, 'robin': True | mask} (a key left out: none of that basis is learnt); the PDE's fluxAmp /
+        robinAmp are the initial guess; fluxBCLr defaults to the network's learning rate; fluxBCBounds = {'flux': ..., 'robin':
+        ...}, each (lo, hi) for every learnt amplitude of that basis or a list with one entry per function, each None or (lo, hi),
+        None for an open side."""
+        return VarNet._keyed_learn_data(VarNet._FBC, PDE, learnFluxBC, fluxBCLr, fluxBCBounds, learning_rate)
 
     def fluxBCAmplitudes(self):
         """{'flux': J_flux amplitudes, 'robin': J_robin amplitudes} of the PDE's flux-datum and Robin-coefficient bases at the
         current state: the learnt values with learnFluxBC, else the PDE's."""
-        Jl, Jc = self._fbc_sizes(self.PDE)
-        if Jl + Jc == 0:
-            raise ValueError('fluxBCAmplitudes: the PDE has no flux or Robin basis (ADPDE(..., fluxBasis=[...], robinBasis=[...]))')
-        v = self._fbc_vector()
-        return {'flux': v[:Jl].copy(), 'robin': v[Jl:].copy()}
+        return self._keyed_amplitudes(self._FBC)
 
     def fluxBCGrad(self):
         """d loss / d amplitude of the last gradient evaluation as {'flux': ..., 'robin': ...} (zeros where not learnt)."""
-        if self.fbcLearn is None:
-            raise ValueError('fluxBCGrad: this instance learns no flux or Robin amplitudes (learnFluxBC=...)')
-        Jl, Jc = self._fbc_sizes(self.PDE)
-        g = np.asarray(self.engine.get_fluxbc_amps(grad=True, J=Jl + Jc)[1], dtype=np.float64)
-        return {'flux': g[:Jl].copy(), 'robin': g[Jl:].copy()}
+        return self._keyed_grad(self._FBC)
 
     def setFluxBCAmplitudes(self, amps):
         """Overwrite amplitudes between train() calls: {'flux': [...], 'robin': [...]} (a key left out keeps its values).  Not
         clamped to fluxBCBounds (the next update is)."""
-        if self.fbcLearn is None:
-            raise ValueError('setFluxBCAmplitudes: this instance learns no flux or Robin amplitudes (learnFluxBC=...)')
-        if not isinstance(amps, dict) or not amps or any(k not in self.FBC_KEYS for k in amps):
-            raise ValueError('setFluxBCAmplitudes takes a dict {\'flux\': [...], \'robin\': [...]}, got %r' % (amps,))
-        Jl, Jc = self._fbc_sizes(self.PDE)
-        cur = self._fbc_vector()
-        for key, sl, J in (('flux', slice(0, Jl), Jl), ('robin', slice(Jl, Jl + Jc), Jc)):
-            if key not in amps:
-                continue
-            try:
-                v = np.asarray(amps[key], dtype=np.float64).reshape(-1)
-            except (TypeError, ValueError):
-                v = np.empty(0)
-            if J == 0 or v.size != J or not np.all(np.isfinite(v)):
-                raise ValueError('setFluxBCAmplitudes[%r] takes %d finite numbers, got %r' % (key, J, amps[key]))
-            cur[sl] = v
-        self.engine.set_fluxbc_amps(cur)
+        self._keyed_set(self._FBC, amps)
 
     # -- causal time-slab weights (extension) ------------------------------------------------------
     @staticmethod
@@ -1940,28 +1808,16 @@ class VarNet:
         if not X:
             return dict(X=np.zeros([0, self.inpDim]), normal=np.zeros([0, dim]), coef=np.zeros(0), label=np.zeros(0), edges=[])
         out = dict(X=np.vstack(X), normal=np.vstack(nrm), coef=np.concatenate(coef), label=np.concatenate(label), edges=edges)
-        Jl, Jc = self._fbc_sizes(PDE)
+        Jl, Jc = self._keyed_sizes(self._FBC, PDE)
         if Jl + Jc > 0:
-            nF = out['X'].shape[0]
             span, i0 = {}, 0
             for bInd, _, n in edges:
                 span[bInd] = (i0, i0 + n)
                 i0 += n
-            S = np.zeros((Jl + Jc, nF), dtype=np.float64)
-            entries = [('fluxBasis', j, e) for j, e in enumerate(getattr(PDE, 'fluxBasis', None) or [])] \
-                + [('robinBasis', j, e) for j, e in enumerate(getattr(PDE, 'robinBasis', None) or [])]
-            for row, (name, j, (bInd, f)) in enumerate(entries):
-                r0, r1 = span[bInd]
-                x = out['X'][r0:r1]
-                targ = [x[:, dim:dim + 1]] if td else []
-                v = np.asarray(f(x[:, :dim], *targ), dtype=np.float64)
-                if v.size != r1 - r0:
-                    raise ValueError('%s[%d] must return one value per point (a column), got shape %s for %d points'
-                                     % (name, j, v.shape, r1 - r0))
-                S[row, r0:r1] = v.reshape(-1)
+            S = self._edge_basis(out['X'], span, ('fluxBasis', 'robinBasis'))
             out['basis'], out['J_flux'] = S, Jl
             if getattr(self, 'fbcLearn', None) is None:
-                a = self._fbc_vector()
+                a = self._keyed_vector(self._FBC)
                 out['label'] = out['label'] + a[:Jl] @ S[:Jl]
                 out['coef'] = out['coef'] + a[Jl:] @ S[Jl:]
                 out['basis'] = None
@@ -2132,8 +1988,8 @@ class VarNet:
         if td:
             arg = biArg[-1] if biArg[-1] is not None else {}
             out = uf.vstack([out, PDE.IC(biInput[ind:, :dim], **arg)])
-        if basis and sum(self._bic_sizes(PDE)) > 0:
-            out = np.asarray(out, dtype=np.float64).reshape(-1, 1) + (self._bic_vector() @ self._bic_basis(biInput, biDof)).reshape(-1, 1)
+        if basis and sum(self._keyed_sizes(self._BIC, PDE)) > 0:
+            out = np.asarray(out, dtype=np.float64).reshape(-1, 1) + (self._keyed_vector(self._BIC) @ self._bic_basis(biInput, biDof)).reshape(-1, 1)
         return out
 
     def PDEinpData(self, Input, inpArg=[], basis=True, field=True):
@@ -2150,14 +2006,14 @@ class VarNet:
         src = PDE.sourceFun(X, *targ, **sourceArg)
         if basis and getattr(PDE, 'sourceBasis', None) is not None:
             src = np.asarray(src, dtype=np.float64).reshape(-1, 1) + self._source_basis(Input) @ self.sourceAmplitudes().reshape(-1, 1)
-        Jk, Jv = self._field_sizes(PDE)
+        Jk, Jv = self._keyed_sizes(self._FIELD, PDE)
         if Jk + Jv == 0:
             return PDE.diffFun(X, *targ, **diffArg), PDE.velFun(X, *targ, **velArg), src
         # (a basis excludes MOR: no extra arguments) the plain fields, plus the sums at the current amplitudes
         diff = np.asarray((PDE.diffFun0 if Jk else PDE.diffFun)(X, *targ), dtype=np.float64).reshape(-1, 1)
         vel = np.asarray((PDE.velFun0 if Jv else PDE.velFun)(X, *targ), dtype=np.float64).reshape(-1, dim)
         if field:
-            b = self._field_vector()
+            b = self._keyed_vector(self._FIELD)
             chi, _, omega = self._field_basis(Input)
             diff = diff + np.tensordot(b[:Jk], chi, axes=1)
             vel = vel + np.tensordot(b[Jk:], omega, axes=1)
@@ -2168,11 +2024,11 @@ class VarNet:
         dim, PDE = self.dim, self.PDE
         targ = [Input[:, dim][np.newaxis].T] if PDE.timeDependent else []
         X = Input[:, 0:dim]
-        Jk = self._field_sizes(PDE)[0]
+        Jk = self._keyed_sizes(self._FIELD, PDE)[0]
         if Jk == 0:
             return PDE.d_diffFun(X, *targ)
         g = np.asarray(PDE.d_diffFun0(X, *targ), dtype=np.float64).reshape(-1, dim)
-        return g + np.tensordot(self._field_vector()[:Jk], self._field_basis(Input, grad=True)[1], axes=1)
+        return g + np.tensordot(self._keyed_vector(self._FIELD)[:Jk], self._field_basis(Input, grad=True)[1], axes=1)
 
     def _reaction_rate(self, Input):
         """Reaction rate at the rows of Input (a column), evaluated like the source (PDEinpData)."""
@@ -2801,7 +2657,7 @@ class VarNet:
                         trainW, w_eff, _ = set_train_weights(tData, weight)
             epoch = first + nblk
         trainRes.flushPlots()
-        for lv in self.LEARNT_ALL:
+        for lv in self.LEARNT:
             data = getattr(self, lv.attr)
             if data is not None and self.rank == 0:
                 scale = data.get('scale', 1.0)           # (coefficients are reported in the user's scale: `coefficients()`)
@@ -2843,7 +2699,7 @@ class VarNet:
         if slot[0] == 'Adam':
             out['beta1_power'] = np.float32(0.9 ** (step + 1))       # TF keeps beta^(t+1) for the next update
             out['beta2_power'] = np.float32(0.999 ** (step + 1))
-        for lv in self.LEARNT_ALL:
+        for lv in self.LEARNT:
             if getattr(self, lv.attr, None) is not None:
                 # the values in the engine's scale (vn_get_*: the nine coefficients, the J source amplitudes, the J field amplitudes
                 # with the diffusivity streams first); their Adam slots have no entry point and restart from zero
@@ -2871,7 +2727,7 @@ class VarNet:
         step = np.array([int(arrays['global_step']) if 'global_step' in arrays else 0], dtype=np.int64)
         blob = np.concatenate([step.view(np.uint8), np.concatenate(th + m + v).astype(np.float32).view(np.uint8)])
         self.engine.import_state(blob)
-        for lv in self.LEARNT_ALL:
+        for lv in self.LEARNT:
             if getattr(self, lv.attr, None) is not None and lv.key in arrays:
                 getattr(self.engine, 'set_' + lv.engine)(np.asarray(arrays[lv.key], dtype=np.float64).reshape(-1))
 
