@@ -519,6 +519,33 @@ int vn_get_fluxbc_amps(vn_engine* h, double* amp, double* grad, int32_t J);
 /* Overwrites all J amplitudes (rounded to fp32, NOT clamped); the Adam slots stay.  Non-finite: VN_EINVAL; learning off: VN_ESTATE.
  * Invalidates the snapshot of vn_state_snapshot. */
 int vn_set_fluxbc_amps(vn_engine* h, const double* amp, int32_t J);
+/* Regularisation of a learnt vector a of length J (kind: one of VN_LEARNT_*, the order of the sections above), with learnt mask M.
+ * Quadratic prior Q(a) = 1/2 weight d^T R d, d = a - mean: R [J*J] symmetric positive semi-definite (NULL: the identity), mean [J]
+ * (NULL: zeros), both host fp64, copied.  weight (R d)_j is added in fp64 to the folded gradient of the masked entries inside
+ * vn_grad / vn_train_step / vn_train_epoch, before the cast to fp32 that feeds Adam; unmasked entries keep gradient 0, but their
+ * fixed values enter d; d is formed from the values the gradient evaluation read.  vn_get_*(..., grad) then returns data gradient
+ * plus prior gradient, and a vn_apply after a vn_grad steps on that gradient as it stands (the prior is not added a second time).
+ * L1 shrinkage: l1 [J] host weights lambda_j >= 0 (NULL: none); the step of a masked entry ends in the proximal map
+ *   c <- copysign(max(|c| - lr_t lambda_j, 0), c)
+ * in fp32 after Adam's move and before the clamp, lr_t the bias-corrected rate of that step; it is no part of the gradient.  The
+ * zero it produces keeps the sign of c: an entry shrunk from below reads -0.0, which compares equal to 0.  An
+ * entry with lambda_j == 0, and every entry without a prior, keeps its arithmetic bit for bit.
+ * The losses that vn_train_step, vn_eval_loss, vn_objective_f64 and the L-BFGS calls report do NOT contain Q or the L1 term: read
+ * them with vn_get_learnt_prior.  weight == 0 with l1 == NULL clears the prior; any vn_set_<kind>_learn call, also a refused one, drops it.  The prior
+ * is static data: the call may be repeated between steps to re-weight, and touches neither the values, the Adam slots nor the
+ * snapshot.  It adds no launch to a step.
+ * The vector not learnt: VN_ESTATE.  VN_EINVAL: kind outside 0..4; J not the registered length; weight negative or not finite; an
+ * entry of R not finite, or R[i*J+j] != R[j*J+i]; an entry of mean not finite; an entry of l1 negative or not finite.  (Whether R
+ * is positive semi-definite is the caller's to check: an indefinite R makes Q unbounded below.) */
+#define VN_LEARNT_COEF 0
+#define VN_LEARNT_SOURCE 1
+#define VN_LEARNT_FIELD 2
+#define VN_LEARNT_BIC 3
+#define VN_LEARNT_FLUXBC 4
+int vn_set_learnt_prior(vn_engine* h, int32_t kind, int32_t J, double weight, const double* R, const double* mean, const double* l1);
+/* out[0] = Q and out[1] = sum_j lambda_j |a_j| at the current values (one launch; synchronises; changes no state); (0, 0) without a
+ * prior.  The vector not learnt: VN_ESTATE. */
+int vn_get_learnt_prior(vn_engine* h, int32_t kind, double out[2]);
 /* updateDictFields('trainW') (VarNetUtility.py:921-922); the caller applies the
  * w[0:2] /= batchNum*puNum rule (VarNetUtility.py:900-901). */
 int vn_set_weights(vn_engine* h, const double w[3]);

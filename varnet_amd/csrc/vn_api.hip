@@ -155,6 +155,12 @@ struct Learnt {
   double* grad = nullptr;                         // [cap] gradient of the last gradient evaluation
   float* part = nullptr;                          // [maxblk, J] partials of the reduction
   int blocks = 0;                                 // partials the current gradient evaluation wrote (0: the batch has nothing to reduce)
+  // the prior of vn_set_learnt_prior (static: vn_state_snapshot has nothing to copy); all null / 0 without one
+  double weight = 0.0;                            // alpha of the quadratic prior
+  double* R = nullptr;                            // [J, J] its matrix; nullptr: the identity
+  double* mean = nullptr;                         // [cap] its mean
+  float* l1 = nullptr;                            // [cap] shrinkage weights; nullptr: none
+  double* pen = nullptr;                          // [2] (Q, sum lambda |a|) of vn_get_learnt_prior
   struct Work { float* p = nullptr; long cap = 0; } work[3];   // the feature's own work buffers, by its *Work slot: allocated on
 };                                                             // first use (lv_ensure), freed with the vector (learnt_free)
 enum CoefWork { CW_ACC };                   // [3, U] accR_j, accF_j, gs_j of the de-duplicated step
@@ -1181,6 +1187,7 @@ int learnt_finish(vn_engine* h, int id, bool fold, bool update, double t) {
   a.val = v.state; a.m = v.state + k.cap; a.v = v.state + 2 * k.cap;
   a.lo = v.bounds; a.hi = v.bounds + k.cap;
   a.mask = v.mask;
+  a.R = v.R; a.mean = v.mean; a.weight = v.weight; a.l1 = v.l1;
   a.update = update ? 1 : 0;
   if (update) {
     const vn_config& c = h->cfg;
@@ -1191,9 +1198,18 @@ int learnt_finish(vn_engine* h, int id, bool fold, bool update, double t) {
   return VN_OK;
 }
 
-// (the feature's own work buffers go with its vector)
+// the prior of a vector, dropped (the caller has drained the stream)
+void learnt_prior_drop(Learnt& v) {
+  for (void* p : {(void*)v.R, (void*)v.mean, (void*)v.l1, (void*)v.pen})
+    if (p) (void)hipFree(p);
+  v.R = nullptr; v.mean = nullptr; v.l1 = nullptr; v.pen = nullptr;
+  v.weight = 0.0;
+}
+
+// (the feature's own work buffers and the prior go with its vector)
 void learnt_free(vn_engine* h, int id) {
   Learnt& v = h->lv[id];
+  learnt_prior_drop(v);
   for (void* p : {(void*)v.state, (void*)v.bounds, (void*)v.grad, (void*)v.part})
     if (p) (void)hipFree(p);
   for (const Learnt::Work& w : v.work)
@@ -1722,7 +1738,7 @@ int vn_set_nldiff(vn_engine* h, int32_t batch, const float* psi, const double co
 
 // ---- learnt vectors: what vn_set_*_learn, vn_get_* and vn_set_* of the three share ----
 // vn_set_*_learn: mask == NULL switches the vector off and frees it; `extra` holds the refusals that are the feature's own.
-// Every call, also a failing one, invalidates the snapshot and the L-BFGS state.
+// Every call, also a failing one, invalidates the snapshot and the L-BFGS state and drops the vector's prior (vn_set_learnt_prior).
 static int learnt_set_learn(vn_engine* h, int id, int32_t J, const int32_t* mask, const double* init, const double* lo, const double* hi,
                             double lr, int (*extra)(vn_engine*) = nullptr) {
   const LearntKind& k = kLearnt[id];
@@ -1731,6 +1747,10 @@ static int learnt_set_learn(vn_engine* h, int id, int32_t J, const int32_t* mask
   HIPCHK(hipSetDevice(h->cfg.device));
   h->snap_step = -1;
   lbfgs_invalidate(h);
+  if (h->lv[id].pen) {                          // a prior belongs to one registration: every call, also a failing one, drops it
+    HIPCHK(hipStreamSynchronize(h->stream));
+    learnt_prior_drop(h->lv[id]);
+  }
   if (!mask) {
     HIPCHK(hipStreamSynchronize(h->stream));
     learnt_free(h, id);
@@ -1813,6 +1833,75 @@ static int learnt_put(vn_engine* h, int id, const double* val, int32_t J) {
   HIPCHK(hipStreamSynchronize(h->stream));
   h->snap_step = -1;
   lbfgs_invalidate(h);
+  return VN_OK;
+}
+
+// vn_set_learnt_prior: the quadratic prior and the L1 weights of one learnt vector.  Static data: the Adam
+// slots, the snapshot and the values stay as they are, so it may be called between steps to re-weight.
+int vn_set_learnt_prior(vn_engine* h, int32_t kind, int32_t J, double weight, const double* R, const double* mean, const double* l1) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (kind < 0 || kind >= LV_N) return fail(VN_EINVAL, "learnt vector kind %d is none of VN_LEARNT_COEF .. VN_LEARNT_FLUXBC (0 to %d)", kind, LV_N - 1);
+  const LearntKind& k = kLearnt[kind];
+  Learnt& v = h->lv[kind];
+  if (!v.on) return fail(VN_ESTATE, "no learnt %s (call %s first)", k.what, k.setter);
+  if (J != v.J) return fail(VN_EINVAL, "the engine holds %d %s, the prior is for %d", v.J, k.what, J);
+  if (!(std::isfinite(weight) && weight >= 0.0)) return fail(VN_EINVAL, "prior weight %g must be finite and >= 0", weight);
+  if (R)
+    for (int i = 0; i < J; ++i)
+      for (int j = 0; j <= i; ++j) {
+        const double x = R[(long)i * J + j], y = R[(long)j * J + i];
+        if (!std::isfinite(x) || !std::isfinite(y))
+          return fail(VN_EINVAL, "prior matrix entries (%d, %d) = %g and (%d, %d) = %g must be finite", i, j, x, j, i, y);
+        if (x != y) return fail(VN_EINVAL, "prior matrix is not symmetric: entry (%d, %d) = %.17g, entry (%d, %d) = %.17g", i, j, x, j, i, y);
+      }
+  if (mean)
+    for (int i = 0; i < J; ++i)
+      if (!std::isfinite(mean[i])) return fail(VN_EINVAL, "prior mean of %s %d = %g must be finite", k.noun, i, mean[i]);
+  if (l1)
+    for (int i = 0; i < J; ++i)
+      if (!(std::isfinite(l1[i]) && l1[i] >= 0.0)) return fail(VN_EINVAL, "L1 weight of %s %d = %g must be finite and >= 0", k.noun, i, l1[i]);
+  (void)hipGetLastError();
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));        // (a step in flight reads the buffers replaced below)
+  learnt_prior_drop(v);
+  if (weight == 0.0 && !l1) return VN_OK;
+  const bool quad = weight > 0.0;
+  hipError_t e = hipMalloc((void**)&v.pen, 2 * sizeof(double));
+  if (e == hipSuccess && quad) e = hipMalloc((void**)&v.mean, (size_t)k.cap * sizeof(double));
+  if (e == hipSuccess && quad && R) e = hipMalloc((void**)&v.R, (size_t)J * J * sizeof(double));
+  if (e == hipSuccess && l1) e = hipMalloc((void**)&v.l1, (size_t)k.cap * sizeof(float));
+  if (e != hipSuccess) { (void)hipGetLastError(); learnt_prior_drop(v); return fail(VN_ENOMEM, "vn_set_learnt_prior: %s", hipGetErrorString(e)); }
+  double mu[LV_CAP] = {};
+  float lam[LV_CAP] = {};
+  for (int i = 0; i < J; ++i) {
+    if (mean) mu[i] = mean[i];
+    if (l1) lam[i] = (float)l1[i];
+  }
+  if (quad) HIPCHK(hipMemcpyAsync(v.mean, mu, (size_t)k.cap * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (v.R) HIPCHK(hipMemcpyAsync(v.R, R, (size_t)J * J * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (v.l1) HIPCHK(hipMemcpyAsync(v.l1, lam, (size_t)k.cap * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));        // (mu, lam leave scope; R is the caller's)
+  v.weight = weight;
+  return VN_OK;
+}
+
+// vn_get_learnt_prior: (Q, sum lambda |a|) at the current values -- the apply kernel's evaluate-only mode; changes no state
+int vn_get_learnt_prior(vn_engine* h, int32_t kind, double out[2]) {
+  if (!h || !out) return fail(VN_EINVAL, "null argument");
+  if (kind < 0 || kind >= LV_N) return fail(VN_EINVAL, "learnt vector kind %d is none of VN_LEARNT_COEF .. VN_LEARNT_FLUXBC (0 to %d)", kind, LV_N - 1);
+  const LearntKind& k = kLearnt[kind];
+  const Learnt& v = h->lv[kind];
+  if (!v.on) return fail(VN_ESTATE, "no learnt %s (call %s first)", k.what, k.setter);
+  out[0] = out[1] = 0.0;
+  if (!v.pen) return VN_OK;                       // no prior: both are 0
+  (void)hipGetLastError();
+  HIPCHK(hipSetDevice(h->cfg.device));
+  VnLearntApplyArgs a{};
+  a.J = v.J; a.lanes = k.lanes; a.val = v.state; a.mask = v.mask;
+  a.R = v.R; a.mean = v.mean; a.weight = v.weight; a.l1 = v.l1; a.pen = v.pen;
+  HIPCHK(vn_learnt_apply_launch(a, h->stream));
+  HIPCHK(hipMemcpyAsync(out, v.pen, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
   return VN_OK;
 }
 

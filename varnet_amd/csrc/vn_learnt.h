@@ -115,6 +115,8 @@ hipError_t vn_fbcgrad_launch(const VnFbcGradArgs& a, int* blocks, hipStream_t s)
 // ---- every vector.  One block: grad[j] = sum over the [blocks, J] partials in fp64 (blocks > 0; else grad as it stands), then
 // with `update` the Adam step of the masked entries and the clamp.  `lanes` (16 or 64) is the fold's lane-group width: 256 / lanes
 // groups each sum their chunk of the blocks in index order, then the group sums are added in group order.
+// Prior (weight > 0): the fold adds weight (R (val - mean))_j in fp64 to the masked entries' gradient (blocks > 0 only), with val
+// as the gradient evaluation read it.  l1: the update ends in the shrinkage by lr_t l1[j], before the clamp.  pen: evaluate only.
 struct VnLearntApplyArgs {
   const float* part; int blocks; int J;
   double* grad;                              // [J]
@@ -124,5 +126,10 @@ struct VnLearntApplyArgs {
   int update;
   float lr_t, b1, b2, eps;
   int lanes;
+  const double* R;                           // [J, J] symmetric, device, or nullptr: the identity
+  const double* mean;                        // [J] device (read with weight > 0)
+  double weight;                             // alpha of 1/2 alpha d^T R d; 0: no quadratic prior
+  const float* l1;                           // [J] device, or nullptr: no shrinkage
+  double* pen;                               // [2] device, or nullptr; given: no fold, no update, pen = (Q, sum_j l1[j] |val[j]|)
 };
 hipError_t vn_learnt_apply_launch(const VnLearntApplyArgs& a, hipStream_t s);

@@ -294,12 +294,22 @@ __global__ __launch_bounds__(TB) void vn_fbcgrad_kernel(VnFbcGradArgs a) {
 // each vector had its own kernel the compiler contracted b2 v + (1 - b2) g g into fma(b2, v, ((1 - b2) g) g) for the coefficients
 // and into fma((1 - b2) g, g, b2 v) for the amplitudes, which round differently; both are written out here, so neither vector's
 // trajectory moves.  (One form for all is a change of behaviour, to be made on purpose.)
+// Prior.  With weight > 0 the quadratic prior Q(a) = 1/2 weight d^T R d, d = a - mean, adds weight (R d)_j
+// in fp64 to the folded gradient of the masked entries, inside the fold (blocks > 0) only, so an apply after a gradient evaluation
+// does not add it twice.  d is staged in shared memory before the barrier: no thread reads a value another has stepped.  Thread j
+// walks column j of R, i ascending -- by symmetry row j, and a wave reads consecutive doubles.  With l1 the step ends in the
+// proximal shrinkage c <- sign(c) max(|c| - lr_t l1[j], 0), fp32, after Adam's move and before the clamp; an entry with l1[j] == 0
+// keeps the arithmetic it had.  pen != nullptr: evaluate only -- no fold, no update; pen[0] = Q and pen[1] = sum_j l1[j] |a_j|,
+// each summed in index order by thread 0 from per-entry fp64 products.
 template <int LANES>
 __global__ __launch_bounds__(TB) void vn_learnt_apply_kernel(VnLearntApplyArgs a) {
   constexpr int GROUPS = TB / LANES;
   __shared__ double sub[GROUPS][LANES];
+  __shared__ double dsh[VN_SRC_JMAX], qsh[VN_SRC_JMAX], lsh[VN_SRC_JMAX];
   const int j = threadIdx.x % LANES, g = threadIdx.x / LANES;
-  if (a.blocks > 0) {
+  const bool in = (int)threadIdx.x < a.J;                      // (J <= LANES: these are the threads of group 0, and j == threadIdx.x)
+  const bool quad = a.weight > 0.0;
+  if (a.blocks > 0 && !a.pen) {
     const int chunk = (a.blocks + GROUPS - 1) / GROUPS;
     const int b1 = (g + 1) * chunk < a.blocks ? (g + 1) * chunk : a.blocks;
     double t = 0.0;
@@ -307,23 +317,48 @@ __global__ __launch_bounds__(TB) void vn_learnt_apply_kernel(VnLearntApplyArgs a
       for (int b = g * chunk; b < b1; ++b) t += (double)a.part[(long)b * a.J + j];
     sub[g][j] = t;
   }
+  if (quad && in) dsh[j] = (double)a.val[j] - a.mean[j];
   __syncthreads();
-  if ((int)threadIdx.x >= a.J) return;
+  double rd = 0.0;                                             // (R d)_j
+  if (quad && in && (a.pen || a.blocks > 0)) {
+    if (a.R)
+      for (int i = 0; i < a.J; ++i) rd += a.R[(long)i * a.J + j] * dsh[i];
+    else
+      rd = dsh[j];
+  }
+  if (a.pen) {                                                 // (uniform: every thread takes the branch, and its barrier)
+    if (in) {
+      qsh[j] = quad ? dsh[j] * rd : 0.0;
+      lsh[j] = a.l1 ? (double)a.l1[j] * fabs((double)a.val[j]) : 0.0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double q = 0.0, l = 0.0;
+      for (int i = 0; i < a.J; ++i) { q += qsh[i]; l += lsh[i]; }
+      a.pen[0] = 0.5 * a.weight * q;
+      a.pen[1] = l;
+    }
+    return;
+  }
+  if (!in) return;                                             // (no barrier below)
   const bool on = a.mask >> j & 1ull;
   double gr = a.grad[j];
   if (a.blocks > 0) {
     gr = 0.0;
     for (int k = 0; k < GROUPS; ++k) gr += sub[k][j];
+    if (quad) gr += a.weight * rd;
     if (!on) gr = 0.0;
     a.grad[j] = gr;
   }
-  if (a.update && on) {                                        // same arithmetic as vn_adam_kernel, then the clamp
+  if (a.update && on) {                                        // same arithmetic as vn_adam_kernel, then the shrinkage and the clamp
     const float gi = (float)gr;
     const float mi = fmaf(1.f - a.b1, gi, a.b1 * a.m[j]);
     const float vi = LANES == 16 ? fmaf(a.b2, a.v[j], (1.f - a.b2) * gi * gi) : fmaf((1.f - a.b2) * gi, gi, a.b2 * a.v[j]);
     a.m[j] = mi;
     a.v[j] = vi;
-    const float c = a.val[j] - a.lr_t * mi / (sqrtf(vi) + a.eps);
+    float c = a.val[j] - a.lr_t * mi / (sqrtf(vi) + a.eps);
+    const float lam = a.l1 ? a.l1[j] : 0.f;
+    if (lam > 0.f) c = copysignf(fmaxf(fabsf(c) - __fmul_rn(a.lr_t, lam), 0.f), c);
     a.val[j] = fminf(fmaxf(c, a.lo[j]), a.hi[j]);
   }
 }

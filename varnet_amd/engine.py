@@ -98,6 +98,9 @@ _SIGS = {
                                       C.POINTER(C.c_double), C.c_double]),
     'vn_get_fluxbc_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32]),
     'vn_set_fluxbc_amps': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
+    'vn_set_learnt_prior': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double)]),
+    'vn_get_learnt_prior': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]),
     'vn_set_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_bind_grad_buffer': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vn_grad': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -139,7 +142,8 @@ ABI_SYMBOLS = tuple(_SIGS.keys())
 
 # the _keep keys of the three polynomial terms, in the order of the coefficient index (vn_set_coef_learn)
 COEF_TERMS = ('react', 'nlflux', 'nldiff')
-# the learnt vectors: the name vn_get_* / vn_set_* carry, and the fixed length (None: the ABI takes the length J)
+# the learnt vectors, in the order of VN_LEARNT_* (the `kind` of vn_set_learnt_prior): the name vn_get_* / vn_set_* carry, and
+# the fixed length (None: the ABI takes the length J)
 LEARNT = {'coef': ('coefs', 9), 'source': ('source_amps', None), 'field': ('field_amps', None), 'bic': ('bic_amps', None),
           'fluxbc': ('fluxbc_amps', None)}
 
@@ -625,6 +629,38 @@ class VNEngine:
         if fixed and v.size != fixed:
             raise ValueError('coef must have nine entries (reaction, flux, diffusivity: three each), got %d' % v.size)
         self._ck(getattr(self.lib, 'vn_set_' + name)(self.h, (C.c_double * max(v.size, 1))(*v), *(() if fixed else (int(v.size),))))
+
+    def set_learnt_prior(self, kind, weight=0.0, matrix=None, mean=None, l1=None):
+        """Regularise the learnt vector `kind` (a key of LEARNT; vn_set_learnt_prior): the quadratic prior
+        1/2 weight (a - mean)^T matrix (a - mean) -- matrix [J, J] symmetric positive semi-definite (None: the identity), mean [J]
+        (None: zeros) -- whose gradient joins the masked entries' folded gradient in fp64, and the L1 weights l1 [J] (or one number
+        for all; None: none) of the proximal shrinkage by lr_t l1[j] that ends their step.  weight=0 with l1=None clears the prior;
+        so does every set_<kind>_learn.  The reported losses do not contain either term: learnt_prior(kind) reads them."""
+        if kind not in LEARNT:
+            raise ValueError('unknown learnt vector %r (one of %s)' % (kind, ', '.join(LEARNT)))
+        if getattr(self, '_learnt_' + kind, None) is None:         # (not learnt: the engine's sentence)
+            self._ck(self.lib.vn_set_learnt_prior(self.h, list(LEARNT).index(kind), 0, 0.0, None, None, None))
+        n = len(getattr(self, '_learnt_' + kind))
+
+        def arr(a, shape, name):
+            if a is None:
+                return None
+            v = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), shape) if np.ndim(a) == 0 and name == 'l1'
+                                     else np.asarray(a, dtype=np.float64))
+            if v.shape != shape:
+                raise ValueError('%s of the %s prior must have shape %s, got %s' % (name, kind, shape, v.shape))
+            return v
+        R, mu, lam = arr(matrix, (n, n), 'matrix'), arr(mean, (n,), 'mean'), arr(l1, (n,), 'l1')
+        dp = lambda v: None if v is None else v.ctypes.data_as(C.POINTER(C.c_double))
+        self._ck(self.lib.vn_set_learnt_prior(self.h, list(LEARNT).index(kind), n, float(weight), dp(R), dp(mu), dp(lam)))
+
+    def learnt_prior(self, kind):
+        """(Q, sum_j l1[j] |a_j|) of the learnt vector `kind` at its current values (vn_get_learnt_prior); (0, 0) without a prior."""
+        if kind not in LEARNT:
+            raise ValueError('unknown learnt vector %r (one of %s)' % (kind, ', '.join(LEARNT)))
+        out = (C.c_double * 2)()
+        self._ck(self.lib.vn_get_learnt_prior(self.h, list(LEARNT).index(kind), out))
+        return float(out[0]), float(out[1])
 
     def _set_basis(self, key, fn, batch, streams, trailing):
         """Register (streams=None: clear) the J basis streams of `batch`, uploaded as [J, rows, *trailing] and kept alive."""

@@ -311,6 +311,13 @@ class TrainResult:
                      % str(list(PDE.nldiffCoef)))
         if getattr(varNet, 'causal', None) is not None:
             L.append('Causal time-slab loss weights: eps = %s, %d slabs\n\n' % (repr(float(varNet.causal)), varNet.causalSlabNum()))
+        for stem, pr in (getattr(varNet, 'learntPrior', None) or {}).items():
+            for key, b in pr['blocks'].items():
+                L.append('Prior on the learnt %s%s: weight %s, matrix %s, mean %s, l1 %s\n\n'
+                         % (stem, '' if key is None else '[%r]' % key, repr(b['weight']),
+                            'identity' if np.array_equal(b['R'], np.eye(len(b['mean']))) else
+                            'difference' if np.array_equal(b['R'], VarNet.priorMatrix('difference', len(b['mean']))) else
+                            '%d x %d given' % b['R'].shape, [float(x) for x in b['mean']], [float(x) for x in b['l1']]))
         L.append('Neural Network architecture:\n')
         L.append('\ttype: ' + str(varNet.modelId) + '\n')
         L.append('\tnumber of inputs: ' + str(varNet.inpDim) + '\n')
@@ -811,7 +818,7 @@ class VarNet:
                  causal=None, causalSlabs=None, periodicDeriv=None, observations=None, obsWeight=None,
                  learnCoef=None, coefLr=None, coefBounds=None, learnSource=None, sourceLr=None, sourceBounds=None,
                  learnField=None, fieldLr=None, fieldBounds=None, learnBic=None, bicLr=None, bicBounds=None,
-                 learnFluxBC=None, fluxBCLr=None, fluxBCBounds=None):
+                 learnFluxBC=None, fluxBCLr=None, fluxBCBounds=None, learntPrior=None):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -915,6 +922,9 @@ class VarNet:
             if causal is not None:
                 raise NotImplementedError('%s with causal=%r: the causal weights are applied after the seeds the %s gradient is '
                                           'reduced from' % (lv.option, causal, lv.noun))
+        # learntPrior={stem: spec} (extension; no reference counterpart): a quadratic prior and L1 shrinkage on the learnt vectors
+        # (`priorData`)
+        self.learntPrior = self.priorData(PDE, learntPrior, {lv.stem: getattr(self, lv.attr) for lv in self.LEARNT})
 
         inpDim = dim + (1 if timeDependent else 0)
         if MORvar is not None:
@@ -1038,6 +1048,8 @@ class VarNet:
             d = getattr(self, lv.attr)
             if d is not None:
                 getattr(self.engine, 'set_%s_learn' % lv.kind)(d['mask'], d['init'], d['lo'], d['hi'], d['lr'])
+                if lv.stem in self.learntPrior:
+                    self._register_prior(lv)
         self.tfData = self.engine       # name kept for scripts that poke at `VarNet.tfData`
         from .launch import mark_stage
         mark_stage('engine_ready')      # past the launcher's bootstrap deadline: a rank that trains for hours is healthy
@@ -1090,28 +1102,29 @@ class VarNet:
 
     # -- the vectors learnt next to the network, in the engine's order: the option, its parser, the attribute that keeps the parsed
     # registration, the noun of an entry, what model-order reduction lacks for it, what towers lack, the checkpoint key, the stem
-    # of the engine's get_* / set_* methods, the title of train()'s closing line, the kind in the engine's set_<kind>_learn, and for
-    # a vector made of two keyed parts its KeyedVector (else None)
-    LearntVector = collections.namedtuple('LearntVector', 'option parser attr noun mor_lacks grads key engine title kind keyed')
+    # of the engine's get_* / set_* methods, the title of train()'s closing line, the kind in the engine's set_<kind>_learn, for
+    # a vector made of two keyed parts its KeyedVector (else None), and the stem learntPrior={stem: ...} names it by
+    LearntVector = collections.namedtuple('LearntVector', 'option parser attr noun mor_lacks grads key engine title kind keyed stem')
     # a vector of two parts, each the amplitudes of one basis of the PDE, which keeps part `key` as <key>Basis / <key>Amp: the stem
     # of its options (<stem>Lr, <stem>Bounds) and methods (<stem>Amplitudes, <stem>Grad, set<Stem>Amplitudes), the two keys in the
     # vector's order, the names of the two sizes in the parsed registration, and how messages call its bases and its amplitudes
     KeyedVector = collections.namedtuple('KeyedVector', 'stem keys sizes bases amps')
     LEARNT = (
         LearntVector('learnCoef', 'coefLearnData', 'coefLearn', 'coefficient', 'the three polynomial terms',
-                     'the nine coefficient gradients', 'pde_coefficients', 'coefs', 'Learnt coefficients', 'coef', None),
+                     'the nine coefficient gradients', 'pde_coefficients', 'coefs', 'Learnt coefficients', 'coef', None, 'coef'),
         LearntVector('learnSource', 'sourceLearnData', 'srcLearn', 'amplitude', 'the source basis',
-                     'the amplitude gradients', 'source_amplitudes', 'source_amps', 'Learnt source amplitudes', 'source', None),
+                     'the amplitude gradients', 'source_amplitudes', 'source_amps', 'Learnt source amplitudes', 'source', None,
+                     'source'),
         LearntVector('learnField', 'fieldLearnData', 'fldLearn', 'amplitude', 'the field bases',
                      'the amplitude gradients', 'field_amplitudes', 'field_amps', 'Learnt field amplitudes (diff, then vel)', 'field',
-                     KeyedVector('field', ('diff', 'vel'), ('Jk', 'Jv'), 'field', 'field amplitudes')),
+                     KeyedVector('field', ('diff', 'vel'), ('Jk', 'Jv'), 'field', 'field amplitudes'), 'field'),
         LearntVector('learnBic', 'bicLearnData', 'bicLearn', 'amplitude', 'the boundary and initial bases',
                      'the amplitude gradients', 'bic_amplitudes', 'bic_amps', 'Learnt boundary and initial amplitudes (bc, then ic)', 'bic',
-                     KeyedVector('bic', ('bc', 'ic'), ('Jb', 'Ji'), 'Dirichlet or initial', 'boundary or initial amplitudes')),
+                     KeyedVector('bic', ('bc', 'ic'), ('Jb', 'Ji'), 'Dirichlet or initial', 'boundary or initial amplitudes'), 'bic'),
         # (its rows are an edge row set's, not a batch's or the BC/IC set's)
         LearntVector('learnFluxBC', 'fluxBCLearnData', 'fbcLearn', 'amplitude', 'the boundary-flux rows',
                      'the amplitude gradients', 'fluxbc_amplitudes', 'fluxbc_amps', 'Learnt flux and Robin amplitudes (flux, then robin)',
-                     'fluxbc', KeyedVector('fluxBC', ('flux', 'robin'), ('Jl', 'Jc'), 'flux or Robin', 'flux or Robin amplitudes')))
+                     'fluxbc', KeyedVector('fluxBC', ('flux', 'robin'), ('Jl', 'Jc'), 'flux or Robin', 'flux or Robin amplitudes'), 'fluxBC'))
     _FIELD, _BIC, _FBC = LEARNT[2:]
 
     # -- what the learnt vectors' options share (coefLearnData, sourceLearnData and the keyed vectors') --
@@ -1535,6 +1548,163 @@ class VarNet:
         """Overwrite amplitudes between train() calls: {'flux': [...], 'robin': [...]} (a key left out keeps its values).  Not
         clamped to fluxBCBounds (the next update is)."""
         self._keyed_set(self._FBC, amps)
+
+    # -- regularisation of the learnt vectors: quadratic prior and L1 shrinkage (extension) ---------------------
+    PRIOR_KEYS = ('weight', 'matrix', 'mean', 'l1')
+
+    @staticmethod
+    def priorMatrix(kind, n):
+        """The named matrices of a prior block of n amplitudes: 'identity', or 'difference' = D^T D of the first differences
+        (D a)_i = a_{i+1} - a_i in amplitude order (zero on constants; the 1 x 1 block is 0)."""
+        if kind == 'identity':
+            return np.eye(n)
+        if kind == 'difference':
+            D = np.diff(np.eye(n), axis=0)
+            return D.T @ D
+        raise ValueError('learntPrior: matrix must be \'identity\', \'difference\' or a symmetric positive semi-definite array, got %r' % (kind,))
+
+    @staticmethod
+    def _prior_block(where, spec, init):
+        """One block of a prior from its spec, for the amplitudes whose starting values are `init`: dict(weight, R [n, n], mean [n],
+        l1 [n]); every refusal names `where`."""
+        n = len(init)
+        if not isinstance(spec, dict) or any(k not in VarNet.PRIOR_KEYS for k in spec):
+            raise ValueError('%s must be a dict with keys among %s, got %r' % (where, ', '.join(VarNet.PRIOR_KEYS), spec))
+
+        def number(x):
+            return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+        w = spec.get('weight', 0.0)
+        if not number(w) or not np.isfinite(w):
+            raise ValueError('%s: weight must be a finite number, got %r' % (where, w))
+        if w < 0:
+            raise ValueError('%s: weight %r is negative (the prior 1/2 weight d^T R d must be bounded below)' % (where, w))
+        m = spec.get('matrix', 'identity')
+        if isinstance(m, str):
+            R = VarNet.priorMatrix(m, n)
+        else:
+            try:
+                R = np.array(m, dtype=np.float64)
+            except (TypeError, ValueError):
+                R = np.empty(0)
+            if R.shape != (n, n) or not np.all(np.isfinite(R)):
+                raise ValueError('%s: matrix must be %d x %d finite numbers (one row per amplitude), got shape %s' % (where, n, n, R.shape))
+            big = float(np.max(np.abs(R))) if n else 0.0
+            if np.max(np.abs(R - R.T), initial=0.0) > 1e-12 * big:
+                i, j = np.unravel_index(np.argmax(np.abs(R - R.T)), R.shape)
+                raise ValueError('%s: matrix is not symmetric (entry (%d, %d) = %r, entry (%d, %d) = %r)' % (where, i, j, R[i, j], j, i, R[j, i]))
+            R = 0.5 * (R + R.T)                           # (the engine takes exact symmetry only)
+            ev = np.linalg.eigvalsh(R)
+            if ev[0] < -1e-10 * max(ev[-1], 0.0) or ev[-1] < 0.0:
+                raise ValueError('%s: matrix is indefinite (smallest eigenvalue %r, largest %r): the prior would be unbounded below'
+                                 % (where, float(ev[0]), float(ev[-1])))
+
+        def vector(key, default, scalar_ok):
+            v = spec.get(key)
+            if v is None:
+                return default
+            try:
+                v = np.asarray(v, dtype=np.float64)
+            except (TypeError, ValueError):
+                v = np.empty((0, 0))
+            if scalar_ok and v.ndim == 0:
+                v = np.full(n, float(v))
+            if v.shape != (n,) or not np.all(np.isfinite(v)):
+                raise ValueError('%s: %s must be %s%d finite numbers (one per amplitude), got %r' % (where, key, 'a number or ' if scalar_ok else '', n, spec.get(key)))
+            return v.copy()
+        mean = vector('mean', np.asarray(init, dtype=np.float64).copy(), False)
+        l1 = vector('l1', np.zeros(n), True)
+        if np.any(l1 < 0):
+            raise ValueError('%s: l1 weight %r is negative' % (where, float(l1.min())))
+        return dict(weight=float(w), R=R, mean=mean, l1=l1)
+
+    @staticmethod
+    def priorData(PDE, learntPrior, learnt):
+        """(No reference counterpart: `VarNet(..., learntPrior={stem: spec})`.)  The parsed priors, {stem: {'blocks': {key: block}}}
+        with a block = dict(weight, R, mean, l1) of `_prior_block`; `learnt`: {stem: the parsed registration of that vector, or
+        None}.  Stems: coef, source, field, bic, fluxBC.  A spec is a dict with the keys weight (alpha >= 0, default 0), matrix
+        ('identity', the default; 'difference'; or a symmetric positive semi-definite array), mean (default: the starting values)
+        and l1 (a number or one per entry, >= 0).  For the keyed vectors (field, bic, fluxBC) the spec is a dict by key -- {'diff':
+        spec, 'vel': spec} and so on -- each block built on its own and placed on the diagonal; a key left out gets a zero
+        block.  The unkeyed vectors have the one block None."""
+        if learntPrior is None:
+            return {}
+        stems = [lv.stem for lv in VarNet.LEARNT]
+        if not isinstance(learntPrior, dict):
+            raise ValueError('learntPrior must be a dict {stem: spec} with stems among %s, got %r' % (', '.join(stems), learntPrior))
+        out = {}
+        for stem, spec in learntPrior.items():
+            if stem not in stems:
+                raise ValueError('learntPrior: unknown stem %r (one of %s)' % (stem, ', '.join(stems)))
+            lv = VarNet.LEARNT[stems.index(stem)]
+            data = learnt.get(stem)
+            if data is None:
+                raise ValueError('learntPrior[%r]: this instance does not learn that vector (%s=...)' % (stem, lv.option))
+            init = np.asarray(data['init'], dtype=np.float64)
+            if lv.keyed is None:
+                out[stem] = {'blocks': {None: VarNet._prior_block('learntPrior[%r]' % stem, spec, init)}}
+                continue
+            keys = lv.keyed.keys
+            if not isinstance(spec, dict) or not spec or any(k not in keys for k in spec):
+                raise ValueError('learntPrior[%r] must be a dict by key {%r: spec, %r: spec}, got %r' % (stem, keys[0], keys[1], spec))
+            blocks, i0 = {}, 0
+            for key, n in zip(keys, (data[z] for z in lv.keyed.sizes)):
+                if key in spec:
+                    if n == 0:
+                        raise ValueError('learntPrior[%r][%r]: the PDE has no %s basis (ADPDE(..., %sBasis=[...]))' % (stem, key, key, key))
+                    blocks[key] = VarNet._prior_block('learntPrior[%r][%r]' % (stem, key), spec[key], init[i0:i0 + n])
+                i0 += n
+            out[stem] = {'blocks': blocks}
+        return out
+
+    @staticmethod
+    def priorArrays(lv, blocks, data):
+        """(weight, R or None, mean, l1 or None) the engine takes for the prior of the LEARNT row `lv` with the parsed `blocks` and
+        the vector's parsed registration `data`: the one block as it stands (the identity as None), the blocks of a keyed vector
+        times their weights on the diagonal under the weight 1."""
+        if lv.keyed is None:
+            b = blocks[None]
+            ident = np.array_equal(b['R'], np.eye(len(b['mean'])))
+            return b['weight'], None if ident else b['R'], b['mean'], b['l1'] if np.any(b['l1'] > 0) else None
+        sizes = [data[z] for z in lv.keyed.sizes]
+        J = sum(sizes)
+        R, mean, l1, i0 = np.zeros((J, J)), np.zeros(J), np.zeros(J), 0
+        for key, n in zip(lv.keyed.keys, sizes):
+            b = blocks.get(key)
+            if b is not None:
+                R[i0:i0 + n, i0:i0 + n] = b['weight'] * b['R']
+                mean[i0:i0 + n], l1[i0:i0 + n] = b['mean'], b['l1']
+            i0 += n
+        return (1.0 if np.any(R != 0.0) else 0.0), R, mean, l1 if np.any(l1 > 0) else None
+
+    def _register_prior(self, lv):
+        w, R, mean, l1 = self.priorArrays(lv, self.learntPrior[lv.stem]['blocks'], getattr(self, lv.attr))
+        self.engine.set_learnt_prior(lv.kind, w, None if w == 0.0 else R, None if w == 0.0 else mean, l1)
+
+    def priorPenalty(self):
+        """{stem: (Q, l1)} of every vector with a prior at the current values: Q = 1/2 weight d^T R d and l1 = sum_j lambda_j |a_j|.
+        Neither is part of the losses train() reports."""
+        return {lv.stem: self.engine.learnt_prior(lv.kind) for lv in self.LEARNT if lv.stem in self.learntPrior}
+
+    def setPriorWeight(self, stem, weight=None, l1=None):
+        """New weights for the prior of `stem` between train() calls (the Adam slots and the values stay): weight and l1 as in
+        learntPrior, None keeps what is registered; for a keyed vector each a number for every registered key or a dict by key."""
+        if stem not in self.learntPrior:
+            raise ValueError('setPriorWeight: no prior on %r (VarNet(learntPrior={%r: ...}))' % (stem, stem))
+        lv = next(v for v in self.LEARNT if v.stem == stem)
+        blocks = self.learntPrior[stem]['blocks']
+        for name, new in (('weight', weight), ('l1', l1)):
+            if new is None:
+                continue
+            per_key = isinstance(new, dict) and lv.keyed is not None
+            if per_key and any(k not in blocks for k in new):
+                raise ValueError('setPriorWeight: %s names a key without a prior block (registered: %s)' % (name, ', '.join(blocks)))
+            for key, b in blocks.items():
+                if per_key and key not in new:
+                    continue
+                where = 'setPriorWeight(%r)' % stem if key is None else 'setPriorWeight(%r)[%r]' % (stem, key)
+                b.update({k: v for k, v in self._prior_block(where, {name: new[key] if per_key else new, 'matrix': b['R'], 'mean': b['mean']},
+                                                             b['mean']).items() if k == name})
+        self._register_prior(lv)
 
     # -- causal time-slab weights (extension) ------------------------------------------------------
     @staticmethod
