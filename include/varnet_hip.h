@@ -235,6 +235,45 @@ int vn_set_observations(vn_engine* h, const float* X_dev, const float* q_dev, co
 int vn_set_obs_weight(vn_engine* h, double lambda);
 /* The unweighted misfit O of the last evaluation (synchronises the engine's stream).  VN_ESTATE without a registration. */
 int vn_get_obs_misfit(vn_engine* h, double* misfit);
+/* OPTIONAL, no reference counterpart: a hard-constraint ansatz.  The solution is written as
+ *     u(x,t) = A(x,t) + B(x,t) n(x,t)
+ * with n the network output, A carrying the Dirichlet and initial data and B vanishing where they must hold (A = IC(x), B = t:
+ * an exact initial state; A = g, B = 1 - x^2: exact Dirichlet walls).  The map is affine in n, so it is an elementwise stage
+ * (vn_ansatz.hip) after every forward and before every reverse pass: with the engine's value n_r and tangent nd_r = grad_x n . G_r
+ * of a row (G: gcoef, a normal, a pair direction, an observation direction)
+ *     u_r = A_r + B_r n_r,   ud_r = a_r + b_r n_r + B_r nd_r,      a_r = grad_x A . G_r,  b_r = grad_x B . G_r
+ * and everything in between (the row integrand, the polynomial terms, the loss weights, the seed kernels of every row set) sees
+ * u and ud as it does without an ansatz.  The time derivative needs no A_t: it is integrated by parts onto the test function.
+ * vn_set_ansatz registers the [n_k*integ_num] interior streams of `batch`, after vn_set_interior of that batch:
+ *   A_dev, a_dev, b_dev   device floats or NULL (zero);   B_dev   required.   All four NULL clears the registration.
+ * A new vn_set_interior clears it; the term, weight and map registrations keep it and it keeps them.  An unregistered batch:
+ * VN_ESTATE; a batch without interior rows: VN_EINVAL; a non-finite entry (checked on the device: the call may synchronise):
+ * VN_EINVAL.  The arrays are READ on every step: they must stay valid while registered.  A change invalidates the L-BFGS
+ * (f_k, g_k) and ring of that batch.
+ * An evaluation is ALL or NOTHING: when the batch has an ansatz, every registered row set (BC/IC rows, flux rows, pairs,
+ * observations) must have one too (vn_set_ansatz_rows), and the other way round -- else vn_grad, vn_train_*, vn_lbfgs_step and
+ * vn_eval_loss return VN_ESTATE and name what is missing: rows evaluated without the map would be a silent wrong answer.
+ * Routes: the generic route carries the stage around its seed kernel; a batch of the single-launch 8-wave route runs the
+ * two-pass sequence, and on both 8-wave sequences (two-pass, de-duplicated) the BC/IC rows leave the seeded reverse launch for
+ * the generic kernels, their partials appended to the step's own.  Refused with VN_EUNSUPPORTED: VN_KERNEL_FUSED (the 4-wave
+ * cross-check geometry), the layer-by-layer route and networks outside the generic kernels' range, vn_objective_f64 and
+ * vn_lbfgs_loss64 on an ansatz batch, a per-batch BC/IC copy (vn_set_batch_bic) next to BC/IC ansatz streams, and any learnt
+ * vector next to an ansatz (at vn_grad).  Without a registration nothing is launched, nothing is allocated and every result is
+ * bit for bit what it is without this call. */
+int vn_set_ansatz(vn_engine* h, int32_t batch, const float* A_dev, const float* B_dev, const float* a_dev, const float* b_dev);
+/* ... at the U unique points of the batch's de-duplication map, after vn_set_dedup of that batch: A and B [U], their spatial
+ * gradients [U, dim].  Au_dev, gAu_dev, gBu_dev may be NULL (zero); all four NULL clears the registration, and so does
+ * vn_set_dedup.  A batch without a map: VN_ESTATE; non-finite entries: VN_EINVAL.  A step on a batch that has a map and an ansatz
+ * but no point streams returns VN_ESTATE. */
+int vn_set_ansatz_points(vn_engine* h, int32_t batch, const float* Au_dev, const float* Bu_dev, const float* gAu_dev,
+                         const float* gBu_dev);
+/* ... on the engine's other row sets.  The row counts are those of the set's registration: nB of vn_set_bic, nF of
+ * vn_set_flux_bc, 2 nP of vn_set_periodic, n of vn_set_observations.  a_dev, b_dev are the derivatives of A and B along the
+ * set's own direction (normal, pair direction, observation direction); passing them for a set without directions (the BC/IC
+ * rows, pairs with gamma == 0, observations without dir) is VN_EINVAL.  All four NULL clears; registering the set again
+ * (vn_set_bic, vn_set_flux_bc, ...) drops its streams.  A set that is not registered: VN_ESTATE. */
+enum { VN_ANSATZ_BIC = 0, VN_ANSATZ_FLUX = 1, VN_ANSATZ_PERIODIC = 2, VN_ANSATZ_OBS = 3 };
+int vn_set_ansatz_rows(vn_engine* h, int32_t set, const float* A_dev, const float* B_dev, const float* a_dev, const float* b_dev);
 /* OPTIONAL, no reference counterpart: a polynomial reaction term for `batch`,
  *     c_t = div(kappa grad c) - v.grad c + s + rate(x,t) p(c),     p(c) = c1 c + c2 c^2 + c3 c^3
  * (first-order decay, Fisher-KPP, Allen-Cahn-type reactions).  The term sits on the source side: the row integrand of the weak

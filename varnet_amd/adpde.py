@@ -1,7 +1,7 @@
 """
 Advection-diffusion(-reaction) PDE container: `ADPDE(domain, diff, vel, source, timeDependent, tInterval,
 BCs, IC, cEx, MORvar, d_diff, reaction, nlflux, nldiff, periodic, sourceBasis, sourceAmp, diffBasis, diffAmp, d_diffBasis, velBasis,
-velAmp, bcBasis, bcAmp, icBasis, icAmp, fluxBasis, fluxAmp, robinBasis, robinAmp)` -- the reference's ADPDE.py:56-246 restated (plot helpers are out of scope).
+velAmp, bcBasis, bcAmp, icBasis, icAmp, fluxBasis, fluxAmp, robinBasis, robinAmp, ansatz)` -- the reference's ADPDE.py:56-246 restated (plot helpers are out of scope).
 
     c_t = div(diff D(c) grad c) - vel . grad c - div(w F(c)) + source + rate * p(c),    a * dc/dn + b * c = g  on each edge,
 
@@ -75,6 +75,14 @@ class ADPDE:
     Neumann indicator, b = 0, is allowed).  Jl + Jc <= 64.  Both are data of the boundary-flux rows (`VarNet(..., fluxBC=True)`);
     the amplitudes can be learnt from observations (`VarNet(..., learnFluxBC=...)`: flux boundary identification), without that
     the sums are part of the rows' label and coefficient.
+
+    ansatz={'A': f, 'B': f, 'dA': f, 'dB': f[, 'A_t': f, 'B_t': f, 'lapA': f, 'lapB': f]} imposes Dirichlet and initial data as
+    hard constraints: the solution is written as c = A + B N with N the network output, A carrying the data and B vanishing where
+    they must hold (A = IC(x), B = t: an exact initial state; A = g, B = 1 - x^2: exact Dirichlet walls on [-1, 1]).  'A' and 'B'
+    are callables f(x[, t]) returning a column, 'dA' and 'dB' their spatial gradients [n, dim]; both gradients are checked against
+    central differences at construction.  The four optional callables (time derivatives and Laplacians, columns) serve the strong
+    residual only.  The data then hold to rounding at every epoch and their loss weights can be 0.  Not with model-order
+    reduction.  None (the default): every condition is a penalty.
     """
     SRC_MAX = 64
     FLD_MAX = 32
@@ -84,7 +92,8 @@ class ADPDE:
     def __init__(self, domain, diff, vel, source=0.0, timeDependent=False, tInterval=None,
                  BCs=None, IC=None, cEx=None, MORvar=None, d_diff=None, reaction=None, nlflux=None, nldiff=None, periodic=None,
                  sourceBasis=None, sourceAmp=None, diffBasis=None, diffAmp=None, d_diffBasis=None, velBasis=None, velAmp=None,
-                 bcBasis=None, bcAmp=None, icBasis=None, icAmp=None, fluxBasis=None, fluxAmp=None, robinBasis=None, robinAmp=None):
+                 bcBasis=None, bcAmp=None, icBasis=None, icAmp=None, fluxBasis=None, fluxAmp=None, robinBasis=None, robinAmp=None,
+                 ansatz=None):
         # the reference ignores the `timeDependent` argument (ADPDE.py:108-109)
         timeDependent = tInterval is not None
 
@@ -390,6 +399,75 @@ class ADPDE:
             self.fluxBasis, self.fluxAmp = fluxBasis, fluxAmp
         if robinBasis is not None:
             self.robinBasis, self.robinAmp = robinBasis, robinAmp
+        # hard-constraint ansatz c = A + B N: the dict of callables; no attribute without one
+        if ansatz is not None:
+            self.ansatz = self._check_ansatz(ansatz, MORvar)
+
+    ANSATZ_KEYS = ('A', 'B', 'dA', 'dB')
+    ANSATZ_OPTIONAL = ('A_t', 'B_t', 'lapA', 'lapB')
+
+    def ansatz_values(self, key, X, ncol=1):
+        """The ansatz callable `key` at the rows X = [x, t] (t: time-dependent problems) as an fp64 [n, ncol] array."""
+        X = np.asarray(X, dtype=np.float64)
+        targ = [X[:, self.dim:self.dim + 1]] if self.timeDependent else []
+        v = np.asarray(self.ansatz[key](X[:, :self.dim], *targ), dtype=np.float64)
+        if v.size != X.shape[0] * ncol:
+            raise ValueError('ansatz[%r] must return %s per point, got shape %s for %d points'
+                             % (key, 'one value' if ncol == 1 else '%d values' % ncol, v.shape, X.shape[0]))
+        v = v.reshape(X.shape[0], ncol)
+        if not np.all(np.isfinite(v)):
+            raise ValueError('ansatz[%r] must be finite on the domain!' % key)
+        return v
+
+    def _check_ansatz(self, ansatz, MORvar):
+        if not isinstance(ansatz, dict):
+            raise ValueError('ansatz must be a dict of callables with the keys \'A\', \'B\', \'dA\', \'dB\' '
+                             '(and optionally \'A_t\', \'B_t\', \'lapA\', \'lapB\')!')
+        unknown = sorted(set(ansatz) - set(self.ANSATZ_KEYS) - set(self.ANSATZ_OPTIONAL), key=str)
+        if unknown:
+            raise ValueError('ansatz has unknown keys %s!' % unknown)
+        for k in self.ANSATZ_KEYS:
+            if not callable(ansatz.get(k)):
+                raise ValueError('ansatz[%r] must be a callable f(x[, t])!' % k)
+        for k in self.ANSATZ_OPTIONAL:
+            if k in ansatz and not callable(ansatz[k]):
+                raise ValueError('ansatz[%r] must be a callable f(x[, t]) (or left out)!' % k)
+        if MORvar is not None:
+            raise NotImplementedError('an ansatz with model-order reduction is not supported: parametric A and B are out of scope')
+        self.ansatz = dict(ansatz)                   # (ansatz_values reads it during the check below)
+        try:
+            return self._check_ansatz_gradients()
+        except Exception:
+            del self.ansatz
+            raise
+
+    def _check_ansatz_gradients(self):
+        # dA, dB against fp64 central differences of A, B at 64 seeded points of the domain: a wrong gradient would train another
+        # PDE without any sign of it
+        dim, lim = self.dim, np.asarray(self.domain.lim, dtype=np.float64).reshape(2, -1)
+        rng = np.random.default_rng(0)
+        x = lim[0] + (lim[1] - lim[0]) * rng.uniform(0.05, 0.95, (4096, dim))
+        inside = np.reshape(self.domain.isInside(x), -1).astype(bool)
+        x = (x[inside] if inside.sum() >= 64 else x)[:64]
+        X = x
+        if self.timeDependent:
+            t0, t1 = float(self.tInterval[0]), float(self.tInterval[1])
+            X = np.hstack([x, t0 + (t1 - t0) * rng.uniform(0.05, 0.95, (x.shape[0], 1))])
+        h = 1e-5 * np.maximum(lim[1] - lim[0], 1e-300)
+        for f, df in (('A', 'dA'), ('B', 'dB')):
+            g = self.ansatz_values(df, X, dim)
+            fd = np.zeros_like(g)
+            for d in range(dim):
+                Xp, Xm = X.copy(), X.copy()
+                Xp[:, d] += h[d]
+                Xm[:, d] -= h[d]
+                fd[:, d] = (self.ansatz_values(f, Xp)[:, 0] - self.ansatz_values(f, Xm)[:, 0]) / (2.0 * h[d])
+            scale = max(float(np.max(np.abs(fd))), float(np.max(np.abs(g))), 1e-300)
+            err = float(np.max(np.abs(g - fd))) / scale
+            if err > 1e-6:
+                raise ValueError('ansatz[%r] is not the spatial gradient of ansatz[%r]: it deviates from central differences by '
+                                 '%.3g of its size at 64 points of the domain (tolerance 1e-6)!' % (df, f, err))
+        return self.ansatz
 
     def _check_basis(self, name, ampName, basis, amp, MORvar, cap, shape_text, entry, hint='[...]'):
         """(checked entries, amplitudes) of one basis option, or (None, None) without one; ValueError names the option.  The basis is

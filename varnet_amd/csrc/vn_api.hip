@@ -1,6 +1,7 @@
 // C-ABI host layer of libvarnet_hip.so (see include/varnet_hip.h for the contract and the
 // reference call sites each entry point replaces).
 #include "vn_internal.h"
+#include "vn_ansatz.h"
 #include "vn_dedup.h"
 #include "vn_edge.h"
 #include "vn_lbfgs.h"
@@ -65,6 +66,15 @@ struct Term {
   double c[3] = {0.0, 0.0, 0.0};
 };
 
+// The streams of a hard-constraint ansatz u = A + B n on one row set (vn_ansatz.hip), caller-owned; B == nullptr: none registered.
+// Rows: a = grad_x A . G_r, b = grad_x B . G_r, [rows]; the unique points of a map: a = grad_x A, b = grad_x B, [U, dim].
+struct Ansatz {
+  const float* A = nullptr;
+  const float* B = nullptr;
+  const float* a = nullptr;
+  const float* b = nullptr;
+};
+
 struct Batch {
   const float* Input = nullptr;
   const float* gcoef = nullptr;
@@ -105,10 +115,14 @@ struct Batch {
   // per-test-function loss weights (vn_weights.hip): static (vn_set_tf_weights) or causal (vn_set_causal); as initialised: none
   VnWeightsReg wt;
   int* wt_own = nullptr;      // owned: the causal registration's slab ids and CSR, one allocation (wt.slab / wt.sptr / wt.sidx)
+  // hard-constraint ansatz (vn_ansatz.hip): the interior rows' streams (vn_set_ansatz) and those of the map's unique points
+  // (vn_set_ansatz_points); as initialised here: none
+  Ansatz az, azp;
 };
 
 inline bool has_terms(const Batch& b) { return b.react.on || b.nlflux.on || b.nldiff.on; }
 inline bool has_weights(const Batch& b) { return vn_weights_on(b.wt); }
+inline bool has_ansatz(const Batch& b) { return b.az.B != nullptr; }
 
 // How an engine computes its gradient, decided once by pick_route (vn_create).
 enum class Route {
@@ -227,7 +241,8 @@ struct vn_engine {
   float* gradbuf_int = nullptr;
   float* gradbuf = nullptr;
   float* lossbuf = nullptr;       // [4] for vn_eval_loss
-  float* partial = nullptr;       // [bwd_grid, P]
+  float* partial = nullptr;       // [partial_rows, P]; partial_rows = bwd_grid until an ansatz step appends its BC/IC rows' partials
+  long partial_rows = 0;
   int bwd_grid = 0, fwd_grid = 0;
 
   float *feN = nullptr, *fedNt = nullptr, *feW = nullptr;
@@ -284,6 +299,8 @@ struct vn_engine {
   const int* orowptr = nullptr;
   double olambda = 0.0;
   double* omisfit = nullptr;                      // device slot: the unweighted misfit O of the last evaluation
+  // hard-constraint ansatz (vn_set_ansatz_rows): the streams of the BC/IC rows and of the edge sets by VnEdgeId, caller-owned
+  Ansatz az_bic, az_edge[VN_EDGE_N];
   // the vectors learnt next to the parameters, by LearntId: the nine coefficients of inverse mode (vn_set_coef_learn),
   // which live on the device while they are learnt, and the engine-wide amplitudes of the batches' source bases
   // (vn_set_source_learn) and gcoef bases (vn_set_field_learn), of the BC/IC label bases (vn_set_bic_learn) and of the flux rows'
@@ -770,6 +787,126 @@ void clear_weights(Batch& b) {
   b.wt = VnWeightsReg();
 }
 
+// ---- hard-constraint ansatz u = A + B n (vn_ansatz.hip): the stages, in the order that file's header fixes ----
+// Fold of one row set right after its forward: (v, vd) = (n, nd) -> (u, ud); vd nullptr: a values-only set
+int ansatz_fold(vn_engine* h, const Ansatz& z, float* v, float* vd, long n) {
+  VnAnsatzRowArgs r{};
+  r.A = z.A; r.B = z.B; r.a = vd ? z.a : nullptr; r.b = vd ? z.b : nullptr; r.n = n; r.v = v; r.vd = vd;
+  HIPCHK(vn_ansatz_fold_launch(r, h->stream));
+  return VN_OK;
+}
+
+// Adjoint of one row set, last before its reverse pass: (v, vd) = (ubar, udbar) -> the seeds of (n, nd)
+int ansatz_adjoint(vn_engine* h, const Ansatz& z, float* v, float* vd, long n) {
+  VnAnsatzRowArgs r{};
+  r.B = z.B; r.b = vd ? z.b : nullptr; r.n = n; r.v = v; r.vd = vd;
+  HIPCHK(vn_ansatz_adjoint_launch(r, h->stream));
+  return VN_OK;
+}
+
+// The unique points of b's map: the record h->dd_uv after point_pass (fold), the gathered seeds (adjoint)
+VnAnsatzPointArgs ansatz_point_args(const vn_engine* h, const Batch& b) {
+  VnAnsatzPointArgs p{};
+  p.A = b.azp.A; p.B = b.azp.B; p.gA = b.azp.a; p.gB = b.azp.b; p.U = b.U; p.dim = h->cfg.dim;
+  p.pack = h->dd_uv; p.seed_u = h->dd_su; p.seed_g = h->dd_sg;
+  return p;
+}
+
+// The routes that carry the stage: the generic kernels serve the BC/IC rows of every ansatz step and the edge sets
+int ansatz_check_route(const vn_engine* h) {
+  if (h->route == Route::fused4)
+    return fail(VN_EUNSUPPORTED, "a hard-constraint ansatz is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry): its "
+                                 "single launch forms the BC/IC seeds itself; the generic and the 8-wave families carry it");
+  if (h->route != Route::layered && vn_net_in_kernel_range(h->net)) return VN_OK;
+  return fail(VN_EUNSUPPORTED, "a hard-constraint ansatz needs a network of the hand-written kernels (<= %d hidden layers, width <= %d, "
+              "<= %d inputs, one activation); this one (%d layers, widest %d, %d inputs%s) runs on the layer-by-layer route "
+              "or the deep fused kernel only", VN_KMAX_LAYERS, VN_KMAX_WIDTH, VN_KMAX_DIN, h->net.L, h->net.hmax,
+              h->net.d_in, h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+}
+
+// Non-finite entries of the streams of a registration, counted on the device (synchronises: registration only)
+int ansatz_check_finite(vn_engine* h, const char* who, const Ansatz& z, long n, long nd) {
+  int bad = 0;
+  auto check = [&](int* err_dev) {
+    hipError_t e = vn_ansatz_check_launch(z.A, n, err_dev, h->stream);
+    if (e == hipSuccess) e = vn_ansatz_check_launch(z.B, n, err_dev, h->stream);
+    if (e == hipSuccess) e = vn_ansatz_check_launch(z.a, nd, err_dev, h->stream);
+    if (e == hipSuccess) e = vn_ansatz_check_launch(z.b, nd, err_dev, h->stream);
+    return e;
+  };
+  if (int rc = count_on_device(h, check, &bad)) return rc;
+  if (bad) return fail(VN_EINVAL, "%s: %d non-finite entr%s in the ansatz streams", who, bad, bad == 1 ? "y" : "ies");
+  return VN_OK;
+}
+
+const char* const kAnsatzSet[] = {"the BC/IC rows (VN_ANSATZ_BIC)", "the boundary-flux rows (VN_ANSATZ_FLUX)",
+                                  "the periodic pairs (VN_ANSATZ_PERIODIC)", "the observations (VN_ANSATZ_OBS)"};
+
+// Before every evaluation of batch b: all of its row sets carry the map, or none does.  Without any registration: one pass over
+// five pointers, nothing else.
+int ansatz_check_eval(const vn_engine* h, const Batch& b, int batch) {
+  const bool on = has_ansatz(b);
+  const Ansatz* sets[1 + VN_EDGE_N] = {&h->az_bic, &h->az_edge[0], &h->az_edge[1], &h->az_edge[2]};
+  const long rows[1 + VN_EDGE_N] = {h->nB, h->es[0].count, h->es[1].count, h->es[2].count};
+  for (int i = 0; i < 1 + VN_EDGE_N; ++i) {
+    const bool reg = rows[i] > 0, has = sets[i]->B != nullptr;
+    if (on && reg && !has)
+      return fail(VN_ESTATE, "batch %d has a hard-constraint ansatz (vn_set_ansatz) but %s have no ansatz streams (vn_set_ansatz_rows): "
+                             "they would be evaluated on the bare network output", batch, kAnsatzSet[i]);
+    if (!on && has)
+      return fail(VN_ESTATE, "%s have ansatz streams (vn_set_ansatz_rows) but batch %d has no ansatz (vn_set_ansatz): its interior rows "
+                             "would be evaluated on the bare network output", kAnsatzSet[i], batch);
+  }
+  if (!on) return VN_OK;
+  if (b.Xu && !b.azp.B)
+    return fail(VN_ESTATE, "batch %d has a de-duplication map and a hard-constraint ansatz but no ansatz streams at the map's unique "
+                           "points (vn_set_ansatz_points)", batch);
+  if (b.biInput && h->az_bic.B)
+    return fail(VN_EUNSUPPORTED, "batch %d has its own copy of the BC/IC rows (vn_set_batch_bic) next to BC/IC ansatz streams "
+                                 "(vn_set_ansatz_rows), which belong to the rows of vn_set_bic", batch);
+  return VN_OK;
+}
+
+// The BC/IC rows of an ansatz step on the 8-wave sequences.  The seeded reverse launch forms their seeds from n - label, which
+// cannot express B (A + B n - label), so they leave it (f.nB = 0) for the generic kernels in the order run_generic shows: forward,
+// fold, the row-wise seed kernel with an empty interior set, ubar_b *= B_b, reverse pass -- gradient partials to `partial`
+// ([*nparts, P] on return), loss partials to `lp` ([*nlp, 3]).
+// h->partial with room for `rows` partials (an ansatz step of the two-pass sequence appends its BC/IC rows' to the launch's own)
+int grow_partial(vn_engine* h, long rows) {
+  if (rows <= h->partial_rows) return VN_OK;
+  float* p = nullptr;
+  HIPCHK(hipMalloc((void**)&p, (size_t)rows * h->net.P * sizeof(float)));
+  (void)hipFree(h->partial);                         // (waits for the launches in flight)
+  h->partial = p; h->partial_rows = rows;
+  return VN_OK;
+}
+
+inline int ansatz_bic_lossparts(const vn_engine* h) { return h->nB > 0 ? (int)((h->nB + 255) / 256) : 0; }
+inline int ansatz_bic_parts(const vn_engine* h) {               // workgroups of the rows' reverse pass, as edge_alloc sizes a set's
+  const long tiles = (h->nB + 31) / 32;
+  return (int)(tiles < h->ncu ? tiles : h->ncu);
+}
+
+int ansatz_bic_rows(vn_engine* h, const Batch& b, float* partial, float* lp, int* nparts, int* nlp) {
+  *nparts = 0; *nlp = 0;
+  if (h->nB <= 0) return VN_OK;
+  VnRows r{}, none{};
+  r.X = bi_x(h, b); r.G = nullptr; r.u = h->ub; r.ud = nullptr; r.n = h->nB;
+  HIPCHK(vn_generic_forward(h->net, h->theta, r, none, h->fwd_grid, h->stream));
+  if (int rc = ansatz_fold(h, h->az_bic, h->ub, nullptr, h->nB)) return rc;
+  VnSeedArgs s = seed_args(h, b);
+  s.n_k = 0; s.source = nullptr; s.feW = nullptr; s.react = 0;   // interior set empty: the BC/IC terms alone
+  s.ubar_b = h->ubar_b; s.part = lp;
+  const int bgrid = ansatz_bic_lossparts(h);
+  HIPCHK(vn_seed_launch(s, bgrid, h->stream));
+  if (int rc = ansatz_adjoint(h, h->az_bic, h->ubar_b, nullptr, h->nB)) return rc;
+  r.u = nullptr; r.ubar = h->ubar_b; r.udbar = nullptr;
+  const int grid = ansatz_bic_parts(h);
+  HIPCHK(vn_generic_backward(h->net, h->theta, r, none, partial, grid, h->stream));
+  *nparts = grid; *nlp = bgrid;
+  return VN_OK;
+}
+
 // Every launch of the 8-wave fused kernel: its global-memory stash (per workgroup; none for most instantiations) is sized here
 int fused8_launch(vn_engine* h, VnFusedArgs& f, int grid) {
   const long per = (long)(vn_fused16_stash_bytes(h->net) / sizeof(float));
@@ -901,9 +1038,14 @@ int edge_pass(vn_engine* h, int id, bool with_grad, VnEdgeSum* sum) {
   VnRows r{}, none{};
   r.X = e.X; r.G = e.G; r.u = e.buf[EB_U]; r.ud = deriv ? e.buf[EB_UD] : nullptr; r.n = e.rows;
   HIPCHK(vn_generic_forward(h->net, h->theta, r, none, h->fwd_grid, h->stream));
+  const Ansatz& z = h->az_edge[id];                  // hard-constraint ansatz: the seed kernel sees u = A + B n and its derivative
+  if (z.B)
+    if (int rc = ansatz_fold(h, z, r.u, r.ud, e.rows)) return rc;
   float* ubar = with_grad ? e.buf[EB_UBAR] : nullptr;
   float* udbar = with_grad && deriv ? e.buf[EB_UDBAR] : nullptr;
   HIPCHK(kEdge[id].seed(h, e, r.ud, ubar, udbar));
+  if (with_grad && z.B)
+    if (int rc = ansatz_adjoint(h, z, ubar, udbar, e.rows)) return rc;
   if (with_grad) {
     r.u = nullptr; r.ud = nullptr; r.ubar = ubar; r.udbar = udbar;
     HIPCHK(vn_generic_backward(h->net, h->theta, r, none, e.buf[EB_PARTIAL], e.grid, h->stream));
@@ -930,6 +1072,7 @@ void edge_drop(vn_engine* h, int id) {
   e.X = e.G = nullptr;
   lbfgs_invalidate(h);
   e.count = e.rows = 0;
+  h->az_edge[id] = Ansatz();                         // the rows' ansatz streams go with them (vn_set_ansatz_rows)
 }
 
 // Step 2, after the call's own argument checks: the edge passes run on the generic kernels, whatever route the interior term takes.
@@ -964,12 +1107,15 @@ int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst, con
   const int bgrid = (int)(((h->nB > 0 ? h->nB : 1) + 255) / 256);
   if (int rc = ensure(&h->losspart, &h->losspart_cap, (long)(sblk + bgrid) * 3)) return rc;
   HIPCHK(point_pass(h, b.Xu, b.U, nullptr, nullptr, h->dd_uv));
+  if (has_ansatz(b)) HIPCHK(vn_ansatz_points_fold_launch(ansatz_point_args(h, b), h->stream));
   VnDedupArgs a = dedup_args(h, b);
   a.lossVec = weights_lossvec(h, b, lossVec); a.part = h->losspart;          // loss only: no seeds
   if (int rc = terms_source_dedup(h, b, a)) return rc;
   HIPCHK(vn_dedup_seed_launch(a, sblk, h->stream));
   if (int rc = weights_stage(h, b, a.lossVec, VN_DEDUP_TFB, nullptr, a.part, false)) return rc;
   if (int rc = fused_forward(h, bi_x(h, b), nullptr, h->nB, h->ub, nullptr)) return rc;
+  if (has_ansatz(b))
+    if (int rc = ansatz_fold(h, h->az_bic, h->ub, nullptr, h->nB)) return rc;
   VnSeedArgs s = seed_args(h, b);
   // interior set empty: the BC/IC terms alone (Nrow, dNtrow and detJv are nullptr on a batch with a de-duplication map)
   s.n_k = 0; s.source = nullptr; s.feW = nullptr;
@@ -1000,6 +1146,10 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
   } else {
     HIPCHK(vn_generic_forward(h->net, h->theta, s0, s1, h->fwd_grid, h->stream));
   }
+  if (has_ansatz(b)) {                               // hard-constraint ansatz: (n, nd) -> (u, ud) before anything reads them
+    if (int rc = ansatz_fold(h, b.az, h->u, h->ud, s0.n)) return rc;
+    if (int rc = ansatz_fold(h, h->az_bic, h->ub, nullptr, h->nB)) return rc;
+  }
 
   const long nthreads = b.n_k > h->nB ? b.n_k : h->nB;
   const int grid = (int)(((nthreads > 0 ? nthreads : 1) + 255) / 256);      // an empty set still zeroes its partials
@@ -1014,6 +1164,10 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
     if (int rc = terms_seed_rows(h, b)) return rc;
   }
   if (int rc = weights_stage(h, b, a.lossVec, 256, nullptr, a.part, with_seeds)) return rc;
+  if (with_seeds && has_ansatz(b)) {                 // ... and last, the seeds of (u, ud) -> those of (n, nd)
+    if (int rc = ansatz_adjoint(h, b.az, h->ubar, h->udbar, s0.n)) return rc;
+    if (int rc = ansatz_adjoint(h, h->az_bic, h->ubar_b, nullptr, h->nB)) return rc;
+  }
   if (lossdst) {
     HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2, lossdst, h->stream,
                             VnOptArgs(), fx));
@@ -1093,7 +1247,10 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
 int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx) {
   const int grid = h->ncu, P = h->net.P;
   const int sgrid = (int)((b.n_k + 255) / 256);
-  if (int rc = ensure(&h->tp_losspart, &h->tp_losspart_cap, (long)(grid + sgrid) * 3)) return rc;
+  const bool az = has_ansatz(b);                     // hard-constraint ansatz: the BC/IC rows leave step 3 (ansatz_bic_rows)
+  if (int rc = ensure(&h->tp_losspart, &h->tp_losspart_cap, (long)(grid + sgrid + (az ? ansatz_bic_lossparts(h) : 0)) * 3)) return rc;
+  if (az)
+    if (int rc = grow_partial(h, grid + ansatz_bic_parts(h))) return rc;
   if (int rc = bic_forward_reduce(h, b)) return rc;
   float* lp = h->tp_losspart;
   VnFusedArgs f = fused_args(h, &b);
@@ -1102,6 +1259,8 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& 
   f.dir = -1; f.ostride = 1;
   f.mode = 1; f.out_u = h->u; f.out_ud = h->ud;
   if (int rc = fused8_launch(h, f, grid)) return rc;
+  if (az)
+    if (int rc = ansatz_fold(h, b.az, h->u, h->ud, f.nT)) return rc;
 
   VnSeedArgs a = seed_args(h, b);
   a.ubar = h->ubar; a.udbar = h->udbar;
@@ -1112,12 +1271,18 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& 
   HIPCHK(vn_seed_launch(a, sgrid, h->stream));
   if (int rc = terms_seed_rows(h, b)) return rc;
   if (int rc = weights_stage(h, b, a.lossVec, 256, nullptr, a.part, true)) return rc;
+  int bparts = 0, blp = 0;
+  if (az) {
+    if (int rc = ansatz_adjoint(h, b.az, h->ubar, h->udbar, f.nT)) return rc;
+    if (int rc = ansatz_bic_rows(h, b, h->partial + (long)grid * P, lp + (long)(grid + sgrid) * 3, &bparts, &blp)) return rc;
+  }
 
-  f.mode = 2; f.out_u = nullptr; f.out_ud = nullptr; f.seed_u = h->ubar; f.seed_ud = h->udbar; f.nB = h->nB;
+  f.mode = 2; f.out_u = nullptr; f.out_ud = nullptr; f.seed_u = h->ubar; f.seed_ud = h->udbar; f.nB = az ? 0 : h->nB;
   if (int rc = prof_start(h)) return rc;
   if (int rc = fused8_launch(h, f, grid)) return rc;
   if (int rc = prof_stop(h)) return rc;
-  HIPCHK(vn_reduce_launch(h->partial, grid, P, lp, grid + sgrid, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream, h->fuse, fx));
+  HIPCHK(vn_reduce_launch(h->partial, grid + bparts, P, lp, grid + sgrid + blp, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream,
+                          h->fuse, fx));
   return VN_OK;
 }
 
@@ -1131,12 +1296,18 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& 
 int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx) {
   const int grid = h->ncu, P = h->net.P;
   const int sblk = (int)((b.n_k + VN_DEDUP_TFB - 1) / VN_DEDUP_TFB);
-  float* lp = h->dd_losspart;                       // [grid + sblk][3]
+  const bool az = has_ansatz(b);                     // hard-constraint ansatz: the BC/IC rows leave step 4 (ansatz_bic_rows)
+  if (az) {
+    if (int rc = ensure(&h->dd_losspart, &h->dd_cap_lp, (long)(grid + sblk + ansatz_bic_lossparts(h)) * 3)) return rc;
+    if (int rc = ensure(&h->dd_partial, &h->dd_partial_cap, (long)(grid + ansatz_bic_parts(h)) * P)) return rc;
+  }
+  float* lp = h->dd_losspart;                       // [grid + sblk][3] (+ the BC/IC rows' of an ansatz step)
   if (int rc = bic_forward_reduce(h, b)) return rc;
   // vn_profile_*: HIP events around the formulation's whole kernel sequence (steps 1-4; the reduction stays outside as
   // in the row-wise step)
   if (int rc = prof_start(h)) return rc;
   HIPCHK(point_pass(h, b.Xu, b.U, nullptr, nullptr, h->dd_uv));
+  if (az) HIPCHK(vn_ansatz_points_fold_launch(ansatz_point_args(h, b), h->stream));
   VnDedupArgs a = dedup_args(h, b);
   a.stf = h->u; a.part = lp + (long)grid * 3;
   a.seed_u = h->dd_su; a.seed_g = h->dd_sg;
@@ -1146,6 +1317,11 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
   if (int rc = weights_stage(h, b, a.lossVec, VN_DEDUP_TFB, a.stf, a.part, false)) return rc;   // stf[k] *= omega_k before the gather
   HIPCHK(vn_dedup_gather_launch(a, h->stream));
   if (int rc = terms_gather_dedup(h, b, a)) return rc;
+  int bparts = 0, blp = 0;
+  if (az) {                                        // last before the reverse launch: the seeds of (u, grad u) -> those of (n, grad n)
+    HIPCHK(vn_ansatz_points_adjoint_launch(ansatz_point_args(h, b), h->stream));
+    if (int rc = ansatz_bic_rows(h, b, h->dd_partial + (long)grid * P, lp + (long)(grid + sblk) * 3, &bparts, &blp)) return rc;
+  }
   if (src_learnt(h, b)) {                          // source identification: a row's seed is stf[k] x its quadrature weight
     VnSrcGradArgs g{};
     g.stf = a.stf; g.feW = fe_w(h); g.feN = h->feN; g.phi = b.sb_phi; g.J = b.sb_J;
@@ -1165,9 +1341,11 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
   f.partial = h->dd_partial; f.losspart = lp;
   f.mode = 2; f.dir = -1; f.ostride = 1;
   f.seed_u = h->dd_su; f.seed_ud = nullptr;          // tangent seed 1
+  if (az) f.nB = 0;
   if (int rc = fused8_launch(h, f, grid)) return rc;
   if (int rc = prof_stop(h)) return rc;
-  HIPCHK(vn_reduce_launch(h->dd_partial, grid, P, lp, grid + sblk, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream, h->fuse, fx));
+  HIPCHK(vn_reduce_launch(h->dd_partial, grid + bparts, P, lp, grid + sblk + blp, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream,
+                          h->fuse, fx));
   return VN_OK;
 }
 
@@ -1380,6 +1558,7 @@ int vn_create(const vn_config* cfg, vn_engine** out) {
   if (a == hipSuccess) a = hipMalloc((void**)&h->gradbuf_int, (P + 4) * sizeof(float));
   if (a == hipSuccess) a = hipMalloc((void**)&h->lossbuf, 4 * sizeof(float));
   if (a == hipSuccess) a = hipMalloc((void**)&h->partial, (size_t)h->bwd_grid * P * sizeof(float));
+  if (a == hipSuccess) h->partial_rows = h->bwd_grid;
   if (a == hipSuccess) a = hipMalloc((void**)&h->feN, cfg->integ_num * sizeof(float));
   if (a == hipSuccess) a = hipMalloc((void**)&h->fedNt, cfg->integ_num * sizeof(float));
   if (a == hipSuccess) a = hipMalloc((void**)&h->feW, cfg->integ_num * sizeof(float));
@@ -1625,6 +1804,7 @@ int vn_set_interior(vn_engine* h, int32_t batch, const float* Input, const float
   const Batch fresh;
   b.react = fresh.react; b.nlflux = fresh.nlflux; b.nldiff = fresh.nldiff;             // ... and the three term setters
   clear_weights(b);                                                                    // ... and vn_set_tf_weights / vn_set_causal
+  b.az = Ansatz(); b.azp = Ansatz();                                                   // ... and vn_set_ansatz / vn_set_ansatz_points
   const long nT = n_k * h->cfg.integ_num;
   if (nT > h->work_rows) {
     long c0 = h->work_rows, c1 = h->work_rows, c2 = h->work_rows, c3 = h->work_rows;
@@ -1644,6 +1824,7 @@ int vn_set_dedup(vn_engine* h, int32_t batch, const float* Xu, int64_t U, const 
     return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
   lbfgs_invalidate(h, batch);
   Batch& b = h->batches[batch];
+  b.azp = Ansatz();                            // the ansatz streams at the previous map's points go with it (vn_set_ansatz_points)
   if (!Xu) {                                   // switch the formulation off for this batch
     b.Xu = nullptr; b.uid = nullptr; b.rowptr = nullptr; b.rowidx = nullptr; b.U = 0;
     return VN_OK;
@@ -2134,6 +2315,7 @@ int vn_set_bic(vn_engine* h, const float* biInput, const float* biLabel, int64_t
   // a steady problem has no initial condition (TFModel.py:646-650): rows behind bDof are never part of its loss
   h->nBreg = nB;
   h->bicB = nullptr; h->bicJ = 0;                    // the shared set's basis goes with it (vn_set_bic_basis)
+  h->az_bic = Ansatz();                              // ... and its ansatz streams (vn_set_ansatz_rows)
   if (!h->cfg.time_dependent) nB = bDof;
   h->biInput = biInput; h->biLabel = biLabel; h->nB = nB; h->bDof = bDof; h->biDimVal = biDimVal;
   lbfgs_invalidate(h);
@@ -2237,11 +2419,87 @@ int vn_get_obs_misfit(vn_engine* h, double* misfit) {
   return VN_OK;
 }
 
+// ---- hard-constraint ansatz (vn_ansatz.hip): the three registrations ----
+int vn_set_ansatz(vn_engine* h, int32_t batch, const float* A, const float* B, const float* a, const float* b_) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
+    return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
+  Batch& b = h->batches[batch];
+  lbfgs_invalidate(h, batch);
+  b.az = Ansatz();                                   // a call replaces the previous registration, also when it fails
+  if (!A && !B && !a && !b_) return VN_OK;
+  if (!B) return fail(VN_EINVAL, "vn_set_ansatz: B_dev is required (u = A + B n; all four NULL clears the registration)");
+  if (b.n_k <= 0) return fail(VN_EINVAL, "batch %d has no interior rows: no ansatz to apply", batch);
+  if (int rc = ansatz_check_route(h)) return rc;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  Ansatz z;
+  z.A = A; z.B = B; z.a = a; z.b = b_;
+  const long nT = b.n_k * h->cfg.integ_num;
+  if (int rc = ansatz_check_finite(h, "vn_set_ansatz", z, nT, nT)) return rc;
+  b.az = z;
+  return VN_OK;
+}
+
+int vn_set_ansatz_points(vn_engine* h, int32_t batch, const float* Au, const float* Bu, const float* gAu, const float* gBu) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
+    return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
+  Batch& b = h->batches[batch];
+  lbfgs_invalidate(h, batch);
+  b.azp = Ansatz();
+  if (!Au && !Bu && !gAu && !gBu) return VN_OK;
+  if (!b.Xu) return fail(VN_ESTATE, "vn_set_ansatz_points: batch %d has no de-duplication map (call vn_set_dedup first)", batch);
+  if (!Bu) return fail(VN_EINVAL, "vn_set_ansatz_points: Bu_dev is required (all four NULL clears the registration)");
+  if (h->cfg.dim > 3) return fail(VN_EINVAL, "vn_set_ansatz_points: the point record holds dim <= 3 gradient entries (dim = %d)", h->cfg.dim);
+  if (int rc = ansatz_check_route(h)) return rc;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  Ansatz z;
+  z.A = Au; z.B = Bu; z.a = gAu; z.b = gBu;
+  if (int rc = ansatz_check_finite(h, "vn_set_ansatz_points", z, b.U, b.U * h->cfg.dim)) return rc;
+  b.azp = z;
+  return VN_OK;
+}
+
+int vn_set_ansatz_rows(vn_engine* h, int32_t set, const float* A, const float* B, const float* a, const float* b_) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (set < VN_ANSATZ_BIC || set > VN_ANSATZ_OBS)
+    return fail(VN_EINVAL, "vn_set_ansatz_rows: set %d is none of VN_ANSATZ_BIC, VN_ANSATZ_FLUX, VN_ANSATZ_PERIODIC, VN_ANSATZ_OBS", set);
+  Ansatz& slot = set == VN_ANSATZ_BIC ? h->az_bic : h->az_edge[set - VN_ANSATZ_FLUX];
+  lbfgs_invalidate(h);
+  slot = Ansatz();
+  if (!A && !B && !a && !b_) return VN_OK;
+  // rows as the caller counts them, and whether the set has a direction to differentiate along
+  long rows = 0;
+  bool deriv = false;
+  if (set == VN_ANSATZ_BIC) rows = h->nBreg;
+  else { const EdgeSet& e = h->es[set - VN_ANSATZ_FLUX]; rows = e.count > 0 ? e.rows : 0; deriv = e.G != nullptr; }
+  if (rows <= 0) return fail(VN_ESTATE, "vn_set_ansatz_rows: %s are not registered", kAnsatzSet[set]);
+  if (!B) return fail(VN_EINVAL, "vn_set_ansatz_rows: B_dev is required (all four NULL clears the registration)");
+  if (!deriv && (a || b_))
+    return fail(VN_EINVAL, "vn_set_ansatz_rows: %s have no direction, so a_dev and b_dev (the derivatives of A and B along it) must be NULL",
+                kAnsatzSet[set]);
+  if (set == VN_ANSATZ_BIC)
+    for (size_t i = 0; i < h->batches.size(); ++i)
+      if (h->batches[i].biInput)
+        return fail(VN_EUNSUPPORTED, "vn_set_ansatz_rows(VN_ANSATZ_BIC) next to batch %zu's own copy of the BC/IC rows (vn_set_batch_bic): "
+                                     "the streams belong to the rows of vn_set_bic", i);
+  if (int rc = ansatz_check_route(h)) return rc;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  Ansatz z;
+  z.A = A; z.B = B; z.a = a; z.b = b_;
+  if (int rc = ansatz_check_finite(h, "vn_set_ansatz_rows", z, rows, rows)) return rc;
+  slot = z;
+  return VN_OK;
+}
+
 int vn_set_batch_bic(vn_engine* h, int32_t batch, const float* biInput, const float* biLabel) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
     return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
   if ((biInput == nullptr) != (biLabel == nullptr)) return fail(VN_EINVAL, "biInput and biLabel must be given together");
+  if (biInput && h->az_bic.B)
+    return fail(VN_EUNSUPPORTED, "vn_set_batch_bic next to BC/IC ansatz streams (vn_set_ansatz_rows): the streams belong to the rows of "
+                                 "vn_set_bic, a batch's own copy of the rows would be evaluated with them");
   h->batches[batch].biInput = biInput;
   h->batches[batch].biLabel = biLabel;
   h->batches[batch].bb_B = nullptr; h->batches[batch].bb_J = 0;     // the copy's basis goes with it (vn_set_bic_basis)
@@ -2269,7 +2527,11 @@ int vn_grad(vn_engine* h, int32_t batch) {
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   const Batch& b = h->batches[batch];
+  if (int rc = ansatz_check_eval(h, b, batch)) return rc;
   const LearntKind* learnt = learnt_any(h);
+  if (learnt && has_ansatz(b))
+    return fail(VN_EUNSUPPORTED, "learnt %s (%s) next to a hard-constraint ansatz (vn_set_ansatz, batch %d): the %s sums next to the "
+                                 "ansatz stage are not built", learnt->what, learnt->setter, batch, learnt->noun);
   if (!learnt) return grad_route(h, b);
   if (has_weights(b)) return learnt_weights_refusal(*learnt, batch);
   if (int rc = source_mix(h, b, batch)) return rc;
@@ -2297,7 +2559,8 @@ static int grad_route(vn_engine* h, const Batch& b) {
     // a reaction term lives in the row-wise seed kernel, a flux term and a diffusivity D(u) around it: the single-launch route
     // runs the two-pass sequence for such a batch
     // ... and so do per-test-function loss weights, applied after it, and learnt source amplitudes, whose sums read udbar
-    case Route::fused8: return has_terms(b) || has_weights(b) || src_learnt(h, b) || fld_learnt(h, b) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
+    // ... and a hard-constraint ansatz, an elementwise stage on either side of it
+    case Route::fused8: return has_terms(b) || has_weights(b) || has_ansatz(b) || src_learnt(h, b) || fld_learnt(h, b) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
     case Route::twopass: return run_twopass(h, b, h->gradbuf, fx);
   }
 }
@@ -2424,6 +2687,9 @@ int vn_lbfgs_step(vn_engine* h, int32_t batch, int32_t max_trials, double info[1
                                  "the parameters but are held constant for the gradient, so the search direction is not the gradient "
                                  "of the reported loss and an Armijo test on it means nothing; static weights (vn_set_tf_weights) work",
                 batch);
+  if (h->lb_loss64 && has_ansatz(h->batches[batch]))
+    return fail(VN_EUNSUPPORTED, "vn_lbfgs_step with vn_lbfgs_loss64 on batch %d, which has a hard-constraint ansatz (vn_set_ansatz): the "
+                                 "fp64 objective does not carry the ansatz stage", batch);
   HIPCHK(hipSetDevice(h->cfg.device));
   if (int rc = lbfgs_alloc(h)) return rc;
   const long P = h->net.P;
@@ -2509,6 +2775,7 @@ int vn_eval_loss(vn_engine* h, int32_t batch, double out[4], float* lossVec_dev)
   (void)hipGetLastError();   // a stale last-error of another library on this thread is not ours to report
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
+  if (int rc = ansatz_check_eval(h, h->batches[batch], batch)) return rc;
   if (int rc = source_mix(h, h->batches[batch], batch)) return rc;
   if (int rc = field_mix(h, h->batches[batch], batch)) return rc;
   if (int rc = bic_mix(h, h->batches[batch], batch)) return rc;
@@ -2532,6 +2799,9 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
                 "inputs, dim <= 3, one activation); this one (%d layers, widest %d, %d inputs, dim %d%s) is outside that range",
                 VN_KMAX_LAYERS, VN_KMAX_WIDTH, VN_KMAX_DIN, h->net.L, h->net.hmax, h->net.d_in, h->net.dim,
                 h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+  if (has_ansatz(h->batches[batch]) || h->az_bic.B || h->az_edge[0].B || h->az_edge[1].B || h->az_edge[2].B)
+    return fail(VN_EUNSUPPORTED, "vn_objective_f64 on batch %d next to a hard-constraint ansatz (vn_set_ansatz, vn_set_ansatz_rows): the "
+                                 "fp64 objective does not carry the ansatz stage", batch);
   HIPCHK(hipSetDevice(h->cfg.device));
   if (!theta_dev) {
     if (int rc = refresh_theta64(h)) return rc;

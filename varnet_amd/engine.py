@@ -68,6 +68,9 @@ _SIGS = {
                                       C.c_int64, C.c_double]),
     'vn_set_obs_weight': (C.c_int, [C.c_void_p, C.c_double]),
     'vn_get_obs_misfit': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    'vn_set_ansatz': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'vn_set_ansatz_points': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'vn_set_ansatz_rows': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'vn_set_reaction': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_nlflux': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_nldiff': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
@@ -139,6 +142,9 @@ _SIGS = {
 }
 
 ABI_SYMBOLS = tuple(_SIGS.keys())
+
+# the row sets of vn_set_ansatz_rows (VN_ANSATZ_*): the _keep key of the set's own registration
+ANSATZ_SETS = {'bic': (0, 'bic'), 'flux': (1, 'flux'), 'periodic': (2, 'periodic'), 'obs': (3, 'obs')}
 
 # the _keep keys of the three polynomial terms, in the order of the coefficient index (vn_set_coef_learn)
 COEF_TERMS = ('react', 'nlflux', 'nldiff')
@@ -413,13 +419,14 @@ class VNEngine:
         self._keep[('int', batch)] = (Input, gcoef, source, detJv, Nr, dNr)
         self._ck(self.lib.vn_set_interior(self.h, batch, _ptr(Input), _ptr(gcoef), _ptr(source), n_k,
                                           _ptr(detJv), detJ_s, _ptr(Nr), _ptr(dNr)))
-        for key in ('react', 'nlflux', 'nldiff', 'tfw', 'causal', 'srcbasis', 'fldbasis', 'bicbasis'):   # vn_set_interior cleared the
+        for key in ('react', 'nlflux', 'nldiff', 'tfw', 'causal', 'srcbasis', 'fldbasis', 'bicbasis', 'ansatz', 'ansatzpts'):   # vn_set_interior cleared the
             self._keep.pop((key, batch), None)      # batch's three polynomial terms, its per-test-function loss weights, its source
-                                                    # and field bases and the basis of its own BC/IC copy
+                                                    # and field bases, the basis of its own BC/IC copy and its ansatz streams
 
     def set_dedup(self, batch, Xu=None, uid=None, rowptr=None, rowidx=None):
         """Register (or, with Xu=None, clear) the de-duplicated formulation of `batch`."""
         t = self.torch
+        self._keep.pop(('ansatzpts', batch), None)   # vn_set_dedup clears the ansatz streams at the previous map's points
         if Xu is None:
             self._keep.pop(('dd', batch), None)
             self._ck(self.lib.vn_set_dedup(self.h, batch, None, 0, None, None, None))
@@ -442,6 +449,7 @@ class VNEngine:
 
     def set_bic(self, biInput, biLabel, bDof, biDimVal):
         self._bic_key = None
+        self._keep.pop(('ansatzrows', 'bic'), None)   # vn_set_bic drops the rows' ansatz streams
         self._keep.pop(('bicbasis', -1), None)     # vn_set_bic clears the shared set's basis
         if biInput is None or len(biInput) == 0:
             self._keep['bic'] = None
@@ -468,6 +476,7 @@ class VNEngine:
     def _set_edge(self, key, fn, tensors, *scalars):
         """One registration call of an edge row set (vn_edge.h): fn(h, pointers of `tensors`, *scalars).  tensors None clears the
         set; else the device tensors are kept alive under `key` in place of the previous registration's."""
+        self._keep.pop(('ansatzrows', key), None)    # a registration of the set drops its ansatz streams (edge_drop)
         if tensors is None:
             self._keep[key] = None
             self._ck(fn(self.h, *[None] * (len(fn.argtypes) - 1 - len(scalars)), *scalars))
@@ -529,6 +538,58 @@ class VNEngine:
         assert wgt is None or wgt.shape[0] == nO, (tuple(wgt.shape), nO)
         assert (rowptr.numel() == nO + 1) if rowptr is not None else (n == nO), (n, nO)
         self._set_edge('obs', self.lib.vn_set_observations, (X, q, dir, rowptr, value, wgt), n, nO, float(weight))
+
+    def _set_ansatz(self, key, fn, index, streams, shapes):
+        """One registration of ansatz streams (vn_ansatz.hip): fn(h, index, A, B, a, b).  streams = (A, B, a, b), each None or
+        an array of the matching entry of `shapes` (None: length unknown here); all None clears.  The device tensors are kept
+        alive under `key` in place of the previous registration's."""
+        t = self.torch
+        dev = []
+        for x, shape in zip(streams, shapes):
+            if x is None:
+                dev.append(None)
+                continue
+            x = self.dev(x if isinstance(x, t.Tensor) else np.asarray(x))
+            # the ABI carries pointers only: the lengths the kernels rely on are checked here
+            if shape is not None:
+                if x.numel() != int(np.prod(shape)):
+                    raise ValueError('ansatz stream of %d entries where %s are registered' % (x.numel(), tuple(shape)))
+                x = x.reshape(shape)
+            dev.append(x.contiguous())
+        old = self._keep.pop(key, None)
+        try:
+            self._ck(fn(self.h, int(index), *[_ptr(x) for x in dev]))
+        finally:
+            del old           # the engine dropped the previous registration before checking this one
+        if any(x is not None for x in dev):
+            self._keep[key] = tuple(dev)
+
+    def set_ansatz(self, batch, A=None, B=None, a=None, b=None):
+        """Register (or, with all None, clear) the hard-constraint ansatz u = A + B n on the interior rows of `batch`
+        (vn_set_ansatz), after set_interior of that batch: one value per interior row each; a = grad_x A . gcoef and
+        b = grad_x B . gcoef with the very gcoef of set_interior.  A, a, b may be None (zero); B is required."""
+        kept = self._keep.get(('int', batch))
+        n = None if kept is None else (int(kept[0].shape[0]),)
+        self._set_ansatz(('ansatz', batch), self.lib.vn_set_ansatz, batch, (A, B, a, b), (n, n, n, n))
+
+    def set_ansatz_points(self, batch, A=None, B=None, gA=None, gB=None):
+        """... at the unique points of the de-duplication map of `batch` (vn_set_ansatz_points), after set_dedup: A, B [U] and
+        their spatial gradients gA, gB [U, dim]."""
+        kept = self._keep.get(('dd', batch))
+        U = None if kept is None else int(kept[0].shape[0])
+        n, g = (None, None) if U is None else ((U,), (U, self.dim))
+        self._set_ansatz(('ansatzpts', batch), self.lib.vn_set_ansatz_points, batch, (A, B, gA, gB), (n, n, g, g))
+
+    def set_ansatz_rows(self, which, A=None, B=None, a=None, b=None):
+        """... on one of the engine's other row sets (vn_set_ansatz_rows): which in 'bic', 'flux', 'periodic', 'obs'; one value
+        per row of the set's registration; a, b the derivatives of A, B along the set's own direction (None for a set without
+        directions)."""
+        if which not in ANSATZ_SETS:
+            raise ValueError('ansatz rows: %r is none of %s' % (which, sorted(ANSATZ_SETS)))
+        index, key = ANSATZ_SETS[which]
+        kept = self._keep.get(key)
+        n = None if not kept else (int(kept[0].shape[0]),)
+        self._set_ansatz(('ansatzrows', key), self.lib.vn_set_ansatz_rows, index, (A, B, a, b), (n, n, n, n))
 
     def set_obs_weight(self, weight):
         """lambda of the observation term, without re-registering (vn_set_obs_weight)."""

@@ -622,6 +622,8 @@ class ManageTrainData:
                 eng.set_interior(self.engine_batch(mb, bi), pick(d['Input']), pick(d['gcoef']), pick(d['source']),
                                  n_k=n1 - n0, detJ=self.detJ if detJ is None else detJ,
                                  N_rows=pick(d.get('N_rows')), dNt_rows=pick(d.get('dNt_rows')))
+                if d.get('az') is not None and n1 > n0:             # the ansatz streams of these rows (vn_set_ansatz)
+                    eng.set_ansatz(self.engine_batch(mb, bi), *[pick(t) for t in d['az']])
                 if d.get('reactCoef') is not None and n1 > n0:      # the reaction term of these rows (vn_set_reaction)
                     eng.set_reaction(self.engine_batch(mb, bi), pick(d.get('rate')), d['reactCoef'])
                 if d.get('phi') is not None and n1 > n0:            # the flux term of these rows (vn_set_nlflux)
@@ -774,10 +776,17 @@ class ManageTrainData:
                 if key not in cache:
                     blk = d['Input_host'][n0 * q:n1 * q]
                     first, uid, rowptr, rowidx = unique_points(blk, fd.feDim, fd.hVec, getattr(vn.engine, 'device', None))
-                    cache[key] = (vn.engine.dev(blk[first]), uid, rowptr, rowidx)
-                Xu, uid, rowptr, rowidx = cache[key]
+                    pts = None
+                    if getattr(vn.PDE, 'ansatz', None) is not None:     # A, B and their gradients at the unique points
+                        Xp = np.asarray(blk[first], dtype=np.float64)[:, :fd.feDim]
+                        pts = tuple(vn.engine.dev(vn.PDE.ansatz_values(k, Xp, n)) for k, n in
+                                    (('A', 1), ('B', 1), ('dA', vn.dim), ('dB', vn.dim)))
+                    cache[key] = (vn.engine.dev(blk[first]), uid, rowptr, rowidx, pts)
+                Xu, uid, rowptr, rowidx, pts = cache[key]
                 # not applicable was decided above; an engine error here is a real failure and propagates
                 vn.engine.set_dedup(self.engine_batch(mb, bi), Xu, uid, rowptr, rowidx)
+                if pts is not None:
+                    vn.engine.set_ansatz_points(self.engine_batch(mb, bi), *pts)
                 total += Xu.shape[0]
         self._dd_cache = cache
         self.dedup_on = True
@@ -805,6 +814,8 @@ class ManageTrainData:
             return
         d = self.mor[mb]
         eng.set_bic(d['biInput'], d['biLabel'], self.bDofsum, self.biDimVal)
+        if d.get('az_bic') is not None:           # the ansatz streams of these rows (vn_set_ansatz_rows)
+            eng.set_ansatz_rows('bic', *d['az_bic'])
         if d.get('bicB') is not None:             # the basis of these labels (vn_set_bic_basis, the shared set)
             eng.set_bic_basis(-1, d['bicB'])
         eng._bic_key = (key, mb)
@@ -901,6 +912,19 @@ class VarNet:
                                           'assembled once, for all parameter batches, and carry no parameter inputs')
             self._check_obs_weight(1.0 if obsWeight is None else obsWeight)
 
+        # ADPDE(..., ansatz={...}) (extension; no reference counterpart): the hard-constraint ansatz c = A + B N; what it does not
+        # combine with is refused here, one sentence each
+        if getattr(PDE, 'ansatz', None) is not None:
+            if isinstance(processors, (list, tuple)) and len(processors) > 1:
+                raise NotImplementedError('an ansatz with towers is not supported: the shards of the ansatz streams per rank are '
+                                          'not built')
+            if lbfgsLoss64:
+                raise NotImplementedError('an ansatz with lbfgsLoss64=True is not supported: the fp64 objective does not carry the '
+                                          'ansatz stage')
+            for opt, (val, _, _) in learnt.items():
+                if val is not None:
+                    raise NotImplementedError('an ansatz with %s is not supported: the sums of a learnt vector next to the ansatz '
+                                              'stage are not built' % opt)
         # learnCoef=..., learnSource=..., learnField=..., learnBic=... (extensions; no reference counterpart): inverse mode, source,
         # field and boundary data identification -- the masked polynomial coefficients of the PDE's reaction / flux / diffusivity,
         # the masked amplitudes of its source basis, those of its diffusivity and velocity bases and those of its Dirichlet and
@@ -991,6 +1015,15 @@ class VarNet:
         self._rng = np.random.default_rng(12345)
         self.engine = self._make_engine(processors)
         self.engine.init_params(seed=0)
+        if getattr(PDE, 'ansatz', None) is not None:
+            if self.world > 1:
+                raise NotImplementedError('an ansatz with towers is not supported: the shards of the ansatz streams per rank are '
+                                          'not built')
+            from .engine import VN_KERNEL_LAYERED
+            if hasattr(self.engine, 'kernel_path') and self.engine.kernel_path()[0] == VN_KERNEL_LAYERED:
+                raise NotImplementedError('an ansatz on the layer-by-layer route is not supported: the network %s lies outside the '
+                                          'hand-written kernels that run the ansatz stage\'s BC/IC and edge passes'
+                                          % (list(layerWidth),))
         if self.lbfgsLoss64:
             self.engine.lbfgs_loss64(True)      # refused (VNError) where the fp64 objective is
         # tower gradient SUM (TFModel.py:342-377): by default an RCCL communicator inside the engine, so a
@@ -1027,6 +1060,8 @@ class VarNet:
             r = self.fluxRows
             if r['X'].shape[0] > 0:
                 self.engine.set_flux_bc(r['X'], r['normal'], r['coef'], r['label'], fd.biDimVal)
+                if getattr(self.PDE, 'ansatz', None) is not None:       # u and its normal derivative under the ansatz
+                    self.engine.set_ansatz_rows('flux', *self._ansatz_rows(r['X'], r['normal']))
                 if r.get('basis') is not None:        # learnt flux and Robin amplitudes: the engine mixes coef and label itself
                     self.engine.set_fluxbc_basis(r['basis'], r['J_flux'])
         if getattr(self.PDE, 'periodic', None) is not None:
@@ -1035,12 +1070,16 @@ class VarNet:
             self.periodicRows = self.periodicTrainData()
             r = self.periodicRows
             self.engine.set_periodic(r['X'], r['dir'], self.periodicDeriv, fd.biDimVal)
+            if getattr(self.PDE, 'ansatz', None) is not None:
+                self.engine.set_ansatz_rows('periodic', *self._ansatz_rows(r['X'], r['dir'] if self.periodicDeriv > 0 else None))
         if self.obsRows is not None:
             # fixed for the whole run and replicated in every feed and on every rank like the Dirichlet rows (optimal re-draws leave
             # them alone): registered once; a network outside the kernels that run the pass is refused here, with the engine's sentence
             r = self.obsRows
             self.engine.set_observations(r['X'], r['value'], q=r['q'], dir=r['dir'], rowptr=r['rowptr'], wgt=r['wgt'],
                                          weight=self.obsWeight / self.world)
+            if getattr(self.PDE, 'ansatz', None) is not None:
+                self.engine.set_ansatz_rows('obs', *self._ansatz_rows(r['X'], r['dir']))
         for lv in self.LEARNT:
             # the engine owns a learnt vector from here on: every batch registered later reads the nine coefficients from its device
             # vector, and carries the basis streams of the source [J, nT], the field [J, nT, dim] and the BC/IC rows [J, nB]; those of
@@ -2270,6 +2309,17 @@ class VarNet:
         return biArg, inpArg, np.reshape(np.asarray(inpNN, dtype=float), [1, len(inpNN)])
 
     # -- device-resident data -----------------------------------------------------------------
+    def _ansatz_rows(self, X, G=None):
+        """The four streams (A, B, a, b) of the ansatz c = A + B N at the rows X in fp64 (uploaded as fp32): a = grad_x A . G and
+        b = grad_x B . G along the rows' directions G [n, dim]; G None: a set without directions (a = b = None)."""
+        PDE, dim = self.PDE, self.dim
+        X = np.asarray(X, dtype=np.float64)
+        A, B = PDE.ansatz_values('A', X)[:, 0], PDE.ansatz_values('B', X)[:, 0]
+        if G is None:
+            return A, B, None, None
+        G = np.asarray(G, dtype=np.float64).reshape(-1, dim)
+        return A, B, (PDE.ansatz_values('dA', X, dim) * G).sum(1), (PDE.ansatz_values('dB', X, dim) * G).sum(1)
+
     def _assemble(self, Input, biInput, biDof, batch, MORdiscArg):
         """Host fp64 assembly of one MOR batch -> dict of device tensors (VarNet.py:778-857)."""
         fd, eng = self.fixData, self.engine
@@ -2316,6 +2366,12 @@ class VarNet:
             # gcoef = kappa*dNx + v*N  (VarNet.py:837) with the period tables broadcast over test functions
             gcoef = (diff.reshape(nt, q, 1) * fd.dNx[None, :, :] +
                      vel.reshape(nt, q, dim) * fd.N[None, :, None]).reshape(nt * q, dim)
+        az = az_bic = None
+        if getattr(self.PDE, 'ansatz', None) is not None:
+            # the ansatz streams beside gcoef, in fp64, contracted with the very gcoef that is uploaded (with D(u): kappa dN/dx alone;
+            # psi reads the transformed u, so nothing else moves); the BC/IC rows have no direction
+            az = tuple(eng.dev(v) for v in self._ansatz_rows(Input, gcoef))
+            az_bic = tuple(None if v is None else eng.dev(v) for v in self._ansatz_rows(biInput))
         fldG = None
         if self.fldLearn is not None:
             # G_j = chi_j dN/dx (diffusivity streams, first) or omega_j N (velocity streams): [J, nT, dim], stream-major, evaluated
@@ -2351,6 +2407,7 @@ class VarNet:
         slab = self._slab_tensor(Input) if self.causal is not None else None   # (time column dim: the same ids for every MOR batch)
         return dict(Input=eng.dev(Input), Input_host=Input, gcoef=eng.dev(gcoef), rate=rate, reactCoef=reactCoef, slab=slab,
                     phi=phi, nlfluxCoef=nlfluxCoef, psi=psi, nldiffCoef=nldiffCoef, srcphi=srcphi, fldG=fldG, bicB=bicB,
+                    az=az, az_bic=az_bic,
                     source=eng.dev(src.reshape(-1)) if self.lossOpt['isSource'] else None,
                     biInput=eng.dev(biInput), biLabel=eng.dev(biLabel.reshape(-1)),
                     N_rows=N_rows, dNt_rows=dNt_rows,
@@ -2410,11 +2467,17 @@ class VarNet:
                 'the controller of forked towers and holds neither.  Build the instance with one processor (or call it on a '
                 'rank of a launched job) to evaluate in double precision -- an fp32 result is never returned in its place' % what)
 
+    def _refuse_fp64_on_ansatz(self, what):
+        if getattr(self.PDE, 'ansatz', None) is not None:
+            raise NotImplementedError('%s with an ansatz: the fp64 objective does not carry the ansatz stage -- an fp32 result is '
+                                      'never returned in its place' % what)
+
     def splitLoss(self, tData, W=None, fp64=False):
         """BC, IC and variational loss summed over MOR batches (VarNet.py:1053-1090).  fp64=True: the components (and the loss
         field) from the device's double-precision evaluation of the same objective (VNEngine.objective64)."""
         if fp64:
             self._refuse_fp64_on_towers('splitLoss(fp64=True)')
+            self._refuse_fp64_on_ansatz('splitLoss(fp64=True)')
         ekw = {'fp64': True} if fp64 else {}
         if W is None:
             W = np.eye(3)
@@ -2453,6 +2516,7 @@ class VarNet:
             'fp32', 'fp64' the summed components themselves, 'batches' the number of mini-batches.
         Diagnostic only: nothing in train() calls it, and it leaves parameters and optimizer state as they are."""
         self._refuse_fp64_on_towers('precisionReport')
+        self._refuse_fp64_on_ansatz('precisionReport')
         if self.world > 1:
             raise NotImplementedError('precisionReport compares one rank\'s step with its fp64 evaluation: run it on one rank')
         if tData is None:
@@ -2647,6 +2711,9 @@ class VarNet:
         if batchNum is None and batchLen is None and shuffleData:
             warnings.warn('shuffling data is possible for batch-optimization, setting \'shuffleData\' to False!')
             shuffleData = False
+        if shuffleData and getattr(self.PDE, 'ansatz', None) is not None:
+            raise NotImplementedError('an ansatz with shuffleData=True is not supported: a shuffle permutes the BC/IC rows per feed '
+                                      '(a per-batch copy), and the ansatz streams belong to the rows as they were registered')
         argDict = {k: v for k, v in locals().items() if k != 'self'}
 
         if not addTrainPts and np.abs(suppFactor - 1.0) > 1.e-15:
@@ -2874,10 +2941,16 @@ class VarNet:
                 # the values in the engine's scale (vn_get_*: the nine coefficients, the J source amplitudes, the J field amplitudes
                 # with the diffusivity streams first); their Adam slots have no entry point and restart from zero
                 out[lv.key] = np.asarray(getattr(self.engine, 'get_' + lv.engine)(), dtype=np.float64)
+        if getattr(self.PDE, 'ansatz', None) is not None:
+            out['ansatz'] = np.int64(1)                              # the parameters are those of N in c = A + B N
         return out
 
     def restore_arrays(self, arrays):
         """Inverse of `checkpoint_arrays`: load {TF variable name: array} into the engine."""
+        has = getattr(self.PDE, 'ansatz', None) is not None
+        if ('ansatz' in arrays) != has:
+            raise ValueError('checkpoint %s an ansatz (c = A + B N) but the PDE of this model %s: the parameters of the one are not '
+                             'a solution of the other!' % (('was trained with', 'has none') if not has else ('was trained without', 'has one')))
         slot = ('RMSProp_1', 'RMSProp') if str(self.optimizer).lower() == 'rmsprop' else ('Adam', 'Adam_1')
         th, m, v, fan = [], [], [], self.inpDim
         for name, h in zip(self._var_names(), self.layerWidth + [1]):
@@ -3178,7 +3251,11 @@ class VarNet:
             else:
                 cols, _, _ = self._mor_columns(batch, Input.shape[0])
                 Input = np.hstack([Input, cols])
-        return self.engine.forward(Input).cpu().numpy().astype(np.float64).reshape(-1, 1)
+        N = self.engine.forward(Input).cpu().numpy().astype(np.float64).reshape(-1, 1)
+        if getattr(PDE, 'ansatz', None) is not None:                 # the constrained solution A + B N
+            Xs = np.asarray(Input, dtype=np.float64)[:, :fd.feDim]
+            return PDE.ansatz_values('A', Xs) + PDE.ansatz_values('B', Xs) * N
+        return N
 
     def residual(self, Input=None, tDiscIND=None, batch=None, fp64=False):
         """
@@ -3191,6 +3268,21 @@ class VarNet:
             return self._towers.call('residual', Input, tDiscIND, batch, fp64)
         dim, PDE, fd = self.dim, self.PDE, self.fixData
         td = PDE.timeDependent
+        az = getattr(PDE, 'ansatz', None)
+        if az is not None:
+            # with c = A + B N the strong residual is composed from one forward_grad and one residual call with zero source:
+            # R(c) = B R0(N) + [-A_t + kappa Lap A - (v - grad kappa) . grad A] + N [-B_t + kappa Lap B - (v - grad kappa) . grad B]
+            #        + 2 kappa grad B . grad N + s
+            need = [k for k in (('A_t', 'B_t') if td else ()) + ('lapA', 'lapB') if k not in az]
+            if need:
+                raise NotImplementedError('the strong residual of a PDE with an ansatz needs ansatz[%s] (the time derivatives and '
+                                          'Laplacians of A and B): residual() and smpScheme=\'optimal\' are not available without them'
+                                          % ', '.join(repr(k) for k in need))
+            if any(getattr(PDE, k, None) is not None for k in ('reaction', 'nlflux', 'nldiff')):
+                raise NotImplementedError('the strong residual of a PDE with an ansatz and a polynomial term is not built')
+            if fp64:
+                raise NotImplementedError('residual(fp64=True) with an ansatz: the fp64 composition is not built -- an fp32 result '
+                                          'is never returned in its place')
         elemSize = np.prod(fd.hVec)
         nb = fd.MORbatchNum
         if batch is not None:
@@ -3230,9 +3322,25 @@ class VarNet:
                 rkw['nlflux'] = (w_rows, cur['nlflux'] if cur else PDE.nlfluxCoef, divw_rows)
             if getattr(PDE, 'nldiff', None) is not None:             # div(kappa D(u) grad u); the advection stays v . grad u
                 rkw['nldiff'] = cur['nldiff'] if cur else PDE.nldiffCoef
-            u, r = self.engine.residual(Inp, diff, vel, src, diff_dx, fp64=fp64, **rkw)
-            cApp = u.cpu().numpy().astype(np.float64).reshape(-1, 1)
-            resVec = r.cpu().numpy().astype(np.float64).reshape(-1, 1)
+            if az is not None:
+                n = Inp.shape[0]
+                _, r0 = self.engine.residual(Inp, diff, vel, np.zeros(n), diff_dx)
+                N, gN = self.engine.forward_grad(Inp)
+                f64 = lambda a, cols: np.asarray(a.cpu().numpy() if hasattr(a, 'cpu') else a, dtype=np.float64).reshape(n, cols)
+                r0, N, gN = f64(r0, 1), f64(N, 1), f64(gN, dim)
+                kap, w = f64(diff, 1), f64(vel, dim) - f64(diff_dx, dim)
+                Xs = np.asarray(Input, dtype=np.float64)[:, :fd.feDim]
+                val = lambda k, cols=1: PDE.ansatz_values(k, Xs, cols)
+                A, B, dA, dB = val('A'), val('B'), val('dA', dim), val('dB', dim)
+                At, Bt = (val('A_t'), val('B_t')) if td else (0.0, 0.0)
+                resVec = (B * r0 + (-At + kap * val('lapA') - (w * dA).sum(1, keepdims=True))
+                          + N * (-Bt + kap * val('lapB') - (w * dB).sum(1, keepdims=True))
+                          + 2.0 * kap * (dB * gN).sum(1, keepdims=True) + f64(src, 1))
+                cApp = A + B * N
+            else:
+                u, r = self.engine.residual(Inp, diff, vel, src, diff_dx, fp64=fp64, **rkw)
+                cApp = u.cpu().numpy().astype(np.float64).reshape(-1, 1)
+                resVec = r.cpu().numpy().astype(np.float64).reshape(-1, 1)
             if PDE.cEx is not None:
                 err += uf.l2Err(cEx, cApp)
             res += np.sqrt(np.sum(resVec ** 2) * elemSize)
