@@ -19,7 +19,7 @@ if echo "$extra" | grep -q "VN_STAMPS\|VN_FIXSTAMPS\|VN_ABL_"; then
   src=$tmp/varnet_amd/csrc/vn_fused16.hip
 fi
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -fno-slp-vectorize -I. $extra -c $src -o $tmp/vn_fused16.o
-objs=$(ls *.o | grep -v "^vn_fused16.o$\|^vn_api_x.o$\|^vn_fused.o$")
+objs=$(ls *.o | grep -v "^vn_fused16.o$\|_x.o$\|^vn_fused.o$")
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 $objs $tmp/vn_fused16.o -o ../libvarnet_hip_$name.so
 rm -rf $tmp
 echo built libvarnet_hip_$name.so

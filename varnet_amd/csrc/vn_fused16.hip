@@ -20,9 +20,10 @@
 //     (registers are short while the forward pass stores 2*KS*L activation values; scratch spills would go
 //     through L2 to HBM).  Fixed summation order everywhere: results are bitwise reproducible.
 //   * Hidden widths 33..50 with 2..5 hidden layers (bf_sweeps): forward and input-gradient sweeps as bf16-piece
-//     products on the bf16 matrix pipe (vn_fused16_common.h); their images need the LDS of the stash, which then
-//     holds one layer in global memory.  The fourth row tile of either sweep (features 48, 49) is folded: its idle rows
-//     carry the m- and l-pieces, three MFMAs per K fragment and stream instead of six (stage_split_hidden, FOLD13).
+//     products on the bf16 matrix pipe (vn_fused16_common.h); their images (20 KB per layer) leave the stash room for one
+//     layer.  The fourth row tile of either sweep (features 48, 49) is folded: its idle rows carry the m- and l-pieces, three
+//     MFMAs per K fragment and stream instead of six (stage_split_hidden, FOLD13); the second K fragment of the other row
+//     tiles pairs its K halves, five MFMAs instead of six (five_khalf).
 // Register budget: 256 VGPRs per wave (stored activations 2*KS*L = 130 at 5x50; 18 spilled at 5x50).
 #include "vn_internal.h"
 #include "vn_fused16_common.h"
@@ -63,15 +64,16 @@ static_assert(vfeat(63) == 63 && vfeat(31) == 31 && vpos(7, 3) == 31, "position 
 __host__ __device__ constexpr bool merged_rounds(int L, int KS) { return VN_MERGED_ROUNDS && KS <= 8 && L >= 2; }   // one publish/contract round per hidden layer
 // Hidden-layer sweeps (forward value + tangent, input-gradient z-bar + z-bar-dot) as bf16-piece products (vn_fused16_common.h):
 // hidden widths 33..50 with 2..5 hidden layers.  The f32 MFMA shares its datapath with the f32 vector unit on gfx950, the bf16
-// MFMA does not.  Each hidden layer's 24 KB piece image replaces its f32 image; the weight-gradient stash moves to global memory
-// to make room.  Six 24 KB images (L = 7) do not fit next to the transposition region; 64-wide layers keep the f32 sweeps.
+// MFMA does not.  Each hidden layer's 20 KB piece image (IMGF) replaces its f32 image; the one stashed layer of weight-gradient
+// accumulators stays in LDS where it fits (Lay::NST), else in global memory.  The second K fragment of both sweeps runs as paired
+// K halves (five_khalf: 11 MFMAs per row tile and stream instead of 12).  64-wide layers and L > 5 keep the f32 sweeps.
 __host__ __device__ constexpr bool bf_sweeps(int L, int KS) { return KS == 13 && L >= 2 && L <= 5; }
 
 template <int L, int KS>
 struct Lay {
   static constexpr int HP = 4 * KS;
   static constexpr bool BF = bf_sweeps(L, KS);
-  static constexpr int HPWS = BF ? IMG / 4 : al4(HP * WS);  // floats per hidden layer image
+  static constexpr int HPWS = BF ? IMGF / 4 : al4(HP * WS);  // floats per hidden layer image
   static constexpr int W1_OFF = 0;                          // [8][WS]
   static constexpr int WH_OFF = al4(8 * WS);                // [L-1][HP][WS] | [L-1] bf16-piece images (BF)
   static constexpr int BI_OFF = WH_OFF + (L - 1) * HPWS;    // [L][64] biases in (tile, g, i) order
@@ -107,15 +109,18 @@ struct Lay {
   static constexpr int ST_OFF = T_OFF + T_SZ;
   static constexpr int ST_LAYER = NW * 2 * 64 * 4;
   static constexpr int ST_FIT = (160 * 256 - ST_OFF) / ST_LAYER;
-  static constexpr int NST = (BF || (KS != 13 && KS != 16) || L < 3) ? 0 : (ST_FIT < L - 1 ? ST_FIT : L - 1);
+  // BF: ONE stashed layer (layer 2, the last of the reverse sweep); the others stay in registers.  Measured at 5 x 50 with the
+  // stash in global memory (DESIGN_LOG G.1): 4 layers in the stash 7.45 ms, 3: 7.24, 2: 7.18, 1: 7.12-7.17, 0: 7.32 -- each stashed
+  // layer's load sits behind a publish round and a barrier, and costs more than the 8 VGPRs of spill traffic it saves, until the
+  // last one.  It lives in LDS like the f32 form's where the 20-block images leave room (they do up to 5 x 50), else in a
+  // per-workgroup buffer in global memory ([layer][wave][slot][lane] f32x4, ST_LAYER floats per layer; every lane re-reads only
+  // what it wrote one tile earlier, L2-resident).
+  static constexpr int NSTB = (BF && L >= 3) ? 1 : 0;
+  static constexpr int NST = BF ? (ST_FIT >= NSTB ? NSTB : 0)
+                                : (((KS != 13 && KS != 16) || L < 3) ? 0 : (ST_FIT < L - 1 ? ST_FIT : L - 1));
   static constexpr int TOTAL = ST_OFF + NST * ST_LAYER;
-  // BF: the stash moves to a per-workgroup buffer in global memory ([layer][wave][slot][lane] f32x4, ST_LAYER floats per layer;
-  // every lane re-reads only what it wrote one tile earlier, L2-resident) and holds ONE layer (layer 2, the last of the reverse
-  // sweep); the others stay in registers.  Measured at 5 x 50 (DESIGN_LOG G.1): 4 layers in the stash 7.45 ms, 3: 7.24, 2: 7.18,
-  // 1: 7.12-7.17, 0: 7.32 -- each stashed layer's load sits behind a publish round and a barrier, and costs more than the
-  // 8 VGPRs of spill traffic it saves, until the last one.
-  static constexpr int NSTG = (!BF || L < 3) ? 0 : 1;
-  static constexpr int NSTK = BF ? NSTG : NST;             // stashed layers, wherever the stash lives
+  static constexpr int NSTG = BF ? NSTB - NST : 0;         // layers stashed in global memory
+  static constexpr int NSTK = NST + NSTG;                  // stashed layers, wherever the stash lives
   static_assert(!BF || TOTAL <= 160 * 256, "bf16-piece images must fit the LDS");
 };
 
@@ -734,21 +739,24 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
   constexpr bool HID13 = (KS == 13);                 // 50-wide hidden layers: 3x3 core tiles + 4x4x1 borders
   constexpr int NHACC = HID13 ? 2 : WHG::TPW;
   constexpr int ST_L = LY::ST_LAYER / 4;
-  f32x4a* stash = (LY::BF ? reinterpret_cast<f32x4a*>(A.stash) + (long)blockIdx.x * LY::NSTG * ST_L
+  f32x4a* stash = (LY::NSTG ? reinterpret_cast<f32x4a*>(A.stash) + (long)blockIdx.x * LY::NSTG * ST_L
                           : reinterpret_cast<f32x4a*>(lds + LY::ST_OFF)) + wave * 2 * 64 + lane;   // [layer][wave][slot][lane]
   // bf16-piece sweeps: lane bases of the row (forward) and transposed (sweep back) fragment reads.
-  // The images of layers 2..5 span 96 KB and a DS instruction's immediate offset reaches 64 KB.  Layers 2-3 are read from the lane
-  // bases below; a layer of the second 48 KB window (layers 4-5) forms its own base ONCE per sweep (win_base: one vector add,
-  // pinned where it stands), so that every (piece, q, row tile) block offset is an immediate of its read instead of a vector
-  // add in front of it.  A second pair of loop-invariant bases would cost two registers for the whole tile (+7 spilled).
-  constexpr int WIN = 2 * IMG;
+  // The images of layers 2..5 span 80 KB and a DS instruction's immediate offset reaches 64 KB.  Layers 2-4 (60 KB) are read from
+  // the lane bases below; layer 5 forms its own base ONCE per sweep (win_base: one vector add, pinned where it stands), so that
+  // every (piece, q, row tile) block offset is an immediate of its read instead of a vector add in front of it.  A second pair
+  // of loop-invariant bases would cost two registers for the whole tile (+7 spilled); two layers per base instead of three
+  // spill 29 registers instead of 18 at L = 5 (DESIGN_LOG G.9).
+  constexpr int WINL = 3;
+  static_assert((WINL - 1) * IMGF + 19 * BLK + 8 + 16 <= 65536, "block offsets of the first window are DS immediates");
+  constexpr int WIN = WINL * IMGF;
   const int rowb = split_row_base(lc.g, lc.c), trb = split_tr_base(lc.g, lc.c);
   auto win_base = [&](int lane_base, int l) {          // image of layer l (2..L) + lane_base
     const char* wh = reinterpret_cast<const char*>(WH);
-    if (l - 2 < 2) return wh + lane_base + (l - 2) * IMG;
+    if (l - 2 < WINL) return wh + lane_base + (l - 2) * IMGF;
     int b = lane_base + WIN;
     asm volatile("" : "+v"(b));
-    return wh + b + (l - 4) * IMG;
+    return wh + b + (l - 2 - WINL) * IMGF;
   };
   f32x4 wacc1[W1G::TPW], wacch[L > 1 ? L - 1 : 1][NHACC];
   float woacc = 0.f, boacc = 0.f;                    // output layer: lane (g, c) holds d w_o[4c + g]; d b_o in every lane
@@ -858,9 +866,13 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       if constexpr (LY::BF) {
         // bf16 pieces: all four row tiles on the matrix pipe (features 48, 49 land in row 48 + 4g as in the edge path), value
         // and tangent share each weight fragment; the activation and the split are scalar f32 forms (no v_pk_* beside bf16 MFMAs).
-        // Invariants of the folded fourth tile: the B operands below are exact zeros at k-steps 13..15 (0u, `full ? .. : 0.f`), the
+        // Invariants of the folded fourth tile: the plain B pieces below are exact zeros at k-steps 13..15 (0u, `full ? .. : 0.f`), the
         // bias image is zero there, and registers 1..3 of tile 3 (finite partial sums after fold_rows, not 0) are read only
         // under ks < KS guards (B operands, H13Pub, the z-bar step) or against the zero padding weights of the output layer.
+        // Invariants of the K halves (second fragment): khalf_pack FEEDS slots 5, 6 (E_h, E_m), so every A fragment holds there the
+        // in-fold of its own slot 4 or an exact zero -- the corner of the folded tile zeros, each weight piece once in slot 4
+        // (stage_split_hidden skips the in-fold in row tile 3), else E_h and E_m would count its mh, lh and mm twice; slot 7 is
+        // zero on both sides; the folded tile takes the same three operands (three_khalf), no plain operand outlives the pack.
         const char* rl = win_base(rowb, l);
         f32x4 nv[GE::MT], nt[GE::MT];
 #pragma unroll
@@ -892,16 +904,31 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
             split2(act_d1<TANH>(a0) * z0, act_d1<TANH>(a1) * z1, h, md, lo);
             Bt[0][e] = h; Bt[1][e] = md; Bt[2][e] = lo;
           }
+          if (qf == 1) {                             // T + the edge entry as K halves: 5 + 5 + 5 + 3 MFMAs per stream (five_khalf)
+            u32x4 Kv[3], Kt[3];
+            khalf_pack(Bv, Kv);
+            khalf_pack(Bt, Kt);
+            const u32x4 (*const Ks[2])[3] = {&Kv, &Kt};
+#pragma unroll
+            for (int mi = 0; mi < GE::MT; ++mi) {
+              const int mt = (mi + 3) & 3;             // the folded tile first: 8 fewer registers spilled at L = 5 (DESIGN_LOG G.9)
+              f32x4* const as[2] = {&nv[mt], &nt[mt]};
+              const u32x4 Ad = ffrag_row1(rl, 0, 1, mt);
+              if (mt == 3) three_khalf<2>(lo_lo(Ad), Ad, hi_hi(Ad), Ks, as);     // features 48, 49: folded edge tile
+              else five_khalf<2>(lo_lo(Ad), ffrag_row1(rl, 1, 1, mt), ffrag_row1(rl, 2, 1, mt), Ad, hi_hi(Ad), Ks, as);
+            }
+            continue;
+          }
 #pragma unroll
           for (int mt = 0; mt < GE::MT; ++mt) {
             const u32x4 (*const Bs[2])[3] = {&Bv, &Bt};
             f32x4* const as[2] = {&nv[mt], &nt[mt]};
             if (mt == 3) {                           // features 48, 49: folded edge tile (the bias image is zero in rows 1..3)
-              three_folded<2>(split_frag_row1(rl, 0, qf, mt), Bs, as);
+              three_folded<2>(ffrag_row1(rl, 0, qf, mt), Bs, as);
               continue;
             }
             u32x4 Af[3];
-            split_frag_row(rl, qf, mt, Af);
+            ffrag_row(rl, qf, mt, Af);
             six<2>(Af, Bs, as);
           }
         }
@@ -1181,7 +1208,10 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
       for (int m = 0; m < GE::MT; ++m) { accv[m] = f32x4{0.f, 0.f, 0.f, 0.f}; acct[m] = f32x4{0.f, 0.f, 0.f, 0.f}; }
       if constexpr (LY::BF) {
         // bf16 pieces through the transposed reads of the same images: K fragment over the OUT-features 4(8qf+j)+g of layer l,
-        // row tile over the IN-positions 16 mt + c (all four on the matrix pipe)
+        // row tile over the IN-positions 16 mt + c (all four on the matrix pipe).  K halves (second fragment): the edge half E0 is
+        // the transposed read of out row tile 3, whose rows 4g + 0, 1, 2 are the h-, m- and l-pieces of out-feature 48 + g (out-fold),
+        // row 4g + 3 zero; for the folded IN tile it is the corner seen transposed -- one row, slots 4, 5, 6 = h, m, l, the in-fold
+        // rows zero there -- so E_h, E_m, E_l give its six products once.  Same invariants as in the forward sweep.
         const char* tl = win_base(trb, l);
 #pragma unroll
         for (int qf = 0; qf < 2; ++qf) {
@@ -1201,16 +1231,34 @@ __global__ __launch_bounds__(NTHREADS, 2) VN_NO_LDS_PAIRING void vn_fused16_kern
             split2(zdb[k0], full ? zdb[k0 + 1] : 0.f, h, md, lo);
             Bzd[0][e] = h; Bzd[1][e] = md; Bzd[2][e] = lo;
           }
+          if (qf == 1) {                             // out-features 32..47 + the out-fold rows of 48, 49 as K halves (five_khalf)
+            u32x4 Kz[3], Kzd[3];
+            khalf_pack(Bz, Kz);
+            khalf_pack(Bzd, Kzd);
+            const u32x4 (*const Ks[2])[3] = {&Kz, &Kzd};
+#pragma unroll
+            for (int mt = 0; mt < GE::MT; ++mt) {
+              f32x4* const as[2] = {&accv[mt], &acct[mt]};
+              const unsigned long long T0 = ffrag_tr_half(tl, 0, 2, mt), E0 = ffrag_tr_half(tl, 0, 3, mt);
+              if (mt == 3) {                         // in-features 48, 49: the mirror fold (in-slots 5, 6 of piece 0)
+                three_khalf<2>(halves(T0, T0), halves(T0, E0), halves(E0, E0), Ks, as);
+                continue;
+              }
+              const unsigned long long T1 = ffrag_tr_half(tl, 1, 2, mt), T2 = ffrag_tr_half(tl, 2, 2, mt);
+              five_khalf<2>(halves(T0, T0), halves(T1, T1), halves(T2, 0ull), halves(T0, E0), halves(E0, E0), Ks, as);
+            }
+            continue;
+          }
 #pragma unroll
           for (int mt = 0; mt < GE::MT; ++mt) {
             const u32x4 (*const Bs[2])[3] = {&Bz, &Bzd};
             f32x4* const as[2] = {&accv[mt], &acct[mt]};
             if (mt == 3) {                           // in-features 48, 49: the mirror fold (in-slots 5, 6 of piece 0)
-              three_folded<2>(split_frag_tr1(tl, 0, qf, mt), Bs, as);
+              three_folded<2>(ffrag_tr1(tl, 0, qf, mt), Bs, as);
               continue;
             }
             u32x4 At[3];
-            split_frag_tr(tl, qf, mt, At);
+            ffrag_tr(tl, qf, mt, At);
             six<2>(At, Bs, as);
           }
         }

@@ -235,6 +235,12 @@ typedef u32x4 u32x4a __attribute__((may_alias));
 
 constexpr int BLK = 1024;                                  // bytes of one (piece, q, row tile) block
 constexpr int IMG = 24 * BLK;                              // bytes of one hidden layer's image
+// The fused step kernel's image (stage_split_hidden, FOLD13): 20 blocks per layer.  Neither of its sweeps reads row tile 3 of a
+// piece-1 or piece-2 image (the folded tile lives in piece 0: three_folded, three_khalf), so those four blocks do not exist:
+// piece 0 keeps its eight blocks [q][row tile 4], pieces 1 and 2 have six each, [q][row tile 3].  Block (piece, q, row tile) is
+// at fblk * BLK; the transposed reads rely on row tiles 2q, 2q + 1 (q == 0) being neighbours in every piece.
+constexpr int IMGF = 20 * BLK;
+__host__ __device__ constexpr int fblk(int p, int q, int mt) { return p == 0 ? q * 4 + mt : 8 + ((p - 1) * 2 + q) * 3 + mt; }
 
 __device__ __forceinline__ u32 fu(float x) { return __builtin_bit_cast(u32, x); }
 __device__ __forceinline__ float uf(u32 x) { return __builtin_bit_cast(float, x); }
@@ -280,9 +286,16 @@ __device__ __forceinline__ void six(const u32x4 (&A)[3], const u32x4 (*const (&B
 //             and three; all nine piece products instead of six);
 //   in-fold:  slots j = 5, 6 of the q == 1 entries (k-steps 13, 14) hold the m- and the l-piece of slot 4 (in-feature 48 + g):
 //             the transposed read of piece 0 hands the sweep back the same three rows.
-// What makes this safe: k-steps 13..15 never hold a feature at KS == 13 (features >= 52), every sweep's B operand is an exact
-// zero there (the constant 0u and the `full ? .. : 0.f` halves), and so is the bias image.  Where both folds meet (rows
-// 4g' + 1, 2 x slots 5, 6) the image stays zero.
+//             Row tile 3 itself has no in-fold: its rows already are the three pieces.
+// What makes this safe: k-steps 13..15 never hold a feature at KS == 13 (features >= 52), and so the bias image is zero there.
+// First K fragment (q == 0, `six` / three_folded): no folded slot is touched.  Second K fragment (K halves, below): the B
+// operands FEED slots 5, 6 (E_h, E_m), so every A fragment must hold there either the in-fold of its own slot 4 or an exact zero:
+//   * row tiles 0..2: the in-fold (forward), the out-fold rows of the same out-feature (sweep back);
+//   * row tile 3 (the corner, rows 4g' + 0, 1, 2 x slots 4, 5, 6): h, m, l in slot 4 and zeros in slots 5, 6 -- each weight
+//     piece once; an in-fold on row 4g' + 0 would count mh, lh and mm of the corner twice;
+//   * slot 7 (k-step 15) and row 4g' + 3 (features >= 60) are zero in every piece.
+// The image has 20 blocks per layer (fblk): row tile 3 of the piece-1 and piece-2 images is read by neither sweep.  The q == 1
+// entries of pieces 1, 2 carry in their edge half what the forward sweep's paired operands need ([A1 | A1], [A2 | 0]).
 template <int L, bool FOLD13 = false>
 __device__ __forceinline__ void stage_split_hidden(const VnNet& net, const float* theta, char* img, int tid) {
   static_assert(NTHREADS == 2 * 4 * 4 * 16, "one entry per thread and layer");
@@ -314,10 +327,27 @@ __device__ __forceinline__ void stage_split_hidden(const VnNet& net, const float
         ph = fold_r == 1 ? pm : pl;
         pm = u32x4{0u, 0u, 0u, 0u};
         pl = u32x4{0u, 0u, 0u, 0u};
-      } else if (q == 1) {     // slot 4 = low half of word 2; slot 5 = its high half, slot 6 = low half of word 3 (both zero so far)
+      } else if (q == 1 && mt != 3) {   // slot 4 = low half of word 2; slot 5 = its high half, slot 6 = low half of word 3 (both zero so far)
+        // (not in row tile 3: the corner holds every weight piece once -- K halves below)
         ph[2] = (ph[2] & 0xffffu) | (pm[2] << 16);
         ph[3] = (ph[3] & 0xffff0000u) | (pl[2] & 0xffffu);
+        // K halves: the edge half of the piece-1 and piece-2 entries is read by neither sweep (five_khalf; the sweep back reads
+        // slots 4..7 of a q == 1 entry for its folded row tile only, from piece 0).  The forward sweep reads its operands
+        // [A1 | A1] and [A2 | 0] as they stand: the piece-1 entry repeats its T half, the piece-2 entry ends in zeros.
+        pm[2] = pm[0];
+        pm[3] = pm[1];
+        pl[2] = 0u;
+        pl[3] = 0u;
       }
+    }
+    if constexpr (FOLD13) {
+      char* il = img + (l - 2) * IMGF;
+      *reinterpret_cast<u32x4a*>(il + fblk(0, q, mt) * BLK + ent) = ph;
+      if (mt != 3) {
+        *reinterpret_cast<u32x4a*>(il + fblk(1, q, mt) * BLK + ent) = pm;
+        *reinterpret_cast<u32x4a*>(il + fblk(2, q, mt) * BLK + ent) = pl;
+      }
+      continue;
     }
     char* il = img + (l - 2) * IMG;
     *reinterpret_cast<u32x4a*>(il + ((0 * 2 + q) * 4 + mt) * BLK + ent) = ph;
@@ -376,6 +406,89 @@ __device__ __forceinline__ void three_folded(const u32x4& A0, const u32x4 (*cons
 // the last bit of a loss of 10.5 stalls with l + m first (DESIGN_LOG G.3).
 __device__ __forceinline__ void fold_rows(f32x4& t) { t[0] = (t[0] + t[1]) + t[2]; }
 
+// ---- K halves (the fused step kernel at KS == 13: stage_split_hidden, FOLD13) -------------------------------------------------
+// A K half of a 16x16x32 MFMA is 16 K entries: words 0, 1 or words 2, 3 of an A fragment (one row tile of the image: half an
+// entry in the forward sweep, one transposed read in the sweep back) against registers e = 0, 1 or e = 2, 3 of a B operand.  Any
+// two halves can share an MFMA as long as the A half and the B half of each pair match.  The second K fragment (q == 1) of a
+// 50-wide layer is one full half T (k-steps 8..11) and one edge half E (k-step 12 and padding), and the in-fold / out-fold put
+// the m- and the l-piece of the edge entry into slots 5, 6 of the PIECE-0 fragment, next to its h-piece in slot 4.  The six B
+// halves of the fragment -- T_h, T_m, T_l and, with b the k-step-12 value, E_h = h(b) h(b) h(b) 0, E_m = m(b) m(b) 0 0,
+// E_l = l(b) 0 0 0 -- are held as THREE operands, as many registers as the plain pieces take (khalf_pack):
+//   K0 = [T_h | T_m]     K1 = [T_l | E_h]     K2 = [E_m | E_l]
+// and a row tile 0..2 takes five MFMAs per stream instead of six (five_khalf; A0, A1, A2 the T halves of the three weight pieces,
+// E0 the edge half of piece 0; a product is written weight piece first):
+//   [A2 | 0 ] x K0    lh                          [A1 | A1] x K0    mh + mm
+//   [E0 | E0] x K2    hm + mm, hl of the edge     [A0 | E0] x K1    hl, and hh + mh + lh of the edge
+//   [A0 | A0] x K0    hh + hm
+// -- the six products of every (in, out) pair exactly once; the edge halves of the piece-1 and piece-2 fragments are not read.
+// The folded row tile (mt == 3), whose rows 0, 1, 2 are the h-, m- and l-pieces of the same weights, takes the same operands in
+// three MFMAs (three_khalf): [E | E] x K2, [T | E] x K1, [T | T] x K0.  Its CORNER (folded rows x edge slots) must hold each
+// weight piece once: rows 0, 1, 2 x slot 4 = h, m, l and zeros in slots 5, 6 (the in-fold skips row tile 3), else E_h and E_m
+// would count mh, lh and mm twice.  The forward sweep then sums all nine piece products of the corner (rows against E_h, E_m,
+// E_l in slot 4), the sweep back -- which sees the corner transposed: one row, slots 4, 5, 6 = h, m, l -- the six.
+// Exact zeros this relies on: slot 7 of every A fragment and B operand (k-step 15), the high half of the k-step-12 B words
+// (`full ? .. : 0.f`) and the k-step-14 B word (0u), the second half of the piece-2 operand.
+// Order: small terms first inside each accumulator, as in `six`; the streams are interleaved product by product.
+__device__ __forceinline__ u32 dup_lo16(u32 x) { return x | (x << 16); }        // x < 2^16: the bf16 in both halves
+__device__ __forceinline__ void khalf_pack(const u32x4 (&B)[3], u32x4 (&K)[3]) {   // plain pieces h, m, l of k-steps 8..15 -> K0, K1, K2
+  K[0] = u32x4{B[0][0], B[0][1], B[1][0], B[1][1]};
+  K[1] = u32x4{B[2][0], B[2][1], dup_lo16(B[0][2]), B[0][2]};
+  K[2] = u32x4{dup_lo16(B[1][2]), 0u, B[2][2], 0u};
+}
+// Aa = [A0 | A0], Ab = [A1 | A1], Ac = [A2 | 0], Ad = [A0 | E0], Ae = [E0 | E0]
+template <int N>
+__device__ __forceinline__ void five_khalf(const u32x4& Aa, const u32x4& Ab, const u32x4& Ac, const u32x4& Ad, const u32x4& Ae,
+                                           const u32x4 (*const (&K)[N])[3], f32x4* const (&acc)[N]) {
+#pragma unroll
+  for (int s = 0; s < N; ++s) *acc[s] = mfma_bf16(Ac, (*K[s])[0], *acc[s]);
+#pragma unroll
+  for (int s = 0; s < N; ++s) *acc[s] = mfma_bf16(Ab, (*K[s])[0], *acc[s]);
+#pragma unroll
+  for (int s = 0; s < N; ++s) *acc[s] = mfma_bf16(Ae, (*K[s])[2], *acc[s]);
+#pragma unroll
+  for (int s = 0; s < N; ++s) *acc[s] = mfma_bf16(Ad, (*K[s])[1], *acc[s]);
+#pragma unroll
+  for (int s = 0; s < N; ++s) *acc[s] = mfma_bf16(Aa, (*K[s])[0], *acc[s]);
+}
+// the folded row tile: At = [T | T], Ad = [T | E], Ae = [E | E] of its one (piece-0) fragment
+template <int N>
+__device__ __forceinline__ void three_khalf(const u32x4& At, const u32x4& Ad, const u32x4& Ae, const u32x4 (*const (&K)[N])[3],
+                                            f32x4* const (&acc)[N]) {
+#pragma unroll
+  for (int s = 0; s < N; ++s) *acc[s] = mfma_bf16(Ae, (*K[s])[2], *acc[s]);
+#pragma unroll
+  for (int s = 0; s < N; ++s) *acc[s] = mfma_bf16(Ad, (*K[s])[1], *acc[s]);
+#pragma unroll
+  for (int s = 0; s < N; ++s) *acc[s] = mfma_bf16(At, (*K[s])[0], *acc[s]);
+}
+__device__ __forceinline__ u32x4 lo_lo(const u32x4& a) { return u32x4{a[0], a[1], a[0], a[1]}; }
+__device__ __forceinline__ u32x4 hi_hi(const u32x4& a) { return u32x4{a[2], a[3], a[2], a[3]}; }
+__device__ __forceinline__ u32x4 halves(unsigned long long lo, unsigned long long hi) {
+  return u32x4{(u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32)};
+}
+
+// Fragment reads of the fused kernel's image (IMGF, fblk)
+__device__ __forceinline__ u32x4 ffrag_row1(const char* rl, int p, int q, int mt) {
+  return *reinterpret_cast<const u32x4a*>(rl + fblk(p, q, mt) * BLK);
+}
+__device__ __forceinline__ void ffrag_row(const char* rl, int q, int mt, u32x4 (&Af)[3]) {
+#pragma unroll
+  for (int p = 0; p < 3; ++p) Af[p] = ffrag_row1(rl, p, q, mt);
+}
+// one transposed read: out-feature row tile mo (a K half of the sweep back) of in-position row tile mt
+__device__ __forceinline__ unsigned long long ffrag_tr_half(const char* tl, int p, int mo, int mt) {
+  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) s16x4*)(tl + fblk(p, mt >> 1, mo) * BLK + 8 * (mt & 1)));
+  return __builtin_bit_cast(unsigned long long, v);
+}
+__device__ __forceinline__ u32x4 ffrag_tr1(const char* tl, int p, int q, int mt) {
+  const unsigned long long l64 = ffrag_tr_half(tl, p, 2 * q, mt), h64 = ffrag_tr_half(tl, p, 2 * q + 1, mt);
+  return u32x4{(u32)l64, (u32)(l64 >> 32), (u32)h64, (u32)(h64 >> 32)};
+}
+__device__ __forceinline__ void ffrag_tr(const char* tl, int q, int mt, u32x4 (&At)[3]) {
+#pragma unroll
+  for (int p = 0; p < 3; ++p) At[p] = ffrag_tr1(tl, p, q, mt);
+}
 // ---- host side: one dispatch walk, one launcher ----------------------------------------------------------------------------
 template <int L_, int KS_, bool TANH_>
 struct Inst {
