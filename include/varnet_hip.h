@@ -585,6 +585,49 @@ int vn_set_learnt_prior(vn_engine* h, int32_t kind, int32_t J, double weight, co
 /* out[0] = Q and out[1] = sum_j lambda_j |a_j| at the current values (one launch; synchronises; changes no state); (0, 0) without a
  * prior.  The vector not learnt: VN_ESTATE. */
 int vn_get_learnt_prior(vn_engine* h, int32_t kind, double out[2]);
+/* OPTIONAL, no reference counterpart: learnt weight scales.  The network every kernel evaluates becomes an EFFECTIVE parameter
+ * vector theta_eff = f(s_group) * V: a raw vector V of P floats and a short vector s of S scales, one per group of entries; an
+ * entry in no group is the ordinary parameter.  The optimizer steps (V, s) through the chain rule.
+ *   VN_REPARAM_RWF    random weight factorization (Wang, Wang, Perdikaris 2022): f(s) = exp(s); one group per output neuron of
+ *                     EVERY layer, the output layer included; a group is column j of W_l, weights only (biases are in no group);
+ *                     S = sum_{l=1..L+1} H[l].  `granularity` and `n` are ignored.
+ *   VN_REPARAM_SLOPE  adaptive activation slopes (Jagtap, Kawaguchi, Karniadakis 2020): f(s) = n s with a fixed n >= 1; hidden
+ *                     layers only; a group covers weights AND bias: column j of W_l with b_l[j] (VN_REPARAM_PER_NEURON,
+ *                     S = sum_{l<=L} H[l]) or all of W_l and b_l (VN_REPARAM_PER_LAYER, S = L).
+ *   VN_REPARAM_NONE   clears: theta keeps its current effective values and the slots of V are the slots of theta again.
+ * The scales are ordered by layer, then by neuron.  With g = d loss / d theta_eff (what vn_grad leaves in the gradient buffer)
+ *   g_V[p] = f(s_group(p)) g[p],     g_s[group] = f'(s_group) sum_{p in group} V[p] g[p]
+ * and one step (vn_apply, vn_train_step, vn_train_epoch) is Adam on V with g_V in the engine's two slots, Adam on s with g_s in
+ * two slots of S floats -- the engine's beta1, beta2, eps and step counter, the rate `lr` in place of cfg.lr -- and then
+ * theta_eff = fl32(f(s_new)) * V_new: g_V uses the scale of BEFORE the step, theta_eff is rebuilt from the values of AFTER it.
+ * The stage is one launch after the gradient reduction (vn_reparam.hip; sums in fp64 in a fixed order, no atomics: two steps on
+ * the same state give the same bits); vn_train_step does not fold the update into the reduction and equals vn_grad + vn_apply
+ * bit for bit.  No compute kernel changes: they read theta_eff, and so do vn_params_get, vn_eval_loss, vn_forward, vn_residual
+ * and vn_objective_f64, whose gradient is with respect to theta_eff.
+ * The call factorises the CURRENT parameters with s_init (S host doubles, rounded once to fp32): V = theta / f(s_init) on
+ * grouped entries, then theta_eff = f * V (within 2 ulp of what it was; bit-equal where f == 1); it zeroes the two scale slots,
+ * keeps m, v and the step counter, and invalidates the snapshot of vn_state_snapshot.
+ * With scales registered: vn_params_set stores theta_eff and re-factorises it with the current s; vn_params_init draws the same
+ * parameters as without, factorises them with the registered s_init and zeroes all four slots; vn_state_export / _import keep
+ * their layout (theta_eff, m, v) -- on import V is re-factorised from theta with the current s, and a full restore calls
+ * vn_set_reparam_state afterwards; vn_state_snapshot / _rollback carry V, s and the scale slots.
+ * VN_EINVAL: S not the mode's count; a non-finite s_init; slope with n < 1 (or not finite) or an s_init of 0; lr negative or not
+ * finite; an unknown mode or granularity.  VN_EUNSUPPORTED: an RMSProp or L-BFGS engine (their state would live in theta_eff
+ * space); a handle with a communicator (and vn_comm_init while scales are registered); the layer-by-layer route and any network
+ * outside the fused / generic kernels' range (at most 8 hidden layers, widths <= 64, d_in <= 8).
+ * Without a registration nothing is launched, nothing is allocated and every result is bit for bit what it is without this call. */
+enum { VN_REPARAM_NONE = 0, VN_REPARAM_RWF = 1, VN_REPARAM_SLOPE = 2 };
+enum { VN_REPARAM_PER_NEURON = 0, VN_REPARAM_PER_LAYER = 1 };
+int vn_set_reparam(vn_engine* h, int32_t mode, int32_t granularity, double n, const double* s_init_host, int32_t S, double lr);
+/* V [P], s [S], fl32(f(s)) [S] as last formed and the scale slots [2 S] (first moment, then second) into host floats; any pointer
+ * may be NULL.  Synchronises.  No registration: VN_ESTATE. */
+int vn_get_reparam(vn_engine* h, float* V_host, float* s_host, float* f_host, float* slots_host);
+/* Overwrites V, s and the scale slots (any pointer may be NULL: that part stays), then rebuilds theta_eff = fl32(f(s)) * V.
+ * Synchronises; invalidates the snapshot.  A non-finite s: VN_EINVAL; no registration: VN_ESTATE. */
+int vn_set_reparam_state(vn_engine* h, const float* V_host, const float* s_host, const float* slots_host);
+/* (g_V [P], g_s [S]) of the gradient buffer as it stands (after a vn_grad), by the stage's dry form: no state changes.  Either
+ * pointer may be NULL.  Synchronises.  No registration: VN_ESTATE. */
+int vn_reparam_grad(vn_engine* h, float* gV_host, float* gs_host);
 /* updateDictFields('trainW') (VarNetUtility.py:921-922); the caller applies the
  * w[0:2] /= batchNum*puNum rule (VarNetUtility.py:900-901). */
 int vn_set_weights(vn_engine* h, const double w[3]);

@@ -12,6 +12,7 @@
 #include "vn_learnt.h"
 #include "vn_weights.h"
 #include "vn_split16.h"
+#include "vn_reparam.h"
 
 hipError_t vn_calibrate_f64(int ncu, hipStream_t s, double ghz, double out[3]);      // vn_calib.hip (fp64 MFMA loop)
 
@@ -306,6 +307,19 @@ struct vn_engine {
   // (vn_set_source_learn) and gcoef bases (vn_set_field_learn), of the BC/IC label bases (vn_set_bic_learn) and of the flux rows'
   // bases (vn_set_fluxbc_learn), all of vn_learnt.hip; each carries its feature's own work buffers
   Learnt lv[LV_N];
+  // learnt weight scales (vn_set_reparam, vn_reparam.hip): while rp.mode != 0, theta is theta_eff = f(s) (.) V and the optimizer
+  // steps (V, s); every buffer below is allocated by the registration and freed when it is cleared
+  struct Reparam {
+    int mode = 0, gran = 0, S = 0;
+    double n = 1.0, lr = 0.0;
+    float* V = nullptr;              // [P]
+    float* sc = nullptr;             // [4 S]: s | first-moment slot | second-moment slot | fl32(f(s)) as last formed
+    float* snap = nullptr;           // [P + 4 S]: vn_state_snapshot's copy of V and sc
+    float* gout = nullptr;           // [P + S]: g_V | g_s of vn_reparam_grad
+    int* group = nullptr;            // [P] entry -> scale index, -1: in no group
+    std::vector<float> s_init;       // what vn_params_init factorises with
+    VnReparamArgs lay;               // mode, layer table and state pointers, filled once
+  } rp;
   float* snap = nullptr;       // vn_state_snapshot: device copy of (theta | m | v), 3 P floats
   int64_t snap_step = -1;      // step counter at the snapshot (-1: none)
   PointRoute point_route = PointRoute::automatic;   // vn_debug_point_route(route & 3)
@@ -1510,6 +1524,48 @@ int load_rccl() {
     if (r_ != ncclSuccess) return fail(VN_ECOMM, "%s: %s", #expr, g_rccl.GetErrorString(r_)); \
   } while (0)
 
+// ---- learnt weight scales (vn_set_reparam) ------------------------------------------------
+void reparam_free(vn_engine* h) {
+  void* ptrs[] = {h->rp.V, h->rp.sc, h->rp.snap, h->rp.gout, h->rp.group};
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  h->rp = vn_engine::Reparam{};
+}
+
+// number of scales of (mode, granularity) on `net`, and the layer table of vn_reparam.hip with the entry -> group map
+int reparam_layout(const VnNet& net, int mode, int gran, VnReparamArgs& a, std::vector<int>& group) {
+  a = VnReparamArgs{};
+  a.mode = mode;
+  a.tied = mode == VN_REPARAM_SLOPE && gran == VN_REPARAM_PER_LAYER;
+  a.nl = net.L + 1;
+  a.P = net.P;
+  group.assign(net.P, -1);
+  int S = 0;
+  for (int l = 1; l <= net.L + 1; ++l) {
+    const int k = l - 1, fi = net.H[l - 1], fo = net.H[l];
+    a.fi[k] = fi; a.fo[k] = fo; a.woff[k] = net.woff[l]; a.boff[k] = net.boff[l];
+    const bool in = mode == VN_REPARAM_RWF || l <= net.L;       // slope: hidden layers only
+    a.soff[k] = in ? S : -1;
+    if (!in) continue;
+    for (int i = 0; i < fi; ++i)
+      for (int j = 0; j < fo; ++j) group[net.woff[l] + i * fo + j] = S + (a.tied ? 0 : j);
+    if (mode == VN_REPARAM_SLOPE)                                // rwf: biases are in no group
+      for (int j = 0; j < fo; ++j) group[net.boff[l] + j] = S + (a.tied ? 0 : j);
+    S += a.tied ? 1 : fo;
+  }
+  a.S = S;
+  return S;
+}
+
+inline bool reparam_on(const vn_engine* h) { return h->rp.mode != VN_REPARAM_NONE; }
+
+// V = theta / f(s) (theta as it stands), then theta_eff = f(s) V: the rebuilt vector is the single source of truth
+int reparam_factorise(vn_engine* h) {
+  HIPCHK(vn_reparam_factorise_launch(h->rp.lay, h->rp.group, h->stream));
+  HIPCHK(vn_reparam_rebuild_launch(h->rp.lay, h->rp.group, h->stream));
+  return VN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1616,6 +1672,7 @@ int vn_destroy(vn_engine* h) {
   if (h->lb.out) (void)hipHostFree(h->lb.out);
   vn_obj64_free(h->o64);
   for (int id = 0; id < LV_N; ++id) learnt_free(h, id);
+  reparam_free(h);
   for (Batch& b : h->batches) {
     if (b.gcsr) (void)hipFree(b.gcsr);
     clear_weights(b);
@@ -1663,6 +1720,12 @@ int vn_params_init(vn_engine* h, uint64_t seed) {
   } else {
     HIPCHK(hipMemsetAsync(h->v, 0, t.size() * sizeof(float), h->stream));
   }
+  if (reparam_on(h)) {          // the same draw, factorised with the registered s_init; the scale slots start at zero
+    const size_t S = (size_t)h->rp.S;
+    HIPCHK(hipMemcpyAsync(h->rp.sc, h->rp.s_init.data(), S * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->rp.sc + S, 0, 2 * S * sizeof(float), h->stream));
+    if (int rc = reparam_factorise(h)) return rc;
+  }
   HIPCHK(hipStreamSynchronize(h->stream));
   h->step = 0;
   lbfgs_invalidate(h);
@@ -1683,6 +1746,8 @@ int vn_params_set(vn_engine* h, const float* host, int64_t n) {
   if (n != h->net.P) return fail(VN_EINVAL, "expected %d parameters, got %lld", h->net.P, (long long)n);
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipMemcpyAsync(h->theta, host, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (reparam_on(h))
+    if (int rc = reparam_factorise(h)) return rc;          // with the current s; the slots stay, as they do without scales
   HIPCHK(hipStreamSynchronize(h->stream));
   lbfgs_invalidate(h);
   return VN_OK;
@@ -1726,6 +1791,11 @@ int vn_state_snapshot(vn_engine* h) {
   HIPCHK(hipMemcpyAsync(h->snap + h->net.P, h->m, nb, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->snap + 2 * (size_t)h->net.P, h->v, nb, hipMemcpyDeviceToDevice, h->stream));
   if (int rc = learnt_copy(h, false)) return rc;
+  if (reparam_on(h)) {
+    const size_t S = (size_t)h->rp.S;
+    HIPCHK(hipMemcpyAsync(h->rp.snap, h->rp.V, nb, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->rp.snap + h->net.P, h->rp.sc, 4 * S * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  }
   h->snap_step = h->step;
   return VN_OK;
 }
@@ -1740,6 +1810,11 @@ int vn_state_rollback(vn_engine* h) {
   HIPCHK(hipMemcpyAsync(h->m, h->snap + h->net.P, nb, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->v, h->snap + 2 * (size_t)h->net.P, nb, hipMemcpyDeviceToDevice, h->stream));
   if (int rc = learnt_copy(h, true)) return rc;
+  if (reparam_on(h)) {
+    const size_t S = (size_t)h->rp.S;
+    HIPCHK(hipMemcpyAsync(h->rp.V, h->rp.snap, nb, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->rp.sc, h->rp.snap + h->net.P, 4 * S * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  }
   h->step = h->snap_step;
   return VN_OK;
 }
@@ -1759,6 +1834,8 @@ int vn_state_import(vn_engine* h, const void* host, int64_t bytes) {
     HIPCHK(hipMemcpyAsync(h->m, p + nb, nb, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->v, p + 2 * nb, nb, hipMemcpyHostToDevice, h->stream));
   }
+  if (reparam_on(h))            // V from the imported theta_eff with the current s; a full restore calls vn_set_reparam_state next
+    if (int rc = reparam_factorise(h)) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
   lbfgs_invalidate(h);
   return VN_OK;
@@ -2507,6 +2584,121 @@ int vn_set_batch_bic(vn_engine* h, int32_t batch, const float* biInput, const fl
   return VN_OK;
 }
 
+int vn_set_reparam(vn_engine* h, int32_t mode, int32_t granularity, double n, const double* s_init, int32_t S, double lr) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (mode == VN_REPARAM_NONE) {          // theta keeps its effective values; m and v are the slots of theta again
+    if (reparam_on(h)) {
+      HIPCHK(hipStreamSynchronize(h->stream));
+      reparam_free(h);
+      h->snap_step = -1;
+    }
+    return VN_OK;
+  }
+  if (mode != VN_REPARAM_RWF && mode != VN_REPARAM_SLOPE) return fail(VN_EINVAL, "vn_set_reparam: unknown mode %d", mode);
+  if (mode == VN_REPARAM_SLOPE && granularity != VN_REPARAM_PER_NEURON && granularity != VN_REPARAM_PER_LAYER)
+    return fail(VN_EINVAL, "vn_set_reparam: unknown granularity %d", granularity);
+  if (h->cfg.optimizer != VN_OPT_ADAM)
+    return fail(VN_EUNSUPPORTED, "vn_set_reparam on %s engine: its optimizer state would live in theta_eff space; the joint step on "
+                                 "(V, s) is built for Adam", is_lbfgs(h) ? "an L-BFGS" : "an RMSProp");
+  if (h->comm)
+    return fail(VN_EUNSUPPORTED, "vn_set_reparam under a communicator: the scales' gradient is formed from each rank's own V after the "
+                                 "all-reduce, a route that is not built");
+  const VnNet& net = h->net;
+  if (h->route == Route::layered || net.L + 1 > VN_RP_MAX_LAYERS || net.hmax > VN_RP_MAX_WIDTH || net.d_in > VN_KMAX_DIN ||
+      net.act == VN_ACT_PER_LAYER)
+    return fail(VN_EUNSUPPORTED, "vn_set_reparam needs a network of the fused / generic kernels (at most 8 hidden layers, widths <= %d, "
+                                 "d_in <= %d, one activation); this one (%d layers, widest %d, %d inputs) runs layer by layer",
+                VN_RP_MAX_WIDTH, VN_KMAX_DIN, net.L, net.hmax, net.d_in);
+  if (!s_init) return fail(VN_EINVAL, "vn_set_reparam: s_init is NULL");
+  if (!(lr >= 0.0) || !std::isfinite(lr)) return fail(VN_EINVAL, "vn_set_reparam: the scales' learning rate must be finite and >= 0");
+  if (mode == VN_REPARAM_SLOPE && (!(n >= 1.0) || !std::isfinite(n)))
+    return fail(VN_EINVAL, "vn_set_reparam: the slope factor n must be finite and >= 1 (got %g)", n);
+  VnReparamArgs lay;
+  std::vector<int> group;
+  const int need = reparam_layout(net, mode, granularity, lay, group);
+  if (S != need) return fail(VN_EINVAL, "vn_set_reparam: this mode has %d scales on this network, got S = %d", need, S);
+  std::vector<float> s32((size_t)S);
+  for (int i = 0; i < S; ++i) {
+    s32[i] = (float)s_init[i];
+    if (!std::isfinite(s_init[i]) || !std::isfinite(s32[i])) return fail(VN_EINVAL, "vn_set_reparam: s_init[%d] is not finite", i);
+    if (mode == VN_REPARAM_SLOPE && s32[i] == 0.f) return fail(VN_EINVAL, "vn_set_reparam: s_init[%d] == 0 (a zero slope cannot be factorised)", i);
+  }
+  if (reparam_on(h)) { HIPCHK(hipStreamSynchronize(h->stream)); reparam_free(h); }     // theta holds the effective values
+  h->snap_step = -1;
+  vn_engine::Reparam& r = h->rp;
+  const size_t P = (size_t)net.P;
+  hipError_t a = hipMalloc((void**)&r.V, P * sizeof(float));
+  if (a == hipSuccess) a = hipMalloc((void**)&r.sc, 4 * (size_t)S * sizeof(float));
+  if (a == hipSuccess) a = hipMalloc((void**)&r.snap, (P + 4 * (size_t)S) * sizeof(float));
+  if (a == hipSuccess) a = hipMalloc((void**)&r.gout, (P + (size_t)S) * sizeof(float));
+  if (a == hipSuccess) a = hipMalloc((void**)&r.group, P * sizeof(int));
+  if (a == hipSuccess) a = hipMemcpyAsync(r.group, group.data(), P * sizeof(int), hipMemcpyHostToDevice, h->stream);
+  if (a == hipSuccess) a = hipMemsetAsync(r.sc, 0, 4 * (size_t)S * sizeof(float), h->stream);
+  if (a == hipSuccess) a = hipMemcpyAsync(r.sc, s32.data(), (size_t)S * sizeof(float), hipMemcpyHostToDevice, h->stream);
+  if (a != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(h->stream);
+    reparam_free(h);
+    return fail(VN_ENOMEM, "vn_set_reparam: device allocation failed: %s", hipGetErrorString(a));
+  }
+  lay.n = n;
+  lay.theta = h->theta; lay.V = r.V; lay.m = h->m; lay.v = h->v;
+  lay.s = r.sc; lay.ms = r.sc + S; lay.vs = r.sc + 2 * (size_t)S; lay.f = r.sc + 3 * (size_t)S;
+  lay.gV = r.gout; lay.gs = r.gout + P;
+  r.lay = lay;
+  r.S = S; r.gran = granularity; r.n = n; r.lr = lr;
+  r.s_init = s32;
+  r.mode = mode;
+  if (int rc = reparam_factorise(h)) { (void)hipStreamSynchronize(h->stream); reparam_free(h); return rc; }
+  HIPCHK(hipStreamSynchronize(h->stream));          // (group and s32 are host vectors of this call)
+  return VN_OK;
+}
+
+int vn_get_reparam(vn_engine* h, float* V_host, float* s_host, float* f_host, float* slots_host) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (!reparam_on(h)) return fail(VN_ESTATE, "vn_get_reparam: no weight scales are registered (vn_set_reparam)");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t S = (size_t)h->rp.S;
+  if (V_host) HIPCHK(hipMemcpyAsync(V_host, h->rp.V, (size_t)h->net.P * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (s_host) HIPCHK(hipMemcpyAsync(s_host, h->rp.sc, S * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (slots_host) HIPCHK(hipMemcpyAsync(slots_host, h->rp.sc + S, 2 * S * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (f_host) HIPCHK(hipMemcpyAsync(f_host, h->rp.sc + 3 * S, S * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return VN_OK;
+}
+
+int vn_set_reparam_state(vn_engine* h, const float* V_host, const float* s_host, const float* slots_host) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (!reparam_on(h)) return fail(VN_ESTATE, "vn_set_reparam_state: no weight scales are registered (vn_set_reparam)");
+  const size_t S = (size_t)h->rp.S;
+  if (s_host)
+    for (size_t i = 0; i < S; ++i)
+      if (!std::isfinite(s_host[i])) return fail(VN_EINVAL, "vn_set_reparam_state: s[%d] is not finite", (int)i);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  h->snap_step = -1;
+  if (V_host) HIPCHK(hipMemcpyAsync(h->rp.V, V_host, (size_t)h->net.P * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (s_host) HIPCHK(hipMemcpyAsync(h->rp.sc, s_host, S * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (slots_host) HIPCHK(hipMemcpyAsync(h->rp.sc + S, slots_host, 2 * S * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(vn_reparam_rebuild_launch(h->rp.lay, h->rp.group, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  lbfgs_invalidate(h);
+  return VN_OK;
+}
+
+int vn_reparam_grad(vn_engine* h, float* gV_host, float* gs_host) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (!reparam_on(h)) return fail(VN_ESTATE, "vn_reparam_grad: no weight scales are registered (vn_set_reparam)");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  VnReparamArgs a = h->rp.lay;
+  a.g = h->gradbuf;
+  HIPCHK(vn_reparam_grad_launch(a, h->stream));
+  if (gV_host) HIPCHK(hipMemcpyAsync(gV_host, a.gV, (size_t)h->net.P * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (gs_host) HIPCHK(hipMemcpyAsync(gs_host, a.gs, (size_t)h->rp.S * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return VN_OK;
+}
+
 int vn_set_weights(vn_engine* h, const double w[3]) {
   if (!h || !w) return fail(VN_EINVAL, "null argument");
   h->w[0] = w[0]; h->w[1] = w[1]; h->w[2] = w[2];   // (VN_OPT_LBFGS: vn_lbfgs_step compares them with those of its (f_k, g_k))
@@ -2577,8 +2769,18 @@ static int apply_impl(vn_engine* h, float* loss_acc) {
   }
   const double t = (double)(h->step + 1);
   const double lr_t = h->cfg.lr * std::sqrt(1.0 - std::pow(h->cfg.beta2, t)) / (1.0 - std::pow(h->cfg.beta1, t));
-  HIPCHK(vn_adam_launch(h->theta, h->m, h->v, h->gradbuf, h->net.P, (float)lr_t, (float)h->cfg.beta1,
-                        (float)h->cfg.beta2, (float)h->cfg.eps, loss_acc, h->stream));
+  if (reparam_on(h)) {         // the joint step on (V, s) and the rebuild of theta_eff, in place of the plain step on theta
+    VnReparamArgs a = h->rp.lay;
+    a.g = h->gradbuf;
+    a.lr_t = (float)lr_t;
+    a.lr_s_t = (float)(h->rp.lr * std::sqrt(1.0 - std::pow(h->cfg.beta2, t)) / (1.0 - std::pow(h->cfg.beta1, t)));
+    a.b1 = (float)h->cfg.beta1; a.b2 = (float)h->cfg.beta2; a.eps = (float)h->cfg.eps;
+    a.loss_acc = loss_acc;
+    HIPCHK(vn_reparam_step_launch(a, h->stream));
+  } else {
+    HIPCHK(vn_adam_launch(h->theta, h->m, h->v, h->gradbuf, h->net.P, (float)lr_t, (float)h->cfg.beta1,
+                          (float)h->cfg.beta2, (float)h->cfg.eps, loss_acc, h->stream));
+  }
   for (int id = 0; id < LV_N; ++id)
     if (h->lv[id].on)
       if (int rc = learnt_finish(h, id, false, true, t)) return rc;
@@ -2602,6 +2804,10 @@ static int step_fused(vn_engine* h, int32_t batch, float* loss_acc) {
     // interval, and reports the failing rank's last stage (VNEngine._ck leaves `engine_error: ...` there).
     if (int rc = vn_grad(h, batch)) return rc;
     if (int rc = vn_allreduce_grad(h)) return rc;
+    return apply_impl(h, loss_acc);
+  }
+  if (reparam_on(h)) {          // learnt weight scales: the update is not folded into the reduction (fuse kind -1); the stage follows it
+    if (int rc = vn_grad(h, batch)) return rc;
     return apply_impl(h, loss_acc);
   }
   h->step += 1;
@@ -2965,6 +3171,9 @@ int vn_comm_init(vn_engine* h, int32_t rank, int32_t world, const void* unique_i
     if (h->lv[id].on)
       return fail(VN_EUNSUPPORTED, "vn_comm_init while %s are learnt (%s): %s are not in the all-reduced buffer, so every rank would "
                                    "follow its own shard's", kLearnt[id].what, kLearnt[id].setter, kLearnt[id].grads);
+  if (reparam_on(h))
+    return fail(VN_EUNSUPPORTED, "vn_comm_init while weight scales are learnt (vn_set_reparam): the scales' gradient is formed from each "
+                                 "rank's own V after the all-reduce, a route that is not built");
   if (int rc = load_rccl()) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   ncclUniqueId id;

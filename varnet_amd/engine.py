@@ -104,6 +104,10 @@ _SIGS = {
     'vn_set_learnt_prior': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double)]),
     'vn_get_learnt_prior': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]),
+    'vn_set_reparam': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_int32, C.c_double]),
+    'vn_get_reparam': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'vn_set_reparam_state': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'vn_reparam_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'vn_set_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_bind_grad_buffer': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vn_grad': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -152,6 +156,24 @@ COEF_TERMS = ('react', 'nlflux', 'nldiff')
 # the fixed length (None: the ABI takes the length J)
 LEARNT = {'coef': ('coefs', 9), 'source': ('source_amps', None), 'field': ('field_amps', None), 'bic': ('bic_amps', None),
           'fluxbc': ('fluxbc_amps', None)}
+
+# learnt weight scales (vn_set_reparam): VN_REPARAM_* and VN_REPARAM_PER_*
+REPARAM_MODES = {'rwf': 1, 'slope': 2}
+REPARAM_PER = {'neuron': 0, 'layer': 1}
+
+
+def reparam_count(mode, per, inpDim, layerWidth):
+    """Number of scales S of a mode on the network inpDim -> layerWidth -> 1 (include/varnet_hip.h, vn_set_reparam)."""
+    if mode == 'rwf':
+        return int(sum(layerWidth)) + 1
+    return len(layerWidth) if per == 'layer' else int(sum(layerWidth))
+
+
+def reparam_layers(mode, per, layerWidth):
+    """Per-layer lengths of the scale vector, in its order (rwf: the output layer last)."""
+    if mode == 'rwf':
+        return [int(w) for w in layerWidth] + [1]
+    return [1] * len(layerWidth) if per == 'layer' else [int(w) for w in layerWidth]
 
 
 class VNError(RuntimeError):
@@ -897,6 +919,63 @@ class VNEngine:
         out = (C.c_double * n)()
         self._ck(self.lib.vn_causal_weights(self.h, int(batch), out, n))
         return np.array(out, dtype=np.float64)
+
+    # -- learnt weight scales --------------------------------------------------------------
+    def set_reparam(self, mode=None, per='neuron', n=1.0, s_init=None, lr=None):
+        """Learnt weight scales theta_eff = f(s) (.) V (include/varnet_hip.h, vn_set_reparam).  mode 'rwf': f = exp(s), one scale
+        per output neuron of every layer, weights only; 'slope': f = n s, hidden layers, weights and bias, `per` 'neuron' or
+        'layer'.  s_init: the S initial scales, or a scalar for all (default: 0 for rwf, 1 / n for slope, both f = 1).  lr: the
+        scales' learning rate (default: the network's).  mode None clears the registration."""
+        if mode is None:
+            self._ck(self.lib.vn_set_reparam(self.h, 0, 0, 1.0, None, 0, 0.0))
+            self._reparam = None
+            return
+        if mode not in REPARAM_MODES:
+            raise ValueError("reparam mode must be 'rwf' or 'slope' (got %r)" % (mode,))
+        if per not in REPARAM_PER:
+            raise ValueError("reparam granularity must be 'neuron' or 'layer' (got %r)" % (per,))
+        S = reparam_count(mode, per, self.inpDim, self.layerWidth)
+        if s_init is None:
+            s_init = 0.0 if mode == 'rwf' else 1.0 / float(n)
+        s0 = np.ascontiguousarray(np.broadcast_to(np.asarray(s_init, dtype=np.float64), (S,)) if np.ndim(s_init) == 0
+                                  else np.asarray(s_init, dtype=np.float64).ravel())
+        lr = self.cfg.lr if lr is None else float(lr)
+        self._ck(self.lib.vn_set_reparam(self.h, REPARAM_MODES[mode], REPARAM_PER[per], float(n),
+                                         s0.ctypes.data_as(C.POINTER(C.c_double)), int(s0.size), lr))
+        self._reparam = (mode, per, float(n), S)
+
+    @property
+    def reparam(self):
+        """(mode, per, n, S) of the registered weight scales, or None."""
+        return getattr(self, '_reparam', None)
+
+    def get_reparam(self):
+        """{'V': [P], 's': [S], 'f': [S] fl32(f(s)) as last formed, 'slots': [2, S]} of the registered scales (synchronises)."""
+        S = self.reparam[3] if self.reparam else 0
+        out = {'V': np.empty(self.P, np.float32), 's': np.empty(S, np.float32), 'f': np.empty(S, np.float32),
+               'slots': np.empty((2, S), np.float32)}
+        self._ck(self.lib.vn_get_reparam(self.h, out['V'].ctypes.data, out['s'].ctypes.data, out['f'].ctypes.data,
+                                         out['slots'].ctypes.data))
+        return out
+
+    def set_reparam_state(self, V=None, s=None, slots=None):
+        """Overwrites V, s and / or the scale slots [2, S], then rebuilds theta_eff (synchronises)."""
+        S = self.reparam[3] if self.reparam else 0
+        arrs = []
+        for a, n_ in ((V, self.P), (s, S), (slots, 2 * S)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float32).ravel()
+                if a.size != n_:
+                    raise ValueError('set_reparam_state: expected %d values, got %d' % (n_, a.size))
+            arrs.append(a)
+        self._ck(self.lib.vn_set_reparam_state(self.h, *[None if a is None else a.ctypes.data for a in arrs]))
+
+    def reparam_grad(self):
+        """(g_V [P], g_s [S]) of the gradient buffer as it stands, by the stage's dry form (synchronises; no state changes)."""
+        S = self.reparam[3] if self.reparam else 0
+        gV, gs = np.empty(self.P, np.float32), np.empty(S, np.float32)
+        self._ck(self.lib.vn_reparam_grad(self.h, gV.ctypes.data, gs.ctypes.data))
+        return gV, gs
 
     def set_weights(self, w):
         arr = (C.c_double * 3)(*[float(x) for x in w])

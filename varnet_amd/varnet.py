@@ -338,7 +338,10 @@ class TrainResult:
         else:
             L.append('\ttype: %s stochastic gradient descent algorithm\n'
                      % ('RMSProp' if str(varNet.optimizer).lower() == 'rmsprop' else 'Adam'))
-            L.append('\tlearning rate: ' + str(varNet.learning_rate) + '\n\n')
+            L.append('\tlearning rate: ' + str(varNet.learning_rate) + '\n')
+            if getattr(varNet, 'reparam', None) is not None:
+                L.append('\tlearnt weight scales: %s, learning rate %s\n' % (varNet.reparam, varNet.reparamLr))
+            L.append('\n')
         L.append('Space-time discretization information:\n')
         L.append('\tspatial domain interior discretization number: ' + str(varNet.discNum) + '\n')
         L.append('\tspatial domain boundary discretization density: ' + str(varNet.bDiscNum) + '\n')
@@ -821,6 +824,37 @@ class ManageTrainData:
         eng._bic_key = (key, mb)
 
 
+def parse_reparam(reparam):
+    """The `reparam` option of VarNet as a full dict, or None.  'rwf' | 'slope' | {'kind': 'rwf', 'mean': 1.0, 'std': 0.1} |
+    {'kind': 'slope', 'n': 10.0, 'per': 'layer' | 'neuron'}; anything else is a ValueError."""
+    if reparam is None:
+        return None
+    if isinstance(reparam, str):
+        reparam = {'kind': reparam}
+    if not isinstance(reparam, dict) or reparam.get('kind') not in ('rwf', 'slope'):
+        raise ValueError("reparam=%r: expected None, 'rwf', 'slope' or a dict with 'kind': 'rwf' | 'slope'" % (reparam,))
+    kind = reparam['kind']
+    allowed = {'rwf': ('kind', 'mean', 'std'), 'slope': ('kind', 'n', 'per')}[kind]
+    extra = sorted(set(reparam) - set(allowed))
+    if extra:
+        raise ValueError('reparam=%r: unknown keys %s for kind %r (known: %s)' % (reparam, extra, kind, list(allowed)))
+    num = lambda key, dflt: float(reparam.get(key, dflt))
+    try:
+        if kind == 'rwf':
+            out = dict(kind='rwf', mean=num('mean', 1.0), std=num('std', 0.1), per='neuron', n=1.0)
+            if not np.isfinite(out['mean']) or not np.isfinite(out['std']) or out['std'] < 0.0:
+                raise ValueError('reparam=%r: mean must be finite and std finite and >= 0' % (reparam,))
+        else:
+            out = dict(kind='slope', n=num('n', 1.0), per=reparam.get('per', 'neuron'), mean=None, std=None)
+            if not np.isfinite(out['n']) or out['n'] < 1.0:
+                raise ValueError('reparam=%r: the slope factor n must be finite and >= 1' % (reparam,))
+            if out['per'] not in ('neuron', 'layer'):
+                raise ValueError("reparam=%r: per must be 'neuron' or 'layer'" % (reparam,))
+    except TypeError:
+        raise ValueError('reparam=%r: mean, std and n must be numbers' % (reparam,))
+    return out
+
+
 # ======================================================================================
 class VarNet:
     def __init__(self, PDE, layerWidth=[20], modelId='MLP', activationFun=None, discNum=20,
@@ -829,7 +863,7 @@ class VarNet:
                  causal=None, causalSlabs=None, periodicDeriv=None, observations=None, obsWeight=None,
                  learnCoef=None, coefLr=None, coefBounds=None, learnSource=None, sourceLr=None, sourceBounds=None,
                  learnField=None, fieldLr=None, fieldBounds=None, learnBic=None, bicLr=None, bicBounds=None,
-                 learnFluxBC=None, fluxBCLr=None, fluxBCBounds=None, learntPrior=None):
+                 learnFluxBC=None, fluxBCLr=None, fluxBCBounds=None, learntPrior=None, reparam=None, reparamLr=None):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -861,6 +895,24 @@ class VarNet:
             raise ValueError('unknown optimizer requested!')
         if lbfgsLoss64 and optimizer.lower() != 'lbfgs':
             raise ValueError('lbfgsLoss64=True is an option of optimizer=\'lbfgs\' (the line search on the fp64 loss)')
+        # reparam=... (extension; no reference counterpart): learnt weight scales theta_eff = f(s) (.) V -- random weight
+        # factorization or adaptive activation slopes -- stepped jointly by Adam (`parse_reparam`, VNEngine.set_reparam)
+        self.reparam = parse_reparam(reparam)
+        self.reparamLr = None
+        if self.reparam is None:
+            if reparamLr is not None:
+                raise ValueError('reparamLr=%r is an option of reparam=...' % (reparamLr,))
+        else:
+            self.reparamLr = float(learning_rate if reparamLr is None else reparamLr)
+            if not np.isfinite(self.reparamLr) or self.reparamLr < 0.0:
+                raise ValueError('reparamLr=%r must be a finite number >= 0' % (reparamLr,))
+            if optimizer.lower() != 'adam':
+                raise NotImplementedError('reparam=%r with optimizer=%r: the joint step on (V, s) is built for Adam only' % (reparam, optimizer))
+            if isinstance(processors, (list, tuple)) and len(processors) > 1:
+                raise NotImplementedError('reparam=%r with towers is not supported: the scales\' gradient after the all-reduce is not built' % (reparam,))
+            if len(layerWidth) > 8 or max(layerWidth) > 64:
+                raise NotImplementedError('reparam=%r on the layer-by-layer route is not supported: layerWidth=%s lies outside the fused / '
+                                          'generic kernels\' range (8 layers, 64 wide)' % (reparam, list(layerWidth)))
         # causal=eps (extension; no reference counterpart): the variational loss of every test function is weighted by
         # exp(-eps * accumulated mean loss of the earlier time slabs), recomputed at every step and held constant for the
         # gradient (causal training, Wang, Sankaran, Perdikaris 2022); causalSlabs: number of slabs (default tDiscNum)
@@ -1014,7 +1066,9 @@ class VarNet:
             return
         self._rng = np.random.default_rng(12345)
         self.engine = self._make_engine(processors)
-        self.engine.init_params(seed=0)
+        if self.reparam is not None and self.world > 1:
+            raise NotImplementedError('reparam=%r with towers is not supported: the scales\' gradient after the all-reduce is not built' % (reparam,))
+        self._init_params(0)
         if getattr(PDE, 'ansatz', None) is not None:
             if self.world > 1:
                 raise NotImplementedError('an ansatz with towers is not supported: the shards of the ansatz streams per rank are '
@@ -2884,7 +2938,7 @@ class VarNet:
                         self.tData = tData
                         msg = '\n\n==========================================================\nTraining points updated.\n\n'
                         if reinitrain:
-                            eng.init_params(seed=tp_updates)            # global_variables_initializer, VarNet.py:1412
+                            self._init_params(tp_updates)               # global_variables_initializer, VarNet.py:1412
                             msg += 'trainable variables reinitialized.\n\n'
                         if verbose and self.rank == 0:
                             print(msg)
@@ -2915,6 +2969,30 @@ class VarNet:
         names = ['dense_%d' % i for i in range(len(self.layerWidth))] + ['output']
         return names
 
+    def _init_params(self, seed):
+        """init_params(seed), then the weight scales of `reparam` registered on the fresh parameters: rwf draws s_init from
+        np.random.RandomState(seed).normal(mean, std, S), slope starts at s = 1 / n (f == 1)."""
+        self.engine.init_params(seed=seed)
+        rp = self.reparam
+        if rp is None:
+            return
+        from .engine import reparam_count
+        S = reparam_count(rp['kind'], rp['per'], self.inpDim, self.layerWidth)
+        s_init = np.random.RandomState(seed).normal(rp['mean'], rp['std'], S) if rp['kind'] == 'rwf' else np.full(S, 1.0 / rp['n'])
+        self.engine.set_reparam(rp['kind'], per=rp['per'], n=rp['n'], s_init=s_init, lr=self.reparamLr)
+
+    def scales(self):
+        """The per-layer arrays of f(s) of `reparam` (rwf: every layer, the output layer last; slope: the hidden layers), or None."""
+        if self.reparam is None:
+            return None
+        from .engine import reparam_layers
+        f = self.engine.get_reparam()['f']
+        out, off = [], 0
+        for n_ in reparam_layers(self.reparam['kind'], self.reparam['per'], self.layerWidth):
+            out.append(f[off:off + n_].copy())
+            off += n_
+        return out
+
     def checkpoint_arrays(self):
         """{TF variable name: array} for the current engine state (see the layout note above)."""
         buf = np.asarray(self.engine.export_state(), dtype=np.uint8)
@@ -2943,6 +3021,11 @@ class VarNet:
                 out[lv.key] = np.asarray(getattr(self.engine, 'get_' + lv.engine)(), dtype=np.float64)
         if getattr(self.PDE, 'ansatz', None) is not None:
             out['ansatz'] = np.int64(1)                              # the parameters are those of N in c = A + B N
+        if self.reparam is not None:
+            # the TF-named kernels and biases above hold theta_eff (a saved model is a plain MLP); these restore the joint state
+            st = self.engine.get_reparam()
+            out['reparam_mode'] = np.array('%s/%s/%r' % (self.reparam['kind'], self.reparam['per'], self.reparam['n']))
+            out['reparam_V'], out['reparam_s'], out['reparam_slots'] = st['V'], st['s'], st['slots']
         return out
 
     def restore_arrays(self, arrays):
@@ -2951,6 +3034,11 @@ class VarNet:
         if ('ansatz' in arrays) != has:
             raise ValueError('checkpoint %s an ansatz (c = A + B N) but the PDE of this model %s: the parameters of the one are not '
                              'a solution of the other!' % (('was trained with', 'has none') if not has else ('was trained without', 'has one')))
+        mode = None if self.reparam is None else '%s/%s/%r' % (self.reparam['kind'], self.reparam['per'], self.reparam['n'])
+        saved = str(arrays['reparam_mode']) if 'reparam_mode' in arrays else None
+        if saved != mode or (mode is not None and np.size(arrays['reparam_s']) != np.size(self.engine.get_reparam()['s'])):
+            raise ValueError('checkpoint was trained with reparam %s but this model has %s: the optimizer state of the one is not that '
+                             'of the other!' % (saved, mode))
         slot = ('RMSProp_1', 'RMSProp') if str(self.optimizer).lower() == 'rmsprop' else ('Adam', 'Adam_1')
         th, m, v, fan = [], [], [], self.inpDim
         for name, h in zip(self._var_names(), self.layerWidth + [1]):
@@ -2970,6 +3058,8 @@ class VarNet:
         step = np.array([int(arrays['global_step']) if 'global_step' in arrays else 0], dtype=np.int64)
         blob = np.concatenate([step.view(np.uint8), np.concatenate(th + m + v).astype(np.float32).view(np.uint8)])
         self.engine.import_state(blob)
+        if mode is not None:
+            self.engine.set_reparam_state(arrays['reparam_V'], arrays['reparam_s'], arrays['reparam_slots'])
         for lv in self.LEARNT:
             if getattr(self, lv.attr, None) is not None and lv.key in arrays:
                 getattr(self.engine, 'set_' + lv.engine)(np.asarray(arrays[lv.key], dtype=np.float64).reshape(-1))
