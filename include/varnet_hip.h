@@ -640,6 +640,41 @@ int vn_bind_grad_buffer(vn_engine* h, float* dev);
 /* compute_gradients(loss) (TFModel.py:709): forward, weak-form loss, backward for `batch`;
  * leaves d loss/d theta and the 4 loss scalars in the gradient buffer. */
 int vn_grad(vn_engine* h, int32_t batch);
+/* OPTIONAL (the reference's updateWeights, VarNet.py:1373, cannot run): per-term gradients and their statistics, the input of an
+ * adaptive loss-balancing rule (vn_balance.hip).  The objective of vn_grad is w0 BC + w1 IC + w2 var + lambda O, linear in the
+ * weights, so the gradient of one term is what vn_grad leaves under a one-hot weight vector. */
+#define VN_TERM_BC 0
+#define VN_TERM_IC 1
+#define VN_TERM_VAR 2
+#define VN_TERM_OBS 3
+#define VN_TERM_N 4
+/* the statistics alone, on caller vectors: T_dev [K][n] fp32, 1 <= K <= VN_TERM_N, n >= 1.
+ * stats [K][3] = {sumsq, sumabs, maxabs}, gram [K][K]; host doubles; synchronises.
+ * All sums in fp64 from exact products, in an order that depends on n alone (no atomics; not on the card): two calls give the same
+ * bits.  gram is symmetric and gram[a][a] is sumsq[a], the same bits.  A NaN entry makes the sums it enters NaN; maxabs ignores it.
+ * VN_EINVAL: K outside 1..VN_TERM_N, n < 1, a null pointer.  VN_ENOMEM: the 150 KB of partials do not fit. */
+int vn_term_stats(vn_engine* h, const float* T_dev, int32_t K, int64_t n, double* stats, double* gram);
+/* per-term gradients of the objective of vn_grad over `batches[0..n)`, and their statistics.
+ * G_k is the gradient buffer vn_grad(batch) leaves with the weights (1,0,0), (0,1,0), (0,0,1) and lambda = 0 for VN_TERM_BC,
+ * VN_TERM_IC, VN_TERM_VAR, and with (0,0,0) and lambda = 1 for VN_TERM_OBS, summed over the listed batches in list order in fp32
+ * (the first batch is copied, every later one added with one rounding).  value[k] is the matching unweighted scalar (BC, IC, var of
+ * the gradient buffer's tail, O of the misfit slot) summed over the batches in double.  Flux rows and periodic pairs belong to
+ * VN_TERM_BC, as they do in the loss.  Every evaluation is vn_grad's own (the learnt-vector mixes first, the batch's route, every
+ * registered extension, no update folded in); with weight scales registered the gradient is with respect to theta_eff.
+ * A term outside `term_mask` (bit k = term k) or without rows (no IC rows on a steady problem, no observations) is skipped: its
+ * rows of stats, gram, value and G_dev are zeros.  stats, gram and value are host doubles, none may be NULL; G_dev (device,
+ * [VN_TERM_N][P] floats) may be.
+ * State: on return the weights and lambda are the caller's, bit for bit; theta, m, v, the step counter, a loss accumulator, the
+ * learnt vectors and their slots, (V, s) and the scale slots and the snapshot are untouched.  CLOBBERED until the next vn_grad: the
+ * gradient buffer (a bound one included), the loss scalars, the misfit slot and the learnt vectors' gradient read-outs, which are
+ * left as the last evaluated term wrote them.  One synchronisation, at the end.
+ * VN_EUNSUPPORTED: an L-BFGS engine (its (f_k, g_k) would be disturbed); a handle with a communicator (each term would need its
+ * own all-reduce).  VN_EINVAL: a null or empty batch list, a batch id that names no registered batch, a term_mask with no bit
+ * or a bit >= VN_TERM_N.  Whatever vn_grad refuses is refused with its code, the weights restored.  VN_ENOMEM: the
+ * [VN_TERM_N][P] scratch, allocated at the first call and freed by vn_destroy, does not fit. */
+int vn_term_grads(vn_engine* h, const int32_t* batches, int32_t n, uint32_t term_mask,
+                  double* stats /*[VN_TERM_N][3]*/, double* gram /*[VN_TERM_N][VN_TERM_N]*/,
+                  double* value /*[VN_TERM_N]*/, float* G_dev /*[VN_TERM_N][P] or NULL*/);
 /* optimizer.apply_gradients (TFModel.py:313): TF-1 Adam (or RMSProp: decay 0.9, momentum 0, eps 1e-10,
  * mean-square slot initialised to ones) step from the gradient buffer. */
 int vn_apply(vn_engine* h);

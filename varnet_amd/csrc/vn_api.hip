@@ -13,6 +13,7 @@
 #include "vn_weights.h"
 #include "vn_split16.h"
 #include "vn_reparam.h"
+#include "vn_balance.h"
 
 hipError_t vn_calibrate_f64(int ncu, hipStream_t s, double ghz, double out[3]);      // vn_calib.hip (fp64 MFMA loop)
 
@@ -320,6 +321,11 @@ struct vn_engine {
     std::vector<float> s_init;       // what vn_params_init factorises with
     VnReparamArgs lay;               // mode, layer table and state pointers, filled once
   } rp;
+  // per-term gradients (vn_term_grads, vn_term_stats; vn_balance.hip), allocated at the first call: the sums G_k, the statistics
+  // kernels' partials, and the result slot -- stats [4][3] | gram [4][4] | value [4], read back in one copy
+  float* tg_T = nullptr;       // [VN_TERM_N][P]
+  double* tg_part = nullptr;   // [VN_BAL_MAX_BLOCKS][VN_BAL_ROW]
+  double* tg_out = nullptr;    // [VN_BAL_OUT + VN_TERM_N]
   float* snap = nullptr;       // vn_state_snapshot: device copy of (theta | m | v), 3 P floats
   int64_t snap_step = -1;      // step counter at the snapshot (-1: none)
   PointRoute point_route = PointRoute::automatic;   // vn_debug_point_route(route & 3)
@@ -1673,6 +1679,9 @@ int vn_destroy(vn_engine* h) {
   vn_obj64_free(h->o64);
   for (int id = 0; id < LV_N; ++id) learnt_free(h, id);
   reparam_free(h);
+  if (h->tg_T) (void)hipFree(h->tg_T);
+  if (h->tg_part) (void)hipFree(h->tg_part);
+  if (h->tg_out) (void)hipFree(h->tg_out);
   for (Batch& b : h->batches) {
     if (b.gcsr) (void)hipFree(b.gcsr);
     clear_weights(b);
@@ -2755,6 +2764,92 @@ static int grad_route(vn_engine* h, const Batch& b) {
     case Route::fused8: return has_terms(b) || has_weights(b) || has_ansatz(b) || src_learnt(h, b) || fld_learnt(h, b) ? run_twopass(h, b, h->gradbuf, fx) : run_fused(h, b, h->gradbuf, fx);
     case Route::twopass: return run_twopass(h, b, h->gradbuf, fx);
   }
+}
+
+// ---- per-term gradients and their statistics (vn_balance.hip) -------------------------------
+static int term_scratch(vn_engine* h, bool with_T) {
+  hipError_t a = hipSuccess;
+  if (!h->tg_part) a = hipMalloc((void**)&h->tg_part, (size_t)VN_BAL_MAX_BLOCKS * VN_BAL_ROW * sizeof(double));
+  if (a == hipSuccess && !h->tg_out) a = hipMalloc((void**)&h->tg_out, (size_t)(VN_BAL_OUT + VN_TERM_N) * sizeof(double));
+  if (a == hipSuccess && with_T && !h->tg_T) a = hipMalloc((void**)&h->tg_T, (size_t)VN_TERM_N * (size_t)h->net.P * sizeof(float));
+  if (a != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(VN_ENOMEM, "per-term gradient scratch: device allocation failed: %s", hipGetErrorString(a));
+  }
+  return VN_OK;
+}
+
+int vn_term_stats(vn_engine* h, const float* T_dev, int32_t K, int64_t n, double* stats, double* gram) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (K < 1 || K > VN_TERM_N) return fail(VN_EINVAL, "vn_term_stats: K = %d is outside 1..%d", K, VN_TERM_N);
+  if (n < 1) return fail(VN_EINVAL, "vn_term_stats: n = %lld must be at least 1", (long long)n);
+  if (!T_dev || !stats || !gram) return fail(VN_EINVAL, "vn_term_stats: null argument");
+  (void)hipGetLastError();
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (int rc = term_scratch(h, false)) return rc;
+  HIPCHK(vn_balance_stats_launch(T_dev, K, n, h->tg_part, h->tg_out, h->stream));
+  double out[VN_BAL_OUT];
+  const size_t nv = (size_t)(3 * K + K * K);
+  HIPCHK(hipMemcpyAsync(out, h->tg_out, nv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  std::memcpy(stats, out, (size_t)(3 * K) * sizeof(double));
+  std::memcpy(gram, out + 3 * K, (size_t)(K * K) * sizeof(double));
+  return VN_OK;
+}
+
+int vn_term_grads(vn_engine* h, const int32_t* batches, int32_t n, uint32_t term_mask, double* stats, double* gram, double* value,
+                  float* G_dev) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (is_lbfgs(h)) return fail(VN_EUNSUPPORTED, "vn_term_grads on an L-BFGS engine: the evaluations would disturb the optimizer's (f_k, g_k)");
+  if (h->comm) return fail(VN_EUNSUPPORTED, "vn_term_grads under a communicator: each term's gradient would need its own all-reduce, which is not built");
+  if (!batches || n < 1) return fail(VN_EINVAL, "vn_term_grads: the batch list is null or empty");
+  if (!stats || !gram || !value) return fail(VN_EINVAL, "vn_term_grads: null output argument");
+  if (term_mask == 0 || (term_mask >> VN_TERM_N) != 0)
+    return fail(VN_EINVAL, "vn_term_grads: term_mask = 0x%x must have at least one bit and none at or above bit %d", term_mask, VN_TERM_N);
+  for (int32_t i = 0; i < n; ++i)
+    if (batches[i] < 0 || batches[i] >= (int)h->batches.size() || !h->batches[batches[i]].set)
+      return fail(VN_EINVAL, "vn_term_grads: batches[%d] = %d names no registered batch", i, batches[i]);
+  (void)hipGetLastError();
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (int rc = term_scratch(h, true)) return rc;
+  const size_t P = (size_t)h->net.P;
+  // a term without rows is skipped: its mean is an empty one (vn_reduce_kernel), and so is its gradient
+  const bool rows[VN_TERM_N] = {h->bDof > 0 || h->es[VN_EDGE_FLUX].count > 0 || h->es[VN_EDGE_PERIODIC].count > 0, h->nB - h->bDof > 0,
+                                true, h->es[VN_EDGE_OBS].count > 0};
+  bool on[VN_TERM_N];
+  for (int k = 0; k < VN_TERM_N; ++k) on[k] = rows[k] && ((term_mask >> k) & 1u);
+  const double w_user[3] = {h->w[0], h->w[1], h->w[2]}, lambda_user = h->olambda;
+  double* const val = h->tg_out + VN_BAL_OUT;
+  int rc = VN_OK;
+  hipError_t e = hipMemsetAsync(val, 0, VN_TERM_N * sizeof(double), h->stream);
+  for (int k = 0; k < VN_TERM_N && rc == VN_OK && e == hipSuccess; ++k) {
+    float* Tk = h->tg_T + (size_t)k * P;
+    if (!on[k]) { e = hipMemsetAsync(Tk, 0, P * sizeof(float), h->stream); continue; }
+    for (int j = 0; j < 3; ++j) h->w[j] = j == k ? 1.0 : 0.0;
+    h->olambda = k == VN_TERM_OBS ? 1.0 : 0.0;
+    for (int32_t i = 0; i < n && rc == VN_OK && e == hipSuccess; ++i) {
+      rc = vn_grad(h, batches[i]);
+      if (rc == VN_OK)
+        e = vn_balance_accum_launch(Tk, h->gradbuf, h->net.P, i == 0, val + k, k == VN_TERM_OBS ? nullptr : h->gradbuf + P + 1 + k,
+                                    k == VN_TERM_OBS ? h->omisfit : nullptr, h->stream);
+    }
+  }
+  h->w[0] = w_user[0]; h->w[1] = w_user[1]; h->w[2] = w_user[2];
+  h->olambda = lambda_user;
+  if (rc != VN_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
+  HIPCHK(e);
+  HIPCHK(vn_balance_stats_launch(h->tg_T, VN_TERM_N, h->net.P, h->tg_part, h->tg_out, h->stream));
+  if (G_dev) HIPCHK(hipMemcpyAsync(G_dev, h->tg_T, VN_TERM_N * P * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  double out[VN_BAL_OUT + VN_TERM_N];
+  HIPCHK(hipMemcpyAsync(out, h->tg_out, sizeof(out), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  // (a skipped term's row of zeros would still carry a NaN of another term into the Gram matrix: 0 * NaN)
+  for (int a = 0; a < VN_TERM_N; ++a) {
+    for (int c = 0; c < 3; ++c) stats[a * 3 + c] = on[a] ? out[a * 3 + c] : 0.0;
+    for (int b = 0; b < VN_TERM_N; ++b) gram[a * VN_TERM_N + b] = on[a] && on[b] ? out[3 * VN_TERM_N + a * VN_TERM_N + b] : 0.0;
+    value[a] = on[a] ? out[VN_BAL_OUT + a] : 0.0;
+  }
+  return VN_OK;
 }
 
 static int apply_impl(vn_engine* h, float* loss_acc) {

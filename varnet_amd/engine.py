@@ -111,6 +111,9 @@ _SIGS = {
     'vn_set_weights': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'vn_bind_grad_buffer': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vn_grad': (C.c_int, [C.c_void_p, C.c_int32]),
+    'vn_term_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    'vn_term_grads': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_uint32, C.POINTER(C.c_double),
+                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     'vn_apply': (C.c_int, [C.c_void_p]),
     'vn_train_step': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     'vn_train_epoch': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
@@ -174,6 +177,10 @@ def reparam_layers(mode, per, layerWidth):
     if mode == 'rwf':
         return [int(w) for w in layerWidth] + [1]
     return [1] * len(layerWidth) if per == 'layer' else [int(w) for w in layerWidth]
+
+
+# the terms of the objective as vn_term_grads numbers them (VN_TERM_*)
+TERMS = ('bc', 'ic', 'var', 'obs')
 
 
 class VNError(RuntimeError):
@@ -994,6 +1001,54 @@ class VNEngine:
 
     def apply(self):
         self._ck(self.lib.vn_apply(self.h))
+
+    # -- per-term gradients (adaptive loss balancing) ---------------------------------------
+    def term_stats(self, T):
+        """Statistics of K <= 4 fp32 device vectors T [K, n] (vn_term_stats): {'stats': [K, 3] = (sumsq, sumabs, maxabs),
+        'gram': [K, K]}, fp64, reduced on the device in an order that depends on n alone.  Synchronises."""
+        if T is None:
+            K, n, ptr = 1, 1, None                 # (a null pointer is the library's to refuse)
+        else:
+            if T.dim() == 1:
+                T = T.reshape(1, -1)
+            if T.dtype != self.torch.float32 or not T.is_contiguous() or T.dim() != 2:
+                raise ValueError('term_stats: T must be a contiguous float32 tensor [K, n]')
+            K, n, ptr = int(T.shape[0]), int(T.shape[1]), _ptr(T)
+        stats, gram = np.zeros((max(K, 1), 3)), np.zeros((max(K, 1), max(K, 1)))
+        self._ck(self.lib.vn_term_stats(self.h, ptr, K, n, stats.ctypes.data_as(C.POINTER(C.c_double)),
+                                        gram.ctypes.data_as(C.POINTER(C.c_double))))
+        return {'stats': stats, 'gram': gram}
+
+    def term_grads(self, batches=(0,), terms=None, grads=False):
+        """Per-term gradients G_k of the objective over `batches` and their statistics (vn_term_grads): G_k is what grad() leaves
+        under the one-hot weights of term k ('bc', 'ic', 'var', 'obs'), summed over the batches.  Returns {'terms': TERMS,
+        'norm2', 'mean_abs', 'max_abs', 'value', 'sumsq', 'sumabs': [4], 'gram': [4, 4], 'G': [4, P] tensor (grads=True)}; a term that is not
+        in `terms` (default: all) or has no rows holds zeros.  The weights are the caller's afterwards; the gradient buffer and the
+        loss scalars are clobbered until the next grad().  Synchronises once."""
+        if terms is None:
+            mask = (1 << len(TERMS)) - 1
+        elif isinstance(terms, int):
+            mask = int(terms)
+        else:
+            mask = 0
+            for t in terms:
+                if t not in TERMS:
+                    raise ValueError('term_grads: unknown term %r (one of %s)' % (t, ', '.join(TERMS)))
+                mask |= 1 << TERMS.index(t)
+        batches = [int(b) for b in batches]
+        arr = (C.c_int32 * max(len(batches), 1))(*batches)
+        n_t = len(TERMS)
+        stats, gram, value = np.zeros((n_t, 3)), np.zeros((n_t, n_t)), np.zeros(n_t)
+        G = self.torch.empty((n_t, self.P), dtype=self.torch.float32, device=self.device) if grads else None
+        dp = C.POINTER(C.c_double)
+        self._ck(self.lib.vn_term_grads(self.h, arr, len(batches), mask, stats.ctypes.data_as(dp), gram.ctypes.data_as(dp),
+                                        value.ctypes.data_as(dp), _ptr(G)))
+        out = {'terms': TERMS, 'sumsq': stats[:, 0].copy(), 'norm2': np.sqrt(stats[:, 0]), 'sumabs': stats[:, 1].copy(),
+               'mean_abs': stats[:, 1] / self.P,
+               'max_abs': stats[:, 2].copy(), 'value': value, 'gram': gram}
+        if grads:
+            out['G'] = G
+        return out
 
     def train_step(self, batch=0, loss_out=None):
         self._ck(self.lib.vn_train_step(self.h, batch, _ptr(loss_out)))

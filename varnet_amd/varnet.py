@@ -14,7 +14,7 @@ constructor and `train / evaluate / residual / loadModel` surface
                                                     gradient over RCCL (torch.distributed)
   loss read back every step (VarNetUtility.py:1044) accumulated on device, read once per epoch
 
-Out of scope here: modelId='RNN', updateWeights, plots.
+Out of scope here: modelId='RNN', updateWeights (its working form is train(balance=...)), plots.
 """
 import collections
 import math
@@ -26,6 +26,7 @@ import warnings
 
 import numpy as np
 
+from . import balance as balance_rules
 from .finite_element import FE
 from .utility import UF
 
@@ -262,6 +263,7 @@ class TrainResult:
         self.inpIter = []
         self.error = [] if not uf.isnone(cExFlg) else None      # (always a list: callers pass a bool)
         self.lossVec = None
+        self.balanceHist = []             # (extension) one (epoch, weights, norms, cosines, skipped) per probe of train(balance=...)
         self.option_stopping = self.option_trainPoint = self.option_weighting = self.option_batchOptim = None
 
     # -- case file ------------------------------------------------------------------------------------
@@ -392,6 +394,10 @@ class TrainResult:
         L.append('\trequested weights: ' + str(g('weight')) + '\n')
         if g('updateWeights'):
             L.append('\tweights updated to maintain the requested balance between terms\n')
+        if g('balance') is not None:
+            b = balance_rules.parse_balance(g('balance'))
+            L.append('\tweights rebalanced from per-term gradient norms: rule %s, every %d epochs, alpha %s, cap %s, keepLoss %s\n'
+                     % (b['rule'], b['freq'], repr(b['alpha']), repr(b['cap']), b['keepLoss']))
         if g('normalizeW'):
             L.append('\tweights normalized by values so that weight times values have requested weights\n')
         if smp != 'uniform' and g('adjustWeight'):
@@ -2674,6 +2680,26 @@ class VarNet:
     def _is_lbfgs(self):
         return str(self.optimizer).lower() == 'lbfgs'
 
+    def termGradients(self, batches=None):
+        """The per-term gradients of the objective at the current parameters, as a diagnostic (vn_term_grads): {'terms', 'norms',
+        'values', 'cosines'} over ('bc', 'ic', 'var', 'obs') at unit weights, summed over `batches` (engine batch ids; default: the
+        mini-batches of the current training set).  A cosine near -1 says that two terms pull against each other; a term without
+        rows holds zeros.  The engine's weights are left as they are; its gradient buffer is overwritten."""
+        if self._towers is not None or self.world > 1:
+            raise NotImplementedError('termGradients with towers is not supported: each term\'s gradient would need its own all-reduce.')
+        if self._is_lbfgs():
+            raise NotImplementedError('termGradients with optimizer=\'lbfgs\' is not supported: the evaluations would disturb the '
+                                      'optimizer\'s gradient pair.')
+        tData = getattr(self, 'tData', None)
+        if tData is None:
+            tData = self.tData = self._build_tdata()
+        if batches is None:
+            tData.select_mor(0)
+            batches = tuple(tData.engine_batch(0, bi) for bi in range(tData.batchNum))
+        r = self.engine.term_grads(tuple(batches))
+        return {'terms': balance_rules.TERMS, 'norms': np.sqrt(r['sumsq']), 'values': np.array(r['value'], dtype=float),
+                'cosines': balance_rules.cosines(r['gram'])}
+
     def _lbfgs_refusals(self, batchNum, batchLen, shuffleData):
         """optimizer='lbfgs' builds its curvature pairs from consecutive gradients of ONE objective: whatever makes consecutive
         iterations see different ones is refused, with its reason."""
@@ -2728,17 +2754,33 @@ class VarNet:
               addTrainPts=True, suppFactor=1.0, multiTrainUpd=False, trainUpdelay=2e4, tolUpd=0.01,
               reinitrain=True, updateWeights=False, normalizeW=False, adjustWeight=False,
               useOriginalW=False, batchNum=None, batchLen=None, shuffleData=False, shuffleFreq=1,
-              dedup='auto', lossLag=None):
+              dedup='auto', lossLag=None, balance=None):
         """Training loop of /root/reference/VarNet.py:1197-1421 (uniform, random and residual-driven
         "optimal" sampling with re-initialisation and re-weighting).
 
         With `observations` the misfit joins the loss as obsWeight * O: obsWeight is on the scale of `weight`, multiplied by
         the factor trainWeight applies to the variational weight (`useOriginalW` leaves it unscaled); `adjustWeight` (which
-        raises the BC/IC weights at a re-draw) leaves it alone, and re-draws leave the observed points alone."""
+        raises the BC/IC weights at a re-draw) leaves it alone, and re-draws leave the observed points alone.
+
+        `balance` (extension; what the reference's `updateWeights` was meant to do): None | 'gradnorm' | 'maxmean' | {'rule',
+        'freq': 1000, 'alpha': 0.9, 'cap': 1e4, 'keepLoss': True}.  Before epoch 1 and before every epoch e with (e - 1) % freq == 0
+        the engine measures the gradient of every active term over the batches of the epoch (vn_term_grads) and the rule of
+        varnet_amd/balance.py moves the train weights; a lossLag block ends there, a re-draw restarts the moving average from the
+        weights it sets, and `trainRes.balanceHist` and the case file record every probe.  Refused with towers, L-BFGS and MOR."""
+        bal = balance_rules.parse_balance(balance)
+        if bal is not None:
+            if self._towers is not None or self.world > 1:
+                raise NotImplementedError('balance= with towers is not supported: each term\'s gradient would need its own all-reduce.')
+            if self._is_lbfgs():
+                raise NotImplementedError('balance= with optimizer=\'lbfgs\' is not supported: a probe would change the objective '
+                                          'between two iterations and disturb the optimizer\'s gradient pair.')
+            if not uf.isnone(self.PDE.MORvar):
+                raise NotImplementedError('balance= with model-order reduction is not supported: every MOR batch is another objective '
+                                          'and would need its own weights.')
         if self._is_lbfgs():
             self._lbfgs_refusals(batchNum, batchLen, shuffleData)
         if self._towers is not None:                  # controller of forked towers: every tower runs the loop
-            kw = {k: v for k, v in locals().items() if k not in ('self', 'folderpath')}
+            kw = {k: v for k, v in locals().items() if k not in ('self', 'folderpath', 'bal')}
             self.folderpath = folderpath
             self.trainRes = self._towers.call('train', folderpath, **kw)
             return self.trainRes
@@ -2768,7 +2810,7 @@ class VarNet:
         if shuffleData and getattr(self.PDE, 'ansatz', None) is not None:
             raise NotImplementedError('an ansatz with shuffleData=True is not supported: a shuffle permutes the BC/IC rows per feed '
                                       '(a per-batch copy), and the ansatz streams belong to the rows as they were registered')
-        argDict = {k: v for k, v in locals().items() if k != 'self'}
+        argDict = {k: v for k, v in locals().items() if k not in ('self', 'bal')}
 
         if not addTrainPts and np.abs(suppFactor - 1.0) > 1.e-15:
             warnings.warn('\'suppFactor\' is set to 1.0 since the number of training points does not change!')
@@ -2800,6 +2842,51 @@ class VarNet:
             return tW, w_e, lv
 
         trainW, w_eff, lossVal = set_train_weights(tData, weight)
+        if bal is not None:
+            # the train-scale weights of the four terms (bc, ic, var, obs) are what the rule moves
+            bal_rows = np.array([fd.bDofsum > 0 or bool((self.fluxRows or {}).get('edges'))
+                                 or bool((getattr(self, 'periodicRows', None) or {}).get('pairs')), bool(td), True,
+                                 self.obsRows is not None])
+
+            def balance_start(tW, wts):
+                """(w, w0, active, rho) from what trainWeight made of the requested weights `wts`: rho_k = weight_k / weight_var is
+                the user's stated preference (after a re-draw: with what adjustWeight made of it)."""
+                w4 = np.array([tW[0], tW[1], tW[2], self.obsWeight * self._obs_scale if self.obsRows is not None else 0.0], dtype=float)
+                w_user = np.array([wts[0], wts[1] if td else 0.0, wts[-1], self.obsWeight if self.obsRows is not None else 0.0],
+                                  dtype=float)
+                if not w_user[2] > 0.0:
+                    raise ValueError('balance= needs a variational weight > 0: the other weights are stated relative to it.')
+                return w4, w4.copy(), bal_rows & (w4 > 0.0), w_user / w_user[2]
+            bal_w, bal_w0, bal_active, bal_rho = balance_start(trainW, weight)
+            if int(np.sum(bal_active)) < 2:
+                raise ValueError('balance= needs at least two active terms (a weight > 0 and rows); this problem has %d.'
+                                 % int(np.sum(bal_active)))
+
+            def balance_probe(e):
+                nonlocal w_eff, bal_w
+                tData.select_mor(0)
+                ids = tuple(tData.engine_batch(0, bi) for bi in range(tData.batchNum))
+                names = [t for t, a in zip(balance_rules.TERMS, bal_active) if a]
+                r = eng.term_grads(ids, terms=names)
+                # BC, IC and observation rows are repeated in every (mini-batch, tower) feed and their engine weights divided by
+                # batchNum * puNum (towerWeights): the same factor makes the measured figures those of the epoch objective
+                f = 1.0 / (tData.batchNum * tData.puNum)
+                sc = np.array([f, f, 1.0, f])
+                new, skipped = balance_rules.update(bal['rule'], bal_w, bal_w0, bal_rho, bal_active, r['sumsq'] * sc * sc,
+                                                    r['max_abs'] * sc, r['mean_abs'] * sc, r['value'] * sc, bal['alpha'],
+                                                    bal['cap'], bal['keepLoss'])
+                if not skipped:
+                    bal_w = new
+                    w_eff = tData.towerWeights(bal_w[:3])
+                    eng.set_weights(w_eff)
+                    if self.obsRows is not None:
+                        self._obs_scale = float(bal_w[3]) / float(self.obsWeight) if self.obsWeight else self._obs_scale
+                        eng.set_obs_weight(self.obsWeight * self._obs_scale / tData.batchNum / tData.puNum)
+                norms = np.sqrt(r['sumsq']) * sc
+                trainRes.balanceHist.append((e, bal_w.copy(), norms, balance_rules.cosines(r['gram']), skipped))
+                trainRes.writeCase('epoch %d: balance (%s)%s weights %s, gradient norms %s\n'
+                                   % (e, bal['rule'], ' skipped (a zero or non-finite gradient norm),' if skipped else '',
+                                      np.array2string(bal_w, precision=4), np.array2string(norms, precision=4)))
         # what the reference stores is the array `updateDictFields('trainW', ...)` has divided IN PLACE by batchNum * puNum
         # (VarNet.py:1324-1325 keeps a reference to it, VarNetUtility.py:900-901 rewrites its BC/IC entries): the record in
         # trainData.vn therefore holds the per-feed weights, not trainWeight's return value
@@ -2848,8 +2935,12 @@ class VarNet:
         done = False
         while epoch <= epochNum and not done:
             nblk = 1
+            if bal is not None and (epoch - 1) % bal['freq'] == 0:
+                balance_probe(epoch)
             if lag > 1:
                 nblk = min(lag, epochNum - epoch + 1, saveFreq - (epoch - 1) % saveFreq)
+                if bal is not None:                                  # a block ends where the next probe sits, as it does at a re-draw
+                    nblk = min(nblk, bal['freq'] - (epoch - 1) % bal['freq'])
                 if shuffleData:
                     nblk = min(nblk, shuffleFreq - (epoch - 1) % shuffleFreq)
                 e_f = redraw_at(epoch)
@@ -2946,6 +3037,8 @@ class VarNet:
                         if adjustWeight:
                             weight = [5 * wv for wv in weight[:-1]] + [weight[-1]]
                         trainW, w_eff, _ = set_train_weights(tData, weight)
+                        if bal is not None:                          # the moving average restarts from the weights of the re-draw
+                            bal_w, bal_w0, bal_active, bal_rho = balance_start(trainW, weight)
             epoch = first + nblk
         trainRes.flushPlots()
         for lv in self.LEARNT:
