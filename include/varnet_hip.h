@@ -377,6 +377,48 @@ int vn_set_causal(vn_engine* h, int32_t batch, const int32_t* slab_dev, int32_t 
 /* omega_s of the batch's causal registration at the current parameters into omega_slab_host[n_slabs] (n_slabs as registered):
  * runs the batch's loss-only evaluation.  Synchronises; changes no engine state.  Without a causal registration: VN_ESTATE. */
 int vn_causal_weights(vn_engine* h, int32_t batch, double* omega_slab_host, int32_t n_slabs);
+/* Self-adaptive per-test-function weights: a state lambda_k >= 0 (fp32) per test function lives on the device and moves at every
+ * gradient step from that step's own unweighted loss field l_k = lossVec[k].  The weights in use are a
+ * function of the COMMITTED state only,
+ *     omega_k = m(lambda_k) / Z,   m(x) = x^power (power 1 or 2),   Z = mean_j m(lambda_j) if normalize else 1,
+ * constant for the gradient like every other weight, and the same in vn_grad / vn_train_step / vn_train_epoch, vn_eval_loss,
+ * vn_term_grads and vn_objective_f64 (widened exactly): the loss vn_eval_loss reports is the loss the step trained on.  The update
+ * is formed from the step's l_k at theta_t and takes effect from the NEXT step (omega lags one step, for both rules):
+ *   rule 1, rba   lambda'_k = gamma lambda_k + eta sqrt(l_k) / max_j sqrt(l_j);  lambda <= max(init, eta / (1 - gamma)) throughout.
+ *   rule 2, sa    Adam ascent on lambda with g_k = m'(lambda_k) l_k / mean_j l_j (fp64 mean in a fixed order), slots m1, m2, the
+ *                 bias-corrected rate of update tau + 1, then clamped to [0, cap].
+ *   rule 0        clears the registration (par and lambda_init_dev are not read).
+ * If max_j l_j (rba) or mean_j l_j (sa) is zero or not finite the state does not move: lambda, slots and tau are kept.
+ *   par[10]   [0], [1] = (gamma, eta) of rba or (lr, cap) of sa;  [2], [3], [4] = beta1, beta2, eps of sa (ignored by rba);
+ *             [5] power;  [6] init;  [7] normalize (0 or 1);  [8] every (updates are enqueued only at gradient evaluations whose
+ *             step index -- optimizer steps completed before them -- is a multiple of it; other steps cost a static-weights
+ *             step);  [9] reserved.  VN_EINVAL for gamma outside [0, 1], eta < 0, lr < 0, cap <= 0, beta outside [0, 1),
+ *             eps <= 0, power not 1 or 2, init < 0, normalize not 0 or 1, every not a whole number >= 1, any entry not finite.
+ *   lambda_init_dev  [n_k] device floats, VALIDATED on the device (finite, >= 0; else VN_EINVAL) and COPIED at this call, which
+ *             therefore synchronises; any alignment.  NULL: par[6] everywhere.  vn_params_init returns to this initial state.
+ * Commit protocol (vn_train_step == vn_grad + vn_apply stays bit for bit): vn_grad of a registered batch applies omega(lambda)
+ * and writes the PENDING state (lambda', slots', omega', Z', tau', statistics) into the second half of a double buffer;
+ * vn_apply -- and the step vn_train_step / vn_train_epoch fold into the reduction -- commits every pending state by swapping
+ * the halves, without a copy.  vn_grad twice without vn_apply recomputes the same pending bits.  vn_eval_loss, vn_term_grads,
+ * vn_objective_f64 and every other loss-only call leave committed state, pending state and pending flag as they found them.
+ * Three n_k-sized launches per updating step (vn_adapt.hip) over a static-weights step; fp64 folds in a fixed order on a grid
+ * fixed by n_k alone, no floating-point atomics: two runs give the same bits on any card.
+ * Registration as for vn_set_tf_weights: per batch, after vn_set_interior (a new one clears it); it and a static or causal
+ * registration of the batch replace each other; VN_ESTATE / VN_EINVAL (n_k == 0) as there.  VN_EUNSUPPORTED: VN_KERNEL_FUSED;
+ * a handle with a communicator, and vn_comm_init on a handle with an adaptive batch (a shard's max, mean and Z are not the
+ * batch's); vn_lbfgs_step on an adaptive batch (the causal refusal, for the same reason); learnt vectors, as for every weight.
+ * vn_state_snapshot / _rollback and vn_state_size / _export / _import carry (scalars incl. Z and tau, lambda, omega, slots) of
+ * every registered batch in batch order after the optimizer state; with none registered their layout is unchanged.  BC / IC
+ * rows stay unweighted. */
+int vn_set_tf_adapt(vn_engine* h, int32_t batch, int32_t rule, const double par[10], const float* lambda_init_dev);
+/* The committed state of the batch's adaptive registration: lambda_host [n_k], omega_host [n_k], slots_host [2 n_k] (m1 | m2; sa
+ * only, VN_EINVAL for rba), stats[6] = min, max, mean omega, effective sample share (sum omega)^2 / (n_k sum omega^2), Z, tau
+ * (updates that moved the state).  Any output pointer may be NULL.  Synchronises; changes no engine state.  Without an adaptive
+ * registration: VN_ESTATE. */
+int vn_get_tf_adapt(vn_engine* h, int32_t batch, float* lambda_host, float* omega_host, float* slots_host, double stats[6]);
+/* Puts a state back (a checkpoint): lambda_host [n_k] (finite, >= 0), slots_host [2 n_k] (sa; NULL: zeros; VN_EINVAL for rba),
+ * tau >= 0.  omega, Z and the statistics are rebuilt on the device, a pending state is dropped.  Synchronises. */
+int vn_set_tf_adapt_state(vn_engine* h, int32_t batch, const float* lambda_host, const float* slots_host, int64_t tau);
 /* Inverse mode: learn the nine polynomial coefficients next to the parameters.  Index 0..2 = (c1, c2, c3) of the reaction,
  * 3..5 = (f1, f2, f3) of the flux, 6..8 = (d0, d1, d2) of the diffusivity.  While learning is on the engine owns ONE device
  * vector of nine fp32 coefficients (`init`, rounded once), shared by every batch; every registered term of every batch reads its

@@ -14,6 +14,7 @@
 #include "vn_split16.h"
 #include "vn_reparam.h"
 #include "vn_balance.h"
+#include "vn_adapt.h"
 
 hipError_t vn_calibrate_f64(int ncu, hipStream_t s, double ghz, double out[3]);      // vn_calib.hip (fp64 MFMA loop)
 
@@ -77,6 +78,20 @@ struct Ansatz {
   const float* b = nullptr;
 };
 
+// The self-adaptive weights of one batch (vn_set_tf_adapt): parameters, the double-buffered device state and its snapshot.
+// f: 13 pieces of `stride` floats -- half 0 and half 1 as (lambda | omega | m1 | m2), the initial lambda, the snapshot's four;
+// d: scalars of half 0, half 1 and the snapshot (VN_ADAPT_SCAL each), then the kernels' partials.
+struct Adapt {
+  int rule = VN_ADAPT_NONE, power = 2, normalize = 1;
+  long every = 1;
+  double par[10] = {};
+  long n_k = 0, stride = 0;
+  float* f = nullptr;
+  double* d = nullptr;
+  int cur = 0;                 // the committed half
+  bool pending = false;        // the other half holds the update of a gradient evaluation that no optimizer step has committed
+};
+
 struct Batch {
   const float* Input = nullptr;
   const float* gcoef = nullptr;
@@ -117,6 +132,8 @@ struct Batch {
   // per-test-function loss weights (vn_weights.hip): static (vn_set_tf_weights) or causal (vn_set_causal); as initialised: none
   VnWeightsReg wt;
   int* wt_own = nullptr;      // owned: the causal registration's slab ids and CSR, one allocation (wt.slab / wt.sptr / wt.sidx)
+  // self-adaptive weights (vn_set_tf_adapt, vn_adapt.hip), owned; while registered, wt.omega is its committed omega buffer
+  Adapt* ad = nullptr;
   // hard-constraint ansatz (vn_ansatz.hip): the interior rows' streams (vn_set_ansatz) and those of the map's unique points
   // (vn_set_ansatz_points); as initialised here: none
   Ansatz az, azp;
@@ -287,6 +304,7 @@ struct vn_engine {
   float* wt_lvec = nullptr; long wt_lvec_cap = 0;
   float* wt_omega = nullptr; long wt_omega_cap = 0;
   float* wt_stat = nullptr; long wt_stat_cap = 0;
+  bool ad_quiet = false;       // vn_term_grads' probes: gradient evaluations that leave every adaptive state (vn_set_tf_adapt) alone
   // the edge row sets by VnEdgeId (es[id].count == 0: none registered), then what each kind keeps beside its record, caller-owned:
   // boundary-flux rows (vn_set_flux_bc), nF = count rows with their normals in G
   EdgeSet es[VN_EDGE_N];
@@ -790,10 +808,86 @@ inline float* weights_lossvec(const vn_engine* h, const Batch& b, float* lossVec
   return lossVec || !has_weights(b) ? lossVec : h->wt_lvec;
 }
 
+// ---- self-adaptive weights (vn_adapt.hip): the state of a batch, double-buffered ----
+inline VnAdaptState adapt_half(const Adapt& ad, int piece0, int scal) {
+  VnAdaptState s;
+  float* f = ad.f + (long)piece0 * ad.stride;
+  s.lambda = f; s.omega = f + ad.stride;
+  if (ad.rule == VN_ADAPT_SA) { s.m1 = f + 2 * ad.stride; s.m2 = f + 3 * ad.stride; }
+  s.scal = ad.d + (long)scal * VN_ADAPT_SCAL;
+  return s;
+}
+inline VnAdaptState adapt_state(const Adapt& ad, int half) { return adapt_half(ad, 4 * half, half); }
+inline VnAdaptState adapt_snap(const Adapt& ad) { return adapt_half(ad, 9, 2); }
+inline float* adapt_lambda0(const Adapt& ad) { return ad.f + 8 * ad.stride; }
+constexpr long kAdaptPieces = 13;
+constexpr long kAdaptDoubles = 3L * VN_ADAPT_SCAL + 6L * VN_ADAPT_MAX_BLOCKS;
+
+VnAdaptArgs adapt_args(const Adapt& ad, int rule, int from, int to) {
+  VnAdaptArgs a;
+  a.rule = rule; a.power = ad.power; a.normalize = ad.normalize; a.n_k = ad.n_k;
+  if (ad.rule == VN_ADAPT_RBA) { a.gamma = (float)ad.par[0]; a.eta = (float)ad.par[1]; }
+  else { a.lr = ad.par[0]; a.cap = (float)ad.par[1]; a.beta1 = ad.par[2]; a.beta2 = ad.par[3]; a.eps = ad.par[4]; }
+  a.cur = adapt_state(ad, from); a.next = adapt_state(ad, to);
+  a.part = ad.d + 3L * VN_ADAPT_SCAL;
+  return a;
+}
+
+// The index of the step a gradient evaluation belongs to: steps completed before it (the folded step has counted itself already)
+inline int64_t adapt_step_index(const vn_engine* h) { return h->step - (h->fuse.kind >= 0 ? 1 : 0); }
+
+// omega, Z and the statistics of the committed half rebuilt from its lambda (in place); nothing is pending afterwards
+int adapt_rebuild(vn_engine* h, Adapt& ad) {
+  HIPCHK(vn_adapt_update_launch(adapt_args(ad, VN_ADAPT_NONE, ad.cur, ad.cur), h->stream));
+  ad.pending = false;
+  return VN_OK;
+}
+
+// Back to the registered initial state: lambda = its initial values, slots and tau zero
+int adapt_reset(vn_engine* h, Adapt& ad) {
+  const VnAdaptState s = adapt_state(ad, ad.cur);
+  const size_t nb = (size_t)ad.n_k * sizeof(float);
+  HIPCHK(hipMemcpyAsync(s.lambda, adapt_lambda0(ad), nb, hipMemcpyDeviceToDevice, h->stream));
+  if (s.m1) HIPCHK(hipMemsetAsync(s.m1, 0, 2 * (size_t)ad.stride * sizeof(float), h->stream));
+  HIPCHK(hipMemsetAsync(s.scal, 0, VN_ADAPT_SCAL * sizeof(double), h->stream));
+  return adapt_rebuild(h, ad);
+}
+
+// The optimizer step's share: every pending state becomes the committed one -- the halves swap, nothing is copied
+void adapt_commit(vn_engine* h) {
+  for (Batch& b : h->batches)
+    if (b.ad && b.ad->pending) {
+      b.ad->cur ^= 1;
+      b.ad->pending = false;
+      b.wt.omega = adapt_state(*b.ad, b.ad->cur).omega;
+    }
+}
+void adapt_drop_pending(vn_engine* h) {
+  for (Batch& b : h->batches)
+    if (b.ad) b.ad->pending = false;
+}
+inline bool adapt_any(const vn_engine* h) {
+  for (const Batch& b : h->batches)
+    if (b.ad) return true;
+  return false;
+}
+// bytes of a batch's state in vn_state_export: scalars, lambda, omega[, m1, m2]
+inline int64_t adapt_bytes(const Adapt& ad) {
+  return (int64_t)(VN_ADAPT_SCAL * sizeof(double)) + (int64_t)(ad.rule == VN_ADAPT_SA ? 4 : 2) * ad.n_k * (int64_t)sizeof(float);
+}
+
 // After the seed kernel and every term's seed kernel: [causal: the weights from lossVec], stf scaled (de-duplicated step),
 // the var loss partials of the seed kernel's blocks (tfb test functions each) replaced, the rows' seeds scaled (row-wise routes)
 int weights_stage(vn_engine* h, const Batch& b, const float* lossVec, int tfb, float* stf, float* part, bool rows) {
   if (!has_weights(b)) return VN_OK;
+  // self-adaptive weights: a gradient evaluation (the only caller with seeds to scale) also forms the pending state from its
+  // own loss field; it reads the committed half and writes the other, so the weights applied below are the committed ones
+  if (b.ad && (rows || stf) && !h->ad_quiet && adapt_step_index(h) % b.ad->every == 0) {
+    VnAdaptArgs a = adapt_args(*b.ad, b.ad->rule, b.ad->cur, b.ad->cur ^ 1);
+    a.lossVec = lossVec;
+    HIPCHK(vn_adapt_update_launch(a, h->stream));
+    b.ad->pending = true;
+  }
   const bool causal = b.wt.S > 0;
   HIPCHK(vn_weights_apply_f32(b.wt, weights_work(h), lossVec, b.n_k, tfb, causal ? h->wt_omega : nullptr, stf, part, h->stream));
   if (rows)
@@ -804,6 +898,12 @@ int weights_stage(vn_engine* h, const Batch& b, const float* lossVec, int tfb, f
 void clear_weights(Batch& b) {
   if (b.wt_own) (void)hipFree(b.wt_own);
   b.wt_own = nullptr;
+  if (b.ad) {
+    if (b.ad->f) (void)hipFree(b.ad->f);
+    if (b.ad->d) (void)hipFree(b.ad->d);
+    delete b.ad;
+    b.ad = nullptr;
+  }
   b.wt = VnWeightsReg();
 }
 
@@ -1735,6 +1835,11 @@ int vn_params_init(vn_engine* h, uint64_t seed) {
     HIPCHK(hipMemsetAsync(h->rp.sc + S, 0, 2 * S * sizeof(float), h->stream));
     if (int rc = reparam_factorise(h)) return rc;
   }
+  for (Batch& b : h->batches)   // self-adaptive weights start over from their registered initial state
+    if (b.ad) {
+      if (int rc = adapt_reset(h, *b.ad)) return rc;
+      b.wt.omega = adapt_state(*b.ad, b.ad->cur).omega;
+    }
   HIPCHK(hipStreamSynchronize(h->stream));
   h->step = 0;
   lbfgs_invalidate(h);
@@ -1765,6 +1870,8 @@ int vn_params_set(vn_engine* h, const float* host, int64_t n) {
 int vn_state_size(const vn_engine* h, int64_t* bytes) {
   if (!h || !bytes) return fail(VN_EINVAL, "null argument");
   *bytes = (int64_t)sizeof(int64_t) + 3ll * h->net.P * (int64_t)sizeof(float);
+  for (const Batch& b : h->batches)   // the adaptive state of every registered batch, in batch order (none registered: nothing)
+    if (b.ad) *bytes += adapt_bytes(*b.ad);
   return VN_OK;
 }
 
@@ -1781,6 +1888,16 @@ int vn_state_export(vn_engine* h, void* host, int64_t bytes) {
   HIPCHK(hipMemcpyAsync(p, h->theta, nb, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(p + nb, h->m, nb, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(p + 2 * nb, h->v, nb, hipMemcpyDeviceToHost, h->stream));
+  p += 3 * nb;
+  for (const Batch& b : h->batches)
+    if (b.ad) {
+      const VnAdaptState s = adapt_state(*b.ad, b.ad->cur);
+      const size_t nk = (size_t)b.ad->n_k * sizeof(float);
+      HIPCHK(hipMemcpyAsync(p, s.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      p += VN_ADAPT_SCAL * sizeof(double);
+      for (const float* piece : {(const float*)s.lambda, (const float*)s.omega, (const float*)s.m1, (const float*)s.m2})
+        if (piece) { HIPCHK(hipMemcpyAsync(p, piece, nk, hipMemcpyDeviceToHost, h->stream)); p += nk; }
+    }
   HIPCHK(hipStreamSynchronize(h->stream));
   return VN_OK;
 }
@@ -1805,6 +1922,12 @@ int vn_state_snapshot(vn_engine* h) {
     HIPCHK(hipMemcpyAsync(h->rp.snap, h->rp.V, nb, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->rp.snap + h->net.P, h->rp.sc, 4 * S * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   }
+  for (const Batch& b : h->batches)   // self-adaptive weights: the committed half (a pending one belongs to no step yet)
+    if (b.ad) {
+      const VnAdaptState s = adapt_state(*b.ad, b.ad->cur), t = adapt_snap(*b.ad);
+      HIPCHK(hipMemcpyAsync(t.lambda, s.lambda, 4 * (size_t)b.ad->stride * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(t.scal, s.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    }
   h->snap_step = h->step;
   return VN_OK;
 }
@@ -1824,6 +1947,13 @@ int vn_state_rollback(vn_engine* h) {
     HIPCHK(hipMemcpyAsync(h->rp.V, h->rp.snap, nb, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->rp.sc, h->rp.snap + h->net.P, 4 * S * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   }
+  for (Batch& b : h->batches)
+    if (b.ad) {
+      const VnAdaptState s = adapt_state(*b.ad, b.ad->cur), t = adapt_snap(*b.ad);
+      HIPCHK(hipMemcpyAsync(s.lambda, t.lambda, 4 * (size_t)b.ad->stride * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(s.scal, t.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+      b.ad->pending = false;
+    }
   h->step = h->snap_step;
   return VN_OK;
 }
@@ -1845,6 +1975,17 @@ int vn_state_import(vn_engine* h, const void* host, int64_t bytes) {
   }
   if (reparam_on(h))            // V from the imported theta_eff with the current s; a full restore calls vn_set_reparam_state next
     if (int rc = reparam_factorise(h)) return rc;
+  p += 3 * nb;
+  for (Batch& b : h->batches)
+    if (b.ad) {
+      const VnAdaptState s = adapt_state(*b.ad, b.ad->cur);
+      const size_t nk = (size_t)b.ad->n_k * sizeof(float);
+      HIPCHK(hipMemcpyAsync(s.scal, p, VN_ADAPT_SCAL * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      p += VN_ADAPT_SCAL * sizeof(double);
+      for (float* piece : {s.lambda, s.omega, s.m1, s.m2})
+        if (piece) { HIPCHK(hipMemcpyAsync(piece, p, nk, hipMemcpyHostToDevice, h->stream)); p += nk; }
+      b.ad->pending = false;
+    }
   HIPCHK(hipStreamSynchronize(h->stream));
   lbfgs_invalidate(h);
   return VN_OK;
@@ -2393,6 +2534,132 @@ int vn_causal_weights(vn_engine* h, int32_t batch, double* omega_slab_host, int3
   return VN_OK;
 }
 
+// ---- self-adaptive weights (vn_adapt.hip) ----
+// par: [0], [1] = (gamma, eta) of rba or (lr, cap) of sa; [2..4] = beta1, beta2, eps of sa; [5] power; [6] init; [7] normalize;
+// [8] every; [9] reserved
+int vn_set_tf_adapt(vn_engine* h, int32_t batch, int32_t rule, const double par[10], const float* lambda_init_dev) {
+  const bool clear = rule == VN_ADAPT_NONE;
+  if (!clear) {
+    if (rule != VN_ADAPT_RBA && rule != VN_ADAPT_SA) return fail(VN_EINVAL, "vn_set_tf_adapt: rule = %d is none of 0 (clear), 1 (rba), 2 (sa)", rule);
+    if (!par) return fail(VN_EINVAL, "vn_set_tf_adapt: null parameter array");
+    for (int i = 0; i < 10; ++i)
+      if (!std::isfinite(par[i])) return fail(VN_EINVAL, "vn_set_tf_adapt: par[%d] = %g is not finite", i, par[i]);
+    if (rule == VN_ADAPT_RBA) {
+      if (!(par[0] >= 0.0 && par[0] <= 1.0)) return fail(VN_EINVAL, "vn_set_tf_adapt: rba gamma = %g must lie in [0, 1]", par[0]);
+      if (!(par[1] >= 0.0)) return fail(VN_EINVAL, "vn_set_tf_adapt: rba eta = %g must be >= 0", par[1]);
+    } else {
+      if (!(par[0] >= 0.0)) return fail(VN_EINVAL, "vn_set_tf_adapt: sa lr = %g must be >= 0", par[0]);
+      if (!(par[1] > 0.0)) return fail(VN_EINVAL, "vn_set_tf_adapt: sa cap = %g must be positive", par[1]);
+      if (!(par[2] >= 0.0 && par[2] < 1.0) || !(par[3] >= 0.0 && par[3] < 1.0))
+        return fail(VN_EINVAL, "vn_set_tf_adapt: sa beta1 = %g, beta2 = %g must lie in [0, 1)", par[2], par[3]);
+      if (!(par[4] > 0.0)) return fail(VN_EINVAL, "vn_set_tf_adapt: sa eps = %g must be positive", par[4]);
+    }
+    if (par[5] != 1.0 && par[5] != 2.0) return fail(VN_EINVAL, "vn_set_tf_adapt: power = %g must be 1 or 2", par[5]);
+    if (!(par[6] >= 0.0)) return fail(VN_EINVAL, "vn_set_tf_adapt: init = %g must be >= 0", par[6]);
+    if (par[7] != 0.0 && par[7] != 1.0) return fail(VN_EINVAL, "vn_set_tf_adapt: normalize = %g must be 0 or 1", par[7]);
+    if (!(par[8] >= 1.0) || par[8] != std::floor(par[8]) || par[8] > 1e15)
+      return fail(VN_EINVAL, "vn_set_tf_adapt: every = %g must be a whole number >= 1", par[8]);
+    if (h && h->comm)
+      return fail(VN_EUNSUPPORTED, "vn_set_tf_adapt under a communicator: a rank's max, mean and Z would cover only its shard, so the "
+                                   "ranks together would train another objective than one rank");
+  }
+  if (int rc = weights_common(h, batch, clear, "vn_set_tf_adapt")) return rc;
+  if (clear) return VN_OK;
+  Batch& b = h->batches[batch];
+  const long n_k = b.n_k;
+  Adapt* ad = new Adapt();
+  ad->rule = rule; ad->power = (int)par[5]; ad->normalize = (int)par[7]; ad->every = (long)par[8];
+  std::copy(par, par + 10, ad->par);
+  ad->n_k = n_k; ad->stride = vn_adapt_stride(n_k);
+  hipError_t e = hipMalloc((void**)&ad->f, (size_t)(kAdaptPieces * ad->stride) * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&ad->d, (size_t)kAdaptDoubles * sizeof(double));
+  if (e == hipSuccess) e = hipMemsetAsync(ad->f, 0, (size_t)(kAdaptPieces * ad->stride) * sizeof(float), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(ad->d, 0, (size_t)kAdaptDoubles * sizeof(double), h->stream);
+  int rc = VN_OK;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    rc = fail(VN_ENOMEM, "vn_set_tf_adapt: the state of %ld test functions does not fit: %s", n_k, hipGetErrorString(e));
+  } else if (lambda_init_dev) {   // validated on the device (finite, >= 0) and copied: the caller's array need not outlive the call
+    int bad = 0;
+    auto check = [&](int* err_dev) { return vn_adapt_check_copy_launch(lambda_init_dev, n_k, adapt_lambda0(*ad), err_dev, h->stream); };
+    rc = count_on_device(h, check, &bad);
+    if (rc == VN_OK && bad) rc = fail(VN_EINVAL, "vn_set_tf_adapt: %d initial lambda(s) negative or not finite", bad);
+  } else {
+    e = vn_adapt_fill_launch(adapt_lambda0(*ad), n_k, (float)par[6], h->stream);
+    if (e != hipSuccess) rc = fail(VN_EHIP, "vn_set_tf_adapt: %s", hipGetErrorString(e));
+  }
+  if (rc == VN_OK) rc = adapt_reset(h, *ad);
+  if (rc == VN_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(VN_EHIP, "vn_set_tf_adapt: the initial state could not be formed");
+  if (rc != VN_OK) {            // the batch keeps what it had
+    if (ad->f) (void)hipFree(ad->f);
+    if (ad->d) (void)hipFree(ad->d);
+    delete ad;
+    return rc;
+  }
+  lbfgs_invalidate(h, batch);
+  clear_weights(b);                                  // replaces a static, a causal or an earlier adaptive registration
+  b.ad = ad;
+  b.wt.omega = adapt_state(*ad, ad->cur).omega;
+  return VN_OK;
+}
+
+static int adapt_of(vn_engine* h, int32_t batch, const char* who, Adapt** ad) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (batch < 0 || batch >= (int)h->batches.size() || !h->batches[batch].set)
+    return fail(VN_ESTATE, "batch %d has no interior data (call vn_set_interior first)", batch);
+  if (!h->batches[batch].ad) return fail(VN_ESTATE, "%s: batch %d has no adaptive registration (call vn_set_tf_adapt first)", who, batch);
+  *ad = h->batches[batch].ad;
+  return VN_OK;
+}
+
+int vn_get_tf_adapt(vn_engine* h, int32_t batch, float* lambda_host, float* omega_host, float* slots_host, double stats[6]) {
+  Adapt* ad = nullptr;
+  if (int rc = adapt_of(h, batch, "vn_get_tf_adapt", &ad)) return rc;
+  const VnAdaptState s = adapt_state(*ad, ad->cur);
+  if (slots_host && !s.m1) return fail(VN_EINVAL, "vn_get_tf_adapt: batch %d runs the rba rule, which has no slots", batch);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t nk = (size_t)ad->n_k * sizeof(float);
+  if (lambda_host) HIPCHK(hipMemcpyAsync(lambda_host, s.lambda, nk, hipMemcpyDeviceToHost, h->stream));
+  if (omega_host) HIPCHK(hipMemcpyAsync(omega_host, s.omega, nk, hipMemcpyDeviceToHost, h->stream));
+  if (slots_host) {
+    HIPCHK(hipMemcpyAsync(slots_host, s.m1, nk, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(slots_host + ad->n_k, s.m2, nk, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (stats) HIPCHK(hipMemcpyAsync(stats, s.scal, 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return VN_OK;
+}
+
+int vn_set_tf_adapt_state(vn_engine* h, int32_t batch, const float* lambda_host, const float* slots_host, int64_t tau) {
+  Adapt* ad = nullptr;
+  if (int rc = adapt_of(h, batch, "vn_set_tf_adapt_state", &ad)) return rc;
+  if (!lambda_host) return fail(VN_EINVAL, "vn_set_tf_adapt_state: null lambda");
+  if (tau < 0) return fail(VN_EINVAL, "vn_set_tf_adapt_state: tau = %lld must be >= 0", (long long)tau);
+  if (slots_host && ad->rule != VN_ADAPT_SA) return fail(VN_EINVAL, "vn_set_tf_adapt_state: batch %d runs the rba rule, which has no slots", batch);
+  for (long k = 0; k < ad->n_k; ++k)
+    if (!(lambda_host[k] >= 0.f && std::isfinite(lambda_host[k])))
+      return fail(VN_EINVAL, "vn_set_tf_adapt_state: lambda[%ld] = %g is negative or not finite", k, (double)lambda_host[k]);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const VnAdaptState s = adapt_state(*ad, ad->cur);
+  const size_t nk = (size_t)ad->n_k * sizeof(float);
+  double scal[VN_ADAPT_SCAL] = {};
+  scal[5] = (double)tau;
+  HIPCHK(hipMemcpyAsync(s.lambda, lambda_host, nk, hipMemcpyHostToDevice, h->stream));
+  if (s.m1) {                   // NULL slots: zeros
+    if (slots_host) {
+      HIPCHK(hipMemcpyAsync(s.m1, slots_host, nk, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(s.m2, slots_host + ad->n_k, nk, hipMemcpyHostToDevice, h->stream));
+    } else {
+      HIPCHK(hipMemsetAsync(s.m1, 0, 2 * (size_t)ad->stride * sizeof(float), h->stream));
+    }
+  }
+  HIPCHK(hipMemcpyAsync(s.scal, scal, sizeof scal, hipMemcpyHostToDevice, h->stream));
+  if (int rc = adapt_rebuild(h, *ad)) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));   // the host arrays may be released on return
+  lbfgs_invalidate(h, batch);
+  return VN_OK;
+}
+
 int vn_set_bic(vn_engine* h, const float* biInput, const float* biLabel, int64_t nB, int64_t bDof, double biDimVal) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (nB < 0 || bDof < 0 || bDof > nB) return fail(VN_EINVAL, "need 0 <= bDof <= nB");
@@ -2828,7 +3095,9 @@ int vn_term_grads(vn_engine* h, const int32_t* batches, int32_t n, uint32_t term
     for (int j = 0; j < 3; ++j) h->w[j] = j == k ? 1.0 : 0.0;
     h->olambda = k == VN_TERM_OBS ? 1.0 : 0.0;
     for (int32_t i = 0; i < n && rc == VN_OK && e == hipSuccess; ++i) {
+      h->ad_quiet = true;       // a probe: committed state, pending state and pending flag of adaptive weights stay as they are
       rc = vn_grad(h, batches[i]);
+      h->ad_quiet = false;
       if (rc == VN_OK)
         e = vn_balance_accum_launch(Tk, h->gradbuf, h->net.P, i == 0, val + k, k == VN_TERM_OBS ? nullptr : h->gradbuf + P + 1 + k,
                                     k == VN_TERM_OBS ? h->omisfit : nullptr, h->stream);
@@ -2859,6 +3128,7 @@ static int apply_impl(vn_engine* h, float* loss_acc) {
   if (h->cfg.optimizer == VN_OPT_RMSPROP) {
     HIPCHK(vn_rmsprop_launch(h->theta, h->m, h->v, h->gradbuf, h->net.P, (float)h->cfg.lr, 0.9f, 0.0f, 1e-10f, loss_acc,
                              h->stream));
+    adapt_commit(h);
     h->step += 1;
     return VN_OK;
   }
@@ -2879,6 +3149,7 @@ static int apply_impl(vn_engine* h, float* loss_acc) {
   for (int id = 0; id < LV_N; ++id)
     if (h->lv[id].on)
       if (int rc = learnt_finish(h, id, false, true, t)) return rc;
+  adapt_commit(h);              // self-adaptive weights: the pending states of the gradient evaluations this step applies
   h->step += 1;
   return VN_OK;
 }
@@ -2918,7 +3189,8 @@ static int step_fused(vn_engine* h, int32_t batch, float* loss_acc) {
   h->fuse = o;
   const int rc = vn_grad(h, batch);
   h->fuse = VnOptArgs();
-  if (rc) h->step -= 1;
+  if (rc) { h->step -= 1; adapt_drop_pending(h); }
+  else adapt_commit(h);
   return rc;
 }
 
@@ -2988,6 +3260,10 @@ int vn_lbfgs_step(vn_engine* h, int32_t batch, int32_t max_trials, double info[1
                                  "the parameters but are held constant for the gradient, so the search direction is not the gradient "
                                  "of the reported loss and an Armijo test on it means nothing; static weights (vn_set_tf_weights) work",
                 batch);
+  if (h->batches[batch].ad)
+    return fail(VN_EUNSUPPORTED, "vn_lbfgs_step on batch %d, which has an adaptive registration (vn_set_tf_adapt): its weights move from "
+                                 "step to step but are held constant for the gradient, so an Armijo test across steps means nothing; "
+                                 "static weights (vn_set_tf_weights) work", batch);
   if (h->lb_loss64 && has_ansatz(h->batches[batch]))
     return fail(VN_EUNSUPPORTED, "vn_lbfgs_step with vn_lbfgs_loss64 on batch %d, which has a hard-constraint ansatz (vn_set_ansatz): the "
                                  "fp64 objective does not carry the ansatz stage", batch);
@@ -3262,6 +3538,10 @@ int vn_comm_init(vn_engine* h, int32_t rank, int32_t world, const void* unique_i
     if (h->batches[i].wt.S > 0)
       return fail(VN_EUNSUPPORTED, "vn_comm_init: batch %d has a causal registration (vn_set_causal); a rank's slab means would cover "
                                    "only its shard, so the ranks together would train another objective than one rank", (int)i);
+  for (size_t i = 0; i < h->batches.size(); ++i)
+    if (h->batches[i].ad)
+      return fail(VN_EUNSUPPORTED, "vn_comm_init: batch %d has an adaptive registration (vn_set_tf_adapt); a rank's max, mean and Z would "
+                                   "cover only its shard, so the ranks together would train another objective than one rank", (int)i);
   for (int id = LV_N - 1; id >= 0; --id)       // (the field amplitudes are reported first)
     if (h->lv[id].on)
       return fail(VN_EUNSUPPORTED, "vn_comm_init while %s are learnt (%s): %s are not in the all-reduced buffer, so every rank would "

@@ -77,6 +77,9 @@ _SIGS = {
     'vn_set_tf_weights': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     'vn_set_causal': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double]),
     'vn_causal_weights': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int32]),
+    'vn_set_tf_adapt': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p]),
+    'vn_get_tf_adapt': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    'vn_set_tf_adapt_state': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     'vn_set_coef_learn': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                     C.POINTER(C.c_double), C.c_double]),
     'vn_get_coefs': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -163,6 +166,64 @@ LEARNT = {'coef': ('coefs', 9), 'source': ('source_amps', None), 'field': ('fiel
 # learnt weight scales (vn_set_reparam): VN_REPARAM_* and VN_REPARAM_PER_*
 REPARAM_MODES = {'rwf': 1, 'slope': 2}
 REPARAM_PER = {'neuron': 0, 'layer': 1}
+
+# self-adaptive test-function weights (vn_set_tf_adapt): the rules, their own keys with defaults, and the keys both share
+ADAPT_RULES = {'rba': 1, 'sa': 2}
+ADAPT_OWN = {'rba': {'gamma': 0.999, 'eta': 0.01},
+             'sa': {'lr': 0.005, 'beta1': 0.9, 'beta2': 0.999, 'eps': 1e-8, 'cap': 1e3}}
+ADAPT_SHARED = {'power': 2, 'init': 1.0, 'normalize': True, 'every': 1}
+
+
+def tf_adapt_spec(spec):
+    """None | 'rba' | 'sa' | {'rule': ..., key: value} -> None or the full dict of the rule's parameters (defaults filled in).
+    ValueError for an unknown rule, an unknown key or a key of the other rule, and for values the engine would refuse."""
+    if spec is None:
+        return None
+    if isinstance(spec, str):
+        spec = {'rule': spec}
+    if not isinstance(spec, dict):
+        raise ValueError("tfAdapt must be None, 'rba', 'sa' or a dict with a 'rule' (got %r)" % (spec,))
+    rule = spec.get('rule')
+    if rule not in ADAPT_RULES:
+        raise ValueError("tfAdapt rule must be 'rba' or 'sa' (got %r)" % (rule,))
+    out = {'rule': rule}
+    out.update(ADAPT_OWN[rule])
+    out.update(ADAPT_SHARED)
+    for k, v in spec.items():
+        if k == 'rule':
+            continue
+        if k not in out:
+            other = [r for r in ADAPT_OWN if r != rule and k in ADAPT_OWN[r]]
+            raise ValueError("tfAdapt: %r is %s" % (k, "a key of the %r rule, not of %r" % (other[0], rule) if other else
+                                                    'no key of the adaptive weights (%s)' % ', '.join(sorted(out))))
+        out[k] = v
+    out['normalize'] = bool(out['normalize'])
+    num = {k: float(v) for k, v in out.items() if k not in ('rule', 'normalize')}
+    if not all(np.isfinite(v) for v in num.values()):
+        raise ValueError('tfAdapt: every parameter must be finite (got %r)' % (out,))
+    if out['power'] not in (1, 2):
+        raise ValueError('tfAdapt: power must be 1 or 2 (got %r)' % (out['power'],))
+    if num['every'] < 1 or num['every'] != int(num['every']):
+        raise ValueError('tfAdapt: every must be a whole number >= 1 (got %r)' % (out['every'],))
+    if num['init'] < 0:
+        raise ValueError('tfAdapt: init must be >= 0 (got %r)' % (out['init'],))
+    if rule == 'rba':
+        if not 0.0 <= num['gamma'] <= 1.0 or num['eta'] < 0:
+            raise ValueError('tfAdapt rba: gamma must lie in [0, 1] and eta be >= 0 (got %r, %r)' % (out['gamma'], out['eta']))
+    else:
+        if num['lr'] < 0 or num['cap'] <= 0 or num['eps'] <= 0 or not 0.0 <= num['beta1'] < 1.0 or not 0.0 <= num['beta2'] < 1.0:
+            raise ValueError('tfAdapt sa: lr >= 0, cap > 0, eps > 0 and beta1, beta2 in [0, 1) are required (got %r)' % (out,))
+    out['power'], out['every'] = int(out['power']), int(out['every'])
+    return out
+
+
+def tf_adapt_par(spec):
+    """(rule id, par[10]) of vn_set_tf_adapt for a full dict of tf_adapt_spec."""
+    own = (spec['gamma'], spec['eta'], 0.0, 0.0, 0.0) if spec['rule'] == 'rba' else \
+        (spec['lr'], spec['cap'], spec['beta1'], spec['beta2'], spec['eps'])
+    par = [float(x) for x in own] + [float(spec['power']), float(spec['init']), 1.0 if spec['normalize'] else 0.0,
+                                     float(spec['every']), 0.0]
+    return ADAPT_RULES[spec['rule']], par
 
 
 def reparam_count(mode, per, inpDim, layerWidth):
@@ -448,7 +509,7 @@ class VNEngine:
         self._keep[('int', batch)] = (Input, gcoef, source, detJv, Nr, dNr)
         self._ck(self.lib.vn_set_interior(self.h, batch, _ptr(Input), _ptr(gcoef), _ptr(source), n_k,
                                           _ptr(detJv), detJ_s, _ptr(Nr), _ptr(dNr)))
-        for key in ('react', 'nlflux', 'nldiff', 'tfw', 'causal', 'srcbasis', 'fldbasis', 'bicbasis', 'ansatz', 'ansatzpts'):   # vn_set_interior cleared the
+        for key in ('react', 'nlflux', 'nldiff', 'tfw', 'causal', 'adapt', 'srcbasis', 'fldbasis', 'bicbasis', 'ansatz', 'ansatzpts'):   # vn_set_interior cleared the
             self._keep.pop((key, batch), None)      # batch's three polynomial terms, its per-test-function loss weights, its source
                                                     # and field bases, the basis of its own BC/IC copy and its ansatz streams
 
@@ -897,6 +958,7 @@ class VNEngine:
         self._ck(self.lib.vn_set_tf_weights(self.h, int(batch), _ptr(omega)))
         self._keep[('tfw', batch)] = omega
         self._keep.pop(('causal', batch), None)
+        self._keep.pop(('adapt', batch), None)
 
     def set_causal(self, batch, slab=None, n_slabs=None, eps=0.0):
         """Register (or, with slab=None, clear) the causal time-slab weights of `batch` (vn_set_causal), after set_interior of
@@ -917,6 +979,7 @@ class VNEngine:
         self._ck(self.lib.vn_set_causal(self.h, int(batch), _ptr(slab), int(n_slabs), float(eps)))
         self._keep[('causal', batch)] = (int(n_slabs), float(eps))      # (the engine copied the ids)
         self._keep.pop(('tfw', batch), None)
+        self._keep.pop(('adapt', batch), None)
 
     def causal_weights(self, batch=0):
         """omega_s [n_slabs] float64 of the batch's causal registration at the current parameters (vn_causal_weights): one
@@ -926,6 +989,68 @@ class VNEngine:
         out = (C.c_double * n)()
         self._ck(self.lib.vn_causal_weights(self.h, int(batch), out, n))
         return np.array(out, dtype=np.float64)
+
+    # -- self-adaptive test-function weights -------------------------------------------------
+    def set_tf_adapt(self, batch, spec=None, lambda_init=None):
+        """Register (or, with spec=None, clear) self-adaptive weights of `batch` (vn_set_tf_adapt), after set_interior of that
+        batch.  spec: 'rba', 'sa' or a dict (tf_adapt_spec).  lambda_init: one value >= 0 per test function (a device tensor of
+        any alignment is passed as it is; validated and copied by the call), default: spec's init everywhere.  Replaces a static
+        or causal registration of the batch."""
+        spec = tf_adapt_spec(spec)
+        if spec is None:
+            self._ck(self.lib.vn_set_tf_adapt(self.h, int(batch), 0, None, None))
+            self._keep.pop(('adapt', batch), None)
+            return
+        t = self.torch
+        lam = None
+        if lambda_init is not None:
+            if isinstance(lambda_init, t.Tensor) and lambda_init.device == self.device and lambda_init.dtype == t.float32 \
+                    and lambda_init.is_contiguous():
+                lam = lambda_init.reshape(-1)
+            else:
+                lam = self.dev(lambda_init.reshape(-1) if isinstance(lambda_init, t.Tensor) else np.reshape(lambda_init, -1))
+            n_k = self._n_k(batch)
+            assert n_k is None or lam.numel() == n_k, 'lambda_init must have one entry per test function (%s != %s)' % (lam.numel(), n_k)
+        rule, par = tf_adapt_par(spec)
+        self._ck(self.lib.vn_set_tf_adapt(self.h, int(batch), rule, (C.c_double * 10)(*par), _ptr(lam)))
+        self._keep[('adapt', batch)] = spec                              # (the engine copied the initial values)
+        self._keep.pop(('tfw', batch), None)
+        self._keep.pop(('causal', batch), None)
+
+    def adapt_batches(self):
+        """The batches that carry an adaptive registration, in increasing order."""
+        return sorted(k[1] for k in self._keep if isinstance(k, tuple) and k[0] == 'adapt')
+
+    def tf_adapt(self, batch=0, arrays=True):
+        """The committed adaptive state of `batch` (vn_get_tf_adapt): {'lambda', 'omega' [n_k] float32, 'slots' [2, n_k] (sa) or
+        None, 'stats': {'min', 'max', 'mean', 'share', 'Z', 'tau'}}; arrays=False reads the statistics alone.  Synchronises;
+        changes no engine state."""
+        n_k = self._n_k(batch) or 0
+        spec = self._keep.get(('adapt', batch))
+        st = (C.c_double * 6)()
+        out = {'lambda': None, 'omega': None, 'slots': None}
+        if arrays:
+            out['lambda'], out['omega'] = np.empty(n_k, np.float32), np.empty(n_k, np.float32)
+            if spec is not None and spec['rule'] == 'sa':
+                out['slots'] = np.empty((2, n_k), np.float32)
+        self._ck(self.lib.vn_get_tf_adapt(self.h, int(batch), *[None if out[k] is None else out[k].ctypes.data
+                                                                 for k in ('lambda', 'omega', 'slots')], st))
+        out['stats'] = dict(zip(('min', 'max', 'mean', 'share', 'Z', 'tau'), [float(x) for x in st]))
+        return out
+
+    def set_tf_adapt_state(self, batch, lam, slots=None, tau=0):
+        """Puts an adaptive state back (vn_set_tf_adapt_state): lambda [n_k], slots [2, n_k] (sa; None: zeros), tau.  omega, Z and
+        the statistics are rebuilt on the device.  Synchronises."""
+        n_k = self._n_k(batch)
+        lam = np.ascontiguousarray(lam, dtype=np.float32).ravel()
+        if n_k is not None and lam.size != n_k:
+            raise ValueError('set_tf_adapt_state: expected %d lambdas, got %d' % (n_k, lam.size))
+        if slots is not None:
+            slots = np.ascontiguousarray(slots, dtype=np.float32).ravel()
+            if slots.size != 2 * lam.size:
+                raise ValueError('set_tf_adapt_state: expected %d slot values, got %d' % (2 * lam.size, slots.size))
+        self._ck(self.lib.vn_set_tf_adapt_state(self.h, int(batch), lam.ctypes.data, None if slots is None else slots.ctypes.data,
+                                                int(tau)))
 
     # -- learnt weight scales --------------------------------------------------------------
     def set_reparam(self, mode=None, per='neuron', n=1.0, s_init=None, lr=None):

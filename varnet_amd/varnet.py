@@ -264,6 +264,7 @@ class TrainResult:
         self.error = [] if not uf.isnone(cExFlg) else None      # (always a list: callers pass a bool)
         self.lossVec = None
         self.balanceHist = []             # (extension) one (epoch, weights, norms, cosines, skipped) per probe of train(balance=...)
+        self.tfAdaptHist = []             # (extension) one (epoch, [stats of every batch]) per monitor of a run with tfAdapt=...
         self.option_stopping = self.option_trainPoint = self.option_weighting = self.option_batchOptim = None
 
     # -- case file ------------------------------------------------------------------------------------
@@ -313,6 +314,10 @@ class TrainResult:
                      % str(list(PDE.nldiffCoef)))
         if getattr(varNet, 'causal', None) is not None:
             L.append('Causal time-slab loss weights: eps = %s, %d slabs\n\n' % (repr(float(varNet.causal)), varNet.causalSlabNum()))
+        if getattr(varNet, 'tfAdapt', None) is not None:
+            ad = varNet.tfAdapt
+            L.append('Self-adaptive test-function weights: rule %s, %s\n\n'
+                     % (ad['rule'], ', '.join('%s = %r' % (k, ad[k]) for k in sorted(ad) if k != 'rule')))
         for stem, pr in (getattr(varNet, 'learntPrior', None) or {}).items():
             for key, b in pr['blocks'].items():
                 L.append('Prior on the learnt %s%s: weight %s, matrix %s, mean %s, l1 %s\n\n'
@@ -608,6 +613,14 @@ class ManageTrainData:
     def _register(self):
         eng, q = self.vn.engine, self.integNum
         torch = eng.torch
+        adapt = getattr(self.vn, 'tfAdapt', None)
+        if adapt is not None:
+            # vn_set_interior clears the adaptive registrations: the set that holds them now (this one again, or the training set
+            # while a monitor borrows the engine) keeps its state on the host and takes it back at its next registration
+            owner = getattr(self.vn, '_adapt_owner', None)
+            if owner is not None:
+                own = {owner.engine_batch(mb, bi) for mb in range(len(owner.mor)) for bi in range(owner.batchNum)}
+                owner._adapt_saved = {b: eng.tf_adapt(b) for b in eng.adapt_batches() if b in own}
         if self.shuffled:                         # one upload of the permutation per shuffle, not one per block
             perm_dev = self._upload_perm(torch, eng.device)
             rows_all = (perm_dev[:, None] * q + torch.arange(q, device=eng.device)[None, :]).reshape(-1)
@@ -645,6 +658,12 @@ class ManageTrainData:
                     eng.set_field_basis(self.engine_batch(mb, bi), d['fldG'][:, n0 * q:n1 * q].contiguous())
                 if d.get('slab') is not None and n1 > n0 and self.vn.causal is not None:      # causal weights (vn_set_causal)
                     eng.set_causal(self.engine_batch(mb, bi), pick_k(d['slab']), self.vn.causalSlabNum(), float(self.vn.causal))
+                if adapt is not None and n1 > n0:                    # self-adaptive weights (vn_set_tf_adapt), state carried
+                    b = self.engine_batch(mb, bi)
+                    eng.set_tf_adapt(b, adapt)
+                    kept = (getattr(self, '_adapt_saved', None) or {}).get(b)
+                    if kept is not None and kept['lambda'].size == n1 - n0:
+                        eng.set_tf_adapt_state(b, kept['lambda'], kept['slots'], int(kept['stats']['tau']))
                 perm = getattr(self, 'biPerm', {}).get(bi)
                 if perm is not None and hasattr(eng, 'set_batch_bic'):
                     ix = torch.as_tensor(perm, device=eng.device, dtype=torch.long)
@@ -652,6 +671,8 @@ class ManageTrainData:
                                       d['biLabel'].index_select(0, ix))
                     if d.get('bicB') is not None:         # the copy's basis: the same permutation of the columns
                         eng.set_bic_basis(self.engine_batch(mb, bi), d['bicB'].index_select(1, ix).contiguous())
+        if adapt is not None:
+            self.vn._adapt_owner = self
 
     def _upload_perm(self, torch, device):
         """Test-function permutation -> device.  On the GPU through one of two persistent pinned buffers and an
@@ -869,7 +890,8 @@ class VarNet:
                  causal=None, causalSlabs=None, periodicDeriv=None, observations=None, obsWeight=None,
                  learnCoef=None, coefLr=None, coefBounds=None, learnSource=None, sourceLr=None, sourceBounds=None,
                  learnField=None, fieldLr=None, fieldBounds=None, learnBic=None, bicLr=None, bicBounds=None,
-                 learnFluxBC=None, fluxBCLr=None, fluxBCBounds=None, learntPrior=None, reparam=None, reparamLr=None):
+                 learnFluxBC=None, fluxBCLr=None, fluxBCBounds=None, learntPrior=None, reparam=None, reparamLr=None,
+                 tfAdapt=None):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -934,6 +956,10 @@ class VarNet:
                 raise ValueError('causalSlabs must be an integer in [1, 4096]')
         elif causalSlabs is not None:
             raise ValueError('causalSlabs is an option of causal=eps')
+        # tfAdapt=... (extension; no reference counterpart): one self-adaptive weight per test function, moved on the device at
+        # every step from that step's own loss field (`tf_adapt_spec`, VNEngine.set_tf_adapt)
+        self.tfAdapt = self._check_tf_adapt(tfAdapt, causal is not None, optimizer.lower() == 'lbfgs', MORvar is not None,
+                                            isinstance(processors, (list, tuple)) and len(processors) > 1)
         if fluxBC and MORvar is not None:
             raise NotImplementedError('fluxBC=True with model-order reduction is not supported: the flux rows carry one label '
                                       'g/a per boundary point, shared by all batches, while a MOR problem needs per-batch labels '
@@ -1004,6 +1030,9 @@ class VarNet:
             if causal is not None:
                 raise NotImplementedError('%s with causal=%r: the causal weights are applied after the seeds the %s gradient is '
                                           'reduced from' % (lv.option, causal, lv.noun))
+            if self.tfAdapt is not None:
+                raise NotImplementedError('%s with tfAdapt=%r: the weights are applied after the seeds the %s gradient is '
+                                          'reduced from' % (lv.option, tfAdapt, lv.noun))
         # learntPrior={stem: spec} (extension; no reference counterpart): a quadratic prior and L1 shrinkage on the learnt vectors
         # (`priorData`)
         self.learntPrior = self.priorData(PDE, learntPrior, {lv.stem: getattr(self, lv.attr) for lv in self.LEARNT})
@@ -1046,6 +1075,8 @@ class VarNet:
                 self.dist, self.rank, self.world = dist, dist.get_rank(), dist.get_world_size()
         except ImportError:
             pass
+        if self.tfAdapt is not None and self.world > 1:
+            self._check_tf_adapt(tfAdapt, False, False, False, True)
         if self.causal is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
             raise NotImplementedError('causal=%r with towers: a rank\'s slab means would cover only its shard of the test '
                                       'functions, so the ranks together would train another objective than one rank'
@@ -1805,6 +1836,60 @@ class VarNet:
                                                              b['mean']).items() if k == name})
         self._register_prior(lv)
 
+    # -- self-adaptive test-function weights (extension) --------------------------------------------
+    @staticmethod
+    def _check_tf_adapt(spec, causal, lbfgs, mor, towers):
+        """The full dict of a `tfAdapt` option (None: off), after the refusals every way in shares."""
+        from .engine import tf_adapt_spec
+        full = tf_adapt_spec(spec)
+        if full is None:
+            return None
+        if causal:
+            raise ValueError('tfAdapt=%r with causal=...: a batch carries one per-test-function registration, and the two replace '
+                             'each other' % (spec,))
+        if lbfgs:
+            raise ValueError('tfAdapt=%r with optimizer=\'lbfgs\': the weights move from step to step but are held constant for the '
+                             'gradient, so an Armijo test across steps means nothing' % (spec,))
+        if mor:
+            raise NotImplementedError('tfAdapt=%r with model-order reduction is not supported: every MOR batch is another objective '
+                                      'with a state of its own, which the monitors and checkpoints do not carry' % (spec,))
+        if towers:
+            raise NotImplementedError('tfAdapt=%r with towers: a rank\'s max, mean and Z would cover only its shard of the test '
+                                      'functions, so the ranks together would train another objective than one rank' % (spec,))
+        return full
+
+    def setTfAdapt(self, spec):
+        """Another rule or other parameters for the self-adaptive weights (None switches them off), re-registered on the training
+        set of the last train() call from the rule's initial state: the option can change between train() calls."""
+        full = self._check_tf_adapt(spec, self.causal is not None, self._is_lbfgs(), not uf.isnone(self.PDE.MORvar),
+                                    self.world > 1 or self._towers is not None)
+        if full is not None:
+            for lv in self.LEARNT:
+                if getattr(self, lv.attr, None) is not None:
+                    raise NotImplementedError('%s with tfAdapt=%r: the weights are applied after the seeds the %s gradient is '
+                                              'reduced from' % (lv.option, spec, lv.noun))
+        self.tfAdapt = full
+        self._adapt_owner = None                          # no state is carried over to the new registration
+        tData = getattr(self, 'tData', None)
+        if tData is not None:
+            tData._adapt_saved = None
+            tData.activate()
+
+    def tfWeights(self, tData=None):
+        """Per batch of `tData` (default: the set of the last train() call, else a freshly built full-batch set) the committed
+        state {'omega', 'lambda' [n_k], 'stats': {'min', 'max', 'mean', 'share', 'Z', 'tau'}} of the self-adaptive weights."""
+        if self.tfAdapt is None:
+            raise ValueError('tfWeights: the self-adaptive weights are off (VarNet(tfAdapt=...) or setTfAdapt(...))')
+        if tData is None:
+            tData = getattr(self, 'tData', None) or self._build_tdata()
+        if getattr(self, '_adapt_owner', None) is not tData:
+            tData.activate()
+        out = []
+        for bi in range(tData.batchNum):
+            s = self.engine.tf_adapt(tData.engine_batch(0, bi))
+            out.append({'omega': s['omega'], 'lambda': s['lambda'], 'stats': s['stats']})
+        return out
+
     # -- causal time-slab weights (extension) ------------------------------------------------------
     @staticmethod
     def _check_causal_eps(eps):
@@ -1831,6 +1916,9 @@ class VarNet:
         eps can be annealed between train() calls."""
         if eps is not None:
             self._check_causal_eps(eps)
+            if getattr(self, 'tfAdapt', None) is not None:
+                raise ValueError('causal=%r with tfAdapt=...: a batch carries one per-test-function registration, and the two '
+                                 'replace each other' % (eps,))
             if not self.PDE.timeDependent:
                 raise ValueError('causal=%r needs a time-dependent PDE: a steady problem has no time slabs' % (eps,))
             if self._is_lbfgs():
@@ -2807,6 +2895,9 @@ class VarNet:
         if batchNum is None and batchLen is None and shuffleData:
             warnings.warn('shuffling data is possible for batch-optimization, setting \'shuffleData\' to False!')
             shuffleData = False
+        if shuffleData and self.tfAdapt is not None:
+            raise NotImplementedError('tfAdapt=... with shuffleData=True is not supported: a shuffle changes which test function is k, '
+                                      'and the state lambda_k belongs to the test function')
         if shuffleData and getattr(self.PDE, 'ansatz', None) is not None:
             raise NotImplementedError('an ansatz with shuffleData=True is not supported: a shuffle permutes the BC/IC rows per feed '
                                       '(a per-batch copy), and the ansatz streams belong to the rows as they were registered')
@@ -2817,6 +2908,9 @@ class VarNet:
             suppFactor = 1.0
         eng, fd = self.engine, self.fixData
         torch = eng.torch
+        self._adapt_owner = None                             # the adaptive state of an earlier train() call is not carried over ...
+        if getattr(self, 'tData', None) is not None:
+            self.tData._adapt_saved = None
         tData = self._build_tdata(batchNum, batchLen)        # first set is always uniform (VarNet.py:1300)
         trainRes = TrainResult(folderpath if self.rank == 0 else None, fd.cEx is not None, verbose, saveFreq, pltReplace)
         trainRes.initializeCase(self, argDict)
@@ -2994,6 +3088,9 @@ class VarNet:
                     if tData0 is not tData:
                         tData.activate()
                     eng.set_weights(w_eff)
+                    if self.tfAdapt is not None:
+                        trainRes.tfAdaptHist.append((epoch, [eng.tf_adapt(tData.engine_batch(0, bi), arrays=False)['stats']
+                                                             for bi in range(tData.batchNum)]))
                 trainRes.iterOutput(epoch, current_loss, min_loss, epoch_time, resVal, err, lossComp, lossVec)
 
                 if current_loss < tol:
@@ -3031,6 +3128,9 @@ class VarNet:
                         if reinitrain:
                             self._init_params(tp_updates)               # global_variables_initializer, VarNet.py:1412
                             msg += 'trainable variables reinitialized.\n\n'
+                        if self.tfAdapt is not None:                    # the new set's test functions are other ones
+                            msg += 'self-adaptive test-function weights reset to their initial state.\n\n'
+                            trainRes.tfAdaptHist.append((epoch, 'reset'))
                         if verbose and self.rank == 0:
                             print(msg)
                         trainRes.writeCase(msg)
@@ -3119,6 +3219,17 @@ class VarNet:
             st = self.engine.get_reparam()
             out['reparam_mode'] = np.array('%s/%s/%r' % (self.reparam['kind'], self.reparam['per'], self.reparam['n']))
             out['reparam_V'], out['reparam_s'], out['reparam_slots'] = st['V'], st['s'], st['slots']
+        if getattr(self, 'tfAdapt', None) is not None:
+            # (the parameters above are the first 3 P floats of the exported state whatever follows them)
+            batches = self.engine.adapt_batches()
+            out['tfadapt_rule'] = np.array(self.tfAdapt['rule'])
+            out['tfadapt_batches'] = np.array(batches, dtype=np.int64)
+            for b in batches:
+                st = self.engine.tf_adapt(b)
+                out['tfadapt_%d_lambda' % b] = st['lambda']
+                out['tfadapt_%d_tau' % b] = np.int64(st['stats']['tau'])
+                if st['slots'] is not None:
+                    out['tfadapt_%d_slots' % b] = st['slots']
         return out
 
     def restore_arrays(self, arrays):
@@ -3150,7 +3261,18 @@ class VarNet:
             fan = h
         step = np.array([int(arrays['global_step']) if 'global_step' in arrays else 0], dtype=np.int64)
         blob = np.concatenate([step.view(np.uint8), np.concatenate(th + m + v).astype(np.float32).view(np.uint8)])
+        rule = None if getattr(self, 'tfAdapt', None) is None else self.tfAdapt['rule']
+        saved_rule = str(arrays['tfadapt_rule']) if 'tfadapt_rule' in arrays else None
+        if rule is not None:
+            # the adaptive states follow the optimizer state in the engine's layout: as they stand for the import, then (when the
+            # checkpoint carries the rule's state for the registered batches) from the checkpoint
+            blob = np.concatenate([blob, np.asarray(self.engine.export_state(), dtype=np.uint8)[blob.size:]])
         self.engine.import_state(blob)
+        if rule is not None and saved_rule == rule:
+            for b in [int(x) for x in arrays['tfadapt_batches']]:
+                if b in self.engine.adapt_batches() and np.size(arrays['tfadapt_%d_lambda' % b]) == self.engine._n_k(b):
+                    self.engine.set_tf_adapt_state(b, arrays['tfadapt_%d_lambda' % b], arrays.get('tfadapt_%d_slots' % b),
+                                                   int(arrays['tfadapt_%d_tau' % b]))
         if mode is not None:
             self.engine.set_reparam_state(arrays['reparam_V'], arrays['reparam_s'], arrays['reparam_slots'])
         for lv in self.LEARNT:
