@@ -408,8 +408,8 @@ int vn_causal_weights(vn_engine* h, int32_t batch, double* omega_slab_host, int3
  * a handle with a communicator, and vn_comm_init on a handle with an adaptive batch (a shard's max, mean and Z are not the
  * batch's); vn_lbfgs_step on an adaptive batch (the causal refusal, for the same reason); learnt vectors, as for every weight.
  * vn_state_snapshot / _rollback and vn_state_size / _export / _import carry (scalars incl. Z and tau, lambda, omega, slots) of
- * every registered batch in batch order after the optimizer state; with none registered their layout is unchanged.  BC / IC
- * rows stay unweighted. */
+ * every registered batch in batch order after the optimizer state; with none registered their layout is unchanged.  The BC / IC
+ * rows have weights of their own (vn_set_bic_weights, vn_set_bic_adapt). */
 int vn_set_tf_adapt(vn_engine* h, int32_t batch, int32_t rule, const double par[10], const float* lambda_init_dev);
 /* The committed state of the batch's adaptive registration: lambda_host [n_k], omega_host [n_k], slots_host [2 n_k] (m1 | m2; sa
  * only, VN_EINVAL for rba), stats[6] = min, max, mean omega, effective sample share (sum omega)^2 / (n_k sum omega^2), Z, tau
@@ -419,6 +419,48 @@ int vn_get_tf_adapt(vn_engine* h, int32_t batch, float* lambda_host, float* omeg
 /* Puts a state back (a checkpoint): lambda_host [n_k] (finite, >= 0), slots_host [2 n_k] (sa; NULL: zeros; VN_EINVAL for rba),
  * tau >= 0.  omega, Z and the statistics are rebuilt on the device, a pending state is dropped.  Synchronises. */
 int vn_set_tf_adapt_state(vn_engine* h, int32_t batch, const float* lambda_host, const float* slots_host, int64_t tau);
+/* Weights on the Dirichlet and initial rows of vn_set_bic.  The rows fall into two PARTS: bc = rows
+ * [0, bDof) (part 0) and ic = rows [bDof, nB) (part 1; absent on a steady engine or when nB == bDof).  Per row e_i = u_i - label_i
+ * and the unweighted loss field l_i = e_i^2; per row of a registered part a state lambda_i >= 0 (fp32), per part a normaliser Z_s
+ * and an update counter tau_s.  With n_s the rows of part s the weights in use are
+ *     omega_i = m(lambda_i) / Z_s,   m(x) = x^p (p 1 or 2),   Z_s = mean over the part of m(lambda) if normalize else 1
+ * (all lambda zero under normalize: Z = 1, omega = 0), and they enter as
+ *     BC = biDimVal (1 / bDof) sum_{i < bDof} omega_i e_i^2,   IC likewise over its part,
+ *     value seed of row i = (the unweighted seed) * omega_i;
+ * omega and Z are constants of the gradient.  A part without a registration has omega = 1.  Flux rows, periodic pairs and
+ * observation rows stay as they are.
+ * vn_set_bic_weights: STATIC weights, omega_dev [nB] device floats (nB as the engine counts them: bDof on a steady engine),
+ * VALIDATED on the device (finite, >= 0; else VN_EINVAL) and COPIED, so the call synchronises; normalize (0 or 1) applies per
+ * part.  It registers every part that has rows and replaces whatever they held.  NULL clears both parts.
+ * vn_set_bic_adapt: ONE part follows rule 1 (rba) or 2 (sa) of vn_set_tf_adapt, with l_i in place of l_k and n_s in place of n_k:
+ * its own max / mean, tau_s, Adam slots, Z_s and `every`; par[10] and lambda_init_dev [n_s] exactly as there.  Each part is run
+ * independently and may have its own rule and parameters.  rule 0 clears that part.  A static and an adaptive registration of the
+ * same part replace each other.  A maximum or a mean that is zero or not finite leaves that part's state, slots and tau_s alone.
+ * Commit protocol: that of vn_set_tf_adapt, with the state belonging to the engine's row set, not to a batch -- a gradient
+ * evaluation of ANY batch applies the committed omega and writes the pending half; vn_apply or the folded step of vn_train_step /
+ * vn_train_epoch commits by a pointer swap; vn_grad twice recomputes the same pending bits; vn_eval_loss, vn_objective_f64 (omega
+ * widened exactly), vn_term_grads and every loss-only call move nothing and see the committed omega; a failed folded step drops the pending state; vn_set_bic clears both
+ * parts; vn_params_init returns to the registered initial state.
+ * While a part is registered the BC/IC rows leave the step's main launch and run as a pass of their own (vn_bicadapt.hip): a
+ * forward of the rows, one kernel for loss field, weighted seeds and weighted loss partials (fp64 sums in a fixed order, no
+ * atomics), a reverse pass; an adaptive part adds the three launches of vn_adapt.hip on its own loss field.  Without a
+ * registration nothing is launched or allocated and every result is bit for bit what it was.
+ * vn_state_snapshot / _rollback carry the committed halves; vn_state_size / _export / _import append (scalars incl. Z and tau,
+ * lambda, omega, slots) per registered part, bc first, after what vn_set_tf_adapt appends; nothing when none is registered.
+ * VN_ESTATE: no rows (vn_set_bic first), a part without rows.  VN_EUNSUPPORTED, in either order of registration: BC/IC ansatz
+ * streams (vn_set_ansatz_rows); learnt vectors; a communicator; a batch's own copy of the rows (vn_set_batch_bic); the
+ * layer-by-layer route, a network outside the hand-written kernels' range and VN_KERNEL_FUSED; an adaptive part on an L-BFGS engine
+ * (static weights work with vn_lbfgs_step, with and without vn_lbfgs_loss64). */
+int vn_set_bic_weights(vn_engine* h, const float* omega_dev, int32_t normalize);
+int vn_set_bic_adapt(vn_engine* h, int32_t part, int32_t rule, const double par[10], const float* lambda_init_dev);
+/* The committed state of a registered part: lambda_host, omega_host [n_s], slots_host [2 n_s] (m1 | m2; sa only, else VN_EINVAL),
+ * lossfield_host [n_s] the unweighted l_i of the last evaluation (zeros before the first), stats[6] as for vn_get_tf_adapt.  A
+ * static part reports lambda = the weights as given.  Any output pointer may be NULL.  Synchronises; changes no engine state.
+ * Without a registration of the part: VN_ESTATE. */
+int vn_get_bic_adapt(vn_engine* h, int32_t part, float* lambda_host, float* omega_host, float* slots_host, float* lossfield_host,
+                     double stats[6]);
+/* Puts the state of an ADAPTIVE part back (a checkpoint), as vn_set_tf_adapt_state does; VN_ESTATE for a static part. */
+int vn_set_bic_adapt_state(vn_engine* h, int32_t part, const float* lambda_host, const float* slots_host, int64_t tau);
 /* Inverse mode: learn the nine polynomial coefficients next to the parameters.  Index 0..2 = (c1, c2, c3) of the reaction,
  * 3..5 = (f1, f2, f3) of the flux, 6..8 = (d0, d1, d2) of the diffusivity.  While learning is on the engine owns ONE device
  * vector of nine fp32 coefficients (`init`, rounded once), shared by every batch; every registered term of every batch reads its

@@ -15,6 +15,7 @@
 #include "vn_reparam.h"
 #include "vn_balance.h"
 #include "vn_adapt.h"
+#include "vn_bicadapt.h"
 
 hipError_t vn_calibrate_f64(int ncu, hipStream_t s, double ghz, double out[3]);      // vn_calib.hip (fp64 MFMA loop)
 
@@ -305,6 +306,11 @@ struct vn_engine {
   float* wt_omega = nullptr; long wt_omega_cap = 0;
   float* wt_stat = nullptr; long wt_stat_cap = 0;
   bool ad_quiet = false;       // vn_term_grads' probes: gradient evaluations that leave every adaptive state (vn_set_tf_adapt) alone
+  // weights on the BC/IC rows (vn_set_bic_weights, vn_set_bic_adapt; vn_bicadapt.hip), owned, by part (0 bc, 1 ic): nullptr: the
+  // part is unweighted.  A static registration is a state that never moves (rule VN_ADAPT_NONE, m(x) = x).  bw_field: the
+  // unweighted loss field of both parts, the ic part's at vn_adapt_stride(bDof); allocated with the first registration
+  Adapt* bw[2] = {nullptr, nullptr};
+  float* bw_field = nullptr; long bw_field_cap = 0;
   // the edge row sets by VnEdgeId (es[id].count == 0: none registered), then what each kind keeps beside its record, caller-owned:
   // boundary-flux rows (vn_set_flux_bc), nF = count rows with their normals in G
   EdgeSet es[VN_EDGE_N];
@@ -861,10 +867,14 @@ void adapt_commit(vn_engine* h) {
       b.ad->pending = false;
       b.wt.omega = adapt_state(*b.ad, b.ad->cur).omega;
     }
+  for (Adapt* ad : h->bw)       // ... and those of the BC/IC rows' parts (vn_set_bic_adapt)
+    if (ad && ad->pending) { ad->cur ^= 1; ad->pending = false; }
 }
 void adapt_drop_pending(vn_engine* h) {
   for (Batch& b : h->batches)
     if (b.ad) b.ad->pending = false;
+  for (Adapt* ad : h->bw)
+    if (ad) ad->pending = false;
 }
 inline bool adapt_any(const vn_engine* h) {
   for (const Batch& b : h->batches)
@@ -895,15 +905,18 @@ int weights_stage(vn_engine* h, const Batch& b, const float* lossVec, int tfb, f
   return VN_OK;
 }
 
+void adapt_free(Adapt*& ad) {
+  if (!ad) return;
+  if (ad->f) (void)hipFree(ad->f);
+  if (ad->d) (void)hipFree(ad->d);
+  delete ad;
+  ad = nullptr;
+}
+
 void clear_weights(Batch& b) {
   if (b.wt_own) (void)hipFree(b.wt_own);
   b.wt_own = nullptr;
-  if (b.ad) {
-    if (b.ad->f) (void)hipFree(b.ad->f);
-    if (b.ad->d) (void)hipFree(b.ad->d);
-    delete b.ad;
-    b.ad = nullptr;
-  }
+  adapt_free(b.ad);
   b.wt = VnWeightsReg();
 }
 
@@ -1024,6 +1037,82 @@ int ansatz_bic_rows(vn_engine* h, const Batch& b, float* partial, float* lp, int
   const int grid = ansatz_bic_parts(h);
   HIPCHK(vn_generic_backward(h->net, h->theta, r, none, partial, grid, h->stream));
   *nparts = grid; *nlp = bgrid;
+  return VN_OK;
+}
+
+// ---- weights on the BC/IC rows (vn_set_bic_weights, vn_set_bic_adapt; vn_bicadapt.hip) ----
+// While a part is registered, the rows leave the step's main launch (nB = 0 there), whose seeds know no omega, and run as a pass
+// of their own, as under an ansatz: a forward of the rows, the rows' seed kernel, the generic reverse pass.
+inline bool bicw_on(const vn_engine* h) { return h->bw[0] || h->bw[1]; }
+inline long bicw_count(const vn_engine* h, int part) { return part == 0 ? h->bDof : h->nB - h->bDof; }
+inline float* bicw_field(const vn_engine* h, int part) { return h->bw_field + (part ? vn_adapt_stride(h->bDof) : 0); }
+inline int bicw_lossparts(const vn_engine* h) { return bicw_on(h) ? vn_bic_rows_blocks(h->nB) : 0; }
+inline int bicw_parts(const vn_engine* h) { return bicw_on(h) ? ansatz_bic_parts(h) : 0; }
+
+const LearntKind* learnt_any(const vn_engine* h);
+int fused_forward(vn_engine* h, const float* X, const float* G, long n, float* out_u, float* out_ud);
+
+// What cannot stand next to a registration, checked by the registration and again before every evaluation (so that it holds in
+// both orders of registration)
+int bicw_check(const vn_engine* h, const char* who) {
+  if (h->az_bic.B)
+    return fail(VN_EUNSUPPORTED, "%s next to BC/IC ansatz streams (vn_set_ansatz_rows): under a hard-constraint ansatz the rows' error is "
+                                 "zero by construction, there is nothing to weight", who);
+  if (const LearntKind* k = learnt_any(h))
+    return fail(VN_EUNSUPPORTED, "%s next to learnt %s (%s): the %s sums next to the rows' own pass are not built (and learnt boundary "
+                                 "data would move the labels the weights follow)", who, k->what, k->setter, k->noun);
+  if (h->comm)
+    return fail(VN_EUNSUPPORTED, "%s under a communicator: a rank's max, mean and Z would follow its own shard's steps, so the ranks "
+                                 "together would train another objective than one rank", who);
+  for (size_t i = 0; i < h->batches.size(); ++i)
+    if (h->batches[i].biInput)
+      return fail(VN_EUNSUPPORTED, "%s next to batch %zu's own copy of the BC/IC rows (vn_set_batch_bic): the weights belong to the rows "
+                                   "of vn_set_bic, one state per row", who, i);
+  return VN_OK;
+}
+
+// The rows' seed kernel on the values in h->ub: loss field, loss partials to lp, with_seeds the weighted seeds to h->ubar_b; and
+// in a gradient evaluation that is no probe, the pending state of every adaptive part from its own loss field (the committed half is
+// read, the other written: the weights applied are the committed ones)
+int bicw_seed(vn_engine* h, const Batch& b, float* lp, bool with_seeds) {
+  VnBicRowsArgs a;
+  a.ub = h->ub; a.label = bi_y(h, b); a.nB = h->nB; a.bDof = h->bDof;
+  a.biDimVal = (float)h->biDimVal; a.w0 = (float)h->w[0]; a.w1 = (float)h->w[1];
+  for (int s = 0; s < 2; ++s) {
+    a.omega[s] = h->bw[s] ? adapt_state(*h->bw[s], h->bw[s]->cur).omega : nullptr;
+    a.field[s] = bicw_count(h, s) > 0 ? bicw_field(h, s) : nullptr;
+  }
+  a.ubar_b = with_seeds ? h->ubar_b : nullptr; a.part = lp;
+  HIPCHK(vn_bic_rows_launch(a, h->stream));
+  if (!with_seeds || h->ad_quiet) return VN_OK;
+  for (int s = 0; s < 2; ++s) {
+    Adapt* ad = h->bw[s];
+    if (!ad || ad->rule == VN_ADAPT_NONE || adapt_step_index(h) % ad->every != 0) continue;
+    VnAdaptArgs u = adapt_args(*ad, ad->rule, ad->cur, ad->cur ^ 1);
+    u.lossVec = bicw_field(h, s);
+    HIPCHK(vn_adapt_update_launch(u, h->stream));
+    ad->pending = true;
+  }
+  return VN_OK;
+}
+
+// The rows' pass of a gradient evaluation on the 8-wave sequences: gradient partials to `partial` ([*nparts, P] on return), loss
+// partials to `lp` ([*nlp, 3])
+int bicw_rows(vn_engine* h, const Batch& b, float* partial, float* lp, int* nparts, int* nlp) {
+  *nparts = 0; *nlp = 0;
+  if (h->nB <= 0) return VN_OK;
+  VnRows r{}, none{};
+  r.X = bi_x(h, b); r.G = nullptr; r.u = h->ub; r.ud = nullptr; r.n = h->nB;
+  if (on_8wave(h)) {                                 // the 8-wave kernel's forward-only mode: the faster of the two (DESIGN.md section
+    if (int rc = fused_forward(h, r.X, nullptr, r.n, r.u, nullptr)) return rc;   // 35); it borrows h->partial's first rows, which
+  } else {                                                                       // the step's own launch writes afterwards
+    HIPCHK(vn_generic_forward(h->net, h->theta, r, none, h->fwd_grid, h->stream));
+  }
+  if (int rc = bicw_seed(h, b, lp, true)) return rc;
+  r.u = nullptr; r.ubar = h->ubar_b; r.udbar = nullptr;
+  const int grid = bicw_parts(h);
+  HIPCHK(vn_generic_backward(h->net, h->theta, r, none, partial, grid, h->stream));
+  *nparts = grid; *nlp = bicw_lossparts(h);
   return VN_OK;
 }
 
@@ -1240,7 +1329,11 @@ int eval_dedup(vn_engine* h, const Batch& b, float* lossVec, float* lossdst, con
   // interior set empty: the BC/IC terms alone (Nrow, dNtrow and detJv are nullptr on a batch with a de-duplication map)
   s.n_k = 0; s.source = nullptr; s.feW = nullptr;
   s.part = h->losspart + (long)sblk * 3;
-  HIPCHK(vn_seed_launch(s, bgrid, h->stream));
+  if (bicw_on(h)) {                                  // weighted rows: their own seed kernel in its loss-only form (bgrid blocks as well)
+    if (int rc = bicw_seed(h, b, s.part, false)) return rc;
+  } else {
+    HIPCHK(vn_seed_launch(s, bgrid, h->stream));
+  }
   if (lossdst)
     HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, sblk + bgrid, h->bDof, h->nB, s.w0, s.w1, s.w2, lossdst, h->stream,
                             VnOptArgs(), fx));
@@ -1273,12 +1366,16 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
 
   const long nthreads = b.n_k > h->nB ? b.n_k : h->nB;
   const int grid = (int)(((nthreads > 0 ? nthreads : 1) + 255) / 256);      // an empty set still zeroes its partials
-  if (int rc = ensure(&h->losspart, &h->losspart_cap, (long)grid * 3)) return rc;
+  const int blp = bicw_lossparts(h);                 // weighted BC/IC rows: their own seed kernel, its partials behind the others
+  if (int rc = ensure(&h->losspart, &h->losspart_cap, (long)(grid + blp) * 3)) return rc;
   VnSeedArgs a = seed_args(h, b);
   if (with_seeds) { a.ubar = h->ubar; a.udbar = h->udbar; a.ubar_b = h->ubar_b; }
   a.lossVec = weights_lossvec(h, b, lossVec); a.part = h->losspart;
+  if (blp) { a.ub = nullptr; a.label = nullptr; a.nB = 0; a.bDof = 0; a.ubar_b = nullptr; }
   if (int rc = terms_fold_rows(h, b)) return rc;
   HIPCHK(vn_seed_launch(a, grid, h->stream));
+  if (blp)
+    if (int rc = bicw_seed(h, b, h->losspart + (long)grid * 3, with_seeds)) return rc;
   if (with_seeds) {
     if (int rc = bic_reduce(h, b)) return rc;      // boundary / initial amplitudes: u_b is in h->ub
     if (int rc = terms_seed_rows(h, b)) return rc;
@@ -1289,7 +1386,7 @@ int run_forward_and_seed(vn_engine* h, const Batch& b, bool with_seeds, float* l
     if (int rc = ansatz_adjoint(h, h->az_bic, h->ubar_b, nullptr, h->nB)) return rc;
   }
   if (lossdst) {
-    HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2, lossdst, h->stream,
+    HIPCHK(vn_reduce_launch(nullptr, 0, 0, h->losspart, grid + blp, h->bDof, h->nB, a.w0, a.w1, a.w2, lossdst, h->stream,
                             VnOptArgs(), fx));
   }
   return VN_OK;
@@ -1322,7 +1419,8 @@ int run_generic(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& 
   HIPCHK(vn_generic_backward(h->net, h->theta, s0, s1, h->partial, h->bwd_grid, h->stream));
   if (int rc = prof_stop(h)) return rc;
   const long nthreads = b.n_k > h->nB ? b.n_k : h->nB;
-  const int lgrid = (int)((nthreads + 255) / 256);
+  // (weighted BC/IC rows: run_forward_and_seed put their seed kernel's partials behind the others, their weighted seeds in ubar_b)
+  const int lgrid = bicw_on(h) ? (int)(((nthreads > 0 ? nthreads : 1) + 255) / 256) + bicw_lossparts(h) : (int)((nthreads + 255) / 256);
   HIPCHK(vn_reduce_launch(h->partial, h->bwd_grid, h->net.P, h->losspart, lgrid, h->bDof, h->nB, (float)h->w[0],
                           (float)h->w[1], (float)h->w[2], gradbuf, h->stream, h->fuse, fx));
   return VN_OK;
@@ -1336,12 +1434,21 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
   a.nT = b.n_k * h->cfg.integ_num; a.n_k = b.n_k; a.feW = fe_w(h);
   a.Nrow = b.Nrow; a.dNtrow = b.dNtrow; a.detJv = b.detJv; a.detJ = (float)b.detJ;
   a.partial = h->partial; a.losspart = h->fused_losspart; a.stamps = h->stamps;
+  const bool bw = bicw_on(h);                        // weighted BC/IC rows leave the launch (bicw_rows)
+  if (bw) a.nB = 0;
   // one persistent workgroup per CU, but never more workgroups than tiles (small mini-batches: idle workgroups would still
   // image the weights, flush and store an all-zero partial that the reduction then has to read)
   const long tt = 128 / a.integ_num > 0 ? 128 / a.integ_num : 1;
   const long tiles = (a.n_k + tt - 1) / tt + (a.nB + 127) / 128;
   const int grid = h->full_grid ? h->ncu : (int)(tiles < 1 ? 1 : tiles < h->ncu ? tiles : h->ncu);
   if (int rc = bic_forward_reduce(h, b)) return rc;
+  int bparts = 0, blp = 0;
+  if (bw) {                                          // their partials behind the launch's own; the loss partials need the room too
+    if (int rc = ensure(&h->tp_losspart, &h->tp_losspart_cap, (long)(grid + bicw_lossparts(h)) * 3)) return rc;
+    if (int rc = grow_partial(h, grid + bicw_parts(h))) return rc;
+    a.partial = h->partial; a.losspart = h->tp_losspart;
+    if (int rc = bicw_rows(h, b, h->partial + (long)grid * h->net.P, a.losspart + (long)grid * 3, &bparts, &blp)) return rc;
+  }
   if (int rc = prof_start(h)) return rc;
   if (h->route == Route::fused8) {
     if (int rc = fused8_launch(h, a, grid)) return rc;
@@ -1349,7 +1456,7 @@ int run_fused(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
     HIPCHK(vn_fused_launch(a, grid, h->stream));
   }
   if (int rc = prof_stop(h)) return rc;
-  HIPCHK(vn_reduce_launch(h->partial, grid, h->net.P, h->fused_losspart, grid, h->bDof, h->nB, a.w0, a.w1, a.w2,
+  HIPCHK(vn_reduce_launch(h->partial, grid + bparts, h->net.P, a.losspart, grid + blp, h->bDof, h->nB, a.w0, a.w1, a.w2,
                           gradbuf, h->stream, h->fuse, fx));
   return VN_OK;
 }
@@ -1368,8 +1475,9 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& 
   const int grid = h->ncu, P = h->net.P;
   const int sgrid = (int)((b.n_k + 255) / 256);
   const bool az = has_ansatz(b);                     // hard-constraint ansatz: the BC/IC rows leave step 3 (ansatz_bic_rows)
-  if (int rc = ensure(&h->tp_losspart, &h->tp_losspart_cap, (long)(grid + sgrid + (az ? ansatz_bic_lossparts(h) : 0)) * 3)) return rc;
-  if (az)
+  const bool bw = bicw_on(h);                        // weighted BC/IC rows: likewise (bicw_rows)
+  if (int rc = ensure(&h->tp_losspart, &h->tp_losspart_cap, (long)(grid + sgrid + (az || bw ? ansatz_bic_lossparts(h) : 0)) * 3)) return rc;
+  if (az || bw)
     if (int rc = grow_partial(h, grid + ansatz_bic_parts(h))) return rc;
   if (int rc = bic_forward_reduce(h, b)) return rc;
   float* lp = h->tp_losspart;
@@ -1396,8 +1504,10 @@ int run_twopass(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& 
     if (int rc = ansatz_adjoint(h, b.az, h->ubar, h->udbar, f.nT)) return rc;
     if (int rc = ansatz_bic_rows(h, b, h->partial + (long)grid * P, lp + (long)(grid + sgrid) * 3, &bparts, &blp)) return rc;
   }
+  if (bw)
+    if (int rc = bicw_rows(h, b, h->partial + (long)grid * P, lp + (long)(grid + sgrid) * 3, &bparts, &blp)) return rc;
 
-  f.mode = 2; f.out_u = nullptr; f.out_ud = nullptr; f.seed_u = h->ubar; f.seed_ud = h->udbar; f.nB = az ? 0 : h->nB;
+  f.mode = 2; f.out_u = nullptr; f.out_ud = nullptr; f.seed_u = h->ubar; f.seed_ud = h->udbar; f.nB = az || bw ? 0 : h->nB;
   if (int rc = prof_start(h)) return rc;
   if (int rc = fused8_launch(h, f, grid)) return rc;
   if (int rc = prof_stop(h)) return rc;
@@ -1417,7 +1527,8 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
   const int grid = h->ncu, P = h->net.P;
   const int sblk = (int)((b.n_k + VN_DEDUP_TFB - 1) / VN_DEDUP_TFB);
   const bool az = has_ansatz(b);                     // hard-constraint ansatz: the BC/IC rows leave step 4 (ansatz_bic_rows)
-  if (az) {
+  const bool bw = bicw_on(h);                        // weighted BC/IC rows: likewise (bicw_rows)
+  if (az || bw) {
     if (int rc = ensure(&h->dd_losspart, &h->dd_cap_lp, (long)(grid + sblk + ansatz_bic_lossparts(h)) * 3)) return rc;
     if (int rc = ensure(&h->dd_partial, &h->dd_partial_cap, (long)(grid + ansatz_bic_parts(h)) * P)) return rc;
   }
@@ -1442,6 +1553,8 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
     HIPCHK(vn_ansatz_points_adjoint_launch(ansatz_point_args(h, b), h->stream));
     if (int rc = ansatz_bic_rows(h, b, h->dd_partial + (long)grid * P, lp + (long)(grid + sblk) * 3, &bparts, &blp)) return rc;
   }
+  if (bw)
+    if (int rc = bicw_rows(h, b, h->dd_partial + (long)grid * P, lp + (long)(grid + sblk) * 3, &bparts, &blp)) return rc;
   if (src_learnt(h, b)) {                          // source identification: a row's seed is stf[k] x its quadrature weight
     VnSrcGradArgs g{};
     g.stf = a.stf; g.feW = fe_w(h); g.feN = h->feN; g.phi = b.sb_phi; g.J = b.sb_J;
@@ -1461,7 +1574,7 @@ int run_dedup(vn_engine* h, const Batch& b, float* gradbuf, const VnEdgeSums& fx
   f.partial = h->dd_partial; f.losspart = lp;
   f.mode = 2; f.dir = -1; f.ostride = 1;
   f.seed_u = h->dd_su; f.seed_ud = nullptr;          // tangent seed 1
-  if (az) f.nB = 0;
+  if (az || bw) f.nB = 0;
   if (int rc = fused8_launch(h, f, grid)) return rc;
   if (int rc = prof_stop(h)) return rc;
   HIPCHK(vn_reduce_launch(h->dd_partial, grid + bparts, P, lp, grid + sblk + blp, h->bDof, h->nB, f.w0, f.w1, f.w2, gradbuf, h->stream,
@@ -1786,6 +1899,8 @@ int vn_destroy(vn_engine* h) {
     if (b.gcsr) (void)hipFree(b.gcsr);
     clear_weights(b);
   }
+  for (Adapt*& ad : h->bw) adapt_free(ad);
+  if (h->bw_field) (void)hipFree(h->bw_field);
   for (auto e : h->ev0) if (e) (void)hipEventDestroy(e);
   for (auto e : h->ev1) if (e) (void)hipEventDestroy(e);
   for (auto e : h->cev0) if (e) (void)hipEventDestroy(e);
@@ -1840,6 +1955,9 @@ int vn_params_init(vn_engine* h, uint64_t seed) {
       if (int rc = adapt_reset(h, *b.ad)) return rc;
       b.wt.omega = adapt_state(*b.ad, b.ad->cur).omega;
     }
+  for (Adapt* ad : h->bw)       // ... and so do the BC/IC rows' parts (a static part: its registered weights, rebuilt)
+    if (ad)
+      if (int rc = adapt_reset(h, *ad)) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
   h->step = 0;
   lbfgs_invalidate(h);
@@ -1872,6 +1990,8 @@ int vn_state_size(const vn_engine* h, int64_t* bytes) {
   *bytes = (int64_t)sizeof(int64_t) + 3ll * h->net.P * (int64_t)sizeof(float);
   for (const Batch& b : h->batches)   // the adaptive state of every registered batch, in batch order (none registered: nothing)
     if (b.ad) *bytes += adapt_bytes(*b.ad);
+  for (const Adapt* ad : h->bw)       // ... then that of every registered part of the BC/IC rows, bc first
+    if (ad) *bytes += adapt_bytes(*ad);
   return VN_OK;
 }
 
@@ -1893,6 +2013,15 @@ int vn_state_export(vn_engine* h, void* host, int64_t bytes) {
     if (b.ad) {
       const VnAdaptState s = adapt_state(*b.ad, b.ad->cur);
       const size_t nk = (size_t)b.ad->n_k * sizeof(float);
+      HIPCHK(hipMemcpyAsync(p, s.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      p += VN_ADAPT_SCAL * sizeof(double);
+      for (const float* piece : {(const float*)s.lambda, (const float*)s.omega, (const float*)s.m1, (const float*)s.m2})
+        if (piece) { HIPCHK(hipMemcpyAsync(p, piece, nk, hipMemcpyDeviceToHost, h->stream)); p += nk; }
+    }
+  for (const Adapt* ad : h->bw)
+    if (ad) {
+      const VnAdaptState s = adapt_state(*ad, ad->cur);
+      const size_t nk = (size_t)ad->n_k * sizeof(float);
       HIPCHK(hipMemcpyAsync(p, s.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToHost, h->stream));
       p += VN_ADAPT_SCAL * sizeof(double);
       for (const float* piece : {(const float*)s.lambda, (const float*)s.omega, (const float*)s.m1, (const float*)s.m2})
@@ -1928,6 +2057,12 @@ int vn_state_snapshot(vn_engine* h) {
       HIPCHK(hipMemcpyAsync(t.lambda, s.lambda, 4 * (size_t)b.ad->stride * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
       HIPCHK(hipMemcpyAsync(t.scal, s.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     }
+  for (const Adapt* ad : h->bw)
+    if (ad) {
+      const VnAdaptState s = adapt_state(*ad, ad->cur), t = adapt_snap(*ad);
+      HIPCHK(hipMemcpyAsync(t.lambda, s.lambda, 4 * (size_t)ad->stride * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(t.scal, s.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    }
   h->snap_step = h->step;
   return VN_OK;
 }
@@ -1953,6 +2088,13 @@ int vn_state_rollback(vn_engine* h) {
       HIPCHK(hipMemcpyAsync(s.lambda, t.lambda, 4 * (size_t)b.ad->stride * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
       HIPCHK(hipMemcpyAsync(s.scal, t.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
       b.ad->pending = false;
+    }
+  for (Adapt* ad : h->bw)
+    if (ad) {
+      const VnAdaptState s = adapt_state(*ad, ad->cur), t = adapt_snap(*ad);
+      HIPCHK(hipMemcpyAsync(s.lambda, t.lambda, 4 * (size_t)ad->stride * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(s.scal, t.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+      ad->pending = false;
     }
   h->step = h->snap_step;
   return VN_OK;
@@ -1985,6 +2127,16 @@ int vn_state_import(vn_engine* h, const void* host, int64_t bytes) {
       for (float* piece : {s.lambda, s.omega, s.m1, s.m2})
         if (piece) { HIPCHK(hipMemcpyAsync(piece, p, nk, hipMemcpyHostToDevice, h->stream)); p += nk; }
       b.ad->pending = false;
+    }
+  for (Adapt* ad : h->bw)
+    if (ad) {
+      const VnAdaptState s = adapt_state(*ad, ad->cur);
+      const size_t nk = (size_t)ad->n_k * sizeof(float);
+      HIPCHK(hipMemcpyAsync(s.scal, p, VN_ADAPT_SCAL * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      p += VN_ADAPT_SCAL * sizeof(double);
+      for (float* piece : {s.lambda, s.omega, s.m1, s.m2})
+        if (piece) { HIPCHK(hipMemcpyAsync(piece, p, nk, hipMemcpyHostToDevice, h->stream)); p += nk; }
+      ad->pending = false;
     }
   HIPCHK(hipStreamSynchronize(h->stream));
   lbfgs_invalidate(h);
@@ -2176,6 +2328,9 @@ static int learnt_set_learn(vn_engine* h, int id, int32_t J, const int32_t* mask
     if (int rc = extra(h)) return rc;
   for (size_t i = 0; i < h->batches.size(); ++i)
     if (has_weights(h->batches[i])) return learnt_weights_refusal(k, (int)i);
+  if (bicw_on(h))
+    return fail(VN_EUNSUPPORTED, "%s next to weights on the BC/IC rows (vn_set_bic_weights / vn_set_bic_adapt): the %s sums next to the "
+                                 "rows' own pass are not built", k.setter, k.noun);
   if (!(std::isfinite(lr) && lr > 0.0)) return fail(VN_EINVAL, "%s learning rate %g must be finite and > 0", k.noun, lr);
   for (int i = 0; i < J; ++i) {
     if (!std::isfinite(init[i])) return fail(VN_EINVAL, "initial %s %d = %g must be finite", k.noun, i, init[i]);
@@ -2537,28 +2692,34 @@ int vn_causal_weights(vn_engine* h, int32_t batch, double* omega_slab_host, int3
 // ---- self-adaptive weights (vn_adapt.hip) ----
 // par: [0], [1] = (gamma, eta) of rba or (lr, cap) of sa; [2..4] = beta1, beta2, eps of sa; [5] power; [6] init; [7] normalize;
 // [8] every; [9] reserved
+// The rule and its parameters (par: the layout above), as vn_set_tf_adapt and vn_set_bic_adapt check them
+static int adapt_check_par(const char* who, int32_t rule, const double par[10]) {
+  if (rule != VN_ADAPT_RBA && rule != VN_ADAPT_SA) return fail(VN_EINVAL, "%s: rule = %d is none of 0 (clear), 1 (rba), 2 (sa)", who, rule);
+  if (!par) return fail(VN_EINVAL, "%s: null parameter array", who);
+  for (int i = 0; i < 10; ++i)
+    if (!std::isfinite(par[i])) return fail(VN_EINVAL, "%s: par[%d] = %g is not finite", who, i, par[i]);
+  if (rule == VN_ADAPT_RBA) {
+    if (!(par[0] >= 0.0 && par[0] <= 1.0)) return fail(VN_EINVAL, "%s: rba gamma = %g must lie in [0, 1]", who, par[0]);
+    if (!(par[1] >= 0.0)) return fail(VN_EINVAL, "%s: rba eta = %g must be >= 0", who, par[1]);
+  } else {
+    if (!(par[0] >= 0.0)) return fail(VN_EINVAL, "%s: sa lr = %g must be >= 0", who, par[0]);
+    if (!(par[1] > 0.0)) return fail(VN_EINVAL, "%s: sa cap = %g must be positive", who, par[1]);
+    if (!(par[2] >= 0.0 && par[2] < 1.0) || !(par[3] >= 0.0 && par[3] < 1.0))
+      return fail(VN_EINVAL, "%s: sa beta1 = %g, beta2 = %g must lie in [0, 1)", who, par[2], par[3]);
+    if (!(par[4] > 0.0)) return fail(VN_EINVAL, "%s: sa eps = %g must be positive", who, par[4]);
+  }
+  if (par[5] != 1.0 && par[5] != 2.0) return fail(VN_EINVAL, "%s: power = %g must be 1 or 2", who, par[5]);
+  if (!(par[6] >= 0.0)) return fail(VN_EINVAL, "%s: init = %g must be >= 0", who, par[6]);
+  if (par[7] != 0.0 && par[7] != 1.0) return fail(VN_EINVAL, "%s: normalize = %g must be 0 or 1", who, par[7]);
+  if (!(par[8] >= 1.0) || par[8] != std::floor(par[8]) || par[8] > 1e15)
+    return fail(VN_EINVAL, "%s: every = %g must be a whole number >= 1", who, par[8]);
+  return VN_OK;
+}
+
 int vn_set_tf_adapt(vn_engine* h, int32_t batch, int32_t rule, const double par[10], const float* lambda_init_dev) {
   const bool clear = rule == VN_ADAPT_NONE;
   if (!clear) {
-    if (rule != VN_ADAPT_RBA && rule != VN_ADAPT_SA) return fail(VN_EINVAL, "vn_set_tf_adapt: rule = %d is none of 0 (clear), 1 (rba), 2 (sa)", rule);
-    if (!par) return fail(VN_EINVAL, "vn_set_tf_adapt: null parameter array");
-    for (int i = 0; i < 10; ++i)
-      if (!std::isfinite(par[i])) return fail(VN_EINVAL, "vn_set_tf_adapt: par[%d] = %g is not finite", i, par[i]);
-    if (rule == VN_ADAPT_RBA) {
-      if (!(par[0] >= 0.0 && par[0] <= 1.0)) return fail(VN_EINVAL, "vn_set_tf_adapt: rba gamma = %g must lie in [0, 1]", par[0]);
-      if (!(par[1] >= 0.0)) return fail(VN_EINVAL, "vn_set_tf_adapt: rba eta = %g must be >= 0", par[1]);
-    } else {
-      if (!(par[0] >= 0.0)) return fail(VN_EINVAL, "vn_set_tf_adapt: sa lr = %g must be >= 0", par[0]);
-      if (!(par[1] > 0.0)) return fail(VN_EINVAL, "vn_set_tf_adapt: sa cap = %g must be positive", par[1]);
-      if (!(par[2] >= 0.0 && par[2] < 1.0) || !(par[3] >= 0.0 && par[3] < 1.0))
-        return fail(VN_EINVAL, "vn_set_tf_adapt: sa beta1 = %g, beta2 = %g must lie in [0, 1)", par[2], par[3]);
-      if (!(par[4] > 0.0)) return fail(VN_EINVAL, "vn_set_tf_adapt: sa eps = %g must be positive", par[4]);
-    }
-    if (par[5] != 1.0 && par[5] != 2.0) return fail(VN_EINVAL, "vn_set_tf_adapt: power = %g must be 1 or 2", par[5]);
-    if (!(par[6] >= 0.0)) return fail(VN_EINVAL, "vn_set_tf_adapt: init = %g must be >= 0", par[6]);
-    if (par[7] != 0.0 && par[7] != 1.0) return fail(VN_EINVAL, "vn_set_tf_adapt: normalize = %g must be 0 or 1", par[7]);
-    if (!(par[8] >= 1.0) || par[8] != std::floor(par[8]) || par[8] > 1e15)
-      return fail(VN_EINVAL, "vn_set_tf_adapt: every = %g must be a whole number >= 1", par[8]);
+    if (int rc = adapt_check_par("vn_set_tf_adapt", rule, par)) return rc;
     if (h && h->comm)
       return fail(VN_EUNSUPPORTED, "vn_set_tf_adapt under a communicator: a rank's max, mean and Z would cover only its shard, so the "
                                    "ranks together would train another objective than one rank");
@@ -2660,6 +2821,185 @@ int vn_set_tf_adapt_state(vn_engine* h, int32_t batch, const float* lambda_host,
   return VN_OK;
 }
 
+// ---- weights on the BC/IC rows (vn_bicadapt.hip): static (vn_set_bic_weights) or self-adaptive (vn_set_bic_adapt), per part ----
+static const char* const kBicPart[2] = {"bc", "ic"};
+
+// What both registrations check before they build a state
+static int bicw_common(vn_engine* h, const char* who) {
+  if (h->nB <= 0) return fail(VN_ESTATE, "%s: no BC/IC rows are registered (call vn_set_bic first)", who);
+  if (h->route == Route::layered || !vn_net_in_kernel_range(h->net))
+    return fail(VN_EUNSUPPORTED, "%s needs a network of the hand-written kernels (<= %d hidden layers, width <= %d, <= %d inputs, one "
+                "activation): the rows' own pass runs on the generic kernels; this one (%d layers, widest %d, %d inputs%s) runs on the "
+                "layer-by-layer route or the deep fused kernel only", who, VN_KMAX_LAYERS, VN_KMAX_WIDTH, VN_KMAX_DIN, h->net.L,
+                h->net.hmax, h->net.d_in, h->net.act == VN_ACT_PER_LAYER ? ", mixed activations" : "");
+  if (h->route == Route::fused4)
+    return fail(VN_EUNSUPPORTED, "%s is not built for VN_KERNEL_FUSED (the 4-wave cross-check geometry); every other kernel family "
+                                 "carries the rows' own pass", who);
+  if (int rc = bicw_check(h, who)) return rc;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const long need = vn_adapt_stride(h->bDof) + vn_adapt_stride(h->nB - h->bDof);
+  if (need > h->bw_field_cap) {
+    if (int rc = ensure(&h->bw_field, &h->bw_field_cap, need)) return rc;
+    HIPCHK(hipMemsetAsync(h->bw_field, 0, (size_t)need * sizeof(float), h->stream));
+  }
+  return VN_OK;
+}
+
+// The state of one part, built and brought to its initial values: lambda from init_dev (validated on the device: finite, >= 0),
+// else `fill`.  *out on success; on failure nothing is kept.
+static int bicw_make(vn_engine* h, const char* who, int part, int rule, const double par[10], int power, int normalize, long every,
+                     const float* init_dev, float fill, Adapt** out) {
+  const long n = bicw_count(h, part);
+  Adapt* ad = new Adapt();
+  ad->rule = rule; ad->power = power; ad->normalize = normalize; ad->every = every;
+  if (par) std::copy(par, par + 10, ad->par);
+  ad->n_k = n; ad->stride = vn_adapt_stride(n);
+  hipError_t e = hipMalloc((void**)&ad->f, (size_t)(kAdaptPieces * ad->stride) * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&ad->d, (size_t)kAdaptDoubles * sizeof(double));
+  if (e == hipSuccess) e = hipMemsetAsync(ad->f, 0, (size_t)(kAdaptPieces * ad->stride) * sizeof(float), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(ad->d, 0, (size_t)kAdaptDoubles * sizeof(double), h->stream);
+  int rc = VN_OK;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    rc = fail(VN_ENOMEM, "%s: the state of %ld %s rows does not fit: %s", who, n, kBicPart[part], hipGetErrorString(e));
+  } else if (init_dev) {
+    int bad = 0;
+    auto check = [&](int* err_dev) { return vn_adapt_check_copy_launch(init_dev, n, adapt_lambda0(*ad), err_dev, h->stream); };
+    rc = count_on_device(h, check, &bad);
+    if (rc == VN_OK && bad)
+      rc = fail(VN_EINVAL, "%s: %d %s of the %s part negative or not finite", who, bad, rule == VN_ADAPT_NONE ? "weight(s)" : "initial lambda(s)",
+                kBicPart[part]);
+  } else {
+    e = vn_adapt_fill_launch(adapt_lambda0(*ad), n, fill, h->stream);
+    if (e != hipSuccess) rc = fail(VN_EHIP, "%s: %s", who, hipGetErrorString(e));
+  }
+  if (rc == VN_OK) rc = adapt_reset(h, *ad);
+  if (rc == VN_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(VN_EHIP, "%s: the initial state could not be formed", who);
+  if (rc != VN_OK) { adapt_free(ad); return rc; }
+  *out = ad;
+  return VN_OK;
+}
+
+int vn_set_bic_weights(vn_engine* h, const float* omega_dev, int32_t normalize) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (!omega_dev) {                                  // clear: both parts, whatever they hold
+    if (!bicw_on(h)) return VN_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (Adapt*& ad : h->bw) adapt_free(ad);
+    lbfgs_invalidate(h);
+    return VN_OK;
+  }
+  if (normalize != 0 && normalize != 1) return fail(VN_EINVAL, "vn_set_bic_weights: normalize = %d must be 0 or 1", normalize);
+  (void)hipGetLastError();
+  if (int rc = bicw_common(h, "vn_set_bic_weights")) return rc;
+  Adapt* made[2] = {nullptr, nullptr};
+  for (int s = 0; s < 2; ++s) {
+    if (bicw_count(h, s) <= 0) continue;
+    // a state that never moves: lambda = the caller's omega, m(x) = x, Z = its mean over the part (normalize) or 1
+    if (int rc = bicw_make(h, "vn_set_bic_weights", s, VN_ADAPT_NONE, nullptr, 1, normalize, 1, omega_dev + (s ? h->bDof : 0), 0.f, &made[s])) {
+      adapt_free(made[0]);
+      return rc;                                     // the rows keep what they had
+    }
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int s = 0; s < 2; ++s) { adapt_free(h->bw[s]); h->bw[s] = made[s]; }   // replaces a static or an adaptive registration
+  lbfgs_invalidate(h);
+  return VN_OK;
+}
+
+int vn_set_bic_adapt(vn_engine* h, int32_t part, int32_t rule, const double par[10], const float* lambda_init_dev) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (part != 0 && part != 1) return fail(VN_EINVAL, "vn_set_bic_adapt: part = %d is neither 0 (bc) nor 1 (ic)", part);
+  if (rule == VN_ADAPT_NONE) {                       // clear this part
+    if (!h->bw[part]) return VN_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    adapt_free(h->bw[part]);
+    lbfgs_invalidate(h);
+    return VN_OK;
+  }
+  if (int rc = adapt_check_par("vn_set_bic_adapt", rule, par)) return rc;
+  if (is_lbfgs(h))
+    return fail(VN_EUNSUPPORTED, "vn_set_bic_adapt on an L-BFGS engine: the weights move from step to step but are held constant for the "
+                                 "gradient, so an Armijo test across steps means nothing; static weights (vn_set_bic_weights) work");
+  (void)hipGetLastError();
+  if (int rc = bicw_common(h, "vn_set_bic_adapt")) return rc;
+  if (bicw_count(h, part) <= 0)
+    return fail(VN_ESTATE, "vn_set_bic_adapt: the %s part has no rows (nB = %ld, bDof = %ld%s)", kBicPart[part], h->nB, h->bDof,
+                h->cfg.time_dependent ? "" : ", a steady engine has no initial rows");
+  Adapt* ad = nullptr;
+  if (int rc = bicw_make(h, "vn_set_bic_adapt", part, rule, par, (int)par[5], (int)par[7], (long)par[8], lambda_init_dev, (float)par[6], &ad))
+    return rc;
+  adapt_free(h->bw[part]);                           // replaces a static or an earlier adaptive registration of this part
+  h->bw[part] = ad;
+  lbfgs_invalidate(h);
+  return VN_OK;
+}
+
+static int bicw_of(vn_engine* h, int32_t part, const char* who, Adapt** ad) {
+  if (!h) return fail(VN_EINVAL, "null handle");
+  if (part != 0 && part != 1) return fail(VN_EINVAL, "%s: part = %d is neither 0 (bc) nor 1 (ic)", who, part);
+  if (!h->bw[part])
+    return fail(VN_ESTATE, "%s: the %s part has no registration (call vn_set_bic_weights or vn_set_bic_adapt first)", who, kBicPart[part]);
+  *ad = h->bw[part];
+  return VN_OK;
+}
+
+int vn_get_bic_adapt(vn_engine* h, int32_t part, float* lambda_host, float* omega_host, float* slots_host, float* lossfield_host,
+                     double stats[6]) {
+  Adapt* ad = nullptr;
+  if (int rc = bicw_of(h, part, "vn_get_bic_adapt", &ad)) return rc;
+  const VnAdaptState s = adapt_state(*ad, ad->cur);
+  if (slots_host && !s.m1) return fail(VN_EINVAL, "vn_get_bic_adapt: the %s part runs no sa rule, so it has no slots", kBicPart[part]);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t nk = (size_t)ad->n_k * sizeof(float);
+  if (lambda_host) HIPCHK(hipMemcpyAsync(lambda_host, s.lambda, nk, hipMemcpyDeviceToHost, h->stream));
+  if (omega_host) HIPCHK(hipMemcpyAsync(omega_host, s.omega, nk, hipMemcpyDeviceToHost, h->stream));
+  if (slots_host) {
+    HIPCHK(hipMemcpyAsync(slots_host, s.m1, nk, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(slots_host + ad->n_k, s.m2, nk, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (lossfield_host) HIPCHK(hipMemcpyAsync(lossfield_host, bicw_field(h, part), nk, hipMemcpyDeviceToHost, h->stream));
+  if (stats) HIPCHK(hipMemcpyAsync(stats, s.scal, 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return VN_OK;
+}
+
+int vn_set_bic_adapt_state(vn_engine* h, int32_t part, const float* lambda_host, const float* slots_host, int64_t tau) {
+  Adapt* ad = nullptr;
+  if (int rc = bicw_of(h, part, "vn_set_bic_adapt_state", &ad)) return rc;
+  if (ad->rule == VN_ADAPT_NONE)
+    return fail(VN_ESTATE, "vn_set_bic_adapt_state: the %s part holds static weights (vn_set_bic_weights), which have no state to set",
+                kBicPart[part]);
+  if (!lambda_host) return fail(VN_EINVAL, "vn_set_bic_adapt_state: null lambda");
+  if (tau < 0) return fail(VN_EINVAL, "vn_set_bic_adapt_state: tau = %lld must be >= 0", (long long)tau);
+  if (slots_host && ad->rule != VN_ADAPT_SA)
+    return fail(VN_EINVAL, "vn_set_bic_adapt_state: the %s part runs the rba rule, which has no slots", kBicPart[part]);
+  for (long k = 0; k < ad->n_k; ++k)
+    if (!(lambda_host[k] >= 0.f && std::isfinite(lambda_host[k])))
+      return fail(VN_EINVAL, "vn_set_bic_adapt_state: lambda[%ld] = %g is negative or not finite", k, (double)lambda_host[k]);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const VnAdaptState s = adapt_state(*ad, ad->cur);
+  const size_t nk = (size_t)ad->n_k * sizeof(float);
+  double scal[VN_ADAPT_SCAL] = {};
+  scal[5] = (double)tau;
+  HIPCHK(hipMemcpyAsync(s.lambda, lambda_host, nk, hipMemcpyHostToDevice, h->stream));
+  if (s.m1) {                   // NULL slots: zeros
+    if (slots_host) {
+      HIPCHK(hipMemcpyAsync(s.m1, slots_host, nk, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(s.m2, slots_host + ad->n_k, nk, hipMemcpyHostToDevice, h->stream));
+    } else {
+      HIPCHK(hipMemsetAsync(s.m1, 0, 2 * (size_t)ad->stride * sizeof(float), h->stream));
+    }
+  }
+  HIPCHK(hipMemcpyAsync(s.scal, scal, sizeof scal, hipMemcpyHostToDevice, h->stream));
+  if (int rc = adapt_rebuild(h, *ad)) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));   // the host arrays may be released on return
+  lbfgs_invalidate(h);
+  return VN_OK;
+}
+
 int vn_set_bic(vn_engine* h, const float* biInput, const float* biLabel, int64_t nB, int64_t bDof, double biDimVal) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (nB < 0 || bDof < 0 || bDof > nB) return fail(VN_EINVAL, "need 0 <= bDof <= nB");
@@ -2669,6 +3009,10 @@ int vn_set_bic(vn_engine* h, const float* biInput, const float* biLabel, int64_t
   h->nBreg = nB;
   h->bicB = nullptr; h->bicJ = 0;                    // the shared set's basis goes with it (vn_set_bic_basis)
   h->az_bic = Ansatz();                              // ... and its ansatz streams (vn_set_ansatz_rows)
+  if (bicw_on(h)) {                                  // ... and the rows' weights (vn_set_bic_weights, vn_set_bic_adapt)
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (Adapt*& ad : h->bw) adapt_free(ad);
+  }
   if (!h->cfg.time_dependent) nB = bDof;
   h->biInput = biInput; h->biLabel = biLabel; h->nB = nB; h->bDof = bDof; h->biDimVal = biDimVal;
   lbfgs_invalidate(h);
@@ -2836,6 +3180,9 @@ int vn_set_ansatz_rows(vn_engine* h, int32_t set, const float* A, const float* B
       if (h->batches[i].biInput)
         return fail(VN_EUNSUPPORTED, "vn_set_ansatz_rows(VN_ANSATZ_BIC) next to batch %zu's own copy of the BC/IC rows (vn_set_batch_bic): "
                                      "the streams belong to the rows of vn_set_bic", i);
+  if (set == VN_ANSATZ_BIC && bicw_on(h))
+    return fail(VN_EUNSUPPORTED, "vn_set_ansatz_rows(VN_ANSATZ_BIC) next to weights on the BC/IC rows (vn_set_bic_weights / vn_set_bic_adapt): "
+                                 "under a hard-constraint ansatz the rows' error is zero by construction, there is nothing to weight");
   if (int rc = ansatz_check_route(h)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   Ansatz z;
@@ -2853,6 +3200,9 @@ int vn_set_batch_bic(vn_engine* h, int32_t batch, const float* biInput, const fl
   if (biInput && h->az_bic.B)
     return fail(VN_EUNSUPPORTED, "vn_set_batch_bic next to BC/IC ansatz streams (vn_set_ansatz_rows): the streams belong to the rows of "
                                  "vn_set_bic, a batch's own copy of the rows would be evaluated with them");
+  if (biInput && bicw_on(h))
+    return fail(VN_EUNSUPPORTED, "vn_set_batch_bic next to weights on the BC/IC rows (vn_set_bic_weights / vn_set_bic_adapt): the weights "
+                                 "belong to the rows of vn_set_bic, one state per row");
   h->batches[batch].biInput = biInput;
   h->batches[batch].biLabel = biLabel;
   h->batches[batch].bb_B = nullptr; h->batches[batch].bb_J = 0;     // the copy's basis goes with it (vn_set_bic_basis)
@@ -2996,6 +3346,8 @@ int vn_grad(vn_engine* h, int32_t batch) {
   HIPCHK(hipSetDevice(h->cfg.device));
   const Batch& b = h->batches[batch];
   if (int rc = ansatz_check_eval(h, b, batch)) return rc;
+  if (bicw_on(h))
+    if (int rc = bicw_check(h, "weights on the BC/IC rows (vn_set_bic_weights / vn_set_bic_adapt)")) return rc;
   const LearntKind* learnt = learnt_any(h);
   if (learnt && has_ansatz(b))
     return fail(VN_EUNSUPPORTED, "learnt %s (%s) next to a hard-constraint ansatz (vn_set_ansatz, batch %d): the %s sums next to the "
@@ -3264,6 +3616,11 @@ int vn_lbfgs_step(vn_engine* h, int32_t batch, int32_t max_trials, double info[1
     return fail(VN_EUNSUPPORTED, "vn_lbfgs_step on batch %d, which has an adaptive registration (vn_set_tf_adapt): its weights move from "
                                  "step to step but are held constant for the gradient, so an Armijo test across steps means nothing; "
                                  "static weights (vn_set_tf_weights) work", batch);
+  for (const Adapt* ad : h->bw)
+    if (ad && ad->rule != VN_ADAPT_NONE)
+      return fail(VN_EUNSUPPORTED, "vn_lbfgs_step next to an adaptive registration on the BC/IC rows (vn_set_bic_adapt): its weights move "
+                                   "from step to step but are held constant for the gradient, so an Armijo test across steps means "
+                                   "nothing; static weights (vn_set_bic_weights) work");
   if (h->lb_loss64 && has_ansatz(h->batches[batch]))
     return fail(VN_EUNSUPPORTED, "vn_lbfgs_step with vn_lbfgs_loss64 on batch %d, which has a hard-constraint ansatz (vn_set_ansatz): the "
                                  "fp64 objective does not carry the ansatz stage", batch);
@@ -3353,6 +3710,8 @@ int vn_eval_loss(vn_engine* h, int32_t batch, double out[4], float* lossVec_dev)
   if (int rc = check_batch(h, batch)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   if (int rc = ansatz_check_eval(h, h->batches[batch], batch)) return rc;
+  if (bicw_on(h))
+    if (int rc = bicw_check(h, "weights on the BC/IC rows (vn_set_bic_weights / vn_set_bic_adapt)")) return rc;
   if (int rc = source_mix(h, h->batches[batch], batch)) return rc;
   if (int rc = field_mix(h, h->batches[batch], batch)) return rc;
   if (int rc = bic_mix(h, h->batches[batch], batch)) return rc;
@@ -3379,6 +3738,8 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
   if (has_ansatz(h->batches[batch]) || h->az_bic.B || h->az_edge[0].B || h->az_edge[1].B || h->az_edge[2].B)
     return fail(VN_EUNSUPPORTED, "vn_objective_f64 on batch %d next to a hard-constraint ansatz (vn_set_ansatz, vn_set_ansatz_rows): the "
                                  "fp64 objective does not carry the ansatz stage", batch);
+  if (bicw_on(h))
+    if (int rc = bicw_check(h, "weights on the BC/IC rows (vn_set_bic_weights / vn_set_bic_adapt)")) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   if (!theta_dev) {
     if (int rc = refresh_theta64(h)) return rc;
@@ -3412,6 +3773,8 @@ int vn_objective_f64(vn_engine* h, int32_t batch, const double* theta_dev, doubl
     for (int i = 0; i < 3; ++i) { p.coef[i] = c[i]; p.fcoef3[i] = c[3 + i]; p.dcoef3[i] = c[6 + i]; }
   }
   p.wt = b.wt;
+  for (int s = 0; s < 2; ++s)   // weights on the BC/IC rows: the committed omega, widened exactly (a probe: nothing moves)
+    p.bic_omega[s] = h->bw[s] ? adapt_state(*h->bw[s], h->bw[s]->cur).omega : nullptr;
   hipError_t e = vn_obj64_run(h->o64, p, grad_dev, lossVec_dev, out, h->ncu, h->stream);
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(h->stream);
@@ -3542,6 +3905,9 @@ int vn_comm_init(vn_engine* h, int32_t rank, int32_t world, const void* unique_i
     if (h->batches[i].ad)
       return fail(VN_EUNSUPPORTED, "vn_comm_init: batch %d has an adaptive registration (vn_set_tf_adapt); a rank's max, mean and Z would "
                                    "cover only its shard, so the ranks together would train another objective than one rank", (int)i);
+  if (bicw_on(h))
+    return fail(VN_EUNSUPPORTED, "vn_comm_init next to weights on the BC/IC rows (vn_set_bic_weights / vn_set_bic_adapt): a rank's max, mean "
+                                 "and Z would follow its own shard's steps, so the ranks together would train another objective than one rank");
   for (int id = LV_N - 1; id >= 0; --id)       // (the field amplitudes are reported first)
     if (h->lv[id].on)
       return fail(VN_EUNSUPPORTED, "vn_comm_init while %s are learnt (%s): %s are not in the all-reduced buffer, so every rank would "

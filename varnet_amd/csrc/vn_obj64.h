@@ -3,6 +3,7 @@
 #pragma once
 #include "vn_internal.h"
 #include "vn_weights.h"
+#include "vn_bicadapt.h"
 
 // Engine-owned work buffers of the evaluation, sized at the call that first needs them and released by vn_obj64_free.
 struct VnObj64Work {
@@ -17,6 +18,8 @@ struct VnObj64Work {
   double* lvec = nullptr;  long lvec_cap = 0;    // [n_k] the loss field when the caller passes none
   double* omega = nullptr; long omega_cap = 0;   // [n_k] omega_k in double
   double* wstat = nullptr; long wstat_cap = 0;   // causal: lsum [S * chunks], then omega_s [S]
+  // weights on the BC/IC rows (vn_bicadapt.hip), allocated by the first evaluation that has them
+  double* bwpart = nullptr; long bwpart_cap = 0; // [row blocks][2]: weighted bc, ic partial sums
 };
 
 // What the evaluation reads: the batch as registered (fp32 device arrays, widened exactly by the kernels).
@@ -47,6 +50,9 @@ struct VnObj64Problem {
   int nldiff; const float* psi; double dcoef3[3];
   // per-test-function loss weights of the batch (vn_set_tf_weights / vn_set_causal); default: none
   VnWeightsReg wt;
+  // weights on the BC/IC rows (vn_set_bic_weights / vn_set_bic_adapt): the committed omega of bc [bDof] and ic [nB - bDof], fp32,
+  // widened exactly; nullptr: 1; default: none
+  const float* bic_omega[2];
 };
 
 bool vn_obj64_supported(const VnNet& net);

@@ -585,12 +585,12 @@ hipError_t ensure_d(double** p, long* cap, long need) {
 bool vn_obj64_supported(const VnNet& net) { return vn_net_in_kernel_range(net) && net.dim <= 3; }
 
 void vn_obj64_free(VnObj64Work& w) {
-  double** ps[] = {&w.img, &w.u, &w.ud, &w.act, &w.part, &w.lpart, &w.out, &w.lvec, &w.omega, &w.wstat};
+  double** ps[] = {&w.img, &w.u, &w.ud, &w.act, &w.part, &w.lpart, &w.out, &w.lvec, &w.omega, &w.wstat, &w.bwpart};
   for (double** p : ps) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
-  w.img_cap = w.u_cap = w.ud_cap = w.act_cap = w.part_cap = w.lpart_cap = w.lvec_cap = w.omega_cap = w.wstat_cap = 0;
+  w.img_cap = w.u_cap = w.ud_cap = w.act_cap = w.part_cap = w.lpart_cap = w.lvec_cap = w.omega_cap = w.wstat_cap = w.bwpart_cap = 0;
 }
 
 hipError_t vn_obj64_run(VnObj64Work& w, const VnObj64Problem& p, double* grad_dev, double* lossVec_dev, double out_host[4],
@@ -652,8 +652,19 @@ hipError_t vn_obj64_run(VnObj64Work& w, const VnObj64Problem& p, double* grad_de
     OCHK(ensure_d(&w.omega, &w.omega_cap, p.n_k));
     if (p.wt.S > 0) OCHK(ensure_d(&w.wstat, &w.wstat_cap, (long)p.wt.S * (p.wt.chunks + 1)));
   }
+  // weights on the BC/IC rows (vn_bicadapt.hip): the weighted partial sums from the forward values before the seed kernel puts
+  // the seeds in their place, then those partials in place of the unweighted ones and the rows' seeds scaled
+  VnBicRows64Args bw;
+  const bool bweighted = (p.bic_omega[0] || p.bic_omega[1]) && nB > 0;
+  if (bweighted) {
+    OCHK(ensure_d(&w.bwpart, &w.bwpart_cap, 2L * vn_bic_rows_blocks(nB)));
+    bw.u = w.u + n0; bw.label = p.label; bw.nB = nB; bw.bDof = p.bDof; bw.biDimVal = p.biDimVal;
+    bw.omega[0] = p.bic_omega[0]; bw.omega[1] = p.bic_omega[1]; bw.wpart = w.bwpart; bw.lpart = w.lpart; bw.seeds = sa.seeds;
+    OCHK(vn_bic_rows_f64_launch(bw, 0, s));
+  }
   hipLaunchKernelGGL(vn_obj64_seed_kernel, dim3(sblk), dim3(256), 0, s, sa);
   OCHK(hipGetLastError());
+  if (bweighted) OCHK(vn_bic_rows_f64_launch(bw, 1, s));
   if (weighted) {
     VnWeightsWork wk;
     wk.lsum = w.wstat; wk.oslab = w.wstat ? w.wstat + (long)p.wt.S * p.wt.chunks : nullptr;

@@ -80,6 +80,10 @@ _SIGS = {
     'vn_set_tf_adapt': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p]),
     'vn_get_tf_adapt': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     'vn_set_tf_adapt_state': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
+    'vn_set_bic_weights': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    'vn_set_bic_adapt': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p]),
+    'vn_get_bic_adapt': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    'vn_set_bic_adapt_state': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     'vn_set_coef_learn': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                     C.POINTER(C.c_double), C.c_double]),
     'vn_get_coefs': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -539,6 +543,9 @@ class VNEngine:
 
     def set_bic(self, biInput, biLabel, bDof, biDimVal):
         self._bic_key = None
+        self._keep.pop('bicw', None)               # vn_set_bic clears the rows' weights (set_bic_weights, set_bic_adapt)
+        nB = 0 if biInput is None else int(len(biInput))
+        self._bic_rows = (int(bDof) if nB else 0, (nB - int(bDof)) if nB and self.cfg.time_dependent else 0)   # rows of (bc, ic)
         self._keep.pop(('ansatzrows', 'bic'), None)   # vn_set_bic drops the rows' ansatz streams
         self._keep.pop(('bicbasis', -1), None)     # vn_set_bic clears the shared set's basis
         if biInput is None or len(biInput) == 0:
@@ -1051,6 +1058,97 @@ class VNEngine:
                 raise ValueError('set_tf_adapt_state: expected %d slot values, got %d' % (2 * lam.size, slots.size))
         self._ck(self.lib.vn_set_tf_adapt_state(self.h, int(batch), lam.ctypes.data, None if slots is None else slots.ctypes.data,
                                                 int(tau)))
+
+    # -- weights on the BC/IC rows -------------------------------------------------------------
+    BIC_PARTS = {'bc': 0, 'ic': 1}
+
+    def _bic_part(self, part):
+        if part not in self.BIC_PARTS and part not in (0, 1):
+            raise ValueError("the part of the BC/IC rows must be 'bc' (0) or 'ic' (1) (got %r)" % (part,))
+        return self.BIC_PARTS.get(part, part)
+
+    def bic_rows(self, part):
+        """Rows of a part of the registered BC/IC rows as the engine counts them (a steady engine has no 'ic' rows)."""
+        return getattr(self, '_bic_rows', (0, 0))[self._bic_part(part)]
+
+    def bic_parts(self):
+        """{part name: 'static' or the adaptive spec} of the parts that carry a registration."""
+        return dict(self._keep.get('bicw') or {})
+
+    def set_bic_weights(self, omega=None, normalize=False):
+        """Register (or, with omega=None, clear -- both parts, whatever they hold) static weights on the BC/IC rows
+        (vn_set_bic_weights), after set_bic: one value >= 0 per row the engine counts, validated and copied by the call;
+        normalize applies per part.  Replaces every registration of the parts that have rows."""
+        if omega is None:
+            self._ck(self.lib.vn_set_bic_weights(self.h, None, 0))
+            self._keep.pop('bicw', None)
+            return
+        t = self.torch
+        om = self.dev(omega.reshape(-1) if isinstance(omega, t.Tensor) else np.reshape(omega, -1))
+        n = sum(getattr(self, '_bic_rows', (0, 0)))
+        if om.numel() != n:
+            raise ValueError('set_bic_weights: expected one weight per BC/IC row (%d), got %d' % (n, om.numel()))
+        self._ck(self.lib.vn_set_bic_weights(self.h, _ptr(om), 1 if normalize else 0))
+        self._keep['bicw'] = {name: 'static' for name, s in self.BIC_PARTS.items() if self._bic_rows[s] > 0}
+
+    def set_bic_adapt(self, part, spec=None, lambda_init=None):
+        """Register (or, with spec=None, clear) self-adaptive weights on one part ('bc' / 'ic') of the BC/IC rows
+        (vn_set_bic_adapt), after set_bic.  spec and lambda_init as for set_tf_adapt, with the part's rows in place of the test
+        functions.  Replaces a static or an adaptive registration of that part."""
+        s = self._bic_part(part)
+        name = ('bc', 'ic')[s]
+        spec = tf_adapt_spec(spec)
+        kept = dict(self._keep.get('bicw') or {})
+        if spec is None:
+            self._ck(self.lib.vn_set_bic_adapt(self.h, s, 0, None, None))
+            kept.pop(name, None)
+        else:
+            lam = None
+            if lambda_init is not None:
+                t = self.torch
+                lam = self.dev(lambda_init.reshape(-1) if isinstance(lambda_init, t.Tensor) else np.reshape(lambda_init, -1))
+                if lam.numel() != self.bic_rows(s):
+                    raise ValueError('set_bic_adapt: lambda_init must have one entry per %s row (%d != %d)'
+                                     % (name, lam.numel(), self.bic_rows(s)))
+            rule, par = tf_adapt_par(spec)
+            self._ck(self.lib.vn_set_bic_adapt(self.h, s, rule, (C.c_double * 10)(*par), _ptr(lam)))
+            kept[name] = spec                                             # (the engine copied the initial values)
+        if kept:
+            self._keep['bicw'] = kept
+        else:
+            self._keep.pop('bicw', None)
+
+    def bic_adapt(self, part, arrays=True):
+        """The committed state of a registered part (vn_get_bic_adapt): {'lambda', 'omega', 'lossfield' [n_s] float32 (the
+        unweighted l_i of the last evaluation), 'slots' [2, n_s] (sa) or None, 'stats': {'min', 'max', 'mean', 'share', 'Z',
+        'tau'}}; arrays=False reads the statistics alone.  Synchronises; changes no engine state."""
+        s = self._bic_part(part)
+        n = self.bic_rows(s)
+        spec = (self._keep.get('bicw') or {}).get(('bc', 'ic')[s])
+        st = (C.c_double * 6)()
+        out = {'lambda': None, 'omega': None, 'slots': None, 'lossfield': None}
+        if arrays:
+            for k in ('lambda', 'omega', 'lossfield'):
+                out[k] = np.empty(n, np.float32)
+            if isinstance(spec, dict) and spec['rule'] == 'sa':
+                out['slots'] = np.empty((2, n), np.float32)
+        self._ck(self.lib.vn_get_bic_adapt(self.h, s, *[None if out[k] is None else out[k].ctypes.data
+                                                        for k in ('lambda', 'omega', 'slots', 'lossfield')], st))
+        out['stats'] = dict(zip(('min', 'max', 'mean', 'share', 'Z', 'tau'), [float(x) for x in st]))
+        return out
+
+    def set_bic_adapt_state(self, part, lam, slots=None, tau=0):
+        """Puts the state of an adaptive part back (vn_set_bic_adapt_state): lambda [n_s], slots [2, n_s] (sa; None: zeros), tau.
+        omega, Z and the statistics are rebuilt on the device.  Synchronises."""
+        s = self._bic_part(part)
+        lam = np.ascontiguousarray(lam, dtype=np.float32).ravel()
+        if lam.size != self.bic_rows(s):
+            raise ValueError('set_bic_adapt_state: expected %d lambdas, got %d' % (self.bic_rows(s), lam.size))
+        if slots is not None:
+            slots = np.ascontiguousarray(slots, dtype=np.float32).ravel()
+            if slots.size != 2 * lam.size:
+                raise ValueError('set_bic_adapt_state: expected %d slot values, got %d' % (2 * lam.size, slots.size))
+        self._ck(self.lib.vn_set_bic_adapt_state(self.h, s, lam.ctypes.data, None if slots is None else slots.ctypes.data, int(tau)))
 
     # -- learnt weight scales --------------------------------------------------------------
     def set_reparam(self, mode=None, per='neuron', n=1.0, s_init=None, lr=None):

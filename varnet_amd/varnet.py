@@ -265,6 +265,7 @@ class TrainResult:
         self.lossVec = None
         self.balanceHist = []             # (extension) one (epoch, weights, norms, cosines, skipped) per probe of train(balance=...)
         self.tfAdaptHist = []             # (extension) one (epoch, [stats of every batch]) per monitor of a run with tfAdapt=...
+        self.bicAdaptHist = []            # (extension) one (epoch, {part: stats}) per monitor of a run with bicWeights= / bicAdapt=
         self.option_stopping = self.option_trainPoint = self.option_weighting = self.option_batchOptim = None
 
     # -- case file ------------------------------------------------------------------------------------
@@ -318,6 +319,15 @@ class TrainResult:
             ad = varNet.tfAdapt
             L.append('Self-adaptive test-function weights: rule %s, %s\n\n'
                      % (ad['rule'], ', '.join('%s = %r' % (k, ad[k]) for k in sorted(ad) if k != 'rule')))
+        if getattr(varNet, 'bicWeights', None) is not None or getattr(varNet, 'bicAdapt', None) is not None:
+            what = []
+            for part in ('bc', 'ic'):
+                ad = (varNet.bicAdapt or {}).get(part)
+                if ad is not None:
+                    what.append('%s: rule %s, %s' % (part, ad['rule'], ', '.join('%s = %r' % (k, ad[k]) for k in sorted(ad) if k != 'rule')))
+                elif varNet.bicWeights is not None and part in varNet.bicWeights:
+                    what.append('%s: static' % part)
+            L.append('Weights on the boundary and initial rows: %s\n\n' % '; '.join(what))
         for stem, pr in (getattr(varNet, 'learntPrior', None) or {}).items():
             for key, b in pr['blocks'].items():
                 L.append('Prior on the learnt %s%s: weight %s, matrix %s, mean %s, l1 %s\n\n'
@@ -843,7 +853,9 @@ class ManageTrainData:
         if getattr(eng, '_bic_key', None) == (key, mb):
             return
         d = self.mor[mb]
+        self.vn._bic_weights_save()               # vn_set_bic clears the rows' weights: the set that holds them keeps its state
         eng.set_bic(d['biInput'], d['biLabel'], self.bDofsum, self.biDimVal)
+        self.vn._bic_weights_register(self, d)    # bicWeights= / bicAdapt= on these rows, this set's own state carried
         if d.get('az_bic') is not None:           # the ansatz streams of these rows (vn_set_ansatz_rows)
             eng.set_ansatz_rows('bic', *d['az_bic'])
         if d.get('bicB') is not None:             # the basis of these labels (vn_set_bic_basis, the shared set)
@@ -891,7 +903,7 @@ class VarNet:
                  learnCoef=None, coefLr=None, coefBounds=None, learnSource=None, sourceLr=None, sourceBounds=None,
                  learnField=None, fieldLr=None, fieldBounds=None, learnBic=None, bicLr=None, bicBounds=None,
                  learnFluxBC=None, fluxBCLr=None, fluxBCBounds=None, learntPrior=None, reparam=None, reparamLr=None,
-                 tfAdapt=None):
+                 tfAdapt=None, bicWeights=None, bicAdapt=None):
         dim = PDE.dim
         timeDependent = PDE.timeDependent
         MORvar = PDE.MORvar
@@ -960,6 +972,13 @@ class VarNet:
         # every step from that step's own loss field (`tf_adapt_spec`, VNEngine.set_tf_adapt)
         self.tfAdapt = self._check_tf_adapt(tfAdapt, causal is not None, optimizer.lower() == 'lbfgs', MORvar is not None,
                                             isinstance(processors, (list, tuple)) and len(processors) > 1)
+        # bicWeights=..., bicAdapt=... (extension; no reference counterpart): one weight per Dirichlet and initial row, static or
+        # moved on the device at every step from that step's own errors (VNEngine.set_bic_weights / set_bic_adapt, DESIGN.md
+        # section 35)
+        self.bicWeights, self.bicAdapt = self._check_bic_weights(
+            bicWeights, bicAdapt, optimizer.lower() == 'lbfgs', MORvar is not None,
+            isinstance(processors, (list, tuple)) and len(processors) > 1, getattr(PDE, 'ansatz', None) is not None, timeDependent)
+        self._bicw_owner = None
         if fluxBC and MORvar is not None:
             raise NotImplementedError('fluxBC=True with model-order reduction is not supported: the flux rows carry one label '
                                       'g/a per boundary point, shared by all batches, while a MOR problem needs per-batch labels '
@@ -1033,6 +1052,10 @@ class VarNet:
             if self.tfAdapt is not None:
                 raise NotImplementedError('%s with tfAdapt=%r: the weights are applied after the seeds the %s gradient is '
                                           'reduced from' % (lv.option, tfAdapt, lv.noun))
+            if self.bicWeights is not None or self.bicAdapt is not None:
+                raise NotImplementedError('%s with bicWeights= / bicAdapt=: the %s sums next to the rows\' own pass are not built%s'
+                                          % (lv.option, lv.noun, ', and learnt boundary data would move the labels the weights follow'
+                                             if lv.option == 'learnBic' else ''))
         # learntPrior={stem: spec} (extension; no reference counterpart): a quadratic prior and L1 shrinkage on the learnt vectors
         # (`priorData`)
         self.learntPrior = self.priorData(PDE, learntPrior, {lv.stem: getattr(self, lv.attr) for lv in self.LEARNT})
@@ -1077,6 +1100,8 @@ class VarNet:
             pass
         if self.tfAdapt is not None and self.world > 1:
             self._check_tf_adapt(tfAdapt, False, False, False, True)
+        if (self.bicWeights is not None or self.bicAdapt is not None) and self.world > 1:
+            self._check_bic_weights(bicWeights, bicAdapt, False, False, True, False, timeDependent)
         if self.causal is not None and (self.world > 1 or (isinstance(processors, (list, tuple)) and len(processors) > 1)):
             raise NotImplementedError('causal=%r with towers: a rank\'s slab means would cover only its shard of the test '
                                       'functions, so the ranks together would train another objective than one rank'
@@ -1888,6 +1913,170 @@ class VarNet:
         for bi in range(tData.batchNum):
             s = self.engine.tf_adapt(tData.engine_batch(0, bi))
             out.append({'omega': s['omega'], 'lambda': s['lambda'], 'stats': s['stats']})
+        return out
+
+    # -- weights on the boundary and initial rows (extension) ----------------------------------------
+    BIC_PARTS = ('bc', 'ic')
+
+    @classmethod
+    def _check_bic_weights(cls, weights, adapt, lbfgs, mor, towers, ansatz, timeDependent):
+        """(bicWeights, bicAdapt) as dicts by part (None: off), after the refusals every way in shares.  bicWeights: an array
+        [nB] (stored under 'rows') or {'bc': array | callable(x[, t]), 'ic': ..., 'normalize': bool}; bicAdapt: 'rba' | 'sa' (the
+        'ic' part of a time-dependent problem, else 'bc') or {'bc': spec, 'ic': spec}."""
+        from .engine import tf_adapt_spec
+        if weights is None and adapt is None:
+            return None, None
+        w = None
+        if weights is not None:
+            if isinstance(weights, dict):
+                bad = [k for k in weights if k not in cls.BIC_PARTS + ('normalize',)]
+                if bad or not any(k in weights for k in cls.BIC_PARTS):
+                    raise ValueError("bicWeights: a dict takes the keys 'bc', 'ic' and 'normalize' (got %r)" % (sorted(weights),))
+                w = dict(weights)
+            else:
+                w = {'rows': np.asarray(weights, dtype=np.float64).reshape(-1)}
+            w['normalize'] = bool(w.get('normalize', False))
+            for k in cls.BIC_PARTS + ('rows',):
+                if k in w and not callable(w[k]):
+                    w[k] = np.asarray(w[k], dtype=np.float64).reshape(-1)
+                    if not (np.all(np.isfinite(w[k])) and np.all(w[k] >= 0.0)):
+                        raise ValueError('bicWeights: every weight must be finite and >= 0 (%r)' % (k,))
+        a = None
+        if adapt is not None:
+            if isinstance(adapt, dict) and 'rule' not in adapt:
+                bad = [k for k in adapt if k not in cls.BIC_PARTS]
+                if bad or not adapt:
+                    raise ValueError("bicAdapt: a dict by part takes the keys 'bc' and 'ic' (got %r)" % (sorted(adapt),))
+                a = {k: tf_adapt_spec(v) for k, v in adapt.items() if v is not None}
+            else:
+                a = {'ic' if timeDependent else 'bc': tf_adapt_spec(adapt)}
+            if 'ic' in a and not timeDependent:
+                raise ValueError("bicAdapt: a steady problem has no initial rows, so no 'ic' part")
+            if not a:
+                a = None
+        if w is not None and not timeDependent and 'ic' in w:
+            raise ValueError("bicWeights: a steady problem has no initial rows, so no 'ic' part")
+        if w is not None and a is not None:
+            both = [k for k in a if k in w or 'rows' in w]
+            if both and 'rows' not in w:
+                raise ValueError('bicWeights and bicAdapt both name the %r part: a static and an adaptive registration of a part '
+                                 'replace each other' % (both[0],))
+        if a is not None and lbfgs:
+            raise ValueError('bicAdapt=%r with optimizer=\'lbfgs\': the weights move from step to step but are held constant for the '
+                             'gradient, so an Armijo test across steps means nothing; static bicWeights= work' % (adapt,))
+        if mor:
+            raise NotImplementedError('bicWeights= / bicAdapt= with model-order reduction is not supported: every MOR batch has rows '
+                                      'and labels of its own, and the engine keeps one state per row of one set')
+        if towers:
+            raise NotImplementedError('bicWeights= / bicAdapt= with towers: a rank\'s max, mean and Z would follow its own shard\'s '
+                                      'steps, so the ranks together would train another objective than one rank')
+        if ansatz:
+            raise NotImplementedError('bicWeights= / bicAdapt= with a hard-constraint ansatz: the rows\' error is zero by '
+                                      'construction, there is nothing to weight')
+        return w, a
+
+    def _bic_weights_save(self):
+        """Before a vn_set_bic: the adaptive state of the set that holds the rows' weights is kept on the host."""
+        owner = getattr(self, '_bicw_owner', None)
+        if owner is None or (self.bicAdapt is None and self.bicWeights is None):
+            return
+        parts = self.engine.bic_parts()
+        owner._bicw_saved = {p: self.engine.bic_adapt(p) for p, v in parts.items() if isinstance(v, dict)}
+        self._bicw_owner = None
+
+    def _bic_static_rows(self, X, nbc):
+        """bicWeights= evaluated on the rows X [nB, dim (+1)] of a training set: one weight per row."""
+        w = self.bicWeights
+        if 'rows' in w:
+            if w['rows'].size != X.shape[0]:
+                raise ValueError('bicWeights: expected one weight per boundary / initial row (%d), got %d' % (X.shape[0], w['rows'].size))
+            return w['rows']
+        out = np.ones(X.shape[0])
+        for part, sl in (('bc', slice(0, nbc)), ('ic', slice(nbc, None))):
+            v = w.get(part)
+            if v is None:
+                continue
+            if callable(v):
+                Xp = X[sl]
+                args = (Xp[:, :self.dim], Xp[:, self.dim:self.dim + 1]) if self.PDE.timeDependent else (Xp[:, :self.dim],)
+                try:
+                    v = v(*args)
+                except TypeError:
+                    v = v(args[0])
+                v = np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(-1), (Xp.shape[0],)) if np.size(v) == 1 \
+                    else np.asarray(v, dtype=np.float64).reshape(-1)
+            if v.size != out[sl].size:
+                raise ValueError('bicWeights[%r]: expected %d weights, got %d' % (part, out[sl].size, v.size))
+            if not (np.all(np.isfinite(v)) and np.all(v >= 0.0)):
+                raise ValueError('bicWeights[%r]: every weight must be finite and >= 0' % (part,))
+            out[sl] = v
+        return out
+
+    def _bic_weights_register(self, tData, d):
+        """After a vn_set_bic of tData's rows: the static weights, then the adaptive parts (which replace a static registration of
+        their part), then the state this set kept while another one used the engine."""
+        if self.bicWeights is None and self.bicAdapt is None:
+            return
+        eng = self.engine
+        if self.bicWeights is not None:
+            X = d['biInput']
+            X = np.asarray(X.cpu() if hasattr(X, 'cpu') else X, dtype=np.float64)
+            nbc = int(tData.bDofsum)
+            om = self._bic_static_rows(X, nbc)
+            if not self.PDE.timeDependent:
+                om = om[:nbc]
+            eng.set_bic_weights(om.astype(np.float32), normalize=self.bicWeights['normalize'])
+        kept = getattr(tData, '_bicw_saved', None) or {}
+        for part, spec in (self.bicAdapt or {}).items():
+            if eng.bic_rows(part) <= 0:
+                continue
+            eng.set_bic_adapt(part, spec)
+            st = kept.get(part)
+            if st is not None and st['lambda'].size == eng.bic_rows(part):
+                eng.set_bic_adapt_state(part, st['lambda'], st['slots'], int(st['stats']['tau']))
+        self._bicw_owner = tData
+
+    def setBicAdapt(self, bicAdapt=None, bicWeights=None):
+        """Other rules, parameters or static weights for the boundary and initial rows (both None switches them off),
+        re-registered on the training set of the last train() call from the initial state: the options can change between
+        train() calls."""
+        w, a = self._check_bic_weights(bicWeights, bicAdapt, self._is_lbfgs(), not uf.isnone(self.PDE.MORvar),
+                                       self.world > 1 or self._towers is not None, getattr(self.PDE, 'ansatz', None) is not None,
+                                       self.PDE.timeDependent)
+        if w is not None or a is not None:
+            for lv in self.LEARNT:
+                if getattr(self, lv.attr, None) is not None:
+                    raise NotImplementedError('%s with bicWeights= / bicAdapt=: the %s sums next to the rows\' own pass are not built'
+                                              % (lv.option, lv.noun))
+        self.bicWeights, self.bicAdapt = w, a
+        self._bicw_owner = None                           # no state is carried over to the new registration
+        tData = getattr(self, 'tData', None)
+        if tData is not None:
+            tData._bicw_saved = None
+            self.engine._bic_key = None                   # the rows are registered again, and the weights with them
+            tData.select_mor(0)
+
+    def bicRowWeights(self, tData=None):
+        """Per registered part ('bc', 'ic') of the training set of the last train() call (default; else `tData`, else a freshly
+        built full-batch set): {'x': the rows' coordinates [n_s, dim (+1)], 'omega', 'lambda', 'l': the unweighted e_i^2 of the
+        last evaluation, 'stats'}.  A read-back of the set that holds the engine's rows (after train(): the training set).  Asked for
+        another set, it first registers that set's rows with the engine (a vn_set_bic: the holder keeps its adaptive state on the
+        host and takes it back at its next registration), as every monitor on another set does."""
+        if self.bicWeights is None and self.bicAdapt is None:
+            raise ValueError('bicRowWeights: the rows carry no weights (VarNet(bicWeights=..., bicAdapt=...) or setBicAdapt(...))')
+        if tData is None:
+            tData = getattr(self, 'tData', None) or self._build_tdata()
+        if getattr(self, '_bicw_owner', None) is not tData:
+            self.engine._bic_key = None
+            tData.select_mor(0)
+        X = tData.mor[0]['biInput']
+        X = np.asarray(X.cpu() if hasattr(X, 'cpu') else X)
+        nbc = int(tData.bDofsum)
+        out = {}
+        for part in self.engine.bic_parts():
+            s = self.engine.bic_adapt(part)
+            rows = X[:nbc] if part == 'bc' else X[nbc:]
+            out[part] = {'x': rows, 'omega': s['omega'], 'lambda': s['lambda'], 'l': s['lossfield'], 'stats': s['stats']}
         return out
 
     # -- causal time-slab weights (extension) ------------------------------------------------------
@@ -2898,6 +3087,9 @@ class VarNet:
         if shuffleData and self.tfAdapt is not None:
             raise NotImplementedError('tfAdapt=... with shuffleData=True is not supported: a shuffle changes which test function is k, '
                                       'and the state lambda_k belongs to the test function')
+        if shuffleData and (self.bicWeights is not None or self.bicAdapt is not None):
+            raise NotImplementedError('bicWeights= / bicAdapt= with shuffleData=True is not supported: a shuffle permutes the BC/IC rows '
+                                      'per feed (a per-batch copy), and the weights belong to the rows as they were registered')
         if shuffleData and getattr(self.PDE, 'ansatz', None) is not None:
             raise NotImplementedError('an ansatz with shuffleData=True is not supported: a shuffle permutes the BC/IC rows per feed '
                                       '(a per-batch copy), and the ansatz streams belong to the rows as they were registered')
@@ -2909,6 +3101,9 @@ class VarNet:
         eng, fd = self.engine, self.fixData
         torch = eng.torch
         self._adapt_owner = None                             # the adaptive state of an earlier train() call is not carried over ...
+        self._bicw_owner = None                              # ... nor that of the boundary and initial rows
+        if getattr(self, 'tData', None) is not None:
+            self.tData._bicw_saved = None
         if getattr(self, 'tData', None) is not None:
             self.tData._adapt_saved = None
         tData = self._build_tdata(batchNum, batchLen)        # first set is always uniform (VarNet.py:1300)
@@ -3091,6 +3286,8 @@ class VarNet:
                     if self.tfAdapt is not None:
                         trainRes.tfAdaptHist.append((epoch, [eng.tf_adapt(tData.engine_batch(0, bi), arrays=False)['stats']
                                                              for bi in range(tData.batchNum)]))
+                    if self.bicWeights is not None or self.bicAdapt is not None:
+                        trainRes.bicAdaptHist.append((epoch, {p: eng.bic_adapt(p, arrays=False)['stats'] for p in eng.bic_parts()}))
                 trainRes.iterOutput(epoch, current_loss, min_loss, epoch_time, resVal, err, lossComp, lossVec)
 
                 if current_loss < tol:
@@ -3230,6 +3427,16 @@ class VarNet:
                 out['tfadapt_%d_tau' % b] = np.int64(st['stats']['tau'])
                 if st['slots'] is not None:
                     out['tfadapt_%d_slots' % b] = st['slots']
+        if getattr(self, 'bicAdapt', None) is not None:
+            for part, spec in self.engine.bic_parts().items():
+                if not isinstance(spec, dict):
+                    continue
+                st = self.engine.bic_adapt(part)
+                out['bicadapt_%s_rule' % part] = np.array(spec['rule'])
+                out['bicadapt_%s_lambda' % part] = st['lambda']
+                out['bicadapt_%s_tau' % part] = np.int64(st['stats']['tau'])
+                if st['slots'] is not None:
+                    out['bicadapt_%s_slots' % part] = st['slots']
         return out
 
     def restore_arrays(self, arrays):
@@ -3263,7 +3470,8 @@ class VarNet:
         blob = np.concatenate([step.view(np.uint8), np.concatenate(th + m + v).astype(np.float32).view(np.uint8)])
         rule = None if getattr(self, 'tfAdapt', None) is None else self.tfAdapt['rule']
         saved_rule = str(arrays['tfadapt_rule']) if 'tfadapt_rule' in arrays else None
-        if rule is not None:
+        bic_parts = self.engine.bic_parts() if hasattr(self.engine, 'bic_parts') else {}
+        if rule is not None or bic_parts:
             # the adaptive states follow the optimizer state in the engine's layout: as they stand for the import, then (when the
             # checkpoint carries the rule's state for the registered batches) from the checkpoint
             blob = np.concatenate([blob, np.asarray(self.engine.export_state(), dtype=np.uint8)[blob.size:]])
@@ -3273,6 +3481,11 @@ class VarNet:
                 if b in self.engine.adapt_batches() and np.size(arrays['tfadapt_%d_lambda' % b]) == self.engine._n_k(b):
                     self.engine.set_tf_adapt_state(b, arrays['tfadapt_%d_lambda' % b], arrays.get('tfadapt_%d_slots' % b),
                                                    int(arrays['tfadapt_%d_tau' % b]))
+        for part, spec in bic_parts.items():
+            key = 'bicadapt_%s_' % part
+            if isinstance(spec, dict) and key + 'rule' in arrays and str(arrays[key + 'rule']) == spec['rule'] \
+                    and np.size(arrays[key + 'lambda']) == self.engine.bic_rows(part):
+                self.engine.set_bic_adapt_state(part, arrays[key + 'lambda'], arrays.get(key + 'slots'), int(arrays[key + 'tau']))
         if mode is not None:
             self.engine.set_reparam_state(arrays['reparam_V'], arrays['reparam_s'], arrays['reparam_slots'])
         for lv in self.LEARNT:
