@@ -600,6 +600,74 @@ def test_snapshot_rollback_replay_and_export_import(i, rule):
             e.close()
 
 
+def both_kinds_engine(i, lam_tf=None):
+    """A batch state and both part states on one engine: batch 0 'sa', bc 'rba' on every second step, ic 'sa', each from
+    non-uniform initial lambdas (lam_tf None: each from its spec's init) -- states without and with slots interleaved, one of
+    them not pending on every second step."""
+    eng = make_engine(i)
+    eng.set_tf_adapt(0, adapt_ref.spec_of('sa'), lam_tf)
+    eng.set_bic_adapt('bc', adapt_ref.spec_of('rba', every=2), None if lam_tf is None else lambda0(i, 0))
+    eng.set_bic_adapt('ic', adapt_ref.spec_of('sa'), None if lam_tf is None else lambda0(i, 1))
+    return eng
+
+
+def both_kinds_state(eng):
+    s = eng.tf_adapt(0)
+    return [s['lambda'], s['omega'], s['slots'], np.array([s['stats'][k] for k in STATS])] + state_of(eng)
+
+
+STATS = ('min', 'max', 'mean', 'share', 'Z', 'tau')
+
+
+def test_batch_and_part_states_on_one_engine_share_one_layout():
+    """vn_set_tf_adapt next to vn_set_bic_adapt: the exported state holds the batch's, then bc's, then ic's; snapshot, rollback,
+    import and vn_params_init reach all three.  n33_21: n_k = 9 and the parts' 21 and 12 rows are no multiples of 4, so every
+    piece's 16-byte stride on the device differs from its length in the exported bytes."""
+    i = IDX['n33_21']
+    n_k, n = CASES[i][5], rows(i)
+    lam_tf = np.random.default_rng(29).uniform(0.5, 2.0, n_k).astype(np.float32)
+    eng, twin, plain = both_kinds_engine(i, lam_tf), both_kinds_engine(i), make_engine(i)
+    try:
+        assert (n_k, n) == (9, (21, 12))
+        plain_bytes = plain.export_state().size
+        assert eng.export_state().size == plain_bytes + (64 + 4 * 4 * 9) + (64 + 2 * 4 * 21) + (64 + 4 * 4 * 12)
+        run_steps(eng, 3)                                                 # an odd count: bc has skipped a step, the others none
+        assert eng.bic_adapt('bc', arrays=False)['stats']['tau'] < 3.0 == eng.bic_adapt('ic', arrays=False)['stats']['tau']
+        assert eng.tf_adapt(0, arrays=False)['stats']['tau'] == 3.0
+        # the bytes behind the optimizer block: per state the scalars, then lambda, omega[, m1, m2], unpadded
+        buf = eng.export_state()
+        at = plain_bytes
+        for s, m in ((eng.tf_adapt(0), n_k), (eng.bic_adapt('bc'), n[0]), (eng.bic_adapt('ic'), n[1])):
+            scal = np.frombuffer(buf[at:at + 64].tobytes(), np.float64)
+            assert np.array_equal(scal[:6], np.array([s['stats'][k] for k in STATS]))
+            at += 64
+            pieces = [s['lambda'], s['omega']] + ([] if s['slots'] is None else [s['slots'][0], s['slots'][1]])
+            for piece in pieces:
+                assert piece.shape == (m,) and np.array_equal(np.frombuffer(buf[at:at + 4 * m].tobytes(), np.float32), piece)
+                at += 4 * m
+        assert at == buf.size and eng.bic_adapt('bc')['slots'] is None and eng.tf_adapt(0)['slots'] is not None
+        # snapshot / rollback
+        eng.state_snapshot()
+        s3, p3 = both_kinds_state(eng), eng.get_params()
+        r5 = run_steps(eng, 5) + both_kinds_state(eng)
+        assert not same(both_kinds_state(eng), s3)
+        eng.state_rollback()
+        assert same(both_kinds_state(eng), s3) and eng.step == 3 and np.array_equal(eng.get_params(), p3)
+        assert same(run_steps(eng, 5) + both_kinds_state(eng), r5)       # replay: the same bits
+        # import into an engine registered the same way from the specs' init
+        twin.import_state(eng.export_state())
+        assert same(both_kinds_state(twin), both_kinds_state(eng)) and twin.step == eng.step == 8
+        assert same(run_steps(twin, 3) + both_kinds_state(twin), run_steps(eng, 3) + both_kinds_state(eng))
+        # vn_params_init returns all three to their registered initial lambdas
+        eng.init_params(seed=1)
+        for s, lam in ((eng.tf_adapt(0), lam_tf), (eng.bic_adapt('bc'), lambda0(i, 0)), (eng.bic_adapt('ic'), lambda0(i, 1))):
+            assert np.array_equal(s['lambda'], lam) and s['stats']['tau'] == 0.0
+            assert s['slots'] is None or not s['slots'].any()
+    finally:
+        for e in (eng, twin, plain):
+            e.close()
+
+
 def _snapshot(eng):
     out, lv = eng.eval_loss(0, lossVec=True)
     g = grad_of(eng).copy()

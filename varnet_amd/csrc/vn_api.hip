@@ -859,31 +859,66 @@ int adapt_reset(vn_engine* h, Adapt& ad) {
   return adapt_rebuild(h, ad);
 }
 
+// Every state registered on the engine, in the order vn_state_export lays them out: each batch's (vn_set_tf_adapt) in batch
+// order, then the bc part's, then the ic part's (vn_set_bic_weights, vn_set_bic_adapt).  A further holder is appended here.
+// f(Adapt&) returns an error code; the first that is not VN_OK ends the walk and is returned.
+template <class F>
+int adapt_each(const vn_engine* h, F f) {
+  for (const Batch& b : h->batches)
+    if (b.ad)
+      if (int rc = f(*b.ad)) return rc;
+  for (Adapt* ad : h->bw)
+    if (ad)
+      if (int rc = f(*ad)) return rc;
+  return VN_OK;
+}
+
+// Batch::wt.omega of every adaptive batch is its state's committed omega: called wherever a state is installed or `cur` may move
+void adapt_point_omega(vn_engine* h) {
+  for (Batch& b : h->batches)
+    if (b.ad) b.wt.omega = adapt_state(*b.ad, b.ad->cur).omega;
+}
+
 // The optimizer step's share: every pending state becomes the committed one -- the halves swap, nothing is copied
 void adapt_commit(vn_engine* h) {
-  for (Batch& b : h->batches)
-    if (b.ad && b.ad->pending) {
-      b.ad->cur ^= 1;
-      b.ad->pending = false;
-      b.wt.omega = adapt_state(*b.ad, b.ad->cur).omega;
-    }
-  for (Adapt* ad : h->bw)       // ... and those of the BC/IC rows' parts (vn_set_bic_adapt)
-    if (ad && ad->pending) { ad->cur ^= 1; ad->pending = false; }
+  adapt_each(h, [](Adapt& ad) -> int {
+    if (ad.pending) { ad.cur ^= 1; ad.pending = false; }
+    return VN_OK;
+  });
+  adapt_point_omega(h);
 }
 void adapt_drop_pending(vn_engine* h) {
-  for (Batch& b : h->batches)
-    if (b.ad) b.ad->pending = false;
-  for (Adapt* ad : h->bw)
-    if (ad) ad->pending = false;
+  adapt_each(h, [](Adapt& ad) -> int { ad.pending = false; return VN_OK; });
 }
-inline bool adapt_any(const vn_engine* h) {
-  for (const Batch& b : h->batches)
-    if (b.ad) return true;
-  return false;
+
+// The committed half into the snapshot (back = false) or the snapshot into the committed half; then nothing is pending
+int adapt_snap_copy(vn_engine* h, Adapt& ad, bool back) {
+  const VnAdaptState s = adapt_state(ad, ad.cur), t = adapt_snap(ad);
+  const VnAdaptState &dst = back ? s : t, &src = back ? t : s;
+  HIPCHK(hipMemcpyAsync(dst.lambda, src.lambda, 4 * (size_t)ad.stride * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dst.scal, src.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  if (back) ad.pending = false;
+  return VN_OK;
 }
-// bytes of a batch's state in vn_state_export: scalars, lambda, omega[, m1, m2]
+
+// A state in vn_state_export's bytes: the scalars, then lambda, omega[, m1, m2] of n_k floats each.  adapt_bytes: its size;
+// adapt_host_copy: the committed half to the cursor p (vn_state_export) or from it (load: vn_state_import; then nothing is
+// pending), and p moves past the state
 inline int64_t adapt_bytes(const Adapt& ad) {
   return (int64_t)(VN_ADAPT_SCAL * sizeof(double)) + (int64_t)(ad.rule == VN_ADAPT_SA ? 4 : 2) * ad.n_k * (int64_t)sizeof(float);
+}
+int adapt_host_copy(vn_engine* h, Adapt& ad, char*& p, bool load) {
+  const VnAdaptState s = adapt_state(ad, ad.cur);
+  auto copy = [&](void* dev, size_t nb) {
+    char* host = p;
+    p += nb;
+    return load ? hipMemcpyAsync(dev, host, nb, hipMemcpyHostToDevice, h->stream) : hipMemcpyAsync(host, dev, nb, hipMemcpyDeviceToHost, h->stream);
+  };
+  HIPCHK(copy(s.scal, VN_ADAPT_SCAL * sizeof(double)));
+  for (float* piece : {s.lambda, s.omega, s.m1, s.m2})
+    if (piece) HIPCHK(copy(piece, (size_t)ad.n_k * sizeof(float)));
+  if (load) ad.pending = false;
+  return VN_OK;
 }
 
 // After the seed kernel and every term's seed kernel: [causal: the weights from lossVec], stf scaled (de-duplicated step),
@@ -1950,14 +1985,9 @@ int vn_params_init(vn_engine* h, uint64_t seed) {
     HIPCHK(hipMemsetAsync(h->rp.sc + S, 0, 2 * S * sizeof(float), h->stream));
     if (int rc = reparam_factorise(h)) return rc;
   }
-  for (Batch& b : h->batches)   // self-adaptive weights start over from their registered initial state
-    if (b.ad) {
-      if (int rc = adapt_reset(h, *b.ad)) return rc;
-      b.wt.omega = adapt_state(*b.ad, b.ad->cur).omega;
-    }
-  for (Adapt* ad : h->bw)       // ... and so do the BC/IC rows' parts (a static part: its registered weights, rebuilt)
-    if (ad)
-      if (int rc = adapt_reset(h, *ad)) return rc;
+  // self-adaptive weights start over from their registered initial state (a static part of the BC/IC rows: its weights, rebuilt)
+  if (int rc = adapt_each(h, [&](Adapt& ad) -> int { return adapt_reset(h, ad); })) return rc;
+  adapt_point_omega(h);
   HIPCHK(hipStreamSynchronize(h->stream));
   h->step = 0;
   lbfgs_invalidate(h);
@@ -1988,10 +2018,8 @@ int vn_params_set(vn_engine* h, const float* host, int64_t n) {
 int vn_state_size(const vn_engine* h, int64_t* bytes) {
   if (!h || !bytes) return fail(VN_EINVAL, "null argument");
   *bytes = (int64_t)sizeof(int64_t) + 3ll * h->net.P * (int64_t)sizeof(float);
-  for (const Batch& b : h->batches)   // the adaptive state of every registered batch, in batch order (none registered: nothing)
-    if (b.ad) *bytes += adapt_bytes(*b.ad);
-  for (const Adapt* ad : h->bw)       // ... then that of every registered part of the BC/IC rows, bc first
-    if (ad) *bytes += adapt_bytes(*ad);
+  // the adaptive state of every registered batch, in batch order, then that of every registered part of the BC/IC rows, bc first
+  adapt_each(h, [&](Adapt& ad) -> int { *bytes += adapt_bytes(ad); return VN_OK; });
   return VN_OK;
 }
 
@@ -2009,24 +2037,7 @@ int vn_state_export(vn_engine* h, void* host, int64_t bytes) {
   HIPCHK(hipMemcpyAsync(p + nb, h->m, nb, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(p + 2 * nb, h->v, nb, hipMemcpyDeviceToHost, h->stream));
   p += 3 * nb;
-  for (const Batch& b : h->batches)
-    if (b.ad) {
-      const VnAdaptState s = adapt_state(*b.ad, b.ad->cur);
-      const size_t nk = (size_t)b.ad->n_k * sizeof(float);
-      HIPCHK(hipMemcpyAsync(p, s.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      p += VN_ADAPT_SCAL * sizeof(double);
-      for (const float* piece : {(const float*)s.lambda, (const float*)s.omega, (const float*)s.m1, (const float*)s.m2})
-        if (piece) { HIPCHK(hipMemcpyAsync(p, piece, nk, hipMemcpyDeviceToHost, h->stream)); p += nk; }
-    }
-  for (const Adapt* ad : h->bw)
-    if (ad) {
-      const VnAdaptState s = adapt_state(*ad, ad->cur);
-      const size_t nk = (size_t)ad->n_k * sizeof(float);
-      HIPCHK(hipMemcpyAsync(p, s.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      p += VN_ADAPT_SCAL * sizeof(double);
-      for (const float* piece : {(const float*)s.lambda, (const float*)s.omega, (const float*)s.m1, (const float*)s.m2})
-        if (piece) { HIPCHK(hipMemcpyAsync(p, piece, nk, hipMemcpyDeviceToHost, h->stream)); p += nk; }
-    }
+  if (int rc = adapt_each(h, [&](Adapt& ad) -> int { return adapt_host_copy(h, ad, p, false); })) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
   return VN_OK;
 }
@@ -2051,18 +2062,8 @@ int vn_state_snapshot(vn_engine* h) {
     HIPCHK(hipMemcpyAsync(h->rp.snap, h->rp.V, nb, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->rp.snap + h->net.P, h->rp.sc, 4 * S * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   }
-  for (const Batch& b : h->batches)   // self-adaptive weights: the committed half (a pending one belongs to no step yet)
-    if (b.ad) {
-      const VnAdaptState s = adapt_state(*b.ad, b.ad->cur), t = adapt_snap(*b.ad);
-      HIPCHK(hipMemcpyAsync(t.lambda, s.lambda, 4 * (size_t)b.ad->stride * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(t.scal, s.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    }
-  for (const Adapt* ad : h->bw)
-    if (ad) {
-      const VnAdaptState s = adapt_state(*ad, ad->cur), t = adapt_snap(*ad);
-      HIPCHK(hipMemcpyAsync(t.lambda, s.lambda, 4 * (size_t)ad->stride * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(t.scal, s.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    }
+  // self-adaptive weights: the committed half (a pending one belongs to no step yet)
+  if (int rc = adapt_each(h, [&](Adapt& ad) -> int { return adapt_snap_copy(h, ad, false); })) return rc;
   h->snap_step = h->step;
   return VN_OK;
 }
@@ -2082,20 +2083,8 @@ int vn_state_rollback(vn_engine* h) {
     HIPCHK(hipMemcpyAsync(h->rp.V, h->rp.snap, nb, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->rp.sc, h->rp.snap + h->net.P, 4 * S * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   }
-  for (Batch& b : h->batches)
-    if (b.ad) {
-      const VnAdaptState s = adapt_state(*b.ad, b.ad->cur), t = adapt_snap(*b.ad);
-      HIPCHK(hipMemcpyAsync(s.lambda, t.lambda, 4 * (size_t)b.ad->stride * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(s.scal, t.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-      b.ad->pending = false;
-    }
-  for (Adapt* ad : h->bw)
-    if (ad) {
-      const VnAdaptState s = adapt_state(*ad, ad->cur), t = adapt_snap(*ad);
-      HIPCHK(hipMemcpyAsync(s.lambda, t.lambda, 4 * (size_t)ad->stride * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(s.scal, t.scal, VN_ADAPT_SCAL * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-      ad->pending = false;
-    }
+  if (int rc = adapt_each(h, [&](Adapt& ad) -> int { return adapt_snap_copy(h, ad, true); })) return rc;
+  adapt_point_omega(h);
   h->step = h->snap_step;
   return VN_OK;
 }
@@ -2117,27 +2106,9 @@ int vn_state_import(vn_engine* h, const void* host, int64_t bytes) {
   }
   if (reparam_on(h))            // V from the imported theta_eff with the current s; a full restore calls vn_set_reparam_state next
     if (int rc = reparam_factorise(h)) return rc;
-  p += 3 * nb;
-  for (Batch& b : h->batches)
-    if (b.ad) {
-      const VnAdaptState s = adapt_state(*b.ad, b.ad->cur);
-      const size_t nk = (size_t)b.ad->n_k * sizeof(float);
-      HIPCHK(hipMemcpyAsync(s.scal, p, VN_ADAPT_SCAL * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      p += VN_ADAPT_SCAL * sizeof(double);
-      for (float* piece : {s.lambda, s.omega, s.m1, s.m2})
-        if (piece) { HIPCHK(hipMemcpyAsync(piece, p, nk, hipMemcpyHostToDevice, h->stream)); p += nk; }
-      b.ad->pending = false;
-    }
-  for (Adapt* ad : h->bw)
-    if (ad) {
-      const VnAdaptState s = adapt_state(*ad, ad->cur);
-      const size_t nk = (size_t)ad->n_k * sizeof(float);
-      HIPCHK(hipMemcpyAsync(s.scal, p, VN_ADAPT_SCAL * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      p += VN_ADAPT_SCAL * sizeof(double);
-      for (float* piece : {s.lambda, s.omega, s.m1, s.m2})
-        if (piece) { HIPCHK(hipMemcpyAsync(piece, p, nk, hipMemcpyHostToDevice, h->stream)); p += nk; }
-      ad->pending = false;
-    }
+  char* q = const_cast<char*>(p) + 3 * nb;   // (read only: load)
+  if (int rc = adapt_each(h, [&](Adapt& ad) -> int { return adapt_host_copy(h, ad, q, true); })) return rc;
+  adapt_point_omega(h);
   HIPCHK(hipStreamSynchronize(h->stream));
   lbfgs_invalidate(h);
   return VN_OK;
@@ -2716,6 +2687,89 @@ static int adapt_check_par(const char* who, int32_t rule, const double par[10]) 
   return VN_OK;
 }
 
+// One state of n weights, built and brought to its initial values: lambda from init_dev (validated on the device: finite, >= 0;
+// copied, so the caller's array need not outlive the call), else par[6].  power, normalize and every come from par as well.
+// who, rows and what word the messages ("<who>: the state of <n> <rows> does not fit", "<who>: <count> <what> negative or not
+// finite").  *out on success; on failure nothing is kept.
+static int adapt_make(vn_engine* h, const char* who, const char* rows, const char* what, long n, int rule, const double par[10],
+                      const float* init_dev, Adapt** out) {
+  Adapt* ad = new Adapt();
+  ad->rule = rule; ad->power = (int)par[5]; ad->normalize = (int)par[7]; ad->every = (long)par[8];
+  std::copy(par, par + 10, ad->par);
+  ad->n_k = n; ad->stride = vn_adapt_stride(n);
+  hipError_t e = hipMalloc((void**)&ad->f, (size_t)(kAdaptPieces * ad->stride) * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&ad->d, (size_t)kAdaptDoubles * sizeof(double));
+  if (e == hipSuccess) e = hipMemsetAsync(ad->f, 0, (size_t)(kAdaptPieces * ad->stride) * sizeof(float), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(ad->d, 0, (size_t)kAdaptDoubles * sizeof(double), h->stream);
+  int rc = VN_OK;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    rc = fail(VN_ENOMEM, "%s: the state of %ld %s does not fit: %s", who, n, rows, hipGetErrorString(e));
+  } else if (init_dev) {
+    int bad = 0;
+    auto check = [&](int* err_dev) { return vn_adapt_check_copy_launch(init_dev, n, adapt_lambda0(*ad), err_dev, h->stream); };
+    rc = count_on_device(h, check, &bad);
+    if (rc == VN_OK && bad) rc = fail(VN_EINVAL, "%s: %d %s negative or not finite", who, bad, what);
+  } else {
+    e = vn_adapt_fill_launch(adapt_lambda0(*ad), n, (float)par[6], h->stream);
+    if (e != hipSuccess) rc = fail(VN_EHIP, "%s: %s", who, hipGetErrorString(e));
+  }
+  if (rc == VN_OK) rc = adapt_reset(h, *ad);
+  if (rc == VN_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(VN_EHIP, "%s: the initial state could not be formed", who);
+  if (rc != VN_OK) { adapt_free(ad); return rc; }
+  *out = ad;
+  return VN_OK;
+}
+
+// The committed half read back, every array optional: lambda, omega [n_k], slots [2 n_k] (the caller has checked that the rule
+// has them), n_k floats of extra_dev (the rows' loss field), the six statistics
+static int adapt_get(vn_engine* h, const Adapt& ad, float* lambda_host, float* omega_host, float* slots_host, const float* extra_dev,
+                     float* extra_host, double stats[6]) {
+  const VnAdaptState s = adapt_state(ad, ad.cur);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t nk = (size_t)ad.n_k * sizeof(float);
+  if (lambda_host) HIPCHK(hipMemcpyAsync(lambda_host, s.lambda, nk, hipMemcpyDeviceToHost, h->stream));
+  if (omega_host) HIPCHK(hipMemcpyAsync(omega_host, s.omega, nk, hipMemcpyDeviceToHost, h->stream));
+  if (slots_host) {
+    HIPCHK(hipMemcpyAsync(slots_host, s.m1, nk, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(slots_host + ad.n_k, s.m2, nk, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (extra_host) HIPCHK(hipMemcpyAsync(extra_host, extra_dev, nk, hipMemcpyDeviceToHost, h->stream));
+  if (stats) HIPCHK(hipMemcpyAsync(stats, s.scal, 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return VN_OK;
+}
+
+// A state put back into the committed half: lambda (checked here: finite, >= 0), the sa slots (NULL: zeros) and tau; omega, Z
+// and the statistics are rebuilt from them.  subject ("batch 0", "the bc part") words the refusal of slots under the rba rule.
+static int adapt_put(vn_engine* h, Adapt& ad, const char* who, const char* subject, const float* lambda_host, const float* slots_host,
+                     int64_t tau) {
+  if (!lambda_host) return fail(VN_EINVAL, "%s: null lambda", who);
+  if (tau < 0) return fail(VN_EINVAL, "%s: tau = %lld must be >= 0", who, (long long)tau);
+  if (slots_host && ad.rule != VN_ADAPT_SA) return fail(VN_EINVAL, "%s: %s runs the rba rule, which has no slots", who, subject);
+  for (long k = 0; k < ad.n_k; ++k)
+    if (!(lambda_host[k] >= 0.f && std::isfinite(lambda_host[k])))
+      return fail(VN_EINVAL, "%s: lambda[%ld] = %g is negative or not finite", who, k, (double)lambda_host[k]);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const VnAdaptState s = adapt_state(ad, ad.cur);
+  const size_t nk = (size_t)ad.n_k * sizeof(float);
+  double scal[VN_ADAPT_SCAL] = {};
+  scal[5] = (double)tau;
+  HIPCHK(hipMemcpyAsync(s.lambda, lambda_host, nk, hipMemcpyHostToDevice, h->stream));
+  if (s.m1) {                   // NULL slots: zeros
+    if (slots_host) {
+      HIPCHK(hipMemcpyAsync(s.m1, slots_host, nk, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(s.m2, slots_host + ad.n_k, nk, hipMemcpyHostToDevice, h->stream));
+    } else {
+      HIPCHK(hipMemsetAsync(s.m1, 0, 2 * (size_t)ad.stride * sizeof(float), h->stream));
+    }
+  }
+  HIPCHK(hipMemcpyAsync(s.scal, scal, sizeof scal, hipMemcpyHostToDevice, h->stream));
+  if (int rc = adapt_rebuild(h, ad)) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));   // the host arrays may be released on return
+  return VN_OK;
+}
+
 int vn_set_tf_adapt(vn_engine* h, int32_t batch, int32_t rule, const double par[10], const float* lambda_init_dev) {
   const bool clear = rule == VN_ADAPT_NONE;
   if (!clear) {
@@ -2727,40 +2781,12 @@ int vn_set_tf_adapt(vn_engine* h, int32_t batch, int32_t rule, const double par[
   if (int rc = weights_common(h, batch, clear, "vn_set_tf_adapt")) return rc;
   if (clear) return VN_OK;
   Batch& b = h->batches[batch];
-  const long n_k = b.n_k;
-  Adapt* ad = new Adapt();
-  ad->rule = rule; ad->power = (int)par[5]; ad->normalize = (int)par[7]; ad->every = (long)par[8];
-  std::copy(par, par + 10, ad->par);
-  ad->n_k = n_k; ad->stride = vn_adapt_stride(n_k);
-  hipError_t e = hipMalloc((void**)&ad->f, (size_t)(kAdaptPieces * ad->stride) * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&ad->d, (size_t)kAdaptDoubles * sizeof(double));
-  if (e == hipSuccess) e = hipMemsetAsync(ad->f, 0, (size_t)(kAdaptPieces * ad->stride) * sizeof(float), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(ad->d, 0, (size_t)kAdaptDoubles * sizeof(double), h->stream);
-  int rc = VN_OK;
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    rc = fail(VN_ENOMEM, "vn_set_tf_adapt: the state of %ld test functions does not fit: %s", n_k, hipGetErrorString(e));
-  } else if (lambda_init_dev) {   // validated on the device (finite, >= 0) and copied: the caller's array need not outlive the call
-    int bad = 0;
-    auto check = [&](int* err_dev) { return vn_adapt_check_copy_launch(lambda_init_dev, n_k, adapt_lambda0(*ad), err_dev, h->stream); };
-    rc = count_on_device(h, check, &bad);
-    if (rc == VN_OK && bad) rc = fail(VN_EINVAL, "vn_set_tf_adapt: %d initial lambda(s) negative or not finite", bad);
-  } else {
-    e = vn_adapt_fill_launch(adapt_lambda0(*ad), n_k, (float)par[6], h->stream);
-    if (e != hipSuccess) rc = fail(VN_EHIP, "vn_set_tf_adapt: %s", hipGetErrorString(e));
-  }
-  if (rc == VN_OK) rc = adapt_reset(h, *ad);
-  if (rc == VN_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(VN_EHIP, "vn_set_tf_adapt: the initial state could not be formed");
-  if (rc != VN_OK) {            // the batch keeps what it had
-    if (ad->f) (void)hipFree(ad->f);
-    if (ad->d) (void)hipFree(ad->d);
-    delete ad;
-    return rc;
-  }
+  Adapt* ad = nullptr;          // on failure the batch keeps what it had
+  if (int rc = adapt_make(h, "vn_set_tf_adapt", "test functions", "initial lambda(s)", b.n_k, rule, par, lambda_init_dev, &ad)) return rc;
   lbfgs_invalidate(h, batch);
   clear_weights(b);                                  // replaces a static, a causal or an earlier adaptive registration
   b.ad = ad;
-  b.wt.omega = adapt_state(*ad, ad->cur).omega;
+  adapt_point_omega(h);
   return VN_OK;
 }
 
@@ -2776,53 +2802,27 @@ static int adapt_of(vn_engine* h, int32_t batch, const char* who, Adapt** ad) {
 int vn_get_tf_adapt(vn_engine* h, int32_t batch, float* lambda_host, float* omega_host, float* slots_host, double stats[6]) {
   Adapt* ad = nullptr;
   if (int rc = adapt_of(h, batch, "vn_get_tf_adapt", &ad)) return rc;
-  const VnAdaptState s = adapt_state(*ad, ad->cur);
-  if (slots_host && !s.m1) return fail(VN_EINVAL, "vn_get_tf_adapt: batch %d runs the rba rule, which has no slots", batch);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const size_t nk = (size_t)ad->n_k * sizeof(float);
-  if (lambda_host) HIPCHK(hipMemcpyAsync(lambda_host, s.lambda, nk, hipMemcpyDeviceToHost, h->stream));
-  if (omega_host) HIPCHK(hipMemcpyAsync(omega_host, s.omega, nk, hipMemcpyDeviceToHost, h->stream));
-  if (slots_host) {
-    HIPCHK(hipMemcpyAsync(slots_host, s.m1, nk, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(slots_host + ad->n_k, s.m2, nk, hipMemcpyDeviceToHost, h->stream));
-  }
-  if (stats) HIPCHK(hipMemcpyAsync(stats, s.scal, 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return VN_OK;
+  if (slots_host && ad->rule != VN_ADAPT_SA) return fail(VN_EINVAL, "vn_get_tf_adapt: batch %d runs the rba rule, which has no slots", batch);
+  return adapt_get(h, *ad, lambda_host, omega_host, slots_host, nullptr, nullptr, stats);
 }
 
 int vn_set_tf_adapt_state(vn_engine* h, int32_t batch, const float* lambda_host, const float* slots_host, int64_t tau) {
   Adapt* ad = nullptr;
   if (int rc = adapt_of(h, batch, "vn_set_tf_adapt_state", &ad)) return rc;
-  if (!lambda_host) return fail(VN_EINVAL, "vn_set_tf_adapt_state: null lambda");
-  if (tau < 0) return fail(VN_EINVAL, "vn_set_tf_adapt_state: tau = %lld must be >= 0", (long long)tau);
-  if (slots_host && ad->rule != VN_ADAPT_SA) return fail(VN_EINVAL, "vn_set_tf_adapt_state: batch %d runs the rba rule, which has no slots", batch);
-  for (long k = 0; k < ad->n_k; ++k)
-    if (!(lambda_host[k] >= 0.f && std::isfinite(lambda_host[k])))
-      return fail(VN_EINVAL, "vn_set_tf_adapt_state: lambda[%ld] = %g is negative or not finite", k, (double)lambda_host[k]);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const VnAdaptState s = adapt_state(*ad, ad->cur);
-  const size_t nk = (size_t)ad->n_k * sizeof(float);
-  double scal[VN_ADAPT_SCAL] = {};
-  scal[5] = (double)tau;
-  HIPCHK(hipMemcpyAsync(s.lambda, lambda_host, nk, hipMemcpyHostToDevice, h->stream));
-  if (s.m1) {                   // NULL slots: zeros
-    if (slots_host) {
-      HIPCHK(hipMemcpyAsync(s.m1, slots_host, nk, hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(s.m2, slots_host + ad->n_k, nk, hipMemcpyHostToDevice, h->stream));
-    } else {
-      HIPCHK(hipMemsetAsync(s.m1, 0, 2 * (size_t)ad->stride * sizeof(float), h->stream));
-    }
-  }
-  HIPCHK(hipMemcpyAsync(s.scal, scal, sizeof scal, hipMemcpyHostToDevice, h->stream));
-  if (int rc = adapt_rebuild(h, *ad)) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));   // the host arrays may be released on return
+  char subject[32];
+  snprintf(subject, sizeof subject, "batch %d", batch);
+  if (int rc = adapt_put(h, *ad, "vn_set_tf_adapt_state", subject, lambda_host, slots_host, tau)) return rc;
   lbfgs_invalidate(h, batch);
   return VN_OK;
 }
 
 // ---- weights on the BC/IC rows (vn_bicadapt.hip): static (vn_set_bic_weights) or self-adaptive (vn_set_bic_adapt), per part ----
 static const char* const kBicPart[2] = {"bc", "ic"};
+// ... as the messages of adapt_make and adapt_put name a part, its rows and its values
+static const char* const kBicThePart[2] = {"the bc part", "the ic part"};
+static const char* const kBicRows[2] = {"bc rows", "ic rows"};
+static const char* const kBicWeights[2] = {"weight(s) of the bc part", "weight(s) of the ic part"};
+static const char* const kBicLambdas[2] = {"initial lambda(s) of the bc part", "initial lambda(s) of the ic part"};
 
 // What both registrations check before they build a state
 static int bicw_common(vn_engine* h, const char* who) {
@@ -2845,41 +2845,6 @@ static int bicw_common(vn_engine* h, const char* who) {
   return VN_OK;
 }
 
-// The state of one part, built and brought to its initial values: lambda from init_dev (validated on the device: finite, >= 0),
-// else `fill`.  *out on success; on failure nothing is kept.
-static int bicw_make(vn_engine* h, const char* who, int part, int rule, const double par[10], int power, int normalize, long every,
-                     const float* init_dev, float fill, Adapt** out) {
-  const long n = bicw_count(h, part);
-  Adapt* ad = new Adapt();
-  ad->rule = rule; ad->power = power; ad->normalize = normalize; ad->every = every;
-  if (par) std::copy(par, par + 10, ad->par);
-  ad->n_k = n; ad->stride = vn_adapt_stride(n);
-  hipError_t e = hipMalloc((void**)&ad->f, (size_t)(kAdaptPieces * ad->stride) * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&ad->d, (size_t)kAdaptDoubles * sizeof(double));
-  if (e == hipSuccess) e = hipMemsetAsync(ad->f, 0, (size_t)(kAdaptPieces * ad->stride) * sizeof(float), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(ad->d, 0, (size_t)kAdaptDoubles * sizeof(double), h->stream);
-  int rc = VN_OK;
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    rc = fail(VN_ENOMEM, "%s: the state of %ld %s rows does not fit: %s", who, n, kBicPart[part], hipGetErrorString(e));
-  } else if (init_dev) {
-    int bad = 0;
-    auto check = [&](int* err_dev) { return vn_adapt_check_copy_launch(init_dev, n, adapt_lambda0(*ad), err_dev, h->stream); };
-    rc = count_on_device(h, check, &bad);
-    if (rc == VN_OK && bad)
-      rc = fail(VN_EINVAL, "%s: %d %s of the %s part negative or not finite", who, bad, rule == VN_ADAPT_NONE ? "weight(s)" : "initial lambda(s)",
-                kBicPart[part]);
-  } else {
-    e = vn_adapt_fill_launch(adapt_lambda0(*ad), n, fill, h->stream);
-    if (e != hipSuccess) rc = fail(VN_EHIP, "%s: %s", who, hipGetErrorString(e));
-  }
-  if (rc == VN_OK) rc = adapt_reset(h, *ad);
-  if (rc == VN_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(VN_EHIP, "%s: the initial state could not be formed", who);
-  if (rc != VN_OK) { adapt_free(ad); return rc; }
-  *out = ad;
-  return VN_OK;
-}
-
 int vn_set_bic_weights(vn_engine* h, const float* omega_dev, int32_t normalize) {
   if (!h) return fail(VN_EINVAL, "null handle");
   if (!omega_dev) {                                  // clear: both parts, whatever they hold
@@ -2894,10 +2859,12 @@ int vn_set_bic_weights(vn_engine* h, const float* omega_dev, int32_t normalize) 
   (void)hipGetLastError();
   if (int rc = bicw_common(h, "vn_set_bic_weights")) return rc;
   Adapt* made[2] = {nullptr, nullptr};
+  // a state that never moves: lambda = the caller's omega, m(x) = x (power 1), Z = its mean over the part (normalize) or 1
+  const double par[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, (double)normalize, 1.0, 0.0};
   for (int s = 0; s < 2; ++s) {
     if (bicw_count(h, s) <= 0) continue;
-    // a state that never moves: lambda = the caller's omega, m(x) = x, Z = its mean over the part (normalize) or 1
-    if (int rc = bicw_make(h, "vn_set_bic_weights", s, VN_ADAPT_NONE, nullptr, 1, normalize, 1, omega_dev + (s ? h->bDof : 0), 0.f, &made[s])) {
+    if (int rc = adapt_make(h, "vn_set_bic_weights", kBicRows[s], kBicWeights[s], bicw_count(h, s), VN_ADAPT_NONE, par,
+                            omega_dev + (s ? h->bDof : 0), &made[s])) {
       adapt_free(made[0]);
       return rc;                                     // the rows keep what they had
     }
@@ -2929,7 +2896,7 @@ int vn_set_bic_adapt(vn_engine* h, int32_t part, int32_t rule, const double par[
     return fail(VN_ESTATE, "vn_set_bic_adapt: the %s part has no rows (nB = %ld, bDof = %ld%s)", kBicPart[part], h->nB, h->bDof,
                 h->cfg.time_dependent ? "" : ", a steady engine has no initial rows");
   Adapt* ad = nullptr;
-  if (int rc = bicw_make(h, "vn_set_bic_adapt", part, rule, par, (int)par[5], (int)par[7], (long)par[8], lambda_init_dev, (float)par[6], &ad))
+  if (int rc = adapt_make(h, "vn_set_bic_adapt", kBicRows[part], kBicLambdas[part], bicw_count(h, part), rule, par, lambda_init_dev, &ad))
     return rc;
   adapt_free(h->bw[part]);                           // replaces a static or an earlier adaptive registration of this part
   h->bw[part] = ad;
@@ -2950,20 +2917,9 @@ int vn_get_bic_adapt(vn_engine* h, int32_t part, float* lambda_host, float* omeg
                      double stats[6]) {
   Adapt* ad = nullptr;
   if (int rc = bicw_of(h, part, "vn_get_bic_adapt", &ad)) return rc;
-  const VnAdaptState s = adapt_state(*ad, ad->cur);
-  if (slots_host && !s.m1) return fail(VN_EINVAL, "vn_get_bic_adapt: the %s part runs no sa rule, so it has no slots", kBicPart[part]);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const size_t nk = (size_t)ad->n_k * sizeof(float);
-  if (lambda_host) HIPCHK(hipMemcpyAsync(lambda_host, s.lambda, nk, hipMemcpyDeviceToHost, h->stream));
-  if (omega_host) HIPCHK(hipMemcpyAsync(omega_host, s.omega, nk, hipMemcpyDeviceToHost, h->stream));
-  if (slots_host) {
-    HIPCHK(hipMemcpyAsync(slots_host, s.m1, nk, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(slots_host + ad->n_k, s.m2, nk, hipMemcpyDeviceToHost, h->stream));
-  }
-  if (lossfield_host) HIPCHK(hipMemcpyAsync(lossfield_host, bicw_field(h, part), nk, hipMemcpyDeviceToHost, h->stream));
-  if (stats) HIPCHK(hipMemcpyAsync(stats, s.scal, 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return VN_OK;
+  if (slots_host && ad->rule != VN_ADAPT_SA)
+    return fail(VN_EINVAL, "vn_get_bic_adapt: the %s part runs no sa rule, so it has no slots", kBicPart[part]);
+  return adapt_get(h, *ad, lambda_host, omega_host, slots_host, bicw_field(h, part), lossfield_host, stats);
 }
 
 int vn_set_bic_adapt_state(vn_engine* h, int32_t part, const float* lambda_host, const float* slots_host, int64_t tau) {
@@ -2972,30 +2928,7 @@ int vn_set_bic_adapt_state(vn_engine* h, int32_t part, const float* lambda_host,
   if (ad->rule == VN_ADAPT_NONE)
     return fail(VN_ESTATE, "vn_set_bic_adapt_state: the %s part holds static weights (vn_set_bic_weights), which have no state to set",
                 kBicPart[part]);
-  if (!lambda_host) return fail(VN_EINVAL, "vn_set_bic_adapt_state: null lambda");
-  if (tau < 0) return fail(VN_EINVAL, "vn_set_bic_adapt_state: tau = %lld must be >= 0", (long long)tau);
-  if (slots_host && ad->rule != VN_ADAPT_SA)
-    return fail(VN_EINVAL, "vn_set_bic_adapt_state: the %s part runs the rba rule, which has no slots", kBicPart[part]);
-  for (long k = 0; k < ad->n_k; ++k)
-    if (!(lambda_host[k] >= 0.f && std::isfinite(lambda_host[k])))
-      return fail(VN_EINVAL, "vn_set_bic_adapt_state: lambda[%ld] = %g is negative or not finite", k, (double)lambda_host[k]);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const VnAdaptState s = adapt_state(*ad, ad->cur);
-  const size_t nk = (size_t)ad->n_k * sizeof(float);
-  double scal[VN_ADAPT_SCAL] = {};
-  scal[5] = (double)tau;
-  HIPCHK(hipMemcpyAsync(s.lambda, lambda_host, nk, hipMemcpyHostToDevice, h->stream));
-  if (s.m1) {                   // NULL slots: zeros
-    if (slots_host) {
-      HIPCHK(hipMemcpyAsync(s.m1, slots_host, nk, hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(s.m2, slots_host + ad->n_k, nk, hipMemcpyHostToDevice, h->stream));
-    } else {
-      HIPCHK(hipMemsetAsync(s.m1, 0, 2 * (size_t)ad->stride * sizeof(float), h->stream));
-    }
-  }
-  HIPCHK(hipMemcpyAsync(s.scal, scal, sizeof scal, hipMemcpyHostToDevice, h->stream));
-  if (int rc = adapt_rebuild(h, *ad)) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));   // the host arrays may be released on return
+  if (int rc = adapt_put(h, *ad, "vn_set_bic_adapt_state", kBicThePart[part], lambda_host, slots_host, tau)) return rc;
   lbfgs_invalidate(h);
   return VN_OK;
 }

@@ -998,6 +998,45 @@ class VNEngine:
         return np.array(out, dtype=np.float64)
 
     # -- self-adaptive test-function weights -------------------------------------------------
+    # What the adaptive states of the batches and of the BC/IC rows' parts share: `n` is the holder's count (None: not known here,
+    # the engine checks), `key` its batch or part index.
+    def _adapt_lambda_init(self, lambda_init, n, exc, text):
+        """lambda_init as a flat float32 device tensor (one that already is one is handed through, no copy), or None; `exc(text %
+        (its length, n))` when the length is not n."""
+        if lambda_init is None:
+            return None
+        lam = self.dev(lambda_init.reshape(-1) if isinstance(lambda_init, self.torch.Tensor) else np.reshape(lambda_init, -1))
+        if n is not None and lam.numel() != n:
+            raise exc(text % (lam.numel(), n))
+        return lam
+
+    def _adapt_read(self, get, key, n, spec, arrays, extra=()):
+        """The dict of tf_adapt / bic_adapt around one get call: 'lambda', 'omega', 'slots' (sa, else None), the `extra` [n]
+        arrays behind them, 'stats'."""
+        names = ('lambda', 'omega', 'slots') + extra
+        st = (C.c_double * 6)()
+        out = dict.fromkeys(names)
+        if arrays:
+            for k in names:
+                if k != 'slots':
+                    out[k] = np.empty(n, np.float32)
+            if isinstance(spec, dict) and spec['rule'] == 'sa':
+                out['slots'] = np.empty((2, n), np.float32)
+        self._ck(get(self.h, key, *[None if out[k] is None else out[k].ctypes.data for k in names], st))
+        out['stats'] = dict(zip(('min', 'max', 'mean', 'share', 'Z', 'tau'), [float(x) for x in st]))
+        return out
+
+    def _adapt_write(self, put, key, who, n, lam, slots, tau):
+        """lam [n] and slots [2, n] (or None) as flat float32 host arrays of checked length around one put call."""
+        lam = np.ascontiguousarray(lam, dtype=np.float32).ravel()
+        if n is not None and lam.size != n:
+            raise ValueError('%s: expected %d lambdas, got %d' % (who, n, lam.size))
+        if slots is not None:
+            slots = np.ascontiguousarray(slots, dtype=np.float32).ravel()
+            if slots.size != 2 * lam.size:
+                raise ValueError('%s: expected %d slot values, got %d' % (who, 2 * lam.size, slots.size))
+        self._ck(put(self.h, key, lam.ctypes.data, None if slots is None else slots.ctypes.data, int(tau)))
+
     def set_tf_adapt(self, batch, spec=None, lambda_init=None):
         """Register (or, with spec=None, clear) self-adaptive weights of `batch` (vn_set_tf_adapt), after set_interior of that
         batch.  spec: 'rba', 'sa' or a dict (tf_adapt_spec).  lambda_init: one value >= 0 per test function (a device tensor of
@@ -1008,16 +1047,8 @@ class VNEngine:
             self._ck(self.lib.vn_set_tf_adapt(self.h, int(batch), 0, None, None))
             self._keep.pop(('adapt', batch), None)
             return
-        t = self.torch
-        lam = None
-        if lambda_init is not None:
-            if isinstance(lambda_init, t.Tensor) and lambda_init.device == self.device and lambda_init.dtype == t.float32 \
-                    and lambda_init.is_contiguous():
-                lam = lambda_init.reshape(-1)
-            else:
-                lam = self.dev(lambda_init.reshape(-1) if isinstance(lambda_init, t.Tensor) else np.reshape(lambda_init, -1))
-            n_k = self._n_k(batch)
-            assert n_k is None or lam.numel() == n_k, 'lambda_init must have one entry per test function (%s != %s)' % (lam.numel(), n_k)
+        lam = self._adapt_lambda_init(lambda_init, self._n_k(batch), AssertionError,
+                                      'lambda_init must have one entry per test function (%s != %s)')
         rule, par = tf_adapt_par(spec)
         self._ck(self.lib.vn_set_tf_adapt(self.h, int(batch), rule, (C.c_double * 10)(*par), _ptr(lam)))
         self._keep[('adapt', batch)] = spec                              # (the engine copied the initial values)
@@ -1032,32 +1063,13 @@ class VNEngine:
         """The committed adaptive state of `batch` (vn_get_tf_adapt): {'lambda', 'omega' [n_k] float32, 'slots' [2, n_k] (sa) or
         None, 'stats': {'min', 'max', 'mean', 'share', 'Z', 'tau'}}; arrays=False reads the statistics alone.  Synchronises;
         changes no engine state."""
-        n_k = self._n_k(batch) or 0
         spec = self._keep.get(('adapt', batch))
-        st = (C.c_double * 6)()
-        out = {'lambda': None, 'omega': None, 'slots': None}
-        if arrays:
-            out['lambda'], out['omega'] = np.empty(n_k, np.float32), np.empty(n_k, np.float32)
-            if spec is not None and spec['rule'] == 'sa':
-                out['slots'] = np.empty((2, n_k), np.float32)
-        self._ck(self.lib.vn_get_tf_adapt(self.h, int(batch), *[None if out[k] is None else out[k].ctypes.data
-                                                                 for k in ('lambda', 'omega', 'slots')], st))
-        out['stats'] = dict(zip(('min', 'max', 'mean', 'share', 'Z', 'tau'), [float(x) for x in st]))
-        return out
+        return self._adapt_read(self.lib.vn_get_tf_adapt, int(batch), self._n_k(batch) or 0, spec, arrays)
 
     def set_tf_adapt_state(self, batch, lam, slots=None, tau=0):
         """Puts an adaptive state back (vn_set_tf_adapt_state): lambda [n_k], slots [2, n_k] (sa; None: zeros), tau.  omega, Z and
         the statistics are rebuilt on the device.  Synchronises."""
-        n_k = self._n_k(batch)
-        lam = np.ascontiguousarray(lam, dtype=np.float32).ravel()
-        if n_k is not None and lam.size != n_k:
-            raise ValueError('set_tf_adapt_state: expected %d lambdas, got %d' % (n_k, lam.size))
-        if slots is not None:
-            slots = np.ascontiguousarray(slots, dtype=np.float32).ravel()
-            if slots.size != 2 * lam.size:
-                raise ValueError('set_tf_adapt_state: expected %d slot values, got %d' % (2 * lam.size, slots.size))
-        self._ck(self.lib.vn_set_tf_adapt_state(self.h, int(batch), lam.ctypes.data, None if slots is None else slots.ctypes.data,
-                                                int(tau)))
+        self._adapt_write(self.lib.vn_set_tf_adapt_state, int(batch), 'set_tf_adapt_state', self._n_k(batch), lam, slots, tau)
 
     # -- weights on the BC/IC rows -------------------------------------------------------------
     BIC_PARTS = {'bc': 0, 'ic': 1}
@@ -1103,13 +1115,8 @@ class VNEngine:
             self._ck(self.lib.vn_set_bic_adapt(self.h, s, 0, None, None))
             kept.pop(name, None)
         else:
-            lam = None
-            if lambda_init is not None:
-                t = self.torch
-                lam = self.dev(lambda_init.reshape(-1) if isinstance(lambda_init, t.Tensor) else np.reshape(lambda_init, -1))
-                if lam.numel() != self.bic_rows(s):
-                    raise ValueError('set_bic_adapt: lambda_init must have one entry per %s row (%d != %d)'
-                                     % (name, lam.numel(), self.bic_rows(s)))
+            lam = self._adapt_lambda_init(lambda_init, self.bic_rows(s), ValueError,
+                                          'set_bic_adapt: lambda_init must have one entry per ' + name + ' row (%d != %d)')
             rule, par = tf_adapt_par(spec)
             self._ck(self.lib.vn_set_bic_adapt(self.h, s, rule, (C.c_double * 10)(*par), _ptr(lam)))
             kept[name] = spec                                             # (the engine copied the initial values)
@@ -1123,32 +1130,14 @@ class VNEngine:
         unweighted l_i of the last evaluation), 'slots' [2, n_s] (sa) or None, 'stats': {'min', 'max', 'mean', 'share', 'Z',
         'tau'}}; arrays=False reads the statistics alone.  Synchronises; changes no engine state."""
         s = self._bic_part(part)
-        n = self.bic_rows(s)
         spec = (self._keep.get('bicw') or {}).get(('bc', 'ic')[s])
-        st = (C.c_double * 6)()
-        out = {'lambda': None, 'omega': None, 'slots': None, 'lossfield': None}
-        if arrays:
-            for k in ('lambda', 'omega', 'lossfield'):
-                out[k] = np.empty(n, np.float32)
-            if isinstance(spec, dict) and spec['rule'] == 'sa':
-                out['slots'] = np.empty((2, n), np.float32)
-        self._ck(self.lib.vn_get_bic_adapt(self.h, s, *[None if out[k] is None else out[k].ctypes.data
-                                                        for k in ('lambda', 'omega', 'slots', 'lossfield')], st))
-        out['stats'] = dict(zip(('min', 'max', 'mean', 'share', 'Z', 'tau'), [float(x) for x in st]))
-        return out
+        return self._adapt_read(self.lib.vn_get_bic_adapt, s, self.bic_rows(s), spec, arrays, ('lossfield',))
 
     def set_bic_adapt_state(self, part, lam, slots=None, tau=0):
         """Puts the state of an adaptive part back (vn_set_bic_adapt_state): lambda [n_s], slots [2, n_s] (sa; None: zeros), tau.
         omega, Z and the statistics are rebuilt on the device.  Synchronises."""
         s = self._bic_part(part)
-        lam = np.ascontiguousarray(lam, dtype=np.float32).ravel()
-        if lam.size != self.bic_rows(s):
-            raise ValueError('set_bic_adapt_state: expected %d lambdas, got %d' % (self.bic_rows(s), lam.size))
-        if slots is not None:
-            slots = np.ascontiguousarray(slots, dtype=np.float32).ravel()
-            if slots.size != 2 * lam.size:
-                raise ValueError('set_bic_adapt_state: expected %d slot values, got %d' % (2 * lam.size, slots.size))
-        self._ck(self.lib.vn_set_bic_adapt_state(self.h, s, lam.ctypes.data, None if slots is None else slots.ctypes.data, int(tau)))
+        self._adapt_write(self.lib.vn_set_bic_adapt_state, s, 'set_bic_adapt_state', self.bic_rows(s), lam, slots, tau)
 
     # -- learnt weight scales --------------------------------------------------------------
     def set_reparam(self, mode=None, per='neuron', n=1.0, s_init=None, lr=None):

@@ -572,6 +572,25 @@ class TrainResult:
 
 
 # ======================================================================================
+# An adaptive weight state on the host, whoever holds it (a batch, or a part of the boundary and initial rows), is the arrays a
+# checkpoint keeps of it under a key prefix: <prefix>lambda, <prefix>tau and, for the sa rule, <prefix>slots.
+def _adapt_arrays(states):
+    """{prefix: a state as engine.tf_adapt / engine.bic_adapt read it} -> those arrays, in one dict."""
+    out = {}
+    for prefix, st in states.items():
+        out[prefix + 'lambda'], out[prefix + 'tau'] = st['lambda'], np.int64(st['stats']['tau'])
+        if st['slots'] is not None:
+            out[prefix + 'slots'] = st['slots']
+    return out
+
+
+def _adapt_put_back(arrays, prefix, put, key, n):
+    """... and back into the registration of `key` with n weights (put: engine.set_*_adapt_state), if `arrays` has that many."""
+    if arrays and prefix + 'lambda' in arrays and np.size(arrays[prefix + 'lambda']) == n:
+        put(key, arrays[prefix + 'lambda'], arrays.get(prefix + 'slots'), int(arrays[prefix + 'tau']))
+
+
+# ======================================================================================
 class ManageTrainData:
     """
     Device-resident training set, sharded and batched the way the reference's feed dicts are
@@ -630,7 +649,7 @@ class ManageTrainData:
             owner = getattr(self.vn, '_adapt_owner', None)
             if owner is not None:
                 own = {owner.engine_batch(mb, bi) for mb in range(len(owner.mor)) for bi in range(owner.batchNum)}
-                owner._adapt_saved = {b: eng.tf_adapt(b) for b in eng.adapt_batches() if b in own}
+                owner._adapt_saved = _adapt_arrays({'%d_' % b: eng.tf_adapt(b) for b in eng.adapt_batches() if b in own})
         if self.shuffled:                         # one upload of the permutation per shuffle, not one per block
             perm_dev = self._upload_perm(torch, eng.device)
             rows_all = (perm_dev[:, None] * q + torch.arange(q, device=eng.device)[None, :]).reshape(-1)
@@ -671,9 +690,7 @@ class ManageTrainData:
                 if adapt is not None and n1 > n0:                    # self-adaptive weights (vn_set_tf_adapt), state carried
                     b = self.engine_batch(mb, bi)
                     eng.set_tf_adapt(b, adapt)
-                    kept = (getattr(self, '_adapt_saved', None) or {}).get(b)
-                    if kept is not None and kept['lambda'].size == n1 - n0:
-                        eng.set_tf_adapt_state(b, kept['lambda'], kept['slots'], int(kept['stats']['tau']))
+                    _adapt_put_back(getattr(self, '_adapt_saved', None), '%d_' % b, eng.set_tf_adapt_state, b, n1 - n0)
                 perm = getattr(self, 'biPerm', {}).get(bi)
                 if perm is not None and hasattr(eng, 'set_batch_bic'):
                     ix = torch.as_tensor(perm, device=eng.device, dtype=torch.long)
@@ -1981,7 +1998,7 @@ class VarNet:
         if owner is None or (self.bicAdapt is None and self.bicWeights is None):
             return
         parts = self.engine.bic_parts()
-        owner._bicw_saved = {p: self.engine.bic_adapt(p) for p, v in parts.items() if isinstance(v, dict)}
+        owner._bicw_saved = _adapt_arrays({p + '_': self.engine.bic_adapt(p) for p, v in parts.items() if isinstance(v, dict)})
         self._bicw_owner = None
 
     def _bic_static_rows(self, X, nbc):
@@ -2026,14 +2043,11 @@ class VarNet:
             if not self.PDE.timeDependent:
                 om = om[:nbc]
             eng.set_bic_weights(om.astype(np.float32), normalize=self.bicWeights['normalize'])
-        kept = getattr(tData, '_bicw_saved', None) or {}
         for part, spec in (self.bicAdapt or {}).items():
             if eng.bic_rows(part) <= 0:
                 continue
             eng.set_bic_adapt(part, spec)
-            st = kept.get(part)
-            if st is not None and st['lambda'].size == eng.bic_rows(part):
-                eng.set_bic_adapt_state(part, st['lambda'], st['slots'], int(st['stats']['tau']))
+            _adapt_put_back(getattr(tData, '_bicw_saved', None), part + '_', eng.set_bic_adapt_state, part, eng.bic_rows(part))
         self._bicw_owner = tData
 
     def setBicAdapt(self, bicAdapt=None, bicWeights=None):
@@ -3100,12 +3114,9 @@ class VarNet:
             suppFactor = 1.0
         eng, fd = self.engine, self.fixData
         torch = eng.torch
-        self._adapt_owner = None                             # the adaptive state of an earlier train() call is not carried over ...
-        self._bicw_owner = None                              # ... nor that of the boundary and initial rows
+        self._adapt_owner = self._bicw_owner = None          # the adaptive states of an earlier train() call are not carried over
         if getattr(self, 'tData', None) is not None:
-            self.tData._bicw_saved = None
-        if getattr(self, 'tData', None) is not None:
-            self.tData._adapt_saved = None
+            self.tData._bicw_saved = self.tData._adapt_saved = None
         tData = self._build_tdata(batchNum, batchLen)        # first set is always uniform (VarNet.py:1300)
         trainRes = TrainResult(folderpath if self.rank == 0 else None, fd.cEx is not None, verbose, saveFreq, pltReplace)
         trainRes.initializeCase(self, argDict)
@@ -3421,22 +3432,13 @@ class VarNet:
             batches = self.engine.adapt_batches()
             out['tfadapt_rule'] = np.array(self.tfAdapt['rule'])
             out['tfadapt_batches'] = np.array(batches, dtype=np.int64)
-            for b in batches:
-                st = self.engine.tf_adapt(b)
-                out['tfadapt_%d_lambda' % b] = st['lambda']
-                out['tfadapt_%d_tau' % b] = np.int64(st['stats']['tau'])
-                if st['slots'] is not None:
-                    out['tfadapt_%d_slots' % b] = st['slots']
+            out.update(_adapt_arrays({'tfadapt_%d_' % b: self.engine.tf_adapt(b) for b in batches}))
         if getattr(self, 'bicAdapt', None) is not None:
             for part, spec in self.engine.bic_parts().items():
                 if not isinstance(spec, dict):
                     continue
-                st = self.engine.bic_adapt(part)
                 out['bicadapt_%s_rule' % part] = np.array(spec['rule'])
-                out['bicadapt_%s_lambda' % part] = st['lambda']
-                out['bicadapt_%s_tau' % part] = np.int64(st['stats']['tau'])
-                if st['slots'] is not None:
-                    out['bicadapt_%s_slots' % part] = st['slots']
+                out.update(_adapt_arrays({'bicadapt_%s_' % part: self.engine.bic_adapt(part)}))
         return out
 
     def restore_arrays(self, arrays):
@@ -3478,14 +3480,12 @@ class VarNet:
         self.engine.import_state(blob)
         if rule is not None and saved_rule == rule:
             for b in [int(x) for x in arrays['tfadapt_batches']]:
-                if b in self.engine.adapt_batches() and np.size(arrays['tfadapt_%d_lambda' % b]) == self.engine._n_k(b):
-                    self.engine.set_tf_adapt_state(b, arrays['tfadapt_%d_lambda' % b], arrays.get('tfadapt_%d_slots' % b),
-                                                   int(arrays['tfadapt_%d_tau' % b]))
+                if b in self.engine.adapt_batches():
+                    _adapt_put_back(arrays, 'tfadapt_%d_' % b, self.engine.set_tf_adapt_state, b, self.engine._n_k(b))
         for part, spec in bic_parts.items():
             key = 'bicadapt_%s_' % part
-            if isinstance(spec, dict) and key + 'rule' in arrays and str(arrays[key + 'rule']) == spec['rule'] \
-                    and np.size(arrays[key + 'lambda']) == self.engine.bic_rows(part):
-                self.engine.set_bic_adapt_state(part, arrays[key + 'lambda'], arrays.get(key + 'slots'), int(arrays[key + 'tau']))
+            if isinstance(spec, dict) and key + 'rule' in arrays and str(arrays[key + 'rule']) == spec['rule']:
+                _adapt_put_back(arrays, key, self.engine.set_bic_adapt_state, part, self.engine.bic_rows(part))
         if mode is not None:
             self.engine.set_reparam_state(arrays['reparam_V'], arrays['reparam_s'], arrays['reparam_slots'])
         for lv in self.LEARNT:
